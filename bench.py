@@ -24,6 +24,8 @@ value = field megabytes (10^6 B) round-tripped per second, whole job (all ranks)
   python bench.py [--gpus N] [--steps K] [--warmup W] [--size 1024] [--tols 1e-3,1e-7] [--batch 12] [--jobs 12] [--pool -1]
                   [--resident]   (fields start and end in HBM instead: the round-1 measurement)
                   [--pool 0 --threads 1]   (no coder pool: every call codes its planes on its own thread)
+                  [--dump-outputs DIR]   (what the last timed step returned for every tolerance -- header, coded bytes,
+                                          reconstruction -- as DIR/*.npy: two builds compared output for output)
 
 N > 1: one process per GPU (torch.distributed / RCCL for the timing barrier only); every rank
 codes its own independent field (seed 12345 + rank): weak scaling, no data-path collective.  Either a
@@ -42,7 +44,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+HBM_PEAK_GBS = 8000.0  # MI355X: HBM3E 8 TB/s spec
 
 
 def box_elems(n, levels=4):
@@ -128,6 +130,56 @@ def parity_vs_pins(n, seed, coded, decoded):
             out["decoded_sha_ok"] = sha_big(arr) == rec["decoded_sha256"]
             out["checked"].append("reconstruction %d^3 tol %g" % (n, tol))
     return out
+
+
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs writes at most this much in all
+DUMP_BLOCK = 4096          # elements per sampled block: contiguous runs are cheap to gather and keep local errors visible
+
+
+def sample_blocks(n, want, seed):
+    """First elements of the blocks of a fixed, seeded sample of about `want` of n elements, and the block length
+    (all n elements when they fit: one block at 0)."""
+    import numpy as np
+    if n <= want:
+        return np.zeros(1, dtype=np.int64), n
+    starts = np.random.default_rng(seed).choice(n // DUMP_BLOCK, max(1, want // DUMP_BLOCK), replace=False)
+    return np.sort(starts).astype(np.int64) * DUMP_BLOCK, DUMP_BLOCK
+
+
+def dump_share(ntols):
+    """bytes of DUMP_BYTES for the outputs of one tolerance, half for the reconstruction, half for the coded bytes (1 MB is
+    left for the headers and block lists)"""
+    return (DUMP_BYTES - (1 << 20)) // ntols
+
+
+def write_dump(dirname, tols, coded, decoded, dec_starts):
+    """--dump-outputs: what the timed path handed its caller for the last field of every tolerance -- the encoder's header
+    and coded bytes, the decoder's reconstruction -- as DIR/tol<tol>_<name>.npy, float64 (the coded bytes as float32).  An
+    output larger than its share of DUMP_BYTES is a fixed, seeded sample in blocks; <name>_blocks.npy holds the blocks'
+    first elements."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    files = {}
+    for k, tol in enumerate(tols):
+        if tol not in coded or tol not in decoded:
+            raise RuntimeError("bench.py --dump-outputs: the last step left no output for tol %g" % tol)
+        enc = coded[tol]
+        pre = "tol%g_" % tol
+        files[pre + "header"] = np.array([enc["tolabs"], enc["midval"], enc["halfspanval"], enc["wlev"], enc["nlay"], enc["ntot_enc"]],
+                                         dtype=np.float64)
+        for key in ("deps_vec", "minval_vec", "len_enc_vec"):
+            files[pre + key] = np.array(enc[key], dtype=np.float64)
+        data = np.asarray(enc["data"]).reshape(-1)[:int(enc["ntot_enc"])]
+        starts, blk = sample_blocks(data.size, dump_share(len(tols)) // 2 // 4, 1 + k)
+        files[pre + "coded"] = np.concatenate([data[s:s + blk] for s in starts]).astype(np.float32)
+        files[pre + "coded_blocks"] = starts.astype(np.float64)
+        files[pre + "decoded"] = decoded[tol]
+        files[pre + "decoded_blocks"] = dec_starts.astype(np.float64)
+    total = sum(a.nbytes for a in files.values())
+    if total > DUMP_BYTES:
+        raise RuntimeError("bench.py --dump-outputs: %d bytes exceed the %d allowed" % (total, DUMP_BYTES))
+    for name, a in files.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def committed_kernel_stats():
@@ -576,7 +628,12 @@ def main():
     ap.add_argument("--secondary-steps", type=int, default=2, help="steps of the secondary pass at --secondary-tol after the timed region (N = 1 only; 0: none)")
     ap.add_argument("--secondary-tol", type=float, default=1e-16, help="BASELINE configs[4]'s near-lossless tolerance: 8 planes per field, mostly noise")
     ap.add_argument("--secondary-lanes", type=int, default=8, help="fields in flight in the secondary pass (each holds up to 2 x 6 GB of coded bytes at 1024^3)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step returned for every tolerance (header, coded bytes, reconstruction; a fixed "
+                         "sample where larger than 64 MB in all) as DIR/*.npy, rank 0 only, to compare two builds output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     tols = [float(t) for t in args.tols.split(",")]
     n = args.size
     host_mode = not args.resident
@@ -780,6 +837,19 @@ def main():
         return diff / amax
 
     main_capture = {"coded": {}, "decoded": []}
+    dump_starts = None
+    if args.dump_outputs and rank == 0:
+        # the reconstruction of the last field of every tolerance is sampled where it is decoded (its output buffer goes back
+        # to the lanes); the coded bytes are held back for the parity check anyway
+        dump_starts, dump_blk = sample_blocks(nelem, dump_share(len(tols)) // 2 // 8, 0)
+        main_capture["samples"] = {}
+
+    def dump_sample(out=None, dev=None):  # the reconstruction's sample from a host array or a device buffer
+        if out is not None:
+            flat = out.reshape(-1)
+            return np.concatenate([flat[s:s + dump_blk] for s in dump_starts])
+        return np.concatenate([dev.download(np.float64, dump_blk, 8 * int(s)) for s in dump_starts])
+
     import ctypes
     libc = ctypes.CDLL(None, use_errno=True)
     libc.madvise.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
@@ -873,6 +943,8 @@ def main():
                             keep = False
                             try:
                                 td = ln["dec"].decode_finish_host(out)  # kernels, download: ~0.25 s
+                                if held_back and "samples" in capture:
+                                    capture["samples"][tol] = dump_sample(out=out)
                                 if capture is not None and i == total - 1:
                                     capture["decoded"].append((tol, out))  # held back: accuracy and parity are taken after the timed region
                                     keep = True
@@ -881,6 +953,8 @@ def main():
                                     out_pool.put(out)
                         else:
                             td = ln["dec"].decode(ln["rec"], shape, enc)
+                            if held_back and "samples" in capture:
+                                capture["samples"][tol] = dump_sample(dev=ln["rec"])
                             if record and i == total - 1:
                                 diff, amax = ln["dec"].linf(orig, ln["rec"], nelem)
                                 accuracy["linf_rel"] = diff / amax
@@ -1016,6 +1090,8 @@ def main():
         cap["decoded"][:] = []
         return res
 
+    if dump_starts is not None:  # before check_capture hands the held-back coded streams back
+        write_dump(args.dump_outputs, tols, {t: e for t, (e, _) in main_capture["coded"].items()}, main_capture["samples"], dump_starts)
     # EVERY rank checks what it coded in the timed region against the reference's pins for its own field (seed 12345 + rank)
     main_check = check_capture(main_capture)
     parity = main_check["parity"]

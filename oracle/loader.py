@@ -12,6 +12,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_SO = os.path.join(HERE, "libwr_oracle.so")
+ORACLE_ABI_SO = os.path.join(HERE, "libwr_oracle_abi.so")  # the oracle under the drop-in ABI names (wr_oracle_abi.c)
 REF_SO = os.path.join(HERE, "_ref", "libwaverange_ref.so")
 REF_WRENC = os.path.join(HERE, "_ref", "wrenc_ref")
 REF_WRDEC = os.path.join(HERE, "_ref", "wrdec_ref")

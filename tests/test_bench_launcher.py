@@ -153,3 +153,34 @@ def test_every_rank_gets_the_ipc_mode_and_the_fault_log():
     assert r.returncode == 0, r.stderr
     line = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")][0]
     assert line["environment"] == {"HSA_ENABLE_IPC_MODE_LEGACY": "0", "WR_FAULT_LOG": "1"}
+
+
+def test_dump_outputs_are_a_seeded_sample_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: outputs larger than their share are sampled in blocks chosen by a fixed seed, the files are
+    float32 / float64 and stay within 64 MB in all; --steps below 1 is refused."""
+    import numpy as np
+    bench = _bench_module()
+    n = 1024 ** 3
+    starts, blk = bench.sample_blocks(n, 10 ** 6, 0)
+    assert np.array_equal(starts, bench.sample_blocks(n, 10 ** 6, 0)[0]) and blk == bench.DUMP_BLOCK
+    assert starts.size * blk <= 10 ** 6 and np.all(np.diff(starts) >= blk) and starts[-1] + blk <= n
+    assert bench.sample_blocks(1000, 10 ** 6, 0)[0].tolist() == [0] and bench.sample_blocks(1000, 10 ** 6, 0)[1] == 1000
+    tols = [1e-3, 1e-7]
+    dec_starts, dec_blk = bench.sample_blocks(n, bench.dump_share(len(tols)) // 2 // 8, 0)
+    data = (np.arange(80 * 10 ** 6) % 251).astype(np.uint8)
+    coded = {t: dict(tolabs=t, midval=0.5, halfspanval=2.0, wlev=4, nlay=2, ntot_enc=data.size - 10, deps_vec=np.array([0.1, 0.2]),
+                     minval_vec=np.array([-1.0, -2.0]), len_enc_vec=[data.size - 100, 90], data=data) for t in tols}
+    decoded = {t: np.full(dec_starts.size * dec_blk, t) for t in tols}
+    bench.write_dump(str(tmp_path), tols, coded, decoded, dec_starts)
+    files = {f[:-len(".npy")]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    assert sum(a.nbytes for a in files.values()) <= 64 * 10 ** 6
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    for t in tols:
+        p = "tol%g_" % t
+        assert files[p + "header"].tolist() == [t, 0.5, 2.0, 4, 2, data.size - 10] and files[p + "len_enc_vec"].tolist() == [data.size - 100, 90]
+        cs = files[p + "coded_blocks"].astype(np.int64)
+        assert cs[-1] + bench.DUMP_BLOCK <= data.size - 10
+        assert np.array_equal(files[p + "coded"], np.concatenate([data[s:s + bench.DUMP_BLOCK] for s in cs]).astype(np.float32))
+        assert np.array_equal(files[p + "decoded"], decoded[t]) and np.array_equal(files[p + "decoded_blocks"], dec_starts)
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0"], env=_clean_env(), capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr

@@ -1,8 +1,9 @@
 """Generic CLI (wrenc / wrdec) parity: .wrh text, .wrb bytes and the decoded file against the
 golden vectors produced by the compiled reference CLI (tools/make_golden_cli.py).
 
-  * CPU: OUR CLI sources linked against the REFERENCE codec (oracle/_ref/*_ours_refcodec) --
-    proves the file formats, the three parameter modes and the C-ABI call compatibility.
+  * CPU: OUR CLI sources linked against the REFERENCE codec (oracle/_ref/libwaverange_ref.so; where it is not built,
+    the oracle under the same ABI, oracle/libwr_oracle_abi.so) -- proves the file formats, the three parameter modes and
+    the C-ABI call compatibility.
   * GPU: OUR CLI on OUR library (waverange_amd/bin), and the REFERENCE's compiled CLI running
     on OUR library under the reference's library name (oracle/_ref/*_ref_dyn) -- the drop-in.
 """
@@ -15,7 +16,7 @@ import tempfile
 import pytest
 
 import cli_cases
-from util import GOLDEN, ROOT
+from util import GOLDEN, ROOT, build_cli, codec_library
 
 REFDIR = os.path.join(ROOT, "oracle", "_ref")
 BINDIR = os.path.join(ROOT, "waverange_amd", "bin")
@@ -47,12 +48,16 @@ def run_case(case, wrenc, wrdec, g, **extra_env):
         assert sha_file(os.path.join(d, "datarec.bin")) == g["rec_sha256"], "decoded file differs"
 
 
+@pytest.fixture(scope="module")
+def cli_on_cpu_codec(tmp_path_factory):
+    d = str(tmp_path_factory.mktemp("cli"))
+    so = codec_library()
+    return build_cli("wrenc", so, d), build_cli("wrdec", so, d)
+
+
 @pytest.mark.parametrize("case", sorted(cli_cases.CASES))
-def test_our_cli_on_reference_codec(case, golden_cli):
-    enc, dec = os.path.join(REFDIR, "wrenc_ours_refcodec"), os.path.join(REFDIR, "wrdec_ours_refcodec")
-    if not (os.path.exists(enc) and os.path.exists(dec)):
-        pytest.skip("oracle/_ref cross binaries not built")
-    run_case(case, enc, dec, golden_cli[case])
+def test_our_cli_on_reference_codec(case, golden_cli, cli_on_cpu_codec):
+    run_case(case, *cli_on_cpu_codec, golden_cli[case])
 
 
 @pytest.mark.gpu

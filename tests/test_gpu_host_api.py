@@ -717,3 +717,35 @@ def test_bench_takes_the_rccl_barrier_under_a_launcher_with_one_rank(tmp_path):
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["config"]["barrier"] == "rccl", line["config"]
     assert line["value"] > 0 and line["parity"] is not None
+
+
+def test_bench_dump_outputs_are_what_the_timed_path_returned(tmp_path, oracle):
+    """bench.py --dump-outputs at a size whose outputs fit whole: runs of different lengths write the same files, and they hold
+    the header, the coded bytes and the reconstruction the oracle gives for the bench's field at every tolerance."""
+    import json
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "WR_BENCH_BACKEND"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--size", "64", "--jobs", "1", "--no-cpu-baseline", "--secondary-steps", "0",
+           "--no-warm-transforms"]
+    dumps = []
+    for steps, warmup in ((2, 1), (1, 0)):
+        d = tmp_path / ("steps%d" % steps)
+        r = subprocess.run(cmd + ["--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(d)], env=env, capture_output=True,
+                           text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == steps
+        dumps.append({f[:-len(".npy")]: np.load(str(d / f)) for f in os.listdir(str(d))})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and all(bits_equal(a[k], b[k]) for k in a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 * 10 ** 6
+    f = synth.field(64, 64, 64, seed=12345)
+    for tol in (1e-3, 1e-7):
+        p = "tol%g_" % tol
+        want = oracle.encode(f, tol)
+        assert bits_equal(a[p + "header"], [want[k] for k in ("tolabs", "midval", "halfspanval", "wlev", "nlay", "ntot_enc")])
+        assert bits_equal(a[p + "deps_vec"], want["deps_vec"]) and bits_equal(a[p + "minval_vec"], want["minval_vec"])
+        assert list(a[p + "len_enc_vec"]) == want["len_enc_vec"]
+        assert np.array_equal(a[p + "coded"], want["data"].astype(np.float32)) and list(a[p + "coded_blocks"]) == [0]
+        assert bits_equal(a[p + "decoded"], oracle.decode(want, f.shape)) and list(a[p + "decoded_blocks"]) == [0]

@@ -5,7 +5,8 @@ Golden outputs come from the REFERENCE's wrmssgenc / wrmssgdec compiled from /ro
 regular GrADS output with and without undefined points (the mask is the reference's only wtflag = 0
 caller), restart sets coded as global fields and subdomain by subdomain; parameters through arguments,
 both "inmeta" formats and stdin.  Every output file must be byte-identical:
-  * CPU: OUR front-end sources linked with the REFERENCE codec (oracle/_ref/*_mssg_ours_refcodec);
+  * CPU: OUR front-end sources linked with the REFERENCE codec (oracle/_ref/libwaverange_ref.so; where it is not built, the
+    oracle under the same ABI, oracle/libwr_oracle_abi.so);
   * GPU: our front-end on the GPU library, and the REFERENCE's front-end linked against our library."""
 import hashlib
 import json
@@ -15,7 +16,7 @@ import tempfile
 
 import pytest
 
-from util import GOLDEN, ROOT
+from util import GOLDEN, ROOT, build_cli, codec_library
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import make_golden_mssg  # noqa: E402  (run_case: drives an encoder / decoder pair over a case)
@@ -46,10 +47,16 @@ def check_case(case, enc, dec, g):
         assert hashlib.sha256(data).hexdigest() == g[name]["sha256"], name
 
 
+@pytest.fixture(scope="module")
+def mssg_on_cpu_codec(tmp_path_factory):
+    d = str(tmp_path_factory.mktemp("mssg"))
+    so = codec_library()
+    return build_cli("mssg_enc", so, d), build_cli("mssg_dec", so, d)
+
+
 @pytest.mark.parametrize("case", sorted(mssg_cases.CASES))
-def test_our_mssg_frontend_on_reference_codec(case, golden_mssg):
-    check_case(case, os.path.join(REFDIR, "wrenc_mssg_ours_refcodec"), os.path.join(REFDIR, "wrdec_mssg_ours_refcodec"),
-               golden_mssg[case])
+def test_our_mssg_frontend_on_reference_codec(case, golden_mssg, mssg_on_cpu_codec):
+    check_case(case, *mssg_on_cpu_codec, golden_mssg[case])
 
 
 @pytest.mark.gpu

@@ -1,53 +1,51 @@
-"""The CPU oracle against the reference itself (oracle/_ref, built from /root/reference by
-oracle/Makefile).  Runs where the reference build is present; CPU only."""
-import numpy as np
+"""The CPU oracle against the reference itself: against the reference's outputs stored in tests/golden/oracle_vs_ref.json
+(tools/make_golden_oracle_vs_ref.py, from oracle/_ref built by oracle/Makefile) and, where oracle/_ref is built, against
+the reference run on the same inputs.  CPU only."""
+import json
+import os
+
 import pytest
 
-from util import bits_equal
-from waverange_amd import synth
-
-SHAPES = [(64, 64, 64), (13, 9, 7), (37, 21, 13), (33, 5, 1), (2, 2, 2), (3, 3, 3), (17, 1, 1),
-          (9, 1, 40), (1, 1, 1), (1, 4, 1), (100, 3, 2)]
+import oracle_vs_ref_cases as C
+from util import GOLDEN
 
 
-@pytest.mark.parametrize("shape", SHAPES)
-def test_transform_matches_reference(oracle, reference, shape):
-    nx, ny, nz = shape
-    f = synth.field(nx, ny, nz, seed=nx * 131 + ny)
-    for lvl in (1, 2, 4):
-        a, b = oracle.cdf97_3d(f, lvl), reference.cdf97_3d(f, lvl)
-        assert bits_equal(a, b)
-        assert bits_equal(oracle.cdf97_3d(a, -lvl), reference.cdf97_3d(b, -lvl))
+@pytest.fixture(scope="module")
+def stored():
+    with open(os.path.join(GOLDEN, "oracle_vs_ref.json")) as fh:
+        return json.load(fh)
 
 
-@pytest.mark.parametrize("tol", [1e-2, 1e-3, 1e-5, 1e-7, 1e-10, 1e-16])
-@pytest.mark.parametrize("shape", [(32, 32, 32), (37, 21, 13), (60, 50, 40)])
-def test_codec_matches_reference(oracle, reference, shape, tol, capfd):
-    nx, ny, nz = shape
-    f = synth.field(nx, ny, nz, seed=99)
-    eo, er = oracle.encode(f, tol), reference.encode(f, tol)
-    for k in ("tolabs", "midval", "halfspanval", "wlev", "nlay", "ntot_enc", "len_enc_vec"):
-        assert eo[k] == er[k], k
-    assert bits_equal(eo["deps_vec"], er["deps_vec"]) and bits_equal(eo["minval_vec"], er["minval_vec"])
-    assert np.array_equal(eo["data"], er["data"])
-    assert bits_equal(eo["residual"], er["residual"])
-    assert bits_equal(oracle.decode(eo, f.shape), reference.decode(er, f.shape))
+@pytest.fixture(scope="module")
+def live_reference():
+    from oracle.loader import Reference, have_ref
+    return Reference() if have_ref() else None
 
 
-def test_wtflag0_and_local_cutoff_match_reference(oracle, reference, capfd):
-    f = synth.field(32, 16, 8, seed=5)
-    eo, er = oracle.encode(f, 1e-4, wtflag=0), reference.encode(f, 1e-4, wtflag=0)
-    assert np.array_equal(eo["data"], er["data"]) and eo["wlev"] == er["wlev"] == 0
-    cut = [1e-3, 1e-5, 1e-4, 1e-6, 1e-3, 1e-3, 1e-5, 1e-4]
-    eo = oracle.encode(f, None, cutoff=cut, m=(2, 2, 2))
-    er = reference.encode(f, None, cutoff=cut, m=(2, 2, 2))
-    assert np.array_equal(eo["data"], er["data"]) and eo["len_enc_vec"] == er["len_enc_vec"]
-    assert bits_equal(eo["deps_vec"], er["deps_vec"])
+def check(case, want, oracle, reference, *args):
+    """the oracle's outputs equal the reference's stored ones -- and the reference, where it is built, still gives them"""
+    if reference is not None:
+        assert case(reference, *args) == want, "tests/golden/oracle_vs_ref.json is not what the reference gives (tools/make_golden_oracle_vs_ref.py)"
+    assert case(oracle, *args) == want
 
 
-def test_ind_p2w_matches_reference(oracle, reference):
-    rs = np.random.RandomState(1)
-    for n1, n2, n3 in ((64, 64, 64), (13, 9, 7), (5, 1, 33), (2, 2, 2)):
-        for _ in range(100):
-            p = (int(rs.randint(n1)), int(rs.randint(n2)), int(rs.randint(n3)))
-            assert oracle.ind_p2w(4, n1, n2, n3, *p) == reference.ind_p2w(4, n1, n2, n3, *p)
+@pytest.mark.parametrize("shape", C.SHAPES)
+def test_transform_matches_reference(oracle, live_reference, stored, shape):
+    check(C.transform, stored["transform"][C.key(shape)], oracle, live_reference, shape)
+
+
+@pytest.mark.parametrize("tol", C.CODEC_TOLS)
+@pytest.mark.parametrize("shape", C.CODEC_SHAPES)
+def test_codec_matches_reference(oracle, live_reference, stored, shape, tol, capfd):
+    check(C.codec, stored["codec"][C.key(shape, tol)], oracle, live_reference, shape, tol)
+
+
+def test_wtflag0_and_local_cutoff_match_reference(oracle, live_reference, stored, capfd):
+    want = stored["wtflag0_and_local_cutoff"]
+    assert want["wtflag0"]["wlev"] == 0
+    check(C.wtflag0_and_local_cutoff, want, oracle, live_reference)
+
+
+def test_ind_p2w_matches_reference(oracle, live_reference, stored):
+    for shape in C.IND_SHAPES:
+        check(C.ind_p2w, stored["ind_p2w"][C.key(shape)], oracle, live_reference, shape)

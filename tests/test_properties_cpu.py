@@ -94,15 +94,19 @@ def test_bench_cpu_share_pinning():
     the affinity change must not leak into the test runner)."""
     import subprocess
     import sys
+    # rank 1 of 2 takes the second half of the physical cores, each with all of its allowed hardware threads (on a host
+    # without SMT: the second half of the allowed CPUs)
     code = ("import os, sys; sys.path.insert(0, %r); import bench; a = sorted(os.sched_getaffinity(0)); "
+            "sib = bench.read_cpu_topology()['siblings']; cores = sorted({tuple(sorted(x for x in sib[c] if x in a)) for c in a}); "
+            "h = len(cores) // 2; want = sorted(c for cs in cores[h:2 * h] for c in cs); "
             "n = bench.take_cpu_share(1, 2); b = sorted(os.sched_getaffinity(0)); "
-            "print(len(a), n, b == a[len(a)//2:2*(len(a)//2)] if n else b == a); "
+            "print(len(a), n, b == want if n else b == a, len(want)); "
             "print(bench.take_cpu_share(0, 1))" % ROOT)
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, check=True).stdout.split("\n")
-    total, share, ok = out[0].split()
+    total, share, ok, half = out[0].split()
     assert ok == "True"
     if int(total) >= 16:
-        assert int(share) == int(total) // 2
+        assert int(share) == int(half) and int(half) >= int(total) // 2 - 1
     else:
         assert share == "None"  # fewer than 8 CPUs per GPU: left alone
     assert out[1] == "None"  # a single visible GPU: nothing to share

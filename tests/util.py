@@ -1,6 +1,7 @@
 """Shared helpers for the parity tests."""
 import hashlib
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -100,3 +101,28 @@ def g7_field(rec):
     f = ((10.0 * sx)[None, None, :] * (sx * sx)[None, :, None]) * cz[:, None, None]
     assert sha(f) == rec["input_sha256"]
     return f
+
+
+CLI_SOURCES = {"wrenc": ["wrenc.cpp", "gen_io.cpp"], "wrdec": ["wrdec.cpp", "gen_io.cpp"],
+               "mssg_enc": ["mssg_enc.cpp", "mssg_io.cpp"], "mssg_dec": ["mssg_dec.cpp", "mssg_io.cpp"]}
+
+
+def codec_library():
+    """The codec the command-line front-ends are tested on without a GPU: the compiled reference (oracle/_ref) where it is
+    built, else the oracle under the drop-in ABI names (oracle/libwr_oracle_abi.so), which is pinned to it bit for bit."""
+    from oracle import loader
+    if loader.have_ref():
+        return loader.REF_SO
+    if not os.path.exists(loader.ORACLE_ABI_SO):
+        loader.build(ref=False)
+    return loader.ORACLE_ABI_SO
+
+
+def build_cli(name, codec_so, outdir, flags=()):
+    """One of our command-line front-ends (waverange_amd/csrc/cli) built with g++ and linked against codec_so."""
+    exe = os.path.join(outdir, name)
+    lib = os.path.basename(codec_so)[len("lib"):-len(".so")]
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off"] + list(flags)
+                          + [os.path.join(ROOT, "waverange_amd", "csrc", "cli", s) for s in CLI_SOURCES[name]]
+                          + ["-o", exe, "-L" + os.path.dirname(codec_so), "-l" + lib, "-Wl,-rpath," + os.path.dirname(codec_so)])
+    return exe
