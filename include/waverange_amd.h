@@ -306,6 +306,28 @@ int wr_decode_begin(wr_ctx *ctx, int nx, int ny, int nz, const wr_enc_info *info
                     const unsigned char *data_enc, size_t data_len, wr_timings *tm);
 int wr_decode_finish_host(wr_ctx *ctx, double *h_fld, wr_timings *tm);
 int wr_decode_finish_device(wr_ctx *ctx, double *d_fld, wr_timings *tm);
+/* The same for single-precision fields (fp32 host buffers, pinned or pageable): 4 bytes per sample cross the bus and
+ * the field is widened / narrowed on the device, inside the first / last transform kernel where the fused transform
+ * runs.  The arithmetic is the fp64 path's: the header, coded bytes and len_enc_vec are those wr_encode_host gives for
+ * the field widened to double, and the decoded field is, bit for bit, (float) of what wr_decode_host returns (round to
+ * nearest even; -0.0 and fp32 subnormals kept; inf where the reconstruction exceeds FLT_MAX).  h_fld of an encode is never
+ * written: with wr_ctx_set_keep_residual(ctx, 1) the encode returns WR_ERR_UNSUPPORTED. */
+int wr_encode_host_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my,
+                       int mz, const double *cutoffvec, wr_enc_info *info, unsigned char *data_enc,
+                       size_t cap, wr_timings *tm);
+int wr_decode_host_f32(wr_ctx *ctx, float *h_fld, int nx, int ny, int nz, const wr_enc_info *info,
+                       const unsigned char *data_enc, size_t data_len, wr_timings *tm);
+int wr_decode_finish_host_f32(wr_ctx *ctx, float *h_fld, wr_timings *tm); /* after wr_decode_begin */
+/* encoding_wrap / decoding_wrap for fp32 fields: the same arguments but the field, an implicit context per call and
+ * the reference's "void + fatal" errors.  fld_1d of an encode is never overwritten (no residual write-back). */
+void wr_encoding_wrap_f32(int nx, int ny, int nz, const float *fld_1d, int wtflag, int mx, int my, int mz,
+                          double *cutoffvec, double *tolabs, double *midval, double *halfspanval,
+                          unsigned char *wlev, unsigned char *nlay, unsigned long *ntot_enc, double *deps_vec,
+                          double *minval_vec, unsigned long *len_enc_vec, unsigned char *data_enc);
+void wr_decoding_wrap_f32(int nx, int ny, int nz, float *fld_1d, double *tolabs, double *midval,
+                          double *halfspanval, unsigned char *wlev, unsigned char *nlay,
+                          unsigned long *ntot_enc, double *deps_vec, double *minval_vec,
+                          unsigned long *len_enc_vec, unsigned char *data_enc);
 /* waveletcdf97_3d on a host array, in place */
 int wr_transform_host(wr_ctx *ctx, double *h_fld, int nx, int ny, int nz, int lvl);
 

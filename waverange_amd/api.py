@@ -110,6 +110,9 @@ def lib():
     L.wr_decode_host.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(EncInfo), _vp, C.c_size_t,
                                  C.POINTER(Timings)]
     L.wr_transform_host.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.wr_encode_host_f32.argtypes = L.wr_encode_host.argtypes
+    L.wr_decode_host_f32.argtypes = L.wr_decode_host.argtypes
+    L.wr_decode_finish_host_f32.argtypes = [_vp, _vp, C.POINTER(Timings)]
     L.wr_decode_begin.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(EncInfo), _vp, C.c_size_t, C.POINTER(Timings)]
     L.wr_decode_finish_host.argtypes = [_vp, _vp, C.POINTER(Timings)]
     L.wr_decode_finish_device.argtypes = [_vp, _vp, C.POINTER(Timings)]
@@ -592,6 +595,36 @@ class Context:
                                     C.byref(tm)))
         return tm.as_dict()
 
+    def encode_host_f32(self, fld, tolrel, wtflag=1, out=None, cutoff=None, m=(1, 1, 1)):
+        """encode_host for a C-contiguous float32 field (pinned or pageable), never written: the coded stream of the field
+        widened to float64, with 4 bytes per sample crossing the bus."""
+        if not (isinstance(fld, np.ndarray) and fld.dtype == np.float32 and fld.flags["C_CONTIGUOUS"]):
+            raise TypeError("encode_host_f32: a C-contiguous float32 array is required")
+        nz, ny, nx = fld.shape
+        _, cap = setup_wr(nx, ny, nz)
+        data = out if out is not None else np.empty(cap, dtype=np.uint8)
+        cut = np.ascontiguousarray([tolrel] if cutoff is None else cutoff, dtype=np.float64)
+        info, tm = EncInfo(), Timings()
+        _check(lib().wr_encode_host_f32(self.h, fld.ctypes.data, nx, ny, nz, wtflag, m[0], m[1], m[2],
+                                        cut.ctypes.data_as(_dp), C.byref(info), data.ctypes.data, data.size, C.byref(tm)))
+        d = info.as_dict()
+        d["data"] = data[:info.ntot_enc]
+        return d, tm.as_dict()
+
+    def decode_host_f32(self, out, enc):
+        """out: C-contiguous float32 array shaped (nz, ny, nx); receives (float) of decode_host's reconstruction."""
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"]):
+            raise TypeError("decode_host_f32: a C-contiguous float32 array is required")
+        nz, ny, nx = out.shape
+        info = EncInfo.from_dict(enc)
+        tm = Timings()
+        data = np.ascontiguousarray(enc["data"], dtype=np.uint8)
+        if data.size == 0:
+            data = np.zeros(1, dtype=np.uint8)
+        _check(lib().wr_decode_host_f32(self.h, out.ctypes.data, nx, ny, nz, C.byref(info), data.ctypes.data, data.size,
+                                        C.byref(tm)))
+        return tm.as_dict()
+
     def decode_begin(self, shape, enc):
         """Host half of a decode (range decoding into the context's staging); no output buffer needed yet."""
         nz, ny, nx = shape
@@ -608,6 +641,14 @@ class Context:
         assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"]
         tm = Timings()
         _check(lib().wr_decode_finish_host(self.h, out.ctypes.data, C.byref(tm)))
+        return tm.as_dict()
+
+    def decode_finish_host_f32(self, out):
+        """decode_finish_host into a C-contiguous float32 array."""
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"]):
+            raise TypeError("decode_finish_host_f32: a C-contiguous float32 array is required")
+        tm = Timings()
+        _check(lib().wr_decode_finish_host_f32(self.h, out.ctypes.data, C.byref(tm)))
         return tm.as_dict()
 
     def decode_finish(self, buf):

@@ -13,6 +13,16 @@
 // Weak: resolved when the tool runs on libwaverange_amd, null on the reference's library (tests/test_cli.py builds the
 // same sources against both).
 extern "C" int wr_autotune_batch(size_t field_elems, int nfields) __attribute__((weak));
+// fp32 records go to the codec as they are (no widening loop, half the bytes over the bus) where the library has the fp32
+// entry points; linked against a codec without them (the reference's libwaverange) these are null and the tools widen on
+// the host and call encoding_wrap / decoding_wrap.  WR_CLI_WIDEN_ON_HOST=1 takes that path on our library too.
+extern "C" void wr_encoding_wrap_f32(int nx, int ny, int nz, const float* fld_1d, int wtflag, int mx, int my, int mz, double* cutoffvec,
+                                     double* tolabs, double* midval, double* halfspanval, unsigned char* wlev, unsigned char* nlay,
+                                     unsigned long* ntot_enc, double* deps_vec, double* minval_vec, unsigned long* len_enc_vec,
+                                     unsigned char* data_enc) __attribute__((weak));
+extern "C" void wr_decoding_wrap_f32(int nx, int ny, int nz, float* fld_1d, double* tolabs, double* midval, double* halfspanval,
+                                     unsigned char* wlev, unsigned char* nlay, unsigned long* ntot_enc, double* deps_vec,
+                                     double* minval_vec, unsigned long* len_enc_vec, unsigned char* data_enc) __attribute__((weak));
 
 namespace wrcli {
 
@@ -80,8 +90,9 @@ private:
 };
 
 // min / max as a scan with libm fmin / fmax gives them (NaNs skipped; of equal values -- only +0 / -0 can tell --
-// the LAST one wins, glibc x86-64), four elements at a time
-inline void minmax(const double* v, size_t n, double* lo_out, double* hi_out)
+// the LAST one wins, glibc x86-64), four elements at a time (T = float: of the samples widened to double)
+template <class T>
+inline void minmax(const T* v, size_t n, double* lo_out, double* hi_out)
 {
     double lo = v[0], hi = v[0];
     size_t j = 1;
@@ -96,10 +107,10 @@ inline void minmax(const double* v, size_t n, double* lo_out, double* hi_out)
         lo = l[0]; hi = h[0];
         for (int k = 1; k < 4; k++) { lo = std::fmin(lo, l[k]); hi = std::fmax(hi, h[k]); }
     }
-    for (; j < n; j++) { lo = std::fmin(lo, v[j]); hi = std::fmax(hi, v[j]); }
+    for (; j < n; j++) { lo = std::fmin(lo, (double)v[j]); hi = std::fmax(hi, (double)v[j]); }
     if (lo == 0.0 || hi == 0.0) {  // the sign of a zero extremum: the plain scan decides
         lo = hi = v[0];
-        for (size_t k = 1; k < n; k++) { lo = std::fmin(lo, v[k]); hi = std::fmax(hi, v[k]); }
+        for (size_t k = 1; k < n; k++) { lo = std::fmin(lo, (double)v[k]); hi = std::fmax(hi, (double)v[k]); }
     }
     *lo_out = lo; *hi_out = hi;
 }

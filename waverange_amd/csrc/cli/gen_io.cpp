@@ -49,10 +49,13 @@ struct Inverted {
 
 }  // namespace
 
-void read_field(const std::string& path, int file_type, bool flip, const FieldSpec& spec, unsigned char recl[8],
-                long* pos, std::vector<double>& fld)
+// T: element type of the field array (float only for 4-byte records)
+template <class T>
+void read_field_t(const std::string& path, int file_type, bool flip, const FieldSpec& spec, unsigned char recl[8],
+                  long* pos, T* fld)
 {
     check_nbytes(spec.nbytes);
+    if (sizeof(T) < (size_t)spec.nbytes) die("internal: an 8-byte record read into a float array");
     std::ifstream in(path, std::ios::in | std::ios::binary);
     if (!in.is_open()) die("Cannot open " + path);
     in.seekg(*pos);
@@ -66,11 +69,10 @@ void read_field(const std::string& path, int file_type, bool flip, const FieldSp
     }
     const size_t n = spec.count();
     const size_t nb = (size_t)spec.nbytes;
-    // the common layout (doubles in memory order, native endianness) goes straight into the field array
-    const bool direct = spec.nbytes == 8 && !flip && !spec.idinv;
+    // the common layout (samples of the array's type in memory order, native endianness) goes straight into the field array
+    const bool direct = (size_t)spec.nbytes == sizeof(T) && !flip && !spec.idinv;
     std::unique_ptr<unsigned char[]> raw(direct ? nullptr : new unsigned char[n * nb]);
-    fld.resize(n);
-    in.read(direct ? reinterpret_cast<char*>(fld.data()) : reinterpret_cast<char*>(raw.get()), (std::streamsize)(n * nb));
+    in.read(direct ? reinterpret_cast<char*>(fld) : reinterpret_cast<char*>(raw.get()), (std::streamsize)(n * nb));
     *pos += (long)(n * nb);
     if (ml) {  // trailing marker: read and discard  gen_aux.cpp:374-383
         unsigned char m[8];
@@ -83,17 +85,19 @@ void read_field(const std::string& path, int file_type, bool flip, const FieldSp
     for (size_t k = 0; k < n; k++) {
         unsigned char* p = raw.get() + k * nb;
         if (flip) reverse_bytes(p, spec.nbytes);
-        double v;
+        T v;
         if (spec.nbytes == 4) { float f; memcpy(&f, p, 4); v = f; }
-        else memcpy(&v, p, 8);
+        else { double d; memcpy(&d, p, 8); v = (T)d; }
         fld[spec.idinv ? inv.mem_index(k) : k] = v;
     }
 }
 
-void write_field(const std::string& path, bool first, int file_type, bool flip, const FieldSpec& spec,
-                 const unsigned char recl[8], const double* fld)
+template <class T>
+void write_field_t(const std::string& path, bool first, int file_type, bool flip, const FieldSpec& spec,
+                   const unsigned char recl[8], const T* fld)
 {
     check_nbytes(spec.nbytes);
+    if (sizeof(T) < (size_t)spec.nbytes) die("internal: an 8-byte record written from a float array");
     std::ofstream out(path, std::ios::out | std::ios::binary | (first ? std::ios::trunc : std::ios::app));
     if (!out.is_open()) die("Cannot open " + path);
     const int ml = marker_len(file_type);
@@ -105,21 +109,46 @@ void write_field(const std::string& path, bool first, int file_type, bool flip, 
     }
     const size_t n = spec.count();
     const size_t nb = (size_t)spec.nbytes;
-    if (spec.nbytes == 8 && !flip && !spec.idinv) {  // the common layout: the field array is the record
+    if ((size_t)spec.nbytes == sizeof(T) && !flip && !spec.idinv) {  // the common layout: the field array is the record
         out.write(reinterpret_cast<const char*>(fld), (std::streamsize)(n * nb));
     } else {
         std::unique_ptr<unsigned char[]> raw(new unsigned char[n * nb]);
         const Inverted inv{(size_t)spec.nx, (size_t)spec.ny, (size_t)spec.nz, (size_t)spec.nh};
         for (size_t k = 0; k < n; k++) {
-            const double v = fld[spec.idinv ? inv.mem_index(k) : k];
+            const T v = fld[spec.idinv ? inv.mem_index(k) : k];
             unsigned char* p = raw.get() + k * nb;
             if (spec.nbytes == 4) { float f = (float)v; memcpy(p, &f, 4); }  // gen_aux.cpp:134-139
-            else memcpy(p, &v, 8);
+            else { const double d = v; memcpy(p, &d, 8); }
             if (flip) reverse_bytes(p, spec.nbytes);
         }
         out.write(reinterpret_cast<char*>(raw.get()), (std::streamsize)(n * nb));
     }
     if (ml) out.write(reinterpret_cast<char*>(m), ml);  // gen_aux.cpp:207-222
+}
+
+void read_field(const std::string& path, int file_type, bool flip, const FieldSpec& spec, unsigned char recl[8],
+                long* pos, std::vector<double>& fld)
+{
+    fld.resize(spec.count());
+    read_field_t(path, file_type, flip, spec, recl, pos, fld.data());
+}
+
+void read_field(const std::string& path, int file_type, bool flip, const FieldSpec& spec, unsigned char recl[8],
+                long* pos, float* fld)
+{
+    read_field_t(path, file_type, flip, spec, recl, pos, fld);
+}
+
+void write_field(const std::string& path, bool first, int file_type, bool flip, const FieldSpec& spec,
+                 const unsigned char recl[8], const double* fld)
+{
+    write_field_t(path, first, file_type, flip, spec, recl, fld);
+}
+
+void write_field(const std::string& path, bool first, int file_type, bool flip, const FieldSpec& spec,
+                 const unsigned char recl[8], const float* fld)
+{
+    write_field_t(path, first, file_type, flip, spec, recl, fld);
 }
 
 void append_bytes(const std::string& path, const unsigned char* data, size_t n)

@@ -42,10 +42,16 @@ struct FieldHeader {
 // marker bytes in recl and advances *pos (gen_aux.cpp:230-397).
 void read_field(const std::string& path, int file_type, bool flip_endian, const FieldSpec& spec,
                 unsigned char recl[8], long* pos, std::vector<double>& fld);
+// The same into a float array of spec.count() elements (spec.nbytes == 4 only): a record in memory order and native
+// endianness is read straight into it.
+void read_field(const std::string& path, int file_type, bool flip_endian, const FieldSpec& spec,
+                unsigned char recl[8], long* pos, float* fld);
 
 // Appends (truncates if first) the field to `path` in the original layout (gen_aux.cpp:49-226).
 void write_field(const std::string& path, bool first, int file_type, bool flip_endian,
                  const FieldSpec& spec, const unsigned char recl[8], const double* fld);
+void write_field(const std::string& path, bool first, int file_type, bool flip_endian,
+                 const FieldSpec& spec, const unsigned char recl[8], const float* fld);  // spec.nbytes == 4 only
 
 // .wrb payloads (gen_aux.cpp:401-408, 419-468)
 void append_bytes(const std::string& path, const unsigned char* data, size_t n);

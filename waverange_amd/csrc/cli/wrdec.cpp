@@ -68,9 +68,13 @@ int main(int argc, char** argv)
     // decoder, GPU kernels, download; min/max for the log), a writer thread writes finished fields to the output file
     // in field order; up to `depth` fields in flight (wr_autotune_batch, which also starts the library's coder pool;
     // WR_CLI_PIPELINE overrides, 0 = strictly one after the other).
+    // fp32 records that were coded are decoded into fp32 by wr_decoding_wrap_f32 and written as they are (batch.h)
+    const char* widen_env = getenv("WR_CLI_WIDEN_ON_HOST");
+    const bool f32_codec = wr_decoding_wrap_f32 != nullptr && !(widen_env && atoi(widen_env));
     struct Item {
         wrio::FieldHeader h;
         std::unique_ptr<double[]> fld;   // not zero-filled: decoding_wrap writes every element
+        std::unique_ptr<float[]> fld32;  // instead of fld: a coded fp32 record, decoded by wr_decoding_wrap_f32
         wrcli::RawBuffer data_enc;
         std::future<void> done;
         bool decoded = false;
@@ -85,9 +89,14 @@ int main(int argc, char** argv)
     std::exception_ptr writer_error;
     auto tail = [&](Item& im, std::ostream& os) {  // after the decode: what the reference prints about the field
         const size_t ntot = im.h.spec.count();
-        if (im.decoded) os << "  decode: fld_1d_rec[0]=" << im.fld[0] << " fld_1d_rec[last]=" << im.fld[ntot - 1] << endl;
         double lo, hi;
-        wrcli::minmax(im.fld.get(), ntot, &lo, &hi);
+        if (im.fld32) {
+            os << "  decode: fld_1d_rec[0]=" << (double)im.fld32[0] << " fld_1d_rec[last]=" << (double)im.fld32[ntot - 1] << endl;
+            wrcli::minmax(im.fld32.get(), ntot, &lo, &hi);
+        } else {
+            if (im.decoded) os << "  decode: fld_1d_rec[0]=" << im.fld[0] << " fld_1d_rec[last]=" << im.fld[ntot - 1] << endl;
+            wrcli::minmax(im.fld.get(), ntot, &lo, &hi);
+        }
         os << "        min=" << lo << " max=" << hi << endl;
     };
     auto finish = [&](int it) {
@@ -96,9 +105,15 @@ int main(int argc, char** argv)
         const size_t ntot = s.count();
         if (im.done.valid()) im.done.get();
         cout << im.log.str();
-        wrio::write_field(out_name, it == 0, file_type, flip != 0, s, im.h.recl, im.fld.get());
-        cout << "  wrote: fld_1d_rec[0]=" << im.fld[0] << " fld_1d_rec[last]=" << im.fld[ntot - 1] << endl;
+        if (im.fld32) {
+            wrio::write_field(out_name, it == 0, file_type, flip != 0, s, im.h.recl, im.fld32.get());
+            cout << "  wrote: fld_1d_rec[0]=" << (double)im.fld32[0] << " fld_1d_rec[last]=" << (double)im.fld32[ntot - 1] << endl;
+        } else {
+            wrio::write_field(out_name, it == 0, file_type, flip != 0, s, im.h.recl, im.fld.get());
+            cout << "  wrote: fld_1d_rec[0]=" << im.fld[0] << " fld_1d_rec[last]=" << im.fld[ntot - 1] << endl;
+        }
         im.fld.reset();
+        im.fld32.reset();
         im.data_enc.release();
     };
     try {
@@ -135,7 +150,8 @@ int main(int argc, char** argv)
         os << "  nx=" << s.nx << "  ny=" << s.ny << "  nz=" << s.nz << "  nh=" << s.nh;
         if (s.idinv) os << " and reordering" << endl; else os << endl;
         const size_t ntot = s.count();
-        im.fld.reset(new double[ntot]);
+        if (f32_codec && s.nbytes == 4 && s.icomp && h.ntot_enc > 0) im.fld32.reset(new float[ntot]);
+        else im.fld.reset(new double[ntot]);
         if (s.icomp) {
             if (h.ntot_enc > 0) {
                 im.data_enc.allocate(h.ntot_enc);
@@ -155,8 +171,12 @@ int main(int argc, char** argv)
                 wrio::FieldHeader& hh = ip->h;
                 const wrio::FieldSpec& sp = hh.spec;
                 unsigned char wlev = (unsigned char)hh.wlev, nlay = (unsigned char)hh.nlay;
-                decoding_wrap(sp.nx, sp.ny, sp.nz * sp.nh, ip->fld.get(), &hh.tolabs, &hh.midval, &hh.halfspanval, &wlev, &nlay,
-                              &hh.ntot_enc, hh.deps_vec, hh.minval_vec, hh.len_enc_vec, ip->data_enc.data());
+                if (ip->fld32)
+                    wr_decoding_wrap_f32(sp.nx, sp.ny, sp.nz * sp.nh, ip->fld32.get(), &hh.tolabs, &hh.midval, &hh.halfspanval, &wlev,
+                                         &nlay, &hh.ntot_enc, hh.deps_vec, hh.minval_vec, hh.len_enc_vec, ip->data_enc.data());
+                else
+                    decoding_wrap(sp.nx, sp.ny, sp.nz * sp.nh, ip->fld.get(), &hh.tolabs, &hh.midval, &hh.halfspanval, &wlev, &nlay,
+                                  &hh.ntot_enc, hh.deps_vec, hh.minval_vec, hh.len_enc_vec, ip->data_enc.data());
             }
             tail(*ip, pipelined ? static_cast<std::ostream&>(ip->log) : cout);
         };

@@ -13,6 +13,7 @@
 #include <future>
 #include <thread>
 #include <iostream>
+#include <memory>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -265,12 +266,16 @@ int main(int argc, char** argv)
     if (depth > 0) setenv("WR_QUIET", "1", 0);  // the library's progress lines of concurrent fields would interleave
     setenv("WR_WRITEBACK_RESIDUAL", "0", 0);    // the residual encoding_wrap leaves in the field array is not used here
 
+    // fp32 records that are compressed go to the codec as fp32 (batch.h): read with no conversion, coded by wr_encoding_wrap_f32
+    const char* widen_env = getenv("WR_CLI_WIDEN_ON_HOST");
+    const bool f32_codec = wr_encoding_wrap_f32 != nullptr && !(widen_env && atoi(widen_env));
     const double cutoff = job.effective_tol;  // quirk Q1: one cutoff for all fields
     long pos = 0;
     unsigned long prev_ntot_enc = 0;  // quirk Q2: stale value reused for uncompressed fields
     struct Item {
         wrio::FieldHeader h;
         std::vector<double> fld;
+        std::unique_ptr<float[]> fld32;  // instead of fld: an fp32 record for wr_encoding_wrap_f32 (not zero-filled)
         wrcli::RawBuffer data_enc;   // setup_wr's worst case, untouched beyond the coded bytes
         std::future<void> done;
         std::ostringstream log;      // this field's lines, printed when it is written (pipelined mode)
@@ -278,9 +283,14 @@ int main(int argc, char** argv)
     std::vector<Item> items(job.nf);
     auto scan = [](const Item& im, std::ostream& os) {
         const size_t ntot = im.h.spec.count();
-        os << "  read: fld_1d[0]=" << im.fld[0] << " fld_1d[last]=" << im.fld[ntot - 1] << endl;
         double lo, hi;
-        wrcli::minmax(im.fld.data(), ntot, &lo, &hi);
+        if (im.fld32) {
+            os << "  read: fld_1d[0]=" << (double)im.fld32[0] << " fld_1d[last]=" << (double)im.fld32[ntot - 1] << endl;
+            wrcli::minmax(im.fld32.get(), ntot, &lo, &hi);
+        } else {
+            os << "  read: fld_1d[0]=" << im.fld[0] << " fld_1d[last]=" << im.fld[ntot - 1] << endl;
+            wrcli::minmax(im.fld.data(), ntot, &lo, &hi);
+        }
         os << "        min=" << lo << " max=" << hi << endl;
     };
     auto finish = [&](int it) {  // in field order: wait for the codec, then append to .wrh / .wrb
@@ -298,6 +308,7 @@ int main(int argc, char** argv)
             wrio::append_raw_field(job.out_name, s.nbytes, im.fld.data(), s.count());
         }
         std::vector<double>().swap(im.fld);
+        im.fld32.reset();
         im.data_enc.release();
     };
     wrcli::InFlight gate(depth);      // fields between "read" and "written"
@@ -320,7 +331,12 @@ int main(int argc, char** argv)
         os << "  contains " << s.nbytes << "-byte floating point data" << endl;
         os << "  nx=" << s.nx << "  ny=" << s.ny << "  nz=" << s.nz << "  nh=" << s.nh;
         if (s.idinv) os << " and reordering" << endl; else os << endl;
-        wrio::read_field(job.in_name, job.file_type, job.flip != 0, s, recl, &pos, im.fld);
+        if (f32_codec && s.nbytes == 4 && s.icomp) {
+            im.fld32.reset(new float[s.count()]);
+            wrio::read_field(job.in_name, job.file_type, job.flip != 0, s, recl, &pos, im.fld32.get());
+        } else {
+            wrio::read_field(job.in_name, job.file_type, job.flip != 0, s, recl, &pos, im.fld);
+        }
         if (depth == 0) scan(im, cout);
 
         im.h.spec = s;
@@ -340,9 +356,14 @@ int main(int argc, char** argv)
             unsigned char wlev = 0, nlay = 0;
             double cut = cutoff;
             // nh > 1 folds into z (gen_enc.cpp:559,596)
-            encoding_wrap(sp.nx, sp.ny, sp.nz * sp.nh, ip->fld.data(), 1, 1, 1, 1, &cut, &ip->h.tolabs, &ip->h.midval,
-                          &ip->h.halfspanval, &wlev, &nlay, &ip->h.ntot_enc, ip->h.deps_vec, ip->h.minval_vec,
-                          ip->h.len_enc_vec, ip->data_enc.data());
+            if (ip->fld32)
+                wr_encoding_wrap_f32(sp.nx, sp.ny, sp.nz * sp.nh, ip->fld32.get(), 1, 1, 1, 1, &cut, &ip->h.tolabs, &ip->h.midval,
+                                     &ip->h.halfspanval, &wlev, &nlay, &ip->h.ntot_enc, ip->h.deps_vec, ip->h.minval_vec,
+                                     ip->h.len_enc_vec, ip->data_enc.data());
+            else
+                encoding_wrap(sp.nx, sp.ny, sp.nz * sp.nh, ip->fld.data(), 1, 1, 1, 1, &cut, &ip->h.tolabs, &ip->h.midval,
+                              &ip->h.halfspanval, &wlev, &nlay, &ip->h.ntot_enc, ip->h.deps_vec, ip->h.minval_vec,
+                              ip->h.len_enc_vec, ip->data_enc.data());
             ip->h.wlev = wlev; ip->h.nlay = nlay;
         };
         if (depth > 0) { im.done = std::async(std::launch::async, work); gate.launched(it); }

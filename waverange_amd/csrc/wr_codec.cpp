@@ -36,7 +36,8 @@ struct Prologue {
     double lo, hi;
 };
 
-int prologue(wr_ctx* c, const double* d_fld, size_t n, int wtflag, wr_enc_info* info, Prologue* p)
+template <typename T>
+int prologue(wr_ctx* c, const T* d_fld, size_t n, int wtflag, wr_enc_info* info, Prologue* p)
 {
     memset(info, 0, sizeof(*info));
     info->wlev = wtflag ? kWavLvl : 0;
@@ -74,10 +75,12 @@ struct Cutoff {
 // are enqueued there, behind the read-back);
 // plane_ready(l, last) is called from the host once everything enqueued for plane l has completed on the
 // device (the download starts there).  *resid = where the coefficient array / residual lives afterwards.
+// f32 != nullptr (an fp32 field on the fused path only): the field is that array, which the fused forward transform reads
+// as it is; d_fld is then n doubles of work space (may be f32's memory: the transform has consumed it before it is used).
 template <class PlaneBuf, class HistBuf, class AfterQuant, class PlaneReady>
 int encode_planes_core(wr_ctx* c, Slot* slot, double* d_fld, int nx, int ny, int nz, int wtflag, const Cutoff& cut,
                        PlaneBuf plane_buf, HistBuf hist_buf, wr_enc_info* info, wr_timings* tm, AfterQuant after_quant, PlaneReady plane_ready,
-                       double** resid)
+                       double** resid, const float* f32 = nullptr)
 {
     // minimum cutoff = the global relative tolerance (wrappers.cpp:288-290)
     double tolrel = cut.vec[0];
@@ -113,15 +116,17 @@ int encode_planes_core(wr_ctx* c, Slot* slot, double* d_fld, int nx, int ny, int
         info->wlev = kWavLvl;
         double* const d_in = d_fld;
         HIPCHK(hipEventRecord(c->ev_b, c->stream));
-        wrk::transform_fwd_fused(d_in, slot->scratch, slot->lowbuf, nx, ny, nz, c->stream, c->d_mm, c->h_result_dev + 4);
+        if (f32) wrk::transform_fwd_fused_f32(f32, d_in, slot->scratch, slot->lowbuf, nx, ny, nz, c->stream, c->d_mm, c->h_result_dev + 4);
+        else wrk::transform_fwd_fused(d_in, slot->scratch, slot->lowbuf, nx, ny, nz, c->stream, c->d_mm, c->h_result_dev + 4);
         HIPCHK(hipEventRecord(c->ev_c, c->stream));
         HIPCHK(hipEventRecord(c->ev_mm, c->stream));
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventSynchronize(c->ev_mm));
         p.lo = c->h_result[4]; p.hi = c->h_result[5];
         lo = c->h_result[6]; hi = c->h_result[7];
-        if (p.lo == 0.0)  // sign of a zero minimum: the reference's scan semantics, rare path
-            if (int rc = read_minmax(c, d_in, n, false, &p.lo, &p.hi)) return rc;
+        if (p.lo == 0.0) {  // sign of a zero minimum: the reference's scan semantics, rare path
+            if (int rc = f32 ? read_minmax(c, f32, n, false, &p.lo, &p.hi) : read_minmax(c, d_in, n, false, &p.lo, &p.hi)) return rc;
+        }
         if (p.lo != p.lo || p.hi != p.hi) return fail(WR_ERR_ARG, "field is all NaN");
         info->halfspanval = (p.hi - p.lo) / 2;
         info->midval = p.lo + info->halfspanval;
@@ -140,14 +145,14 @@ int encode_planes_core(wr_ctx* c, Slot* slot, double* d_fld, int nx, int ny, int
         if (tm) { HIPCHK(hipEventElapsedTime(&ms, c->ev_b, c->ev_c)); tm->transform_ms = ms; tm->minmax_ms = 0; }
     } else {
     HIPCHK(hipEventRecord(c->ev_a, c->stream));
-    if (int rc = prologue(c, d_fld, n, wtflag, info, &p)) return rc;
+    if (int rc = f32 ? prologue(c, f32, n, wtflag, info, &p) : prologue(c, (const double*)d_fld, n, wtflag, info, &p)) return rc;
     if (verbose()) printf("Wavelet decomposition...\n");
     if (p.trivial) {  // wrappers.cpp:256-266
         info->ntot_enc = 0; info->nlay = 0; info->tolabs = 0;
         return WR_OK;
     }
     HIPCHK(hipEventRecord(c->ev_b, c->stream));
-    if (int rc = run_transform(c, slot, d_fld, nx, ny, nz, (int)info->wlev, &d_fld)) return rc;  // d_fld := coefficients
+    if (int rc = run_transform(c, slot, d_fld, nx, ny, nz, (int)info->wlev, &d_fld, f32)) return rc;  // d_fld := coefficients
     *resid = d_fld;
     HIPCHK(hipEventRecord(c->ev_c, c->stream));
     if (verbose()) printf("Range encoding...\n");
@@ -303,7 +308,9 @@ namespace {
 // where the field of an encode call comes from / the field of a decode call goes to
 struct FieldRef {
     double* dev = nullptr;   // device-resident (caller's buffer), or
-    double* host = nullptr;  // host buffer (pinned or pageable): staged through the slot
+    double* host = nullptr;  // host buffer (pinned or pageable): staged through the slot, or
+    float* host_f32 = nullptr;  // an fp32 host buffer: 4 bytes per sample cross the bus, widened / narrowed on the device
+    bool none() const { return !dev && !host && !host_f32; }
 };
 
 int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, const Cutoff& cut, wr_enc_info* info,
@@ -311,9 +318,11 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
 {
     if (int rc = ctx_bind(c)) return rc;
     if (int rc = check_dims(nx, ny, nz, fld.dev)) return rc;
-    if (!fld.dev && !fld.host) return fail(WR_ERR_ARG, "null field pointer");
+    if (fld.none()) return fail(WR_ERR_ARG, "null field pointer");
     if (cut.mx < 1 || cut.my < 1 || cut.mz < 1 || !cut.vec) return fail(WR_ERR_ARG, "bad local cutoff description");
     std::lock_guard<std::mutex> lk(c->mu);
+    if (fld.host_f32 && c->keep_residual)  // (the residual is fp64: narrowing it into the caller's field would lose bits)
+        return fail(WR_ERR_UNSUPPORTED, "an fp32 field cannot take the residual back: wr_ctx_set_keep_residual(ctx, 0) for fp32 encodes");
     ActiveCall active(c->pool);
     if (tm) wrdma::enable_timing();
     const double t0 = now();
@@ -396,7 +405,7 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
 
     SlotNeed need;
     transform_need(nx, ny, nz, wtflag ? kWavLvl : 0, &need);
-    if (fld.host) need.field_elems = n;
+    if (fld.host || fld.host_f32) need.field_elems = n;
     need.hist_elems = hist_per_plane * WR_NLAYMAX;
     if (int rc = ensure_host_hist(c, hist_per_plane * WR_NLAYMAX)) return rc;
 
@@ -414,6 +423,19 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
             d_fld = slot->field;
             if ((rc = xfer_field(c, &c->x_field, d_fld, fld.host, n * sizeof(double), kUp)) != WR_OK) return rc;
             local.h2d_ms = (float)c->x_field.ms;
+        }
+        // An fp32 field: the fused forward transform reads it where it lands (the slot's field buffer, which is work space of n
+        // doubles from then on).  Elsewhere it lands in the scratch buffer and is widened into the field buffer in front of
+        // the fp64 path (the general transform's scratch is free until then).
+        const float* d_f32 = nullptr;
+        float* widen_from = nullptr;
+        if (fld.host_f32) {
+            d_fld = slot->field;
+            float* const stage = (wtflag && use_fused(nx, ny, nz, kWavLvl)) ? reinterpret_cast<float*>(slot->field) : reinterpret_cast<float*>(slot->scratch);
+            if ((rc = xfer_field(c, &c->x_field, stage, fld.host_f32, n * sizeof(float), kUp)) != WR_OK) return rc;
+            local.h2d_ms = (float)c->x_field.ms;
+            if (stage == reinterpret_cast<float*>(slot->field)) d_f32 = stage;
+            else widen_from = stage;
         }
         double* resid = d_fld;
         auto hist_buf = [&](unsigned l) { return slot->hist + l * hist_per_plane; };
@@ -477,7 +499,9 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
             // ---- stage "kernels"
             cu.lock();
             clock_warmup(c, n);
-            rc = encode_planes_core(c, slot.get(), d_fld, nx, ny, nz, wtflag, cut, plane_buf, hist_buf, info, &local, after_quant, plane_ready, &resid);
+            if (widen_from) wrk::widen_f32(widen_from, d_fld, n, c->stream);
+            rc = encode_planes_core(c, slot.get(), d_fld, nx, ny, nz, wtflag, cut, plane_buf, hist_buf, info, &local, after_quant, plane_ready, &resid,
+                                    d_f32);
             if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the encoder's kernel stage failed on the device" + launch_describe(c));
             if (rc == WR_OK && c->keep_residual && info->nlay && !fld.host && resid != fld.dev) {  // leave the residual where the reference leaves it
                 if (hipMemcpyAsync(fld.dev, resid, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
@@ -586,7 +610,7 @@ int decode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_in
     // (a finish that is refused for its arguments leaves the begin pending: the caller may try again with a usable
     // pointer, and the parked planes are not orphaned)
     if (int rc = check_dims(nx, ny, nz, fld.dev)) return rc;
-    if (mode != kDecodeBegin && !fld.dev && !fld.host) return fail(WR_ERR_ARG, "null field pointer");
+    if (mode != kDecodeBegin && fld.none()) return fail(WR_ERR_ARG, "null field pointer");
     if (mode == kDecodeFinish) c->pend_valid = false;
     // From here on the context's device planes go back on every way out, unless a begin parks them (a finish finds the
     // planes its begin parked; a begin or a whole decode discards what an earlier begin left).
@@ -600,6 +624,7 @@ int decode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_in
     if (info->ntot_enc == 0) {  // wrappers.cpp:462-469
         if (mode == kDecodeBegin) { c->pend_tm = local; c->pend_valid = true; if (tm) *tm = local; return WR_OK; }
         if (fld.host) for (size_t j = 0; j < n; j++) fld.host[j] = info->midval;
+        else if (fld.host_f32) for (size_t j = 0; j < n; j++) fld.host_f32[j] = (float)info->midval;
         else { wrk::fill(fld.dev, n, info->midval, c->stream); HIPCHK(hipStreamSynchronize(c->stream)); }
         local.total += now() - t0;
         if (tm) *tm = local;
@@ -649,7 +674,7 @@ int decode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_in
 
     SlotNeed need;
     transform_need(nx, ny, nz, info->wlev ? -kWavLvl : 0, &need);
-    if (fld.host) need.field_elems = n;
+    if (fld.host || fld.host_f32) need.field_elems = n;
 
     size_t got[WR_NLAYMAX] = {0};
     double coder_s[WR_NLAYMAX] = {0};
@@ -735,13 +760,14 @@ int decode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_in
             p.deps[l] = info->deps_vec[l]; p.minval[l] = info->minval_vec[l]; p.q[l] = c->ps[l].ref;
             if (!wrk::plane_ref_covers(p.q[l], n)) return fail(WR_ERR_HIP, "internal: the device buffer of plane " + std::to_string(l) + " has a hole");
         }
-        launch_note(c, "dequant", nlay - 1, fld.host ? slot->field : fld.dev, n, nullptr, p.q[nlay - 1]);
-        double* d_fld = fld.host ? slot->field : fld.dev;
+        launch_note(c, "dequant", nlay - 1, fld.dev ? (void*)fld.dev : (void*)slot->field, n, nullptr, p.q[nlay - 1]);
+        double* d_fld = fld.dev ? fld.dev : slot->field;
+        float* d_f32 = nullptr;  // fp32: where inverse_from_planes leaves the narrowed reconstruction
         {
             // ---- stage "kernels"
             StageLock cu(pool->cu_mu);
             clock_warmup(c, n);
-            rc = inverse_from_planes(c, slot.get(), d_fld, nx, ny, nz, (int)info->wlev, p);
+            rc = inverse_from_planes(c, slot.get(), d_fld, nx, ny, nz, (int)info->wlev, p, fld.host_f32 ? &d_f32 : nullptr);
             if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
             if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the decoder's kernel stage failed on the device" + launch_describe(c));
             pool->last_stage_end.store(now());
@@ -750,6 +776,9 @@ int decode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_in
         if (fld.host) {
             // ---- stage "down": the reconstructed field, device -> host
             if ((rc = xfer_field(c, &c->x_field, fld.host, d_fld, n * sizeof(double), kDown)) != WR_OK) return rc;
+            local.d2h_ms = (float)c->x_field.ms;
+        } else if (fld.host_f32) {
+            if ((rc = xfer_field(c, &c->x_field, fld.host_f32, d_f32, n * sizeof(float), kDown)) != WR_OK) return rc;
             local.d2h_ms = (float)c->x_field.ms;
         }
     } catch (const std::exception& e) {
@@ -821,6 +850,28 @@ int wr_decode_begin(wr_ctx* c, int nx, int ny, int nz, const wr_enc_info* info, 
 int wr_decode_finish_host(wr_ctx* c, double* h_fld, wr_timings* tm)
 {
     FieldRef f; f.host = h_fld;
+    if (!h_fld) return fail(WR_ERR_ARG, "null field pointer");
+    return decode_impl(c, f, 0, 0, 0, nullptr, nullptr, 0, tm, kDecodeFinish);
+}
+
+int wr_encode_host_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                       const double* cutoffvec, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm)
+{
+    Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
+    FieldRef f; f.host_f32 = const_cast<float*>(h_fld);  // (read only: an fp32 encode never writes the residual back)
+    return encode_impl(c, f, nx, ny, nz, wtflag, cut, info, data_enc, cap, tm);
+}
+
+int wr_decode_host_f32(wr_ctx* c, float* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc,
+                       size_t data_len, wr_timings* tm)
+{
+    FieldRef f; f.host_f32 = h_fld;
+    return decode_impl(c, f, nx, ny, nz, info, data_enc, data_len, tm);
+}
+
+int wr_decode_finish_host_f32(wr_ctx* c, float* h_fld, wr_timings* tm)
+{
+    FieldRef f; f.host_f32 = h_fld;
     if (!h_fld) return fail(WR_ERR_ARG, "null field pointer");
     return decode_impl(c, f, 0, 0, 0, nullptr, nullptr, 0, tm, kDecodeFinish);
 }

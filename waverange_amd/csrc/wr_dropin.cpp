@@ -1,6 +1,7 @@
 // wr_dropin.cpp -- Part 1 of include/waverange_amd.h: the reference's own entry points (same unmangled symbols, argument
 // order and meaning as libwaverange, src/core/wrappers.h:53,70,75,95,111,119; waveletcdf97_3d) on host pointers, on top of
-// wr_encode_host / wr_decode_host / wr_transform_host.  "void + fatal" error behaviour as the reference's.
+// wr_encode_host / wr_decode_host / wr_transform_host.  "void + fatal" error behaviour as the reference's.  Also their fp32
+// counterparts wr_encoding_wrap_f32 / wr_decoding_wrap_f32 (Part 2 of the header: not symbols of the reference).
 #include "wr_internal.h"
 
 using namespace wri;
@@ -89,6 +90,46 @@ void decoding_wrap(int nx, int ny, int nz, double* fld_1d, double* tolabs, doubl
         info.len_enc_vec[l] = len_enc_vec[l];
     }
     if (wr_decode_host(ic.c, fld_1d, nx, ny, nz, &info, data_enc, 0, nullptr)) fatal("decoding_wrap");
+}
+
+void wr_encoding_wrap_f32(int nx, int ny, int nz, const float* fld_1d, int wtflag, int mx, int my, int mz, double* cutoffvec,
+                          double* tolabs, double* midval, double* halfspanval, unsigned char* wlev, unsigned char* nlay,
+                          unsigned long* ntot_enc, double* deps_vec, double* minval_vec, unsigned long* len_enc_vec,
+                          unsigned char* data_enc)
+{
+    if (mx < 1 || my < 1 || mz < 1) { last_error() = "mx, my, mz must be >= 1"; fatal("wr_encoding_wrap_f32"); }
+    ImplicitCtx ic("wr_encoding_wrap_f32");
+    unsigned char nl; unsigned long cap;
+    setup_wr(nx, ny, nz, &nl, &cap);
+    wr_enc_info info;
+    ic.c->keep_residual = false;  // an fp32 field never takes the residual back
+    if (wr_encode_host_f32(ic.c, fld_1d, nx, ny, nz, wtflag, mx, my, mz, cutoffvec, &info, data_enc, cap, nullptr))
+        fatal("wr_encoding_wrap_f32");
+    *tolabs = info.tolabs; *midval = info.midval; *halfspanval = info.halfspanval;
+    *wlev = info.wlev; *nlay = info.nlay; *ntot_enc = info.ntot_enc;
+    for (int l = 0; l < info.nlay; l++) {
+        deps_vec[l] = info.deps_vec[l];
+        minval_vec[l] = info.minval_vec[l];
+        len_enc_vec[l] = info.len_enc_vec[l];
+    }
+}
+
+void wr_decoding_wrap_f32(int nx, int ny, int nz, float* fld_1d, double* tolabs, double* midval, double* halfspanval,
+                          unsigned char* wlev, unsigned char* nlay, unsigned long* ntot_enc, double* deps_vec,
+                          double* minval_vec, unsigned long* len_enc_vec, unsigned char* data_enc)
+{
+    (void)tolabs; (void)halfspanval;
+    ImplicitCtx ic("wr_decoding_wrap_f32");
+    wr_enc_info info;
+    memset(&info, 0, sizeof info);
+    info.midval = *midval; info.wlev = *wlev; info.nlay = *nlay; info.ntot_enc = *ntot_enc;
+    if (info.nlay > WR_NLAYMAX) { last_error() = "nlay > 8"; fatal("wr_decoding_wrap_f32"); }
+    for (int l = 0; l < info.nlay; l++) {
+        info.deps_vec[l] = deps_vec[l];
+        info.minval_vec[l] = minval_vec[l];
+        info.len_enc_vec[l] = len_enc_vec[l];
+    }
+    if (wr_decode_host_f32(ic.c, fld_1d, nx, ny, nz, &info, data_enc, 0, nullptr)) fatal("wr_decoding_wrap_f32");
 }
 
 void setup_wr_f(int* nx, int* ny, int* nz, int* nlaymax, long* ntot_enc_max)

@@ -161,13 +161,20 @@ __device__ inline void lift_fwd_n(const double s[N + 4], const double d[N + 3], 
 
 }  // namespace
 
+// TIN: the element type of the level input.  float (level 0 of an fp32 field only): a lane loads its x-pair as 8 bytes into
+// registers (global_load_lds takes 1, 2, 4, 12 or 16 bytes per lane, and the rows of a field with nx = 2 mod 4 are only
+// 8-byte aligned) and writes it widened to the chunk global_load_lds would have filled: the LDS image, its pitches and
+// everything that reads it are those of the fp64 kernel.  fp32 -> fp64 is exact, so are the results.
 // MM_IN / MM_OUT: also reduce min/max of the samples read (the whole level input: level 0 = the field) / of the
 // coefficients stored to their final positions (mm_lll: including the low-pass octant, i.e. this is the last
 // level), one {in lo, in hi, out lo, out hi} record per wave in mm_partial -- replaces the two stand-alone
 // min/max passes of the encoder (wrappers.cpp:244-250, 308-314) at ~3 % more vector instructions.
-template <bool MM_IN, bool MM_OUT>
+// (TIN is a template parameter of the kernel itself: a __global__ wrapper around a device-function body shared by both types
+// compiles the fp64 kernels into different code -- selects for the z step's branches, 18 VGPRs fewer -- where this form leaves
+// their instructions exactly as they were)
+template <bool MM_IN, bool MM_OUT, typename TIN = double>
 __global__ __launch_bounds__(NTHR, 2) void k_fwd_fused(
-    const double* __restrict__ src, size_t s_sy, size_t s_sz,  // level input (x stride 1)
+    const TIN* __restrict__ src, size_t s_sy, size_t s_sz,     // level input (x stride 1)
     double* __restrict__ dst, size_t d_sy, size_t d_sz,        // coefficient array (final positions)
     double* __restrict__ low, size_t l_sy, size_t l_sz,        // low-pass octant destination
     int n1, int n2, int n3, int zps, double* __restrict__ mm_partial, int mm_lll
@@ -216,15 +223,32 @@ __global__ __launch_bounds__(NTHR, 2) void k_fwd_fused(
     }
     // global -> LDS without a register round trip: each lane supplies its own 16-byte source,
     // the wave's 64 chunks land contiguously at a wave-uniform LDS base (global_load_lds_dwordx4)
+    constexpr bool F32 = sizeof(TIN) == 4;
+    float2 stg[2][F32 ? KCH : 1];  // fp32: the x-pairs of planes 2t, 2t+1 on their way to LDS
     auto fetch = [&](int t, int p) {
-        const double* pl = src + (size_t)(2 * t + p) * s_sz;
+        const TIN* pl = src + (size_t)(2 * t + p) * s_sz;
 #pragma unroll
         for (int k = 0; k < KCH; k++) {
             if (offa[k] >= 0) {
-                double2* l = raw + p * NCHUNK + NTHR * k + (w << 6);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pl + offa[k]),
-                                                 (__attribute__((address_space(3))) void*)l, 16, 0, 0);
+                if constexpr (F32) {
+                    stg[p][k] = *reinterpret_cast<const float2*>(pl + offa[k]);
+                } else {
+                    double2* l = raw + p * NCHUNK + NTHR * k + (w << 6);
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pl + offa[k]),
+                                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
+                }
             }
+        }
+    };
+    // fp32: the staged pairs, widened, to the chunks the DMA would have written (lane-linear: ds_write_b128 of 8 consecutive
+    // lanes covers 128 consecutive bytes, no bank conflict)
+    auto commit = [&]() {
+        if constexpr (F32) {
+#pragma unroll
+            for (int p = 0; p < 2; p++)
+#pragma unroll
+                for (int k = 0; k < KCH; k++)
+                    if (offa[k] >= 0) raw[p * NCHUNK + NTHR * k + tid] = make_double2((double)stg[p][k].x, (double)stg[p][k].y);
         }
     };
     const bool left_edge = px0 == 0, right_edge = px0 + TXP >= m1;
@@ -311,6 +335,7 @@ __global__ __launch_bounds__(NTHR, 2) void k_fwd_fused(
             const bool more = t + 1 <= te && t + 1 < m3;
             STAMP(7);
             __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's chunks of planes 2t, 2t+1 have landed
+            commit();                             // (fp32: ... in registers; they go to LDS now)
             STAMP(0);
             __syncthreads();                      // ... and everybody else's
             STAMP(1);
@@ -527,6 +552,11 @@ __device__ inline void quad_exchange(bool odd, double& a, double& b)
 __device__ inline int mirror_s(int k, int M) { if (k < 0) k = -k; if (k >= M) k = 2 * M - 1 - k; return k < 0 ? 0 : (k >= M ? M - 1 : k); }
 __device__ inline int mirror_d(int k, int M) { if (k < 0) k = -k - 1; if (k >= M) k = 2 * M - 2 - k; return k < 0 ? 0 : (k >= M ? M - 1 : k); }
 
+// Two adjacent output samples of a row to the reconstructed box: 16 bytes as they are, or -- level 0 of an fp32 field --
+// narrowed with the C cast (v_cvt_f32_f64: round to nearest even, fp32 subnormals kept, inf beyond FLT_MAX), 8 bytes.
+__device__ inline void store_pair(double* p, double a, double b) { *reinterpret_cast<double2*>(p) = make_double2(a, b); }
+__device__ inline void store_pair(float* p, double a, double b) { *reinterpret_cast<float2*>(p) = make_float2((float)a, (float)b); }
+
 // inverse lifting of two adjacent pairs from s[-1..3], d[-2..3], both already scaled (s * 1/zeta, d * zeta)  (:314-337):
 // 14 lifting steps
 __device__ inline void lift_inv_two(const double s[5], const double d[6], double out[4])
@@ -567,10 +597,12 @@ __device__ inline void lift_inv_four(const double s[7], const double d[8], doubl
 // pass over the whole array, 16 GB of traffic less per decode -- was built in round 4, bit-exact, and measured EQUAL: 6.6 ms
 // against 2.5 + 4.2 = 6.7 ms, its ~480 extra vector instructions per thread and z step sitting in the z phase of a kernel
 // whose eight waves per CU move through their phases together.  Removed in round 5: profiles/r04/j_inverse_from_planes.txt.)
+// TOUT: element type of the reconstructed box (float: level 0 of an fp32 field only; everything before the store is fp64)
+template <typename TOUT = double>
 __global__ __launch_bounds__(INTHR, 2) void k_inv_fused(
     const double* __restrict__ src, size_t s_sy, size_t s_sz,  // coefficient array (detail octants)
     const double* __restrict__ low, size_t l_sy, size_t l_sz,  // low-pass octant (previous level's output)
-    double* __restrict__ out, size_t o_sy, size_t o_sz,        // reconstructed box of this level
+    TOUT* __restrict__ out, size_t o_sy, size_t o_sz,          // reconstructed box of this level
     int n1, int n2, int n3, int zps
 #ifdef WR_STAMP
     , unsigned long long* __restrict__ stamp_out
@@ -702,7 +734,7 @@ __global__ __launch_bounds__(INTHR, 2) void k_inv_fused(
         constexpr int RPS = 64 / ITXP;
         const int srow = lane / ITXP, spair = lane % ITXP;
         const bool own = px0 + spair < m1;
-        double* dstp = out + (size_t)zplane * o_sz + (size_t)(yrow0 + srow) * o_sy + 2 * (px0 + spair);
+        TOUT* dstp = out + (size_t)zplane * o_sz + (size_t)(yrow0 + srow) * o_sy + 2 * (px0 + spair);
 #if WR_ITXP == 64 && !defined(WR_INV_LDS_STORE)
         // 64-pair tiles: a quad of lanes IS the four rows of one lane column (lane = 4 * column + row), and lane 4 c + p of the
         // row-wise store wants pair 4 c + p of every row: a 4 x 4 transpose of {ev, od} pairs inside the quad -- two DPP
@@ -719,7 +751,7 @@ __global__ __launch_bounds__(INTHR, 2) void k_inv_fused(
         static_assert(WR_ITXP != 64 || (RW == 4 && RPS == 1), "a quad of lanes holds the four rows of a lane column");
 #pragma unroll
         for (int st = 0; st < RW / RPS; st++)
-            if (own && yrow0 + st < n2) *reinterpret_cast<double2*>(dstp + (size_t)st * o_sy) = make_double2(ev[st & 3], od[st & 3]);
+            if (own && yrow0 + st < n2) store_pair(dstp + (size_t)st * o_sy, ev[st & 3], od[st & 3]);
 #else
         // through the wave's rows (everything has been read: LDS runs a wave's instructions in order)
         double* o = ybw + yrow_off(r) + 2 * i;
@@ -729,7 +761,7 @@ __global__ __launch_bounds__(INTHR, 2) void k_inv_fused(
         for (int st = 0; st < RW / RPS; st++) {
             const int rr = st * RPS + srow;
             const double2 v = *reinterpret_cast<const double2*>(ybw + yrow_off(rr) + 2 * spair);
-            if (own && yrow0 + rr < n2) *reinterpret_cast<double2*>(dstp + (size_t)(st * RPS) * o_sy) = v;
+            if (own && yrow0 + rr < n2) store_pair(dstp + (size_t)(st * RPS) * o_sy, v.x, v.y);
         }
 #endif
     };
@@ -810,11 +842,11 @@ __global__ __launch_bounds__(INTHR, 2) void k_inv_fused(
 #pragma unroll
                 for (int pl2 = 0; pl2 < 2; pl2++) {
                     const int yrow0 = 2 * (py0 + J);
-                    double* dstp = out + (size_t)(2 * j + pl2) * o_sz + (size_t)(yrow0 + srow) * o_sy + 2 * (px0 + spair);
+                    TOUT* dstp = out + (size_t)(2 * j + pl2) * o_sz + (size_t)(yrow0 + srow) * o_sy + 2 * (px0 + spair);
 #pragma unroll
                     for (int st = 0; st < RW / RPS; st++) {
                         const int rr = st * RPS + srow;
-                        if (own && yrow0 + rr < n2) *reinterpret_cast<double2*>(dstp + (size_t)(st * RPS) * o_sy) = make_double2(acc, acc + pl2);
+                        if (own && yrow0 + rr < n2) store_pair(dstp + (size_t)(st * RPS) * o_sy, acc, acc + pl2);
                     }
                 }
             }
@@ -998,7 +1030,10 @@ const char* fused_prepare()
         {(const void*)k_fwd_fused<false, false>, "k_fwd_fused<false,false>", (int)LDS_BYTES},
         {(const void*)k_fwd_fused<true, true>, "k_fwd_fused<true,true>", (int)LDS_BYTES},
         {(const void*)k_fwd_fused<false, true>, "k_fwd_fused<false,true>", (int)LDS_BYTES},
-        {(const void*)k_inv_fused, "k_inv_fused", (int)LDS_INV}};
+        {(const void*)k_fwd_fused<false, false, float>, "k_fwd_fused<false,false,float>", (int)LDS_BYTES},
+        {(const void*)k_fwd_fused<true, true, float>, "k_fwd_fused<true,true,float>", (int)LDS_BYTES},
+        {(const void*)k_inv_fused<double>, "k_inv_fused<double>", (int)LDS_INV},
+        {(const void*)k_inv_fused<float>, "k_inv_fused<float>", (int)LDS_INV}};
     for (const auto& k : ks) {
         const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes);
         if (e != hipSuccess) {
@@ -1013,16 +1048,43 @@ const char* fused_prepare()
     return nullptr;
 }
 
+// one fused forward level: level 0 reads the field (double or float), the levels below it the previous level's low-pass
+// box (double)
+#define WR_FWD_LAUNCH(K) hipLaunchKernelGGL(K, grid, dim3(NTHR), LDS_BYTES, st, in, in_sy, in_sz, dst, d_sy, d_sz, lo, lo_sy, lo_sz, n1, n2, \
+                                            n3, zps, rec, lll WR_FWD_STAMP)
+#ifdef WR_STAMP
+#define WR_FWD_STAMP , first ? g_stamp_buf : nullptr
+#else
+#define WR_FWD_STAMP
+#endif
+static void fwd_level(dim3 grid, hipStream_t st, const double* in, size_t in_sy, size_t in_sz, double* dst, size_t d_sy, size_t d_sz,
+                      double* lo, size_t lo_sy, size_t lo_sz, int n1, int n2, int n3, int zps, bool mm, bool first, double* rec, int lll)
+{
+    if (!mm) { rec = nullptr; lll = 0; WR_FWD_LAUNCH((k_fwd_fused<false, false>)); }
+    else if (first) WR_FWD_LAUNCH((k_fwd_fused<true, true>));
+    else WR_FWD_LAUNCH((k_fwd_fused<false, true>));
+}
+static void fwd_level(dim3 grid, hipStream_t st, const float* in, size_t in_sy, size_t in_sz, double* dst, size_t d_sy, size_t d_sz,
+                      double* lo, size_t lo_sy, size_t lo_sz, int n1, int n2, int n3, int zps, bool mm, bool first, double* rec, int lll)
+{
+    if (!mm) { rec = nullptr; lll = 0; WR_FWD_LAUNCH((k_fwd_fused<false, false, float>)); }
+    else WR_FWD_LAUNCH((k_fwd_fused<true, true, float>));  // (level 0 only: first)
+}
+#undef WR_FWD_LAUNCH
+#undef WR_FWD_STAMP
+
 // mm_partial != nullptr (needs fused_minmax_records() > 0): min/max of the field and of the coefficient array
-// are reduced on the way and land in mm_result[0..3].
-void transform_fwd_fused(double* src, double* dst, double* lowbuf, int nx, int ny, int nz, hipStream_t st,
-                         double* mm_partial, double* mm_result)
+// are reduced on the way and land in mm_result[0..3].  scratch: ping-pong buffer of the general levels (n doubles; may be
+// the memory src lies in, which level 0 has consumed by then).
+template <typename TIN>
+static void fwd_fused(const TIN* src, double* scratch, double* dst, double* lowbuf, int nx, int ny, int nz, hipStream_t st,
+                      double* mm_partial, double* mm_result)
 {
     (void)fused_prepare();  // (callers check it before they choose this path: wr_pipeline.cpp, wr_codec.cpp)
     const size_t d_sy = (size_t)nx, d_sz = (size_t)nx * ny;
     const int nfused = fused_levels(nx, ny, nz, false);
     const bool mm = mm_partial != nullptr && nfused == 4;
-    const double* in = src;
+    const double* in = nullptr;  // input of the levels below the first
     size_t in_sy = d_sy, in_sz = d_sz;
     double* lb = lowbuf;
     double* rec = mm_partial;
@@ -1038,20 +1100,8 @@ void transform_fwd_fused(double* src, double* dst, double* lowbuf, int nx, int n
         int zps;
         const dim3 grid = fwd_grid(n1, n2, n3, &zps);
         const int lll = l == nfused - 1;
-#ifdef WR_STAMP
-        hipLaunchKernelGGL((k_fwd_fused<false, false>), grid, dim3(NTHR), LDS_BYTES, st, in, in_sy, in_sz, dst, d_sy, d_sz, lo, lo_sy,
-                           lo_sz, n1, n2, n3, zps, (double*)nullptr, 0, l == 0 ? g_stamp_buf : nullptr);
-#else
-        if (!mm)
-            hipLaunchKernelGGL((k_fwd_fused<false, false>), grid, dim3(NTHR), LDS_BYTES, st, in, in_sy, in_sz, dst, d_sy, d_sz, lo, lo_sy,
-                               lo_sz, n1, n2, n3, zps, (double*)nullptr, 0);
-        else if (l == 0)
-            hipLaunchKernelGGL((k_fwd_fused<true, true>), grid, dim3(NTHR), LDS_BYTES, st, in, in_sy, in_sz, dst, d_sy, d_sz, lo, lo_sy,
-                               lo_sz, n1, n2, n3, zps, rec, lll);
-        else
-            hipLaunchKernelGGL((k_fwd_fused<false, true>), grid, dim3(NTHR), LDS_BYTES, st, in, in_sy, in_sz, dst, d_sy, d_sz, lo, lo_sy,
-                               lo_sz, n1, n2, n3, zps, rec, lll);
-#endif
+        if (l == 0) fwd_level(grid, st, src, in_sy, in_sz, dst, d_sy, d_sz, lo, lo_sy, lo_sz, n1, n2, n3, zps, mm, true, rec, lll);
+        else fwd_level(grid, st, in, in_sy, in_sz, dst, d_sy, d_sz, lo, lo_sy, lo_sz, n1, n2, n3, zps, mm, false, rec, lll);
         const int nrec = (int)(grid.x * grid.y * NWAVE);
         if (l == 0) n_in = nrec;
         n_all += nrec;
@@ -1060,13 +1110,27 @@ void transform_fwd_fused(double* src, double* dst, double* lowbuf, int nx, int n
         lb += (size_t)m1 * m2 * m3;
     }
     if (mm) hipLaunchKernelGGL(k_minmax_final4, dim3(1), dim3(256), 0, st, mm_partial, n_in, n_all, mm_result);
-    // coarser levels whose boxes are odd somewhere: general kernels, in place on the corner box of
-    // dst; the input array has been fully consumed by level 0 and serves as their ping-pong scratch
-    for (int k = nfused; k < 4; k++) transform_level(dst, src, nx, ny, nz, k, false, st);
+    // coarser levels whose boxes are odd somewhere: general kernels, in place on the corner box of dst
+    for (int k = nfused; k < 4; k++) transform_level(dst, scratch, nx, ny, nz, k, false, st);
 }
 
-// src holds the coefficient array; the reconstruction lands in dst
-void transform_inv_fused(double* src, double* dst, double* lowbuf, int nx, int ny, int nz, hipStream_t st)
+void transform_fwd_fused(double* src, double* dst, double* lowbuf, int nx, int ny, int nz, hipStream_t st,
+                         double* mm_partial, double* mm_result)
+{
+    // the input array has been fully consumed by level 0 and serves as the general levels' ping-pong scratch
+    fwd_fused<double>(src, src, dst, lowbuf, nx, ny, nz, st, mm_partial, mm_result);
+}
+
+void transform_fwd_fused_f32(const float* src, double* scratch, double* dst, double* lowbuf, int nx, int ny, int nz, hipStream_t st,
+                             double* mm_partial, double* mm_result)
+{
+    fwd_fused<float>(src, scratch, dst, lowbuf, nx, ny, nz, st, mm_partial, mm_result);
+}
+
+// src holds the coefficient array; the reconstruction lands in dst (TOUT: written by level 0 only).  scratch: ping-pong buffer
+// of the general levels (n doubles; may be the memory dst lies in: they run before any fused level writes dst).
+template <typename TOUT>
+static void inv_fused(double* src, TOUT* dst, double* scratch, double* lowbuf, int nx, int ny, int nz, hipStream_t st)
 {
     (void)fused_prepare();
     const size_t f_sy = (size_t)nx, f_sz = (size_t)nx * ny;
@@ -1076,9 +1140,8 @@ void transform_inv_fused(double* src, double* dst, double* lowbuf, int nx, int n
     cbuf[2] = cbuf[1] + (size_t)(nx >> 1) * (ny >> 1) * (nz >> 1);
     cbuf[3] = cbuf[2] + (size_t)(nx >> 2) * (ny >> 2) * (nz >> 2);
     // coarsest levels the fused kernel cannot take (odd boxes, or an x-high half that is not 16-byte
-    // aligned): general kernels, in place on the corner box of the coefficient array; dst has not
-    // been written yet and serves as their ping-pong scratch
-    for (int k = 3; k >= nfused; k--) transform_level(src, dst, nx, ny, nz, k, true, st);
+    // aligned): general kernels, in place on the corner box of the coefficient array
+    for (int k = 3; k >= nfused; k--) transform_level(src, scratch, nx, ny, nz, k, true, st);
     for (int l = nfused - 1; l >= 0; l--) {
         const int n1 = nx >> l, n2 = ny >> l, n3 = nz >> l;
         const int m1 = n1 / 2, m2 = n2 / 2, m3 = n3 / 2;
@@ -1087,21 +1150,33 @@ void transform_inv_fused(double* src, double* dst, double* lowbuf, int nx, int n
         // the coarsest fused level finds its low-pass octant in the coefficient array itself
         if (l == nfused - 1) { lo = src; lo_sy = f_sy; lo_sz = f_sz; }
         else { lo = cbuf[l + 1]; lo_sy = (size_t)m1; lo_sz = (size_t)m1 * m2; }
-        double* o;
-        size_t o_sy, o_sz;
-        if (l == 0) { o = dst; o_sy = f_sy; o_sz = f_sz; }
-        else { o = cbuf[l]; o_sy = (size_t)n1; o_sz = (size_t)n1 * n2; }
         const int tiles = ((m1 + ITXP - 1) / ITXP) * ((m2 + ITYP - 1) / ITYP);
         const int zps = pick_zps(tiles, m3, 256 * (int)(160 * 1024 / LDS_INV));
         dim3 grid(tiles, (m3 + zps - 1) / zps);
 #ifdef WR_STAMP
-        hipLaunchKernelGGL(k_inv_fused, grid, dim3(INTHR), LDS_INV, st, src, f_sy, f_sz, lo, lo_sy, lo_sz, o, o_sy, o_sz, n1,
-                           n2, n3, zps, l == 0 ? g_stamp_buf : nullptr);
+#define WR_INV_STAMP_ARG , l == 0 ? g_stamp_buf : nullptr
 #else
-        hipLaunchKernelGGL(k_inv_fused, grid, dim3(INTHR), LDS_INV, st, src, f_sy, f_sz, lo, lo_sy, lo_sz, o, o_sy, o_sz, n1,
-                           n2, n3, zps);
+#define WR_INV_STAMP_ARG
 #endif
+        if (l > 0)
+            hipLaunchKernelGGL(k_inv_fused<double>, grid, dim3(INTHR), LDS_INV, st, src, f_sy, f_sz, lo, lo_sy, lo_sz, cbuf[l], (size_t)n1,
+                               (size_t)n1 * n2, n1, n2, n3, zps WR_INV_STAMP_ARG);
+        else
+            hipLaunchKernelGGL(k_inv_fused<TOUT>, grid, dim3(INTHR), LDS_INV, st, src, f_sy, f_sz, lo, lo_sy, lo_sz, dst, f_sy, f_sz, n1, n2,
+                               n3, zps WR_INV_STAMP_ARG);
+#undef WR_INV_STAMP_ARG
     }
+}
+
+void transform_inv_fused(double* src, double* dst, double* lowbuf, int nx, int ny, int nz, hipStream_t st)
+{
+    // dst has not been written yet when the general levels run: it serves as their ping-pong scratch
+    inv_fused<double>(src, dst, dst, lowbuf, nx, ny, nz, st);
+}
+
+void transform_inv_fused_f32(double* src, float* dst, double* scratch, double* lowbuf, int nx, int ny, int nz, hipStream_t st)
+{
+    inv_fused<float>(src, dst, scratch, lowbuf, nx, ny, nz, st);
 }
 
 }  // namespace wrk

@@ -362,9 +362,14 @@ struct PlaneHold {
 
 bool use_fused(int nx, int ny, int nz, int lvl);
 void transform_need(int nx, int ny, int nz, int lvl, SlotNeed* need);
-int run_transform(wr_ctx* c, Slot* s, double* d_fld, int nx, int ny, int nz, int lvl, double** out);
-int inverse_from_planes(wr_ctx* c, Slot* s, double* d_fld, int nx, int ny, int nz, int wlev, const wrk::DequantParams& p);
+// f32 (forward on the fused path only): the field is that fp32 array, d_fld is n doubles of scratch (may be f32's memory)
+int run_transform(wr_ctx* c, Slot* s, double* d_fld, int nx, int ny, int nz, int lvl, double** out, const float* f32 = nullptr);
+// out_f32 != nullptr: the reconstruction is wanted in fp32; *out_f32 = where it landed (the slot's field or scratch buffer;
+// d_fld is then work space of n doubles)
+int inverse_from_planes(wr_ctx* c, Slot* s, double* d_fld, int nx, int ny, int nz, int wlev, const wrk::DequantParams& p,
+                        float** out_f32 = nullptr);
 int read_minmax(wr_ctx* c, const double* d_x, size_t n, bool pending, double* mn, double* mx);
+int read_minmax(wr_ctx* c, const float* d_x, size_t n, bool pending, double* mn, double* mx);  // of an fp32 field
 struct ActiveCall {  // RAII: a codec call is inside the library
     DevPool* p;
     explicit ActiveCall(DevPool* pool) : p(pool) { p->active_calls++; }

@@ -21,9 +21,16 @@ void transform_level(double* fld, double* scratch, int nx, int ny, int nz, int k
 // partial[] needs 2*minmax_partials() doubles; result (min, max) lands in result[0..1] (device).
 int minmax_partials();
 void minmax(const double* x, size_t n, double* partial, double* result, hipStream_t st);
+void minmax(const float* x, size_t n, double* partial, double* result, hipStream_t st);  // of an fp32 field (8-byte aligned)
 // sign bit of the LAST element equal to zero (the reference's fmin scan keeps the last of
 // equal values): out[0] = index+1 of that element (0 if none).  Rare path (min == 0 only).
 void last_zero_index(const double* x, size_t n, unsigned long long* out, hipStream_t st);
+void last_zero_index(const float* x, size_t n, unsigned long long* out, hipStream_t st);
+
+// ---- fp32 fields on the paths that do not run the fused kernels (general transform, wtflag = 0): one pass each way.
+// dst[i] = (double)src[i] (exact) / dst[i] = (float)src[i] (round to nearest even, as the C cast).  Not in place.
+void widen_f32(const float* src, double* dst, size_t n, hipStream_t st);
+void narrow_f64(const double* src, float* dst, size_t n, hipStream_t st);
 
 // A quantized plane as the kernels see it: one array, or up to kPlaneChunks chunks of 2^shift bytes each (a large plane
 // of a call in flight lives in chunks that come and go as the host coder drains or fills it: wr_pipeline.cpp).  Byte i of
@@ -137,4 +144,12 @@ size_t fused_minmax_records(int nx, int ny, int nz);
 void transform_fwd_fused(double* src, double* dst, double* lowbuf, int nx, int ny, int nz, hipStream_t st,
                          double* mm_partial = nullptr, double* mm_result = nullptr);
 void transform_inv_fused(double* src, double* dst, double* lowbuf, int nx, int ny, int nz, hipStream_t st);
+// The same with an fp32 field: level 0 reads (forward) / writes (inverse) 4 bytes per sample and widens / narrows in the
+// kernel (k_fwd_fused_f32, k_inv_fused_f32); every other level and all arithmetic are those of the fp64 path, so the
+// coefficients are bit for bit those of the widened field and the reconstruction is (float) of the fp64 one.  src / dst
+// are 8-byte aligned.  `scratch` (n doubles) takes the general levels' ping-pong traffic that the fp64 forms put into
+// their fp64 src / dst; it may be the memory the fp32 src (forward) or dst (inverse) lies in.
+void transform_fwd_fused_f32(const float* src, double* scratch, double* dst, double* lowbuf, int nx, int ny, int nz, hipStream_t st,
+                             double* mm_partial = nullptr, double* mm_result = nullptr);
+void transform_inv_fused_f32(double* src, float* dst, double* scratch, double* lowbuf, int nx, int ny, int nz, hipStream_t st);
 }  // namespace wrk

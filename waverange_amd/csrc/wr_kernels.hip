@@ -341,19 +341,25 @@ __device__ inline void block_minmax(double lo, double hi, double* __restrict__ p
     }
 }
 
-__global__ __launch_bounds__(WR_RED_THREADS) void k_minmax(const double* __restrict__ x, size_t n,
+template <typename T> struct Pair;
+template <> struct Pair<double> { using type = double2; };
+template <> struct Pair<float> { using type = float2; };
+
+// (fp32: the samples widened, which changes no minimum, maximum or NaN)
+template <typename T>
+__global__ __launch_bounds__(WR_RED_THREADS) void k_minmax(const T* __restrict__ x, size_t n,
                                                            double* __restrict__ partial)
 {
     const double nan = __builtin_nan("");
     double lo = nan, hi = nan;
     const size_t n2 = n >> 1;
-    const double2* x2 = reinterpret_cast<const double2*>(x);  // hipMalloc'd base: 16-B aligned
+    const typename Pair<T>::type* x2 = reinterpret_cast<const typename Pair<T>::type*>(x);  // hipMalloc'd base: aligned
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (size_t)gridDim.x * blockDim.x) {
-        double2 v = x2[i];
-        mm_acc(v.x, lo, hi);
-        mm_acc(v.y, lo, hi);
+        const typename Pair<T>::type v = x2[i];
+        mm_acc((double)v.x, lo, hi);
+        mm_acc((double)v.y, lo, hi);
     }
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) mm_acc(x[n - 1], lo, hi);
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) mm_acc((double)x[n - 1], lo, hi);
     block_minmax(lo, hi, partial);
 }
 
@@ -377,25 +383,50 @@ static int red_grid(size_t n, int per_thread)
     return (int)g;
 }
 
-void minmax(const double* x, size_t n, double* partial, double* result, hipStream_t st)
+template <typename T>
+static void minmax_t(const T* x, size_t n, double* partial, double* result, hipStream_t st)
 {
     const int g = red_grid(n, 2);
-    hipLaunchKernelGGL(k_minmax, dim3(g), dim3(WR_RED_THREADS), 0, st, x, n, partial);
+    hipLaunchKernelGGL(k_minmax<T>, dim3(g), dim3(WR_RED_THREADS), 0, st, x, n, partial);
     hipLaunchKernelGGL(k_minmax_final, dim3(1), dim3(WR_RED_THREADS), 0, st, partial, g, result);
 }
+void minmax(const double* x, size_t n, double* partial, double* result, hipStream_t st) { minmax_t(x, n, partial, result, st); }
+void minmax(const float* x, size_t n, double* partial, double* result, hipStream_t st) { minmax_t(x, n, partial, result, st); }
 
-__global__ void k_last_zero(const double* __restrict__ x, size_t n, unsigned long long* out)
+template <typename T>
+__global__ void k_last_zero(const T* __restrict__ x, size_t n, unsigned long long* out)
 {
     unsigned long long best = 0;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        if (x[i] == 0.0) best = i + 1;  // grid-stride: i only grows, so the last hit is the largest
+        if (x[i] == (T)0) best = i + 1;  // grid-stride: i only grows, so the last hit is the largest
     if (best) atomicMax(out, best);
 }
 
-void last_zero_index(const double* x, size_t n, unsigned long long* out, hipStream_t st)
+template <typename T>
+static void last_zero_index_t(const T* x, size_t n, unsigned long long* out, hipStream_t st)
 {
     (void)hipMemsetAsync(out, 0, sizeof(unsigned long long), st);
-    hipLaunchKernelGGL(k_last_zero, dim3(red_grid(n, 1)), dim3(WR_RED_THREADS), 0, st, x, n, out);
+    hipLaunchKernelGGL(k_last_zero<T>, dim3(red_grid(n, 1)), dim3(WR_RED_THREADS), 0, st, x, n, out);
+}
+void last_zero_index(const double* x, size_t n, unsigned long long* out, hipStream_t st) { last_zero_index_t(x, n, out, st); }
+void last_zero_index(const float* x, size_t n, unsigned long long* out, hipStream_t st) { last_zero_index_t(x, n, out, st); }
+
+// fp32 fields where the fused kernels do not run (wr_codec.cpp): widened before the encoder, narrowed after the decoder
+__global__ void k_widen_f32(const float* __restrict__ src, double* __restrict__ dst, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = (double)src[i];
+}
+__global__ void k_narrow_f64(const double* __restrict__ src, float* __restrict__ dst, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = (float)src[i];
+}
+void widen_f32(const float* src, double* dst, size_t n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_widen_f32, dim3(red_grid(n, 1)), dim3(WR_RED_THREADS), 0, st, src, dst, n);
+}
+void narrow_f64(const double* src, float* dst, size_t n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_narrow_f64, dim3(red_grid(n, 1)), dim3(WR_RED_THREADS), 0, st, src, dst, n);
 }
 
 // =====================================================================================

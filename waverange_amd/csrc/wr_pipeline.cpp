@@ -675,12 +675,14 @@ void transform_need(int nx, int ny, int nz, int lvl, SlotNeed* need)
 
 // Forward (lvl > 0) or inverse (lvl < 0) transform of d_fld.  The fused path is out of place: the result
 // lands in the slot's scratch buffer and *out points there; the general path works in place.
-int run_transform(wr_ctx* c, Slot* s, double* d_fld, int nx, int ny, int nz, int lvl, double** out)
+int run_transform(wr_ctx* c, Slot* s, double* d_fld, int nx, int ny, int nz, int lvl, double** out, const float* f32)
 {
     *out = d_fld;
+    if (f32 && !(lvl > 0 && use_fused(nx, ny, nz, lvl))) return fail(WR_ERR_ARG, "internal: an fp32 field outside the fused forward transform");
     if (use_fused(nx, ny, nz, lvl)) {
         if (const char* why = wrk::fused_prepare()) return fail(WR_ERR_HIP, why);
-        if (lvl > 0) wrk::transform_fwd_fused(d_fld, s->scratch, s->lowbuf, nx, ny, nz, c->stream);
+        if (f32) wrk::transform_fwd_fused_f32(f32, d_fld, s->scratch, s->lowbuf, nx, ny, nz, c->stream);
+        else if (lvl > 0) wrk::transform_fwd_fused(d_fld, s->scratch, s->lowbuf, nx, ny, nz, c->stream);
         else wrk::transform_inv_fused(d_fld, s->scratch, s->lowbuf, nx, ny, nz, c->stream);
         *out = s->scratch;
     } else {
@@ -692,7 +694,10 @@ int run_transform(wr_ctx* c, Slot* s, double* d_fld, int nx, int ny, int nz, int
 // decoder back end: acc = sum of planes, then the inverse transform, result in d_fld.
 // Fused path: accumulate into the scratch buffer and transform out of place into d_fld.
 // Records ev_a / ev_b / ev_c around the two stages (for the timings).
-int inverse_from_planes(wr_ctx* c, Slot* s, double* d_fld, int nx, int ny, int nz, int wlev, const wrk::DequantParams& p)
+// fp32 output: the fused inverse narrows on its last store into d_fld's memory; the general path narrows d_fld into the
+// scratch buffer, which it is done with by then (one extra pass, not a hot path).
+int inverse_from_planes(wr_ctx* c, Slot* s, double* d_fld, int nx, int ny, int nz, int wlev, const wrk::DequantParams& p,
+                        float** out_f32)
 {
     const size_t n = (size_t)nx * ny * nz;
     const bool fused = wlev == 4 && use_fused(nx, ny, nz, -4);
@@ -700,8 +705,18 @@ int inverse_from_planes(wr_ctx* c, Slot* s, double* d_fld, int nx, int ny, int n
     HIPCHK(hipEventRecord(c->ev_a, c->stream));
     wrk::dequant_accum(fused ? s->scratch : d_fld, n, p, c->stream);
     HIPCHK(hipEventRecord(c->ev_b, c->stream));
-    if (fused) wrk::transform_inv_fused(s->scratch, d_fld, s->lowbuf, nx, ny, nz, c->stream);
-    else wrk::transform(d_fld, s->scratch, nx, ny, nz, -wlev, c->stream);
+    if (fused && out_f32) {
+        *out_f32 = reinterpret_cast<float*>(d_fld);
+        wrk::transform_inv_fused_f32(s->scratch, *out_f32, d_fld, s->lowbuf, nx, ny, nz, c->stream);
+    } else if (fused) {
+        wrk::transform_inv_fused(s->scratch, d_fld, s->lowbuf, nx, ny, nz, c->stream);
+    } else {
+        wrk::transform(d_fld, s->scratch, nx, ny, nz, -wlev, c->stream);
+        if (out_f32) {
+            *out_f32 = reinterpret_cast<float*>(s->scratch);
+            wrk::narrow_f64(d_fld, *out_f32, n, c->stream);
+        }
+    }
     HIPCHK(hipEventRecord(c->ev_c, c->stream));
     return WR_OK;
 }
@@ -712,7 +727,8 @@ int inverse_from_planes(wr_ctx* c, Slot* s, double* d_fld, int nx, int ny, int n
 // `pending` = a fused kernel has already been enqueued that stores the reduction into h_result[0..1].
 // Waits on an event recorded right behind the read-back, so kernels enqueued afterwards do not
 // delay the answer.
-int read_minmax(wr_ctx* c, const double* d_x, size_t n, bool pending, double* mn, double* mx)
+template <typename T>
+static int read_minmax_t(wr_ctx* c, const T* d_x, size_t n, bool pending, double* mn, double* mx)
 {
     // the final reduction kernel stores min and max straight into pinned host memory: no copy command
     if (!pending) wrk::minmax(d_x, n, c->d_partial, c->h_result_dev, c->stream);
@@ -725,14 +741,18 @@ int read_minmax(wr_ctx* c, const double* d_x, size_t n, bool pending, double* mn
         HIPCHK(hipMemcpyAsync(hidx, c->d_idx, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         if (*hidx) {
-            HIPCHK(hipMemcpyAsync(c->h_result + 2, d_x + (*hidx - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(c->h_result + 2, d_x + (*hidx - 1), sizeof(T), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
-            lo = c->h_result[2];
+            T z;
+            memcpy(&z, c->h_result + 2, sizeof z);
+            lo = (double)z;
         }
     }
     *mn = lo; *mx = hi;
     return WR_OK;
 }
+int read_minmax(wr_ctx* c, const double* d_x, size_t n, bool pending, double* mn, double* mx) { return read_minmax_t(c, d_x, n, pending, mn, mx); }
+int read_minmax(wr_ctx* c, const float* d_x, size_t n, bool pending, double* mn, double* mx) { return read_minmax_t(c, d_x, n, pending, mn, mx); }
 
 // The shader clock of an idle GPU is down, and it takes ~30 ms of load to come all the way up -- longer than a whole
 // kernel stage; the transforms (half VALU issue) run 20-30 % slower at the start of a stage than back to back
