@@ -434,6 +434,102 @@ int main() {
             if (got2[1] != n || memcmp(sink.data(), p[0].data(), n)) { printf("served windows: decoder failed\n"); return 1; }
         }
     }
+    // PlaneJob, whoever codes it: the same jobs built three times -- whole planes, planes through windows, streams held to
+    // dst_limit by their histograms (one plane's are wrong) -- and run by encode_planes / decode_planes (fed from the jobs),
+    // run_jobs and pool_run must give the same bytes and results.  Planes of mixed lengths, more than one symbol loop holds;
+    // exact-size buffers and windows allocated afresh, so ASan sees any access outside them.
+    {
+        struct Win {
+            const uint8_t* plane; uint8_t* out; size_t chunk; uint8_t* cur; size_t cur_first, cur_count;
+            static uint8_t* fn(void* u, size_t first, size_t* count)
+            {
+                Win* w = (Win*)u;
+                if (w->out && w->cur) memcpy(w->out + w->cur_first, w->cur, w->cur_count);
+                delete[] w->cur; w->cur = nullptr;
+                if (*count == 0) return nullptr;
+                const size_t c = *count < w->chunk ? *count : w->chunk;
+                w->cur = new uint8_t[c]; w->cur_first = first; w->cur_count = c;
+                if (w->plane) memcpy(w->cur, w->plane + first, c);
+                *count = c;
+                return w->cur;
+            }
+        };
+        const int count = 6, victim = 3, runs = 3;
+        std::vector<size_t> n(count), ref_len(count);
+        std::vector<std::vector<uint8_t>> p(count), ref(count);
+        std::vector<std::vector<uint16_t>> hist(count);
+        for (int k = 0; k < count; k++) {
+            n[k] = k == 0 ? 7 : (size_t)60000 * k + 311 * (k % 3);
+            p[k].resize(n[k]);
+            for (size_t i = 0; i < n[k]; i++) { unsigned r = rnd(); p[k][i] = k % 3 == 0 ? r & 255 : k % 3 == 1 ? ((r & 15) ? 254 : 255) : (uint8_t)(100 + (r & 31)); }
+            hist[k].assign((n[k] / 60000 + 1) * 256, 0);
+            for (size_t i = 0; i < n[k]; i++) hist[k][(i / 60000) * 256 + p[k][i]]++;
+            std::vector<uint8_t> o(wrrc::encode_bound(n[k]));
+            ref_len[k] = wrrc::encode_plane(p[k].data(), n[k], o.data(), nullptr);
+            ref[k].assign(o.begin(), o.begin() + ref_len[k]);
+        }
+        hist[victim][2 * 256 + p[victim][2 * 60000]]++;  // block 2 of the victim: one count too many
+        wrrc::pool_configure(3, 4);
+        for (int variant = 0; variant < 3; variant++) {
+            const bool windowed = variant == 1, limited = variant == 2;
+            for (int decode = 0; decode < 2; decode++) {
+                std::vector<std::vector<wrrc::PlaneJob>> jobs(runs, std::vector<wrrc::PlaneJob>(count));
+                std::vector<std::vector<std::vector<uint8_t>>> out(runs, std::vector<std::vector<uint8_t>>(count));
+                std::vector<std::vector<Win>> win(runs, std::vector<Win>(count));
+                std::vector<std::vector<wrrc::PlaneWindow>> io(runs, std::vector<wrrc::PlaneWindow>(count));
+                for (int r = 0; r < runs; r++) for (int k = 0; k < count; k++) {
+                    wrrc::PlaneJob& j = jobs[r][k];
+                    j.kind = decode ? wrrc::PlaneJob::kDecode : wrrc::PlaneJob::kEncode;
+                    j.n = n[k];
+                    out[r][k].assign(decode ? n[k] : limited ? wrrc::encode_bound_hist(hist[k].data(), n[k]) + wrrc::kFailedBlockSlack : wrrc::encode_bound(n[k]), 0xEE);
+                    out[r][k].shrink_to_fit();
+                    if (decode) { j.src = ref[k].data(); j.src_len = ref_len[k]; j.dst = out[r][k].data(); }
+                    else { j.src = p[k].data(); j.dst = out[r][k].data(); }
+                    if (limited && !decode) { j.hist = hist[k].data(); j.dst_limit = wrrc::encode_bound_hist(hist[k].data(), n[k]); }
+                    if (windowed) {
+                        win[r][k] = Win{decode ? nullptr : p[k].data(), decode ? out[r][k].data() : nullptr, (size_t)60000 * (1 + k % 2), nullptr, 0, 0};
+                        io[r][k] = wrrc::PlaneWindow{Win::fn, &win[r][k]};
+                        j.io = &io[r][k];
+                        if (decode) j.dst = nullptr; else j.src = nullptr;
+                    }
+                }
+                for (wrrc::PlaneJob& j : jobs[0]) {  // the array entry points, one job at a time (the lengths differ)
+                    uint8_t* dst = j.dst;
+                    if (decode) wrrc::decode_planes(1, &j.src, &j.src_len, &dst, j.n, &j.result, &j.io);
+                    else wrrc::encode_planes(1, &j.src, j.n, &dst, &j.hist, &j.result, &j.io, &j.dst_limit);
+                }
+                if (!wrrc::run_jobs(jobs[1].data(), count)) { printf("run_jobs refused jobs of one kind\n"); return 1; }
+                for (int k = 1; k < count; k++)
+                    if (jobs[1][k].seconds != jobs[1][0].seconds || !(jobs[1][0].seconds >= 0)) { printf("run_jobs: seconds are not the call's\n"); return 1; }
+                if (!wrrc::pool_run(jobs[2].data(), count)) { printf("pool_run refused\n"); return 1; }
+                for (int r = 0; r < runs; r++) for (int k = 0; k < count; k++) {
+                    delete[] win[r][k].cur; win[r][k].cur = nullptr;
+                    const size_t got = jobs[r][k].result;
+                    const bool fails = limited && !decode && k == victim;
+                    const bool ok = fails ? got == (size_t)-1
+                                   : decode ? got == n[k] && !memcmp(out[r][k].data(), p[k].data(), n[k])
+                                            : got == ref_len[k] && !memcmp(out[r][k].data(), ref[k].data(), ref_len[k]);
+                    if (!ok || got != jobs[0][k].result) {
+                        printf("PlaneJob: %s differs variant=%d run=%d k=%d result=%zu\n", decode ? "decode" : "encode", variant, r, k, got); return 1;
+                    }
+                }
+            }
+        }
+        // a batch of mixed kinds is refused and left as it was; a stopped pool refuses too
+        std::vector<uint8_t> out(wrrc::encode_bound(n[2]), 0xEE), back(n[2], 0xEE);
+        wrrc::PlaneJob mixed[2];
+        mixed[0].kind = wrrc::PlaneJob::kEncode; mixed[0].src = p[2].data(); mixed[0].n = n[2]; mixed[0].dst = out.data();
+        mixed[1].kind = wrrc::PlaneJob::kDecode; mixed[1].src = ref[2].data(); mixed[1].src_len = ref_len[2]; mixed[1].n = n[2]; mixed[1].dst = back.data();
+        for (wrrc::PlaneJob& j : mixed) { j.result = 777; j.seconds = -1; }
+        const bool refused = !wrrc::run_jobs(mixed, 2);
+        for (uint8_t b : out) if (b != 0xEE) { printf("mixed kinds: the encoder wrote\n"); return 1; }
+        for (uint8_t b : back) if (b != 0xEE) { printf("mixed kinds: the decoder wrote\n"); return 1; }
+        if (!refused || mixed[0].result != 777 || mixed[1].result != 777 || mixed[0].seconds != -1 || mixed[1].seconds != -1) {
+            printf("mixed kinds: run_jobs did not refuse the batch untouched\n"); return 1;
+        }
+        wrrc::pool_configure(0, 0);
+        if (wrrc::pool_run(mixed, 1) || mixed[0].result != 777) { printf("pool_run: a stopped pool took jobs\n"); return 1; }
+    }
     printf("range coder sanitizer run OK\n");
     return 0;
 }

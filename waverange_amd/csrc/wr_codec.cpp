@@ -333,8 +333,6 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
     const size_t hist_per_plane = (n / wrrc::kBlock + 1) * 256;
     DevPool* const pool = c->pool;
 
-    size_t lens[WR_NLAYMAX] = {0};
-    double coder_s[WR_NLAYMAX] = {0};
     int copy_failed[WR_NLAYMAX] = {0};
     std::string logs[WR_NLAYMAX];
     Sem sem(encoder_threads());
@@ -349,9 +347,8 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
     // their number is known and each thread codes its group with the symbol loops interleaved.
     const bool pooled = wrrc::pool_threads() > 0;  // the process-wide coder pool codes the planes (wr_set_coder_pool)
     const bool per_plane = !pooled && encoder_threads() >= WR_NLAYMAX;
-    wrrc::PlaneJob jobs[WR_NLAYMAX];
+    wrrc::PlaneJob jobs[WR_NLAYMAX];  // what coding plane l means, whoever codes it
     wrrc::JobBatch batch;
-    unsigned pool_mask = 0;  // planes the pool took
     // Where a plane's coder writes.  The reference codes every plane into a buffer of its own and copies the streams
     // together (wrappers.cpp:412-427); here the planes are coded at the same time, so a plane's place in data_enc is not
     // known when its coder starts -- but an upper bound on the length of every plane before it is, from their block
@@ -381,25 +378,23 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
         }
         return plane_out[k];
     };
-    auto code_group = [&](unsigned l0, unsigned l1) {
+    // jobs[k] once plane k's histograms are on the host; false (copy_failed[k]) if the plane cannot be coded
+    auto prepare_job = [&](unsigned k) -> bool {
+        if (xfer_wait(&c->x_plane[k]) != WR_OK) copy_failed[k] = 1;
+        uint8_t* const dst = place_plane(k);
+        if (!dst || copy_failed[k]) { copy_failed[k] = 1; return false; }
+        wrrc::PlaneJob& j = jobs[k];
+        j.kind = wrrc::PlaneJob::kEncode;
+        j.io = &c->ps[k].io; j.dst = dst; j.n = n; j.hist = c->h_hist + k * hist_per_plane; j.dst_limit = est_len[k];
+        return true;
+    };
+    // a thread of this call codes planes l0 .. l1-1 (prepare: their jobs are not built yet)
+    auto code_group = [&](unsigned l0, unsigned l1, bool prepare) {
         (void)hipSetDevice(dev);
-        for (unsigned l = l0; l < l1; l++)
-            if (xfer_wait(&c->x_plane[l]) != WR_OK) copy_failed[l] = 1;
-        for (unsigned l = l0; l < l1; l++)
-            if (!place_plane(l)) { copy_failed[l] = 1; return; }
+        for (unsigned l = l0; l < l1 && prepare; l++)
+            if (!prepare_job(l)) return;
         sem.acquire();
-        const double t = now();
-        const uint8_t* syms[WR_NLAYMAX];
-        uint8_t* outs[WR_NLAYMAX];
-        const uint16_t* hs[WR_NLAYMAX];
-        const wrrc::PlaneWindow* ios[WR_NLAYMAX];
-        size_t limits[WR_NLAYMAX];
-        for (unsigned l = l0; l < l1; l++) {
-            syms[l - l0] = nullptr; outs[l - l0] = plane_out[l]; hs[l - l0] = c->h_hist + l * hist_per_plane; ios[l - l0] = &c->ps[l].io;
-            limits[l - l0] = est_len[l];
-        }
-        wrrc::encode_planes((int)(l1 - l0), syms, n, outs, hs, lens + l0, ios, limits);
-        for (unsigned l = l0; l < l1; l++) coder_s[l] = now() - t;
+        wrrc::run_jobs(jobs + l0, (int)(l1 - l0));
         sem.release();
     };
 
@@ -455,15 +450,10 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
         unsigned ready = 0;   // planes whose histograms and first window are on their way to the host (plane_ready has run)
         auto submit_plane = [&](unsigned k) {
             if (handed >> k & 1) return;
-            if (xfer_wait(&c->x_plane[k]) != WR_OK) { copy_failed[k] = 1; return; }
-            uint8_t* const dst = place_plane(k);
-            if (!dst || copy_failed[k]) { copy_failed[k] = 1; return; }
+            if (!prepare_job(k)) return;
             handed |= 1u << k;
-            wrrc::PlaneJob& j = jobs[k];
-            j.kind = wrrc::PlaneJob::kEncode;
-            j.src = nullptr; j.io = &c->ps[k].io; j.dst = dst; j.n = n; j.hist = c->h_hist + k * hist_per_plane; j.dst_limit = est_len[k];
-            if (wrrc::pool_submit(&j, 1, &batch)) pool_mask |= 1u << k;
-            else workers.v.emplace_back(code_group, k, k + 1);  // the pool was stopped meanwhile: a thread of this call codes the plane
+            if (!wrrc::pool_submit(&jobs[k], 1, &batch))
+                workers.v.emplace_back(code_group, k, k + 1, false);  // the pool was stopped meanwhile: a thread of this call codes the plane
         };
         auto plane_ready = [&](unsigned l, bool) -> int {
             // plane l and its histograms are complete on the device: the histograms go to pinned host memory, the
@@ -474,7 +464,7 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
             if (int r = xfer_start(c, &c->x_plane[l], &pc, 1, kDown)) return r;
             plane_prefetch(c, (int)l);
             planes_started = l + 1;
-            if (per_plane) workers.v.emplace_back(code_group, l, l + 1);
+            if (per_plane) workers.v.emplace_back(code_group, l, l + 1, true);
             // the plane before this one is handed to the pool now (its histograms have had a quantizer launch's time to
             // arrive): its coder drains it while the stage goes on -- what a later plane of this call may be waiting for
             // if device memory is short (plane_prepare)
@@ -529,14 +519,13 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
         wrrc::pool_wait(&batch);
         return fail(WR_ERR_ARG, std::string("encode: ") + e.what());
     }
-    if (pooled) {
+    if (pooled)
         wrrc::pool_wait(&batch);
-        for (unsigned l = 0; l < WR_NLAYMAX; l++) if (pool_mask >> l & 1) { lens[l] = jobs[l].result; coder_s[l] = jobs[l].seconds; }
-    } else if (rc == WR_OK && !per_plane && info->nlay) {
+    else if (rc == WR_OK && !per_plane && info->nlay) {
         try {
             const unsigned groups = std::min<unsigned>(info->nlay, (unsigned)encoder_threads());
             for (unsigned g = 0; g < groups; g++)
-                workers.v.emplace_back(code_group, g * info->nlay / groups, (g + 1) * info->nlay / groups);
+                workers.v.emplace_back(code_group, g * info->nlay / groups, (g + 1) * info->nlay / groups, true);
         } catch (const std::exception& e) {
             workers.join();
             return fail(WR_ERR_ARG, std::string("encode: ") + e.what());
@@ -546,35 +535,35 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
     if (rc) return rc;
     for (unsigned l = 0; l < info->nlay; l++) {
         if (copy_failed[l] || c->ps[l].err) return fail(WR_ERR_HIP, "download of plane " + std::to_string(l) + " failed");
-        if (lens[l] == (size_t)-1)  // (a refused window sets ps[l].err as well; what is left: histograms that are not the plane's)
+        if (jobs[l].result == (size_t)-1)  // (a refused window sets ps[l].err as well; what is left: histograms that are not the plane's)
             return fail(WR_ERR_HIP, "internal: the coder gave plane " + std::to_string(l) + " up (its block histograms are not its symbols')");
         local.d2h_ms += (float)(c->x_plane[l].ms + c->ps[l].copy_ms);
-        if (verbose()) logs[l] = plane_log(c, (int)l, n, info, true, lens[l]);  // wrappers.cpp:401-409, 430
+        if (verbose()) logs[l] = plane_log(c, (int)l, n, info, true, jobs[l].result);  // wrappers.cpp:401-409, 430
     }
     const double t_coded = now();
     // concatenate the plane streams (wrappers.cpp:412-427)
     size_t total = 0, offs[WR_NLAYMAX] = {0};
     for (unsigned l = 0; l < info->nlay; l++) {
         offs[l] = total;
-        total += lens[l];
-        info->len_enc_vec[l] = lens[l];
-        local.plane_coder_s[l] = coder_s[l];
-        if (coder_s[l] > local.rangecoder) local.rangecoder = coder_s[l];
+        total += jobs[l].result;
+        info->len_enc_vec[l] = jobs[l].result;
+        local.plane_coder_s[l] = jobs[l].seconds;
+        if (jobs[l].seconds > local.rangecoder) local.rangecoder = jobs[l].seconds;
     }
     for (unsigned l = 0; l < info->nlay; l++)  // (cannot happen: the bound is rigorous; if it did, a neighbour's bytes are gone)
-        if (lens[l] > est_len[l]) return fail(WR_ERR_OVERFLOW, "internal: plane " + std::to_string(l) + " outgrew the bound computed from its histograms");
+        if (jobs[l].result > est_len[l]) return fail(WR_ERR_OVERFLOW, "internal: plane " + std::to_string(l) + " outgrew the bound computed from its histograms");
     if (total > cap) return fail(WR_ERR_OVERFLOW, "Error: encoded array is too large. Use larger SAFETY_BUFFER_FACTOR");
     // close the gaps: plane l moves down by what the planes before it stayed below their bounds.  In plane order, one after
     // the other: plane l's new place may still hold the end of plane l-1's old one.
     for (unsigned l = 0; l < info->nlay; l++) {
-        if (!direct[l]) memcpy(data_enc + offs[l], c->enc_buf[l], lens[l]);
-        else if (est_off[l] != offs[l]) memmove(data_enc + offs[l], data_enc + est_off[l], lens[l]);
+        if (!direct[l]) memcpy(data_enc + offs[l], c->enc_buf[l], jobs[l].result);
+        else if (est_off[l] != offs[l]) memmove(data_enc + offs[l], data_enc + est_off[l], jobs[l].result);
     }
     // (a plane that went through c->enc_buf: hand its pages back, a noise plane's gigabyte would otherwise stay resident in
     // every context that once coded one)
     for (unsigned l = 0; l < info->nlay; l++) {
         if (direct[l]) continue;
-        const uintptr_t a = ((uintptr_t)c->enc_buf[l] + 4095) & ~(uintptr_t)4095, e = ((uintptr_t)c->enc_buf[l] + lens[l]) & ~(uintptr_t)4095;
+        const uintptr_t a = ((uintptr_t)c->enc_buf[l] + 4095) & ~(uintptr_t)4095, e = ((uintptr_t)c->enc_buf[l] + jobs[l].result) & ~(uintptr_t)4095;
         if (e > a && e - a >= ((size_t)64 << 20)) (void)madvise(reinterpret_cast<void*>(a), e - a, MADV_DONTNEED);
     }
     if (verbose())
@@ -676,8 +665,11 @@ int decode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_in
     transform_need(nx, ny, nz, info->wlev ? -kWavLvl : 0, &need);
     if (fld.host || fld.host_f32) need.field_elems = n;
 
-    size_t got[WR_NLAYMAX] = {0};
-    double coder_s[WR_NLAYMAX] = {0};
+    wrrc::PlaneJob jobs[WR_NLAYMAX];  // what decoding plane l means, whoever decodes it
+    for (int l = 0; l < nlay && host_half; l++) {
+        jobs[l].kind = wrrc::PlaneJob::kDecode;
+        jobs[l].src = data_enc + off[l]; jobs[l].src_len = info->len_enc_vec[l]; jobs[l].io = &c->ps[l].io; jobs[l].n = n;
+    }
     Sem sem(coder_threads());
     // one thread per plane, or (wr_set_threads) fewer threads with their planes interleaved, or the process-wide
     // coder pool (wr_set_coder_pool), whose workers interleave planes of several fields
@@ -687,19 +679,11 @@ int decode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_in
     try {
         SlotLease slot;
         if (pooled && host_half) {
-            wrrc::PlaneJob jobs[WR_NLAYMAX];
             wrrc::JobBatch batch;
-            for (int l = 0; l < nlay; l++) {
-                jobs[l].kind = wrrc::PlaneJob::kDecode;
-                jobs[l].src = data_enc + off[l]; jobs[l].src_len = info->len_enc_vec[l]; jobs[l].dst = nullptr; jobs[l].io = &c->ps[l].io; jobs[l].n = n;
-            }
             const bool queued = wrrc::pool_submit(jobs, nlay, &batch);
             if (gate.owns_lock()) gate.unlock();  // the next decode may look at the queues now
-            if (queued) {
-                wrrc::pool_wait(&batch);
-                for (int l = 0; l < nlay; l++) { got[l] = jobs[l].result; coder_s[l] = jobs[l].seconds; }
-            } else
-                pooled = false;  // the pool was stopped meanwhile: this call's own threads decode the planes
+            if (queued) wrrc::pool_wait(&batch);
+            else pooled = false;  // the pool was stopped meanwhile: this call's own threads decode the planes
         }
         if (gate.owns_lock()) gate.unlock();
         const int groups = (pooled || !host_half) ? 0 : std::min(nlay, coder_threads());
@@ -713,21 +697,15 @@ int decode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_in
                 workers.v.emplace_back([&, g]() {
                     const int l0 = g * nlay / groups, l1 = (g + 1) * nlay / groups;
                     sem.acquire();
-                    const double t = now();
-                    const uint8_t* ins[WR_NLAYMAX];
-                    uint8_t* syms[WR_NLAYMAX];
-                    const wrrc::PlaneWindow* ios[WR_NLAYMAX];
-                    for (int l = l0; l < l1; l++) { ins[l - l0] = data_enc + off[l]; syms[l - l0] = nullptr; ios[l - l0] = &c->ps[l].io; }
-                    wrrc::decode_planes(l1 - l0, ins, info->len_enc_vec + l0, syms, n, got + l0, ios);
-                    for (int l = l0; l < l1; l++) coder_s[l] = now() - t;
+                    wrrc::run_jobs(jobs + l0, l1 - l0);
                     sem.release();
                 });
         }
         int bad = -1;
         for (int l = 0; l < nlay && host_half; l++) {
-            if (got[l] != n) bad = l;
-            local.plane_coder_s[l] = coder_s[l];
-            if (coder_s[l] > local.rangecoder) local.rangecoder = coder_s[l];
+            if (jobs[l].result != n) bad = l;
+            local.plane_coder_s[l] = jobs[l].seconds;
+            if (jobs[l].seconds > local.rangecoder) local.rangecoder = jobs[l].seconds;
         }
         if (bad >= 0) return fail(WR_ERR_STREAM, "plane " + std::to_string(bad) + ": stream does not decode to nx*ny*nz symbols");
         if (host_half) {

@@ -38,10 +38,8 @@ int wr_range_encode_pool(int count, const unsigned char* const* sym, const size_
     if (wrrc::pool_threads() < 1) return fail(WR_ERR_ARG, "the coder pool is not running (wr_set_coder_pool)");
     if (count < 1) return WR_OK;
     std::vector<wrrc::PlaneJob> jobs((size_t)count);
-    wrrc::JobBatch batch;
     for (int k = 0; k < count; k++) { jobs[k].kind = wrrc::PlaneJob::kEncode; jobs[k].src = sym[k]; jobs[k].n = n[k]; jobs[k].dst = out[k]; }
-    if (!wrrc::pool_submit(jobs.data(), count, &batch)) return fail(WR_ERR_ARG, "the coder pool is not running (wr_set_coder_pool)");
-    wrrc::pool_wait(&batch);
+    if (!wrrc::pool_run(jobs.data(), count)) return fail(WR_ERR_ARG, "the coder pool is not running (wr_set_coder_pool)");
     for (int k = 0; k < count; k++) lens[k] = jobs[k].result;
     return WR_OK;
 }
@@ -52,12 +50,10 @@ int wr_range_decode_pool(int count, const unsigned char* const* in, const size_t
     if (wrrc::pool_threads() < 1) return fail(WR_ERR_ARG, "the coder pool is not running (wr_set_coder_pool)");
     if (count < 1) return WR_OK;
     std::vector<wrrc::PlaneJob> jobs((size_t)count);
-    wrrc::JobBatch batch;
     for (int k = 0; k < count; k++) {
         jobs[k].kind = wrrc::PlaneJob::kDecode; jobs[k].src = in[k]; jobs[k].src_len = len[k]; jobs[k].dst = sym[k]; jobs[k].n = n[k];
     }
-    if (!wrrc::pool_submit(jobs.data(), count, &batch)) return fail(WR_ERR_ARG, "the coder pool is not running (wr_set_coder_pool)");
-    wrrc::pool_wait(&batch);
+    if (!wrrc::pool_run(jobs.data(), count)) return fail(WR_ERR_ARG, "the coder pool is not running (wr_set_coder_pool)");
     for (int k = 0; k < count; k++) produced[k] = jobs[k].result;
     return WR_OK;
 }
@@ -114,18 +110,15 @@ int wr_range_encode_windowed(int mode, int count, const unsigned char* const* sy
     std::vector<const wrrc::PlaneWindow*> io((size_t)count);
     std::vector<size_t> ns((size_t)count, n);
     std::vector<const unsigned char*> none((size_t)count, nullptr);
-    for (int k = 0; k < count; k++) { w[k].plane = sym[k]; w[k].init(n, chunk, false); io[k] = &w[k].io; }
-    if (mode == 0) wrrc::encode_planes(count, none.data(), n, out, nullptr, lens, io.data());
-    else if (mode == 2) { if (!wrrc::encode_planes_vec(count, none.data(), ns.data(), out, lens, io.data())) return fail(WR_ERR_UNSUPPORTED, "this CPU has no AVX-512"); }
-    else {
-        if (wrrc::pool_threads() < 1) return fail(WR_ERR_ARG, "the coder pool is not running (wr_set_coder_pool)");
-        std::vector<wrrc::PlaneJob> jobs((size_t)count);
-        wrrc::JobBatch batch;
-        for (int k = 0; k < count; k++) { jobs[k].kind = wrrc::PlaneJob::kEncode; jobs[k].n = n; jobs[k].dst = out[k]; jobs[k].io = io[k]; }
-        if (!wrrc::pool_submit(jobs.data(), count, &batch)) return fail(WR_ERR_ARG, "the coder pool is not running (wr_set_coder_pool)");
-        wrrc::pool_wait(&batch);
-        for (int k = 0; k < count; k++) lens[k] = jobs[k].result;
+    std::vector<wrrc::PlaneJob> jobs((size_t)count);
+    for (int k = 0; k < count; k++) {
+        w[k].plane = sym[k]; w[k].init(n, chunk, false); io[k] = &w[k].io;
+        jobs[k].kind = wrrc::PlaneJob::kEncode; jobs[k].n = n; jobs[k].dst = out[k]; jobs[k].io = io[k];
     }
+    if (mode == 2) return wrrc::encode_planes_vec(count, none.data(), ns.data(), out, lens, io.data()) ? WR_OK : fail(WR_ERR_UNSUPPORTED, "this CPU has no AVX-512");
+    if (mode == 0) wrrc::run_jobs(jobs.data(), count);
+    else if (!wrrc::pool_run(jobs.data(), count)) return fail(WR_ERR_ARG, "the coder pool is not running (wr_set_coder_pool)");
+    for (int k = 0; k < count; k++) lens[k] = jobs[k].result;
     return WR_OK;
 }
 
@@ -138,20 +131,15 @@ int wr_range_decode_windowed(int mode, int count, const unsigned char* const* in
     std::vector<const wrrc::PlaneWindow*> io((size_t)count);
     std::vector<size_t> ns((size_t)count, n);
     std::vector<unsigned char*> none((size_t)count, nullptr);
-    for (int k = 0; k < count; k++) { w[k].out = sym[k]; w[k].init(n, chunk, true); io[k] = &w[k].io; }
-    if (mode == 0) wrrc::decode_planes(count, in, len, none.data(), n, produced, io.data());
-    else if (mode == 2) { if (!wrrc::decode_planes_vec(count, in, len, none.data(), ns.data(), produced, io.data())) return fail(WR_ERR_UNSUPPORTED, "this CPU has no AVX-512"); }
-    else {
-        if (wrrc::pool_threads() < 1) return fail(WR_ERR_ARG, "the coder pool is not running (wr_set_coder_pool)");
-        std::vector<wrrc::PlaneJob> jobs((size_t)count);
-        wrrc::JobBatch batch;
-        for (int k = 0; k < count; k++) {
-            jobs[k].kind = wrrc::PlaneJob::kDecode; jobs[k].src = in[k]; jobs[k].src_len = len[k]; jobs[k].n = n; jobs[k].io = io[k];
-        }
-        if (!wrrc::pool_submit(jobs.data(), count, &batch)) return fail(WR_ERR_ARG, "the coder pool is not running (wr_set_coder_pool)");
-        wrrc::pool_wait(&batch);
-        for (int k = 0; k < count; k++) produced[k] = jobs[k].result;
+    std::vector<wrrc::PlaneJob> jobs((size_t)count);
+    for (int k = 0; k < count; k++) {
+        w[k].out = sym[k]; w[k].init(n, chunk, true); io[k] = &w[k].io;
+        jobs[k].kind = wrrc::PlaneJob::kDecode; jobs[k].src = in[k]; jobs[k].src_len = len[k]; jobs[k].n = n; jobs[k].io = io[k];
     }
+    if (mode == 2) return wrrc::decode_planes_vec(count, in, len, none.data(), ns.data(), produced, io.data()) ? WR_OK : fail(WR_ERR_UNSUPPORTED, "this CPU has no AVX-512");
+    if (mode == 0) wrrc::run_jobs(jobs.data(), count);
+    else if (!wrrc::pool_run(jobs.data(), count)) return fail(WR_ERR_ARG, "the coder pool is not running (wr_set_coder_pool)");
+    for (int k = 0; k < count; k++) produced[k] = jobs[k].result;
     return WR_OK;
 }
 

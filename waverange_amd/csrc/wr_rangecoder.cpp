@@ -645,16 +645,14 @@ bool encode_planes_vec(int count, const uint8_t* const* sym, const size_t* n, ui
 void encode_planes(int count, const uint8_t* const* sym, size_t n, uint8_t* const* out, const uint16_t* const* hists, size_t* lens,
                    const PlaneWindow* const* io, const size_t* limits)
 {
-    // up to kMaxEncStreams planes at a time in one symbol loop; further planes join as earlier ones end
-    EncGroup g;
-    int next = 0;
-    while (next < count || g.count()) {
-        while (next < count && !g.full()) {
-            g.add(sym[next], n, out[next], (hists && hists[next]) ? hists[next] : nullptr, lens + next, io ? io[next] : nullptr, limits ? limits[next] : 0);
-            next++;
-        }
-        g.step([](void* tag, size_t len) { *static_cast<size_t*>(tag) = len; });
+    std::vector<PlaneJob> jobs((size_t)(count > 0 ? count : 0));
+    for (int k = 0; k < count; k++) {
+        PlaneJob& j = jobs[k];
+        j.kind = PlaneJob::kEncode; j.src = sym[k]; j.n = n; j.dst = out[k]; j.hist = hists ? hists[k] : nullptr;
+        j.io = io ? io[k] : nullptr; j.dst_limit = limits ? limits[k] : 0;
     }
+    run_jobs(jobs.data(), count);
+    for (int k = 0; k < count; k++) lens[k] = jobs[k].result;
 }
 
 size_t encode_plane(const uint8_t* sym, size_t n, uint8_t* out, const uint16_t* hists)
@@ -1555,20 +1553,41 @@ bool decode_planes_vec(int count, const uint8_t* const* in, const size_t* len, u
     return true;
 }
 
+bool run_jobs(PlaneJob* jobs, int count)
+{
+    for (int k = 1; k < count; k++)
+        if (jobs[k].kind != jobs[0].kind) return false;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto run = [&](auto& g, auto add) {
+        // up to the group's capacity at a time in one symbol loop; further planes join as earlier ones end
+        int next = 0;
+        while (next < count || g.count()) {
+            while (next < count && !g.full()) add(g, jobs[next++]);
+            g.step([](void* tag, size_t result) { *static_cast<size_t*>(tag) = result; });
+        }
+    };
+    if (count > 0 && jobs[0].kind == PlaneJob::kEncode) {
+        EncGroup g;
+        run(g, [](EncGroup& eg, PlaneJob& j) { eg.add(j.src, j.n, j.dst, j.hist, &j.result, j.io, j.dst_limit); });
+    } else if (count > 0) {
+        DecGroup g(kMaxStreams);
+        run(g, [](DecGroup& dg, PlaneJob& j) { j.result = 0; dg.add(j.src, j.src_len, j.dst, j.n, &j.result, j.io); });
+    }
+    const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (int k = 0; k < count; k++) jobs[k].seconds = s;
+    return true;
+}
+
 void decode_planes(int count, const uint8_t* const* in, const size_t* len, uint8_t* const* sym, size_t n, size_t* produced,
                    const PlaneWindow* const* io)
 {
-    // up to kMaxStreams planes at a time in one symbol loop; further planes join as earlier ones end
-    DecGroup g(kMaxStreams);
-    int next = 0;
-    while (next < count || g.count()) {
-        while (next < count && !g.full()) {
-            produced[next] = 0;
-            g.add(in[next], len[next], sym[next], n, produced + next, io ? io[next] : nullptr);
-            next++;
-        }
-        g.step([](void* tag, size_t got) { *static_cast<size_t*>(tag) = got; });
+    std::vector<PlaneJob> jobs((size_t)(count > 0 ? count : 0));
+    for (int k = 0; k < count; k++) {
+        PlaneJob& j = jobs[k];
+        j.kind = PlaneJob::kDecode; j.src = in[k]; j.src_len = len[k]; j.dst = sym[k]; j.n = n; j.io = io ? io[k] : nullptr;
     }
+    run_jobs(jobs.data(), count);
+    for (int k = 0; k < count; k++) produced[k] = jobs[k].result;
 }
 
 size_t decode_plane(const uint8_t* in, size_t len, uint8_t* sym, size_t n)
@@ -1916,6 +1935,13 @@ void pool_wait(JobBatch* batch)
 {
     std::unique_lock<std::mutex> lk(batch->mu);
     batch->cv.wait(lk, [&] { return batch->remaining == 0; });
+}
+bool pool_run(PlaneJob* jobs, int count)
+{
+    JobBatch batch;
+    if (!pool_submit(jobs, count, &batch)) return false;
+    pool_wait(&batch);
+    return true;
 }
 
 }  // namespace wrrc

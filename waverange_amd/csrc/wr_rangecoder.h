@@ -94,10 +94,14 @@ struct PlaneJob {
                                      // histograms allow (they are not this plane's); dst then holds dst_limit + kFailedBlockSlack bytes.  0: no check
     const PlaneWindow* io = nullptr; // the symbol side (encode: src, decode: dst) comes / goes through windows instead
     size_t result = 0;             // encode: stream length, (size_t)-1 if given up; decode: symbols the stream held, (size_t)-1 if undecodable or given up
-    double seconds = 0;            // from the moment a worker took the job to its end
+    double seconds = 0;            // pool: from the moment a worker took the job to its end; run_jobs: the whole call
     double submitted = 0;          // (pool) when the job was queued
     JobBatch* batch = nullptr;
 };
+// `count` jobs of one kind on the calling thread, in the interleaved loops of encode_planes / decode_planes (which are this
+// with their arrays made into jobs); every job's `seconds` is the wall time of the call.  False (nothing coded) for a batch
+// of mixed kinds.
+bool run_jobs(PlaneJob* jobs, int count);
 void pool_configure(int nthreads, int dec_streams);  // nthreads = 0 stops the pool; dec_streams < 1 keeps the setting
 void pool_test_steal_idle_min(int workers);  // native tests: a hand-over of streams needs only this many idle workers (0: the product's rule)
 int pool_threads();
@@ -113,5 +117,6 @@ double pool_idle_seconds();  // time the workers have spent waiting for a job si
 // been stopped by another thread since the caller looked at pool_threads(): the caller then codes the planes itself.
 bool pool_submit(PlaneJob* jobs, int count, JobBatch* batch);
 void pool_wait(JobBatch* batch);
+bool pool_run(PlaneJob* jobs, int count);  // pool_submit and pool_wait; false (nothing coded) if the pool has no workers
 
 }  // namespace wrrc
