@@ -21,7 +21,15 @@ of the fields (upload / kernels / download, three work-space slots per GPU, copi
 one another and with the host coding inside the library.
 value = field megabytes (10^6 B) round-tripped per second, whole job (all ranks).
 
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints the line: `value`,
+`ms_per_step` and what the timed steps themselves recorded (stage times, in-pipeline rooflines, host load).  Everything that
+costs work of its own after the timed region runs only with --full: the accuracy of the last reconstruction and the parity of
+the timed run's bytes against the reference's pins (tests/golden/large.json), the warm-clock transforms (roofline_warm), the
+resident-field figure committed under profiles/, the secondary pass at --secondary-tol, one field alone (single_field) and the
+reference on the CPU (cpu_baseline).
+
   python bench.py [--gpus N] [--steps K] [--warmup W] [--size 1024] [--tols 1e-3,1e-7] [--batch 12] [--jobs 12] [--pool -1]
+                  [--full]   (all of the above beside the headline figure: a few minutes more)
                   [--resident]   (fields start and end in HBM instead: the round-1 measurement)
                   [--pool 0 --threads 1]   (no coder pool: every call codes its planes on its own thread)
                   [--dump-outputs DIR]   (what the last timed step returned for every tolerance -- header, coded bytes,
@@ -106,7 +114,7 @@ def parity_vs_pins(n, seed, coded, decoded):
     """What the TIMED run produced against the reference's own outputs (tests/golden/large.json, written by
     tools/make_golden_large.py from the compiled reference in the build container): the coded bytes of the last field
     of every tolerance (header scalars as bit patterns, plane lengths, SHA-256 of data_enc) and the last reconstruction.
-    Runs after the timed region, on every rank for its own field.  None where no pin exists for (size, tolerance, seed)."""
+    Runs after the timed region (--full), on every rank for its own field.  None where no pin exists for (size, tolerance, seed)."""
     try:
         with open(os.path.join(ROOT, "tests", "golden", "large.json")) as fh:
             pins = json.load(fh)
@@ -607,8 +615,10 @@ def main():
                     "queue, so up to --jobs x tols fields are in flight whatever the batch and steps overlap")
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--tols", type=str, default="1e-3,1e-7")
-    ap.add_argument("--cpu-size", type=int, default=448)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also check and measure beside the headline figure after the timed region: "
+                    "accuracy and parity against the reference's pins, roofline_warm, the secondary pass, single_field, cpu_baseline")
+    ap.add_argument("--cpu-size", type=int, default=448, help="field size of the CPU baseline (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without single_field and cpu_baseline")
     ap.add_argument("--jobs", type=int, default=20, help="fields in flight per tolerance (lanes = jobs x tols); cut down to what the rank's CPUs, host memory and HBM allow")
     ap.add_argument("--fields-per-cpu", type=float, default=2.5, help="fields in flight per CPU of the rank that the coder pool is given (the upper bound the CPUs put on --jobs)")
     ap.add_argument("--hbm-per-lane", type=float, default=0.6, help="plane memory a lane is budgeted in HBM, in field sizes at four planes per field (measured: 40 lanes "
@@ -623,9 +633,9 @@ def main():
     ap.add_argument("--pool", type=int, default=-1, help="coder-pool worker threads shared by all fields in flight (-1: one per CPU of this rank; 0: no pool, "
                     "every call runs its own --threads coder threads)")
     ap.add_argument("--dec-streams", type=int, default=4, help="plane streams a pool worker's decoder loop interleaves (1..4)")
-    ap.add_argument("--no-warm-transforms", action="store_true", help="skip the back-to-back transforms behind the timed region (roofline_warm): a profiled run "
-                    "then holds only the pipeline's launches of k_inv_fused (tools/final_profiles.sh)")
-    ap.add_argument("--secondary-steps", type=int, default=2, help="steps of the secondary pass at --secondary-tol after the timed region (N = 1 only; 0: none)")
+    ap.add_argument("--no-warm-transforms", action="store_true", help="--full without the back-to-back transforms behind the timed region (roofline_warm): a "
+                    "profiled run then holds only the pipeline's launches of k_inv_fused (a plain run never has them)")
+    ap.add_argument("--secondary-steps", type=int, default=2, help="steps of the secondary pass at --secondary-tol after the timed region (--full, N = 1 only; 0: none)")
     ap.add_argument("--secondary-tol", type=float, default=1e-16, help="BASELINE configs[4]'s near-lossless tolerance: 8 planes per field, mostly noise")
     ap.add_argument("--secondary-lanes", type=int, default=8, help="fields in flight in the secondary pass (each holds up to 2 x 6 GB of coded bytes at 1024^3)")
     ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
@@ -1073,7 +1083,7 @@ def main():
         dt = float(t.item())
 
     # accuracy of the last reconstruction (tols[-1]) against the original, and the bytes of the timed run against the
-    # reference's pins -- outside the timed region
+    # reference's pins -- outside the timed region, --full only
     def check_capture(cap):
         """accuracy of the held-back reconstruction and parity of the held-back bytes against this rank's pins; everything that
         was held back goes into circulation again"""
@@ -1092,13 +1102,15 @@ def main():
 
     if dump_starts is not None:  # before check_capture hands the held-back coded streams back
         write_dump(args.dump_outputs, tols, {t: e for t, (e, _) in main_capture["coded"].items()}, main_capture["samples"], dump_starts)
-    # EVERY rank checks what it coded in the timed region against the reference's pins for its own field (seed 12345 + rank)
-    main_check = check_capture(main_capture)
-    parity = main_check["parity"]
-    if main_check["linf_rel"] is not None:
-        accuracy["linf_rel"] = main_check["linf_rel"]
+    parity = None
+    if args.full:
+        # EVERY rank checks what it coded in the timed region against the reference's pins for its own field (seed 12345 + rank)
+        main_check = check_capture(main_capture)
+        parity = main_check["parity"]
+        if main_check["linf_rel"] is not None:
+            accuracy["linf_rel"] = main_check["linf_rel"]
     linf_rel = accuracy.get("linf_rel")
-    if dist is not None and world > 1:
+    if args.full and dist is not None and world > 1:
         every = [None] * world
         dist.all_gather_object(every, {"rank": rank, "parity": parity, "linf_rel": linf_rel})
         if rank == 0 and parity is not None:
@@ -1190,31 +1202,32 @@ def main():
                                 "field_d2h_GBps": round(nbytes_field / 1e6 / max(1e-9, mean(acc["dec_d2h_ms"])), 1) if host_mode else None},
                        "burn_ms_per_field": round(burn_ms, 2),
                        "device_only_MBps": round(2 * field_mb / max(1e-9, mean(acc["enc_gpu_s"]) + mean(acc["dec_gpu_s"])), 1)},
-            "accuracy": {"tol": tols[-1], "linf_rel": linf_rel},
-            "parity": parity,
         }
-        # the same transform kernels back to back on a busy GPU (outside the timed region): what they do with the
-        # shader clock up -- inside the pipeline every kernel stage starts on a GPU that has been idle
-        try:
-            if args.no_warm_transforms:
-                raise RuntimeError("skipped (--no-warm-transforms)")
-            ctx.trim()  # the plane pool holds the timed run's plane memory idle (most of the HBM): this leg needs a field's worth of it
-            wbuf = ctx.alloc(nelem * 8)
-            ctx.synth_field(wbuf, n, n, n, 12345 + rank)
-            ctx.sync()
-            for lvl in (4, -4):
-                ctx.bench_transform(wbuf, shape, lvl, 6)   # brings the clocks up
-            wf, wi = ctx.bench_transform(wbuf, shape, 4, 8), ctx.bench_transform(wbuf, shape, -4, 8)
-            wbuf.free()
-            wa = alg_bytes / (0.5 * (wf + wi) * 1e-3) / 1e9
-            out["roofline_warm"] = {"achieved": round(wa, 1), "frac": round(wa / HBM_PEAK_GBS, 4), "fwd_ms": round(wf, 3), "inv_ms": round(wi, 3),
-                                    "note": "plain forward kernels (no min/max riding along), 8 transforms back to back after 12 to warm up: the shader clock is up "
-                                            "(what WR_CLOCK_WARMUP_MS buys inside the pipeline; it does not move `value`)"}
-        except Exception as exc:  # noqa: BLE001
-            out["roofline_warm"] = {"error": str(exc)}
-        other, other_src = committed_extra("bench%d_resident.json" % n if host_mode else "bench%d_host.json" % n)
-        if other:
-            out["resident_fields" if host_mode else "host_buffers"] = {"value": other.get("value"), "unit": "MB/s", "source": other_src}
+        if args.full:
+            out["accuracy"] = {"tol": tols[-1], "linf_rel": linf_rel}
+            out["parity"] = parity
+            # the same transform kernels back to back on a busy GPU (outside the timed region): what they do with the
+            # shader clock up -- inside the pipeline every kernel stage starts on a GPU that has been idle
+            try:
+                if args.no_warm_transforms:
+                    raise RuntimeError("skipped (--no-warm-transforms)")
+                ctx.trim()  # the plane pool holds the timed run's plane memory idle (most of the HBM): this leg needs a field's worth of it
+                wbuf = ctx.alloc(nelem * 8)
+                ctx.synth_field(wbuf, n, n, n, 12345 + rank)
+                ctx.sync()
+                for lvl in (4, -4):
+                    ctx.bench_transform(wbuf, shape, lvl, 6)   # brings the clocks up
+                wf, wi = ctx.bench_transform(wbuf, shape, 4, 8), ctx.bench_transform(wbuf, shape, -4, 8)
+                wbuf.free()
+                wa = alg_bytes / (0.5 * (wf + wi) * 1e-3) / 1e9
+                out["roofline_warm"] = {"achieved": round(wa, 1), "frac": round(wa / HBM_PEAK_GBS, 4), "fwd_ms": round(wf, 3), "inv_ms": round(wi, 3),
+                                        "note": "plain forward kernels (no min/max riding along), 8 transforms back to back after 12 to warm up: the shader clock is up "
+                                                "(what WR_CLOCK_WARMUP_MS buys inside the pipeline; it does not move `value`)"}
+            except Exception as exc:  # noqa: BLE001
+                out["roofline_warm"] = {"error": str(exc)}
+            other, other_src = committed_extra("bench%d_resident.json" % n if host_mode else "bench%d_host.json" % n)
+            if other:
+                out["resident_fields" if host_mode else "host_buffers"] = {"value": other.get("value"), "unit": "MB/s", "source": other_src}
         try:  # peak resident host memory of this rank (pinned staging included)
             with open("/proc/self/status") as fh:
                 hwm = [l for l in fh if l.startswith("VmHWM")][0].split()
@@ -1233,7 +1246,7 @@ def main():
         out["pool_workers_idle"] = round(pool_idle, 2)  # of the pool's workers, how many were waiting for a job on average
         if throttled is not None:
             out["cpu_quota_throttled"] = round(throttled, 3)  # cgroup cpu.stat throttled time / wall time of the timed region
-        if world == 1 and args.secondary_steps > 0 and host_mode and pool_workers:
+        if args.full and world == 1 and args.secondary_steps > 0 and host_mode and pool_workers:
             # BASELINE configs[4]'s tolerance on the same pipeline, outside the timed region: a bounded sample (few lanes, few
             # steps: mostly fill and drain) so that the command stays within minutes; `bench.py --tols 1e-16` is the full run
             try:
@@ -1267,7 +1280,7 @@ def main():
                             % (args.secondary_steps * sb, nl, args.secondary_tol)}}
             except Exception as exc:  # noqa: BLE001
                 out["secondary"] = {"error": str(exc)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # one field alone on the idle machine, a coder thread per plane: the latency a single
             # encoding_wrap / decoding_wrap caller sees (outside the timed region)
             api.set_coder_pool(0)
@@ -1308,6 +1321,11 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+    # the pages of the hand-over buffers (~80 GiB at 1024^3) go back on one thread per CPU of the rank: left to the
+    # interpreter, which frees the buffers one after the other on its way out, they keep the run from exiting for seconds
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max(1, int(limits["cpus_per_rank"]))) as ex:
+        list(ex.map(lambda buf: drop_pages(buf, buf.size), all_bufs))
     for ln in lanes:
         ln["dec"].close()
         ln["enc"].close()

@@ -712,7 +712,7 @@ def test_bench_takes_the_rccl_barrier_under_a_launcher_with_one_rank(tmp_path):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--size", "256", "--steps", "1", "--warmup", "0",
-                        "--no-cpu-baseline", "--secondary-steps", "0"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--secondary-steps", "0"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["config"]["barrier"] == "rccl", line["config"]
@@ -749,3 +749,20 @@ def test_bench_dump_outputs_are_what_the_timed_path_returned(tmp_path, oracle):
         assert list(a[p + "len_enc_vec"]) == want["len_enc_vec"]
         assert np.array_equal(a[p + "coded"], want["data"].astype(np.float32)) and list(a[p + "coded_blocks"]) == [0]
         assert bits_equal(a[p + "decoded"], oracle.decode(want, f.shape)) and list(a[p + "decoded_blocks"]) == [0]
+
+
+def test_plain_bench_run_leaves_the_full_legs_out():
+    """bench.py without --full prints the headline line and runs nothing after its timed steps: no accuracy or parity check,
+    no warm-clock transforms, secondary pass, single field or CPU baseline (the legs are not switched off one by one here:
+    a plain run has none of them)."""
+    import json
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "WR_BENCH_BACKEND"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "64", "--jobs", "1", "--steps", "1", "--warmup", "0"],
+                       env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["value"] > 0 and line["unit"] == "MB/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["steps"] == 1 and line["ms_per_step"] > 0
+    assert not {"accuracy", "parity", "roofline_warm", "resident_fields", "secondary", "single_field", "cpu_baseline"} & set(line)
