@@ -318,6 +318,46 @@ int wr_encode_host_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny, int nz, 
 int wr_decode_host_f32(wr_ctx *ctx, float *h_fld, int nx, int ny, int nz, const wr_enc_info *info,
                        const unsigned char *data_enc, size_t data_len, wr_timings *tm);
 int wr_decode_finish_host_f32(wr_ctx *ctx, float *h_fld, wr_timings *tm); /* after wr_decode_begin */
+/* ---- Segmented plane streams ("WRS1"): an opt-in second stream format, coded and decoded on the GPU.
+ * Transform, quantizer and header scalars are those of wr_encode_host for the same field; only the bytes of every plane in
+ * data_enc differ.  A plane of n symbols is cut into segments of `seg` symbols, each coded as a complete stream of its own
+ * (byte for byte wr_range_encode of those symbols), so that a field is tens of thousands of independent chains instead
+ * of one per plane:
+ *   plane blob := 'W','R','S','1' | u32 seg | u32 nseg = ceil(n / seg) | u32 len[nseg] | the segment streams, in order
+ * (little endian; 16 <= seg <= 59999, a multiple of 16).  len_enc_vec[l] is the length of plane l's blob, ntot_enc their
+ * sum.  The reference's tools and the other wr_decode_* entry points do NOT read this format (a reference stream starts
+ * with byte 0x00).  seg = 0 means WR_SEG_DEFAULT everywhere. */
+#define WR_SEG_DEFAULT 59904
+size_t wr_seg_bound(size_t n, unsigned seg); /* worst-case blob bytes of one plane; 0 if seg is refused */
+/* stage level, device pointers (16-byte aligned): code / decode one plane of n symbols.  bad_segments: segments whose
+ * stream did not decode to their symbols (WR_ERR_STREAM then); a malformed index is refused before anything is launched. */
+int wr_dev_seg_encode(wr_ctx *ctx, const unsigned char *d_sym, size_t n, unsigned seg, unsigned char *d_blob,
+                      size_t cap, size_t *blob_len);
+int wr_dev_seg_decode(wr_ctx *ctx, const unsigned char *d_blob, size_t blob_len, unsigned char *d_sym, size_t n,
+                      size_t *bad_segments);
+/* whole path: as wr_encode_host / wr_decode_host (and the fp32 and device-field forms), the planes coded by the GPU.
+ * No coder pool, no host coder threads.  wr_timings: `rangecoder` is the time of the coder kernels and the compaction,
+ * plane_coder_s[l] plane l's.  cap too small: WR_ERR_OVERFLOW; a malformed blob: WR_ERR_STREAM. */
+int wr_encode_host_seg(wr_ctx *ctx, const double *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                       const double *cutoffvec, unsigned seg, wr_enc_info *info, unsigned char *data_enc, size_t cap,
+                       wr_timings *tm);
+int wr_decode_host_seg(wr_ctx *ctx, double *h_fld, int nx, int ny, int nz, const wr_enc_info *info,
+                       const unsigned char *data_enc, size_t data_len, wr_timings *tm);
+int wr_encode_host_seg_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                           const double *cutoffvec, unsigned seg, wr_enc_info *info, unsigned char *data_enc,
+                           size_t cap, wr_timings *tm);
+int wr_decode_host_seg_f32(wr_ctx *ctx, float *h_fld, int nx, int ny, int nz, const wr_enc_info *info,
+                           const unsigned char *data_enc, size_t data_len, wr_timings *tm);
+int wr_encode_device_seg(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                         const double *cutoffvec, unsigned seg, wr_enc_info *info, unsigned char *data_enc, size_t cap,
+                         wr_timings *tm);
+int wr_decode_device_seg(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, const wr_enc_info *info,
+                         const unsigned char *data_enc, size_t data_len, wr_timings *tm);
+/* host reference of the format (the definition above, on the calling thread): for tests and for readers without a GPU.
+ * blob holds wr_seg_bound(n, seg) bytes; returns the blob's length (0: seg refused, wr_last_error says why). */
+size_t wr_seg_encode_host_ref(const unsigned char *sym, size_t n, unsigned seg, unsigned char *blob);
+int wr_seg_decode_host_ref(const unsigned char *blob, size_t len, unsigned char *sym, size_t n);
+
 /* encoding_wrap / decoding_wrap for fp32 fields: the same arguments but the field, an implicit context per call and
  * the reference's "void + fatal" errors.  fld_1d of an encode is never overwritten (no residual write-back). */
 void wr_encoding_wrap_f32(int nx, int ny, int nz, const float *fld_1d, int wtflag, int mx, int my, int mz,

@@ -147,6 +147,20 @@ def lib():
     L.wr_range_encode_vec.argtypes = [C.c_int, _vp, _vp, _vp, _vp]
     L.wr_range_encode_windowed.argtypes = [C.c_int, C.c_int, _vp, C.c_size_t, C.c_size_t, _vp, _vp]
     L.wr_range_decode_windowed.argtypes = [C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp]
+    L.wr_seg_bound.restype = C.c_size_t
+    L.wr_seg_bound.argtypes = [C.c_size_t, C.c_uint]
+    L.wr_seg_encode_host_ref.restype = C.c_size_t
+    L.wr_seg_encode_host_ref.argtypes = [_vp, C.c_size_t, C.c_uint, _vp]
+    L.wr_seg_decode_host_ref.argtypes = [_vp, C.c_size_t, _vp, C.c_size_t]
+    L.wr_dev_seg_encode.argtypes = [_vp, _vp, C.c_size_t, C.c_uint, _vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.wr_dev_seg_decode.argtypes = [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.wr_encode_host_seg.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_uint,
+                                     C.POINTER(EncInfo), _vp, C.c_size_t, C.POINTER(Timings)]
+    L.wr_encode_host_seg_f32.argtypes = L.wr_encode_host_seg.argtypes
+    L.wr_encode_device_seg.argtypes = L.wr_encode_host_seg.argtypes
+    L.wr_decode_host_seg.argtypes = L.wr_decode_host.argtypes
+    L.wr_decode_host_seg_f32.argtypes = L.wr_decode_host.argtypes
+    L.wr_decode_device_seg.argtypes = L.wr_decode_host.argtypes
     L.wr_bench_transform.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]
     # drop-in symbols (reference src/core/wrappers.h:53,70,75)
     L.setup_wr.argtypes = [C.c_int] * 3 + [_u8p, _ulp]
@@ -295,6 +309,56 @@ def range_decode(stream, n):
     out = np.zeros(max(n, 1), dtype=np.uint8)
     got = lib().wr_range_decode(s.ctypes.data, s.size, out.ctypes.data, n)
     return out[:n], got
+
+
+SEG_DEFAULT = 59904  # WR_SEG_DEFAULT
+
+
+def seg_bound(n, seg=0):
+    """Worst-case bytes of one plane's segmented blob (0 if `seg` is refused)."""
+    return int(lib().wr_seg_bound(n, seg))
+
+
+def seg_encode_host_ref(plane, seg=0):
+    """The segmented blob of a plane, coded on the calling thread: the definition of the format (wr_seg_encode_host_ref)."""
+    p = np.ascontiguousarray(plane, dtype=np.uint8).ravel()
+    bound = seg_bound(p.size, seg)
+    if not bound:
+        raise WaveRangeError("segment length must be a multiple of 16 in [16, 59999]")
+    out = np.empty(bound, dtype=np.uint8)
+    src = p if p.size else np.zeros(1, dtype=np.uint8)
+    n = lib().wr_seg_encode_host_ref(src.ctypes.data, p.size, seg, out.ctypes.data)
+    if not n:
+        raise WaveRangeError(lib().wr_last_error().decode())
+    return out[:n].copy()
+
+
+def seg_decode_host_ref(blob, n):
+    """The n symbols of a segmented blob, decoded on the calling thread; raises WaveRangeError for a malformed blob."""
+    b = np.ascontiguousarray(blob, dtype=np.uint8).ravel()
+    src = b if b.size else np.zeros(1, dtype=np.uint8)
+    out = np.zeros(max(n, 1), dtype=np.uint8)
+    _check(lib().wr_seg_decode_host_ref(src.ctypes.data, b.size, out.ctypes.data, n))
+    return out[:n]
+
+
+def seg_split(blob):
+    """(seg, [segment stream bytes, ...]) of a segmented blob whose index is well formed (ValueError otherwise)."""
+    b = np.ascontiguousarray(blob, dtype=np.uint8).ravel()
+    if b.size < 12 or bytes(b[:4]) != b"WRS1":
+        raise ValueError("not a WRS1 blob")
+    seg, nseg = (int(v) for v in b[4:12].view("<u4"))
+    if 12 + 4 * nseg > b.size:
+        raise ValueError("index longer than the blob")
+    lens = b[12:12 + 4 * nseg].view("<u4").astype(np.int64)
+    at = 12 + 4 * nseg
+    if at + int(lens.sum()) != b.size:
+        raise ValueError("segment lengths do not add up to the blob")
+    out = []
+    for ln in lens:
+        out.append(bytes(b[at:at + int(ln)]))
+        at += int(ln)
+    return seg, out
 
 
 def range_encode_multi(planes):
@@ -624,6 +688,92 @@ class Context:
         _check(lib().wr_decode_host_f32(self.h, out.ctypes.data, nx, ny, nz, C.byref(info), data.ctypes.data, data.size,
                                         C.byref(tm)))
         return tm.as_dict()
+
+    # ---- segmented plane streams ("WRS1"): the planes are coded and decoded by the GPU; not readable by the reference's tools
+    def _seg_cap(self, shape, seg):
+        nz, ny, nx = shape
+        _, cap = setup_wr(nx, ny, nz)
+        n = nx * ny * nz
+        return cap + NLAYMAX * max(seg_bound(n, seg) - n, 0)
+
+    def _encode_seg(self, fn, ptr, shape, tolrel, wtflag, seg, out, cutoff, m):
+        nz, ny, nx = shape
+        data = out if out is not None else np.empty(self._seg_cap(shape, seg), dtype=np.uint8)
+        cut = np.ascontiguousarray([tolrel] if cutoff is None else cutoff, dtype=np.float64)
+        info, tm = EncInfo(), Timings()
+        _check(fn(self.h, ptr, nx, ny, nz, wtflag, m[0], m[1], m[2], cut.ctypes.data_as(_dp), seg, C.byref(info),
+                  data.ctypes.data, data.size, C.byref(tm)))
+        d = info.as_dict()
+        d["data"] = data[:info.ntot_enc]
+        return d, tm.as_dict()
+
+    def _decode_seg(self, fn, ptr, shape, enc):
+        nz, ny, nx = shape
+        info = EncInfo.from_dict(enc)
+        tm = Timings()
+        data = np.ascontiguousarray(enc["data"], dtype=np.uint8)
+        if data.size == 0:
+            data = np.zeros(1, dtype=np.uint8)
+        _check(fn(self.h, ptr, nx, ny, nz, C.byref(info), data.ctypes.data, data.size, C.byref(tm)))
+        return tm.as_dict()
+
+    def encode_host_seg(self, fld, tolrel, wtflag=1, seg=0, out=None, cutoff=None, m=(1, 1, 1)):
+        """encode_host with every plane as a segmented blob (seg = 0: SEG_DEFAULT); header scalars as encode_host's."""
+        assert fld.dtype == np.float64 and fld.flags["C_CONTIGUOUS"]
+        return self._encode_seg(lib().wr_encode_host_seg, fld.ctypes.data, fld.shape, tolrel, wtflag, seg, out, cutoff, m)
+
+    def decode_host_seg(self, out, enc):
+        assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"]
+        return self._decode_seg(lib().wr_decode_host_seg, out.ctypes.data, out.shape, enc)
+
+    def encode_host_seg_f32(self, fld, tolrel, wtflag=1, seg=0, out=None, cutoff=None, m=(1, 1, 1)):
+        if not (isinstance(fld, np.ndarray) and fld.dtype == np.float32 and fld.flags["C_CONTIGUOUS"]):
+            raise TypeError("encode_host_seg_f32: a C-contiguous float32 array is required")
+        return self._encode_seg(lib().wr_encode_host_seg_f32, fld.ctypes.data, fld.shape, tolrel, wtflag, seg, out, cutoff, m)
+
+    def decode_host_seg_f32(self, out, enc):
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"]):
+            raise TypeError("decode_host_seg_f32: a C-contiguous float32 array is required")
+        return self._decode_seg(lib().wr_decode_host_seg_f32, out.ctypes.data, out.shape, enc)
+
+    def encode_seg(self, buf, shape, tolrel, wtflag=1, seg=0, out=None, cutoff=None, m=(1, 1, 1)):
+        """encode_host_seg with the field resident on the device (`buf` is consumed, as by encode)."""
+        return self._encode_seg(lib().wr_encode_device_seg, buf.ptr, shape, tolrel, wtflag, seg, out, cutoff, m)
+
+    def decode_seg(self, buf, shape, enc):
+        return self._decode_seg(lib().wr_decode_device_seg, buf.ptr, shape, enc)
+
+    def seg_encode_plane(self, plane, seg=0):
+        """Stage level: one plane of symbols (a numpy uint8 array) through the coder kernels; returns the blob."""
+        p = np.ascontiguousarray(plane, dtype=np.uint8).ravel()
+        bound = seg_bound(p.size, seg)
+        if not bound:
+            raise WaveRangeError("segment length must be a multiple of 16 in [16, 59999]")
+        d_sym, d_blob = self.alloc(max(p.size, 16)), self.alloc(bound)
+        try:
+            if p.size:
+                d_sym.upload(p)
+            got = C.c_size_t(0)
+            _check(lib().wr_dev_seg_encode(self.h, d_sym.ptr, p.size, seg, d_blob.ptr, bound, C.byref(got)))
+            return d_blob.download(np.uint8, got.value)
+        finally:
+            d_sym.free()
+            d_blob.free()
+
+    def seg_decode_plane(self, blob, n):
+        """Stage level: a blob through the decoder kernel; returns (symbols, bad_segments).  Raises for a malformed index
+        or a segment that does not decode."""
+        b = np.ascontiguousarray(blob, dtype=np.uint8).ravel()
+        d_blob, d_sym = self.alloc(max(b.size, 16)), self.alloc(max(n, 16))
+        try:
+            if b.size:
+                d_blob.upload(b)
+            bad = C.c_size_t(0)
+            _check(lib().wr_dev_seg_decode(self.h, d_blob.ptr, b.size, d_sym.ptr, n, C.byref(bad)))
+            return (d_sym.download(np.uint8, n) if n else np.zeros(0, np.uint8)), int(bad.value)
+        finally:
+            d_blob.free()
+            d_sym.free()
 
     def decode_begin(self, shape, enc):
         """Host half of a decode (range decoding into the context's staging); no output buffer needed yet."""

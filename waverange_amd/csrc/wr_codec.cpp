@@ -6,6 +6,7 @@
 // Compiled with hipcc, strict IEEE (-ffp-contract=off): the scalar arithmetic on deps/aopt/bopt/tolabs below must round
 // exactly as wrappers.cpp:292-340 does.
 #include "wr_internal.h"
+#include "wr_segcoder.h"
 
 using namespace wri;
 
@@ -975,6 +976,399 @@ int wr_bench_transform(wr_ctx* c, double* d_fld, int nx, int ny, int nz, int lvl
     HIPCHK(hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
     *ms_out = (double)ms / reps;
     return WR_OK;
+}
+
+}  // extern "C"
+
+// ---- segmented plane streams: the planes are coded and decoded by the GPU (wr_segcoder.hip) -------------------------------
+// The format is wr_segcoder.h's.  These drivers replace the hand-off to the host coder (block histograms, plane windows,
+// coder threads or pool, the admission gate) by coder kernels and whole-blob copies; transform, quantizer and the header
+// scalars are encode_planes_core's / inverse_from_planes', shared with the reference-format path.
+namespace {
+
+// device memory of a segmented call, from the plane pool (its accounting, cap and reserve); goes back when the call ends,
+// behind everything the context's stream still has queued
+struct SegBufs {
+    wr_ctx* c;
+    DevPlanes::Buf stage, blob[WR_NLAYMAX], work[WR_NLAYMAX];
+    hipEvent_t ev[2 * WR_NLAYMAX] = {nullptr};
+    explicit SegBufs(wr_ctx* ctx) : c(ctx) {}
+    SegBufs(const SegBufs&) = delete;
+    SegBufs& operator=(const SegBufs&) = delete;
+    ~SegBufs()
+    {
+        (void)hipStreamSynchronize(c->stream);
+        if (stage.p) c->pool->planes.give(stage);
+        for (int l = 0; l < WR_NLAYMAX; l++) {
+            if (blob[l].p) c->pool->planes.give(blob[l]);
+            if (work[l].p) c->pool->planes.give(work[l]);
+        }
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+    int events(int l)
+    {
+        for (int k = 2 * l; k < 2 * l + 2; k++)
+            if (!ev[k]) HIPCHK(hipEventCreate(&ev[k]));
+        return WR_OK;
+    }
+    double seconds(int l) const
+    {
+        float ms = 0;
+        if (!ev[2 * l] || hipEventElapsedTime(&ms, ev[2 * l], ev[2 * l + 1]) != hipSuccess) { (void)hipGetLastError(); return 0; }
+        return ms * 1e-3;
+    }
+};
+
+unsigned long long* seg_result_host(wr_ctx* c, int l) { return reinterpret_cast<unsigned long long*>(c->h_result + 8) + 2 * l; }
+unsigned long long* seg_result_dev(wr_ctx* c, int l) { return reinterpret_cast<unsigned long long*>(c->h_result_dev + 8) + 2 * l; }
+
+int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, const Cutoff& cut, unsigned seg, wr_enc_info* info,
+                    unsigned char* data_enc, size_t cap, wr_timings* tm)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
+    if (int rc = ctx_bind(c)) return rc;
+    if (int rc = check_dims(nx, ny, nz, fld.dev)) return rc;
+    if (fld.none()) return fail(WR_ERR_ARG, "null field pointer");
+    if (!info) return fail(WR_ERR_ARG, "null wr_enc_info");
+    if (cut.mx < 1 || cut.my < 1 || cut.mz < 1 || !cut.vec) return fail(WR_ERR_ARG, "bad local cutoff description");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (fld.host_f32 && c->keep_residual)
+        return fail(WR_ERR_UNSUPPORTED, "an fp32 field cannot take the residual back: wr_ctx_set_keep_residual(ctx, 0) for fp32 encodes");
+    ActiveCall active(c->pool);
+    if (tm) wrdma::enable_timing();
+    const double t0 = now();
+    const size_t n = (size_t)nx * ny * nz;
+    if (wrseg::seg_count(n, seg) > 0xffffffffu) return fail(WR_ERR_ARG, "too many segments");
+    wr_timings local; memset(&local, 0, sizeof local);
+    DevPool* const pool = c->pool;
+    c->pend_valid = false;  // planes a wr_decode_begin parked in this context do not survive an encode on it
+    PlaneHold planes(c);
+    SegBufs bufs(c);  // (after the planes: it goes first when the call unwinds, and waits for the stream)
+    const size_t blob_cap = (wr_seg_bound(n, seg) + 15) & ~(size_t)15;
+
+    SlotNeed need;
+    transform_need(nx, ny, nz, wtflag ? kWavLvl : 0, &need);
+    if (fld.host || fld.host_f32) need.field_elems = n;
+    SlotLease slot;
+    if (int rc = slot.acquire(c, need)) return rc;
+    const double t_phase = now();
+    double* d_fld = fld.dev;
+    if (fld.host) {
+        d_fld = slot->field;
+        if (int rc = xfer_field(c, &c->x_field, d_fld, fld.host, n * sizeof(double), kUp)) return rc;
+        local.h2d_ms = (float)c->x_field.ms;
+    }
+    const float* d_f32 = nullptr;  // (as encode_impl: the fused forward transform reads an fp32 field where it lands)
+    float* widen_from = nullptr;
+    if (fld.host_f32) {
+        d_fld = slot->field;
+        float* const stage = (wtflag && use_fused(nx, ny, nz, kWavLvl)) ? reinterpret_cast<float*>(slot->field) : reinterpret_cast<float*>(slot->scratch);
+        if (int rc = xfer_field(c, &c->x_field, stage, fld.host_f32, n * sizeof(float), kUp)) return rc;
+        local.h2d_ms = (float)c->x_field.ms;
+        if (stage == reinterpret_cast<float*>(slot->field)) d_f32 = stage;
+        else widen_from = stage;
+    }
+    // one staging buffer for the uncompacted streams, used by every plane in turn (the planes' coder kernels are ordered by
+    // the context's stream); a blob buffer per plane
+    bufs.stage = plane_scratch(c, wrk::seg_stage_bytes(n, seg));
+    if (!bufs.stage.p) return WR_ERR_HIP;
+    double* resid = d_fld;
+    int rc = WR_OK;
+    {
+        StageLock cu(pool->cu_mu);
+        const bool one_array = cut.count() > 1;
+        auto plane_buf = [&](unsigned l) -> const wrk::PlaneRef* {
+            if (plane_prepare(c, (int)l, n, false, one_array, &cu, nullptr, false) != WR_OK) return nullptr;
+            bufs.blob[l] = plane_scratch(c, blob_cap);
+            if (!bufs.blob[l].p || bufs.events((int)l) != WR_OK) return nullptr;
+            return &c->ps[l].ref;
+        };
+        // plane l's coder kernels go behind its quantizer (and the read-back of the next plane's min/max) on the same stream
+        auto after_quant = [&](unsigned l, bool) -> int {
+            launch_note(c, "seg_encode", (int)l, bufs.blob[l].p, n, bufs.stage.p, c->ps[l].ref);
+            HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
+            wrk::seg_encode(c->ps[l].ref, n, seg, bufs.stage.p, bufs.blob[l].p, blob_cap, seg_result_dev(c, (int)l), c->stream);
+            HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
+            if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented coder launch failed" + launch_describe(c));
+            return WR_OK;
+        };
+        clock_warmup(c, n);
+        if (widen_from) wrk::widen_f32(widen_from, d_fld, n, c->stream);
+        rc = encode_planes_core(c, slot.get(), d_fld, nx, ny, nz, wtflag, cut, plane_buf, [](unsigned) { return (uint16_t*)nullptr; }, info, &local,
+                                after_quant, [](unsigned, bool) { return WR_OK; }, &resid, d_f32);
+        if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the encoder's kernel stage failed on the device" + launch_describe(c));
+        if (rc == WR_OK && c->keep_residual && info->nlay && !fld.host && resid != fld.dev) {
+            if (hipMemcpyAsync(fld.dev, resid, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
+                hipStreamSynchronize(c->stream) != hipSuccess)
+                rc = fail(WR_ERR_HIP, "residual copy failed");
+        }
+        pool->last_stage_end.store(now());
+    }
+    if (rc) return rc;
+    if (c->keep_residual && info->nlay && fld.host)
+        if ((rc = xfer_field(c, &c->x_field, fld.host, resid, n * sizeof(double), kDown)) != WR_OK) return rc;
+    // ---- stage "down": every plane's blob, one copy each, to its place in data_enc
+    size_t total = 0;
+    for (unsigned l = 0; l < info->nlay; l++) {
+        const unsigned long long len = seg_result_host(c, (int)l)[0], bad = seg_result_host(c, (int)l)[1];
+        if (bad || len > blob_cap) return fail(WR_ERR_HIP, "internal: plane " + std::to_string(l) + ": a segment outgrew the segment bound");
+        info->len_enc_vec[l] = len;
+        total += len;
+    }
+    if (total > cap || (total && !data_enc)) return fail(WR_ERR_OVERFLOW, "Error: encoded array is too large. Use larger SAFETY_BUFFER_FACTOR");
+    size_t at = 0;
+    for (unsigned l = 0; l < info->nlay; l++) {
+        if ((rc = xfer_field(c, &c->x_field, data_enc + at, bufs.blob[l].p, info->len_enc_vec[l], kDown)) != WR_OK) return rc;
+        local.d2h_ms += (float)c->x_field.ms;
+        at += info->len_enc_vec[l];
+        local.plane_coder_s[l] = bufs.seconds((int)l);
+        local.rangecoder += local.plane_coder_s[l];
+    }
+    info->ntot_enc = total;
+    local.total = now() - t0;
+    local.wait = t_phase - t0;
+    local.gpu = now() - t_phase;
+    if (tm) *tm = local;
+    return WR_OK;
+}
+
+// the byte offsets of the segment streams behind the index, from an index that check_index has passed, into work + 256
+int seg_upload_offsets(wr_ctx* c, const uint8_t* front, uint32_t nseg, uint8_t* work)
+{
+    std::vector<unsigned long long> offs((size_t)nseg + 1);
+    unsigned long long run = 0;
+    for (uint32_t k = 0; k < nseg; k++) { offs[k] = run; run += wrseg::get_u32(front + wrseg::kHeaderBytes + 4 * (size_t)k); }
+    offs[nseg] = run;
+    HIPCHK(hipMemcpy(work + 256, offs.data(), offs.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    return WR_OK;
+}
+
+int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
+                    wr_timings* tm)
+{
+    if (int rc = ctx_bind(c)) return rc;
+    if (!info) return fail(WR_ERR_ARG, "null wr_enc_info");
+    std::lock_guard<std::mutex> lk(c->mu);
+    ActiveCall active(c->pool);
+    if (tm) wrdma::enable_timing();
+    if (int rc = check_dims(nx, ny, nz, fld.dev)) return rc;
+    if (fld.none()) return fail(WR_ERR_ARG, "null field pointer");
+    c->pend_valid = false;
+    PlaneHold planes(c);
+    SegBufs bufs(c);
+    const double t0 = now();
+    const size_t n = (size_t)nx * ny * nz;
+    wr_timings local; memset(&local, 0, sizeof local);
+    DevPool* const pool = c->pool;
+    if (info->ntot_enc == 0) {  // wrappers.cpp:462-469
+        if (fld.host) for (size_t j = 0; j < n; j++) fld.host[j] = info->midval;
+        else if (fld.host_f32) for (size_t j = 0; j < n; j++) fld.host_f32[j] = (float)info->midval;
+        else { wrk::fill(fld.dev, n, info->midval, c->stream); HIPCHK(hipStreamSynchronize(c->stream)); }
+        local.total = now() - t0;
+        if (tm) *tm = local;
+        return WR_OK;
+    }
+    const int nlay = info->nlay;
+    if (nlay < 1 || nlay > WR_NLAYMAX) return fail(WR_ERR_ARG, "nlay out of range");
+    if (info->wlev != 0 && info->wlev != kWavLvl) return fail(WR_ERR_ARG, "wlev must be 0 or 4");
+    if (!data_enc) return fail(WR_ERR_ARG, "null coded buffer");
+    size_t off[WR_NLAYMAX + 1] = {0};
+    for (int l = 0; l < nlay; l++) off[l + 1] = off[l] + info->len_enc_vec[l];
+    if (off[nlay] > info->ntot_enc) return fail(WR_ERR_STREAM, "len_enc_vec exceeds ntot_enc");
+    if (data_len && info->ntot_enc > data_len) return fail(WR_ERR_STREAM, "ntot_enc exceeds the length of the coded buffer");
+    // every plane's header and index are validated here, on the host, before anything is launched: the kernels only ever see
+    // offsets that lie inside their blob, in order, each stream no longer than a segment can be
+    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0};
+    for (int l = 0; l < nlay; l++)
+        if (const char* why = wrseg::check_index(data_enc + off[l], info->len_enc_vec[l], info->len_enc_vec[l], n, &seg[l], &nseg[l]))
+            return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + why);
+    {
+        std::lock_guard<std::mutex> gather(pool->planes.gather_mu);  // one decode at a time gathers its planes (decode_impl)
+        for (int l = 0; l < nlay; l++) {
+            if (int rc = plane_prepare(c, l, n, true, false, nullptr, nullptr, false)) return rc;
+            bufs.blob[l] = plane_scratch(c, info->len_enc_vec[l]);
+            bufs.work[l] = plane_scratch(c, wrk::seg_decode_work_bytes(nseg[l]));
+            if (!bufs.blob[l].p || !bufs.work[l].p) return WR_ERR_HIP;
+            if (int rc = bufs.events(l)) return rc;
+        }
+    }
+    // ---- stage "up": one copy per blob
+    for (int l = 0; l < nlay; l++) {
+        if (int rc = xfer_field(c, &c->x_field, bufs.blob[l].p, data_enc + off[l], info->len_enc_vec[l], kUp)) return rc;
+        local.h2d_ms += (float)c->x_field.ms;
+        if (int rc = seg_upload_offsets(c, data_enc + off[l], nseg[l], bufs.work[l].p)) return rc;
+    }
+    const double t_coded = now();
+    SlotNeed need;
+    transform_need(nx, ny, nz, info->wlev ? -kWavLvl : 0, &need);
+    if (fld.host || fld.host_f32) need.field_elems = n;
+    SlotLease slot;
+    if (int rc = slot.acquire(c, need)) return rc;
+    const double t_phase = now();
+    wrk::DequantParams p;
+    memset(&p, 0, sizeof p);
+    p.nlay = nlay;
+    for (int l = 0; l < nlay; l++) {
+        p.deps[l] = info->deps_vec[l]; p.minval[l] = info->minval_vec[l]; p.q[l] = c->ps[l].ref;
+        if (!wrk::plane_ref_covers(p.q[l], n)) return fail(WR_ERR_HIP, "internal: the device buffer of plane " + std::to_string(l) + " has a hole");
+    }
+    double* d_fld = fld.dev ? fld.dev : slot->field;
+    float* d_f32 = nullptr;
+    int rc = WR_OK;
+    {
+        StageLock cu(pool->cu_mu);
+        clock_warmup(c, n);
+        for (int l = 0; l < nlay; l++) {
+            launch_note(c, "seg_decode", l, bufs.blob[l].p, n, bufs.work[l].p, p.q[l]);
+            HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
+            wrk::seg_decode(bufs.blob[l].p, info->len_enc_vec[l], p.q[l], n, seg[l], bufs.work[l].p, c->stream);
+            HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
+        }
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented decoder launch failed" + launch_describe(c));
+        // the dequantizer only runs on planes whose every segment decoded
+        unsigned int bad[WR_NLAYMAX] = {0};
+        for (int l = 0; l < nlay; l++) HIPCHK(hipMemcpyAsync(&bad[l], bufs.work[l].p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the segmented decoder failed on the device" + launch_describe(c));
+        for (int l = 0; l < nlay; l++) {
+            if (bad[l]) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + std::to_string(bad[l]) + " segment(s) do not decode to their symbols");
+            local.plane_coder_s[l] = bufs.seconds(l);
+            local.rangecoder += local.plane_coder_s[l];
+        }
+        launch_note(c, "dequant", nlay - 1, d_fld, n, nullptr, p.q[nlay - 1]);
+        rc = inverse_from_planes(c, slot.get(), d_fld, nx, ny, nz, (int)info->wlev, p, fld.host_f32 ? &d_f32 : nullptr);
+        if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
+        if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the decoder's kernel stage failed on the device" + launch_describe(c));
+        pool->last_stage_end.store(now());
+    }
+    if (rc) return rc;
+    if (fld.host) {
+        if ((rc = xfer_field(c, &c->x_field, fld.host, d_fld, n * sizeof(double), kDown)) != WR_OK) return rc;
+        local.d2h_ms = (float)c->x_field.ms;
+    } else if (fld.host_f32) {
+        if ((rc = xfer_field(c, &c->x_field, fld.host_f32, d_f32, n * sizeof(float), kDown)) != WR_OK) return rc;
+        local.d2h_ms = (float)c->x_field.ms;
+    }
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev_a, c->ev_b)); local.quant_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev_b, c->ev_c)); local.transform_ms = ms;
+    local.total = now() - t0;
+    local.gpu = now() - t_phase;
+    local.wait = t_phase - t_coded;
+    local.transfer = t_coded - t0;
+    if (tm) *tm = local;
+    return WR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wr_dev_seg_encode(wr_ctx* c, const unsigned char* d_sym, size_t n, unsigned seg, unsigned char* d_blob, size_t cap, size_t* blob_len)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
+    if (int rc = ctx_bind(c)) return rc;
+    if (!d_blob || !blob_len || (n && !d_sym)) return fail(WR_ERR_ARG, "null pointer");
+    if (((uintptr_t)d_sym | (uintptr_t)d_blob) & 15) return fail(WR_ERR_ARG, "plane and blob buffers must be 16-byte aligned");
+    const size_t nseg = wrseg::seg_count(n, seg);
+    if (nseg > 0xffffffffu) return fail(WR_ERR_ARG, "too many segments");
+    if (cap < wrseg::kHeaderBytes + 4 * nseg) return fail(WR_ERR_OVERFLOW, "the blob buffer does not hold the plane's index");
+    std::lock_guard<std::mutex> lk(c->mu);
+    SegBufs bufs(c);
+    bufs.stage = plane_scratch(c, wrk::seg_stage_bytes(n, seg));
+    if (!bufs.stage.p) return WR_ERR_HIP;
+    StageLock cu(c->pool->cu_mu);
+    wrk::seg_encode(wrk::plane_ref(d_sym), n, seg, bufs.stage.p, d_blob, cap, seg_result_dev(c, 0), c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const unsigned long long len = seg_result_host(c, 0)[0], bad = seg_result_host(c, 0)[1];
+    if (bad) return fail(WR_ERR_HIP, "internal: a segment outgrew the segment bound");
+    if (len > cap) return fail(WR_ERR_OVERFLOW, "the blob buffer is too small for the plane");
+    *blob_len = (size_t)len;
+    return WR_OK;
+}
+
+int wr_dev_seg_decode(wr_ctx* c, const unsigned char* d_blob, size_t blob_len, unsigned char* d_sym, size_t n, size_t* bad_segments)
+{
+    if (int rc = ctx_bind(c)) return rc;
+    if (!d_blob || (n && !d_sym)) return fail(WR_ERR_ARG, "null pointer");
+    if (((uintptr_t)d_sym | (uintptr_t)d_blob) & 15) return fail(WR_ERR_ARG, "plane and blob buffers must be 16-byte aligned");
+    if (bad_segments) *bad_segments = 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    // the header, then the index, come to the host and are validated before anything is launched
+    std::vector<uint8_t> front(wrseg::kHeaderBytes);
+    if (blob_len < front.size()) return fail(WR_ERR_STREAM, "segmented plane: shorter than its header");
+    HIPCHK(hipMemcpy(front.data(), d_blob, front.size(), hipMemcpyDeviceToHost));
+    uint32_t seg = 0, nseg = 0;
+    const char* why = wrseg::check_index(front.data(), front.size(), blob_len, n, &seg, &nseg);
+    if (why == wrseg::kIndexNotAvailable) {  // (the index fits into the blob: check_index has looked)
+        front.resize(wrseg::kHeaderBytes + 4 * (size_t)wrseg::get_u32(front.data() + 8));
+        HIPCHK(hipMemcpy(front.data(), d_blob, front.size(), hipMemcpyDeviceToHost));
+        why = wrseg::check_index(front.data(), front.size(), blob_len, n, &seg, &nseg);
+    }
+    if (why) return fail(WR_ERR_STREAM, why);
+    if (!nseg) return WR_OK;
+    SegBufs bufs(c);
+    bufs.work[0] = plane_scratch(c, wrk::seg_decode_work_bytes(nseg));
+    if (!bufs.work[0].p) return WR_ERR_HIP;
+    if (int rc = seg_upload_offsets(c, front.data(), nseg, bufs.work[0].p)) return rc;
+    StageLock cu(c->pool->cu_mu);
+    wrk::seg_decode(d_blob, blob_len, wrk::plane_ref(d_sym), n, seg, bufs.work[0].p, c->stream);
+    HIPCHK(hipGetLastError());
+    unsigned int bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, bufs.work[0].p, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (bad_segments) *bad_segments = bad;
+    if (bad) return fail(WR_ERR_STREAM, "segmented plane: " + std::to_string(bad) + " segment(s) do not decode to their symbols");
+    return WR_OK;
+}
+
+int wr_encode_host_seg(wr_ctx* c, const double* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,
+                       unsigned seg, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm)
+{
+    Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
+    FieldRef f; f.host = const_cast<double*>(h_fld);  // (written only with wr_ctx_set_keep_residual(ctx, 1), as wr_encode_host)
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, info, data_enc, cap, tm);
+}
+
+int wr_decode_host_seg(wr_ctx* c, double* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
+                       wr_timings* tm)
+{
+    FieldRef f; f.host = h_fld;
+    return decode_seg_impl(c, f, nx, ny, nz, info, data_enc, data_len, tm);
+}
+
+int wr_encode_host_seg_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,
+                           unsigned seg, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm)
+{
+    Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
+    FieldRef f; f.host_f32 = const_cast<float*>(h_fld);
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, info, data_enc, cap, tm);
+}
+
+int wr_decode_host_seg_f32(wr_ctx* c, float* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
+                           wr_timings* tm)
+{
+    FieldRef f; f.host_f32 = h_fld;
+    return decode_seg_impl(c, f, nx, ny, nz, info, data_enc, data_len, tm);
+}
+
+int wr_encode_device_seg(wr_ctx* c, double* d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec, unsigned seg,
+                         wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm)
+{
+    Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
+    FieldRef f; f.dev = d_fld;
+    if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, info, data_enc, cap, tm);
+}
+
+int wr_decode_device_seg(wr_ctx* c, double* d_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
+                         wr_timings* tm)
+{
+    FieldRef f; f.dev = d_fld;
+    if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
+    return decode_seg_impl(c, f, nx, ny, nz, info, data_enc, data_len, tm);
 }
 
 }  // extern "C"

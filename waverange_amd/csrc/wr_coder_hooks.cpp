@@ -2,6 +2,7 @@
 // interleaved planes, the coder pool, the 16-lane loops, and the windowed symbol path with host buffers standing in for
 // device-resident planes (test hooks).
 #include "wr_internal.h"
+#include "wr_segcoder.h"
 
 using namespace wri;
 
@@ -140,6 +141,54 @@ int wr_range_decode_windowed(int mode, int count, const unsigned char* const* in
     if (mode == 0) wrrc::run_jobs(jobs.data(), count);
     else if (!wrrc::pool_run(jobs.data(), count)) return fail(WR_ERR_ARG, "the coder pool is not running (wr_set_coder_pool)");
     for (int k = 0; k < count; k++) produced[k] = jobs[k].result;
+    return WR_OK;
+}
+
+// ---- the segmented plane stream (wr_segcoder.h) on the calling thread: the definition of the format, for tests and for
+// readers without a GPU
+size_t wr_seg_bound(size_t n, unsigned seg)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) return 0;
+    return wrseg::kHeaderBytes + wrseg::seg_count(n, seg) * (4 + (size_t)wrseg::stream_bound(seg));
+}
+
+size_t wr_seg_encode_host_ref(const unsigned char* sym, size_t n, unsigned seg, unsigned char* blob)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
+    if (!blob || (n && !sym)) { fail(WR_ERR_ARG, "null pointer"); return 0; }
+    const size_t nseg = wrseg::seg_count(n, seg);
+    if (nseg > 0xffffffffu) { fail(WR_ERR_ARG, "too many segments"); return 0; }
+    memcpy(blob, wrseg::kMagic, 4);
+    wrseg::put_u32(blob + 4, seg);
+    wrseg::put_u32(blob + 8, (uint32_t)nseg);
+    size_t at = wrseg::kHeaderBytes + 4 * nseg;
+    for (size_t k = 0; k < nseg; k++) {
+        const size_t base = k * seg;
+        const uint32_t bs = n - base < seg ? (uint32_t)(n - base) : seg;
+        const uint32_t len = wrseg::encode_segment_host(sym + base, bs, blob + at, wrseg::stream_bound(seg));
+        if (!len) { fail(WR_ERR_OVERFLOW, "internal: a segment outgrew the segment bound"); return 0; }
+        wrseg::put_u32(blob + wrseg::kHeaderBytes + 4 * k, len);
+        at += len;
+    }
+    return at;
+}
+
+int wr_seg_decode_host_ref(const unsigned char* blob, size_t len, unsigned char* sym, size_t n)
+{
+    if (!blob || (n && !sym)) return fail(WR_ERR_ARG, "null pointer");
+    uint32_t seg = 0, nseg = 0;
+    if (const char* why = wrseg::check_index(blob, len, len, n, &seg, &nseg)) return fail(WR_ERR_STREAM, why);
+    size_t at = wrseg::kHeaderBytes + 4 * (size_t)nseg;
+    for (uint32_t k = 0; k < nseg; k++) {
+        const size_t base = (size_t)k * seg;
+        const uint32_t bs = n - base < seg ? (uint32_t)(n - base) : seg;
+        const uint32_t l = wrseg::get_u32(blob + wrseg::kHeaderBytes + 4 * (size_t)k);
+        if (wrseg::decode_segment_host(blob + at, l, blob, blob + len, sym + base, bs) != wrseg::kSegOk)
+            return fail(WR_ERR_STREAM, "segmented plane: segment " + std::to_string(k) + " does not decode to its symbols");
+        at += l;
+    }
     return WR_OK;
 }
 

@@ -160,7 +160,7 @@ struct wr_ctx {
     double* d_mm = nullptr; size_t mm_records = 0;  // min/max records of the fused forward transform
     unsigned long long* d_idx = nullptr;
     // pinned host
-    double* h_result = nullptr;  // [0..1] min/max, [2] probe value, [3] index, [4..7] fused min/max
+    double* h_result = nullptr;  // [0..1] min/max, [2] probe value, [3] index, [4..7] fused min/max, [8 + 2l, 9 + 2l] plane l's segmented-coder result (u64: blob length, failed segments)
     double* h_result_dev = nullptr;  // the same block as the device sees it: reductions write their result straight to the host
     uint16_t* h_hist = nullptr; size_t h_hist_elems = 0;  // pinned: per-block byte histograms, all planes
     // host coded-stream staging, one per plane
@@ -333,8 +333,12 @@ void plane_release(wr_ctx* c, int l);
 // and that must not be held while waiting for device memory that other calls' kernel stages have to free (nullptr: none)
 // before_wait: called once, with the context's stream synchronised and the lock still held, before the call starts to wait:
 // an encoder hands the planes it has already quantized to their coders there, so that they drain while it waits (nullptr: none)
+// windows = false: the plane is coded on the device (segmented streams): no pinned ring, no window callbacks, and chunks need not hold a window
 int plane_prepare(wr_ctx* c, int l, size_t n, bool decode, bool contiguous = false, std::unique_lock<std::mutex>* unlock_while_waiting = nullptr,
-                  const std::function<void()>* before_wait = nullptr);
+                  const std::function<void()>* before_wait = nullptr, bool windows = true);
+// a buffer of `bytes` of device memory from the plane pool (its accounting, its cap and its reserve), waiting like a plane's if
+// there is none; {nullptr, 0} and the error set if nothing came back.  Goes back with c->pool->planes.give().
+DevPlanes::Buf plane_scratch(wr_ctx* c, size_t bytes);
 // remembers what a plane kernel of the context is about to be launched with (wr_ctx::last_launch and the fault log's ring)
 void launch_note(wr_ctx* c, const char* what, int plane, const void* x, size_t n, const void* partial, const wrk::PlaneRef& q);
 std::string launch_describe(const wr_ctx* c);  // " [last plane kernel: ...]" for error messages

@@ -121,6 +121,20 @@ void burn(double ms, int mode, int workgroups, double* sink, hipStream_t st);
 // bytes (a multiple of 16, 16-byte aligned pointers) copied by `workgroups` workgroups; src / dst may be pinned host memory
 void copy_kernel(void* dst, const void* src, size_t bytes, int workgroups, hipStream_t st);
 
+// ---- segmented plane streams (wr_segcoder.hip; the format and the coder step: wr_segcoder.h).  One lane codes one segment.
+// Encode: the plane's blob (header, index, segment streams) lands in blob[0, cap) -- 16-byte aligned -- unless it is longer than
+// cap; result_host (pinned, as the device sees it; may be null) and the first two words of `stage` take {the blob's length,
+// segments that failed}.  `stage`: seg_stage_bytes(n, seg) of device memory, 256-byte aligned (the uncompacted streams, one
+// region of the segment bound per segment, and the scan's arrays).  The symbols' plane is 16-byte aligned.
+size_t seg_stage_bytes(size_t n, unsigned seg);
+void seg_encode(const PlaneRef& sym, size_t n, unsigned seg, uint8_t* stage, uint8_t* blob, size_t cap, unsigned long long* result_host,
+                hipStream_t st);
+// Decode: `work` is seg_decode_work_bytes(nseg) of device memory, 256-byte aligned: {u32 bad segments} at 0 (zeroed here), at
+// 256 the nseg + 1 byte offsets of the segment streams behind the index (u64, put there by the caller from the index it
+// has VALIDATED on the host), then a u32 flag per segment (0: decoded).  A lane writes only its segment's symbols.
+size_t seg_decode_work_bytes(size_t nseg);
+void seg_decode(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, hipStream_t st);
+
 }  // namespace wrk
 
 namespace wrk {

@@ -560,7 +560,7 @@ uint8_t* plane_window_decode(void* user, size_t first, size_t* count)
 // plane l of n symbols for this call: a device buffer (kept if the context holds one that fits: a finish after a
 // begin), the ring, and the window callbacks of the direction
 int plane_prepare(wr_ctx* c, int l, size_t n, bool decode, bool contiguous, std::unique_lock<std::mutex>* unlock_while_waiting,
-                  const std::function<void()>* before_wait)
+                  const std::function<void()>* before_wait, bool windows)
 {
     PlaneStream& s = c->ps[l];
     const size_t bytes = wr_plane_pitch(n);
@@ -569,7 +569,7 @@ int plane_prepare(wr_ctx* c, int l, size_t n, bool decode, bool contiguous, std:
     // a plane of two chunks or more lives in chunks: of the configured size, or larger so that kPlaneChunks of them hold it
     size_t cb = dp.chunk_bytes;
     while (cb < bytes && cb * wrk::kPlaneChunks < bytes) cb <<= 1;
-    const bool want_chunks = !contiguous && bytes >= 2 * cb && cb >= kChunkSyms;  // (a window never spans more than two chunks)
+    const bool want_chunks = !contiguous && bytes >= 2 * cb && (!windows || cb >= kChunkSyms);  // (a window never spans more than two chunks)
     const bool have_chunks = !s.chunks.empty();
     const bool reusable = s.dev && s.dev_bytes >= bytes && have_chunks == want_chunks && !s.released_chunks;
     if (!reusable) {
@@ -604,8 +604,8 @@ int plane_prepare(wr_ctx* c, int l, size_t n, bool decode, bool contiguous, std:
     }
     // an encoder's plane drains: its chunks go back as the coder has fetched the windows they hold -- unless the plane is
     // looked at again afterwards (the verbose mode's per-plane diagnostics, plane_log)
-    s.drain = !s.chunks.empty() && !decode && !verbose();
-    for (int b = 0; b < 2; b++) {
+    s.drain = windows && !s.chunks.empty() && !decode && !verbose();
+    for (int b = 0; b < 2 && windows; b++) {
         if (s.buf[b]) continue;
         if (hipHostMalloc(reinterpret_cast<void**>(&s.buf[b]), kChunkBytes, hipHostMallocDefault) == hipSuccess) { s.buf_pinned[b] = true; continue; }
         // no pinned memory left: a pageable window works (the copies are then staged by the runtime, xfer_start)
@@ -623,7 +623,17 @@ int plane_prepare(wr_ctx* c, int l, size_t n, bool decode, bool contiguous, std:
     tk.s = &s; tk.gen = g;
     s.io.window = decode ? plane_window_decode : plane_window_encode;
     s.io.user = &tk;
+    if (!windows) { s.io.window = nullptr; s.io.user = nullptr; }  // the plane never leaves the device: nobody gets a handle
     return WR_OK;
+}
+
+DevPlanes::Buf plane_scratch(wr_ctx* c, size_t bytes)
+{
+    planes_configure(c->pool->planes);
+    bool unlocked = false;
+    const DevPlanes::Buf b = plane_buffer_wait(c, (bytes + 255) & ~(size_t)255, nullptr, &unlocked, nullptr);
+    if (!b.p) fail(WR_ERR_HIP, "out of device memory for the segmented coder's buffers: nothing came back in five minutes");
+    return b;
 }
 
 // encode: the plane is complete on the device -- its first chunk sets off for the host before a coder asks for it
@@ -859,7 +869,7 @@ static int ctx_init(wr_ctx* c, int device, void* hip_stream)
     else { HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
     HIPCHK(hipMalloc(&c->d_partial, 2 * wrk::minmax_partials() * sizeof(double)));
     HIPCHK(hipMalloc(&c->d_idx, sizeof(unsigned long long)));
-    HIPCHK(hipHostMalloc(&c->h_result, 8 * sizeof(double), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(&c->h_result, (8 + 2 * WR_NLAYMAX) * sizeof(double), hipHostMallocDefault));  // ([8 + 2l ..]: plane l's segmented-coder result)
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_result_dev), c->h_result, 0));
     for (int i = 0; i < WR_NLAYMAX; i++) {
         HIPCHK(hipEventCreateWithFlags(&c->ev_plane[i], hipEventDisableTiming));
