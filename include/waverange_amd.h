@@ -192,6 +192,8 @@ int wr_set_device_slots(int device, int nslots);
                                     * coder pool is blocked then, not idle), summed over coders */
 #define WR_STAT_DECODE_GATE_MS 9   /* milliseconds decode calls have waited for admission to the coder pool, holding no device memory yet
                                       (before: the same time in the pool's queues with their planes allocated), summed over calls */
+#define WR_STAT_LOWRES_SEGMENTS 11 /* segments the low-resolution decodes (wr_decode_*_seg_lowres) have launched, summed over planes */
+#define WR_STAT_LOWRES_BYTES_UP 12 /* coded payload bytes those calls have copied to the device (the offsets tables are not counted) */
 unsigned long wr_stat(int what);
 /* Hands the idle buffers of the device's plane pool back to the device (the pool keeps the plane memory of finished calls for
  * the next ones: after a burst of concurrent calls that can be most of the HBM).  Buffers in use are not touched. */
@@ -353,7 +355,47 @@ int wr_encode_device_seg(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, int
                          wr_timings *tm);
 int wr_decode_device_seg(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, const wr_enc_info *info,
                          const unsigned char *data_enc, size_t data_len, wr_timings *tm);
-/* host reference of the format (the definition above, on the calling thread): for tests and for readers without a GPU.
+/* ---- Low-resolution decode of segmented streams: a coarse version of the field without decoding the field.
+ * The transform is a Mallat decomposition (waveletcdf97_3d.c:73-78): after level r the low-pass coefficients of an nx*ny*nz
+ * field sit in the corner box [0,bx) x [0,by) x [0,bz) of the coefficient array.  With h(n) = (n + 1) / 2 in integer
+ * arithmetic, for a header record `info` and a level r, 0 <= r <= info->wlev:
+ *   box       bx = h^r(nx), likewise by, bz
+ *   exponent  e = the sum over the three axes and the levels j = 1..r of [h^(j-1)(n_axis) > 1] (an axis of extent 1 at a level
+ *             is not transformed there and adds nothing: the DC gain of a level is sqrt(2) per transformed axis)
+ *   scale     s = 2^(-e/2) as a double: ldexp(e odd ? 0x1.6a09e667f3bcdp-1 : 1.0, -(e / 2))
+ *   planes    p planes are used, 1 <= p <= info->nlay; max_planes == 0 means all of them
+ * The result D(r, p) is an array of bx*by*bz doubles, x fastest:
+ *   1. C[j] = 0; for l = 0..p-1 in order: C[j] += q_l[j] * deps_vec[l] + minval_vec[l]   (no contraction, this order)
+ *   2. A = the contiguous copy of C over z < bz, y < by, x < bx
+ *   3. if wlev - r > 0: waveletcdf97_3d(bx, by, bz, -(wlev - r), A)
+ *   4. out = A * s, one multiply and one rounding (s = 1 at r = 0)
+ *   5. for fp32 output (float)out, rounded as wr_decode_host_seg_f32 rounds
+ * D(0, nlay) is the full decode, bit for bit.  A constant field (info->ntot_enc == 0) gives midval at the box's size.
+ * wlev == 0 with r > 0, r > wlev, r outside [0, 4] or p > nlay: WR_ERR_ARG.
+ * Segments: for a plane cut at `seg`, run (y, z) of the box needs the segments floor(row*nx / seg) .. floor((row*nx + bx - 1)
+ * / seg), row = y + ny*z; the union over the box's runs is decoded, and only those segments' bytes go to the device.  Every
+ * plane's header and index are validated as by wr_decode_host_seg before anything is launched. */
+int wr_lowres_dims(int nx, int ny, int nz, int level, int *bx, int *by, int *bz); /* host only */
+double wr_lowres_scale(int nx, int ny, int nz, int level); /* s above; host only; 0 for a refused argument */
+/* ascending ids of the segments a level needs; returns their number (ids may be NULL to count; at most cap are written),
+ * 0 if seg or another argument is refused */
+size_t wr_seg_lowres_segments(int nx, int ny, int nz, int level, unsigned seg, uint32_t *ids, size_t cap);
+/* stage level: from nlay full planes at a pitch of wr_plane_pitch(n) in device memory (any format decoded them); d_out
+ * receives bx*by*bz doubles */
+int wr_dev_decode_planes_lowres(wr_ctx *ctx, double *d_out, int nx, int ny, int nz, int level, int max_planes,
+                                const unsigned char *d_planes, const wr_enc_info *info);
+/* whole path, as wr_decode_host_seg / _f32 / wr_decode_device_seg; the output holds bx*by*bz elements.  wr_timings as there:
+ * h2d_ms the copies of the needed streams, rangecoder / plane_coder_s the decoder launches, quant_ms the box dequantiser,
+ * transform_ms the inverse on the box and the scaling. */
+int wr_decode_host_seg_lowres(wr_ctx *ctx, double *h_out, int nx, int ny, int nz, int level, int max_planes,
+                              const wr_enc_info *info, const unsigned char *data_enc, size_t data_len, wr_timings *tm);
+int wr_decode_host_seg_lowres_f32(wr_ctx *ctx, float *h_out, int nx, int ny, int nz, int level, int max_planes,
+                                  const wr_enc_info *info, const unsigned char *data_enc, size_t data_len,
+                                  wr_timings *tm);
+int wr_decode_device_seg_lowres(wr_ctx *ctx, double *d_out, int nx, int ny, int nz, int level, int max_planes,
+                                const wr_enc_info *info, const unsigned char *data_enc, size_t data_len,
+                                wr_timings *tm);
+/* host reference of the WRS1 format (its definition further up, on the calling thread): for tests and for readers without a GPU.
  * blob holds wr_seg_bound(n, seg) bytes; returns the blob's length (0: seg refused, wr_last_error says why). */
 size_t wr_seg_encode_host_ref(const unsigned char *sym, size_t n, unsigned seg, unsigned char *blob);
 int wr_seg_decode_host_ref(const unsigned char *blob, size_t len, unsigned char *sym, size_t n);

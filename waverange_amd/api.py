@@ -161,6 +161,16 @@ def lib():
     L.wr_decode_host_seg.argtypes = L.wr_decode_host.argtypes
     L.wr_decode_host_seg_f32.argtypes = L.wr_decode_host.argtypes
     L.wr_decode_device_seg.argtypes = L.wr_decode_host.argtypes
+    L.wr_lowres_dims.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)] * 3
+    L.wr_lowres_scale.restype = C.c_double
+    L.wr_lowres_scale.argtypes = [C.c_int] * 4
+    L.wr_seg_lowres_segments.restype = C.c_size_t
+    L.wr_seg_lowres_segments.argtypes = [C.c_int] * 4 + [C.c_uint, _vp, C.c_size_t]
+    L.wr_dev_decode_planes_lowres.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(EncInfo)]
+    L.wr_decode_host_seg_lowres.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncInfo), _vp, C.c_size_t,
+                                            C.POINTER(Timings)]
+    L.wr_decode_host_seg_lowres_f32.argtypes = L.wr_decode_host_seg_lowres.argtypes
+    L.wr_decode_device_seg_lowres.argtypes = L.wr_decode_host_seg_lowres.argtypes
     L.wr_bench_transform.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]
     # drop-in symbols (reference src/core/wrappers.h:53,70,75)
     L.setup_wr.argtypes = [C.c_int] * 3 + [_u8p, _ulp]
@@ -204,6 +214,7 @@ def set_device_slots(device, nslots):
 STAT_EARLY_DECODES, STAT_SLOTS_POPULATED, STAT_DEVICE_PLANE_BYTES, STAT_POOL_IDLE_MS, STAT_POOL_STREAMS_MOVED = 0, 1, 2, 3, 4
 STAT_POOL_QUEUE_MS, STAT_PLANE_WAIT_MS, STAT_HANDOVER_ERRORS, STAT_CLOCK_WARMUP_MS, STAT_DECODE_GATE_MS = 5, 6, 7, 8, 9
 STAT_WINDOW_WAIT_MS = 10
+STAT_LOWRES_SEGMENTS, STAT_LOWRES_BYTES_UP = 11, 12
 
 
 def stat(what):
@@ -359,6 +370,35 @@ def seg_split(blob):
         out.append(bytes(b[at:at + int(ln)]))
         at += int(ln)
     return seg, out
+
+
+def lowres_shape(shape, level):
+    """(bz, by, bx): the box that a low-resolution decode of a field shaped (nz, ny, nx) returns at `level` (wr_lowres_dims)."""
+    nz, ny, nx = shape
+    bx, by, bz = C.c_int(), C.c_int(), C.c_int()
+    _check(lib().wr_lowres_dims(nx, ny, nz, level, C.byref(bx), C.byref(by), C.byref(bz)))
+    return bz.value, by.value, bx.value
+
+
+def lowres_scale(shape, level):
+    """The factor 2^(-e/2) that takes the gain of `level` transform levels out of the box (wr_lowres_scale)."""
+    nz, ny, nx = shape
+    s = lib().wr_lowres_scale(nx, ny, nz, level)
+    if s == 0.0:
+        raise WaveRangeError(lib().wr_last_error().decode())
+    return s
+
+
+def seg_lowres_segments(shape, level, seg=0):
+    """Ascending ids (uint32) of the segments of a plane cut at `seg` that a decode at `level` needs (seg = 0: SEG_DEFAULT)."""
+    nz, ny, nx = shape
+    count = lib().wr_seg_lowres_segments(nx, ny, nz, level, seg, None, 0)
+    if not count:
+        raise WaveRangeError(lib().wr_last_error().decode())
+    ids = np.empty(count, dtype=np.uint32)
+    got = lib().wr_seg_lowres_segments(nx, ny, nz, level, seg, ids.ctypes.data, ids.size)
+    assert got == count
+    return ids
 
 
 def range_encode_multi(planes):
@@ -742,6 +782,37 @@ class Context:
 
     def decode_seg(self, buf, shape, enc):
         return self._decode_seg(lib().wr_decode_device_seg, buf.ptr, shape, enc)
+
+    # ---- low-resolution decode: the box of `level` (lowres_shape) out of the first max_planes planes (0: all of them)
+    def decode_planes_lowres(self, buf, shape, level, planes, info, max_planes=0):
+        """Stage level: `planes` as encode_planes left them; `buf` receives the box as float64."""
+        nz, ny, nx = shape
+        _check(lib().wr_dev_decode_planes_lowres(self.h, buf.ptr, nx, ny, nz, level, max_planes, planes.ptr, C.byref(info)))
+
+    def _decode_seg_lowres(self, fn, ptr, shape, level, enc, max_planes):
+        nz, ny, nx = shape
+        info = EncInfo.from_dict(enc)
+        tm = Timings()
+        data = np.ascontiguousarray(enc["data"], dtype=np.uint8)
+        if data.size == 0:
+            data = np.zeros(1, dtype=np.uint8)
+        _check(fn(self.h, ptr, nx, ny, nz, level, max_planes, C.byref(info), data.ctypes.data, data.size, C.byref(tm)))
+        return tm.as_dict()
+
+    def decode_host_seg_lowres(self, out, shape, level, enc, max_planes=0):
+        """out: C-contiguous float64 array shaped lowres_shape(shape, level); shape: the coded field's (nz, ny, nx)."""
+        assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"] and tuple(out.shape) == lowres_shape(shape, level)
+        return self._decode_seg_lowres(lib().wr_decode_host_seg_lowres, out.ctypes.data, shape, level, enc, max_planes)
+
+    def decode_host_seg_lowres_f32(self, out, shape, level, enc, max_planes=0):
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"]):
+            raise TypeError("decode_host_seg_lowres_f32: a C-contiguous float32 array is required")
+        assert tuple(out.shape) == lowres_shape(shape, level)
+        return self._decode_seg_lowres(lib().wr_decode_host_seg_lowres_f32, out.ctypes.data, shape, level, enc, max_planes)
+
+    def decode_seg_lowres(self, buf, shape, level, enc, max_planes=0):
+        """decode_host_seg_lowres into device memory: `buf` holds the box's elements as float64."""
+        return self._decode_seg_lowres(lib().wr_decode_device_seg_lowres, buf.ptr, shape, level, enc, max_planes)
 
     def seg_encode_plane(self, plane, seg=0):
         """Stage level: one plane of symbols (a numpy uint8 array) through the coder kernels; returns the blob."""

@@ -6,6 +6,7 @@
 // Compiled with hipcc, strict IEEE (-ffp-contract=off): the scalar arithmetic on deps/aopt/bopt/tolabs below must round
 // exactly as wrappers.cpp:292-340 does.
 #include "wr_internal.h"
+#include "wr_lowres.h"
 #include "wr_segcoder.h"
 
 using namespace wri;
@@ -303,6 +304,88 @@ int wr_dev_decode_planes(wr_ctx* c, double* d_fld, int nx, int ny, int nz, const
 }
 
 }  // extern "C"
+
+// ---- low-resolution decode (include/waverange_amd.h): the box of level r out of the first p planes, the remaining levels
+// inverted on the box, the gain of the r levels that stay taken out
+namespace {
+
+struct LowresPlan {
+    wrlow::Box box;
+    int planes;   // p
+    int inverse;  // levels the box is still transformed by: wlev - r
+    double scale;
+};
+
+int lowres_plan(int nx, int ny, int nz, int level, int max_planes, const wr_enc_info* info, LowresPlan* pl)
+{
+    if (!wrlow::level_ok(level)) return fail(WR_ERR_ARG, "level must be in [0, 4]");
+    if (info->wlev != 0 && info->wlev != kWavLvl) return fail(WR_ERR_ARG, "wlev must be 0 or 4");
+    if (level > (int)info->wlev) return fail(WR_ERR_ARG, "level exceeds the transform depth of the stream (a field coded without the transform has level 0 only)");
+    if (info->nlay > WR_NLAYMAX) return fail(WR_ERR_ARG, "nlay out of range");
+    if (max_planes < 0 || max_planes > (int)info->nlay) return fail(WR_ERR_ARG, "max_planes exceeds the planes of the stream");
+    pl->box = wrlow::box_of(nx, ny, nz, level);
+    pl->planes = max_planes ? max_planes : (int)info->nlay;
+    pl->inverse = (int)info->wlev - level;
+    pl->scale = wrlow::scale_of(pl->box);
+    return WR_OK;
+}
+
+// Kernel stage (slot leased, DevPool::cu_mu held): d_box := the box of the planes in p, inverted and scaled.  The slot's
+// scratch buffer holds box.elems() doubles.  out_f32 != nullptr: the result is wanted in fp32; *out_f32 = where it landed
+// (the scratch buffer, which the transform is done with by then).  Records ev_a / ev_b / ev_c as inverse_from_planes.
+int lowres_from_planes(wr_ctx* c, Slot* s, double* d_box, int nx, int ny, const LowresPlan& pl, const wrk::DequantParams& p, float** out_f32)
+{
+    const wrlow::Box& b = pl.box;
+    HIPCHK(hipEventRecord(c->ev_a, c->stream));
+    wrk::dequant_box(d_box, b.bx, b.by, b.bz, nx, ny, p, c->stream);
+    HIPCHK(hipEventRecord(c->ev_b, c->stream));
+    if (pl.inverse > 0) wrk::transform(d_box, s->scratch, b.bx, b.by, b.bz, -pl.inverse, c->stream);
+    if (out_f32) {
+        *out_f32 = reinterpret_cast<float*>(s->scratch);
+        wrk::scale_narrow_f64(d_box, *out_f32, b.elems(), pl.scale, c->stream);
+    } else if (pl.scale != 1.0) {
+        wrk::scale_f64(d_box, d_box, b.elems(), pl.scale, c->stream);
+    }
+    HIPCHK(hipEventRecord(c->ev_c, c->stream));
+    return WR_OK;
+}
+
+}  // namespace
+
+extern "C" int wr_dev_decode_planes_lowres(wr_ctx* c, double* d_out, int nx, int ny, int nz, int level, int max_planes, const unsigned char* d_planes,
+                                           const wr_enc_info* info)
+{
+    if (int rc = ctx_bind(c)) return rc;
+    if (int rc = check_dims(nx, ny, nz, d_out)) return rc;
+    if (!d_out || !info) return fail(WR_ERR_ARG, "null pointer");
+    LowresPlan pl;
+    if (int rc = lowres_plan(nx, ny, nz, level, max_planes, info, &pl)) return rc;
+    const size_t n = (size_t)nx * ny * nz;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (info->ntot_enc == 0 && info->nlay == 0) {  // a constant field, as wr_dev_decode_planes
+        wrk::fill(d_out, pl.box.elems(), info->midval, c->stream);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return WR_OK;
+    }
+    if (!d_planes) return fail(WR_ERR_ARG, "null plane pointer");
+    SlotNeed need;
+    need.scratch_elems = pl.box.elems();
+    SlotLease slot;
+    if (int rc = slot.acquire(c, need)) return rc;
+    StageLock cu(c->pool->cu_mu);
+    wrk::DequantParams p;
+    memset(&p, 0, sizeof p);
+    p.nlay = pl.planes;
+    for (int l = 0; l < p.nlay; l++) {
+        p.q[l] = wrk::plane_ref(d_planes + l * wr_plane_pitch(n));
+        p.deps[l] = info->deps_vec[l];
+        p.minval[l] = info->minval_vec[l];
+    }
+    int rc = lowres_from_planes(c, slot.get(), d_out, nx, ny, pl, p, nullptr);
+    if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the low-resolution kernel stage failed on the device");
+    return rc;
+}
 
 namespace {
 
@@ -1260,6 +1343,172 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
     return WR_OK;
 }
 
+// The streams of the segments in ids (ascending), from the host blob to the same place in the device blob: consecutive
+// segments go as one copy, nothing else of the blob is touched.  *ms and *bytes are added to.
+int seg_upload_streams(wr_ctx* c, uint8_t* d_blob, const uint8_t* h_blob, size_t front, const std::vector<unsigned long long>& offs,
+                       const std::vector<uint32_t>& ids, float* ms, size_t* bytes)
+{
+    constexpr size_t kPiece = (size_t)128 << 20;  // (as xfer_field: a long copy holds up whatever is queued behind it)
+    Piece pc[4];
+    int np = 0;
+    auto flush = [&]() -> int {
+        if (!np) return WR_OK;
+        if (int rc = xfer_start(c, &c->x_field, pc, np, kUp)) return rc;
+        if (int rc = xfer_wait(&c->x_field)) return rc;
+        *ms += (float)c->x_field.ms;
+        np = 0;
+        return WR_OK;
+    };
+    for (size_t i = 0; i < ids.size();) {
+        size_t j = i;
+        while (j + 1 < ids.size() && ids[j + 1] == ids[j] + 1) j++;
+        const size_t a = front + (size_t)offs[ids[i]], b = front + (size_t)offs[(size_t)ids[j] + 1];
+        for (size_t at = a; at < b; at += kPiece) {
+            pc[np++] = Piece{d_blob + at, h_blob + at, b - at < kPiece ? b - at : kPiece};
+            if (np == 4) if (int rc = flush()) return rc;
+        }
+        *bytes += b - a;
+        i = j + 1;
+    }
+    return flush();
+}
+
+// decode_seg_impl for the box of level `level`, from the first planes only: the segments the box's runs touch are uploaded
+// and decoded, the others are not looked at beyond their length in the index.  fld receives box.elems() elements.
+int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int level, int max_planes, const wr_enc_info* info,
+                           const unsigned char* data_enc, size_t data_len, wr_timings* tm)
+{
+    if (int rc = ctx_bind(c)) return rc;
+    if (!info) return fail(WR_ERR_ARG, "null wr_enc_info");
+    std::lock_guard<std::mutex> lk(c->mu);
+    ActiveCall active(c->pool);
+    if (tm) wrdma::enable_timing();
+    if (int rc = check_dims(nx, ny, nz, fld.dev)) return rc;
+    if (fld.none()) return fail(WR_ERR_ARG, "null output pointer");
+    LowresPlan pl;
+    if (int rc = lowres_plan(nx, ny, nz, level, max_planes, info, &pl)) return rc;
+    c->pend_valid = false;
+    PlaneHold planes(c);
+    SegBufs bufs(c);
+    const double t0 = now();
+    const size_t n = (size_t)nx * ny * nz, nbox = pl.box.elems();
+    wr_timings local; memset(&local, 0, sizeof local);
+    DevPool* const pool = c->pool;
+    if (info->ntot_enc == 0) {  // a constant field: midval at the box's size
+        if (fld.host) for (size_t j = 0; j < nbox; j++) fld.host[j] = info->midval;
+        else if (fld.host_f32) for (size_t j = 0; j < nbox; j++) fld.host_f32[j] = (float)info->midval;
+        else { wrk::fill(fld.dev, nbox, info->midval, c->stream); HIPCHK(hipStreamSynchronize(c->stream)); }
+        local.total = now() - t0;
+        if (tm) *tm = local;
+        return WR_OK;
+    }
+    const int nlay = info->nlay, used = pl.planes;
+    if (nlay < 1) return fail(WR_ERR_ARG, "nlay out of range");
+    if (!data_enc) return fail(WR_ERR_ARG, "null coded buffer");
+    size_t off[WR_NLAYMAX + 1] = {0};
+    for (int l = 0; l < nlay; l++) off[l + 1] = off[l] + info->len_enc_vec[l];
+    if (off[nlay] > info->ntot_enc) return fail(WR_ERR_STREAM, "len_enc_vec exceeds ntot_enc");
+    if (data_len && info->ntot_enc > data_len) return fail(WR_ERR_STREAM, "ntot_enc exceeds the length of the coded buffer");
+    // every plane's header and index, used or not, are validated on the host before anything is launched (decode_seg_impl)
+    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0};
+    for (int l = 0; l < nlay; l++)
+        if (const char* why = wrseg::check_index(data_enc + off[l], info->len_enc_vec[l], info->len_enc_vec[l], n, &seg[l], &nseg[l]))
+            return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + why);
+    // the segments the box needs, per plane (planes may have been cut at different lengths)
+    std::vector<uint32_t> ids[WR_NLAYMAX];
+    for (int l = 0; l < used; l++) {
+        int same = -1;
+        for (int k = 0; k < l; k++) if (seg[k] == seg[l]) same = k;
+        if (same >= 0) { ids[l] = ids[same]; continue; }
+        ids[l].resize(wrlow::segments_of(nx, ny, pl.box, seg[l], nullptr, 0));
+        wrlow::segments_of(nx, ny, pl.box, seg[l], ids[l].data(), ids[l].size());
+    }
+    {
+        std::lock_guard<std::mutex> gather(pool->planes.gather_mu);
+        for (int l = 0; l < used; l++) {
+            if (int rc = plane_prepare(c, l, n, true, false, nullptr, nullptr, false)) return rc;
+            bufs.blob[l] = plane_scratch(c, info->len_enc_vec[l]);
+            bufs.work[l] = plane_scratch(c, wrk::seg_decode_list_work_bytes(nseg[l], ids[l].size()));
+            if (!bufs.blob[l].p || !bufs.work[l].p) return WR_ERR_HIP;
+            if (int rc = bufs.events(l)) return rc;
+        }
+    }
+    // ---- stage "up": per plane the offsets table, the id list and the streams of the listed segments
+    size_t bytes_up = 0;
+    for (int l = 0; l < used; l++) {
+        const uint8_t* const front = data_enc + off[l];
+        std::vector<unsigned long long> offs((size_t)nseg[l] + 1);
+        unsigned long long run = 0;
+        for (uint32_t k = 0; k < nseg[l]; k++) { offs[k] = run; run += wrseg::get_u32(front + wrseg::kHeaderBytes + 4 * (size_t)k); }
+        offs[nseg[l]] = run;
+        HIPCHK(hipMemcpy(bufs.work[l].p + 256, offs.data(), offs.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+        if (!ids[l].empty())
+            HIPCHK(hipMemcpy(wrk::seg_decode_list_ids(bufs.work[l].p, nseg[l]), ids[l].data(), ids[l].size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (int rc = seg_upload_streams(c, bufs.blob[l].p, front, wrseg::kHeaderBytes + 4 * (size_t)nseg[l], offs, ids[l], &local.h2d_ms, &bytes_up)) return rc;
+    }
+    g_stat[WR_STAT_LOWRES_BYTES_UP] += bytes_up;
+    const double t_coded = now();
+    SlotNeed need;
+    need.scratch_elems = nbox;
+    if (fld.host || fld.host_f32) need.field_elems = nbox;
+    SlotLease slot;
+    if (int rc = slot.acquire(c, need)) return rc;
+    const double t_phase = now();
+    wrk::DequantParams p;
+    memset(&p, 0, sizeof p);
+    p.nlay = used;
+    for (int l = 0; l < used; l++) {
+        p.deps[l] = info->deps_vec[l]; p.minval[l] = info->minval_vec[l]; p.q[l] = c->ps[l].ref;
+        if (!wrk::plane_ref_covers(p.q[l], n)) return fail(WR_ERR_HIP, "internal: the device buffer of plane " + std::to_string(l) + " has a hole");
+    }
+    double* d_box = fld.dev ? fld.dev : slot->field;
+    float* d_f32 = nullptr;
+    int rc = WR_OK;
+    {
+        StageLock cu(pool->cu_mu);
+        clock_warmup(c, nbox);
+        for (int l = 0; l < used; l++) {
+            launch_note(c, "seg_decode_list", l, bufs.blob[l].p, n, bufs.work[l].p, p.q[l]);
+            HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
+            wrk::seg_decode_list(bufs.blob[l].p, info->len_enc_vec[l], p.q[l], n, seg[l], bufs.work[l].p, ids[l].size(), c->stream);
+            HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
+            g_stat[WR_STAT_LOWRES_SEGMENTS] += ids[l].size();
+        }
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented decoder launch failed" + launch_describe(c));
+        // the dequantizer only runs on planes whose every listed segment decoded
+        unsigned int bad[WR_NLAYMAX] = {0};
+        for (int l = 0; l < used; l++) HIPCHK(hipMemcpyAsync(&bad[l], bufs.work[l].p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the segmented decoder failed on the device" + launch_describe(c));
+        for (int l = 0; l < used; l++) {
+            if (bad[l]) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + std::to_string(bad[l]) + " segment(s) do not decode to their symbols");
+            local.plane_coder_s[l] = bufs.seconds(l);
+            local.rangecoder += local.plane_coder_s[l];
+        }
+        launch_note(c, "dequant_box", used - 1, d_box, nbox, nullptr, p.q[used - 1]);
+        rc = lowres_from_planes(c, slot.get(), d_box, nx, ny, pl, p, fld.host_f32 ? &d_f32 : nullptr);
+        if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
+        if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the decoder's kernel stage failed on the device" + launch_describe(c));
+        pool->last_stage_end.store(now());
+    }
+    if (rc) return rc;
+    if (fld.host) {
+        if ((rc = xfer_field(c, &c->x_field, fld.host, d_box, nbox * sizeof(double), kDown)) != WR_OK) return rc;
+        local.d2h_ms = (float)c->x_field.ms;
+    } else if (fld.host_f32) {
+        if ((rc = xfer_field(c, &c->x_field, fld.host_f32, d_f32, nbox * sizeof(float), kDown)) != WR_OK) return rc;
+        local.d2h_ms = (float)c->x_field.ms;
+    }
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev_a, c->ev_b)); local.quant_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev_b, c->ev_c)); local.transform_ms = ms;
+    local.total = now() - t0;
+    local.gpu = now() - t_phase;
+    local.wait = t_phase - t_coded;
+    local.transfer = t_coded - t0;
+    if (tm) *tm = local;
+    return WR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1369,6 +1618,28 @@ int wr_decode_device_seg(wr_ctx* c, double* d_fld, int nx, int ny, int nz, const
     FieldRef f; f.dev = d_fld;
     if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
     return decode_seg_impl(c, f, nx, ny, nz, info, data_enc, data_len, tm);
+}
+
+int wr_decode_host_seg_lowres(wr_ctx* c, double* h_out, int nx, int ny, int nz, int level, int max_planes, const wr_enc_info* info,
+                              const unsigned char* data_enc, size_t data_len, wr_timings* tm)
+{
+    FieldRef f; f.host = h_out;
+    return decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, info, data_enc, data_len, tm);
+}
+
+int wr_decode_host_seg_lowres_f32(wr_ctx* c, float* h_out, int nx, int ny, int nz, int level, int max_planes, const wr_enc_info* info,
+                                  const unsigned char* data_enc, size_t data_len, wr_timings* tm)
+{
+    FieldRef f; f.host_f32 = h_out;
+    return decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, info, data_enc, data_len, tm);
+}
+
+int wr_decode_device_seg_lowres(wr_ctx* c, double* d_out, int nx, int ny, int nz, int level, int max_planes, const wr_enc_info* info,
+                                const unsigned char* data_enc, size_t data_len, wr_timings* tm)
+{
+    FieldRef f; f.dev = d_out;
+    if (!d_out) return fail(WR_ERR_ARG, "null device output pointer");
+    return decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, info, data_enc, data_len, tm);
 }
 
 }  // extern "C"

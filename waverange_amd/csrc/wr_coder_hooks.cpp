@@ -2,6 +2,7 @@
 // interleaved planes, the coder pool, the 16-lane loops, and the windowed symbol path with host buffers standing in for
 // device-resident planes (test hooks).
 #include "wr_internal.h"
+#include "wr_lowres.h"
 #include "wr_segcoder.h"
 
 using namespace wri;
@@ -190,6 +191,32 @@ int wr_seg_decode_host_ref(const unsigned char* blob, size_t len, unsigned char*
         at += l;
     }
     return WR_OK;
+}
+
+// ---- the geometry of a low-resolution decode (wr_lowres.h): host only, no device is touched
+int wr_lowres_dims(int nx, int ny, int nz, int level, int* bx, int* by, int* bz)
+{
+    if (nx < 1 || ny < 1 || nz < 1) return fail(WR_ERR_ARG, "non-positive dimension");
+    if (!wrlow::level_ok(level)) return fail(WR_ERR_ARG, "level must be in [0, 4]");
+    const wrlow::Box b = wrlow::box_of(nx, ny, nz, level);
+    if (bx) *bx = b.bx;
+    if (by) *by = b.by;
+    if (bz) *bz = b.bz;
+    return WR_OK;
+}
+
+double wr_lowres_scale(int nx, int ny, int nz, int level)
+{
+    if (nx < 1 || ny < 1 || nz < 1 || !wrlow::level_ok(level)) { fail(WR_ERR_ARG, "non-positive dimension or level outside [0, 4]"); return 0.0; }
+    return wrlow::scale_of(wrlow::box_of(nx, ny, nz, level));
+}
+
+size_t wr_seg_lowres_segments(int nx, int ny, int nz, int level, unsigned seg, uint32_t* ids, size_t cap)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
+    if (nx < 1 || ny < 1 || nz < 1 || !wrlow::level_ok(level)) { fail(WR_ERR_ARG, "non-positive dimension or level outside [0, 4]"); return 0; }
+    return wrlow::segments_of(nx, ny, wrlow::box_of(nx, ny, nz, level), seg, ids, ids ? cap : 0);
 }
 
 }  // extern "C"

@@ -134,6 +134,22 @@ void seg_encode(const PlaneRef& sym, size_t n, unsigned seg, uint8_t* stage, uin
 // has VALIDATED on the host), then a u32 flag per segment (0: decoded).  A lane writes only its segment's symbols.
 size_t seg_decode_work_bytes(size_t nseg);
 void seg_decode(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, hipStream_t st);
+// The same over a subset of the segments: `work` is seg_decode_list_work_bytes(nseg, nlist) bytes laid out as above, followed
+// by the nlist segment ids at seg_decode_list_ids(work, nseg) (u32, ascending, every one below nseg, put there by the
+// caller).  Lane j of the grid decodes segment ids[j]; only the bytes of those segments' streams are read from the blob,
+// only their symbols are written, flags[] is set for them alone.
+size_t seg_decode_list_work_bytes(size_t nseg, size_t nlist);
+uint32_t* seg_decode_list_ids(uint8_t* work, size_t nseg);
+void seg_decode_list(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, size_t nlist, hipStream_t st);
+
+// ---- low-resolution decode (wr_lowres.hip): the corner box [0,bx) x [0,by) x [0,bz) of the coefficient array, gathered out
+// of the planes.  box[(z*by + y)*bx + x] = sum over the planes, in order, of q_l[(y + ny*z)*nx + x] * deps_l + minval_l (the
+// arithmetic of dequant_accum).  Nothing of a plane outside those by*bz runs of bx bytes is read.
+void dequant_box(double* box, int bx, int by, int bz, int nx, int ny, const DequantParams& p, hipStream_t st);
+// dst[i] = src[i] * s (one multiply, one rounding), narrowed to fp32 as the C cast in the second form.  The fp64 form may run
+// in place; 16-byte aligned src, 8-byte aligned dst.
+void scale_f64(const double* src, double* dst, size_t n, double s, hipStream_t st);
+void scale_narrow_f64(const double* src, float* dst, size_t n, double s, hipStream_t st);
 
 }  // namespace wrk
 

@@ -9,7 +9,8 @@
 //                  staging buffer (stride = the segment bound, 4-byte aligned); lens[k] = its length
 //   k_seg_scan     exclusive scan of lens -> offs, the blob's header and index, the blob's length
 //   k_seg_gather   staging regions -> the blob, coalesced, destination-aligned words
-//   k_seg_decode   lane k: stream of segment k (at offs[k] in the blob) -> the plane's symbols [k*seg, k*seg + bs)
+//   k_seg_decode   lane k: stream of segment k (at offs[k] in the blob) -> the plane's symbols [k*seg, k*seg + bs); with a
+//                  list of segment ids, lane j takes segment ids[j] and the others are left alone (a low-resolution decode)
 #include "wr_kernels.h"
 #include "wr_segcoder.h"
 
@@ -197,12 +198,20 @@ __global__ __launch_bounds__(kGatherThreads) void k_seg_gather(const uint32_t* s
     }
 }
 
+// kList: lane j of the grid takes segment ids[j], j < nlist (ascending ids below nseg: the host made the list); otherwise
+// segment j, and ids / nlist are not looked at.  flags[] is indexed by the segment either way.
+template <bool kList>
 __global__ __launch_bounds__(kLanes) void k_seg_decode(const uint8_t* blob, size_t blob_len, const unsigned long long* offs, PlaneRef sym, size_t n,
-                                                       uint32_t seg, uint32_t nseg, uint32_t* flags, unsigned int* bad)
+                                                       uint32_t seg, uint32_t nseg, uint32_t* flags, unsigned int* bad, const uint32_t* ids,
+                                                       uint32_t nlist)
 {
     __shared__ uint32_t tab[256 * kLanes];
     const uint32_t lane = threadIdx.x;
-    const size_t k = (size_t)blockIdx.x * kLanes + lane;
+    size_t k = (size_t)blockIdx.x * kLanes + lane;
+    if (kList) {
+        if (k >= nlist) return;
+        k = ids[k];
+    }
     if (k >= nseg) return;
     LdsTable t{tab + lane};
     const size_t base = k * seg;
@@ -260,8 +269,24 @@ void seg_decode(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_
     (void)hipMemsetAsync(bad, 0, sizeof *bad, st);
     const unsigned long long* const offs = reinterpret_cast<const unsigned long long*>(work + 256);
     uint32_t* const flags = reinterpret_cast<uint32_t*>(work + 256 + ((8 * (nseg + 1) + 255) & ~(size_t)255));
-    hipLaunchKernelGGL(k_seg_decode, dim3((unsigned)((nseg + kLanes - 1) / kLanes)), dim3(kLanes), 0, st, blob, blob_len, offs, sym, n, (uint32_t)seg,
-                       (uint32_t)nseg, flags, bad);
+    hipLaunchKernelGGL(k_seg_decode<false>, dim3((unsigned)((nseg + kLanes - 1) / kLanes)), dim3(kLanes), 0, st, blob, blob_len, offs, sym, n,
+                       (uint32_t)seg, (uint32_t)nseg, flags, bad, (const uint32_t*)nullptr, 0u);
+}
+
+size_t seg_decode_list_work_bytes(size_t nseg, size_t nlist) { return ((seg_decode_work_bytes(nseg) + 255) & ~(size_t)255) + 4 * nlist; }
+
+uint32_t* seg_decode_list_ids(uint8_t* work, size_t nseg) { return reinterpret_cast<uint32_t*>(work + ((seg_decode_work_bytes(nseg) + 255) & ~(size_t)255)); }
+
+void seg_decode_list(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, size_t nlist, hipStream_t st)
+{
+    const size_t nseg = wrseg::seg_count(n, seg);
+    unsigned int* const bad = reinterpret_cast<unsigned int*>(work);
+    (void)hipMemsetAsync(bad, 0, sizeof *bad, st);
+    if (!nseg || !nlist) return;
+    const unsigned long long* const offs = reinterpret_cast<const unsigned long long*>(work + 256);
+    uint32_t* const flags = reinterpret_cast<uint32_t*>(work + 256 + ((8 * (nseg + 1) + 255) & ~(size_t)255));
+    hipLaunchKernelGGL(k_seg_decode<true>, dim3((unsigned)((nlist + kLanes - 1) / kLanes)), dim3(kLanes), 0, st, blob, blob_len, offs, sym, n,
+                       (uint32_t)seg, (uint32_t)nseg, flags, bad, seg_decode_list_ids(work, nseg), (uint32_t)nlist);
 }
 
 }  // namespace wrk
