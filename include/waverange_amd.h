@@ -413,6 +413,23 @@ void wr_decoding_wrap_f32(int nx, int ny, int nz, float *fld_1d, double *tolabs,
 /* waveletcdf97_3d on a host array, in place */
 int wr_transform_host(wr_ctx *ctx, double *h_fld, int nx, int ny, int nz, int lvl);
 
+/* --- which kernels a transform of this shape runs on (host only: no device call, no context).  The finest `levels` levels
+ * of a four-level forward (inverse != 0: inverse) transform can run on the fused single-pass kernels, the coarser ones run on
+ * the general kernels; `used` says whether wr_dev_transform(.., +-4) and the codec take the fused path for this shape at all
+ * (two fused levels, or one of a field of 2^21 samples or more), before the WR_NO_FUSED environment switch is looked at.
+ * level[l], l < levels, finest first, is the launch of fused level l on its box (nx >> l) x (ny >> l) x (nz >> l), from the
+ * function the launch itself takes its grid from: tiles_x * tiles_y workgroup columns, each cut along z into zsegs segments
+ * of zps z-pairs, the last one of zlast.  Entries from `levels` on are zero.  A non-positive dimension or out == NULL:
+ * WR_ERR_ARG. */
+typedef struct wr_fused_level {
+    int tiles_x, tiles_y, zps, zsegs, zlast;
+} wr_fused_level;
+typedef struct wr_fused_plan_t {
+    int levels, used;
+    wr_fused_level level[4];
+} wr_fused_plan_t;
+int wr_fused_plan(int nx, int ny, int nz, int inverse, wr_fused_plan_t *out);
+
 /* --- host range coder alone (one plane stream), rows a6/a7/a10 of SURVEY.md 8a */
 size_t wr_range_encode_bound(size_t n);
 /* the same for a plane whose byte histograms per 60000-symbol block are known (unsigned short[256] per block, n/60000+1

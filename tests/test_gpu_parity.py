@@ -484,7 +484,9 @@ def test_random_shapes_tolerances_and_field_kinds_vs_oracle(ctx, oracle):
 def test_zero_minimum_and_nans_on_the_fused_minmax_path(ctx, oracle, shape):
     """All four levels fused: min/max of the field and of the coefficients come out of the forward kernels.  The
     reference's scan semantics must survive that: the sign of a zero minimum is the sign of the LAST zero in
-    memory order (it shows in midval / minval_vec), NaN samples are skipped by fmin/fmax."""
+    memory order (it shows in midval / minval_vec).  (No NaN sample here: it would spread through the transform into
+    a float-to-byte cast that the reference leaves undefined, so nothing could be pinned; min/max alone skip NaNs
+    as fmin / fmax do, test_minmax_and_zero_sign.)"""
     nx, ny, nz = shape
     rs = np.random.RandomState(nx)
     f = np.abs(synth.field(nx, ny, nz, seed=8)) + 0.25

@@ -60,6 +60,15 @@ class Timings(C.Structure):
         return {k: (list(getattr(self, k)) if k == "plane_coder_s" else getattr(self, k)) for k, _ in self._fields_}
 
 
+class FusedLevel(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("tiles_x", "tiles_y", "zps", "zsegs", "zlast")]
+
+
+class FusedPlan(C.Structure):
+    """wr_fused_plan_t"""
+    _fields_ = [("levels", C.c_int), ("used", C.c_int), ("level", FusedLevel * 4)]
+
+
 class WaveRangeError(RuntimeError):
     pass
 
@@ -171,6 +180,7 @@ def lib():
                                             C.POINTER(Timings)]
     L.wr_decode_host_seg_lowres_f32.argtypes = L.wr_decode_host_seg_lowres.argtypes
     L.wr_decode_device_seg_lowres.argtypes = L.wr_decode_host_seg_lowres.argtypes
+    L.wr_fused_plan.argtypes = [C.c_int] * 4 + [C.POINTER(FusedPlan)]
     L.wr_bench_transform.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]
     # drop-in symbols (reference src/core/wrappers.h:53,70,75)
     L.setup_wr.argtypes = [C.c_int] * 3 + [_u8p, _ulp]
@@ -378,6 +388,16 @@ def lowres_shape(shape, level):
     bx, by, bz = C.c_int(), C.c_int(), C.c_int()
     _check(lib().wr_lowres_dims(nx, ny, nz, level, C.byref(bx), C.byref(by), C.byref(bz)))
     return bz.value, by.value, bx.value
+
+
+def fused_plan(shape, inverse=False):
+    """Which kernels a four-level transform of a field shaped (nz, ny, nx) runs on (wr_fused_plan; host only, needs no GPU):
+    dict(levels, used, grid), grid = one (tiles_x, tiles_y, zps, zsegs, zlast) per fused level, finest first."""
+    nz, ny, nx = shape
+    p = FusedPlan()
+    _check(lib().wr_fused_plan(nx, ny, nz, int(bool(inverse)), C.byref(p)))
+    return dict(levels=p.levels, used=bool(p.used),
+                grid=[tuple(getattr(p.level[l], k) for k, _ in FusedLevel._fields_) for l in range(p.levels)])
 
 
 def lowres_scale(shape, level):

@@ -962,14 +962,36 @@ extern "C" __attribute__((visibility("default"))) unsigned long long* wr_stamp_b
 }
 #endif
 
+// Launch geometry of one fused level on a box of n1 x n2 x n3 samples: the one place it is worked out, for the forward and
+// the inverse launches and for fused_plan()
+FusedGrid fused_grid(int n1, int n2, int n3, bool inverse)
+{
+    const int m1 = n1 / 2, m2 = n2 / 2, m3 = n3 / 2;
+    const int txp = inverse ? ITXP : TXP, typ = inverse ? ITYP : TYP;
+    FusedGrid g;
+    g.tiles_x = (m1 + txp - 1) / txp;
+    g.tiles_y = (m2 + typ - 1) / typ;
+    g.zps = pick_zps(g.tiles_x * g.tiles_y, m3, 256 * (int)(160 * 1024 / (inverse ? LDS_INV : LDS_BYTES)));
+    g.zsegs = (m3 + g.zps - 1) / g.zps;
+    g.zlast = m3 - (g.zsegs - 1) * g.zps;
+    return g;
+}
+
+static dim3 grid_dim(const FusedGrid& g) { return dim3(g.tiles_x * g.tiles_y, g.zsegs); }
+
 // grid of one fused forward level
 static dim3 fwd_grid(int n1, int n2, int n3, int* zps_out)
 {
-    const int m1 = n1 / 2, m2 = n2 / 2, m3 = n3 / 2;
-    const int tiles = ((m1 + TXP - 1) / TXP) * ((m2 + TYP - 1) / TYP);
-    const int zps = pick_zps(tiles, m3, 256 * (int)(160 * 1024 / LDS_BYTES));
-    *zps_out = zps;
-    return dim3(tiles, (m3 + zps - 1) / zps);
+    const FusedGrid g = fused_grid(n1, n2, n3, false);
+    *zps_out = g.zps;
+    return grid_dim(g);
+}
+
+int fused_plan(int nx, int ny, int nz, bool inverse, FusedGrid* levels)
+{
+    const int nfused = fused_levels(nx, ny, nz, inverse);
+    for (int l = 0; l < nfused; l++) levels[l] = fused_grid(nx >> l, ny >> l, nz >> l, inverse);
+    return nfused;
 }
 
 // min/max records (4 doubles each) transform_fwd_fused writes when it reduces min/max on the way; 0 if the
@@ -1144,15 +1166,15 @@ static void inv_fused(double* src, TOUT* dst, double* scratch, double* lowbuf, i
     for (int k = 3; k >= nfused; k--) transform_level(src, scratch, nx, ny, nz, k, true, st);
     for (int l = nfused - 1; l >= 0; l--) {
         const int n1 = nx >> l, n2 = ny >> l, n3 = nz >> l;
-        const int m1 = n1 / 2, m2 = n2 / 2, m3 = n3 / 2;
+        const int m1 = n1 / 2, m2 = n2 / 2;
         const double* lo;
         size_t lo_sy, lo_sz;
         // the coarsest fused level finds its low-pass octant in the coefficient array itself
         if (l == nfused - 1) { lo = src; lo_sy = f_sy; lo_sz = f_sz; }
         else { lo = cbuf[l + 1]; lo_sy = (size_t)m1; lo_sz = (size_t)m1 * m2; }
-        const int tiles = ((m1 + ITXP - 1) / ITXP) * ((m2 + ITYP - 1) / ITYP);
-        const int zps = pick_zps(tiles, m3, 256 * (int)(160 * 1024 / LDS_INV));
-        dim3 grid(tiles, (m3 + zps - 1) / zps);
+        const FusedGrid g = fused_grid(n1, n2, n3, true);
+        const int zps = g.zps;
+        const dim3 grid = grid_dim(g);
 #ifdef WR_STAMP
 #define WR_INV_STAMP_ARG , l == 0 ? g_stamp_buf : nullptr
 #else

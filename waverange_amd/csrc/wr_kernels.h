@@ -164,6 +164,12 @@ namespace wrk {
 int fused_levels(int nx, int ny, int nz, bool inverse);
 bool fused_ok(int nx, int ny, int nz, int lvl);
 size_t fused_lowbuf_elems(int nx, int ny, int nz);
+// Launch geometry of one fused level: tiles in x and y (gridDim.x = tiles_x * tiles_y), z-pairs per segment, z segments
+// (gridDim.y) and the z-pairs of the last segment.  fused_plan() fills levels[0 .. return value) (room for 4), finest level
+// first, from the function the launches take their grids from; host only.
+struct FusedGrid { int tiles_x, tiles_y, zps, zsegs, zlast; };
+FusedGrid fused_grid(int n1, int n2, int n3, bool inverse);
+int fused_plan(int nx, int ny, int nz, bool inverse, FusedGrid* levels);
 // one-time set-up of the fused kernels (their dynamic LDS limit); nullptr, or why they cannot run on this device
 const char* fused_prepare();
 // mm_partial (fused_minmax_records() x 4 doubles, device) and mm_result (4 doubles, device): when given -- and all

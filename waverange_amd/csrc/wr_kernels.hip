@@ -433,6 +433,13 @@ void narrow_f64(const double* src, float* dst, size_t n, hipStream_t st)
 // quantizer plane, fused: q = (uchar)(aopt*x + bopt); r = x - (q*deps + minval); min/max(r)
 // Each lane handles 2 adjacent elements per step (16-B load, 2-B plane store, 16-B store).
 // =====================================================================================
+// (unsigned char)(double) as the reference's x86-64 builds perform it: cvttsd2si to 32 bits, then the low byte.  For the values
+// a quantizer plane is made of, [0.5, 255.5], that is C's truncation toward zero.  Outside the int range and for a NaN C leaves
+// the cast undefined, and a field can get there: with a residual of subnormals deps falls below 2^-1024, aopt = 1 / deps is
+// infinite and aopt * x + bopt is +inf or NaN.  cvttsd2si then gives 0x80000000 ("integer indefinite"): byte 0, where
+// v_cvt_i32_f64 saturates +inf to 0x7fffffff: byte 255.  The oracle and the compiled reference code such planes as zeros.
+__device__ inline unsigned char quant_byte(double fq) { return (unsigned char)(fabs(fq) < 0x1p31 ? (int)fq : 0); }
+
 template <bool RESID>
 __global__ __launch_bounds__(WR_RED_THREADS) void k_quant(double* __restrict__ x, size_t n, double aopt,
                                                           double bopt, double deps, double minval,
@@ -445,9 +452,9 @@ __global__ __launch_bounds__(WR_RED_THREADS) void k_quant(double* __restrict__ x
     uchar2* q2 = reinterpret_cast<uchar2*>(q);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (size_t)gridDim.x * blockDim.x) {
         double2 v = x2[i];
-        // (unsigned char)(double): C truncation toward zero of a value in [0.5, 255.5]
-        const unsigned char qa = (unsigned char)(int)(aopt * v.x + bopt);
-        const unsigned char qb = (unsigned char)(int)(aopt * v.y + bopt);
+        // (unsigned char)(double): quant_byte
+        const unsigned char qa = quant_byte(aopt * v.x + bopt);
+        const unsigned char qb = quant_byte(aopt * v.y + bopt);
         q2[i] = make_uchar2(qa, qb);
         if (RESID) {
             v.x = v.x - ((double)qa * deps + minval);
@@ -459,7 +466,7 @@ __global__ __launch_bounds__(WR_RED_THREADS) void k_quant(double* __restrict__ x
     }
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         double v = x[n - 1];
-        const unsigned char qa = (unsigned char)(int)(aopt * v + bopt);
+        const unsigned char qa = quant_byte(aopt * v + bopt);
         q[n - 1] = qa;
         if (RESID) {
             v = v - ((double)qa * deps + minval);
@@ -490,8 +497,8 @@ __global__ __launch_bounds__(WR_RED_THREADS) void k_quant_lds(double* __restrict
         for (int j = 0; j < Q_CHUNK / 512; j++) v[j] = x2[j * 256 + t];
 #pragma unroll
         for (int j = 0; j < Q_CHUNK / 512; j++) {
-            const unsigned char qa = (unsigned char)(int)(aopt * v[j].x + bopt);
-            const unsigned char qb = (unsigned char)(int)(aopt * v[j].y + bopt);
+            const unsigned char qa = quant_byte(aopt * v[j].x + bopt);
+            const unsigned char qb = quant_byte(aopt * v[j].y + bopt);
             sq[j * 256 + t] = make_uchar2(qa, qb);
             if (RESID) {
                 v[j].x = v[j].x - ((double)qa * deps + minval);
@@ -615,8 +622,8 @@ __global__ __launch_bounds__(WR_RED_THREADS) void k_quant_blk(double* __restrict
                     const double pa = prev.aopt[p], pb = prev.bopt[p], pd = prev.deps[p], pm = prev.minval[p];
 #pragma unroll
                     for (int j = 0; j < QW / 128; j++) {
-                        const unsigned char qa = (unsigned char)(int)(pa * v[j].x + pb);
-                        const unsigned char qb = (unsigned char)(int)(pa * v[j].y + pb);
+                        const unsigned char qa = quant_byte(pa * v[j].x + pb);
+                        const unsigned char qb = quant_byte(pa * v[j].y + pb);
                         v[j].x = v[j].x - ((double)qa * pd + pm);
                         v[j].y = v[j].y - ((double)qb * pd + pm);
                     }
@@ -624,9 +631,9 @@ __global__ __launch_bounds__(WR_RED_THREADS) void k_quant_blk(double* __restrict
             }
 #pragma unroll
             for (int j = 0; j < QW / 128; j++) {
-                // (unsigned char)(double): C truncation toward zero of a value in [0.5, 255.5]
-                const unsigned char qa = (unsigned char)(int)(aopt * v[j].x + bopt);
-                const unsigned char qb = (unsigned char)(int)(aopt * v[j].y + bopt);
+                // (unsigned char)(double): quant_byte
+                const unsigned char qa = quant_byte(aopt * v[j].x + bopt);
+                const unsigned char qb = quant_byte(aopt * v[j].y + bopt);
                 sq[w][j * 64 + lane] = make_uchar2(qa, qb);
                 if (WRITE || MM) {
                     v[j].x = v[j].x - ((double)qa * deps + minval);
@@ -691,7 +698,7 @@ __global__ __launch_bounds__(WR_RED_THREADS) void k_resid_apply(double* __restri
 #pragma unroll
         for (int p = 0; p < kQuantPrevMax; p++)
             if (p < prev.n) {
-                const unsigned char qa = (unsigned char)(int)(prev.aopt[p] * v + prev.bopt[p]);
+                const unsigned char qa = quant_byte(prev.aopt[p] * v + prev.bopt[p]);
                 v = v - ((double)qa * prev.deps[p] + prev.minval[p]);
             }
         x[i] = v;
@@ -761,7 +768,7 @@ __global__ __launch_bounds__(WR_RED_THREADS) void k_quant_local(double* __restri
         double v = x[jw];
         unsigned char qq;
         if (lc.span < mask) { qq = 0; v = minval; }
-        else qq = (unsigned char)(int)(aopt * v + bopt);
+        else qq = quant_byte(aopt * v + bopt);
         q[jw] = qq;
         v = v - ((double)qq * deps + minval);
         x[jw] = v;

@@ -1070,6 +1070,18 @@ int wr_dev_linf(wr_ctx* c, const double* d_a, const double* d_b, size_t n, doubl
     return WR_OK;
 }
 
+int wr_fused_plan(int nx, int ny, int nz, int inverse, wr_fused_plan_t* out)
+{
+    if (!out) return fail(WR_ERR_ARG, "wr_fused_plan: out is NULL");
+    memset(out, 0, sizeof *out);
+    if (nx < 1 || ny < 1 || nz < 1) return fail(WR_ERR_ARG, "non-positive dimension");
+    wrk::FusedGrid g[4];
+    out->levels = wrk::fused_plan(nx, ny, nz, inverse != 0, g);
+    out->used = wrk::fused_ok(nx, ny, nz, inverse ? -4 : 4);
+    for (int l = 0; l < out->levels; l++) out->level[l] = {g[l].tiles_x, g[l].tiles_y, g[l].zps, g[l].zsegs, g[l].zlast};
+    return WR_OK;
+}
+
 int wr_dev_transform(wr_ctx* c, double* d_fld, int nx, int ny, int nz, int lvl)
 {
     if (int rc = ctx_bind(c)) return rc;
