@@ -194,6 +194,8 @@ int wr_set_device_slots(int device, int nslots);
                                       (before: the same time in the pool's queues with their planes allocated), summed over calls */
 #define WR_STAT_LOWRES_SEGMENTS 11 /* segments the low-resolution decodes (wr_decode_*_seg_lowres) have launched, summed over planes */
 #define WR_STAT_LOWRES_BYTES_UP 12 /* coded payload bytes those calls have copied to the device (the offsets tables are not counted) */
+#define WR_STAT_ROI_SEGMENTS 13 /* segments the region decodes (wr_decode_*_seg_roi) have launched, summed over planes */
+#define WR_STAT_ROI_BYTES_UP 14 /* coded payload bytes those calls have copied to the device (the offsets tables are not counted) */
 unsigned long wr_stat(int what);
 /* Hands the idle buffers of the device's plane pool back to the device (the pool keeps the plane memory of finished calls for
  * the next ones: after a burst of concurrent calls that can be most of the HBM).  Buffers in use are not touched. */
@@ -395,6 +397,56 @@ int wr_decode_host_seg_lowres_f32(wr_ctx *ctx, float *h_out, int nx, int ny, int
 int wr_decode_device_seg_lowres(wr_ctx *ctx, double *d_out, int nx, int ny, int nz, int level, int max_planes,
                                 const wr_enc_info *info, const unsigned char *data_enc, size_t data_len,
                                 wr_timings *tm);
+/* ---- Region decode of segmented streams: a sub-box of the field (or of a low-resolution box) without decoding the field.
+ * D(r, p) is the low-resolution decode above before its fp32 narrowing; D(0, nlay) is the full decode.  For a level
+ * 0 <= r <= wlev, p planes (max_planes, 0 = all) and a half-open box roi = [x0,x1) x [y0,y1) x [z0,z1) in the coordinates of
+ * D(r, p), 0 <= lo < hi <= b_axis, b = h^r(n):
+ *   R(r, p, roi) is the contiguous copy of D(r, p) over the box, bit for bit, x fastest;
+ *   for fp32 output (float) of that, rounded as wr_decode_host_seg_f32 rounds;
+ *   a constant field (info->ntot_enc == 0) gives midval at the box's size;
+ *   an empty or out-of-range box and every argument the low-resolution decode refuses: WR_ERR_ARG.
+ * Lifting is local: with d = wlev - r levels still to invert an output sample depends on coefficients within a bounded
+ * distance, so the region is inverted inside a window.  Per axis, n the extent of the level-r box, [lo, hi) the region:
+ *   d = 0:  a = lo, b = hi
+ *   else    m(0) = 0, m(k) = 2 (m(k-1) + 2)   (4, 12, 28, 60);  A = 2^d
+ *           a = floor(max(0, lo - m(d)) / A) * A
+ *           b = ceil((hi + m(d)) / A) * A, replaced by n when it reaches or passes n
+ * A window starts on a multiple of 2^d (pair parity is the field's at every level) and ends on one or on the field's true end
+ * (its level extents w_l = ceil(b / 2^l) - a / 2^l follow the field's ceil chain, so the odd-length step of
+ * waveletcdf97_3d.c:314 happens where the field's does); each inverse level spoils at most 2 pairs beyond what a cut edge had
+ * already spoilt (the stages at waveletcdf97_3d.c:316-330), which is the recursion for m.
+ * The window's coefficient array W is wx*wy*wz doubles in the Mallat layout of its own extents;
+ * waveletcdf97_3d(wx, wy, wz, -d, W) inverts it as it stands.  It is filled from the coefficient array C of step 1 above: for a
+ * window point c = (cx, cy, cz),
+ *   lambda = the number of l in 1..d with c_axis < w_l(axis) on all three axes;  ell = min(lambda + 1, d)
+ *   per axis, with n_ell = h^ell(n) and a_ell = a >> ell:  f = a_ell + c  when c < w_ell,  n_ell + a_ell + (c - w_ell) otherwise
+ *   W[c] = C[fx + nx * (fy + ny * fz)]          (nx, ny: the extents of the FIELD, not of the level-r box)
+ * i.e. the low-pass box of level d plus up to seven detail octants per level, at most 29 source boxes.  The map is not
+ * separable per axis: a point that is a level-1 detail in x takes its y and z at level-1 granularity.
+ * The result is W inverted, cropped to [lo - a, hi - a) per axis and multiplied by s = wr_lowres_scale(nx, ny, nz, r), one
+ * multiply and one rounding.
+ * Segments: a plane cut at `seg` needs the segments the x-runs of those source boxes touch, and no others; only their bytes go
+ * to the device.  Every plane's header and index are validated as by wr_decode_host_seg before anything is launched. */
+typedef struct wr_box { int x0, y0, z0, x1, y1, z1; } wr_box;
+/* the window of a region, in the coordinates of the level's box; wlev is 0 or 4 (the stream's); host only */
+int wr_roi_window(int nx, int ny, int nz, int level, int wlev, const wr_box *roi, wr_box *win);
+/* ascending ids of the segments a region needs; conventions of wr_seg_lowres_segments */
+size_t wr_seg_roi_segments(int nx, int ny, int nz, int level, int wlev, const wr_box *roi, unsigned seg, uint32_t *ids,
+                           size_t cap);
+/* stage level, as wr_dev_decode_planes_lowres; d_out receives the region's elements */
+int wr_dev_decode_planes_roi(wr_ctx *ctx, double *d_out, int nx, int ny, int nz, int level, int max_planes,
+                             const wr_box *roi, const unsigned char *d_planes, const wr_enc_info *info);
+/* whole path, as wr_decode_host_seg_lowres / _f32 / wr_decode_device_seg_lowres; the output holds the region's elements.
+ * wr_timings: quant_ms is the window dequantiser, transform_ms the inverse on the window, the crop and the scaling. */
+int wr_decode_host_seg_roi(wr_ctx *ctx, double *h_out, int nx, int ny, int nz, int level, int max_planes,
+                           const wr_box *roi, const wr_enc_info *info, const unsigned char *data_enc, size_t data_len,
+                           wr_timings *tm);
+int wr_decode_host_seg_roi_f32(wr_ctx *ctx, float *h_out, int nx, int ny, int nz, int level, int max_planes,
+                               const wr_box *roi, const wr_enc_info *info, const unsigned char *data_enc, size_t data_len,
+                               wr_timings *tm);
+int wr_decode_device_seg_roi(wr_ctx *ctx, double *d_out, int nx, int ny, int nz, int level, int max_planes,
+                             const wr_box *roi, const wr_enc_info *info, const unsigned char *data_enc, size_t data_len,
+                             wr_timings *tm);
 /* host reference of the WRS1 format (its definition further up, on the calling thread): for tests and for readers without a GPU.
  * blob holds wr_seg_bound(n, seg) bytes; returns the blob's length (0: seg refused, wr_last_error says why). */
 size_t wr_seg_encode_host_ref(const unsigned char *sym, size_t n, unsigned seg, unsigned char *blob);

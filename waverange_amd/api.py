@@ -69,6 +69,11 @@ class FusedPlan(C.Structure):
     _fields_ = [("levels", C.c_int), ("used", C.c_int), ("level", FusedLevel * 4)]
 
 
+class Box(C.Structure):
+    """wr_box: the half-open box [x0, x1) x [y0, y1) x [z0, z1)"""
+    _fields_ = [(k, C.c_int) for k in ("x0", "y0", "z0", "x1", "y1", "z1")]
+
+
 class WaveRangeError(RuntimeError):
     pass
 
@@ -180,6 +185,14 @@ def lib():
                                             C.POINTER(Timings)]
     L.wr_decode_host_seg_lowres_f32.argtypes = L.wr_decode_host_seg_lowres.argtypes
     L.wr_decode_device_seg_lowres.argtypes = L.wr_decode_host_seg_lowres.argtypes
+    L.wr_roi_window.argtypes = [C.c_int] * 5 + [C.POINTER(Box), C.POINTER(Box)]
+    L.wr_seg_roi_segments.restype = C.c_size_t
+    L.wr_seg_roi_segments.argtypes = [C.c_int] * 5 + [C.POINTER(Box), C.c_uint, _vp, C.c_size_t]
+    L.wr_dev_decode_planes_roi.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Box), _vp, C.POINTER(EncInfo)]
+    L.wr_decode_host_seg_roi.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Box), C.POINTER(EncInfo), _vp, C.c_size_t,
+                                         C.POINTER(Timings)]
+    L.wr_decode_host_seg_roi_f32.argtypes = L.wr_decode_host_seg_roi.argtypes
+    L.wr_decode_device_seg_roi.argtypes = L.wr_decode_host_seg_roi.argtypes
     L.wr_fused_plan.argtypes = [C.c_int] * 4 + [C.POINTER(FusedPlan)]
     L.wr_bench_transform.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]
     # drop-in symbols (reference src/core/wrappers.h:53,70,75)
@@ -225,6 +238,7 @@ STAT_EARLY_DECODES, STAT_SLOTS_POPULATED, STAT_DEVICE_PLANE_BYTES, STAT_POOL_IDL
 STAT_POOL_QUEUE_MS, STAT_PLANE_WAIT_MS, STAT_HANDOVER_ERRORS, STAT_CLOCK_WARMUP_MS, STAT_DECODE_GATE_MS = 5, 6, 7, 8, 9
 STAT_WINDOW_WAIT_MS = 10
 STAT_LOWRES_SEGMENTS, STAT_LOWRES_BYTES_UP = 11, 12
+STAT_ROI_SEGMENTS, STAT_ROI_BYTES_UP = 13, 14
 
 
 def stat(what):
@@ -417,6 +431,39 @@ def seg_lowres_segments(shape, level, seg=0):
         raise WaveRangeError(lib().wr_last_error().decode())
     ids = np.empty(count, dtype=np.uint32)
     got = lib().wr_seg_lowres_segments(nx, ny, nz, level, seg, ids.ctypes.data, ids.size)
+    assert got == count
+    return ids
+
+
+def _box(roi):
+    """wr_box of a region given as ((z0, z1), (y0, y1), (x0, x1))"""
+    (z0, z1), (y0, y1), (x0, x1) = roi
+    return Box(int(x0), int(y0), int(z0), int(x1), int(y1), int(z1))
+
+
+def roi_shape(roi):
+    """(cz, cy, cx): the shape of the array a region decode of `roi` returns."""
+    return tuple(int(hi) - int(lo) for lo, hi in roi)
+
+
+def roi_window(shape, level, roi, wlev=4):
+    """((a, b) for z, y, x): the window of the box of `level` that a region decode of `roi` inverts (wr_roi_window); shape is
+    the coded field's (nz, ny, nx), roi is ((z0, z1), (y0, y1), (x0, x1)) in the coordinates of that box."""
+    nz, ny, nx = shape
+    r, w = _box(roi), Box()
+    _check(lib().wr_roi_window(nx, ny, nz, level, wlev, C.byref(r), C.byref(w)))
+    return (w.z0, w.z1), (w.y0, w.y1), (w.x0, w.x1)
+
+
+def seg_roi_segments(shape, level, roi, seg=0, wlev=4):
+    """Ascending ids (uint32) of the segments of a plane cut at `seg` that a region decode needs (seg = 0: SEG_DEFAULT)."""
+    nz, ny, nx = shape
+    r = _box(roi)
+    count = lib().wr_seg_roi_segments(nx, ny, nz, level, wlev, C.byref(r), seg, None, 0)
+    if not count:
+        raise WaveRangeError(lib().wr_last_error().decode())
+    ids = np.empty(count, dtype=np.uint32)
+    got = lib().wr_seg_roi_segments(nx, ny, nz, level, wlev, C.byref(r), seg, ids.ctypes.data, ids.size)
     assert got == count
     return ids
 
@@ -833,6 +880,39 @@ class Context:
     def decode_seg_lowres(self, buf, shape, level, enc, max_planes=0):
         """decode_host_seg_lowres into device memory: `buf` holds the box's elements as float64."""
         return self._decode_seg_lowres(lib().wr_decode_device_seg_lowres, buf.ptr, shape, level, enc, max_planes)
+
+    # ---- region decode: the sub-box `roi` = ((z0, z1), (y0, y1), (x0, x1)) of the box of `level`, out of the first max_planes planes
+    def decode_planes_roi(self, buf, shape, level, roi, planes, info, max_planes=0):
+        """Stage level: `planes` as encode_planes left them; `buf` receives the region as float64."""
+        nz, ny, nx = shape
+        r = _box(roi)
+        _check(lib().wr_dev_decode_planes_roi(self.h, buf.ptr, nx, ny, nz, level, max_planes, C.byref(r), planes.ptr, C.byref(info)))
+
+    def _decode_seg_roi(self, fn, ptr, shape, level, roi, enc, max_planes):
+        nz, ny, nx = shape
+        info = EncInfo.from_dict(enc)
+        tm = Timings()
+        r = _box(roi)
+        data = np.ascontiguousarray(enc["data"], dtype=np.uint8)
+        if data.size == 0:
+            data = np.zeros(1, dtype=np.uint8)
+        _check(fn(self.h, ptr, nx, ny, nz, level, max_planes, C.byref(r), C.byref(info), data.ctypes.data, data.size, C.byref(tm)))
+        return tm.as_dict()
+
+    def decode_host_seg_roi(self, out, shape, level, roi, enc, max_planes=0):
+        """out: C-contiguous float64 array shaped roi_shape(roi); shape: the coded field's (nz, ny, nx)."""
+        assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"] and tuple(out.shape) == roi_shape(roi)
+        return self._decode_seg_roi(lib().wr_decode_host_seg_roi, out.ctypes.data, shape, level, roi, enc, max_planes)
+
+    def decode_host_seg_roi_f32(self, out, shape, level, roi, enc, max_planes=0):
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"]):
+            raise TypeError("decode_host_seg_roi_f32: a C-contiguous float32 array is required")
+        assert tuple(out.shape) == roi_shape(roi)
+        return self._decode_seg_roi(lib().wr_decode_host_seg_roi_f32, out.ctypes.data, shape, level, roi, enc, max_planes)
+
+    def decode_seg_roi(self, buf, shape, level, roi, enc, max_planes=0):
+        """decode_host_seg_roi into device memory: `buf` holds the region's elements as float64."""
+        return self._decode_seg_roi(lib().wr_decode_device_seg_roi, buf.ptr, shape, level, roi, enc, max_planes)
 
     def seg_encode_plane(self, plane, seg=0):
         """Stage level: one plane of symbols (a numpy uint8 array) through the coder kernels; returns the blob."""

@@ -7,6 +7,7 @@
 // exactly as wrappers.cpp:292-340 does.
 #include "wr_internal.h"
 #include "wr_lowres.h"
+#include "wr_roi.h"
 #include "wr_segcoder.h"
 
 using namespace wri;
@@ -309,11 +310,36 @@ int wr_dev_decode_planes(wr_ctx* c, double* d_fld, int nx, int ny, int nz, const
 // inverted on the box, the gain of the r levels that stay taken out
 namespace {
 
+// What a partial decode of segmented planes runs on: the box of level r (roi == false, the low-resolution decode) or the
+// window of a region of that box (roi == true, wr_roi.h).  The plan carries the segments the planes need, the gather, the
+// extents of the array the inverse runs on and the finish; the drivers below are the same for both.
 struct LowresPlan {
     wrlow::Box box;
     int planes;   // p
     int inverse;  // levels the box is still transformed by: wlev - r
     double scale;
+    bool roi = false;
+    wrroi::Geometry win;  // roi only
+    int stat_segments = WR_STAT_LOWRES_SEGMENTS, stat_bytes_up = WR_STAT_LOWRES_BYTES_UP;
+
+    size_t out_elems() const { return roi ? win.out_elems() : box.elems(); }   // what the caller receives
+    size_t work_elems() const { return roi ? win.elems() : box.elems(); }      // what the inverse runs on
+    bool fused() const { return roi && inverse == kWavLvl && use_fused(win.w(0), win.w(1), win.w(2), -kWavLvl); }
+    // the ascending ids of the segments a plane cut at `seg` needs
+    void segments(int nx, int ny, int nz, uint32_t seg, std::vector<uint32_t>* ids) const
+    {
+        ids->resize(roi ? wrroi::segments_of(nx, ny, nz, win, seg, nullptr, 0) : wrlow::segments_of(nx, ny, box, seg, nullptr, 0));
+        if (roi) wrroi::segments_of(nx, ny, nz, win, seg, ids->data(), ids->size());
+        else wrlow::segments_of(nx, ny, box, seg, ids->data(), ids->size());
+    }
+    // the work space of the kernel stage: a box is inverted in the caller's (or the staging) array, a window in the slot's
+    // field buffer whoever the caller is, and what comes out of it is smaller
+    void need(bool host, SlotNeed* nd) const
+    {
+        nd->scratch_elems = work_elems();
+        if (host || roi) nd->field_elems = work_elems();
+        if (fused()) nd->lowbuf_elems = wrk::fused_lowbuf_elems(win.w(0), win.w(1), win.w(2));
+    }
 };
 
 int lowres_plan(int nx, int ny, int nz, int level, int max_planes, const wr_enc_info* info, LowresPlan* pl)
@@ -327,6 +353,19 @@ int lowres_plan(int nx, int ny, int nz, int level, int max_planes, const wr_enc_
     pl->planes = max_planes ? max_planes : (int)info->nlay;
     pl->inverse = (int)info->wlev - level;
     pl->scale = wrlow::scale_of(pl->box);
+    return WR_OK;
+}
+
+// roi == nullptr: the plan of the low-resolution decode
+int region_plan(int nx, int ny, int nz, int level, int max_planes, const wr_box* roi, const wr_enc_info* info, LowresPlan* pl)
+{
+    if (int rc = lowres_plan(nx, ny, nz, level, max_planes, info, pl)) return rc;
+    if (!roi) return WR_OK;
+    if (!wrroi::roi_ok(pl->box, *roi)) return fail(WR_ERR_ARG, "the region is empty or reaches outside the box of the level");
+    pl->roi = true;
+    pl->win = wrroi::geometry_of(pl->box, pl->inverse, *roi);
+    pl->stat_segments = WR_STAT_ROI_SEGMENTS;
+    pl->stat_bytes_up = WR_STAT_ROI_BYTES_UP;
     return WR_OK;
 }
 
@@ -350,26 +389,53 @@ int lowres_from_planes(wr_ctx* c, Slot* s, double* d_box, int nx, int ny, const 
     return WR_OK;
 }
 
-}  // namespace
-
-extern "C" int wr_dev_decode_planes_lowres(wr_ctx* c, double* d_out, int nx, int ny, int nz, int level, int max_planes, const unsigned char* d_planes,
-                                           const wr_enc_info* info)
+// The same for a region: the window's coefficients gathered, inverted in the slot (the fused kernels where the window's
+// extents allow them: out of place, from the scratch buffer into the field buffer; otherwise in place in the field buffer),
+// then the crop, scaled, into d_out -- or, d_out == nullptr (a host caller), into the scratch buffer, which the transform is
+// done with by then; *landed = where.  f32: the crop is narrowed.
+int roi_from_planes(wr_ctx* c, Slot* s, double* d_out, int nx, int ny, const LowresPlan& pl, const wrk::DequantParams& p, bool f32, void** landed)
 {
-    if (int rc = ctx_bind(c)) return rc;
-    if (int rc = check_dims(nx, ny, nz, d_out)) return rc;
-    if (!d_out || !info) return fail(WR_ERR_ARG, "null pointer");
-    LowresPlan pl;
-    if (int rc = lowres_plan(nx, ny, nz, level, max_planes, info, &pl)) return rc;
+    const wrroi::Geometry& g = pl.win;
+    const int wx = g.w(0), wy = g.w(1), wz = g.w(2);
+    wrk::WindowMap m;
+    memset(&m, 0, sizeof m);
+    m.nbox = g.nbox;
+    m.wx = (uint32_t)wx; m.wy = (uint32_t)wy; m.nx = (uint32_t)nx; m.ny = (uint32_t)ny;
+    for (int i = 0; i < g.nbox; i++) {
+        const wrroi::SrcBox& b = g.box[i];
+        m.box[i] = wrk::WindowBox{(uint32_t)b.src[0], (uint32_t)b.src[1], (uint32_t)b.src[2], (uint32_t)b.dst[0], (uint32_t)b.dst[1], (uint32_t)b.dst[2],
+                                  (uint32_t)b.len[0], (uint32_t)b.len[1], (uint32_t)b.len[2]};
+    }
+    const bool fused = pl.fused();
+    if (fused) if (const char* why = wrk::fused_prepare()) return fail(WR_ERR_HIP, why);
+    HIPCHK(hipEventRecord(c->ev_a, c->stream));
+    wrk::dequant_window(fused ? s->scratch : s->field, m, p, c->stream);
+    HIPCHK(hipEventRecord(c->ev_b, c->stream));
+    if (fused) wrk::transform_inv_fused(s->scratch, s->field, s->lowbuf, wx, wy, wz, c->stream);
+    else if (pl.inverse > 0) wrk::transform(s->field, s->scratch, wx, wy, wz, -pl.inverse, c->stream);
+    const wrk::CropBox crop{(uint32_t)wx, (uint32_t)wy, (uint32_t)(g.ax[0].lo - g.ax[0].a), (uint32_t)(g.ax[1].lo - g.ax[1].a),
+                            (uint32_t)(g.ax[2].lo - g.ax[2].a), (uint32_t)(g.ax[0].hi - g.ax[0].lo), (uint32_t)(g.ax[1].hi - g.ax[1].lo),
+                            (uint32_t)(g.ax[2].hi - g.ax[2].lo)};
+    *landed = d_out ? (void*)d_out : (void*)s->scratch;
+    if (f32) wrk::crop_scale_narrow_f64(s->field, reinterpret_cast<float*>(*landed), crop, pl.scale, c->stream);
+    else wrk::crop_scale_f64(s->field, reinterpret_cast<double*>(*landed), crop, pl.scale, c->stream);
+    HIPCHK(hipEventRecord(c->ev_c, c->stream));
+    return WR_OK;
+}
+
+// stage level: the plan's result from nlay full planes in device memory
+int decode_planes_plan(wr_ctx* c, double* d_out, int nx, int ny, int nz, const LowresPlan& pl, const unsigned char* d_planes, const wr_enc_info* info)
+{
     const size_t n = (size_t)nx * ny * nz;
     std::lock_guard<std::mutex> lk(c->mu);
     if (info->ntot_enc == 0 && info->nlay == 0) {  // a constant field, as wr_dev_decode_planes
-        wrk::fill(d_out, pl.box.elems(), info->midval, c->stream);
+        wrk::fill(d_out, pl.out_elems(), info->midval, c->stream);
         HIPCHK(hipStreamSynchronize(c->stream));
         return WR_OK;
     }
     if (!d_planes) return fail(WR_ERR_ARG, "null plane pointer");
     SlotNeed need;
-    need.scratch_elems = pl.box.elems();
+    pl.need(false, &need);
     SlotLease slot;
     if (int rc = slot.acquire(c, need)) return rc;
     StageLock cu(c->pool->cu_mu);
@@ -381,10 +447,35 @@ extern "C" int wr_dev_decode_planes_lowres(wr_ctx* c, double* d_out, int nx, int
         p.deps[l] = info->deps_vec[l];
         p.minval[l] = info->minval_vec[l];
     }
-    int rc = lowres_from_planes(c, slot.get(), d_out, nx, ny, pl, p, nullptr);
+    void* landed = nullptr;
+    int rc = pl.roi ? roi_from_planes(c, slot.get(), d_out, nx, ny, pl, p, false, &landed) : lowres_from_planes(c, slot.get(), d_out, nx, ny, pl, p, nullptr);
     if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
     if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the low-resolution kernel stage failed on the device");
     return rc;
+}
+
+}  // namespace
+
+extern "C" int wr_dev_decode_planes_lowres(wr_ctx* c, double* d_out, int nx, int ny, int nz, int level, int max_planes, const unsigned char* d_planes,
+                                           const wr_enc_info* info)
+{
+    if (int rc = ctx_bind(c)) return rc;
+    if (int rc = check_dims(nx, ny, nz, d_out)) return rc;
+    if (!d_out || !info) return fail(WR_ERR_ARG, "null pointer");
+    LowresPlan pl;
+    if (int rc = region_plan(nx, ny, nz, level, max_planes, nullptr, info, &pl)) return rc;
+    return decode_planes_plan(c, d_out, nx, ny, nz, pl, d_planes, info);
+}
+
+extern "C" int wr_dev_decode_planes_roi(wr_ctx* c, double* d_out, int nx, int ny, int nz, int level, int max_planes, const wr_box* roi,
+                                        const unsigned char* d_planes, const wr_enc_info* info)
+{
+    if (int rc = ctx_bind(c)) return rc;
+    if (int rc = check_dims(nx, ny, nz, d_out)) return rc;
+    if (!d_out || !info || !roi) return fail(WR_ERR_ARG, "null pointer");
+    LowresPlan pl;
+    if (int rc = region_plan(nx, ny, nz, level, max_planes, roi, info, &pl)) return rc;
+    return decode_planes_plan(c, d_out, nx, ny, nz, pl, d_planes, info);
 }
 
 namespace {
@@ -1373,9 +1464,10 @@ int seg_upload_streams(wr_ctx* c, uint8_t* d_blob, const uint8_t* h_blob, size_t
     return flush();
 }
 
-// decode_seg_impl for the box of level `level`, from the first planes only: the segments the box's runs touch are uploaded
-// and decoded, the others are not looked at beyond their length in the index.  fld receives box.elems() elements.
-int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int level, int max_planes, const wr_enc_info* info,
+// decode_seg_impl for a plan (LowresPlan), from the first planes only: the box of level `level`, or with roi != nullptr a
+// region of it.  The segments the plan needs are uploaded and decoded, the others are not looked at beyond their length in
+// the index.  fld receives the plan's out_elems() elements.
+int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int level, int max_planes, const wr_box* roi, const wr_enc_info* info,
                            const unsigned char* data_enc, size_t data_len, wr_timings* tm)
 {
     if (int rc = ctx_bind(c)) return rc;
@@ -1386,12 +1478,12 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     if (int rc = check_dims(nx, ny, nz, fld.dev)) return rc;
     if (fld.none()) return fail(WR_ERR_ARG, "null output pointer");
     LowresPlan pl;
-    if (int rc = lowres_plan(nx, ny, nz, level, max_planes, info, &pl)) return rc;
+    if (int rc = region_plan(nx, ny, nz, level, max_planes, roi, info, &pl)) return rc;
     c->pend_valid = false;
     PlaneHold planes(c);
     SegBufs bufs(c);
     const double t0 = now();
-    const size_t n = (size_t)nx * ny * nz, nbox = pl.box.elems();
+    const size_t n = (size_t)nx * ny * nz, nbox = pl.out_elems();  // (the box's elements, or the region's)
     wr_timings local; memset(&local, 0, sizeof local);
     DevPool* const pool = c->pool;
     if (info->ntot_enc == 0) {  // a constant field: midval at the box's size
@@ -1414,14 +1506,13 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     for (int l = 0; l < nlay; l++)
         if (const char* why = wrseg::check_index(data_enc + off[l], info->len_enc_vec[l], info->len_enc_vec[l], n, &seg[l], &nseg[l]))
             return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + why);
-    // the segments the box needs, per plane (planes may have been cut at different lengths)
+    // the segments the plan needs, per plane (planes may have been cut at different lengths)
     std::vector<uint32_t> ids[WR_NLAYMAX];
     for (int l = 0; l < used; l++) {
         int same = -1;
         for (int k = 0; k < l; k++) if (seg[k] == seg[l]) same = k;
         if (same >= 0) { ids[l] = ids[same]; continue; }
-        ids[l].resize(wrlow::segments_of(nx, ny, pl.box, seg[l], nullptr, 0));
-        wrlow::segments_of(nx, ny, pl.box, seg[l], ids[l].data(), ids[l].size());
+        pl.segments(nx, ny, nz, seg[l], &ids[l]);
     }
     {
         std::lock_guard<std::mutex> gather(pool->planes.gather_mu);
@@ -1446,11 +1537,10 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
             HIPCHK(hipMemcpy(wrk::seg_decode_list_ids(bufs.work[l].p, nseg[l]), ids[l].data(), ids[l].size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         if (int rc = seg_upload_streams(c, bufs.blob[l].p, front, wrseg::kHeaderBytes + 4 * (size_t)nseg[l], offs, ids[l], &local.h2d_ms, &bytes_up)) return rc;
     }
-    g_stat[WR_STAT_LOWRES_BYTES_UP] += bytes_up;
+    g_stat[pl.stat_bytes_up] += bytes_up;
     const double t_coded = now();
     SlotNeed need;
-    need.scratch_elems = nbox;
-    if (fld.host || fld.host_f32) need.field_elems = nbox;
+    pl.need(fld.host || fld.host_f32, &need);
     SlotLease slot;
     if (int rc = slot.acquire(c, need)) return rc;
     const double t_phase = now();
@@ -1463,16 +1553,17 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     }
     double* d_box = fld.dev ? fld.dev : slot->field;
     float* d_f32 = nullptr;
+    void* d_roi = nullptr;  // where a region's crop landed
     int rc = WR_OK;
     {
         StageLock cu(pool->cu_mu);
-        clock_warmup(c, nbox);
+        clock_warmup(c, pl.work_elems());
         for (int l = 0; l < used; l++) {
             launch_note(c, "seg_decode_list", l, bufs.blob[l].p, n, bufs.work[l].p, p.q[l]);
             HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
             wrk::seg_decode_list(bufs.blob[l].p, info->len_enc_vec[l], p.q[l], n, seg[l], bufs.work[l].p, ids[l].size(), c->stream);
             HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
-            g_stat[WR_STAT_LOWRES_SEGMENTS] += ids[l].size();
+            g_stat[pl.stat_segments] += ids[l].size();
         }
         if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented decoder launch failed" + launch_describe(c));
         // the dequantizer only runs on planes whose every listed segment decoded
@@ -1484,8 +1575,14 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
             local.plane_coder_s[l] = bufs.seconds(l);
             local.rangecoder += local.plane_coder_s[l];
         }
-        launch_note(c, "dequant_box", used - 1, d_box, nbox, nullptr, p.q[used - 1]);
-        rc = lowres_from_planes(c, slot.get(), d_box, nx, ny, pl, p, fld.host_f32 ? &d_f32 : nullptr);
+        if (pl.roi) {
+            launch_note(c, "dequant_window", used - 1, slot->field, pl.work_elems(), nullptr, p.q[used - 1]);
+            rc = roi_from_planes(c, slot.get(), fld.dev, nx, ny, pl, p, fld.host_f32 != nullptr, &d_roi);
+            d_box = reinterpret_cast<double*>(d_roi); d_f32 = reinterpret_cast<float*>(d_roi);
+        } else {
+            launch_note(c, "dequant_box", used - 1, d_box, nbox, nullptr, p.q[used - 1]);
+            rc = lowres_from_planes(c, slot.get(), d_box, nx, ny, pl, p, fld.host_f32 ? &d_f32 : nullptr);
+        }
         if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
         if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the decoder's kernel stage failed on the device" + launch_describe(c));
         pool->last_stage_end.store(now());
@@ -1624,14 +1721,14 @@ int wr_decode_host_seg_lowres(wr_ctx* c, double* h_out, int nx, int ny, int nz, 
                               const unsigned char* data_enc, size_t data_len, wr_timings* tm)
 {
     FieldRef f; f.host = h_out;
-    return decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, info, data_enc, data_len, tm);
+    return decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, nullptr, info, data_enc, data_len, tm);
 }
 
 int wr_decode_host_seg_lowres_f32(wr_ctx* c, float* h_out, int nx, int ny, int nz, int level, int max_planes, const wr_enc_info* info,
                                   const unsigned char* data_enc, size_t data_len, wr_timings* tm)
 {
     FieldRef f; f.host_f32 = h_out;
-    return decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, info, data_enc, data_len, tm);
+    return decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, nullptr, info, data_enc, data_len, tm);
 }
 
 int wr_decode_device_seg_lowres(wr_ctx* c, double* d_out, int nx, int ny, int nz, int level, int max_planes, const wr_enc_info* info,
@@ -1639,7 +1736,32 @@ int wr_decode_device_seg_lowres(wr_ctx* c, double* d_out, int nx, int ny, int nz
 {
     FieldRef f; f.dev = d_out;
     if (!d_out) return fail(WR_ERR_ARG, "null device output pointer");
-    return decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, info, data_enc, data_len, tm);
+    return decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, nullptr, info, data_enc, data_len, tm);
+}
+
+int wr_decode_host_seg_roi(wr_ctx* c, double* h_out, int nx, int ny, int nz, int level, int max_planes, const wr_box* roi, const wr_enc_info* info,
+                           const unsigned char* data_enc, size_t data_len, wr_timings* tm)
+{
+    FieldRef f; f.host = h_out;
+    if (!roi) return fail(WR_ERR_ARG, "null region pointer");
+    return decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, roi, info, data_enc, data_len, tm);
+}
+
+int wr_decode_host_seg_roi_f32(wr_ctx* c, float* h_out, int nx, int ny, int nz, int level, int max_planes, const wr_box* roi, const wr_enc_info* info,
+                               const unsigned char* data_enc, size_t data_len, wr_timings* tm)
+{
+    FieldRef f; f.host_f32 = h_out;
+    if (!roi) return fail(WR_ERR_ARG, "null region pointer");
+    return decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, roi, info, data_enc, data_len, tm);
+}
+
+int wr_decode_device_seg_roi(wr_ctx* c, double* d_out, int nx, int ny, int nz, int level, int max_planes, const wr_box* roi, const wr_enc_info* info,
+                             const unsigned char* data_enc, size_t data_len, wr_timings* tm)
+{
+    FieldRef f; f.dev = d_out;
+    if (!d_out) return fail(WR_ERR_ARG, "null device output pointer");
+    if (!roi) return fail(WR_ERR_ARG, "null region pointer");
+    return decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, roi, info, data_enc, data_len, tm);
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 // device-resident planes (test hooks).
 #include "wr_internal.h"
 #include "wr_lowres.h"
+#include "wr_roi.h"
 #include "wr_segcoder.h"
 
 using namespace wri;
@@ -217,6 +218,32 @@ size_t wr_seg_lowres_segments(int nx, int ny, int nz, int level, unsigned seg, u
     if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
     if (nx < 1 || ny < 1 || nz < 1 || !wrlow::level_ok(level)) { fail(WR_ERR_ARG, "non-positive dimension or level outside [0, 4]"); return 0; }
     return wrlow::segments_of(nx, ny, wrlow::box_of(nx, ny, nz, level), seg, ids, ids ? cap : 0);
+}
+
+// ---- the geometry of a region decode (wr_roi.h): host only
+static bool roi_args_ok(int nx, int ny, int nz, int level, int wlev, const wr_box* roi)
+{
+    if (nx < 1 || ny < 1 || nz < 1 || !wrlow::level_ok(level)) { fail(WR_ERR_ARG, "non-positive dimension or level outside [0, 4]"); return false; }
+    if (wlev != 0 && wlev != wrlow::kMaxLevel) { fail(WR_ERR_ARG, "wlev must be 0 or 4"); return false; }
+    if (level > wlev) { fail(WR_ERR_ARG, "level exceeds the transform depth"); return false; }
+    if (!roi || !wrroi::roi_ok(wrlow::box_of(nx, ny, nz, level), *roi)) { fail(WR_ERR_ARG, "the region is empty or reaches outside the box of the level"); return false; }
+    return true;
+}
+
+int wr_roi_window(int nx, int ny, int nz, int level, int wlev, const wr_box* roi, wr_box* win)
+{
+    if (!roi_args_ok(nx, ny, nz, level, wlev, roi)) return WR_ERR_ARG;
+    const wrroi::Geometry g = wrroi::geometry_of(wrlow::box_of(nx, ny, nz, level), wlev - level, *roi);
+    if (win) *win = wr_box{g.ax[0].a, g.ax[1].a, g.ax[2].a, g.ax[0].b, g.ax[1].b, g.ax[2].b};
+    return WR_OK;
+}
+
+size_t wr_seg_roi_segments(int nx, int ny, int nz, int level, int wlev, const wr_box* roi, unsigned seg, uint32_t* ids, size_t cap)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
+    if (!roi_args_ok(nx, ny, nz, level, wlev, roi)) return 0;
+    return wrroi::segments_of(nx, ny, nz, wrroi::geometry_of(wrlow::box_of(nx, ny, nz, level), wlev - level, *roi), seg, ids, ids ? cap : 0);
 }
 
 }  // extern "C"

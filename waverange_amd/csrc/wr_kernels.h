@@ -151,6 +151,25 @@ void dequant_box(double* box, int bx, int by, int bz, int nx, int ny, const Dequ
 void scale_f64(const double* src, double* dst, size_t n, double s, hipStream_t st);
 void scale_narrow_f64(const double* src, float* dst, size_t n, double s, hipStream_t st);
 
+// ---- region decode (wr_roi.hip): the coefficient array of a window (wr_roi.h), wx*wy*wz doubles in the Mallat layout of its
+// own extents, gathered out of the planes.  Box b of the map copies lx*ly*lz coefficients: win[((oz + z)*wy + oy + y)*wx + ox
+// + x] = sum over the planes, in order, of q_l[(sy + y + ny*(sz + z))*nx + sx + x] * deps_l + minval_l (the arithmetic of
+// dequant_accum); nx, ny are the extents of the field.  The boxes tile the window; nothing of a plane outside their x-runs is
+// read.  The map travels in the kernel's arguments.
+constexpr int kWindowBoxes = 29;  // the low-pass box and seven detail octants of each of four levels
+struct WindowBox { uint32_t sx, sy, sz, ox, oy, oz, lx, ly, lz; };
+struct WindowMap {
+    int nbox;
+    uint32_t wx, wy, nx, ny;
+    WindowBox box[kWindowBoxes];
+};
+void dequant_window(double* win, const WindowMap& m, const DequantParams& p, hipStream_t st);
+// out[(z*cy + y)*cx + x] = win[((z + oz)*wy + y + oy)*wx + x + ox] * s (one multiply, one rounding; s == 1: the bits as they
+// are), narrowed to fp32 as the C cast in the second form.  Not in place.
+struct CropBox { uint32_t wx, wy, ox, oy, oz, cx, cy, cz; };
+void crop_scale_f64(const double* win, double* out, const CropBox& c, double s, hipStream_t st);
+void crop_scale_narrow_f64(const double* win, float* out, const CropBox& c, double s, hipStream_t st);
+
 }  // namespace wrk
 
 namespace wrk {
