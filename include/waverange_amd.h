@@ -452,6 +452,60 @@ int wr_decode_device_seg_roi(wr_ctx *ctx, double *d_out, int nx, int ny, int nz,
 size_t wr_seg_encode_host_ref(const unsigned char *sym, size_t n, unsigned seg, unsigned char *blob);
 int wr_seg_decode_host_ref(const unsigned char *blob, size_t len, unsigned char *sym, size_t n);
 
+/* ---- Blocked symbol order for segmented streams ("WRS2"): an opt-in third stream format.  Everything is WRS1's -- transform,
+ * quantizer, header scalars, the segment coder, the rules for `seg` -- except the ORDER in which a plane's symbols are cut
+ * into segments: subband by subband, and inside a subband in bricks of B^3, so that the low-pass box of every level is a
+ * prefix of the plane and a region of the field is a few bricks of every subband.
+ * For a field nx*ny*nz, wlev levels (the stream's: 0 or 4), h(n) = (n + 1) / 2, level extents e_0 = n, e_l = h(e_{l-1}) per
+ * axis, and a brick edge B:
+ *   boxes    first the low-pass box [0, e_wlev)^3; then for l = wlev, ..., 1 the seven octants o = 1..7, bit 0 / 1 / 2 of o
+ *            saying whether x / y / z takes the high part [e_l, e_{l-1}) or the low part [0, e_l) of level l.  A box with an
+ *            empty axis (the high part of an axis of extent 1) contributes nothing.  wlev = 0: one box, the field.
+ *   bricks   inside a box in (tz, ty, tx) order, tx fastest; brick (tx, ty, tz) covers [tx*B, min((tx+1)*B, ex)) and likewise
+ *            in y and z.  Partial bricks at the high edges hold exactly their hx*hy*hz symbols, no padding.
+ *   symbols  inside a brick x fastest, then y, then z.
+ * This is a permutation pi of [0, n): stream position -> coefficient index fx + nx * (fy + ny * fz).  The boxes of the levels
+ * above r tile the box of level r (the low-resolution decode's), so that box is the first bx*by*bz stream positions, for
+ * every r <= wlev.
+ *   plane blob := 'W','R','S','2' | u32 seg | u32 nseg | u32 brick | u32 len[nseg] | the segment streams, in order
+ * Segment k is byte for byte wr_range_encode of the stream positions [k*seg, ...) of the permuted plane.  B is one of 8, 16,
+ * 32, 64; brick = 0 means WR_BRICK_DEFAULT everywhere.  Every plane of a stream has the same format and the same brick:
+ * anything else is WR_ERR_STREAM, as is a brick that is not one of the four, before anything is launched.
+ * The wr_decode_*_seg, _seg_lowres and _seg_roi entry points above read the magic of every plane and decode either format;
+ * their results are bit for bit those of the WRS1 stream of the same field.  A low-resolution decode of a blocked stream
+ * needs the segments 0 .. ceil(bx*by*bz / seg) - 1; a region decode the segments that the x-runs of its source boxes fall
+ * into under pi. */
+#define WR_BRICK_DEFAULT 32
+int wr_blocked_order(int nx, int ny, int nz, int wlev, unsigned brick, uint64_t *pi); /* pi[n]; host only */
+size_t wr_seg_bound_blocked(size_t n, unsigned seg); /* worst-case blob bytes of one plane; 0 if seg is refused */
+/* ascending ids of the segments a level / a region needs of a blocked plane; conventions of wr_seg_lowres_segments and
+ * wr_seg_roi_segments */
+size_t wr_seg_lowres_segments_blocked(int nx, int ny, int nz, int level, int wlev, unsigned brick, unsigned seg,
+                                      uint32_t *ids, size_t cap);
+size_t wr_seg_roi_segments_blocked(int nx, int ny, int nz, int level, int wlev, const wr_box *roi, unsigned brick,
+                                   unsigned seg, uint32_t *ids, size_t cap);
+/* stage level, device pointers (16-byte aligned), n = nx*ny*nz bytes each, not in place.  inverse == 0: d_dst[p] =
+ * d_src[pi[p]] (natural order to blocked); otherwise d_dst[pi[p]] = d_src[p]. */
+int wr_dev_plane_reorder(wr_ctx *ctx, unsigned char *d_dst, const unsigned char *d_src, int nx, int ny, int nz, int wlev,
+                         unsigned brick, int inverse);
+/* whole path: wr_encode_host_seg / _f32 / wr_encode_device_seg with every plane as a WRS2 blob */
+int wr_encode_host_seg_blocked(wr_ctx *ctx, const double *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my,
+                               int mz, const double *cutoffvec, unsigned seg, unsigned brick, wr_enc_info *info,
+                               unsigned char *data_enc, size_t cap, wr_timings *tm);
+int wr_encode_host_seg_blocked_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my,
+                                   int mz, const double *cutoffvec, unsigned seg, unsigned brick, wr_enc_info *info,
+                                   unsigned char *data_enc, size_t cap, wr_timings *tm);
+int wr_encode_device_seg_blocked(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                 const double *cutoffvec, unsigned seg, unsigned brick, wr_enc_info *info,
+                                 unsigned char *data_enc, size_t cap, wr_timings *tm);
+/* host reference of the WRS2 format, on the calling thread: sym is the plane in NATURAL order (nx*ny*nz symbols), the
+ * permutation is done here.  blob holds wr_seg_bound_blocked(n, seg) bytes; returns the blob's length (0: an argument was
+ * refused).  The decoder reads a WRS1 blob too (wlev and brick are then not looked at). */
+size_t wr_seg_encode_host_ref_blocked(const unsigned char *sym, int nx, int ny, int nz, int wlev, unsigned brick,
+                                      unsigned seg, unsigned char *blob);
+int wr_seg_decode_host_ref_blocked(const unsigned char *blob, size_t len, unsigned char *sym, int nx, int ny, int nz,
+                                   int wlev);
+
 /* encoding_wrap / decoding_wrap for fp32 fields: the same arguments but the field, an implicit context per call and
  * the reference's "void + fatal" errors.  fld_1d of an encode is never overwritten (no residual write-back). */
 void wr_encoding_wrap_f32(int nx, int ny, int nz, const float *fld_1d, int wtflag, int mx, int my, int mz,

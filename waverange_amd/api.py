@@ -175,6 +175,21 @@ def lib():
     L.wr_decode_host_seg.argtypes = L.wr_decode_host.argtypes
     L.wr_decode_host_seg_f32.argtypes = L.wr_decode_host.argtypes
     L.wr_decode_device_seg.argtypes = L.wr_decode_host.argtypes
+    L.wr_encode_host_seg_blocked.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_uint, C.c_uint,
+                                             C.POINTER(EncInfo), _vp, C.c_size_t, C.POINTER(Timings)]
+    L.wr_encode_host_seg_blocked_f32.argtypes = L.wr_encode_host_seg_blocked.argtypes
+    L.wr_encode_device_seg_blocked.argtypes = L.wr_encode_host_seg_blocked.argtypes
+    L.wr_blocked_order.argtypes = [C.c_int] * 4 + [C.c_uint, _vp]
+    L.wr_seg_bound_blocked.restype = C.c_size_t
+    L.wr_seg_bound_blocked.argtypes = [C.c_size_t, C.c_uint]
+    L.wr_seg_lowres_segments_blocked.restype = C.c_size_t
+    L.wr_seg_lowres_segments_blocked.argtypes = [C.c_int] * 5 + [C.c_uint, C.c_uint, _vp, C.c_size_t]
+    L.wr_seg_roi_segments_blocked.restype = C.c_size_t
+    L.wr_seg_roi_segments_blocked.argtypes = [C.c_int] * 5 + [C.POINTER(Box), C.c_uint, C.c_uint, _vp, C.c_size_t]
+    L.wr_dev_plane_reorder.argtypes = [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int]
+    L.wr_seg_encode_host_ref_blocked.restype = C.c_size_t
+    L.wr_seg_encode_host_ref_blocked.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint, _vp]
+    L.wr_seg_decode_host_ref_blocked.argtypes = [_vp, C.c_size_t, _vp, C.c_int, C.c_int, C.c_int, C.c_int]
     L.wr_lowres_dims.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)] * 3
     L.wr_lowres_scale.restype = C.c_double
     L.wr_lowres_scale.argtypes = [C.c_int] * 4
@@ -375,6 +390,73 @@ def seg_decode_host_ref(blob, n):
     out = np.zeros(max(n, 1), dtype=np.uint8)
     _check(lib().wr_seg_decode_host_ref(src.ctypes.data, b.size, out.ctypes.data, n))
     return out[:n]
+
+
+BRICK_DEFAULT = 32  # WR_BRICK_DEFAULT
+
+
+def seg_bound_blocked(n, seg=0):
+    """Worst-case bytes of one plane's blocked ("WRS2") blob (0 if `seg` is refused)."""
+    return int(lib().wr_seg_bound_blocked(n, seg))
+
+
+def blocked_order(shape, wlev=4, brick=0):
+    """pi (uint64, nz*ny*nx entries): stream position -> coefficient index x + nx * (y + ny * z) of the blocked order of a field
+    shaped (nz, ny, nx) (wr_blocked_order; brick = 0: BRICK_DEFAULT).  blocked = plane.ravel()[pi]."""
+    nz, ny, nx = shape
+    pi = np.empty(nx * ny * nz, dtype=np.uint64)
+    _check(lib().wr_blocked_order(nx, ny, nz, wlev, brick, pi.ctypes.data))
+    return pi
+
+
+def seg_encode_host_ref_blocked(plane, shape, wlev=4, brick=0, seg=0):
+    """The WRS2 blob of a plane given in natural order, permuted and coded on the calling thread: the definition of the format."""
+    nz, ny, nx = shape
+    p = np.ascontiguousarray(plane, dtype=np.uint8).ravel()
+    assert p.size == nx * ny * nz
+    bound = seg_bound_blocked(p.size, seg)
+    if not bound:
+        raise WaveRangeError("segment length must be a multiple of 16 in [16, 59999]")
+    out = np.empty(bound, dtype=np.uint8)
+    n = lib().wr_seg_encode_host_ref_blocked(p.ctypes.data, nx, ny, nz, wlev, brick, seg, out.ctypes.data)
+    if not n:
+        raise WaveRangeError(lib().wr_last_error().decode())
+    return out[:n].copy()
+
+
+def seg_decode_host_ref_blocked(blob, shape, wlev=4):
+    """The plane (natural order, nz*ny*nx symbols) of a WRS2 or WRS1 blob, decoded on the calling thread."""
+    nz, ny, nx = shape
+    b = np.ascontiguousarray(blob, dtype=np.uint8).ravel()
+    src = b if b.size else np.zeros(1, dtype=np.uint8)
+    out = np.zeros(nx * ny * nz, dtype=np.uint8)
+    _check(lib().wr_seg_decode_host_ref_blocked(src.ctypes.data, b.size, out.ctypes.data, nx, ny, nz, wlev))
+    return out
+
+
+def seg_lowres_segments_blocked(shape, level, seg=0, wlev=4, brick=0):
+    """seg_lowres_segments for a plane in the blocked order: the prefix 0 .. ceil(bx*by*bz / seg) - 1."""
+    nz, ny, nx = shape
+    count = lib().wr_seg_lowres_segments_blocked(nx, ny, nz, level, wlev, brick, seg, None, 0)
+    if not count:
+        raise WaveRangeError(lib().wr_last_error().decode())
+    ids = np.empty(count, dtype=np.uint32)
+    got = lib().wr_seg_lowres_segments_blocked(nx, ny, nz, level, wlev, brick, seg, ids.ctypes.data, ids.size)
+    assert got == count
+    return ids
+
+
+def seg_roi_segments_blocked(shape, level, roi, seg=0, wlev=4, brick=0):
+    """seg_roi_segments for a plane in the blocked order."""
+    nz, ny, nx = shape
+    r = _box(roi)
+    count = lib().wr_seg_roi_segments_blocked(nx, ny, nz, level, wlev, C.byref(r), brick, seg, None, 0)
+    if not count:
+        raise WaveRangeError(lib().wr_last_error().decode())
+    ids = np.empty(count, dtype=np.uint32)
+    got = lib().wr_seg_roi_segments_blocked(nx, ny, nz, level, wlev, C.byref(r), brick, seg, ids.ctypes.data, ids.size)
+    assert got == count
+    return ids
 
 
 def seg_split(blob):
@@ -797,18 +879,21 @@ class Context:
         return tm.as_dict()
 
     # ---- segmented plane streams ("WRS1"): the planes are coded and decoded by the GPU; not readable by the reference's tools
-    def _seg_cap(self, shape, seg):
+    def _seg_cap(self, shape, seg, brick=None):
         nz, ny, nx = shape
         _, cap = setup_wr(nx, ny, nz)
         n = nx * ny * nz
-        return cap + NLAYMAX * max(seg_bound(n, seg) - n, 0)
+        bound = seg_bound(n, seg) if brick is None else seg_bound_blocked(n, seg)
+        return cap + NLAYMAX * max(bound - n, 0)
 
-    def _encode_seg(self, fn, ptr, shape, tolrel, wtflag, seg, out, cutoff, m):
+    def _encode_seg(self, fn, ptr, shape, tolrel, wtflag, seg, out, cutoff, m, brick=None):
+        """brick is None: `fn` is a WRS1 encoder; otherwise its _blocked form (brick = 0: BRICK_DEFAULT)"""
         nz, ny, nx = shape
-        data = out if out is not None else np.empty(self._seg_cap(shape, seg), dtype=np.uint8)
+        data = out if out is not None else np.empty(self._seg_cap(shape, seg, brick), dtype=np.uint8)
         cut = np.ascontiguousarray([tolrel] if cutoff is None else cutoff, dtype=np.float64)
         info, tm = EncInfo(), Timings()
-        _check(fn(self.h, ptr, nx, ny, nz, wtflag, m[0], m[1], m[2], cut.ctypes.data_as(_dp), seg, C.byref(info),
+        fmt = (seg,) if brick is None else (seg, brick)
+        _check(fn(self.h, ptr, nx, ny, nz, wtflag, m[0], m[1], m[2], cut.ctypes.data_as(_dp), *fmt, C.byref(info),
                   data.ctypes.data, data.size, C.byref(tm)))
         d = info.as_dict()
         d["data"] = data[:info.ntot_enc]
@@ -824,28 +909,46 @@ class Context:
         _check(fn(self.h, ptr, nx, ny, nz, C.byref(info), data.ctypes.data, data.size, C.byref(tm)))
         return tm.as_dict()
 
-    def encode_host_seg(self, fld, tolrel, wtflag=1, seg=0, out=None, cutoff=None, m=(1, 1, 1)):
-        """encode_host with every plane as a segmented blob (seg = 0: SEG_DEFAULT); header scalars as encode_host's."""
+    def encode_host_seg(self, fld, tolrel, wtflag=1, seg=0, out=None, cutoff=None, m=(1, 1, 1), brick=None):
+        """encode_host with every plane as a segmented blob (seg = 0: SEG_DEFAULT); header scalars as encode_host's.  brick is
+        None: WRS1; otherwise the blocked order ("WRS2") with that brick edge (0: BRICK_DEFAULT).  The decoders read either."""
         assert fld.dtype == np.float64 and fld.flags["C_CONTIGUOUS"]
-        return self._encode_seg(lib().wr_encode_host_seg, fld.ctypes.data, fld.shape, tolrel, wtflag, seg, out, cutoff, m)
+        fn = lib().wr_encode_host_seg if brick is None else lib().wr_encode_host_seg_blocked
+        return self._encode_seg(fn, fld.ctypes.data, fld.shape, tolrel, wtflag, seg, out, cutoff, m, brick)
 
     def decode_host_seg(self, out, enc):
         assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"]
         return self._decode_seg(lib().wr_decode_host_seg, out.ctypes.data, out.shape, enc)
 
-    def encode_host_seg_f32(self, fld, tolrel, wtflag=1, seg=0, out=None, cutoff=None, m=(1, 1, 1)):
+    def encode_host_seg_f32(self, fld, tolrel, wtflag=1, seg=0, out=None, cutoff=None, m=(1, 1, 1), brick=None):
         if not (isinstance(fld, np.ndarray) and fld.dtype == np.float32 and fld.flags["C_CONTIGUOUS"]):
             raise TypeError("encode_host_seg_f32: a C-contiguous float32 array is required")
-        return self._encode_seg(lib().wr_encode_host_seg_f32, fld.ctypes.data, fld.shape, tolrel, wtflag, seg, out, cutoff, m)
+        fn = lib().wr_encode_host_seg_f32 if brick is None else lib().wr_encode_host_seg_blocked_f32
+        return self._encode_seg(fn, fld.ctypes.data, fld.shape, tolrel, wtflag, seg, out, cutoff, m, brick)
 
     def decode_host_seg_f32(self, out, enc):
         if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"]):
             raise TypeError("decode_host_seg_f32: a C-contiguous float32 array is required")
         return self._decode_seg(lib().wr_decode_host_seg_f32, out.ctypes.data, out.shape, enc)
 
-    def encode_seg(self, buf, shape, tolrel, wtflag=1, seg=0, out=None, cutoff=None, m=(1, 1, 1)):
+    def encode_seg(self, buf, shape, tolrel, wtflag=1, seg=0, out=None, cutoff=None, m=(1, 1, 1), brick=None):
         """encode_host_seg with the field resident on the device (`buf` is consumed, as by encode)."""
-        return self._encode_seg(lib().wr_encode_device_seg, buf.ptr, shape, tolrel, wtflag, seg, out, cutoff, m)
+        fn = lib().wr_encode_device_seg if brick is None else lib().wr_encode_device_seg_blocked
+        return self._encode_seg(fn, buf.ptr, shape, tolrel, wtflag, seg, out, cutoff, m, brick)
+
+    def plane_reorder(self, plane, shape, wlev=4, brick=0, inverse=False):
+        """Stage level: a plane (uint8, nz*ny*nx symbols) through the reorder kernel (wr_dev_plane_reorder).  Forward: natural
+        order in, blocked order out (plane.ravel()[blocked_order(...)]); inverse: the other way."""
+        nz, ny, nx = shape
+        p = np.ascontiguousarray(plane, dtype=np.uint8).ravel()
+        assert p.size == nx * ny * nz
+        d_src, d_dst = self.to_device(p), self.alloc(p.size)
+        try:
+            _check(lib().wr_dev_plane_reorder(self.h, d_dst.ptr, d_src.ptr, nx, ny, nz, wlev, brick, int(bool(inverse))))
+            return d_dst.download(np.uint8, p.size)
+        finally:
+            d_src.free()
+            d_dst.free()
 
     def decode_seg(self, buf, shape, enc):
         return self._decode_seg(lib().wr_decode_device_seg, buf.ptr, shape, enc)

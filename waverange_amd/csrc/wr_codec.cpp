@@ -5,6 +5,7 @@
 //   decoding_wrap : range decoder -> dequantise-accumulate -> inverse transform                  (wrappers.cpp:456-527)
 // Compiled with hipcc, strict IEEE (-ffp-contract=off): the scalar arithmetic on deps/aopt/bopt/tolabs below must round
 // exactly as wrappers.cpp:292-340 does.
+#include "wr_blocked.h"
 #include "wr_internal.h"
 #include "wr_lowres.h"
 #include "wr_roi.h"
@@ -331,6 +332,27 @@ struct LowresPlan {
         ids->resize(roi ? wrroi::segments_of(nx, ny, nz, win, seg, nullptr, 0) : wrlow::segments_of(nx, ny, box, seg, nullptr, 0));
         if (roi) wrroi::segments_of(nx, ny, nz, win, seg, ids->data(), ids->size());
         else wrlow::segments_of(nx, ny, box, seg, ids->data(), ids->size());
+    }
+    // the same for a plane in the blocked order (wr_blocked.h): a prefix for a box
+    void segments_blocked(const wrblk::Order& od, uint32_t seg, std::vector<uint32_t>* ids) const
+    {
+        if (roi) {
+            ids->resize(wrblk::region_segments(od, win, seg, nullptr, 0));
+            wrblk::region_segments(od, win, seg, ids->data(), ids->size());
+        } else {
+            ids->resize(wrblk::lowres_segments(od.nx, od.ny, od.nz, od.wlev - inverse, seg, nullptr, 0));
+            wrblk::lowres_segments(od.nx, od.ny, od.nz, od.wlev - inverse, seg, ids->data(), ids->size());
+        }
+    }
+    // the ascending ids of the bricks the plan needs: those the window's source boxes meet, or all bricks of the boxes that
+    // tile the box of the level
+    void bricks(const wrblk::Order& od, std::vector<uint32_t>* ids) const
+    {
+        if (roi) { wrblk::region_bricks(od, win, ids); return; }
+        const int nb = wrblk::prefix_boxes(od, od.wlev - inverse);
+        const uint64_t count = nb < od.nbox ? od.box[nb].first_brick : od.nbricks;
+        ids->resize(count);
+        for (uint64_t k = 0; k < count; k++) (*ids)[k] = (uint32_t)k;
     }
     // the work space of the kernel stage: a box is inverted in the caller's (or the staging) array, a window in the slot's
     // field buffer whoever the caller is, and what comes out of it is smaller
@@ -1165,6 +1187,7 @@ namespace {
 struct SegBufs {
     wr_ctx* c;
     DevPlanes::Buf stage, blob[WR_NLAYMAX], work[WR_NLAYMAX];
+    DevPlanes::Buf perm, bricks;  // a blocked stream: one plane in stream order (every plane in turn), the brick list of a partial decode
     hipEvent_t ev[2 * WR_NLAYMAX] = {nullptr};
     explicit SegBufs(wr_ctx* ctx) : c(ctx) {}
     SegBufs(const SegBufs&) = delete;
@@ -1173,6 +1196,8 @@ struct SegBufs {
     {
         (void)hipStreamSynchronize(c->stream);
         if (stage.p) c->pool->planes.give(stage);
+        if (perm.p) c->pool->planes.give(perm);
+        if (bricks.p) c->pool->planes.give(bricks);
         for (int l = 0; l < WR_NLAYMAX; l++) {
             if (blob[l].p) c->pool->planes.give(blob[l]);
             if (work[l].p) c->pool->planes.give(work[l]);
@@ -1196,11 +1221,13 @@ struct SegBufs {
 unsigned long long* seg_result_host(wr_ctx* c, int l) { return reinterpret_cast<unsigned long long*>(c->h_result + 8) + 2 * l; }
 unsigned long long* seg_result_dev(wr_ctx* c, int l) { return reinterpret_cast<unsigned long long*>(c->h_result_dev + 8) + 2 * l; }
 
-int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, const Cutoff& cut, unsigned seg, wr_enc_info* info,
+// brick == 0: WRS1; otherwise WRS2 with that brick edge (wr_blocked.h)
+int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, const Cutoff& cut, unsigned seg, unsigned brick, wr_enc_info* info,
                     unsigned char* data_enc, size_t cap, wr_timings* tm)
 {
     if (!seg) seg = WR_SEG_DEFAULT;
     if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
+    if (brick && !wrblk::brick_ok(brick)) return fail(WR_ERR_ARG, "brick edge must be one of 8, 16, 32, 64");
     if (int rc = ctx_bind(c)) return rc;
     if (int rc = check_dims(nx, ny, nz, fld.dev)) return rc;
     if (fld.none()) return fail(WR_ERR_ARG, "null field pointer");
@@ -1219,7 +1246,9 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
     c->pend_valid = false;  // planes a wr_decode_begin parked in this context do not survive an encode on it
     PlaneHold planes(c);
     SegBufs bufs(c);  // (after the planes: it goes first when the call unwinds, and waits for the stream)
-    const size_t blob_cap = (wr_seg_bound(n, seg) + 15) & ~(size_t)15;
+    const size_t blob_cap = ((brick ? wr_seg_bound_blocked(n, seg) : wr_seg_bound(n, seg)) + 15) & ~(size_t)15;
+    wrblk::Order od{};
+    if (brick) od = wrblk::order_of(nx, ny, nz, wtflag ? kWavLvl : 0, brick);
 
     SlotNeed need;
     transform_need(nx, ny, nz, wtflag ? kWavLvl : 0, &need);
@@ -1247,6 +1276,10 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
     // the context's stream); a blob buffer per plane
     bufs.stage = plane_scratch(c, wrk::seg_stage_bytes(n, seg));
     if (!bufs.stage.p) return WR_ERR_HIP;
+    if (brick) {  // the plane in stream order: like the staging buffer one for all planes
+        bufs.perm = plane_scratch(c, n);
+        if (!bufs.perm.p) return WR_ERR_HIP;
+    }
     double* resid = d_fld;
     int rc = WR_OK;
     {
@@ -1262,7 +1295,12 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
         auto after_quant = [&](unsigned l, bool) -> int {
             launch_note(c, "seg_encode", (int)l, bufs.blob[l].p, n, bufs.stage.p, c->ps[l].ref);
             HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
-            wrk::seg_encode(c->ps[l].ref, n, seg, bufs.stage.p, bufs.blob[l].p, blob_cap, seg_result_dev(c, (int)l), c->stream);
+            wrk::PlaneRef sym = c->ps[l].ref;
+            if (brick) {
+                if (!wrk::plane_reorder(sym, bufs.perm.p, od, false, nullptr, 0, c->stream)) return fail(WR_ERR_ARG, "too many bricks");
+                sym = wrk::plane_ref(bufs.perm.p);
+            }
+            wrk::seg_encode(sym, n, seg, bufs.stage.p, bufs.blob[l].p, blob_cap, seg_result_dev(c, (int)l), c->stream, brick);
             HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
             if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented coder launch failed" + launch_describe(c));
             return WR_OK;
@@ -1307,12 +1345,30 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
     return WR_OK;
 }
 
+// Every plane's header and index, validated on the host before anything is launched: the kernels only ever see offsets that
+// lie inside their blob, in order, each stream no longer than a segment can be.  *brick: 0 for a WRS1 stream, the brick edge
+// of a WRS2 stream; a stream whose planes differ in format or brick is refused.
+int seg_check_planes(const unsigned char* data_enc, const size_t* off, const wr_enc_info* info, int nlay, size_t n, uint32_t* seg, uint32_t* nseg,
+                     uint32_t* brick)
+{
+    *brick = 0;
+    for (int l = 0; l < nlay; l++) {
+        uint32_t b = 0;
+        if (const char* why = wrseg::check_index(data_enc + off[l], info->len_enc_vec[l], info->len_enc_vec[l], n, &seg[l], &nseg[l], &b))
+            return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + why);
+        if (l == 0) *brick = b;
+        else if ((b != 0) != (*brick != 0)) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": the stream mixes WRS1 and WRS2 planes");
+        else if (b != *brick) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": the planes of the stream differ in their brick edge");
+    }
+    return WR_OK;
+}
+
 // the byte offsets of the segment streams behind the index, from an index that check_index has passed, into work + 256
-int seg_upload_offsets(wr_ctx* c, const uint8_t* front, uint32_t nseg, uint8_t* work)
+int seg_upload_offsets(wr_ctx* c, const uint8_t* front, uint32_t nseg, uint8_t* work, uint32_t brick = 0)
 {
     std::vector<unsigned long long> offs((size_t)nseg + 1);
     unsigned long long run = 0;
-    for (uint32_t k = 0; k < nseg; k++) { offs[k] = run; run += wrseg::get_u32(front + wrseg::kHeaderBytes + 4 * (size_t)k); }
+    for (uint32_t k = 0; k < nseg; k++) { offs[k] = run; run += wrseg::get_u32(front + wrseg::header_bytes(brick) + 4 * (size_t)k); }
     offs[nseg] = run;
     HIPCHK(hipMemcpy(work + 256, offs.data(), offs.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
     return WR_OK;
@@ -1351,14 +1407,16 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
     for (int l = 0; l < nlay; l++) off[l + 1] = off[l] + info->len_enc_vec[l];
     if (off[nlay] > info->ntot_enc) return fail(WR_ERR_STREAM, "len_enc_vec exceeds ntot_enc");
     if (data_len && info->ntot_enc > data_len) return fail(WR_ERR_STREAM, "ntot_enc exceeds the length of the coded buffer");
-    // every plane's header and index are validated here, on the host, before anything is launched: the kernels only ever see
-    // offsets that lie inside their blob, in order, each stream no longer than a segment can be
-    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0};
-    for (int l = 0; l < nlay; l++)
-        if (const char* why = wrseg::check_index(data_enc + off[l], info->len_enc_vec[l], info->len_enc_vec[l], n, &seg[l], &nseg[l]))
-            return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + why);
+    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0}, brick = 0;
+    if (int rc = seg_check_planes(data_enc, off, info, nlay, n, seg, nseg, &brick)) return rc;
+    wrblk::Order od{};
+    if (brick) od = wrblk::order_of(nx, ny, nz, (int)info->wlev, brick);
     {
         std::lock_guard<std::mutex> gather(pool->planes.gather_mu);  // one decode at a time gathers its planes (decode_impl)
+        if (brick) {  // the plane in stream order, every plane in turn
+            bufs.perm = plane_scratch(c, n);
+            if (!bufs.perm.p) return WR_ERR_HIP;
+        }
         for (int l = 0; l < nlay; l++) {
             if (int rc = plane_prepare(c, l, n, true, false, nullptr, nullptr, false)) return rc;
             bufs.blob[l] = plane_scratch(c, info->len_enc_vec[l]);
@@ -1371,7 +1429,7 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
     for (int l = 0; l < nlay; l++) {
         if (int rc = xfer_field(c, &c->x_field, bufs.blob[l].p, data_enc + off[l], info->len_enc_vec[l], kUp)) return rc;
         local.h2d_ms += (float)c->x_field.ms;
-        if (int rc = seg_upload_offsets(c, data_enc + off[l], nseg[l], bufs.work[l].p)) return rc;
+        if (int rc = seg_upload_offsets(c, data_enc + off[l], nseg[l], bufs.work[l].p, brick)) return rc;
     }
     const double t_coded = now();
     SlotNeed need;
@@ -1396,7 +1454,9 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
         for (int l = 0; l < nlay; l++) {
             launch_note(c, "seg_decode", l, bufs.blob[l].p, n, bufs.work[l].p, p.q[l]);
             HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
-            wrk::seg_decode(bufs.blob[l].p, info->len_enc_vec[l], p.q[l], n, seg[l], bufs.work[l].p, c->stream);
+            wrk::seg_decode(bufs.blob[l].p, info->len_enc_vec[l], brick ? wrk::plane_ref(bufs.perm.p) : p.q[l], n, seg[l], bufs.work[l].p, c->stream,
+                            brick);
+            if (brick && !wrk::plane_reorder(p.q[l], bufs.perm.p, od, true, nullptr, 0, c->stream)) return fail(WR_ERR_ARG, "too many bricks");
             HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
         }
         if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented decoder launch failed" + launch_describe(c));
@@ -1502,20 +1562,32 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     if (off[nlay] > info->ntot_enc) return fail(WR_ERR_STREAM, "len_enc_vec exceeds ntot_enc");
     if (data_len && info->ntot_enc > data_len) return fail(WR_ERR_STREAM, "ntot_enc exceeds the length of the coded buffer");
     // every plane's header and index, used or not, are validated on the host before anything is launched (decode_seg_impl)
-    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0};
-    for (int l = 0; l < nlay; l++)
-        if (const char* why = wrseg::check_index(data_enc + off[l], info->len_enc_vec[l], info->len_enc_vec[l], n, &seg[l], &nseg[l]))
-            return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + why);
+    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0}, brick = 0;
+    if (int rc = seg_check_planes(data_enc, off, info, nlay, n, seg, nseg, &brick)) return rc;
+    // a blocked stream: the bricks the plan needs, the same in every plane
+    wrblk::Order od{};
+    std::vector<uint32_t> bricks;
+    if (brick) {
+        od = wrblk::order_of(nx, ny, nz, (int)info->wlev, brick);
+        if (od.nbricks > 0x7fffffffu) return fail(WR_ERR_ARG, "too many bricks");
+        pl.bricks(od, &bricks);
+    }
     // the segments the plan needs, per plane (planes may have been cut at different lengths)
     std::vector<uint32_t> ids[WR_NLAYMAX];
     for (int l = 0; l < used; l++) {
         int same = -1;
         for (int k = 0; k < l; k++) if (seg[k] == seg[l]) same = k;
         if (same >= 0) { ids[l] = ids[same]; continue; }
-        pl.segments(nx, ny, nz, seg[l], &ids[l]);
+        if (brick) pl.segments_blocked(od, seg[l], &ids[l]);
+        else pl.segments(nx, ny, nz, seg[l], &ids[l]);
     }
     {
         std::lock_guard<std::mutex> gather(pool->planes.gather_mu);
+        if (brick) {
+            bufs.perm = plane_scratch(c, n);
+            bufs.bricks = plane_scratch(c, 4 * bricks.size() + 4);
+            if (!bufs.perm.p || !bufs.bricks.p) return WR_ERR_HIP;
+        }
         for (int l = 0; l < used; l++) {
             if (int rc = plane_prepare(c, l, n, true, false, nullptr, nullptr, false)) return rc;
             bufs.blob[l] = plane_scratch(c, info->len_enc_vec[l]);
@@ -1526,16 +1598,18 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     }
     // ---- stage "up": per plane the offsets table, the id list and the streams of the listed segments
     size_t bytes_up = 0;
+    const size_t head = wrseg::header_bytes(brick);
+    if (!bricks.empty()) HIPCHK(hipMemcpy(bufs.bricks.p, bricks.data(), bricks.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     for (int l = 0; l < used; l++) {
         const uint8_t* const front = data_enc + off[l];
         std::vector<unsigned long long> offs((size_t)nseg[l] + 1);
         unsigned long long run = 0;
-        for (uint32_t k = 0; k < nseg[l]; k++) { offs[k] = run; run += wrseg::get_u32(front + wrseg::kHeaderBytes + 4 * (size_t)k); }
+        for (uint32_t k = 0; k < nseg[l]; k++) { offs[k] = run; run += wrseg::get_u32(front + head + 4 * (size_t)k); }
         offs[nseg[l]] = run;
         HIPCHK(hipMemcpy(bufs.work[l].p + 256, offs.data(), offs.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
         if (!ids[l].empty())
             HIPCHK(hipMemcpy(wrk::seg_decode_list_ids(bufs.work[l].p, nseg[l]), ids[l].data(), ids[l].size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        if (int rc = seg_upload_streams(c, bufs.blob[l].p, front, wrseg::kHeaderBytes + 4 * (size_t)nseg[l], offs, ids[l], &local.h2d_ms, &bytes_up)) return rc;
+        if (int rc = seg_upload_streams(c, bufs.blob[l].p, front, head + 4 * (size_t)nseg[l], offs, ids[l], &local.h2d_ms, &bytes_up)) return rc;
     }
     g_stat[pl.stat_bytes_up] += bytes_up;
     const double t_coded = now();
@@ -1561,7 +1635,11 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
         for (int l = 0; l < used; l++) {
             launch_note(c, "seg_decode_list", l, bufs.blob[l].p, n, bufs.work[l].p, p.q[l]);
             HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
-            wrk::seg_decode_list(bufs.blob[l].p, info->len_enc_vec[l], p.q[l], n, seg[l], bufs.work[l].p, ids[l].size(), c->stream);
+            wrk::seg_decode_list(bufs.blob[l].p, info->len_enc_vec[l], brick ? wrk::plane_ref(bufs.perm.p) : p.q[l], n, seg[l], bufs.work[l].p,
+                                 ids[l].size(), c->stream, brick);
+            // the listed segments are in the scratch buffer in stream order: the needed bricks go to their places in the plane
+            if (brick && !wrk::plane_reorder(p.q[l], bufs.perm.p, od, true, reinterpret_cast<const uint32_t*>(bufs.bricks.p), bricks.size(), c->stream))
+                return fail(WR_ERR_ARG, "too many bricks");
             HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
             g_stat[pl.stat_segments] += ids[l].size();
         }
@@ -1675,7 +1753,7 @@ int wr_encode_host_seg(wr_ctx* c, const double* h_fld, int nx, int ny, int nz, i
 {
     Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
     FieldRef f; f.host = const_cast<double*>(h_fld);  // (written only with wr_ctx_set_keep_residual(ctx, 1), as wr_encode_host)
-    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, info, data_enc, cap, tm);
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, 0, info, data_enc, cap, tm);
 }
 
 int wr_decode_host_seg(wr_ctx* c, double* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
@@ -1690,7 +1768,7 @@ int wr_encode_host_seg_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz
 {
     Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
     FieldRef f; f.host_f32 = const_cast<float*>(h_fld);
-    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, info, data_enc, cap, tm);
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, 0, info, data_enc, cap, tm);
 }
 
 int wr_decode_host_seg_f32(wr_ctx* c, float* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
@@ -1706,7 +1784,7 @@ int wr_encode_device_seg(wr_ctx* c, double* d_fld, int nx, int ny, int nz, int w
     Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
     FieldRef f; f.dev = d_fld;
     if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
-    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, info, data_enc, cap, tm);
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, 0, info, data_enc, cap, tm);
 }
 
 int wr_decode_device_seg(wr_ctx* c, double* d_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
@@ -1715,6 +1793,52 @@ int wr_decode_device_seg(wr_ctx* c, double* d_fld, int nx, int ny, int nz, const
     FieldRef f; f.dev = d_fld;
     if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
     return decode_seg_impl(c, f, nx, ny, nz, info, data_enc, data_len, tm);
+}
+
+int wr_encode_host_seg_blocked(wr_ctx* c, const double* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,
+                               unsigned seg, unsigned brick, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm)
+{
+    Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
+    FieldRef f; f.host = const_cast<double*>(h_fld);
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick ? brick : WR_BRICK_DEFAULT, info, data_enc, cap, tm);
+}
+
+int wr_encode_host_seg_blocked_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,
+                                   unsigned seg, unsigned brick, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm)
+{
+    Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
+    FieldRef f; f.host_f32 = const_cast<float*>(h_fld);
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick ? brick : WR_BRICK_DEFAULT, info, data_enc, cap, tm);
+}
+
+int wr_encode_device_seg_blocked(wr_ctx* c, double* d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,
+                                 unsigned seg, unsigned brick, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm)
+{
+    Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
+    FieldRef f; f.dev = d_fld;
+    if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick ? brick : WR_BRICK_DEFAULT, info, data_enc, cap, tm);
+}
+
+int wr_dev_plane_reorder(wr_ctx* c, unsigned char* d_dst, const unsigned char* d_src, int nx, int ny, int nz, int wlev, unsigned brick, int inverse)
+{
+    if (!brick) brick = WR_BRICK_DEFAULT;
+    if (!wrblk::brick_ok(brick)) return fail(WR_ERR_ARG, "brick edge must be one of 8, 16, 32, 64");
+    if (wlev != 0 && wlev != kWavLvl) return fail(WR_ERR_ARG, "wlev must be 0 or 4");
+    if (int rc = ctx_bind(c)) return rc;
+    if (int rc = check_dims(nx, ny, nz, d_dst)) return rc;
+    if (!d_dst || !d_src || d_dst == d_src) return fail(WR_ERR_ARG, "null pointer, or source and destination are the same");
+    if (((uintptr_t)d_src | (uintptr_t)d_dst) & 15) return fail(WR_ERR_ARG, "plane buffers must be 16-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    const wrblk::Order od = wrblk::order_of(nx, ny, nz, wlev, brick);
+    StageLock cu(c->pool->cu_mu);
+    // the natural-order side is the source of a forward reorder and the destination of an inverse one
+    const bool ok = inverse ? wrk::plane_reorder(wrk::plane_ref(d_dst), const_cast<unsigned char*>(d_src), od, true, nullptr, 0, c->stream)
+                            : wrk::plane_reorder(wrk::plane_ref(d_src), d_dst, od, false, nullptr, 0, c->stream);
+    if (!ok) return fail(WR_ERR_ARG, "too many bricks");
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return WR_OK;
 }
 
 int wr_decode_host_seg_lowres(wr_ctx* c, double* h_out, int nx, int ny, int nz, int level, int max_planes, const wr_enc_info* info,

@@ -1,6 +1,7 @@
 // wr_coder_hooks.cpp -- the host range coder alone behind the C ABI (rows a6/a7/a10 of SURVEY.md 8a): whole planes,
 // interleaved planes, the coder pool, the 16-lane loops, and the windowed symbol path with host buffers standing in for
 // device-resident planes (test hooks).
+#include "wr_blocked.h"
 #include "wr_internal.h"
 #include "wr_lowres.h"
 #include "wr_roi.h"
@@ -155,26 +156,49 @@ size_t wr_seg_bound(size_t n, unsigned seg)
     return wrseg::kHeaderBytes + wrseg::seg_count(n, seg) * (4 + (size_t)wrseg::stream_bound(seg));
 }
 
-size_t wr_seg_encode_host_ref(const unsigned char* sym, size_t n, unsigned seg, unsigned char* blob)
+// the container around the symbols as they stand; brick != 0: the WRS2 header (the caller has permuted the symbols)
+static size_t seg_encode_ref(const unsigned char* sym, size_t n, unsigned seg, unsigned brick, unsigned char* blob)
 {
-    if (!seg) seg = WR_SEG_DEFAULT;
-    if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
-    if (!blob || (n && !sym)) { fail(WR_ERR_ARG, "null pointer"); return 0; }
-    const size_t nseg = wrseg::seg_count(n, seg);
+    const size_t nseg = wrseg::seg_count(n, seg), head = wrseg::header_bytes(brick);
     if (nseg > 0xffffffffu) { fail(WR_ERR_ARG, "too many segments"); return 0; }
-    memcpy(blob, wrseg::kMagic, 4);
+    memcpy(blob, brick ? wrseg::kMagicBlocked : wrseg::kMagic, 4);
     wrseg::put_u32(blob + 4, seg);
     wrseg::put_u32(blob + 8, (uint32_t)nseg);
-    size_t at = wrseg::kHeaderBytes + 4 * nseg;
+    if (brick) wrseg::put_u32(blob + 12, brick);
+    size_t at = head + 4 * nseg;
     for (size_t k = 0; k < nseg; k++) {
         const size_t base = k * seg;
         const uint32_t bs = n - base < seg ? (uint32_t)(n - base) : seg;
         const uint32_t len = wrseg::encode_segment_host(sym + base, bs, blob + at, wrseg::stream_bound(seg));
         if (!len) { fail(WR_ERR_OVERFLOW, "internal: a segment outgrew the segment bound"); return 0; }
-        wrseg::put_u32(blob + wrseg::kHeaderBytes + 4 * k, len);
+        wrseg::put_u32(blob + head + 4 * k, len);
         at += len;
     }
     return at;
+}
+
+// the symbols of a blob that check_index has passed, in the order they were coded in
+static int seg_decode_ref(const unsigned char* blob, size_t len, unsigned char* sym, size_t n, uint32_t seg, uint32_t nseg, uint32_t brick)
+{
+    const size_t head = wrseg::header_bytes(brick);
+    size_t at = head + 4 * (size_t)nseg;
+    for (uint32_t k = 0; k < nseg; k++) {
+        const size_t base = (size_t)k * seg;
+        const uint32_t bs = n - base < seg ? (uint32_t)(n - base) : seg;
+        const uint32_t l = wrseg::get_u32(blob + head + 4 * (size_t)k);
+        if (wrseg::decode_segment_host(blob + at, l, blob, blob + len, sym + base, bs) != wrseg::kSegOk)
+            return fail(WR_ERR_STREAM, "segmented plane: segment " + std::to_string(k) + " does not decode to its symbols");
+        at += l;
+    }
+    return WR_OK;
+}
+
+size_t wr_seg_encode_host_ref(const unsigned char* sym, size_t n, unsigned seg, unsigned char* blob)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
+    if (!blob || (n && !sym)) { fail(WR_ERR_ARG, "null pointer"); return 0; }
+    return seg_encode_ref(sym, n, seg, 0, blob);
 }
 
 int wr_seg_decode_host_ref(const unsigned char* blob, size_t len, unsigned char* sym, size_t n)
@@ -182,15 +206,57 @@ int wr_seg_decode_host_ref(const unsigned char* blob, size_t len, unsigned char*
     if (!blob || (n && !sym)) return fail(WR_ERR_ARG, "null pointer");
     uint32_t seg = 0, nseg = 0;
     if (const char* why = wrseg::check_index(blob, len, len, n, &seg, &nseg)) return fail(WR_ERR_STREAM, why);
-    size_t at = wrseg::kHeaderBytes + 4 * (size_t)nseg;
-    for (uint32_t k = 0; k < nseg; k++) {
-        const size_t base = (size_t)k * seg;
-        const uint32_t bs = n - base < seg ? (uint32_t)(n - base) : seg;
-        const uint32_t l = wrseg::get_u32(blob + wrseg::kHeaderBytes + 4 * (size_t)k);
-        if (wrseg::decode_segment_host(blob + at, l, blob, blob + len, sym + base, bs) != wrseg::kSegOk)
-            return fail(WR_ERR_STREAM, "segmented plane: segment " + std::to_string(k) + " does not decode to its symbols");
-        at += l;
-    }
+    return seg_decode_ref(blob, len, sym, n, seg, nseg, 0);
+}
+
+// ---- the blocked symbol order (wr_blocked.h) and the WRS2 container on the calling thread
+static bool blocked_args_ok(int nx, int ny, int nz, int wlev, unsigned* brick)
+{
+    if (!*brick) *brick = WR_BRICK_DEFAULT;
+    if (nx < 1 || ny < 1 || nz < 1) { fail(WR_ERR_ARG, "non-positive dimension"); return false; }
+    if (wlev != 0 && wlev != wrlow::kMaxLevel) { fail(WR_ERR_ARG, "wlev must be 0 or 4"); return false; }
+    if (!wrblk::brick_ok(*brick)) { fail(WR_ERR_ARG, "brick edge must be one of 8, 16, 32, 64"); return false; }
+    return true;
+}
+
+int wr_blocked_order(int nx, int ny, int nz, int wlev, unsigned brick, uint64_t* pi)
+{
+    if (!blocked_args_ok(nx, ny, nz, wlev, &brick)) return WR_ERR_ARG;
+    if (!pi) return fail(WR_ERR_ARG, "null pointer");
+    wrblk::fill_order(wrblk::order_of(nx, ny, nz, wlev, brick), pi);
+    return WR_OK;
+}
+
+size_t wr_seg_bound_blocked(size_t n, unsigned seg)
+{
+    const size_t b = wr_seg_bound(n, seg);
+    return b ? b + (wrseg::kHeaderBytesBlocked - wrseg::kHeaderBytes) : 0;
+}
+
+size_t wr_seg_encode_host_ref_blocked(const unsigned char* sym, int nx, int ny, int nz, int wlev, unsigned brick, unsigned seg, unsigned char* blob)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
+    if (!blocked_args_ok(nx, ny, nz, wlev, &brick)) return 0;
+    if (!blob || !sym) { fail(WR_ERR_ARG, "null pointer"); return 0; }
+    const wrblk::Order od = wrblk::order_of(nx, ny, nz, wlev, brick);
+    std::vector<unsigned char> perm(od.n());
+    wrblk::reorder_host(od, sym, perm.data(), false);
+    return seg_encode_ref(perm.data(), od.n(), seg, brick, blob);
+}
+
+int wr_seg_decode_host_ref_blocked(const unsigned char* blob, size_t len, unsigned char* sym, int nx, int ny, int nz, int wlev)
+{
+    unsigned any = WR_BRICK_DEFAULT;
+    if (!blocked_args_ok(nx, ny, nz, wlev, &any)) return WR_ERR_ARG;
+    if (!blob || !sym) return fail(WR_ERR_ARG, "null pointer");
+    const size_t n = (size_t)nx * ny * nz;
+    uint32_t seg = 0, nseg = 0, brick = 0;
+    if (const char* why = wrseg::check_index(blob, len, len, n, &seg, &nseg, &brick)) return fail(WR_ERR_STREAM, why);
+    if (!brick) return seg_decode_ref(blob, len, sym, n, seg, nseg, 0);  // a WRS1 blob: the symbols are in natural order
+    std::vector<unsigned char> perm(n);
+    if (int rc = seg_decode_ref(blob, len, perm.data(), n, seg, nseg, brick)) return rc;
+    wrblk::reorder_host(wrblk::order_of(nx, ny, nz, wlev, brick), perm.data(), sym, true);
     return WR_OK;
 }
 
@@ -244,6 +310,26 @@ size_t wr_seg_roi_segments(int nx, int ny, int nz, int level, int wlev, const wr
     if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
     if (!roi_args_ok(nx, ny, nz, level, wlev, roi)) return 0;
     return wrroi::segments_of(nx, ny, nz, wrroi::geometry_of(wrlow::box_of(nx, ny, nz, level), wlev - level, *roi), seg, ids, ids ? cap : 0);
+}
+
+size_t wr_seg_lowres_segments_blocked(int nx, int ny, int nz, int level, int wlev, unsigned brick, unsigned seg, uint32_t* ids, size_t cap)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
+    if (!blocked_args_ok(nx, ny, nz, wlev, &brick)) return 0;
+    if (!wrlow::level_ok(level) || level > wlev) { fail(WR_ERR_ARG, "level outside [0, wlev]"); return 0; }
+    return wrblk::lowres_segments(nx, ny, nz, level, seg, ids, ids ? cap : 0);
+}
+
+size_t wr_seg_roi_segments_blocked(int nx, int ny, int nz, int level, int wlev, const wr_box* roi, unsigned brick, unsigned seg, uint32_t* ids,
+                                   size_t cap)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
+    if (!blocked_args_ok(nx, ny, nz, wlev, &brick)) return 0;
+    if (!roi_args_ok(nx, ny, nz, level, wlev, roi)) return 0;
+    return wrblk::region_segments(wrblk::order_of(nx, ny, nz, wlev, brick), wrroi::geometry_of(wrlow::box_of(nx, ny, nz, level), wlev - level, *roi),
+                                  seg, ids, ids ? cap : 0);
 }
 
 }  // extern "C"

@@ -8,6 +8,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+namespace wrblk { struct Order; }
+
 namespace wrk {
 
 // ---- 3-D CDF-9/7 lifting transform (reference src/waveletcdf97_3d/waveletcdf97_3d.c:38-468)
@@ -127,20 +129,43 @@ void copy_kernel(void* dst, const void* src, size_t bytes, int workgroups, hipSt
 // segments that failed}.  `stage`: seg_stage_bytes(n, seg) of device memory, 256-byte aligned (the uncompacted streams, one
 // region of the segment bound per segment, and the scan's arrays).  The symbols' plane is 16-byte aligned.
 size_t seg_stage_bytes(size_t n, unsigned seg);
+// brick != 0 (here and in the decoders): the blob is a WRS2 blob with that brick edge in its header -- `sym` is then the plane in
+// the blocked order (plane_reorder below); the coder does not care.
 void seg_encode(const PlaneRef& sym, size_t n, unsigned seg, uint8_t* stage, uint8_t* blob, size_t cap, unsigned long long* result_host,
-                hipStream_t st);
+                hipStream_t st, unsigned brick = 0);
 // Decode: `work` is seg_decode_work_bytes(nseg) of device memory, 256-byte aligned: {u32 bad segments} at 0 (zeroed here), at
 // 256 the nseg + 1 byte offsets of the segment streams behind the index (u64, put there by the caller from the index it
 // has VALIDATED on the host), then a u32 flag per segment (0: decoded).  A lane writes only its segment's symbols.
 size_t seg_decode_work_bytes(size_t nseg);
-void seg_decode(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, hipStream_t st);
+void seg_decode(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, hipStream_t st, unsigned brick = 0);
 // The same over a subset of the segments: `work` is seg_decode_list_work_bytes(nseg, nlist) bytes laid out as above, followed
 // by the nlist segment ids at seg_decode_list_ids(work, nseg) (u32, ascending, every one below nseg, put there by the
 // caller).  Lane j of the grid decodes segment ids[j]; only the bytes of those segments' streams are read from the blob,
 // only their symbols are written, flags[] is set for them alone.
 size_t seg_decode_list_work_bytes(size_t nseg, size_t nlist);
 uint32_t* seg_decode_list_ids(uint8_t* work, size_t nseg);
-void seg_decode_list(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, size_t nlist, hipStream_t st);
+void seg_decode_list(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, size_t nlist, hipStream_t st,
+                     unsigned brick = 0);
+
+// ---- the blocked symbol order of WRS2 (wr_blocked.hip; the order itself and its host geometry: wr_blocked.h).  `nat` is the
+// plane in natural order, `blk` the same n bytes in the blocked order, one array.  Forward: blk := nat permuted; inverse:
+// nat := blk permuted back.  ids == nullptr: the whole plane.  Otherwise ids[0, nlist) are ascending brick ids in device
+// memory (every one below od.nbricks: the host made the list) and the grid is the list: nothing outside those bricks is read
+// or written.  The box table travels in the kernel's arguments.
+constexpr int kReorderBoxes = 29;  // as kWindowBoxes
+struct ReorderBox {
+    uint32_t ox, oy, oz, ex, ey, ez;
+    uint32_t first;  // the first work item of the box
+    uint32_t wide;   // 16-byte accesses on both sides
+    unsigned long long start;
+};
+struct ReorderMap {
+    int nbox;
+    uint32_t nx, ny, brick, group, items;  // group: bricks along x per work item
+    ReorderBox box[kReorderBoxes];
+};
+// false: the plane has more work items than a grid has blocks, nothing was launched.
+bool plane_reorder(const PlaneRef& nat, uint8_t* blk, const wrblk::Order& od, bool inverse, const uint32_t* ids, size_t nlist, hipStream_t st);
 
 // ---- low-resolution decode (wr_lowres.hip): the corner box [0,bx) x [0,by) x [0,bz) of the coefficient array, gathered out
 // of the planes.  box[(z*by + y)*bx + x] = sum over the planes, in order, of q_l[(y + ny*z)*nx + x] * deps_l + minval_l (the

@@ -31,6 +31,12 @@ constexpr int kShift = 23, kExtra = 7;
 constexpr uint32_t kSegMin = 16, kSegMax = 59999, kSegDefault = 59904;
 constexpr size_t kHeaderBytes = 12;  // magic, seg, nseg
 constexpr uint8_t kMagic[4] = {'W', 'R', 'S', '1'};
+// "WRS2": the same container over the plane in the blocked symbol order (wr_blocked.h); its header has a fourth word, the
+// brick edge.  Everywhere below `brick` == 0 stands for a WRS1 blob.
+constexpr size_t kHeaderBytesBlocked = 16;  // magic, seg, nseg, brick
+constexpr uint8_t kMagicBlocked[4] = {'W', 'R', 'S', '2'};
+WRSEG_HD size_t header_bytes(uint32_t brick) { return brick ? kHeaderBytesBlocked : kHeaderBytes; }
+WRSEG_HD bool brick_ok(uint32_t b) { return b == 8 || b == 16 || b == 32 || b == 64; }
 
 WRSEG_HD bool seg_ok(uint32_t seg) { return seg >= kSegMin && seg <= kSegMax && seg % 16 == 0; }
 WRSEG_HD size_t seg_count(size_t n, uint32_t seg) { return (n + seg - 1) / seg; }
@@ -353,26 +359,40 @@ inline void put_u32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t
 // header and the index if the blob is well formed) for a plane of n symbols.  nullptr, or what is wrong with it.  On success
 // *seg and *nseg are the header's.  Nothing is read beyond `have`.
 static const char kIndexNotAvailable[] = "segmented plane: index not available";
-inline const char* check_index(const uint8_t* blob, size_t have, size_t len, size_t n, uint32_t* seg, uint32_t* nseg)
+// *brick: 0 for a WRS1 blob, the brick edge of a WRS2 blob (refused unless it is one of 8, 16, 32, 64).
+inline const char* check_index(const uint8_t* blob, size_t have, size_t len, size_t n, uint32_t* seg, uint32_t* nseg, uint32_t* brick)
 {
     if (have > len) have = len;
     if (have < kHeaderBytes) return "segmented plane: shorter than its header";
-    if (memcmp(blob, kMagic, 4) != 0) return "segmented plane: wrong magic (not a WRS1 stream)";
-    const uint32_t s = get_u32(blob + 4), k = get_u32(blob + 8);
+    const bool blocked = memcmp(blob, kMagicBlocked, 4) == 0;
+    if (!blocked && memcmp(blob, kMagic, 4) != 0) return "segmented plane: wrong magic (neither a WRS1 nor a WRS2 stream)";
+    const size_t head = blocked ? kHeaderBytesBlocked : kHeaderBytes;
+    if (have < head) return "segmented plane: shorter than its header";
+    const uint32_t s = get_u32(blob + 4), k = get_u32(blob + 8), b = blocked ? get_u32(blob + 12) : 0;
     if (!seg_ok(s)) return "segmented plane: segment length out of range";
+    if (blocked && !brick_ok(b)) return "segmented plane: brick edge is not one of 8, 16, 32, 64";
     if ((size_t)k != seg_count(n, s)) return "segmented plane: segment count does not match the plane";
-    if ((len - kHeaderBytes) / 4 < k) return "segmented plane: index longer than the blob";
-    if (have < kHeaderBytes + 4 * (size_t)k) return kIndexNotAvailable;
+    if ((len - head) / 4 < k) return "segmented plane: index longer than the blob";
+    if (have < head + 4 * (size_t)k) return kIndexNotAvailable;
     size_t sum = 0;
     const uint32_t bound = stream_bound(s);
     for (uint32_t j = 0; j < k; j++) {
-        const uint32_t l = get_u32(blob + kHeaderBytes + 4 * (size_t)j);
+        const uint32_t l = get_u32(blob + head + 4 * (size_t)j);
         if (l > bound) return "segmented plane: a segment is longer than a segment can be";
         sum += l;
     }
-    if (sum != len - kHeaderBytes - 4 * (size_t)k) return "segmented plane: segment lengths do not add up to the blob";
-    *seg = s; *nseg = k;
+    if (sum != len - head - 4 * (size_t)k) return "segmented plane: segment lengths do not add up to the blob";
+    *seg = s; *nseg = k; *brick = b;
     return nullptr;
+}
+
+// the same for a caller that reads WRS1 only
+inline const char* check_index(const uint8_t* blob, size_t have, size_t len, size_t n, uint32_t* seg, uint32_t* nseg)
+{
+    if ((have > len ? len : have) < kHeaderBytes) return "segmented plane: shorter than its header";
+    if (memcmp(blob, kMagic, 4) != 0) return "segmented plane: wrong magic (not a WRS1 stream)";
+    uint32_t brick = 0;
+    return check_index(blob, have, len, n, seg, nseg, &brick);
 }
 
 }  // namespace wrseg

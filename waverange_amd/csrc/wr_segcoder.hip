@@ -118,13 +118,14 @@ constexpr int kScanThreads = 1024;
 
 // result[0] = the blob's length, result[1] = segments that did not fit their region (0 always: see k_seg_encode).  The blob's
 // header and index are written if they fit under cap (the host has checked that before the launch).
-__global__ __launch_bounds__(kScanThreads) void k_seg_scan(const uint32_t* lens, uint32_t nseg, uint32_t seg, unsigned long long* offs,
+__global__ __launch_bounds__(kScanThreads) void k_seg_scan(const uint32_t* lens, uint32_t nseg, uint32_t seg, uint32_t brick, unsigned long long* offs,
                                                            uint8_t* blob, size_t cap, unsigned long long* result,
                                                            unsigned long long* result_host)
 {
     __shared__ unsigned long long part[kScanThreads];
     __shared__ unsigned int bad;
     const uint32_t t = threadIdx.x;
+    const size_t head = wrseg::header_bytes(brick);  // (brick != 0: the blocked format's header, one word longer)
     if (t == 0) bad = 0;
     __syncthreads();
     const uint32_t per = (nseg + kScanThreads - 1) / kScanThreads;
@@ -142,19 +143,21 @@ __global__ __launch_bounds__(kScanThreads) void k_seg_scan(const uint32_t* lens,
     if (t == 0) {
         unsigned long long run = 0;
         for (int j = 0; j < kScanThreads; j++) { const unsigned long long v = part[j]; part[j] = run; run += v; }
-        const unsigned long long total = wrseg::kHeaderBytes + 4ull * nseg + run;
+        const unsigned long long total = head + 4ull * nseg + run;
         offs[nseg] = run;
         result[0] = total; result[1] = bad;
         if (result_host) { result_host[0] = total; result_host[1] = bad; }
-        if (cap >= wrseg::kHeaderBytes) {
+        if (cap >= head) {
             uint32_t* const h = reinterpret_cast<uint32_t*>(blob);
-            h[0] = (uint32_t)wrseg::kMagic[0] | (uint32_t)wrseg::kMagic[1] << 8 | (uint32_t)wrseg::kMagic[2] << 16 | (uint32_t)wrseg::kMagic[3] << 24;
+            const uint8_t* const mg = brick ? wrseg::kMagicBlocked : wrseg::kMagic;
+            h[0] = (uint32_t)mg[0] | (uint32_t)mg[1] << 8 | (uint32_t)mg[2] << 16 | (uint32_t)mg[3] << 24;
             h[1] = seg; h[2] = nseg;
+            if (brick) h[3] = brick;
         }
     }
     __syncthreads();
-    const bool index_fits = cap >= wrseg::kHeaderBytes + 4ull * nseg;
-    uint32_t* const index = reinterpret_cast<uint32_t*>(blob + wrseg::kHeaderBytes);
+    const bool index_fits = cap >= head + 4ull * nseg;
+    uint32_t* const index = reinterpret_cast<uint32_t*>(blob + head);
     unsigned long long run = part[t];
     for (size_t k = k0; k < k1; k++) {
         const uint32_t l = lens[k];
@@ -169,11 +172,11 @@ constexpr int kGatherThreads = 256;
 // blob[header + index + offs[k] ...) := the first lens[k] bytes of segment k's staging region.  Nothing is written unless the
 // whole blob fits under cap and every segment is good.
 __global__ __launch_bounds__(kGatherThreads) void k_seg_gather(const uint32_t* stage, uint32_t stride_words, const uint32_t* lens,
-                                                               const unsigned long long* offs, uint32_t nseg, uint8_t* blob, size_t cap,
-                                                               const unsigned long long* result)
+                                                               const unsigned long long* offs, uint32_t nseg, uint32_t brick, uint8_t* blob,
+                                                               size_t cap, const unsigned long long* result)
 {
     if (result[0] > cap || result[1]) return;
-    const size_t front = wrseg::kHeaderBytes + 4 * (size_t)nseg;
+    const size_t front = wrseg::header_bytes(brick) + 4 * (size_t)nseg;
     const uint32_t t = threadIdx.x;
     for (size_t k = blockIdx.x; k < nseg; k += gridDim.x) {
         const uint32_t* const src = stage + k * stride_words;
@@ -202,8 +205,8 @@ __global__ __launch_bounds__(kGatherThreads) void k_seg_gather(const uint32_t* s
 // segment j, and ids / nlist are not looked at.  flags[] is indexed by the segment either way.
 template <bool kList>
 __global__ __launch_bounds__(kLanes) void k_seg_decode(const uint8_t* blob, size_t blob_len, const unsigned long long* offs, PlaneRef sym, size_t n,
-                                                       uint32_t seg, uint32_t nseg, uint32_t* flags, unsigned int* bad, const uint32_t* ids,
-                                                       uint32_t nlist)
+                                                       uint32_t seg, uint32_t nseg, uint32_t brick, uint32_t* flags, unsigned int* bad,
+                                                       const uint32_t* ids, uint32_t nlist)
 {
     __shared__ uint32_t tab[256 * kLanes];
     const uint32_t lane = threadIdx.x;
@@ -217,7 +220,7 @@ __global__ __launch_bounds__(kLanes) void k_seg_decode(const uint8_t* blob, size
     const size_t base = k * seg;
     const uint32_t bs = n - base < seg ? (uint32_t)(n - base) : seg;
     // (the host has validated the index: the streams lie inside the blob, in order, each no longer than a segment can be)
-    const size_t front = wrseg::kHeaderBytes + 4 * (size_t)nseg;
+    const size_t front = wrseg::header_bytes(brick) + 4 * (size_t)nseg;
     const unsigned long long o0 = offs[k], o1 = offs[k + 1];
     uint32_t why = wrseg::kSegOverflow;
     if (o1 >= o0 && front + o1 <= blob_len && o1 - o0 <= wrseg::stream_bound(seg)) {
@@ -241,7 +244,7 @@ size_t seg_stage_bytes(size_t n, unsigned seg)
 }
 
 void seg_encode(const PlaneRef& sym, size_t n, unsigned seg, uint8_t* stage, uint8_t* blob, size_t cap, unsigned long long* result_host,
-                hipStream_t st)
+                hipStream_t st, unsigned brick)
 {
     const size_t nseg = wrseg::seg_count(n, seg);
     const uint32_t stride_words = (wrseg::stream_bound(seg) + 3) / 4;
@@ -252,16 +255,18 @@ void seg_encode(const PlaneRef& sym, size_t n, unsigned seg, uint8_t* stage, uin
     if (nseg)
         hipLaunchKernelGGL(k_seg_encode, dim3((unsigned)((nseg + kLanes - 1) / kLanes)), dim3(kLanes), 0, st, sym, n, (uint32_t)seg, (uint32_t)nseg,
                            regions, stride_words, lens);
-    hipLaunchKernelGGL(k_seg_scan, dim3(1), dim3(kScanThreads), 0, st, lens, (uint32_t)nseg, (uint32_t)seg, offs, blob, cap, result, result_host);
+    hipLaunchKernelGGL(k_seg_scan, dim3(1), dim3(kScanThreads), 0, st, lens, (uint32_t)nseg, (uint32_t)seg, (uint32_t)brick, offs, blob, cap, result,
+                       result_host);
     if (nseg) {
         const unsigned grid = (unsigned)(nseg < 65536 ? nseg : 65536);
-        hipLaunchKernelGGL(k_seg_gather, dim3(grid), dim3(kGatherThreads), 0, st, regions, stride_words, lens, offs, (uint32_t)nseg, blob, cap, result);
+        hipLaunchKernelGGL(k_seg_gather, dim3(grid), dim3(kGatherThreads), 0, st, regions, stride_words, lens, offs, (uint32_t)nseg, (uint32_t)brick, blob,
+                           cap, result);
     }
 }
 
 size_t seg_decode_work_bytes(size_t nseg) { return 256 + ((8 * (nseg + 1) + 255) & ~(size_t)255) + 4 * nseg; }
 
-void seg_decode(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, hipStream_t st)
+void seg_decode(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, hipStream_t st, unsigned brick)
 {
     const size_t nseg = wrseg::seg_count(n, seg);
     if (!nseg) return;
@@ -270,14 +275,15 @@ void seg_decode(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_
     const unsigned long long* const offs = reinterpret_cast<const unsigned long long*>(work + 256);
     uint32_t* const flags = reinterpret_cast<uint32_t*>(work + 256 + ((8 * (nseg + 1) + 255) & ~(size_t)255));
     hipLaunchKernelGGL(k_seg_decode<false>, dim3((unsigned)((nseg + kLanes - 1) / kLanes)), dim3(kLanes), 0, st, blob, blob_len, offs, sym, n,
-                       (uint32_t)seg, (uint32_t)nseg, flags, bad, (const uint32_t*)nullptr, 0u);
+                       (uint32_t)seg, (uint32_t)nseg, (uint32_t)brick, flags, bad, (const uint32_t*)nullptr, 0u);
 }
 
 size_t seg_decode_list_work_bytes(size_t nseg, size_t nlist) { return ((seg_decode_work_bytes(nseg) + 255) & ~(size_t)255) + 4 * nlist; }
 
 uint32_t* seg_decode_list_ids(uint8_t* work, size_t nseg) { return reinterpret_cast<uint32_t*>(work + ((seg_decode_work_bytes(nseg) + 255) & ~(size_t)255)); }
 
-void seg_decode_list(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, size_t nlist, hipStream_t st)
+void seg_decode_list(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, size_t nlist, hipStream_t st,
+                     unsigned brick)
 {
     const size_t nseg = wrseg::seg_count(n, seg);
     unsigned int* const bad = reinterpret_cast<unsigned int*>(work);
@@ -286,7 +292,7 @@ void seg_decode_list(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, 
     const unsigned long long* const offs = reinterpret_cast<const unsigned long long*>(work + 256);
     uint32_t* const flags = reinterpret_cast<uint32_t*>(work + 256 + ((8 * (nseg + 1) + 255) & ~(size_t)255));
     hipLaunchKernelGGL(k_seg_decode<true>, dim3((unsigned)((nlist + kLanes - 1) / kLanes)), dim3(kLanes), 0, st, blob, blob_len, offs, sym, n,
-                       (uint32_t)seg, (uint32_t)nseg, flags, bad, seg_decode_list_ids(work, nseg), (uint32_t)nlist);
+                       (uint32_t)seg, (uint32_t)nseg, (uint32_t)brick, flags, bad, seg_decode_list_ids(work, nseg), (uint32_t)nlist);
 }
 
 }  // namespace wrk
