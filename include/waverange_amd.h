@@ -506,6 +506,65 @@ size_t wr_seg_encode_host_ref_blocked(const unsigned char *sym, int nx, int ny, 
 int wr_seg_decode_host_ref_blocked(const unsigned char *blob, size_t len, unsigned char *sym, int nx, int ny, int nz,
                                    int wlev);
 
+/* ---- Stranded segments ("WRS3"): an opt-in fourth stream format -- short coder chains that share one model.
+ * Everything is WRS1's (or, with a brick edge, WRS2's) -- transform, quantizer, header scalars, the rules for `seg`, the
+ * symbol order -- except how a segment is coded.  A WRS1 segment is one chain of up to 59 999 dependent coder steps and carries
+ * its own model of 256 counts (about 512 bytes), so a shorter chain used to mean a shorter segment and a model per chain.
+ * WRS3 keeps the MODEL per segment and cuts the CHAIN: the segment's symbols are coded as K independent strands, each a complete
+ * coder run over a contiguous K-th of the segment, all with the segment's one table.  A strand costs about ten bytes (a length
+ * word, the start byte, the five bytes of the finish).  All fields little endian:
+ *   plane blob := 'W','R','S','3' | u32 seg | u32 nseg | u32 brick | u32 strands | u32 len[nseg] | segment records, in order
+ *   seg      as WRS1: a multiple of 16 in [16, 59999]; nseg = ceil(n / seg)
+ *   brick    0: the natural (WRS1) symbol order; 8 / 16 / 32 / 64: the blocked (WRS2) order with that brick edge
+ *   strands  K, one of 1, 2, 4, 8, 16, 32 with 16 * K <= seg.  strands = 0 in a call means WR_STRANDS_DEFAULT.
+ *   L        the strand length, 16 * ceil(seg / (16 * K))
+ * Segment k holds the bs stream positions [k*seg, k*seg + bs) of the (possibly permuted) plane, bs = min(seg, n - k*seg).
+ * Strand j of it covers the segment's positions [j*L, min((j+1)*L, bs)); the first Kk = ceil(bs / L) strands are non-empty.
+ *   record k := u32 tlen | u32 slen[K] | T | S_0 | ... | S_{Kk-1} | 0-3 zero bytes up to a multiple of 4
+ * In terms of the range coder's calls (rangecod.c; csrc/wr_segcoder.h holds them as wrseg::Enc), with count_s the number of
+ * times symbol s occurs in the whole segment and cum_s the sum of the counts below s:
+ *   T    start_encoding(0); encode_short(count_s) for s = 0..255; done_encoding                       tlen bytes
+ *   S_j  start_encoding(0); encode_freq(count_s, cum_s, bs) for each symbol s of strand j in order;
+ *        encode_freq(1, 0, 2); done_encoding                                                            slen[j] bytes
+ * slen[j] = 0 and no bytes for j >= Kk.  len[k] is the record's length including the padding; the header and the index are
+ * 4-byte aligned, so every record and every slen array is.
+ * Bounds (derived in csrc/wr_segcoder.h from the coder step): tlen <= 520, slen[j] <= 2 * L + 8, a record is at most
+ * 4 * (K + 1) + 520 + K * (2 * L + 8) bytes.  WRS1's bound of about 1.03 bytes per symbol does NOT hold for a strand: a symbol
+ * that is rare in its segment costs up to 16 bits wherever it stands.
+ * Refused before anything is launched (WR_ERR_STREAM): what WRS1 / WRS2 refuse in a header or index, a strand count or brick
+ * outside the lists above, a len[k] above the record bound or not a multiple of 4, planes of one stream that differ in
+ * format, brick or strand count.  Refused per record, before a symbol of it is written, and counted in bad_segments:
+ * len[k] < 4 * (K + 1); a slen[j] above its bound or non-zero for j >= Kk; tlen above its bound; round_up4(4 * (K + 1) + tlen
+ * + sum slen) != len[k]; counts in T that do not sum to bs.  A strand whose run does not end with the zero flag is refused
+ * after its symbols.  A strand decoder runs exactly its strand's symbol count of steps, reads zeros past slen[j], and writes
+ * nothing outside its strand.
+ * The wr_decode_*_seg, _seg_lowres and _seg_roi entry points and wr_dev_seg_decode read the magic and decode this format too
+ * (wr_dev_seg_decode gives the symbols in stream order: permuted if brick != 0); segment lists, byte ranges and WR_STAT_*
+ * counters are per segment exactly as for the same seg and order in WRS1 / WRS2.  Results are bit for bit those of the WRS1
+ * stream of the same field. */
+#define WR_STRANDS_DEFAULT 8
+size_t wr_seg_bound_strands(size_t n, unsigned seg, unsigned strands); /* worst-case blob bytes of one plane; 0 if refused */
+/* stage level, as wr_dev_seg_encode: the plane as it stands, brick = 0 in the header */
+int wr_dev_seg_encode_strands(wr_ctx *ctx, const unsigned char *d_sym, size_t n, unsigned seg, unsigned strands,
+                              unsigned char *d_blob, size_t cap, size_t *blob_len);
+/* whole path: wr_encode_host_seg / _f32 / wr_encode_device_seg with every plane as a WRS3 blob.  brick = 0: the natural
+ * order (no reorder pass); 8 / 16 / 32 / 64: the blocked order. */
+int wr_encode_host_seg_strands(wr_ctx *ctx, const double *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my,
+                               int mz, const double *cutoffvec, unsigned seg, unsigned brick, unsigned strands,
+                               wr_enc_info *info, unsigned char *data_enc, size_t cap, wr_timings *tm);
+int wr_encode_host_seg_strands_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my,
+                                   int mz, const double *cutoffvec, unsigned seg, unsigned brick, unsigned strands,
+                                   wr_enc_info *info, unsigned char *data_enc, size_t cap, wr_timings *tm);
+int wr_encode_device_seg_strands(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                 const double *cutoffvec, unsigned seg, unsigned brick, unsigned strands,
+                                 wr_enc_info *info, unsigned char *data_enc, size_t cap, wr_timings *tm);
+/* host reference of the WRS3 format, on the calling thread: sym is the plane in NATURAL order (nx*ny*nz symbols; with
+ * brick = 0 only the product matters and wlev is not looked at, and a dimension may be 0).  blob holds
+ * wr_seg_bound_strands(n, seg, strands) bytes; returns the blob's length (0: an argument was refused).
+ * wr_seg_decode_host_ref_blocked reads WRS3 blobs too; wr_seg_decode_host_ref stays WRS1-only. */
+size_t wr_seg_encode_host_ref_strands(const unsigned char *sym, int nx, int ny, int nz, int wlev, unsigned brick,
+                                      unsigned seg, unsigned strands, unsigned char *blob);
+
 /* encoding_wrap / decoding_wrap for fp32 fields: the same arguments but the field, an implicit context per call and
  * the reference's "void + fatal" errors.  fld_1d of an encode is never overwritten (no residual write-back). */
 void wr_encoding_wrap_f32(int nx, int ny, int nz, const float *fld_1d, int wtflag, int mx, int my, int mz,

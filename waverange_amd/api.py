@@ -180,6 +180,15 @@ def lib():
     L.wr_encode_host_seg_blocked_f32.argtypes = L.wr_encode_host_seg_blocked.argtypes
     L.wr_encode_device_seg_blocked.argtypes = L.wr_encode_host_seg_blocked.argtypes
     L.wr_blocked_order.argtypes = [C.c_int] * 4 + [C.c_uint, _vp]
+    L.wr_seg_bound_strands.restype = C.c_size_t
+    L.wr_seg_bound_strands.argtypes = [C.c_size_t, C.c_uint, C.c_uint]
+    L.wr_seg_encode_host_ref_strands.restype = C.c_size_t
+    L.wr_seg_encode_host_ref_strands.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_uint, _vp]
+    L.wr_dev_seg_encode_strands.argtypes = [_vp, _vp, C.c_size_t, C.c_uint, C.c_uint, _vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    a = list(L.wr_encode_host_seg_blocked.argtypes)
+    L.wr_encode_host_seg_strands.argtypes = a[:12] + [C.c_uint] + a[12:]
+    L.wr_encode_host_seg_strands_f32.argtypes = L.wr_encode_host_seg_strands.argtypes
+    L.wr_encode_device_seg_strands.argtypes = L.wr_encode_host_seg_strands.argtypes
     L.wr_seg_bound_blocked.restype = C.c_size_t
     L.wr_seg_bound_blocked.argtypes = [C.c_size_t, C.c_uint]
     L.wr_seg_lowres_segments_blocked.restype = C.c_size_t
@@ -457,6 +466,64 @@ def seg_roi_segments_blocked(shape, level, roi, seg=0, wlev=4, brick=0):
     got = lib().wr_seg_roi_segments_blocked(nx, ny, nz, level, wlev, C.byref(r), brick, seg, ids.ctypes.data, ids.size)
     assert got == count
     return ids
+
+
+STRANDS_DEFAULT = 8  # WR_STRANDS_DEFAULT
+_BAD_SEG = "segment length must be a multiple of 16 in [16, 59999]"
+_BAD_SEG_STRANDS = _BAD_SEG + ", strands one of 1, 2, 4, 8, 16, 32 with 16 * strands <= seg"
+
+
+def seg_bound_strands(n, seg=0, strands=0):
+    """Worst-case bytes of one plane's stranded ("WRS3") blob (0 if `seg` or `strands` is refused)."""
+    return int(lib().wr_seg_bound_strands(n, seg, strands))
+
+
+def seg_encode_host_ref_strands(plane, shape=None, wlev=4, brick=0, seg=0, strands=0):
+    """The WRS3 blob of a plane given in natural order, coded on the calling thread: the definition of the format.  brick = 0:
+    the natural order (shape may be None); otherwise the blocked order of a field shaped (nz, ny, nx) with that brick edge."""
+    p = np.ascontiguousarray(plane, dtype=np.uint8).ravel()
+    nz, ny, nx = (1, 1, p.size) if shape is None else shape
+    assert p.size == nx * ny * nz
+    bound = seg_bound_strands(p.size, seg, strands)
+    if not bound:
+        raise WaveRangeError(_BAD_SEG_STRANDS)
+    out = np.empty(bound, dtype=np.uint8)
+    src = p if p.size else np.zeros(1, dtype=np.uint8)
+    n = lib().wr_seg_encode_host_ref_strands(src.ctypes.data, nx, ny, nz, wlev, brick, seg, strands, out.ctypes.data)
+    if not n:
+        raise WaveRangeError(lib().wr_last_error().decode())
+    return out[:n].copy()
+
+
+def seg_split_strands(blob):
+    """(seg, brick, K, [(T, [S_0, ..., S_{K-1}]), ...]) of a WRS3 blob whose index and length words are well formed (ValueError
+    otherwise); the strands past a record's last non-empty one are b""."""
+    b = np.ascontiguousarray(blob, dtype=np.uint8).ravel()
+    if b.size < 20 or bytes(b[:4]) != b"WRS3":
+        raise ValueError("not a WRS3 blob")
+    seg, nseg, brick, K = (int(v) for v in b[4:20].view("<u4"))
+    if 20 + 4 * nseg > b.size:
+        raise ValueError("index longer than the blob")
+    lens = b[20:20 + 4 * nseg].view("<u4").astype(np.int64)
+    at = 20 + 4 * nseg
+    if at + int(lens.sum()) != b.size:
+        raise ValueError("segment lengths do not add up to the blob")
+    out = []
+    for ln in lens:
+        ln = int(ln)
+        if ln < 4 * (K + 1) or ln % 4:
+            raise ValueError("a record shorter than its length words")
+        words = [int(v) for v in b[at:at + 4 * (K + 1)].view("<u4")]
+        if (4 * (K + 1) + sum(words) + 3) // 4 * 4 != ln:
+            raise ValueError("a record's lengths do not add up to the record")
+        p = at + 4 * (K + 1)
+        pieces = []
+        for w in words:
+            pieces.append(bytes(b[p:p + w]))
+            p += w
+        out.append((pieces[0], pieces[1:]))
+        at += ln
+    return seg, brick, K, out
 
 
 def seg_split(blob):
@@ -879,20 +946,21 @@ class Context:
         return tm.as_dict()
 
     # ---- segmented plane streams ("WRS1"): the planes are coded and decoded by the GPU; not readable by the reference's tools
-    def _seg_cap(self, shape, seg, brick=None):
+    def _seg_cap(self, shape, seg, brick=None, strands=None):
         nz, ny, nx = shape
         _, cap = setup_wr(nx, ny, nz)
         n = nx * ny * nz
-        bound = seg_bound(n, seg) if brick is None else seg_bound_blocked(n, seg)
+        bound = seg_bound_strands(n, seg, strands) if strands is not None else seg_bound(n, seg) if brick is None else seg_bound_blocked(n, seg)
         return cap + NLAYMAX * max(bound - n, 0)
 
-    def _encode_seg(self, fn, ptr, shape, tolrel, wtflag, seg, out, cutoff, m, brick=None):
-        """brick is None: `fn` is a WRS1 encoder; otherwise its _blocked form (brick = 0: BRICK_DEFAULT)"""
+    def _encode_seg(self, fn, ptr, shape, tolrel, wtflag, seg, out, cutoff, m, brick=None, strands=None):
+        """brick is None: `fn` is a WRS1 encoder; otherwise its _blocked form (brick = 0: BRICK_DEFAULT).  strands is not None:
+        `fn` is the _strands form (WRS3; strands = 0: STRANDS_DEFAULT; brick None or 0: the natural order)"""
         nz, ny, nx = shape
-        data = out if out is not None else np.empty(self._seg_cap(shape, seg, brick), dtype=np.uint8)
+        data = out if out is not None else np.empty(self._seg_cap(shape, seg, brick, strands), dtype=np.uint8)
         cut = np.ascontiguousarray([tolrel] if cutoff is None else cutoff, dtype=np.float64)
         info, tm = EncInfo(), Timings()
-        fmt = (seg,) if brick is None else (seg, brick)
+        fmt = (seg, brick or 0, strands) if strands is not None else (seg,) if brick is None else (seg, brick)
         _check(fn(self.h, ptr, nx, ny, nz, wtflag, m[0], m[1], m[2], cut.ctypes.data_as(_dp), *fmt, C.byref(info),
                   data.ctypes.data, data.size, C.byref(tm)))
         d = info.as_dict()
@@ -909,32 +977,35 @@ class Context:
         _check(fn(self.h, ptr, nx, ny, nz, C.byref(info), data.ctypes.data, data.size, C.byref(tm)))
         return tm.as_dict()
 
-    def encode_host_seg(self, fld, tolrel, wtflag=1, seg=0, out=None, cutoff=None, m=(1, 1, 1), brick=None):
+    def encode_host_seg(self, fld, tolrel, wtflag=1, seg=0, out=None, cutoff=None, m=(1, 1, 1), brick=None, strands=None):
         """encode_host with every plane as a segmented blob (seg = 0: SEG_DEFAULT); header scalars as encode_host's.  brick is
-        None: WRS1; otherwise the blocked order ("WRS2") with that brick edge (0: BRICK_DEFAULT).  The decoders read either."""
+        None: WRS1; otherwise the blocked order ("WRS2") with that brick edge (0: BRICK_DEFAULT).  strands is not None: stranded
+        segments ("WRS3") with that many strands (0: STRANDS_DEFAULT), in the natural order (brick None or 0) or the blocked
+        order with the brick edge `brick`.  The decoders read all three."""
         assert fld.dtype == np.float64 and fld.flags["C_CONTIGUOUS"]
-        fn = lib().wr_encode_host_seg if brick is None else lib().wr_encode_host_seg_blocked
-        return self._encode_seg(fn, fld.ctypes.data, fld.shape, tolrel, wtflag, seg, out, cutoff, m, brick)
+        fn = lib().wr_encode_host_seg_strands if strands is not None else lib().wr_encode_host_seg if brick is None else lib().wr_encode_host_seg_blocked
+        return self._encode_seg(fn, fld.ctypes.data, fld.shape, tolrel, wtflag, seg, out, cutoff, m, brick, strands)
 
     def decode_host_seg(self, out, enc):
         assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"]
         return self._decode_seg(lib().wr_decode_host_seg, out.ctypes.data, out.shape, enc)
 
-    def encode_host_seg_f32(self, fld, tolrel, wtflag=1, seg=0, out=None, cutoff=None, m=(1, 1, 1), brick=None):
+    def encode_host_seg_f32(self, fld, tolrel, wtflag=1, seg=0, out=None, cutoff=None, m=(1, 1, 1), brick=None, strands=None):
         if not (isinstance(fld, np.ndarray) and fld.dtype == np.float32 and fld.flags["C_CONTIGUOUS"]):
             raise TypeError("encode_host_seg_f32: a C-contiguous float32 array is required")
-        fn = lib().wr_encode_host_seg_f32 if brick is None else lib().wr_encode_host_seg_blocked_f32
-        return self._encode_seg(fn, fld.ctypes.data, fld.shape, tolrel, wtflag, seg, out, cutoff, m, brick)
+        fn = (lib().wr_encode_host_seg_strands_f32 if strands is not None else
+              lib().wr_encode_host_seg_f32 if brick is None else lib().wr_encode_host_seg_blocked_f32)
+        return self._encode_seg(fn, fld.ctypes.data, fld.shape, tolrel, wtflag, seg, out, cutoff, m, brick, strands)
 
     def decode_host_seg_f32(self, out, enc):
         if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"]):
             raise TypeError("decode_host_seg_f32: a C-contiguous float32 array is required")
         return self._decode_seg(lib().wr_decode_host_seg_f32, out.ctypes.data, out.shape, enc)
 
-    def encode_seg(self, buf, shape, tolrel, wtflag=1, seg=0, out=None, cutoff=None, m=(1, 1, 1), brick=None):
+    def encode_seg(self, buf, shape, tolrel, wtflag=1, seg=0, out=None, cutoff=None, m=(1, 1, 1), brick=None, strands=None):
         """encode_host_seg with the field resident on the device (`buf` is consumed, as by encode)."""
-        fn = lib().wr_encode_device_seg if brick is None else lib().wr_encode_device_seg_blocked
-        return self._encode_seg(fn, buf.ptr, shape, tolrel, wtflag, seg, out, cutoff, m, brick)
+        fn = lib().wr_encode_device_seg_strands if strands is not None else lib().wr_encode_device_seg if brick is None else lib().wr_encode_device_seg_blocked
+        return self._encode_seg(fn, buf.ptr, shape, tolrel, wtflag, seg, out, cutoff, m, brick, strands)
 
     def plane_reorder(self, plane, shape, wlev=4, brick=0, inverse=False):
         """Stage level: a plane (uint8, nz*ny*nx symbols) through the reorder kernel (wr_dev_plane_reorder).  Forward: natural
@@ -1017,18 +1088,22 @@ class Context:
         """decode_host_seg_roi into device memory: `buf` holds the region's elements as float64."""
         return self._decode_seg_roi(lib().wr_decode_device_seg_roi, buf.ptr, shape, level, roi, enc, max_planes)
 
-    def seg_encode_plane(self, plane, seg=0):
-        """Stage level: one plane of symbols (a numpy uint8 array) through the coder kernels; returns the blob."""
+    def seg_encode_plane(self, plane, seg=0, strands=None):
+        """Stage level: one plane of symbols (a numpy uint8 array) through the coder kernels; returns the blob (WRS1, or with
+        strands not None WRS3 in the natural order)."""
         p = np.ascontiguousarray(plane, dtype=np.uint8).ravel()
-        bound = seg_bound(p.size, seg)
+        bound = seg_bound(p.size, seg) if strands is None else seg_bound_strands(p.size, seg, strands)
         if not bound:
-            raise WaveRangeError("segment length must be a multiple of 16 in [16, 59999]")
+            raise WaveRangeError(_BAD_SEG if strands is None else _BAD_SEG_STRANDS)
         d_sym, d_blob = self.alloc(max(p.size, 16)), self.alloc(bound)
         try:
             if p.size:
                 d_sym.upload(p)
             got = C.c_size_t(0)
-            _check(lib().wr_dev_seg_encode(self.h, d_sym.ptr, p.size, seg, d_blob.ptr, bound, C.byref(got)))
+            if strands is None:
+                _check(lib().wr_dev_seg_encode(self.h, d_sym.ptr, p.size, seg, d_blob.ptr, bound, C.byref(got)))
+            else:
+                _check(lib().wr_dev_seg_encode_strands(self.h, d_sym.ptr, p.size, seg, strands, d_blob.ptr, bound, C.byref(got)))
             return d_blob.download(np.uint8, got.value)
         finally:
             d_sym.free()

@@ -1221,13 +1221,15 @@ struct SegBufs {
 unsigned long long* seg_result_host(wr_ctx* c, int l) { return reinterpret_cast<unsigned long long*>(c->h_result + 8) + 2 * l; }
 unsigned long long* seg_result_dev(wr_ctx* c, int l) { return reinterpret_cast<unsigned long long*>(c->h_result_dev + 8) + 2 * l; }
 
-// brick == 0: WRS1; otherwise WRS2 with that brick edge (wr_blocked.h)
-int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, const Cutoff& cut, unsigned seg, unsigned brick, wr_enc_info* info,
-                    unsigned char* data_enc, size_t cap, wr_timings* tm)
+// strands == 0: WRS1 (brick == 0) or WRS2 with that brick edge (wr_blocked.h); otherwise WRS3 with that many strands, in the
+// natural order (brick == 0) or the blocked one
+int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, const Cutoff& cut, unsigned seg, unsigned brick, unsigned strands,
+                    wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm)
 {
     if (!seg) seg = WR_SEG_DEFAULT;
     if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
     if (brick && !wrblk::brick_ok(brick)) return fail(WR_ERR_ARG, "brick edge must be one of 8, 16, 32, 64");
+    if (strands && !wrseg::strands_ok(strands, seg)) return fail(WR_ERR_ARG, "strands must be one of 1, 2, 4, 8, 16, 32 with 16 * strands <= seg");
     if (int rc = ctx_bind(c)) return rc;
     if (int rc = check_dims(nx, ny, nz, fld.dev)) return rc;
     if (fld.none()) return fail(WR_ERR_ARG, "null field pointer");
@@ -1246,7 +1248,7 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
     c->pend_valid = false;  // planes a wr_decode_begin parked in this context do not survive an encode on it
     PlaneHold planes(c);
     SegBufs bufs(c);  // (after the planes: it goes first when the call unwinds, and waits for the stream)
-    const size_t blob_cap = ((brick ? wr_seg_bound_blocked(n, seg) : wr_seg_bound(n, seg)) + 15) & ~(size_t)15;
+    const size_t blob_cap = ((strands ? wr_seg_bound_strands(n, seg, strands) : brick ? wr_seg_bound_blocked(n, seg) : wr_seg_bound(n, seg)) + 15) & ~(size_t)15;
     wrblk::Order od{};
     if (brick) od = wrblk::order_of(nx, ny, nz, wtflag ? kWavLvl : 0, brick);
 
@@ -1274,7 +1276,7 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
     }
     // one staging buffer for the uncompacted streams, used by every plane in turn (the planes' coder kernels are ordered by
     // the context's stream); a blob buffer per plane
-    bufs.stage = plane_scratch(c, wrk::seg_stage_bytes(n, seg));
+    bufs.stage = plane_scratch(c, strands ? wrk::strand_stage_bytes(n, seg, strands) : wrk::seg_stage_bytes(n, seg));
     if (!bufs.stage.p) return WR_ERR_HIP;
     if (brick) {  // the plane in stream order: like the staging buffer one for all planes
         bufs.perm = plane_scratch(c, n);
@@ -1300,7 +1302,8 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
                 if (!wrk::plane_reorder(sym, bufs.perm.p, od, false, nullptr, 0, c->stream)) return fail(WR_ERR_ARG, "too many bricks");
                 sym = wrk::plane_ref(bufs.perm.p);
             }
-            wrk::seg_encode(sym, n, seg, bufs.stage.p, bufs.blob[l].p, blob_cap, seg_result_dev(c, (int)l), c->stream, brick);
+            if (strands) wrk::strand_encode(sym, n, seg, strands, brick, bufs.stage.p, bufs.blob[l].p, blob_cap, seg_result_dev(c, (int)l), c->stream);
+            else wrk::seg_encode(sym, n, seg, bufs.stage.p, bufs.blob[l].p, blob_cap, seg_result_dev(c, (int)l), c->stream, brick);
             HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
             if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented coder launch failed" + launch_describe(c));
             return WR_OK;
@@ -1347,16 +1350,18 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
 
 // Every plane's header and index, validated on the host before anything is launched: the kernels only ever see offsets that
 // lie inside their blob, in order, each stream no longer than a segment can be.  *brick: 0 for a WRS1 stream, the brick edge
-// of a WRS2 stream; a stream whose planes differ in format or brick is refused.
+// of a WRS2 stream; *strands: 0, or the strand count of a WRS3 stream (whose brick may be 0).  A stream whose planes differ in
+// format, brick or strand count is refused.
 int seg_check_planes(const unsigned char* data_enc, const size_t* off, const wr_enc_info* info, int nlay, size_t n, uint32_t* seg, uint32_t* nseg,
-                     uint32_t* brick)
+                     uint32_t* brick, uint32_t* strands)
 {
-    *brick = 0;
+    *brick = 0; *strands = 0;
     for (int l = 0; l < nlay; l++) {
-        uint32_t b = 0;
-        if (const char* why = wrseg::check_index(data_enc + off[l], info->len_enc_vec[l], info->len_enc_vec[l], n, &seg[l], &nseg[l], &b))
+        uint32_t b = 0, K = 0;
+        if (const char* why = wrseg::check_index(data_enc + off[l], info->len_enc_vec[l], info->len_enc_vec[l], n, &seg[l], &nseg[l], &b, &K))
             return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + why);
-        if (l == 0) *brick = b;
+        if (l == 0) { *brick = b; *strands = K; }
+        else if (K != *strands) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": the planes of the stream differ in format or in their strand count");
         else if ((b != 0) != (*brick != 0)) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": the stream mixes WRS1 and WRS2 planes");
         else if (b != *brick) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": the planes of the stream differ in their brick edge");
     }
@@ -1364,11 +1369,11 @@ int seg_check_planes(const unsigned char* data_enc, const size_t* off, const wr_
 }
 
 // the byte offsets of the segment streams behind the index, from an index that check_index has passed, into work + 256
-int seg_upload_offsets(wr_ctx* c, const uint8_t* front, uint32_t nseg, uint8_t* work, uint32_t brick = 0)
+int seg_upload_offsets(wr_ctx* c, const uint8_t* front, uint32_t nseg, uint8_t* work, uint32_t brick = 0, uint32_t strands = 0)
 {
     std::vector<unsigned long long> offs((size_t)nseg + 1);
     unsigned long long run = 0;
-    for (uint32_t k = 0; k < nseg; k++) { offs[k] = run; run += wrseg::get_u32(front + wrseg::header_bytes(brick) + 4 * (size_t)k); }
+    for (uint32_t k = 0; k < nseg; k++) { offs[k] = run; run += wrseg::get_u32(front + wrseg::header_bytes(brick, strands) + 4 * (size_t)k); }
     offs[nseg] = run;
     HIPCHK(hipMemcpy(work + 256, offs.data(), offs.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
     return WR_OK;
@@ -1407,8 +1412,8 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
     for (int l = 0; l < nlay; l++) off[l + 1] = off[l] + info->len_enc_vec[l];
     if (off[nlay] > info->ntot_enc) return fail(WR_ERR_STREAM, "len_enc_vec exceeds ntot_enc");
     if (data_len && info->ntot_enc > data_len) return fail(WR_ERR_STREAM, "ntot_enc exceeds the length of the coded buffer");
-    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0}, brick = 0;
-    if (int rc = seg_check_planes(data_enc, off, info, nlay, n, seg, nseg, &brick)) return rc;
+    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0}, brick = 0, strands = 0;
+    if (int rc = seg_check_planes(data_enc, off, info, nlay, n, seg, nseg, &brick, &strands)) return rc;
     wrblk::Order od{};
     if (brick) od = wrblk::order_of(nx, ny, nz, (int)info->wlev, brick);
     {
@@ -1429,7 +1434,7 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
     for (int l = 0; l < nlay; l++) {
         if (int rc = xfer_field(c, &c->x_field, bufs.blob[l].p, data_enc + off[l], info->len_enc_vec[l], kUp)) return rc;
         local.h2d_ms += (float)c->x_field.ms;
-        if (int rc = seg_upload_offsets(c, data_enc + off[l], nseg[l], bufs.work[l].p, brick)) return rc;
+        if (int rc = seg_upload_offsets(c, data_enc + off[l], nseg[l], bufs.work[l].p, brick, strands)) return rc;
     }
     const double t_coded = now();
     SlotNeed need;
@@ -1455,7 +1460,7 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
             launch_note(c, "seg_decode", l, bufs.blob[l].p, n, bufs.work[l].p, p.q[l]);
             HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
             wrk::seg_decode(bufs.blob[l].p, info->len_enc_vec[l], brick ? wrk::plane_ref(bufs.perm.p) : p.q[l], n, seg[l], bufs.work[l].p, c->stream,
-                            brick);
+                            brick, strands);
             if (brick && !wrk::plane_reorder(p.q[l], bufs.perm.p, od, true, nullptr, 0, c->stream)) return fail(WR_ERR_ARG, "too many bricks");
             HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
         }
@@ -1562,8 +1567,8 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     if (off[nlay] > info->ntot_enc) return fail(WR_ERR_STREAM, "len_enc_vec exceeds ntot_enc");
     if (data_len && info->ntot_enc > data_len) return fail(WR_ERR_STREAM, "ntot_enc exceeds the length of the coded buffer");
     // every plane's header and index, used or not, are validated on the host before anything is launched (decode_seg_impl)
-    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0}, brick = 0;
-    if (int rc = seg_check_planes(data_enc, off, info, nlay, n, seg, nseg, &brick)) return rc;
+    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0}, brick = 0, strands = 0;
+    if (int rc = seg_check_planes(data_enc, off, info, nlay, n, seg, nseg, &brick, &strands)) return rc;
     // a blocked stream: the bricks the plan needs, the same in every plane
     wrblk::Order od{};
     std::vector<uint32_t> bricks;
@@ -1598,7 +1603,7 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     }
     // ---- stage "up": per plane the offsets table, the id list and the streams of the listed segments
     size_t bytes_up = 0;
-    const size_t head = wrseg::header_bytes(brick);
+    const size_t head = wrseg::header_bytes(brick, strands);
     if (!bricks.empty()) HIPCHK(hipMemcpy(bufs.bricks.p, bricks.data(), bricks.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     for (int l = 0; l < used; l++) {
         const uint8_t* const front = data_enc + off[l];
@@ -1636,7 +1641,7 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
             launch_note(c, "seg_decode_list", l, bufs.blob[l].p, n, bufs.work[l].p, p.q[l]);
             HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
             wrk::seg_decode_list(bufs.blob[l].p, info->len_enc_vec[l], brick ? wrk::plane_ref(bufs.perm.p) : p.q[l], n, seg[l], bufs.work[l].p,
-                                 ids[l].size(), c->stream, brick);
+                                 ids[l].size(), c->stream, brick, strands);
             // the listed segments are in the scratch buffer in stream order: the needed bricks go to their places in the plane
             if (brick && !wrk::plane_reorder(p.q[l], bufs.perm.p, od, true, reinterpret_cast<const uint32_t*>(bufs.bricks.p), bricks.size(), c->stream))
                 return fail(WR_ERR_ARG, "too many bricks");
@@ -1713,6 +1718,34 @@ int wr_dev_seg_encode(wr_ctx* c, const unsigned char* d_sym, size_t n, unsigned 
     return WR_OK;
 }
 
+int wr_dev_seg_encode_strands(wr_ctx* c, const unsigned char* d_sym, size_t n, unsigned seg, unsigned strands, unsigned char* d_blob, size_t cap,
+                              size_t* blob_len)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!strands) strands = WR_STRANDS_DEFAULT;
+    if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
+    if (!wrseg::strands_ok(strands, seg)) return fail(WR_ERR_ARG, "strands must be one of 1, 2, 4, 8, 16, 32 with 16 * strands <= seg");
+    if (int rc = ctx_bind(c)) return rc;
+    if (!d_blob || !blob_len || (n && !d_sym)) return fail(WR_ERR_ARG, "null pointer");
+    if (((uintptr_t)d_sym | (uintptr_t)d_blob) & 15) return fail(WR_ERR_ARG, "plane and blob buffers must be 16-byte aligned");
+    const size_t nseg = wrseg::seg_count(n, seg);
+    if (nseg > 0xffffffffu) return fail(WR_ERR_ARG, "too many segments");
+    if (cap < wrseg::kHeaderBytesStrands + 4 * nseg) return fail(WR_ERR_OVERFLOW, "the blob buffer does not hold the plane's index");
+    std::lock_guard<std::mutex> lk(c->mu);
+    SegBufs bufs(c);
+    bufs.stage = plane_scratch(c, wrk::strand_stage_bytes(n, seg, strands));
+    if (!bufs.stage.p) return WR_ERR_HIP;
+    StageLock cu(c->pool->cu_mu);
+    wrk::strand_encode(wrk::plane_ref(d_sym), n, seg, strands, 0, bufs.stage.p, d_blob, cap, seg_result_dev(c, 0), c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const unsigned long long len = seg_result_host(c, 0)[0], bad = seg_result_host(c, 0)[1];
+    if (bad) return fail(WR_ERR_HIP, "internal: a record outgrew the record bound");
+    if (len > cap) return fail(WR_ERR_OVERFLOW, "the blob buffer is too small for the plane");
+    *blob_len = (size_t)len;
+    return WR_OK;
+}
+
 int wr_dev_seg_decode(wr_ctx* c, const unsigned char* d_blob, size_t blob_len, unsigned char* d_sym, size_t n, size_t* bad_segments)
 {
     if (int rc = ctx_bind(c)) return rc;
@@ -1724,21 +1757,30 @@ int wr_dev_seg_decode(wr_ctx* c, const unsigned char* d_blob, size_t blob_len, u
     std::vector<uint8_t> front(wrseg::kHeaderBytes);
     if (blob_len < front.size()) return fail(WR_ERR_STREAM, "segmented plane: shorter than its header");
     HIPCHK(hipMemcpy(front.data(), d_blob, front.size(), hipMemcpyDeviceToHost));
-    uint32_t seg = 0, nseg = 0;
-    const char* why = wrseg::check_index(front.data(), front.size(), blob_len, n, &seg, &nseg);
-    if (why == wrseg::kIndexNotAvailable) {  // (the index fits into the blob: check_index has looked)
-        front.resize(wrseg::kHeaderBytes + 4 * (size_t)wrseg::get_u32(front.data() + 8));
+    uint32_t seg = 0, nseg = 0, brick = 0, strands = 0;
+    const bool wrs3 = memcmp(front.data(), wrseg::kMagicStrands, 4) == 0;  // (a WRS3 blob's symbols come out in stream order)
+    if (wrs3 && blob_len >= wrseg::kHeaderBytesStrands) {
+        front.resize(wrseg::kHeaderBytesStrands);
         HIPCHK(hipMemcpy(front.data(), d_blob, front.size(), hipMemcpyDeviceToHost));
-        why = wrseg::check_index(front.data(), front.size(), blob_len, n, &seg, &nseg);
+    }
+    auto check = [&]() {
+        return wrs3 ? wrseg::check_index(front.data(), front.size(), blob_len, n, &seg, &nseg, &brick, &strands)
+                    : wrseg::check_index(front.data(), front.size(), blob_len, n, &seg, &nseg);
+    };
+    const char* why = check();
+    if (why == wrseg::kIndexNotAvailable) {  // (the index fits into the blob: check_index has looked)
+        front.resize(front.size() + 4 * (size_t)wrseg::get_u32(front.data() + 8));
+        HIPCHK(hipMemcpy(front.data(), d_blob, front.size(), hipMemcpyDeviceToHost));
+        why = check();
     }
     if (why) return fail(WR_ERR_STREAM, why);
     if (!nseg) return WR_OK;
     SegBufs bufs(c);
     bufs.work[0] = plane_scratch(c, wrk::seg_decode_work_bytes(nseg));
     if (!bufs.work[0].p) return WR_ERR_HIP;
-    if (int rc = seg_upload_offsets(c, front.data(), nseg, bufs.work[0].p)) return rc;
+    if (int rc = seg_upload_offsets(c, front.data(), nseg, bufs.work[0].p, 0, strands)) return rc;
     StageLock cu(c->pool->cu_mu);
-    wrk::seg_decode(d_blob, blob_len, wrk::plane_ref(d_sym), n, seg, bufs.work[0].p, c->stream);
+    wrk::seg_decode(d_blob, blob_len, wrk::plane_ref(d_sym), n, seg, bufs.work[0].p, c->stream, 0, strands);
     HIPCHK(hipGetLastError());
     unsigned int bad = 0;
     HIPCHK(hipMemcpyAsync(&bad, bufs.work[0].p, sizeof bad, hipMemcpyDeviceToHost, c->stream));
@@ -1753,7 +1795,7 @@ int wr_encode_host_seg(wr_ctx* c, const double* h_fld, int nx, int ny, int nz, i
 {
     Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
     FieldRef f; f.host = const_cast<double*>(h_fld);  // (written only with wr_ctx_set_keep_residual(ctx, 1), as wr_encode_host)
-    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, 0, info, data_enc, cap, tm);
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, 0, 0, info, data_enc, cap, tm);
 }
 
 int wr_decode_host_seg(wr_ctx* c, double* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
@@ -1768,7 +1810,7 @@ int wr_encode_host_seg_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz
 {
     Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
     FieldRef f; f.host_f32 = const_cast<float*>(h_fld);
-    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, 0, info, data_enc, cap, tm);
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, 0, 0, info, data_enc, cap, tm);
 }
 
 int wr_decode_host_seg_f32(wr_ctx* c, float* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
@@ -1784,7 +1826,7 @@ int wr_encode_device_seg(wr_ctx* c, double* d_fld, int nx, int ny, int nz, int w
     Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
     FieldRef f; f.dev = d_fld;
     if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
-    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, 0, info, data_enc, cap, tm);
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, 0, 0, info, data_enc, cap, tm);
 }
 
 int wr_decode_device_seg(wr_ctx* c, double* d_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
@@ -1800,7 +1842,7 @@ int wr_encode_host_seg_blocked(wr_ctx* c, const double* h_fld, int nx, int ny, i
 {
     Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
     FieldRef f; f.host = const_cast<double*>(h_fld);
-    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick ? brick : WR_BRICK_DEFAULT, info, data_enc, cap, tm);
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick ? brick : WR_BRICK_DEFAULT, 0, info, data_enc, cap, tm);
 }
 
 int wr_encode_host_seg_blocked_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,
@@ -1808,7 +1850,7 @@ int wr_encode_host_seg_blocked_f32(wr_ctx* c, const float* h_fld, int nx, int ny
 {
     Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
     FieldRef f; f.host_f32 = const_cast<float*>(h_fld);
-    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick ? brick : WR_BRICK_DEFAULT, info, data_enc, cap, tm);
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick ? brick : WR_BRICK_DEFAULT, 0, info, data_enc, cap, tm);
 }
 
 int wr_encode_device_seg_blocked(wr_ctx* c, double* d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,
@@ -1817,7 +1859,33 @@ int wr_encode_device_seg_blocked(wr_ctx* c, double* d_fld, int nx, int ny, int n
     Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
     FieldRef f; f.dev = d_fld;
     if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
-    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick ? brick : WR_BRICK_DEFAULT, info, data_enc, cap, tm);
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick ? brick : WR_BRICK_DEFAULT, 0, info, data_enc, cap, tm);
+}
+
+int wr_encode_host_seg_strands(wr_ctx* c, const double* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,
+                               unsigned seg, unsigned brick, unsigned strands, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm)
+{
+    Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
+    FieldRef f; f.host = const_cast<double*>(h_fld);
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick, strands ? strands : WR_STRANDS_DEFAULT, info, data_enc, cap, tm);
+}
+
+int wr_encode_host_seg_strands_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,
+                                   unsigned seg, unsigned brick, unsigned strands, wr_enc_info* info, unsigned char* data_enc, size_t cap,
+                                   wr_timings* tm)
+{
+    Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
+    FieldRef f; f.host_f32 = const_cast<float*>(h_fld);
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick, strands ? strands : WR_STRANDS_DEFAULT, info, data_enc, cap, tm);
+}
+
+int wr_encode_device_seg_strands(wr_ctx* c, double* d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,
+                                 unsigned seg, unsigned brick, unsigned strands, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm)
+{
+    Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
+    FieldRef f; f.dev = d_fld;
+    if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
+    return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick, strands ? strands : WR_STRANDS_DEFAULT, info, data_enc, cap, tm);
 }
 
 int wr_dev_plane_reorder(wr_ctx* c, unsigned char* d_dst, const unsigned char* d_src, int nx, int ny, int nz, int wlev, unsigned brick, int inverse)

@@ -245,14 +245,85 @@ size_t wr_seg_encode_host_ref_blocked(const unsigned char* sym, int nx, int ny, 
     return seg_encode_ref(perm.data(), od.n(), seg, brick, blob);
 }
 
+// ---- stranded segments ("WRS3", wr_segcoder.h) on the calling thread
+size_t wr_seg_bound_strands(size_t n, unsigned seg, unsigned strands)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!strands) strands = WR_STRANDS_DEFAULT;
+    if (!wrseg::seg_ok(seg) || !wrseg::strands_ok(strands, seg)) return 0;
+    return wrseg::kHeaderBytesStrands + wrseg::seg_count(n, seg) * (4 + (size_t)wrseg::record_bound(seg, strands));
+}
+
+// the WRS3 container around the symbols as they stand (the caller has permuted them if brick != 0)
+static size_t strands_encode_ref(const unsigned char* sym, size_t n, unsigned seg, unsigned brick, unsigned K, unsigned char* blob)
+{
+    const size_t nseg = wrseg::seg_count(n, seg), head = wrseg::kHeaderBytesStrands;
+    if (nseg > 0xffffffffu) { fail(WR_ERR_ARG, "too many segments"); return 0; }
+    memcpy(blob, wrseg::kMagicStrands, 4);
+    wrseg::put_u32(blob + 4, seg);
+    wrseg::put_u32(blob + 8, (uint32_t)nseg);
+    wrseg::put_u32(blob + 12, brick);
+    wrseg::put_u32(blob + 16, K);
+    size_t at = head + 4 * nseg;
+    for (size_t k = 0; k < nseg; k++) {
+        const size_t base = k * seg;
+        const uint32_t bs = n - base < seg ? (uint32_t)(n - base) : seg;
+        const uint32_t len = wrseg::encode_record_host(sym + base, bs, seg, K, blob + at, wrseg::record_bound(seg, K));
+        if (!len) { fail(WR_ERR_OVERFLOW, "internal: a record outgrew the record bound"); return 0; }
+        wrseg::put_u32(blob + head + 4 * k, len);
+        at += len;
+    }
+    return at;
+}
+
+static int strands_decode_ref(const unsigned char* blob, size_t len, unsigned char* sym, size_t n, uint32_t seg, uint32_t nseg, uint32_t K)
+{
+    const size_t head = wrseg::kHeaderBytesStrands;
+    size_t at = head + 4 * (size_t)nseg;
+    for (uint32_t k = 0; k < nseg; k++) {
+        const size_t base = (size_t)k * seg;
+        const uint32_t bs = n - base < seg ? (uint32_t)(n - base) : seg;
+        const uint32_t l = wrseg::get_u32(blob + head + 4 * (size_t)k);
+        if (wrseg::decode_record_host(blob + at, l, blob, blob + len, sym + base, bs, seg, K))
+            return fail(WR_ERR_STREAM, "segmented plane: segment " + std::to_string(k) + " does not decode to its symbols");
+        at += l;
+    }
+    return WR_OK;
+}
+
+size_t wr_seg_encode_host_ref_strands(const unsigned char* sym, int nx, int ny, int nz, int wlev, unsigned brick, unsigned seg, unsigned strands,
+                                      unsigned char* blob)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!strands) strands = WR_STRANDS_DEFAULT;
+    if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
+    if (!wrseg::strands_ok(strands, seg)) { fail(WR_ERR_ARG, "strands must be one of 1, 2, 4, 8, 16, 32 with 16 * strands <= seg"); return 0; }
+    if (nx < 0 || ny < 0 || nz < 0) { fail(WR_ERR_ARG, "negative dimension"); return 0; }
+    const size_t n = (size_t)nx * ny * nz;
+    if (!blob || (n && !sym)) { fail(WR_ERR_ARG, "null pointer"); return 0; }
+    if (!brick) return strands_encode_ref(sym, n, seg, 0, strands, blob);  // the natural order: the shape is only its product
+    if (!blocked_args_ok(nx, ny, nz, wlev, &brick)) return 0;
+    const wrblk::Order od = wrblk::order_of(nx, ny, nz, wlev, brick);
+    std::vector<unsigned char> perm(od.n());
+    wrblk::reorder_host(od, sym, perm.data(), false);
+    return strands_encode_ref(perm.data(), od.n(), seg, brick, strands, blob);
+}
+
 int wr_seg_decode_host_ref_blocked(const unsigned char* blob, size_t len, unsigned char* sym, int nx, int ny, int nz, int wlev)
 {
     unsigned any = WR_BRICK_DEFAULT;
     if (!blocked_args_ok(nx, ny, nz, wlev, &any)) return WR_ERR_ARG;
     if (!blob || !sym) return fail(WR_ERR_ARG, "null pointer");
     const size_t n = (size_t)nx * ny * nz;
-    uint32_t seg = 0, nseg = 0, brick = 0;
-    if (const char* why = wrseg::check_index(blob, len, len, n, &seg, &nseg, &brick)) return fail(WR_ERR_STREAM, why);
+    uint32_t seg = 0, nseg = 0, brick = 0, strands = 0;
+    if (const char* why = wrseg::check_index(blob, len, len, n, &seg, &nseg, &brick, &strands)) return fail(WR_ERR_STREAM, why);
+    if (strands) {
+        if (!brick) return strands_decode_ref(blob, len, sym, n, seg, nseg, strands);
+        std::vector<unsigned char> perm(n);
+        if (int rc = strands_decode_ref(blob, len, perm.data(), n, seg, nseg, strands)) return rc;
+        wrblk::reorder_host(wrblk::order_of(nx, ny, nz, wlev, brick), perm.data(), sym, true);
+        return WR_OK;
+    }
     if (!brick) return seg_decode_ref(blob, len, sym, n, seg, nseg, 0);  // a WRS1 blob: the symbols are in natural order
     std::vector<unsigned char> perm(n);
     if (int rc = seg_decode_ref(blob, len, perm.data(), n, seg, nseg, brick)) return rc;

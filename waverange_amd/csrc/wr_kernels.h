@@ -137,7 +137,10 @@ void seg_encode(const PlaneRef& sym, size_t n, unsigned seg, uint8_t* stage, uin
 // 256 the nseg + 1 byte offsets of the segment streams behind the index (u64, put there by the caller from the index it
 // has VALIDATED on the host), then a u32 flag per segment (0: decoded).  A lane writes only its segment's symbols.
 size_t seg_decode_work_bytes(size_t nseg);
-void seg_decode(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, hipStream_t st, unsigned brick = 0);
+// strands != 0 (here and in seg_decode_list): the blob is a WRS3 blob of that many strands per segment (its brick may be 0);
+// `work` is laid out the same, the launch is `strands` times as wide.
+void seg_decode(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, hipStream_t st, unsigned brick = 0,
+                unsigned strands = 0);
 // The same over a subset of the segments: `work` is seg_decode_list_work_bytes(nseg, nlist) bytes laid out as above, followed
 // by the nlist segment ids at seg_decode_list_ids(work, nseg) (u32, ascending, every one below nseg, put there by the
 // caller).  Lane j of the grid decodes segment ids[j]; only the bytes of those segments' streams are read from the blob,
@@ -145,7 +148,13 @@ void seg_decode(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_
 size_t seg_decode_list_work_bytes(size_t nseg, size_t nlist);
 uint32_t* seg_decode_list_ids(uint8_t* work, size_t nseg);
 void seg_decode_list(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, size_t nlist, hipStream_t st,
-                     unsigned brick = 0);
+                     unsigned brick = 0, unsigned strands = 0);
+// Stranded segments ("WRS3"): seg_encode with `strands` lanes per segment.  `stage`: strand_stage_bytes(n, seg, strands) bytes,
+// 256-byte aligned (a region of the record's bound per segment, the lengths and the scan's arrays).  brick goes into the header
+// as it is (0: `sym` is in natural order).
+size_t strand_stage_bytes(size_t n, unsigned seg, unsigned strands);
+void strand_encode(const PlaneRef& sym, size_t n, unsigned seg, unsigned strands, unsigned brick, uint8_t* stage, uint8_t* blob, size_t cap,
+                   unsigned long long* result_host, hipStream_t st);
 
 // ---- the blocked symbol order of WRS2 (wr_blocked.hip; the order itself and its host geometry: wr_blocked.h).  `nat` is the
 // plane in natural order, `blk` the same n bytes in the blocked order, one array.  Forward: blk := nat permuted; inverse:
