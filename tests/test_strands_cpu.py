@@ -11,176 +11,12 @@ import tempfile
 import numpy as np
 import pytest
 
+from py_coder import model_of, py_blob, py_decode_model, py_decode_strand, py_wrs1_segment, strand_len
 from util import ROOT, kat_plane
 from oracle.loader import Oracle
 from waverange_amd import api, synth
 
 CSRC = os.path.join(ROOT, "waverange_amd", "csrc")
-TOP, BOTTOM, SHIFT = 1 << 31, 1 << 23, 23
-
-
-# ---- the definition: the coder steps in their classical form ----------------------------------------------------------------
-class PyEnc:
-    """rngcod13's encoder with the carry propagated back into the bytes already written (the library keeps a held byte and a
-    count of pending 0xff bytes instead).  out[0] is the byte given to start_encoding."""
-
-    def __init__(self):
-        self.low, self.range, self.n, self.out = 0, TOP, 0, bytearray([0])
-
-    def _carry(self):
-        i = len(self.out) - 1
-        while self.out[i] == 0xFF:
-            self.out[i] = 0
-            i -= 1
-        self.out[i] += 1
-
-    def _renorm(self):
-        while self.range <= BOTTOM:
-            if self.low & TOP:
-                self._carry()
-            self.out.append((self.low >> SHIFT) & 0xFF)
-            self.low = (self.low << 8) & (TOP - 1)
-            self.range <<= 8
-            self.n += 1
-
-    def freq(self, sy, lt, tot):
-        self._renorm()
-        r = self.range // tot
-        t = r * lt
-        self.low += t
-        self.range = r * sy if lt + sy < tot else self.range - t
-
-    def short(self, v):
-        self._renorm()
-        r = self.range >> 16
-        t = r * v
-        self.low += t
-        self.range = self.range - t if (v + 1) >> 16 else r
-
-    def done(self):
-        self._renorm()
-        self.n += 5
-        t = self.low >> SHIFT
-        if (self.low & (BOTTOM - 1)) >= ((self.n & 0xFFFFFF) >> 1):
-            t += 1
-        if t > 0xFF:
-            self._carry()
-        self.out.append(t & 0xFF)
-        self.out += bytes([(self.n >> 16) & 0xFF, (self.n >> 8) & 0xFF, self.n & 0xFF])
-        return bytes(self.out)
-
-
-def model_of(sym):
-    count = np.bincount(sym, minlength=256).tolist()
-    cum = [0] * 256
-    for s in range(1, 256):
-        cum[s] = cum[s - 1] + count[s - 1]
-    return count, cum
-
-
-def py_wrs1_segment(sym):
-    """One WRS1 segment: the reference's block structure around the restated steps."""
-    count, cum = model_of(sym)
-    e = PyEnc()
-    e.freq(1, 1, 2)
-    for s in range(256):
-        e.short(count[s])
-    bs = len(sym)
-    for s in sym.tolist():
-        e.freq(count[s], cum[s], bs)
-    e.freq(1, 0, 2)
-    return e.done()
-
-
-def strand_len(seg, K):
-    return 16 * ((seg + 16 * K - 1) // (16 * K))
-
-
-def py_record(sym, seg, K):
-    """record := u32 tlen | u32 slen[K] | T | S_0 .. | zero bytes up to a multiple of 4"""
-    count, cum = model_of(sym)
-    bs, L = len(sym), strand_len(seg, K)
-    e = PyEnc()
-    for s in range(256):
-        e.short(count[s])
-    T = e.done()
-    strands = []
-    for j in range(K):
-        part = sym[j * L:min((j + 1) * L, bs)].tolist()
-        if not part:
-            strands.append(b"")
-            continue
-        e = PyEnc()
-        for s in part:
-            e.freq(count[s], cum[s], bs)
-        e.freq(1, 0, 2)
-        strands.append(e.done())
-    body = struct.pack("<%dI" % (K + 1), len(T), *[len(s) for s in strands]) + T + b"".join(strands)
-    return body + bytes(-len(body) % 4)
-
-
-def py_blob(plane, seg, K, brick=0):
-    n = plane.size
-    nseg = (n + seg - 1) // seg
-    recs = [py_record(plane[k * seg:min(n, (k + 1) * seg)], seg, K) for k in range(nseg)]
-    return b"WRS3" + struct.pack("<IIII", seg, nseg, brick, K) + b"".join(struct.pack("<I", len(r)) for r in recs) + b"".join(recs)
-
-
-class PyDec:
-    """rngcod13's decoder; past the end of its bytes it reads zeros."""
-
-    def __init__(self, data):
-        self.d, self.pos = data, 1  # (the byte given to start_encoding)
-        self.buffer = self._get()
-        self.low, self.range, self.help = self.buffer >> 1, 1 << 7, 0
-
-    def _get(self):
-        b = self.d[self.pos] if self.pos < len(self.d) else 0
-        self.pos += 1
-        return b
-
-    def _renorm(self):
-        while self.range <= BOTTOM:
-            self.low = (self.low << 8) | ((self.buffer << 7) & 0xFF)
-            self.buffer = self._get()
-            self.low |= self.buffer >> 1
-            self.range <<= 8
-
-    def culfreq(self, tot):
-        self._renorm()
-        self.help = self.range // tot
-        return min(self.low // self.help, tot - 1)
-
-    def culshort(self):
-        self._renorm()
-        self.help = self.range >> 16
-        return min(self.low // self.help, 0xFFFF)
-
-    def update(self, sy, lt, tot):
-        t = self.help * lt
-        self.low -= t
-        self.range = self.help * sy if lt + sy < tot else self.range - t
-
-
-def py_decode_model(T):
-    d, count = PyDec(T), []
-    for _ in range(256):
-        c = d.culshort()
-        d.update(1, c, 1 << 16)
-        count.append(c)
-    return count
-
-
-def py_decode_strand(S, count, m):
-    cum = np.concatenate(([0], np.cumsum(count)[:-1]))
-    bs, d, out = int(sum(count)), PyDec(S), []
-    for _ in range(m):
-        cf = d.culfreq(bs)
-        s = int(np.searchsorted(cum, cf, side="right")) - 1  # the last s whose cumulative count is <= cf
-        d.update(count[s], int(cum[s]), bs)
-        out.append(s)
-    assert d.culfreq(2) == 0  # the zero flag
-    return np.array(out, dtype=np.uint8)
 
 
 def test_restatement_is_the_reference_coder():
