@@ -565,6 +565,68 @@ int wr_encode_device_seg_strands(wr_ctx *ctx, double *d_fld, int nx, int ny, int
 size_t wr_seg_encode_host_ref_strands(const unsigned char *sym, int nx, int ny, int nz, int wlev, unsigned brick,
                                       unsigned seg, unsigned strands, unsigned char *blob);
 
+/* ---- Batched segmented streams: plane l of N same-shaped fields in ONE coder launch.  No new format.
+ * A plane's coder kernels take as long as one segment's chain, however few segments the plane has: a 128^3 plane is 36 lanes
+ * of a device that holds tens of thousands.  A batch call codes plane index l of all its fields in one launch sequence, one
+ * lane per segment of any field, so N small fields cost about one field's coder time.
+ *   For every field of a batch, the header record and every byte of data_enc are exactly what the single-field call returns for
+ *   that field alone -- wr_encode_host_seg with brick == 0, wr_encode_host_seg_blocked otherwise (brick != 0; there is no
+ *   default here) -- whatever the other fields of the batch are and whatever their order.  A batched decode gives, bit for bit,
+ *   what wr_decode_host_seg gives per field.  Either side may be mixed freely with the single-field calls.
+ * All fields of a batch share nx, ny, nz, wtflag, mx, my, mz, seg and brick; each has its own cutoff vector (mx*my*mz entries),
+ * its own wr_enc_info and its own output buffer of caps[i] bytes.  A decode batch may mix WRS1 and WRS2 fields.
+ * Refused with WR_ERR_ARG: nfields outside 1..WR_SEG_BATCH_MAX, null arrays or entries, and a batch whose segments of one plane
+ * index number 2^31 or more.  WR_ERR_UNSUPPORTED: a WRS3 field in a decode batch (strands are not batched), and a context with
+ * wr_ctx_set_keep_residual(ctx, 1).  The first failing field decides the return code; wr_last_error() starts with
+ * "field <index>: " and names the plane where there is one; the other fields' outputs are then unspecified.  On decode every
+ * field's lengths, headers and indices are validated on the host BEFORE anything is copied or launched for any field, and no
+ * dequantizer runs unless every segment of every field decoded.  Constant fields (nlay == 0) take part with no job.
+ * wr_timings is one record for the call: `rangecoder` is the sum of the batched coder launches, plane_coder_s[l] the launch
+ * sequence of plane index l; h2d_ms, d2h_ms, quant_ms and transform_ms are summed over the fields.
+ * Device memory: beside one work-space slot a batch takes, from the plane pool (its accounting, cap and reserve),
+ *   per (field, plane)   wr_plane_pitch(n) for the plane, the blob (encode: its bound rounded up to 16; decode: its length),
+ *                        decode: the offsets and flags of its segments
+ *   per field            brick != 0: wr_plane_pitch(n) for the plane in stream order
+ *   once                 encode: the staging of one plane index (a region of the segment bound per segment of every field, the
+ *                        scan's arrays, the job table); decode: a job table per plane index and the failure counts
+ * wr_seg_batch_device_bytes is that sum for nfields fields of n samples and nlay planes each (host only; 0 for a refused
+ * argument: nfields, n == 0, nlay outside 0..WR_NLAYMAX, seg, brick); it is the arithmetic the drivers allocate by, with every
+ * blob at its bound.  A batch the pool cannot hold fails with the pool's error before the first coder launch. */
+#define WR_SEG_BATCH_MAX 1024
+size_t wr_seg_batch_device_bytes(int nfields, size_t n, int nlay, unsigned seg, unsigned brick, int decode);
+/* the locator of the batched kernels (csrc/wr_segbatch.h), for tests: first[0 .. njobs] is the exclusive prefix of the jobs'
+ * segment counts; lane g < first[njobs] is segment *k of job *job.  WR_ERR_ARG: a prefix that does not start at 0 or
+ * decreases, njobs outside 1..WR_SEG_BATCH_MAX, g past the end. */
+int wr_seg_batch_locate(const uint32_t *first, uint32_t njobs, uint32_t g, uint32_t *job, uint32_t *k);
+/* stage level, device pointers (16-byte aligned): njobs planes of n symbols each in one launch sequence.  Every blob equals
+ * wr_dev_seg_encode's for that plane; errors as in the single-plane calls, the first failing job deciding ("job <index>: ").
+ * blob_len[j] is set for every job that was coded, bad_segments[j] (may be NULL) for every job that was decoded. */
+int wr_dev_seg_encode_batch(wr_ctx *ctx, int njobs, const unsigned char *const *d_sym, size_t n, unsigned seg,
+                            unsigned char *const *d_blob, const size_t *cap, size_t *blob_len);
+int wr_dev_seg_decode_batch(wr_ctx *ctx, int njobs, const unsigned char *const *d_blob, const size_t *blob_len,
+                            unsigned char *const *d_sym, size_t n, size_t *bad_segments);
+/* whole path */
+int wr_encode_host_seg_batch(wr_ctx *ctx, int nfields, const double *const *h_flds, int nx, int ny, int nz, int wtflag,
+                             int mx, int my, int mz, const double *const *cutoffvecs, unsigned seg, unsigned brick,
+                             wr_enc_info *infos, unsigned char *const *data_encs, const size_t *caps, wr_timings *tm);
+int wr_decode_host_seg_batch(wr_ctx *ctx, int nfields, double *const *h_flds, int nx, int ny, int nz,
+                             const wr_enc_info *infos, const unsigned char *const *data_encs, const size_t *data_lens,
+                             wr_timings *tm);
+int wr_encode_host_seg_batch_f32(wr_ctx *ctx, int nfields, const float *const *h_flds, int nx, int ny, int nz, int wtflag,
+                                 int mx, int my, int mz, const double *const *cutoffvecs, unsigned seg, unsigned brick,
+                                 wr_enc_info *infos, unsigned char *const *data_encs, const size_t *caps,
+                                 wr_timings *tm);
+int wr_decode_host_seg_batch_f32(wr_ctx *ctx, int nfields, float *const *h_flds, int nx, int ny, int nz,
+                                 const wr_enc_info *infos, const unsigned char *const *data_encs,
+                                 const size_t *data_lens, wr_timings *tm);
+/* device fields (consumed by an encode, as wr_encode_device_seg's) */
+int wr_encode_device_seg_batch(wr_ctx *ctx, int nfields, double *const *d_flds, int nx, int ny, int nz, int wtflag,
+                               int mx, int my, int mz, const double *const *cutoffvecs, unsigned seg, unsigned brick,
+                               wr_enc_info *infos, unsigned char *const *data_encs, const size_t *caps, wr_timings *tm);
+int wr_decode_device_seg_batch(wr_ctx *ctx, int nfields, double *const *d_flds, int nx, int ny, int nz,
+                               const wr_enc_info *infos, const unsigned char *const *data_encs,
+                               const size_t *data_lens, wr_timings *tm);
+
 /* encoding_wrap / decoding_wrap for fp32 fields: the same arguments but the field, an implicit context per call and
  * the reference's "void + fatal" errors.  fld_1d of an encode is never overwritten (no residual write-back). */
 void wr_encoding_wrap_f32(int nx, int ny, int nz, const float *fld_1d, int wtflag, int mx, int my, int mz,

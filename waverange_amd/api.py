@@ -189,6 +189,18 @@ def lib():
     L.wr_encode_host_seg_strands.argtypes = a[:12] + [C.c_uint] + a[12:]
     L.wr_encode_host_seg_strands_f32.argtypes = L.wr_encode_host_seg_strands.argtypes
     L.wr_encode_device_seg_strands.argtypes = L.wr_encode_host_seg_strands.argtypes
+    L.wr_seg_batch_device_bytes.restype = C.c_size_t
+    L.wr_seg_batch_device_bytes.argtypes = [C.c_int, C.c_size_t, C.c_int, C.c_uint, C.c_uint, C.c_int]
+    L.wr_seg_batch_locate.argtypes = [_vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.wr_dev_seg_encode_batch.argtypes = [_vp, C.c_int, _vp, C.c_size_t, C.c_uint, _vp, _vp, _vp]
+    L.wr_dev_seg_decode_batch.argtypes = [_vp, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp]
+    L.wr_encode_host_seg_batch.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_uint, C.c_uint,
+                                           _vp, _vp, _vp, C.POINTER(Timings)]
+    L.wr_encode_host_seg_batch_f32.argtypes = L.wr_encode_host_seg_batch.argtypes
+    L.wr_encode_device_seg_batch.argtypes = L.wr_encode_host_seg_batch.argtypes
+    L.wr_decode_host_seg_batch.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(Timings)]
+    L.wr_decode_host_seg_batch_f32.argtypes = L.wr_decode_host_seg_batch.argtypes
+    L.wr_decode_device_seg_batch.argtypes = L.wr_decode_host_seg_batch.argtypes
     L.wr_seg_bound_blocked.restype = C.c_size_t
     L.wr_seg_bound_blocked.argtypes = [C.c_size_t, C.c_uint]
     L.wr_seg_lowres_segments_blocked.restype = C.c_size_t
@@ -493,6 +505,24 @@ def seg_encode_host_ref_strands(plane, shape=None, wlev=4, brick=0, seg=0, stran
     if not n:
         raise WaveRangeError(lib().wr_last_error().decode())
     return out[:n].copy()
+
+
+SEG_BATCH_MAX = 1024  # WR_SEG_BATCH_MAX
+
+
+def seg_batch_device_bytes(nfields, n, nlay, seg=0, brick=0, decode=False):
+    """Device memory a batch of `nfields` fields of n samples and nlay planes each takes beside the work-space slot
+    (wr_seg_batch_device_bytes; brick = 0: WRS1); 0 for a refused argument."""
+    return int(lib().wr_seg_batch_device_bytes(nfields, n, nlay, seg, brick, 1 if decode else 0))
+
+
+def seg_batch_locate(first, g):
+    """(job, segment) of lane g of a batched coder launch; first: the exclusive prefix of the jobs' segment counts,
+    njobs + 1 entries (wr_seg_batch_locate)."""
+    f = np.ascontiguousarray(first, dtype=np.uint32)
+    job, k = C.c_uint32(0), C.c_uint32(0)
+    _check(lib().wr_seg_batch_locate(f.ctypes.data, max(f.size, 1) - 1, g, C.byref(job), C.byref(k)))
+    return int(job.value), int(k.value)
 
 
 def seg_split_strands(blob):
@@ -1123,6 +1153,126 @@ class Context:
         finally:
             d_blob.free()
             d_sym.free()
+
+    # ---- batched segmented streams: plane l of all fields of a batch in one coder launch; every field's stream is the single call's
+    def _encode_seg_batch(self, fn, ptrs, shape, tolrels, wtflag, seg, brick, cutoffs, m, caps=None, strands=None, outs=None):
+        if strands is not None:  # (the C entry points have no such argument: WR_ERR_UNSUPPORTED, as a WRS3 field in a decode batch)
+            raise WaveRangeError("libwaverange_amd error -3: stranded segments (WRS3) are not coded in a batch")
+        nz, ny, nx = shape
+        nf = len(ptrs)
+        b = 0 if brick is None else (brick or BRICK_DEFAULT)
+        if cutoffs is None:
+            tol = [tolrels] * nf if np.isscalar(tolrels) else list(tolrels)
+            cutoffs = [[t] for t in tol]
+        cuts = [np.ascontiguousarray(cv, dtype=np.float64) for cv in cutoffs]
+        cap = self._seg_cap(shape, seg, None if brick is None else b) if nf else 0
+        datas = list(outs) if outs is not None else [np.empty(cap if caps is None else caps[i], dtype=np.uint8) for i in range(nf)]
+        infos, tm = (EncInfo * max(nf, 1))(), Timings()
+        fp = (C.c_void_p * max(nf, 1))(*ptrs)
+        cp = (C.c_void_p * max(nf, 1))(*[cv.ctypes.data for cv in cuts])
+        dp = (C.c_void_p * max(nf, 1))(*[d.ctypes.data for d in datas])
+        sz = (C.c_size_t * max(nf, 1))(*[d.size for d in datas])
+        _check(fn(self.h, nf, fp, nx, ny, nz, wtflag, m[0], m[1], m[2], cp, seg, b, infos, dp, sz, C.byref(tm)))
+        encs = []
+        for i in range(nf):
+            d = infos[i].as_dict()
+            d["data"] = datas[i][:infos[i].ntot_enc]
+            encs.append(d)
+        return encs, tm.as_dict()
+
+    def _decode_seg_batch(self, fn, ptrs, shape, encs):
+        nz, ny, nx = shape
+        nf = len(ptrs)
+        infos, tm = (EncInfo * max(nf, 1))(), Timings()
+        datas = []
+        for i, enc in enumerate(encs):
+            infos[i] = EncInfo.from_dict(enc)
+            d = np.ascontiguousarray(enc["data"], dtype=np.uint8)
+            datas.append(d if d.size else np.zeros(1, dtype=np.uint8))
+        fp = (C.c_void_p * max(nf, 1))(*ptrs)
+        dp = (C.c_void_p * max(nf, 1))(*[d.ctypes.data for d in datas])
+        sz = (C.c_size_t * max(nf, 1))(*[d.size for d in datas])
+        _check(fn(self.h, nf, fp, nx, ny, nz, infos, dp, sz, C.byref(tm)))
+        return tm.as_dict()
+
+    def encode_host_seg_batch(self, fields, tolrels, wtflag=1, seg=0, brick=None, cutoffs=None, m=(1, 1, 1), caps=None, strands=None, outs=None):
+        """encode_host_seg for a list of same-shaped float64 fields, plane l of all of them in one coder launch.  tolrels: one
+        tolerance or one per field; cutoffs: a local cutoff vector per field instead.  brick is None: WRS1; otherwise WRS2
+        (0: BRICK_DEFAULT).  outs: a uint8 array per field for its coded bytes (caps: their sizes, if they are to be allocated
+        here).  Returns ([enc dict per field], timings): every enc is what encode_host_seg returns for that field."""
+        assert all(f.dtype == np.float64 and f.flags["C_CONTIGUOUS"] and f.shape == fields[0].shape for f in fields)
+        shape = fields[0].shape if len(fields) else (1, 1, 1)
+        return self._encode_seg_batch(lib().wr_encode_host_seg_batch, [f.ctypes.data for f in fields], shape, tolrels, wtflag, seg, brick, cutoffs, m, caps, strands, outs)
+
+    def decode_host_seg_batch(self, outs, encs):
+        """decode_host_seg for a list of streams (WRS1 and WRS2 may be mixed) into the same-shaped float64 arrays `outs`."""
+        assert len(outs) == len(encs) and all(o.dtype == np.float64 and o.flags["C_CONTIGUOUS"] and o.shape == outs[0].shape for o in outs)
+        shape = outs[0].shape if len(outs) else (1, 1, 1)
+        return self._decode_seg_batch(lib().wr_decode_host_seg_batch, [o.ctypes.data for o in outs], shape, encs)
+
+    def encode_host_seg_batch_f32(self, fields, tolrels, wtflag=1, seg=0, brick=None, cutoffs=None, m=(1, 1, 1), caps=None, strands=None, outs=None):
+        if not all(isinstance(f, np.ndarray) and f.dtype == np.float32 and f.flags["C_CONTIGUOUS"] and f.shape == fields[0].shape for f in fields):
+            raise TypeError("encode_host_seg_batch_f32: C-contiguous float32 arrays of one shape are required")
+        shape = fields[0].shape if len(fields) else (1, 1, 1)
+        return self._encode_seg_batch(lib().wr_encode_host_seg_batch_f32, [f.ctypes.data for f in fields], shape, tolrels, wtflag, seg, brick, cutoffs, m, caps, strands, outs)
+
+    def decode_host_seg_batch_f32(self, outs, encs):
+        if not (len(outs) == len(encs) and all(isinstance(o, np.ndarray) and o.dtype == np.float32 and o.flags["C_CONTIGUOUS"] and o.shape == outs[0].shape for o in outs)):
+            raise TypeError("decode_host_seg_batch_f32: C-contiguous float32 arrays of one shape are required")
+        shape = outs[0].shape if len(outs) else (1, 1, 1)
+        return self._decode_seg_batch(lib().wr_decode_host_seg_batch_f32, [o.ctypes.data for o in outs], shape, encs)
+
+    def encode_seg_batch(self, bufs, shape, tolrels, wtflag=1, seg=0, brick=None, cutoffs=None, m=(1, 1, 1), caps=None, strands=None, outs=None):
+        """encode_host_seg_batch with the fields resident on the device (the buffers are consumed, as by encode_seg)."""
+        return self._encode_seg_batch(lib().wr_encode_device_seg_batch, [b.ptr for b in bufs], shape, tolrels, wtflag, seg, brick, cutoffs, m, caps, strands, outs)
+
+    def decode_seg_batch(self, bufs, shape, encs):
+        assert len(bufs) == len(encs)
+        return self._decode_seg_batch(lib().wr_decode_device_seg_batch, [b.ptr for b in bufs], shape, encs)
+
+    def seg_encode_planes_batch(self, planes, seg=0):
+        """Stage level: planes of one size (numpy uint8 arrays) through ONE batched coder launch sequence; returns the WRS1
+        blob of each, byte for byte seg_encode_plane's."""
+        ps = [np.ascontiguousarray(p, dtype=np.uint8).ravel() for p in planes]
+        n = ps[0].size if ps else 0
+        assert all(p.size == n for p in ps)
+        bound = seg_bound(n, seg)
+        if not bound:
+            raise WaveRangeError(_BAD_SEG)
+        nj = len(ps)
+        d_sym, d_blob = [self.alloc(max(n, 16)) for _ in ps], [self.alloc(bound) for _ in ps]
+        try:
+            for d, p in zip(d_sym, ps):
+                if n:
+                    d.upload(p)
+            sp = (C.c_void_p * max(nj, 1))(*[d.ptr for d in d_sym])
+            bp = (C.c_void_p * max(nj, 1))(*[d.ptr for d in d_blob])
+            cap = (C.c_size_t * max(nj, 1))(*([bound] * nj))
+            got = (C.c_size_t * max(nj, 1))()
+            _check(lib().wr_dev_seg_encode_batch(self.h, nj, sp, n, seg, bp, cap, got))
+            return [d_blob[j].download(np.uint8, got[j]) for j in range(nj)]
+        finally:
+            for d in d_sym + d_blob:
+                d.free()
+
+    def seg_decode_planes_batch(self, blobs, n):
+        """Stage level: WRS1 blobs of planes of n symbols through ONE batched decoder launch; returns ([symbols], [bad segments])."""
+        bs = [np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in blobs]
+        nj = len(bs)
+        d_blob, d_sym = [self.alloc(max(b.size, 16)) for b in bs], [self.alloc(max(n, 16)) for _ in bs]
+        try:
+            for d, b in zip(d_blob, bs):
+                if b.size:
+                    d.upload(b)
+            bp = (C.c_void_p * max(nj, 1))(*[d.ptr for d in d_blob])
+            sp = (C.c_void_p * max(nj, 1))(*[d.ptr for d in d_sym])
+            ln = (C.c_size_t * max(nj, 1))(*[b.size for b in bs])
+            bad = (C.c_size_t * max(nj, 1))()
+            _check(lib().wr_dev_seg_decode_batch(self.h, nj, bp, ln, sp, n, bad))
+            return [d.download(np.uint8, n) if n else np.zeros(0, np.uint8) for d in d_sym], [int(bad[j]) for j in range(nj)]
+        finally:
+            for d in d_blob + d_sym:
+                d.free()
 
     def decode_begin(self, shape, enc):
         """Host half of a decode (range decoding into the context's staging); no output buffer needed yet."""

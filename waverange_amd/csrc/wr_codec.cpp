@@ -9,6 +9,7 @@
 #include "wr_internal.h"
 #include "wr_lowres.h"
 #include "wr_roi.h"
+#include "wr_segbatch.h"
 #include "wr_segcoder.h"
 
 using namespace wri;
@@ -1954,6 +1955,615 @@ int wr_decode_device_seg_roi(wr_ctx* c, double* d_out, int nx, int ny, int nz, i
     if (!d_out) return fail(WR_ERR_ARG, "null device output pointer");
     if (!roi) return fail(WR_ERR_ARG, "null region pointer");
     return decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, roi, info, data_enc, data_len, tm);
+}
+
+}  // extern "C"
+
+// ---- batched segmented streams (include/waverange_amd.h): plane index l of all fields of a batch in one coder launch --------
+// Transform and quantizer run field by field through the one leased slot, exactly as in encode_seg_impl / decode_seg_impl; the
+// quantized planes wait in batch-owned buffers from the plane pool, and the coder kernels of wr_segbatch.hip take plane l of
+// every field that has one in a single launch sequence.  No new format: every blob is the single-field call's.
+namespace {
+
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// What a batch takes from the plane pool, piece by piece.  The drivers allocate by these and wr_seg_batch_device_bytes sums them.
+size_t batch_plane_bytes(size_t n) { return wr_plane_pitch(n); }
+size_t batch_perm_bytes(size_t n, unsigned brick) { return brick ? wr_plane_pitch(n) : 0; }  // per field: the plane in stream order
+size_t batch_blob_cap(size_t n, unsigned seg, unsigned brick) { return ((brick ? wr_seg_bound_blocked(n, seg) : wr_seg_bound(n, seg)) + 15) & ~(size_t)15; }
+size_t batch_work_bytes(size_t nseg) { return wrk::seg_decode_work_bytes(nseg); }  // per decoded (field, plane): offsets and flags
+// once per call.  encode: the staging of one plane index; decode: a job table per plane index and a failure count per job
+size_t batch_once_bytes(size_t nfields, size_t n, int nlay, unsigned seg, bool decode)
+{
+    if (!nlay) return 0;
+    return decode ? (size_t)nlay * wrk::seg_batch_table_bytes(nfields) + up256(4 * nfields * (size_t)nlay) : wrk::seg_batch_stage_bytes(nfields, n, seg);
+}
+// pinned host memory of a call: the job tables of its launch sequences, then 16 bytes per job for what comes back
+size_t batch_pinned_bytes(size_t njobs_max, int nlay) { return (size_t)nlay * (wrk::seg_batch_table_bytes(njobs_max) + up256(16 * njobs_max)); }
+
+// device and pinned memory of a batch call; goes back when the call ends, behind everything the context's stream still has queued
+struct BatchBufs {
+    wr_ctx* c;
+    std::vector<DevPlanes::Buf> taken;
+    uint8_t* pinned = nullptr;      // the job tables (they stay alive until the stream has drained) and the results
+    uint8_t* pinned_dev = nullptr;  // the same block as the device sees it
+    hipEvent_t ev[2 * WR_NLAYMAX] = {nullptr};
+    explicit BatchBufs(wr_ctx* ctx) : c(ctx) {}
+    BatchBufs(const BatchBufs&) = delete;
+    BatchBufs& operator=(const BatchBufs&) = delete;
+    ~BatchBufs()
+    {
+        (void)hipStreamSynchronize(c->stream);
+        for (const DevPlanes::Buf& b : taken) c->pool->planes.give(b);
+        if (pinned) (void)hipHostFree(pinned);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+    uint8_t* take(size_t bytes)  // nullptr: the error is set (plane_scratch)
+    {
+        const DevPlanes::Buf b = plane_scratch(c, bytes ? bytes : 256);
+        if (b.p) taken.push_back(b);
+        return b.p;
+    }
+    int pin(size_t bytes)
+    {
+        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&pinned), bytes ? bytes : 256, hipHostMallocDefault));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&pinned_dev), pinned, 0));
+        memset(pinned, 0, bytes);
+        return WR_OK;
+    }
+    int events(int l)
+    {
+        for (int k = 2 * l; k < 2 * l + 2; k++)
+            if (!ev[k]) HIPCHK(hipEventCreate(&ev[k]));
+        return WR_OK;
+    }
+    double seconds(int l) const
+    {
+        float ms = 0;
+        if (!ev[2 * l] || hipEventElapsedTime(&ms, ev[2 * l], ev[2 * l + 1]) != hipSuccess) { (void)hipGetLastError(); return 0; }
+        return ms * 1e-3;
+    }
+};
+
+// the error of a step that ran for one field (or job) of a batch: the same code, the message with the index in front
+int fail_at(const char* what, int i, int rc)
+{
+    const std::string msg = last_error();
+    return fail(rc, std::string(what) + " " + std::to_string(i) + ": " + msg);
+}
+
+constexpr unsigned long long kBatchLaneLimit = 1ull << 31;
+
+int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                          const double* const* cutoffvecs, unsigned seg, unsigned brick, wr_enc_info* infos, unsigned char* const* data_encs,
+                          const size_t* caps, wr_timings* tm)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
+    if (brick && !wrblk::brick_ok(brick)) return fail(WR_ERR_ARG, "brick edge must be one of 8, 16, 32, 64");
+    if (!cutoffvecs || !infos || !data_encs || !caps) return fail(WR_ERR_ARG, "null array");
+    if (mx < 1 || my < 1 || mz < 1) return fail(WR_ERR_ARG, "bad local cutoff description");
+    if (int rc = ctx_bind(c)) return rc;
+    bool any_host = false;
+    for (int f = 0; f < nfields; f++) {
+        if (flds[f].none()) return fail(WR_ERR_ARG, "field " + std::to_string(f) + ": null field pointer");
+        if (!cutoffvecs[f]) return fail(WR_ERR_ARG, "field " + std::to_string(f) + ": bad local cutoff description");
+        if (int rc = check_dims(nx, ny, nz, flds[f].dev)) return fail_at("field", f, rc);
+        any_host = any_host || !flds[f].dev;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->keep_residual) return fail(WR_ERR_UNSUPPORTED, "a batch does not write residuals back: wr_ctx_set_keep_residual(ctx, 0) for batched encodes");
+    ActiveCall active(c->pool);
+    if (tm) wrdma::enable_timing();
+    const double t0 = now();
+    const size_t n = (size_t)nx * ny * nz;
+    const size_t nseg = wrseg::seg_count(n, seg);
+    if ((unsigned long long)nseg * (unsigned)nfields >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the planes of one index have 2^31 segments or more");
+    wr_timings local; memset(&local, 0, sizeof local);
+    DevPool* const pool = c->pool;
+    c->pend_valid = false;
+    PlaneHold planes(c);
+    BatchBufs bufs(c);  // (goes first when the call unwinds, and waits for the stream)
+    const size_t blob_cap = batch_blob_cap(n, seg, brick);
+    wrblk::Order od{};
+    if (brick) od = wrblk::order_of(nx, ny, nz, wtflag ? kWavLvl : 0, brick);
+
+    SlotNeed need;
+    transform_need(nx, ny, nz, wtflag ? kWavLvl : 0, &need);
+    if (any_host) need.field_elems = n;
+    SlotLease slot;
+    if (int rc = slot.acquire(c, need)) return rc;
+    const double t_phase = now();
+    std::vector<wrk::PlaneRef> refs((size_t)nfields * WR_NLAYMAX);
+    std::vector<uint8_t*> blob((size_t)nfields * WR_NLAYMAX, nullptr), perm(nfields, nullptr);
+    std::vector<int> job_of((size_t)nfields * WR_NLAYMAX, -1);  // (field, plane) -> its job in the launch sequence of that plane index
+    int maxlay = 0;
+    {
+        StageLock cu(pool->cu_mu);
+        clock_warmup(c, n);
+        // ---- every field in turn through the slot: upload, transform, quantizer; its planes stay in the batch's buffers
+        for (int f = 0; f < nfields; f++) {
+            const FieldRef& fld = flds[f];
+            Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvecs[f];
+            double* d_fld = fld.dev;
+            if (fld.host) {
+                d_fld = slot->field;
+                if (int rc = xfer_field(c, &c->x_field, d_fld, fld.host, n * sizeof(double), kUp)) return fail_at("field", f, rc);
+                local.h2d_ms += (float)c->x_field.ms;
+            }
+            const float* d_f32 = nullptr;  // (as encode_seg_impl: the fused forward transform reads an fp32 field where it lands)
+            if (fld.host_f32) {
+                d_fld = slot->field;
+                float* const stage = (wtflag && use_fused(nx, ny, nz, kWavLvl)) ? reinterpret_cast<float*>(slot->field) : reinterpret_cast<float*>(slot->scratch);
+                if (int rc = xfer_field(c, &c->x_field, stage, fld.host_f32, n * sizeof(float), kUp)) return fail_at("field", f, rc);
+                local.h2d_ms += (float)c->x_field.ms;
+                if (stage == reinterpret_cast<float*>(slot->field)) d_f32 = stage;
+                else wrk::widen_f32(stage, d_fld, n, c->stream);
+            }
+            auto plane_buf = [&](unsigned l) -> const wrk::PlaneRef* {
+                uint8_t* const p = bufs.take(batch_plane_bytes(n));
+                if (!p) return nullptr;
+                refs[(size_t)f * WR_NLAYMAX + l] = wrk::plane_ref(p);
+                return &refs[(size_t)f * WR_NLAYMAX + l];
+            };
+            double* resid = d_fld;
+            wr_timings ft; memset(&ft, 0, sizeof ft);
+            int rc = encode_planes_core(c, slot.get(), d_fld, nx, ny, nz, wtflag, cut, plane_buf, [](unsigned) { return (uint16_t*)nullptr; }, &infos[f], &ft,
+                                        [](unsigned, bool) { return WR_OK; }, [](unsigned, bool) { return WR_OK; }, &resid, d_f32);
+            // the slot is the next field's from here on
+            if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the encoder's kernel stage failed on the device" + launch_describe(c));
+            if (rc) return fail_at("field", f, rc);
+            local.quant_ms += ft.quant_ms; local.transform_ms += ft.transform_ms; local.minmax_ms += ft.minmax_ms;
+            if ((int)infos[f].nlay > maxlay) maxlay = infos[f].nlay;
+        }
+        // ---- one launch sequence per plane index over the fields that have such a plane
+        if (maxlay) {
+            uint8_t* const stage = bufs.take(batch_once_bytes(nfields, n, maxlay, seg, false));
+            if (!stage) return WR_ERR_HIP;
+            for (int f = 0; f < nfields; f++) {
+                for (int l = 0; l < (int)infos[f].nlay; l++)
+                    if (!(blob[(size_t)f * WR_NLAYMAX + l] = bufs.take(blob_cap))) return fail_at("field", f, WR_ERR_HIP);
+                if (brick && infos[f].nlay && !(perm[f] = bufs.take(batch_perm_bytes(n, brick)))) return fail_at("field", f, WR_ERR_HIP);
+            }
+            if (int rc = bufs.pin(batch_pinned_bytes(nfields, maxlay))) return rc;
+            const size_t table = wrk::seg_batch_table_bytes(nfields), per_l = table + up256(16 * (size_t)nfields);
+            std::vector<wrk::SegJob> jobs;
+            for (int l = 0; l < maxlay; l++) {
+                if (int rc = bufs.events(l)) return rc;
+                HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
+                jobs.clear();
+                for (int f = 0; f < nfields; f++) {
+                    if ((int)infos[f].nlay <= l) continue;
+                    const size_t at = (size_t)f * WR_NLAYMAX + l;
+                    wrk::SegJob j; memset(&j, 0, sizeof j);
+                    j.sym = refs[at];
+                    if (brick) {  // the plane in stream order: a pass of milliseconds per field, not batched
+                        if (!wrk::plane_reorder(refs[at], perm[f], od, false, nullptr, 0, c->stream)) return fail(WR_ERR_ARG, "too many bricks");
+                        j.sym = wrk::plane_ref(perm[f]);
+                    }
+                    j.blob = blob[at]; j.cap = blob_cap; j.brick = brick;
+                    job_of[at] = (int)jobs.size();
+                    jobs.push_back(j);
+                }
+                launch_note(c, "seg_encode_batch", l, stage, n, bufs.pinned + l * per_l, jobs[0].sym);
+                wrk::seg_encode_batch(jobs.data(), jobs.size(), n, seg, bufs.pinned + l * per_l, stage,
+                                      reinterpret_cast<unsigned long long*>(bufs.pinned_dev + l * per_l + table), c->stream);
+                HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
+                if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "batched segment coder launch failed" + launch_describe(c));
+            }
+            if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the batched segment coder failed on the device" + launch_describe(c));
+        }
+        pool->last_stage_end.store(now());
+    }
+    // ---- stage "down": every blob, one copy each, to its place in its field's data_enc
+    const size_t table = wrk::seg_batch_table_bytes(nfields), per_l = table + up256(16 * (size_t)nfields);
+    for (int f = 0; f < nfields; f++) {
+        wr_enc_info* const info = &infos[f];
+        size_t total = 0;
+        for (int l = 0; l < (int)info->nlay; l++) {
+            const unsigned long long* const res = reinterpret_cast<const unsigned long long*>(bufs.pinned + l * per_l + table) + 2 * job_of[(size_t)f * WR_NLAYMAX + l];
+            if (res[1] || res[0] > blob_cap)
+                return fail(WR_ERR_HIP, "field " + std::to_string(f) + ": internal: plane " + std::to_string(l) + ": a segment outgrew the segment bound");
+            info->len_enc_vec[l] = res[0];
+            total += res[0];
+        }
+        if (total > caps[f] || (total && !data_encs[f]))
+            return fail(WR_ERR_OVERFLOW, "field " + std::to_string(f) + ": Error: encoded array is too large. Use larger SAFETY_BUFFER_FACTOR");
+        size_t at = 0;
+        for (int l = 0; l < (int)info->nlay; l++) {
+            if (int rc = xfer_field(c, &c->x_field, data_encs[f] + at, blob[(size_t)f * WR_NLAYMAX + l], info->len_enc_vec[l], kDown)) return fail_at("field", f, rc);
+            local.d2h_ms += (float)c->x_field.ms;
+            at += info->len_enc_vec[l];
+        }
+        info->ntot_enc = total;
+    }
+    for (int l = 0; l < maxlay; l++) {
+        local.plane_coder_s[l] = bufs.seconds(l);
+        local.rangecoder += local.plane_coder_s[l];
+    }
+    local.total = now() - t0;
+    local.wait = t_phase - t0;
+    local.gpu = now() - t_phase;
+    if (tm) *tm = local;
+    return WR_OK;
+}
+
+struct BatchField {  // a field of a decode batch as the host has validated it
+    int nlay = 0;    // 0: a constant field, no job
+    size_t off[WR_NLAYMAX + 1] = {0};
+    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0}, brick = 0;
+    uint8_t *plane[WR_NLAYMAX] = {nullptr}, *blob[WR_NLAYMAX] = {nullptr}, *work[WR_NLAYMAX] = {nullptr}, *perm = nullptr;
+    wrblk::Order od{};
+};
+
+int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& flds, int nx, int ny, int nz, const wr_enc_info* infos,
+                          const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm)
+{
+    if (!infos || !data_encs) return fail(WR_ERR_ARG, "null array");
+    if (int rc = ctx_bind(c)) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    ActiveCall active(c->pool);
+    if (tm) wrdma::enable_timing();
+    bool any_host = false;
+    for (int f = 0; f < nfields; f++) {
+        if (flds[f].none()) return fail(WR_ERR_ARG, "field " + std::to_string(f) + ": null field pointer");
+        if (int rc = check_dims(nx, ny, nz, flds[f].dev)) return fail_at("field", f, rc);
+        any_host = any_host || !flds[f].dev;
+    }
+    const double t0 = now();
+    const size_t n = (size_t)nx * ny * nz;
+    wr_timings local; memset(&local, 0, sizeof local);
+    DevPool* const pool = c->pool;
+    // ---- every field's lengths, headers and indices, on the host, before anything is copied or launched for any field
+    std::vector<BatchField> bf(nfields);
+    int maxlay = 0, wlev_any = 0;
+    unsigned long long lanes[WR_NLAYMAX] = {0};
+    for (int f = 0; f < nfields; f++) {
+        const wr_enc_info* const info = &infos[f];
+        BatchField& b = bf[f];
+        if (info->ntot_enc == 0) continue;  // a constant field: filled with midval below
+        const int nlay = info->nlay;
+        const std::string who = "field " + std::to_string(f) + ": ";
+        if (nlay < 1 || nlay > WR_NLAYMAX) return fail(WR_ERR_ARG, who + "nlay out of range");
+        if (info->wlev != 0 && info->wlev != kWavLvl) return fail(WR_ERR_ARG, who + "wlev must be 0 or 4");
+        if (!data_encs[f]) return fail(WR_ERR_ARG, who + "null coded buffer");
+        for (int l = 0; l < nlay; l++) b.off[l + 1] = b.off[l] + info->len_enc_vec[l];
+        if (b.off[nlay] > info->ntot_enc) return fail(WR_ERR_STREAM, who + "len_enc_vec exceeds ntot_enc");
+        if (data_lens && data_lens[f] && info->ntot_enc > data_lens[f]) return fail(WR_ERR_STREAM, who + "ntot_enc exceeds the length of the coded buffer");
+        uint32_t strands = 0;
+        if (int rc = seg_check_planes(data_encs[f], b.off, info, nlay, n, b.seg, b.nseg, &b.brick, &strands)) return fail_at("field", f, rc);
+        if (strands) return fail(WR_ERR_UNSUPPORTED, who + "a WRS3 stream: stranded segments are not decoded in a batch (wr_decode_host_seg reads them)");
+        if (b.brick) b.od = wrblk::order_of(nx, ny, nz, (int)info->wlev, b.brick);
+        b.nlay = nlay;
+        for (int l = 0; l < nlay; l++) lanes[l] += b.nseg[l];
+        if (nlay > maxlay) maxlay = nlay;
+        if (info->wlev) wlev_any = kWavLvl;
+    }
+    for (int l = 0; l < maxlay; l++)
+        if (lanes[l] >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the planes of index " + std::to_string(l) + " have 2^31 segments or more");
+    c->pend_valid = false;
+    PlaneHold planes(c);
+    BatchBufs bufs(c);
+    uint8_t* d_once = nullptr;
+    const size_t table = wrk::seg_batch_table_bytes(nfields);
+    if (maxlay) {
+        std::lock_guard<std::mutex> gather(pool->planes.gather_mu);  // one decode at a time gathers its planes (decode_impl)
+        for (int f = 0; f < nfields; f++) {
+            BatchField& b = bf[f];
+            for (int l = 0; l < b.nlay; l++) {
+                b.plane[l] = bufs.take(batch_plane_bytes(n));
+                b.blob[l] = bufs.take(infos[f].len_enc_vec[l]);
+                b.work[l] = bufs.take(batch_work_bytes(b.nseg[l]));
+                if (!b.plane[l] || !b.blob[l] || !b.work[l]) return fail_at("field", f, WR_ERR_HIP);
+            }
+            if (b.brick && !(b.perm = bufs.take(batch_perm_bytes(n, b.brick)))) return fail_at("field", f, WR_ERR_HIP);
+        }
+        if (!(d_once = bufs.take(batch_once_bytes(nfields, n, maxlay, 0, true)))) return WR_ERR_HIP;
+        if (int rc = bufs.pin(batch_pinned_bytes(nfields, maxlay))) return rc;
+    }
+    // ---- stage "up": one copy per blob, and its segments' offsets
+    for (int f = 0; f < nfields; f++)
+        for (int l = 0; l < bf[f].nlay; l++) {
+            if (int rc = xfer_field(c, &c->x_field, bf[f].blob[l], data_encs[f] + bf[f].off[l], infos[f].len_enc_vec[l], kUp)) return fail_at("field", f, rc);
+            local.h2d_ms += (float)c->x_field.ms;
+            if (int rc = seg_upload_offsets(c, data_encs[f] + bf[f].off[l], bf[f].nseg[l], bf[f].work[l], bf[f].brick, 0)) return fail_at("field", f, rc);
+        }
+    const double t_coded = now();
+    SlotNeed need;
+    transform_need(nx, ny, nz, wlev_any ? -kWavLvl : 0, &need);
+    if (any_host) need.field_elems = n;
+    SlotLease slot;
+    if (int rc = slot.acquire(c, need)) return rc;
+    const double t_phase = now();
+    {
+        StageLock cu(pool->cu_mu);
+        clock_warmup(c, n);
+        if (maxlay) {
+            // the jobs' failure counts lie behind the tables: job (f, l) counts into d_bad[l * nfields + f]
+            unsigned int* const d_bad = reinterpret_cast<unsigned int*>(d_once + (size_t)maxlay * table);
+            const size_t per_l = table + up256(16 * (size_t)nfields);
+            HIPCHK(hipMemsetAsync(d_bad, 0, 4 * (size_t)nfields * maxlay, c->stream));
+            std::vector<wrk::SegJob> jobs;
+            for (int l = 0; l < maxlay; l++) {
+                if (int rc = bufs.events(l)) return rc;
+                jobs.clear();
+                for (int f = 0; f < nfields; f++) {
+                    const BatchField& b = bf[f];
+                    if (b.nlay <= l) continue;
+                    wrk::SegJob j; memset(&j, 0, sizeof j);
+                    j.sym = wrk::plane_ref(b.brick ? b.perm : b.plane[l]);
+                    j.n = n; j.blob = b.blob[l]; j.cap = infos[f].len_enc_vec[l];
+                    j.offs = reinterpret_cast<unsigned long long*>(b.work[l] + 256);
+                    j.flags = reinterpret_cast<uint32_t*>(b.work[l] + 256 + up256(8 * ((size_t)b.nseg[l] + 1)));
+                    j.bad = d_bad + (size_t)l * nfields + f;
+                    j.seg = b.seg[l]; j.nseg = b.nseg[l]; j.brick = b.brick;
+                    jobs.push_back(j);
+                }
+                launch_note(c, "seg_decode_batch", l, d_once + l * table, n, bufs.pinned + l * per_l, jobs[0].sym);
+                HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
+                wrk::seg_decode_batch(jobs.data(), jobs.size(), bufs.pinned + l * per_l, d_once + l * table, c->stream);
+                for (int f = 0; f < nfields; f++)  // WRS2 fields: back to the natural order, per field as in decode_seg_impl
+                    if (bf[f].nlay > l && bf[f].brick &&
+                        !wrk::plane_reorder(wrk::plane_ref(bf[f].plane[l]), bf[f].perm, bf[f].od, true, nullptr, 0, c->stream))
+                        return fail(WR_ERR_ARG, "field " + std::to_string(f) + ": too many bricks");
+                HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
+                if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "batched segment decoder launch failed" + launch_describe(c));
+            }
+            // the dequantizers only run if every segment of every field decoded: the counts come back once
+            std::vector<unsigned int> bad((size_t)nfields * maxlay);
+            HIPCHK(hipMemcpyAsync(bad.data(), d_bad, 4 * bad.size(), hipMemcpyDeviceToHost, c->stream));
+            if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the batched segment decoder failed on the device" + launch_describe(c));
+            for (int f = 0; f < nfields; f++)
+                for (int l = 0; l < bf[f].nlay; l++)
+                    if (const unsigned int k = bad[(size_t)l * nfields + f])
+                        return fail(WR_ERR_STREAM, "field " + std::to_string(f) + ": plane " + std::to_string(l) + ": " + std::to_string(k) +
+                                                       " segment(s) do not decode to their symbols");
+            for (int l = 0; l < maxlay; l++) {
+                local.plane_coder_s[l] = bufs.seconds(l);
+                local.rangecoder += local.plane_coder_s[l];
+            }
+        }
+        // ---- every field in turn through the slot: dequantizer, inverse transform, download
+        for (int f = 0; f < nfields; f++) {
+            const FieldRef& fld = flds[f];
+            const wr_enc_info* const info = &infos[f];
+            const BatchField& b = bf[f];
+            if (!b.nlay) {  // wrappers.cpp:462-469
+                if (fld.host) for (size_t j = 0; j < n; j++) fld.host[j] = info->midval;
+                else if (fld.host_f32) for (size_t j = 0; j < n; j++) fld.host_f32[j] = (float)info->midval;
+                else { wrk::fill(fld.dev, n, info->midval, c->stream); HIPCHK(hipStreamSynchronize(c->stream)); }
+                continue;
+            }
+            wrk::DequantParams p;
+            memset(&p, 0, sizeof p);
+            p.nlay = b.nlay;
+            for (int l = 0; l < b.nlay; l++) { p.deps[l] = info->deps_vec[l]; p.minval[l] = info->minval_vec[l]; p.q[l] = wrk::plane_ref(b.plane[l]); }
+            double* const d_fld = fld.dev ? fld.dev : slot->field;
+            float* d_f32 = nullptr;
+            launch_note(c, "dequant", b.nlay - 1, d_fld, n, nullptr, p.q[b.nlay - 1]);
+            int rc = inverse_from_planes(c, slot.get(), d_fld, nx, ny, nz, (int)info->wlev, p, fld.host_f32 ? &d_f32 : nullptr);
+            if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
+            if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the decoder's kernel stage failed on the device" + launch_describe(c));
+            if (rc) return fail_at("field", f, rc);
+            if (fld.host) {
+                if ((rc = xfer_field(c, &c->x_field, fld.host, d_fld, n * sizeof(double), kDown)) != WR_OK) return fail_at("field", f, rc);
+                local.d2h_ms += (float)c->x_field.ms;
+            } else if (fld.host_f32) {
+                if ((rc = xfer_field(c, &c->x_field, fld.host_f32, d_f32, n * sizeof(float), kDown)) != WR_OK) return fail_at("field", f, rc);
+                local.d2h_ms += (float)c->x_field.ms;
+            }
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, c->ev_a, c->ev_b)); local.quant_ms += ms;
+            HIPCHK(hipEventElapsedTime(&ms, c->ev_b, c->ev_c)); local.transform_ms += ms;
+        }
+        pool->last_stage_end.store(now());
+    }
+    local.total = now() - t0;
+    local.gpu = now() - t_phase;
+    local.wait = t_phase - t_coded;
+    local.transfer = t_coded - t0;
+    if (tm) *tm = local;
+    return WR_OK;
+}
+
+template <class T>
+int batch_fields(int nfields, T* const* ptrs, int kind, std::vector<FieldRef>* out)
+{
+    if (nfields < 1 || nfields > WR_SEG_BATCH_MAX) return fail(WR_ERR_ARG, "nfields must be in 1.." + std::to_string(WR_SEG_BATCH_MAX));
+    if (!ptrs) return fail(WR_ERR_ARG, "null array");
+    out->resize(nfields);
+    for (int f = 0; f < nfields; f++) {
+        FieldRef& r = (*out)[f];
+        if (kind == 0) r.host = (double*)ptrs[f];
+        else if (kind == 1) r.host_f32 = (float*)ptrs[f];
+        else r.dev = (double*)ptrs[f];
+    }
+    return WR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t wr_seg_batch_device_bytes(int nfields, size_t n, int nlay, unsigned seg, unsigned brick, int decode)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (nfields < 1 || nfields > WR_SEG_BATCH_MAX || !n || nlay < 0 || nlay > WR_NLAYMAX || !wrseg::seg_ok(seg) || (brick && !wrblk::brick_ok(brick))) return 0;
+    const size_t N = (size_t)nfields;
+    size_t per_plane = batch_plane_bytes(n) + up256(batch_blob_cap(n, seg, brick));
+    if (decode) per_plane += up256(batch_work_bytes(wrseg::seg_count(n, seg)));
+    return N * (size_t)nlay * per_plane + N * batch_perm_bytes(n, brick) + up256(batch_once_bytes(N, n, nlay, seg, decode != 0));
+}
+
+int wr_seg_batch_locate(const uint32_t* first, uint32_t njobs, uint32_t g, uint32_t* job, uint32_t* k)
+{
+    if (!first || !job || !k) return fail(WR_ERR_ARG, "null pointer");
+    if (njobs < 1 || njobs > wrsb::kBatchMax) return fail(WR_ERR_ARG, "njobs must be in 1.." + std::to_string(wrsb::kBatchMax));
+    if (!wrsb::prefix_ok(first, njobs)) return fail(WR_ERR_ARG, "not an exclusive prefix: it must start at 0 and never decrease");
+    if (g >= first[njobs]) return fail(WR_ERR_ARG, "lane past the end of the launch");
+    wrsb::locate(first, njobs, g, job, k);
+    return WR_OK;
+}
+
+int wr_dev_seg_encode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_sym, size_t n, unsigned seg, unsigned char* const* d_blob, const size_t* cap,
+                            size_t* blob_len)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
+    if (njobs < 1 || njobs > WR_SEG_BATCH_MAX) return fail(WR_ERR_ARG, "njobs must be in 1.." + std::to_string(WR_SEG_BATCH_MAX));
+    if (int rc = ctx_bind(c)) return rc;
+    if (!d_sym || !d_blob || !cap || !blob_len) return fail(WR_ERR_ARG, "null array");
+    const size_t nseg = wrseg::seg_count(n, seg);
+    if ((unsigned long long)nseg * (unsigned)njobs >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the batch has 2^31 segments or more");
+    for (int j = 0; j < njobs; j++) {
+        if (!d_blob[j] || (n && !d_sym[j])) return fail(WR_ERR_ARG, "job " + std::to_string(j) + ": null pointer");
+        if (((uintptr_t)d_sym[j] | (uintptr_t)d_blob[j]) & 15) return fail(WR_ERR_ARG, "job " + std::to_string(j) + ": plane and blob buffers must be 16-byte aligned");
+        if (cap[j] < wrseg::kHeaderBytes + 4 * nseg) return fail(WR_ERR_OVERFLOW, "job " + std::to_string(j) + ": the blob buffer does not hold the plane's index");
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    BatchBufs bufs(c);
+    uint8_t* const stage = bufs.take(wrk::seg_batch_stage_bytes(njobs, n, seg));
+    if (!stage) return WR_ERR_HIP;
+    if (int rc = bufs.pin(batch_pinned_bytes(njobs, 1))) return rc;
+    const size_t table = wrk::seg_batch_table_bytes(njobs);
+    std::vector<wrk::SegJob> jobs(njobs);
+    for (int j = 0; j < njobs; j++) {
+        memset(&jobs[j], 0, sizeof jobs[j]);
+        jobs[j].sym = wrk::plane_ref(d_sym[j]);
+        jobs[j].blob = d_blob[j]; jobs[j].cap = cap[j];
+    }
+    StageLock cu(c->pool->cu_mu);
+    wrk::seg_encode_batch(jobs.data(), jobs.size(), n, seg, bufs.pinned, stage, reinterpret_cast<unsigned long long*>(bufs.pinned_dev + table), c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const unsigned long long* const res = reinterpret_cast<const unsigned long long*>(bufs.pinned + table);
+    int rc = WR_OK;
+    for (int j = 0; j < njobs; j++) {
+        if (res[2 * j + 1]) { if (!rc) rc = fail(WR_ERR_HIP, "job " + std::to_string(j) + ": internal: a segment outgrew the segment bound"); continue; }
+        if (res[2 * j] > cap[j]) { if (!rc) rc = fail(WR_ERR_OVERFLOW, "job " + std::to_string(j) + ": the blob buffer is too small for the plane"); continue; }
+        blob_len[j] = (size_t)res[2 * j];
+    }
+    return rc;
+}
+
+int wr_dev_seg_decode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_blob, const size_t* blob_len, unsigned char* const* d_sym, size_t n,
+                            size_t* bad_segments)
+{
+    if (njobs < 1 || njobs > WR_SEG_BATCH_MAX) return fail(WR_ERR_ARG, "njobs must be in 1.." + std::to_string(WR_SEG_BATCH_MAX));
+    if (int rc = ctx_bind(c)) return rc;
+    if (!d_blob || !blob_len || !d_sym) return fail(WR_ERR_ARG, "null array");
+    for (int j = 0; j < njobs; j++) {
+        if (!d_blob[j] || (n && !d_sym[j])) return fail(WR_ERR_ARG, "job " + std::to_string(j) + ": null pointer");
+        if (((uintptr_t)d_sym[j] | (uintptr_t)d_blob[j]) & 15) return fail(WR_ERR_ARG, "job " + std::to_string(j) + ": plane and blob buffers must be 16-byte aligned");
+        if (bad_segments) bad_segments[j] = 0;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    // every header, then every index, come to the host and are validated before anything is launched for any job
+    std::vector<std::vector<uint8_t>> front(njobs);
+    std::vector<uint32_t> seg(njobs, 0), nseg(njobs, 0);
+    unsigned long long lanes = 0;
+    for (int j = 0; j < njobs; j++) {
+        const std::string who = "job " + std::to_string(j) + ": ";
+        front[j].resize(wrseg::kHeaderBytes);
+        if (blob_len[j] < front[j].size()) return fail(WR_ERR_STREAM, who + "segmented plane: shorter than its header");
+        HIPCHK(hipMemcpy(front[j].data(), d_blob[j], front[j].size(), hipMemcpyDeviceToHost));
+        if (memcmp(front[j].data(), wrseg::kMagicStrands, 4) == 0)
+            return fail(WR_ERR_UNSUPPORTED, who + "a WRS3 blob: stranded segments are not decoded in a batch (wr_dev_seg_decode reads them)");
+        const char* why = wrseg::check_index(front[j].data(), front[j].size(), blob_len[j], n, &seg[j], &nseg[j]);
+        if (why == wrseg::kIndexNotAvailable) {  // (the index fits into the blob: check_index has looked)
+            front[j].resize(front[j].size() + 4 * (size_t)wrseg::get_u32(front[j].data() + 8));
+            HIPCHK(hipMemcpy(front[j].data(), d_blob[j], front[j].size(), hipMemcpyDeviceToHost));
+            why = wrseg::check_index(front[j].data(), front[j].size(), blob_len[j], n, &seg[j], &nseg[j]);
+        }
+        if (why) return fail(WR_ERR_STREAM, who + why);
+        lanes += nseg[j];
+    }
+    if (lanes >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the batch has 2^31 segments or more");
+    if (!lanes) return WR_OK;
+    BatchBufs bufs(c);
+    const size_t table = wrk::seg_batch_table_bytes(njobs);
+    uint8_t* const d_once = bufs.take(batch_once_bytes(njobs, n, 1, 0, true));
+    if (!d_once) return WR_ERR_HIP;
+    if (int rc = bufs.pin(batch_pinned_bytes(njobs, 1))) return rc;
+    unsigned int* const d_bad = reinterpret_cast<unsigned int*>(d_once + table);
+    std::vector<wrk::SegJob> jobs(njobs);
+    for (int j = 0; j < njobs; j++) {
+        wrk::SegJob& job = jobs[j];
+        memset(&job, 0, sizeof job);
+        job.sym = wrk::plane_ref(d_sym[j]);
+        job.n = n; job.blob = const_cast<unsigned char*>(d_blob[j]); job.cap = blob_len[j];
+        job.bad = d_bad + j; job.seg = seg[j]; job.nseg = nseg[j];
+        if (!nseg[j]) continue;
+        uint8_t* const work = bufs.take(batch_work_bytes(nseg[j]));
+        if (!work) return WR_ERR_HIP;
+        if (int rc = seg_upload_offsets(c, front[j].data(), nseg[j], work, 0, 0)) return rc;
+        job.offs = reinterpret_cast<unsigned long long*>(work + 256);
+        job.flags = reinterpret_cast<uint32_t*>(work + 256 + up256(8 * ((size_t)nseg[j] + 1)));
+    }
+    StageLock cu(c->pool->cu_mu);
+    HIPCHK(hipMemsetAsync(d_bad, 0, 4 * (size_t)njobs, c->stream));
+    wrk::seg_decode_batch(jobs.data(), jobs.size(), bufs.pinned, d_once, c->stream);
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned int> bad(njobs, 0);
+    HIPCHK(hipMemcpyAsync(bad.data(), d_bad, 4 * (size_t)njobs, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    int rc = WR_OK;
+    for (int j = 0; j < njobs; j++) {
+        if (bad_segments) bad_segments[j] = bad[j];
+        if (bad[j] && !rc) rc = fail(WR_ERR_STREAM, "job " + std::to_string(j) + ": segmented plane: " + std::to_string(bad[j]) + " segment(s) do not decode to their symbols");
+    }
+    return rc;
+}
+
+int wr_encode_host_seg_batch(wr_ctx* c, int nfields, const double* const* h_flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                             const double* const* cutoffvecs, unsigned seg, unsigned brick, wr_enc_info* infos, unsigned char* const* data_encs,
+                             const size_t* caps, wr_timings* tm)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, h_flds, 0, &flds)) return rc;
+    return encode_seg_batch_impl(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, infos, data_encs, caps, tm);
+}
+
+int wr_decode_host_seg_batch(wr_ctx* c, int nfields, double* const* h_flds, int nx, int ny, int nz, const wr_enc_info* infos,
+                             const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, h_flds, 0, &flds)) return rc;
+    return decode_seg_batch_impl(c, nfields, flds, nx, ny, nz, infos, data_encs, data_lens, tm);
+}
+
+int wr_encode_host_seg_batch_f32(wr_ctx* c, int nfields, const float* const* h_flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                 const double* const* cutoffvecs, unsigned seg, unsigned brick, wr_enc_info* infos, unsigned char* const* data_encs,
+                                 const size_t* caps, wr_timings* tm)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, h_flds, 1, &flds)) return rc;
+    return encode_seg_batch_impl(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, infos, data_encs, caps, tm);
+}
+
+int wr_decode_host_seg_batch_f32(wr_ctx* c, int nfields, float* const* h_flds, int nx, int ny, int nz, const wr_enc_info* infos,
+                                 const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, h_flds, 1, &flds)) return rc;
+    return decode_seg_batch_impl(c, nfields, flds, nx, ny, nz, infos, data_encs, data_lens, tm);
+}
+
+int wr_encode_device_seg_batch(wr_ctx* c, int nfields, double* const* d_flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                               const double* const* cutoffvecs, unsigned seg, unsigned brick, wr_enc_info* infos, unsigned char* const* data_encs,
+                               const size_t* caps, wr_timings* tm)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, d_flds, 2, &flds)) return rc;
+    return encode_seg_batch_impl(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, infos, data_encs, caps, tm);
+}
+
+int wr_decode_device_seg_batch(wr_ctx* c, int nfields, double* const* d_flds, int nx, int ny, int nz, const wr_enc_info* infos,
+                               const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, d_flds, 2, &flds)) return rc;
+    return decode_seg_batch_impl(c, nfields, flds, nx, ny, nz, infos, data_encs, data_lens, tm);
 }
 
 }  // extern "C"

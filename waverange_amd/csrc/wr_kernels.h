@@ -156,6 +156,37 @@ size_t strand_stage_bytes(size_t n, unsigned seg, unsigned strands);
 void strand_encode(const PlaneRef& sym, size_t n, unsigned seg, unsigned strands, unsigned brick, uint8_t* stage, uint8_t* blob, size_t cap,
                    unsigned long long* result_host, hipStream_t st);
 
+// ---- the segment coder over the planes of a batch of fields (wr_segbatch.hip): one launch sequence codes `njobs` planes, one
+// lane per segment of any of them (the locator: wr_segbatch.h).  A job is one (field, plane); every blob is byte for byte what
+// seg_encode / the single-plane decoder make of that plane alone.
+struct SegJob {
+    PlaneRef sym;               // the plane's symbols (the blocked order for a WRS2 blob), 16-byte aligned
+    unsigned long long n;       // symbols of the plane
+    uint8_t* blob;              // encode: where the blob lands (16-byte aligned); decode: the blob
+    unsigned long long cap;     // encode: the room at blob; decode: the blob's length
+    unsigned long long* offs;   // nseg + 1 byte offsets of the segment streams behind the index (encode: set by seg_encode_batch)
+    uint32_t* flags;            // decode: a flag per segment (0: decoded)
+    unsigned int* bad;          // decode: the job's count of segments that did not decode (zeroed by the caller)
+    uint32_t seg, nseg, brick;  // brick != 0: a WRS2 blob with that brick edge in its header
+    uint32_t pad;
+};
+// The table of a launch sequence as it lies in device memory: the jobs, then first[njobs + 1], each 256-byte aligned.
+size_t seg_batch_table_bytes(size_t njobs);
+// host_table := the table of jobs[0, njobs); returns the segments of the launch (the caller keeps them below 2^31)
+size_t seg_batch_table_fill(uint8_t* host_table, const SegJob* jobs, size_t njobs);
+// Encode: all jobs share n and seg.  `stage`: seg_batch_stage_bytes(njobs, n, seg) of device memory, 256-byte aligned: the table,
+// {length, failed segments} per job (u64 pairs, at seg_batch_results(stage, njobs)), every job's offs and lens, and one region
+// of the segment bound per segment of the launch.  jobs[j].offs is set here; host_table (seg_batch_table_bytes(njobs) bytes of
+// host memory) is filled and copied up, and has to stay alive until the stream has drained.  result_host: njobs u64 pairs of
+// pinned memory as the device sees it, written like the pairs in `stage`.
+size_t seg_batch_stage_bytes(size_t njobs, size_t n, unsigned seg);
+unsigned long long* seg_batch_results(uint8_t* stage, size_t njobs);
+void seg_encode_batch(SegJob* jobs, size_t njobs, size_t n, unsigned seg, uint8_t* host_table, uint8_t* stage, unsigned long long* result_host,
+                      hipStream_t st);
+// Decode: jobs may differ in n, seg and brick.  `table`: seg_batch_table_bytes(njobs) of device memory, 256-byte aligned;
+// host_table as above.  Every job's offs come from an index the caller has VALIDATED on the host.
+void seg_decode_batch(const SegJob* jobs, size_t njobs, uint8_t* host_table, uint8_t* table, hipStream_t st);
+
 // ---- the blocked symbol order of WRS2 (wr_blocked.hip; the order itself and its host geometry: wr_blocked.h).  `nat` is the
 // plane in natural order, `blk` the same n bytes in the blocked order, one array.  Forward: blk := nat permuted; inverse:
 // nat := blk permuted back.  ids == nullptr: the whole plane.  Otherwise ids[0, nlist) are ascending brick ids in device
