@@ -196,6 +196,8 @@ int wr_set_device_slots(int device, int nslots);
 #define WR_STAT_LOWRES_BYTES_UP 12 /* coded payload bytes those calls have copied to the device (the offsets tables are not counted) */
 #define WR_STAT_ROI_SEGMENTS 13 /* segments the region decodes (wr_decode_*_seg_roi) have launched, summed over planes */
 #define WR_STAT_ROI_BYTES_UP 14 /* coded payload bytes those calls have copied to the device (the offsets tables are not counted) */
+#define WR_STAT_ROI_CODER_LAUNCHES 15 /* coder kernel launches of the region decodes: one per used plane of a single-region call and
+                                       * of a multi-region call on a WRS3 stream, one per multi-region call on a WRS1 / WRS2 stream */
 unsigned long wr_stat(int what);
 /* Hands the idle buffers of the device's plane pool back to the device (the pool keeps the plane memory of finished calls for
  * the next ones: after a burst of concurrent calls that can be most of the HBM).  Buffers in use are not touched. */
@@ -626,6 +628,58 @@ int wr_encode_device_seg_batch(wr_ctx *ctx, int nfields, double *const *d_flds, 
 int wr_decode_device_seg_batch(wr_ctx *ctx, int nfields, double *const *d_flds, int nx, int ny, int nz,
                                const wr_enc_info *infos, const unsigned char *const *data_encs,
                                const size_t *data_lens, wr_timings *tm);
+
+/* ---- Region decode, many regions per call: Q regions of one stream, and all used planes in ONE coder launch.  No new format.
+ * A single-region call launches the coder once per used plane, back to back, and each launch lasts one segment's chain however
+ * few lanes it has; Q probes of one snapshot pay that Q times.  Here the segments that any of the regions needs -- per plane the
+ * ascending UNION of the regions' lists for that plane's `seg` -- are uploaded and decoded once, on a WRS1 / WRS2 stream by one
+ * launch over all used planes (a job per plane, a lane per listed segment: csrc/wr_segbatch.hip), on a WRS3 stream by one
+ * launch per plane over the union.  Then the regions are finished one after another as the single-region call finishes its
+ * one: window dequantiser, inverse on the window, crop and scale.
+ *   rois[0, nroi), 1 <= nroi <= WR_ROI_MULTI_MAX, are boxes in the coordinates of D(r, p) as above; one level and one
+ *   max_planes hold for the call; regions may overlap or repeat.  The output is ONE contiguous buffer: region i lies at element
+ *   offset offs[i] of wr_roi_multi_elems (the exclusive prefix of the regions' element counts) and is, bit for bit, what
+ *   wr_decode_host_seg_roi (the _f32 form: wr_decode_host_seg_roi_f32) returns for rois[i] alone.
+ * Order of validation: the plan of every region first -- the first bad region gives WR_ERR_ARG and wr_last_error() starts with
+ * "region <index>: " --, then every plane's header and index, used or not, as by wr_decode_host_seg; nothing is copied or
+ * launched before both have passed.  A constant field gives midval in every region.  The per-plane counts of segments that did
+ * not decode come back once; any non-zero count is WR_ERR_STREAM naming the plane, before a dequantiser runs.
+ * A blocked stream takes one stream-order scratch plane per used plane from the plane pool (the single-region call reuses one);
+ * a host caller's crops are gathered in one pool buffer of the total size and come down in one copy.
+ * WR_STAT_ROI_SEGMENTS moves by the union's size summed over the used planes, WR_STAT_ROI_BYTES_UP by the union's stream bytes,
+ * WR_STAT_ROI_CODER_LAUNCHES by 1 (WRS1 / WRS2) or by the used planes (WRS3).  wr_timings: `rangecoder` is the coder launch(es);
+ * on the one-launch path plane_coder_s[0] is that time and the other entries are 0; quant_ms and transform_ms are summed over
+ * the regions (the call then waits for every region's kernels before it queues the next one's).
+ * The single-region entry points are unchanged; a caller who wants one launch for one region passes nroi = 1. */
+#define WR_ROI_MULTI_MAX 1024
+/* host only.  offs[0 .. nroi] (may be NULL): the exclusive prefix of the regions' element counts; returns the total, or 0 for a
+ * refused argument (nroi outside 1..WR_ROI_MULTI_MAX, null rois, a level outside [0, 4], an empty or out-of-range box). */
+size_t wr_roi_multi_elems(int nx, int ny, int nz, int level, const wr_box *rois, int nroi, size_t *offs);
+/* host only.  The ascending union of what wr_seg_roi_segments (brick == 0) or wr_seg_roi_segments_blocked (brick != 0) lists
+ * per region; their conventions (the count of the whole union is returned, at most cap ids are written, 0: refused). */
+size_t wr_seg_roi_segments_multi(int nx, int ny, int nz, int level, int wlev, const wr_box *rois, int nroi,
+                                 unsigned brick, unsigned seg, uint32_t *ids, size_t cap);
+/* stage level, as wr_dev_decode_planes_roi (the window stage only): d_out receives wr_roi_multi_elems elements */
+int wr_dev_decode_planes_roi_multi(wr_ctx *ctx, double *d_out, int nx, int ny, int nz, int level, int max_planes,
+                                   const wr_box *rois, int nroi, const unsigned char *d_planes, const wr_enc_info *info);
+/* stage level, for tests of the kernel: njobs (1..WR_SEG_BATCH_MAX) WRS1 / WRS2 blobs in device memory, job j a plane of n[j]
+ * symbols of which the segments ids[j][0, nlist[j]) -- HOST arrays, ascending, below the blob's segment count; nlist[j] may be
+ * 0 -- are decoded by one launch into d_sym[j] (stream order for a WRS2 blob).  Device pointers are 16-byte aligned.  Every
+ * header, index and list is validated on the host before the launch (WR_ERR_STREAM / WR_ERR_ARG, "job <index>: "); only listed
+ * segments are read and written.  bad_segments[j] (may be NULL): the job's segments that did not decode (WR_ERR_STREAM). */
+int wr_dev_seg_decode_lists(wr_ctx *ctx, int njobs, const unsigned char *const *d_blob, const size_t *blob_len,
+                            unsigned char *const *d_sym, const size_t *n, const uint32_t *const *ids, const size_t *nlist,
+                            size_t *bad_segments);
+/* whole path: wr_decode_host_seg_roi / _f32 / wr_decode_device_seg_roi with rois, nroi in place of roi */
+int wr_decode_host_seg_roi_multi(wr_ctx *ctx, double *h_out, int nx, int ny, int nz, int level, int max_planes,
+                                 const wr_box *rois, int nroi, const wr_enc_info *info, const unsigned char *data_enc,
+                                 size_t data_len, wr_timings *tm);
+int wr_decode_host_seg_roi_multi_f32(wr_ctx *ctx, float *h_out, int nx, int ny, int nz, int level, int max_planes,
+                                     const wr_box *rois, int nroi, const wr_enc_info *info, const unsigned char *data_enc,
+                                     size_t data_len, wr_timings *tm);
+int wr_decode_device_seg_roi_multi(wr_ctx *ctx, double *d_out, int nx, int ny, int nz, int level, int max_planes,
+                                   const wr_box *rois, int nroi, const wr_enc_info *info, const unsigned char *data_enc,
+                                   size_t data_len, wr_timings *tm);
 
 /* encoding_wrap / decoding_wrap for fp32 fields: the same arguments but the field, an implicit context per call and
  * the reference's "void + fatal" errors.  fld_1d of an encode is never overwritten (no residual write-back). */

@@ -229,6 +229,16 @@ def lib():
                                          C.POINTER(Timings)]
     L.wr_decode_host_seg_roi_f32.argtypes = L.wr_decode_host_seg_roi.argtypes
     L.wr_decode_device_seg_roi.argtypes = L.wr_decode_host_seg_roi.argtypes
+    L.wr_roi_multi_elems.restype = C.c_size_t
+    L.wr_roi_multi_elems.argtypes = [C.c_int] * 4 + [_vp, C.c_int, _vp]
+    L.wr_seg_roi_segments_multi.restype = C.c_size_t
+    L.wr_seg_roi_segments_multi.argtypes = [C.c_int] * 5 + [_vp, C.c_int, C.c_uint, C.c_uint, _vp, C.c_size_t]
+    L.wr_dev_decode_planes_roi_multi.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.POINTER(EncInfo)]
+    L.wr_dev_seg_decode_lists.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.wr_decode_host_seg_roi_multi.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.POINTER(EncInfo), _vp, C.c_size_t,
+                                               C.POINTER(Timings)]
+    L.wr_decode_host_seg_roi_multi_f32.argtypes = L.wr_decode_host_seg_roi_multi.argtypes
+    L.wr_decode_device_seg_roi_multi.argtypes = L.wr_decode_host_seg_roi_multi.argtypes
     L.wr_fused_plan.argtypes = [C.c_int] * 4 + [C.POINTER(FusedPlan)]
     L.wr_bench_transform.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]
     # drop-in symbols (reference src/core/wrappers.h:53,70,75)
@@ -275,6 +285,7 @@ STAT_POOL_QUEUE_MS, STAT_PLANE_WAIT_MS, STAT_HANDOVER_ERRORS, STAT_CLOCK_WARMUP_
 STAT_WINDOW_WAIT_MS = 10
 STAT_LOWRES_SEGMENTS, STAT_LOWRES_BYTES_UP = 11, 12
 STAT_ROI_SEGMENTS, STAT_ROI_BYTES_UP = 13, 14
+STAT_ROI_CODER_LAUNCHES = 15
 
 
 def stat(what):
@@ -643,6 +654,43 @@ def seg_roi_segments(shape, level, roi, seg=0, wlev=4):
         raise WaveRangeError(lib().wr_last_error().decode())
     ids = np.empty(count, dtype=np.uint32)
     got = lib().wr_seg_roi_segments(nx, ny, nz, level, wlev, C.byref(r), seg, ids.ctypes.data, ids.size)
+    assert got == count
+    return ids
+
+
+ROI_MULTI_MAX = 1024  # WR_ROI_MULTI_MAX
+
+
+def _boxes(rois):
+    """a wr_box array of regions given as ((z0, z1), (y0, y1), (x0, x1)) each (at least one entry, so that it has an address)"""
+    arr = (Box * max(len(rois), 1))()
+    for i, r in enumerate(rois):
+        arr[i] = _box(r)
+    return arr
+
+
+def roi_multi_offsets(shape, level, rois):
+    """offs (int64, len(rois) + 1): region i of a multi-region decode lies at elements [offs[i], offs[i + 1]) of the output
+    (wr_roi_multi_elems); shape is the coded field's (nz, ny, nx)."""
+    nz, ny, nx = shape
+    offs = (C.c_size_t * (len(rois) + 1))()
+    total = lib().wr_roi_multi_elems(nx, ny, nz, level, _boxes(rois), len(rois), offs)
+    if not total:
+        raise WaveRangeError(lib().wr_last_error().decode())
+    return np.array(list(offs), dtype=np.int64)
+
+
+def seg_roi_segments_multi(shape, level, rois, seg=0, wlev=4, brick=None):
+    """Ascending ids (uint32) of the segments of a plane cut at `seg` that any of the regions needs: the union of
+    seg_roi_segments (brick is None) or seg_roi_segments_blocked (0: BRICK_DEFAULT) over `rois`."""
+    nz, ny, nx = shape
+    b = 0 if brick is None else (brick or BRICK_DEFAULT)
+    arr = _boxes(rois)
+    count = lib().wr_seg_roi_segments_multi(nx, ny, nz, level, wlev, arr, len(rois), b, seg, None, 0)
+    if not count:
+        raise WaveRangeError(lib().wr_last_error().decode())
+    ids = np.empty(count, dtype=np.uint32)
+    got = lib().wr_seg_roi_segments_multi(nx, ny, nz, level, wlev, arr, len(rois), b, seg, ids.ctypes.data, ids.size)
     assert got == count
     return ids
 
@@ -1117,6 +1165,74 @@ class Context:
     def decode_seg_roi(self, buf, shape, level, roi, enc, max_planes=0):
         """decode_host_seg_roi into device memory: `buf` holds the region's elements as float64."""
         return self._decode_seg_roi(lib().wr_decode_device_seg_roi, buf.ptr, shape, level, roi, enc, max_planes)
+
+    # ---- region decode, many regions per call: the union of the regions' segments decoded once, all used planes in one launch
+    def decode_planes_rois(self, buf, shape, level, rois, planes, info, max_planes=0):
+        """Stage level: `planes` as encode_planes left them; `buf` receives the regions as float64, region i at element
+        roi_multi_offsets(shape, level, rois)[i]."""
+        nz, ny, nx = shape
+        _check(lib().wr_dev_decode_planes_roi_multi(self.h, buf.ptr, nx, ny, nz, level, max_planes, _boxes(rois), len(rois), planes.ptr, C.byref(info)))
+
+    def _decode_seg_rois(self, fn, ptr, shape, level, rois, enc, max_planes):
+        nz, ny, nx = shape
+        info = EncInfo.from_dict(enc)
+        tm = Timings()
+        data = np.ascontiguousarray(enc["data"], dtype=np.uint8)
+        if data.size == 0:
+            data = np.zeros(1, dtype=np.uint8)
+        _check(fn(self.h, ptr, nx, ny, nz, level, max_planes, _boxes(rois), len(rois), C.byref(info), data.ctypes.data, data.size, C.byref(tm)))
+        return tm.as_dict()
+
+    def decode_host_seg_rois(self, shape, level, rois, enc, max_planes=0, dtype=np.float64, timings=None):
+        """The regions `rois` (each ((z0, z1), (y0, y1), (x0, x1)) in the box of `level`) of a segmented stream in one call:
+        a list of arrays, views of one buffer, each shaped roi_shape(roi) and bit for bit what decode_host_seg_roi (float32:
+        decode_host_seg_roi_f32) gives for that region alone.  shape: the coded field's (nz, ny, nx).  timings: a dict that
+        receives the call's wr_timings."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise TypeError("decode_host_seg_rois: dtype must be float64 or float32")
+        try:
+            offs = roi_multi_offsets(shape, level, rois)
+        except WaveRangeError as e:  # (there is no buffer to size: what the call itself would refuse with, WR_ERR_ARG)
+            raise WaveRangeError("libwaverange_amd error -1: %s" % e) from None
+        out = np.empty(int(offs[-1]), dtype=dt)
+        fn = lib().wr_decode_host_seg_roi_multi if dt == np.dtype(np.float64) else lib().wr_decode_host_seg_roi_multi_f32
+        tm = self._decode_seg_rois(fn, out.ctypes.data, shape, level, rois, enc, max_planes)
+        if timings is not None:
+            timings.update(tm)
+        return [out[offs[i]:offs[i + 1]].reshape(roi_shape(r)) for i, r in enumerate(rois)]
+
+    def decode_seg_rois(self, buf, shape, level, rois, enc, max_planes=0):
+        """decode_host_seg_rois into device memory: `buf` holds roi_multi_offsets(...)[-1] float64 elements, region i at
+        element offset [i].  Returns the timings."""
+        return self._decode_seg_rois(lib().wr_decode_device_seg_roi_multi, buf.ptr, shape, level, rois, enc, max_planes)
+
+    def seg_decode_lists(self, blobs, ns, lists):
+        """Stage level: WRS1 / WRS2 blobs of planes of ns[j] symbols; the segments lists[j] (ascending ids) of every one are
+        decoded by ONE launch into planes prefilled with 0xEE.  Returns ([symbols], [bad segments])."""
+        bs = [np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in blobs]
+        ls = [np.ascontiguousarray(l, dtype=np.uint32).ravel() for l in lists]
+        nj = len(bs)
+        assert len(ns) == nj and len(ls) == nj
+        d_blob, d_sym = [self.alloc(max(b.size, 16)) for b in bs], [self.alloc(max(int(n), 16)) for n in ns]
+        try:
+            for d, b in zip(d_blob, bs):
+                if b.size:
+                    d.upload(b)
+            for d, n in zip(d_sym, ns):
+                d.upload(np.full(max(int(n), 16), 0xEE, dtype=np.uint8))
+            bp = (C.c_void_p * max(nj, 1))(*[d.ptr for d in d_blob])
+            sp = (C.c_void_p * max(nj, 1))(*[d.ptr for d in d_sym])
+            ln = (C.c_size_t * max(nj, 1))(*[b.size for b in bs])
+            nn = (C.c_size_t * max(nj, 1))(*[int(n) for n in ns])
+            ip = (C.c_void_p * max(nj, 1))(*[l.ctypes.data if l.size else None for l in ls])
+            il = (C.c_size_t * max(nj, 1))(*[l.size for l in ls])
+            bad = (C.c_size_t * max(nj, 1))()
+            _check(lib().wr_dev_seg_decode_lists(self.h, nj, bp, ln, sp, nn, ip, il, bad))
+            return [d.download(np.uint8, int(n)) if n else np.zeros(0, np.uint8) for d, n in zip(d_sym, ns)], [int(bad[j]) for j in range(nj)]
+        finally:
+            for d in d_blob + d_sym:
+                d.free()
 
     def seg_encode_plane(self, plane, seg=0, strands=None):
         """Stage level: one plane of symbols (a numpy uint8 array) through the coder kernels; returns the blob (WRS1, or with

@@ -187,16 +187,7 @@ inline void region_touch(const Order& od, const wrroi::Geometry& g, uint32_t seg
     }
 }
 
-inline size_t list_marks(const std::vector<bool>& need, uint32_t* ids, size_t cap)
-{
-    size_t count = 0;
-    for (size_t k = 0; k < need.size(); k++)
-        if (need[k]) {
-            if (ids && count < cap) ids[count] = (uint32_t)k;
-            count++;
-        }
-    return count;
-}
+using wrroi::list_marks;
 
 // The ascending ids of the segments of length `seg` that a region needs of a blocked plane; conventions of wrlow::segments_of.
 inline size_t region_segments(const Order& od, const wrroi::Geometry& g, uint32_t seg, uint32_t* ids, size_t cap)
@@ -211,6 +202,22 @@ inline void region_bricks(const Order& od, const wrroi::Geometry& g, std::vector
 {
     std::vector<bool> need(od.nbricks, false);
     region_touch(od, g, 0, nullptr, &need);
+    ids->resize(list_marks(need, nullptr, 0));
+    list_marks(need, ids->data(), ids->size());
+}
+
+// the ascending unions of region_segments / region_bricks over the regions g[0, ng)
+inline size_t region_segments_multi(const Order& od, const wrroi::Geometry* g, size_t ng, uint32_t seg, uint32_t* ids, size_t cap)
+{
+    std::vector<bool> need((od.n() + seg - 1) / seg, false);
+    for (size_t i = 0; i < ng; i++) region_touch(od, g[i], seg, &need, nullptr);
+    return list_marks(need, ids, cap);
+}
+
+inline void region_bricks_multi(const Order& od, const wrroi::Geometry* g, size_t ng, std::vector<uint32_t>* ids)
+{
+    std::vector<bool> need(od.nbricks, false);
+    for (size_t i = 0; i < ng; i++) region_touch(od, g[i], 0, nullptr, &need);
     ids->resize(list_marks(need, nullptr, 0));
     list_marks(need, ids->data(), ids->size());
 }

@@ -1648,6 +1648,7 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
                 return fail(WR_ERR_ARG, "too many bricks");
             HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
             g_stat[pl.stat_segments] += ids[l].size();
+            if (pl.roi) g_stat[WR_STAT_ROI_CODER_LAUNCHES] += 1;
         }
         if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented decoder launch failed" + launch_describe(c));
         // the dequantizer only runs on planes whose every listed segment decoded
@@ -2564,6 +2565,414 @@ int wr_decode_device_seg_batch(wr_ctx* c, int nfields, double* const* d_flds, in
     std::vector<FieldRef> flds;
     if (int rc = batch_fields(nfields, d_flds, 2, &flds)) return rc;
     return decode_seg_batch_impl(c, nfields, flds, nx, ny, nz, infos, data_encs, data_lens, tm);
+}
+
+}  // extern "C"
+
+// ---- region decode, many regions per call (include/waverange_amd.h): the union of the regions' segments is uploaded and decoded
+// once -- on a WRS1 / WRS2 stream by ONE launch over all used planes (k_seg_decode_list_batch: a job per plane, a lane per
+// listed segment), on a WRS3 stream by one launch per plane --, then every region is finished as the single-region call
+// finishes its one (roi_from_planes), its crop landing at its offset of one output buffer.  No new format, and the
+// single-region drivers above are not touched: region i is bit for bit their result for rois[i] alone, because the planes hold
+// the same symbols wherever a window reads them and the window stage is the same code.
+namespace {
+
+// the plan of every region and offs[0 .. nroi], the exclusive prefix of their element counts; the first bad region decides
+int roi_multi_plans(int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi, const wr_enc_info* info,
+                    std::vector<LowresPlan>* pls, std::vector<size_t>* offs)
+{
+    if (nroi < 1 || nroi > WR_ROI_MULTI_MAX) return fail(WR_ERR_ARG, "nroi must be in 1.." + std::to_string(WR_ROI_MULTI_MAX));
+    if (!rois) return fail(WR_ERR_ARG, "null region array");
+    pls->resize((size_t)nroi);
+    offs->assign((size_t)nroi + 1, 0);
+    size_t run = 0;
+    for (int i = 0; i < nroi; i++) {
+        if (int rc = region_plan(nx, ny, nz, level, max_planes, &rois[i], info, &(*pls)[i])) return fail_at("region", i, rc);
+        (*offs)[i] = run;
+        run += (*pls)[i].out_elems();
+    }
+    (*offs)[nroi] = run;
+    return WR_OK;
+}
+
+// the slot of the window stage: sized for the largest window
+SlotNeed roi_multi_need(const std::vector<LowresPlan>& pls)
+{
+    SlotNeed need;
+    for (const LowresPlan& pl : pls) {
+        SlotNeed nd;
+        pl.need(false, &nd);
+        need.field_elems = std::max(need.field_elems, nd.field_elems);
+        need.scratch_elems = std::max(need.scratch_elems, nd.scratch_elems);
+        need.lowbuf_elems = std::max(need.lowbuf_elems, nd.lowbuf_elems);
+    }
+    return need;
+}
+
+// Kernel stage (slot leased, cu_mu held): the regions one after another on the stream, region i's crop at d_out + offs[i]
+// elements (fp32 elements if f32).  tm != nullptr: quant_ms and transform_ms are summed into it, which takes a wait per region
+// (the context has one set of events).
+int roi_multi_from_planes(wr_ctx* c, Slot* s, void* d_out, int nx, int ny, const std::vector<LowresPlan>& pls, const std::vector<size_t>& offs,
+                          const wrk::DequantParams& p, bool f32, wr_timings* tm)
+{
+    for (size_t i = 0; i < pls.size(); i++) {
+        uint8_t* const at = reinterpret_cast<uint8_t*>(d_out) + offs[i] * (f32 ? sizeof(float) : sizeof(double));
+        void* landed = nullptr;
+        if (int rc = roi_from_planes(c, s, reinterpret_cast<double*>(at), nx, ny, pls[i], p, f32, &landed)) return fail_at("region", (int)i, rc);
+        if (!tm) continue;
+        float ms = 0;
+        HIPCHK(hipEventSynchronize(c->ev_c));
+        HIPCHK(hipEventElapsedTime(&ms, c->ev_a, c->ev_b)); tm->quant_ms += ms;
+        HIPCHK(hipEventElapsedTime(&ms, c->ev_b, c->ev_c)); tm->transform_ms += ms;
+    }
+    return WR_OK;
+}
+
+int decode_seg_roi_multi_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                              const wr_enc_info* info, const unsigned char* data_enc, size_t data_len, wr_timings* tm)
+{
+    if (int rc = ctx_bind(c)) return rc;
+    if (!info) return fail(WR_ERR_ARG, "null wr_enc_info");
+    std::lock_guard<std::mutex> lk(c->mu);
+    ActiveCall active(c->pool);
+    if (tm) wrdma::enable_timing();
+    if (int rc = check_dims(nx, ny, nz, fld.dev)) return rc;
+    if (fld.none()) return fail(WR_ERR_ARG, "null output pointer");
+    std::vector<LowresPlan> pls;
+    std::vector<size_t> out_at;
+    if (int rc = roi_multi_plans(nx, ny, nz, level, max_planes, rois, nroi, info, &pls, &out_at)) return rc;
+    c->pend_valid = false;
+    PlaneHold planes(c);
+    SegBufs bufs(c);
+    BatchBufs more(c);  // the extra stream-order planes of a blocked stream, the job table, a host caller's output
+    const double t0 = now();
+    const size_t n = (size_t)nx * ny * nz, total = out_at[(size_t)nroi];
+    const bool f32 = fld.host_f32 != nullptr;
+    wr_timings local; memset(&local, 0, sizeof local);
+    DevPool* const pool = c->pool;
+    if (info->ntot_enc == 0) {  // a constant field: midval in every region
+        if (fld.host) for (size_t j = 0; j < total; j++) fld.host[j] = info->midval;
+        else if (fld.host_f32) for (size_t j = 0; j < total; j++) fld.host_f32[j] = (float)info->midval;
+        else { wrk::fill(fld.dev, total, info->midval, c->stream); HIPCHK(hipStreamSynchronize(c->stream)); }
+        local.total = now() - t0;
+        if (tm) *tm = local;
+        return WR_OK;
+    }
+    const int nlay = info->nlay, used = pls[0].planes;
+    if (nlay < 1) return fail(WR_ERR_ARG, "nlay out of range");
+    if (!data_enc) return fail(WR_ERR_ARG, "null coded buffer");
+    size_t off[WR_NLAYMAX + 1] = {0};
+    for (int l = 0; l < nlay; l++) off[l + 1] = off[l] + info->len_enc_vec[l];
+    if (off[nlay] > info->ntot_enc) return fail(WR_ERR_STREAM, "len_enc_vec exceeds ntot_enc");
+    if (data_len && info->ntot_enc > data_len) return fail(WR_ERR_STREAM, "ntot_enc exceeds the length of the coded buffer");
+    // every plane's header and index, used or not, are validated on the host before anything is launched (decode_seg_impl)
+    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0}, brick = 0, strands = 0;
+    if (int rc = seg_check_planes(data_enc, off, info, nlay, n, seg, nseg, &brick, &strands)) return rc;
+    std::vector<wrroi::Geometry> geos(pls.size());
+    for (size_t i = 0; i < pls.size(); i++) geos[i] = pls[i].win;
+    // a blocked stream: the union of the bricks the regions need, the same in every plane
+    wrblk::Order od{};
+    std::vector<uint32_t> bricks;
+    if (brick) {
+        od = wrblk::order_of(nx, ny, nz, (int)info->wlev, brick);
+        if (od.nbricks > 0x7fffffffu) return fail(WR_ERR_ARG, "too many bricks");
+        wrblk::region_bricks_multi(od, geos.data(), geos.size(), &bricks);
+    }
+    // per plane the union of the segments the regions need (planes may have been cut at different lengths)
+    std::vector<uint32_t> ids[WR_NLAYMAX];
+    unsigned long long lanes = 0;
+    for (int l = 0; l < used; l++) {
+        int same = -1;
+        for (int k = 0; k < l; k++) if (seg[k] == seg[l]) same = k;
+        if (same >= 0) ids[l] = ids[same];
+        else if (brick) {
+            ids[l].resize(wrblk::region_segments_multi(od, geos.data(), geos.size(), seg[l], nullptr, 0));
+            wrblk::region_segments_multi(od, geos.data(), geos.size(), seg[l], ids[l].data(), ids[l].size());
+        } else {
+            ids[l].resize(wrroi::segments_of_multi(nx, ny, nz, geos.data(), geos.size(), seg[l], nullptr, 0));
+            wrroi::segments_of_multi(nx, ny, nz, geos.data(), geos.size(), seg[l], ids[l].data(), ids[l].size());
+        }
+        lanes += ids[l].size();
+    }
+    if (lanes >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the call has 2^31 segments or more");
+    const bool one_launch = strands == 0;
+    const size_t table_bytes = wrk::seg_lists_table_bytes((size_t)used);
+    uint8_t* perm[WR_NLAYMAX] = {nullptr};  // the plane in stream order: one per used plane on the one-launch path
+    uint8_t* d_table = nullptr;
+    uint8_t* d_host_out = nullptr;
+    {
+        std::lock_guard<std::mutex> gather(pool->planes.gather_mu);
+        if (brick) {
+            bufs.perm = plane_scratch(c, n);
+            bufs.bricks = plane_scratch(c, 4 * bricks.size() + 4);
+            if (!bufs.perm.p || !bufs.bricks.p) return WR_ERR_HIP;
+            perm[0] = bufs.perm.p;
+            for (int l = 1; l < used; l++) {
+                perm[l] = one_launch ? more.take(n) : perm[0];
+                if (!perm[l]) return WR_ERR_HIP;
+            }
+        }
+        for (int l = 0; l < used; l++) {
+            if (int rc = plane_prepare(c, l, n, true, false, nullptr, nullptr, false)) return rc;
+            bufs.blob[l] = plane_scratch(c, info->len_enc_vec[l]);
+            bufs.work[l] = plane_scratch(c, wrk::seg_decode_list_work_bytes(nseg[l], ids[l].size()));
+            if (!bufs.blob[l].p || !bufs.work[l].p) return WR_ERR_HIP;
+            if (l == 0 || !one_launch) if (int rc = bufs.events(l)) return rc;
+        }
+        if (one_launch) {
+            d_table = more.take(table_bytes);
+            if (!d_table) return WR_ERR_HIP;
+            if (int rc = more.pin(table_bytes)) return rc;
+        }
+        if (!fld.dev) {
+            d_host_out = more.take(total * (f32 ? sizeof(float) : sizeof(double)));
+            if (!d_host_out) return WR_ERR_HIP;
+        }
+    }
+    // ---- stage "up": per plane the offsets table, the id list and the streams of the listed segments, once
+    size_t bytes_up = 0;
+    const size_t head = wrseg::header_bytes(brick, strands);
+    if (!bricks.empty()) HIPCHK(hipMemcpy(bufs.bricks.p, bricks.data(), bricks.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    for (int l = 0; l < used; l++) {
+        const uint8_t* const front = data_enc + off[l];
+        std::vector<unsigned long long> offs((size_t)nseg[l] + 1);
+        unsigned long long run = 0;
+        for (uint32_t k = 0; k < nseg[l]; k++) { offs[k] = run; run += wrseg::get_u32(front + head + 4 * (size_t)k); }
+        offs[nseg[l]] = run;
+        HIPCHK(hipMemcpy(bufs.work[l].p + 256, offs.data(), offs.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+        if (!ids[l].empty())
+            HIPCHK(hipMemcpy(wrk::seg_decode_list_ids(bufs.work[l].p, nseg[l]), ids[l].data(), ids[l].size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (int rc = seg_upload_streams(c, bufs.blob[l].p, front, head + 4 * (size_t)nseg[l], offs, ids[l], &local.h2d_ms, &bytes_up)) return rc;
+    }
+    g_stat[WR_STAT_ROI_BYTES_UP] += bytes_up;
+    const double t_coded = now();
+    const SlotNeed need = roi_multi_need(pls);
+    SlotLease slot;
+    if (int rc = slot.acquire(c, need)) return rc;
+    const double t_phase = now();
+    wrk::DequantParams p;
+    memset(&p, 0, sizeof p);
+    p.nlay = used;
+    for (int l = 0; l < used; l++) {
+        p.deps[l] = info->deps_vec[l]; p.minval[l] = info->minval_vec[l]; p.q[l] = c->ps[l].ref;
+        if (!wrk::plane_ref_covers(p.q[l], n)) return fail(WR_ERR_HIP, "internal: the device buffer of plane " + std::to_string(l) + " has a hole");
+    }
+    void* const d_out = fld.dev ? (void*)fld.dev : (void*)d_host_out;
+    int rc = WR_OK;
+    {
+        StageLock cu(pool->cu_mu);
+        clock_warmup(c, need.field_elems);
+        const uint32_t* const d_bricks = reinterpret_cast<const uint32_t*>(bufs.bricks.p);
+        if (one_launch) {
+            wrk::SegJob jobs[WR_NLAYMAX];
+            wrk::SegList lists[WR_NLAYMAX];
+            memset(jobs, 0, sizeof jobs);
+            memset(lists, 0, sizeof lists);
+            for (int l = 0; l < used; l++) {
+                uint8_t* const work = bufs.work[l].p;
+                wrk::SegJob& job = jobs[l];
+                job.sym = brick ? wrk::plane_ref(perm[l]) : p.q[l];
+                job.n = n; job.blob = bufs.blob[l].p; job.cap = info->len_enc_vec[l];
+                job.offs = reinterpret_cast<unsigned long long*>(work + 256);
+                job.flags = reinterpret_cast<uint32_t*>(work + 256 + up256(8 * ((size_t)nseg[l] + 1)));
+                job.bad = reinterpret_cast<unsigned int*>(work);
+                job.seg = seg[l]; job.nseg = nseg[l]; job.brick = brick;
+                lists[l].ids = wrk::seg_decode_list_ids(work, nseg[l]);
+                lists[l].nlist = (uint32_t)ids[l].size();
+                HIPCHK(hipMemsetAsync(work, 0, sizeof(unsigned int), c->stream));
+                g_stat[WR_STAT_ROI_SEGMENTS] += ids[l].size();
+            }
+            launch_note(c, "seg_decode_lists", 0, bufs.blob[0].p, n, bufs.work[0].p, p.q[0]);
+            HIPCHK(hipEventRecord(bufs.ev[0], c->stream));
+            wrk::seg_decode_lists(jobs, lists, (size_t)used, more.pinned, d_table, c->stream);
+            HIPCHK(hipEventRecord(bufs.ev[1], c->stream));
+            g_stat[WR_STAT_ROI_CODER_LAUNCHES] += 1;
+            // the listed segments are in the scratch planes in stream order: the needed bricks go to their places in the planes
+            for (int l = 0; brick && l < used; l++)
+                if (!wrk::plane_reorder(p.q[l], perm[l], od, true, d_bricks, bricks.size(), c->stream)) return fail(WR_ERR_ARG, "too many bricks");
+        } else {
+            for (int l = 0; l < used; l++) {
+                launch_note(c, "seg_decode_list", l, bufs.blob[l].p, n, bufs.work[l].p, p.q[l]);
+                HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
+                wrk::seg_decode_list(bufs.blob[l].p, info->len_enc_vec[l], brick ? wrk::plane_ref(perm[l]) : p.q[l], n, seg[l], bufs.work[l].p, ids[l].size(),
+                                     c->stream, brick, strands);
+                if (brick && !wrk::plane_reorder(p.q[l], perm[l], od, true, d_bricks, bricks.size(), c->stream)) return fail(WR_ERR_ARG, "too many bricks");
+                HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
+                g_stat[WR_STAT_ROI_SEGMENTS] += ids[l].size();
+                g_stat[WR_STAT_ROI_CODER_LAUNCHES] += 1;
+            }
+        }
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented decoder launch failed" + launch_describe(c));
+        // the per-plane counts come back once; no dequantizer runs unless every listed segment of every plane decoded
+        unsigned int bad[WR_NLAYMAX] = {0};
+        for (int l = 0; l < used; l++) HIPCHK(hipMemcpyAsync(&bad[l], bufs.work[l].p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the segmented decoder failed on the device" + launch_describe(c));
+        for (int l = 0; l < used; l++)
+            if (bad[l]) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + std::to_string(bad[l]) + " segment(s) do not decode to their symbols");
+        for (int l = 0; l < (one_launch ? 1 : used); l++) {
+            local.plane_coder_s[l] = bufs.seconds(l);
+            local.rangecoder += local.plane_coder_s[l];
+        }
+        launch_note(c, "dequant_window", used - 1, slot->field, need.field_elems, nullptr, p.q[used - 1]);
+        rc = roi_multi_from_planes(c, slot.get(), d_out, nx, ny, pls, out_at, p, f32, tm ? &local : nullptr);
+        if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
+        if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the decoder's kernel stage failed on the device" + launch_describe(c));
+        pool->last_stage_end.store(now());
+    }
+    if (rc) return rc;
+    if (fld.host) {
+        if ((rc = xfer_field(c, &c->x_field, fld.host, d_host_out, total * sizeof(double), kDown)) != WR_OK) return rc;
+        local.d2h_ms = (float)c->x_field.ms;
+    } else if (fld.host_f32) {
+        if ((rc = xfer_field(c, &c->x_field, fld.host_f32, d_host_out, total * sizeof(float), kDown)) != WR_OK) return rc;
+        local.d2h_ms = (float)c->x_field.ms;
+    }
+    local.total = now() - t0;
+    local.gpu = now() - t_phase;
+    local.wait = t_phase - t_coded;
+    local.transfer = t_coded - t0;
+    if (tm) *tm = local;
+    return WR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wr_dev_decode_planes_roi_multi(wr_ctx* c, double* d_out, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                                   const unsigned char* d_planes, const wr_enc_info* info)
+{
+    if (int rc = ctx_bind(c)) return rc;
+    if (int rc = check_dims(nx, ny, nz, d_out)) return rc;
+    if (!d_out || !info) return fail(WR_ERR_ARG, "null pointer");
+    std::vector<LowresPlan> pls;
+    std::vector<size_t> out_at;
+    if (int rc = roi_multi_plans(nx, ny, nz, level, max_planes, rois, nroi, info, &pls, &out_at)) return rc;
+    const size_t n = (size_t)nx * ny * nz;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (info->ntot_enc == 0 && info->nlay == 0) {  // a constant field, as wr_dev_decode_planes_roi
+        wrk::fill(d_out, out_at[(size_t)nroi], info->midval, c->stream);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return WR_OK;
+    }
+    if (!d_planes) return fail(WR_ERR_ARG, "null plane pointer");
+    SlotLease slot;
+    if (int rc = slot.acquire(c, roi_multi_need(pls))) return rc;
+    StageLock cu(c->pool->cu_mu);
+    wrk::DequantParams p;
+    memset(&p, 0, sizeof p);
+    p.nlay = pls[0].planes;
+    for (int l = 0; l < p.nlay; l++) {
+        p.q[l] = wrk::plane_ref(d_planes + l * wr_plane_pitch(n));
+        p.deps[l] = info->deps_vec[l];
+        p.minval[l] = info->minval_vec[l];
+    }
+    int rc = roi_multi_from_planes(c, slot.get(), d_out, nx, ny, pls, out_at, p, false, nullptr);
+    if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the region kernel stage failed on the device");
+    return rc;
+}
+
+int wr_dev_seg_decode_lists(wr_ctx* c, int njobs, const unsigned char* const* d_blob, const size_t* blob_len, unsigned char* const* d_sym, const size_t* n,
+                            const uint32_t* const* ids, const size_t* nlist, size_t* bad_segments)
+{
+    if (njobs < 1 || njobs > WR_SEG_BATCH_MAX) return fail(WR_ERR_ARG, "njobs must be in 1.." + std::to_string(WR_SEG_BATCH_MAX));
+    if (int rc = ctx_bind(c)) return rc;
+    if (!d_blob || !blob_len || !d_sym || !n || !ids || !nlist) return fail(WR_ERR_ARG, "null array");
+    for (int j = 0; j < njobs; j++) {
+        const std::string who = "job " + std::to_string(j) + ": ";
+        if (!d_blob[j] || (n[j] && !d_sym[j]) || (nlist[j] && !ids[j])) return fail(WR_ERR_ARG, who + "null pointer");
+        if (((uintptr_t)d_sym[j] | (uintptr_t)d_blob[j]) & 15) return fail(WR_ERR_ARG, who + "plane and blob buffers must be 16-byte aligned");
+        if (bad_segments) bad_segments[j] = 0;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    // every header, index and list is validated on the host before anything is launched for any job
+    std::vector<std::vector<uint8_t>> front(njobs);
+    std::vector<uint32_t> seg(njobs, 0), nseg(njobs, 0), brick(njobs, 0);
+    unsigned long long lanes = 0;
+    for (int j = 0; j < njobs; j++) {
+        const std::string who = "job " + std::to_string(j) + ": ";
+        if (blob_len[j] < wrseg::kHeaderBytes) return fail(WR_ERR_STREAM, who + "segmented plane: shorter than its header");
+        front[j].resize(std::min(blob_len[j], wrseg::kHeaderBytesBlocked));
+        HIPCHK(hipMemcpy(front[j].data(), d_blob[j], front[j].size(), hipMemcpyDeviceToHost));
+        if (memcmp(front[j].data(), wrseg::kMagicStrands, 4) == 0)
+            return fail(WR_ERR_UNSUPPORTED, who + "a WRS3 blob: stranded segments have no batched list decoder");
+        const char* why = wrseg::check_index(front[j].data(), front[j].size(), blob_len[j], n[j], &seg[j], &nseg[j], &brick[j]);
+        if (why == wrseg::kIndexNotAvailable) {  // (the index fits into the blob: check_index has looked)
+            const size_t head = memcmp(front[j].data(), wrseg::kMagicBlocked, 4) == 0 ? wrseg::kHeaderBytesBlocked : wrseg::kHeaderBytes;
+            front[j].resize(head + 4 * (size_t)wrseg::get_u32(front[j].data() + 8));
+            HIPCHK(hipMemcpy(front[j].data(), d_blob[j], front[j].size(), hipMemcpyDeviceToHost));
+            why = wrseg::check_index(front[j].data(), front[j].size(), blob_len[j], n[j], &seg[j], &nseg[j], &brick[j]);
+        }
+        if (why) return fail(WR_ERR_STREAM, who + why);
+        if (nlist[j] > nseg[j]) return fail(WR_ERR_ARG, who + "the list is longer than the plane has segments");
+        for (size_t i = 0; i < nlist[j]; i++)
+            if (ids[j][i] >= nseg[j] || (i && ids[j][i] <= ids[j][i - 1])) return fail(WR_ERR_ARG, who + "the list must be ascending, every id below the segment count");
+        lanes += nlist[j];
+    }
+    if (lanes >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the launch has 2^31 lanes or more");
+    if (!lanes) return WR_OK;
+    BatchBufs bufs(c);
+    const size_t table = wrk::seg_lists_table_bytes(njobs);
+    uint8_t* const d_table = bufs.take(table);
+    if (!d_table) return WR_ERR_HIP;
+    if (int rc = bufs.pin(table)) return rc;
+    std::vector<wrk::SegJob> jobs(njobs);
+    std::vector<wrk::SegList> lists(njobs);
+    std::vector<uint8_t*> works(njobs, nullptr);
+    for (int j = 0; j < njobs; j++) {
+        wrk::SegJob& job = jobs[j];
+        memset(&job, 0, sizeof job);
+        memset(&lists[j], 0, sizeof lists[j]);
+        job.sym = wrk::plane_ref(d_sym[j]);
+        job.n = n[j]; job.blob = const_cast<unsigned char*>(d_blob[j]); job.cap = blob_len[j];
+        job.seg = seg[j]; job.nseg = nseg[j]; job.brick = brick[j];
+        if (!nlist[j]) continue;
+        uint8_t* const work = works[j] = bufs.take(wrk::seg_decode_list_work_bytes(nseg[j], nlist[j]));
+        if (!work) return WR_ERR_HIP;
+        if (int rc = seg_upload_offsets(c, front[j].data(), nseg[j], work, brick[j], 0)) return rc;
+        HIPCHK(hipMemcpy(wrk::seg_decode_list_ids(work, nseg[j]), ids[j], nlist[j] * sizeof(uint32_t), hipMemcpyHostToDevice));
+        job.offs = reinterpret_cast<unsigned long long*>(work + 256);
+        job.flags = reinterpret_cast<uint32_t*>(work + 256 + up256(8 * ((size_t)nseg[j] + 1)));
+        job.bad = reinterpret_cast<unsigned int*>(work);
+        lists[j].ids = wrk::seg_decode_list_ids(work, nseg[j]);
+        lists[j].nlist = (uint32_t)nlist[j];
+    }
+    StageLock cu(c->pool->cu_mu);
+    for (int j = 0; j < njobs; j++) if (works[j]) HIPCHK(hipMemsetAsync(works[j], 0, sizeof(unsigned int), c->stream));
+    wrk::seg_decode_lists(jobs.data(), lists.data(), jobs.size(), bufs.pinned, d_table, c->stream);
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned int> bad(njobs, 0);
+    for (int j = 0; j < njobs; j++) if (works[j]) HIPCHK(hipMemcpyAsync(&bad[j], works[j], sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    int rc = WR_OK;
+    for (int j = 0; j < njobs; j++) {
+        if (bad_segments) bad_segments[j] = bad[j];
+        if (bad[j] && !rc) rc = fail(WR_ERR_STREAM, "job " + std::to_string(j) + ": segmented plane: " + std::to_string(bad[j]) + " segment(s) do not decode to their symbols");
+    }
+    return rc;
+}
+
+int wr_decode_host_seg_roi_multi(wr_ctx* c, double* h_out, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                                 const wr_enc_info* info, const unsigned char* data_enc, size_t data_len, wr_timings* tm)
+{
+    FieldRef f; f.host = h_out;
+    return decode_seg_roi_multi_impl(c, f, nx, ny, nz, level, max_planes, rois, nroi, info, data_enc, data_len, tm);
+}
+
+int wr_decode_host_seg_roi_multi_f32(wr_ctx* c, float* h_out, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                                     const wr_enc_info* info, const unsigned char* data_enc, size_t data_len, wr_timings* tm)
+{
+    FieldRef f; f.host_f32 = h_out;
+    return decode_seg_roi_multi_impl(c, f, nx, ny, nz, level, max_planes, rois, nroi, info, data_enc, data_len, tm);
+}
+
+int wr_decode_device_seg_roi_multi(wr_ctx* c, double* d_out, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                                   const wr_enc_info* info, const unsigned char* data_enc, size_t data_len, wr_timings* tm)
+{
+    FieldRef f; f.dev = d_out;
+    if (!d_out) return fail(WR_ERR_ARG, "null device output pointer");
+    return decode_seg_roi_multi_impl(c, f, nx, ny, nz, level, max_planes, rois, nroi, info, data_enc, data_len, tm);
 }
 
 }  // extern "C"

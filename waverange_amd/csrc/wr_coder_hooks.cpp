@@ -403,4 +403,40 @@ size_t wr_seg_roi_segments_blocked(int nx, int ny, int nz, int level, int wlev, 
                                   seg, ids, ids ? cap : 0);
 }
 
+// ---- the geometry of a region decode over several regions (include/waverange_amd.h, "many regions per call"): host only
+static bool roi_multi_args_ok(int nx, int ny, int nz, int level, int wlev, const wr_box* rois, int nroi)
+{
+    if (nroi < 1 || nroi > WR_ROI_MULTI_MAX) { fail(WR_ERR_ARG, "nroi must be in 1.." + std::to_string(WR_ROI_MULTI_MAX)); return false; }
+    if (!rois) { fail(WR_ERR_ARG, "null region array"); return false; }
+    for (int i = 0; i < nroi; i++)
+        if (!roi_args_ok(nx, ny, nz, level, wlev, &rois[i])) { fail(WR_ERR_ARG, "region " + std::to_string(i) + ": " + wr_last_error()); return false; }
+    return true;
+}
+
+size_t wr_roi_multi_elems(int nx, int ny, int nz, int level, const wr_box* rois, int nroi, size_t* offs)
+{
+    if (!roi_multi_args_ok(nx, ny, nz, level, wrlow::kMaxLevel, rois, nroi)) return 0;  // (the box of a level does not depend on wlev)
+    size_t run = 0;
+    for (int i = 0; i < nroi; i++) {
+        if (offs) offs[i] = run;
+        run += (size_t)(rois[i].x1 - rois[i].x0) * (size_t)(rois[i].y1 - rois[i].y0) * (size_t)(rois[i].z1 - rois[i].z0);
+    }
+    if (offs) offs[nroi] = run;
+    return run;
+}
+
+size_t wr_seg_roi_segments_multi(int nx, int ny, int nz, int level, int wlev, const wr_box* rois, int nroi, unsigned brick, unsigned seg, uint32_t* ids,
+                                 size_t cap)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
+    if (brick && !blocked_args_ok(nx, ny, nz, wlev, &brick)) return 0;
+    if (!roi_multi_args_ok(nx, ny, nz, level, wlev, rois, nroi)) return 0;
+    const wrlow::Box box = wrlow::box_of(nx, ny, nz, level);
+    std::vector<wrroi::Geometry> g((size_t)nroi);
+    for (int i = 0; i < nroi; i++) g[i] = wrroi::geometry_of(box, wlev - level, rois[i]);
+    if (brick) return wrblk::region_segments_multi(wrblk::order_of(nx, ny, nz, wlev, brick), g.data(), g.size(), seg, ids, ids ? cap : 0);
+    return wrroi::segments_of_multi(nx, ny, nz, g.data(), g.size(), seg, ids, ids ? cap : 0);
+}
+
 }  // extern "C"

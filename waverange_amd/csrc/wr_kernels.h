@@ -186,6 +186,20 @@ void seg_encode_batch(SegJob* jobs, size_t njobs, size_t n, unsigned seg, uint8_
 // Decode: jobs may differ in n, seg and brick.  `table`: seg_batch_table_bytes(njobs) of device memory, 256-byte aligned;
 // host_table as above.  Every job's offs come from an index the caller has VALIDATED on the host.
 void seg_decode_batch(const SegJob* jobs, size_t njobs, uint8_t* host_table, uint8_t* table, hipStream_t st);
+// The same over a subset of every job's segments (k_seg_decode_list_batch): job j decodes the segments lists[j].ids[0, nlist)
+// -- u32 in DEVICE memory, ascending, every one below the job's nseg, put there by the caller -- and nothing else of its blob
+// is read, nothing else of its plane written, flags[] set for those segments alone.  A lane per listed segment of any job; a
+// job with nlist == 0 owns none.  `table`: seg_lists_table_bytes(njobs) of device memory, 256-byte aligned (the table of
+// seg_decode_batch with first[] the prefix of the list lengths, then the lists' records); host_table: as many bytes of host
+// memory, alive until the stream has drained.  Every job's `bad` is zeroed by the caller.  Returns the lanes of the launch
+// (the caller keeps them below 2^31); 0: nothing was launched.
+struct SegList {
+    const uint32_t* ids;
+    uint32_t nlist;
+    uint32_t pad;
+};
+size_t seg_lists_table_bytes(size_t njobs);
+size_t seg_decode_lists(const SegJob* jobs, const SegList* lists, size_t njobs, uint8_t* host_table, uint8_t* table, hipStream_t st);
 
 // ---- the blocked symbol order of WRS2 (wr_blocked.hip; the order itself and its host geometry: wr_blocked.h).  `nat` is the
 // plane in natural order, `blk` the same n bytes in the blocked order, one array.  Forward: blk := nat permuted; inverse:

@@ -23,7 +23,7 @@ std::string& last_error() { return g_err; }
 std::atomic<int> g_verbose{-1};      // -1: not initialised from the environment yet
 std::atomic<int> g_threads{-1};      // -1: not initialised from the environment yet (WR_THREADS, default one per plane)
 std::atomic<int> g_enc_threads{0};   // 0: same as g_threads (wr_set_encoder_threads)
-std::atomic<unsigned long> g_stat[15];  // see wr_stat()
+std::atomic<unsigned long> g_stat[16];  // see wr_stat()
 std::atomic<int> g_writeback{-1};    // drop-in encoding_wrap leaves the residual in fld_1d (-1: from WR_WRITEBACK_RESIDUAL, default 1)
 
 int coder_threads()
@@ -832,7 +832,7 @@ unsigned long wr_stat(int what)
     if (what == WR_STAT_POOL_STREAMS_MOVED) return wrrc::pool_streams_moved();
     if (what == WR_STAT_POOL_QUEUE_MS) return (unsigned long)(wrrc::pool_queue_seconds() * 1e3);
     if (what == WR_STAT_WINDOW_WAIT_MS) return (unsigned long)(g_window_wait_us.load() / 1000);
-    return (what >= 0 && what < 15) ? g_stat[what].load() : 0;
+    return (what >= 0 && what < 16) ? g_stat[what].load() : 0;
 }
 void wr_set_coder_pool(int nthreads, int decoder_streams)
 {

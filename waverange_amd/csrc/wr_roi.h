@@ -101,27 +101,47 @@ inline Geometry geometry_of(const wrlow::Box& b, int d, const wr_box& roi)
     return g;
 }
 
-// The ascending ids of the segments of length `seg` that the source boxes' x-runs touch in a plane of an nx * ny * nz field;
-// conventions of wrlow::segments_of.
-inline size_t segments_of(int nx, int ny, int nz, const Geometry& g, uint32_t seg, uint32_t* ids, size_t cap)
+// need[k] = true for every segment of length `seg` that the source boxes' x-runs touch in a plane of an nx * ny * nz field
+// (need has one entry per segment of the plane; marks that are set stay set, so several regions can share one array)
+inline void mark_segments(int nx, int ny, const Geometry& g, uint32_t seg, std::vector<bool>* need)
 {
-    const size_t n = (size_t)nx * ny * nz, nseg = (n + seg - 1) / seg;
-    std::vector<bool> need(nseg, false);
     for (int i = 0; i < g.nbox; i++) {
         const SrcBox& s = g.box[i];
         for (int z = s.src[2]; z < s.src[2] + s.len[2]; z++)
             for (int y = s.src[1]; y < s.src[1] + s.len[1]; y++) {
                 const size_t at = ((size_t)y + (size_t)ny * z) * nx + s.src[0];
-                for (size_t k = at / seg; k <= (at + s.len[0] - 1) / seg; k++) need[k] = true;
+                for (size_t k = at / seg; k <= (at + s.len[0] - 1) / seg; k++) (*need)[k] = true;
             }
     }
+}
+
+// the marked ids, ascending: the first `cap` of them go to ids (if it is not null), the count of all of them is returned
+inline size_t list_marks(const std::vector<bool>& need, uint32_t* ids, size_t cap)
+{
     size_t count = 0;
-    for (size_t k = 0; k < nseg; k++)
+    for (size_t k = 0; k < need.size(); k++)
         if (need[k]) {
             if (ids && count < cap) ids[count] = (uint32_t)k;
             count++;
         }
     return count;
+}
+
+// The ascending ids of the segments of length `seg` that the source boxes' x-runs touch in a plane of an nx * ny * nz field;
+// conventions of wrlow::segments_of.
+inline size_t segments_of(int nx, int ny, int nz, const Geometry& g, uint32_t seg, uint32_t* ids, size_t cap)
+{
+    std::vector<bool> need(((size_t)nx * ny * nz + seg - 1) / seg, false);
+    mark_segments(nx, ny, g, seg, &need);
+    return list_marks(need, ids, cap);
+}
+
+// the ascending union of segments_of over the regions g[0, ng)
+inline size_t segments_of_multi(int nx, int ny, int nz, const Geometry* g, size_t ng, uint32_t seg, uint32_t* ids, size_t cap)
+{
+    std::vector<bool> need(((size_t)nx * ny * nz + seg - 1) / seg, false);
+    for (size_t i = 0; i < ng; i++) mark_segments(nx, ny, g[i], seg, &need);
+    return list_marks(need, ids, cap);
 }
 
 }  // namespace wrroi

@@ -11,6 +11,9 @@
 //   k_seg_scan_batch     one workgroup per job: k_seg_scan on the job's slice of lens -> the job's offs, header, index, result
 //   k_seg_gather_batch   k_seg_gather with the job found per segment
 //   k_seg_decode_batch   k_seg_decode<false> behind the locator; flags and the count of failed segments are per job
+//   k_seg_decode_list_batch   k_seg_decode<true> behind the locator: a job carries an ascending list of segment ids, first[] is
+//                        the exclusive prefix of the jobs' LIST LENGTHS, and lane g takes segment ids[g - first[j]] of job j.  The
+//                        planes of one stream, each with the union of the segments some regions need, go into one launch.
 //
 // The coder steps are wr_segcoder.h's and the lane's tools wr_segcoder_dev.h's, as in wr_segcoder.hip: every blob is byte for
 // byte the single-plane kernels' blob.
@@ -174,6 +177,41 @@ __global__ __launch_bounds__(kLanes) void k_seg_decode_batch(const SegJob* jobs,
     if (why != wrseg::kSegOk) atomicAdd(job.bad, 1u);
 }
 
+// Lane g is position i of the list of job j: it decodes segment ids[i] of that job, as lane i of k_seg_decode<true> launched
+// for the job alone would.  No barrier: a lane past the end may go.
+__global__ __launch_bounds__(kLanes) void k_seg_decode_list_batch(const SegJob* jobs, const SegList* lists, const uint32_t* first, uint32_t njobs)
+{
+    __shared__ uint32_t tab[256 * kLanes];
+    const uint32_t lane = threadIdx.x;
+    const size_t g = (size_t)blockIdx.x * kLanes + lane;
+    if (g >= first[njobs]) return;
+    uint32_t j, i;
+    wrsb::locate(first, njobs, (uint32_t)g, &j, &i);
+    const SegJob& job = jobs[j];
+    const size_t k = lists[j].ids[i];
+    const uint32_t seg = job.seg, nseg = job.nseg;
+    if (k >= nseg) return;  // (the host made the list: every id is below nseg)
+    LdsTable t{tab + lane};
+    const size_t n = job.n;
+    const uint8_t* const blob = job.blob;
+    const size_t blob_len = job.cap;
+    const size_t base = k * seg;
+    const uint32_t bs = n - base < seg ? (uint32_t)(n - base) : seg;
+    // (the host has validated the index: the streams lie inside the blob, in order, each no longer than a segment can be)
+    const size_t front = wrseg::header_bytes(job.brick) + 4 * (size_t)nseg;
+    const unsigned long long o0 = job.offs[k], o1 = job.offs[k + 1];
+    uint32_t why = wrseg::kSegOverflow;
+    if (o1 >= o0 && front + o1 <= blob_len && o1 - o0 <= wrseg::stream_bound(seg)) {
+        wrseg::Dec d;
+        d.in.open(blob + front + o0, (uint32_t)(o1 - o0), blob, blob + blob_len);
+        SymSink sink{SegSpan(job.sym, base, bs), bs, 0, 0};
+        why = wrseg::decode_segment(d, t, sink, bs);
+        sink.flush();
+    }
+    job.flags[k] = why;
+    if (why != wrseg::kSegOk) atomicAdd(job.bad, 1u);
+}
+
 size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -238,6 +276,26 @@ void seg_decode_batch(const SegJob* jobs, size_t njobs, uint8_t* host_table, uin
     (void)hipMemcpyAsync(table, host_table, seg_batch_table_bytes(njobs), hipMemcpyHostToDevice, st);
     hipLaunchKernelGGL(k_seg_decode_batch, dim3((unsigned)((total + kLanes - 1) / kLanes)), dim3(kLanes), 0, st, reinterpret_cast<const SegJob*>(table),
                        reinterpret_cast<const uint32_t*>(table + up256(njobs * sizeof(SegJob))), (uint32_t)njobs);
+}
+
+size_t seg_lists_table_bytes(size_t njobs) { return seg_batch_table_bytes(njobs) + up256(njobs * sizeof(SegList)); }
+
+size_t seg_decode_lists(const SegJob* jobs, const SegList* lists, size_t njobs, uint8_t* host_table, uint8_t* table, hipStream_t st)
+{
+    // the table of seg_decode_batch with first[] over the list lengths, and the lists' records behind it
+    const size_t at_first = up256(njobs * sizeof(SegJob)), at_lists = seg_batch_table_bytes(njobs);
+    memset(host_table, 0, seg_lists_table_bytes(njobs));
+    memcpy(host_table, jobs, njobs * sizeof(SegJob));
+    memcpy(host_table + at_lists, lists, njobs * sizeof(SegList));
+    uint32_t* const first = reinterpret_cast<uint32_t*>(host_table + at_first);
+    size_t total = 0;
+    for (size_t j = 0; j < njobs; j++) { first[j] = (uint32_t)total; total += lists[j].nlist; }
+    first[njobs] = (uint32_t)total;
+    if (!total) return 0;
+    (void)hipMemcpyAsync(table, host_table, seg_lists_table_bytes(njobs), hipMemcpyHostToDevice, st);
+    hipLaunchKernelGGL(k_seg_decode_list_batch, dim3((unsigned)((total + kLanes - 1) / kLanes)), dim3(kLanes), 0, st, reinterpret_cast<const SegJob*>(table),
+                       reinterpret_cast<const SegList*>(table + at_lists), reinterpret_cast<const uint32_t*>(table + at_first), (uint32_t)njobs);
+    return total;
 }
 
 }  // namespace wrk
