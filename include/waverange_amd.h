@@ -41,6 +41,7 @@ extern "C" {
 void setup_wr(int nx, int ny, int nz, unsigned char *nlaymax, unsigned long *ntot_enc_max);
 
 /* replaces encoding_wrap, reference src/core/wrappers.cpp:228-452 (wrappers.h:53).
+ * Writes the reference's stream unless wr_set_stream_format / WR_STREAM_FORMAT (Part 2) select a segmented format.
  * fld_1d: host double[nx*ny*nz], x fastest.  data_enc: host buffer of ntot_enc_max bytes.
  * mx*my*mz > 1 selects the reference's non-uniform (local) cutoff branch, wrappers.cpp:343-379.
  * As in the reference (wrappers.cpp:397-398, README.md:197) fld_1d is overwritten with the residual
@@ -680,6 +681,38 @@ int wr_decode_host_seg_roi_multi_f32(wr_ctx *ctx, float *h_out, int nx, int ny, 
 int wr_decode_device_seg_roi_multi(wr_ctx *ctx, double *d_out, int nx, int ny, int nz, int level, int max_planes,
                                    const wr_box *rois, int nroi, const wr_enc_info *info, const unsigned char *data_enc,
                                    size_t data_len, wr_timings *tm);
+
+/* ---- The stream format of the drop-in symbols: which of the four formats the implicit-context ENCODERS write.
+ * encoding_wrap, encoding_wrap_f and wr_encoding_wrap_f32 write the reference's stream unless this process-wide setting says
+ * otherwise; then they run wr_encode_host_seg / _seg_blocked / _seg_strands (the _f32 forms) with the setting's parameters.
+ * Header scalars, the residual write-back of an fp64 field and setup_wr are unchanged; a stream that outgrows setup_wr's
+ * bound is fatal with the reference's message (only the bytes actually produced count, also for WRS3, whose worst case is
+ * larger).  The DECODERS -- decoding_wrap, decoding_wrap_f, wr_decoding_wrap_f32 -- do not look at the setting: a coded field
+ * of four bytes or more that starts with "WRS1" / "WRS2" / "WRS3" goes through wr_decode_host_seg (_f32), anything else through
+ * wr_decode_host (every plane of a reference stream starts with byte 0x00).  The explicit-context entry points (wr_encode_host,
+ * wr_decode_host, ...) neither change nor look at the setting.
+ * Grammar of the text form:  ref | wrs1 | wrs2 | wrs3, then :seg=N, :brick=B, :strands=K in any order, each at most once,
+ *   e.g. "wrs3:seg=4096:brick=16:strands=8".  Missing values are the defaults: WR_SEG_DEFAULT; WR_BRICK_DEFAULT for wrs2 and
+ *   0 (the natural order) for wrs3; WR_STRANDS_DEFAULT.  Refused (WR_ERR_ARG, wr_last_error() quotes the offending token): an
+ *   unknown name or key, a key given twice, any key with ref, brick with wrs1, strands without wrs3, a value the _seg encoders
+ *   refuse, anything else after the name.
+ * The environment variable WR_STREAM_FORMAT holds the same grammar.  It is read once, by the first implicit-context encode (or
+ * the first wr_get_stream_format); a value that does not parse is fatal at that encode, with the parser's message -- there is
+ * no silent fall back to the reference's stream.  wr_set_stream_format overrides it, before or after.
+ * All four functions are host only: no device call, no context. */
+#define WR_FORMAT_REF 0
+#define WR_FORMAT_WRS1 1
+#define WR_FORMAT_WRS2 2
+#define WR_FORMAT_WRS3 3
+/* text -> the four values, defaults filled in (ref: 0, 0, 0, 0); outputs may be NULL and are untouched on an error */
+int wr_stream_format_parse(const char *text, int *format, unsigned *seg, unsigned *brick, unsigned *strands);
+/* 0 for seg, brick (wrs2) or strands (wrs3) means the default, as in the _seg calls; WR_ERR_ARG on what those calls refuse,
+ * on a non-zero brick with WRS1, non-zero strands without WRS3 and any non-zero parameter with WR_FORMAT_REF */
+int wr_set_stream_format(int format, unsigned seg, unsigned brick, unsigned strands);
+/* the setting in force, defaults filled in; WR_ERR_ARG (the parser's message) if WR_STREAM_FORMAT decides and does not parse */
+int wr_get_stream_format(int *format, unsigned *seg, unsigned *brick, unsigned *strands);
+/* WR_FORMAT_* of a coded field's first bytes; -1: neither (fewer than four bytes of a magic, an unknown magic, no bytes) */
+int wr_stream_sniff(const unsigned char *data, size_t len);
 
 /* encoding_wrap / decoding_wrap for fp32 fields: the same arguments but the field, an implicit context per call and
  * the reference's "void + fatal" errors.  fld_1d of an encode is never overwritten (no residual write-back). */

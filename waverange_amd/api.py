@@ -247,6 +247,11 @@ def lib():
         _u8p, _u8p, _ulp, _dp, _dp, _ulp, _u8p]
     L.decoding_wrap.argtypes = [C.c_int] * 3 + [_dp] + [_dp] * 3 + [_u8p, _u8p, _ulp, _dp, _dp, _ulp, _u8p]
     L.waveletcdf97_3d.argtypes = [C.c_int] * 4 + [_dp]
+    _up = C.POINTER(C.c_uint)
+    L.wr_stream_format_parse.argtypes = [C.c_char_p, C.POINTER(C.c_int), _up, _up, _up]
+    L.wr_set_stream_format.argtypes = [C.c_int, C.c_uint, C.c_uint, C.c_uint]
+    L.wr_get_stream_format.argtypes = [C.POINTER(C.c_int), _up, _up, _up]
+    L.wr_stream_sniff.argtypes = [_vp, C.c_size_t]
     _lib = L
     return L
 
@@ -810,6 +815,37 @@ def decoding_wrap(enc, shape):
                         C.byref(wlev), C.byref(nlay), C.byref(ntot_enc), p(deps, _dp), p(mins, _dp),
                         p(lens, _ulp), p(data, _u8p))
     return out.reshape(shape)
+
+
+# the stream format the drop-in encoders write (wr_set_stream_format; the decoders read what the bytes say)
+FORMAT_REF, FORMAT_WRS1, FORMAT_WRS2, FORMAT_WRS3 = 0, 1, 2, 3
+
+
+def stream_format_parse(text):
+    """(format, seg, brick, strands) of "ref" | "wrs1" | "wrs2" | "wrs3" [":seg=N"] [":brick=B"] [":strands=K"], defaults filled
+    in; WaveRangeError (error -1, the message quotes the offending token) for anything else."""
+    f, seg, brick, strands = C.c_int(), C.c_uint(), C.c_uint(), C.c_uint()
+    _check(lib().wr_stream_format_parse(text.encode(), C.byref(f), C.byref(seg), C.byref(brick), C.byref(strands)))
+    return f.value, seg.value, brick.value, strands.value
+
+
+def set_stream_format(text):
+    """What encoding_wrap (and every other implicit-context encoder of the library) writes from now on, process-wide; None:
+    the reference's stream.  Overrides WR_STREAM_FORMAT."""
+    _check(lib().wr_set_stream_format(*(stream_format_parse(text) if text is not None else (FORMAT_REF, 0, 0, 0))))
+
+
+def stream_format():
+    """(format, seg, brick, strands) in force: the last set_stream_format, else WR_STREAM_FORMAT, else the reference's stream."""
+    f, seg, brick, strands = C.c_int(), C.c_uint(), C.c_uint(), C.c_uint()
+    _check(lib().wr_get_stream_format(C.byref(f), C.byref(seg), C.byref(brick), C.byref(strands)))
+    return f.value, seg.value, brick.value, strands.value
+
+
+def stream_sniff(buf):
+    """FORMAT_* of a coded field's first bytes (bytes or a uint8 array); -1: neither a reference stream nor a segmented one."""
+    b = np.frombuffer(bytes(buf[:4]), dtype=np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else np.ascontiguousarray(buf, dtype=np.uint8).ravel()[:4]
+    return int(lib().wr_stream_sniff(b.ctypes.data if b.size else None, b.size))
 
 
 def waveletcdf97_3d(x, lvl):

@@ -178,11 +178,11 @@ void read_raw_field(std::istream& in, int nbytes, double* fld, size_t n)
     for (size_t j = 0; j < n; j++) fld[j] = f[j];
 }
 
-void write_header_preamble(const std::string& path, const std::string& wrb_name, int file_type, bool flip, int nf)
+void write_header_preamble(const std::string& path, const std::string& wrb_name, int file_type, bool flip, int nf, bool segmented)
 {
     std::ofstream h(path, std::ios::out | std::ios::trunc);  // gen_enc.cpp:509-520
     if (!h.is_open()) die("Cannot open " + path);
-    h << " ===== Header file for compressed data =====" << std::endl;
+    h << (segmented ? " ===== Header file for compressed data (segmented plane streams) =====" : " ===== Header file for compressed data =====") << std::endl;
     h << " Coder version: " << kCoderVersion << std::endl;
     h << " Encoded data file name: " << wrb_name << std::endl;
     h << " File type (0: Fortran sequential w 4-byte recl; 1: Fortran sequential w 8-byte recl; 2: C/C++): "

@@ -59,8 +59,9 @@ void append_raw_field(const std::string& path, int nbytes, const double* fld, si
 void read_raw_field(std::istream& in, int nbytes, double* fld, size_t n);
 
 // .wrh text (gen_enc.cpp:509-520, gen_aux.cpp:505-556, 559-644, gen_dec.cpp:160-168)
+// segmented: the coded fields are not the reference's plane streams; the first line (which no reader parses) says so
 void write_header_preamble(const std::string& path, const std::string& wrb_name, int file_type,
-                           bool flip_endian, int nf);
+                           bool flip_endian, int nf, bool segmented = false);
 // `reminder_ntot_enc` reproduces quirk Q2: the reference tests the ntot_enc
 // variable of the PREVIOUS field when the current one is not compressed.
 void append_field_header(const std::string& path, int id, const FieldHeader& h, unsigned long reminder_ntot_enc);

@@ -2,9 +2,23 @@
 //
 // Same command line, prompts and output files as the reference's generic decoder
 // (src/generic/gen_dec.cpp):   wrdec ENCODED_FILE HEADER_FILE EXTRACTED_FILE TYPE ENDIANFLIP
+// A full decode needs no option: every coded field is whatever its bytes say, field by field -- the reference's plane streams go
+// through the drop-in decoders, a segmented stream through wr_decode_host_seg on a context of the tool's, so that a damaged
+// stream ends the tool with a message and exit status 1 (the drop-in decoders, void + fatal, abort the process).
+// Arguments that start with "--" are options of this tool, taken out before the arguments are counted.  They select a PARTIAL
+// decode of fields coded as segmented streams (waverange_amd.h: low-resolution and region decode):
+//   --level=R               the low-pass box of level R (0..4, default 0: the field's own resolution)
+//   --roi=x0:x1,y0:y1,z0:z1 a half-open box in the coordinates of the box of level R, in the order NX NY NZ (default: all of it);
+//                           a field with nh > 1 is addressed as the array it was coded as, z in [0, nz*nh)
+//   --planes=P              the first P quantizer planes only (default 0: all)
+//   --field=K               field K only (default: every field)
+// Any of --level > 0, --roi, --planes selects the partial path.  The output file then holds one record per selected field: the
+// region's elements, x fastest, in the field's precision, with record markers for the region's byte count; the header's
+// dimension inversion (idinv) is not applied.  The coded bytes are mapped, not read: only what the region needs is touched.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <future>
 #include <memory>
@@ -17,18 +31,140 @@
 #include "../../../include/waverange_amd.h"
 #include "batch.h"
 #include "gen_io.h"
+#include "segfmt.h"
 
 using std::cout;
 using std::endl;
 using std::string;
 
-int main(int argc, char** argv)
+namespace {
+
+struct Partial {
+    int level = 0, planes = 0, field = -1;
+    bool have_roi = false, have_planes = false;
+    wr_box roi{0, 0, 0, 0, 0, 0};
+    bool selected() const { return level > 0 || have_roi || have_planes; }
+};
+
+void usage()
 {
-    string in_name = "data.wrb", header_name = "data.wrh", out_name = "datarec.bin";
-    int file_type = 0, flip = 0;
     cout << "usage: ./wrdec ENCODED_FILE HEADER_FILE EXTRACTED_FILE TYPE ENDIANFLIP\n";
     cout << "where TYPE=(0: Fortran sequential w 4-byte recl; 1: Fortran sequential w 8-byte recl; 2: C/C++) and ENDIANFLIP=(0:no; 1:yes)\n";
     cout << "interactive mode if not enough arguments are passed.\n";
+}
+
+void usage_options()
+{
+    cout << "options (partial decode of segmented streams): --level=R (0..4) --roi=x0:x1,y0:y1,z0:z1 --planes=P --field=K\n";
+}
+
+// The partial path: one record per selected field.  Returns the exit status: 0, or 1 if any selected field was refused (a
+// message names it and nothing is written for it).
+int partial_decode(const Partial& pd, const string& in_name, const string& header_name, const string& out_name, int file_type, bool flip)
+{
+    std::ifstream fheader(header_name);
+    if (!fheader.is_open()) { cout << "Cannot open " << header_name << endl; return 1; }
+    const int nf = wrio::read_header_preamble(fheader);
+    wrcli::MappedFile wrb;
+    if (!wrb.open(in_name)) { cout << "Cannot open " << in_name << endl; return 1; }
+    if (pd.field >= nf) { cout << "Error: field " << pd.field << " is not in the file (" << nf << " fields)" << endl; return 1; }
+    wrcli::ContextPool contexts;
+    wr_ctx* ctx = nullptr;
+    int status = 0;
+    bool first = true;
+    size_t at = 0;  // of the field's bytes in the .wrb
+    for (int it = 0; it < nf; it++) {
+        wrio::FieldHeader h;
+        try { wrio::read_field_header(fheader, it, h); } catch (...) { status = 1; break; }
+        const wrio::FieldSpec& s = h.spec;
+        const size_t here = at, len = s.icomp ? (size_t)h.ntot_enc : s.count() * (size_t)s.nbytes;
+        at += len;
+        if (here + len > wrb.size()) { cout << "Error: field " << it << ": " << in_name << " is shorter than its header says" << endl; status = 1; break; }
+        if (pd.field >= 0 && it != pd.field) continue;
+        auto refuse = [&](const string& why) { cout << "Error: field " << it << ": " << why << endl; status = 1; };
+        if (!s.icomp) { refuse("stored uncompressed (icomp = 0): there is no partial decode of it"); continue; }
+        static const unsigned char kNoBytes[4] = {0, 0, 0, 0};
+        const unsigned char* data = len ? wrb.data() + here : kNoBytes;  // (a constant field has no coded bytes)
+        if (len > 0 && (len < 4 || wr_stream_sniff(data, len) < 1)) { refuse("not a segmented stream: the reference's plane streams decode only as a whole"); continue; }
+        const int nx = s.nx, ny = s.ny, nz = s.nz * s.nh;  // nh > 1 folds into z, as it was coded
+        if (len > 0 && pd.level > (int)h.wlev) { refuse("level " + std::to_string(pd.level) + " is above the stream's " + std::to_string(h.wlev) + " transform levels"); continue; }
+        int bx = 0, by = 0, bz = 0;
+        if (wr_lowres_dims(nx, ny, nz, pd.level, &bx, &by, &bz) != 0) { refuse(wr_last_error()); continue; }
+        wr_box box{0, 0, 0, bx, by, bz};
+        if (pd.have_roi) {
+            box = pd.roi;
+            if (box.x0 >= box.x1 || box.y0 >= box.y1 || box.z0 >= box.z1 || box.x1 > bx || box.y1 > by || box.z1 > bz) {
+                refuse("the region is empty or outside the box of level " + std::to_string(pd.level) + ", " + std::to_string(bx) + " x " + std::to_string(by) + " x " + std::to_string(bz));
+                continue;
+            }
+        }
+        if (pd.planes > (int)h.nlay) { refuse(std::to_string(pd.planes) + " planes asked, the stream has " + std::to_string(h.nlay)); continue; }
+        if (!ctx && !(ctx = contexts.borrow())) { cout << "Error: " << wr_last_error() << endl; return 1; }
+        wr_enc_info info;
+        memset(&info, 0, sizeof info);
+        info.tolabs = h.tolabs; info.midval = h.midval; info.halfspanval = h.halfspanval;
+        info.wlev = (unsigned char)h.wlev; info.nlay = (unsigned char)h.nlay; info.ntot_enc = h.ntot_enc;
+        for (unsigned l = 0; l < h.nlay; l++) { info.deps_vec[l] = h.deps_vec[l]; info.minval_vec[l] = h.minval_vec[l]; info.len_enc_vec[l] = h.len_enc_vec[l]; }
+        wrio::FieldSpec rs;  // the record that is written: the region as an array of its own
+        rs.nbytes = s.nbytes; rs.nx = box.x1 - box.x0; rs.ny = box.y1 - box.y0; rs.nz = box.z1 - box.z0; rs.nh = 1; rs.idinv = 0;
+        const size_t count = rs.count();
+        std::unique_ptr<double[]> out;
+        std::unique_ptr<float[]> out32;
+        int rc;
+        if (s.nbytes == 4) {
+            out32.reset(new float[count]);
+            rc = pd.have_roi ? wr_decode_host_seg_roi_f32(ctx, out32.get(), nx, ny, nz, pd.level, pd.planes, &box, &info, data, len, nullptr)
+                             : wr_decode_host_seg_lowres_f32(ctx, out32.get(), nx, ny, nz, pd.level, pd.planes, &info, data, len, nullptr);
+        } else {
+            out.reset(new double[count]);
+            rc = pd.have_roi ? wr_decode_host_seg_roi(ctx, out.get(), nx, ny, nz, pd.level, pd.planes, &box, &info, data, len, nullptr)
+                             : wr_decode_host_seg_lowres(ctx, out.get(), nx, ny, nz, pd.level, pd.planes, &info, data, len, nullptr);
+        }
+        if (rc != 0) { refuse(wr_last_error()); continue; }
+        cout << "  partial decode, field " << it << ": region [" << box.x0 << "," << box.x1 << ") x [" << box.y0 << "," << box.y1 << ") x [" << box.z0 << ","
+             << box.z1 << ") of the " << bx << " x " << by << " x " << bz << " box of level " << pd.level << ", ";
+        if (pd.planes) cout << pd.planes << " of " << h.nlay << " planes"; else cout << "all " << h.nlay << " planes";
+        cout << "; the order of the dimensions is not inverted (idinv is not applied to a partial output)" << endl;
+        unsigned char recl[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // record markers of the region's byte count, native byte order
+        const unsigned long long bytes = (unsigned long long)count * (unsigned long long)s.nbytes;
+        memcpy(recl, &bytes, 8);
+        if (out32) wrio::write_field(out_name, first, file_type, flip, rs, recl, out32.get());
+        else wrio::write_field(out_name, first, file_type, flip, rs, recl, out.get());
+        first = false;
+    }
+    if (ctx) contexts.give(ctx);
+    return status;
+}
+
+}  // namespace
+
+int main(int argc, char** argv)
+{
+    std::vector<string> options;
+    argc = wrcli::take_options(argc, argv, options);
+    Partial pd;
+    bool have_field = false;
+    for (const string& o : options) {
+        string v;
+        bool good;
+        if (wrcli::option_value(o, "level", &v)) good = wrcli::parse_uint(v, &pd.level) && pd.level <= 9;
+        else if (wrcli::option_value(o, "roi", &v)) good = pd.have_roi = wrcli::parse_roi(v, &pd.roi);
+        else if (wrcli::option_value(o, "planes", &v)) good = pd.have_planes = wrcli::parse_uint(v, &pd.planes);
+        else if (wrcli::option_value(o, "field", &v)) good = have_field = wrcli::parse_uint(v, &pd.field);
+        else { usage(); usage_options(); cout << "Error: unknown option " << o << endl; return 2; }
+        if (!good) { usage(); usage_options(); cout << "Error: " << o << " is not understood" << endl; return 2; }
+    }
+    if (have_field && !pd.selected()) { usage(); usage_options(); cout << "Error: --field selects fields of a partial decode: give --level, --roi or --planes with it" << endl; return 2; }
+    if (pd.selected() && !(wr_stream_sniff && wr_ctx_create && wr_ctx_destroy && wr_lowres_dims && wr_last_error && wr_decode_host_seg_lowres &&
+                           wr_decode_host_seg_lowres_f32 && wr_decode_host_seg_roi && wr_decode_host_seg_roi_f32)) {
+        usage(); usage_options();
+        cout << "Error: a partial decode is " << wrcli::kNotSupported << endl;
+        return 2;
+    }
+    wrcli::PhaseClock clock("wrdec");
+    string in_name = "data.wrb", header_name = "data.wrh", out_name = "datarec.bin";
+    int file_type = 0, flip = 0;
+    usage();
     if (argc == 6) {  // gen_dec.cpp:105-117
         cout << "automatic mode.";
         in_name = argv[1]; header_name = argv[2]; out_name = argv[3];
@@ -56,6 +192,11 @@ int main(int argc, char** argv)
         cout << "=== End of decompression ===\n";
         return 0;
     }
+    if (pd.selected()) {
+        const int status = partial_decode(pd, in_name, header_name, out_name, file_type, flip != 0);
+        cout << (status ? "=== decompression failed ===\n" : "=== End of decompression ===\n");
+        return status;
+    }
 
     std::ifstream fheader(header_name);
     if (!fheader.is_open()) { cout << "Cannot open " << header_name << endl; return 1; }
@@ -80,7 +221,12 @@ int main(int argc, char** argv)
         bool decoded = false;
         std::ostringstream log;
     };
+    wrcli::ContextPool contexts;  // for the segmented fields (declared before the items, whose futures wait for the calls that use it)
     std::vector<Item> items(nf);
+    auto report = [](std::exception_ptr e) {
+        try { if (e) std::rethrow_exception(e); } catch (const std::exception& x) { cout << "Error: " << x.what() << endl; } catch (...) {}
+        cout << "=== decompression failed ===\n";
+    };
     // the field sizes are only known record by record; the first record sizes the pipeline
     int depth = -1;
     wrcli::InFlight* gate = nullptr;
@@ -105,6 +251,7 @@ int main(int argc, char** argv)
         const size_t ntot = s.count();
         if (im.done.valid()) im.done.get();
         cout << im.log.str();
+        const double t_write = wrcli::PhaseClock::now();
         if (im.fld32) {
             wrio::write_field(out_name, it == 0, file_type, flip != 0, s, im.h.recl, im.fld32.get());
             cout << "  wrote: fld_1d_rec[0]=" << (double)im.fld32[0] << " fld_1d_rec[last]=" << (double)im.fld32[ntot - 1] << endl;
@@ -112,6 +259,7 @@ int main(int argc, char** argv)
             wrio::write_field(out_name, it == 0, file_type, flip != 0, s, im.h.recl, im.fld.get());
             cout << "  wrote: fld_1d_rec[0]=" << im.fld[0] << " fld_1d_rec[last]=" << im.fld[ntot - 1] << endl;
         }
+        clock.add(wrcli::PhaseClock::kWrite, t_write);
         im.fld.reset();
         im.fld32.reset();
         im.data_enc.release();
@@ -150,6 +298,7 @@ int main(int argc, char** argv)
         os << "  nx=" << s.nx << "  ny=" << s.ny << "  nz=" << s.nz << "  nh=" << s.nh;
         if (s.idinv) os << " and reordering" << endl; else os << endl;
         const size_t ntot = s.count();
+        const double t_read = wrcli::PhaseClock::now();
         if (f32_codec && s.nbytes == 4 && s.icomp && h.ntot_enc > 0) im.fld32.reset(new float[ntot]);
         else im.fld.reset(new double[ntot]);
         if (s.icomp) {
@@ -162,21 +311,40 @@ int main(int argc, char** argv)
         } else {
             wrio::read_raw_field(finput, s.nbytes, im.fld.get(), ntot);
         }
+        clock.add(wrcli::PhaseClock::kRead, t_read);
         im.decoded = s.icomp && h.ntot_enc > 0;
         if (im.decoded) os << "  decoding fld_1d_rec, field number " << it << endl;
         Item* ip = &im;
         const bool pipelined = depth > 0;
-        auto work = [ip, pipelined, &tail]() {
+        auto work = [ip, it, pipelined, &tail, &clock, &contexts]() {
             if (ip->decoded) {
+                const double t_codec = wrcli::PhaseClock::now();
                 wrio::FieldHeader& hh = ip->h;
                 const wrio::FieldSpec& sp = hh.spec;
                 unsigned char wlev = (unsigned char)hh.wlev, nlay = (unsigned char)hh.nlay;
-                if (ip->fld32)
+                if (wrcli::is_segmented(ip->data_enc.data(), hh.ntot_enc)) {
+                    const string who = "field " + std::to_string(it) + ": ";
+                    if (!(wr_decode_host_seg && wr_decode_host_seg_f32 && wr_ctx_create && wr_ctx_destroy && wr_last_error))
+                        throw std::runtime_error(who + "a segmented stream is " + wrcli::kNotSupported);
+                    wr_enc_info info;
+                    memset(&info, 0, sizeof info);
+                    info.tolabs = hh.tolabs; info.midval = hh.midval; info.halfspanval = hh.halfspanval;
+                    info.wlev = wlev; info.nlay = nlay; info.ntot_enc = hh.ntot_enc;
+                    for (unsigned l = 0; l < hh.nlay; l++) { info.deps_vec[l] = hh.deps_vec[l]; info.minval_vec[l] = hh.minval_vec[l]; info.len_enc_vec[l] = hh.len_enc_vec[l]; }
+                    wr_ctx* c = contexts.borrow();
+                    if (!c) throw std::runtime_error(who + wr_last_error());
+                    const int rc = ip->fld32 ? wr_decode_host_seg_f32(c, ip->fld32.get(), sp.nx, sp.ny, sp.nz * sp.nh, &info, ip->data_enc.data(), hh.ntot_enc, nullptr)
+                                             : wr_decode_host_seg(c, ip->fld.get(), sp.nx, sp.ny, sp.nz * sp.nh, &info, ip->data_enc.data(), hh.ntot_enc, nullptr);
+                    const string why = rc ? who + wr_last_error() : string();  // (this thread's message)
+                    contexts.give(c);
+                    if (rc) throw std::runtime_error(why);
+                } else if (ip->fld32)
                     wr_decoding_wrap_f32(sp.nx, sp.ny, sp.nz * sp.nh, ip->fld32.get(), &hh.tolabs, &hh.midval, &hh.halfspanval, &wlev,
                                          &nlay, &hh.ntot_enc, hh.deps_vec, hh.minval_vec, hh.len_enc_vec, ip->data_enc.data());
                 else
                     decoding_wrap(sp.nx, sp.ny, sp.nz * sp.nh, ip->fld.get(), &hh.tolabs, &hh.midval, &hh.halfspanval, &wlev, &nlay,
                                   &hh.ntot_enc, hh.deps_vec, hh.minval_vec, hh.len_enc_vec, ip->data_enc.data());
+                clock.add(wrcli::PhaseClock::kCodec, t_codec);
             }
             tail(*ip, pipelined ? static_cast<std::ostream&>(ip->log) : cout);
         };
@@ -184,13 +352,14 @@ int main(int argc, char** argv)
         else { work(); finish(it); }
     }
     } catch (...) {
+        const std::exception_ptr e = std::current_exception();
         if (gate) gate->abort();
         if (writer.joinable()) writer.join();
-        cout << "=== decompression failed ===\n";
+        report(writer_error ? writer_error : e);
         return 1;
     }
     if (writer.joinable()) writer.join();
-    if (writer_error) { cout << "=== decompression failed ===\n"; return 1; }
+    if (writer_error) { report(writer_error); return 1; }
     cout << "=== End of decompression ===\n";
     return 0;
 }

@@ -5,6 +5,9 @@
 //   wrenc INPUT_FILE ENCODED_FILE HEADER_FILE TYPE ENDIANFLIP NF PRECISION NX NY NZ TOLERANCE
 // Parameter sources in the reference's priority order (gen_enc.cpp:112-486): a file named
 // `inmeta` in the working directory, then 11 arguments, then interactive prompts.
+// Arguments that start with "--" are options of this tool and are taken out before any of that:
+//   --format=ref|wrs1|wrs2|wrs3[:seg=N][:brick=B][:strands=K]   the stream format of the coded fields (waverange_amd.h,
+//       wr_stream_format_parse); without it the library's setting decides (WR_STREAM_FORMAT, else the reference's stream)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -21,6 +24,7 @@
 #include "../../../include/waverange_amd.h"
 #include "batch.h"
 #include "gen_io.h"
+#include "segfmt.h"
 
 using std::cout;
 using std::endl;
@@ -178,6 +182,7 @@ void usage()
     cout << "      ENDIANFLIP=(0:no; 1:yes), NF=(how many fields, e.g. 1), PRECISION=(1:single; 2:double),\n";
     cout << "      NX=(e.g. 16), NY=(e.g. 16), NZ=(e.g. 16) and TOLERANCE=(e.g. 1.0e-16)\n";
     cout << "interactive mode if not enough arguments are passed.\n";
+    cout << "option: --format=ref|wrs1|wrs2|wrs3[:seg=N][:brick=B][:strands=K] (stream format of the coded fields; default: WR_STREAM_FORMAT, else ref)\n";
 }
 
 void parse_argv(char** argv, Job& job)  // gen_enc.cpp:365-412
@@ -227,6 +232,28 @@ void parse_interactive(Job& job)  // gen_enc.cpp:413-486
 
 int main(int argc, char** argv)
 {
+    // options first: nothing is read, created or truncated before they are known to be good
+    std::vector<string> options;
+    argc = wrcli::take_options(argc, argv, options);
+    string format_text;
+    bool have_format = false;
+    for (const string& o : options) {
+        if (wrcli::option_value(o, "format", &format_text)) { have_format = true; continue; }
+        usage();
+        cout << "Error: unknown option " << o << endl;
+        return 2;
+    }
+    int stream_format = 0;
+    {
+        string why;
+        if (!wrcli::choose_stream_format(have_format ? &format_text : nullptr, &stream_format, &why)) {
+            usage();
+            cout << "Error: " << why << endl;
+            return 2;
+        }
+    }
+    wrcli::PhaseClock clock("wrenc");
+
     Job job;
     std::ifstream meta("inmeta");
     if (!meta.fail()) {
@@ -250,7 +277,9 @@ int main(int argc, char** argv)
     if (job.flip) cout << "Convert big endian to little endian or vice versa" << endl;
     cout << "Number of fields in the file, nf: " << job.nf << endl;
 
-    wrio::write_header_preamble(job.header_name, job.out_name, job.file_type, job.flip != 0, job.nf);
+    // (a segmented file says so in the first line of its header, which every reader skips: for the person who feeds it to
+    // the reference's wrdec)
+    wrio::write_header_preamble(job.header_name, job.out_name, job.file_type, job.flip != 0, job.nf, stream_format != 0);
     { std::ofstream trunc(job.out_name, std::ios::binary | std::ios::out | std::ios::trunc); }
     if (job.file_type < 0 || job.file_type > 2) { cout << "Error: unknown file type" << endl; return 0; }
 
@@ -298,6 +327,7 @@ int main(int argc, char** argv)
         const wrio::FieldSpec& s = im.h.spec;
         if (im.done.valid()) im.done.get();
         cout << im.log.str();
+        const double t_write = wrcli::PhaseClock::now();
         if (s.icomp) {
             cout << "        tolabs=" << im.h.tolabs << endl;
             wrio::append_field_header(job.header_name, it, im.h, im.h.ntot_enc);
@@ -307,6 +337,7 @@ int main(int argc, char** argv)
             wrio::append_field_header(job.header_name, it, im.h, prev_ntot_enc);
             wrio::append_raw_field(job.out_name, s.nbytes, im.fld.data(), s.count());
         }
+        clock.add(wrcli::PhaseClock::kWrite, t_write);
         std::vector<double>().swap(im.fld);
         im.fld32.reset();
         im.data_enc.release();
@@ -331,12 +362,14 @@ int main(int argc, char** argv)
         os << "  contains " << s.nbytes << "-byte floating point data" << endl;
         os << "  nx=" << s.nx << "  ny=" << s.ny << "  nz=" << s.nz << "  nh=" << s.nh;
         if (s.idinv) os << " and reordering" << endl; else os << endl;
+        const double t_read = wrcli::PhaseClock::now();
         if (f32_codec && s.nbytes == 4 && s.icomp) {
             im.fld32.reset(new float[s.count()]);
             wrio::read_field(job.in_name, job.file_type, job.flip != 0, s, recl, &pos, im.fld32.get());
         } else {
             wrio::read_field(job.in_name, job.file_type, job.flip != 0, s, recl, &pos, im.fld);
         }
+        clock.add(wrcli::PhaseClock::kRead, t_read);
         if (depth == 0) scan(im, cout);
 
         im.h.spec = s;
@@ -348,13 +381,14 @@ int main(int argc, char** argv)
         }
         Item* ip = &im;
         const bool pipelined = depth > 0;
-        auto work = [ip, cutoff, pipelined, &scan]() {
+        auto work = [ip, cutoff, pipelined, &scan, &clock]() {
             const wrio::FieldSpec& sp = ip->h.spec;
             if (pipelined) scan(*ip, ip->log);
             if (!sp.icomp) { (pipelined ? static_cast<std::ostream&>(ip->log) : cout) << "  Compression disabled" << endl; return; }
             (pipelined ? static_cast<std::ostream&>(ip->log) : cout) << "  Compression enabled with base relative tolerance " << sp.tol_base << endl;
             unsigned char wlev = 0, nlay = 0;
             double cut = cutoff;
+            const double t_codec = wrcli::PhaseClock::now();
             // nh > 1 folds into z (gen_enc.cpp:559,596)
             if (ip->fld32)
                 wr_encoding_wrap_f32(sp.nx, sp.ny, sp.nz * sp.nh, ip->fld32.get(), 1, 1, 1, 1, &cut, &ip->h.tolabs, &ip->h.midval,
@@ -364,6 +398,7 @@ int main(int argc, char** argv)
                 encoding_wrap(sp.nx, sp.ny, sp.nz * sp.nh, ip->fld.data(), 1, 1, 1, 1, &cut, &ip->h.tolabs, &ip->h.midval,
                               &ip->h.halfspanval, &wlev, &nlay, &ip->h.ntot_enc, ip->h.deps_vec, ip->h.minval_vec,
                               ip->h.len_enc_vec, ip->data_enc.data());
+            clock.add(wrcli::PhaseClock::kCodec, t_codec);
             ip->h.wlev = wlev; ip->h.nlay = nlay;
         };
         if (depth > 0) { im.done = std::async(std::launch::async, work); gate.launched(it); }
