@@ -714,6 +714,49 @@ int wr_get_stream_format(int *format, unsigned *seg, unsigned *brick, unsigned *
 /* WR_FORMAT_* of a coded field's first bytes; -1: neither (fewer than four bytes of a magic, an unknown magic, no bytes) */
 int wr_stream_sniff(const unsigned char *data, size_t len);
 
+/* ---- Transcoding: a coded field from one of the four stream formats to another, on its planes.  No new format.
+ * A coded field is nlay planes of byte symbols plus its header record, and all four formats code the SAME planes under the same
+ * header scalars; only the bytes of every plane differ.  A transcode decodes the planes with the source format's decoder and
+ * codes them with the target's coder: no transform, no quantizer, no tolerance, and nothing is quantized a second time (a
+ * decode followed by an encode codes the RECONSTRUCTION, whose min / max and therefore plane scalars are its own).
+ *   source   whatever wr_stream_sniff says of the first plane; the planes of a stream must agree
+ *   target   format is one of WR_FORMAT_*; seg, brick, strands are normalised and refused as by wr_set_stream_format (0 = the
+ *            format's default, a parameter the format does not have must be 0).  All 16 pairs take the same path, same-format
+ *            pairs included (a new seg, brick or strand count; ref -> ref is a check of the stream)
+ *   result   *info_out is *info_in with only len_enc_vec and ntot_enc changed (info_out may be info_in); data_out is, byte for
+ *            byte, what the target format's encoder -- wr_encode_host, or wr_encode_host_seg / _seg_blocked / _seg_strands with
+ *            the same seg / brick / strands -- returns for the field the source stream was made from
+ *   trivial  a constant field (info_in->ntot_enc == 0) passes through: the header is copied, no device work
+ *   bound    wr_transcode_bound = nlay times the per-plane bound of the target (wr_range_encode_bound, wr_seg_bound,
+ *            wr_seg_bound_blocked, wr_seg_bound_strands); any cap that holds the bytes actually produced succeeds
+ *   len_in   bytes readable at data_in (0 = trust info_in->ntot_enc)
+ * Refusals, in this order; *info_out is written only on success, and the context keeps working after every one of them:
+ *   WR_ERR_ARG       null pointers, non-positive dimensions, a target the format setting refuses; then, for a field that is not
+ *                    trivial, nlay outside 1..WR_NLAYMAX, wlev not 0 or 4, null buffers, data_out[0, cap) overlapping the input
+ *   WR_ERR_STREAM    lengths that do not fit ntot_enc or len_in; first bytes that are no stream; planes that differ in format;
+ *                    for a segmented source every header and index as by wr_decode_host_seg -- all of this on the host, before
+ *                    anything is copied or launched; then a plane that does not decode (segments flagged by the kernels, or
+ *                    "stream does not decode to nx*ny*nz symbols" from the host decoder).  The message starts "plane <l>: "
+ *   WR_ERR_OVERFLOW  cap below the bytes produced, with the encoders' message
+ * wr_transcode_host runs on a context: a segmented side is decoded / coded by the GPU's segment coders (with the inverse /
+ * forward plane reorder of a blocked stream), a reference side by the host coder as in wr_decode_host / wr_encode_host -- the
+ * coder pool, per-plane threads or wr_set_threads groups -- through the planes' pinned windows, the block histograms counted on
+ * the device.  It takes no work-space slot; planes, blobs (the target's at their bound), one staging buffer and one stream-order
+ * plane come from the plane pool.  A wr_decode_begin pending on the context is discarded.
+ * wr_timings: plane_coder_s[l] is plane l's decoder time plus its coder time; `rangecoder` is the sum of the two halves' figures,
+ * each as its own driver defines it (host coder: the slowest plane; segment coders: the sum over the planes); h2d_ms the blobs
+ * or decoded windows going up, d2h_ms the histograms and windows or the blobs coming down; gpu the wall time of the kernel
+ * stages; transfer = total - rangecoder; the transform and quantizer fields stay 0.
+ * wr_transcode_host_ref is the definition on the calling thread (no context, no GPU): wr_range_decode / wr_range_encode and the
+ * wr_seg_*_host_ref* functions, plane by plane; the same refusals in the same order, the same bytes. */
+size_t wr_transcode_bound(size_t n, int nlay, int format, unsigned seg, unsigned brick, unsigned strands); /* host only; 0: refused */
+int wr_transcode_host(wr_ctx *ctx, int nx, int ny, int nz, const wr_enc_info *info_in, const unsigned char *data_in,
+                      size_t len_in, int format, unsigned seg, unsigned brick, unsigned strands, wr_enc_info *info_out,
+                      unsigned char *data_out, size_t cap, wr_timings *tm);
+int wr_transcode_host_ref(int nx, int ny, int nz, const wr_enc_info *info_in, const unsigned char *data_in, size_t len_in,
+                          int format, unsigned seg, unsigned brick, unsigned strands, wr_enc_info *info_out,
+                          unsigned char *data_out, size_t cap);
+
 /* encoding_wrap / decoding_wrap for fp32 fields: the same arguments but the field, an implicit context per call and
  * the reference's "void + fatal" errors.  fld_1d of an encode is never overwritten (no residual write-back). */
 void wr_encoding_wrap_f32(int nx, int ny, int nz, const float *fld_1d, int wtflag, int mx, int my, int mz,

@@ -252,6 +252,11 @@ def lib():
     L.wr_set_stream_format.argtypes = [C.c_int, C.c_uint, C.c_uint, C.c_uint]
     L.wr_get_stream_format.argtypes = [C.POINTER(C.c_int), _up, _up, _up]
     L.wr_stream_sniff.argtypes = [_vp, C.c_size_t]
+    L.wr_transcode_bound.restype = C.c_size_t
+    L.wr_transcode_bound.argtypes = [C.c_size_t, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_uint]
+    _tc = [C.c_int] * 3 + [C.POINTER(EncInfo), _vp, C.c_size_t, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.POINTER(EncInfo), _vp, C.c_size_t]
+    L.wr_transcode_host.argtypes = [_vp] + _tc + [C.POINTER(Timings)]
+    L.wr_transcode_host_ref.argtypes = _tc
     _lib = L
     return L
 
@@ -848,6 +853,41 @@ def stream_sniff(buf):
     return int(lib().wr_stream_sniff(b.ctypes.data if b.size else None, b.size))
 
 
+def _format_args(format):
+    """(format, seg, brick, strands) of a format text, or of such a tuple as it stands (0 = the format's default)"""
+    return stream_format_parse(format) if isinstance(format, str) else tuple(int(v) for v in format)
+
+
+def transcode_bound(n, nlay, format):
+    """Bytes that hold any transcode of nlay planes of n symbols into `format` (text, or a (format, seg, brick, strands) tuple):
+    nlay times the per-plane bound of the target; 0 if an argument is refused."""
+    return int(lib().wr_transcode_bound(n, nlay, *_format_args(format)))
+
+
+def _transcode(call, shape, info, data, format, cap, out=None):
+    nz, ny, nx = shape
+    fmt = _format_args(format)
+    src = np.ascontiguousarray(data, dtype=np.uint8).ravel()
+    i_in, i_out = EncInfo.from_dict(info), EncInfo()
+    if cap is None:
+        cap = out.size if out is not None else transcode_bound(nx * ny * nz, i_in.nlay, fmt)
+    if out is None:
+        out = np.empty(max(int(cap), 1), dtype=np.uint8)
+    assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.size >= cap
+    _check(call(nx, ny, nz, C.byref(i_in), src.ctypes.data if src.size else None, src.size, *fmt, C.byref(i_out), out.ctypes.data, int(cap)))
+    d = i_out.as_dict()
+    d["data"] = out[:i_out.ntot_enc]
+    return d["data"], d
+
+
+def transcode_host_ref(shape, info, data, format, cap=None, out=None):
+    """The definition of Context.transcode on the calling thread (no context, no GPU): the coded field `data` with the header
+    record `info` (the dict an encode returns; its "data" entry is not looked at) of a field shaped (nz, ny, nx), in the stream
+    format `format`.  Returns (data_out, info_out); info_out is info with the new lengths and carries data_out as "data".  cap: the
+    bytes the output may take (default: transcode_bound); out: a uint8 array to code into (e.g. a pinned one)."""
+    return _transcode(lib().wr_transcode_host_ref, shape, info, data, format, cap, out)
+
+
 def waveletcdf97_3d(x, lvl):
     y = np.ascontiguousarray(x, dtype=np.float64).copy()
     nz, ny, nx = y.shape
@@ -1425,6 +1465,20 @@ class Context:
         finally:
             for d in d_blob + d_sym:
                 d.free()
+
+    def transcode(self, info, data, format="wrs3", shape=None, cap=None, timings=None, out=None):
+        """The coded field `data` with the header record `info` from whatever format it is in to `format` ("ref" | "wrs1" |
+        "wrs2" | "wrs3" [":seg=N"] [":brick=B"] [":strands=K"]) on its planes: no transform, no quantizer, byte for byte what
+        the target's encoder returns for the original field.  shape: (nz, ny, nx) of the field (or info["shape"]).  Returns
+        (data_out, info_out) as transcode_host_ref; timings: a dict that receives the call's wr_timings."""
+        if shape is None:
+            shape = info["shape"]
+        tm = Timings()
+        h = self.h
+        r = _transcode(lambda *a: lib().wr_transcode_host(h, *a, C.byref(tm)), shape, info, data, format, cap, out)
+        if timings is not None:
+            timings.update(tm.as_dict())
+        return r
 
     def decode_begin(self, shape, enc):
         """Host half of a decode (range decoding into the context's staging); no output buffer needed yet."""

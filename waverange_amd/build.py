@@ -20,6 +20,8 @@ SOURCES = ["wr_kernels.hip", "wr_fused.hip", "wr_segcoder.hip", "wr_segbatch.hip
 # per-file extra flags: the AVX-512 coder loop is only entered when the CPU has the instructions (vec_available)
 EXTRA = {"wr_rangecoder_avx512.cpp": ["-mavx512f", "-mavx512bw", "-mavx512dq", "-mavx512vl"]}
 CLI = {"wrenc": ["cli/wrenc.cpp", "cli/gen_io.cpp"], "wrdec": ["cli/wrdec.cpp", "cli/gen_io.cpp"],
+       # .wrh/.wrb container from one stream format to another (wr_transcode_host)
+       "wrconv": ["cli/wrconv.cpp", "cli/gen_io.cpp"],
        # MSSG front-end (GrADS regular output, restart sets united / divided)
        "wrenc_mssg": ["cli/mssg_enc.cpp", "cli/mssg_io.cpp"], "wrdec_mssg": ["cli/mssg_dec.cpp", "cli/mssg_io.cpp"]}
 # FluSI HDF5 front-end (libhdf5 is looked up at run time: HDF5_ROOT, the default path, /opt/conda)

@@ -11,6 +11,7 @@
 #include "wr_roi.h"
 #include "wr_segbatch.h"
 #include "wr_segcoder.h"
+#include "wr_transcode.h"
 
 using namespace wri;
 
@@ -1356,16 +1357,8 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
 int seg_check_planes(const unsigned char* data_enc, const size_t* off, const wr_enc_info* info, int nlay, size_t n, uint32_t* seg, uint32_t* nseg,
                      uint32_t* brick, uint32_t* strands)
 {
-    *brick = 0; *strands = 0;
-    for (int l = 0; l < nlay; l++) {
-        uint32_t b = 0, K = 0;
-        if (const char* why = wrseg::check_index(data_enc + off[l], info->len_enc_vec[l], info->len_enc_vec[l], n, &seg[l], &nseg[l], &b, &K))
-            return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + why);
-        if (l == 0) { *brick = b; *strands = K; }
-        else if (K != *strands) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": the planes of the stream differ in format or in their strand count");
-        else if ((b != 0) != (*brick != 0)) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": the stream mixes WRS1 and WRS2 planes");
-        else if (b != *brick) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": the planes of the stream differ in their brick edge");
-    }
+    std::string why;
+    if (!wrtc::check_planes(data_enc, off, info, nlay, n, seg, nseg, brick, strands, &why)) return fail(WR_ERR_STREAM, why);
     return WR_OK;
 }
 
@@ -1691,6 +1684,317 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     return WR_OK;
 }
 
+// ---- transcoding: the planes of a coded field from one stream format to another (include/waverange_amd.h, wr_transcode.h)
+// No transform, no quantizer, no work-space slot: the source's decoder fills the context's device planes, the target's coder
+// reads them.  The halves are the drivers' above -- the host half of decode_impl or the coder stage of decode_seg_impl, then
+// the coder stage of encode_seg_impl or the placement and hand-over of encode_impl -- with every plane ready at once.
+//
+// A plane's second role.  A plane that the host coder touches lives behind a ring of pinned windows that plane_prepare arms
+// for ONE direction.  Here a plane may be written through upload windows (a reference source) or by a decoder kernel (a
+// segmented source) and then read through download windows (a reference target).  The second plane_prepare(decode = false)
+// keeps the plane's storage only if the layout it wants is the layout the plane has, so a plane that will be read through
+// windows is laid out for windows when it is first prepared, whoever fills it.  It is re-armed only when nothing is in
+// flight on it: a host decoder has waited for its last upload inside its end-of-stream request, a decoder kernel is behind a
+// stream synchronisation.  The re-arming starts a new generation (wr_handover.h), resets the ring, and lets the encoder
+// drain the plane chunk by chunk as it does after a quantizer.
+int transcode_impl(wr_ctx* c, int nx, int ny, int nz, const wr_enc_info* info_in, const unsigned char* data_in, size_t len_in, int format, unsigned seg_t,
+                   unsigned brick_t, unsigned strands_t, wr_enc_info* info_out, unsigned char* data_out, size_t cap, wr_timings* tm)
+{
+    if (!c) return fail(WR_ERR_ARG, "null context");
+    wrtc::Source s;
+    {
+        std::string why;
+        if (int rc = wrtc::validate(nx, ny, nz, info_in, data_in, len_in, format, seg_t, brick_t, strands_t, info_out, data_out, cap, &s, &why)) return fail(rc, why);
+    }
+    if (int rc = ctx_bind(c)) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    ActiveCall active(c->pool);
+    if (tm) wrdma::enable_timing();
+    const double t0 = now();
+    wr_timings local; memset(&local, 0, sizeof local);
+    c->pend_valid = false;  // planes a wr_decode_begin parked in this context do not survive a transcode on it
+    PlaneHold planes(c);
+    SegBufs sbufs(c), tbufs(c);  // the source's blobs and decoder tables; the target's blobs, staging (or histograms) and the stream-order plane
+    if (s.trivial) {  // the header is the field
+        const wr_enc_info keep = *info_in;
+        *info_out = keep;
+        local.total = now() - t0;
+        if (tm) *tm = local;
+        return WR_OK;
+    }
+    const size_t n = s.n;
+    const int nlay = s.nlay;
+    const wrtc::StreamFormat& t = s.target;
+    const bool ref_target = t.format == WR_FORMAT_REF;
+    DevPool* const pool = c->pool;
+    const int dev = c->device;
+    double gpu_s = 0;
+    if ((s.brick || (!ref_target && t.brick)) && !tbufs.perm.p) {  // one plane in stream order, for both halves in turn
+        tbufs.perm = plane_scratch(c, n);
+        if (!tbufs.perm.p) return WR_ERR_HIP;
+    }
+
+    // ---- source half: the planes into c->ps[l]
+    if (s.format == WR_FORMAT_REF) {
+        // the host half of decode_impl: admission gate, one decode at a time gathers its planes, the pool or this call's threads
+        if (verbose()) printf("Range decoding...\n");
+        std::unique_lock<std::mutex> gate(pool->planes.gate_mu, std::defer_lock);
+        if (wrrc::pool_threads() > 0) {
+            gate.lock();
+            const double t_gate = now();
+            for (;;) {
+                int qs = 0, qv = 0;
+                wrrc::pool_queued_decode(&qs, &qv);
+                if ((qs < kGateScalarJobs && qv < kGateVectorJobs) || now() - t_gate > 120.0) break;
+                std::this_thread::sleep_for(std::chrono::milliseconds(2));
+            }
+            g_stat[WR_STAT_DECODE_GATE_MS] += (unsigned long)((now() - t_gate) * 1e3);
+        }
+        {
+            const double t_turn = now();
+            std::lock_guard<std::mutex> gather(pool->planes.gather_mu);
+            const double t_got = now();
+            if (t_got - t_turn > 1e-3) g_stat[WR_STAT_PLANE_WAIT_MS] += (unsigned long)((t_got - t_turn) * 1e3);
+            for (int l = 0; l < nlay; l++) if (int rc = plane_prepare(c, l, n, true)) return rc;
+        }
+        wrrc::PlaneJob jobs[WR_NLAYMAX];
+        for (int l = 0; l < nlay; l++) {
+            jobs[l].kind = wrrc::PlaneJob::kDecode;
+            jobs[l].src = data_in + s.off[l]; jobs[l].src_len = info_in->len_enc_vec[l]; jobs[l].io = &c->ps[l].io; jobs[l].n = n;
+        }
+        bool pooled = wrrc::pool_threads() > 0;
+        try {
+            if (pooled) {
+                wrrc::JobBatch batch;
+                const bool queued = wrrc::pool_submit(jobs, nlay, &batch);
+                if (gate.owns_lock()) gate.unlock();
+                if (queued) wrrc::pool_wait(&batch);
+                else pooled = false;  // the pool was stopped meanwhile
+            }
+            if (gate.owns_lock()) gate.unlock();
+            const int groups = pooled ? 0 : std::min(nlay, coder_threads());
+            Workers workers;
+            for (int g = 0; g < groups; g++)
+                workers.v.emplace_back([&, g]() {
+                    (void)hipSetDevice(dev);
+                    const int l0 = g * nlay / groups, l1 = (g + 1) * nlay / groups;
+                    wrrc::run_jobs(jobs + l0, l1 - l0);
+                });
+        } catch (const std::exception& e) {
+            return fail(WR_ERR_ARG, std::string("transcode: ") + e.what());
+        }
+        double slowest = 0;
+        for (int l = 0; l < nlay; l++) {
+            if (jobs[l].result != n) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": stream does not decode to nx*ny*nz symbols");
+            local.plane_coder_s[l] = jobs[l].seconds;
+            if (jobs[l].seconds > slowest) slowest = jobs[l].seconds;
+        }
+        local.rangecoder += slowest;
+        for (int l = 0; l < nlay; l++) {
+            if (c->ps[l].err) return fail(WR_ERR_HIP, "upload of plane " + std::to_string(l) + " failed");
+            local.h2d_ms += (float)c->ps[l].copy_ms;
+        }
+    } else {
+        // validation has passed (wrtc::validate): upload and coder stage of decode_seg_impl.  A plane the host encoder will read
+        // is laid out for its windows from the start.
+        wrblk::Order od{};
+        if (s.brick) od = wrblk::order_of(nx, ny, nz, (int)info_in->wlev, s.brick);
+        {
+            std::lock_guard<std::mutex> gather(pool->planes.gather_mu);
+            for (int l = 0; l < nlay; l++) {
+                if (int rc = plane_prepare(c, l, n, true, false, nullptr, nullptr, ref_target)) return rc;
+                sbufs.blob[l] = plane_scratch(c, info_in->len_enc_vec[l]);
+                sbufs.work[l] = plane_scratch(c, wrk::seg_decode_work_bytes(s.nseg[l]));
+                if (!sbufs.blob[l].p || !sbufs.work[l].p) return WR_ERR_HIP;
+                if (int rc = sbufs.events(l)) return rc;
+            }
+        }
+        for (int l = 0; l < nlay; l++) {
+            if (int rc = xfer_field(c, &c->x_field, sbufs.blob[l].p, data_in + s.off[l], info_in->len_enc_vec[l], kUp)) return rc;
+            local.h2d_ms += (float)c->x_field.ms;
+            if (int rc = seg_upload_offsets(c, data_in + s.off[l], s.nseg[l], sbufs.work[l].p, s.brick, s.strands)) return rc;
+        }
+        const double t_stage = now();
+        StageLock cu(pool->cu_mu);
+        clock_warmup(c, n);
+        for (int l = 0; l < nlay; l++) {
+            const wrk::PlaneRef& q = c->ps[l].ref;
+            if (!wrk::plane_ref_covers(q, n)) return fail(WR_ERR_HIP, "internal: the device buffer of plane " + std::to_string(l) + " has a hole");
+            launch_note(c, "seg_decode", l, sbufs.blob[l].p, n, sbufs.work[l].p, q);
+            HIPCHK(hipEventRecord(sbufs.ev[2 * l], c->stream));
+            wrk::seg_decode(sbufs.blob[l].p, info_in->len_enc_vec[l], s.brick ? wrk::plane_ref(tbufs.perm.p) : q, n, s.seg[l], sbufs.work[l].p, c->stream, s.brick,
+                            s.strands);
+            if (s.brick && !wrk::plane_reorder(q, tbufs.perm.p, od, true, nullptr, 0, c->stream)) return fail(WR_ERR_ARG, "too many bricks");
+            HIPCHK(hipEventRecord(sbufs.ev[2 * l + 1], c->stream));
+        }
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented decoder launch failed" + launch_describe(c));
+        // the target's coder only runs on planes whose every segment decoded
+        unsigned int bad[WR_NLAYMAX] = {0};
+        for (int l = 0; l < nlay; l++) HIPCHK(hipMemcpyAsync(&bad[l], sbufs.work[l].p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the segmented decoder failed on the device" + launch_describe(c));
+        pool->last_stage_end.store(now());
+        for (int l = 0; l < nlay; l++) {
+            if (bad[l]) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + std::to_string(bad[l]) + " segment(s) do not decode to their symbols");
+            local.plane_coder_s[l] = sbufs.seconds(l);
+            local.rangecoder += local.plane_coder_s[l];
+        }
+        gpu_s += now() - t_stage;
+    }
+
+    // ---- target half
+    size_t lens[WR_NLAYMAX] = {0};
+    if (!ref_target) {
+        // per plane the body of encode_seg_impl's after_quant, then its "down" stage
+        const size_t blob_cap = (wrtc::plane_bound(n, t) + 15) & ~(size_t)15;
+        wrblk::Order od{};
+        if (t.brick) od = wrblk::order_of(nx, ny, nz, (int)info_in->wlev, t.brick);
+        tbufs.stage = plane_scratch(c, t.strands ? wrk::strand_stage_bytes(n, t.seg, t.strands) : wrk::seg_stage_bytes(n, t.seg));
+        if (!tbufs.stage.p) return WR_ERR_HIP;
+        for (int l = 0; l < nlay; l++) {
+            tbufs.blob[l] = plane_scratch(c, blob_cap);
+            if (!tbufs.blob[l].p) return WR_ERR_HIP;
+            if (int rc = tbufs.events(l)) return rc;
+        }
+        const double t_stage = now();
+        {
+            StageLock cu(pool->cu_mu);
+            for (int l = 0; l < nlay; l++) {
+                launch_note(c, "seg_encode", l, tbufs.blob[l].p, n, tbufs.stage.p, c->ps[l].ref);
+                HIPCHK(hipEventRecord(tbufs.ev[2 * l], c->stream));
+                wrk::PlaneRef sym = c->ps[l].ref;
+                if (t.brick) {
+                    if (!wrk::plane_reorder(sym, tbufs.perm.p, od, false, nullptr, 0, c->stream)) return fail(WR_ERR_ARG, "too many bricks");
+                    sym = wrk::plane_ref(tbufs.perm.p);
+                }
+                if (t.strands) wrk::strand_encode(sym, n, t.seg, t.strands, t.brick, tbufs.stage.p, tbufs.blob[l].p, blob_cap, seg_result_dev(c, l), c->stream);
+                else wrk::seg_encode(sym, n, t.seg, tbufs.stage.p, tbufs.blob[l].p, blob_cap, seg_result_dev(c, l), c->stream, t.brick);
+                HIPCHK(hipEventRecord(tbufs.ev[2 * l + 1], c->stream));
+                if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented coder launch failed" + launch_describe(c));
+            }
+            if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the segmented coder failed on the device" + launch_describe(c));
+            pool->last_stage_end.store(now());
+        }
+        size_t total = 0;
+        for (int l = 0; l < nlay; l++) {
+            const unsigned long long len = seg_result_host(c, l)[0], bad = seg_result_host(c, l)[1];
+            if (bad || len > blob_cap) return fail(WR_ERR_HIP, "internal: plane " + std::to_string(l) + ": a segment outgrew the segment bound");
+            lens[l] = len;
+            total += len;
+        }
+        if (total > cap) return fail(WR_ERR_OVERFLOW, wrtc::kTooLarge);
+        size_t at = 0;
+        for (int l = 0; l < nlay; l++) {
+            if (int rc = xfer_field(c, &c->x_field, data_out + at, tbufs.blob[l].p, lens[l], kDown)) return rc;
+            local.d2h_ms += (float)c->x_field.ms;
+            at += lens[l];
+            const double sec = tbufs.seconds(l);
+            local.plane_coder_s[l] += sec;
+            local.rangecoder += sec;
+        }
+        gpu_s += now() - t_stage;
+    } else {
+        // block histograms of every plane, then the placement, hand-over and concatenation of encode_impl with all planes ready
+        const size_t hist_per_plane = (n / wrrc::kBlock + 1) * 256;
+        if (int rc = ensure_host_hist(c, hist_per_plane * WR_NLAYMAX)) return rc;
+        tbufs.stage = plane_scratch(c, hist_per_plane * (size_t)nlay * sizeof(uint16_t));  // (the device histograms: a reference target stages nothing else)
+        if (!tbufs.stage.p) return WR_ERR_HIP;
+        uint16_t* const d_hist = reinterpret_cast<uint16_t*>(tbufs.stage.p);
+        const double t_stage = now();
+        {
+            StageLock cu(pool->cu_mu);
+            for (int l = 0; l < nlay; l++) {
+                launch_note(c, "hist", l, d_hist + l * hist_per_plane, n, nullptr, c->ps[l].ref);
+                wrk::block_histograms(c->ps[l].ref, n, d_hist + l * hist_per_plane, c->stream);
+            }
+            if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "histogram launch failed" + launch_describe(c));
+            if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the histogram stage failed on the device" + launch_describe(c));
+            pool->last_stage_end.store(now());
+        }
+        gpu_s += now() - t_stage;
+        for (int l = 0; l < nlay; l++) {
+            const Piece pc = {c->h_hist + l * hist_per_plane, d_hist + l * hist_per_plane, hist_per_plane * sizeof(uint16_t)};
+            if (int rc = xfer_start(c, &c->x_plane[l], &pc, 1, kDown)) { for (int k = 0; k < l; k++) (void)xfer_wait(&c->x_plane[k]); return rc; }
+        }
+        bool hist_failed = false;
+        for (int l = 0; l < nlay; l++) {
+            if (xfer_wait(&c->x_plane[l]) != WR_OK) hist_failed = true;
+            local.d2h_ms += (float)c->x_plane[l].ms;
+        }
+        if (hist_failed) return fail(WR_ERR_HIP, "download of the block histograms failed");
+        // the second role: the planes are complete and nothing is in flight on them (see above)
+        for (int l = 0; l < nlay; l++) {
+            if (int rc = plane_prepare(c, l, n, false)) return rc;
+            if (!wrk::plane_ref_covers(c->ps[l].ref, n)) return fail(WR_ERR_HIP, "internal: the device buffer of plane " + std::to_string(l) + " has a hole");
+        }
+        // where a plane's coder writes: at the sum of the histogram bounds of the planes before it, or -- under a cap that the
+        // bounds do not fit -- into the context's buffer of that plane (encode_impl)
+        size_t est_off[WR_NLAYMAX + 1] = {0}, est_len[WR_NLAYMAX] = {0};
+        bool direct[WR_NLAYMAX] = {false};
+        wrrc::PlaneJob jobs[WR_NLAYMAX];
+        for (int l = 0; l < nlay; l++) {
+            est_len[l] = wrrc::encode_bound_hist(c->h_hist + l * hist_per_plane, n);
+            est_off[l + 1] = est_off[l] + est_len[l];
+            direct[l] = est_off[l + 1] + wrrc::kFailedBlockSlack <= cap;
+            if (!direct[l]) if (int rc = ensure_enc_buf(c, l, est_len[l] + wrrc::kFailedBlockSlack)) return rc;
+            wrrc::PlaneJob& j = jobs[l];
+            j.kind = wrrc::PlaneJob::kEncode;
+            j.io = &c->ps[l].io; j.dst = direct[l] ? data_out + est_off[l] : c->enc_buf[l]; j.n = n; j.hist = c->h_hist + l * hist_per_plane; j.dst_limit = est_len[l];
+        }
+        for (int l = 0; l < nlay; l++) plane_prefetch(c, l);
+        try {
+            bool pooled = wrrc::pool_threads() > 0;
+            if (pooled) {
+                wrrc::JobBatch batch;
+                if (wrrc::pool_submit(jobs, nlay, &batch)) wrrc::pool_wait(&batch);
+                else pooled = false;
+            }
+            const int groups = pooled ? 0 : std::min(nlay, encoder_threads());
+            Workers workers;
+            for (int g = 0; g < groups; g++)
+                workers.v.emplace_back([&, g]() {
+                    (void)hipSetDevice(dev);
+                    const int l0 = g * nlay / groups, l1 = (g + 1) * nlay / groups;
+                    wrrc::run_jobs(jobs + l0, l1 - l0);
+                });
+        } catch (const std::exception& e) {
+            return fail(WR_ERR_ARG, std::string("transcode: ") + e.what());
+        }
+        double slowest = 0;
+        size_t total = 0, offs[WR_NLAYMAX] = {0};
+        for (int l = 0; l < nlay; l++) {
+            if (c->ps[l].err) return fail(WR_ERR_HIP, "download of plane " + std::to_string(l) + " failed");
+            if (jobs[l].result == (size_t)-1)
+                return fail(WR_ERR_HIP, "internal: the coder gave plane " + std::to_string(l) + " up (its block histograms are not its symbols')");
+            if (jobs[l].result > est_len[l]) return fail(WR_ERR_OVERFLOW, "internal: plane " + std::to_string(l) + " outgrew the bound computed from its histograms");
+            local.d2h_ms += (float)c->ps[l].copy_ms;
+            offs[l] = total;
+            lens[l] = jobs[l].result;
+            total += lens[l];
+            local.plane_coder_s[l] += jobs[l].seconds;
+            if (jobs[l].seconds > slowest) slowest = jobs[l].seconds;
+        }
+        local.rangecoder += slowest;
+        if (total > cap) return fail(WR_ERR_OVERFLOW, wrtc::kTooLarge);
+        // close the gaps, in plane order (encode_impl)
+        for (int l = 0; l < nlay; l++) {
+            if (!direct[l]) memcpy(data_out + offs[l], c->enc_buf[l], lens[l]);
+            else if (est_off[l] != offs[l]) memmove(data_out + offs[l], data_out + est_off[l], lens[l]);
+        }
+        for (int l = 0; l < nlay; l++) {
+            if (direct[l]) continue;
+            const uintptr_t a = ((uintptr_t)c->enc_buf[l] + 4095) & ~(uintptr_t)4095, e = ((uintptr_t)c->enc_buf[l] + lens[l]) & ~(uintptr_t)4095;
+            if (e > a && e - a >= ((size_t)64 << 20)) (void)madvise(reinterpret_cast<void*>(a), e - a, MADV_DONTNEED);
+        }
+    }
+    wrtc::finish_info(*info_in, lens, nlay, info_out);
+    local.total = now() - t0;
+    local.gpu = gpu_s;
+    local.transfer = local.total - local.rangecoder;  // uploads, downloads, placement and concatenation
+    if (local.transfer < 0) local.transfer = 0;
+    if (tm) *tm = local;
+    return WR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1888,6 +2192,12 @@ int wr_encode_device_seg_strands(wr_ctx* c, double* d_fld, int nx, int ny, int n
     FieldRef f; f.dev = d_fld;
     if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
     return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick, strands ? strands : WR_STRANDS_DEFAULT, info, data_enc, cap, tm);
+}
+
+int wr_transcode_host(wr_ctx* c, int nx, int ny, int nz, const wr_enc_info* info_in, const unsigned char* data_in, size_t len_in, int format, unsigned seg,
+                      unsigned brick, unsigned strands, wr_enc_info* info_out, unsigned char* data_out, size_t cap, wr_timings* tm)
+{
+    return transcode_impl(c, nx, ny, nz, info_in, data_in, len_in, format, seg, brick, strands, info_out, data_out, cap, tm);
 }
 
 int wr_dev_plane_reorder(wr_ctx* c, unsigned char* d_dst, const unsigned char* d_src, int nx, int ny, int nz, int wlev, unsigned brick, int inverse)

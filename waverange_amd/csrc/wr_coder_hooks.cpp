@@ -6,6 +6,7 @@
 #include "wr_lowres.h"
 #include "wr_roi.h"
 #include "wr_segcoder.h"
+#include "wr_transcode.h"
 
 using namespace wri;
 
@@ -156,41 +157,21 @@ size_t wr_seg_bound(size_t n, unsigned seg)
     return wrseg::kHeaderBytes + wrseg::seg_count(n, seg) * (4 + (size_t)wrseg::stream_bound(seg));
 }
 
-// the container around the symbols as they stand; brick != 0: the WRS2 header (the caller has permuted the symbols)
+// the containers (wr_transcode.h) with their failures made the thread's error
 static size_t seg_encode_ref(const unsigned char* sym, size_t n, unsigned seg, unsigned brick, unsigned char* blob)
 {
-    const size_t nseg = wrseg::seg_count(n, seg), head = wrseg::header_bytes(brick);
-    if (nseg > 0xffffffffu) { fail(WR_ERR_ARG, "too many segments"); return 0; }
-    memcpy(blob, brick ? wrseg::kMagicBlocked : wrseg::kMagic, 4);
-    wrseg::put_u32(blob + 4, seg);
-    wrseg::put_u32(blob + 8, (uint32_t)nseg);
-    if (brick) wrseg::put_u32(blob + 12, brick);
-    size_t at = head + 4 * nseg;
-    for (size_t k = 0; k < nseg; k++) {
-        const size_t base = k * seg;
-        const uint32_t bs = n - base < seg ? (uint32_t)(n - base) : seg;
-        const uint32_t len = wrseg::encode_segment_host(sym + base, bs, blob + at, wrseg::stream_bound(seg));
-        if (!len) { fail(WR_ERR_OVERFLOW, "internal: a segment outgrew the segment bound"); return 0; }
-        wrseg::put_u32(blob + head + 4 * k, len);
-        at += len;
-    }
-    return at;
+    int code = WR_OK;
+    std::string why;
+    const size_t len = wrtc::seg_encode_ref(sym, n, seg, brick, blob, &code, &why);
+    if (!len) fail(code, why);
+    return len;
 }
 
-// the symbols of a blob that check_index has passed, in the order they were coded in
 static int seg_decode_ref(const unsigned char* blob, size_t len, unsigned char* sym, size_t n, uint32_t seg, uint32_t nseg, uint32_t brick)
 {
-    const size_t head = wrseg::header_bytes(brick);
-    size_t at = head + 4 * (size_t)nseg;
-    for (uint32_t k = 0; k < nseg; k++) {
-        const size_t base = (size_t)k * seg;
-        const uint32_t bs = n - base < seg ? (uint32_t)(n - base) : seg;
-        const uint32_t l = wrseg::get_u32(blob + head + 4 * (size_t)k);
-        if (wrseg::decode_segment_host(blob + at, l, blob, blob + len, sym + base, bs) != wrseg::kSegOk)
-            return fail(WR_ERR_STREAM, "segmented plane: segment " + std::to_string(k) + " does not decode to its symbols");
-        at += l;
-    }
-    return WR_OK;
+    std::string why;
+    const int rc = wrtc::seg_decode_ref(blob, len, sym, n, seg, nseg, brick, &why);
+    return rc ? fail(rc, why) : WR_OK;
 }
 
 size_t wr_seg_encode_host_ref(const unsigned char* sym, size_t n, unsigned seg, unsigned char* blob)
@@ -254,41 +235,20 @@ size_t wr_seg_bound_strands(size_t n, unsigned seg, unsigned strands)
     return wrseg::kHeaderBytesStrands + wrseg::seg_count(n, seg) * (4 + (size_t)wrseg::record_bound(seg, strands));
 }
 
-// the WRS3 container around the symbols as they stand (the caller has permuted them if brick != 0)
 static size_t strands_encode_ref(const unsigned char* sym, size_t n, unsigned seg, unsigned brick, unsigned K, unsigned char* blob)
 {
-    const size_t nseg = wrseg::seg_count(n, seg), head = wrseg::kHeaderBytesStrands;
-    if (nseg > 0xffffffffu) { fail(WR_ERR_ARG, "too many segments"); return 0; }
-    memcpy(blob, wrseg::kMagicStrands, 4);
-    wrseg::put_u32(blob + 4, seg);
-    wrseg::put_u32(blob + 8, (uint32_t)nseg);
-    wrseg::put_u32(blob + 12, brick);
-    wrseg::put_u32(blob + 16, K);
-    size_t at = head + 4 * nseg;
-    for (size_t k = 0; k < nseg; k++) {
-        const size_t base = k * seg;
-        const uint32_t bs = n - base < seg ? (uint32_t)(n - base) : seg;
-        const uint32_t len = wrseg::encode_record_host(sym + base, bs, seg, K, blob + at, wrseg::record_bound(seg, K));
-        if (!len) { fail(WR_ERR_OVERFLOW, "internal: a record outgrew the record bound"); return 0; }
-        wrseg::put_u32(blob + head + 4 * k, len);
-        at += len;
-    }
-    return at;
+    int code = WR_OK;
+    std::string why;
+    const size_t len = wrtc::strands_encode_ref(sym, n, seg, brick, K, blob, &code, &why);
+    if (!len) fail(code, why);
+    return len;
 }
 
 static int strands_decode_ref(const unsigned char* blob, size_t len, unsigned char* sym, size_t n, uint32_t seg, uint32_t nseg, uint32_t K)
 {
-    const size_t head = wrseg::kHeaderBytesStrands;
-    size_t at = head + 4 * (size_t)nseg;
-    for (uint32_t k = 0; k < nseg; k++) {
-        const size_t base = (size_t)k * seg;
-        const uint32_t bs = n - base < seg ? (uint32_t)(n - base) : seg;
-        const uint32_t l = wrseg::get_u32(blob + head + 4 * (size_t)k);
-        if (wrseg::decode_record_host(blob + at, l, blob, blob + len, sym + base, bs, seg, K))
-            return fail(WR_ERR_STREAM, "segmented plane: segment " + std::to_string(k) + " does not decode to its symbols");
-        at += l;
-    }
-    return WR_OK;
+    std::string why;
+    const int rc = wrtc::strands_decode_ref(blob, len, sym, n, seg, nseg, K, &why);
+    return rc ? fail(rc, why) : WR_OK;
 }
 
 size_t wr_seg_encode_host_ref_strands(const unsigned char* sym, int nx, int ny, int nz, int wlev, unsigned brick, unsigned seg, unsigned strands,
@@ -329,6 +289,24 @@ int wr_seg_decode_host_ref_blocked(const unsigned char* blob, size_t len, unsign
     if (int rc = seg_decode_ref(blob, len, perm.data(), n, seg, nseg, brick)) return rc;
     wrblk::reorder_host(wrblk::order_of(nx, ny, nz, wlev, brick), perm.data(), sym, true);
     return WR_OK;
+}
+
+// ---- transcoding on the calling thread (wr_transcode.h): the definition of wr_transcode_host
+size_t wr_transcode_bound(size_t n, int nlay, int format, unsigned seg, unsigned brick, unsigned strands)
+{
+    wrtc::StreamFormat f;
+    f.format = format; f.seg = seg; f.brick = brick; f.strands = strands;
+    std::string why;
+    if (nlay < 0 || nlay > WR_NLAYMAX || !wrtc::format_normalise(&f, &why)) return 0;
+    return (size_t)nlay * wrtc::plane_bound(n, f);
+}
+
+int wr_transcode_host_ref(int nx, int ny, int nz, const wr_enc_info* info_in, const unsigned char* data_in, size_t len_in, int format, unsigned seg,
+                          unsigned brick, unsigned strands, wr_enc_info* info_out, unsigned char* data_out, size_t cap)
+{
+    std::string why;
+    const int rc = wrtc::transcode_ref(nx, ny, nz, info_in, data_in, len_in, format, seg, brick, strands, info_out, data_out, cap, &why);
+    return rc ? fail(rc, why) : WR_OK;
 }
 
 // ---- the geometry of a low-resolution decode (wr_lowres.h): host only, no device is touched

@@ -7,6 +7,7 @@
 #include "wr_blocked.h"
 #include "wr_internal.h"
 #include "wr_segcoder.h"
+#include "wr_transcode.h"
 
 using namespace wri;
 
@@ -45,37 +46,10 @@ struct ImplicitCtx {
     }
 };
 
-// ---- the stream format of the implicit-context encoders
-struct StreamFormat {
-    int format = WR_FORMAT_REF;
-    unsigned seg = 0, brick = 0, strands = 0;
-};
-
-const char* const kFormatNames[4] = {"ref", "wrs1", "wrs2", "wrs3"};
-
-// Fills in the defaults of the format and refuses what its encoder would refuse (and, for the reference's stream and for
-// WRS1, parameters the format does not have).  The message starts with the offending value as "key=value".
-bool format_normalise(StreamFormat* f, std::string* why)
-{
-    if (f->format < WR_FORMAT_REF || f->format > WR_FORMAT_WRS3) { *why = "format " + std::to_string(f->format) + " is not one of WR_FORMAT_REF .. WR_FORMAT_WRS3"; return false; }
-    const char* name = kFormatNames[f->format];
-    if (f->format == WR_FORMAT_REF) {
-        if (f->seg || f->brick || f->strands) { *why = std::string(name) + " takes no seg, brick or strands"; return false; }
-        return true;
-    }
-    if (!f->seg) f->seg = WR_SEG_DEFAULT;
-    if (!wrseg::seg_ok(f->seg)) { *why = "seg=" + std::to_string(f->seg) + ": segment length must be a multiple of 16 in [16, 59999]"; return false; }
-    if (f->format == WR_FORMAT_WRS1 && f->brick) { *why = "brick=" + std::to_string(f->brick) + ": wrs1 has no brick"; return false; }
-    if (f->format == WR_FORMAT_WRS2 && !f->brick) f->brick = WR_BRICK_DEFAULT;
-    if (f->brick && !wrblk::brick_ok(f->brick)) { *why = "brick=" + std::to_string(f->brick) + ": brick edge must be one of 8, 16, 32, 64"; return false; }
-    if (f->format != WR_FORMAT_WRS3) {
-        if (f->strands) { *why = "strands=" + std::to_string(f->strands) + ": only wrs3 has strands"; return false; }
-        return true;
-    }
-    if (!f->strands) f->strands = WR_STRANDS_DEFAULT;
-    if (!wrseg::strands_ok(f->strands, f->seg)) { *why = "strands=" + std::to_string(f->strands) + ": strands must be one of 1, 2, 4, 8, 16, 32 with 16 * strands <= seg"; return false; }
-    return true;
-}
+// ---- the stream format of the implicit-context encoders (its normalisation is shared with the transcoder: wr_transcode.h)
+using wrtc::StreamFormat;
+using wrtc::kFormatNames;
+using wrtc::format_normalise;
 
 // The grammar of include/waverange_amd.h: NAME[:seg=N][:brick=B][:strands=K], keys in any order, each at most once.
 bool format_parse(const char* text, StreamFormat* out, std::string* why)
@@ -148,12 +122,7 @@ StreamFormat format_or_fatal(const char* where)
     return f;
 }
 
-int sniff(const unsigned char* data, size_t len)
-{
-    if (!data || !len) return -1;
-    if (len >= 4 && data[0] == 'W' && data[1] == 'R' && data[2] == 'S' && data[3] >= '1' && data[3] <= '3') return data[3] - '0';
-    return data[0] == 0 ? WR_FORMAT_REF : -1;  // every plane of a reference stream starts with byte 0 (rangecod.c: start_encoding)
-}
+using wrtc::sniff;
 
 }  // namespace
 
