@@ -433,6 +433,21 @@ int wr_decode_device_seg_lowres(wr_ctx *ctx, double *d_out, int nx, int ny, int 
 typedef struct wr_box { int x0, y0, z0, x1, y1, z1; } wr_box;
 /* the window of a region, in the coordinates of the level's box; wlev is 0 or 4 (the stream's); host only */
 int wr_roi_window(int nx, int ny, int nz, int level, int wlev, const wr_box *roi, wr_box *win);
+/* which kernels a region decode runs (host only: no device call, no context; the refusals of wr_roi_window, and out == NULL:
+ * WR_ERR_ARG).  `inverse` = wlev - level levels are still to invert on the window `win`; `fused` says whether they run on the
+ * fused inverse (out of place, as wr_fused_plan's `used` for the window's extents, after the WR_NO_FUSED switch) and
+ * `fused_levels` how many of them it takes itself (0 when it does not run), the rest and every window with inverse < 4 run on
+ * the general kernels.  box[0, nbox) are the source boxes of the gather in launch order, x, y, z: len coefficients per axis
+ * from src of the field's array land at dst of the window; `wide`: the box is gathered 4 symbols at a time, otherwise byte by
+ * byte (planes and work space aligned as the library's own always are). */
+typedef struct wr_roi_plan_t {
+    wr_box win;
+    int inverse;
+    int fused, fused_levels;
+    int nbox;
+    struct { int src[3], dst[3], len[3]; int wide; } box[29];
+} wr_roi_plan_t;
+int wr_roi_plan(int nx, int ny, int nz, int level, int wlev, const wr_box *roi, wr_roi_plan_t *out);
 /* ascending ids of the segments a region needs; conventions of wr_seg_lowres_segments */
 size_t wr_seg_roi_segments(int nx, int ny, int nz, int level, int wlev, const wr_box *roi, unsigned seg, uint32_t *ids,
                            size_t cap);

@@ -74,6 +74,16 @@ class Box(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("x0", "y0", "z0", "x1", "y1", "z1")]
 
 
+class RoiPlanBox(C.Structure):
+    _fields_ = [("src", C.c_int * 3), ("dst", C.c_int * 3), ("len", C.c_int * 3), ("wide", C.c_int)]
+
+
+class RoiPlan(C.Structure):
+    """wr_roi_plan_t"""
+    _fields_ = [("win", Box), ("inverse", C.c_int), ("fused", C.c_int), ("fused_levels", C.c_int), ("nbox", C.c_int),
+                ("box", RoiPlanBox * 29)]
+
+
 class WaveRangeError(RuntimeError):
     pass
 
@@ -222,6 +232,7 @@ def lib():
     L.wr_decode_host_seg_lowres_f32.argtypes = L.wr_decode_host_seg_lowres.argtypes
     L.wr_decode_device_seg_lowres.argtypes = L.wr_decode_host_seg_lowres.argtypes
     L.wr_roi_window.argtypes = [C.c_int] * 5 + [C.POINTER(Box), C.POINTER(Box)]
+    L.wr_roi_plan.argtypes = [C.c_int] * 5 + [C.POINTER(Box), C.POINTER(RoiPlan)]
     L.wr_seg_roi_segments.restype = C.c_size_t
     L.wr_seg_roi_segments.argtypes = [C.c_int] * 5 + [C.POINTER(Box), C.c_uint, _vp, C.c_size_t]
     L.wr_dev_decode_planes_roi.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Box), _vp, C.POINTER(EncInfo)]
@@ -653,6 +664,18 @@ def roi_window(shape, level, roi, wlev=4):
     r, w = _box(roi), Box()
     _check(lib().wr_roi_window(nx, ny, nz, level, wlev, C.byref(r), C.byref(w)))
     return (w.z0, w.z1), (w.y0, w.y1), (w.x0, w.x1)
+
+
+def roi_plan(shape, level, roi, wlev=4):
+    """Which kernels a region decode of `roi` runs (wr_roi_plan; host only, needs no GPU): dict(box = lowres_shape(shape, level),
+    win = ((a, b) for z, y, x), inverse, fused, fused_levels, boxes), boxes = one dict(src, dst, len, wide) per source box of
+    the gather in launch order, src / dst / len as (x, y, z).  Arguments as roi_window."""
+    nz, ny, nx = shape
+    r, p = _box(roi), RoiPlan()
+    _check(lib().wr_roi_plan(nx, ny, nz, level, wlev, C.byref(r), C.byref(p)))
+    w = p.win
+    return dict(box=lowres_shape(shape, level), win=((w.z0, w.z1), (w.y0, w.y1), (w.x0, w.x1)), inverse=p.inverse, fused=bool(p.fused), fused_levels=p.fused_levels,
+                boxes=[dict(src=tuple(b.src), dst=tuple(b.dst), len=tuple(b.len), wide=bool(b.wide)) for b in p.box[:p.nbox]])
 
 
 def seg_roi_segments(shape, level, roi, seg=0, wlev=4):

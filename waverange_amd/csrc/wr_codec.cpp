@@ -327,7 +327,7 @@ struct LowresPlan {
 
     size_t out_elems() const { return roi ? win.out_elems() : box.elems(); }   // what the caller receives
     size_t work_elems() const { return roi ? win.elems() : box.elems(); }      // what the inverse runs on
-    bool fused() const { return roi && inverse == kWavLvl && use_fused(win.w(0), win.w(1), win.w(2), -kWavLvl); }
+    bool fused() const { return roi && use_fused_window(win.w(0), win.w(1), win.w(2), inverse); }
     // the ascending ids of the segments a plane cut at `seg` needs
     void segments(int nx, int ny, int nz, uint32_t seg, std::vector<uint32_t>* ids) const
     {
@@ -421,15 +421,7 @@ int roi_from_planes(wr_ctx* c, Slot* s, double* d_out, int nx, int ny, const Low
 {
     const wrroi::Geometry& g = pl.win;
     const int wx = g.w(0), wy = g.w(1), wz = g.w(2);
-    wrk::WindowMap m;
-    memset(&m, 0, sizeof m);
-    m.nbox = g.nbox;
-    m.wx = (uint32_t)wx; m.wy = (uint32_t)wy; m.nx = (uint32_t)nx; m.ny = (uint32_t)ny;
-    for (int i = 0; i < g.nbox; i++) {
-        const wrroi::SrcBox& b = g.box[i];
-        m.box[i] = wrk::WindowBox{(uint32_t)b.src[0], (uint32_t)b.src[1], (uint32_t)b.src[2], (uint32_t)b.dst[0], (uint32_t)b.dst[1], (uint32_t)b.dst[2],
-                                  (uint32_t)b.len[0], (uint32_t)b.len[1], (uint32_t)b.len[2]};
-    }
+    const wrk::WindowMap m = window_map_of(g, nx, ny);
     const bool fused = pl.fused();
     if (fused) if (const char* why = wrk::fused_prepare()) return fail(WR_ERR_HIP, why);
     HIPCHK(hipEventRecord(c->ev_a, c->stream));

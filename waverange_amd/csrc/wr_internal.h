@@ -30,6 +30,7 @@
 #include "wr_handover.h"
 #include "wr_kernels.h"
 #include "wr_rangecoder.h"
+#include "wr_roi.h"
 
 #pragma clang fp contract(off)
 
@@ -365,6 +366,11 @@ struct PlaneHold {
 };
 
 bool use_fused(int nx, int ny, int nz, int lvl);
+// a region decode (wr_roi.h): whether the inverse of a window of these extents, `inverse` levels deep, runs on the fused
+// kernels, and the gather of its coefficient array out of the planes of an nx * ny * nz field.  The region drivers and
+// wr_roi_plan both ask here.
+bool use_fused_window(int wx, int wy, int wz, int inverse);
+wrk::WindowMap window_map_of(const wrroi::Geometry& g, int nx, int ny);
 void transform_need(int nx, int ny, int nz, int lvl, SlotNeed* need);
 // f32 (forward on the fused path only): the field is that fp32 array, d_fld is n doubles of scratch (may be f32's memory)
 int run_transform(wr_ctx* c, Slot* s, double* d_fld, int nx, int ny, int nz, int lvl, double** out, const float* f32 = nullptr);

@@ -243,6 +243,14 @@ struct WindowMap {
     WindowBox box[kWindowBoxes];
 };
 void dequant_window(double* win, const WindowMap& m, const DequantParams& p, hipStream_t st);
+// Whether k_dequant_window gathers box x of the map 4 symbols at a time (one 4-byte load per plane, two 16-byte stores) or
+// byte by byte: a run's offsets in the plane and in the window and its length must be multiples of 4.  `aligned`: the window
+// array is 16-byte aligned and every plane chunk 4-byte aligned and a multiple of 4096 bytes long, which the library's own
+// slots and planes always are.  Host only; dequant_window and wr_roi_plan both decide here.
+inline bool window_box_wide(bool aligned, const WindowMap& m, const WindowBox& x)
+{
+    return aligned && m.nx % 4 == 0 && m.wx % 4 == 0 && x.sx % 4 == 0 && x.ox % 4 == 0 && x.lx % 4 == 0;
+}
 // out[(z*cy + y)*cx + x] = win[((z + oz)*wy + y + oy)*wx + x + ox] * s (one multiply, one rounding; s == 1: the bits as they
 // are), narrowed to fp32 as the C cast in the second form.  Not in place.
 struct CropBox { uint32_t wx, wy, ox, oy, oz, cx, cy, cz; };

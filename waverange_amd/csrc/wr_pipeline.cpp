@@ -676,6 +676,25 @@ bool use_fused(int nx, int ny, int nz, int lvl)
     return wrk::fused_ok(nx, ny, nz, lvl) && !getenv("WR_NO_FUSED");
 }
 
+bool use_fused_window(int wx, int wy, int wz, int inverse)
+{
+    return inverse == kWavLvl && use_fused(wx, wy, wz, -kWavLvl);
+}
+
+wrk::WindowMap window_map_of(const wrroi::Geometry& g, int nx, int ny)
+{
+    wrk::WindowMap m;
+    memset(&m, 0, sizeof m);
+    m.nbox = g.nbox;
+    m.wx = (uint32_t)g.w(0); m.wy = (uint32_t)g.w(1); m.nx = (uint32_t)nx; m.ny = (uint32_t)ny;
+    for (int i = 0; i < g.nbox; i++) {
+        const wrroi::SrcBox& b = g.box[i];
+        m.box[i] = wrk::WindowBox{(uint32_t)b.src[0], (uint32_t)b.src[1], (uint32_t)b.src[2], (uint32_t)b.dst[0], (uint32_t)b.dst[1], (uint32_t)b.dst[2],
+                                  (uint32_t)b.len[0], (uint32_t)b.len[1], (uint32_t)b.len[2]};
+    }
+    return m;
+}
+
 // work space a transform of this shape needs next to the field itself
 void transform_need(int nx, int ny, int nz, int lvl, SlotNeed* need)
 {
@@ -1079,6 +1098,27 @@ int wr_fused_plan(int nx, int ny, int nz, int inverse, wr_fused_plan_t* out)
     out->levels = wrk::fused_plan(nx, ny, nz, inverse != 0, g);
     out->used = wrk::fused_ok(nx, ny, nz, inverse ? -4 : 4);
     for (int l = 0; l < out->levels; l++) out->level[l] = {g[l].tiles_x, g[l].tiles_y, g[l].zps, g[l].zsegs, g[l].zlast};
+    return WR_OK;
+}
+
+int wr_roi_plan(int nx, int ny, int nz, int level, int wlev, const wr_box* roi, wr_roi_plan_t* out)
+{
+    if (!out) return fail(WR_ERR_ARG, "wr_roi_plan: out is NULL");
+    wr_box win;
+    if (int rc = wr_roi_window(nx, ny, nz, level, wlev, roi, &win)) return rc;
+    memset(out, 0, sizeof *out);
+    const wrroi::Geometry g = wrroi::geometry_of(wrlow::box_of(nx, ny, nz, level), wlev - level, *roi);
+    out->win = win;
+    out->inverse = g.d;
+    out->fused = use_fused_window(g.w(0), g.w(1), g.w(2), g.d);
+    out->fused_levels = out->fused ? wrk::fused_levels(g.w(0), g.w(1), g.w(2), true) : 0;
+    const wrk::WindowMap m = window_map_of(g, nx, ny);
+    out->nbox = m.nbox;
+    for (int i = 0; i < m.nbox; i++) {
+        const wrk::WindowBox& b = m.box[i];
+        out->box[i] = {{(int)b.sx, (int)b.sy, (int)b.sz}, {(int)b.ox, (int)b.oy, (int)b.oz}, {(int)b.lx, (int)b.ly, (int)b.lz},
+                       wrk::window_box_wide(true, m, b)};
+    }
     return WR_OK;
 }
 

@@ -105,7 +105,7 @@ void crop_scale(const double* win, T* out, const CropBox& c, double s, hipStream
 
 void dequant_window(double* win, const WindowMap& m, const DequantParams& p, hipStream_t st)
 {
-    bool aligned = m.nx % 4 == 0 && m.wx % 4 == 0 && ((uintptr_t)win & 15) == 0;
+    bool aligned = ((uintptr_t)win & 15) == 0;
     for (int l = 0; l < p.nlay; l++) {
         if (p.q[l].shift < 12) aligned = false;
         for (int k = 0; k < kPlaneChunks; k++) aligned = aligned && ((uintptr_t)p.q[l].chunk[k] & 3) == 0;
@@ -114,7 +114,7 @@ void dequant_window(double* win, const WindowMap& m, const DequantParams& p, hip
     memset(&it, 0, sizeof it);
     for (int b = 0; b < m.nbox; b++) {
         const WindowBox& x = m.box[b];
-        it.wide[b] = aligned && x.sx % 4 == 0 && x.ox % 4 == 0 && x.lx % 4 == 0;
+        it.wide[b] = window_box_wide(aligned, m, x);
         it.gpr[b] = it.wide[b] ? x.lx / 4 : x.lx;
         it.first[b + 1] = it.first[b] + (size_t)it.gpr[b] * x.ly * x.lz;
     }
