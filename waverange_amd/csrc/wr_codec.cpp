@@ -74,6 +74,56 @@ struct Cutoff {
     int count() const { return mx * my * mz; }
 };
 
+// where the field of an encode call comes from / the field of a decode call goes to
+struct FieldRef {
+    double* dev = nullptr;   // device-resident (caller's buffer), or
+    double* host = nullptr;  // host buffer (pinned or pageable): staged through the slot, or
+    float* host_f32 = nullptr;  // an fp32 host buffer: 4 bytes per sample cross the bus, widened / narrowed on the device
+    bool none() const { return !dev && !host && !host_f32; }
+};
+
+// a constant field (ntot_enc == 0, wrappers.cpp:462-469): `count` elements of midval wherever the caller's field is
+int fill_constant(wr_ctx* c, const FieldRef& fld, size_t count, double midval)
+{
+    if (fld.host) for (size_t j = 0; j < count; j++) fld.host[j] = midval;
+    else if (fld.host_f32) for (size_t j = 0; j < count; j++) fld.host_f32[j] = (float)midval;
+    else { wrk::fill(fld.dev, count, midval, c->stream); HIPCHK(hipStreamSynchronize(c->stream)); }
+    return WR_OK;
+}
+
+// off[0 .. nlay]: where every plane's stream starts in the coded buffer, by the header's lengths; they must fit into ntot_enc,
+// and that into the buffer (data_len == 0: its length is not known).  who: put in front of the messages ("field 3: ")
+int plane_offsets(const wr_enc_info* info, int nlay, size_t data_len, size_t* off, const std::string& who = std::string())
+{
+    off[0] = 0;
+    for (int l = 0; l < nlay; l++) off[l + 1] = off[l] + info->len_enc_vec[l];
+    if (off[nlay] > info->ntot_enc) return fail(WR_ERR_STREAM, who + "len_enc_vec exceeds ntot_enc");
+    if (data_len && info->ntot_enc > data_len) return fail(WR_ERR_STREAM, who + "ntot_enc exceeds the length of the coded buffer");
+    return WR_OK;
+}
+
+// q[l] := ref_of(l), the symbols of plane l, for the first `used` planes; every one of them must be whole before a kernel writes it
+template <class RefOf>
+int plane_refs(int used, size_t n, RefOf ref_of, wrk::PlaneRef* q)
+{
+    for (int l = 0; l < used; l++) {
+        q[l] = ref_of(l);
+        if (!wrk::plane_ref_covers(q[l], n)) return fail(WR_ERR_HIP, "internal: the device buffer of plane " + std::to_string(l) + " has a hole");
+    }
+    return WR_OK;
+}
+
+// What the dequantizer is told: the first `used` planes of the header, their symbols as plane_refs finds them.
+template <class RefOf>
+int dequant_params(const wr_enc_info* info, int used, size_t n, RefOf ref_of, wrk::DequantParams* p)
+{
+    memset(p, 0, sizeof *p);
+    p->nlay = used;
+    for (int l = 0; l < used; l++) { p->deps[l] = info->deps_vec[l]; p->minval[l] = info->minval_vec[l]; }
+    return plane_refs(used, n, ref_of, p->q);
+}
+
+
 // Kernel stage of the encoder (call with the slot leased and DevPool::cu_mu held).  Hooks for the full
 // pipeline: hist_buf(l) says where plane l's block histograms go on the device (nullptr: nobody wants them);
 // after_quant(l, hist_done) is called right after plane l's quantizer kernel and the read-back of the next
@@ -282,11 +332,7 @@ int wr_dev_decode_planes(wr_ctx* c, double* d_fld, int nx, int ny, int nz, const
     if (int rc = check_dims(nx, ny, nz, d_fld)) return rc;
     const size_t n = (size_t)nx * ny * nz;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (info->ntot_enc == 0 && info->nlay == 0) {  // trivial field, wrappers.cpp:462-469
-        wrk::fill(d_fld, n, info->midval, c->stream);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return WR_OK;
-    }
+    if (info->ntot_enc == 0 && info->nlay == 0) return fill_constant(c, FieldRef{d_fld}, n, info->midval);
     if (info->nlay > WR_NLAYMAX) return fail(WR_ERR_ARG, "nlay out of range");
     SlotNeed need;
     transform_need(nx, ny, nz, info->wlev ? -kWavLvl : 0, &need);
@@ -444,11 +490,7 @@ int decode_planes_plan(wr_ctx* c, double* d_out, int nx, int ny, int nz, const L
 {
     const size_t n = (size_t)nx * ny * nz;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (info->ntot_enc == 0 && info->nlay == 0) {  // a constant field, as wr_dev_decode_planes
-        wrk::fill(d_out, pl.out_elems(), info->midval, c->stream);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return WR_OK;
-    }
+    if (info->ntot_enc == 0 && info->nlay == 0) return fill_constant(c, FieldRef{d_out}, pl.out_elems(), info->midval);
     if (!d_planes) return fail(WR_ERR_ARG, "null plane pointer");
     SlotNeed need;
     pl.need(false, &need);
@@ -495,14 +537,6 @@ extern "C" int wr_dev_decode_planes_roi(wr_ctx* c, double* d_out, int nx, int ny
 }
 
 namespace {
-
-// where the field of an encode call comes from / the field of a decode call goes to
-struct FieldRef {
-    double* dev = nullptr;   // device-resident (caller's buffer), or
-    double* host = nullptr;  // host buffer (pinned or pageable): staged through the slot, or
-    float* host_f32 = nullptr;  // an fp32 host buffer: 4 bytes per sample cross the bus, widened / narrowed on the device
-    bool none() const { return !dev && !host && !host_f32; }
-};
 
 int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, const Cutoff& cut, wr_enc_info* info,
                 unsigned char* data_enc, size_t cap, wr_timings* tm)
@@ -803,9 +837,7 @@ int decode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_in
     if (mode == kDecodeBegin) { c->pend_info = *info; c->pend_nx = nx; c->pend_ny = ny; c->pend_nz = nz; }
     if (info->ntot_enc == 0) {  // wrappers.cpp:462-469
         if (mode == kDecodeBegin) { c->pend_tm = local; c->pend_valid = true; if (tm) *tm = local; return WR_OK; }
-        if (fld.host) for (size_t j = 0; j < n; j++) fld.host[j] = info->midval;
-        else if (fld.host_f32) for (size_t j = 0; j < n; j++) fld.host_f32[j] = (float)info->midval;
-        else { wrk::fill(fld.dev, n, info->midval, c->stream); HIPCHK(hipStreamSynchronize(c->stream)); }
+        if (int rc = fill_constant(c, fld, n, info->midval)) return rc;
         local.total += now() - t0;
         if (tm) *tm = local;
         return WR_OK;
@@ -816,9 +848,7 @@ int decode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_in
     const bool host_half = mode != kDecodeFinish, device_half = mode != kDecodeBegin;
     if (host_half && verbose()) printf("Range decoding...\n");
     size_t off[WR_NLAYMAX + 1] = {0};
-    for (int l = 0; l < nlay; l++) off[l + 1] = off[l] + info->len_enc_vec[l];
-    if (off[nlay] > info->ntot_enc) return fail(WR_ERR_STREAM, "len_enc_vec exceeds ntot_enc");
-    if (host_half && data_len && info->ntot_enc > data_len) return fail(WR_ERR_STREAM, "ntot_enc exceeds the length of the coded buffer");
+    if (int rc = plane_offsets(info, nlay, host_half ? data_len : 0, off)) return rc;
 
     // Admission to the coder pool.  A decoder's planes take device memory from the moment they are prepared, and with every
     // session of the pool full a decode's jobs sat in the queues for seconds (4 of a decode's 15 s at 32 lanes) -- a third of
@@ -923,12 +953,7 @@ int decode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_in
         if ((rc = slot.acquire(c, need)) != WR_OK) return rc;  // the planes are on the device already: no "up" stage
         t_phase = now();
         wrk::DequantParams p;
-        memset(&p, 0, sizeof p);
-        p.nlay = nlay;
-        for (int l = 0; l < nlay; l++) {
-            p.deps[l] = info->deps_vec[l]; p.minval[l] = info->minval_vec[l]; p.q[l] = c->ps[l].ref;
-            if (!wrk::plane_ref_covers(p.q[l], n)) return fail(WR_ERR_HIP, "internal: the device buffer of plane " + std::to_string(l) + " has a hole");
-        }
+        if ((rc = dequant_params(info, nlay, n, [&](int l) { return c->ps[l].ref; }, &p)) != WR_OK) return rc;
         launch_note(c, "dequant", nlay - 1, fld.dev ? (void*)fld.dev : (void*)slot->field, n, nullptr, p.q[nlay - 1]);
         double* d_fld = fld.dev ? fld.dev : slot->field;
         float* d_f32 = nullptr;  // fp32: where inverse_from_planes leaves the narrowed reconstruction
@@ -1342,146 +1367,126 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
     return WR_OK;
 }
 
-// Every plane's header and index, validated on the host before anything is launched: the kernels only ever see offsets that
-// lie inside their blob, in order, each stream no longer than a segment can be.  *brick: 0 for a WRS1 stream, the brick edge
-// of a WRS2 stream; *strands: 0, or the strand count of a WRS3 stream (whose brick may be 0).  A stream whose planes differ in
-// format, brick or strand count is refused.
-int seg_check_planes(const unsigned char* data_enc, const size_t* off, const wr_enc_info* info, int nlay, size_t n, uint32_t* seg, uint32_t* nseg,
-                     uint32_t* brick, uint32_t* strands)
+// ---- the stages of a segmented decode.  Every driver below -- the full decode, the box and region decodes, the many-region
+// decode, the batch, the segmented source of a transcode and the stage calls -- is a composition of these; none of them
+// states the stream parse, the work-buffer layout, the coder stage or the tail a second time.
+
+// The host's view of a validated coded field.  Every plane's header and index are checked on the host before anything is
+// launched: the kernels only ever see offsets that lie inside their blob, in order, each stream no longer than a segment can
+// be.  brick: 0 for a WRS1 stream, the brick edge of a WRS2 stream; strands: 0, or the strand count of a WRS3 stream (whose
+// brick may be 0).  A stream whose planes differ in format, brick or strand count is refused.
+struct SegStream {
+    bool constant = false;  // ntot_enc == 0: the field is midval, nothing else is looked at (wrappers.cpp:462-469)
+    int nlay = 0;
+    size_t off[WR_NLAYMAX + 1] = {0};  // where plane l's blob starts in the coded buffer
+    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0}, brick = 0, strands = 0;
+    wrblk::Order od{};  // brick != 0: the blocked order of the planes
+    size_t head() const { return wrseg::header_bytes(brick, strands); }
+};
+
+// who: put in front of every message ("field 3: " in a batch)
+int seg_stream_of(int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len, SegStream* s,
+                  const std::string& who = std::string())
 {
+    if (info->ntot_enc == 0) { s->constant = true; return WR_OK; }
+    const int nlay = info->nlay;
+    if (nlay < 1 || nlay > WR_NLAYMAX) return fail(WR_ERR_ARG, who + "nlay out of range");
+    if (info->wlev != 0 && info->wlev != kWavLvl) return fail(WR_ERR_ARG, who + "wlev must be 0 or 4");
+    if (!data_enc) return fail(WR_ERR_ARG, who + "null coded buffer");
+    if (int rc = plane_offsets(info, nlay, data_len, s->off, who)) return rc;
     std::string why;
-    if (!wrtc::check_planes(data_enc, off, info, nlay, n, seg, nseg, brick, strands, &why)) return fail(WR_ERR_STREAM, why);
+    if (!wrtc::check_planes(data_enc, s->off, info, nlay, (size_t)nx * ny * nz, s->seg, s->nseg, &s->brick, &s->strands, &why)) return fail(WR_ERR_STREAM, who + why);
+    if (s->brick) s->od = wrblk::order_of(nx, ny, nz, (int)info->wlev, s->brick);
+    s->nlay = nlay;
     return WR_OK;
 }
 
-// the byte offsets of the segment streams behind the index, from an index that check_index has passed, into work + 256
-int seg_upload_offsets(wr_ctx* c, const uint8_t* front, uint32_t nseg, uint8_t* work, uint32_t brick = 0, uint32_t strands = 0)
+// the segmented source of a transcode: wrtc::validate has run the same checks (wr_transcode.h; it also serves the host-only form)
+SegStream seg_stream_of(const wrtc::Source& src, int nx, int ny, int nz, int wlev)
+{
+    SegStream s;
+    s.nlay = src.nlay;
+    memcpy(s.off, src.off, sizeof s.off);
+    memcpy(s.seg, src.seg, sizeof s.seg);
+    memcpy(s.nseg, src.nseg, sizeof s.nseg);
+    s.brick = src.brick; s.strands = src.strands;
+    if (s.brick) s.od = wrblk::order_of(nx, ny, nz, wlev, s.brick);
+    return s;
+}
+
+// the constant field of a call, and the call's end
+int finish_constant(wr_ctx* c, const FieldRef& fld, size_t count, double midval, double t0, wr_timings* local, wr_timings* tm)
+{
+    if (int rc = fill_constant(c, fld, count, midval)) return rc;
+    local->total = now() - t0;
+    if (tm) *tm = *local;
+    return WR_OK;
+}
+
+// the byte offsets of the segment streams behind the index (nseg + 1 of them), from an index that check_index has passed
+std::vector<unsigned long long> seg_offsets(const uint8_t* front, size_t head, uint32_t nseg)
 {
     std::vector<unsigned long long> offs((size_t)nseg + 1);
     unsigned long long run = 0;
-    for (uint32_t k = 0; k < nseg; k++) { offs[k] = run; run += wrseg::get_u32(front + wrseg::header_bytes(brick, strands) + 4 * (size_t)k); }
+    for (uint32_t k = 0; k < nseg; k++) { offs[k] = run; run += wrseg::get_u32(front + head + 4 * (size_t)k); }
     offs[nseg] = run;
-    HIPCHK(hipMemcpy(work + 256, offs.data(), offs.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    return offs;
+}
+
+// ... to their place in a decoder's work buffer (wr_kernels.h)
+int seg_upload_offsets(const std::vector<unsigned long long>& offs, uint8_t* work)
+{
+    HIPCHK(hipMemcpy(wrk::seg_work_offs(work), offs.data(), offs.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
     return WR_OK;
 }
 
-int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
-                    wr_timings* tm)
+int seg_upload_offsets(const uint8_t* front, size_t head, uint32_t nseg, uint8_t* work) { return seg_upload_offsets(seg_offsets(front, head, nseg), work); }
+
+// The job of one plane for the batched decoder kernels: its blob of `len` bytes, decoded into sym.  work (may be null for a
+// plane without segments to decode): the plane's work buffer, whose offsets, flags and failure count the job points at.
+wrk::SegJob seg_job(const wrk::PlaneRef& sym, const uint8_t* blob, size_t len, uint8_t* work, size_t n, uint32_t seg, uint32_t nseg, uint32_t brick)
 {
-    if (int rc = ctx_bind(c)) return rc;
-    if (!info) return fail(WR_ERR_ARG, "null wr_enc_info");
-    std::lock_guard<std::mutex> lk(c->mu);
-    ActiveCall active(c->pool);
-    if (tm) wrdma::enable_timing();
-    if (int rc = check_dims(nx, ny, nz, fld.dev)) return rc;
-    if (fld.none()) return fail(WR_ERR_ARG, "null field pointer");
-    c->pend_valid = false;
-    PlaneHold planes(c);
-    SegBufs bufs(c);
-    const double t0 = now();
-    const size_t n = (size_t)nx * ny * nz;
-    wr_timings local; memset(&local, 0, sizeof local);
-    DevPool* const pool = c->pool;
-    if (info->ntot_enc == 0) {  // wrappers.cpp:462-469
-        if (fld.host) for (size_t j = 0; j < n; j++) fld.host[j] = info->midval;
-        else if (fld.host_f32) for (size_t j = 0; j < n; j++) fld.host_f32[j] = (float)info->midval;
-        else { wrk::fill(fld.dev, n, info->midval, c->stream); HIPCHK(hipStreamSynchronize(c->stream)); }
-        local.total = now() - t0;
-        if (tm) *tm = local;
-        return WR_OK;
+    wrk::SegJob j;
+    memset(&j, 0, sizeof j);
+    j.sym = sym;
+    j.n = n; j.blob = const_cast<uint8_t*>(blob); j.cap = len;
+    j.seg = seg; j.nseg = nseg; j.brick = brick;
+    if (work) { j.offs = wrk::seg_work_offs(work); j.flags = wrk::seg_work_flags(work, nseg); j.bad = wrk::seg_work_bad(work); }
+    return j;
+}
+
+// what a decoder's failure count says, behind the caller's "plane 2: " or "job 5: segmented plane: "
+std::string bad_segments_text(unsigned int k) { return std::to_string(k) + " segment(s) do not decode to their symbols"; }
+
+// the coder seconds of a call, from the event pairs the coder stage recorded: plane_coder_s[0, count) and their sum
+template <class Bufs>
+void fold_coder_seconds(const Bufs& bufs, int count, wr_timings* tm)
+{
+    for (int l = 0; l < count; l++) {
+        tm->plane_coder_s[l] = bufs.seconds(l);
+        tm->rangecoder += tm->plane_coder_s[l];
     }
-    const int nlay = info->nlay;
-    if (nlay < 1 || nlay > WR_NLAYMAX) return fail(WR_ERR_ARG, "nlay out of range");
-    if (info->wlev != 0 && info->wlev != kWavLvl) return fail(WR_ERR_ARG, "wlev must be 0 or 4");
-    if (!data_enc) return fail(WR_ERR_ARG, "null coded buffer");
-    size_t off[WR_NLAYMAX + 1] = {0};
-    for (int l = 0; l < nlay; l++) off[l + 1] = off[l] + info->len_enc_vec[l];
-    if (off[nlay] > info->ntot_enc) return fail(WR_ERR_STREAM, "len_enc_vec exceeds ntot_enc");
-    if (data_len && info->ntot_enc > data_len) return fail(WR_ERR_STREAM, "ntot_enc exceeds the length of the coded buffer");
-    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0}, brick = 0, strands = 0;
-    if (int rc = seg_check_planes(data_enc, off, info, nlay, n, seg, nseg, &brick, &strands)) return rc;
-    wrblk::Order od{};
-    if (brick) od = wrblk::order_of(nx, ny, nz, (int)info->wlev, brick);
-    {
-        std::lock_guard<std::mutex> gather(pool->planes.gather_mu);  // one decode at a time gathers its planes (decode_impl)
-        if (brick) {  // the plane in stream order, every plane in turn
-            bufs.perm = plane_scratch(c, n);
-            if (!bufs.perm.p) return WR_ERR_HIP;
-        }
-        for (int l = 0; l < nlay; l++) {
-            if (int rc = plane_prepare(c, l, n, true, false, nullptr, nullptr, false)) return rc;
-            bufs.blob[l] = plane_scratch(c, info->len_enc_vec[l]);
-            bufs.work[l] = plane_scratch(c, wrk::seg_decode_work_bytes(nseg[l]));
-            if (!bufs.blob[l].p || !bufs.work[l].p) return WR_ERR_HIP;
-            if (int rc = bufs.events(l)) return rc;
-        }
+}
+
+// (gather_mu held) plane l of the context made ready for a decoder kernel, with its blob and work buffers and, if wanted, its
+// pair of events.  windows: the plane is laid out for the host coder's windows (a transcode into the reference format)
+int seg_plane_bufs(wr_ctx* c, SegBufs* bufs, int l, size_t n, size_t blob_bytes, size_t work_bytes, bool windows, bool events)
+{
+    if (int rc = plane_prepare(c, l, n, true, false, nullptr, nullptr, windows)) return rc;
+    bufs->blob[l] = plane_scratch(c, blob_bytes);
+    bufs->work[l] = plane_scratch(c, work_bytes);
+    if (!bufs->blob[l].p || !bufs->work[l].p) return WR_ERR_HIP;
+    return events ? bufs->events(l) : WR_OK;
+}
+
+// stage "up" of a decode of whole planes: one copy per blob, and its segments' offsets
+int seg_upload_planes(wr_ctx* c, const SegStream& s, const wr_enc_info* info, const unsigned char* data_enc, SegBufs* bufs, float* ms)
+{
+    for (int l = 0; l < s.nlay; l++) {
+        if (int rc = xfer_field(c, &c->x_field, bufs->blob[l].p, data_enc + s.off[l], info->len_enc_vec[l], kUp)) return rc;
+        *ms += (float)c->x_field.ms;
+        if (int rc = seg_upload_offsets(data_enc + s.off[l], s.head(), s.nseg[l], bufs->work[l].p)) return rc;
     }
-    // ---- stage "up": one copy per blob
-    for (int l = 0; l < nlay; l++) {
-        if (int rc = xfer_field(c, &c->x_field, bufs.blob[l].p, data_enc + off[l], info->len_enc_vec[l], kUp)) return rc;
-        local.h2d_ms += (float)c->x_field.ms;
-        if (int rc = seg_upload_offsets(c, data_enc + off[l], nseg[l], bufs.work[l].p, brick, strands)) return rc;
-    }
-    const double t_coded = now();
-    SlotNeed need;
-    transform_need(nx, ny, nz, info->wlev ? -kWavLvl : 0, &need);
-    if (fld.host || fld.host_f32) need.field_elems = n;
-    SlotLease slot;
-    if (int rc = slot.acquire(c, need)) return rc;
-    const double t_phase = now();
-    wrk::DequantParams p;
-    memset(&p, 0, sizeof p);
-    p.nlay = nlay;
-    for (int l = 0; l < nlay; l++) {
-        p.deps[l] = info->deps_vec[l]; p.minval[l] = info->minval_vec[l]; p.q[l] = c->ps[l].ref;
-        if (!wrk::plane_ref_covers(p.q[l], n)) return fail(WR_ERR_HIP, "internal: the device buffer of plane " + std::to_string(l) + " has a hole");
-    }
-    double* d_fld = fld.dev ? fld.dev : slot->field;
-    float* d_f32 = nullptr;
-    int rc = WR_OK;
-    {
-        StageLock cu(pool->cu_mu);
-        clock_warmup(c, n);
-        for (int l = 0; l < nlay; l++) {
-            launch_note(c, "seg_decode", l, bufs.blob[l].p, n, bufs.work[l].p, p.q[l]);
-            HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
-            wrk::seg_decode(bufs.blob[l].p, info->len_enc_vec[l], brick ? wrk::plane_ref(bufs.perm.p) : p.q[l], n, seg[l], bufs.work[l].p, c->stream,
-                            brick, strands);
-            if (brick && !wrk::plane_reorder(p.q[l], bufs.perm.p, od, true, nullptr, 0, c->stream)) return fail(WR_ERR_ARG, "too many bricks");
-            HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
-        }
-        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented decoder launch failed" + launch_describe(c));
-        // the dequantizer only runs on planes whose every segment decoded
-        unsigned int bad[WR_NLAYMAX] = {0};
-        for (int l = 0; l < nlay; l++) HIPCHK(hipMemcpyAsync(&bad[l], bufs.work[l].p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the segmented decoder failed on the device" + launch_describe(c));
-        for (int l = 0; l < nlay; l++) {
-            if (bad[l]) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + std::to_string(bad[l]) + " segment(s) do not decode to their symbols");
-            local.plane_coder_s[l] = bufs.seconds(l);
-            local.rangecoder += local.plane_coder_s[l];
-        }
-        launch_note(c, "dequant", nlay - 1, d_fld, n, nullptr, p.q[nlay - 1]);
-        rc = inverse_from_planes(c, slot.get(), d_fld, nx, ny, nz, (int)info->wlev, p, fld.host_f32 ? &d_f32 : nullptr);
-        if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
-        if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the decoder's kernel stage failed on the device" + launch_describe(c));
-        pool->last_stage_end.store(now());
-    }
-    if (rc) return rc;
-    if (fld.host) {
-        if ((rc = xfer_field(c, &c->x_field, fld.host, d_fld, n * sizeof(double), kDown)) != WR_OK) return rc;
-        local.d2h_ms = (float)c->x_field.ms;
-    } else if (fld.host_f32) {
-        if ((rc = xfer_field(c, &c->x_field, fld.host_f32, d_f32, n * sizeof(float), kDown)) != WR_OK) return rc;
-        local.d2h_ms = (float)c->x_field.ms;
-    }
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev_a, c->ev_b)); local.quant_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev_b, c->ev_c)); local.transform_ms = ms;
-    local.total = now() - t0;
-    local.gpu = now() - t_phase;
-    local.wait = t_phase - t_coded;
-    local.transfer = t_coded - t0;
-    if (tm) *tm = local;
     return WR_OK;
 }
 
@@ -1515,9 +1520,201 @@ int seg_upload_streams(wr_ctx* c, uint8_t* d_blob, const uint8_t* h_blob, size_t
     return flush();
 }
 
-// decode_seg_impl for a plan (LowresPlan), from the first planes only: the box of level `level`, or with roi != nullptr a
-// region of it.  The segments the plan needs are uploaded and decoded, the others are not looked at beyond their length in
-// the index.  fld receives the plan's out_elems() elements.
+// Per used plane the list of segments to decode; planes cut at the same length share it (planes may have been cut at
+// different lengths).  list_of(seg, &ids): the ascending ids for a plane cut at seg.
+template <class ListOf>
+void seg_plane_lists(const SegStream& s, int used, std::vector<uint32_t>* ids, ListOf list_of)
+{
+    for (int l = 0; l < used; l++) {
+        int same = -1;
+        for (int k = 0; k < l; k++) if (s.seg[k] == s.seg[l]) same = k;
+        if (same >= 0) ids[l] = ids[same];
+        else list_of(s.seg[l], &ids[l]);
+    }
+}
+
+// stage "up" of a partial decode: the brick list, then per used plane the offsets table, the id list and the streams of the
+// listed segments -- the others are not looked at beyond their length in the index.  *bytes_up: the payload bytes copied.
+int seg_upload_lists(wr_ctx* c, const SegStream& s, int used, const unsigned char* data_enc, SegBufs* bufs, const std::vector<uint32_t>* ids,
+                     const std::vector<uint32_t>& bricks, float* ms, size_t* bytes_up)
+{
+    if (!bricks.empty()) HIPCHK(hipMemcpy(bufs->bricks.p, bricks.data(), bricks.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    for (int l = 0; l < used; l++) {
+        const uint8_t* const front = data_enc + s.off[l];
+        uint8_t* const work = bufs->work[l].p;
+        const std::vector<unsigned long long> offs = seg_offsets(front, s.head(), s.nseg[l]);
+        if (int rc = seg_upload_offsets(offs, work)) return rc;
+        if (!ids[l].empty()) HIPCHK(hipMemcpy(wrk::seg_decode_list_ids(work, s.nseg[l]), ids[l].data(), ids[l].size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (int rc = seg_upload_streams(c, bufs->blob[l].p, front, s.head() + 4 * (size_t)s.nseg[l], offs, ids[l], ms, bytes_up)) return rc;
+    }
+    return WR_OK;
+}
+
+// One coder stage (cu_mu held): the first `planes` planes of the stream, from bufs->blob[l] into q[l].
+struct CoderCall {
+    const SegStream* s;
+    const wr_enc_info* info;  // the blobs' lengths
+    int planes;
+    size_t n;
+    SegBufs* bufs;              // blob[l], work[l] as the "up" stage left them, and the event pairs
+    const wrk::PlaneRef* q;     // where plane l's symbols go, in the natural order
+    uint8_t* perm[WR_NLAYMAX] = {nullptr};       // a blocked stream: plane l in stream order (one buffer may serve every plane unless all go in one launch)
+    const std::vector<uint32_t>* ids = nullptr;  // per plane the segments to decode; nullptr: all of them
+    const uint32_t* d_bricks = nullptr;          // a blocked stream with lists: the bricks they cover (device memory) ...
+    size_t nbricks = 0;                          // ... nullptr: every brick goes back to its place
+    uint8_t *host_table = nullptr, *d_table = nullptr;  // set: all planes in ONE seg_decode_lists launch, timed as plane 0
+    int stat_segments = -1;      // the g_stat counter of the segments launched (none: -1)
+    bool stat_launches = false;  // the launches count in WR_STAT_ROI_CODER_LAUNCHES
+};
+
+// Launch per plane (the whole plane or its list) or one launch over all planes, the inverse reorder of a blocked stream, the
+// event pairs; then every plane's failure count comes back once and the stream is drained: whatever runs next only sees
+// planes whose every (listed) segment decoded.  tm: plane_coder_s and rangecoder.
+int seg_coder_stage(wr_ctx* c, const CoderCall& k, wr_timings* tm)
+{
+    const SegStream& s = *k.s;
+    SegBufs& b = *k.bufs;
+    const bool one_launch = k.d_table != nullptr;
+    auto sym = [&](int l) { return s.brick ? wrk::plane_ref(k.perm[l]) : k.q[l]; };
+    // (what was decoded is in the scratch plane in stream order: the bricks go to their places in the plane)
+    auto reorder = [&](int l) { return !s.brick || wrk::plane_reorder(k.q[l], k.perm[l], s.od, true, k.d_bricks, k.nbricks, c->stream); };
+    if (one_launch) {
+        wrk::SegJob jobs[WR_NLAYMAX];
+        wrk::SegList lists[WR_NLAYMAX];
+        memset(jobs, 0, sizeof jobs);
+        memset(lists, 0, sizeof lists);
+        for (int l = 0; l < k.planes; l++) {
+            uint8_t* const work = b.work[l].p;
+            jobs[l] = seg_job(sym(l), b.blob[l].p, k.info->len_enc_vec[l], work, k.n, s.seg[l], s.nseg[l], s.brick);
+            lists[l].ids = wrk::seg_decode_list_ids(work, s.nseg[l]);
+            lists[l].nlist = (uint32_t)k.ids[l].size();
+            HIPCHK(hipMemsetAsync(wrk::seg_work_bad(work), 0, sizeof(unsigned int), c->stream));
+            if (k.stat_segments >= 0) g_stat[k.stat_segments] += k.ids[l].size();
+        }
+        launch_note(c, "seg_decode_lists", 0, b.blob[0].p, k.n, b.work[0].p, k.q[0]);
+        HIPCHK(hipEventRecord(b.ev[0], c->stream));
+        wrk::seg_decode_lists(jobs, lists, (size_t)k.planes, k.host_table, k.d_table, c->stream);
+        HIPCHK(hipEventRecord(b.ev[1], c->stream));
+        if (k.stat_launches) g_stat[WR_STAT_ROI_CODER_LAUNCHES] += 1;
+        for (int l = 0; l < k.planes; l++) if (!reorder(l)) return fail(WR_ERR_ARG, "too many bricks");
+    } else {
+        for (int l = 0; l < k.planes; l++) {
+            launch_note(c, k.ids ? "seg_decode_list" : "seg_decode", l, b.blob[l].p, k.n, b.work[l].p, k.q[l]);
+            HIPCHK(hipEventRecord(b.ev[2 * l], c->stream));
+            if (k.ids) wrk::seg_decode_list(b.blob[l].p, k.info->len_enc_vec[l], sym(l), k.n, s.seg[l], b.work[l].p, k.ids[l].size(), c->stream, s.brick, s.strands);
+            else wrk::seg_decode(b.blob[l].p, k.info->len_enc_vec[l], sym(l), k.n, s.seg[l], b.work[l].p, c->stream, s.brick, s.strands);
+            if (!reorder(l)) return fail(WR_ERR_ARG, "too many bricks");
+            HIPCHK(hipEventRecord(b.ev[2 * l + 1], c->stream));
+            if (k.stat_segments >= 0) g_stat[k.stat_segments] += k.ids[l].size();
+            if (k.stat_launches) g_stat[WR_STAT_ROI_CODER_LAUNCHES] += 1;
+        }
+    }
+    if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented decoder launch failed" + launch_describe(c));
+    unsigned int bad[WR_NLAYMAX] = {0};
+    for (int l = 0; l < k.planes; l++) HIPCHK(hipMemcpyAsync(&bad[l], wrk::seg_work_bad(b.work[l].p), sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the segmented decoder failed on the device" + launch_describe(c));
+    for (int l = 0; l < k.planes; l++)
+        if (bad[l]) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + bad_segments_text(bad[l]));
+    fold_coder_seconds(b, one_launch ? 1 : k.planes, tm);
+    return WR_OK;
+}
+
+// the end of a driver's kernel stage (cu_mu held): rc is the finisher's
+int kernel_stage_end(wr_ctx* c, int rc)
+{
+    if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the decoder's kernel stage failed on the device" + launch_describe(c));
+    c->pool->last_stage_end.store(now());
+    return rc;
+}
+
+// The tail of a decode call: `count` elements from where the finisher left them (d_f64, or d_f32 for an fp32 caller) to a host
+// caller, then the call's timings.  events: quant_ms and transform_ms are the finisher's ev_a / ev_b / ev_c (a finisher that
+// ran more than once has summed them itself).
+int finish_call(wr_ctx* c, const FieldRef& fld, const void* d_f64, const void* d_f32, size_t count, bool events, double t0, double t_coded, double t_phase,
+                wr_timings* local, wr_timings* tm)
+{
+    if (fld.host) {
+        if (int rc = xfer_field(c, &c->x_field, fld.host, d_f64, count * sizeof(double), kDown)) return rc;
+        local->d2h_ms = (float)c->x_field.ms;
+    } else if (fld.host_f32) {
+        if (int rc = xfer_field(c, &c->x_field, fld.host_f32, d_f32, count * sizeof(float), kDown)) return rc;
+        local->d2h_ms = (float)c->x_field.ms;
+    }
+    if (events) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, c->ev_a, c->ev_b)); local->quant_ms = ms;
+        HIPCHK(hipEventElapsedTime(&ms, c->ev_b, c->ev_c)); local->transform_ms = ms;
+    }
+    local->total = now() - t0;
+    local->gpu = now() - t_phase;
+    local->wait = t_phase - t_coded;
+    local->transfer = t_coded - t0;
+    if (tm) *tm = *local;
+    return WR_OK;
+}
+
+// ---- the drivers.  They differ in the plan (everything; one box or region: a LowresPlan; many regions), in the finisher
+// (inverse_from_planes, lowres_from_planes / roi_from_planes, roi_multi_from_planes) and in where the result lands; the rest
+// is the stages above, in the same order: parse, gather the planes' buffers, "up", lease the slot, coder stage, finisher, tail.
+int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
+                    wr_timings* tm)
+{
+    if (int rc = ctx_bind(c)) return rc;
+    if (!info) return fail(WR_ERR_ARG, "null wr_enc_info");
+    std::lock_guard<std::mutex> lk(c->mu);
+    ActiveCall active(c->pool);
+    if (tm) wrdma::enable_timing();
+    if (int rc = check_dims(nx, ny, nz, fld.dev)) return rc;
+    if (fld.none()) return fail(WR_ERR_ARG, "null field pointer");
+    c->pend_valid = false;
+    PlaneHold planes(c);
+    SegBufs bufs(c);
+    const double t0 = now();
+    const size_t n = (size_t)nx * ny * nz;
+    wr_timings local; memset(&local, 0, sizeof local);
+    DevPool* const pool = c->pool;
+    SegStream s;
+    if (int rc = seg_stream_of(nx, ny, nz, info, data_enc, data_len, &s)) return rc;
+    if (s.constant) return finish_constant(c, fld, n, info->midval, t0, &local, tm);
+    {
+        std::lock_guard<std::mutex> gather(pool->planes.gather_mu);  // one decode at a time gathers its planes (decode_impl)
+        if (s.brick) {  // the plane in stream order, every plane in turn
+            bufs.perm = plane_scratch(c, n);
+            if (!bufs.perm.p) return WR_ERR_HIP;
+        }
+        for (int l = 0; l < s.nlay; l++)
+            if (int rc = seg_plane_bufs(c, &bufs, l, n, info->len_enc_vec[l], wrk::seg_decode_work_bytes(s.nseg[l]), false, true)) return rc;
+    }
+    if (int rc = seg_upload_planes(c, s, info, data_enc, &bufs, &local.h2d_ms)) return rc;
+    const double t_coded = now();
+    SlotNeed need;
+    transform_need(nx, ny, nz, info->wlev ? -kWavLvl : 0, &need);
+    if (fld.host || fld.host_f32) need.field_elems = n;
+    SlotLease slot;
+    if (int rc = slot.acquire(c, need)) return rc;
+    const double t_phase = now();
+    wrk::DequantParams p;
+    if (int rc = dequant_params(info, s.nlay, n, [&](int l) { return c->ps[l].ref; }, &p)) return rc;
+    double* d_fld = fld.dev ? fld.dev : slot->field;
+    float* d_f32 = nullptr;
+    int rc = WR_OK;
+    {
+        StageLock cu(pool->cu_mu);
+        clock_warmup(c, n);
+        CoderCall k{&s, info, s.nlay, n, &bufs, p.q};
+        for (int l = 0; l < s.nlay; l++) k.perm[l] = bufs.perm.p;
+        if (int rc = seg_coder_stage(c, k, &local)) return rc;
+        launch_note(c, "dequant", s.nlay - 1, d_fld, n, nullptr, p.q[s.nlay - 1]);
+        rc = kernel_stage_end(c, inverse_from_planes(c, slot.get(), d_fld, nx, ny, nz, (int)info->wlev, p, fld.host_f32 ? &d_f32 : nullptr));
+    }
+    if (rc) return rc;
+    return finish_call(c, fld, d_fld, d_f32, n, true, t0, t_coded, t_phase, &local, tm);
+}
+
+// The box of level `level` from the first planes only, or with roi != nullptr a region of it: the segments the plan needs are
+// uploaded and decoded, a launch per used plane.  fld receives the plan's out_elems() elements; a region's crop comes
+// through the slot (roi_from_planes).
 int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int level, int max_planes, const wr_box* roi, const wr_enc_info* info,
                            const unsigned char* data_enc, size_t data_len, wr_timings* tm)
 {
@@ -1537,71 +1734,34 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     const size_t n = (size_t)nx * ny * nz, nbox = pl.out_elems();  // (the box's elements, or the region's)
     wr_timings local; memset(&local, 0, sizeof local);
     DevPool* const pool = c->pool;
-    if (info->ntot_enc == 0) {  // a constant field: midval at the box's size
-        if (fld.host) for (size_t j = 0; j < nbox; j++) fld.host[j] = info->midval;
-        else if (fld.host_f32) for (size_t j = 0; j < nbox; j++) fld.host_f32[j] = (float)info->midval;
-        else { wrk::fill(fld.dev, nbox, info->midval, c->stream); HIPCHK(hipStreamSynchronize(c->stream)); }
-        local.total = now() - t0;
-        if (tm) *tm = local;
-        return WR_OK;
-    }
-    const int nlay = info->nlay, used = pl.planes;
-    if (nlay < 1) return fail(WR_ERR_ARG, "nlay out of range");
-    if (!data_enc) return fail(WR_ERR_ARG, "null coded buffer");
-    size_t off[WR_NLAYMAX + 1] = {0};
-    for (int l = 0; l < nlay; l++) off[l + 1] = off[l] + info->len_enc_vec[l];
-    if (off[nlay] > info->ntot_enc) return fail(WR_ERR_STREAM, "len_enc_vec exceeds ntot_enc");
-    if (data_len && info->ntot_enc > data_len) return fail(WR_ERR_STREAM, "ntot_enc exceeds the length of the coded buffer");
-    // every plane's header and index, used or not, are validated on the host before anything is launched (decode_seg_impl)
-    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0}, brick = 0, strands = 0;
-    if (int rc = seg_check_planes(data_enc, off, info, nlay, n, seg, nseg, &brick, &strands)) return rc;
+    // every plane's header and index, used or not, are validated (region_plan has refused what seg_stream_of would of nlay and wlev)
+    SegStream s;
+    if (int rc = seg_stream_of(nx, ny, nz, info, data_enc, data_len, &s)) return rc;
+    if (s.constant) return finish_constant(c, fld, nbox, info->midval, t0, &local, tm);
+    const int used = pl.planes;
     // a blocked stream: the bricks the plan needs, the same in every plane
-    wrblk::Order od{};
     std::vector<uint32_t> bricks;
-    if (brick) {
-        od = wrblk::order_of(nx, ny, nz, (int)info->wlev, brick);
-        if (od.nbricks > 0x7fffffffu) return fail(WR_ERR_ARG, "too many bricks");
-        pl.bricks(od, &bricks);
+    if (s.brick) {
+        if (s.od.nbricks > 0x7fffffffu) return fail(WR_ERR_ARG, "too many bricks");
+        pl.bricks(s.od, &bricks);
     }
-    // the segments the plan needs, per plane (planes may have been cut at different lengths)
     std::vector<uint32_t> ids[WR_NLAYMAX];
-    for (int l = 0; l < used; l++) {
-        int same = -1;
-        for (int k = 0; k < l; k++) if (seg[k] == seg[l]) same = k;
-        if (same >= 0) { ids[l] = ids[same]; continue; }
-        if (brick) pl.segments_blocked(od, seg[l], &ids[l]);
-        else pl.segments(nx, ny, nz, seg[l], &ids[l]);
-    }
+    seg_plane_lists(s, used, ids, [&](uint32_t seg, std::vector<uint32_t>* out) {
+        if (s.brick) pl.segments_blocked(s.od, seg, out);
+        else pl.segments(nx, ny, nz, seg, out);
+    });
     {
         std::lock_guard<std::mutex> gather(pool->planes.gather_mu);
-        if (brick) {
+        if (s.brick) {
             bufs.perm = plane_scratch(c, n);
             bufs.bricks = plane_scratch(c, 4 * bricks.size() + 4);
             if (!bufs.perm.p || !bufs.bricks.p) return WR_ERR_HIP;
         }
-        for (int l = 0; l < used; l++) {
-            if (int rc = plane_prepare(c, l, n, true, false, nullptr, nullptr, false)) return rc;
-            bufs.blob[l] = plane_scratch(c, info->len_enc_vec[l]);
-            bufs.work[l] = plane_scratch(c, wrk::seg_decode_list_work_bytes(nseg[l], ids[l].size()));
-            if (!bufs.blob[l].p || !bufs.work[l].p) return WR_ERR_HIP;
-            if (int rc = bufs.events(l)) return rc;
-        }
+        for (int l = 0; l < used; l++)
+            if (int rc = seg_plane_bufs(c, &bufs, l, n, info->len_enc_vec[l], wrk::seg_decode_list_work_bytes(s.nseg[l], ids[l].size()), false, true)) return rc;
     }
-    // ---- stage "up": per plane the offsets table, the id list and the streams of the listed segments
     size_t bytes_up = 0;
-    const size_t head = wrseg::header_bytes(brick, strands);
-    if (!bricks.empty()) HIPCHK(hipMemcpy(bufs.bricks.p, bricks.data(), bricks.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    for (int l = 0; l < used; l++) {
-        const uint8_t* const front = data_enc + off[l];
-        std::vector<unsigned long long> offs((size_t)nseg[l] + 1);
-        unsigned long long run = 0;
-        for (uint32_t k = 0; k < nseg[l]; k++) { offs[k] = run; run += wrseg::get_u32(front + head + 4 * (size_t)k); }
-        offs[nseg[l]] = run;
-        HIPCHK(hipMemcpy(bufs.work[l].p + 256, offs.data(), offs.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
-        if (!ids[l].empty())
-            HIPCHK(hipMemcpy(wrk::seg_decode_list_ids(bufs.work[l].p, nseg[l]), ids[l].data(), ids[l].size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        if (int rc = seg_upload_streams(c, bufs.blob[l].p, front, head + 4 * (size_t)nseg[l], offs, ids[l], &local.h2d_ms, &bytes_up)) return rc;
-    }
+    if (int rc = seg_upload_lists(c, s, used, data_enc, &bufs, ids, bricks, &local.h2d_ms, &bytes_up)) return rc;
     g_stat[pl.stat_bytes_up] += bytes_up;
     const double t_coded = now();
     SlotNeed need;
@@ -1610,12 +1770,7 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     if (int rc = slot.acquire(c, need)) return rc;
     const double t_phase = now();
     wrk::DequantParams p;
-    memset(&p, 0, sizeof p);
-    p.nlay = used;
-    for (int l = 0; l < used; l++) {
-        p.deps[l] = info->deps_vec[l]; p.minval[l] = info->minval_vec[l]; p.q[l] = c->ps[l].ref;
-        if (!wrk::plane_ref_covers(p.q[l], n)) return fail(WR_ERR_HIP, "internal: the device buffer of plane " + std::to_string(l) + " has a hole");
-    }
+    if (int rc = dequant_params(info, used, n, [&](int l) { return c->ps[l].ref; }, &p)) return rc;
     double* d_box = fld.dev ? fld.dev : slot->field;
     float* d_f32 = nullptr;
     void* d_roi = nullptr;  // where a region's crop landed
@@ -1623,28 +1778,13 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     {
         StageLock cu(pool->cu_mu);
         clock_warmup(c, pl.work_elems());
-        for (int l = 0; l < used; l++) {
-            launch_note(c, "seg_decode_list", l, bufs.blob[l].p, n, bufs.work[l].p, p.q[l]);
-            HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
-            wrk::seg_decode_list(bufs.blob[l].p, info->len_enc_vec[l], brick ? wrk::plane_ref(bufs.perm.p) : p.q[l], n, seg[l], bufs.work[l].p,
-                                 ids[l].size(), c->stream, brick, strands);
-            // the listed segments are in the scratch buffer in stream order: the needed bricks go to their places in the plane
-            if (brick && !wrk::plane_reorder(p.q[l], bufs.perm.p, od, true, reinterpret_cast<const uint32_t*>(bufs.bricks.p), bricks.size(), c->stream))
-                return fail(WR_ERR_ARG, "too many bricks");
-            HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
-            g_stat[pl.stat_segments] += ids[l].size();
-            if (pl.roi) g_stat[WR_STAT_ROI_CODER_LAUNCHES] += 1;
-        }
-        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented decoder launch failed" + launch_describe(c));
-        // the dequantizer only runs on planes whose every listed segment decoded
-        unsigned int bad[WR_NLAYMAX] = {0};
-        for (int l = 0; l < used; l++) HIPCHK(hipMemcpyAsync(&bad[l], bufs.work[l].p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the segmented decoder failed on the device" + launch_describe(c));
-        for (int l = 0; l < used; l++) {
-            if (bad[l]) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + std::to_string(bad[l]) + " segment(s) do not decode to their symbols");
-            local.plane_coder_s[l] = bufs.seconds(l);
-            local.rangecoder += local.plane_coder_s[l];
-        }
+        CoderCall k{&s, info, used, n, &bufs, p.q};
+        for (int l = 0; l < used; l++) k.perm[l] = bufs.perm.p;
+        k.ids = ids;
+        k.d_bricks = reinterpret_cast<const uint32_t*>(bufs.bricks.p); k.nbricks = bricks.size();
+        k.stat_segments = pl.stat_segments;
+        k.stat_launches = pl.roi;
+        if (int rc = seg_coder_stage(c, k, &local)) return rc;
         if (pl.roi) {
             launch_note(c, "dequant_window", used - 1, slot->field, pl.work_elems(), nullptr, p.q[used - 1]);
             rc = roi_from_planes(c, slot.get(), fld.dev, nx, ny, pl, p, fld.host_f32 != nullptr, &d_roi);
@@ -1653,27 +1793,10 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
             launch_note(c, "dequant_box", used - 1, d_box, nbox, nullptr, p.q[used - 1]);
             rc = lowres_from_planes(c, slot.get(), d_box, nx, ny, pl, p, fld.host_f32 ? &d_f32 : nullptr);
         }
-        if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
-        if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the decoder's kernel stage failed on the device" + launch_describe(c));
-        pool->last_stage_end.store(now());
+        rc = kernel_stage_end(c, rc);
     }
     if (rc) return rc;
-    if (fld.host) {
-        if ((rc = xfer_field(c, &c->x_field, fld.host, d_box, nbox * sizeof(double), kDown)) != WR_OK) return rc;
-        local.d2h_ms = (float)c->x_field.ms;
-    } else if (fld.host_f32) {
-        if ((rc = xfer_field(c, &c->x_field, fld.host_f32, d_f32, nbox * sizeof(float), kDown)) != WR_OK) return rc;
-        local.d2h_ms = (float)c->x_field.ms;
-    }
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev_a, c->ev_b)); local.quant_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev_b, c->ev_c)); local.transform_ms = ms;
-    local.total = now() - t0;
-    local.gpu = now() - t_phase;
-    local.wait = t_phase - t_coded;
-    local.transfer = t_coded - t0;
-    if (tm) *tm = local;
-    return WR_OK;
+    return finish_call(c, fld, d_box, d_f32, nbox, true, t0, t_coded, t_phase, &local, tm);
 }
 
 // ---- transcoding: the planes of a coded field from one stream format to another (include/waverange_amd.h, wr_transcode.h)
@@ -1787,49 +1910,26 @@ int transcode_impl(wr_ctx* c, int nx, int ny, int nz, const wr_enc_info* info_in
             local.h2d_ms += (float)c->ps[l].copy_ms;
         }
     } else {
-        // validation has passed (wrtc::validate): upload and coder stage of decode_seg_impl.  A plane the host encoder will read
-        // is laid out for its windows from the start.
-        wrblk::Order od{};
-        if (s.brick) od = wrblk::order_of(nx, ny, nz, (int)info_in->wlev, s.brick);
+        // validation has passed (wrtc::validate): the "up" and coder stages of the full decode.  A plane the host encoder will
+        // read is laid out for its windows from the start.
+        const SegStream ss = seg_stream_of(s, nx, ny, nz, (int)info_in->wlev);
         {
             std::lock_guard<std::mutex> gather(pool->planes.gather_mu);
-            for (int l = 0; l < nlay; l++) {
-                if (int rc = plane_prepare(c, l, n, true, false, nullptr, nullptr, ref_target)) return rc;
-                sbufs.blob[l] = plane_scratch(c, info_in->len_enc_vec[l]);
-                sbufs.work[l] = plane_scratch(c, wrk::seg_decode_work_bytes(s.nseg[l]));
-                if (!sbufs.blob[l].p || !sbufs.work[l].p) return WR_ERR_HIP;
-                if (int rc = sbufs.events(l)) return rc;
-            }
+            for (int l = 0; l < nlay; l++)
+                if (int rc = seg_plane_bufs(c, &sbufs, l, n, info_in->len_enc_vec[l], wrk::seg_decode_work_bytes(ss.nseg[l]), ref_target, true)) return rc;
         }
-        for (int l = 0; l < nlay; l++) {
-            if (int rc = xfer_field(c, &c->x_field, sbufs.blob[l].p, data_in + s.off[l], info_in->len_enc_vec[l], kUp)) return rc;
-            local.h2d_ms += (float)c->x_field.ms;
-            if (int rc = seg_upload_offsets(c, data_in + s.off[l], s.nseg[l], sbufs.work[l].p, s.brick, s.strands)) return rc;
-        }
+        if (int rc = seg_upload_planes(c, ss, info_in, data_in, &sbufs, &local.h2d_ms)) return rc;
         const double t_stage = now();
         StageLock cu(pool->cu_mu);
         clock_warmup(c, n);
-        for (int l = 0; l < nlay; l++) {
-            const wrk::PlaneRef& q = c->ps[l].ref;
-            if (!wrk::plane_ref_covers(q, n)) return fail(WR_ERR_HIP, "internal: the device buffer of plane " + std::to_string(l) + " has a hole");
-            launch_note(c, "seg_decode", l, sbufs.blob[l].p, n, sbufs.work[l].p, q);
-            HIPCHK(hipEventRecord(sbufs.ev[2 * l], c->stream));
-            wrk::seg_decode(sbufs.blob[l].p, info_in->len_enc_vec[l], s.brick ? wrk::plane_ref(tbufs.perm.p) : q, n, s.seg[l], sbufs.work[l].p, c->stream, s.brick,
-                            s.strands);
-            if (s.brick && !wrk::plane_reorder(q, tbufs.perm.p, od, true, nullptr, 0, c->stream)) return fail(WR_ERR_ARG, "too many bricks");
-            HIPCHK(hipEventRecord(sbufs.ev[2 * l + 1], c->stream));
-        }
-        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented decoder launch failed" + launch_describe(c));
+        wrk::PlaneRef q[WR_NLAYMAX];
+        if (int rc = plane_refs(nlay, n, [&](int l) { return c->ps[l].ref; }, q)) return rc;
         // the target's coder only runs on planes whose every segment decoded
-        unsigned int bad[WR_NLAYMAX] = {0};
-        for (int l = 0; l < nlay; l++) HIPCHK(hipMemcpyAsync(&bad[l], sbufs.work[l].p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the segmented decoder failed on the device" + launch_describe(c));
+        CoderCall k{&ss, info_in, nlay, n, &sbufs, q};
+        for (int l = 0; l < nlay; l++) k.perm[l] = tbufs.perm.p;
+        const int rc = seg_coder_stage(c, k, &local);
         pool->last_stage_end.store(now());
-        for (int l = 0; l < nlay; l++) {
-            if (bad[l]) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + std::to_string(bad[l]) + " segment(s) do not decode to their symbols");
-            local.plane_coder_s[l] = sbufs.seconds(l);
-            local.rangecoder += local.plane_coder_s[l];
-        }
+        if (rc) return rc;
         gpu_s += now() - t_stage;
     }
 
@@ -1987,6 +2087,42 @@ int transcode_impl(wr_ctx* c, int nx, int ny, int nz, const wr_enc_info* info_in
     return WR_OK;
 }
 
+// The front of a blob in device memory for a stage call: its header comes to the host, then -- once check_index has seen that
+// the index fits into the blob -- header and index, and both are validated before anything is launched.  blocked: the call
+// decodes WRS2 blobs beside WRS1; no_strands: nullptr if it decodes WRS3 blobs too, else the words it refuses one with (nothing
+// else of the blob has been looked at then).  Every refusal is made here, with `who` ("job 3: ") in front.
+struct Front {
+    std::vector<uint8_t> bytes;
+    uint32_t seg = 0, nseg = 0, brick = 0, strands = 0;
+};
+
+int fetch_front(const unsigned char* d_blob, size_t blob_len, size_t n, bool blocked, const char* no_strands, const std::string& who, Front* f)
+{
+    if (blob_len < wrseg::kHeaderBytes) return fail(WR_ERR_STREAM, who + "segmented plane: shorter than its header");
+    f->bytes.resize(blocked ? std::min(blob_len, wrseg::kHeaderBytesBlocked) : wrseg::kHeaderBytes);
+    HIPCHK(hipMemcpy(f->bytes.data(), d_blob, f->bytes.size(), hipMemcpyDeviceToHost));
+    const bool wrs3 = memcmp(f->bytes.data(), wrseg::kMagicStrands, 4) == 0;
+    if (wrs3 && no_strands) return fail(WR_ERR_UNSUPPORTED, who + no_strands);
+    if (wrs3 && blob_len >= wrseg::kHeaderBytesStrands) {
+        f->bytes.resize(wrseg::kHeaderBytesStrands);
+        HIPCHK(hipMemcpy(f->bytes.data(), d_blob, f->bytes.size(), hipMemcpyDeviceToHost));
+    }
+    auto check = [&]() {
+        const uint8_t* const b = f->bytes.data();
+        if (wrs3) return wrseg::check_index(b, f->bytes.size(), blob_len, n, &f->seg, &f->nseg, &f->brick, &f->strands);
+        if (blocked) return wrseg::check_index(b, f->bytes.size(), blob_len, n, &f->seg, &f->nseg, &f->brick);
+        return wrseg::check_index(b, f->bytes.size(), blob_len, n, &f->seg, &f->nseg);
+    };
+    const char* why = check();
+    if (why == wrseg::kIndexNotAvailable) {  // (the index fits into the blob: check_index has looked)
+        const size_t head = wrs3 ? wrseg::kHeaderBytesStrands : memcmp(f->bytes.data(), wrseg::kMagicBlocked, 4) == 0 ? wrseg::kHeaderBytesBlocked : wrseg::kHeaderBytes;
+        f->bytes.resize(head + 4 * (size_t)wrseg::get_u32(f->bytes.data() + 8));
+        HIPCHK(hipMemcpy(f->bytes.data(), d_blob, f->bytes.size(), hipMemcpyDeviceToHost));
+        why = check();
+    }
+    return why ? fail(WR_ERR_STREAM, who + why) : WR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2051,40 +2187,21 @@ int wr_dev_seg_decode(wr_ctx* c, const unsigned char* d_blob, size_t blob_len, u
     if (((uintptr_t)d_sym | (uintptr_t)d_blob) & 15) return fail(WR_ERR_ARG, "plane and blob buffers must be 16-byte aligned");
     if (bad_segments) *bad_segments = 0;
     std::lock_guard<std::mutex> lk(c->mu);
-    // the header, then the index, come to the host and are validated before anything is launched
-    std::vector<uint8_t> front(wrseg::kHeaderBytes);
-    if (blob_len < front.size()) return fail(WR_ERR_STREAM, "segmented plane: shorter than its header");
-    HIPCHK(hipMemcpy(front.data(), d_blob, front.size(), hipMemcpyDeviceToHost));
-    uint32_t seg = 0, nseg = 0, brick = 0, strands = 0;
-    const bool wrs3 = memcmp(front.data(), wrseg::kMagicStrands, 4) == 0;  // (a WRS3 blob's symbols come out in stream order)
-    if (wrs3 && blob_len >= wrseg::kHeaderBytesStrands) {
-        front.resize(wrseg::kHeaderBytesStrands);
-        HIPCHK(hipMemcpy(front.data(), d_blob, front.size(), hipMemcpyDeviceToHost));
-    }
-    auto check = [&]() {
-        return wrs3 ? wrseg::check_index(front.data(), front.size(), blob_len, n, &seg, &nseg, &brick, &strands)
-                    : wrseg::check_index(front.data(), front.size(), blob_len, n, &seg, &nseg);
-    };
-    const char* why = check();
-    if (why == wrseg::kIndexNotAvailable) {  // (the index fits into the blob: check_index has looked)
-        front.resize(front.size() + 4 * (size_t)wrseg::get_u32(front.data() + 8));
-        HIPCHK(hipMemcpy(front.data(), d_blob, front.size(), hipMemcpyDeviceToHost));
-        why = check();
-    }
-    if (why) return fail(WR_ERR_STREAM, why);
-    if (!nseg) return WR_OK;
+    Front f;  // (a WRS3 blob's symbols come out in stream order)
+    if (int rc = fetch_front(d_blob, blob_len, n, false, nullptr, std::string(), &f)) return rc;
+    if (!f.nseg) return WR_OK;
     SegBufs bufs(c);
-    bufs.work[0] = plane_scratch(c, wrk::seg_decode_work_bytes(nseg));
+    bufs.work[0] = plane_scratch(c, wrk::seg_decode_work_bytes(f.nseg));
     if (!bufs.work[0].p) return WR_ERR_HIP;
-    if (int rc = seg_upload_offsets(c, front.data(), nseg, bufs.work[0].p, 0, strands)) return rc;
+    if (int rc = seg_upload_offsets(f.bytes.data(), wrseg::header_bytes(0, f.strands), f.nseg, bufs.work[0].p)) return rc;
     StageLock cu(c->pool->cu_mu);
-    wrk::seg_decode(d_blob, blob_len, wrk::plane_ref(d_sym), n, seg, bufs.work[0].p, c->stream, 0, strands);
+    wrk::seg_decode(d_blob, blob_len, wrk::plane_ref(d_sym), n, f.seg, bufs.work[0].p, c->stream, 0, f.strands);
     HIPCHK(hipGetLastError());
     unsigned int bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, bufs.work[0].p, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&bad, wrk::seg_work_bad(bufs.work[0].p), sizeof bad, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (bad_segments) *bad_segments = bad;
-    if (bad) return fail(WR_ERR_STREAM, "segmented plane: " + std::to_string(bad) + " segment(s) do not decode to their symbols");
+    if (bad) return fail(WR_ERR_STREAM, "segmented plane: " + bad_segments_text(bad));
     return WR_OK;
 }
 
@@ -2491,12 +2608,9 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
     return WR_OK;
 }
 
-struct BatchField {  // a field of a decode batch as the host has validated it
-    int nlay = 0;    // 0: a constant field, no job
-    size_t off[WR_NLAYMAX + 1] = {0};
-    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0}, brick = 0;
+struct BatchField {  // a field of a decode batch: its stream as the host has validated it (nlay == 0: a constant field, no job), and its buffers
+    SegStream s;
     uint8_t *plane[WR_NLAYMAX] = {nullptr}, *blob[WR_NLAYMAX] = {nullptr}, *work[WR_NLAYMAX] = {nullptr}, *perm = nullptr;
-    wrblk::Order od{};
 };
 
 int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& flds, int nx, int ny, int nz, const wr_enc_info* infos,
@@ -2523,23 +2637,13 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
     unsigned long long lanes[WR_NLAYMAX] = {0};
     for (int f = 0; f < nfields; f++) {
         const wr_enc_info* const info = &infos[f];
-        BatchField& b = bf[f];
+        SegStream& s = bf[f].s;
         if (info->ntot_enc == 0) continue;  // a constant field: filled with midval below
-        const int nlay = info->nlay;
         const std::string who = "field " + std::to_string(f) + ": ";
-        if (nlay < 1 || nlay > WR_NLAYMAX) return fail(WR_ERR_ARG, who + "nlay out of range");
-        if (info->wlev != 0 && info->wlev != kWavLvl) return fail(WR_ERR_ARG, who + "wlev must be 0 or 4");
-        if (!data_encs[f]) return fail(WR_ERR_ARG, who + "null coded buffer");
-        for (int l = 0; l < nlay; l++) b.off[l + 1] = b.off[l] + info->len_enc_vec[l];
-        if (b.off[nlay] > info->ntot_enc) return fail(WR_ERR_STREAM, who + "len_enc_vec exceeds ntot_enc");
-        if (data_lens && data_lens[f] && info->ntot_enc > data_lens[f]) return fail(WR_ERR_STREAM, who + "ntot_enc exceeds the length of the coded buffer");
-        uint32_t strands = 0;
-        if (int rc = seg_check_planes(data_encs[f], b.off, info, nlay, n, b.seg, b.nseg, &b.brick, &strands)) return fail_at("field", f, rc);
-        if (strands) return fail(WR_ERR_UNSUPPORTED, who + "a WRS3 stream: stranded segments are not decoded in a batch (wr_decode_host_seg reads them)");
-        if (b.brick) b.od = wrblk::order_of(nx, ny, nz, (int)info->wlev, b.brick);
-        b.nlay = nlay;
-        for (int l = 0; l < nlay; l++) lanes[l] += b.nseg[l];
-        if (nlay > maxlay) maxlay = nlay;
+        if (int rc = seg_stream_of(nx, ny, nz, info, data_encs[f], data_lens ? data_lens[f] : 0, &s, who)) return rc;
+        if (s.strands) return fail(WR_ERR_UNSUPPORTED, who + "a WRS3 stream: stranded segments are not decoded in a batch (wr_decode_host_seg reads them)");
+        for (int l = 0; l < s.nlay; l++) lanes[l] += s.nseg[l];
+        if (s.nlay > maxlay) maxlay = s.nlay;
         if (info->wlev) wlev_any = kWavLvl;
     }
     for (int l = 0; l < maxlay; l++)
@@ -2553,23 +2657,24 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
         std::lock_guard<std::mutex> gather(pool->planes.gather_mu);  // one decode at a time gathers its planes (decode_impl)
         for (int f = 0; f < nfields; f++) {
             BatchField& b = bf[f];
-            for (int l = 0; l < b.nlay; l++) {
+            for (int l = 0; l < b.s.nlay; l++) {
                 b.plane[l] = bufs.take(batch_plane_bytes(n));
                 b.blob[l] = bufs.take(infos[f].len_enc_vec[l]);
-                b.work[l] = bufs.take(batch_work_bytes(b.nseg[l]));
+                b.work[l] = bufs.take(batch_work_bytes(b.s.nseg[l]));
                 if (!b.plane[l] || !b.blob[l] || !b.work[l]) return fail_at("field", f, WR_ERR_HIP);
             }
-            if (b.brick && !(b.perm = bufs.take(batch_perm_bytes(n, b.brick)))) return fail_at("field", f, WR_ERR_HIP);
+            if (b.s.brick && !(b.perm = bufs.take(batch_perm_bytes(n, b.s.brick)))) return fail_at("field", f, WR_ERR_HIP);
         }
         if (!(d_once = bufs.take(batch_once_bytes(nfields, n, maxlay, 0, true)))) return WR_ERR_HIP;
         if (int rc = bufs.pin(batch_pinned_bytes(nfields, maxlay))) return rc;
     }
     // ---- stage "up": one copy per blob, and its segments' offsets
     for (int f = 0; f < nfields; f++)
-        for (int l = 0; l < bf[f].nlay; l++) {
-            if (int rc = xfer_field(c, &c->x_field, bf[f].blob[l], data_encs[f] + bf[f].off[l], infos[f].len_enc_vec[l], kUp)) return fail_at("field", f, rc);
+        for (int l = 0; l < bf[f].s.nlay; l++) {
+            const SegStream& s = bf[f].s;
+            if (int rc = xfer_field(c, &c->x_field, bf[f].blob[l], data_encs[f] + s.off[l], infos[f].len_enc_vec[l], kUp)) return fail_at("field", f, rc);
             local.h2d_ms += (float)c->x_field.ms;
-            if (int rc = seg_upload_offsets(c, data_encs[f] + bf[f].off[l], bf[f].nseg[l], bf[f].work[l], bf[f].brick, 0)) return fail_at("field", f, rc);
+            if (int rc = seg_upload_offsets(data_encs[f] + s.off[l], s.head(), s.nseg[l], bf[f].work[l])) return fail_at("field", f, rc);
         }
     const double t_coded = now();
     SlotNeed need;
@@ -2592,22 +2697,16 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
                 jobs.clear();
                 for (int f = 0; f < nfields; f++) {
                     const BatchField& b = bf[f];
-                    if (b.nlay <= l) continue;
-                    wrk::SegJob j; memset(&j, 0, sizeof j);
-                    j.sym = wrk::plane_ref(b.brick ? b.perm : b.plane[l]);
-                    j.n = n; j.blob = b.blob[l]; j.cap = infos[f].len_enc_vec[l];
-                    j.offs = reinterpret_cast<unsigned long long*>(b.work[l] + 256);
-                    j.flags = reinterpret_cast<uint32_t*>(b.work[l] + 256 + up256(8 * ((size_t)b.nseg[l] + 1)));
-                    j.bad = d_bad + (size_t)l * nfields + f;
-                    j.seg = b.seg[l]; j.nseg = b.nseg[l]; j.brick = b.brick;
-                    jobs.push_back(j);
+                    if (b.s.nlay <= l) continue;
+                    jobs.push_back(seg_job(wrk::plane_ref(b.s.brick ? b.perm : b.plane[l]), b.blob[l], infos[f].len_enc_vec[l], b.work[l], n, b.s.seg[l], b.s.nseg[l], b.s.brick));
+                    jobs.back().bad = d_bad + (size_t)l * nfields + f;  // (the batch counts in one array, read back once)
                 }
                 launch_note(c, "seg_decode_batch", l, d_once + l * table, n, bufs.pinned + l * per_l, jobs[0].sym);
                 HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
                 wrk::seg_decode_batch(jobs.data(), jobs.size(), bufs.pinned + l * per_l, d_once + l * table, c->stream);
-                for (int f = 0; f < nfields; f++)  // WRS2 fields: back to the natural order, per field as in decode_seg_impl
-                    if (bf[f].nlay > l && bf[f].brick &&
-                        !wrk::plane_reorder(wrk::plane_ref(bf[f].plane[l]), bf[f].perm, bf[f].od, true, nullptr, 0, c->stream))
+                for (int f = 0; f < nfields; f++)  // WRS2 fields: back to the natural order, per field as in the single-field coder stage
+                    if (bf[f].s.nlay > l && bf[f].s.brick &&
+                        !wrk::plane_reorder(wrk::plane_ref(bf[f].plane[l]), bf[f].perm, bf[f].s.od, true, nullptr, 0, c->stream))
                         return fail(WR_ERR_ARG, "field " + std::to_string(f) + ": too many bricks");
                 HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
                 if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "batched segment decoder launch failed" + launch_describe(c));
@@ -2617,33 +2716,25 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
             HIPCHK(hipMemcpyAsync(bad.data(), d_bad, 4 * bad.size(), hipMemcpyDeviceToHost, c->stream));
             if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the batched segment decoder failed on the device" + launch_describe(c));
             for (int f = 0; f < nfields; f++)
-                for (int l = 0; l < bf[f].nlay; l++)
+                for (int l = 0; l < bf[f].s.nlay; l++)
                     if (const unsigned int k = bad[(size_t)l * nfields + f])
-                        return fail(WR_ERR_STREAM, "field " + std::to_string(f) + ": plane " + std::to_string(l) + ": " + std::to_string(k) +
-                                                       " segment(s) do not decode to their symbols");
-            for (int l = 0; l < maxlay; l++) {
-                local.plane_coder_s[l] = bufs.seconds(l);
-                local.rangecoder += local.plane_coder_s[l];
-            }
+                        return fail(WR_ERR_STREAM, "field " + std::to_string(f) + ": plane " + std::to_string(l) + ": " + bad_segments_text(k));
+            fold_coder_seconds(bufs, maxlay, &local);  // one entry per plane index
         }
         // ---- every field in turn through the slot: dequantizer, inverse transform, download
         for (int f = 0; f < nfields; f++) {
             const FieldRef& fld = flds[f];
             const wr_enc_info* const info = &infos[f];
             const BatchField& b = bf[f];
-            if (!b.nlay) {  // wrappers.cpp:462-469
-                if (fld.host) for (size_t j = 0; j < n; j++) fld.host[j] = info->midval;
-                else if (fld.host_f32) for (size_t j = 0; j < n; j++) fld.host_f32[j] = (float)info->midval;
-                else { wrk::fill(fld.dev, n, info->midval, c->stream); HIPCHK(hipStreamSynchronize(c->stream)); }
+            if (!b.s.nlay) {
+                if (int rc = fill_constant(c, fld, n, info->midval)) return rc;
                 continue;
             }
             wrk::DequantParams p;
-            memset(&p, 0, sizeof p);
-            p.nlay = b.nlay;
-            for (int l = 0; l < b.nlay; l++) { p.deps[l] = info->deps_vec[l]; p.minval[l] = info->minval_vec[l]; p.q[l] = wrk::plane_ref(b.plane[l]); }
+            if (int rc = dequant_params(info, b.s.nlay, n, [&](int l) { return wrk::plane_ref(b.plane[l]); }, &p)) return fail_at("field", f, rc);
             double* const d_fld = fld.dev ? fld.dev : slot->field;
             float* d_f32 = nullptr;
-            launch_note(c, "dequant", b.nlay - 1, d_fld, n, nullptr, p.q[b.nlay - 1]);
+            launch_note(c, "dequant", b.s.nlay - 1, d_fld, n, nullptr, p.q[b.s.nlay - 1]);
             int rc = inverse_from_planes(c, slot.get(), d_fld, nx, ny, nz, (int)info->wlev, p, fld.host_f32 ? &d_f32 : nullptr);
             if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
             if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the decoder's kernel stage failed on the device" + launch_describe(c));
@@ -2762,24 +2853,12 @@ int wr_dev_seg_decode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_
     }
     std::lock_guard<std::mutex> lk(c->mu);
     // every header, then every index, come to the host and are validated before anything is launched for any job
-    std::vector<std::vector<uint8_t>> front(njobs);
-    std::vector<uint32_t> seg(njobs, 0), nseg(njobs, 0);
+    std::vector<Front> front(njobs);
     unsigned long long lanes = 0;
     for (int j = 0; j < njobs; j++) {
         const std::string who = "job " + std::to_string(j) + ": ";
-        front[j].resize(wrseg::kHeaderBytes);
-        if (blob_len[j] < front[j].size()) return fail(WR_ERR_STREAM, who + "segmented plane: shorter than its header");
-        HIPCHK(hipMemcpy(front[j].data(), d_blob[j], front[j].size(), hipMemcpyDeviceToHost));
-        if (memcmp(front[j].data(), wrseg::kMagicStrands, 4) == 0)
-            return fail(WR_ERR_UNSUPPORTED, who + "a WRS3 blob: stranded segments are not decoded in a batch (wr_dev_seg_decode reads them)");
-        const char* why = wrseg::check_index(front[j].data(), front[j].size(), blob_len[j], n, &seg[j], &nseg[j]);
-        if (why == wrseg::kIndexNotAvailable) {  // (the index fits into the blob: check_index has looked)
-            front[j].resize(front[j].size() + 4 * (size_t)wrseg::get_u32(front[j].data() + 8));
-            HIPCHK(hipMemcpy(front[j].data(), d_blob[j], front[j].size(), hipMemcpyDeviceToHost));
-            why = wrseg::check_index(front[j].data(), front[j].size(), blob_len[j], n, &seg[j], &nseg[j]);
-        }
-        if (why) return fail(WR_ERR_STREAM, who + why);
-        lanes += nseg[j];
+        if (int rc = fetch_front(d_blob[j], blob_len[j], n, false, "a WRS3 blob: stranded segments are not decoded in a batch (wr_dev_seg_decode reads them)", who, &front[j])) return rc;
+        lanes += front[j].nseg;
     }
     if (lanes >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the batch has 2^31 segments or more");
     if (!lanes) return WR_OK;
@@ -2791,17 +2870,14 @@ int wr_dev_seg_decode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_
     unsigned int* const d_bad = reinterpret_cast<unsigned int*>(d_once + table);
     std::vector<wrk::SegJob> jobs(njobs);
     for (int j = 0; j < njobs; j++) {
-        wrk::SegJob& job = jobs[j];
-        memset(&job, 0, sizeof job);
-        job.sym = wrk::plane_ref(d_sym[j]);
-        job.n = n; job.blob = const_cast<unsigned char*>(d_blob[j]); job.cap = blob_len[j];
-        job.bad = d_bad + j; job.seg = seg[j]; job.nseg = nseg[j];
-        if (!nseg[j]) continue;
-        uint8_t* const work = bufs.take(batch_work_bytes(nseg[j]));
-        if (!work) return WR_ERR_HIP;
-        if (int rc = seg_upload_offsets(c, front[j].data(), nseg[j], work, 0, 0)) return rc;
-        job.offs = reinterpret_cast<unsigned long long*>(work + 256);
-        job.flags = reinterpret_cast<uint32_t*>(work + 256 + up256(8 * ((size_t)nseg[j] + 1)));
+        const Front& f = front[j];
+        uint8_t* work = nullptr;
+        if (f.nseg) {
+            if (!(work = bufs.take(batch_work_bytes(f.nseg)))) return WR_ERR_HIP;
+            if (int rc = seg_upload_offsets(f.bytes.data(), wrseg::kHeaderBytes, f.nseg, work)) return rc;
+        }
+        jobs[j] = seg_job(wrk::plane_ref(d_sym[j]), d_blob[j], blob_len[j], work, n, f.seg, f.nseg, 0);
+        jobs[j].bad = d_bad + j;
     }
     StageLock cu(c->pool->cu_mu);
     HIPCHK(hipMemsetAsync(d_bad, 0, 4 * (size_t)njobs, c->stream));
@@ -2813,7 +2889,7 @@ int wr_dev_seg_decode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_
     int rc = WR_OK;
     for (int j = 0; j < njobs; j++) {
         if (bad_segments) bad_segments[j] = bad[j];
-        if (bad[j] && !rc) rc = fail(WR_ERR_STREAM, "job " + std::to_string(j) + ": segmented plane: " + std::to_string(bad[j]) + " segment(s) do not decode to their symbols");
+        if (bad[j] && !rc) rc = fail(WR_ERR_STREAM, "job " + std::to_string(j) + ": segmented plane: " + bad_segments_text(bad[j]));
     }
     return rc;
 }
@@ -2952,59 +3028,41 @@ int decode_seg_roi_multi_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, i
     const bool f32 = fld.host_f32 != nullptr;
     wr_timings local; memset(&local, 0, sizeof local);
     DevPool* const pool = c->pool;
-    if (info->ntot_enc == 0) {  // a constant field: midval in every region
-        if (fld.host) for (size_t j = 0; j < total; j++) fld.host[j] = info->midval;
-        else if (fld.host_f32) for (size_t j = 0; j < total; j++) fld.host_f32[j] = (float)info->midval;
-        else { wrk::fill(fld.dev, total, info->midval, c->stream); HIPCHK(hipStreamSynchronize(c->stream)); }
-        local.total = now() - t0;
-        if (tm) *tm = local;
-        return WR_OK;
-    }
-    const int nlay = info->nlay, used = pls[0].planes;
-    if (nlay < 1) return fail(WR_ERR_ARG, "nlay out of range");
-    if (!data_enc) return fail(WR_ERR_ARG, "null coded buffer");
-    size_t off[WR_NLAYMAX + 1] = {0};
-    for (int l = 0; l < nlay; l++) off[l + 1] = off[l] + info->len_enc_vec[l];
-    if (off[nlay] > info->ntot_enc) return fail(WR_ERR_STREAM, "len_enc_vec exceeds ntot_enc");
-    if (data_len && info->ntot_enc > data_len) return fail(WR_ERR_STREAM, "ntot_enc exceeds the length of the coded buffer");
-    // every plane's header and index, used or not, are validated on the host before anything is launched (decode_seg_impl)
-    uint32_t seg[WR_NLAYMAX] = {0}, nseg[WR_NLAYMAX] = {0}, brick = 0, strands = 0;
-    if (int rc = seg_check_planes(data_enc, off, info, nlay, n, seg, nseg, &brick, &strands)) return rc;
+    // every plane's header and index, used or not, are validated (region_plan has refused what seg_stream_of would of nlay and wlev)
+    SegStream s;
+    if (int rc = seg_stream_of(nx, ny, nz, info, data_enc, data_len, &s)) return rc;
+    if (s.constant) return finish_constant(c, fld, total, info->midval, t0, &local, tm);  // midval in every region
+    const int used = pls[0].planes;
     std::vector<wrroi::Geometry> geos(pls.size());
     for (size_t i = 0; i < pls.size(); i++) geos[i] = pls[i].win;
     // a blocked stream: the union of the bricks the regions need, the same in every plane
-    wrblk::Order od{};
     std::vector<uint32_t> bricks;
-    if (brick) {
-        od = wrblk::order_of(nx, ny, nz, (int)info->wlev, brick);
-        if (od.nbricks > 0x7fffffffu) return fail(WR_ERR_ARG, "too many bricks");
-        wrblk::region_bricks_multi(od, geos.data(), geos.size(), &bricks);
+    if (s.brick) {
+        if (s.od.nbricks > 0x7fffffffu) return fail(WR_ERR_ARG, "too many bricks");
+        wrblk::region_bricks_multi(s.od, geos.data(), geos.size(), &bricks);
     }
-    // per plane the union of the segments the regions need (planes may have been cut at different lengths)
+    // per plane the union of the segments the regions need
     std::vector<uint32_t> ids[WR_NLAYMAX];
-    unsigned long long lanes = 0;
-    for (int l = 0; l < used; l++) {
-        int same = -1;
-        for (int k = 0; k < l; k++) if (seg[k] == seg[l]) same = k;
-        if (same >= 0) ids[l] = ids[same];
-        else if (brick) {
-            ids[l].resize(wrblk::region_segments_multi(od, geos.data(), geos.size(), seg[l], nullptr, 0));
-            wrblk::region_segments_multi(od, geos.data(), geos.size(), seg[l], ids[l].data(), ids[l].size());
+    seg_plane_lists(s, used, ids, [&](uint32_t seg, std::vector<uint32_t>* out) {
+        if (s.brick) {
+            out->resize(wrblk::region_segments_multi(s.od, geos.data(), geos.size(), seg, nullptr, 0));
+            wrblk::region_segments_multi(s.od, geos.data(), geos.size(), seg, out->data(), out->size());
         } else {
-            ids[l].resize(wrroi::segments_of_multi(nx, ny, nz, geos.data(), geos.size(), seg[l], nullptr, 0));
-            wrroi::segments_of_multi(nx, ny, nz, geos.data(), geos.size(), seg[l], ids[l].data(), ids[l].size());
+            out->resize(wrroi::segments_of_multi(nx, ny, nz, geos.data(), geos.size(), seg, nullptr, 0));
+            wrroi::segments_of_multi(nx, ny, nz, geos.data(), geos.size(), seg, out->data(), out->size());
         }
-        lanes += ids[l].size();
-    }
+    });
+    unsigned long long lanes = 0;
+    for (int l = 0; l < used; l++) lanes += ids[l].size();
     if (lanes >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the call has 2^31 segments or more");
-    const bool one_launch = strands == 0;
+    const bool one_launch = s.strands == 0;
     const size_t table_bytes = wrk::seg_lists_table_bytes((size_t)used);
     uint8_t* perm[WR_NLAYMAX] = {nullptr};  // the plane in stream order: one per used plane on the one-launch path
     uint8_t* d_table = nullptr;
     uint8_t* d_host_out = nullptr;
     {
         std::lock_guard<std::mutex> gather(pool->planes.gather_mu);
-        if (brick) {
+        if (s.brick) {
             bufs.perm = plane_scratch(c, n);
             bufs.bricks = plane_scratch(c, 4 * bricks.size() + 4);
             if (!bufs.perm.p || !bufs.bricks.p) return WR_ERR_HIP;
@@ -3014,13 +3072,9 @@ int decode_seg_roi_multi_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, i
                 if (!perm[l]) return WR_ERR_HIP;
             }
         }
-        for (int l = 0; l < used; l++) {
-            if (int rc = plane_prepare(c, l, n, true, false, nullptr, nullptr, false)) return rc;
-            bufs.blob[l] = plane_scratch(c, info->len_enc_vec[l]);
-            bufs.work[l] = plane_scratch(c, wrk::seg_decode_list_work_bytes(nseg[l], ids[l].size()));
-            if (!bufs.blob[l].p || !bufs.work[l].p) return WR_ERR_HIP;
-            if (l == 0 || !one_launch) if (int rc = bufs.events(l)) return rc;
-        }
+        for (int l = 0; l < used; l++)
+            if (int rc = seg_plane_bufs(c, &bufs, l, n, info->len_enc_vec[l], wrk::seg_decode_list_work_bytes(s.nseg[l], ids[l].size()), false, l == 0 || !one_launch))
+                return rc;
         if (one_launch) {
             d_table = more.take(table_bytes);
             if (!d_table) return WR_ERR_HIP;
@@ -3031,21 +3085,8 @@ int decode_seg_roi_multi_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, i
             if (!d_host_out) return WR_ERR_HIP;
         }
     }
-    // ---- stage "up": per plane the offsets table, the id list and the streams of the listed segments, once
     size_t bytes_up = 0;
-    const size_t head = wrseg::header_bytes(brick, strands);
-    if (!bricks.empty()) HIPCHK(hipMemcpy(bufs.bricks.p, bricks.data(), bricks.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    for (int l = 0; l < used; l++) {
-        const uint8_t* const front = data_enc + off[l];
-        std::vector<unsigned long long> offs((size_t)nseg[l] + 1);
-        unsigned long long run = 0;
-        for (uint32_t k = 0; k < nseg[l]; k++) { offs[k] = run; run += wrseg::get_u32(front + head + 4 * (size_t)k); }
-        offs[nseg[l]] = run;
-        HIPCHK(hipMemcpy(bufs.work[l].p + 256, offs.data(), offs.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
-        if (!ids[l].empty())
-            HIPCHK(hipMemcpy(wrk::seg_decode_list_ids(bufs.work[l].p, nseg[l]), ids[l].data(), ids[l].size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        if (int rc = seg_upload_streams(c, bufs.blob[l].p, front, head + 4 * (size_t)nseg[l], offs, ids[l], &local.h2d_ms, &bytes_up)) return rc;
-    }
+    if (int rc = seg_upload_lists(c, s, used, data_enc, &bufs, ids, bricks, &local.h2d_ms, &bytes_up)) return rc;
     g_stat[WR_STAT_ROI_BYTES_UP] += bytes_up;
     const double t_coded = now();
     const SlotNeed need = roi_multi_need(pls);
@@ -3053,88 +3094,25 @@ int decode_seg_roi_multi_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, i
     if (int rc = slot.acquire(c, need)) return rc;
     const double t_phase = now();
     wrk::DequantParams p;
-    memset(&p, 0, sizeof p);
-    p.nlay = used;
-    for (int l = 0; l < used; l++) {
-        p.deps[l] = info->deps_vec[l]; p.minval[l] = info->minval_vec[l]; p.q[l] = c->ps[l].ref;
-        if (!wrk::plane_ref_covers(p.q[l], n)) return fail(WR_ERR_HIP, "internal: the device buffer of plane " + std::to_string(l) + " has a hole");
-    }
+    if (int rc = dequant_params(info, used, n, [&](int l) { return c->ps[l].ref; }, &p)) return rc;
     void* const d_out = fld.dev ? (void*)fld.dev : (void*)d_host_out;
     int rc = WR_OK;
     {
         StageLock cu(pool->cu_mu);
         clock_warmup(c, need.field_elems);
-        const uint32_t* const d_bricks = reinterpret_cast<const uint32_t*>(bufs.bricks.p);
-        if (one_launch) {
-            wrk::SegJob jobs[WR_NLAYMAX];
-            wrk::SegList lists[WR_NLAYMAX];
-            memset(jobs, 0, sizeof jobs);
-            memset(lists, 0, sizeof lists);
-            for (int l = 0; l < used; l++) {
-                uint8_t* const work = bufs.work[l].p;
-                wrk::SegJob& job = jobs[l];
-                job.sym = brick ? wrk::plane_ref(perm[l]) : p.q[l];
-                job.n = n; job.blob = bufs.blob[l].p; job.cap = info->len_enc_vec[l];
-                job.offs = reinterpret_cast<unsigned long long*>(work + 256);
-                job.flags = reinterpret_cast<uint32_t*>(work + 256 + up256(8 * ((size_t)nseg[l] + 1)));
-                job.bad = reinterpret_cast<unsigned int*>(work);
-                job.seg = seg[l]; job.nseg = nseg[l]; job.brick = brick;
-                lists[l].ids = wrk::seg_decode_list_ids(work, nseg[l]);
-                lists[l].nlist = (uint32_t)ids[l].size();
-                HIPCHK(hipMemsetAsync(work, 0, sizeof(unsigned int), c->stream));
-                g_stat[WR_STAT_ROI_SEGMENTS] += ids[l].size();
-            }
-            launch_note(c, "seg_decode_lists", 0, bufs.blob[0].p, n, bufs.work[0].p, p.q[0]);
-            HIPCHK(hipEventRecord(bufs.ev[0], c->stream));
-            wrk::seg_decode_lists(jobs, lists, (size_t)used, more.pinned, d_table, c->stream);
-            HIPCHK(hipEventRecord(bufs.ev[1], c->stream));
-            g_stat[WR_STAT_ROI_CODER_LAUNCHES] += 1;
-            // the listed segments are in the scratch planes in stream order: the needed bricks go to their places in the planes
-            for (int l = 0; brick && l < used; l++)
-                if (!wrk::plane_reorder(p.q[l], perm[l], od, true, d_bricks, bricks.size(), c->stream)) return fail(WR_ERR_ARG, "too many bricks");
-        } else {
-            for (int l = 0; l < used; l++) {
-                launch_note(c, "seg_decode_list", l, bufs.blob[l].p, n, bufs.work[l].p, p.q[l]);
-                HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
-                wrk::seg_decode_list(bufs.blob[l].p, info->len_enc_vec[l], brick ? wrk::plane_ref(perm[l]) : p.q[l], n, seg[l], bufs.work[l].p, ids[l].size(),
-                                     c->stream, brick, strands);
-                if (brick && !wrk::plane_reorder(p.q[l], perm[l], od, true, d_bricks, bricks.size(), c->stream)) return fail(WR_ERR_ARG, "too many bricks");
-                HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
-                g_stat[WR_STAT_ROI_SEGMENTS] += ids[l].size();
-                g_stat[WR_STAT_ROI_CODER_LAUNCHES] += 1;
-            }
-        }
-        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented decoder launch failed" + launch_describe(c));
-        // the per-plane counts come back once; no dequantizer runs unless every listed segment of every plane decoded
-        unsigned int bad[WR_NLAYMAX] = {0};
-        for (int l = 0; l < used; l++) HIPCHK(hipMemcpyAsync(&bad[l], bufs.work[l].p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the segmented decoder failed on the device" + launch_describe(c));
-        for (int l = 0; l < used; l++)
-            if (bad[l]) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": " + std::to_string(bad[l]) + " segment(s) do not decode to their symbols");
-        for (int l = 0; l < (one_launch ? 1 : used); l++) {
-            local.plane_coder_s[l] = bufs.seconds(l);
-            local.rangecoder += local.plane_coder_s[l];
-        }
+        CoderCall k{&s, info, used, n, &bufs, p.q};
+        memcpy(k.perm, perm, sizeof perm);
+        k.ids = ids;
+        k.d_bricks = reinterpret_cast<const uint32_t*>(bufs.bricks.p); k.nbricks = bricks.size();
+        k.host_table = more.pinned; k.d_table = d_table;  // (both null on a WRS3 stream: a launch per plane)
+        k.stat_segments = WR_STAT_ROI_SEGMENTS;
+        k.stat_launches = true;
+        if (int rc = seg_coder_stage(c, k, &local)) return rc;
         launch_note(c, "dequant_window", used - 1, slot->field, need.field_elems, nullptr, p.q[used - 1]);
-        rc = roi_multi_from_planes(c, slot.get(), d_out, nx, ny, pls, out_at, p, f32, tm ? &local : nullptr);
-        if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
-        if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the decoder's kernel stage failed on the device" + launch_describe(c));
-        pool->last_stage_end.store(now());
+        rc = kernel_stage_end(c, roi_multi_from_planes(c, slot.get(), d_out, nx, ny, pls, out_at, p, f32, tm ? &local : nullptr));
     }
     if (rc) return rc;
-    if (fld.host) {
-        if ((rc = xfer_field(c, &c->x_field, fld.host, d_host_out, total * sizeof(double), kDown)) != WR_OK) return rc;
-        local.d2h_ms = (float)c->x_field.ms;
-    } else if (fld.host_f32) {
-        if ((rc = xfer_field(c, &c->x_field, fld.host_f32, d_host_out, total * sizeof(float), kDown)) != WR_OK) return rc;
-        local.d2h_ms = (float)c->x_field.ms;
-    }
-    local.total = now() - t0;
-    local.gpu = now() - t_phase;
-    local.wait = t_phase - t_coded;
-    local.transfer = t_coded - t0;
-    if (tm) *tm = local;
-    return WR_OK;
+    return finish_call(c, fld, d_host_out, d_host_out, total, false, t0, t_coded, t_phase, &local, tm);
 }
 
 }  // namespace
@@ -3152,11 +3130,7 @@ int wr_dev_decode_planes_roi_multi(wr_ctx* c, double* d_out, int nx, int ny, int
     if (int rc = roi_multi_plans(nx, ny, nz, level, max_planes, rois, nroi, info, &pls, &out_at)) return rc;
     const size_t n = (size_t)nx * ny * nz;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (info->ntot_enc == 0 && info->nlay == 0) {  // a constant field, as wr_dev_decode_planes_roi
-        wrk::fill(d_out, out_at[(size_t)nroi], info->midval, c->stream);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return WR_OK;
-    }
+    if (info->ntot_enc == 0 && info->nlay == 0) return fill_constant(c, FieldRef{d_out}, out_at[(size_t)nroi], info->midval);
     if (!d_planes) return fail(WR_ERR_ARG, "null plane pointer");
     SlotLease slot;
     if (int rc = slot.acquire(c, roi_multi_need(pls))) return rc;
@@ -3189,27 +3163,14 @@ int wr_dev_seg_decode_lists(wr_ctx* c, int njobs, const unsigned char* const* d_
     }
     std::lock_guard<std::mutex> lk(c->mu);
     // every header, index and list is validated on the host before anything is launched for any job
-    std::vector<std::vector<uint8_t>> front(njobs);
-    std::vector<uint32_t> seg(njobs, 0), nseg(njobs, 0), brick(njobs, 0);
+    std::vector<Front> front(njobs);
     unsigned long long lanes = 0;
     for (int j = 0; j < njobs; j++) {
         const std::string who = "job " + std::to_string(j) + ": ";
-        if (blob_len[j] < wrseg::kHeaderBytes) return fail(WR_ERR_STREAM, who + "segmented plane: shorter than its header");
-        front[j].resize(std::min(blob_len[j], wrseg::kHeaderBytesBlocked));
-        HIPCHK(hipMemcpy(front[j].data(), d_blob[j], front[j].size(), hipMemcpyDeviceToHost));
-        if (memcmp(front[j].data(), wrseg::kMagicStrands, 4) == 0)
-            return fail(WR_ERR_UNSUPPORTED, who + "a WRS3 blob: stranded segments have no batched list decoder");
-        const char* why = wrseg::check_index(front[j].data(), front[j].size(), blob_len[j], n[j], &seg[j], &nseg[j], &brick[j]);
-        if (why == wrseg::kIndexNotAvailable) {  // (the index fits into the blob: check_index has looked)
-            const size_t head = memcmp(front[j].data(), wrseg::kMagicBlocked, 4) == 0 ? wrseg::kHeaderBytesBlocked : wrseg::kHeaderBytes;
-            front[j].resize(head + 4 * (size_t)wrseg::get_u32(front[j].data() + 8));
-            HIPCHK(hipMemcpy(front[j].data(), d_blob[j], front[j].size(), hipMemcpyDeviceToHost));
-            why = wrseg::check_index(front[j].data(), front[j].size(), blob_len[j], n[j], &seg[j], &nseg[j], &brick[j]);
-        }
-        if (why) return fail(WR_ERR_STREAM, who + why);
-        if (nlist[j] > nseg[j]) return fail(WR_ERR_ARG, who + "the list is longer than the plane has segments");
+        if (int rc = fetch_front(d_blob[j], blob_len[j], n[j], true, "a WRS3 blob: stranded segments have no batched list decoder", who, &front[j])) return rc;
+        if (nlist[j] > front[j].nseg) return fail(WR_ERR_ARG, who + "the list is longer than the plane has segments");
         for (size_t i = 0; i < nlist[j]; i++)
-            if (ids[j][i] >= nseg[j] || (i && ids[j][i] <= ids[j][i - 1])) return fail(WR_ERR_ARG, who + "the list must be ascending, every id below the segment count");
+            if (ids[j][i] >= front[j].nseg || (i && ids[j][i] <= ids[j][i - 1])) return fail(WR_ERR_ARG, who + "the list must be ascending, every id below the segment count");
         lanes += nlist[j];
     }
     if (lanes >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the launch has 2^31 lanes or more");
@@ -3223,34 +3184,29 @@ int wr_dev_seg_decode_lists(wr_ctx* c, int njobs, const unsigned char* const* d_
     std::vector<wrk::SegList> lists(njobs);
     std::vector<uint8_t*> works(njobs, nullptr);
     for (int j = 0; j < njobs; j++) {
-        wrk::SegJob& job = jobs[j];
-        memset(&job, 0, sizeof job);
+        const Front& f = front[j];
         memset(&lists[j], 0, sizeof lists[j]);
-        job.sym = wrk::plane_ref(d_sym[j]);
-        job.n = n[j]; job.blob = const_cast<unsigned char*>(d_blob[j]); job.cap = blob_len[j];
-        job.seg = seg[j]; job.nseg = nseg[j]; job.brick = brick[j];
-        if (!nlist[j]) continue;
-        uint8_t* const work = works[j] = bufs.take(wrk::seg_decode_list_work_bytes(nseg[j], nlist[j]));
-        if (!work) return WR_ERR_HIP;
-        if (int rc = seg_upload_offsets(c, front[j].data(), nseg[j], work, brick[j], 0)) return rc;
-        HIPCHK(hipMemcpy(wrk::seg_decode_list_ids(work, nseg[j]), ids[j], nlist[j] * sizeof(uint32_t), hipMemcpyHostToDevice));
-        job.offs = reinterpret_cast<unsigned long long*>(work + 256);
-        job.flags = reinterpret_cast<uint32_t*>(work + 256 + up256(8 * ((size_t)nseg[j] + 1)));
-        job.bad = reinterpret_cast<unsigned int*>(work);
-        lists[j].ids = wrk::seg_decode_list_ids(work, nseg[j]);
-        lists[j].nlist = (uint32_t)nlist[j];
+        if (nlist[j]) {
+            uint8_t* const work = works[j] = bufs.take(wrk::seg_decode_list_work_bytes(f.nseg, nlist[j]));
+            if (!work) return WR_ERR_HIP;
+            if (int rc = seg_upload_offsets(f.bytes.data(), wrseg::header_bytes(f.brick), f.nseg, work)) return rc;
+            HIPCHK(hipMemcpy(wrk::seg_decode_list_ids(work, f.nseg), ids[j], nlist[j] * sizeof(uint32_t), hipMemcpyHostToDevice));
+            lists[j].ids = wrk::seg_decode_list_ids(work, f.nseg);
+            lists[j].nlist = (uint32_t)nlist[j];
+        }
+        jobs[j] = seg_job(wrk::plane_ref(d_sym[j]), d_blob[j], blob_len[j], works[j], n[j], f.seg, f.nseg, f.brick);
     }
     StageLock cu(c->pool->cu_mu);
-    for (int j = 0; j < njobs; j++) if (works[j]) HIPCHK(hipMemsetAsync(works[j], 0, sizeof(unsigned int), c->stream));
+    for (int j = 0; j < njobs; j++) if (works[j]) HIPCHK(hipMemsetAsync(wrk::seg_work_bad(works[j]), 0, sizeof(unsigned int), c->stream));
     wrk::seg_decode_lists(jobs.data(), lists.data(), jobs.size(), bufs.pinned, d_table, c->stream);
     HIPCHK(hipGetLastError());
     std::vector<unsigned int> bad(njobs, 0);
-    for (int j = 0; j < njobs; j++) if (works[j]) HIPCHK(hipMemcpyAsync(&bad[j], works[j], sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    for (int j = 0; j < njobs; j++) if (works[j]) HIPCHK(hipMemcpyAsync(&bad[j], wrk::seg_work_bad(works[j]), sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     int rc = WR_OK;
     for (int j = 0; j < njobs; j++) {
         if (bad_segments) bad_segments[j] = bad[j];
-        if (bad[j] && !rc) rc = fail(WR_ERR_STREAM, "job " + std::to_string(j) + ": segmented plane: " + std::to_string(bad[j]) + " segment(s) do not decode to their symbols");
+        if (bad[j] && !rc) rc = fail(WR_ERR_STREAM, "job " + std::to_string(j) + ": segmented plane: " + bad_segments_text(bad[j]));
     }
     return rc;
 }

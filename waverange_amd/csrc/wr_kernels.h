@@ -136,6 +136,11 @@ void seg_encode(const PlaneRef& sym, size_t n, unsigned seg, uint8_t* stage, uin
 // Decode: `work` is seg_decode_work_bytes(nseg) of device memory, 256-byte aligned: {u32 bad segments} at 0 (zeroed here), at
 // 256 the nseg + 1 byte offsets of the segment streams behind the index (u64, put there by the caller from the index it
 // has VALIDATED on the host), then a u32 flag per segment (0: decoded).  A lane writes only its segment's symbols.
+// The layout is written here and nowhere else: the launchers and every caller that fills `work` or a SegJob go through these.
+inline size_t seg_work_flags_at(size_t nseg) { return 256 + ((8 * (nseg + 1) + 255) & ~(size_t)255); }
+inline unsigned int* seg_work_bad(uint8_t* work) { return reinterpret_cast<unsigned int*>(work); }
+inline unsigned long long* seg_work_offs(uint8_t* work) { return reinterpret_cast<unsigned long long*>(work + 256); }
+inline uint32_t* seg_work_flags(uint8_t* work, size_t nseg) { return reinterpret_cast<uint32_t*>(work + seg_work_flags_at(nseg)); }
 size_t seg_decode_work_bytes(size_t nseg);
 // strands != 0 (here and in seg_decode_list): the blob is a WRS3 blob of that many strands per segment (its brick may be 0);
 // `work` is laid out the same, the launch is `strands` times as wide.

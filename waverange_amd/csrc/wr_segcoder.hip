@@ -445,17 +445,17 @@ void strand_encode(const PlaneRef& sym, size_t n, unsigned seg, unsigned strands
     }
 }
 
-size_t seg_decode_work_bytes(size_t nseg) { return 256 + ((8 * (nseg + 1) + 255) & ~(size_t)255) + 4 * nseg; }
+size_t seg_decode_work_bytes(size_t nseg) { return seg_work_flags_at(nseg) + 4 * nseg; }
 
 void seg_decode(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, size_t n, unsigned seg, uint8_t* work, hipStream_t st, unsigned brick,
                 unsigned strands)
 {
     const size_t nseg = wrseg::seg_count(n, seg);
     if (!nseg) return;
-    unsigned int* const bad = reinterpret_cast<unsigned int*>(work);
+    unsigned int* const bad = seg_work_bad(work);
     (void)hipMemsetAsync(bad, 0, sizeof *bad, st);
-    const unsigned long long* const offs = reinterpret_cast<const unsigned long long*>(work + 256);
-    uint32_t* const flags = reinterpret_cast<uint32_t*>(work + 256 + ((8 * (nseg + 1) + 255) & ~(size_t)255));
+    const unsigned long long* const offs = seg_work_offs(work);
+    uint32_t* const flags = seg_work_flags(work, nseg);
     if (strands) {
         hipLaunchKernelGGL(k_strand_decode<false>, dim3((unsigned)((nseg * strands + kLanes - 1) / kLanes)), dim3(kLanes), 0, st, blob, blob_len, offs, sym,
                            n, (uint32_t)seg, (uint32_t)nseg, (uint32_t)strands, log2_of(strands), wrseg::strand_len(seg, strands), flags, bad,
@@ -474,11 +474,11 @@ void seg_decode_list(const uint8_t* blob, size_t blob_len, const PlaneRef& sym, 
                      unsigned brick, unsigned strands)
 {
     const size_t nseg = wrseg::seg_count(n, seg);
-    unsigned int* const bad = reinterpret_cast<unsigned int*>(work);
+    unsigned int* const bad = seg_work_bad(work);
     (void)hipMemsetAsync(bad, 0, sizeof *bad, st);
     if (!nseg || !nlist) return;
-    const unsigned long long* const offs = reinterpret_cast<const unsigned long long*>(work + 256);
-    uint32_t* const flags = reinterpret_cast<uint32_t*>(work + 256 + ((8 * (nseg + 1) + 255) & ~(size_t)255));
+    const unsigned long long* const offs = seg_work_offs(work);
+    uint32_t* const flags = seg_work_flags(work, nseg);
     if (strands) {
         hipLaunchKernelGGL(k_strand_decode<true>, dim3((unsigned)((nlist * strands + kLanes - 1) / kLanes)), dim3(kLanes), 0, st, blob, blob_len, offs, sym,
                            n, (uint32_t)seg, (uint32_t)nseg, (uint32_t)strands, log2_of(strands), wrseg::strand_len(seg, strands), flags, bad,
