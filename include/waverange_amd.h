@@ -697,6 +697,71 @@ int wr_decode_device_seg_roi_multi(wr_ctx *ctx, double *d_out, int nx, int ny, i
                                    const wr_box *rois, int nroi, const wr_enc_info *info, const unsigned char *data_enc,
                                    size_t data_len, wr_timings *tm);
 
+/* ---- Region decode across a batch of fields: the regions of N same-shaped fields, and at most TWO coder launches per call.
+ * The many-region call above works on one coded field; a probe's time history or the same slice of every snapshot loops over
+ * the fields and pays one coder launch -- one segment's chain -- per field (WRS3: per field and plane).  Here a job is one
+ * (non-constant field, used plane) with the union of the segments the regions need, as the many-region call lists it; the
+ * jobs of all WRS1 / WRS2 fields go into one launch and those of all WRS3 fields into a second one (csrc/wr_segbatch.hip:
+ * k_seg_decode_list_batch, k_strand_decode_list_batch).  Then every field's regions are finished as the many-region call
+ * finishes them.  No new format.
+ *   All fields have the shape nx, ny, nz; one level, one max_planes and one region list rois[0, nroi), 1 <= nroi <=
+ *   WR_ROI_MULTI_MAX, hold for the call.  The fields may differ in tolerance, plane count, wlev, seg, brick and strands, and
+ *   WRS1, WRS2 and WRS3 fields may be mixed.  With T = wr_roi_multi_elems(nx, ny, nz, level, rois, nroi, offs) the output is
+ *   ONE contiguous buffer of nfields * T elements: region i of field f lies at element f * T + offs[i] and is, bit for bit,
+ *   what wr_decode_host_seg_roi_multi (the _f32 form: ..._f32) returns for field f alone with the same arguments.  A region
+ *   that is the whole box of the level makes this the batched low-resolution decode.  Constant fields take part with no job;
+ *   as in the per-field call, max_planes may not exceed a field's plane count, so a constant field (no planes) together with
+ *   max_planes > 0 is WR_ERR_ARG ("field <f>: region 0: ").
+ * Refused with WR_ERR_ARG before anything is copied or launched: nfields < 1, a null array, more than WR_SEG_BATCH_MAX jobs,
+ * a launch of 2^31 lanes or more.  Order of validation: every field's region plans against that field's own record -- the
+ * first failure gives its code and a text starting "field <f>: region <i>: " --, then every field's stream, every plane's
+ * header and index, used or not ("field <f>: ").  The first failing field decides the return code.  The per-job counts of
+ * segments that did not decode come back once; a non-zero count is WR_ERR_STREAM naming field and plane, before any
+ * dequantiser runs, and the output buffer is then untouched.
+ * WR_STAT_ROI_SEGMENTS moves by the listed segments summed over all jobs, WR_STAT_ROI_BYTES_UP by the stream bytes uploaded,
+ * WR_STAT_ROI_CODER_LAUNCHES by the launches made: 0, 1 or 2.  wr_timings is one record for the call: `rangecoder` is the
+ * coder launches, plane_coder_s[0] carries that time and the other entries are 0; quant_ms and transform_ms are summed over
+ * fields and regions.
+ * Device memory, from the plane pool beside one work-space slot:
+ *   per job     wr_plane_pitch(n) for the plane (full pitch, sparsely filled), the blob's length, the offsets, flags and list
+ *               of its segments; a WRS2 job: wr_plane_pitch(n) for the plane in stream order
+ *   per field   WRS2: its brick list
+ *   once        the two job tables, a failure count per job; a host caller: the output, nfields * T elements, one copy down
+ * wr_seg_roi_batch_device_bytes is an upper bound of that sum for nfields fields of n samples with `planes` used planes each
+ * (host only; every blob at its bound, every list at the plane's segment count, the brick list at n entries; strands != 0:
+ * WRS3 fields; out_elems: T for a host caller, 0 for a device caller).  0 for a refused argument: nfields < 1, n == 0, planes
+ * outside 0..WR_NLAYMAX, seg, brick, strands, nfields * planes above WR_SEG_BATCH_MAX.  The call does not split a batch: one
+ * that does not get its memory fails with the pool's error before the coder launch. */
+size_t wr_seg_roi_batch_device_bytes(int nfields, size_t n, int planes, unsigned seg, unsigned brick, unsigned strands,
+                                     size_t out_elems);
+/* the free memory of the context's device in bytes, as the runtime reports it now (0: it could not be asked); what a caller
+ * holds wr_seg_roi_batch_device_bytes against when it cuts a long series of fields into calls.  Idle buffers of the library's
+ * own pools count as used, so it is a lower bound of what a call can get. */
+size_t wr_ctx_device_free_bytes(wr_ctx *ctx);
+/* host only: the lane layout of a launch over lists (csrc/wr_segbatch.h).  Job j decodes nlist[j] segments; strands[j] == 0: a
+ * WRS1 / WRS2 job of nlist[j] lanes, no padding; strands[j] == K: a WRS3 job of nlist[j] * K lanes ROUNDED UP to a multiple
+ * of 64, lane r of it being strand r & (K - 1) of list position r / K (a position >= nlist[j]: padding).  first[0 .. njobs]
+ * (may be NULL): the exclusive prefix of the jobs' lanes, as wr_seg_batch_locate takes it.  strands == NULL: all 0.  Returns
+ * the lanes of the launch, or 0 if refused (njobs outside 1..WR_SEG_BATCH_MAX, null nlist, a strand count that is not 0, 1, 2,
+ * 4, 8, 16 or 32, 2^31 lanes or more; wr_last_error() says which) -- and 0 with first[] all zeros if every list is empty. */
+size_t wr_seg_lists_lanes(int njobs, const size_t *nlist, const unsigned *strands, uint32_t *first);
+/* stage level, for tests of the kernels: wr_dev_seg_decode_lists that also accepts WRS3 blobs (strands and brick are read from
+ * each header after host validation; a WRS3 blob's symbols come out in stream order).  The WRS1 / WRS2 jobs go through one
+ * kernel and the WRS3 jobs through the other, whatever their order in the call. */
+int wr_dev_seg_decode_lists_mixed(wr_ctx *ctx, int njobs, const unsigned char *const *d_blob, const size_t *blob_len,
+                                  unsigned char *const *d_sym, const size_t *n, const uint32_t *const *ids,
+                                  const size_t *nlist, size_t *bad_segments);
+/* whole path: h_out / d_out receive nfields * T elements */
+int wr_decode_host_seg_roi_batch(wr_ctx *ctx, double *h_out, int nfields, int nx, int ny, int nz, int level, int max_planes,
+                                 const wr_box *rois, int nroi, const wr_enc_info *infos,
+                                 const unsigned char *const *data_encs, const size_t *data_lens, wr_timings *tm);
+int wr_decode_host_seg_roi_batch_f32(wr_ctx *ctx, float *h_out, int nfields, int nx, int ny, int nz, int level,
+                                     int max_planes, const wr_box *rois, int nroi, const wr_enc_info *infos,
+                                     const unsigned char *const *data_encs, const size_t *data_lens, wr_timings *tm);
+int wr_decode_device_seg_roi_batch(wr_ctx *ctx, double *d_out, int nfields, int nx, int ny, int nz, int level,
+                                   int max_planes, const wr_box *rois, int nroi, const wr_enc_info *infos,
+                                   const unsigned char *const *data_encs, const size_t *data_lens, wr_timings *tm);
+
 /* ---- The stream format of the drop-in symbols: which of the four formats the implicit-context ENCODERS write.
  * encoding_wrap, encoding_wrap_f and wr_encoding_wrap_f32 write the reference's stream unless this process-wide setting says
  * otherwise; then they run wr_encode_host_seg / _seg_blocked / _seg_strands (the _f32 forms) with the setting's parameters.

@@ -250,6 +250,17 @@ def lib():
                                                C.POINTER(Timings)]
     L.wr_decode_host_seg_roi_multi_f32.argtypes = L.wr_decode_host_seg_roi_multi.argtypes
     L.wr_decode_device_seg_roi_multi.argtypes = L.wr_decode_host_seg_roi_multi.argtypes
+    L.wr_seg_roi_batch_device_bytes.restype = C.c_size_t
+    L.wr_seg_roi_batch_device_bytes.argtypes = [C.c_int, C.c_size_t, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_size_t]
+    L.wr_ctx_device_free_bytes.restype = C.c_size_t
+    L.wr_ctx_device_free_bytes.argtypes = [_vp]
+    L.wr_seg_lists_lanes.restype = C.c_size_t
+    L.wr_seg_lists_lanes.argtypes = [C.c_int, _vp, _vp, _vp]
+    L.wr_dev_seg_decode_lists_mixed.argtypes = L.wr_dev_seg_decode_lists.argtypes
+    L.wr_decode_host_seg_roi_batch.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp,
+                                               C.POINTER(Timings)]
+    L.wr_decode_host_seg_roi_batch_f32.argtypes = L.wr_decode_host_seg_roi_batch.argtypes
+    L.wr_decode_device_seg_roi_batch.argtypes = L.wr_decode_host_seg_roi_batch.argtypes
     L.wr_fused_plan.argtypes = [C.c_int] * 4 + [C.POINTER(FusedPlan)]
     L.wr_bench_transform.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]
     # drop-in symbols (reference src/core/wrappers.h:53,70,75)
@@ -726,6 +737,54 @@ def seg_roi_segments_multi(shape, level, rois, seg=0, wlev=4, brick=None):
     got = lib().wr_seg_roi_segments_multi(nx, ny, nz, level, wlev, arr, len(rois), b, seg, ids.ctypes.data, ids.size)
     assert got == count
     return ids
+
+
+def seg_lists_lanes(nlist, strands=None):
+    """(lanes, first) of a coder launch over lists (wr_seg_lists_lanes): job j decodes nlist[j] segments with strands[j]
+    lanes each (0: a WRS1 / WRS2 job, one lane per segment and no padding; K: a WRS3 job, rounded up to whole waves).
+    first (uint32, len(nlist) + 1) is the exclusive prefix of the jobs' lanes, as seg_batch_locate takes it.  A refused
+    argument raises; lanes == 0 with first all zeros: every list is empty."""
+    nl = (C.c_size_t * max(len(nlist), 1))(*[int(v) for v in nlist])
+    st = None if strands is None else (C.c_uint * max(len(strands), 1))(*[int(v) for v in strands])
+    assert strands is None or len(strands) == len(nlist)
+    first = np.full(len(nlist) + 1, 0xFFFFFFFF, dtype=np.uint32)
+    lanes = int(lib().wr_seg_lists_lanes(len(nlist), nl, st, first.ctypes.data))
+    if not lanes and (len(nlist) < 1 or first.any()):
+        raise WaveRangeError("libwaverange_amd error -1: %s" % lib().wr_last_error().decode())
+    return lanes, first
+
+
+def seg_roi_batch_device_bytes(nfields, n, planes, seg=0, brick=0, strands=0, out_elems=0):
+    """An upper bound of the device memory a region decode over `nfields` fields of n samples with `planes` used planes each
+    takes beside the work-space slot (wr_seg_roi_batch_device_bytes; brick = 0 and strands = 0: WRS1; out_elems: the
+    elements per field a host caller receives); 0 for a refused argument."""
+    return int(lib().wr_seg_roi_batch_device_bytes(nfields, n, planes, seg, brick, strands, out_elems))
+
+
+def roi_batch_groups(nfields, n, planes, budget, seg=0, brick=0, strands=0, out_elems=0):
+    """Cuts range(nfields) into consecutive groups for Context.decode_host_seg_rois_batch: every group's
+    seg_roi_batch_device_bytes is within `budget` bytes and its jobs (fields times planes) within SEG_BATCH_MAX.  planes:
+    the used planes per field, one number or one per field (the largest of a group sizes it).  Returns (groups, alone):
+    groups is a list of ranges that cover range(nfields) in order; alone lists the fields that exceed the budget even as a
+    group of one -- each of them is a group of its own, for the caller to decode another way or to let fail."""
+    pl = [int(planes)] * nfields if np.isscalar(planes) else [int(p) for p in planes]
+    assert len(pl) == nfields
+    groups, alone = [], []
+    a = 0
+    while a < nfields:
+        b, most = a, 0
+        while b < nfields:
+            m = max(most, pl[b])
+            size = seg_roi_batch_device_bytes(b + 1 - a, n, m, seg, brick, strands, out_elems)
+            if not size or size > budget:  # (0: the jobs exceed SEG_BATCH_MAX, or an argument no group size mends)
+                break
+            b, most = b + 1, m
+        if b == a:
+            alone.append(a)
+            b = a + 1
+        groups.append(range(a, b))
+        a = b
+    return groups, alone
 
 
 def range_encode_multi(planes):
@@ -1309,6 +1368,9 @@ class Context:
     def seg_decode_lists(self, blobs, ns, lists):
         """Stage level: WRS1 / WRS2 blobs of planes of ns[j] symbols; the segments lists[j] (ascending ids) of every one are
         decoded by ONE launch into planes prefilled with 0xEE.  Returns ([symbols], [bad segments])."""
+        return self._seg_decode_lists(lib().wr_dev_seg_decode_lists, blobs, ns, lists)
+
+    def _seg_decode_lists(self, fn, blobs, ns, lists):
         bs = [np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in blobs]
         ls = [np.ascontiguousarray(l, dtype=np.uint32).ravel() for l in lists]
         nj = len(bs)
@@ -1327,11 +1389,60 @@ class Context:
             ip = (C.c_void_p * max(nj, 1))(*[l.ctypes.data if l.size else None for l in ls])
             il = (C.c_size_t * max(nj, 1))(*[l.size for l in ls])
             bad = (C.c_size_t * max(nj, 1))()
-            _check(lib().wr_dev_seg_decode_lists(self.h, nj, bp, ln, sp, nn, ip, il, bad))
+            _check(fn(self.h, nj, bp, ln, sp, nn, ip, il, bad))
             return [d.download(np.uint8, int(n)) if n else np.zeros(0, np.uint8) for d, n in zip(d_sym, ns)], [int(bad[j]) for j in range(nj)]
         finally:
             for d in d_blob + d_sym:
                 d.free()
+
+    def device_free_bytes(self):
+        """The free memory of the context's device (wr_ctx_device_free_bytes): the budget of roi_batch_groups."""
+        return int(lib().wr_ctx_device_free_bytes(self.h))
+
+    def seg_decode_lists_mixed(self, blobs, ns, lists):
+        """seg_decode_lists that also takes WRS3 blobs (wr_dev_seg_decode_lists_mixed): the WRS1 / WRS2 jobs go through one
+        launch, the WRS3 jobs through a second one.  A WRS3 blob's symbols come out in stream order."""
+        return self._seg_decode_lists(lib().wr_dev_seg_decode_lists_mixed, blobs, ns, lists)
+
+    def _decode_seg_rois_batch(self, fn, ptr, shape, level, rois, encs, max_planes):
+        nz, ny, nx = shape
+        nf = len(encs)
+        infos = (EncInfo * max(nf, 1))(*[EncInfo.from_dict(e) for e in encs])
+        datas = [np.ascontiguousarray(e["data"], dtype=np.uint8) for e in encs]
+        datas = [d if d.size else np.zeros(1, dtype=np.uint8) for d in datas]
+        ptrs = (C.c_void_p * max(nf, 1))(*[d.ctypes.data for d in datas])
+        lens = (C.c_size_t * max(nf, 1))(*[d.size for d in datas])
+        tm = Timings()
+        _check(fn(self.h, ptr, nf, nx, ny, nz, level, max_planes, _boxes(rois), len(rois), infos, ptrs, lens, C.byref(tm)))
+        return tm.as_dict()
+
+    def decode_host_seg_rois_batch(self, shape, level, rois, encs, max_planes=0, dtype=np.float64, timings=None, out=None):
+        """The regions `rois` of every coded field of `encs` (same shape; WRS1, WRS2 and WRS3 may be mixed) with at most two
+        coder launches for the whole call: a list per field of the list of region arrays -- views of one buffer of
+        len(encs) * T elements -- each bit for bit what decode_host_seg_rois gives for that field alone.  out: a flat array
+        of that size and dtype to decode into (a pinned one, for instance)."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise TypeError("decode_host_seg_rois_batch: dtype must be float64 or float32")
+        try:
+            offs = roi_multi_offsets(shape, level, rois)
+        except WaveRangeError as e:  # (there is no buffer to size: what the call itself would refuse with, WR_ERR_ARG)
+            raise WaveRangeError("libwaverange_amd error -1: %s" % e) from None
+        T = int(offs[-1])
+        if out is None:
+            out = np.empty(max(len(encs), 1) * T, dtype=dt)
+        assert out.dtype == dt and out.size >= len(encs) * T and out.flags.c_contiguous
+        fn = lib().wr_decode_host_seg_roi_batch if dt == np.dtype(np.float64) else lib().wr_decode_host_seg_roi_batch_f32
+        tm = self._decode_seg_rois_batch(fn, out.ctypes.data, shape, level, rois, encs, max_planes)
+        if timings is not None:
+            timings.update(tm)
+        flat = out.reshape(-1)
+        return [[flat[f * T + offs[i]:f * T + offs[i + 1]].reshape(roi_shape(r)) for i, r in enumerate(rois)] for f in range(len(encs))]
+
+    def decode_seg_rois_batch(self, buf, shape, level, rois, encs, max_planes=0):
+        """decode_host_seg_rois_batch into device memory: `buf` holds len(encs) * roi_multi_offsets(...)[-1] float64 elements,
+        region i of field f at element f * T + offset [i].  Returns the timings."""
+        return self._decode_seg_rois_batch(lib().wr_decode_device_seg_roi_batch, buf.ptr, shape, level, rois, encs, max_planes)
 
     def seg_encode_plane(self, plane, seg=0, strands=None):
         """Stage level: one plane of symbols (a numpy uint8 array) through the coder kernels; returns the blob (WRS1, or with

@@ -44,6 +44,16 @@ int wr_decode_host_seg_roi_f32(wr_ctx* ctx, float* h_out, int nx, int ny, int nz
                                const wr_enc_info* info, const unsigned char* data_enc, size_t data_len, wr_timings* tm) __attribute__((weak));
 }
 
+// the region decode over a batch of fields (wrdec --batch)
+extern "C" {
+int wr_decode_host_seg_roi_batch(wr_ctx* ctx, double* h_out, int nfields, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                                 const wr_enc_info* infos, const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm) __attribute__((weak));
+int wr_decode_host_seg_roi_batch_f32(wr_ctx* ctx, float* h_out, int nfields, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                                     const wr_enc_info* infos, const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm) __attribute__((weak));
+size_t wr_seg_roi_batch_device_bytes(int nfields, size_t n, int planes, unsigned seg, unsigned brick, unsigned strands, size_t out_elems) __attribute__((weak));
+size_t wr_ctx_device_free_bytes(wr_ctx* ctx) __attribute__((weak));
+}
+
 namespace wrcli {
 
 constexpr const char* kNotSupported = "not supported by this codec library";

@@ -12,6 +12,10 @@
 //                           a field with nh > 1 is addressed as the array it was coded as, z in [0, nz*nh)
 //   --planes=P              the first P quantizer planes only (default 0: all)
 //   --field=K               field K only (default: every field)
+//   --batch=N               up to N consecutive selected fields of one shape and precision go through ONE region-decode call
+//                           (wr_decode_host_seg_roi_batch: at most two coder launches for all of them); groups are cut
+//                           further so that wr_seg_roi_batch_device_bytes fits the device's free memory.  Default 1: a call
+//                           per field.  The output file is byte for byte the same whatever N is.
 // Any of --level > 0, --roi, --planes selects the partial path.  The output file then holds one record per selected field: the
 // region's elements, x fastest, in the field's precision, with record markers for the region's byte count; the header's
 // dimension inversion (idinv) is not applied.  The coded bytes are mapped, not read: only what the region needs is touched.
@@ -40,10 +44,45 @@ using std::string;
 namespace {
 
 struct Partial {
-    int level = 0, planes = 0, field = -1;
+    int level = 0, planes = 0, field = -1, batch = 1;
     bool have_roi = false, have_planes = false;
     wr_box roi{0, 0, 0, 0, 0, 0};
     bool selected() const { return level > 0 || have_roi || have_planes; }
+};
+
+// a selected field of the partial path that has passed the tool's checks
+struct Ready {
+    int it = 0, nx = 0, ny = 0, nz = 0, bx = 0, by = 0, bz = 0, nbytes = 8;
+    unsigned nlay = 0;
+    wr_box box{0, 0, 0, 0, 0, 0};
+    wr_enc_info info;
+    const unsigned char* data = nullptr;
+    size_t len = 0;
+    unsigned seg = 0, brick = 0, strands = 0;  // as the planes' headers say (the shortest seg of the used planes): what --batch sizes by
+    wrio::FieldSpec record() const  // the record that is written: the region as an array of its own
+    {
+        wrio::FieldSpec rs;
+        rs.nbytes = nbytes; rs.nx = box.x1 - box.x0; rs.ny = box.y1 - box.y0; rs.nz = box.z1 - box.z0; rs.nh = 1; rs.idinv = 0;
+        return rs;
+    }
+    // seg, brick, strands from the front of the used planes' blobs (magic, seg, nseg, then brick in a WRS2 / WRS3 header and
+    // strands in a WRS3 one); the library validates them, here they only size a call
+    void read_headers(int max_planes)
+    {
+        const int used = max_planes ? max_planes : (int)nlay;
+        size_t at = 0;
+        for (int l = 0; l < used && l < WR_NLAYMAX; at += info.len_enc_vec[l], l++) {
+            if (at + 20 > len) break;
+            const unsigned char* const h = data + at;
+            uint32_t w[5];
+            memcpy(w, h, sizeof w);
+            if (!seg || w[1] < seg) seg = w[1];
+            if (memcmp(h, "WRS1", 4) != 0) brick = w[3];
+            if (memcmp(h, "WRS3", 4) == 0) strands = w[4];
+        }
+    }
+    // whether `next` may share a batch call with this one: the shape, the precision and hence the region are the same
+    bool joins(const Ready& next) const { return nx == next.nx && ny == next.ny && nz == next.nz && nbytes == next.nbytes; }
 };
 
 void usage()
@@ -55,7 +94,7 @@ void usage()
 
 void usage_options()
 {
-    cout << "options (partial decode of segmented streams): --level=R (0..4) --roi=x0:x1,y0:y1,z0:z1 --planes=P --field=K\n";
+    cout << "options (partial decode of segmented streams): --level=R (0..4) --roi=x0:x1,y0:y1,z0:z1 --planes=P --field=K --batch=N\n";
 }
 
 // The partial path: one record per selected field.  Returns the exit status: 0, or 1 if any selected field was refused (a
@@ -73,6 +112,85 @@ int partial_decode(const Partial& pd, const string& in_name, const string& heade
     int status = 0;
     bool first = true;
     size_t at = 0;  // of the field's bytes in the .wrb
+    // a field that has passed the checks: decoded and written by decode_one, or with its neighbours by flush (--batch)
+    auto write_record = [&](const Ready& r, const double* out, const float* out32) {
+        cout << "  partial decode, field " << r.it << ": region [" << r.box.x0 << "," << r.box.x1 << ") x [" << r.box.y0 << "," << r.box.y1 << ") x [" << r.box.z0
+             << "," << r.box.z1 << ") of the " << r.bx << " x " << r.by << " x " << r.bz << " box of level " << pd.level << ", ";
+        if (pd.planes) cout << pd.planes << " of " << r.nlay << " planes"; else cout << "all " << r.nlay << " planes";
+        cout << "; the order of the dimensions is not inverted (idinv is not applied to a partial output)" << endl;
+        const wrio::FieldSpec rs = r.record();
+        unsigned char recl[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // record markers of the region's byte count, native byte order
+        const unsigned long long bytes = (unsigned long long)rs.count() * (unsigned long long)r.nbytes;
+        memcpy(recl, &bytes, 8);
+        if (out32) wrio::write_field(out_name, first, file_type, flip, rs, recl, out32);
+        else wrio::write_field(out_name, first, file_type, flip, rs, recl, out);
+        first = false;
+    };
+    auto decode_one = [&](const Ready& r) {
+        const size_t count = r.record().count();
+        std::unique_ptr<double[]> out;
+        std::unique_ptr<float[]> out32;
+        int rc;
+        if (r.nbytes == 4) {
+            out32.reset(new float[count]);
+            rc = pd.have_roi ? wr_decode_host_seg_roi_f32(ctx, out32.get(), r.nx, r.ny, r.nz, pd.level, pd.planes, &r.box, &r.info, r.data, r.len, nullptr)
+                             : wr_decode_host_seg_lowres_f32(ctx, out32.get(), r.nx, r.ny, r.nz, pd.level, pd.planes, &r.info, r.data, r.len, nullptr);
+        } else {
+            out.reset(new double[count]);
+            rc = pd.have_roi ? wr_decode_host_seg_roi(ctx, out.get(), r.nx, r.ny, r.nz, pd.level, pd.planes, &r.box, &r.info, r.data, r.len, nullptr)
+                             : wr_decode_host_seg_lowres(ctx, out.get(), r.nx, r.ny, r.nz, pd.level, pd.planes, &r.info, r.data, r.len, nullptr);
+        }
+        if (rc != 0) { cout << "Error: field " << r.it << ": " << wr_last_error() << endl; status = 1; return; }
+        write_record(r, out.get(), out32.get());
+    };
+    std::vector<Ready> group;  // --batch: consecutive fields of one shape, precision and region, waiting for one call
+    // the fields [a, b) of the group through one batch call; false: the call failed, nothing was written
+    auto decode_many = [&](size_t a, size_t b) {
+        const Ready& r0 = group[a];
+        const size_t count = r0.record().count(), nfields = b - a;
+        std::vector<wr_enc_info> infos(nfields);
+        std::vector<const unsigned char*> datas(nfields);
+        std::vector<size_t> lens(nfields);
+        for (size_t f = 0; f < nfields; f++) { infos[f] = group[a + f].info; datas[f] = group[a + f].data; lens[f] = group[a + f].len; }
+        std::unique_ptr<double[]> out;
+        std::unique_ptr<float[]> out32;
+        int rc;
+        if (r0.nbytes == 4) {
+            out32.reset(new float[count * nfields]);
+            rc = wr_decode_host_seg_roi_batch_f32(ctx, out32.get(), (int)nfields, r0.nx, r0.ny, r0.nz, pd.level, pd.planes, &r0.box, 1, infos.data(), datas.data(), lens.data(), nullptr);
+        } else {
+            out.reset(new double[count * nfields]);
+            rc = wr_decode_host_seg_roi_batch(ctx, out.get(), (int)nfields, r0.nx, r0.ny, r0.nz, pd.level, pd.planes, &r0.box, 1, infos.data(), datas.data(), lens.data(), nullptr);
+        }
+        if (rc != 0) return false;
+        for (size_t f = 0; f < nfields; f++) write_record(group[a + f], out ? out.get() + f * count : nullptr, out32 ? out32.get() + f * count : nullptr);
+        return true;
+    };
+    // The group in field order: cut into calls that fit the device's free memory and the job limit (a call of one field, and
+    // the fields of a call that failed, go the way --batch=1 goes: the same messages, the same records)
+    auto flush = [&]() {
+        size_t a = 0;
+        while (a < group.size()) {
+            const Ready& r0 = group[a];
+            const size_t budget = wr_ctx_device_free_bytes(ctx) / 4 * 3, n = (size_t)r0.nx * r0.ny * r0.nz, count = r0.record().count();
+            size_t b = a, need = 0, jobs = 0;
+            while (b < group.size()) {
+                // every field is sized as a call of its own by what its headers say -- its used planes, its shortest seg, its brick
+                // and strands --, and the sum holds the tables and the output once per field: an upper bound of the group's call
+                const Ready& r = group[b];
+                const int used = r.len ? (pd.planes ? pd.planes : (int)r.nlay) : 0;  // (a constant field has no job)
+                const size_t one = wr_seg_roi_batch_device_bytes(1, n, used, r.seg, r.brick, r.strands, count);
+                if (!one || need + one > budget || jobs + (size_t)used > WR_SEG_BATCH_MAX) break;  // (0: headers the library will refuse)
+                need += one; jobs += (size_t)used; b++;
+            }
+            if (b - a < 2 || !decode_many(a, b)) {
+                if (b == a) b = a + 1;
+                for (size_t k = a; k < b; k++) decode_one(group[k]);
+            }
+            a = b;
+        }
+        group.clear();
+    };
     for (int it = 0; it < nf; it++) {
         wrio::FieldHeader h;
         try { wrio::read_field_header(fheader, it, h); } catch (...) { status = 1; break; }
@@ -81,7 +199,7 @@ int partial_decode(const Partial& pd, const string& in_name, const string& heade
         at += len;
         if (here + len > wrb.size()) { cout << "Error: field " << it << ": " << in_name << " is shorter than its header says" << endl; status = 1; break; }
         if (pd.field >= 0 && it != pd.field) continue;
-        auto refuse = [&](const string& why) { cout << "Error: field " << it << ": " << why << endl; status = 1; };
+        auto refuse = [&](const string& why) { flush(); cout << "Error: field " << it << ": " << why << endl; status = 1; };
         if (!s.icomp) { refuse("stored uncompressed (icomp = 0): there is no partial decode of it"); continue; }
         static const unsigned char kNoBytes[4] = {0, 0, 0, 0};
         const unsigned char* data = len ? wrb.data() + here : kNoBytes;  // (a constant field has no coded bytes)
@@ -100,38 +218,20 @@ int partial_decode(const Partial& pd, const string& in_name, const string& heade
         }
         if (pd.planes > (int)h.nlay) { refuse(std::to_string(pd.planes) + " planes asked, the stream has " + std::to_string(h.nlay)); continue; }
         if (!ctx && !(ctx = contexts.borrow())) { cout << "Error: " << wr_last_error() << endl; return 1; }
-        wr_enc_info info;
-        memset(&info, 0, sizeof info);
-        info.tolabs = h.tolabs; info.midval = h.midval; info.halfspanval = h.halfspanval;
-        info.wlev = (unsigned char)h.wlev; info.nlay = (unsigned char)h.nlay; info.ntot_enc = h.ntot_enc;
-        for (unsigned l = 0; l < h.nlay; l++) { info.deps_vec[l] = h.deps_vec[l]; info.minval_vec[l] = h.minval_vec[l]; info.len_enc_vec[l] = h.len_enc_vec[l]; }
-        wrio::FieldSpec rs;  // the record that is written: the region as an array of its own
-        rs.nbytes = s.nbytes; rs.nx = box.x1 - box.x0; rs.ny = box.y1 - box.y0; rs.nz = box.z1 - box.z0; rs.nh = 1; rs.idinv = 0;
-        const size_t count = rs.count();
-        std::unique_ptr<double[]> out;
-        std::unique_ptr<float[]> out32;
-        int rc;
-        if (s.nbytes == 4) {
-            out32.reset(new float[count]);
-            rc = pd.have_roi ? wr_decode_host_seg_roi_f32(ctx, out32.get(), nx, ny, nz, pd.level, pd.planes, &box, &info, data, len, nullptr)
-                             : wr_decode_host_seg_lowres_f32(ctx, out32.get(), nx, ny, nz, pd.level, pd.planes, &info, data, len, nullptr);
-        } else {
-            out.reset(new double[count]);
-            rc = pd.have_roi ? wr_decode_host_seg_roi(ctx, out.get(), nx, ny, nz, pd.level, pd.planes, &box, &info, data, len, nullptr)
-                             : wr_decode_host_seg_lowres(ctx, out.get(), nx, ny, nz, pd.level, pd.planes, &info, data, len, nullptr);
-        }
-        if (rc != 0) { refuse(wr_last_error()); continue; }
-        cout << "  partial decode, field " << it << ": region [" << box.x0 << "," << box.x1 << ") x [" << box.y0 << "," << box.y1 << ") x [" << box.z0 << ","
-             << box.z1 << ") of the " << bx << " x " << by << " x " << bz << " box of level " << pd.level << ", ";
-        if (pd.planes) cout << pd.planes << " of " << h.nlay << " planes"; else cout << "all " << h.nlay << " planes";
-        cout << "; the order of the dimensions is not inverted (idinv is not applied to a partial output)" << endl;
-        unsigned char recl[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // record markers of the region's byte count, native byte order
-        const unsigned long long bytes = (unsigned long long)count * (unsigned long long)s.nbytes;
-        memcpy(recl, &bytes, 8);
-        if (out32) wrio::write_field(out_name, first, file_type, flip, rs, recl, out32.get());
-        else wrio::write_field(out_name, first, file_type, flip, rs, recl, out.get());
-        first = false;
+        Ready r;
+        r.it = it; r.nlay = h.nlay; r.nbytes = s.nbytes;
+        r.nx = nx; r.ny = ny; r.nz = nz; r.bx = bx; r.by = by; r.bz = bz;
+        r.box = box; r.data = data; r.len = len;
+        memset(&r.info, 0, sizeof r.info);
+        r.info.tolabs = h.tolabs; r.info.midval = h.midval; r.info.halfspanval = h.halfspanval;
+        r.info.wlev = (unsigned char)h.wlev; r.info.nlay = (unsigned char)h.nlay; r.info.ntot_enc = h.ntot_enc;
+        for (unsigned l = 0; l < h.nlay; l++) { r.info.deps_vec[l] = h.deps_vec[l]; r.info.minval_vec[l] = h.minval_vec[l]; r.info.len_enc_vec[l] = h.len_enc_vec[l]; }
+        if (pd.batch <= 1) { decode_one(r); continue; }
+        r.read_headers(pd.planes);
+        if (!group.empty() && ((int)group.size() >= pd.batch || !group.back().joins(r))) flush();
+        group.push_back(r);
     }
+    flush();
     if (ctx) contexts.give(ctx);
     return status;
 }
@@ -151,6 +251,7 @@ int main(int argc, char** argv)
         else if (wrcli::option_value(o, "roi", &v)) good = pd.have_roi = wrcli::parse_roi(v, &pd.roi);
         else if (wrcli::option_value(o, "planes", &v)) good = pd.have_planes = wrcli::parse_uint(v, &pd.planes);
         else if (wrcli::option_value(o, "field", &v)) good = have_field = wrcli::parse_uint(v, &pd.field);
+        else if (wrcli::option_value(o, "batch", &v)) good = wrcli::parse_uint(v, &pd.batch) && pd.batch >= 1;
         else { usage(); usage_options(); cout << "Error: unknown option " << o << endl; return 2; }
         if (!good) { usage(); usage_options(); cout << "Error: " << o << " is not understood" << endl; return 2; }
     }
@@ -159,6 +260,12 @@ int main(int argc, char** argv)
                            wr_decode_host_seg_lowres_f32 && wr_decode_host_seg_roi && wr_decode_host_seg_roi_f32)) {
         usage(); usage_options();
         cout << "Error: a partial decode is " << wrcli::kNotSupported << endl;
+        return 2;
+    }
+    if (pd.batch > 1 && !pd.selected()) { usage(); usage_options(); cout << "Error: --batch groups fields of a partial decode: give --level, --roi or --planes with it" << endl; return 2; }
+    if (pd.batch > 1 && !(wr_decode_host_seg_roi_batch && wr_decode_host_seg_roi_batch_f32 && wr_seg_roi_batch_device_bytes && wr_ctx_device_free_bytes)) {
+        usage(); usage_options();
+        cout << "Error: --batch is " << wrcli::kNotSupported << endl;
         return 2;
     }
     wrcli::PhaseClock clock("wrdec");

@@ -1535,19 +1535,28 @@ void seg_plane_lists(const SegStream& s, int used, std::vector<uint32_t>* ids, L
 
 // stage "up" of a partial decode: the brick list, then per used plane the offsets table, the id list and the streams of the
 // listed segments -- the others are not looked at beyond their length in the index.  *bytes_up: the payload bytes copied.
-int seg_upload_lists(wr_ctx* c, const SegStream& s, int used, const unsigned char* data_enc, SegBufs* bufs, const std::vector<uint32_t>* ids,
-                     const std::vector<uint32_t>& bricks, float* ms, size_t* bytes_up)
+// blob[l], work[l]: the device buffers of plane l; d_bricks: where the brick list goes (not looked at if there is none)
+int seg_upload_lists(wr_ctx* c, const SegStream& s, int used, const unsigned char* data_enc, uint8_t* const* blob, uint8_t* const* work_of, uint8_t* d_bricks,
+                     const std::vector<uint32_t>* ids, const std::vector<uint32_t>& bricks, float* ms, size_t* bytes_up)
 {
-    if (!bricks.empty()) HIPCHK(hipMemcpy(bufs->bricks.p, bricks.data(), bricks.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (!bricks.empty()) HIPCHK(hipMemcpy(d_bricks, bricks.data(), bricks.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     for (int l = 0; l < used; l++) {
         const uint8_t* const front = data_enc + s.off[l];
-        uint8_t* const work = bufs->work[l].p;
+        uint8_t* const work = work_of[l];
         const std::vector<unsigned long long> offs = seg_offsets(front, s.head(), s.nseg[l]);
         if (int rc = seg_upload_offsets(offs, work)) return rc;
         if (!ids[l].empty()) HIPCHK(hipMemcpy(wrk::seg_decode_list_ids(work, s.nseg[l]), ids[l].data(), ids[l].size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        if (int rc = seg_upload_streams(c, bufs->blob[l].p, front, s.head() + 4 * (size_t)s.nseg[l], offs, ids[l], ms, bytes_up)) return rc;
+        if (int rc = seg_upload_streams(c, blob[l], front, s.head() + 4 * (size_t)s.nseg[l], offs, ids[l], ms, bytes_up)) return rc;
     }
     return WR_OK;
+}
+
+int seg_upload_lists(wr_ctx* c, const SegStream& s, int used, const unsigned char* data_enc, SegBufs* bufs, const std::vector<uint32_t>* ids,
+                     const std::vector<uint32_t>& bricks, float* ms, size_t* bytes_up)
+{
+    uint8_t *blob[WR_NLAYMAX], *work[WR_NLAYMAX];
+    for (int l = 0; l < WR_NLAYMAX; l++) { blob[l] = bufs->blob[l].p; work[l] = bufs->work[l].p; }
+    return seg_upload_lists(c, s, used, data_enc, blob, work, bufs->bricks.p, ids, bricks, ms, bytes_up);
 }
 
 // One coder stage (cu_mu held): the first `planes` planes of the stream, from bufs->blob[l] into q[l].
@@ -3231,6 +3240,373 @@ int wr_decode_device_seg_roi_multi(wr_ctx* c, double* d_out, int nx, int ny, int
     FieldRef f; f.dev = d_out;
     if (!d_out) return fail(WR_ERR_ARG, "null device output pointer");
     return decode_seg_roi_multi_impl(c, f, nx, ny, nz, level, max_planes, rois, nroi, info, data_enc, data_len, tm);
+}
+
+}  // extern "C"
+
+// ---- region decode across a batch of fields (include/waverange_amd.h): the listed segments of all used planes of N fields in
+// at most TWO coder launches -- the WRS1 / WRS2 jobs through k_seg_decode_list_batch, the WRS3 jobs through
+// k_strand_decode_list_batch --, then every field's regions through the window stage of the many-region call.  A job is one
+// (non-constant field, used plane) with the union of the segments the regions need, as the many-region call lists it.  The
+// stages are the ones above; field f's part of the output is bit for bit the many-region call's for that field alone, because
+// its planes hold the same symbols wherever a window reads them and the window stage is the same code.
+namespace {
+
+// What the call takes from the plane pool, piece by piece; the driver allocates by these and wr_seg_roi_batch_device_bytes sums
+// them with every list at its longest and every blob at its bound.
+size_t roi_batch_work_bytes(size_t nseg, size_t nlist) { return wrk::seg_decode_list_work_bytes(nseg, nlist); }  // per job
+size_t roi_batch_bricks_bytes(size_t nbricks) { return 4 * nbricks + 4; }                                        // per WRS2 field
+// once per call: the two job tables and a failure count per job (plain: the WRS1 / WRS2 jobs, stranded: the WRS3 jobs)
+size_t roi_batch_tables_bytes(size_t plain, size_t stranded) { return wrk::seg_lists_table_bytes(plain) + wrk::strand_lists_table_bytes(stranded); }
+size_t roi_batch_once_bytes(size_t plain, size_t stranded) { return roi_batch_tables_bytes(plain, stranded) + up256(4 * (plain + stranded)); }
+
+// The jobs of a coder stage over lists, in the two groups the two kernels take
+struct ListJobs {
+    std::vector<wrk::SegJob> plain, stranded;
+    std::vector<wrk::SegList> plain_lists;
+    std::vector<wrk::StrandList> strand_lists;
+    void add(const wrk::SegJob& job, const uint32_t* d_ids, size_t nlist, uint32_t strands)
+    {
+        if (strands) {
+            wrk::StrandList ls;
+            memset(&ls, 0, sizeof ls);
+            ls.ids = d_ids; ls.nlist = (uint32_t)nlist;
+            ls.K = strands; ls.kshift = wrsb::strands_shift(strands); ls.L = wrseg::strand_len(job.seg, strands);
+            stranded.push_back(job);
+            strand_lists.push_back(ls);
+        } else {
+            wrk::SegList ls;
+            memset(&ls, 0, sizeof ls);
+            ls.ids = d_ids; ls.nlist = (uint32_t)nlist;
+            plain.push_back(job);
+            plain_lists.push_back(ls);
+        }
+    }
+    // the lanes of the two launches, each below 2^31 (false: refused)
+    bool lanes_ok() const
+    {
+        unsigned long long a = 0, b = 0;
+        for (const wrk::SegList& l : plain_lists) a += l.nlist;
+        for (const wrk::StrandList& l : strand_lists) b += wrsb::job_lanes(l.nlist, l.K);
+        return a < wrsb::kLaneLimit && b < wrsb::kLaneLimit;
+    }
+    // (cu_mu held) host_table / d_table: roi_batch_tables_bytes(plain.size(), stranded.size()), pinned and device.  Returns the
+    // launches made: 0, 1 or 2.
+    int launch(uint8_t* host_table, uint8_t* d_table, hipStream_t st) const
+    {
+        int launches = 0;
+        const size_t at = wrk::seg_lists_table_bytes(plain.size());
+        if (!plain.empty() && wrk::seg_decode_lists(plain.data(), plain_lists.data(), plain.size(), host_table, d_table, st)) launches++;
+        if (!stranded.empty() && wrk::strand_decode_lists(stranded.data(), strand_lists.data(), stranded.size(), host_table + at, d_table + at, st)) launches++;
+        return launches;
+    }
+};
+
+struct RoiBatchField : BatchField {  // ... of a region decode: its plans, its lists, its brick list
+    std::vector<LowresPlan> pls;
+    int used = 0;
+    std::vector<uint32_t> ids[WR_NLAYMAX], bricks;
+    uint8_t* perms[WR_NLAYMAX] = {nullptr};  // a WRS2 field: one stream-order plane per job (all jobs go in one launch)
+    uint8_t* d_bricks = nullptr;
+    int job0 = 0;  // its first job's place in the failure counts
+};
+
+int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                              const wr_enc_info* infos, const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm)
+{
+    if (nfields < 1) return fail(WR_ERR_ARG, "nfields must be at least 1");
+    if (!infos || !data_encs || !data_lens) return fail(WR_ERR_ARG, "null array");
+    if (int rc = ctx_bind(c)) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    ActiveCall active(c->pool);
+    if (tm) wrdma::enable_timing();
+    if (int rc = check_dims(nx, ny, nz, fld.dev)) return rc;
+    if (fld.none()) return fail(WR_ERR_ARG, "null output pointer");
+    const double t0 = now();
+    const size_t n = (size_t)nx * ny * nz;
+    const bool f32 = fld.host_f32 != nullptr;
+    const size_t elem = f32 ? sizeof(float) : sizeof(double);
+    wr_timings local; memset(&local, 0, sizeof local);
+    DevPool* const pool = c->pool;
+    // ---- 1. every field's region plans against its own record; 2. every field's stream, every plane's header and index
+    std::vector<RoiBatchField> bf((size_t)nfields);
+    std::vector<size_t> out_at;
+    for (int f = 0; f < nfields; f++)
+        if (int rc = roi_multi_plans(nx, ny, nz, level, max_planes, rois, nroi, &infos[f], &bf[f].pls, &out_at)) return fail_at("field", f, rc);
+    const size_t T = out_at[(size_t)nroi];  // (the regions' extents do not depend on the record)
+    size_t njobs = 0;
+    for (int f = 0; f < nfields; f++) {
+        RoiBatchField& b = bf[f];
+        if (int rc = seg_stream_of(nx, ny, nz, &infos[f], data_encs[f], data_lens[f], &b.s, "field " + std::to_string(f) + ": ")) return rc;
+        if (b.s.constant) continue;
+        b.used = b.pls[0].planes;
+        njobs += (size_t)b.used;
+    }
+    if (njobs > WR_SEG_BATCH_MAX)
+        return fail(WR_ERR_ARG, "too many jobs: the call has " + std::to_string(njobs) + " (field, plane) pairs, WR_SEG_BATCH_MAX is " + std::to_string(WR_SEG_BATCH_MAX));
+    // ---- per field the union of the bricks and, per used plane, of the segments the regions need (as the many-region call)
+    size_t nplain = 0, nstranded = 0;
+    unsigned long long lanes_plain = 0, lanes_stranded = 0;
+    SlotNeed need;
+    for (int f = 0; f < nfields; f++) {
+        RoiBatchField& b = bf[f];
+        if (b.s.constant) continue;
+        const SegStream& s = b.s;
+        std::vector<wrroi::Geometry> geos(b.pls.size());
+        for (size_t i = 0; i < b.pls.size(); i++) geos[i] = b.pls[i].win;
+        if (s.brick) {
+            if (s.od.nbricks > 0x7fffffffu) return fail(WR_ERR_ARG, "field " + std::to_string(f) + ": too many bricks");
+            wrblk::region_bricks_multi(s.od, geos.data(), geos.size(), &b.bricks);
+        }
+        seg_plane_lists(s, b.used, b.ids, [&](uint32_t seg, std::vector<uint32_t>* out) {
+            if (s.brick) {
+                out->resize(wrblk::region_segments_multi(s.od, geos.data(), geos.size(), seg, nullptr, 0));
+                wrblk::region_segments_multi(s.od, geos.data(), geos.size(), seg, out->data(), out->size());
+            } else {
+                out->resize(wrroi::segments_of_multi(nx, ny, nz, geos.data(), geos.size(), seg, nullptr, 0));
+                wrroi::segments_of_multi(nx, ny, nz, geos.data(), geos.size(), seg, out->data(), out->size());
+            }
+        });
+        for (int l = 0; l < b.used; l++) {
+            if (s.strands) lanes_stranded += wrsb::job_lanes(b.ids[l].size(), s.strands);
+            else lanes_plain += b.ids[l].size();
+        }
+        (s.strands ? nstranded : nplain) += (size_t)b.used;
+        const SlotNeed nd = roi_multi_need(b.pls);
+        need.field_elems = std::max(need.field_elems, nd.field_elems);
+        need.scratch_elems = std::max(need.scratch_elems, nd.scratch_elems);
+        need.lowbuf_elems = std::max(need.lowbuf_elems, nd.lowbuf_elems);
+    }
+    if (lanes_plain >= wrsb::kLaneLimit || lanes_stranded >= wrsb::kLaneLimit) return fail(WR_ERR_ARG, "too many segments: a launch of the call has 2^31 lanes or more");
+    c->pend_valid = false;
+    PlaneHold planes(c);
+    BatchBufs bufs(c);
+    uint8_t *d_once = nullptr, *d_host_out = nullptr;
+    {
+        std::lock_guard<std::mutex> gather(pool->planes.gather_mu);  // one decode at a time gathers its planes (decode_impl)
+        for (int f = 0; f < nfields; f++) {
+            RoiBatchField& b = bf[f];
+            for (int l = 0; l < b.used; l++) {
+                b.plane[l] = bufs.take(batch_plane_bytes(n));
+                b.blob[l] = bufs.take(infos[f].len_enc_vec[l]);
+                b.work[l] = bufs.take(roi_batch_work_bytes(b.s.nseg[l], b.ids[l].size()));
+                if (!b.plane[l] || !b.blob[l] || !b.work[l]) return fail_at("field", f, WR_ERR_HIP);
+                if (b.s.brick && !(b.perms[l] = bufs.take(batch_perm_bytes(n, b.s.brick)))) return fail_at("field", f, WR_ERR_HIP);
+            }
+            if (b.used && b.s.brick && !(b.d_bricks = bufs.take(roi_batch_bricks_bytes(b.bricks.size())))) return fail_at("field", f, WR_ERR_HIP);
+        }
+        if (njobs) {
+            if (!(d_once = bufs.take(roi_batch_once_bytes(nplain, nstranded)))) return WR_ERR_HIP;
+            if (int rc = bufs.pin(roi_batch_tables_bytes(nplain, nstranded))) return rc;
+            if (int rc = bufs.events(0)) return rc;
+        }
+        if (njobs && !fld.dev && !(d_host_out = bufs.take((size_t)nfields * T * elem))) return WR_ERR_HIP;
+    }
+    // ---- stage "up": only the listed segments' bytes
+    size_t bytes_up = 0, segments = 0;
+    for (int f = 0; f < nfields; f++) {
+        RoiBatchField& b = bf[f];
+        if (!b.used) continue;
+        if (int rc = seg_upload_lists(c, b.s, b.used, data_encs[f], b.blob, b.work, b.d_bricks, b.ids, b.bricks, &local.h2d_ms, &bytes_up)) return fail_at("field", f, rc);
+        for (int l = 0; l < b.used; l++) segments += b.ids[l].size();
+    }
+    g_stat[WR_STAT_ROI_BYTES_UP] += bytes_up;
+    const double t_coded = now();
+    SlotLease slot;
+    if (njobs)
+        if (int rc = slot.acquire(c, need)) return rc;
+    const double t_phase = now();
+    uint8_t* const d_out = fld.dev ? reinterpret_cast<uint8_t*>(fld.dev) : d_host_out;
+    int rc = WR_OK;
+    if (njobs) {
+        StageLock cu(pool->cu_mu);
+        clock_warmup(c, need.field_elems);
+        // the jobs' failure counts lie behind the tables, in the order of the fields and their planes
+        unsigned int* const d_bad = reinterpret_cast<unsigned int*>(d_once + roi_batch_tables_bytes(nplain, nstranded));
+        HIPCHK(hipMemsetAsync(d_bad, 0, 4 * njobs, c->stream));
+        ListJobs jobs;
+        int at = 0;
+        for (int f = 0; f < nfields; f++) {
+            RoiBatchField& b = bf[f];
+            b.job0 = at;
+            for (int l = 0; l < b.used; l++, at++) {
+                wrk::SegJob job = seg_job(wrk::plane_ref(b.s.brick ? b.perms[l] : b.plane[l]), b.blob[l], infos[f].len_enc_vec[l], b.work[l], n, b.s.seg[l], b.s.nseg[l], b.s.brick);
+                job.bad = d_bad + at;  // (the batch counts in one array, read back once)
+                jobs.add(job, wrk::seg_decode_list_ids(b.work[l], b.s.nseg[l]), b.ids[l].size(), b.s.strands);
+            }
+        }
+        launch_note(c, "seg_decode_lists_batch", 0, d_once, n, bufs.pinned, wrk::plane_ref(d_once));
+        HIPCHK(hipEventRecord(bufs.ev[0], c->stream));
+        const int launches = jobs.launch(bufs.pinned, d_once, c->stream);
+        HIPCHK(hipEventRecord(bufs.ev[1], c->stream));
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "batched segment decoder launch failed" + launch_describe(c));
+        g_stat[WR_STAT_ROI_SEGMENTS] += segments;  // (behind the check: a launch that failed does not count as made)
+        g_stat[WR_STAT_ROI_CODER_LAUNCHES] += (unsigned long)launches;
+        // no dequantiser runs unless every listed segment of every field decoded: the counts come back once
+        std::vector<unsigned int> bad(njobs);
+        HIPCHK(hipMemcpyAsync(bad.data(), d_bad, 4 * njobs, hipMemcpyDeviceToHost, c->stream));
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the batched segment decoder failed on the device" + launch_describe(c));
+        for (int f = 0; f < nfields; f++)
+            for (int l = 0; l < bf[f].used; l++)
+                if (const unsigned int k = bad[(size_t)bf[f].job0 + l])
+                    return fail(WR_ERR_STREAM, "field " + std::to_string(f) + ": plane " + std::to_string(l) + ": " + bad_segments_text(k));
+        fold_coder_seconds(bufs, 1, &local);
+        // ---- every field in turn: its bricks back to their places, then its regions through the window stage
+        for (int f = 0; f < nfields && rc == WR_OK; f++) {
+            const RoiBatchField& b = bf[f];
+            if (!b.used) continue;
+            for (int l = 0; l < b.used; l++)
+                if (b.s.brick && !wrk::plane_reorder(wrk::plane_ref(b.plane[l]), b.perms[l], b.s.od, true, reinterpret_cast<const uint32_t*>(b.d_bricks), b.bricks.size(), c->stream))
+                    return fail(WR_ERR_ARG, "field " + std::to_string(f) + ": too many bricks");
+            wrk::DequantParams p;
+            if ((rc = dequant_params(&infos[f], b.used, n, [&](int l) { return wrk::plane_ref(b.plane[l]); }, &p)) != WR_OK) { rc = fail_at("field", f, rc); break; }
+            launch_note(c, "dequant_window", b.used - 1, slot->field, need.field_elems, nullptr, p.q[b.used - 1]);
+            rc = roi_multi_from_planes(c, slot.get(), d_out + (size_t)f * T * elem, nx, ny, b.pls, out_at, p, f32, tm ? &local : nullptr);
+            if (rc) rc = fail_at("field", f, rc);
+        }
+        rc = kernel_stage_end(c, rc);
+    }
+    if (rc) return rc;
+    // constant fields: midval in every region (device callers here, host callers behind the one copy down)
+    for (int f = 0; f < nfields; f++)
+        if (bf[f].s.constant && fld.dev)
+            if (int rc2 = fill_constant(c, FieldRef{fld.dev + (size_t)f * T}, T, infos[f].midval)) return rc2;
+    if (njobs)  // (an all-constant call has nothing to bring down)
+        if (int rc2 = finish_call(c, fld, d_host_out, d_host_out, (size_t)nfields * T, false, t0, t_coded, t_phase, &local, nullptr)) return rc2;
+    for (int f = 0; f < nfields; f++) {
+        if (!bf[f].s.constant || fld.dev) continue;
+        FieldRef part;
+        if (f32) part.host_f32 = fld.host_f32 + (size_t)f * T;
+        else part.host = fld.host + (size_t)f * T;
+        if (int rc2 = fill_constant(c, part, T, infos[f].midval)) return rc2;
+    }
+    local.total = now() - t0;
+    if (tm) *tm = local;
+    return WR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t wr_seg_lists_lanes(int njobs, const size_t* nlist, const unsigned* strands, uint32_t* first)
+{
+    const unsigned long long lanes = wrsb::lists_lanes(njobs, nlist, strands, first);
+    if (lanes) return (size_t)lanes;
+    if (njobs < 1 || njobs > (int)wrsb::kBatchMax) { fail(WR_ERR_ARG, "njobs must be in 1.." + std::to_string(wrsb::kBatchMax)); return 0; }
+    if (!nlist) { fail(WR_ERR_ARG, "null array"); return 0; }
+    unsigned long long any = 0;
+    for (int j = 0; j < njobs; j++) {
+        if (strands && !wrsb::strands_layout_ok(strands[j])) { fail(WR_ERR_ARG, "job " + std::to_string(j) + ": strands must be 0 or one of 1, 2, 4, 8, 16, 32"); return 0; }
+        any |= nlist[j];
+    }
+    if (any) fail(WR_ERR_ARG, "too many segments: the launch has 2^31 lanes or more");
+    return 0;  // (every list empty: no lanes, first[] is all zeros, nothing was refused)
+}
+
+size_t wr_seg_roi_batch_device_bytes(int nfields, size_t n, int planes, unsigned seg, unsigned brick, unsigned strands, size_t out_elems)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (nfields < 1 || !n || planes < 0 || planes > WR_NLAYMAX || !wrseg::seg_ok(seg) || (brick && !wrblk::brick_ok(brick))) return 0;
+    if (strands && !wrseg::strands_ok(strands, seg)) return 0;
+    const size_t N = (size_t)nfields, jobs = N * (size_t)planes;
+    if (jobs > WR_SEG_BATCH_MAX) return 0;
+    const size_t nseg = wrseg::seg_count(n, seg);
+    const size_t blob = ((strands ? wr_seg_bound_strands(n, seg, strands) : brick ? wr_seg_bound_blocked(n, seg) : wr_seg_bound(n, seg)) + 15) & ~(size_t)15;
+    const size_t per_job = batch_plane_bytes(n) + up256(blob) + up256(roi_batch_work_bytes(nseg, nseg)) + batch_perm_bytes(n, brick);
+    const size_t per_field = brick && planes ? up256(roi_batch_bricks_bytes(n)) : 0;  // (a brick holds a sample at least)
+    return jobs * per_job + N * per_field + up256(roi_batch_once_bytes(strands ? 0 : jobs, strands ? jobs : 0)) + up256(N * out_elems * sizeof(double));
+}
+
+size_t wr_ctx_device_free_bytes(wr_ctx* c)
+{
+    if (ctx_bind(c)) return 0;
+    size_t free_bytes = 0, total = 0;
+    if (hipMemGetInfo(&free_bytes, &total) != hipSuccess) { (void)hipGetLastError(); fail(WR_ERR_HIP, "hipMemGetInfo failed"); return 0; }
+    return free_bytes;
+}
+
+int wr_dev_seg_decode_lists_mixed(wr_ctx* c, int njobs, const unsigned char* const* d_blob, const size_t* blob_len, unsigned char* const* d_sym, const size_t* n,
+                                  const uint32_t* const* ids, const size_t* nlist, size_t* bad_segments)
+{
+    if (njobs < 1 || njobs > WR_SEG_BATCH_MAX) return fail(WR_ERR_ARG, "njobs must be in 1.." + std::to_string(WR_SEG_BATCH_MAX));
+    if (int rc = ctx_bind(c)) return rc;
+    if (!d_blob || !blob_len || !d_sym || !n || !ids || !nlist) return fail(WR_ERR_ARG, "null array");
+    for (int j = 0; j < njobs; j++) {
+        const std::string who = "job " + std::to_string(j) + ": ";
+        if (!d_blob[j] || (n[j] && !d_sym[j]) || (nlist[j] && !ids[j])) return fail(WR_ERR_ARG, who + "null pointer");
+        if (((uintptr_t)d_sym[j] | (uintptr_t)d_blob[j]) & 15) return fail(WR_ERR_ARG, who + "plane and blob buffers must be 16-byte aligned");
+        if (bad_segments) bad_segments[j] = 0;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    // every header, index and list is validated on the host before anything is launched for any job
+    std::vector<Front> front(njobs);
+    size_t nplain = 0, nstranded = 0, any = 0;
+    for (int j = 0; j < njobs; j++) {
+        const std::string who = "job " + std::to_string(j) + ": ";
+        if (int rc = fetch_front(d_blob[j], blob_len[j], n[j], true, nullptr, who, &front[j])) return rc;
+        if (nlist[j] > front[j].nseg) return fail(WR_ERR_ARG, who + "the list is longer than the plane has segments");
+        for (size_t i = 0; i < nlist[j]; i++)
+            if (ids[j][i] >= front[j].nseg || (i && ids[j][i] <= ids[j][i - 1])) return fail(WR_ERR_ARG, who + "the list must be ascending, every id below the segment count");
+        (front[j].strands ? nstranded : nplain)++;
+        any += nlist[j];
+    }
+    if (!any) return WR_OK;
+    BatchBufs bufs(c);
+    ListJobs jobs;
+    std::vector<uint8_t*> works(njobs, nullptr);
+    for (int j = 0; j < njobs; j++) {
+        const Front& f = front[j];
+        const uint32_t* d_ids = nullptr;
+        if (nlist[j]) {
+            uint8_t* const work = works[j] = bufs.take(roi_batch_work_bytes(f.nseg, nlist[j]));
+            if (!work) return WR_ERR_HIP;
+            if (int rc = seg_upload_offsets(f.bytes.data(), wrseg::header_bytes(f.brick, f.strands), f.nseg, work)) return rc;
+            HIPCHK(hipMemcpy(wrk::seg_decode_list_ids(work, f.nseg), ids[j], nlist[j] * sizeof(uint32_t), hipMemcpyHostToDevice));
+            d_ids = wrk::seg_decode_list_ids(work, f.nseg);
+        }
+        jobs.add(seg_job(wrk::plane_ref(d_sym[j]), d_blob[j], blob_len[j], works[j], n[j], f.seg, f.nseg, f.brick), d_ids, nlist[j], f.strands);
+    }
+    if (!jobs.lanes_ok()) return fail(WR_ERR_ARG, "too many segments: a launch has 2^31 lanes or more");
+    const size_t table = roi_batch_tables_bytes(nplain, nstranded);
+    uint8_t* const d_table = bufs.take(table);
+    if (!d_table) return WR_ERR_HIP;
+    if (int rc = bufs.pin(table)) return rc;
+    StageLock cu(c->pool->cu_mu);
+    for (int j = 0; j < njobs; j++) if (works[j]) HIPCHK(hipMemsetAsync(wrk::seg_work_bad(works[j]), 0, sizeof(unsigned int), c->stream));
+    jobs.launch(bufs.pinned, d_table, c->stream);
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned int> bad(njobs, 0);
+    for (int j = 0; j < njobs; j++) if (works[j]) HIPCHK(hipMemcpyAsync(&bad[j], wrk::seg_work_bad(works[j]), sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    int rc = WR_OK;
+    for (int j = 0; j < njobs; j++) {
+        if (bad_segments) bad_segments[j] = bad[j];
+        if (bad[j] && !rc) rc = fail(WR_ERR_STREAM, "job " + std::to_string(j) + ": segmented plane: " + bad_segments_text(bad[j]));
+    }
+    return rc;
+}
+
+int wr_decode_host_seg_roi_batch(wr_ctx* c, double* h_out, int nfields, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                                 const wr_enc_info* infos, const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm)
+{
+    FieldRef f; f.host = h_out;
+    return decode_seg_roi_batch_impl(c, f, nfields, nx, ny, nz, level, max_planes, rois, nroi, infos, data_encs, data_lens, tm);
+}
+
+int wr_decode_host_seg_roi_batch_f32(wr_ctx* c, float* h_out, int nfields, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                                     const wr_enc_info* infos, const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm)
+{
+    FieldRef f; f.host_f32 = h_out;
+    return decode_seg_roi_batch_impl(c, f, nfields, nx, ny, nz, level, max_planes, rois, nroi, infos, data_encs, data_lens, tm);
+}
+
+int wr_decode_device_seg_roi_batch(wr_ctx* c, double* d_out, int nfields, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                                   const wr_enc_info* infos, const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm)
+{
+    FieldRef f; f.dev = d_out;
+    if (!d_out) return fail(WR_ERR_ARG, "null device output pointer");
+    return decode_seg_roi_batch_impl(c, f, nfields, nx, ny, nz, level, max_planes, rois, nroi, infos, data_encs, data_lens, tm);
 }
 
 }  // extern "C"

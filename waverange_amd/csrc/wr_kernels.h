@@ -205,6 +205,19 @@ struct SegList {
 };
 size_t seg_lists_table_bytes(size_t njobs);
 size_t seg_decode_lists(const SegJob* jobs, const SegList* lists, size_t njobs, uint8_t* host_table, uint8_t* table, hipStream_t st);
+// The same for WRS3 blobs (k_strand_decode_list_batch): job j decodes its listed segments with K lanes each, as
+// k_strand_decode<true> launched for the job alone would.  The record stands next to SegList; SegJob is as above (its brick is
+// not looked at: the header of a WRS3 blob has one length).  first[] is the prefix of the jobs' lanes, each job's rounded up to
+// a whole wave (wrsb::lists_lanes in wr_segbatch.h).  `table`: strand_lists_table_bytes(njobs) of device memory, 256-byte
+// aligned; host_table as above.  Returns the lanes of the launch (a multiple of 64; the caller keeps them below 2^31).
+struct StrandList {
+    const uint32_t* ids;
+    uint32_t nlist;
+    uint32_t K, kshift, L;  // strands per segment, log2(K), strand_len(seg, K)
+    uint32_t pad[2];
+};
+size_t strand_lists_table_bytes(size_t njobs);
+size_t strand_decode_lists(const SegJob* jobs, const StrandList* lists, size_t njobs, uint8_t* host_table, uint8_t* table, hipStream_t st);
 
 // ---- the blocked symbol order of WRS2 (wr_blocked.hip; the order itself and its host geometry: wr_blocked.h).  `nat` is the
 // plane in natural order, `blk` the same n bytes in the blocked order, one array.  Forward: blk := nat permuted; inverse:

@@ -14,6 +14,8 @@
 //   k_seg_decode_list_batch   k_seg_decode<true> behind the locator: a job carries an ascending list of segment ids, first[] is
 //                        the exclusive prefix of the jobs' LIST LENGTHS, and lane g takes segment ids[g - first[j]] of job j.  The
 //                        planes of one stream, each with the union of the segments some regions need, go into one launch.
+//   k_strand_decode_list_batch   (at the end of the file) k_strand_decode<true> behind the locator: the WRS3 jobs of a region
+//                        decode over a batch of fields; a job's lanes are its list length times K, rounded up to a whole wave.
 //
 // The coder steps are wr_segcoder.h's and the lane's tools wr_segcoder_dev.h's, as in wr_segcoder.hip: every blob is byte for
 // byte the single-plane kernels' blob.
@@ -295,6 +297,91 @@ size_t seg_decode_lists(const SegJob* jobs, const SegList* lists, size_t njobs, 
     (void)hipMemcpyAsync(table, host_table, seg_lists_table_bytes(njobs), hipMemcpyHostToDevice, st);
     hipLaunchKernelGGL(k_seg_decode_list_batch, dim3((unsigned)((total + kLanes - 1) / kLanes)), dim3(kLanes), 0, st, reinterpret_cast<const SegJob*>(table),
                        reinterpret_cast<const SegList*>(table + at_lists), reinterpret_cast<const uint32_t*>(table + at_first), (uint32_t)njobs);
+    return total;
+}
+
+// ---- stranded (WRS3) jobs behind the locator: the coder launch of a region decode over a batch of fields -------------------
+namespace {
+
+static_assert(kLanes == (int)wrsb::kWaveLanes, "the host's lane layout rounds a job to the coder kernels' workgroup");
+
+// k_strand_decode<true> behind the locator.  first[] is the exclusive prefix of the jobs' lanes, job j's being nlist_j * K_j
+// rounded up to a multiple of kLanes (wrsb::lists_lanes), so first[njobs] is a multiple of kLanes too: a workgroup -- one
+// wave -- lies inside one job or past the end, K is uniform in it, and the K lanes of a segment sit aligned in it.  Lane
+// first[j] + r is strand r & (K - 1) of list position i = r >> kshift and takes segment ids[i] if i < nlist; the other lanes of
+// the job are padding.  Padding lanes and lanes past the end are not live, but nobody returns before the shuffles.
+__global__ __launch_bounds__(kLanes) void k_strand_decode_list_batch(const SegJob* jobs, const StrandList* lists, const uint32_t* first, uint32_t njobs)
+{
+    __shared__ uint32_t tab[256 * kLanes];
+    const uint32_t lane = threadIdx.x;
+    const size_t g = (size_t)blockIdx.x * kLanes + lane;
+    bool live = g < first[njobs];
+    uint32_t jb = 0, r = 0;
+    if (live) wrsb::locate(first, njobs, (uint32_t)g, &jb, &r);
+    const SegJob& job = jobs[jb];  // (a lane past the end looks at job 0 and decodes nothing)
+    const StrandList& ls = lists[jb];
+    const uint32_t K = ls.K, L = ls.L, j = r & (K - 1);
+    const uint32_t i = r >> ls.kshift;
+    live = live && i < ls.nlist;
+    const size_t k = live ? ls.ids[i] : 0;
+    const uint32_t seg = job.seg, nseg = job.nseg;
+    live = live && k < nseg;  // (the K lanes of a segment agree; nobody returns before the shuffles)
+    uint32_t why = 0;
+    if (live) {
+        LdsTable t{tab + lane};
+        const size_t n = job.n;
+        const uint8_t* const blob = job.blob;
+        const size_t blob_len = job.cap;
+        const size_t base = k * seg;
+        const uint32_t bs = n - base < seg ? (uint32_t)(n - base) : seg;
+        // (the host has validated the index: the records lie inside the blob, in order, aligned, each no longer than one can be)
+        const size_t front = wrseg::kHeaderBytesStrands + 4 * (size_t)nseg;
+        const unsigned long long o0 = job.offs[k], o1 = job.offs[k + 1];
+        const uint8_t* const rec = blob + front + o0;
+        why = wrseg::kRecOverflow;
+        if (o1 >= o0 && front + o1 <= blob_len && o1 - o0 <= wrseg::record_bound(seg, K) && !(reinterpret_cast<uintptr_t>(rec) & 3)) {
+            uint32_t tlen = 0, off = 0, len = 0;
+            why = wrseg::check_record(rec, (size_t)(o1 - o0), K, L, bs, j, &tlen, &off, &len);
+            wrseg::Dec d;
+            if (!why) {
+                d.in.open(rec + 4 * (size_t)(K + 1), tlen, blob, blob + blob_len);
+                why = wrseg::decode_model(d, t, bs);
+            }
+            const uint32_t s0 = j * L, m = s0 < bs ? (bs - s0 < L ? bs - s0 : L) : 0;
+            if (!why && m) {
+                d.in.open(rec + off, len, blob, blob + blob_len);
+                SymSink sink{SegSpan(job.sym, base + s0, m), m, 0, 0};
+                why = wrseg::decode_strand(d, t, sink, m, bs);
+                sink.flush();
+            }
+        }
+    }
+    for (uint32_t off = 1; off < K; off <<= 1) why |= __shfl_xor(why, (int)off);
+    if (live && j == 0) {
+        job.flags[k] = why;
+        if (why) atomicAdd(job.bad, 1u);
+    }
+}
+
+}  // namespace
+
+size_t strand_lists_table_bytes(size_t njobs) { return seg_batch_table_bytes(njobs) + up256(njobs * sizeof(StrandList)); }
+
+size_t strand_decode_lists(const SegJob* jobs, const StrandList* lists, size_t njobs, uint8_t* host_table, uint8_t* table, hipStream_t st)
+{
+    // the table of seg_decode_lists with first[] over the jobs' lanes (whole waves each), and the strand records behind it
+    const size_t at_first = up256(njobs * sizeof(SegJob)), at_lists = seg_batch_table_bytes(njobs);
+    memset(host_table, 0, strand_lists_table_bytes(njobs));
+    memcpy(host_table, jobs, njobs * sizeof(SegJob));
+    memcpy(host_table + at_lists, lists, njobs * sizeof(StrandList));
+    uint32_t* const first = reinterpret_cast<uint32_t*>(host_table + at_first);
+    size_t total = 0;
+    for (size_t j = 0; j < njobs; j++) { first[j] = (uint32_t)total; total += (size_t)wrsb::job_lanes(lists[j].nlist, lists[j].K); }
+    first[njobs] = (uint32_t)total;
+    if (!total) return 0;
+    (void)hipMemcpyAsync(table, host_table, strand_lists_table_bytes(njobs), hipMemcpyHostToDevice, st);
+    hipLaunchKernelGGL(k_strand_decode_list_batch, dim3((unsigned)(total / kLanes)), dim3(kLanes), 0, st, reinterpret_cast<const SegJob*>(table),
+                       reinterpret_cast<const StrandList*>(table + at_lists), reinterpret_cast<const uint32_t*>(table + at_first), (uint32_t)njobs);
     return total;
 }
 
