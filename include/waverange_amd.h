@@ -115,6 +115,7 @@ void ind_p2w_3d(int lvlin, int n1, int n2, int n3, int i1in, int i2in, int i3in,
 #define WR_ERR_UNSUPPORTED (-3)
 #define WR_ERR_STREAM (-4)
 #define WR_ERR_OVERFLOW (-5)
+#define WR_ERR_BUDGET (-6) /* an encode to a byte budget: no tolerance of the grid fits the budget */
 
 typedef struct wr_ctx wr_ctx;
 
@@ -199,6 +200,8 @@ int wr_set_device_slots(int device, int nslots);
 #define WR_STAT_ROI_BYTES_UP 14 /* coded payload bytes those calls have copied to the device (the offsets tables are not counted) */
 #define WR_STAT_ROI_CODER_LAUNCHES 15 /* coder kernel launches of the region decodes: one per used plane of a single-region call and
                                        * of a multi-region call on a WRS3 stream, one per multi-region call on a WRS1 / WRS2 stream */
+#define WR_STAT_BUDGET_CODER_RUNS 16 /* planes the encodes to a byte budget (wr_encode_*_seg_budget) have handed to the segment coder:
+                                      info->nlay per call, however many tolerances the search looked at */
 unsigned long wr_stat(int what);
 /* Hands the idle buffers of the device's plane pool back to the device (the pool keeps the plane memory of finished calls for
  * the next ones: after a burst of concurrent calls that can be most of the HBM).  Buffers in use are not touched. */
@@ -360,6 +363,60 @@ int wr_encode_device_seg(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, int
                          wr_timings *tm);
 int wr_decode_device_seg(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, const wr_enc_info *info,
                          const unsigned char *data_enc, size_t data_len, wr_timings *tm);
+/* ---- Encode to a byte budget: the call picks the tolerance, and codes every plane once.
+ * The grid.  Relative tolerances are searched on the exact doubles
+ *   t(g) = ldexp(64 + (g & 63), (g >> 6) - 66),  0 <= g <= WR_BUDGET_GMAX:  t(0) = 2^-60, t(3840) = 1,
+ * neighbours at most a factor 65/64 apart.  wr_budget_tol(g) is t(g) (g clamped to the grid); wr_budget_index(tolrel) the
+ * smallest g with t(g) >= tolrel, clamped to the grid.
+ * The bound.  wr_seg_size_bound_host_ref(sym, n, seg) is an upper bound on wr_seg_encode_host_ref(sym, n, seg, ...) computed
+ * from the segments' histograms alone: 12 + 4 nseg bytes of header and index, and per segment
+ *   floor(bits / 8) + 5,  bits = 2 (1 + loss(2)) + 256 (16 + loss(2^16)) + bs (log2(bs) + loss(bs)) - sum c_s log2(c_s)
+ * with bs the segment's symbols, c_s the count of symbol s and loss(t) = -log2(1 - t / 2^23), the rounding loss of a coder
+ * step.  The arithmetic is integer (bits in units of 2^-12, from a table rounded in the safe direction), so the GPU gives
+ * the same number.  0: seg refused.  B(g), the bound of a field at t(g), is the sum of this over the planes the quantizer
+ * loop produces for cutoffvec = { t(g) }.
+ * The call.  wr_encode_*_seg_budget take the arguments of wr_encode_host_seg / _f32 / wr_encode_device_seg with the cutoff
+ * vector replaced by max_bytes and tol_min, and a result record.  With g_min = wr_budget_index(tol_min) they return a g in
+ * [g_min, WR_BUDGET_GMAX] and a stream such that
+ *   it fits          B(g) <= max_bytes, hence info->ntot_enc <= res->bound = B(g) <= max_bytes;
+ *   it is tight      g == g_min or B(g - 1) > max_bytes (B is not proven monotone: this local property is the contract, not
+ *                    "the smallest g of all");
+ *   it is the same   info and data_enc are bit for bit what wr_encode_host_seg returns for cutoffvec = { t(g) } and this seg;
+ *   coded once       WR_STAT_BUDGET_CODER_RUNS grows by info->nlay; res->probe_passes counts the launches of the size probe,
+ *                    a pass over the coefficients that writes nothing.
+ * A constant field gives nlay = 0, g = g_min, bound = 0.  WR_ERR_BUDGET: B(WR_BUDGET_GMAX) > max_bytes -- the floor is the
+ * headers, about 520 bytes per segment; wr_last_error() names the smallest budget that would do, and data_enc is not written.
+ * WR_ERR_UNSUPPORTED: a local cutoff (mx * my * mz > 1) and wr_ctx_set_keep_residual(ctx, 1).  WR_ERR_ARG: tol_min that is
+ * not a positive number, and what wr_encode_host_seg refuses.  The stream is WRS1; for WRS2 / WRS3 recut it with
+ * wr_transcode_host, which is lossless and runs no transform. */
+#define WR_BUDGET_GMAX 3840
+double wr_budget_tol(int g);
+int wr_budget_index(double tolrel);
+size_t wr_seg_size_bound_host_ref(const unsigned char *sym, size_t n, unsigned seg);
+typedef struct wr_budget_result {
+    int g;            /* the grid point chosen */
+    double tolrel;    /* t(g) */
+    size_t bound;     /* B(g) */
+    int probe_passes; /* launches of the size probe */
+} wr_budget_result;
+#define WR_BUDGET_PROBE_MAX 8 /* candidate steps one pass of the size probe takes */
+/* stage level, device pointers (16-byte aligned).  wr_dev_plane_size_bound: the bound of a plane of symbols, equal to
+ * wr_seg_size_bound_host_ref of them.  wr_dev_quant_size_probe: for each of the ncand <= WR_BUDGET_PROBE_MAX steps deps[k],
+ * bounds[k] = the bound of the plane (unsigned char)((d_resid[j] - minval) / deps[k] + 0.5) in the quantizer's own arithmetic
+ * (aopt = 1 / deps, bopt = -minval * aopt + 0.5); d_resid is only read and no plane is written.  ncand outside
+ * 1..WR_BUDGET_PROBE_MAX: WR_ERR_ARG. */
+int wr_dev_plane_size_bound(wr_ctx *ctx, const unsigned char *d_sym, size_t n, unsigned seg, size_t *bound);
+int wr_dev_quant_size_probe(wr_ctx *ctx, const double *d_resid, size_t n, double minval, int ncand, const double *deps,
+                            unsigned seg, size_t *bounds);
+int wr_encode_host_seg_budget(wr_ctx *ctx, const double *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                              size_t max_bytes, double tol_min, unsigned seg, wr_enc_info *info, unsigned char *data_enc,
+                              size_t cap, wr_timings *tm, wr_budget_result *res);
+int wr_encode_host_seg_budget_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my,
+                                  int mz, size_t max_bytes, double tol_min, unsigned seg, wr_enc_info *info,
+                                  unsigned char *data_enc, size_t cap, wr_timings *tm, wr_budget_result *res);
+int wr_encode_device_seg_budget(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                size_t max_bytes, double tol_min, unsigned seg, wr_enc_info *info, unsigned char *data_enc,
+                                size_t cap, wr_timings *tm, wr_budget_result *res);
 /* ---- Low-resolution decode of segmented streams: a coarse version of the field without decoding the field.
  * The transform is a Mallat decomposition (waveletcdf97_3d.c:73-78): after level r the low-pass coefficients of an nx*ny*nz
  * field sit in the corner box [0,bx) x [0,by) x [0,bz) of the coefficient array.  With h(n) = (n + 1) / 2 in integer

@@ -60,6 +60,11 @@ class Timings(C.Structure):
         return {k: (list(getattr(self, k)) if k == "plane_coder_s" else getattr(self, k)) for k, _ in self._fields_}
 
 
+class BudgetResult(C.Structure):
+    """wr_budget_result"""
+    _fields_ = [("g", C.c_int), ("tolrel", C.c_double), ("bound", C.c_size_t), ("probe_passes", C.c_int)]
+
+
 class FusedLevel(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("tiles_x", "tiles_y", "zps", "zsegs", "zlast")]
 
@@ -181,6 +186,18 @@ def lib():
     L.wr_encode_host_seg.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_uint,
                                      C.POINTER(EncInfo), _vp, C.c_size_t, C.POINTER(Timings)]
     L.wr_encode_host_seg_f32.argtypes = L.wr_encode_host_seg.argtypes
+    # an encode to a byte budget: the grid, the size bound, the stage calls and the drivers
+    L.wr_budget_tol.restype = C.c_double
+    L.wr_budget_tol.argtypes = [C.c_int]
+    L.wr_budget_index.argtypes = [C.c_double]
+    L.wr_seg_size_bound_host_ref.restype = C.c_size_t
+    L.wr_seg_size_bound_host_ref.argtypes = [_vp, C.c_size_t, C.c_uint]
+    L.wr_dev_plane_size_bound.argtypes = [_vp, _vp, C.c_size_t, C.c_uint, C.POINTER(C.c_size_t)]
+    L.wr_dev_quant_size_probe.argtypes = [_vp, _vp, C.c_size_t, C.c_double, C.c_int, _dp, C.c_uint, C.POINTER(C.c_size_t)]
+    L.wr_encode_host_seg_budget.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_double,
+                                            C.c_uint, C.POINTER(EncInfo), _vp, C.c_size_t, C.POINTER(Timings), C.POINTER(BudgetResult)]
+    L.wr_encode_host_seg_budget_f32.argtypes = L.wr_encode_host_seg_budget.argtypes
+    L.wr_encode_device_seg_budget.argtypes = L.wr_encode_host_seg_budget.argtypes
     L.wr_encode_device_seg.argtypes = L.wr_encode_host_seg.argtypes
     L.wr_decode_host_seg.argtypes = L.wr_decode_host.argtypes
     L.wr_decode_host_seg_f32.argtypes = L.wr_decode_host.argtypes
@@ -318,6 +335,7 @@ STAT_WINDOW_WAIT_MS = 10
 STAT_LOWRES_SEGMENTS, STAT_LOWRES_BYTES_UP = 11, 12
 STAT_ROI_SEGMENTS, STAT_ROI_BYTES_UP = 13, 14
 STAT_ROI_CODER_LAUNCHES = 15
+STAT_BUDGET_CODER_RUNS = 16
 
 
 def stat(what):
@@ -426,6 +444,32 @@ def range_decode(stream, n):
 
 
 SEG_DEFAULT = 59904  # WR_SEG_DEFAULT
+
+
+# ---- an encode to a byte budget (include/waverange_amd.h): the tolerance grid and the size bound of a plane, on the host
+BUDGET_GMAX = 3840
+BUDGET_PROBE_MAX = 8
+ERR_BUDGET = -6
+
+
+def budget_tol(g):
+    """t(g) = ldexp(64 + (g & 63), (g >> 6) - 66), g clamped to [0, BUDGET_GMAX] (wr_budget_tol)."""
+    return float(lib().wr_budget_tol(int(g)))
+
+
+def budget_index(tolrel):
+    """The smallest g with budget_tol(g) >= tolrel, clamped to the grid (wr_budget_index)."""
+    return int(lib().wr_budget_index(float(tolrel)))
+
+
+def seg_size_bound_host_ref(plane, seg=0):
+    """An upper bound on len(seg_encode_host_ref(plane, seg)) from the segments' histograms alone (wr_seg_size_bound_host_ref)."""
+    p = np.ascontiguousarray(plane, dtype=np.uint8).ravel()
+    src = p if p.size else np.zeros(1, np.uint8)
+    b = int(lib().wr_seg_size_bound_host_ref(src.ctypes.data, p.size, seg))
+    if not b:
+        raise WaveRangeError(_BAD_SEG)
+    return b
 
 
 def seg_bound(n, seg=0):
@@ -1242,6 +1286,59 @@ class Context:
         """encode_host_seg with the field resident on the device (`buf` is consumed, as by encode)."""
         fn = lib().wr_encode_device_seg_strands if strands is not None else lib().wr_encode_device_seg if brick is None else lib().wr_encode_device_seg_blocked
         return self._encode_seg(fn, buf.ptr, shape, tolrel, wtflag, seg, out, cutoff, m, brick, strands)
+
+    # ---- encode to a byte budget: the library picks the tolerance on the grid budget_tol(g), every plane is coded once
+    def _encode_seg_budget(self, fn, ptr, shape, max_bytes, tol_min, wtflag, seg, out, m):
+        nz, ny, nx = shape
+        data = out if out is not None else np.empty(self._seg_cap(shape, seg), dtype=np.uint8)
+        info, tm, res = EncInfo(), Timings(), BudgetResult()
+        _check(fn(self.h, ptr, nx, ny, nz, wtflag, m[0], m[1], m[2], int(max_bytes), float(tol_min), seg, C.byref(info),
+                  data.ctypes.data, data.size, C.byref(tm), C.byref(res)))
+        d = info.as_dict()
+        d["data"] = data[:info.ntot_enc]
+        return d, d["data"], {"g": res.g, "tolrel": res.tolrel, "bound": res.bound, "probe_passes": res.probe_passes, "timings": tm.as_dict()}
+
+    def encode_host_seg_budget(self, fld, max_bytes, tol_min=2.0 ** -60, wtflag=1, seg=0, out=None, m=(1, 1, 1)):
+        """The WRS1 stream of `fld` at the finest tolerance of the grid, not below tol_min, whose size bound fits max_bytes
+        (wr_encode_host_seg_budget).  Returns (info, data, result): info as encode_host_seg gives it for
+        tolrel = result["tolrel"] = budget_tol(result["g"]), data = info["data"], result["bound"] >= len(data)."""
+        assert fld.dtype == np.float64 and fld.flags["C_CONTIGUOUS"]
+        return self._encode_seg_budget(lib().wr_encode_host_seg_budget, fld.ctypes.data, fld.shape, max_bytes, tol_min, wtflag, seg, out, m)
+
+    def encode_host_seg_budget_f32(self, fld, max_bytes, tol_min=2.0 ** -60, wtflag=1, seg=0, out=None, m=(1, 1, 1)):
+        if not (isinstance(fld, np.ndarray) and fld.dtype == np.float32 and fld.flags["C_CONTIGUOUS"]):
+            raise TypeError("encode_host_seg_budget_f32: a C-contiguous float32 array is required")
+        return self._encode_seg_budget(lib().wr_encode_host_seg_budget_f32, fld.ctypes.data, fld.shape, max_bytes, tol_min, wtflag, seg, out, m)
+
+    def encode_seg_budget(self, buf, shape, max_bytes, tol_min=2.0 ** -60, wtflag=1, seg=0, out=None, m=(1, 1, 1)):
+        """encode_host_seg_budget with the field resident on the device (`buf` is consumed, as by encode)."""
+        return self._encode_seg_budget(lib().wr_encode_device_seg_budget, buf.ptr, shape, max_bytes, tol_min, wtflag, seg, out, m)
+
+    def plane_size_bound(self, plane, seg=0):
+        """Stage level: the size bound of a plane of symbols, computed on the device (wr_dev_plane_size_bound)."""
+        p = np.ascontiguousarray(plane, dtype=np.uint8).ravel()
+        d_sym = self.alloc(max(p.size, 16))
+        try:
+            if p.size:
+                d_sym.upload(p)
+            got = C.c_size_t(0)
+            _check(lib().wr_dev_plane_size_bound(self.h, d_sym.ptr, p.size, seg, C.byref(got)))
+            return int(got.value)
+        finally:
+            d_sym.free()
+
+    def quant_size_probe(self, resid, minval, deps, seg=0):
+        """Stage level: the size bounds of the planes the steps `deps` would cut from the residual array `resid` (float64),
+        one pass, nothing written (wr_dev_quant_size_probe).  Returns a list of len(deps) integers."""
+        r = np.ascontiguousarray(resid, dtype=np.float64).ravel()
+        dv = np.ascontiguousarray(deps, dtype=np.float64).ravel()
+        d_res = self.to_device(r)
+        try:
+            got = (C.c_size_t * max(dv.size, 1))()
+            _check(lib().wr_dev_quant_size_probe(self.h, d_res.ptr, r.size, float(minval), int(dv.size), dv.ctypes.data_as(_dp), seg, got))
+            return [int(got[k]) for k in range(dv.size)]
+        finally:
+            d_res.free()
 
     def plane_reorder(self, plane, shape, wlev=4, brick=0, inverse=False):
         """Stage level: a plane (uint8, nz*ny*nx symbols) through the reorder kernel (wr_dev_plane_reorder).  Forward: natural

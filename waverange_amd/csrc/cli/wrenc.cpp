@@ -8,6 +8,9 @@
 // Arguments that start with "--" are options of this tool and are taken out before any of that:
 //   --format=ref|wrs1|wrs2|wrs3[:seg=N][:brick=B][:strands=K]   the stream format of the coded fields (waverange_amd.h,
 //       wr_stream_format_parse); without it the library's setting decides (WR_STREAM_FORMAT, else the reference's stream)
+//   --ratio=R   encode every compressed field to a byte budget (wr_encode_host_seg_budget): the field's bytes on disk divided
+//       by R.  TOLERANCE is then the finest tolerance the search may choose; the tool prints the one it chose.  Needs
+//       --format=wrs1.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -183,6 +186,7 @@ void usage()
     cout << "      NX=(e.g. 16), NY=(e.g. 16), NZ=(e.g. 16) and TOLERANCE=(e.g. 1.0e-16)\n";
     cout << "interactive mode if not enough arguments are passed.\n";
     cout << "option: --format=ref|wrs1|wrs2|wrs3[:seg=N][:brick=B][:strands=K] (stream format of the coded fields; default: WR_STREAM_FORMAT, else ref)\n";
+    cout << "option: --ratio=R (with --format=wrs1: every field coded into its bytes on disk / R, at the finest tolerance not below TOLERANCE that fits)\n";
 }
 
 void parse_argv(char** argv, Job& job)  // gen_enc.cpp:365-412
@@ -237,8 +241,20 @@ int main(int argc, char** argv)
     argc = wrcli::take_options(argc, argv, options);
     string format_text;
     bool have_format = false;
+    string ratio_text;
+    double ratio = 0;
     for (const string& o : options) {
         if (wrcli::option_value(o, "format", &format_text)) { have_format = true; continue; }
+        if (wrcli::option_value(o, "ratio", &ratio_text)) {
+            char* end = nullptr;
+            ratio = strtod(ratio_text.c_str(), &end);
+            if (ratio_text.empty() || *end || !(ratio >= 1.0) || !(ratio < 1e12)) {
+                usage();
+                cout << "Error: --ratio=" << ratio_text << ": a number of at least 1 is required" << endl;
+                return 2;
+            }
+            continue;
+        }
         usage();
         cout << "Error: unknown option " << o << endl;
         return 2;
@@ -252,6 +268,21 @@ int main(int argc, char** argv)
             return 2;
         }
     }
+    unsigned budget_seg = 0;
+    if (ratio > 0) {
+        if (stream_format != WR_FORMAT_WRS1) {
+            usage();
+            cout << "Error: --ratio needs --format=wrs1" << endl;
+            return 2;
+        }
+        if (!wr_encode_host_seg_budget || !wr_encode_host_seg_budget_f32 || !wr_get_stream_format || !wr_ctx_create) {
+            usage();
+            cout << "Error: --ratio: " << wrcli::kNotSupported << endl;
+            return 2;
+        }
+        wr_get_stream_format(nullptr, &budget_seg, nullptr, nullptr);
+    }
+    wrcli::ContextPool contexts;  // --ratio: one explicit context per field in flight
     wrcli::PhaseClock clock("wrenc");
 
     Job job;
@@ -306,6 +337,7 @@ int main(int argc, char** argv)
         std::vector<double> fld;
         std::unique_ptr<float[]> fld32;  // instead of fld: an fp32 record for wr_encoding_wrap_f32 (not zero-filled)
         wrcli::RawBuffer data_enc;   // setup_wr's worst case, untouched beyond the coded bytes
+        size_t cap = 0;              // its size
         std::future<void> done;
         std::ostringstream log;      // this field's lines, printed when it is written (pipelined mode)
     };
@@ -378,10 +410,11 @@ int main(int argc, char** argv)
             unsigned char nlaymax; unsigned long cap;
             setup_wr(s.nx, s.ny, s.nz * s.nh, &nlaymax, &cap);
             im.data_enc.allocate(cap);
+            im.cap = cap;
         }
         Item* ip = &im;
         const bool pipelined = depth > 0;
-        auto work = [ip, cutoff, pipelined, &scan, &clock]() {
+        auto work = [ip, cutoff, pipelined, ratio, budget_seg, &contexts, &scan, &clock]() {
             const wrio::FieldSpec& sp = ip->h.spec;
             if (pipelined) scan(*ip, ip->log);
             if (!sp.icomp) { (pipelined ? static_cast<std::ostream&>(ip->log) : cout) << "  Compression disabled" << endl; return; }
@@ -390,7 +423,34 @@ int main(int argc, char** argv)
             double cut = cutoff;
             const double t_codec = wrcli::PhaseClock::now();
             // nh > 1 folds into z (gen_enc.cpp:559,596)
-            if (ip->fld32)
+            if (ratio > 0) {  // to a byte budget: the field's bytes on disk / R, no tolerance finer than the command line's
+                const size_t budget = (size_t)((double)(sp.count() * (size_t)sp.nbytes) / ratio);
+                wr_ctx* ctx = contexts.borrow();
+                wr_enc_info info;
+                wr_budget_result res;
+                int rc = ctx ? 0 : -1;
+                if (ctx)
+                    rc = ip->fld32 ? wr_encode_host_seg_budget_f32(ctx, ip->fld32.get(), sp.nx, sp.ny, sp.nz * sp.nh, 1, 1, 1, 1, budget, cut, budget_seg,
+                                                                   &info, ip->data_enc.data(), ip->cap, nullptr, &res)
+                                   : wr_encode_host_seg_budget(ctx, ip->fld.data(), sp.nx, sp.ny, sp.nz * sp.nh, 1, 1, 1, 1, budget, cut, budget_seg, &info,
+                                                               ip->data_enc.data(), ip->cap, nullptr, &res);
+                if (ctx) contexts.give(ctx);
+                if (rc != 0) {  // (as the codec's own failures: the tool ends here, whatever other fields are in flight)
+                    cout.flush();
+                    fprintf(stderr, "Error: field with a budget of %zu bytes: %s\n", budget, wr_last_error());
+                    std::_Exit(1);
+                }
+                char line[200];
+                snprintf(line, sizeof line, "  Budget %zu bytes: relative tolerance %.17g (grid point %d), bound %zu bytes, coded %lu bytes\n", budget, res.tolrel,
+                         res.g, res.bound, info.ntot_enc);
+                (pipelined ? static_cast<std::ostream&>(ip->log) : cout) << line;
+                ip->h.tolabs = info.tolabs; ip->h.midval = info.midval; ip->h.halfspanval = info.halfspanval;
+                wlev = info.wlev; nlay = info.nlay;
+                ip->h.ntot_enc = info.ntot_enc;
+                for (int l = 0; l < WR_NLAYMAX; l++) {
+                    ip->h.deps_vec[l] = info.deps_vec[l]; ip->h.minval_vec[l] = info.minval_vec[l]; ip->h.len_enc_vec[l] = info.len_enc_vec[l];
+                }
+            } else if (ip->fld32)
                 wr_encoding_wrap_f32(sp.nx, sp.ny, sp.nz * sp.nh, ip->fld32.get(), 1, 1, 1, 1, &cut, &ip->h.tolabs, &ip->h.midval,
                                      &ip->h.halfspanval, &wlev, &nlay, &ip->h.ntot_enc, ip->h.deps_vec, ip->h.minval_vec,
                                      ip->h.len_enc_vec, ip->data_enc.data());

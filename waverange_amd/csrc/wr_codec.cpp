@@ -5,7 +5,10 @@
 //   decoding_wrap : range decoder -> dequantise-accumulate -> inverse transform                  (wrappers.cpp:456-527)
 // Compiled with hipcc, strict IEEE (-ffp-contract=off): the scalar arithmetic on deps/aopt/bopt/tolabs below must round
 // exactly as wrappers.cpp:292-340 does.
+#include <algorithm>
+
 #include "wr_blocked.h"
+#include "wr_budget.h"
 #include "wr_internal.h"
 #include "wr_lowres.h"
 #include "wr_roi.h"
@@ -133,10 +136,15 @@ int dequant_params(const wr_enc_info* info, int used, size_t n, RefOf ref_of, wr
 // device (the download starts there).  *resid = where the coefficient array / residual lives afterwards.
 // f32 != nullptr (an fp32 field on the fused path only): the field is that array, which the fused forward transform reads
 // as it is; d_fld is then n doubles of work space (may be f32's memory: the transform has consumed it before it is used).
+// pick != nullptr (an encode to a byte budget): the tolerance is not known when the loop starts.  Before every plane's step is
+// formed, pick is told what the plane is cut from -- its number, the residual's range, the planes before and the array they
+// apply to -- and sets info->tolabs: 0 for a plane that stays full, the chosen tolerance's for the last one.
+using PickStep = std::function<int(unsigned ilay, double lo, double hi, const wrk::QuantPrev& prev, const double* d_coef, const Prologue& p, double* tolabs)>;
+
 template <class PlaneBuf, class HistBuf, class AfterQuant, class PlaneReady>
 int encode_planes_core(wr_ctx* c, Slot* slot, double* d_fld, int nx, int ny, int nz, int wtflag, const Cutoff& cut,
                        PlaneBuf plane_buf, HistBuf hist_buf, wr_enc_info* info, wr_timings* tm, AfterQuant after_quant, PlaneReady plane_ready,
-                       double** resid, const float* f32 = nullptr)
+                       double** resid, const float* f32 = nullptr, const PickStep* pick = nullptr)
 {
     // minimum cutoff = the global relative tolerance (wrappers.cpp:288-290)
     double tolrel = cut.vec[0];
@@ -230,6 +238,7 @@ int encode_planes_core(wr_ctx* c, Slot* slot, double* d_fld, int nx, int ny, int
     // pointers keep the reference's form (the array is updated in place after every plane).
     wrk::QuantPrev prev;
     for (;;) {
+        if (pick) if (int rc = (*pick)(ilay, lo, hi, prev, d_fld, p, &info->tolabs)) return rc;
         PlaneStep s = plane_step(lo, hi, info->tolabs, ilay);
         info->minval_vec[ilay] = s.minval;
         info->deps_vec[ilay] = s.deps;
@@ -1242,8 +1251,236 @@ unsigned long long* seg_result_dev(wr_ctx* c, int l) { return reinterpret_cast<u
 
 // strands == 0: WRS1 (brick == 0) or WRS2 with that brick edge (wr_blocked.h); otherwise WRS3 with that many strands, in the
 // natural order (brick == 0) or the blocked one
+// ---- the search of an encode to a byte budget (include/waverange_amd.h; the grid and the bound: wr_budget.h) ----------------
+// Only the last plane depends on the tolerance: plane l is cut with the full step (hi - lo) / 255 of its residual until that
+// falls below tolabs, and is then the last, cut with tolabs.  So the grid falls into one interval per plane count: with
+// a_l the finest point at which plane l is the last one, plane l is last on [a_l, a_{l-1} - 1] (plane 0 up to the grid's end),
+// and there B(g) = (the bounds of the full planes 0 .. l-1) + the bound of plane l cut with tolabs(g).  The size probe gives
+// the second term for kProbeK points of the interval in one pass over the coefficients, and the first term is the probe's
+// number for the full step, so the search walks down the planes and never quantizes, let alone codes, a plane to look.
+//
+// At plane l:  pass 1 probes points spread over [a_l, top] (both ends among them) and the full step.
+//   B(a_l) > max_bytes:   a point that fits lies above (B(top) fits: for plane 0 the call fails otherwise, for the others
+//                         pass 1 was only kept because it does), so a (kProbeK + 1)-section finds neighbours g - 1, g with
+//                         B(g - 1) > max_bytes >= B(g).  Plane l is the last, at t(g).
+//   B(a_l) fits, a_l is g_min:  done, at g_min.
+//   B(a_l) fits otherwise:  finer points keep plane l full -- but whether one of them fits is plane l + 1's business, and
+//                         the answer "none" would make a_l the result, with plane l the LAST plane.  So plane l is not
+//                         declared full before pass 1 of plane l + 1 has run (on the residual range the full-step
+//                         candidate's min/max gives) and B(a_l - 1) is known to fit.  Then plane l goes to the quantizer
+//                         and its coder kernels start, under the remaining probes of plane l + 1, whose pass 1 is kept.
+// The probes run on a stream of their own so that they do not queue behind those coder kernels; they only read the
+// coefficient array, which nothing writes while the loop runs (no residual is kept).  The pick is called with the context's
+// stream idle but for coder kernels: the quantizer's partials and its result slot are free for the probe's min/max.
+struct BudgetSearch {
+    // what the caller asks for
+    size_t max_bytes = 0;
+    int g_min = 0;
+    // what comes out
+    int g = -1;
+    size_t bound = 0;
+    int passes = 0;
+
+    wr_ctx* c = nullptr;
+    hipStream_t st = nullptr;
+    size_t n = 0, nseg = 0;
+    unsigned seg = 0;
+    size_t full_sum = 0;           // the bounds of the full planes before the current one
+    int top = wrbud::kGMax;        // the coarsest point at which the current plane is the last
+    bool fits_above = false;       // a point above the current interval's bottom is known to fit
+    struct Pass1 {
+        bool valid = false, empty = false;
+        unsigned ilay = 0;
+        double lo = 0, hi = 0;     // the residual range it was made for
+        int a = 0, top = 0;
+        size_t full_sum = 0;
+        std::vector<std::pair<int, size_t>> B;  // ascending g
+        size_t full_bound = 0;     // the plane cut with the full step
+        double next_lo = 0, next_hi = 0;  // the range that leaves
+        bool has_full = false;
+    } kept;
+
+    BudgetSearch() = default;
+    BudgetSearch(const BudgetSearch&) = delete;
+    BudgetSearch& operator=(const BudgetSearch&) = delete;
+    ~BudgetSearch() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
+
+    static int tables(wr_ctx* c)
+    {
+        if (c->d_bound_tab) return WR_OK;
+        const wrbud::Tables& t = wrbud::tables();
+        uint32_t* tab = nullptr;
+        HIPCHK(hipMalloc(&tab, wrbud::kTabWords * sizeof(uint32_t)));
+        if (hipMemcpy(tab, t.words.data(), wrbud::kTabWords * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError(); (void)hipFree(tab);
+            return fail(WR_ERR_HIP, "the size bound's table could not be copied to the device");
+        }
+        if (!c->d_bound_tot) HIPCHK(hipMalloc(&c->d_bound_tot, wrk::kProbeK * sizeof(unsigned long long)));
+        c->d_bound_tab = tab;
+        return WR_OK;
+    }
+    static unsigned long long* totals_host(wr_ctx* c) { return reinterpret_cast<unsigned long long*>(c->h_result + 8 + 2 * WR_NLAYMAX); }
+
+    int begin(wr_ctx* ctx, size_t count, unsigned s)
+    {
+        c = ctx; n = count; seg = s; nseg = wrseg::seg_count(n, seg);
+        if (int rc = tables(c)) return rc;
+        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        return WR_OK;
+    }
+
+    // one launch: the candidates' segment sums into out[0, cd.n) (the blob's header and index added)
+    static int launch(wr_ctx* c, hipStream_t st, const double* d_coef, size_t n, unsigned seg, const wrk::QuantPrev& prev, const wrk::ProbeCands& cd,
+                      bool want_minmax, size_t* out)
+    {
+        wrk::quant_probe(d_coef, n, seg, prev, cd, want_minmax, c->d_bound_tab, wrbud::tables().fixed, c->d_bound_tot, c->d_partial, c->h_result_dev, st);
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "size probe launch failed");
+        HIPCHK(hipMemcpyAsync(totals_host(c), c->d_bound_tot, wrk::kProbeK * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const size_t over = wrbud::blob_overhead(wrseg::seg_count(n, seg));
+        for (int k = 0; k < cd.n; k++) out[k] = over + (size_t)totals_host(c)[k];
+        return WR_OK;
+    }
+
+    // up to m points of [a, b], both ends among them, ascending
+    static std::vector<int> spread(int a, int b, int m)
+    {
+        std::vector<int> v;
+        if (b - a + 1 <= m) { for (int x = a; x <= b; x++) v.push_back(x); return v; }
+        for (int i = 0; i < m; i++) {
+            const int x = a + (int)(((long long)(b - a) * i + (m - 1) / 2) / (m - 1));
+            if (v.empty() || x > v.back()) v.push_back(x);
+        }
+        return v;
+    }
+
+    // B at the points gs (fewer than kProbeK with the full step, kProbeK without) of plane ilay's interval
+    int eval(unsigned ilay, double lo, double hi, const wrk::QuantPrev& prev, const double* d_coef, const Prologue& p, size_t sum_before,
+             const std::vector<int>& gs, bool with_full, bool want_minmax, Pass1* out)
+    {
+        wrk::ProbeCands cd;
+        if (with_full) {
+            const PlaneStep s = plane_step(lo, hi, 0.0, ilay);
+            cd.aopt[0] = s.aopt; cd.bopt[0] = s.bopt; cd.deps0 = s.deps; cd.minval0 = s.minval;
+            cd.n = 1;
+        }
+        for (int gk : gs) {
+            const PlaneStep s = plane_step(lo, hi, abs_tolerance(wrbud::grid_tol(gk), p), ilay);
+            cd.aopt[cd.n] = s.aopt; cd.bopt[cd.n] = s.bopt;
+            cd.n++;
+        }
+        size_t got[wrk::kProbeK];
+        if (int rc = launch(c, st, d_coef, n, seg, prev, cd, with_full && want_minmax, got)) return rc;
+        passes++;
+        int k = 0;
+        if (with_full) {
+            out->full_bound = got[k++];
+            out->has_full = true;
+            if (want_minmax) { out->next_lo = c->h_result[0]; out->next_hi = c->h_result[1]; }
+        }
+        for (int gk : gs) out->B.emplace_back(gk, sum_before + got[k++]);
+        std::sort(out->B.begin(), out->B.end());
+        return WR_OK;
+    }
+
+    int pass1(unsigned ilay, double lo, double hi, const wrk::QuantPrev& prev, const double* d_coef, const Prologue& p, size_t sum_before, int top_g, Pass1* out)
+    {
+        *out = Pass1();
+        out->valid = true; out->ilay = ilay; out->lo = lo; out->hi = hi; out->top = top_g; out->full_sum = sum_before;
+        auto last_at = [&](int gk) { return plane_step(lo, hi, abs_tolerance(wrbud::grid_tol(gk), p), ilay).last; };
+        if (top_g < g_min || !last_at(top_g)) {  // the plane is full wherever the search may still go
+            out->empty = true;
+            return eval(ilay, lo, hi, prev, d_coef, p, sum_before, std::vector<int>(), true, false, out);
+        }
+        int a = top_g;  // the finest point of [g_min, top] at which the plane is the last (tolabs does not fall as g grows)
+        if (last_at(g_min)) a = g_min;
+        else {
+            int below = g_min;
+            while (a - below > 1) {
+                const int mid = (a + below) / 2;
+                if (last_at(mid)) a = mid;
+                else below = mid;
+            }
+        }
+        out->a = a;
+        const bool with_full = a > g_min && ilay + 1 < (unsigned)WR_NLAYMAX;
+        return eval(ilay, lo, hi, prev, d_coef, p, sum_before, spread(a, top_g, wrk::kProbeK - (with_full ? 1 : 0)), with_full, true, out);
+    }
+
+    static size_t at(const Pass1& q, int gk)
+    {
+        for (const auto& e : q.B) if (e.first == gk) return e.second;
+        return ~(size_t)0;
+    }
+
+    int choose(int gk, size_t b, const Prologue& p, double* tolabs)
+    {
+        g = gk; bound = b;
+        *tolabs = abs_tolerance(wrbud::grid_tol(gk), p);
+        return WR_OK;
+    }
+
+    int pick(unsigned ilay, double lo, double hi, const wrk::QuantPrev& prev, const double* d_coef, const Prologue& p, double* tolabs)
+    {
+        if ((uintptr_t)d_coef & 15) return fail(WR_ERR_ARG, "an encode to a byte budget needs a 16-byte aligned coefficient array");
+        Pass1 cur;
+        // (== on the range: the probe's min/max and the quantizer's are the same values but for the sign of a zero)
+        if (kept.valid && kept.ilay == ilay && kept.lo == lo && kept.hi == hi) cur = kept;
+        else if (int rc = pass1(ilay, lo, hi, prev, d_coef, p, full_sum, top, &cur)) return rc;
+        kept = Pass1();
+        if (cur.empty) {
+            if (ilay + 1 >= (unsigned)WR_NLAYMAX) return fail(WR_ERR_HIP, "internal: the budget search ran out of planes");
+            full_sum += cur.full_bound;
+            *tolabs = 0;
+            return WR_OK;
+        }
+        const size_t b_top = at(cur, cur.top);
+        if (!fits_above && b_top > max_bytes)
+            return fail(WR_ERR_BUDGET, "the budget of " + std::to_string(max_bytes) + " bytes is below what the coarsest tolerance takes: " +
+                                           std::to_string(b_top) + " bytes is the smallest budget that would do");
+        if (b_top > max_bytes) return fail(WR_ERR_HIP, "internal: the budget search lost the point that fits");
+        fits_above = true;
+        const size_t b_a = at(cur, cur.a);
+        if (b_a <= max_bytes) {
+            if (cur.a == g_min) return choose(cur.a, b_a, p, tolabs);
+            if (!cur.has_full) return fail(WR_ERR_HIP, "internal: the budget search has no bound of the full plane");
+            // does a finer point fit?  pass 1 of the next plane, on what the full step leaves
+            const PlaneStep s = plane_step(lo, hi, 0.0, ilay);
+            wrk::QuantPrev next_prev = prev;
+            if (next_prev.n >= wrk::kQuantPrevMax) return fail(WR_ERR_HIP, "internal: the budget search ran out of planes");
+            next_prev.push(s.aopt, s.bopt, s.deps, s.minval);
+            Pass1 nxt;
+            if (int rc = pass1(ilay + 1, cur.next_lo, cur.next_hi, next_prev, d_coef, p, full_sum + cur.full_bound, cur.a - 1, &nxt)) return rc;
+            if (nxt.empty) return fail(WR_ERR_HIP, "internal: the budget search found no tolerance for plane " + std::to_string(ilay + 1));
+            if (at(nxt, nxt.top) > max_bytes) return choose(cur.a, b_a, p, tolabs);  // B(a - 1) does not fit: a is tight
+            full_sum += cur.full_bound;
+            top = cur.a - 1;
+            kept = nxt;
+            *tolabs = 0;
+            return WR_OK;
+        }
+        // B(a) does not fit, B(top) does: neighbours bad, good between them
+        int bad = cur.a, good = cur.top;
+        size_t b_good = b_top;
+        for (size_t i = cur.B.size(); i-- > 0;) {
+            if (cur.B[i].second > max_bytes) { bad = cur.B[i].first; break; }
+            good = cur.B[i].first; b_good = cur.B[i].second;
+        }
+        while (good - bad > 1) {
+            Pass1 more;
+            if (int rc = eval(ilay, lo, hi, prev, d_coef, p, full_sum, spread(bad + 1, good - 1, wrk::kProbeK), false, false, &more)) return rc;
+            for (size_t i = more.B.size(); i-- > 0;) {
+                if (more.B[i].second > max_bytes) { bad = more.B[i].first; break; }
+                good = more.B[i].first; b_good = more.B[i].second;
+            }
+        }
+        return choose(good, b_good, p, tolabs);
+    }
+};
+
+// bud != nullptr: an encode to a byte budget (WRS1): the tolerance comes from the search, cut.vec[0] only names the finest one
 int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, const Cutoff& cut, unsigned seg, unsigned brick, unsigned strands,
-                    wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm)
+                    wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm, BudgetSearch* bud = nullptr)
 {
     if (!seg) seg = WR_SEG_DEFAULT;
     if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
@@ -1257,6 +1494,8 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
     std::lock_guard<std::mutex> lk(c->mu);
     if (fld.host_f32 && c->keep_residual)
         return fail(WR_ERR_UNSUPPORTED, "an fp32 field cannot take the residual back: wr_ctx_set_keep_residual(ctx, 0) for fp32 encodes");
+    if (bud && c->keep_residual)
+        return fail(WR_ERR_UNSUPPORTED, "an encode to a byte budget does not keep the residual: wr_ctx_set_keep_residual(ctx, 0)");
     ActiveCall active(c->pool);
     if (tm) wrdma::enable_timing();
     const double t0 = now();
@@ -1325,12 +1564,20 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
             else wrk::seg_encode(sym, n, seg, bufs.stage.p, bufs.blob[l].p, blob_cap, seg_result_dev(c, (int)l), c->stream, brick);
             HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
             if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented coder launch failed" + launch_describe(c));
+            if (bud) g_stat[WR_STAT_BUDGET_CODER_RUNS]++;
             return WR_OK;
         };
         clock_warmup(c, n);
         if (widen_from) wrk::widen_f32(widen_from, d_fld, n, c->stream);
+        PickStep pick;
+        if (bud) {
+            if ((rc = bud->begin(c, n, seg)) != WR_OK) return rc;
+            pick = [bud](unsigned l, double lo, double hi, const wrk::QuantPrev& prev, const double* d_coef, const Prologue& p, double* tolabs) {
+                return bud->pick(l, lo, hi, prev, d_coef, p, tolabs);
+            };
+        }
         rc = encode_planes_core(c, slot.get(), d_fld, nx, ny, nz, wtflag, cut, plane_buf, [](unsigned) { return (uint16_t*)nullptr; }, info, &local,
-                                after_quant, [](unsigned, bool) { return WR_OK; }, &resid, d_f32);
+                                after_quant, [](unsigned, bool) { return WR_OK; }, &resid, d_f32, bud ? &pick : nullptr);
         if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the encoder's kernel stage failed on the device" + launch_describe(c));
         if (rc == WR_OK && c->keep_residual && info->nlay && !fld.host && resid != fld.dev) {
             if (hipMemcpyAsync(fld.dev, resid, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
@@ -1351,6 +1598,7 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
         total += len;
     }
     if (total > cap || (total && !data_enc)) return fail(WR_ERR_OVERFLOW, "Error: encoded array is too large. Use larger SAFETY_BUFFER_FACTOR");
+    if (bud && total > bud->bound) return fail(WR_ERR_HIP, "internal: the coded planes are longer than their size bound");
     size_t at = 0;
     for (unsigned l = 0; l < info->nlay; l++) {
         if ((rc = xfer_field(c, &c->x_field, data_enc + at, bufs.blob[l].p, info->len_enc_vec[l], kDown)) != WR_OK) return rc;
@@ -2251,6 +2499,92 @@ int wr_encode_device_seg(wr_ctx* c, double* d_fld, int nx, int ny, int nz, int w
     FieldRef f; f.dev = d_fld;
     if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
     return encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, 0, 0, info, data_enc, cap, tm);
+}
+
+// ---- encode to a byte budget (the search: BudgetSearch above)
+static int encode_seg_budget(wr_ctx* c, FieldRef f, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, size_t max_bytes, double tol_min,
+                             unsigned seg, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm, wr_budget_result* res)
+{
+    if (!res) return fail(WR_ERR_ARG, "null wr_budget_result");
+    if (!(tol_min > 0) || tol_min > DBL_MAX) return fail(WR_ERR_ARG, "tol_min must be a positive number");
+    if (mx < 1 || my < 1 || mz < 1) return fail(WR_ERR_ARG, "bad local cutoff description");
+    if ((long long)mx * my * mz > 1) return fail(WR_ERR_UNSUPPORTED, "an encode to a byte budget takes no local cutoff (mx * my * mz > 1)");
+    BudgetSearch bud;
+    bud.max_bytes = max_bytes;
+    bud.g_min = wrbud::grid_index(tol_min);
+    const double t_min = wrbud::grid_tol(bud.g_min);  // (the loop's tolerance until the search sets it; a constant field never gets there)
+    Cutoff cut; cut.vec = &t_min;
+    memset(res, 0, sizeof *res);
+    const int rc = encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, 0, 0, info, data_enc, cap, tm, &bud);
+    res->probe_passes = bud.passes;
+    if (rc) return rc;
+    if (info->nlay == 0) { bud.g = bud.g_min; bud.bound = 0; }
+    if (bud.g < 0) return fail(WR_ERR_HIP, "internal: the budget search chose no tolerance");
+    res->g = bud.g;
+    res->tolrel = wrbud::grid_tol(bud.g);
+    res->bound = bud.bound;
+    return WR_OK;
+}
+
+int wr_encode_host_seg_budget(wr_ctx* c, const double* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, size_t max_bytes, double tol_min,
+                              unsigned seg, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm, wr_budget_result* res)
+{
+    FieldRef f; f.host = const_cast<double*>(h_fld);  // (never written: the residual is not kept)
+    return encode_seg_budget(c, f, nx, ny, nz, wtflag, mx, my, mz, max_bytes, tol_min, seg, info, data_enc, cap, tm, res);
+}
+
+int wr_encode_host_seg_budget_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, size_t max_bytes,
+                                  double tol_min, unsigned seg, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm,
+                                  wr_budget_result* res)
+{
+    FieldRef f; f.host_f32 = const_cast<float*>(h_fld);
+    return encode_seg_budget(c, f, nx, ny, nz, wtflag, mx, my, mz, max_bytes, tol_min, seg, info, data_enc, cap, tm, res);
+}
+
+int wr_encode_device_seg_budget(wr_ctx* c, double* d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, size_t max_bytes, double tol_min,
+                                unsigned seg, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm, wr_budget_result* res)
+{
+    FieldRef f; f.dev = d_fld;
+    if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
+    return encode_seg_budget(c, f, nx, ny, nz, wtflag, mx, my, mz, max_bytes, tol_min, seg, info, data_enc, cap, tm, res);
+}
+
+int wr_dev_plane_size_bound(wr_ctx* c, const unsigned char* d_sym, size_t n, unsigned seg, size_t* bound)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
+    if (int rc = ctx_bind(c)) return rc;
+    if (!bound || (n && !d_sym)) return fail(WR_ERR_ARG, "null pointer");
+    if ((uintptr_t)d_sym & 15) return fail(WR_ERR_ARG, "the plane must be 16-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int rc = BudgetSearch::tables(c)) return rc;
+    StageLock cu(c->pool->cu_mu);
+    wrk::plane_bound(d_sym, n, seg, c->d_bound_tab, wrbud::tables().fixed, c->d_bound_tot, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(BudgetSearch::totals_host(c), c->d_bound_tot, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *bound = wrbud::blob_overhead(wrseg::seg_count(n, seg)) + (size_t)BudgetSearch::totals_host(c)[0];
+    return WR_OK;
+}
+
+int wr_dev_quant_size_probe(wr_ctx* c, const double* d_resid, size_t n, double minval, int ncand, const double* deps, unsigned seg, size_t* bounds)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
+    if (ncand < 1 || ncand > wrk::kProbeK) return fail(WR_ERR_ARG, "a size probe takes 1 to " + std::to_string(wrk::kProbeK) + " candidate steps");
+    if (int rc = ctx_bind(c)) return rc;
+    if (!bounds || !deps || (n && !d_resid)) return fail(WR_ERR_ARG, "null pointer");
+    if ((uintptr_t)d_resid & 15) return fail(WR_ERR_ARG, "the residual array must be 16-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int rc = BudgetSearch::tables(c)) return rc;
+    wrk::ProbeCands cd;
+    cd.n = ncand;
+    for (int k = 0; k < ncand; k++) {  // plane_step's expressions
+        cd.aopt[k] = 1.0 / deps[k];
+        cd.bopt[k] = -minval * cd.aopt[k] + 0.5;
+    }
+    StageLock cu(c->pool->cu_mu);
+    return BudgetSearch::launch(c, c->stream, d_resid, n, seg, wrk::QuantPrev(), cd, false, bounds);
 }
 
 int wr_decode_device_seg(wr_ctx* c, double* d_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,

@@ -2,6 +2,7 @@
 // interleaved planes, the coder pool, the 16-lane loops, and the windowed symbol path with host buffers standing in for
 // device-resident planes (test hooks).
 #include "wr_blocked.h"
+#include "wr_budget.h"
 #include "wr_internal.h"
 #include "wr_lowres.h"
 #include "wr_roi.h"
@@ -155,6 +156,18 @@ size_t wr_seg_bound(size_t n, unsigned seg)
     if (!seg) seg = WR_SEG_DEFAULT;
     if (!wrseg::seg_ok(seg)) return 0;
     return wrseg::kHeaderBytes + wrseg::seg_count(n, seg) * (4 + (size_t)wrseg::stream_bound(seg));
+}
+
+// ---- an encode to a byte budget (wr_budget.h): the tolerance grid and the size bound of a plane, on the calling thread
+double wr_budget_tol(int g) { return wrbud::grid_tol(g); }
+int wr_budget_index(double tolrel) { return wrbud::grid_index(tolrel); }
+
+size_t wr_seg_size_bound_host_ref(const unsigned char* sym, size_t n, unsigned seg)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
+    if (n && !sym) { fail(WR_ERR_ARG, "null pointer"); return 0; }
+    return wrbud::plane_bound(sym, n, seg);
 }
 
 // the containers (wr_transcode.h) with their failures made the thread's error

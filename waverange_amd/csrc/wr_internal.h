@@ -42,7 +42,7 @@ constexpr double kWavAccCoef = 1.75;
 constexpr unsigned long kSafetyBufferFactor = 1;
 constexpr int kMaxDevices = 64;
 
-extern std::atomic<unsigned long> g_stat[16];  // see wr_stat()
+extern std::atomic<unsigned long> g_stat[32];  // see wr_stat()
 std::string& last_error();            // this thread's message (wr_last_error)
 int coder_threads();                  // wr_set_threads / WR_THREADS, default one per plane
 int encoder_threads();
@@ -160,8 +160,10 @@ struct wr_ctx {
     double* d_partial = nullptr;
     double* d_mm = nullptr; size_t mm_records = 0;  // min/max records of the fused forward transform
     unsigned long long* d_idx = nullptr;
+    uint32_t* d_bound_tab = nullptr;              // the size bound's table (wr_budget.h), uploaded at the first budget call
+    unsigned long long* d_bound_tot = nullptr;    // the size probe's totals, wrk::kProbeK words
     // pinned host
-    double* h_result = nullptr;  // [0..1] min/max, [2] probe value, [3] index, [4..7] fused min/max, [8 + 2l, 9 + 2l] plane l's segmented-coder result (u64: blob length, failed segments)
+    double* h_result = nullptr;  // [0..1] min/max, [2] probe value, [3] index, [4..7] fused min/max, [8 + 2l, 9 + 2l] plane l's segmented-coder result (u64: blob length, failed segments), [8 + 2 WR_NLAYMAX ..] the size probe's kProbeK totals (u64)
     double* h_result_dev = nullptr;  // the same block as the device sees it: reductions write their result straight to the host
     uint16_t* h_hist = nullptr; size_t h_hist_elems = 0;  // pinned: per-block byte histograms, all planes
     // host coded-stream staging, one per plane

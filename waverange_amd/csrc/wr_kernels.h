@@ -85,6 +85,24 @@ void quantize_plane_blk(double* x, size_t n, const QuantPrev& prev, double aopt,
 // x := the residual after the planes in prev
 void residual_apply(double* x, size_t n, const QuantPrev& prev, hipStream_t st);
 
+// ---- the size probe of an encode to a byte budget (k_quant_probe; the bound and its table: wr_budget.h).  x holds the
+// COEFFICIENTS (16-byte aligned, read only); the plane in question is cut from the residual after the planes in prev.  For
+// each of the cd.n <= kProbeK candidate steps (aopt, bopt) totals[k] becomes the sum over the plane's segments of the bound
+// of the segment stream that step would give (the blob's header and index are not in it).  Nothing else is written.
+// want_minmax: result[0..1] = min/max of the residual that candidate 0 (step cd.deps0, offset cd.minval0) would leave.
+// tab: wrbud::kTabWords words of device memory, the host's table; fixed: its Tables::fixed.  totals: kProbeK words of
+// device memory, zeroed here.  seg: wrseg::seg_ok.
+constexpr int kProbeK = 8;
+struct ProbeCands {
+    int n = 0;
+    double aopt[kProbeK], bopt[kProbeK];
+    double deps0 = 0, minval0 = 0;
+};
+void quant_probe(const double* x, size_t n, unsigned seg, const QuantPrev& prev, const ProbeCands& cd, bool want_minmax, const uint32_t* tab,
+                 unsigned long long fixed, unsigned long long* totals, double* partial, double* result, hipStream_t st);
+// the same sum for a plane of symbols that exists (16-byte aligned, one array): totals[0]
+void plane_bound(const uint8_t* sym, size_t n, unsigned seg, const uint32_t* tab, unsigned long long fixed, unsigned long long* totals, hipStream_t st);
+
 // ---- quantizer plane with the non-uniform (local) cutoff mask (wrappers.cpp:343-379, 397-398):
 // loops over PHYSICAL positions, maps each to its wavelet-space index (ind_p2w_3d,
 // waveletcdf97_3d.c:473-553) and quantizes there; coefficients of the finest level whose plane

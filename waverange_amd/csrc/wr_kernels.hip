@@ -14,6 +14,7 @@
 // with -ffp-contract=off and additionally pins it with the pragma below.  No MFMA: this is
 // a 9-tap stencil + byte packing, HBM-bound.
 #include "wr_kernels.h"
+#include "wr_budget.h"
 
 #include <stdlib.h>
 
@@ -734,6 +735,195 @@ void quantize_plane_blk(double* x, size_t n, const QuantPrev& prev, double aopt,
     }
 #undef WR_QB_LAUNCH
     if (want_minmax) hipLaunchKernelGGL(k_minmax_final, dim3(1), dim3(WR_RED_THREADS), 0, st, partial, g, result);
+}
+
+// =====================================================================================
+// The size probe of an encode to a byte budget (wr_budget.h): what WOULD the WRS1 blob of this plane take at most, for up to
+// kProbeK quantizer steps at once?  The pass of k_quant_blk -- the coefficients in 16-byte loads, the planes before redone in
+// registers -- but nothing is written: every candidate's bytes go through the wave's staging into one LDS histogram per
+// candidate, and at the end of a segment 256 lanes turn each histogram into the segment's bound by table look-ups.  One
+// workgroup takes one segment at a time.  The bounds are integers added up with integer atomics: the totals do not depend
+// on the order the segments finish in.  MM: min/max of the residual candidate 0 would leave (the next plane's range).
+// The histograms keep k_quant_blk's two answers to the one dominant symbol of a smooth plane: several copies that start
+// in different banks, and one add per run of equal symbols among a lane's 16.
+// =====================================================================================
+constexpr int kProbeCopies = 4;
+
+// the histograms of one segment of bs symbols -> acc (lane k < ncand: candidate k's bytes).  All 256 lanes, between barriers.
+template <int K>
+__device__ inline void probe_segment_end(unsigned int (*h)[kProbeCopies][256 + 1], unsigned long long (*wsum)[WR_RED_THREADS / 64], int ncand, uint32_t bs,
+                                         const uint32_t* __restrict__ tab, unsigned long long fixed, unsigned long long& acc)
+{
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    __syncthreads();
+    for (int k = 0; k < K; k++) {
+        if (k >= ncand) break;
+        unsigned int c = 0;
+#pragma unroll
+        for (int j = 0; j < kProbeCopies; j++) c += h[k][j][t];
+        unsigned long long d = tab[c < wrbud::kTabN ? c : 0];  // (c <= bs < kTabN: the clamp never acts, it keeps the look-up in the table whatever happens)
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned int lo32 = __shfl_down((unsigned int)d, o, 64), hi32 = __shfl_down((unsigned int)(d >> 32), o, 64);
+            d += (unsigned long long)hi32 << 32 | lo32;
+        }
+        if (lane == 0) wsum[k][w] = d;
+    }
+    __syncthreads();
+    if (t < ncand) {
+        unsigned long long sum = 0;
+        for (int i = 0; i < WR_RED_THREADS / 64; i++) sum += wsum[t][i];
+        acc += wrbud::segment_bytes(fixed, tab[wrbud::kTabN + (bs < wrbud::kTabN ? bs : 0)], sum);
+    }
+    __syncthreads();  // before the next segment zeroes the bins
+}
+
+// a lane's 16 symbols (cnt of them count) into its copy of a histogram, one add per run
+__device__ inline void probe_count16(unsigned int* mine, const uint4& wq, int cnt)
+{
+    const unsigned int words[4] = {wq.x, wq.y, wq.z, wq.w};
+    unsigned int prevs = words[0] & 0xff, run = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const unsigned int sb = (words[k >> 2] >> (8 * (k & 3))) & 0xff;
+        if (k < cnt) {
+            if (sb != prevs) { atomicAdd(&mine[prevs], run); prevs = sb; run = 0; }
+            run++;
+        }
+    }
+    atomicAdd(&mine[prevs], run);
+}
+
+template <int K, bool MM>
+__global__ __launch_bounds__(WR_RED_THREADS) void k_quant_probe(const double* __restrict__ x, size_t n, unsigned seg, QuantPrev prev, ProbeCands cd,
+                                                                const uint32_t* __restrict__ tab, unsigned long long fixed,
+                                                                unsigned long long* __restrict__ totals, double* __restrict__ partial)
+{
+    constexpr int NW = WR_RED_THREADS / 64;
+    __shared__ unsigned int h[K][kProbeCopies][256 + 1];
+    __shared__ unsigned long long wsum[K][NW];
+    __shared__ uchar2 sq[NW][QW / 2];  // wave-private staging, as in k_quant_blk
+    const double nan = __builtin_nan("");
+    double lo = nan, hi = nan;
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int ncand = cd.n < K ? cd.n : K;
+    unsigned long long acc = 0;
+    const size_t nseg = (n + seg - 1) / seg;
+    for (size_t s = blockIdx.x; s < nseg; s += gridDim.x) {
+        const size_t s0 = s * seg, s1 = (s0 + seg < n) ? s0 + seg : n;
+        for (int i = t; i < K * kProbeCopies * 257; i += WR_RED_THREADS) (&h[0][0][0])[i] = 0;
+        __syncthreads();
+        for (size_t g0 = s0 + (size_t)w * QW; g0 < s1; g0 += (size_t)NW * QW) {
+            const bool full = g0 + QW <= s1;  // wave-uniform
+            const double2* const x2 = reinterpret_cast<const double2*>(x + g0);  // (seg is a multiple of 16: 128-byte aligned)
+            double2 v[QW / 128];
+            if (full) {
+#pragma unroll
+                for (int j = 0; j < QW / 128; j++) v[j] = x2[j * 64 + lane];
+            } else {
+#pragma unroll
+                for (int j = 0; j < QW / 128; j++) {
+                    const size_t e = g0 + 2 * (size_t)(j * 64 + lane);
+                    v[j] = make_double2(0.0, 0.0);
+                    if (e + 1 < s1) v[j] = x2[j * 64 + lane];
+                    else if (e < s1) v[j].x = x[e];
+                }
+            }
+#pragma unroll
+            for (int p = 0; p < kQuantPrevMax; p++) {
+                if (p < prev.n) {
+                    const double pa = prev.aopt[p], pb = prev.bopt[p], pd = prev.deps[p], pm = prev.minval[p];
+#pragma unroll
+                    for (int j = 0; j < QW / 128; j++) {
+                        const unsigned char qa = quant_byte(pa * v[j].x + pb);
+                        const unsigned char qb = quant_byte(pa * v[j].y + pb);
+                        v[j].x = v[j].x - ((double)qa * pd + pm);
+                        v[j].y = v[j].y - ((double)qb * pd + pm);
+                    }
+                }
+            }
+            const size_t i = g0 + 16 * (size_t)lane;  // this lane's 16 symbols
+            const int cnt = i < s1 ? ((s1 - i < 16) ? (int)(s1 - i) : 16) : 0;
+            for (int k = 0; k < K; k++) {
+                if (k >= ncand) break;
+                const double aopt = cd.aopt[k], bopt = cd.bopt[k];
+#pragma unroll
+                for (int j = 0; j < QW / 128; j++) {
+                    const unsigned char qa = quant_byte(aopt * v[j].x + bopt);
+                    const unsigned char qb = quant_byte(aopt * v[j].y + bopt);
+                    sq[w][j * 64 + lane] = make_uchar2(qa, qb);
+                    if (MM && k == 0) {
+                        const double ra = v[j].x - ((double)qa * cd.deps0 + cd.minval0);
+                        const double rb = v[j].y - ((double)qb * cd.deps0 + cd.minval0);
+                        const size_t e = g0 + 2 * (size_t)(j * 64 + lane);
+                        if (full || e + 1 < s1) { mm_acc(ra, lo, hi); mm_acc(rb, lo, hi); }
+                        else if (e < s1) mm_acc(ra, lo, hi);
+                    }
+                }
+                wave_lds_fence();  // the byte pairs above -> the 16-byte piece below
+                const uint4 wq = reinterpret_cast<const uint4*>(&sq[w][0])[lane];
+                wave_lds_fence();  // ... and the next candidate's stores stay behind these loads
+                if (cnt) probe_count16(h[k][t & (kProbeCopies - 1)], wq, cnt);
+            }
+        }
+        probe_segment_end<K>(h, wsum, ncand, (uint32_t)(s1 - s0), tab, fixed, acc);
+    }
+    if (t < ncand && acc) atomicAdd(&totals[t], acc);
+    if (MM) block_minmax(lo, hi, partial);
+}
+
+// the same bound for a plane of symbols that exists (one candidate, no arithmetic)
+__global__ __launch_bounds__(WR_RED_THREADS) void k_plane_bound(const uint8_t* __restrict__ sym, size_t n, unsigned seg, const uint32_t* __restrict__ tab,
+                                                                unsigned long long fixed, unsigned long long* __restrict__ totals)
+{
+    __shared__ unsigned int h[1][kProbeCopies][256 + 1];
+    __shared__ unsigned long long wsum[1][WR_RED_THREADS / 64];
+    const int t = threadIdx.x;
+    unsigned long long acc = 0;
+    const size_t nseg = (n + seg - 1) / seg;
+    for (size_t s = blockIdx.x; s < nseg; s += gridDim.x) {
+        const size_t s0 = s * seg, s1 = (s0 + seg < n) ? s0 + seg : n;
+        for (int i = t; i < kProbeCopies * 257; i += WR_RED_THREADS) (&h[0][0][0])[i] = 0;
+        __syncthreads();
+        for (size_t i = s0 + 16 * (size_t)t; i < s1; i += 16 * (size_t)WR_RED_THREADS) {  // (s0 and the plane are 16-byte aligned)
+            const int cnt = (s1 - i < 16) ? (int)(s1 - i) : 16;
+            uint4 wq = make_uint4(0, 0, 0, 0);
+            if (cnt == 16) wq = *reinterpret_cast<const uint4*>(sym + i);
+            else {
+                unsigned int words[4] = {0, 0, 0, 0};
+                for (int k = 0; k < cnt; k++) words[k >> 2] |= (unsigned int)sym[i + k] << (8 * (k & 3));
+                wq = make_uint4(words[0], words[1], words[2], words[3]);
+            }
+            probe_count16(h[0][t & (kProbeCopies - 1)], wq, cnt);
+        }
+        probe_segment_end<1>(h, wsum, 1, (uint32_t)(s1 - s0), tab, fixed, acc);
+    }
+    if (t == 0 && acc) atomicAdd(&totals[0], acc);
+}
+
+static int probe_grid(size_t n, unsigned seg)
+{
+    const size_t nseg = (n + seg - 1) / seg;
+    constexpr size_t gmax = (size_t)WR_RED_BLOCKS / 2;  // (one round of resident workgroups; the partials of MM fit d_partial)
+    return (int)(nseg < gmax ? (nseg ? nseg : 1) : gmax);
+}
+
+void quant_probe(const double* x, size_t n, unsigned seg, const QuantPrev& prev, const ProbeCands& cd, bool want_minmax, const uint32_t* tab,
+                 unsigned long long fixed, unsigned long long* totals, double* partial, double* result, hipStream_t st)
+{
+    (void)hipMemsetAsync(totals, 0, kProbeK * sizeof(unsigned long long), st);
+    const int g = probe_grid(n, seg);
+    if (want_minmax) {
+        hipLaunchKernelGGL((k_quant_probe<kProbeK, true>), dim3(g), dim3(WR_RED_THREADS), 0, st, x, n, seg, prev, cd, tab, fixed, totals, partial);
+        hipLaunchKernelGGL(k_minmax_final, dim3(1), dim3(WR_RED_THREADS), 0, st, partial, g, result);
+    } else
+        hipLaunchKernelGGL((k_quant_probe<kProbeK, false>), dim3(g), dim3(WR_RED_THREADS), 0, st, x, n, seg, prev, cd, tab, fixed, totals, partial);
+}
+
+void plane_bound(const uint8_t* sym, size_t n, unsigned seg, const uint32_t* tab, unsigned long long fixed, unsigned long long* totals, hipStream_t st)
+{
+    (void)hipMemsetAsync(totals, 0, sizeof(unsigned long long), st);
+    hipLaunchKernelGGL(k_plane_bound, dim3(probe_grid(n, seg)), dim3(WR_RED_THREADS), 0, st, sym, n, seg, tab, fixed, totals);
 }
 
 // local-cutoff variant: one thread per physical position (a bijection onto wavelet space)

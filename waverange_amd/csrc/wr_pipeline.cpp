@@ -23,7 +23,7 @@ std::string& last_error() { return g_err; }
 std::atomic<int> g_verbose{-1};      // -1: not initialised from the environment yet
 std::atomic<int> g_threads{-1};      // -1: not initialised from the environment yet (WR_THREADS, default one per plane)
 std::atomic<int> g_enc_threads{0};   // 0: same as g_threads (wr_set_encoder_threads)
-std::atomic<unsigned long> g_stat[16];  // see wr_stat()
+std::atomic<unsigned long> g_stat[32];  // see wr_stat()
 std::atomic<int> g_writeback{-1};    // drop-in encoding_wrap leaves the residual in fld_1d (-1: from WR_WRITEBACK_RESIDUAL, default 1)
 
 int coder_threads()
@@ -851,7 +851,7 @@ unsigned long wr_stat(int what)
     if (what == WR_STAT_POOL_STREAMS_MOVED) return wrrc::pool_streams_moved();
     if (what == WR_STAT_POOL_QUEUE_MS) return (unsigned long)(wrrc::pool_queue_seconds() * 1e3);
     if (what == WR_STAT_WINDOW_WAIT_MS) return (unsigned long)(g_window_wait_us.load() / 1000);
-    return (what >= 0 && what < 16) ? g_stat[what].load() : 0;
+    return (what >= 0 && what < 32) ? g_stat[what].load() : 0;
 }
 void wr_set_coder_pool(int nthreads, int decoder_streams)
 {
@@ -888,7 +888,7 @@ static int ctx_init(wr_ctx* c, int device, void* hip_stream)
     else { HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
     HIPCHK(hipMalloc(&c->d_partial, 2 * wrk::minmax_partials() * sizeof(double)));
     HIPCHK(hipMalloc(&c->d_idx, sizeof(unsigned long long)));
-    HIPCHK(hipHostMalloc(&c->h_result, (8 + 2 * WR_NLAYMAX) * sizeof(double), hipHostMallocDefault));  // ([8 + 2l ..]: plane l's segmented-coder result)
+    HIPCHK(hipHostMalloc(&c->h_result, (8 + 2 * WR_NLAYMAX + wrk::kProbeK) * sizeof(double), hipHostMallocDefault));  // ([8 + 2l ..]: plane l's segmented-coder result; then the size probe's totals)
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_result_dev), c->h_result, 0));
     for (int i = 0; i < WR_NLAYMAX; i++) {
         HIPCHK(hipEventCreateWithFlags(&c->ev_plane[i], hipEventDisableTiming));
@@ -938,6 +938,7 @@ void wr_ctx_destroy(wr_ctx* c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)hipFree(c->d_cutoff);
     (void)hipFree(c->d_partial); (void)hipFree(c->d_idx); (void)hipFree(c->d_mm);
+    (void)hipFree(c->d_bound_tab); (void)hipFree(c->d_bound_tot);
     if (c->h_result) (void)hipHostFree(c->h_result);
     if (c->h_hist) (void)hipHostFree(c->h_hist);
     for (int l = 0; l < WR_NLAYMAX; l++) {
