@@ -116,6 +116,7 @@ void ind_p2w_3d(int lvlin, int n1, int n2, int n3, int i1in, int i2in, int i3in,
 #define WR_ERR_STREAM (-4)
 #define WR_ERR_OVERFLOW (-5)
 #define WR_ERR_BUDGET (-6) /* an encode to a byte budget: no tolerance of the grid fits the budget */
+#define WR_ERR_BOUND (-7)  /* an encode to an error bound: the finest tolerance allowed does not meet the bound */
 
 typedef struct wr_ctx wr_ctx;
 
@@ -202,6 +203,7 @@ int wr_set_device_slots(int device, int nslots);
                                        * of a multi-region call on a WRS3 stream, one per multi-region call on a WRS1 / WRS2 stream */
 #define WR_STAT_BUDGET_CODER_RUNS 16 /* planes the encodes to a byte budget (wr_encode_*_seg_budget) have handed to the segment coder:
                                       info->nlay per call, however many tolerances the search looked at */
+#define WR_STAT_BOUNDED_CODER_RUNS 17 /* the same for the encodes to an error bound (wr_encode_*_seg_bounded) */
 unsigned long wr_stat(int what);
 /* Hands the idle buffers of the device's plane pool back to the device (the pool keeps the plane memory of finished calls for
  * the next ones: after a burst of concurrent calls that can be most of the HBM).  Buffers in use are not touched. */
@@ -417,6 +419,70 @@ int wr_encode_host_seg_budget_f32(wr_ctx *ctx, const float *h_fld, int nx, int n
 int wr_encode_device_seg_budget(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
                                 size_t max_bytes, double tol_min, unsigned seg, wr_enc_info *info, unsigned char *data_enc,
                                 size_t cap, wr_timings *tm, wr_budget_result *res);
+/* ---- Encode to a pointwise error bound: the call picks the tolerance, and codes every plane once.
+ * The relative tolerance of the plain calls steps the wavelet coefficients; what the samples end up with is only roughly
+ * tolrel * max|f|.  These calls take the bound on the samples itself.
+ * E(g).  For a field f and a point g of the grid above, E(g) = max_j |f[j] - r_g[j]|, r_g being bit for bit what
+ * wr_decode_host_seg returns for the stream wr_encode_host_seg makes at cutoffvec = { wr_budget_tol(g) }.  One IEEE fp64
+ * subtraction per sample; the maximum of such values is exact, so E(g) is a well-defined double.  For an fp32 field r_g is
+ * the fp32 reconstruction of wr_decode_host_seg_f32 and both operands are widened to fp64 first.  The reconstruction does
+ * not depend on the segmented format, seg, brick or strands, so E does not either.
+ * The start.  wr_bounded_start(max_abs_err, absmax) is the largest g with wr_budget_tol(g) * absmax <= max_abs_err (one fp64
+ * multiply, found by comparison over the grid, no libm), clamped to the grid; -1 when even t(0) is too coarse or an
+ * argument is not a positive finite number.  absmax is max(|lo|, |hi|) of the field.
+ * The call.  wr_encode_*_seg_bounded take the arguments of wr_encode_host_seg_strands / _f32 / wr_encode_device_seg_strands
+ * with the cutoff vector replaced by max_abs_err and tol_min, and a result record.  brick = 0, strands = 0: WRS1; brick > 0:
+ * WRS2; strands > 0: WRS3 (with or without a brick edge).  With g_min = wr_budget_index(tol_min) they return a g in
+ * [g_min, WR_BUDGET_GMAX] such that
+ *   it holds         E(g) <= max_abs_err, and res->err == E(g);
+ *   it is tight      g == WR_BUDGET_GMAX or E(g + 1) > max_abs_err (E is not monotone: this local property is the contract,
+ *                    not "the largest g of all");
+ *   it is the same   info and data_enc are bit for bit what the plain call of the chosen format returns at cutoffvec = { t(g) };
+ *   coded once       WR_STAT_BOUNDED_CODER_RUNS grows by info->nlay; res->trials counts the tolerances whose reconstruction
+ *                    was formed.  A trial is a pass over the coefficients that writes the decoder's coefficient sum (no plane,
+ *                    no coder), the decoder's inverse transform and a compare against the field, all on the device.
+ * A constant field gives nlay = 0, g = WR_BUDGET_GMAX, err = 0, trials = 0.  WR_ERR_BOUND: E(g_min) > max_abs_err;
+ * wr_last_error() names E(g_min) and data_enc is not written.  WR_ERR_ARG: a field holding a NaN or an infinity (the message
+ * counts such samples; from these calls only), a max_abs_err or tol_min that is not a positive finite number, and what the
+ * plain calls refuse.  WR_ERR_UNSUPPORTED: a local cutoff (mx * my * mz > 1) and wr_ctx_set_keep_residual(ctx, 1).
+ * wtflag = 0 is supported (a trial then has no inverse).
+ * Device memory.  Next to what the plain call takes, the trials take two work arrays of nx * ny * nz doubles and, where the
+ * forward transform does not leave the field intact (any shape whose four levels do not all run on the fused kernels, and
+ * wtflag = 0), a copy of the field (8 bytes per sample, 4 for an fp32 field).  They come from the plane pool and go back when
+ * the call ends; a device that cannot give them returns the pool's usual error.
+ * wr_seg_error_host / _f32: the measuring half on its own.  *err = max_j |h_fld[j] - r[j]| for the reconstruction r of an
+ * existing segmented stream (WRS1, WRS2 or WRS3), formed and compared on the device; h_fld is only read.  WR_ERR_ARG when a
+ * difference is not finite. */
+typedef struct wr_bounded_result {
+    int g;         /* the grid point chosen */
+    double tolrel; /* t(g) */
+    double err;    /* E(g) */
+    int trials;    /* tolerances whose reconstruction was formed */
+} wr_bounded_result;
+int wr_bounded_start(double max_abs_err, double absmax);
+/* stage level: d_acc[j] = the decoder's coefficient sum (what wr_dev_decode_planes accumulates before its inverse) of the nlay
+ * planes the quantizer loop cuts from d_coef with the steps deps[l] and offsets minval[l], l = 0 .. nlay - 1, in its own
+ * arithmetic (aopt = 1 / deps, bopt = -minval * aopt + 0.5); no plane is written, d_coef is only read and must not overlap
+ * d_acc.  Pointers that are not 16-byte aligned take an element-wise form.  nlay outside 1 .. WR_NLAYMAX: WR_ERR_ARG. */
+int wr_dev_requant_accum(wr_ctx *ctx, const double *d_coef, size_t n, int nlay, const double *deps, const double *minval,
+                         double *d_acc);
+int wr_encode_host_seg_bounded(wr_ctx *ctx, const double *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                               double max_abs_err, double tol_min, unsigned seg, unsigned brick, unsigned strands,
+                               wr_enc_info *info, unsigned char *data_enc, size_t cap, wr_timings *tm, wr_bounded_result *res);
+int wr_encode_host_seg_bounded_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                   double max_abs_err, double tol_min, unsigned seg, unsigned brick, unsigned strands,
+                                   wr_enc_info *info, unsigned char *data_enc, size_t cap, wr_timings *tm,
+                                   wr_bounded_result *res);
+int wr_encode_device_seg_bounded(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                 double max_abs_err, double tol_min, unsigned seg, unsigned brick, unsigned strands,
+                                 wr_enc_info *info, unsigned char *data_enc, size_t cap, wr_timings *tm, wr_bounded_result *res);
+int wr_seg_error_host(wr_ctx *ctx, const double *h_fld, int nx, int ny, int nz, const wr_enc_info *info,
+                      const unsigned char *data_enc, size_t data_len, double *err);
+int wr_seg_error_host_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny, int nz, const wr_enc_info *info,
+                          const unsigned char *data_enc, size_t data_len, double *err);
+/* measurement hook: HIP-event milliseconds of the three stages of a trial -- the coefficient sum, the inverse, the compare --
+ * summed over the trials of the context's last encode to an error bound (null pointers are skipped) */
+int wr_ctx_bounded_trial_ms(wr_ctx *ctx, double *requant_ms, double *inverse_ms, double *compare_ms);
 /* ---- Low-resolution decode of segmented streams: a coarse version of the field without decoding the field.
  * The transform is a Mallat decomposition (waveletcdf97_3d.c:73-78): after level r the low-pass coefficients of an nx*ny*nz
  * field sit in the corner box [0,bx) x [0,by) x [0,bz) of the coefficient array.  With h(n) = (n + 1) / 2 in integer

@@ -65,6 +65,11 @@ class BudgetResult(C.Structure):
     _fields_ = [("g", C.c_int), ("tolrel", C.c_double), ("bound", C.c_size_t), ("probe_passes", C.c_int)]
 
 
+class BoundedResult(C.Structure):
+    """wr_bounded_result"""
+    _fields_ = [("g", C.c_int), ("tolrel", C.c_double), ("err", C.c_double), ("trials", C.c_int)]
+
+
 class FusedLevel(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("tiles_x", "tiles_y", "zps", "zsegs", "zlast")]
 
@@ -198,6 +203,17 @@ def lib():
                                             C.c_uint, C.POINTER(EncInfo), _vp, C.c_size_t, C.POINTER(Timings), C.POINTER(BudgetResult)]
     L.wr_encode_host_seg_budget_f32.argtypes = L.wr_encode_host_seg_budget.argtypes
     L.wr_encode_device_seg_budget.argtypes = L.wr_encode_host_seg_budget.argtypes
+    # an encode to an error bound: the start point, the stage call, the drivers and the measuring half
+    L.wr_bounded_start.argtypes = [C.c_double, C.c_double]
+    L.wr_dev_requant_accum.argtypes = [_vp, _vp, C.c_size_t, C.c_int, _dp, _dp, _vp]
+    L.wr_encode_host_seg_bounded.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                             C.c_uint, C.c_uint, C.c_uint, C.POINTER(EncInfo), _vp, C.c_size_t, C.POINTER(Timings),
+                                             C.POINTER(BoundedResult)]
+    L.wr_encode_host_seg_bounded_f32.argtypes = L.wr_encode_host_seg_bounded.argtypes
+    L.wr_encode_device_seg_bounded.argtypes = L.wr_encode_host_seg_bounded.argtypes
+    L.wr_seg_error_host.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(EncInfo), _vp, C.c_size_t, _dp]
+    L.wr_seg_error_host_f32.argtypes = L.wr_seg_error_host.argtypes
+    L.wr_ctx_bounded_trial_ms.argtypes = [_vp, _dp, _dp, _dp]
     L.wr_encode_device_seg.argtypes = L.wr_encode_host_seg.argtypes
     L.wr_decode_host_seg.argtypes = L.wr_decode_host.argtypes
     L.wr_decode_host_seg_f32.argtypes = L.wr_decode_host.argtypes
@@ -336,6 +352,7 @@ STAT_LOWRES_SEGMENTS, STAT_LOWRES_BYTES_UP = 11, 12
 STAT_ROI_SEGMENTS, STAT_ROI_BYTES_UP = 13, 14
 STAT_ROI_CODER_LAUNCHES = 15
 STAT_BUDGET_CODER_RUNS = 16
+STAT_BOUNDED_CODER_RUNS = 17
 
 
 def stat(what):
@@ -450,6 +467,7 @@ SEG_DEFAULT = 59904  # WR_SEG_DEFAULT
 BUDGET_GMAX = 3840
 BUDGET_PROBE_MAX = 8
 ERR_BUDGET = -6
+ERR_BOUND = -7
 
 
 def budget_tol(g):
@@ -460,6 +478,12 @@ def budget_tol(g):
 def budget_index(tolrel):
     """The smallest g with budget_tol(g) >= tolrel, clamped to the grid (wr_budget_index)."""
     return int(lib().wr_budget_index(float(tolrel)))
+
+
+def bounded_start(max_abs_err, absmax):
+    """The largest g with budget_tol(g) * absmax <= max_abs_err, clamped to the grid; -1 when even budget_tol(0) is too coarse
+    or an argument is not a positive finite number (wr_bounded_start)."""
+    return int(lib().wr_bounded_start(float(max_abs_err), float(absmax)))
 
 
 def seg_size_bound_host_ref(plane, seg=0):
@@ -1313,6 +1337,81 @@ class Context:
     def encode_seg_budget(self, buf, shape, max_bytes, tol_min=2.0 ** -60, wtflag=1, seg=0, out=None, m=(1, 1, 1)):
         """encode_host_seg_budget with the field resident on the device (`buf` is consumed, as by encode)."""
         return self._encode_seg_budget(lib().wr_encode_device_seg_budget, buf.ptr, shape, max_bytes, tol_min, wtflag, seg, out, m)
+
+    # ---- encode to a pointwise error bound: the library picks the tolerance on the grid budget_tol(g), every plane is coded once
+    def _encode_seg_bounded(self, fn, ptr, shape, max_abs_err, tol_min, wtflag, seg, brick, strands, out, m):
+        nz, ny, nx = shape
+        cap = self._seg_cap(shape, seg, brick if brick else None, strands if strands else None)
+        data = out if out is not None else np.empty(cap, dtype=np.uint8)
+        info, tm, res = EncInfo(), Timings(), BoundedResult()
+        _check(fn(self.h, ptr, nx, ny, nz, wtflag, m[0], m[1], m[2], float(max_abs_err), float(tol_min), seg, brick, strands, C.byref(info),
+                  data.ctypes.data, data.size, C.byref(tm), C.byref(res)))
+        d = info.as_dict()
+        d["data"] = data[:info.ntot_enc]
+        return d, d["data"], {"g": res.g, "tolrel": res.tolrel, "err": res.err, "trials": res.trials, "timings": tm.as_dict()}
+
+    def encode_host_seg_bounded(self, fld, max_abs_err, tol_min=2.0 ** -60, seg=0, brick=0, strands=0, wtflag=1, out=None, m=(1, 1, 1)):
+        """The segmented stream of `fld` at a tolerance of the grid, not below tol_min, whose reconstruction is within
+        max_abs_err of `fld` at every sample while the next coarser point's is not (wr_encode_host_seg_bounded).  brick = 0,
+        strands = 0: WRS1; brick > 0: WRS2; strands > 0: WRS3.  Returns (info, data, result): info as encode_host_seg gives it for
+        tolrel = result["tolrel"] = budget_tol(result["g"]), data = info["data"], result["err"] the error reached."""
+        assert fld.dtype == np.float64 and fld.flags["C_CONTIGUOUS"]
+        return self._encode_seg_bounded(lib().wr_encode_host_seg_bounded, fld.ctypes.data, fld.shape, max_abs_err, tol_min, wtflag, seg, brick, strands, out, m)
+
+    def encode_host_seg_bounded_f32(self, fld, max_abs_err, tol_min=2.0 ** -60, seg=0, brick=0, strands=0, wtflag=1, out=None, m=(1, 1, 1)):
+        if not (isinstance(fld, np.ndarray) and fld.dtype == np.float32 and fld.flags["C_CONTIGUOUS"]):
+            raise TypeError("encode_host_seg_bounded_f32: a C-contiguous float32 array is required")
+        return self._encode_seg_bounded(lib().wr_encode_host_seg_bounded_f32, fld.ctypes.data, fld.shape, max_abs_err, tol_min, wtflag, seg, brick, strands, out, m)
+
+    def encode_seg_bounded(self, buf, shape, max_abs_err, tol_min=2.0 ** -60, seg=0, brick=0, strands=0, wtflag=1, out=None, m=(1, 1, 1)):
+        """encode_host_seg_bounded with the field resident on the device (`buf` is consumed, as by encode)."""
+        return self._encode_seg_bounded(lib().wr_encode_device_seg_bounded, buf.ptr, shape, max_abs_err, tol_min, wtflag, seg, brick, strands, out, m)
+
+    def bounded_trial_ms(self):
+        """(requantize, inverse, compare) milliseconds summed over the trials of the last bounded encode on this context."""
+        a, b, d = C.c_double(0), C.c_double(0), C.c_double(0)
+        _check(lib().wr_ctx_bounded_trial_ms(self.h, C.byref(a), C.byref(b), C.byref(d)))
+        return float(a.value), float(b.value), float(d.value)
+
+    def _seg_error(self, fn, fld, enc):
+        nz, ny, nx = fld.shape
+        info = EncInfo.from_dict(enc)
+        data = np.ascontiguousarray(enc["data"], dtype=np.uint8)
+        if data.size == 0:
+            data = np.zeros(1, dtype=np.uint8)
+        err = C.c_double(0)
+        _check(fn(self.h, fld.ctypes.data, nx, ny, nz, C.byref(info), data.ctypes.data, data.size, C.byref(err)))
+        return float(err.value)
+
+    def seg_error_host(self, fld, enc):
+        """max |fld - reconstruction| of the segmented stream `enc`, formed and compared on the device (wr_seg_error_host)."""
+        assert fld.dtype == np.float64 and fld.flags["C_CONTIGUOUS"]
+        return self._seg_error(lib().wr_seg_error_host, fld, enc)
+
+    def seg_error_host_f32(self, fld, enc):
+        if not (isinstance(fld, np.ndarray) and fld.dtype == np.float32 and fld.flags["C_CONTIGUOUS"]):
+            raise TypeError("seg_error_host_f32: a C-contiguous float32 array is required")
+        return self._seg_error(lib().wr_seg_error_host_f32, fld, enc)
+
+    def requant_accum(self, coef, deps, minval, offset=0):
+        """Stage level: the decoder's coefficient sum of the len(deps) planes the quantizer loop cuts from `coef` (float64) with
+        those steps and offsets; no plane is written (wr_dev_requant_accum).  offset: bytes the coefficient array is moved off
+        its 16-byte alignment on the device (a multiple of 8)."""
+        x = np.ascontiguousarray(coef, dtype=np.float64).ravel()
+        dv = np.ascontiguousarray(deps, dtype=np.float64).ravel()
+        mv = np.ascontiguousarray(minval, dtype=np.float64).ravel()
+        assert dv.size == mv.size and offset % 8 == 0
+        d_x, d_acc = self.alloc(max(x.nbytes, 16) + offset), self.alloc(max(x.nbytes, 16))
+        try:
+            if x.size:
+                _check(lib().wr_dev_upload(self.h, d_x.ptr + offset, x.ctypes.data, x.nbytes))
+            dd = dv if dv.size else np.zeros(1)
+            mm = mv if mv.size else np.zeros(1)
+            _check(lib().wr_dev_requant_accum(self.h, d_x.ptr + offset, x.size, int(dv.size), dd.ctypes.data_as(_dp), mm.ctypes.data_as(_dp), d_acc.ptr))
+            return d_acc.download(np.float64, x.size)
+        finally:
+            d_x.free()
+            d_acc.free()
 
     def plane_size_bound(self, plane, seg=0):
         """Stage level: the size bound of a plane of symbols, computed on the device (wr_dev_plane_size_bound)."""

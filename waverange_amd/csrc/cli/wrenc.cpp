@@ -8,6 +8,8 @@
 // Arguments that start with "--" are options of this tool and are taken out before any of that:
 //   --format=ref|wrs1|wrs2|wrs3[:seg=N][:brick=B][:strands=K]   the stream format of the coded fields (waverange_amd.h,
 //       wr_stream_format_parse); without it the library's setting decides (WR_STREAM_FORMAT, else the reference's stream)
+//   --maxerr=E  encode every compressed field to a pointwise error bound (wr_encode_host_seg_bounded): E is absolute, in the
+//               field's units; TOLERANCE is the finest tolerance allowed; needs --format=wrs1, wrs2 or wrs3, excludes --ratio
 //   --ratio=R   encode every compressed field to a byte budget (wr_encode_host_seg_budget): the field's bytes on disk divided
 //       by R.  TOLERANCE is then the finest tolerance the search may choose; the tool prints the one it chose.  Needs
 //       --format=wrs1.
@@ -187,6 +189,7 @@ void usage()
     cout << "interactive mode if not enough arguments are passed.\n";
     cout << "option: --format=ref|wrs1|wrs2|wrs3[:seg=N][:brick=B][:strands=K] (stream format of the coded fields; default: WR_STREAM_FORMAT, else ref)\n";
     cout << "option: --ratio=R (with --format=wrs1: every field coded into its bytes on disk / R, at the finest tolerance not below TOLERANCE that fits)\n";
+    cout << "option: --maxerr=E (with --format=wrs1|wrs2|wrs3: every field coded at the coarsest tolerance not below TOLERANCE that keeps every sample within E, in the field's units)\n";
 }
 
 void parse_argv(char** argv, Job& job)  // gen_enc.cpp:365-412
@@ -243,6 +246,8 @@ int main(int argc, char** argv)
     bool have_format = false;
     string ratio_text;
     double ratio = 0;
+    string maxerr_text;
+    double maxerr = 0;
     for (const string& o : options) {
         if (wrcli::option_value(o, "format", &format_text)) { have_format = true; continue; }
         if (wrcli::option_value(o, "ratio", &ratio_text)) {
@@ -251,6 +256,16 @@ int main(int argc, char** argv)
             if (ratio_text.empty() || *end || !(ratio >= 1.0) || !(ratio < 1e12)) {
                 usage();
                 cout << "Error: --ratio=" << ratio_text << ": a number of at least 1 is required" << endl;
+                return 2;
+            }
+            continue;
+        }
+        if (wrcli::option_value(o, "maxerr", &maxerr_text)) {
+            char* end = nullptr;
+            maxerr = strtod(maxerr_text.c_str(), &end);
+            if (maxerr_text.empty() || *end || !(maxerr > 0) || !(maxerr < 1e308)) {
+                usage();
+                cout << "Error: --maxerr=" << maxerr_text << ": a positive number is required" << endl;
                 return 2;
             }
             continue;
@@ -282,7 +297,30 @@ int main(int argc, char** argv)
         }
         wr_get_stream_format(nullptr, &budget_seg, nullptr, nullptr);
     }
-    wrcli::ContextPool contexts;  // --ratio: one explicit context per field in flight
+    unsigned bounded_fmt[3] = {0, 0, 0};  // --maxerr: seg, brick, strands of the bounded calls
+    if (maxerr > 0) {
+        if (ratio > 0) {
+            usage();
+            cout << "Error: --maxerr and --ratio exclude one another" << endl;
+            return 2;
+        }
+        if (stream_format != WR_FORMAT_WRS1 && stream_format != WR_FORMAT_WRS2 && stream_format != WR_FORMAT_WRS3) {
+            usage();
+            cout << "Error: --maxerr needs --format=wrs1, wrs2 or wrs3" << endl;
+            return 2;
+        }
+        if (!wr_encode_host_seg_bounded || !wr_encode_host_seg_bounded_f32 || !wr_get_stream_format || !wr_ctx_create) {
+            usage();
+            cout << "Error: --maxerr: " << wrcli::kNotSupported << endl;
+            return 2;
+        }
+        wr_get_stream_format(nullptr, &bounded_fmt[0], &bounded_fmt[1], &bounded_fmt[2]);
+        if (stream_format == WR_FORMAT_WRS1) bounded_fmt[1] = bounded_fmt[2] = 0;
+        if (stream_format == WR_FORMAT_WRS2) { bounded_fmt[2] = 0; if (!bounded_fmt[1]) bounded_fmt[1] = WR_BRICK_DEFAULT; }
+        if (stream_format == WR_FORMAT_WRS3 && !bounded_fmt[2]) bounded_fmt[2] = WR_STRANDS_DEFAULT;
+    }
+    const unsigned bseg = bounded_fmt[0], bbrick = bounded_fmt[1], bstrands = bounded_fmt[2];
+    wrcli::ContextPool contexts;  // --ratio, --maxerr: one explicit context per field in flight
     wrcli::PhaseClock clock("wrenc");
 
     Job job;
@@ -414,7 +452,7 @@ int main(int argc, char** argv)
         }
         Item* ip = &im;
         const bool pipelined = depth > 0;
-        auto work = [ip, cutoff, pipelined, ratio, budget_seg, &contexts, &scan, &clock]() {
+        auto work = [ip, cutoff, pipelined, ratio, budget_seg, maxerr, bseg, bbrick, bstrands, &contexts, &scan, &clock]() {
             const wrio::FieldSpec& sp = ip->h.spec;
             if (pipelined) scan(*ip, ip->log);
             if (!sp.icomp) { (pipelined ? static_cast<std::ostream&>(ip->log) : cout) << "  Compression disabled" << endl; return; }
@@ -443,6 +481,32 @@ int main(int argc, char** argv)
                 char line[200];
                 snprintf(line, sizeof line, "  Budget %zu bytes: relative tolerance %.17g (grid point %d), bound %zu bytes, coded %lu bytes\n", budget, res.tolrel,
                          res.g, res.bound, info.ntot_enc);
+                (pipelined ? static_cast<std::ostream&>(ip->log) : cout) << line;
+                ip->h.tolabs = info.tolabs; ip->h.midval = info.midval; ip->h.halfspanval = info.halfspanval;
+                wlev = info.wlev; nlay = info.nlay;
+                ip->h.ntot_enc = info.ntot_enc;
+                for (int l = 0; l < WR_NLAYMAX; l++) {
+                    ip->h.deps_vec[l] = info.deps_vec[l]; ip->h.minval_vec[l] = info.minval_vec[l]; ip->h.len_enc_vec[l] = info.len_enc_vec[l];
+                }
+            } else if (maxerr > 0) {  // to an error bound: no sample further than E from its reconstruction, no tolerance finer than the command line's
+                wr_ctx* ctx = contexts.borrow();
+                wr_enc_info info;
+                wr_bounded_result res;
+                int rc = ctx ? 0 : -1;
+                if (ctx)
+                    rc = ip->fld32 ? wr_encode_host_seg_bounded_f32(ctx, ip->fld32.get(), sp.nx, sp.ny, sp.nz * sp.nh, 1, 1, 1, 1, maxerr, cut, bseg, bbrick,
+                                                                    bstrands, &info, ip->data_enc.data(), ip->cap, nullptr, &res)
+                                   : wr_encode_host_seg_bounded(ctx, ip->fld.data(), sp.nx, sp.ny, sp.nz * sp.nh, 1, 1, 1, 1, maxerr, cut, bseg, bbrick, bstrands,
+                                                                &info, ip->data_enc.data(), ip->cap, nullptr, &res);
+                if (ctx) contexts.give(ctx);
+                if (rc != 0) {  // (as the codec's own failures: the tool ends here, whatever other fields are in flight)
+                    cout.flush();
+                    fprintf(stderr, "Error: field with an error bound of %.17g: %s\n", maxerr, wr_last_error());
+                    std::_Exit(1);
+                }
+                char line[240];
+                snprintf(line, sizeof line, "  Error bound %.17g: relative tolerance %.17g (grid point %d), error %.17g, %d trials, coded %lu bytes\n", maxerr,
+                         res.tolrel, res.g, res.err, res.trials, info.ntot_enc);
                 (pipelined ? static_cast<std::ostream&>(ip->log) : cout) << line;
                 ip->h.tolabs = info.tolabs; ip->h.midval = info.midval; ip->h.halfspanval = info.halfspanval;
                 wlev = info.wlev; nlay = info.nlay;

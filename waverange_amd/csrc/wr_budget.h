@@ -1,6 +1,7 @@
 // wr_budget.h -- what an encode to a byte budget is made of, shared by host and device (g++ and hipcc alike, as wr_segcoder.h):
 // the grid of relative tolerances the search runs on, and a rigorous upper bound on the bytes of a WRS1 plane blob that
-// needs nothing but the segments' histograms.
+// needs nothing but the segments' histograms.  An encode to an error bound searches the same grid: its start point and its walk
+// over the grid (bounded_start, bounded_walk) are here too, host code only.
 //
 // The bound.  A segment stream is start(); freq(1, 1, 2); 256 x shift16(count); freq(count, cum, bs) per symbol; freq(1, 0, 2);
 // finish() (wr_segcoder.h: encode_segment).  Let P = 8 N - log2(range), N the iterations of Enc::renorm() so far.  An
@@ -22,6 +23,7 @@
 // every entry fits 32 bits (59999 x 15.884 x 4096 < 2^32).  256 entries rounded by less than 2^-12 bit each cost a
 // segment 1/16 bit.
 #pragma once
+#include <float.h>
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -57,6 +59,86 @@ inline int grid_index(double tolrel)
         else lo = mid;
     }
     return hi;
+}
+
+// where the search of an encode to an error bound starts: the largest g with t(g) * absmax <= max_abs_err (one fp64 multiply,
+// which does not fall as g grows, so a bisection by comparison finds it); -1 when even t(0) is too coarse or an argument is
+// not a positive finite number
+inline int bounded_start(double max_abs_err, double absmax)
+{
+    if (!(max_abs_err > 0) || !(absmax > 0) || max_abs_err > DBL_MAX || absmax > DBL_MAX) return -1;
+    if (!(grid_tol(0) * absmax <= max_abs_err)) return -1;
+    if (grid_tol(kGMax) * absmax <= max_abs_err) return kGMax;
+    int lo = 0, hi = kGMax;  // t(lo) * absmax <= max_abs_err < t(hi) * absmax
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) / 2;
+        if (grid_tol(mid) * absmax <= max_abs_err) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// grid points a change of the error by the factor r (> 1) is worth at nominal: 64 to the octave, a quarter kept back
+inline int bounded_points(double r)
+{
+    const double d = 48.0 * log2(r);
+    return d >= (double)kGMax ? kGMax : d > 0 ? (int)d : 0;
+}
+
+// The walk of an encode to an error bound over E(g), the error reached at grid point g.  eval(g, &e) forms E(g) (0: done,
+// otherwise the walk ends with that code); it is asked about a point at most once.  From `start` (clamped to [g_min, kGMax]):
+// while the bound does not hold, finer by the ratio E / max_err, or by twice the last step if that is more; then coarser
+// likewise by max_err / E, and when a step lands on a point that does not hold, a bisection between it and the last one that
+// does ends on neighbours.  Near nominal that is a jump and a few single steps; it is never more than 2 log2 of the grid.
+// Returns 0 with *g in [g_min, kGMax], *e = E(*g) <= max_err and *g == kGMax or E(*g + 1) > max_err (E is not monotone: the
+// property is this local one); kBoundedMiss with *e = E(g_min) > max_err; or eval's code.
+constexpr int kBoundedMiss = -1000;
+template <class Eval>
+int bounded_walk(double max_err, int g_min, int start, Eval eval, int* g, double* e)
+{
+    std::vector<double> known((size_t)kGMax + 1, -1.0);  // E >= 0 where it has been formed
+    auto E = [&](int at, double* out) {
+        if (known[(size_t)at] < 0) {
+            if (int rc = eval(at, out)) return rc;
+            known[(size_t)at] = *out;
+        }
+        *out = known[(size_t)at];
+        return 0;
+    };
+    if (g_min < 0) g_min = 0;
+    if (g_min > kGMax) g_min = kGMax;
+    int at = start < g_min ? g_min : start > kGMax ? kGMax : start;
+    double cur = 0, e2 = 0;
+    if (int rc = E(at, &cur)) return rc;
+    int step = 0;
+    while (!(cur <= max_err)) {
+        if (at == g_min) { *g = at; *e = cur; return kBoundedMiss; }
+        const int d = bounded_points(cur / max_err);
+        step = d > 2 * step ? d : 2 * step;  // (doubling: an error that does not follow the tolerance costs log2 of the grid, not the grid)
+        if (step < 1) step = 1;
+        at = at - step < g_min ? g_min : at - step;
+        if (int rc = E(at, &cur)) return rc;
+    }
+    step = 0;
+    while (at < kGMax) {
+        const int d = cur > 0 ? bounded_points(max_err / cur) : kGMax;
+        step = d > 2 * step ? d : 2 * step;
+        if (step < 1) step = 1;
+        const int far = at + step > kGMax ? kGMax : at + step;
+        if (int rc = E(far, &e2)) return rc;
+        if (e2 <= max_err) { at = far; cur = e2; continue; }
+        int good = at, bad = far;  // E(good) holds, E(bad) does not: neighbours of that kind between them
+        while (bad - good > 1) {
+            const int mid = good + (bad - good) / 2;
+            if (int rc = E(mid, &e2)) return rc;
+            if (e2 <= max_err) { good = mid; cur = e2; }
+            else bad = mid;
+        }
+        at = good;
+        break;
+    }
+    *g = at; *e = cur;
+    return 0;
 }
 
 // ---- the size bound

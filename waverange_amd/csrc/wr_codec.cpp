@@ -1216,6 +1216,7 @@ struct SegBufs {
     wr_ctx* c;
     DevPlanes::Buf stage, blob[WR_NLAYMAX], work[WR_NLAYMAX];
     DevPlanes::Buf perm, bricks;  // a blocked stream: one plane in stream order (every plane in turn), the brick list of a partial decode
+    DevPlanes::Buf trial[3];      // an encode to an error bound / wr_seg_error_host: two work arrays of a trial, the copy of the field
     hipEvent_t ev[2 * WR_NLAYMAX] = {nullptr};
     explicit SegBufs(wr_ctx* ctx) : c(ctx) {}
     SegBufs(const SegBufs&) = delete;
@@ -1226,6 +1227,7 @@ struct SegBufs {
         if (stage.p) c->pool->planes.give(stage);
         if (perm.p) c->pool->planes.give(perm);
         if (bricks.p) c->pool->planes.give(bricks);
+        for (DevPlanes::Buf& b : trial) if (b.p) c->pool->planes.give(b);
         for (int l = 0; l < WR_NLAYMAX; l++) {
             if (blob[l].p) c->pool->planes.give(blob[l]);
             if (work[l].p) c->pool->planes.give(work[l]);
@@ -1478,9 +1480,137 @@ struct BudgetSearch {
     }
 };
 
+// ---- the search of an encode to an error bound (include/waverange_amd.h) ------------------------------------------------------
+// E(g) is measured, not bounded: a trial at g forms the reconstruction the decoder would return and compares it with the field.
+// The planes of a trial are never written.  As above only the last plane depends on the tolerance: the residual range plane l
+// is cut from, given that planes 0 .. l-1 were full, is the same at every tolerance (range[l]: the size probe's min/max of the
+// full-step candidate, once per depth), so the host replays the quantizer loop's scalars at tolabs(g) and one kernel
+// (requant_accum) turns the coefficient array into the decoder's coefficient sum.  Then the decoder's own inverse stage, as
+// inverse_from_planes runs it, and the compare; one read-back per trial.
+// The whole search runs at the pick of plane 0, on the context's stream, before anything is quantized: the loop then runs at
+// tolabs(g) exactly as the plain call does, which is what makes the stream the plain call's and codes every plane once.
+// The walk over the grid is wrbud::bounded_walk (wr_budget.h: plain host code, fuzzed on its own), from wrbud::bounded_start.
+struct BoundedSearch {
+    // what the caller asks for
+    double max_err = 0;
+    int g_min = 0;
+    // what comes out
+    int g = -1;
+    double err = 0;
+    int trials = 0;
+    double ms[3] = {0, 0, 0};
+
+    wr_ctx* c = nullptr;
+    Slot* slot = nullptr;
+    int nx = 0, ny = 0, nz = 0, wlev = 0;
+    size_t n = 0;
+    unsigned seg = 0;
+    const double* orig = nullptr;    // the field as the caller gave it, on the device, or
+    const float* orig_f32 = nullptr;
+    double *w1 = nullptr, *w2 = nullptr;
+    const double* d_coef = nullptr;
+    Prologue p{};
+    int nrange = 0;
+    double rlo[WR_NLAYMAX], rhi[WR_NLAYMAX];  // range[l], known for l < nrange
+
+    static double* result_host(wr_ctx* c) { return c->h_result + 8 + 2 * WR_NLAYMAX + wrk::kProbeK; }
+    static double* result_dev(wr_ctx* c) { return c->h_result_dev + 8 + 2 * WR_NLAYMAX + wrk::kProbeK; }
+
+    // max |a - b| and the count of differences that are not finite, read back
+    template <class T>
+    static int compare(wr_ctx* c, const T* a, const T* b, size_t n, double* mx, double* bad)
+    {
+        wrk::linf_count(a, b, n, c->d_partial, result_dev(c), c->stream);
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "compare launch failed");
+        HIPCHK(hipEventRecord(c->ev_d, c->stream));
+        HIPCHK(hipEventSynchronize(c->ev_d));
+        *mx = result_host(c)[0]; *bad = result_host(c)[1];
+        return WR_OK;
+    }
+
+    int nonfinite_field(const std::string& what)
+    {
+        double mx = 0, bad = 0;
+        if (int rc = orig_f32 ? compare(c, orig_f32, orig_f32, n, &mx, &bad) : compare(c, orig, orig, n, &mx, &bad)) return rc;
+        if (bad > 0) return fail(WR_ERR_ARG, "an encode to an error bound needs a finite field: " + std::to_string((unsigned long long)bad) +
+                                                 " sample(s) are a NaN or an infinity");
+        return fail(WR_ERR_ARG, what);
+    }
+
+    // range[l + 1]: what the full step of plane l leaves, the planes before being `prev`
+    int next_range(int l, const wrk::QuantPrev& prev, const PlaneStep& s)
+    {
+        if (int rc = BudgetSearch::tables(c)) return rc;
+        wrk::ProbeCands cd;
+        cd.n = 1; cd.aopt[0] = s.aopt; cd.bopt[0] = s.bopt; cd.deps0 = s.deps; cd.minval0 = s.minval;
+        size_t unused[wrk::kProbeK];
+        if (int rc = BudgetSearch::launch(c, c->stream, d_coef, n, seg, prev, cd, true, unused)) return rc;
+        rlo[l + 1] = c->h_result[0]; rhi[l + 1] = c->h_result[1];
+        nrange = l + 2;
+        return WR_OK;
+    }
+
+    // E(gk), formed on the device
+    int eval(int gk, double* e)
+    {
+        const double tolabs = abs_tolerance(wrbud::grid_tol(gk), p);
+        wrk::QuantPrev prev;
+        PlaneStep s;
+        for (int l = 0;; l++) {  // (plane WR_NLAYMAX - 1 is the last whatever its step: prev never outgrows kQuantPrevMax)
+            s = plane_step(rlo[l], rhi[l], tolabs, (unsigned)l);
+            if (s.last) break;
+            if (l + 1 >= nrange) if (int rc = next_range(l, prev, s)) return rc;
+            prev.push(s.aopt, s.bopt, s.deps, s.minval);
+        }
+        const bool fused = wlev == kWavLvl && use_fused(nx, ny, nz, -kWavLvl);
+        if (fused) if (const char* why = wrk::fused_prepare()) return fail(WR_ERR_HIP, why);
+        HIPCHK(hipEventRecord(c->ev_a, c->stream));
+        wrk::requant_accum(d_coef, n, prev, s.aopt, s.bopt, s.deps, s.minval, w1, c->stream);
+        HIPCHK(hipEventRecord(c->ev_b, c->stream));
+        // the decoder's inverse stage (inverse_from_planes), the sum in w1 and w2 in the place of the slot's arrays
+        const double* rec = w1;
+        const float* rec_f32 = reinterpret_cast<const float*>(w2);
+        if (fused && orig_f32) wrk::transform_inv_fused_f32(w1, reinterpret_cast<float*>(w2), w2, slot->lowbuf, nx, ny, nz, c->stream);
+        else if (fused) { wrk::transform_inv_fused(w1, w2, slot->lowbuf, nx, ny, nz, c->stream); rec = w2; }
+        else {
+            if (wlev) wrk::transform(w1, w2, nx, ny, nz, -wlev, c->stream);
+            if (orig_f32) wrk::narrow_f64(w1, reinterpret_cast<float*>(w2), n, c->stream);
+        }
+        HIPCHK(hipEventRecord(c->ev_c, c->stream));
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "a trial's kernel launch failed");
+        double bad = 0;
+        if (int rc = orig_f32 ? compare(c, orig_f32, rec_f32, n, e, &bad) : compare(c, orig, rec, n, e, &bad)) return rc;
+        float t = 0;
+        HIPCHK(hipEventElapsedTime(&t, c->ev_a, c->ev_b)); ms[0] += t;
+        HIPCHK(hipEventElapsedTime(&t, c->ev_b, c->ev_c)); ms[1] += t;
+        HIPCHK(hipEventElapsedTime(&t, c->ev_c, c->ev_d)); ms[2] += t;
+        trials++;
+        if (bad > 0) return nonfinite_field("an encode to an error bound: the reconstruction at tolerance " + std::to_string(wrbud::grid_tol(gk)) + " is not finite");
+        return WR_OK;
+    }
+
+    int run(double lo, double hi, const double* coef, const Prologue& pro)
+    {
+        d_coef = coef; p = pro;
+        if ((uintptr_t)d_coef & 15) return fail(WR_ERR_ARG, "an encode to an error bound needs a 16-byte aligned coefficient array");
+        const double absmax = fmax(fabs(p.lo), fabs(p.hi));
+        if (!(absmax <= DBL_MAX)) return nonfinite_field("an encode to an error bound needs a finite field");
+        rlo[0] = lo; rhi[0] = hi; nrange = 1;
+        const int rc = wrbud::bounded_walk(max_err, g_min, wrbud::bounded_start(max_err, absmax), [this](int gk, double* e) { return eval(gk, e); }, &g, &err);
+        if (rc == wrbud::kBoundedMiss) {
+            char b[200];
+            snprintf(b, sizeof b, "the error bound %.17g is below what the finest tolerance allowed reaches: E(g_min = %d) = %.17g", max_err, g, err);
+            g = -1;
+            return fail(WR_ERR_BOUND, b);
+        }
+        return rc;
+    }
+};
+
 // bud != nullptr: an encode to a byte budget (WRS1): the tolerance comes from the search, cut.vec[0] only names the finest one
+// bnd != nullptr: an encode to an error bound (any of the formats), likewise
 int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, const Cutoff& cut, unsigned seg, unsigned brick, unsigned strands,
-                    wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm, BudgetSearch* bud = nullptr)
+                    wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm, BudgetSearch* bud = nullptr, BoundedSearch* bnd = nullptr)
 {
     if (!seg) seg = WR_SEG_DEFAULT;
     if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
@@ -1496,6 +1626,8 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
         return fail(WR_ERR_UNSUPPORTED, "an fp32 field cannot take the residual back: wr_ctx_set_keep_residual(ctx, 0) for fp32 encodes");
     if (bud && c->keep_residual)
         return fail(WR_ERR_UNSUPPORTED, "an encode to a byte budget does not keep the residual: wr_ctx_set_keep_residual(ctx, 0)");
+    if (bnd && c->keep_residual)
+        return fail(WR_ERR_UNSUPPORTED, "an encode to an error bound does not keep the residual: wr_ctx_set_keep_residual(ctx, 0)");
     ActiveCall active(c->pool);
     if (tm) wrdma::enable_timing();
     const double t0 = now();
@@ -1540,6 +1672,25 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
         bufs.perm = plane_scratch(c, n);
         if (!bufs.perm.p) return WR_ERR_HIP;
     }
+    if (bnd) {  // the trials' work arrays, and the field where the forward transform will not leave it as it is
+        for (int k = 0; k < 2; k++) {
+            bufs.trial[k] = plane_scratch(c, n * sizeof(double));
+            if (!bufs.trial[k].p) return WR_ERR_HIP;
+        }
+        const bool intact = wtflag && use_fused(nx, ny, nz, kWavLvl) && wrk::fused_minmax_records(nx, ny, nz) != 0;  // all four levels out of place
+        const void* src = fld.host_f32 ? (d_f32 ? (const void*)d_f32 : (const void*)widen_from) : (const void*)d_fld;
+        if (!intact) {
+            const size_t bytes = n * (fld.host_f32 ? sizeof(float) : sizeof(double));
+            bufs.trial[2] = plane_scratch(c, bytes);
+            if (!bufs.trial[2].p) return WR_ERR_HIP;
+            HIPCHK(hipMemcpyAsync(bufs.trial[2].p, src, bytes, hipMemcpyDeviceToDevice, c->stream));
+            src = bufs.trial[2].p;
+        }
+        bnd->c = c; bnd->slot = slot.get(); bnd->nx = nx; bnd->ny = ny; bnd->nz = nz; bnd->wlev = wtflag ? kWavLvl : 0; bnd->n = n; bnd->seg = seg;
+        if (fld.host_f32) bnd->orig_f32 = static_cast<const float*>(src);
+        else bnd->orig = static_cast<const double*>(src);
+        bnd->w1 = reinterpret_cast<double*>(bufs.trial[0].p); bnd->w2 = reinterpret_cast<double*>(bufs.trial[1].p);
+    }
     double* resid = d_fld;
     int rc = WR_OK;
     {
@@ -1565,6 +1716,7 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
             HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
             if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented coder launch failed" + launch_describe(c));
             if (bud) g_stat[WR_STAT_BUDGET_CODER_RUNS]++;
+            if (bnd) g_stat[WR_STAT_BOUNDED_CODER_RUNS]++;
             return WR_OK;
         };
         clock_warmup(c, n);
@@ -1576,8 +1728,16 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
                 return bud->pick(l, lo, hi, prev, d_coef, p, tolabs);
             };
         }
+        if (bnd) {  // the whole search at plane 0; the loop then runs at the tolerance it chose, as the plain call does
+            pick = [bnd](unsigned l, double lo, double hi, const wrk::QuantPrev&, const double* d_coef, const Prologue& p, double* tolabs) {
+                if (l) return (int)WR_OK;
+                if (int prc = bnd->run(lo, hi, d_coef, p)) return prc;
+                *tolabs = abs_tolerance(wrbud::grid_tol(bnd->g), p);
+                return (int)WR_OK;
+            };
+        }
         rc = encode_planes_core(c, slot.get(), d_fld, nx, ny, nz, wtflag, cut, plane_buf, [](unsigned) { return (uint16_t*)nullptr; }, info, &local,
-                                after_quant, [](unsigned, bool) { return WR_OK; }, &resid, d_f32, bud ? &pick : nullptr);
+                                after_quant, [](unsigned, bool) { return WR_OK; }, &resid, d_f32, (bud || bnd) ? &pick : nullptr);
         if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the encoder's kernel stage failed on the device" + launch_describe(c));
         if (rc == WR_OK && c->keep_residual && info->nlay && !fld.host && resid != fld.dev) {
             if (hipMemcpyAsync(fld.dev, resid, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
@@ -1914,8 +2074,10 @@ int finish_call(wr_ctx* c, const FieldRef& fld, const void* d_f64, const void* d
 // ---- the drivers.  They differ in the plan (everything; one box or region: a LowresPlan; many regions), in the finisher
 // (inverse_from_planes, lowres_from_planes / roi_from_planes, roi_multi_from_planes) and in where the result lands; the rest
 // is the stages above, in the same order: parse, gather the planes' buffers, "up", lease the slot, coder stage, finisher, tail.
+// err_out != nullptr (wr_seg_error_host): fld is the ORIGINAL field on the host and is only read; the reconstruction stays on
+// the device, where it is compared with an upload of the field: *err_out = max |field - reconstruction|
 int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
-                    wr_timings* tm)
+                    wr_timings* tm, double* err_out = nullptr)
 {
     if (int rc = ctx_bind(c)) return rc;
     if (!info) return fail(WR_ERR_ARG, "null wr_enc_info");
@@ -1933,6 +2095,18 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
     DevPool* const pool = c->pool;
     SegStream s;
     if (int rc = seg_stream_of(nx, ny, nz, info, data_enc, data_len, &s)) return rc;
+    if (s.constant && err_out) {  // the reconstruction is midval everywhere (fill_constant)
+        double mx = 0;
+        size_t bad = 0;
+        for (size_t j = 0; j < n; j++) {
+            const double d = fld.host ? fabs(fld.host[j] - info->midval) : fabs((double)fld.host_f32[j] - (double)(float)info->midval);
+            if (d <= DBL_MAX) mx = d > mx ? d : mx;
+            else bad++;
+        }
+        if (bad) return fail(WR_ERR_ARG, std::to_string(bad) + " difference(s) between the field and the reconstruction are not finite");
+        *err_out = mx;
+        return WR_OK;
+    }
     if (s.constant) return finish_constant(c, fld, n, info->midval, t0, &local, tm);
     {
         std::lock_guard<std::mutex> gather(pool->planes.gather_mu);  // one decode at a time gathers its planes (decode_impl)
@@ -1942,6 +2116,12 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
         }
         for (int l = 0; l < s.nlay; l++)
             if (int rc = seg_plane_bufs(c, &bufs, l, n, info->len_enc_vec[l], wrk::seg_decode_work_bytes(s.nseg[l]), false, true)) return rc;
+        if (err_out) {  // the field, next to the reconstruction
+            const size_t bytes = n * (fld.host_f32 ? sizeof(float) : sizeof(double));
+            bufs.trial[2] = plane_scratch(c, bytes);
+            if (!bufs.trial[2].p) return WR_ERR_HIP;
+            if (int rc = xfer_field(c, &c->x_field, bufs.trial[2].p, fld.host ? (const void*)fld.host : (const void*)fld.host_f32, bytes, kUp)) return rc;
+        }
     }
     if (int rc = seg_upload_planes(c, s, info, data_enc, &bufs, &local.h2d_ms)) return rc;
     const double t_coded = now();
@@ -1964,8 +2144,16 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
         if (int rc = seg_coder_stage(c, k, &local)) return rc;
         launch_note(c, "dequant", s.nlay - 1, d_fld, n, nullptr, p.q[s.nlay - 1]);
         rc = kernel_stage_end(c, inverse_from_planes(c, slot.get(), d_fld, nx, ny, nz, (int)info->wlev, p, fld.host_f32 ? &d_f32 : nullptr));
+        if (rc == WR_OK && err_out) {
+            double bad = 0;
+            rc = fld.host_f32 ? BoundedSearch::compare(c, reinterpret_cast<const float*>(bufs.trial[2].p), (const float*)d_f32, n, err_out, &bad)
+                              : BoundedSearch::compare(c, reinterpret_cast<const double*>(bufs.trial[2].p), (const double*)d_fld, n, err_out, &bad);
+            if (rc == WR_OK && bad > 0)
+                rc = fail(WR_ERR_ARG, std::to_string((unsigned long long)bad) + " difference(s) between the field and the reconstruction are not finite");
+        }
     }
     if (rc) return rc;
+    if (err_out) return WR_OK;
     return finish_call(c, fld, d_fld, d_f32, n, true, t0, t_coded, t_phase, &local, tm);
 }
 
@@ -2547,6 +2735,110 @@ int wr_encode_device_seg_budget(wr_ctx* c, double* d_fld, int nx, int ny, int nz
     FieldRef f; f.dev = d_fld;
     if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
     return encode_seg_budget(c, f, nx, ny, nz, wtflag, mx, my, mz, max_bytes, tol_min, seg, info, data_enc, cap, tm, res);
+}
+
+// ---- encode to an error bound (the search: BoundedSearch above)
+static int encode_seg_bounded(wr_ctx* c, FieldRef f, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, double max_abs_err, double tol_min,
+                              unsigned seg, unsigned brick, unsigned strands, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm,
+                              wr_bounded_result* res)
+{
+    if (!res) return fail(WR_ERR_ARG, "null wr_bounded_result");
+    if (!(max_abs_err > 0) || max_abs_err > DBL_MAX) return fail(WR_ERR_ARG, "max_abs_err must be a positive finite number");
+    if (!(tol_min > 0) || tol_min > DBL_MAX) return fail(WR_ERR_ARG, "tol_min must be a positive number");
+    if (mx < 1 || my < 1 || mz < 1) return fail(WR_ERR_ARG, "bad local cutoff description");
+    if ((long long)mx * my * mz > 1) return fail(WR_ERR_UNSUPPORTED, "an encode to an error bound takes no local cutoff (mx * my * mz > 1)");
+    BoundedSearch bnd;
+    bnd.max_err = max_abs_err;
+    bnd.g_min = wrbud::grid_index(tol_min);
+    const double t_min = wrbud::grid_tol(bnd.g_min);  // (the loop's tolerance until the search sets it; a constant field never gets there)
+    Cutoff cut; cut.vec = &t_min;
+    memset(res, 0, sizeof *res);
+    const int rc = encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick, strands, info, data_enc, cap, tm, nullptr, &bnd);
+    res->trials = bnd.trials;
+    if (c) for (int k = 0; k < 3; k++) c->bounded_ms[k] = bnd.ms[k];
+    if (rc) return rc;
+    if (info->nlay == 0) { bnd.g = wrbud::kGMax; bnd.err = 0; }
+    if (bnd.g < 0) return fail(WR_ERR_HIP, "internal: the search of an encode to an error bound chose no tolerance");
+    res->g = bnd.g;
+    res->tolrel = wrbud::grid_tol(bnd.g);
+    res->err = bnd.err;
+    return WR_OK;
+}
+
+int wr_encode_host_seg_bounded(wr_ctx* c, const double* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, double max_abs_err, double tol_min,
+                               unsigned seg, unsigned brick, unsigned strands, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm,
+                               wr_bounded_result* res)
+{
+    FieldRef f; f.host = const_cast<double*>(h_fld);  // (never written: the residual is not kept)
+    return encode_seg_bounded(c, f, nx, ny, nz, wtflag, mx, my, mz, max_abs_err, tol_min, seg, brick, strands, info, data_enc, cap, tm, res);
+}
+
+int wr_encode_host_seg_bounded_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, double max_abs_err,
+                                   double tol_min, unsigned seg, unsigned brick, unsigned strands, wr_enc_info* info, unsigned char* data_enc, size_t cap,
+                                   wr_timings* tm, wr_bounded_result* res)
+{
+    FieldRef f; f.host_f32 = const_cast<float*>(h_fld);
+    return encode_seg_bounded(c, f, nx, ny, nz, wtflag, mx, my, mz, max_abs_err, tol_min, seg, brick, strands, info, data_enc, cap, tm, res);
+}
+
+int wr_encode_device_seg_bounded(wr_ctx* c, double* d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, double max_abs_err, double tol_min,
+                                 unsigned seg, unsigned brick, unsigned strands, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm,
+                                 wr_bounded_result* res)
+{
+    FieldRef f; f.dev = d_fld;
+    if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
+    return encode_seg_bounded(c, f, nx, ny, nz, wtflag, mx, my, mz, max_abs_err, tol_min, seg, brick, strands, info, data_enc, cap, tm, res);
+}
+
+static int seg_error(wr_ctx* c, FieldRef f, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len, double* err)
+{
+    if (!err) return fail(WR_ERR_ARG, "null result pointer");
+    if (f.none()) return fail(WR_ERR_ARG, "null field pointer");
+    return decode_seg_impl(c, f, nx, ny, nz, info, data_enc, data_len, nullptr, err);
+}
+
+int wr_seg_error_host(wr_ctx* c, const double* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
+                      double* err)
+{
+    FieldRef f; f.host = const_cast<double*>(h_fld);  // (only read: decode_seg_impl's err_out)
+    return seg_error(c, f, nx, ny, nz, info, data_enc, data_len, err);
+}
+
+int wr_seg_error_host_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
+                          double* err)
+{
+    FieldRef f; f.host_f32 = const_cast<float*>(h_fld);
+    return seg_error(c, f, nx, ny, nz, info, data_enc, data_len, err);
+}
+
+int wr_ctx_bounded_trial_ms(wr_ctx* c, double* requant_ms, double* inverse_ms, double* compare_ms)
+{
+    if (!c) return fail(WR_ERR_ARG, "null context");
+    if (requant_ms) *requant_ms = c->bounded_ms[0];
+    if (inverse_ms) *inverse_ms = c->bounded_ms[1];
+    if (compare_ms) *compare_ms = c->bounded_ms[2];
+    return WR_OK;
+}
+
+int wr_dev_requant_accum(wr_ctx* c, const double* d_coef, size_t n, int nlay, const double* deps, const double* minval, double* d_acc)
+{
+    if (nlay < 1 || nlay > WR_NLAYMAX) return fail(WR_ERR_ARG, "a coefficient sum takes 1 to " + std::to_string(WR_NLAYMAX) + " planes");
+    if (int rc = ctx_bind(c)) return rc;
+    if (!deps || !minval || (n && (!d_coef || !d_acc))) return fail(WR_ERR_ARG, "null pointer");
+    if (d_coef < d_acc + n && d_acc < d_coef + n) return fail(WR_ERR_ARG, "the coefficient array and the sum overlap");
+    std::lock_guard<std::mutex> lk(c->mu);
+    wrk::QuantPrev prev;
+    double aopt = 0, bopt = 0;
+    for (int l = 0; l < nlay; l++) {  // plane_step's expressions
+        aopt = 1.0 / deps[l];
+        bopt = -minval[l] * aopt + 0.5;
+        if (l + 1 < nlay) prev.push(aopt, bopt, deps[l], minval[l]);
+    }
+    StageLock cu(c->pool->cu_mu);
+    wrk::requant_accum(d_coef, n, prev, aopt, bopt, deps[nlay - 1], minval[nlay - 1], d_acc, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return WR_OK;
 }
 
 int wr_dev_plane_size_bound(wr_ctx* c, const unsigned char* d_sym, size_t n, unsigned seg, size_t* bound)

@@ -162,8 +162,9 @@ struct wr_ctx {
     unsigned long long* d_idx = nullptr;
     uint32_t* d_bound_tab = nullptr;              // the size bound's table (wr_budget.h), uploaded at the first budget call
     unsigned long long* d_bound_tot = nullptr;    // the size probe's totals, wrk::kProbeK words
+    double bounded_ms[3] = {0, 0, 0};             // the last encode to an error bound: its trials' requantize, inverse and compare stages, summed (HIP events)
     // pinned host
-    double* h_result = nullptr;  // [0..1] min/max, [2] probe value, [3] index, [4..7] fused min/max, [8 + 2l, 9 + 2l] plane l's segmented-coder result (u64: blob length, failed segments), [8 + 2 WR_NLAYMAX ..] the size probe's kProbeK totals (u64)
+    double* h_result = nullptr;  // [0..1] min/max, [2] probe value, [3] index, [4..7] fused min/max, [8 + 2l, 9 + 2l] plane l's segmented-coder result (u64: blob length, failed segments), [8 + 2 WR_NLAYMAX ..] the size probe's kProbeK totals (u64), then {max |diff|, non-finite differences} of a bounded encode's compare
     double* h_result_dev = nullptr;  // the same block as the device sees it: reductions write their result straight to the host
     uint16_t* h_hist = nullptr; size_t h_hist_elems = 0;  // pinned: per-block byte histograms, all planes
     // host coded-stream staging, one per plane

@@ -103,6 +103,16 @@ void quant_probe(const double* x, size_t n, unsigned seg, const QuantPrev& prev,
 // the same sum for a plane of symbols that exists (16-byte aligned, one array): totals[0]
 void plane_bound(const uint8_t* sym, size_t n, unsigned seg, const uint32_t* tab, unsigned long long fixed, unsigned long long* totals, hipStream_t st);
 
+// ---- the trial of an encode to an error bound (k_requant_accum).  x holds the COEFFICIENTS (read only); acc[j] becomes what
+// dequant_accum gives from the planes quantize_plane_blk would write for the full planes in prev, in order, and then a last
+// plane cut with (aopt, bopt, deps, minval), bit for bit.  No plane is written.  acc must not overlap x.  Both pointers
+// 16-byte aligned: 16-byte loads and stores; otherwise an element-wise form of the same arithmetic.
+void requant_accum(const double* x, size_t n, const QuantPrev& prev, double aopt, double bopt, double deps, double minval, double* acc, hipStream_t st);
+// ---- its compare: result[0] = max |a[j] - b[j]| over the differences that are finite (both operands widened to fp64, one
+// subtraction each; 0 if there is none), result[1] = the count of those that are not.  partial: 2 * minmax_partials() doubles.
+void linf_count(const double* a, const double* b, size_t n, double* partial, double* result, hipStream_t st);
+void linf_count(const float* a, const float* b, size_t n, double* partial, double* result, hipStream_t st);
+
 // ---- quantizer plane with the non-uniform (local) cutoff mask (wrappers.cpp:343-379, 397-398):
 // loops over PHYSICAL positions, maps each to its wavelet-space index (ind_p2w_3d,
 // waveletcdf97_3d.c:473-553) and quantizes there; coefficients of the finest level whose plane

@@ -1085,6 +1085,156 @@ void linf_diff(const double* a, const double* b, size_t n, double* partial, doub
     hipLaunchKernelGGL(k_neg0, dim3(1), dim3(1), 0, st, result);
 }
 
+// The compare of an encode to an error bound: max |a - b| over the differences that are finite, and the count of those that
+// are not (a NaN or an infinity on either side).  Both operands widened to fp64, one subtraction per sample; the maximum of
+// such values is exact, whatever the order of the reduction.  partial[2b] = block b's maximum, partial[2b + 1] its count
+// (an integer below 2^53 in a double: the sums are exact).
+__device__ inline void linf_cnt_acc(double a, double b, double& mx, double& cnt)
+{
+    const double d = fabs(a - b);
+    if (d <= DBL_MAX) mx = fmax(mx, d);
+    else cnt += 1.0;
+}
+
+__device__ inline void block_max_sum(double mx, double cnt, double* __restrict__ out)
+{
+    for (int o = 32; o > 0; o >>= 1) {
+        mx = fmax(mx, __shfl_down(mx, o, 64));
+        cnt += __shfl_down(cnt, o, 64);
+    }
+    __shared__ double smx[WR_RED_THREADS / 64], scn[WR_RED_THREADS / 64];
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { smx[w] = mx; scn[w] = cnt; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < WR_RED_THREADS / 64; i++) { mx = fmax(mx, smx[i]); cnt += scn[i]; }
+        out[0] = mx;
+        out[1] = cnt;
+    }
+}
+
+// PAIRS: both arrays are aligned for the two-sample loads of k_minmax (16 bytes fp64, 8 bytes fp32)
+template <typename T, bool PAIRS>
+__global__ __launch_bounds__(WR_RED_THREADS) void k_linf_cnt(const T* __restrict__ a, const T* __restrict__ b, size_t n, double* __restrict__ partial)
+{
+    double mx = 0.0, cnt = 0.0;
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (size_t)gridDim.x * blockDim.x;
+    if (PAIRS) {
+        const size_t n2 = n >> 1;
+        const typename Pair<T>::type* a2 = reinterpret_cast<const typename Pair<T>::type*>(a);
+        const typename Pair<T>::type* b2 = reinterpret_cast<const typename Pair<T>::type*>(b);
+        for (size_t i = tid; i < n2; i += nthr) {
+            const typename Pair<T>::type va = a2[i], vb = b2[i];
+            linf_cnt_acc((double)va.x, (double)vb.x, mx, cnt);
+            linf_cnt_acc((double)va.y, (double)vb.y, mx, cnt);
+        }
+        if ((n & 1) && tid == 0) linf_cnt_acc((double)a[n - 1], (double)b[n - 1], mx, cnt);
+    } else {
+        for (size_t i = tid; i < n; i += nthr) linf_cnt_acc((double)a[i], (double)b[i], mx, cnt);
+    }
+    block_max_sum(mx, cnt, partial + 2 * blockIdx.x);
+}
+
+__global__ __launch_bounds__(WR_RED_THREADS) void k_linf_cnt_final(const double* __restrict__ partial, int np, double* __restrict__ result)
+{
+    double mx = 0.0, cnt = 0.0;
+    for (int i = threadIdx.x; i < np; i += blockDim.x) {
+        mx = fmax(mx, partial[2 * i]);
+        cnt += partial[2 * i + 1];
+    }
+    block_max_sum(mx, cnt, result);  // single block: lands in result[0], result[1]
+}
+
+template <typename T>
+static void linf_count_t(const T* a, const T* b, size_t n, double* partial, double* result, hipStream_t st)
+{
+    const bool pairs = (((uintptr_t)a | (uintptr_t)b) & (2 * sizeof(T) - 1)) == 0;
+    const int g = red_grid(n, 2);
+    if (pairs) hipLaunchKernelGGL((k_linf_cnt<T, true>), dim3(g), dim3(WR_RED_THREADS), 0, st, a, b, n, partial);
+    else hipLaunchKernelGGL((k_linf_cnt<T, false>), dim3(g), dim3(WR_RED_THREADS), 0, st, a, b, n, partial);
+    hipLaunchKernelGGL(k_linf_cnt_final, dim3(1), dim3(WR_RED_THREADS), 0, st, partial, g, result);
+}
+void linf_count(const double* a, const double* b, size_t n, double* partial, double* result, hipStream_t st) { linf_count_t(a, b, n, partial, result, st); }
+void linf_count(const float* a, const float* b, size_t n, double* partial, double* result, hipStream_t st) { linf_count_t(a, b, n, partial, result, st); }
+
+// =====================================================================================
+// The trial of an encode to an error bound: what would the decoder's coefficient sum be, had the planes been cut with these
+// steps?  acc[j] is what k_dequant / k_dequant_lds give from the planes k_quant_blk would have written -- the full planes in
+// `prev`, then the last one -- formed straight from the coefficient: per plane q = quant_byte(aopt * r + bopt),
+// t = (double)q * deps + minval, acc = acc + t, r = r - t, the operations of those kernels on the same operands (the term t is
+// the one value both of them form), so every bit agrees.  No plane, residual or histogram is written: 8 bytes read and 8
+// written per sample, no LDS.  A wave takes RQW elements at a time, 8 x 16-byte loads per lane in flight, as k_quant_blk; the
+// waves stride over the whole tiles, the elements behind the last whole tile go one by one.  ntiles = 0 (unaligned pointers):
+// everything goes one by one.
+// =====================================================================================
+constexpr int RQW = 1024;
+__device__ inline double requant_one(double v, const QuantPrev& prev, double aopt, double bopt, double deps, double minval)
+{
+    double a = 0.0;
+#pragma unroll
+    for (int p = 0; p < kQuantPrevMax; p++) {
+        if (p < prev.n) {
+            const unsigned char q = quant_byte(prev.aopt[p] * v + prev.bopt[p]);
+            const double t = (double)q * prev.deps[p] + prev.minval[p];
+            a = a + t;
+            v = v - t;
+        }
+    }
+    const unsigned char q = quant_byte(aopt * v + bopt);
+    return a + ((double)q * deps + minval);
+}
+
+__global__ __launch_bounds__(WR_RED_THREADS) void k_requant_accum(const double* __restrict__ x, size_t n, size_t ntiles, QuantPrev prev, double aopt,
+                                                                  double bopt, double deps, double minval, double* __restrict__ acc)
+{
+    constexpr int NW = WR_RED_THREADS / 64;
+    const int lane = threadIdx.x & 63;
+    const size_t wave = (size_t)blockIdx.x * NW + (threadIdx.x >> 6), nwaves = (size_t)gridDim.x * NW;
+    for (size_t tile = wave; tile < ntiles; tile += nwaves) {
+        const double2* const x2 = reinterpret_cast<const double2*>(x + tile * RQW);
+        double2* const a2 = reinterpret_cast<double2*>(acc + tile * RQW);
+        double2 v[RQW / 128], a[RQW / 128];
+#pragma unroll
+        for (int j = 0; j < RQW / 128; j++) { v[j] = x2[j * 64 + lane]; a[j] = make_double2(0.0, 0.0); }
+#pragma unroll
+        for (int p = 0; p < kQuantPrevMax; p++) {
+            if (p < prev.n) {
+                const double pa = prev.aopt[p], pb = prev.bopt[p], pd = prev.deps[p], pm = prev.minval[p];
+#pragma unroll
+                for (int j = 0; j < RQW / 128; j++) {
+                    const unsigned char qa = quant_byte(pa * v[j].x + pb);
+                    const unsigned char qb = quant_byte(pa * v[j].y + pb);
+                    const double ta = (double)qa * pd + pm, tb = (double)qb * pd + pm;
+                    a[j].x = a[j].x + ta; a[j].y = a[j].y + tb;
+                    v[j].x = v[j].x - ta; v[j].y = v[j].y - tb;
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < RQW / 128; j++) {
+            const unsigned char qa = quant_byte(aopt * v[j].x + bopt);
+            const unsigned char qb = quant_byte(aopt * v[j].y + bopt);
+            a[j].x = a[j].x + ((double)qa * deps + minval);
+            a[j].y = a[j].y + ((double)qb * deps + minval);
+            a2[j * 64 + lane] = a[j];
+        }
+    }
+    for (size_t i = ntiles * RQW + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        acc[i] = requant_one(x[i], prev, aopt, bopt, deps, minval);
+}
+
+void requant_accum(const double* x, size_t n, const QuantPrev& prev, double aopt, double bopt, double deps, double minval, double* acc, hipStream_t st)
+{
+    if (!n) return;
+    const bool aligned = (((uintptr_t)x | (uintptr_t)acc) & 15) == 0;
+    const size_t ntiles = aligned ? n / RQW : 0;
+    constexpr size_t NW = WR_RED_THREADS / 64;
+    // one round of resident workgroups over the whole tiles; without any, the grid of an element-wise pass
+    size_t g = ntiles ? (ntiles + NW - 1) / NW : (size_t)red_grid(n, 1);
+    if (g > (size_t)WR_RED_BLOCKS) g = WR_RED_BLOCKS;
+    hipLaunchKernelGGL(k_requant_accum, dim3((unsigned)g), dim3(WR_RED_THREADS), 0, st, x, n, ntiles, prev, aopt, bopt, deps, minval, acc);
+}
+
 __global__ void k_fill(double* x, size_t n, double v)
 {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) x[i] = v;
