@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
-"""One segmented decode call on a small field, to be run under a kernel trace: the device work of a driver, call by call.
+"""One segmented call on a small field, to be run under a kernel trace: the device work of a driver, call by call.
 
-    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 tools/seg_driver_trace.py multi|batch
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 tools/seg_driver_trace.py MODE
 
-The field is tests/test_gpu_seg_drivers.py's: 64^3, tolerance 1e-6, coded as WRS1 (seg 1008) and as WRS2 (brick 16).  `multi`:
-one wr_decode_host_seg_roi_multi call of the region set W on the WRS2 stream; `batch`: one wr_decode_host_seg_batch call of the
-two streams.  The two encodes in front of the call are in the trace as well; they are the same in every run."""
+The field is tests/test_gpu_seg_drivers.py's: 64^3, tolerance 1e-6, seg 1008.  The decode modes code it as WRS1 and as WRS2
+(brick 16) first; those two encodes are in the trace as well, the same in every run.
+    multi          one wr_decode_host_seg_roi_multi call of the region set W on the WRS2 stream
+    batch          one wr_decode_host_seg_batch call of the two streams
+    encode         one WRS2 (brick 16) and one WRS3 (8 strands) encode, nothing else
+    encode_batch   one wr_encode_host_seg_batch call of two fields as WRS2, nothing else
+    transcode      the reference's stream of the field (one wr_encode_host), then reference -> WRS3 and WRS2 -> reference"""
 import os
 import sys
 
@@ -18,6 +22,13 @@ import numpy as np
 from roi_multi_cases import regions_at
 from waverange_amd import api, synth
 
+TOL, SEG = 1e-6, 1008
+
+
+def own(enc):
+    enc["data"] = enc["data"].copy()
+    return enc
+
 
 def main():
     what = sys.argv[1] if len(sys.argv) > 1 else "multi"
@@ -25,11 +36,23 @@ def main():
     shape = (64, 64, 64)
     f = synth.field(64, 64, 64, seed=41)
     with api.Context(0) as ctx:
-        encs = []
-        for kw in (dict(), dict(brick=16)):
-            enc, _ = ctx.encode_host_seg(f, 1e-6, 1, 1008, **kw)
-            enc["data"] = enc["data"].copy()
-            encs.append(enc)
+        if what == "encode":
+            a, _ = ctx.encode_host_seg(f, TOL, 1, SEG, brick=16)
+            b, _ = ctx.encode_host_seg(f, TOL, 1, SEG, strands=8)
+            print("encode ok", a["ntot_enc"], b["ntot_enc"])
+            return
+        if what == "encode_batch":
+            encs, _ = ctx.encode_host_seg_batch([f, synth.field(64, 64, 64, seed=7)], TOL, 1, SEG, brick=16)
+            print("encode_batch ok", [e["ntot_enc"] for e in encs])
+            return
+        if what == "transcode":
+            ref = own(ctx.encode_host(f, TOL)[0])
+            wrs3, _ = ctx.transcode(ref, ref["data"], "wrs3:seg=1008:strands=8", shape=shape)
+            wrs2, info2 = api.transcode_host_ref(shape, ref, ref["data"], "wrs2:seg=1008:brick=16")  # (on the host: no kernel)
+            back, _ = ctx.transcode(info2, wrs2, "ref", shape=shape)
+            print("transcode ok", wrs3.size, back.tobytes() == ref["data"].tobytes())
+            return
+        encs = [own(ctx.encode_host_seg(f, TOL, 1, SEG, **kw)[0]) for kw in (dict(), dict(brick=16))]
         if what == "multi":
             out = ctx.decode_host_seg_rois(shape, 0, regions_at("W", 0), encs[1])
             print("multi ok", [o.shape for o in out])

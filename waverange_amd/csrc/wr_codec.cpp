@@ -6,6 +6,7 @@
 // Compiled with hipcc, strict IEEE (-ffp-contract=off): the scalar arithmetic on deps/aopt/bopt/tolabs below must round
 // exactly as wrappers.cpp:292-340 does.
 #include <algorithm>
+#include <cassert>
 
 #include "wr_blocked.h"
 #include "wr_budget.h"
@@ -547,6 +548,87 @@ extern "C" int wr_dev_decode_planes_roi(wr_ctx* c, double* d_out, int nx, int ny
 
 namespace {
 
+// ---- stages that every encode driver takes, whatever codes the planes ---------------------------------------------------
+// Stage "up": a host field onto the leased slot.  An fp32 field: the fused forward transform reads it where it lands (the
+// slot's field buffer, which is work space of n doubles from then on); elsewhere it lands in the scratch buffer and the caller
+// widens it into the field buffer in front of the fp64 path (the general transform's scratch is free until then).
+struct FieldUpload {
+    double* d_fld = nullptr;       // the field as doubles, or -- d_f32 set -- n doubles of work space
+    const float* d_f32 = nullptr;  // the fp32 field as the fused forward transform reads it
+    float* widen_from = nullptr;   // the fp32 field that wrk::widen_f32 takes to d_fld
+    float ms = 0;                  // the copy, for h2d_ms
+};
+
+int upload_field(wr_ctx* c, Slot* slot, const FieldRef& fld, int nx, int ny, int nz, int wtflag, FieldUpload* u)
+{
+    const size_t n = (size_t)nx * ny * nz;
+    u->d_fld = fld.dev ? fld.dev : slot->field;
+    if (fld.dev) return WR_OK;
+    if (fld.host) {
+        if (int rc = xfer_field(c, &c->x_field, u->d_fld, fld.host, n * sizeof(double), kUp)) return rc;
+    } else {
+        float* const stage = (wtflag && use_fused(nx, ny, nz, kWavLvl)) ? reinterpret_cast<float*>(slot->field) : reinterpret_cast<float*>(slot->scratch);
+        if (int rc = xfer_field(c, &c->x_field, stage, fld.host_f32, n * sizeof(float), kUp)) return rc;
+        if (stage == reinterpret_cast<float*>(slot->field)) u->d_f32 = stage;
+        else u->widen_from = stage;
+    }
+    u->ms = (float)c->x_field.ms;
+    return WR_OK;
+}
+
+// The end of a single-field encode's kernel stage (cu_mu held): rc is encode_planes_core's.  With the residual kept, a
+// device-resident field receives it here, where the reference leaves it; a host field's follows in the caller's "down" stage.
+int encode_stage_end(wr_ctx* c, int rc, const FieldRef& fld, const double* resid, size_t n, const wr_enc_info* info)
+{
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the encoder's kernel stage failed on the device" + launch_describe(c));
+    if (rc == WR_OK && c->keep_residual && info->nlay && !fld.host && resid != fld.dev) {
+        if (hipMemcpyAsync(fld.dev, resid, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+            rc = fail(WR_ERR_HIP, "residual copy failed");
+    }
+    c->pool->last_stage_end.store(now());
+    return rc;
+}
+
+// The tail of an encode into the reference's format, once every plane's coder has returned: jobs[l] coded plane l to where it
+// was placed -- direct[l]: at out + est_off[l], the sum of the histogram bounds est_len of the planes before it; otherwise into
+// c->enc_buf[l].  Checks every plane (download_failed(l): its symbols did not reach the coder), gives lens[l] and *total,
+// closes the gaps in `out` and hands the pages of the context's buffers back.  too_large: the text of total > cap.
+template <class Failed>
+int ref_stream_tail(wr_ctx* c, const wrrc::PlaneJob* jobs, unsigned nlay, Failed download_failed, const size_t* est_off, const size_t* est_len, const bool* direct,
+                    unsigned char* out, size_t cap, const char* too_large, size_t* lens, size_t* total)
+{
+    for (unsigned l = 0; l < nlay; l++) {
+        if (download_failed(l)) return fail(WR_ERR_HIP, "download of plane " + std::to_string(l) + " failed");
+        if (jobs[l].result == (size_t)-1)  // (a refused window sets ps[l].err as well; what is left: histograms that are not the plane's)
+            return fail(WR_ERR_HIP, "internal: the coder gave plane " + std::to_string(l) + " up (its block histograms are not its symbols')");
+    }
+    // concatenate the plane streams (wrappers.cpp:412-427)
+    size_t offs[WR_NLAYMAX] = {0};
+    *total = 0;
+    for (unsigned l = 0; l < nlay; l++) {
+        offs[l] = *total;
+        *total += jobs[l].result;
+        lens[l] = jobs[l].result;
+    }
+    for (unsigned l = 0; l < nlay; l++)  // (cannot happen: the bound is rigorous; if it did, a neighbour's bytes are gone)
+        if (jobs[l].result > est_len[l]) return fail(WR_ERR_OVERFLOW, "internal: plane " + std::to_string(l) + " outgrew the bound computed from its histograms");
+    if (*total > cap) return fail(WR_ERR_OVERFLOW, too_large);
+    // close the gaps: plane l moves down by what the planes before it stayed below their bounds.  In plane order, one after
+    // the other: plane l's new place may still hold the end of plane l-1's old one.
+    for (unsigned l = 0; l < nlay; l++) {
+        if (!direct[l]) memcpy(out + offs[l], c->enc_buf[l], lens[l]);
+        else if (est_off[l] != offs[l]) memmove(out + offs[l], out + est_off[l], lens[l]);
+    }
+    // (a plane that went through c->enc_buf: hand its pages back, a noise plane's gigabyte would otherwise stay resident in
+    // every context that once coded one)
+    for (unsigned l = 0; l < nlay; l++) {
+        if (direct[l]) continue;
+        const uintptr_t a = ((uintptr_t)c->enc_buf[l] + 4095) & ~(uintptr_t)4095, e = ((uintptr_t)c->enc_buf[l] + lens[l]) & ~(uintptr_t)4095;
+        if (e > a && e - a >= ((size_t)64 << 20)) (void)madvise(reinterpret_cast<void*>(a), e - a, MADV_DONTNEED);
+    }
+    return WR_OK;
+}
+
 int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, const Cutoff& cut, wr_enc_info* info,
                 unsigned char* data_enc, size_t cap, wr_timings* tm)
 {
@@ -568,7 +650,6 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
     DevPool* const pool = c->pool;
 
     int copy_failed[WR_NLAYMAX] = {0};
-    std::string logs[WR_NLAYMAX];
     Sem sem(encoder_threads());
     const int dev = c->device;
     c->pend_valid = false;  // planes a wr_decode_begin parked in this context do not survive an encode on it
@@ -645,27 +726,12 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
         SlotLease slot;
         if ((rc = slot.acquire(c, need)) != WR_OK) return rc;
         t_phase = now();
-        double* d_fld = fld.dev;
-        if (fld.host) {
-            // ---- stage "up": the field goes host -> device; the kernel stage is only claimed once it has
-            // arrived, so other calls compute meanwhile
-            d_fld = slot->field;
-            if ((rc = xfer_field(c, &c->x_field, d_fld, fld.host, n * sizeof(double), kUp)) != WR_OK) return rc;
-            local.h2d_ms = (float)c->x_field.ms;
-        }
-        // An fp32 field: the fused forward transform reads it where it lands (the slot's field buffer, which is work space of n
-        // doubles from then on).  Elsewhere it lands in the scratch buffer and is widened into the field buffer in front of
-        // the fp64 path (the general transform's scratch is free until then).
-        const float* d_f32 = nullptr;
-        float* widen_from = nullptr;
-        if (fld.host_f32) {
-            d_fld = slot->field;
-            float* const stage = (wtflag && use_fused(nx, ny, nz, kWavLvl)) ? reinterpret_cast<float*>(slot->field) : reinterpret_cast<float*>(slot->scratch);
-            if ((rc = xfer_field(c, &c->x_field, stage, fld.host_f32, n * sizeof(float), kUp)) != WR_OK) return rc;
-            local.h2d_ms = (float)c->x_field.ms;
-            if (stage == reinterpret_cast<float*>(slot->field)) d_f32 = stage;
-            else widen_from = stage;
-        }
+        // ---- stage "up": the field goes host -> device; the kernel stage is only claimed once it has arrived, so other calls
+        // compute meanwhile
+        FieldUpload up;
+        if ((rc = upload_field(c, slot.get(), fld, nx, ny, nz, wtflag, &up)) != WR_OK) return rc;
+        local.h2d_ms = up.ms;
+        double* const d_fld = up.d_fld;
         double* resid = d_fld;
         auto hist_buf = [&](unsigned l) { return slot->hist + l * hist_per_plane; };
         auto after_quant = [&](unsigned l, bool hist_done) -> int {
@@ -723,16 +789,10 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
             // ---- stage "kernels"
             cu.lock();
             clock_warmup(c, n);
-            if (widen_from) wrk::widen_f32(widen_from, d_fld, n, c->stream);
+            if (up.widen_from) wrk::widen_f32(up.widen_from, d_fld, n, c->stream);
             rc = encode_planes_core(c, slot.get(), d_fld, nx, ny, nz, wtflag, cut, plane_buf, hist_buf, info, &local, after_quant, plane_ready, &resid,
-                                    d_f32);
-            if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the encoder's kernel stage failed on the device" + launch_describe(c));
-            if (rc == WR_OK && c->keep_residual && info->nlay && !fld.host && resid != fld.dev) {  // leave the residual where the reference leaves it
-                if (hipMemcpyAsync(fld.dev, resid, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
-                    hipStreamSynchronize(c->stream) != hipSuccess)
-                    rc = fail(WR_ERR_HIP, "residual copy failed");
-            }
-            pool->last_stage_end.store(now());
+                                    up.d_f32);
+            rc = encode_stage_end(c, rc, fld, resid, n, info);
             cu.unlock();
         }
         // ---- stage "down": the histograms were sent off as the planes completed; the residual follows them
@@ -767,41 +827,17 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
     }
     workers.join();
     if (rc) return rc;
-    for (unsigned l = 0; l < info->nlay; l++) {
-        if (copy_failed[l] || c->ps[l].err) return fail(WR_ERR_HIP, "download of plane " + std::to_string(l) + " failed");
-        if (jobs[l].result == (size_t)-1)  // (a refused window sets ps[l].err as well; what is left: histograms that are not the plane's)
-            return fail(WR_ERR_HIP, "internal: the coder gave plane " + std::to_string(l) + " up (its block histograms are not its symbols')");
-        local.d2h_ms += (float)(c->x_plane[l].ms + c->ps[l].copy_ms);
-        if (verbose()) logs[l] = plane_log(c, (int)l, n, info, true, jobs[l].result);  // wrappers.cpp:401-409, 430
-    }
     const double t_coded = now();
-    // concatenate the plane streams (wrappers.cpp:412-427)
-    size_t total = 0, offs[WR_NLAYMAX] = {0};
+    size_t total = 0;
+    if (int r = ref_stream_tail(c, jobs, info->nlay, [&](unsigned l) { return copy_failed[l] || c->ps[l].err; }, est_off, est_len, direct, data_enc, cap,
+                                wrtc::kTooLarge, info->len_enc_vec, &total))
+        return r;
     for (unsigned l = 0; l < info->nlay; l++) {
-        offs[l] = total;
-        total += jobs[l].result;
-        info->len_enc_vec[l] = jobs[l].result;
+        local.d2h_ms += (float)(c->x_plane[l].ms + c->ps[l].copy_ms);
         local.plane_coder_s[l] = jobs[l].seconds;
-        if (jobs[l].seconds > local.rangecoder) local.rangecoder = jobs[l].seconds;
+        if (jobs[l].seconds > local.rangecoder) local.rangecoder = jobs[l].seconds;  // (the planes are coded at the same time)
+        if (verbose()) fputs(plane_log(c, (int)l, n, info, true, jobs[l].result).c_str(), stdout);  // wrappers.cpp:401-409, 430
     }
-    for (unsigned l = 0; l < info->nlay; l++)  // (cannot happen: the bound is rigorous; if it did, a neighbour's bytes are gone)
-        if (jobs[l].result > est_len[l]) return fail(WR_ERR_OVERFLOW, "internal: plane " + std::to_string(l) + " outgrew the bound computed from its histograms");
-    if (total > cap) return fail(WR_ERR_OVERFLOW, "Error: encoded array is too large. Use larger SAFETY_BUFFER_FACTOR");
-    // close the gaps: plane l moves down by what the planes before it stayed below their bounds.  In plane order, one after
-    // the other: plane l's new place may still hold the end of plane l-1's old one.
-    for (unsigned l = 0; l < info->nlay; l++) {
-        if (!direct[l]) memcpy(data_enc + offs[l], c->enc_buf[l], jobs[l].result);
-        else if (est_off[l] != offs[l]) memmove(data_enc + offs[l], data_enc + est_off[l], jobs[l].result);
-    }
-    // (a plane that went through c->enc_buf: hand its pages back, a noise plane's gigabyte would otherwise stay resident in
-    // every context that once coded one)
-    for (unsigned l = 0; l < info->nlay; l++) {
-        if (direct[l]) continue;
-        const uintptr_t a = ((uintptr_t)c->enc_buf[l] + 4095) & ~(uintptr_t)4095, e = ((uintptr_t)c->enc_buf[l] + jobs[l].result) & ~(uintptr_t)4095;
-        if (e > a && e - a >= ((size_t)64 << 20)) (void)madvise(reinterpret_cast<void*>(a), e - a, MADV_DONTNEED);
-    }
-    if (verbose())
-        for (unsigned l = 0; l < info->nlay; l++) fputs(logs[l].c_str(), stdout);
     info->ntot_enc = total;
     local.total = now() - t0;
     local.wait = t_phase - t0;
@@ -1212,13 +1248,31 @@ namespace {
 
 // device memory of a segmented call, from the plane pool (its accounting, cap and reserve); goes back when the call ends,
 // behind everything the context's stream still has queued
+// the event pairs around the coder kernels of a call, one per plane (or plane index of a batch); they go with the call's buffers
+struct PlaneEvents {
+    hipEvent_t e[2 * WR_NLAYMAX] = {nullptr};
+    PlaneEvents() = default;
+    PlaneEvents(const PlaneEvents&) = delete;
+    PlaneEvents& operator=(const PlaneEvents&) = delete;
+    ~PlaneEvents() { for (hipEvent_t v : e) if (v) (void)hipEventDestroy(v); }
+    hipEvent_t operator[](int k) const { return e[k]; }
+    int create(int l) { for (int k = 2 * l; k < 2 * l + 2; k++) if (!e[k]) HIPCHK(hipEventCreate(&e[k])); return WR_OK; }
+    double seconds(int l) const
+    {
+        float ms = 0;
+        if (!e[2 * l] || hipEventElapsedTime(&ms, e[2 * l], e[2 * l + 1]) != hipSuccess) { (void)hipGetLastError(); return 0; }
+        return ms * 1e-3;
+    }
+};
+
 struct SegBufs {
     wr_ctx* c;
     DevPlanes::Buf stage, blob[WR_NLAYMAX], work[WR_NLAYMAX];
     DevPlanes::Buf perm, bricks;  // a blocked stream: one plane in stream order (every plane in turn), the brick list of a partial decode
     DevPlanes::Buf trial[3];      // an encode to an error bound / wr_seg_error_host: two work arrays of a trial, the copy of the field
-    hipEvent_t ev[2 * WR_NLAYMAX] = {nullptr};
+    PlaneEvents ev;
     explicit SegBufs(wr_ctx* ctx) : c(ctx) {}
+    int coded_plane(int l, size_t cap) { blob[l] = plane_scratch(c, cap); return blob[l].p ? ev.create(l) : WR_ERR_HIP; }  // an encoder's blob and event pair
     SegBufs(const SegBufs&) = delete;
     SegBufs& operator=(const SegBufs&) = delete;
     ~SegBufs()
@@ -1232,27 +1286,113 @@ struct SegBufs {
             if (blob[l].p) c->pool->planes.give(blob[l]);
             if (work[l].p) c->pool->planes.give(work[l]);
         }
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
-    int events(int l)
-    {
-        for (int k = 2 * l; k < 2 * l + 2; k++)
-            if (!ev[k]) HIPCHK(hipEventCreate(&ev[k]));
-        return WR_OK;
-    }
-    double seconds(int l) const
-    {
-        float ms = 0;
-        if (!ev[2 * l] || hipEventElapsedTime(&ms, ev[2 * l], ev[2 * l + 1]) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        return ms * 1e-3;
     }
 };
 
+// a coder's result slot: the blob's length, and whether a stream outgrew its bound
 unsigned long long* seg_result_host(wr_ctx* c, int l) { return reinterpret_cast<unsigned long long*>(c->h_result + 8) + 2 * l; }
 unsigned long long* seg_result_dev(wr_ctx* c, int l) { return reinterpret_cast<unsigned long long*>(c->h_result_dev + 8) + 2 * l; }
 
-// strands == 0: WRS1 (brick == 0) or WRS2 with that brick edge (wr_blocked.h); otherwise WRS3 with that many strands, in the
-// natural order (brick == 0) or the blocked one
+// ---- the stages of a segmented encode.  The drivers -- the single field, the batch, the segmented target of a transcode, the
+// stage calls -- compose these and upload_field / encode_stage_end above; the decode stages follow further down.
+// The parameters of a format as every entry point takes them: seg == 0 is WR_SEG_DEFAULT (nullptr: the call has no segment
+// length).  strands == 0: WRS1 (brick == 0) or WRS2 with that brick edge (wr_blocked.h); otherwise WRS3 with that many
+// strands, in the natural order (brick == 0) or the blocked one.  (Where 0 names a default, the entry point has put it in.)
+int seg_format_params(unsigned* seg, unsigned brick, unsigned strands)
+{
+    if (seg && !*seg) *seg = WR_SEG_DEFAULT;
+    if (seg && !wrseg::seg_ok(*seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
+    if (brick && !wrblk::brick_ok(brick)) return fail(WR_ERR_ARG, "brick edge must be one of 8, 16, 32, 64");
+    if (strands && !wrseg::strands_ok(strands, *seg)) return fail(WR_ERR_ARG, "strands must be one of 1, 2, 4, 8, 16, 32 with 16 * strands <= seg");
+    return WR_OK;
+}
+
+// bytes that hold any blob of a plane of n symbols, rounded up to 16: wr_transcode.h's bound, which is the public one
+size_t seg_blob_cap(size_t n, unsigned seg, unsigned brick, unsigned strands)
+{
+    wrtc::StreamFormat f;
+    f.format = strands ? WR_FORMAT_WRS3 : brick ? WR_FORMAT_WRS2 : WR_FORMAT_WRS1; f.seg = seg; f.brick = brick; f.strands = strands;
+    const size_t bound = wrtc::plane_bound(n, f);
+    assert(bound == (strands ? wr_seg_bound_strands(n, seg, strands) : brick ? wr_seg_bound_blocked(n, seg) : wr_seg_bound(n, seg)));
+    return (bound + 15) & ~(size_t)15;
+}
+
+const char* const kOutgrew = "a segment outgrew the segment bound";
+
+// What the planes of a call are coded into; the two buffers serve every plane in turn (the context's stream orders the coders)
+struct SegTarget {
+    unsigned seg = 0, brick = 0, strands = 0;
+    wrblk::Order od{};         // brick != 0: the blocked order of the planes
+    size_t blob_cap = 0;
+    uint8_t* stage = nullptr;  // the uncompacted streams of one plane
+    uint8_t* perm = nullptr;   // brick != 0: one plane in stream order
+};
+
+// ... with its buffers from the plane pool, kept in bufs (a stream-order plane that bufs has already is taken as it is)
+int seg_target(wr_ctx* c, SegBufs* bufs, size_t n, unsigned seg, unsigned brick, unsigned strands, const wrblk::Order& od, SegTarget* t)
+{
+    t->seg = seg; t->brick = brick; t->strands = strands; t->od = od;
+    t->blob_cap = seg_blob_cap(n, seg, brick, strands);
+    bufs->stage = plane_scratch(c, strands ? wrk::strand_stage_bytes(n, seg, strands) : wrk::seg_stage_bytes(n, seg));
+    if (bufs->stage.p && brick && !bufs->perm.p) bufs->perm = plane_scratch(c, n);
+    if (!bufs->stage.p || (brick && !bufs->perm.p)) return WR_ERR_HIP;
+    t->stage = bufs->stage.p; t->perm = bufs->perm.p;
+    return WR_OK;
+}
+
+// the coder kernels of one plane, its symbols in stream order: the blob into [blob, blob + cap), its length into result slot l
+void seg_encode_launch(wr_ctx* c, const SegTarget& t, const wrk::PlaneRef& sym, size_t n, uint8_t* blob, size_t cap, int l)
+{
+    if (t.strands) wrk::strand_encode(sym, n, t.seg, t.strands, t.brick, t.stage, blob, cap, seg_result_dev(c, l), c->stream);
+    else wrk::seg_encode(sym, n, t.seg, t.stage, blob, cap, seg_result_dev(c, l), c->stream, t.brick);
+}
+
+// Plane l of a pipeline call (cu_mu held) into its blob of t.blob_cap bytes, behind whatever the context's stream has queued
+int seg_encode_plane(wr_ctx* c, const SegTarget& t, const wrk::PlaneRef& plane, size_t n, int l, uint8_t* blob, const PlaneEvents& ev)
+{
+    launch_note(c, "seg_encode", l, blob, n, t.stage, plane);
+    HIPCHK(hipEventRecord(ev[2 * l], c->stream));
+    wrk::PlaneRef sym = plane;
+    if (t.brick) {
+        if (!wrk::plane_reorder(sym, t.perm, t.od, false, nullptr, 0, c->stream)) return fail(WR_ERR_ARG, "too many bricks");
+        sym = wrk::plane_ref(t.perm);
+    }
+    seg_encode_launch(c, t, sym, n, blob, t.blob_cap, l);
+    HIPCHK(hipEventRecord(ev[2 * l + 1], c->stream));
+    if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented coder launch failed" + launch_describe(c));
+    return WR_OK;
+}
+
+// Stage "down", first half: the result slots of nlay planes (res_of(l)), once the stream has drained.  Every blob must have
+// stayed inside blob_cap; lens[l] and *total.  who: put in front of the message ("field 3: " in a batch)
+template <class ResOf>
+int seg_coded_lengths(int nlay, size_t blob_cap, ResOf res_of, size_t* lens, size_t* total, const std::string& who = std::string())
+{
+    *total = 0;
+    for (int l = 0; l < nlay; l++) {
+        const unsigned long long* const res = res_of(l);
+        if (res[1] || res[0] > blob_cap) return fail(WR_ERR_HIP, who + "internal: plane " + std::to_string(l) + ": " + kOutgrew);
+        lens[l] = res[0];
+        *total += res[0];
+    }
+    return WR_OK;
+}
+
+// ... second half: a copy per blob, behind one another at `out`; the coder seconds add to tm's (a transcode's source half's)
+int seg_download_blobs(wr_ctx* c, const SegBufs& bufs, int nlay, const size_t* lens, unsigned char* out, wr_timings* tm)
+{
+    size_t at = 0;
+    for (int l = 0; l < nlay; l++) {
+        if (int rc = xfer_field(c, &c->x_field, out + at, bufs.blob[l].p, lens[l], kDown)) return rc;
+        tm->d2h_ms += (float)c->x_field.ms;
+        at += lens[l];
+        const double sec = bufs.ev.seconds(l);
+        tm->plane_coder_s[l] += sec;
+        tm->rangecoder += sec;
+    }
+    return WR_OK;
+}
+
 // ---- the search of an encode to a byte budget (include/waverange_amd.h; the grid and the bound: wr_budget.h) ----------------
 // Only the last plane depends on the tolerance: plane l is cut with the full step (hi - lo) / 255 of its residual until that
 // falls below tolabs, and is then the last, cut with tolabs.  So the grid falls into one interval per plane count: with
@@ -1612,10 +1752,7 @@ struct BoundedSearch {
 int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, const Cutoff& cut, unsigned seg, unsigned brick, unsigned strands,
                     wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm, BudgetSearch* bud = nullptr, BoundedSearch* bnd = nullptr)
 {
-    if (!seg) seg = WR_SEG_DEFAULT;
-    if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
-    if (brick && !wrblk::brick_ok(brick)) return fail(WR_ERR_ARG, "brick edge must be one of 8, 16, 32, 64");
-    if (strands && !wrseg::strands_ok(strands, seg)) return fail(WR_ERR_ARG, "strands must be one of 1, 2, 4, 8, 16, 32 with 16 * strands <= seg");
+    if (int rc = seg_format_params(&seg, brick, strands)) return rc;
     if (int rc = ctx_bind(c)) return rc;
     if (int rc = check_dims(nx, ny, nz, fld.dev)) return rc;
     if (fld.none()) return fail(WR_ERR_ARG, "null field pointer");
@@ -1638,9 +1775,6 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
     c->pend_valid = false;  // planes a wr_decode_begin parked in this context do not survive an encode on it
     PlaneHold planes(c);
     SegBufs bufs(c);  // (after the planes: it goes first when the call unwinds, and waits for the stream)
-    const size_t blob_cap = ((strands ? wr_seg_bound_strands(n, seg, strands) : brick ? wr_seg_bound_blocked(n, seg) : wr_seg_bound(n, seg)) + 15) & ~(size_t)15;
-    wrblk::Order od{};
-    if (brick) od = wrblk::order_of(nx, ny, nz, wtflag ? kWavLvl : 0, brick);
 
     SlotNeed need;
     transform_need(nx, ny, nz, wtflag ? kWavLvl : 0, &need);
@@ -1648,37 +1782,19 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
     SlotLease slot;
     if (int rc = slot.acquire(c, need)) return rc;
     const double t_phase = now();
-    double* d_fld = fld.dev;
-    if (fld.host) {
-        d_fld = slot->field;
-        if (int rc = xfer_field(c, &c->x_field, d_fld, fld.host, n * sizeof(double), kUp)) return rc;
-        local.h2d_ms = (float)c->x_field.ms;
-    }
-    const float* d_f32 = nullptr;  // (as encode_impl: the fused forward transform reads an fp32 field where it lands)
-    float* widen_from = nullptr;
-    if (fld.host_f32) {
-        d_fld = slot->field;
-        float* const stage = (wtflag && use_fused(nx, ny, nz, kWavLvl)) ? reinterpret_cast<float*>(slot->field) : reinterpret_cast<float*>(slot->scratch);
-        if (int rc = xfer_field(c, &c->x_field, stage, fld.host_f32, n * sizeof(float), kUp)) return rc;
-        local.h2d_ms = (float)c->x_field.ms;
-        if (stage == reinterpret_cast<float*>(slot->field)) d_f32 = stage;
-        else widen_from = stage;
-    }
-    // one staging buffer for the uncompacted streams, used by every plane in turn (the planes' coder kernels are ordered by
-    // the context's stream); a blob buffer per plane
-    bufs.stage = plane_scratch(c, strands ? wrk::strand_stage_bytes(n, seg, strands) : wrk::seg_stage_bytes(n, seg));
-    if (!bufs.stage.p) return WR_ERR_HIP;
-    if (brick) {  // the plane in stream order: like the staging buffer one for all planes
-        bufs.perm = plane_scratch(c, n);
-        if (!bufs.perm.p) return WR_ERR_HIP;
-    }
+    FieldUpload up;
+    if (int rc = upload_field(c, slot.get(), fld, nx, ny, nz, wtflag, &up)) return rc;
+    local.h2d_ms = up.ms;
+    double* const d_fld = up.d_fld;
+    SegTarget t;  // (a blob buffer per plane, as the planes come)
+    if (int rc = seg_target(c, &bufs, n, seg, brick, strands, brick ? wrblk::order_of(nx, ny, nz, wtflag ? kWavLvl : 0, brick) : wrblk::Order{}, &t)) return rc;
     if (bnd) {  // the trials' work arrays, and the field where the forward transform will not leave it as it is
         for (int k = 0; k < 2; k++) {
             bufs.trial[k] = plane_scratch(c, n * sizeof(double));
             if (!bufs.trial[k].p) return WR_ERR_HIP;
         }
         const bool intact = wtflag && use_fused(nx, ny, nz, kWavLvl) && wrk::fused_minmax_records(nx, ny, nz) != 0;  // all four levels out of place
-        const void* src = fld.host_f32 ? (d_f32 ? (const void*)d_f32 : (const void*)widen_from) : (const void*)d_fld;
+        const void* src = fld.host_f32 ? (up.d_f32 ? (const void*)up.d_f32 : (const void*)up.widen_from) : (const void*)d_fld;
         if (!intact) {
             const size_t bytes = n * (fld.host_f32 ? sizeof(float) : sizeof(double));
             bufs.trial[2] = plane_scratch(c, bytes);
@@ -1697,30 +1813,18 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
         StageLock cu(pool->cu_mu);
         const bool one_array = cut.count() > 1;
         auto plane_buf = [&](unsigned l) -> const wrk::PlaneRef* {
-            if (plane_prepare(c, (int)l, n, false, one_array, &cu, nullptr, false) != WR_OK) return nullptr;
-            bufs.blob[l] = plane_scratch(c, blob_cap);
-            if (!bufs.blob[l].p || bufs.events((int)l) != WR_OK) return nullptr;
+            if (plane_prepare(c, (int)l, n, false, one_array, &cu, nullptr, false) != WR_OK || bufs.coded_plane((int)l, t.blob_cap) != WR_OK) return nullptr;
             return &c->ps[l].ref;
         };
         // plane l's coder kernels go behind its quantizer (and the read-back of the next plane's min/max) on the same stream
         auto after_quant = [&](unsigned l, bool) -> int {
-            launch_note(c, "seg_encode", (int)l, bufs.blob[l].p, n, bufs.stage.p, c->ps[l].ref);
-            HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
-            wrk::PlaneRef sym = c->ps[l].ref;
-            if (brick) {
-                if (!wrk::plane_reorder(sym, bufs.perm.p, od, false, nullptr, 0, c->stream)) return fail(WR_ERR_ARG, "too many bricks");
-                sym = wrk::plane_ref(bufs.perm.p);
-            }
-            if (strands) wrk::strand_encode(sym, n, seg, strands, brick, bufs.stage.p, bufs.blob[l].p, blob_cap, seg_result_dev(c, (int)l), c->stream);
-            else wrk::seg_encode(sym, n, seg, bufs.stage.p, bufs.blob[l].p, blob_cap, seg_result_dev(c, (int)l), c->stream, brick);
-            HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
-            if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented coder launch failed" + launch_describe(c));
+            if (int arc = seg_encode_plane(c, t, c->ps[l].ref, n, (int)l, bufs.blob[l].p, bufs.ev)) return arc;
             if (bud) g_stat[WR_STAT_BUDGET_CODER_RUNS]++;
             if (bnd) g_stat[WR_STAT_BOUNDED_CODER_RUNS]++;
             return WR_OK;
         };
         clock_warmup(c, n);
-        if (widen_from) wrk::widen_f32(widen_from, d_fld, n, c->stream);
+        if (up.widen_from) wrk::widen_f32(up.widen_from, d_fld, n, c->stream);
         PickStep pick;
         if (bud) {
             if ((rc = bud->begin(c, n, seg)) != WR_OK) return rc;
@@ -1737,36 +1841,18 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
             };
         }
         rc = encode_planes_core(c, slot.get(), d_fld, nx, ny, nz, wtflag, cut, plane_buf, [](unsigned) { return (uint16_t*)nullptr; }, info, &local,
-                                after_quant, [](unsigned, bool) { return WR_OK; }, &resid, d_f32, (bud || bnd) ? &pick : nullptr);
-        if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the encoder's kernel stage failed on the device" + launch_describe(c));
-        if (rc == WR_OK && c->keep_residual && info->nlay && !fld.host && resid != fld.dev) {
-            if (hipMemcpyAsync(fld.dev, resid, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
-                hipStreamSynchronize(c->stream) != hipSuccess)
-                rc = fail(WR_ERR_HIP, "residual copy failed");
-        }
-        pool->last_stage_end.store(now());
+                                after_quant, [](unsigned, bool) { return WR_OK; }, &resid, up.d_f32, (bud || bnd) ? &pick : nullptr);
+        rc = encode_stage_end(c, rc, fld, resid, n, info);
     }
     if (rc) return rc;
     if (c->keep_residual && info->nlay && fld.host)
         if ((rc = xfer_field(c, &c->x_field, fld.host, resid, n * sizeof(double), kDown)) != WR_OK) return rc;
     // ---- stage "down": every plane's blob, one copy each, to its place in data_enc
     size_t total = 0;
-    for (unsigned l = 0; l < info->nlay; l++) {
-        const unsigned long long len = seg_result_host(c, (int)l)[0], bad = seg_result_host(c, (int)l)[1];
-        if (bad || len > blob_cap) return fail(WR_ERR_HIP, "internal: plane " + std::to_string(l) + ": a segment outgrew the segment bound");
-        info->len_enc_vec[l] = len;
-        total += len;
-    }
-    if (total > cap || (total && !data_enc)) return fail(WR_ERR_OVERFLOW, "Error: encoded array is too large. Use larger SAFETY_BUFFER_FACTOR");
+    if ((rc = seg_coded_lengths(info->nlay, t.blob_cap, [&](int l) { return seg_result_host(c, l); }, info->len_enc_vec, &total)) != WR_OK) return rc;
+    if (total > cap || (total && !data_enc)) return fail(WR_ERR_OVERFLOW, wrtc::kTooLarge);
     if (bud && total > bud->bound) return fail(WR_ERR_HIP, "internal: the coded planes are longer than their size bound");
-    size_t at = 0;
-    for (unsigned l = 0; l < info->nlay; l++) {
-        if ((rc = xfer_field(c, &c->x_field, data_enc + at, bufs.blob[l].p, info->len_enc_vec[l], kDown)) != WR_OK) return rc;
-        local.d2h_ms += (float)c->x_field.ms;
-        at += info->len_enc_vec[l];
-        local.plane_coder_s[l] = bufs.seconds((int)l);
-        local.rangecoder += local.plane_coder_s[l];
-    }
+    if ((rc = seg_download_blobs(c, bufs, info->nlay, info->len_enc_vec, data_enc, &local)) != WR_OK) return rc;
     info->ntot_enc = total;
     local.total = now() - t0;
     local.wait = t_phase - t0;
@@ -1871,7 +1957,7 @@ template <class Bufs>
 void fold_coder_seconds(const Bufs& bufs, int count, wr_timings* tm)
 {
     for (int l = 0; l < count; l++) {
-        tm->plane_coder_s[l] = bufs.seconds(l);
+        tm->plane_coder_s[l] = bufs.ev.seconds(l);
         tm->rangecoder += tm->plane_coder_s[l];
     }
 }
@@ -1884,7 +1970,7 @@ int seg_plane_bufs(wr_ctx* c, SegBufs* bufs, int l, size_t n, size_t blob_bytes,
     bufs->blob[l] = plane_scratch(c, blob_bytes);
     bufs->work[l] = plane_scratch(c, work_bytes);
     if (!bufs->blob[l].p || !bufs->work[l].p) return WR_ERR_HIP;
-    return events ? bufs->events(l) : WR_OK;
+    return events ? bufs->ev.create(l) : WR_OK;
 }
 
 // stage "up" of a decode of whole planes: one copy per blob, and its segments' offsets
@@ -2381,53 +2467,23 @@ int transcode_impl(wr_ctx* c, int nx, int ny, int nz, const wr_enc_info* info_in
     // ---- target half
     size_t lens[WR_NLAYMAX] = {0};
     if (!ref_target) {
-        // per plane the body of encode_seg_impl's after_quant, then its "down" stage
-        const size_t blob_cap = (wrtc::plane_bound(n, t) + 15) & ~(size_t)15;
-        wrblk::Order od{};
-        if (t.brick) od = wrblk::order_of(nx, ny, nz, (int)info_in->wlev, t.brick);
-        tbufs.stage = plane_scratch(c, t.strands ? wrk::strand_stage_bytes(n, t.seg, t.strands) : wrk::seg_stage_bytes(n, t.seg));
-        if (!tbufs.stage.p) return WR_ERR_HIP;
-        for (int l = 0; l < nlay; l++) {
-            tbufs.blob[l] = plane_scratch(c, blob_cap);
-            if (!tbufs.blob[l].p) return WR_ERR_HIP;
-            if (int rc = tbufs.events(l)) return rc;
-        }
+        // the coder stage of encode_seg_impl with every plane ready at once, then its "down" stage
+        SegTarget st;
+        if (int rc = seg_target(c, &tbufs, n, t.seg, t.brick, t.strands, t.brick ? wrblk::order_of(nx, ny, nz, (int)info_in->wlev, t.brick) : wrblk::Order{}, &st)) return rc;
+        for (int l = 0; l < nlay; l++)
+            if (int rc = tbufs.coded_plane(l, st.blob_cap)) return rc;
         const double t_stage = now();
         {
             StageLock cu(pool->cu_mu);
-            for (int l = 0; l < nlay; l++) {
-                launch_note(c, "seg_encode", l, tbufs.blob[l].p, n, tbufs.stage.p, c->ps[l].ref);
-                HIPCHK(hipEventRecord(tbufs.ev[2 * l], c->stream));
-                wrk::PlaneRef sym = c->ps[l].ref;
-                if (t.brick) {
-                    if (!wrk::plane_reorder(sym, tbufs.perm.p, od, false, nullptr, 0, c->stream)) return fail(WR_ERR_ARG, "too many bricks");
-                    sym = wrk::plane_ref(tbufs.perm.p);
-                }
-                if (t.strands) wrk::strand_encode(sym, n, t.seg, t.strands, t.brick, tbufs.stage.p, tbufs.blob[l].p, blob_cap, seg_result_dev(c, l), c->stream);
-                else wrk::seg_encode(sym, n, t.seg, tbufs.stage.p, tbufs.blob[l].p, blob_cap, seg_result_dev(c, l), c->stream, t.brick);
-                HIPCHK(hipEventRecord(tbufs.ev[2 * l + 1], c->stream));
-                if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "segmented coder launch failed" + launch_describe(c));
-            }
+            for (int l = 0; l < nlay; l++)
+                if (int rc = seg_encode_plane(c, st, c->ps[l].ref, n, l, tbufs.blob[l].p, tbufs.ev)) return rc;
             if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the segmented coder failed on the device" + launch_describe(c));
             pool->last_stage_end.store(now());
         }
         size_t total = 0;
-        for (int l = 0; l < nlay; l++) {
-            const unsigned long long len = seg_result_host(c, l)[0], bad = seg_result_host(c, l)[1];
-            if (bad || len > blob_cap) return fail(WR_ERR_HIP, "internal: plane " + std::to_string(l) + ": a segment outgrew the segment bound");
-            lens[l] = len;
-            total += len;
-        }
+        if (int rc = seg_coded_lengths(nlay, st.blob_cap, [&](int l) { return seg_result_host(c, l); }, lens, &total)) return rc;
         if (total > cap) return fail(WR_ERR_OVERFLOW, wrtc::kTooLarge);
-        size_t at = 0;
-        for (int l = 0; l < nlay; l++) {
-            if (int rc = xfer_field(c, &c->x_field, data_out + at, tbufs.blob[l].p, lens[l], kDown)) return rc;
-            local.d2h_ms += (float)c->x_field.ms;
-            at += lens[l];
-            const double sec = tbufs.seconds(l);
-            local.plane_coder_s[l] += sec;
-            local.rangecoder += sec;
-        }
+        if (int rc = seg_download_blobs(c, tbufs, nlay, lens, data_out, &local)) return rc;
         gpu_s += now() - t_stage;
     } else {
         // block histograms of every plane, then the placement, hand-over and concatenation of encode_impl with all planes ready
@@ -2496,32 +2552,17 @@ int transcode_impl(wr_ctx* c, int nx, int ny, int nz, const wr_enc_info* info_in
         } catch (const std::exception& e) {
             return fail(WR_ERR_ARG, std::string("transcode: ") + e.what());
         }
-        double slowest = 0;
-        size_t total = 0, offs[WR_NLAYMAX] = {0};
+        size_t total = 0;
+        if (int rc = ref_stream_tail(c, jobs, (unsigned)nlay, [&](unsigned l) { return c->ps[l].err != 0; }, est_off, est_len, direct, data_out, cap, wrtc::kTooLarge,
+                                     lens, &total))
+            return rc;
+        double slowest = 0;  // (the planes are coded at the same time, behind the source half)
         for (int l = 0; l < nlay; l++) {
-            if (c->ps[l].err) return fail(WR_ERR_HIP, "download of plane " + std::to_string(l) + " failed");
-            if (jobs[l].result == (size_t)-1)
-                return fail(WR_ERR_HIP, "internal: the coder gave plane " + std::to_string(l) + " up (its block histograms are not its symbols')");
-            if (jobs[l].result > est_len[l]) return fail(WR_ERR_OVERFLOW, "internal: plane " + std::to_string(l) + " outgrew the bound computed from its histograms");
             local.d2h_ms += (float)c->ps[l].copy_ms;
-            offs[l] = total;
-            lens[l] = jobs[l].result;
-            total += lens[l];
             local.plane_coder_s[l] += jobs[l].seconds;
             if (jobs[l].seconds > slowest) slowest = jobs[l].seconds;
         }
         local.rangecoder += slowest;
-        if (total > cap) return fail(WR_ERR_OVERFLOW, wrtc::kTooLarge);
-        // close the gaps, in plane order (encode_impl)
-        for (int l = 0; l < nlay; l++) {
-            if (!direct[l]) memcpy(data_out + offs[l], c->enc_buf[l], lens[l]);
-            else if (est_off[l] != offs[l]) memmove(data_out + offs[l], data_out + est_off[l], lens[l]);
-        }
-        for (int l = 0; l < nlay; l++) {
-            if (direct[l]) continue;
-            const uintptr_t a = ((uintptr_t)c->enc_buf[l] + 4095) & ~(uintptr_t)4095, e = ((uintptr_t)c->enc_buf[l] + lens[l]) & ~(uintptr_t)4095;
-            if (e > a && e - a >= ((size_t)64 << 20)) (void)madvise(reinterpret_cast<void*>(a), e - a, MADV_DONTNEED);
-        }
     }
     wrtc::finish_info(*info_in, lens, nlay, info_out);
     local.total = now() - t0;
@@ -2572,57 +2613,40 @@ int fetch_front(const unsigned char* d_blob, size_t blob_len, size_t n, bool blo
 
 extern "C" {
 
-int wr_dev_seg_encode(wr_ctx* c, const unsigned char* d_sym, size_t n, unsigned seg, unsigned char* d_blob, size_t cap, size_t* blob_len)
+// one plane, as it stands, into the caller's blob buffer: strands == 0 a WRS1 blob, otherwise WRS3 in the natural order
+static int dev_seg_encode(wr_ctx* c, const unsigned char* d_sym, size_t n, unsigned seg, unsigned strands, unsigned char* d_blob, size_t cap, size_t* blob_len)
 {
-    if (!seg) seg = WR_SEG_DEFAULT;
-    if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
+    if (int rc = seg_format_params(&seg, 0, strands)) return rc;
     if (int rc = ctx_bind(c)) return rc;
     if (!d_blob || !blob_len || (n && !d_sym)) return fail(WR_ERR_ARG, "null pointer");
     if (((uintptr_t)d_sym | (uintptr_t)d_blob) & 15) return fail(WR_ERR_ARG, "plane and blob buffers must be 16-byte aligned");
     const size_t nseg = wrseg::seg_count(n, seg);
     if (nseg > 0xffffffffu) return fail(WR_ERR_ARG, "too many segments");
-    if (cap < wrseg::kHeaderBytes + 4 * nseg) return fail(WR_ERR_OVERFLOW, "the blob buffer does not hold the plane's index");
+    if (cap < wrseg::header_bytes(0, strands) + 4 * nseg) return fail(WR_ERR_OVERFLOW, "the blob buffer does not hold the plane's index");
     std::lock_guard<std::mutex> lk(c->mu);
     SegBufs bufs(c);
-    bufs.stage = plane_scratch(c, wrk::seg_stage_bytes(n, seg));
-    if (!bufs.stage.p) return WR_ERR_HIP;
+    SegTarget t;
+    if (int rc = seg_target(c, &bufs, n, seg, 0, strands, wrblk::Order{}, &t)) return rc;
     StageLock cu(c->pool->cu_mu);
-    wrk::seg_encode(wrk::plane_ref(d_sym), n, seg, bufs.stage.p, d_blob, cap, seg_result_dev(c, 0), c->stream);
+    seg_encode_launch(c, t, wrk::plane_ref(d_sym), n, d_blob, cap, 0);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
     const unsigned long long len = seg_result_host(c, 0)[0], bad = seg_result_host(c, 0)[1];
-    if (bad) return fail(WR_ERR_HIP, "internal: a segment outgrew the segment bound");
+    if (bad) return fail(WR_ERR_HIP, strands ? "internal: a record outgrew the record bound" : std::string("internal: ") + kOutgrew);
     if (len > cap) return fail(WR_ERR_OVERFLOW, "the blob buffer is too small for the plane");
     *blob_len = (size_t)len;
     return WR_OK;
 }
 
+int wr_dev_seg_encode(wr_ctx* c, const unsigned char* d_sym, size_t n, unsigned seg, unsigned char* d_blob, size_t cap, size_t* blob_len)
+{
+    return dev_seg_encode(c, d_sym, n, seg, 0, d_blob, cap, blob_len);
+}
+
 int wr_dev_seg_encode_strands(wr_ctx* c, const unsigned char* d_sym, size_t n, unsigned seg, unsigned strands, unsigned char* d_blob, size_t cap,
                               size_t* blob_len)
 {
-    if (!seg) seg = WR_SEG_DEFAULT;
-    if (!strands) strands = WR_STRANDS_DEFAULT;
-    if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
-    if (!wrseg::strands_ok(strands, seg)) return fail(WR_ERR_ARG, "strands must be one of 1, 2, 4, 8, 16, 32 with 16 * strands <= seg");
-    if (int rc = ctx_bind(c)) return rc;
-    if (!d_blob || !blob_len || (n && !d_sym)) return fail(WR_ERR_ARG, "null pointer");
-    if (((uintptr_t)d_sym | (uintptr_t)d_blob) & 15) return fail(WR_ERR_ARG, "plane and blob buffers must be 16-byte aligned");
-    const size_t nseg = wrseg::seg_count(n, seg);
-    if (nseg > 0xffffffffu) return fail(WR_ERR_ARG, "too many segments");
-    if (cap < wrseg::kHeaderBytesStrands + 4 * nseg) return fail(WR_ERR_OVERFLOW, "the blob buffer does not hold the plane's index");
-    std::lock_guard<std::mutex> lk(c->mu);
-    SegBufs bufs(c);
-    bufs.stage = plane_scratch(c, wrk::strand_stage_bytes(n, seg, strands));
-    if (!bufs.stage.p) return WR_ERR_HIP;
-    StageLock cu(c->pool->cu_mu);
-    wrk::strand_encode(wrk::plane_ref(d_sym), n, seg, strands, 0, bufs.stage.p, d_blob, cap, seg_result_dev(c, 0), c->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const unsigned long long len = seg_result_host(c, 0)[0], bad = seg_result_host(c, 0)[1];
-    if (bad) return fail(WR_ERR_HIP, "internal: a record outgrew the record bound");
-    if (len > cap) return fail(WR_ERR_OVERFLOW, "the blob buffer is too small for the plane");
-    *blob_len = (size_t)len;
-    return WR_OK;
+    return dev_seg_encode(c, d_sym, n, seg, strands ? strands : WR_STRANDS_DEFAULT, d_blob, cap, blob_len);
 }
 
 int wr_dev_seg_decode(wr_ctx* c, const unsigned char* d_blob, size_t blob_len, unsigned char* d_sym, size_t n, size_t* bad_segments)
@@ -2843,8 +2867,7 @@ int wr_dev_requant_accum(wr_ctx* c, const double* d_coef, size_t n, int nlay, co
 
 int wr_dev_plane_size_bound(wr_ctx* c, const unsigned char* d_sym, size_t n, unsigned seg, size_t* bound)
 {
-    if (!seg) seg = WR_SEG_DEFAULT;
-    if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
+    if (int rc = seg_format_params(&seg, 0, 0)) return rc;
     if (int rc = ctx_bind(c)) return rc;
     if (!bound || (n && !d_sym)) return fail(WR_ERR_ARG, "null pointer");
     if ((uintptr_t)d_sym & 15) return fail(WR_ERR_ARG, "the plane must be 16-byte aligned");
@@ -2861,8 +2884,7 @@ int wr_dev_plane_size_bound(wr_ctx* c, const unsigned char* d_sym, size_t n, uns
 
 int wr_dev_quant_size_probe(wr_ctx* c, const double* d_resid, size_t n, double minval, int ncand, const double* deps, unsigned seg, size_t* bounds)
 {
-    if (!seg) seg = WR_SEG_DEFAULT;
-    if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
+    if (int rc = seg_format_params(&seg, 0, 0)) return rc;
     if (ncand < 1 || ncand > wrk::kProbeK) return fail(WR_ERR_ARG, "a size probe takes 1 to " + std::to_string(wrk::kProbeK) + " candidate steps");
     if (int rc = ctx_bind(c)) return rc;
     if (!bounds || !deps || (n && !d_resid)) return fail(WR_ERR_ARG, "null pointer");
@@ -2947,7 +2969,7 @@ int wr_transcode_host(wr_ctx* c, int nx, int ny, int nz, const wr_enc_info* info
 int wr_dev_plane_reorder(wr_ctx* c, unsigned char* d_dst, const unsigned char* d_src, int nx, int ny, int nz, int wlev, unsigned brick, int inverse)
 {
     if (!brick) brick = WR_BRICK_DEFAULT;
-    if (!wrblk::brick_ok(brick)) return fail(WR_ERR_ARG, "brick edge must be one of 8, 16, 32, 64");
+    if (int rc = seg_format_params(nullptr, brick, 0)) return rc;
     if (wlev != 0 && wlev != kWavLvl) return fail(WR_ERR_ARG, "wlev must be 0 or 4");
     if (int rc = ctx_bind(c)) return rc;
     if (int rc = check_dims(nx, ny, nz, d_dst)) return rc;
@@ -3025,7 +3047,6 @@ size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 // What a batch takes from the plane pool, piece by piece.  The drivers allocate by these and wr_seg_batch_device_bytes sums them.
 size_t batch_plane_bytes(size_t n) { return wr_plane_pitch(n); }
 size_t batch_perm_bytes(size_t n, unsigned brick) { return brick ? wr_plane_pitch(n) : 0; }  // per field: the plane in stream order
-size_t batch_blob_cap(size_t n, unsigned seg, unsigned brick) { return ((brick ? wr_seg_bound_blocked(n, seg) : wr_seg_bound(n, seg)) + 15) & ~(size_t)15; }
 size_t batch_work_bytes(size_t nseg) { return wrk::seg_decode_work_bytes(nseg); }  // per decoded (field, plane): offsets and flags
 // once per call.  encode: the staging of one plane index; decode: a job table per plane index and a failure count per job
 size_t batch_once_bytes(size_t nfields, size_t n, int nlay, unsigned seg, bool decode)
@@ -3033,8 +3054,22 @@ size_t batch_once_bytes(size_t nfields, size_t n, int nlay, unsigned seg, bool d
     if (!nlay) return 0;
     return decode ? (size_t)nlay * wrk::seg_batch_table_bytes(nfields) + up256(4 * nfields * (size_t)nlay) : wrk::seg_batch_stage_bytes(nfields, n, seg);
 }
-// pinned host memory of a call: the job tables of its launch sequences, then 16 bytes per job for what comes back
-size_t batch_pinned_bytes(size_t njobs_max, int nlay) { return (size_t)nlay * (wrk::seg_batch_table_bytes(njobs_max) + up256(16 * njobs_max)); }
+// pinned host memory of a call, per launch sequence (plane index): the job table, then 16 bytes per job for what comes back
+struct BatchPinned {
+    size_t table, per_l;
+    explicit BatchPinned(size_t njobs_max) : table(wrk::seg_batch_table_bytes(njobs_max)), per_l(table + up256(16 * njobs_max)) {}
+    size_t bytes(int nlay) const { return (size_t)nlay * per_l; }
+    uint8_t* jobs(uint8_t* pinned, int l) const { return pinned + l * per_l; }
+    unsigned long long* results(uint8_t* pinned, int l) const { return reinterpret_cast<unsigned long long*>(pinned + l * per_l + table); }
+};
+
+// the job of one plane for the batched coder kernels: its symbols in stream order into [blob, blob + cap)
+wrk::SegJob seg_encode_job(const wrk::PlaneRef& sym, uint8_t* blob, size_t cap, uint32_t brick)
+{
+    wrk::SegJob j; memset(&j, 0, sizeof j);
+    j.sym = sym; j.blob = blob; j.cap = cap; j.brick = brick;
+    return j;
+}
 
 // device and pinned memory of a batch call; goes back when the call ends, behind everything the context's stream still has queued
 struct BatchBufs {
@@ -3042,7 +3077,7 @@ struct BatchBufs {
     std::vector<DevPlanes::Buf> taken;
     uint8_t* pinned = nullptr;      // the job tables (they stay alive until the stream has drained) and the results
     uint8_t* pinned_dev = nullptr;  // the same block as the device sees it
-    hipEvent_t ev[2 * WR_NLAYMAX] = {nullptr};
+    PlaneEvents ev;                 // one pair per plane index
     explicit BatchBufs(wr_ctx* ctx) : c(ctx) {}
     BatchBufs(const BatchBufs&) = delete;
     BatchBufs& operator=(const BatchBufs&) = delete;
@@ -3051,7 +3086,6 @@ struct BatchBufs {
         (void)hipStreamSynchronize(c->stream);
         for (const DevPlanes::Buf& b : taken) c->pool->planes.give(b);
         if (pinned) (void)hipHostFree(pinned);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     }
     uint8_t* take(size_t bytes)  // nullptr: the error is set (plane_scratch)
     {
@@ -3065,18 +3099,6 @@ struct BatchBufs {
         HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&pinned_dev), pinned, 0));
         memset(pinned, 0, bytes);
         return WR_OK;
-    }
-    int events(int l)
-    {
-        for (int k = 2 * l; k < 2 * l + 2; k++)
-            if (!ev[k]) HIPCHK(hipEventCreate(&ev[k]));
-        return WR_OK;
-    }
-    double seconds(int l) const
-    {
-        float ms = 0;
-        if (!ev[2 * l] || hipEventElapsedTime(&ms, ev[2 * l], ev[2 * l + 1]) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        return ms * 1e-3;
     }
 };
 
@@ -3093,9 +3115,7 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
                           const double* const* cutoffvecs, unsigned seg, unsigned brick, wr_enc_info* infos, unsigned char* const* data_encs,
                           const size_t* caps, wr_timings* tm)
 {
-    if (!seg) seg = WR_SEG_DEFAULT;
-    if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
-    if (brick && !wrblk::brick_ok(brick)) return fail(WR_ERR_ARG, "brick edge must be one of 8, 16, 32, 64");
+    if (int rc = seg_format_params(&seg, brick, 0)) return rc;
     if (!cutoffvecs || !infos || !data_encs || !caps) return fail(WR_ERR_ARG, "null array");
     if (mx < 1 || my < 1 || mz < 1) return fail(WR_ERR_ARG, "bad local cutoff description");
     if (int rc = ctx_bind(c)) return rc;
@@ -3119,7 +3139,8 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
     c->pend_valid = false;
     PlaneHold planes(c);
     BatchBufs bufs(c);  // (goes first when the call unwinds, and waits for the stream)
-    const size_t blob_cap = batch_blob_cap(n, seg, brick);
+    const size_t blob_cap = seg_blob_cap(n, seg, brick, 0);
+    const BatchPinned pin(nfields);
     wrblk::Order od{};
     if (brick) od = wrblk::order_of(nx, ny, nz, wtflag ? kWavLvl : 0, brick);
 
@@ -3140,21 +3161,11 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
         for (int f = 0; f < nfields; f++) {
             const FieldRef& fld = flds[f];
             Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvecs[f];
-            double* d_fld = fld.dev;
-            if (fld.host) {
-                d_fld = slot->field;
-                if (int rc = xfer_field(c, &c->x_field, d_fld, fld.host, n * sizeof(double), kUp)) return fail_at("field", f, rc);
-                local.h2d_ms += (float)c->x_field.ms;
-            }
-            const float* d_f32 = nullptr;  // (as encode_seg_impl: the fused forward transform reads an fp32 field where it lands)
-            if (fld.host_f32) {
-                d_fld = slot->field;
-                float* const stage = (wtflag && use_fused(nx, ny, nz, kWavLvl)) ? reinterpret_cast<float*>(slot->field) : reinterpret_cast<float*>(slot->scratch);
-                if (int rc = xfer_field(c, &c->x_field, stage, fld.host_f32, n * sizeof(float), kUp)) return fail_at("field", f, rc);
-                local.h2d_ms += (float)c->x_field.ms;
-                if (stage == reinterpret_cast<float*>(slot->field)) d_f32 = stage;
-                else wrk::widen_f32(stage, d_fld, n, c->stream);
-            }
+            FieldUpload up;
+            if (int rc = upload_field(c, slot.get(), fld, nx, ny, nz, wtflag, &up)) return fail_at("field", f, rc);
+            local.h2d_ms += up.ms;
+            double* const d_fld = up.d_fld;
+            if (up.widen_from) wrk::widen_f32(up.widen_from, d_fld, n, c->stream);  // (the stage is held: at once)
             auto plane_buf = [&](unsigned l) -> const wrk::PlaneRef* {
                 uint8_t* const p = bufs.take(batch_plane_bytes(n));
                 if (!p) return nullptr;
@@ -3164,7 +3175,7 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
             double* resid = d_fld;
             wr_timings ft; memset(&ft, 0, sizeof ft);
             int rc = encode_planes_core(c, slot.get(), d_fld, nx, ny, nz, wtflag, cut, plane_buf, [](unsigned) { return (uint16_t*)nullptr; }, &infos[f], &ft,
-                                        [](unsigned, bool) { return WR_OK; }, [](unsigned, bool) { return WR_OK; }, &resid, d_f32);
+                                        [](unsigned, bool) { return WR_OK; }, [](unsigned, bool) { return WR_OK; }, &resid, up.d_f32);
             // the slot is the next field's from here on
             if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the encoder's kernel stage failed on the device" + launch_describe(c));
             if (rc) return fail_at("field", f, rc);
@@ -3180,29 +3191,22 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
                     if (!(blob[(size_t)f * WR_NLAYMAX + l] = bufs.take(blob_cap))) return fail_at("field", f, WR_ERR_HIP);
                 if (brick && infos[f].nlay && !(perm[f] = bufs.take(batch_perm_bytes(n, brick)))) return fail_at("field", f, WR_ERR_HIP);
             }
-            if (int rc = bufs.pin(batch_pinned_bytes(nfields, maxlay))) return rc;
-            const size_t table = wrk::seg_batch_table_bytes(nfields), per_l = table + up256(16 * (size_t)nfields);
+            if (int rc = bufs.pin(pin.bytes(maxlay))) return rc;
             std::vector<wrk::SegJob> jobs;
             for (int l = 0; l < maxlay; l++) {
-                if (int rc = bufs.events(l)) return rc;
+                if (int rc = bufs.ev.create(l)) return rc;
                 HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
                 jobs.clear();
                 for (int f = 0; f < nfields; f++) {
                     if ((int)infos[f].nlay <= l) continue;
                     const size_t at = (size_t)f * WR_NLAYMAX + l;
-                    wrk::SegJob j; memset(&j, 0, sizeof j);
-                    j.sym = refs[at];
-                    if (brick) {  // the plane in stream order: a pass of milliseconds per field, not batched
-                        if (!wrk::plane_reorder(refs[at], perm[f], od, false, nullptr, 0, c->stream)) return fail(WR_ERR_ARG, "too many bricks");
-                        j.sym = wrk::plane_ref(perm[f]);
-                    }
-                    j.blob = blob[at]; j.cap = blob_cap; j.brick = brick;
+                    // a blocked stream: the plane in stream order first, a pass of milliseconds per field, not batched
+                    if (brick && !wrk::plane_reorder(refs[at], perm[f], od, false, nullptr, 0, c->stream)) return fail(WR_ERR_ARG, "too many bricks");
                     job_of[at] = (int)jobs.size();
-                    jobs.push_back(j);
+                    jobs.push_back(seg_encode_job(brick ? wrk::plane_ref(perm[f]) : refs[at], blob[at], blob_cap, brick));
                 }
-                launch_note(c, "seg_encode_batch", l, stage, n, bufs.pinned + l * per_l, jobs[0].sym);
-                wrk::seg_encode_batch(jobs.data(), jobs.size(), n, seg, bufs.pinned + l * per_l, stage,
-                                      reinterpret_cast<unsigned long long*>(bufs.pinned_dev + l * per_l + table), c->stream);
+                launch_note(c, "seg_encode_batch", l, stage, n, pin.jobs(bufs.pinned, l), jobs[0].sym);
+                wrk::seg_encode_batch(jobs.data(), jobs.size(), n, seg, pin.jobs(bufs.pinned, l), stage, pin.results(bufs.pinned_dev, l), c->stream);
                 HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
                 if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "batched segment coder launch failed" + launch_describe(c));
             }
@@ -3211,19 +3215,13 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
         pool->last_stage_end.store(now());
     }
     // ---- stage "down": every blob, one copy each, to its place in its field's data_enc
-    const size_t table = wrk::seg_batch_table_bytes(nfields), per_l = table + up256(16 * (size_t)nfields);
     for (int f = 0; f < nfields; f++) {
         wr_enc_info* const info = &infos[f];
+        const std::string who = "field " + std::to_string(f) + ": ";
         size_t total = 0;
-        for (int l = 0; l < (int)info->nlay; l++) {
-            const unsigned long long* const res = reinterpret_cast<const unsigned long long*>(bufs.pinned + l * per_l + table) + 2 * job_of[(size_t)f * WR_NLAYMAX + l];
-            if (res[1] || res[0] > blob_cap)
-                return fail(WR_ERR_HIP, "field " + std::to_string(f) + ": internal: plane " + std::to_string(l) + ": a segment outgrew the segment bound");
-            info->len_enc_vec[l] = res[0];
-            total += res[0];
-        }
-        if (total > caps[f] || (total && !data_encs[f]))
-            return fail(WR_ERR_OVERFLOW, "field " + std::to_string(f) + ": Error: encoded array is too large. Use larger SAFETY_BUFFER_FACTOR");
+        auto res_of = [&](int l) { return pin.results(bufs.pinned, l) + 2 * job_of[(size_t)f * WR_NLAYMAX + l]; };
+        if (int rc = seg_coded_lengths(info->nlay, blob_cap, res_of, info->len_enc_vec, &total, who)) return rc;
+        if (total > caps[f] || (total && !data_encs[f])) return fail(WR_ERR_OVERFLOW, who + wrtc::kTooLarge);
         size_t at = 0;
         for (int l = 0; l < (int)info->nlay; l++) {
             if (int rc = xfer_field(c, &c->x_field, data_encs[f] + at, blob[(size_t)f * WR_NLAYMAX + l], info->len_enc_vec[l], kDown)) return fail_at("field", f, rc);
@@ -3232,10 +3230,7 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
         }
         info->ntot_enc = total;
     }
-    for (int l = 0; l < maxlay; l++) {
-        local.plane_coder_s[l] = bufs.seconds(l);
-        local.rangecoder += local.plane_coder_s[l];
-    }
+    fold_coder_seconds(bufs, maxlay, &local);  // one entry per plane index
     local.total = now() - t0;
     local.wait = t_phase - t0;
     local.gpu = now() - t_phase;
@@ -3301,7 +3296,7 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
             if (b.s.brick && !(b.perm = bufs.take(batch_perm_bytes(n, b.s.brick)))) return fail_at("field", f, WR_ERR_HIP);
         }
         if (!(d_once = bufs.take(batch_once_bytes(nfields, n, maxlay, 0, true)))) return WR_ERR_HIP;
-        if (int rc = bufs.pin(batch_pinned_bytes(nfields, maxlay))) return rc;
+        if (int rc = bufs.pin(BatchPinned(nfields).bytes(maxlay))) return rc;
     }
     // ---- stage "up": one copy per blob, and its segments' offsets
     for (int f = 0; f < nfields; f++)
@@ -3324,11 +3319,11 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
         if (maxlay) {
             // the jobs' failure counts lie behind the tables: job (f, l) counts into d_bad[l * nfields + f]
             unsigned int* const d_bad = reinterpret_cast<unsigned int*>(d_once + (size_t)maxlay * table);
-            const size_t per_l = table + up256(16 * (size_t)nfields);
+            const size_t per_l = BatchPinned(nfields).per_l;
             HIPCHK(hipMemsetAsync(d_bad, 0, 4 * (size_t)nfields * maxlay, c->stream));
             std::vector<wrk::SegJob> jobs;
             for (int l = 0; l < maxlay; l++) {
-                if (int rc = bufs.events(l)) return rc;
+                if (int rc = bufs.ev.create(l)) return rc;
                 jobs.clear();
                 for (int f = 0; f < nfields; f++) {
                     const BatchField& b = bf[f];
@@ -3419,7 +3414,7 @@ size_t wr_seg_batch_device_bytes(int nfields, size_t n, int nlay, unsigned seg, 
     if (!seg) seg = WR_SEG_DEFAULT;
     if (nfields < 1 || nfields > WR_SEG_BATCH_MAX || !n || nlay < 0 || nlay > WR_NLAYMAX || !wrseg::seg_ok(seg) || (brick && !wrblk::brick_ok(brick))) return 0;
     const size_t N = (size_t)nfields;
-    size_t per_plane = batch_plane_bytes(n) + up256(batch_blob_cap(n, seg, brick));
+    size_t per_plane = batch_plane_bytes(n) + up256(seg_blob_cap(n, seg, brick, 0));
     if (decode) per_plane += up256(batch_work_bytes(wrseg::seg_count(n, seg)));
     return N * (size_t)nlay * per_plane + N * batch_perm_bytes(n, brick) + up256(batch_once_bytes(N, n, nlay, seg, decode != 0));
 }
@@ -3437,8 +3432,7 @@ int wr_seg_batch_locate(const uint32_t* first, uint32_t njobs, uint32_t g, uint3
 int wr_dev_seg_encode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_sym, size_t n, unsigned seg, unsigned char* const* d_blob, const size_t* cap,
                             size_t* blob_len)
 {
-    if (!seg) seg = WR_SEG_DEFAULT;
-    if (!wrseg::seg_ok(seg)) return fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]");
+    if (int rc = seg_format_params(&seg, 0, 0)) return rc;
     if (njobs < 1 || njobs > WR_SEG_BATCH_MAX) return fail(WR_ERR_ARG, "njobs must be in 1.." + std::to_string(WR_SEG_BATCH_MAX));
     if (int rc = ctx_bind(c)) return rc;
     if (!d_sym || !d_blob || !cap || !blob_len) return fail(WR_ERR_ARG, "null array");
@@ -3453,22 +3447,18 @@ int wr_dev_seg_encode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_
     BatchBufs bufs(c);
     uint8_t* const stage = bufs.take(wrk::seg_batch_stage_bytes(njobs, n, seg));
     if (!stage) return WR_ERR_HIP;
-    if (int rc = bufs.pin(batch_pinned_bytes(njobs, 1))) return rc;
-    const size_t table = wrk::seg_batch_table_bytes(njobs);
-    std::vector<wrk::SegJob> jobs(njobs);
-    for (int j = 0; j < njobs; j++) {
-        memset(&jobs[j], 0, sizeof jobs[j]);
-        jobs[j].sym = wrk::plane_ref(d_sym[j]);
-        jobs[j].blob = d_blob[j]; jobs[j].cap = cap[j];
-    }
+    const BatchPinned pin(njobs);
+    if (int rc = bufs.pin(pin.bytes(1))) return rc;
+    std::vector<wrk::SegJob> jobs;
+    for (int j = 0; j < njobs; j++) jobs.push_back(seg_encode_job(wrk::plane_ref(d_sym[j]), d_blob[j], cap[j], 0));
     StageLock cu(c->pool->cu_mu);
-    wrk::seg_encode_batch(jobs.data(), jobs.size(), n, seg, bufs.pinned, stage, reinterpret_cast<unsigned long long*>(bufs.pinned_dev + table), c->stream);
+    wrk::seg_encode_batch(jobs.data(), jobs.size(), n, seg, pin.jobs(bufs.pinned, 0), stage, pin.results(bufs.pinned_dev, 0), c->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
-    const unsigned long long* const res = reinterpret_cast<const unsigned long long*>(bufs.pinned + table);
+    const unsigned long long* const res = pin.results(bufs.pinned, 0);
     int rc = WR_OK;
     for (int j = 0; j < njobs; j++) {
-        if (res[2 * j + 1]) { if (!rc) rc = fail(WR_ERR_HIP, "job " + std::to_string(j) + ": internal: a segment outgrew the segment bound"); continue; }
+        if (res[2 * j + 1]) { if (!rc) rc = fail(WR_ERR_HIP, "job " + std::to_string(j) + ": internal: " + kOutgrew); continue; }
         if (res[2 * j] > cap[j]) { if (!rc) rc = fail(WR_ERR_OVERFLOW, "job " + std::to_string(j) + ": the blob buffer is too small for the plane"); continue; }
         blob_len[j] = (size_t)res[2 * j];
     }
@@ -3501,7 +3491,7 @@ int wr_dev_seg_decode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_
     const size_t table = wrk::seg_batch_table_bytes(njobs);
     uint8_t* const d_once = bufs.take(batch_once_bytes(njobs, n, 1, 0, true));
     if (!d_once) return WR_ERR_HIP;
-    if (int rc = bufs.pin(batch_pinned_bytes(njobs, 1))) return rc;
+    if (int rc = bufs.pin(BatchPinned(njobs).bytes(1))) return rc;
     unsigned int* const d_bad = reinterpret_cast<unsigned int*>(d_once + table);
     std::vector<wrk::SegJob> jobs(njobs);
     for (int j = 0; j < njobs; j++) {
@@ -4024,7 +4014,7 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
         if (njobs) {
             if (!(d_once = bufs.take(roi_batch_once_bytes(nplain, nstranded)))) return WR_ERR_HIP;
             if (int rc = bufs.pin(roi_batch_tables_bytes(nplain, nstranded))) return rc;
-            if (int rc = bufs.events(0)) return rc;
+            if (int rc = bufs.ev.create(0)) return rc;
         }
         if (njobs && !fld.dev && !(d_host_out = bufs.take((size_t)nfields * T * elem))) return WR_ERR_HIP;
     }
