@@ -629,6 +629,28 @@ size_t wr_seg_roi_segments_blocked(int nx, int ny, int nz, int level, int wlev, 
  * d_src[pi[p]] (natural order to blocked); otherwise d_dst[pi[p]] = d_src[p]. */
 int wr_dev_plane_reorder(wr_ctx *ctx, unsigned char *d_dst, const unsigned char *d_src, int nx, int ny, int nz, int wlev,
                          unsigned brick, int inverse);
+/* the same over a subset of the bricks: only the stream positions of the listed bricks (and the coefficients they map to) are
+ * read and written, so what d_dst held everywhere else is still there afterwards -- d_dst is NOT cleared.  Brick ids count the
+ * bricks of the boxes in stream order (box after box, inside a box tz, ty, tx with tx fastest).  ids[0, nlist) is in HOST
+ * memory, strictly ascending, every id below the plane's number of bricks (wr_reorder_plan's nbricks): anything else, a null
+ * ids with nlist > 0 and what wr_dev_plane_reorder refuses is WR_ERR_ARG before any copy or launch.  nlist == 0: WR_OK,
+ * nothing is launched. */
+int wr_dev_plane_reorder_list(wr_ctx *ctx, unsigned char *d_dst, const unsigned char *d_src, int nx, int ny, int nz, int wlev,
+                              unsigned brick, int inverse, const uint32_t *ids, size_t nlist);
+/* how the reorder kernel walks a plane (host only: no device call, no context; the refusals of wr_dev_plane_reorder, and
+ * out == NULL: WR_ERR_ARG; a refused call leaves *out alone).  A work item is `group` bricks that follow each other along x in
+ * one box (128 / B of them; list != 0, a launch over a brick list: 1), `items` of them in all, over the `nbricks` bricks of
+ * the plane's nbox boxes.  box[0, nbox) are the boxes in stream order, x, y, z: origin and extent in the coefficient array,
+ * bricks per axis, `first` the box's first work item, `first_brick` the id of its first brick, `start` the stream position
+ * of its first symbol; `wide`: the box moves 16 bytes per lane, otherwise a byte (planes aligned as the library's own always
+ * are: B >= 16 and the box's origin and extent in x, nx and start all multiples of 16). */
+typedef struct wr_reorder_plan_t {
+    int group;
+    uint32_t items, nbricks;
+    int nbox;
+    struct { int origin[3], extent[3], bricks[3]; uint32_t first, first_brick; uint64_t start; int wide; } box[29];
+} wr_reorder_plan_t;
+int wr_reorder_plan(int nx, int ny, int nz, int wlev, unsigned brick, int list, wr_reorder_plan_t *out);
 /* whole path: wr_encode_host_seg / _f32 / wr_encode_device_seg with every plane as a WRS2 blob */
 int wr_encode_host_seg_blocked(wr_ctx *ctx, const double *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my,
                                int mz, const double *cutoffvec, unsigned seg, unsigned brick, wr_enc_info *info,

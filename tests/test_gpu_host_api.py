@@ -167,10 +167,12 @@ def test_concurrent_host_calls_share_the_slots(api, oracle, nslots):
         assert api.stat(api.STAT_SLOTS_POPULATED) == expect
 
 
-@pytest.mark.parametrize("shape", [(4, 70000, 2), (2, 3, 66000), (12000, 3, 2), (16, 65600, 16)])
+@pytest.mark.parametrize("shape", [(4, 70000, 2), (2, 3, 66000), (12000, 3, 2), (16, 65600, 16), (6200, 2, 3), (10200, 3, 2), (10201, 2, 2)])
 def test_dimensions_beyond_the_launch_grid_limits(ctx, oracle, shape):
     """ny or nz > 65535 (the limit of gridDim.y/z) and x lines longer than the LDS-staged kernel takes: the
-    reference has no such limits (it loops), so the drop-in must not have them either."""
+    reference has no such limits (it loops), so the drop-in must not have them either.  Lines of 6200 and 10200 samples are
+    staged whole in more than 48 KiB of dynamic LDS (the line kernel raises its limit for them), 10200 is the longest line it
+    takes and 10201 the first that goes to the streaming pass; 12000 streams at level 0 and has a 6000-sample line below."""
     nx, ny, nz = shape
     f = synth.field(nx, ny, nz, seed=3)
     want = oracle.encode(f, 1e-5)

@@ -94,6 +94,16 @@ class RoiPlan(C.Structure):
                 ("box", RoiPlanBox * 29)]
 
 
+class ReorderPlanBox(C.Structure):
+    _fields_ = [("origin", C.c_int * 3), ("extent", C.c_int * 3), ("bricks", C.c_int * 3), ("first", C.c_uint32), ("first_brick", C.c_uint32),
+                ("start", C.c_uint64), ("wide", C.c_int)]
+
+
+class ReorderPlan(C.Structure):
+    """wr_reorder_plan_t"""
+    _fields_ = [("group", C.c_int), ("items", C.c_uint32), ("nbricks", C.c_uint32), ("nbox", C.c_int), ("box", ReorderPlanBox * 29)]
+
+
 class WaveRangeError(RuntimeError):
     pass
 
@@ -251,6 +261,8 @@ def lib():
     L.wr_seg_roi_segments_blocked.restype = C.c_size_t
     L.wr_seg_roi_segments_blocked.argtypes = [C.c_int] * 5 + [C.POINTER(Box), C.c_uint, C.c_uint, _vp, C.c_size_t]
     L.wr_dev_plane_reorder.argtypes = [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int]
+    L.wr_dev_plane_reorder_list.argtypes = L.wr_dev_plane_reorder.argtypes + [_vp, C.c_size_t]
+    L.wr_reorder_plan.argtypes = [C.c_int] * 4 + [C.c_uint, C.c_int, C.POINTER(ReorderPlan)]
     L.wr_seg_encode_host_ref_blocked.restype = C.c_size_t
     L.wr_seg_encode_host_ref_blocked.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint, _vp]
     L.wr_seg_decode_host_ref_blocked.argtypes = [_vp, C.c_size_t, _vp, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -539,6 +551,18 @@ def blocked_order(shape, wlev=4, brick=0):
     pi = np.empty(nx * ny * nz, dtype=np.uint64)
     _check(lib().wr_blocked_order(nx, ny, nz, wlev, brick, pi.ctypes.data))
     return pi
+
+
+def reorder_plan(shape, wlev=4, brick=0, list=False):
+    """How the reorder kernel walks a plane of a field shaped (nz, ny, nx) (wr_reorder_plan; host only, needs no GPU):
+    dict(group, items, nbricks, boxes), boxes = one dict(origin, extent, bricks, first, first_brick, start, wide) per box in
+    stream order, origin / extent / bricks as (x, y, z).  list: the plan of a launch over a brick list."""
+    nz, ny, nx = shape
+    p = ReorderPlan()
+    _check(lib().wr_reorder_plan(nx, ny, nz, wlev, brick, int(bool(list)), C.byref(p)))
+    return dict(group=p.group, items=p.items, nbricks=p.nbricks,
+                boxes=[dict(origin=tuple(b.origin), extent=tuple(b.extent), bricks=tuple(b.bricks), first=b.first, first_brick=b.first_brick,
+                            start=b.start, wide=bool(b.wide)) for b in p.box[:p.nbox]])
 
 
 def seg_encode_host_ref_blocked(plane, shape, wlev=4, brick=0, seg=0):
@@ -1448,6 +1472,24 @@ class Context:
         d_src, d_dst = self.to_device(p), self.alloc(p.size)
         try:
             _check(lib().wr_dev_plane_reorder(self.h, d_dst.ptr, d_src.ptr, nx, ny, nz, wlev, brick, int(bool(inverse))))
+            return d_dst.download(np.uint8, p.size)
+        finally:
+            d_src.free()
+            d_dst.free()
+
+    def plane_reorder_list(self, plane, shape, wlev, brick, ids, inverse=False, fill=None):
+        """Stage level: the bricks `ids` (ascending brick ids, reorder_plan's numbering) of a plane through the reorder kernel
+        (wr_dev_plane_reorder_list).  The destination first receives `fill` (uint8, nz*ny*nx bytes; None: zeros) and is
+        returned: outside the listed bricks it still holds it."""
+        nz, ny, nx = shape
+        p = np.ascontiguousarray(plane, dtype=np.uint8).ravel()
+        f = np.zeros(p.size, dtype=np.uint8) if fill is None else np.ascontiguousarray(fill, dtype=np.uint8).ravel()
+        assert p.size == f.size == nx * ny * nz
+        v = np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+        d_src, d_dst = self.to_device(p), self.to_device(f)
+        try:
+            _check(lib().wr_dev_plane_reorder_list(self.h, d_dst.ptr, d_src.ptr, nx, ny, nz, wlev, brick, int(bool(inverse)),
+                                                   v.ctypes.data if v.size else None, v.size))
             return d_dst.download(np.uint8, p.size)
         finally:
             d_src.free()

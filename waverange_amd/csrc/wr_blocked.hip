@@ -102,8 +102,8 @@ bool plane_reorder(const PlaneRef& nat, uint8_t* blk, const wrblk::Order& od, bo
     memset(&m, 0, sizeof m);
     m.nbox = od.nbox;
     m.nx = (uint32_t)od.nx; m.ny = (uint32_t)od.ny; m.brick = od.B;
-    m.group = list || od.B >= 128 ? 1 : 128 / od.B;
-    bool aligned = od.B >= 16 && od.nx % 16 == 0 && ((uintptr_t)blk & 15) == 0 && nat.shift >= 12;
+    m.group = reorder_group(od.B, list);
+    bool aligned = ((uintptr_t)blk & 15) == 0 && nat.shift >= 12;
     for (int k = 0; k < kPlaneChunks; k++) aligned = aligned && ((uintptr_t)nat.chunk[k] & 15) == 0;
     uint64_t first = 0;
     for (int i = 0; i < od.nbox; i++) {
@@ -112,9 +112,9 @@ bool plane_reorder(const PlaneRef& nat, uint8_t* blk, const wrblk::Order& od, bo
         r.ox = (uint32_t)b.o[0]; r.oy = (uint32_t)b.o[1]; r.oz = (uint32_t)b.o[2];
         r.ex = (uint32_t)b.e[0]; r.ey = (uint32_t)b.e[1]; r.ez = (uint32_t)b.e[2];
         r.first = (uint32_t)first;
-        r.wide = aligned && b.o[0] % 16 == 0 && b.e[0] % 16 == 0 && b.start % 16 == 0;
+        r.wide = reorder_box_wide(aligned, od, b);
         r.start = b.start;
-        first += (uint64_t)((b.t[0] + m.group - 1) / m.group) * b.t[1] * b.t[2];
+        first += reorder_box_items(b, m.group);
     }
     if (first > 0x7fffffffu || nlist > 0x7fffffffu) return false;  // more work items than a grid has blocks: nothing is launched
     m.items = (uint32_t)first;

@@ -2987,6 +2987,71 @@ int wr_dev_plane_reorder(wr_ctx* c, unsigned char* d_dst, const unsigned char* d
     return WR_OK;
 }
 
+int wr_dev_plane_reorder_list(wr_ctx* c, unsigned char* d_dst, const unsigned char* d_src, int nx, int ny, int nz, int wlev, unsigned brick, int inverse,
+                              const uint32_t* ids, size_t nlist)
+{
+    if (!brick) brick = WR_BRICK_DEFAULT;
+    if (int rc = seg_format_params(nullptr, brick, 0)) return rc;
+    if (wlev != 0 && wlev != kWavLvl) return fail(WR_ERR_ARG, "wlev must be 0 or 4");
+    if (int rc = ctx_bind(c)) return rc;
+    if (int rc = check_dims(nx, ny, nz, d_dst)) return rc;
+    if (!d_dst || !d_src || d_dst == d_src) return fail(WR_ERR_ARG, "null pointer, or source and destination are the same");
+    if (((uintptr_t)d_src | (uintptr_t)d_dst) & 15) return fail(WR_ERR_ARG, "plane buffers must be 16-byte aligned");
+    if (nlist && !ids) return fail(WR_ERR_ARG, "null brick list");
+    const wrblk::Order od = wrblk::order_of(nx, ny, nz, wlev, brick);
+    if (od.nbricks > 0x7fffffffu || nlist > od.nbricks) return fail(WR_ERR_ARG, "too many bricks");
+    for (size_t k = 0; k < nlist; k++)
+        if (ids[k] >= od.nbricks || (k && ids[k] <= ids[k - 1])) return fail(WR_ERR_ARG, "brick ids must be strictly ascending and below the plane's number of bricks");
+    if (!nlist) return WR_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    uint32_t* d_ids = nullptr;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&d_ids), nlist * sizeof(uint32_t)));
+    StageLock cu(c->pool->cu_mu);
+    hipError_t e = hipMemcpy(d_ids, ids, nlist * sizeof(uint32_t), hipMemcpyHostToDevice);
+    bool ok = true;
+    if (e == hipSuccess) {
+        ok = inverse ? wrk::plane_reorder(wrk::plane_ref(d_dst), const_cast<unsigned char*>(d_src), od, true, d_ids, nlist, c->stream)
+                     : wrk::plane_reorder(wrk::plane_ref(d_src), d_dst, od, false, d_ids, nlist, c->stream);
+        if (ok) e = hipGetLastError();
+        if (ok && e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    (void)hipFree(d_ids);
+    if (!ok) return fail(WR_ERR_ARG, "too many bricks");
+    HIPCHK(e);
+    return WR_OK;
+}
+
+int wr_reorder_plan(int nx, int ny, int nz, int wlev, unsigned brick, int list, wr_reorder_plan_t* out)
+{
+    if (!out) return fail(WR_ERR_ARG, "wr_reorder_plan: out is NULL");
+    if (!brick) brick = WR_BRICK_DEFAULT;
+    if (int rc = seg_format_params(nullptr, brick, 0)) return rc;
+    if (wlev != 0 && wlev != kWavLvl) return fail(WR_ERR_ARG, "wlev must be 0 or 4");
+    if (int rc = check_dims(nx, ny, nz, nullptr)) return rc;
+    const wrblk::Order od = wrblk::order_of(nx, ny, nz, wlev, brick);
+    const uint32_t group = wrk::reorder_group(od.B, list != 0);
+    uint64_t first = 0;
+    for (int i = 0; i < od.nbox; i++) first += wrk::reorder_box_items(od.box[i], group);
+    if (first > 0x7fffffffu || od.nbricks > 0x7fffffffu) return fail(WR_ERR_ARG, "too many bricks");
+    memset(out, 0, sizeof *out);
+    out->group = (int)group;
+    out->items = (uint32_t)first;
+    out->nbricks = (uint32_t)od.nbricks;
+    out->nbox = od.nbox;
+    first = 0;
+    for (int i = 0; i < od.nbox; i++) {
+        const wrblk::Box& b = od.box[i];
+        auto& o = out->box[i];
+        for (int k = 0; k < 3; k++) { o.origin[k] = b.o[k]; o.extent[k] = b.e[k]; o.bricks[k] = (int)b.t[k]; }
+        o.first = (uint32_t)first;
+        o.first_brick = (uint32_t)b.first_brick;
+        o.start = b.start;
+        o.wide = wrk::reorder_box_wide(true, od, b);
+        first += wrk::reorder_box_items(b, group);
+    }
+    return WR_OK;
+}
+
 int wr_decode_host_seg_lowres(wr_ctx* c, double* h_out, int nx, int ny, int nz, int level, int max_planes, const wr_enc_info* info,
                               const unsigned char* data_enc, size_t data_len, wr_timings* tm)
 {

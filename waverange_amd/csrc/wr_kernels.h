@@ -8,7 +8,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-namespace wrblk { struct Order; }
+#include "wr_blocked.h"
 
 namespace wrk {
 
@@ -264,6 +264,17 @@ struct ReorderMap {
     uint32_t nx, ny, brick, group, items;  // group: bricks along x per work item
     ReorderBox box[kReorderBoxes];
 };
+// Bricks along x per work item: a row of the group is 128 bytes of the natural plane; with a list an item is one brick.
+inline uint32_t reorder_group(uint32_t B, bool list) { return list || B >= 128 ? 1 : 128 / B; }
+inline uint64_t reorder_box_items(const wrblk::Box& b, uint32_t group) { return (uint64_t)((b.t[0] + group - 1) / group) * b.t[1] * b.t[2]; }
+// Whether k_plane_reorder moves box b of the order 16 bytes per lane or byte by byte: B >= 16, and the box's origin and extent in
+// x, nx and the box's start in the stream are multiples of 16 (then every brick offset is one too).  `aligned`: both arrays
+// are 16-byte aligned and every plane chunk a multiple of 4096 bytes long, which the library's own planes always are.  Host
+// only; plane_reorder and wr_reorder_plan both decide here.
+inline bool reorder_box_wide(bool aligned, const wrblk::Order& od, const wrblk::Box& b)
+{
+    return aligned && od.B >= 16 && od.nx % 16 == 0 && b.o[0] % 16 == 0 && b.e[0] % 16 == 0 && b.start % 16 == 0;
+}
 // false: the plane has more work items than a grid has blocks, nothing was launched.
 bool plane_reorder(const PlaneRef& nat, uint8_t* blk, const wrblk::Order& od, bool inverse, const uint32_t* ids, size_t nlist, hipStream_t st);
 
