@@ -589,13 +589,48 @@ int encode_stage_end(wr_ctx* c, int rc, const FieldRef& fld, const double* resid
     return rc;
 }
 
+// Where the host coder of a plane writes (an encode into the reference's format; a transcode into it).  The reference codes
+// every plane into a buffer of its own and copies the streams together (wrappers.cpp:412-427); here the planes are coded at the
+// same time, so a plane's place in `out` is not known when its coder starts -- but an upper bound on the length of every plane
+// before it is, from their block histograms (wrrc::encode_bound_hist: rigorous, ~0.2 % above the stream).  Plane l is coded
+// straight into `out` at the sum of the bounds of planes 0 .. l-1, and the gaps are closed afterwards by moving the planes down
+// in order (a few megabytes each: ref_stream_tail).  The coded bytes of a field then exist once in host memory, not twice (a
+// 1e-7 field at 1024^3: 2 GB), and the context keeps no per-plane output buffers.  A plane whose bound does not fit under `cap`
+// takes the old way through c->enc_buf (only then can total <= cap < sum of bounds happen).  The coder is told the bound
+// (dst_limit): a stream that outgrows it was coded against histograms that are not its plane's and is given up, at most one
+// block (wrrc::kFailedBlockSlack) late -- which is why that much room lies behind every plane's place.
+struct RefPlacement {
+    size_t est_off[WR_NLAYMAX + 1] = {0}, est_len[WR_NLAYMAX] = {0};
+    bool direct[WR_NLAYMAX] = {false};
+
+    // Places plane j, the planes before it being placed: hist: its block histograms on the host (nullptr: they did not
+    // arrive, the bound is that of any plane of n symbols).  *dst = where its coder writes, nullptr if there is no host memory.
+    int place(wr_ctx* c, unsigned j, const uint16_t* hist, size_t n, unsigned char* out, size_t cap, uint8_t** dst)
+    {
+        *dst = nullptr;
+        est_len[j] = hist ? wrrc::encode_bound_hist(hist, n) : wrrc::encode_bound(n);
+        est_off[j + 1] = est_off[j] + est_len[j];
+        direct[j] = out && est_off[j + 1] + wrrc::kFailedBlockSlack <= cap;
+        if (!direct[j]) if (int rc = ensure_enc_buf(c, (int)j, est_len[j] + wrrc::kFailedBlockSlack)) return rc;
+        *dst = direct[j] ? out + est_off[j] : c->enc_buf[j];
+        return WR_OK;
+    }
+};
+
+// what coding plane l to dst, its place (RefPlacement::place), means to whoever codes it
+void ref_encode_job(wr_ctx* c, unsigned l, size_t n, const uint16_t* hist, const RefPlacement& pl, uint8_t* dst, wrrc::PlaneJob* j)
+{
+    j->kind = wrrc::PlaneJob::kEncode;
+    j->io = &c->ps[l].io; j->dst = dst; j->n = n; j->hist = hist; j->dst_limit = pl.est_len[l];
+}
+
 // The tail of an encode into the reference's format, once every plane's coder has returned: jobs[l] coded plane l to where it
-// was placed -- direct[l]: at out + est_off[l], the sum of the histogram bounds est_len of the planes before it; otherwise into
-// c->enc_buf[l].  Checks every plane (download_failed(l): its symbols did not reach the coder), gives lens[l] and *total,
-// closes the gaps in `out` and hands the pages of the context's buffers back.  too_large: the text of total > cap.
+// was placed -- pl.direct[l]: at out + pl.est_off[l]; otherwise into c->enc_buf[l].  Checks every plane (download_failed(l): its
+// symbols did not reach the coder), gives lens[l] and *total, closes the gaps in `out` and hands the pages of the context's
+// buffers back.  too_large: the text of total > cap.
 template <class Failed>
-int ref_stream_tail(wr_ctx* c, const wrrc::PlaneJob* jobs, unsigned nlay, Failed download_failed, const size_t* est_off, const size_t* est_len, const bool* direct,
-                    unsigned char* out, size_t cap, const char* too_large, size_t* lens, size_t* total)
+int ref_stream_tail(wr_ctx* c, const wrrc::PlaneJob* jobs, unsigned nlay, Failed download_failed, const RefPlacement& pl, unsigned char* out, size_t cap,
+                    const char* too_large, size_t* lens, size_t* total)
 {
     for (unsigned l = 0; l < nlay; l++) {
         if (download_failed(l)) return fail(WR_ERR_HIP, "download of plane " + std::to_string(l) + " failed");
@@ -611,21 +646,167 @@ int ref_stream_tail(wr_ctx* c, const wrrc::PlaneJob* jobs, unsigned nlay, Failed
         lens[l] = jobs[l].result;
     }
     for (unsigned l = 0; l < nlay; l++)  // (cannot happen: the bound is rigorous; if it did, a neighbour's bytes are gone)
-        if (jobs[l].result > est_len[l]) return fail(WR_ERR_OVERFLOW, "internal: plane " + std::to_string(l) + " outgrew the bound computed from its histograms");
+        if (jobs[l].result > pl.est_len[l]) return fail(WR_ERR_OVERFLOW, "internal: plane " + std::to_string(l) + " outgrew the bound computed from its histograms");
     if (*total > cap) return fail(WR_ERR_OVERFLOW, too_large);
     // close the gaps: plane l moves down by what the planes before it stayed below their bounds.  In plane order, one after
     // the other: plane l's new place may still hold the end of plane l-1's old one.
     for (unsigned l = 0; l < nlay; l++) {
-        if (!direct[l]) memcpy(out + offs[l], c->enc_buf[l], lens[l]);
-        else if (est_off[l] != offs[l]) memmove(out + offs[l], out + est_off[l], lens[l]);
+        if (!pl.direct[l]) memcpy(out + offs[l], c->enc_buf[l], lens[l]);
+        else if (pl.est_off[l] != offs[l]) memmove(out + offs[l], out + pl.est_off[l], lens[l]);
     }
     // (a plane that went through c->enc_buf: hand its pages back, a noise plane's gigabyte would otherwise stay resident in
     // every context that once coded one)
     for (unsigned l = 0; l < nlay; l++) {
-        if (direct[l]) continue;
+        if (pl.direct[l]) continue;
         const uintptr_t a = ((uintptr_t)c->enc_buf[l] + 4095) & ~(uintptr_t)4095, e = ((uintptr_t)c->enc_buf[l] + lens[l]) & ~(uintptr_t)4095;
         if (e > a && e - a >= ((size_t)64 << 20)) (void)madvise(reinterpret_cast<void*>(a), e - a, MADV_DONTNEED);
     }
+    return WR_OK;
+}
+
+// plane_coder_s[l] += the seconds jobs[l]'s coder took; returns the slowest plane's, which is what the call waited for (the
+// planes are coded at the same time)
+double fold_plane_seconds(const wrrc::PlaneJob* jobs, int count, wr_timings* tm)
+{
+    double slowest = 0;
+    for (int l = 0; l < count; l++) {
+        tm->plane_coder_s[l] += jobs[l].seconds;
+        slowest = std::max(slowest, jobs[l].seconds);
+    }
+    return slowest;
+}
+
+// Hands jobs[0, count), every one of them ready, to whoever codes them, and returns when all are done: the process-wide coder
+// pool (wr_set_coder_pool), whose workers interleave planes of several fields -- or, without a pool or with one that was stopped
+// meanwhile, min(count, threads) threads of this call, each with its contiguous group of planes interleaved (wr_set_threads;
+// one plane each by default).  gate != nullptr: the admission-gate lock of a decode (ref_decode_planes), released once the jobs
+// are queued, and on every other way out.  who ("decode: "): in front of the text of a thread that cannot start.
+int run_plane_jobs(wrrc::PlaneJob* jobs, int count, int threads, int dev, std::unique_lock<std::mutex>* gate, const char* who)
+{
+    bool pooled = wrrc::pool_threads() > 0;
+    if (pooled) {
+        wrrc::JobBatch batch;
+        pooled = wrrc::pool_submit(jobs, count, &batch);
+        if (gate && gate->owns_lock()) gate->unlock();  // the next decode may look at the queues now
+        if (pooled) wrrc::pool_wait(&batch);
+    }
+    if (gate && gate->owns_lock()) gate->unlock();
+    if (pooled) return WR_OK;
+    const int groups = std::min(count, threads);
+    try {
+        Workers workers;  // (joined on every way out of the block)
+        for (int g = 0; g < groups; g++)
+            workers.v.emplace_back([=]() {
+                (void)hipSetDevice(dev);
+                const int l0 = g * count / groups, l1 = (g + 1) * count / groups;
+                wrrc::run_jobs(jobs + l0, l1 - l0);
+            });
+    } catch (const std::exception& e) {
+        return fail(WR_ERR_ARG, std::string(who) + e.what());
+    }
+    return WR_OK;
+}
+
+// admission gate of the pooled decoder (ref_decode_planes): queued jobs of a kind at which a further decode waits
+constexpr int kGateScalarJobs = 3, kGateVectorJobs = 6;
+
+// The host half of a decode from the reference's format: plane l of the stream (`data` + off[l], info->len_enc_vec[l] bytes) is
+// range-decoded into the context's device plane l, every decoded window going up while the decoder fills the next one
+// (chunk by chunk: wrappers.cpp:492-516 reorganised); no field buffer and no slot is needed.  tm receives
+// plane_coder_s, the slowest plane's seconds (added to rangecoder) and the uploads (h2d_ms).  Of several planes that do not
+// decode, the first is named.
+int ref_decode_planes(wr_ctx* c, const wr_enc_info* info, int nlay, size_t n, const unsigned char* data, const size_t* off, const char* who, wr_timings* tm)
+{
+    if (verbose()) printf("Range decoding...\n");
+    DevPool* const pool = c->pool;
+    // Admission to the coder pool.  A decoder's planes take device memory from the moment they are prepared, and with every
+    // session of the pool full a decode's jobs sat in the queues for seconds (4 of a decode's 15 s at 32 lanes) -- a third of
+    // the decoders' plane memory was held by planes nobody was writing yet, and plane memory is what bounds the fields in
+    // flight.  So a decode waits HERE, holding nothing, until the queues of its kind are short (a free lane of a session is
+    // refilled at the next block boundary, half a millisecond away: a couple of queued jobs keep every session topped up),
+    // and only then prepares its planes and submits: the same wait, without the memory.  One decode at a time passes, from
+    // the look at the queues to the submit (else all that wait would pass together).
+    std::unique_lock<std::mutex> gate(pool->planes.gate_mu, std::defer_lock);
+    if (wrrc::pool_threads() > 0) {
+        gate.lock();
+        const double t_gate = now();
+        for (;;) {
+            int qs = 0, qv = 0;
+            wrrc::pool_queued_decode(&qs, &qv);
+            if ((qs < kGateScalarJobs && qv < kGateVectorJobs) || now() - t_gate > 120.0) break;
+            std::this_thread::sleep_for(std::chrono::milliseconds(2));
+        }
+        g_stat[WR_STAT_DECODE_GATE_MS] += (unsigned long)((now() - t_gate) * 1e3);
+    }
+    {
+        // one decode at a time gathers its planes: a decoder keeps them all until its field is done, so two that each hold
+        // half of theirs and wait for the other half would never finish
+        const double t_turn = now();
+        std::lock_guard<std::mutex> gather(pool->planes.gather_mu);
+        const double t_got = now();
+        if (t_got - t_turn > 1e-3) g_stat[WR_STAT_PLANE_WAIT_MS] += (unsigned long)((t_got - t_turn) * 1e3);
+        for (int l = 0; l < nlay; l++) if (int rc = plane_prepare(c, l, n, true)) return rc;
+    }
+    wrrc::PlaneJob jobs[WR_NLAYMAX];  // what decoding plane l means, whoever decodes it
+    for (int l = 0; l < nlay; l++) {
+        jobs[l].kind = wrrc::PlaneJob::kDecode;
+        jobs[l].src = data + off[l]; jobs[l].src_len = info->len_enc_vec[l]; jobs[l].io = &c->ps[l].io; jobs[l].n = n;
+    }
+    if (int rc = run_plane_jobs(jobs, nlay, coder_threads(), c->device, &gate, who)) return rc;
+    for (int l = 0; l < nlay; l++)
+        if (jobs[l].result != n) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": stream does not decode to nx*ny*nz symbols");
+    tm->rangecoder += fold_plane_seconds(jobs, nlay, tm);
+    for (int l = 0; l < nlay; l++) {
+        if (c->ps[l].err) return fail(WR_ERR_HIP, "upload of plane " + std::to_string(l) + " failed");
+        tm->h2d_ms += (float)c->ps[l].copy_ms;
+    }
+    return WR_OK;
+}
+
+// ---- the tail that every decode driver takes, whatever filled the planes ----------------------------------------------------
+// the end of a driver's kernel stage (cu_mu held): rc is the finisher's
+int kernel_stage_end(wr_ctx* c, int rc)
+{
+    if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the decoder's kernel stage failed on the device" + launch_describe(c));
+    c->pool->last_stage_end.store(now());
+    return rc;
+}
+
+// stage "down": `count` elements from where the finisher left them (d_f64, or d_f32 for an fp32 caller) to a host caller
+int result_down(wr_ctx* c, const FieldRef& fld, const void* d_f64, const void* d_f32, size_t count, wr_timings* local)
+{
+    if (fld.host) {
+        if (int rc = xfer_field(c, &c->x_field, fld.host, d_f64, count * sizeof(double), kDown)) return rc;
+        local->d2h_ms = (float)c->x_field.ms;
+    } else if (fld.host_f32) {
+        if (int rc = xfer_field(c, &c->x_field, fld.host_f32, d_f32, count * sizeof(float), kDown)) return rc;
+        local->d2h_ms = (float)c->x_field.ms;
+    }
+    return WR_OK;
+}
+
+// quant_ms and transform_ms of a finisher that ran once: its ev_a / ev_b / ev_c
+int finisher_ms(wr_ctx* c, wr_timings* local)
+{
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev_a, c->ev_b)); local->quant_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev_b, c->ev_c)); local->transform_ms = ms;
+    return WR_OK;
+}
+
+// The tail of a segmented decode call: the result to a host caller, then the call's timings.  events: quant_ms and transform_ms
+// are the finisher's events (a finisher that ran more than once has summed them itself).
+int finish_call(wr_ctx* c, const FieldRef& fld, const void* d_f64, const void* d_f32, size_t count, bool events, double t0, double t_coded, double t_phase,
+                wr_timings* local, wr_timings* tm)
+{
+    if (int rc = result_down(c, fld, d_f64, d_f32, count, local)) return rc;
+    if (events) if (int rc = finisher_ms(c, local)) return rc;
+    local->total = now() - t0;
+    local->gpu = now() - t_phase;
+    local->wait = t_phase - t_coded;
+    local->transfer = t_coded - t0;
+    if (tm) *tm = *local;
     return WR_OK;
 }
 
@@ -664,31 +845,18 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
     const bool per_plane = !pooled && encoder_threads() >= WR_NLAYMAX;
     wrrc::PlaneJob jobs[WR_NLAYMAX];  // what coding plane l means, whoever codes it
     wrrc::JobBatch batch;
-    // Where a plane's coder writes.  The reference codes every plane into a buffer of its own and copies the streams
-    // together (wrappers.cpp:412-427); here the planes are coded at the same time, so a plane's place in data_enc is not
-    // known when its coder starts -- but an upper bound on the length of every plane before it is, from their block
-    // histograms (wrrc::encode_bound_hist: rigorous, ~0.2 % above the stream).  Plane l is coded straight into data_enc at
-    // the sum of the bounds of planes 0 .. l-1, and the gaps are closed afterwards by moving the planes down in order (a few
-    // megabytes each).  The coded bytes of a field then exist once in host memory, not twice (a 1e-7 field at 1024^3: 2 GB),
-    // and the context keeps no per-plane output buffers.  A plane whose bound does not fit under `cap` takes the old way
-    // through c->enc_buf (only then can total <= cap < sum of bounds happen).  The coder is told the bound (dst_limit): a
-    // stream that outgrows it was coded against histograms that are not its plane's and is given up, at most one block
-    // (wrrc::kFailedBlockSlack) late -- which is why that much room lies behind every plane's place.
+    // Where a plane's coder writes (RefPlacement): the planes are placed in plane order, as their histograms arrive.
     std::mutex place_mu;
     unsigned placed = 0;
-    size_t est_off[WR_NLAYMAX + 1] = {0}, est_len[WR_NLAYMAX] = {0};
+    RefPlacement placement;
     uint8_t* plane_out[WR_NLAYMAX] = {nullptr};
-    bool direct[WR_NLAYMAX] = {false};
+    auto hist_of = [&](unsigned l) { return c->h_hist + l * hist_per_plane; };
     // (callable from the coder threads: the histograms of plane k and of the planes before it have been sent off)
     auto place_plane = [&](unsigned k) -> uint8_t* {
         std::lock_guard<std::mutex> lk(place_mu);
         for (unsigned j = placed; j <= k; j++) {
             if (xfer_wait(&c->x_plane[j]) != WR_OK) copy_failed[j] = 1;
-            est_len[j] = copy_failed[j] ? wrrc::encode_bound(n) : wrrc::encode_bound_hist(c->h_hist + j * hist_per_plane, n);
-            est_off[j + 1] = est_off[j] + est_len[j];
-            direct[j] = data_enc && est_off[j + 1] + wrrc::kFailedBlockSlack <= cap;
-            if (direct[j]) plane_out[j] = data_enc + est_off[j];
-            else plane_out[j] = ensure_enc_buf(c, (int)j, est_len[j] + wrrc::kFailedBlockSlack) == WR_OK ? c->enc_buf[j] : nullptr;
+            (void)placement.place(c, j, copy_failed[j] ? nullptr : hist_of(j), n, data_enc, cap, &plane_out[j]);  // (refused: the plane is not coded)
             placed = j + 1;
         }
         return plane_out[k];
@@ -698,9 +866,7 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
         if (xfer_wait(&c->x_plane[k]) != WR_OK) copy_failed[k] = 1;
         uint8_t* const dst = place_plane(k);
         if (!dst || copy_failed[k]) { copy_failed[k] = 1; return false; }
-        wrrc::PlaneJob& j = jobs[k];
-        j.kind = wrrc::PlaneJob::kEncode;
-        j.io = &c->ps[k].io; j.dst = dst; j.n = n; j.hist = c->h_hist + k * hist_per_plane; j.dst_limit = est_len[k];
+        ref_encode_job(c, k, n, hist_of(k), placement, dst, &jobs[k]);
         return true;
     };
     // a thread of this call codes planes l0 .. l1-1 (prepare: their jobs are not built yet)
@@ -829,13 +995,12 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
     if (rc) return rc;
     const double t_coded = now();
     size_t total = 0;
-    if (int r = ref_stream_tail(c, jobs, info->nlay, [&](unsigned l) { return copy_failed[l] || c->ps[l].err; }, est_off, est_len, direct, data_enc, cap,
-                                wrtc::kTooLarge, info->len_enc_vec, &total))
+    if (int r = ref_stream_tail(c, jobs, info->nlay, [&](unsigned l) { return copy_failed[l] || c->ps[l].err; }, placement, data_enc, cap, wrtc::kTooLarge,
+                                info->len_enc_vec, &total))
         return r;
+    local.rangecoder = fold_plane_seconds(jobs, (int)info->nlay, &local);
     for (unsigned l = 0; l < info->nlay; l++) {
         local.d2h_ms += (float)(c->x_plane[l].ms + c->ps[l].copy_ms);
-        local.plane_coder_s[l] = jobs[l].seconds;
-        if (jobs[l].seconds > local.rangecoder) local.rangecoder = jobs[l].seconds;  // (the planes are coded at the same time)
         if (verbose()) fputs(plane_log(c, (int)l, n, info, true, jobs[l].result).c_str(), stdout);  // wrappers.cpp:401-409, 430
     }
     info->ntot_enc = total;
@@ -852,8 +1017,6 @@ int encode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, con
 // buffer: no field buffer and no slot needed, wr_decode_begin); or only its device half on planes decoded before
 // (wr_decode_finish_*)
 enum DecodeMode { kDecodeWhole, kDecodeBegin, kDecodeFinish };
-// admission gate of the pooled decoder (decode_impl): queued jobs of a kind at which a further decode waits
-constexpr int kGateScalarJobs = 3, kGateVectorJobs = 6;
 
 int decode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc,
                 size_t data_len, wr_timings* tm, DecodeMode mode = kDecodeWhole)
@@ -891,141 +1054,53 @@ int decode_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_in
     if (nlay < 1 || nlay > WR_NLAYMAX) return fail(WR_ERR_ARG, "nlay out of range");
     if (info->wlev != 0 && info->wlev != kWavLvl) return fail(WR_ERR_ARG, "wlev must be 0 or 4");
     const bool host_half = mode != kDecodeFinish, device_half = mode != kDecodeBegin;
-    if (host_half && verbose()) printf("Range decoding...\n");
     size_t off[WR_NLAYMAX + 1] = {0};
     if (int rc = plane_offsets(info, nlay, host_half ? data_len : 0, off)) return rc;
-
-    // Admission to the coder pool.  A decoder's planes take device memory from the moment they are prepared, and with every
-    // session of the pool full a decode's jobs sat in the queues for seconds (4 of a decode's 15 s at 32 lanes) -- a third of
-    // the decoders' plane memory was held by planes nobody was writing yet, and plane memory is what bounds the fields in
-    // flight.  So a decode waits HERE, holding nothing, until the queues of its kind are short (a free lane of a session is
-    // refilled at the next block boundary, half a millisecond away: a couple of queued jobs keep every session topped up),
-    // and only then prepares its planes and submits: the same wait, without the memory.  One decode at a time passes, from
-    // the look at the queues to the submit (else all that wait would pass together).
-    std::unique_lock<std::mutex> gate(pool->planes.gate_mu, std::defer_lock);
-    if (host_half && wrrc::pool_threads() > 0) {
-        gate.lock();
-        const double t_gate = now();
-        for (;;) {
-            int qs = 0, qv = 0;
-            wrrc::pool_queued_decode(&qs, &qv);
-            if ((qs < kGateScalarJobs && qv < kGateVectorJobs) || now() - t_gate > 120.0) break;
-            std::this_thread::sleep_for(std::chrono::milliseconds(2));
-        }
-        g_stat[WR_STAT_DECODE_GATE_MS] += (unsigned long)((now() - t_gate) * 1e3);
-    }
+    double t_coded = t0;
     if (host_half) {
         c->pend_valid = false;  // whatever an earlier begin parked here is overwritten now
-        // one decode at a time gathers its planes: a decoder keeps them all until its field is done, so two that each hold
-        // half of theirs and wait for the other half would never finish
-        const double t_turn = now();
-        std::lock_guard<std::mutex> gather(pool->planes.gather_mu);
-        const double t_got = now();
-        if (t_got - t_turn > 1e-3) g_stat[WR_STAT_PLANE_WAIT_MS] += (unsigned long)((t_got - t_turn) * 1e3);
-        for (int l = 0; l < nlay; l++) if (int rc = plane_prepare(c, l, n, true)) return rc;
+        g_stat[WR_STAT_EARLY_DECODES]++;
+        if (int rc = ref_decode_planes(c, info, nlay, n, data_enc, off, "decode: ", &local)) return rc;
+        t_coded = now();
+        local.transfer = (t_coded - t0) - local.rangecoder;
+        if (local.transfer < 0) local.transfer = 0;
     }
     for (int l = 0; l < nlay; l++)
         if (!c->ps[l].dev || c->ps[l].n != n) return fail(WR_ERR_ARG, "wr_decode_finish: the planes of the begin are gone");
-
+    if (!device_half) {  // the planes wait in the context's device buffers for wr_decode_finish_*
+        local.total = now() - t0;
+        c->pend_tm = local;
+        c->pend_valid = true;
+        planes.keep = true;
+        if (tm) *tm = local;
+        return WR_OK;
+    }
+    if (host_half && verbose()) {  // wrappers.cpp:489, 503-510
+        for (int l = 0; l < nlay; l++) fputs(plane_log(c, l, n, info, false, 0).c_str(), stdout);
+        printf("Wavelet reconstruction...\n");
+    }
+    // the accumulate kernel consumes the planes in plane order; they are on the device already: no "up" stage
     SlotNeed need;
     transform_need(nx, ny, nz, info->wlev ? -kWavLvl : 0, &need);
     if (fld.host || fld.host_f32) need.field_elems = n;
-
-    wrrc::PlaneJob jobs[WR_NLAYMAX];  // what decoding plane l means, whoever decodes it
-    for (int l = 0; l < nlay && host_half; l++) {
-        jobs[l].kind = wrrc::PlaneJob::kDecode;
-        jobs[l].src = data_enc + off[l]; jobs[l].src_len = info->len_enc_vec[l]; jobs[l].io = &c->ps[l].io; jobs[l].n = n;
-    }
-    Sem sem(coder_threads());
-    // one thread per plane, or (wr_set_threads) fewer threads with their planes interleaved, or the process-wide
-    // coder pool (wr_set_coder_pool), whose workers interleave planes of several fields
-    bool pooled = wrrc::pool_threads() > 0;
+    SlotLease slot;
+    if (int rc = slot.acquire(c, need)) return rc;
+    const double t_phase = now();
+    wrk::DequantParams p;
+    if (int rc = dequant_params(info, nlay, n, [&](int l) { return c->ps[l].ref; }, &p)) return rc;
+    launch_note(c, "dequant", nlay - 1, fld.dev ? (void*)fld.dev : (void*)slot->field, n, nullptr, p.q[nlay - 1]);
+    double* d_fld = fld.dev ? fld.dev : slot->field;
+    float* d_f32 = nullptr;  // fp32: where inverse_from_planes leaves the narrowed reconstruction
     int rc = WR_OK;
-    double t_phase = 0, t_coded = t0;
-    try {
-        SlotLease slot;
-        if (pooled && host_half) {
-            wrrc::JobBatch batch;
-            const bool queued = wrrc::pool_submit(jobs, nlay, &batch);
-            if (gate.owns_lock()) gate.unlock();  // the next decode may look at the queues now
-            if (queued) wrrc::pool_wait(&batch);
-            else pooled = false;  // the pool was stopped meanwhile: this call's own threads decode the planes
-        }
-        if (gate.owns_lock()) gate.unlock();
-        const int groups = (pooled || !host_half) ? 0 : std::min(nlay, coder_threads());
-        // Every decoded window of a plane goes to the plane's device buffer while the decoder fills the next one
-        // (chunk by chunk: wrappers.cpp:492-516 reorganised); the accumulate kernel consumes the
-        // planes in plane order afterwards.
-        if (host_half) g_stat[WR_STAT_EARLY_DECODES]++;
-        {
-            Workers workers;
-            for (int g = 0; g < groups; g++)
-                workers.v.emplace_back([&, g]() {
-                    const int l0 = g * nlay / groups, l1 = (g + 1) * nlay / groups;
-                    sem.acquire();
-                    wrrc::run_jobs(jobs + l0, l1 - l0);
-                    sem.release();
-                });
-        }
-        int bad = -1;
-        for (int l = 0; l < nlay && host_half; l++) {
-            if (jobs[l].result != n) bad = l;
-            local.plane_coder_s[l] = jobs[l].seconds;
-            if (jobs[l].seconds > local.rangecoder) local.rangecoder = jobs[l].seconds;
-        }
-        if (bad >= 0) return fail(WR_ERR_STREAM, "plane " + std::to_string(bad) + ": stream does not decode to nx*ny*nz symbols");
-        if (host_half) {
-            for (int l = 0; l < nlay; l++) {
-                if (c->ps[l].err) return fail(WR_ERR_HIP, "upload of plane " + std::to_string(l) + " failed");
-                local.h2d_ms += (float)c->ps[l].copy_ms;
-            }
-            t_coded = now();
-            local.transfer = (t_coded - t0) - local.rangecoder;
-            if (local.transfer < 0) local.transfer = 0;
-        }
-        if (!device_half) {  // the planes wait in the context's device buffers for wr_decode_finish_*
-            local.total = now() - t0;
-            c->pend_tm = local;
-            c->pend_valid = true;
-            planes.keep = true;
-            if (tm) *tm = local;
-            return WR_OK;
-        }
-        if (host_half && verbose()) {  // wrappers.cpp:489, 503-510
-            for (int l = 0; l < nlay; l++) fputs(plane_log(c, l, n, info, false, 0).c_str(), stdout);
-            printf("Wavelet reconstruction...\n");
-        }
-        if ((rc = slot.acquire(c, need)) != WR_OK) return rc;  // the planes are on the device already: no "up" stage
-        t_phase = now();
-        wrk::DequantParams p;
-        if ((rc = dequant_params(info, nlay, n, [&](int l) { return c->ps[l].ref; }, &p)) != WR_OK) return rc;
-        launch_note(c, "dequant", nlay - 1, fld.dev ? (void*)fld.dev : (void*)slot->field, n, nullptr, p.q[nlay - 1]);
-        double* d_fld = fld.dev ? fld.dev : slot->field;
-        float* d_f32 = nullptr;  // fp32: where inverse_from_planes leaves the narrowed reconstruction
-        {
-            // ---- stage "kernels"
-            StageLock cu(pool->cu_mu);
-            clock_warmup(c, n);
-            rc = inverse_from_planes(c, slot.get(), d_fld, nx, ny, nz, (int)info->wlev, p, fld.host_f32 ? &d_f32 : nullptr);
-            if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
-            if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the decoder's kernel stage failed on the device" + launch_describe(c));
-            pool->last_stage_end.store(now());
-        }
-        if (rc) return rc;
-        if (fld.host) {
-            // ---- stage "down": the reconstructed field, device -> host
-            if ((rc = xfer_field(c, &c->x_field, fld.host, d_fld, n * sizeof(double), kDown)) != WR_OK) return rc;
-            local.d2h_ms = (float)c->x_field.ms;
-        } else if (fld.host_f32) {
-            if ((rc = xfer_field(c, &c->x_field, fld.host_f32, d_f32, n * sizeof(float), kDown)) != WR_OK) return rc;
-            local.d2h_ms = (float)c->x_field.ms;
-        }
-    } catch (const std::exception& e) {
-        return fail(WR_ERR_ARG, std::string("decode: ") + e.what());
+    {
+        // ---- stage "kernels"
+        StageLock cu(pool->cu_mu);
+        clock_warmup(c, n);
+        rc = kernel_stage_end(c, inverse_from_planes(c, slot.get(), d_fld, nx, ny, nz, (int)info->wlev, p, fld.host_f32 ? &d_f32 : nullptr));
     }
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev_a, c->ev_b)); local.quant_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev_b, c->ev_c)); local.transform_ms = ms;
+    if (rc) return rc;
+    if ((rc = result_down(c, fld, d_fld, d_f32, n, &local)) != WR_OK) return rc;
+    if ((rc = finisher_ms(c, &local)) != WR_OK) return rc;
     local.total += now() - t0;  // (a finish adds to what its begin took)
     local.gpu = now() - t_phase;  // without the wait for a slot
     local.wait = t_phase - t_coded;
@@ -2122,41 +2197,6 @@ int seg_coder_stage(wr_ctx* c, const CoderCall& k, wr_timings* tm)
     return WR_OK;
 }
 
-// the end of a driver's kernel stage (cu_mu held): rc is the finisher's
-int kernel_stage_end(wr_ctx* c, int rc)
-{
-    if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
-    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the decoder's kernel stage failed on the device" + launch_describe(c));
-    c->pool->last_stage_end.store(now());
-    return rc;
-}
-
-// The tail of a decode call: `count` elements from where the finisher left them (d_f64, or d_f32 for an fp32 caller) to a host
-// caller, then the call's timings.  events: quant_ms and transform_ms are the finisher's ev_a / ev_b / ev_c (a finisher that
-// ran more than once has summed them itself).
-int finish_call(wr_ctx* c, const FieldRef& fld, const void* d_f64, const void* d_f32, size_t count, bool events, double t0, double t_coded, double t_phase,
-                wr_timings* local, wr_timings* tm)
-{
-    if (fld.host) {
-        if (int rc = xfer_field(c, &c->x_field, fld.host, d_f64, count * sizeof(double), kDown)) return rc;
-        local->d2h_ms = (float)c->x_field.ms;
-    } else if (fld.host_f32) {
-        if (int rc = xfer_field(c, &c->x_field, fld.host_f32, d_f32, count * sizeof(float), kDown)) return rc;
-        local->d2h_ms = (float)c->x_field.ms;
-    }
-    if (events) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_a, c->ev_b)); local->quant_ms = ms;
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_b, c->ev_c)); local->transform_ms = ms;
-    }
-    local->total = now() - t0;
-    local->gpu = now() - t_phase;
-    local->wait = t_phase - t_coded;
-    local->transfer = t_coded - t0;
-    if (tm) *tm = *local;
-    return WR_OK;
-}
-
 // ---- the drivers.  They differ in the plan (everything; one box or region: a LowresPlan; many regions), in the finisher
 // (inverse_from_planes, lowres_from_planes / roi_from_planes, roi_multi_from_planes) and in where the result lands; the rest
 // is the stages above, in the same order: parse, gather the planes' buffers, "up", lease the slot, coder stage, finisher, tail.
@@ -2332,8 +2372,9 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
 
 // ---- transcoding: the planes of a coded field from one stream format to another (include/waverange_amd.h, wr_transcode.h)
 // No transform, no quantizer, no work-space slot: the source's decoder fills the context's device planes, the target's coder
-// reads them.  The halves are the drivers' above -- the host half of decode_impl or the coder stage of decode_seg_impl, then
-// the coder stage of encode_seg_impl or the placement and hand-over of encode_impl -- with every plane ready at once.
+// reads them.  The halves are the drivers' above -- ref_decode_planes or the coder stage of decode_seg_impl, then the coder
+// stage of encode_seg_impl or encode_impl's placement and tail (RefPlacement, run_plane_jobs, ref_stream_tail) -- with every
+// plane ready at once.
 //
 // A plane's second role.  A plane that the host coder touches lives behind a ring of pinned windows that plane_prepare arms
 // for ONE direction.  Here a plane may be written through upload windows (a reference source) or by a decoder kernel (a
@@ -2382,64 +2423,7 @@ int transcode_impl(wr_ctx* c, int nx, int ny, int nz, const wr_enc_info* info_in
 
     // ---- source half: the planes into c->ps[l]
     if (s.format == WR_FORMAT_REF) {
-        // the host half of decode_impl: admission gate, one decode at a time gathers its planes, the pool or this call's threads
-        if (verbose()) printf("Range decoding...\n");
-        std::unique_lock<std::mutex> gate(pool->planes.gate_mu, std::defer_lock);
-        if (wrrc::pool_threads() > 0) {
-            gate.lock();
-            const double t_gate = now();
-            for (;;) {
-                int qs = 0, qv = 0;
-                wrrc::pool_queued_decode(&qs, &qv);
-                if ((qs < kGateScalarJobs && qv < kGateVectorJobs) || now() - t_gate > 120.0) break;
-                std::this_thread::sleep_for(std::chrono::milliseconds(2));
-            }
-            g_stat[WR_STAT_DECODE_GATE_MS] += (unsigned long)((now() - t_gate) * 1e3);
-        }
-        {
-            const double t_turn = now();
-            std::lock_guard<std::mutex> gather(pool->planes.gather_mu);
-            const double t_got = now();
-            if (t_got - t_turn > 1e-3) g_stat[WR_STAT_PLANE_WAIT_MS] += (unsigned long)((t_got - t_turn) * 1e3);
-            for (int l = 0; l < nlay; l++) if (int rc = plane_prepare(c, l, n, true)) return rc;
-        }
-        wrrc::PlaneJob jobs[WR_NLAYMAX];
-        for (int l = 0; l < nlay; l++) {
-            jobs[l].kind = wrrc::PlaneJob::kDecode;
-            jobs[l].src = data_in + s.off[l]; jobs[l].src_len = info_in->len_enc_vec[l]; jobs[l].io = &c->ps[l].io; jobs[l].n = n;
-        }
-        bool pooled = wrrc::pool_threads() > 0;
-        try {
-            if (pooled) {
-                wrrc::JobBatch batch;
-                const bool queued = wrrc::pool_submit(jobs, nlay, &batch);
-                if (gate.owns_lock()) gate.unlock();
-                if (queued) wrrc::pool_wait(&batch);
-                else pooled = false;  // the pool was stopped meanwhile
-            }
-            if (gate.owns_lock()) gate.unlock();
-            const int groups = pooled ? 0 : std::min(nlay, coder_threads());
-            Workers workers;
-            for (int g = 0; g < groups; g++)
-                workers.v.emplace_back([&, g]() {
-                    (void)hipSetDevice(dev);
-                    const int l0 = g * nlay / groups, l1 = (g + 1) * nlay / groups;
-                    wrrc::run_jobs(jobs + l0, l1 - l0);
-                });
-        } catch (const std::exception& e) {
-            return fail(WR_ERR_ARG, std::string("transcode: ") + e.what());
-        }
-        double slowest = 0;
-        for (int l = 0; l < nlay; l++) {
-            if (jobs[l].result != n) return fail(WR_ERR_STREAM, "plane " + std::to_string(l) + ": stream does not decode to nx*ny*nz symbols");
-            local.plane_coder_s[l] = jobs[l].seconds;
-            if (jobs[l].seconds > slowest) slowest = jobs[l].seconds;
-        }
-        local.rangecoder += slowest;
-        for (int l = 0; l < nlay; l++) {
-            if (c->ps[l].err) return fail(WR_ERR_HIP, "upload of plane " + std::to_string(l) + " failed");
-            local.h2d_ms += (float)c->ps[l].copy_ms;
-        }
+        if (int rc = ref_decode_planes(c, info_in, nlay, n, data_in, s.off, "transcode: ", &local)) return rc;
     } else {
         // validation has passed (wrtc::validate): the "up" and coder stages of the full decode.  A plane the host encoder will
         // read is laid out for its windows from the start.
@@ -2486,7 +2470,7 @@ int transcode_impl(wr_ctx* c, int nx, int ny, int nz, const wr_enc_info* info_in
         if (int rc = seg_download_blobs(c, tbufs, nlay, lens, data_out, &local)) return rc;
         gpu_s += now() - t_stage;
     } else {
-        // block histograms of every plane, then the placement, hand-over and concatenation of encode_impl with all planes ready
+        // block histograms of every plane, then the placement and concatenation of encode_impl with all planes ready
         const size_t hist_per_plane = (n / wrrc::kBlock + 1) * 256;
         if (int rc = ensure_host_hist(c, hist_per_plane * WR_NLAYMAX)) return rc;
         tbufs.stage = plane_scratch(c, hist_per_plane * (size_t)nlay * sizeof(uint16_t));  // (the device histograms: a reference target stages nothing else)
@@ -2519,50 +2503,21 @@ int transcode_impl(wr_ctx* c, int nx, int ny, int nz, const wr_enc_info* info_in
             if (int rc = plane_prepare(c, l, n, false)) return rc;
             if (!wrk::plane_ref_covers(c->ps[l].ref, n)) return fail(WR_ERR_HIP, "internal: the device buffer of plane " + std::to_string(l) + " has a hole");
         }
-        // where a plane's coder writes: at the sum of the histogram bounds of the planes before it, or -- under a cap that the
-        // bounds do not fit -- into the context's buffer of that plane (encode_impl)
-        size_t est_off[WR_NLAYMAX + 1] = {0}, est_len[WR_NLAYMAX] = {0};
-        bool direct[WR_NLAYMAX] = {false};
+        // every plane is placed and handed over at once (RefPlacement)
+        RefPlacement placement;
         wrrc::PlaneJob jobs[WR_NLAYMAX];
         for (int l = 0; l < nlay; l++) {
-            est_len[l] = wrrc::encode_bound_hist(c->h_hist + l * hist_per_plane, n);
-            est_off[l + 1] = est_off[l] + est_len[l];
-            direct[l] = est_off[l + 1] + wrrc::kFailedBlockSlack <= cap;
-            if (!direct[l]) if (int rc = ensure_enc_buf(c, l, est_len[l] + wrrc::kFailedBlockSlack)) return rc;
-            wrrc::PlaneJob& j = jobs[l];
-            j.kind = wrrc::PlaneJob::kEncode;
-            j.io = &c->ps[l].io; j.dst = direct[l] ? data_out + est_off[l] : c->enc_buf[l]; j.n = n; j.hist = c->h_hist + l * hist_per_plane; j.dst_limit = est_len[l];
+            uint8_t* dst = nullptr;
+            if (int rc = placement.place(c, (unsigned)l, c->h_hist + l * hist_per_plane, n, data_out, cap, &dst)) return rc;
+            ref_encode_job(c, (unsigned)l, n, c->h_hist + l * hist_per_plane, placement, dst, &jobs[l]);
         }
         for (int l = 0; l < nlay; l++) plane_prefetch(c, l);
-        try {
-            bool pooled = wrrc::pool_threads() > 0;
-            if (pooled) {
-                wrrc::JobBatch batch;
-                if (wrrc::pool_submit(jobs, nlay, &batch)) wrrc::pool_wait(&batch);
-                else pooled = false;
-            }
-            const int groups = pooled ? 0 : std::min(nlay, encoder_threads());
-            Workers workers;
-            for (int g = 0; g < groups; g++)
-                workers.v.emplace_back([&, g]() {
-                    (void)hipSetDevice(dev);
-                    const int l0 = g * nlay / groups, l1 = (g + 1) * nlay / groups;
-                    wrrc::run_jobs(jobs + l0, l1 - l0);
-                });
-        } catch (const std::exception& e) {
-            return fail(WR_ERR_ARG, std::string("transcode: ") + e.what());
-        }
+        if (int rc = run_plane_jobs(jobs, nlay, encoder_threads(), dev, nullptr, "transcode: ")) return rc;
         size_t total = 0;
-        if (int rc = ref_stream_tail(c, jobs, (unsigned)nlay, [&](unsigned l) { return c->ps[l].err != 0; }, est_off, est_len, direct, data_out, cap, wrtc::kTooLarge,
-                                     lens, &total))
+        if (int rc = ref_stream_tail(c, jobs, (unsigned)nlay, [&](unsigned l) { return c->ps[l].err != 0; }, placement, data_out, cap, wrtc::kTooLarge, lens, &total))
             return rc;
-        double slowest = 0;  // (the planes are coded at the same time, behind the source half)
-        for (int l = 0; l < nlay; l++) {
-            local.d2h_ms += (float)c->ps[l].copy_ms;
-            local.plane_coder_s[l] += jobs[l].seconds;
-            if (jobs[l].seconds > slowest) slowest = jobs[l].seconds;
-        }
-        local.rangecoder += slowest;
+        for (int l = 0; l < nlay; l++) local.d2h_ms += (float)c->ps[l].copy_ms;
+        local.rangecoder += fold_plane_seconds(jobs, nlay, &local);  // (behind the source half)
     }
     wrtc::finish_info(*info_in, lens, nlay, info_out);
     local.total = now() - t0;
