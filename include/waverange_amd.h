@@ -204,6 +204,9 @@ int wr_set_device_slots(int device, int nslots);
 #define WR_STAT_BUDGET_CODER_RUNS 16 /* planes the encodes to a byte budget (wr_encode_*_seg_budget) have handed to the segment coder:
                                       info->nlay per call, however many tolerances the search looked at */
 #define WR_STAT_BOUNDED_CODER_RUNS 17 /* the same for the encodes to an error bound (wr_encode_*_seg_bounded) */
+#define WR_STAT_BATCH_CODER_LAUNCHES 18 /* coder kernel launches (k_*_encode_batch, k_*_decode_batch) of the batch calls, whole path
+                                          and stage level: one per plane index of an encode and of wr_decode_*_seg_batch, at most two
+                                          per wr_decode_*_seg_batch_mixed while neither kind of job exceeds WR_SEG_BATCH_MAX */
 unsigned long wr_stat(int what);
 /* Hands the idle buffers of the device's plane pool back to the device (the pool keeps the plane memory of finished calls for
  * the next ones: after a burst of concurrent calls that can be most of the HBM).  Buffers in use are not touched. */
@@ -789,6 +792,74 @@ int wr_encode_device_seg_batch(wr_ctx *ctx, int nfields, double *const *d_flds, 
 int wr_decode_device_seg_batch(wr_ctx *ctx, int nfields, double *const *d_flds, int nx, int ny, int nz,
                                const wr_enc_info *infos, const unsigned char *const *data_encs,
                                const size_t *data_lens, wr_timings *tm);
+
+/* ---- Batch calls for WRS3: stranded fields in the batched coder launches.  No new format.
+ * The calls above keep their contract (a WRS3 field is WR_ERR_UNSUPPORTED there); the ones here take strands.
+ * Encode: wr_encode_*_seg_batch_strands is wr_encode_*_seg_batch with `strands` after `brick`, in the place it has in
+ *   wr_encode_host_seg_strands: strands = 0 means WR_STRANDS_DEFAULT, brick = 0 the natural order.  For every field, the header
+ *   record and every byte of data_enc are exactly what wr_encode_host_seg_strands (_f32, wr_encode_device_seg_strands) returns
+ *   for that field alone with the same seg, brick and strands.  Plane index l of all fields is one launch sequence, strands
+ *   lanes per segment of any field.  Refused with WR_ERR_ARG beside the refusals above: a seg / brick / strands combination
+ *   the single call refuses, and a batch whose strands of one plane index number 2^31 or more.
+ * Decode: wr_decode_*_seg_batch_mixed is wr_decode_*_seg_batch for any mix of WRS1, WRS2 and WRS3 fields; brick edge, seg,
+ *   strands, tolerance and plane count may differ per field, constant fields take part without a job.  Every reconstruction is
+ *   bit for bit wr_decode_host_seg's.  Every (field, plane) of the call is a job of its own: the WRS1 / WRS2 jobs go into one
+ *   coder launch and the WRS3 jobs into another -- at most two launches per call while neither kind has more than
+ *   WR_SEG_BATCH_MAX jobs, further launches of at most WR_SEG_BATCH_MAX jobs each beyond that.  Validation, refusals and error
+ *   texts are those of wr_decode_host_seg_batch (every stream is parsed on the host before anything is copied or launched; a
+ *   failed segment is WR_ERR_STREAM naming field and plane before any dequantizer runs), except that a launch, not a plane
+ *   index, is what must stay below 2^31 lanes.  wr_timings: `rangecoder` and plane_coder_s[0] are the call's coder launches.
+ * Device memory: as above, with the blob at wr_seg_bound_strands, and
+ *   encode, once         the staging of one plane index at the record's stride: 520 + K (2 L + 8) bytes per segment of every
+ *                        field (L = the strand length), about 2.0 n per plane where WRS1 takes 1.07 n
+ *   decode, per job      brick != 0: wr_plane_pitch(n) for the plane in stream order (all jobs are in flight at once)
+ *   decode, once         a job table per launch and the failure counts
+ * wr_seg_batch_device_bytes_strands is that sum (strands = 0: WR_STRANDS_DEFAULT; 0 for a refused argument: those of
+ * wr_seg_batch_device_bytes, and strands not one of 1, 2, 4, 8, 16, 32 or 16 * strands > seg); it never decreases when
+ * nfields, n or nlay grows. */
+size_t wr_seg_batch_device_bytes_strands(int nfields, size_t n, int nlay, unsigned seg, unsigned brick, unsigned strands,
+                                         int decode);
+/* the lane layout of the batched strand ENCODER (csrc/wr_segbatch.h), for tests: all jobs share `strands` (one of 1, 2, 4, 8,
+ * 16, 32), first[0 .. njobs] is the exclusive prefix of the jobs' segment counts, and lane g of the grid is strand
+ * g & (strands - 1) of launch segment g / strands, which is segment *segment of job *job.  Returns 1, or 0 for a lane past the
+ * end (g / strands >= first[njobs]: nothing is written, and it is no error); WR_ERR_ARG for refused arguments (a null pointer,
+ * njobs outside 1..WR_SEG_BATCH_MAX, such a strand count, a prefix that does not start at 0 or decreases).
+ * The batched strand DECODER's layout is wr_seg_lists_lanes with nlist[j] = the segments of job j. */
+int wr_seg_batch_strand_lane(const uint32_t *first, uint32_t njobs, unsigned strands, unsigned long long g, uint32_t *job,
+                             uint32_t *segment, uint32_t *strand);
+/* stage level, device pointers (16-byte aligned).  Encode: njobs planes of n symbols each as WRS3 blobs in the natural order
+ * (strands = 0: WR_STRANDS_DEFAULT) in one launch sequence; every blob equals wr_dev_seg_encode_strands' for that plane.  A
+ * blob buffer too small for its blob is WR_ERR_OVERFLOW naming the job, with the other jobs complete.  Decode: njobs WRS1, WRS2
+ * and WRS3 blobs of planes of n symbols, the plain jobs in one launch and the stranded ones in another; the symbols come out
+ * in stream order, as with wr_dev_seg_decode_lists_mixed.  Every header and index is validated on the host first: a malformed
+ * one in job j is WR_ERR_STREAM with "job j" and nothing is launched.  A segment or record that does not decode on the device
+ * is counted in bad_segments[j] (may be NULL) and the call returns WR_ERR_STREAM naming the first such job. */
+int wr_dev_seg_encode_batch_strands(wr_ctx *ctx, int njobs, const unsigned char *const *d_sym, size_t n, unsigned seg,
+                                    unsigned strands, unsigned char *const *d_blob, const size_t *cap, size_t *blob_len);
+int wr_dev_seg_decode_batch_mixed(wr_ctx *ctx, int njobs, const unsigned char *const *d_blob, const size_t *blob_len,
+                                  unsigned char *const *d_sym, size_t n, size_t *bad_segments);
+/* whole path */
+int wr_encode_host_seg_batch_strands(wr_ctx *ctx, int nfields, const double *const *h_flds, int nx, int ny, int nz,
+                                     int wtflag, int mx, int my, int mz, const double *const *cutoffvecs, unsigned seg,
+                                     unsigned brick, unsigned strands, wr_enc_info *infos, unsigned char *const *data_encs,
+                                     const size_t *caps, wr_timings *tm);
+int wr_encode_host_seg_batch_strands_f32(wr_ctx *ctx, int nfields, const float *const *h_flds, int nx, int ny, int nz,
+                                         int wtflag, int mx, int my, int mz, const double *const *cutoffvecs, unsigned seg,
+                                         unsigned brick, unsigned strands, wr_enc_info *infos,
+                                         unsigned char *const *data_encs, const size_t *caps, wr_timings *tm);
+int wr_encode_device_seg_batch_strands(wr_ctx *ctx, int nfields, double *const *d_flds, int nx, int ny, int nz, int wtflag,
+                                       int mx, int my, int mz, const double *const *cutoffvecs, unsigned seg,
+                                       unsigned brick, unsigned strands, wr_enc_info *infos,
+                                       unsigned char *const *data_encs, const size_t *caps, wr_timings *tm);
+int wr_decode_host_seg_batch_mixed(wr_ctx *ctx, int nfields, double *const *h_flds, int nx, int ny, int nz,
+                                   const wr_enc_info *infos, const unsigned char *const *data_encs,
+                                   const size_t *data_lens, wr_timings *tm);
+int wr_decode_host_seg_batch_mixed_f32(wr_ctx *ctx, int nfields, float *const *h_flds, int nx, int ny, int nz,
+                                       const wr_enc_info *infos, const unsigned char *const *data_encs,
+                                       const size_t *data_lens, wr_timings *tm);
+int wr_decode_device_seg_batch_mixed(wr_ctx *ctx, int nfields, double *const *d_flds, int nx, int ny, int nz,
+                                     const wr_enc_info *infos, const unsigned char *const *data_encs,
+                                     const size_t *data_lens, wr_timings *tm);
 
 /* ---- Region decode, many regions per call: Q regions of one stream, and all used planes in ONE coder launch.  No new format.
  * A single-region call launches the coder once per used plane, back to back, and each launch lasts one segment's chain however

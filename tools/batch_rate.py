@@ -13,6 +13,16 @@ sum over the fields), and GB/s of field data.  WRS1 always; WRS2 at brick 32 onc
     python tools/batch_rate.py [--sizes 64,128,256] [--counts 1,8,64] [--tols 1e-3,1e-7] [--reps 5] [--seg 0]
                                [--wrs2-at 128,8,1e-3] [--out profiles/batch/batch_rate.json]
 
+--strands K measures the batch calls for WRS3 instead.  Per (size, tolerance, N), in the same process and inside each repetition:
+
+  wrs3_batch     encode_host_seg_batch_strands, then decode_host_seg_batch_mixed on its streams (one coder launch)
+  wrs1_batch     encode_host_seg_batch and decode_host_seg_batch: the yardstick of the new encode, and of the line below
+  wrs1_mixed     decode_host_seg_batch_mixed on those same WRS1 streams (one launch where the line above makes one per plane index)
+  wrs3_singles   a loop of N encode_host_seg(strands=K) / decode_host_seg calls: the yardstick of the batching
+
+The warm-up round compares every field's bytes and reconstruction with the single call's.  The yardsticks are rows of the same
+run, never figures printed elsewhere.
+
 Prints one JSON object (and rewrites --out after every row, so that a run that is cut short leaves what it measured)."""
 import argparse
 import json
@@ -102,6 +112,85 @@ def row(api, ctx, fields, recs, tol, count, reps, seg, brick):
     return out
 
 
+def strand_row(api, ctx, fields, recs, tol, count, reps, seg, K):
+    fs = [fields[i % len(fields)] for i in range(count)]
+    outs = recs[:count]
+    field_gb = count * fs[0].nbytes / 1e9
+    whos = ("wrs3_batch", "wrs1_batch", "wrs1_mixed", "wrs3_singles")
+    t = {who: {"encode_s": [], "decode_s": [], "enc_coder_s": [], "dec_coder_s": []} for who in whos}
+    coded3 = coded1 = None
+    info = {}
+    for rep in range(reps + 1):  # the first round warms up and checks the bits
+        # ---- the loop of single WRS3 calls
+        dt_e = dt_d = ce = cd = 0.0
+        singles = []
+        for i, f in enumerate(fs):
+            dt, (enc, tm) = timed(ctx.encode_host_seg, f, tol, 1, seg, out=None if coded3 is None else coded3[i], strands=K)
+            dt_e += dt; ce += tm["rangecoder"]
+            if not rep:
+                enc["data"] = enc["data"].copy()
+            singles.append(enc)
+            dt, tm = timed(ctx.decode_host_seg, outs[i], enc)
+            dt_d += dt; cd += tm["rangecoder"]
+        if not rep:
+            want = [o.copy() for o in outs[:min(count, len(fields))]]
+        else:
+            for k, v in zip(("encode_s", "decode_s", "enc_coder_s", "dec_coder_s"), (dt_e, dt_d, ce, cd)):
+                t["wrs3_singles"][k].append(v)
+
+        def check(encs, ref, what):
+            for i in range(count):
+                if ref is not None and not (encs[i]["len_enc_vec"] == ref[i]["len_enc_vec"] and np.array_equal(encs[i]["data"], ref[i]["data"])):
+                    raise SystemExit("batch_rate: %s: field %d of %d (%s, tol %g) has other bytes than the single call's" % (what, i, count, fs[0].shape, tol))
+                if not same_bits(outs[i], want[i % len(want)]):
+                    raise SystemExit("batch_rate: %s: field %d of %d (%s, tol %g) is reconstructed differently" % (what, i, count, fs[0].shape, tol))
+
+        def wipe():
+            if not rep:
+                for o in outs:
+                    o[:] = 0
+
+        # ---- the strand batch and the mixed decode of its streams
+        wipe()
+        dt_e, (encs3, tm_e) = timed(ctx.encode_host_seg_batch_strands, fs, tol, 1, seg, 0, K, outs=coded3)
+        dt_d, tm_d = timed(ctx.decode_host_seg_batch_mixed, outs, encs3)
+        if not rep:
+            check(encs3, singles, "wrs3_batch")
+        else:
+            for k, v in zip(("encode_s", "decode_s", "enc_coder_s", "dec_coder_s"), (dt_e, dt_d, tm_e["rangecoder"], tm_d["rangecoder"])):
+                t["wrs3_batch"][k].append(v)
+        # ---- the WRS1 batch calls, and the mixed decode on the same WRS1 streams
+        wipe()
+        dt_e, (encs1, tm_e) = timed(ctx.encode_host_seg_batch, fs, tol, 1, seg, None, outs=coded1)
+        dt_d, tm_d = timed(ctx.decode_host_seg_batch, outs, encs1)
+        if not rep:
+            check(encs1, None, "wrs1_batch")  # (the same quantized planes, so the same reconstruction)
+        else:
+            for k, v in zip(("encode_s", "decode_s", "enc_coder_s", "dec_coder_s"), (dt_e, dt_d, tm_e["rangecoder"], tm_d["rangecoder"])):
+                t["wrs1_batch"][k].append(v)
+        wipe()
+        dt_d, tm_d = timed(ctx.decode_host_seg_batch_mixed, outs, encs1)
+        if not rep:
+            check(encs1, None, "wrs1_mixed")
+            nlay = max(int(e["nlay"]) for e in encs3)
+            info = dict(fields=count, field_gb=round(field_gb, 4), strands=K, nlay=[int(e["nlay"]) for e in encs3[:len(fields)]],
+                        coded_bytes_wrs3=int(sum(e["ntot_enc"] for e in encs3)), coded_bytes_wrs1=int(sum(e["ntot_enc"] for e in encs1)), same_bits=True,
+                        device_bytes_formula=api.seg_batch_device_bytes_strands(count, fs[0].size, nlay, seg, 0, K),
+                        device_bytes_formula_decode=api.seg_batch_device_bytes_strands(count, fs[0].size, nlay, seg, 0, K, True))
+            coded3 = [api.pinned_array((max(int(e["ntot_enc"]), 16),), np.uint8) for e in encs3]
+            coded1 = [api.pinned_array((max(int(e["ntot_enc"]), 16),), np.uint8) for e in encs1]
+            continue
+        t["wrs1_mixed"]["decode_s"].append(dt_d); t["wrs1_mixed"]["dec_coder_s"].append(tm_d["rangecoder"])
+    out = dict(info)
+    for who in whos:
+        out[who] = {k: med(v) for k, v in t[who].items() if v}
+    ratio = lambda a, b, k: round(out[a][k] / out[b][k], 2) if out[b].get(k) else None
+    out["wrs1_batch_over_wrs3_batch"] = {k: ratio("wrs1_batch", "wrs3_batch", k) for k in ("encode_s", "decode_s", "enc_coder_s", "dec_coder_s")}
+    out["wrs3_singles_over_wrs3_batch"] = {k: ratio("wrs3_singles", "wrs3_batch", k) for k in ("encode_s", "decode_s", "enc_coder_s", "dec_coder_s")}
+    out["wrs1_batch_over_wrs1_mixed"] = {k: ratio("wrs1_batch", "wrs1_mixed", k) for k in ("decode_s", "dec_coder_s")}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="64,128,256")
@@ -110,6 +199,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--seg", type=int, default=0)
     ap.add_argument("--wrs2-at", default="128,8,1e-3", help="size,count,tol of the one WRS2 (brick 32) row; empty: none")
+    ap.add_argument("--strands", type=int, default=None, help="K: measure the batch calls for WRS3 (0: the default strand count)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     from waverange_amd import api
@@ -139,6 +229,11 @@ def main():
             for tol in tols:
                 for count in counts:
                     key = "%d^3 tol %g N=%d" % (n, tol, count)
+                    if a.strands is not None:
+                        res["rows"][key + " K=%d" % (a.strands or api.STRANDS_DEFAULT)] = strand_row(api, ctx, fields, recs, tol, count, a.reps, a.seg, a.strands)
+                        emit()
+                        print(key, "done", file=sys.stderr, flush=True)
+                        continue
                     res["rows"][key + " wrs1"] = row(api, ctx, fields, recs, tol, count, a.reps, a.seg, None)
                     emit()
                     print(key, "done", file=sys.stderr, flush=True)

@@ -254,6 +254,18 @@ def lib():
     L.wr_decode_host_seg_batch.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(Timings)]
     L.wr_decode_host_seg_batch_f32.argtypes = L.wr_decode_host_seg_batch.argtypes
     L.wr_decode_device_seg_batch.argtypes = L.wr_decode_host_seg_batch.argtypes
+    L.wr_seg_batch_device_bytes_strands.restype = C.c_size_t
+    L.wr_seg_batch_device_bytes_strands.argtypes = [C.c_int, C.c_size_t, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_int]
+    L.wr_seg_batch_strand_lane.argtypes = [_vp, C.c_uint32, C.c_uint, C.c_ulonglong, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.wr_dev_seg_encode_batch_strands.argtypes = [_vp, C.c_int, _vp, C.c_size_t, C.c_uint, C.c_uint, _vp, _vp, _vp]
+    L.wr_dev_seg_decode_batch_mixed.argtypes = L.wr_dev_seg_decode_batch.argtypes
+    a = L.wr_encode_host_seg_batch.argtypes
+    L.wr_encode_host_seg_batch_strands.argtypes = a[:13] + [C.c_uint] + a[13:]
+    L.wr_encode_host_seg_batch_strands_f32.argtypes = L.wr_encode_host_seg_batch_strands.argtypes
+    L.wr_encode_device_seg_batch_strands.argtypes = L.wr_encode_host_seg_batch_strands.argtypes
+    L.wr_decode_host_seg_batch_mixed.argtypes = L.wr_decode_host_seg_batch.argtypes
+    L.wr_decode_host_seg_batch_mixed_f32.argtypes = L.wr_decode_host_seg_batch.argtypes
+    L.wr_decode_device_seg_batch_mixed.argtypes = L.wr_decode_host_seg_batch.argtypes
     L.wr_seg_bound_blocked.restype = C.c_size_t
     L.wr_seg_bound_blocked.argtypes = [C.c_size_t, C.c_uint]
     L.wr_seg_lowres_segments_blocked.restype = C.c_size_t
@@ -658,6 +670,23 @@ def seg_batch_locate(first, g):
     job, k = C.c_uint32(0), C.c_uint32(0)
     _check(lib().wr_seg_batch_locate(f.ctypes.data, max(f.size, 1) - 1, g, C.byref(job), C.byref(k)))
     return int(job.value), int(k.value)
+
+
+def seg_batch_device_bytes_strands(nfields, n, nlay, seg=0, brick=0, strands=0, decode=False):
+    """seg_batch_device_bytes for the WRS3 batch calls (wr_seg_batch_device_bytes_strands; strands = 0: STRANDS_DEFAULT;
+    decode: the mixed decode of such fields); 0 for a refused argument."""
+    return int(lib().wr_seg_batch_device_bytes_strands(nfields, n, nlay, seg, brick, strands, 1 if decode else 0))
+
+
+def seg_batch_strand_lane(first, strands, g):
+    """(job, segment, strand) of lane g of a batched strand-encoder launch, or None for a lane past the end; first: the
+    exclusive prefix of the jobs' segment counts, njobs + 1 entries (wr_seg_batch_strand_lane).  Refused arguments raise."""
+    f = np.ascontiguousarray(first, dtype=np.uint32)
+    job, k, j = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    rc = lib().wr_seg_batch_strand_lane(f.ctypes.data, max(f.size, 1) - 1, strands, g, C.byref(job), C.byref(k), C.byref(j))
+    if rc < 0:
+        _check(rc)
+    return (job.value, k.value, j.value) if rc else None
 
 
 def seg_split_strands(blob):
@@ -1719,24 +1748,26 @@ class Context:
             d_sym.free()
 
     # ---- batched segmented streams: plane l of all fields of a batch in one coder launch; every field's stream is the single call's
-    def _encode_seg_batch(self, fn, ptrs, shape, tolrels, wtflag, seg, brick, cutoffs, m, caps=None, strands=None, outs=None):
-        if strands is not None:  # (the C entry points have no such argument: WR_ERR_UNSUPPORTED, as a WRS3 field in a decode batch)
-            raise WaveRangeError("libwaverange_amd error -3: stranded segments (WRS3) are not coded in a batch")
+    def _encode_seg_batch(self, fn, ptrs, shape, tolrels, wtflag, seg, brick, cutoffs, m, caps=None, strands=None, outs=None, stranded=False):
+        """stranded: `fn` is a _batch_strands entry point (strands = 0 or None: STRANDS_DEFAULT; brick None or 0: the natural order)"""
+        if strands is not None and not stranded:  # (these C entry points have no such argument: WR_ERR_UNSUPPORTED, as a WRS3 field in their decode batch)
+            raise WaveRangeError("libwaverange_amd error -3: stranded segments (WRS3) are not coded in a batch (the _batch_strands calls code them)")
         nz, ny, nx = shape
         nf = len(ptrs)
-        b = 0 if brick is None else (brick or BRICK_DEFAULT)
+        b = (brick or 0) if stranded else 0 if brick is None else (brick or BRICK_DEFAULT)
         if cutoffs is None:
             tol = [tolrels] * nf if np.isscalar(tolrels) else list(tolrels)
             cutoffs = [[t] for t in tol]
         cuts = [np.ascontiguousarray(cv, dtype=np.float64) for cv in cutoffs]
-        cap = self._seg_cap(shape, seg, None if brick is None else b) if nf else 0
+        cap = 0 if not nf else self._seg_cap(shape, seg, b, strands or 0) if stranded else self._seg_cap(shape, seg, None if brick is None else b)
         datas = list(outs) if outs is not None else [np.empty(cap if caps is None else caps[i], dtype=np.uint8) for i in range(nf)]
         infos, tm = (EncInfo * max(nf, 1))(), Timings()
         fp = (C.c_void_p * max(nf, 1))(*ptrs)
         cp = (C.c_void_p * max(nf, 1))(*[cv.ctypes.data for cv in cuts])
         dp = (C.c_void_p * max(nf, 1))(*[d.ctypes.data for d in datas])
         sz = (C.c_size_t * max(nf, 1))(*[d.size for d in datas])
-        _check(fn(self.h, nf, fp, nx, ny, nz, wtflag, m[0], m[1], m[2], cp, seg, b, infos, dp, sz, C.byref(tm)))
+        fmt = (seg, b, strands or 0) if stranded else (seg, b)
+        _check(fn(self.h, nf, fp, nx, ny, nz, wtflag, m[0], m[1], m[2], cp, *fmt, infos, dp, sz, C.byref(tm)))
         encs = []
         for i in range(nf):
             d = infos[i].as_dict()
@@ -1794,15 +1825,60 @@ class Context:
         assert len(bufs) == len(encs)
         return self._decode_seg_batch(lib().wr_decode_device_seg_batch, [b.ptr for b in bufs], shape, encs)
 
-    def seg_encode_planes_batch(self, planes, seg=0):
+    # ---- the batch calls for WRS3: the encoders with strands, the decoders that take any mix of WRS1, WRS2 and WRS3 fields
+    def encode_host_seg_batch_strands(self, fields, tolrels, wtflag=1, seg=0, brick=0, strands=0, cutoffs=None, m=(1, 1, 1), caps=None, outs=None):
+        """encode_host_seg(..., strands=strands) for a list of same-shaped float64 fields, plane l of all of them in one coder
+        launch (wr_encode_host_seg_batch_strands).  strands = 0: STRANDS_DEFAULT; brick 0 or None: the natural order.  Returns
+        ([enc dict per field], timings): every enc is what encode_host_seg returns for that field with the same parameters."""
+        assert all(f.dtype == np.float64 and f.flags["C_CONTIGUOUS"] and f.shape == fields[0].shape for f in fields)
+        shape = fields[0].shape if len(fields) else (1, 1, 1)
+        return self._encode_seg_batch(lib().wr_encode_host_seg_batch_strands, [f.ctypes.data for f in fields], shape, tolrels, wtflag, seg, brick, cutoffs, m, caps,
+                                      strands, outs, True)
+
+    def encode_host_seg_batch_strands_f32(self, fields, tolrels, wtflag=1, seg=0, brick=0, strands=0, cutoffs=None, m=(1, 1, 1), caps=None, outs=None):
+        if not all(isinstance(f, np.ndarray) and f.dtype == np.float32 and f.flags["C_CONTIGUOUS"] and f.shape == fields[0].shape for f in fields):
+            raise TypeError("encode_host_seg_batch_strands_f32: C-contiguous float32 arrays of one shape are required")
+        shape = fields[0].shape if len(fields) else (1, 1, 1)
+        return self._encode_seg_batch(lib().wr_encode_host_seg_batch_strands_f32, [f.ctypes.data for f in fields], shape, tolrels, wtflag, seg, brick, cutoffs, m,
+                                      caps, strands, outs, True)
+
+    def encode_seg_batch_strands(self, bufs, shape, tolrels, wtflag=1, seg=0, brick=0, strands=0, cutoffs=None, m=(1, 1, 1), caps=None, outs=None):
+        """encode_host_seg_batch_strands with the fields resident on the device (the buffers are consumed, as by encode_seg)."""
+        return self._encode_seg_batch(lib().wr_encode_device_seg_batch_strands, [b.ptr for b in bufs], shape, tolrels, wtflag, seg, brick, cutoffs, m, caps, strands,
+                                      outs, True)
+
+    def decode_host_seg_batch_mixed(self, outs, encs):
+        """decode_host_seg for a list of streams -- WRS1, WRS2 and WRS3 mixed freely, each with its own seg, brick edge and strand
+        count -- into the same-shaped float64 arrays `outs`: every (field, plane) is a job, the plain jobs go into one coder
+        launch and the stranded ones into another (wr_decode_host_seg_batch_mixed)."""
+        assert len(outs) == len(encs) and all(o.dtype == np.float64 and o.flags["C_CONTIGUOUS"] and o.shape == outs[0].shape for o in outs)
+        shape = outs[0].shape if len(outs) else (1, 1, 1)
+        return self._decode_seg_batch(lib().wr_decode_host_seg_batch_mixed, [o.ctypes.data for o in outs], shape, encs)
+
+    def decode_host_seg_batch_mixed_f32(self, outs, encs):
+        if not (len(outs) == len(encs) and all(isinstance(o, np.ndarray) and o.dtype == np.float32 and o.flags["C_CONTIGUOUS"] and o.shape == outs[0].shape for o in outs)):
+            raise TypeError("decode_host_seg_batch_mixed_f32: C-contiguous float32 arrays of one shape are required")
+        shape = outs[0].shape if len(outs) else (1, 1, 1)
+        return self._decode_seg_batch(lib().wr_decode_host_seg_batch_mixed_f32, [o.ctypes.data for o in outs], shape, encs)
+
+    def decode_seg_batch_mixed(self, bufs, shape, encs):
+        assert len(bufs) == len(encs)
+        return self._decode_seg_batch(lib().wr_decode_device_seg_batch_mixed, [b.ptr for b in bufs], shape, encs)
+
+    def seg_encode_planes_batch_strands(self, planes, seg=0, strands=0):
+        """Stage level: planes of one size through ONE batched strand-coder launch sequence; returns the WRS3 blob (natural
+        order) of each, byte for byte seg_encode_plane(p, seg, strands=strands)'s."""
+        return self.seg_encode_planes_batch(planes, seg, strands)
+
+    def seg_encode_planes_batch(self, planes, seg=0, _strands=None):
         """Stage level: planes of one size (numpy uint8 arrays) through ONE batched coder launch sequence; returns the WRS1
         blob of each, byte for byte seg_encode_plane's."""
         ps = [np.ascontiguousarray(p, dtype=np.uint8).ravel() for p in planes]
         n = ps[0].size if ps else 0
         assert all(p.size == n for p in ps)
-        bound = seg_bound(n, seg)
+        bound = seg_bound(n, seg) if _strands is None else seg_bound_strands(n, seg, _strands)
         if not bound:
-            raise WaveRangeError(_BAD_SEG)
+            raise WaveRangeError(_BAD_SEG if _strands is None else _BAD_SEG_STRANDS)
         nj = len(ps)
         d_sym, d_blob = [self.alloc(max(n, 16)) for _ in ps], [self.alloc(bound) for _ in ps]
         try:
@@ -1813,7 +1889,10 @@ class Context:
             bp = (C.c_void_p * max(nj, 1))(*[d.ptr for d in d_blob])
             cap = (C.c_size_t * max(nj, 1))(*([bound] * nj))
             got = (C.c_size_t * max(nj, 1))()
-            _check(lib().wr_dev_seg_encode_batch(self.h, nj, sp, n, seg, bp, cap, got))
+            if _strands is None:
+                _check(lib().wr_dev_seg_encode_batch(self.h, nj, sp, n, seg, bp, cap, got))
+            else:
+                _check(lib().wr_dev_seg_encode_batch_strands(self.h, nj, sp, n, seg, _strands, bp, cap, got))
             return [d_blob[j].download(np.uint8, got[j]) for j in range(nj)]
         finally:
             for d in d_sym + d_blob:
@@ -1821,6 +1900,16 @@ class Context:
 
     def seg_decode_planes_batch(self, blobs, n):
         """Stage level: WRS1 blobs of planes of n symbols through ONE batched decoder launch; returns ([symbols], [bad segments])."""
+        return self._seg_decode_planes_batch(lib().wr_dev_seg_decode_batch, blobs, n, True)
+
+    def seg_decode_planes_batch_mixed(self, blobs, n, check=True):
+        """Stage level: WRS1, WRS2 and WRS3 blobs of planes of n symbols, the plain ones through one batched decoder launch and
+        the stranded ones through another (wr_dev_seg_decode_batch_mixed); the symbols come out in stream order.  Returns
+        ([symbols], [bad segments]).  check = False: segments that do not decode on the device are only counted (the call's
+        WR_ERR_STREAM is not raised if some count is non-zero); a header or index refused on the host raises all the same."""
+        return self._seg_decode_planes_batch(lib().wr_dev_seg_decode_batch_mixed, blobs, n, check)
+
+    def _seg_decode_planes_batch(self, fn, blobs, n, check):
         bs = [np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in blobs]
         nj = len(bs)
         d_blob, d_sym = [self.alloc(max(b.size, 16)) for b in bs], [self.alloc(max(n, 16)) for _ in bs]
@@ -1832,7 +1921,9 @@ class Context:
             sp = (C.c_void_p * max(nj, 1))(*[d.ptr for d in d_sym])
             ln = (C.c_size_t * max(nj, 1))(*[b.size for b in bs])
             bad = (C.c_size_t * max(nj, 1))()
-            _check(lib().wr_dev_seg_decode_batch(self.h, nj, bp, ln, sp, n, bad))
+            rc = fn(self.h, nj, bp, ln, sp, n, bad)
+            if check or rc != -4 or not any(bad[j] for j in range(nj)):
+                _check(rc)
             return [d.download(np.uint8, n) if n else np.zeros(0, np.uint8) for d in d_sym], [int(bad[j]) for j in range(nj)]
         finally:
             for d in d_blob + d_sym:

@@ -3068,12 +3068,24 @@ size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 size_t batch_plane_bytes(size_t n) { return wr_plane_pitch(n); }
 size_t batch_perm_bytes(size_t n, unsigned brick) { return brick ? wr_plane_pitch(n) : 0; }  // per field: the plane in stream order
 size_t batch_work_bytes(size_t nseg) { return wrk::seg_decode_work_bytes(nseg); }  // per decoded (field, plane): offsets and flags
-// once per call.  encode: the staging of one plane index; decode: a job table per plane index and a failure count per job
-size_t batch_once_bytes(size_t nfields, size_t n, int nlay, unsigned seg, bool decode)
+// once per call.  encode: the staging of one plane index (strands != 0: at the strand stride); decode: a job table per plane
+// index and a failure count per job
+size_t batch_once_bytes(size_t nfields, size_t n, int nlay, unsigned seg, bool decode, unsigned strands = 0)
 {
     if (!nlay) return 0;
-    return decode ? (size_t)nlay * wrk::seg_batch_table_bytes(nfields) + up256(4 * nfields * (size_t)nlay) : wrk::seg_batch_stage_bytes(nfields, n, seg);
+    if (decode) return (size_t)nlay * wrk::seg_batch_table_bytes(nfields) + up256(4 * nfields * (size_t)nlay);
+    return strands ? wrk::strand_batch_stage_bytes(nfields, n, seg, strands) : wrk::seg_batch_stage_bytes(nfields, n, seg);
 }
+// ... of a mixed decode: its jobs are all (field, plane) pairs, the plain ones (WRS1 / WRS2) and the stranded ones (WRS3) each in
+// launches of at most WR_SEG_BATCH_MAX jobs, a table per launch, and a failure count per job behind the tables
+size_t batch_chunk_tables_bytes(size_t njobs)
+{
+    size_t bytes = 0;
+    for (size_t a = 0; a < njobs; a += wrsb::kBatchMax) bytes += wrk::seg_batch_table_bytes(std::min<size_t>(wrsb::kBatchMax, njobs - a));
+    return bytes;
+}
+size_t batch_mixed_tables_bytes(size_t plain, size_t stranded) { return batch_chunk_tables_bytes(plain) + batch_chunk_tables_bytes(stranded); }
+size_t batch_mixed_once_bytes(size_t plain, size_t stranded) { return batch_mixed_tables_bytes(plain, stranded) + up256(4 * (plain + stranded)); }
 // pinned host memory of a call, per launch sequence (plane index): the job table, then 16 bytes per job for what comes back
 struct BatchPinned {
     size_t table, per_l;
@@ -3132,10 +3144,11 @@ int fail_at(const char* what, int i, int rc)
 constexpr unsigned long long kBatchLaneLimit = 1ull << 31;
 
 int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
-                          const double* const* cutoffvecs, unsigned seg, unsigned brick, wr_enc_info* infos, unsigned char* const* data_encs,
-                          const size_t* caps, wr_timings* tm)
+                          const double* const* cutoffvecs, unsigned seg, unsigned brick, unsigned strands, wr_enc_info* infos,
+                          unsigned char* const* data_encs, const size_t* caps, wr_timings* tm)
 {
-    if (int rc = seg_format_params(&seg, brick, 0)) return rc;
+    // strands == 0: WRS1 / WRS2 (the entry points without that argument); otherwise WRS3, K lanes per segment
+    if (int rc = seg_format_params(&seg, brick, strands)) return rc;
     if (!cutoffvecs || !infos || !data_encs || !caps) return fail(WR_ERR_ARG, "null array");
     if (mx < 1 || my < 1 || mz < 1) return fail(WR_ERR_ARG, "bad local cutoff description");
     if (int rc = ctx_bind(c)) return rc;
@@ -3154,12 +3167,13 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
     const size_t n = (size_t)nx * ny * nz;
     const size_t nseg = wrseg::seg_count(n, seg);
     if ((unsigned long long)nseg * (unsigned)nfields >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the planes of one index have 2^31 segments or more");
+    if ((unsigned long long)nseg * strands * (unsigned)nfields >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many strands: the planes of one index have 2^31 strands or more");
     wr_timings local; memset(&local, 0, sizeof local);
     DevPool* const pool = c->pool;
     c->pend_valid = false;
     PlaneHold planes(c);
     BatchBufs bufs(c);  // (goes first when the call unwinds, and waits for the stream)
-    const size_t blob_cap = seg_blob_cap(n, seg, brick, 0);
+    const size_t blob_cap = seg_blob_cap(n, seg, brick, strands);
     const BatchPinned pin(nfields);
     wrblk::Order od{};
     if (brick) od = wrblk::order_of(nx, ny, nz, wtflag ? kWavLvl : 0, brick);
@@ -3204,7 +3218,7 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
         }
         // ---- one launch sequence per plane index over the fields that have such a plane
         if (maxlay) {
-            uint8_t* const stage = bufs.take(batch_once_bytes(nfields, n, maxlay, seg, false));
+            uint8_t* const stage = bufs.take(batch_once_bytes(nfields, n, maxlay, seg, false, strands));
             if (!stage) return WR_ERR_HIP;
             for (int f = 0; f < nfields; f++) {
                 for (int l = 0; l < (int)infos[f].nlay; l++)
@@ -3225,10 +3239,12 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
                     job_of[at] = (int)jobs.size();
                     jobs.push_back(seg_encode_job(brick ? wrk::plane_ref(perm[f]) : refs[at], blob[at], blob_cap, brick));
                 }
-                launch_note(c, "seg_encode_batch", l, stage, n, pin.jobs(bufs.pinned, l), jobs[0].sym);
-                wrk::seg_encode_batch(jobs.data(), jobs.size(), n, seg, pin.jobs(bufs.pinned, l), stage, pin.results(bufs.pinned_dev, l), c->stream);
+                launch_note(c, strands ? "strand_encode_batch" : "seg_encode_batch", l, stage, n, pin.jobs(bufs.pinned, l), jobs[0].sym);
+                if (strands) wrk::strand_encode_batch(jobs.data(), jobs.size(), n, seg, strands, pin.jobs(bufs.pinned, l), stage, pin.results(bufs.pinned_dev, l), c->stream);
+                else wrk::seg_encode_batch(jobs.data(), jobs.size(), n, seg, pin.jobs(bufs.pinned, l), stage, pin.results(bufs.pinned_dev, l), c->stream);
                 HIPCHK(hipEventRecord(bufs.ev[2 * l + 1], c->stream));
                 if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "batched segment coder launch failed" + launch_describe(c));
+                g_stat[WR_STAT_BATCH_CODER_LAUNCHES] += 1;
             }
             if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the batched segment coder failed on the device" + launch_describe(c));
         }
@@ -3261,10 +3277,45 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
 struct BatchField {  // a field of a decode batch: its stream as the host has validated it (nlay == 0: a constant field, no job), and its buffers
     SegStream s;
     uint8_t *plane[WR_NLAYMAX] = {nullptr}, *blob[WR_NLAYMAX] = {nullptr}, *work[WR_NLAYMAX] = {nullptr}, *perm = nullptr;
+    uint8_t* perms[WR_NLAYMAX] = {nullptr};  // a blocked field of a mixed decode: one stream-order plane per job (all jobs go in one launch)
+    int job0 = 0;                            // its first job's place in the failure counts
 };
 
+// The coder launches of a mixed decode: the jobs of one kind in launches of at most WR_SEG_BATCH_MAX jobs, their tables behind
+// one another at host_table / d_table.  First: whether every such launch stays below 2^31 lanes.
+bool batch_chunk_lanes_ok(const std::vector<wrk::SegJob>& jobs)
+{
+    for (size_t a = 0; a < jobs.size(); a += wrsb::kBatchMax) {
+        unsigned long long lanes = 0;
+        for (size_t j = a; j < std::min<size_t>(jobs.size(), a + wrsb::kBatchMax); j++) lanes += wrsb::job_lanes(jobs[j].nseg, jobs[j].strands);
+        if (lanes >= wrsb::kLaneLimit) return false;
+    }
+    return true;
+}
+
+// (cu_mu held) returns the launches made; *at: where the next table goes, moved on
+int batch_chunk_launch(const std::vector<wrk::SegJob>& jobs, bool stranded, uint8_t* host_table, uint8_t* d_table, size_t* at, hipStream_t st)
+{
+    int launches = 0;
+    for (size_t a = 0; a < jobs.size(); a += wrsb::kBatchMax) {
+        const size_t count = std::min<size_t>(wrsb::kBatchMax, jobs.size() - a);
+        size_t lanes = 0;
+        for (size_t j = a; j < a + count; j++) lanes += jobs[j].nseg;
+        if (!lanes) continue;  // (neither launcher launches for jobs without segments)
+        if (stranded) wrk::strand_decode_batch(jobs.data() + a, count, host_table + *at, d_table + *at, st);
+        else wrk::seg_decode_batch(jobs.data() + a, count, host_table + *at, d_table + *at, st);
+        launches++;
+        *at += wrk::seg_batch_table_bytes(count);
+    }
+    return launches;
+}
+
+// mixed == false: wr_decode_*_seg_batch -- WRS1 and WRS2 fields, a WRS3 field is refused, one coder launch per plane index.
+// mixed == true: wr_decode_*_seg_batch_mixed -- WRS3 fields beside them, every (field, plane) of the call a job of its own, the
+// plain jobs through k_seg_decode_batch and the stranded ones through k_strand_decode_batch: two launches while neither kind has
+// more than WR_SEG_BATCH_MAX jobs.  Everything around the coder stage is the same code.
 int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& flds, int nx, int ny, int nz, const wr_enc_info* infos,
-                          const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm)
+                          const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm, bool mixed = false)
 {
     if (!infos || !data_encs) return fail(WR_ERR_ARG, "null array");
     if (int rc = ctx_bind(c)) return rc;
@@ -3284,6 +3335,7 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
     // ---- every field's lengths, headers and indices, on the host, before anything is copied or launched for any field
     std::vector<BatchField> bf(nfields);
     int maxlay = 0, wlev_any = 0;
+    size_t njobs = 0, nplain = 0, nstranded = 0;
     unsigned long long lanes[WR_NLAYMAX] = {0};
     for (int f = 0; f < nfields; f++) {
         const wr_enc_info* const info = &infos[f];
@@ -3291,18 +3343,23 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
         if (info->ntot_enc == 0) continue;  // a constant field: filled with midval below
         const std::string who = "field " + std::to_string(f) + ": ";
         if (int rc = seg_stream_of(nx, ny, nz, info, data_encs[f], data_lens ? data_lens[f] : 0, &s, who)) return rc;
-        if (s.strands) return fail(WR_ERR_UNSUPPORTED, who + "a WRS3 stream: stranded segments are not decoded in a batch (wr_decode_host_seg reads them)");
+        if (s.strands && !mixed) return fail(WR_ERR_UNSUPPORTED, who + "a WRS3 stream: stranded segments are not decoded in a batch (wr_decode_host_seg reads them)");
         for (int l = 0; l < s.nlay; l++) lanes[l] += s.nseg[l];
+        bf[f].job0 = (int)njobs;
+        njobs += (size_t)s.nlay;
+        (s.strands ? nstranded : nplain) += (size_t)s.nlay;
         if (s.nlay > maxlay) maxlay = s.nlay;
         if (info->wlev) wlev_any = kWavLvl;
     }
-    for (int l = 0; l < maxlay; l++)
+    for (int l = 0; l < maxlay && !mixed; l++)
         if (lanes[l] >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the planes of index " + std::to_string(l) + " have 2^31 segments or more");
     c->pend_valid = false;
     PlaneHold planes(c);
     BatchBufs bufs(c);
     uint8_t* d_once = nullptr;
     const size_t table = wrk::seg_batch_table_bytes(nfields);
+    // the jobs' failure counts lie behind the tables, in the order of the fields and their planes
+    const size_t tables_bytes = mixed ? batch_mixed_tables_bytes(nplain, nstranded) : (size_t)maxlay * table;
     if (maxlay) {
         std::lock_guard<std::mutex> gather(pool->planes.gather_mu);  // one decode at a time gathers its planes (decode_impl)
         for (int f = 0; f < nfields; f++) {
@@ -3312,11 +3369,12 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
                 b.blob[l] = bufs.take(infos[f].len_enc_vec[l]);
                 b.work[l] = bufs.take(batch_work_bytes(b.s.nseg[l]));
                 if (!b.plane[l] || !b.blob[l] || !b.work[l]) return fail_at("field", f, WR_ERR_HIP);
+                if (mixed && b.s.brick && !(b.perms[l] = bufs.take(batch_perm_bytes(n, b.s.brick)))) return fail_at("field", f, WR_ERR_HIP);
             }
-            if (b.s.brick && !(b.perm = bufs.take(batch_perm_bytes(n, b.s.brick)))) return fail_at("field", f, WR_ERR_HIP);
+            if (!mixed && b.s.brick && !(b.perm = bufs.take(batch_perm_bytes(n, b.s.brick)))) return fail_at("field", f, WR_ERR_HIP);
         }
-        if (!(d_once = bufs.take(batch_once_bytes(nfields, n, maxlay, 0, true)))) return WR_ERR_HIP;
-        if (int rc = bufs.pin(BatchPinned(nfields).bytes(maxlay))) return rc;
+        if (!(d_once = bufs.take(mixed ? batch_mixed_once_bytes(nplain, nstranded) : batch_once_bytes(nfields, n, maxlay, 0, true)))) return WR_ERR_HIP;
+        if (int rc = bufs.pin(mixed ? tables_bytes : BatchPinned(nfields).bytes(maxlay))) return rc;
     }
     // ---- stage "up": one copy per blob, and its segments' offsets
     for (int f = 0; f < nfields; f++)
@@ -3337,23 +3395,47 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
         StageLock cu(pool->cu_mu);
         clock_warmup(c, n);
         if (maxlay) {
-            // the jobs' failure counts lie behind the tables: job (f, l) counts into d_bad[l * nfields + f]
-            unsigned int* const d_bad = reinterpret_cast<unsigned int*>(d_once + (size_t)maxlay * table);
+            // job (f, l) counts into d_bad[job0 of f + l]
+            unsigned int* const d_bad = reinterpret_cast<unsigned int*>(d_once + tables_bytes);
             const size_t per_l = BatchPinned(nfields).per_l;
-            HIPCHK(hipMemsetAsync(d_bad, 0, 4 * (size_t)nfields * maxlay, c->stream));
+            HIPCHK(hipMemsetAsync(d_bad, 0, 4 * njobs, c->stream));
             std::vector<wrk::SegJob> jobs;
-            for (int l = 0; l < maxlay; l++) {
+            if (mixed) {
+                // ---- every (field, plane) of the call: the plain jobs in one launch, the stranded ones in another
+                std::vector<wrk::SegJob> stranded;
+                for (int f = 0; f < nfields; f++) {
+                    const BatchField& b = bf[f];
+                    for (int l = 0; l < b.s.nlay; l++) {
+                        wrk::SegJob job = seg_job(wrk::plane_ref(b.s.brick ? b.perms[l] : b.plane[l]), b.blob[l], infos[f].len_enc_vec[l], b.work[l], n, b.s.seg[l], b.s.nseg[l], b.s.brick);
+                        job.strands = b.s.strands;
+                        job.bad = d_bad + b.job0 + l;  // (the batch counts in one array, read back once)
+                        (b.s.strands ? stranded : jobs).push_back(job);
+                    }
+                }
+                if (!batch_chunk_lanes_ok(jobs) || !batch_chunk_lanes_ok(stranded)) return fail(WR_ERR_ARG, "too many segments: a launch of the call has 2^31 lanes or more");
+                if (int rc = bufs.ev.create(0)) return rc;
+                launch_note(c, "seg_decode_batch_mixed", 0, d_once, n, bufs.pinned, wrk::plane_ref(d_once));
+                HIPCHK(hipEventRecord(bufs.ev[0], c->stream));
+                size_t at = 0;
+                int launches = batch_chunk_launch(jobs, false, bufs.pinned, d_once, &at, c->stream);
+                launches += batch_chunk_launch(stranded, true, bufs.pinned, d_once, &at, c->stream);
+                HIPCHK(hipEventRecord(bufs.ev[1], c->stream));
+                if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "batched segment decoder launch failed" + launch_describe(c));
+                g_stat[WR_STAT_BATCH_CODER_LAUNCHES] += (unsigned long)launches;
+            }
+            for (int l = 0; l < maxlay && !mixed; l++) {
                 if (int rc = bufs.ev.create(l)) return rc;
                 jobs.clear();
                 for (int f = 0; f < nfields; f++) {
                     const BatchField& b = bf[f];
                     if (b.s.nlay <= l) continue;
                     jobs.push_back(seg_job(wrk::plane_ref(b.s.brick ? b.perm : b.plane[l]), b.blob[l], infos[f].len_enc_vec[l], b.work[l], n, b.s.seg[l], b.s.nseg[l], b.s.brick));
-                    jobs.back().bad = d_bad + (size_t)l * nfields + f;  // (the batch counts in one array, read back once)
+                    jobs.back().bad = d_bad + b.job0 + l;  // (the batch counts in one array, read back once)
                 }
                 launch_note(c, "seg_decode_batch", l, d_once + l * table, n, bufs.pinned + l * per_l, jobs[0].sym);
                 HIPCHK(hipEventRecord(bufs.ev[2 * l], c->stream));
                 wrk::seg_decode_batch(jobs.data(), jobs.size(), bufs.pinned + l * per_l, d_once + l * table, c->stream);
+                g_stat[WR_STAT_BATCH_CODER_LAUNCHES] += 1;
                 for (int f = 0; f < nfields; f++)  // WRS2 fields: back to the natural order, per field as in the single-field coder stage
                     if (bf[f].s.nlay > l && bf[f].s.brick &&
                         !wrk::plane_reorder(wrk::plane_ref(bf[f].plane[l]), bf[f].perm, bf[f].s.od, true, nullptr, 0, c->stream))
@@ -3362,14 +3444,14 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
                 if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "batched segment decoder launch failed" + launch_describe(c));
             }
             // the dequantizers only run if every segment of every field decoded: the counts come back once
-            std::vector<unsigned int> bad((size_t)nfields * maxlay);
+            std::vector<unsigned int> bad(njobs);
             HIPCHK(hipMemcpyAsync(bad.data(), d_bad, 4 * bad.size(), hipMemcpyDeviceToHost, c->stream));
             if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the batched segment decoder failed on the device" + launch_describe(c));
             for (int f = 0; f < nfields; f++)
                 for (int l = 0; l < bf[f].s.nlay; l++)
-                    if (const unsigned int k = bad[(size_t)l * nfields + f])
+                    if (const unsigned int k = bad[(size_t)bf[f].job0 + l])
                         return fail(WR_ERR_STREAM, "field " + std::to_string(f) + ": plane " + std::to_string(l) + ": " + bad_segments_text(k));
-            fold_coder_seconds(bufs, maxlay, &local);  // one entry per plane index
+            fold_coder_seconds(bufs, mixed ? 1 : maxlay, &local);  // one entry per plane index; mixed: one for the call's launches
         }
         // ---- every field in turn through the slot: dequantizer, inverse transform, download
         for (int f = 0; f < nfields; f++) {
@@ -3380,6 +3462,9 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
                 if (int rc = fill_constant(c, fld, n, info->midval)) return rc;
                 continue;
             }
+            for (int l = 0; l < b.s.nlay && mixed; l++)  // a blocked field of a mixed decode: its planes back to the natural order
+                if (b.s.brick && !wrk::plane_reorder(wrk::plane_ref(b.plane[l]), b.perms[l], b.s.od, true, nullptr, 0, c->stream))
+                    return fail(WR_ERR_ARG, "field " + std::to_string(f) + ": too many bricks");
             wrk::DequantParams p;
             if (int rc = dequant_params(info, b.s.nlay, n, [&](int l) { return wrk::plane_ref(b.plane[l]); }, &p)) return fail_at("field", f, rc);
             double* const d_fld = fld.dev ? fld.dev : slot->field;
@@ -3439,6 +3524,29 @@ size_t wr_seg_batch_device_bytes(int nfields, size_t n, int nlay, unsigned seg, 
     return N * (size_t)nlay * per_plane + N * batch_perm_bytes(n, brick) + up256(batch_once_bytes(N, n, nlay, seg, decode != 0));
 }
 
+size_t wr_seg_batch_device_bytes_strands(int nfields, size_t n, int nlay, unsigned seg, unsigned brick, unsigned strands, int decode)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!strands) strands = WR_STRANDS_DEFAULT;
+    if (nfields < 1 || nfields > WR_SEG_BATCH_MAX || !n || nlay < 0 || nlay > WR_NLAYMAX || !wrseg::seg_ok(seg) || (brick && !wrblk::brick_ok(brick))) return 0;
+    if (!wrseg::strands_ok(strands, seg)) return 0;
+    const size_t N = (size_t)nfields, jobs = N * (size_t)nlay;
+    size_t per_plane = batch_plane_bytes(n) + up256(seg_blob_cap(n, seg, brick, strands));
+    if (!decode) return jobs * per_plane + N * batch_perm_bytes(n, brick) + up256(batch_once_bytes(N, n, nlay, seg, false, strands));
+    // the mixed decode: a stream-order plane per job of a blocked field, a table per launch of at most WR_SEG_BATCH_MAX jobs
+    per_plane += up256(batch_work_bytes(wrseg::seg_count(n, seg))) + batch_perm_bytes(n, brick);
+    return jobs * per_plane + up256(batch_mixed_once_bytes(0, jobs));
+}
+
+int wr_seg_batch_strand_lane(const uint32_t* first, uint32_t njobs, unsigned strands, unsigned long long g, uint32_t* job, uint32_t* segment, uint32_t* strand)
+{
+    if (!first || !job || !segment || !strand) return fail(WR_ERR_ARG, "null pointer");
+    if (njobs < 1 || njobs > wrsb::kBatchMax) return fail(WR_ERR_ARG, "njobs must be in 1.." + std::to_string(wrsb::kBatchMax));
+    if (!strands || !wrsb::strands_layout_ok(strands)) return fail(WR_ERR_ARG, "strands must be one of 1, 2, 4, 8, 16, 32");
+    if (!wrsb::prefix_ok(first, njobs)) return fail(WR_ERR_ARG, "not an exclusive prefix: it must start at 0 and never decrease");
+    return wrsb::strand_lane(first, njobs, strands, g, job, segment, strand) ? 1 : 0;  // (0: a lane past the end, which is no error)
+}
+
 int wr_seg_batch_locate(const uint32_t* first, uint32_t njobs, uint32_t g, uint32_t* job, uint32_t* k)
 {
     if (!first || !job || !k) return fail(WR_ERR_ARG, "null pointer");
@@ -3449,44 +3557,62 @@ int wr_seg_batch_locate(const uint32_t* first, uint32_t njobs, uint32_t g, uint3
     return WR_OK;
 }
 
-int wr_dev_seg_encode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_sym, size_t n, unsigned seg, unsigned char* const* d_blob, const size_t* cap,
-                            size_t* blob_len)
+// `njobs` planes, as they stand, into the callers' blob buffers: strands == 0 WRS1 blobs, otherwise WRS3 in the natural order
+static int dev_seg_encode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_sym, size_t n, unsigned seg, unsigned strands, unsigned char* const* d_blob,
+                                const size_t* cap, size_t* blob_len)
 {
-    if (int rc = seg_format_params(&seg, 0, 0)) return rc;
+    if (int rc = seg_format_params(&seg, 0, strands)) return rc;
     if (njobs < 1 || njobs > WR_SEG_BATCH_MAX) return fail(WR_ERR_ARG, "njobs must be in 1.." + std::to_string(WR_SEG_BATCH_MAX));
     if (int rc = ctx_bind(c)) return rc;
     if (!d_sym || !d_blob || !cap || !blob_len) return fail(WR_ERR_ARG, "null array");
     const size_t nseg = wrseg::seg_count(n, seg);
     if ((unsigned long long)nseg * (unsigned)njobs >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the batch has 2^31 segments or more");
+    if ((unsigned long long)nseg * strands * (unsigned)njobs >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many strands: the batch has 2^31 strands or more");
     for (int j = 0; j < njobs; j++) {
         if (!d_blob[j] || (n && !d_sym[j])) return fail(WR_ERR_ARG, "job " + std::to_string(j) + ": null pointer");
         if (((uintptr_t)d_sym[j] | (uintptr_t)d_blob[j]) & 15) return fail(WR_ERR_ARG, "job " + std::to_string(j) + ": plane and blob buffers must be 16-byte aligned");
-        if (cap[j] < wrseg::kHeaderBytes + 4 * nseg) return fail(WR_ERR_OVERFLOW, "job " + std::to_string(j) + ": the blob buffer does not hold the plane's index");
+        if (cap[j] < wrseg::header_bytes(0, strands) + 4 * nseg) return fail(WR_ERR_OVERFLOW, "job " + std::to_string(j) + ": the blob buffer does not hold the plane's index");
     }
     std::lock_guard<std::mutex> lk(c->mu);
     BatchBufs bufs(c);
-    uint8_t* const stage = bufs.take(wrk::seg_batch_stage_bytes(njobs, n, seg));
+    uint8_t* const stage = bufs.take(batch_once_bytes(njobs, n, 1, seg, false, strands));
     if (!stage) return WR_ERR_HIP;
     const BatchPinned pin(njobs);
     if (int rc = bufs.pin(pin.bytes(1))) return rc;
     std::vector<wrk::SegJob> jobs;
     for (int j = 0; j < njobs; j++) jobs.push_back(seg_encode_job(wrk::plane_ref(d_sym[j]), d_blob[j], cap[j], 0));
     StageLock cu(c->pool->cu_mu);
-    wrk::seg_encode_batch(jobs.data(), jobs.size(), n, seg, pin.jobs(bufs.pinned, 0), stage, pin.results(bufs.pinned_dev, 0), c->stream);
+    if (strands) wrk::strand_encode_batch(jobs.data(), jobs.size(), n, seg, strands, pin.jobs(bufs.pinned, 0), stage, pin.results(bufs.pinned_dev, 0), c->stream);
+    else wrk::seg_encode_batch(jobs.data(), jobs.size(), n, seg, pin.jobs(bufs.pinned, 0), stage, pin.results(bufs.pinned_dev, 0), c->stream);
     HIPCHK(hipGetLastError());
+    if (nseg) g_stat[WR_STAT_BATCH_CODER_LAUNCHES] += 1;
     HIPCHK(hipStreamSynchronize(c->stream));
     const unsigned long long* const res = pin.results(bufs.pinned, 0);
     int rc = WR_OK;
     for (int j = 0; j < njobs; j++) {
-        if (res[2 * j + 1]) { if (!rc) rc = fail(WR_ERR_HIP, "job " + std::to_string(j) + ": internal: " + kOutgrew); continue; }
+        if (res[2 * j + 1]) { if (!rc) rc = fail(WR_ERR_HIP, "job " + std::to_string(j) + ": internal: " + (strands ? "a record outgrew the record bound" : kOutgrew)); continue; }
         if (res[2 * j] > cap[j]) { if (!rc) rc = fail(WR_ERR_OVERFLOW, "job " + std::to_string(j) + ": the blob buffer is too small for the plane"); continue; }
         blob_len[j] = (size_t)res[2 * j];
     }
     return rc;
 }
 
-int wr_dev_seg_decode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_blob, const size_t* blob_len, unsigned char* const* d_sym, size_t n,
-                            size_t* bad_segments)
+int wr_dev_seg_encode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_sym, size_t n, unsigned seg, unsigned char* const* d_blob, const size_t* cap,
+                            size_t* blob_len)
+{
+    return dev_seg_encode_batch(c, njobs, d_sym, n, seg, 0, d_blob, cap, blob_len);
+}
+
+int wr_dev_seg_encode_batch_strands(wr_ctx* c, int njobs, const unsigned char* const* d_sym, size_t n, unsigned seg, unsigned strands,
+                                    unsigned char* const* d_blob, const size_t* cap, size_t* blob_len)
+{
+    return dev_seg_encode_batch(c, njobs, d_sym, n, seg, strands ? strands : WR_STRANDS_DEFAULT, d_blob, cap, blob_len);
+}
+
+// mixed == false: WRS1 blobs, a WRS3 blob is refused; mixed == true: WRS1, WRS2 and WRS3 blobs side by side, the symbols in
+// stream order, the plain jobs in one launch and the stranded ones in another
+static int dev_seg_decode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_blob, const size_t* blob_len, unsigned char* const* d_sym, size_t n,
+                                size_t* bad_segments, bool mixed)
 {
     if (njobs < 1 || njobs > WR_SEG_BATCH_MAX) return fail(WR_ERR_ARG, "njobs must be in 1.." + std::to_string(WR_SEG_BATCH_MAX));
     if (int rc = ctx_bind(c)) return rc;
@@ -3502,32 +3628,39 @@ int wr_dev_seg_decode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_
     unsigned long long lanes = 0;
     for (int j = 0; j < njobs; j++) {
         const std::string who = "job " + std::to_string(j) + ": ";
-        if (int rc = fetch_front(d_blob[j], blob_len[j], n, false, "a WRS3 blob: stranded segments are not decoded in a batch (wr_dev_seg_decode reads them)", who, &front[j])) return rc;
-        lanes += front[j].nseg;
+        const char* const no_strands = mixed ? nullptr : "a WRS3 blob: stranded segments are not decoded in a batch (wr_dev_seg_decode reads them)";
+        if (int rc = fetch_front(d_blob[j], blob_len[j], n, mixed, no_strands, who, &front[j])) return rc;
+        lanes += wrsb::job_lanes(front[j].nseg, front[j].strands);
     }
     if (lanes >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the batch has 2^31 segments or more");
     if (!lanes) return WR_OK;
     BatchBufs bufs(c);
-    const size_t table = wrk::seg_batch_table_bytes(njobs);
-    uint8_t* const d_once = bufs.take(batch_once_bytes(njobs, n, 1, 0, true));
+    // (at most WR_SEG_BATCH_MAX jobs: a table for the plain jobs, one for the stranded ones, the failure counts behind them)
+    const size_t tables = 2 * wrk::seg_batch_table_bytes(njobs);
+    uint8_t* const d_once = bufs.take(tables + up256(4 * (size_t)njobs));
     if (!d_once) return WR_ERR_HIP;
-    if (int rc = bufs.pin(BatchPinned(njobs).bytes(1))) return rc;
-    unsigned int* const d_bad = reinterpret_cast<unsigned int*>(d_once + table);
-    std::vector<wrk::SegJob> jobs(njobs);
+    if (int rc = bufs.pin(tables)) return rc;
+    unsigned int* const d_bad = reinterpret_cast<unsigned int*>(d_once + tables);
+    std::vector<wrk::SegJob> jobs, stranded;
     for (int j = 0; j < njobs; j++) {
         const Front& f = front[j];
         uint8_t* work = nullptr;
         if (f.nseg) {
             if (!(work = bufs.take(batch_work_bytes(f.nseg)))) return WR_ERR_HIP;
-            if (int rc = seg_upload_offsets(f.bytes.data(), wrseg::kHeaderBytes, f.nseg, work)) return rc;
+            if (int rc = seg_upload_offsets(f.bytes.data(), wrseg::header_bytes(f.brick, f.strands), f.nseg, work)) return rc;
         }
-        jobs[j] = seg_job(wrk::plane_ref(d_sym[j]), d_blob[j], blob_len[j], work, n, f.seg, f.nseg, 0);
-        jobs[j].bad = d_bad + j;
+        wrk::SegJob job = seg_job(wrk::plane_ref(d_sym[j]), d_blob[j], blob_len[j], work, n, f.seg, f.nseg, f.brick);
+        job.strands = f.strands;
+        job.bad = d_bad + j;
+        (f.strands ? stranded : jobs).push_back(job);
     }
     StageLock cu(c->pool->cu_mu);
     HIPCHK(hipMemsetAsync(d_bad, 0, 4 * (size_t)njobs, c->stream));
-    wrk::seg_decode_batch(jobs.data(), jobs.size(), bufs.pinned, d_once, c->stream);
+    size_t at = 0;
+    int launches = batch_chunk_launch(jobs, false, bufs.pinned, d_once, &at, c->stream);
+    launches += batch_chunk_launch(stranded, true, bufs.pinned, d_once, &at, c->stream);
     HIPCHK(hipGetLastError());
+    g_stat[WR_STAT_BATCH_CODER_LAUNCHES] += (unsigned long)launches;
     std::vector<unsigned int> bad(njobs, 0);
     HIPCHK(hipMemcpyAsync(bad.data(), d_bad, 4 * (size_t)njobs, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -3539,13 +3672,77 @@ int wr_dev_seg_decode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_
     return rc;
 }
 
+int wr_dev_seg_decode_batch(wr_ctx* c, int njobs, const unsigned char* const* d_blob, const size_t* blob_len, unsigned char* const* d_sym, size_t n,
+                            size_t* bad_segments)
+{
+    return dev_seg_decode_batch(c, njobs, d_blob, blob_len, d_sym, n, bad_segments, false);
+}
+
+int wr_dev_seg_decode_batch_mixed(wr_ctx* c, int njobs, const unsigned char* const* d_blob, const size_t* blob_len, unsigned char* const* d_sym, size_t n,
+                                  size_t* bad_segments)
+{
+    return dev_seg_decode_batch(c, njobs, d_blob, blob_len, d_sym, n, bad_segments, true);
+}
+
+// ---- the batch calls for WRS3: the encoders with `strands` (0: WR_STRANDS_DEFAULT), the decoders that take any mix of formats
+int wr_encode_host_seg_batch_strands(wr_ctx* c, int nfields, const double* const* h_flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                     const double* const* cutoffvecs, unsigned seg, unsigned brick, unsigned strands, wr_enc_info* infos,
+                                     unsigned char* const* data_encs, const size_t* caps, wr_timings* tm)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, h_flds, 0, &flds)) return rc;
+    return encode_seg_batch_impl(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, strands ? strands : WR_STRANDS_DEFAULT, infos, data_encs, caps, tm);
+}
+
+int wr_encode_host_seg_batch_strands_f32(wr_ctx* c, int nfields, const float* const* h_flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                         const double* const* cutoffvecs, unsigned seg, unsigned brick, unsigned strands, wr_enc_info* infos,
+                                         unsigned char* const* data_encs, const size_t* caps, wr_timings* tm)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, h_flds, 1, &flds)) return rc;
+    return encode_seg_batch_impl(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, strands ? strands : WR_STRANDS_DEFAULT, infos, data_encs, caps, tm);
+}
+
+int wr_encode_device_seg_batch_strands(wr_ctx* c, int nfields, double* const* d_flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                       const double* const* cutoffvecs, unsigned seg, unsigned brick, unsigned strands, wr_enc_info* infos,
+                                       unsigned char* const* data_encs, const size_t* caps, wr_timings* tm)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, d_flds, 2, &flds)) return rc;
+    return encode_seg_batch_impl(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, strands ? strands : WR_STRANDS_DEFAULT, infos, data_encs, caps, tm);
+}
+
+int wr_decode_host_seg_batch_mixed(wr_ctx* c, int nfields, double* const* h_flds, int nx, int ny, int nz, const wr_enc_info* infos,
+                                   const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, h_flds, 0, &flds)) return rc;
+    return decode_seg_batch_impl(c, nfields, flds, nx, ny, nz, infos, data_encs, data_lens, tm, true);
+}
+
+int wr_decode_host_seg_batch_mixed_f32(wr_ctx* c, int nfields, float* const* h_flds, int nx, int ny, int nz, const wr_enc_info* infos,
+                                       const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, h_flds, 1, &flds)) return rc;
+    return decode_seg_batch_impl(c, nfields, flds, nx, ny, nz, infos, data_encs, data_lens, tm, true);
+}
+
+int wr_decode_device_seg_batch_mixed(wr_ctx* c, int nfields, double* const* d_flds, int nx, int ny, int nz, const wr_enc_info* infos,
+                                     const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, d_flds, 2, &flds)) return rc;
+    return decode_seg_batch_impl(c, nfields, flds, nx, ny, nz, infos, data_encs, data_lens, tm, true);
+}
+
 int wr_encode_host_seg_batch(wr_ctx* c, int nfields, const double* const* h_flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
                              const double* const* cutoffvecs, unsigned seg, unsigned brick, wr_enc_info* infos, unsigned char* const* data_encs,
                              const size_t* caps, wr_timings* tm)
 {
     std::vector<FieldRef> flds;
     if (int rc = batch_fields(nfields, h_flds, 0, &flds)) return rc;
-    return encode_seg_batch_impl(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, infos, data_encs, caps, tm);
+    return encode_seg_batch_impl(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, 0, infos, data_encs, caps, tm);
 }
 
 int wr_decode_host_seg_batch(wr_ctx* c, int nfields, double* const* h_flds, int nx, int ny, int nz, const wr_enc_info* infos,
@@ -3562,7 +3759,7 @@ int wr_encode_host_seg_batch_f32(wr_ctx* c, int nfields, const float* const* h_f
 {
     std::vector<FieldRef> flds;
     if (int rc = batch_fields(nfields, h_flds, 1, &flds)) return rc;
-    return encode_seg_batch_impl(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, infos, data_encs, caps, tm);
+    return encode_seg_batch_impl(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, 0, infos, data_encs, caps, tm);
 }
 
 int wr_decode_host_seg_batch_f32(wr_ctx* c, int nfields, float* const* h_flds, int nx, int ny, int nz, const wr_enc_info* infos,
@@ -3579,7 +3776,7 @@ int wr_encode_device_seg_batch(wr_ctx* c, int nfields, double* const* d_flds, in
 {
     std::vector<FieldRef> flds;
     if (int rc = batch_fields(nfields, d_flds, 2, &flds)) return rc;
-    return encode_seg_batch_impl(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, infos, data_encs, caps, tm);
+    return encode_seg_batch_impl(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, 0, infos, data_encs, caps, tm);
 }
 
 int wr_decode_device_seg_batch(wr_ctx* c, int nfields, double* const* d_flds, int nx, int ny, int nz, const wr_enc_info* infos,

@@ -200,8 +200,8 @@ struct SegJob {
     unsigned long long* offs;   // nseg + 1 byte offsets of the segment streams behind the index (encode: set by seg_encode_batch)
     uint32_t* flags;            // decode: a flag per segment (0: decoded)
     unsigned int* bad;          // decode: the job's count of segments that did not decode (zeroed by the caller)
-    uint32_t seg, nseg, brick;  // brick != 0: a WRS2 blob with that brick edge in its header
-    uint32_t pad;
+    uint32_t seg, nseg, brick;  // brick != 0: a WRS2 blob with that brick edge in its header (a WRS3 blob: the edge, or 0)
+    uint32_t strands;           // 0: a WRS1 / WRS2 job; K: a WRS3 job of K strands per segment (the strand launchers below)
 };
 // The table of a launch sequence as it lies in device memory: the jobs, then first[njobs + 1], each 256-byte aligned.
 size_t seg_batch_table_bytes(size_t njobs);
@@ -246,6 +246,18 @@ struct StrandList {
 };
 size_t strand_lists_table_bytes(size_t njobs);
 size_t strand_decode_lists(const SegJob* jobs, const StrandList* lists, size_t njobs, uint8_t* host_table, uint8_t* table, hipStream_t st);
+// Stranded (WRS3) jobs through whole-plane launches.  Encode (k_strand_encode_batch, k_seg_scan_batch, k_strand_gather_batch):
+// seg_encode_batch with `strands` lanes per segment; all jobs share n, seg and strands, jobs[j].strands is set here and
+// jobs[j].brick goes into the header as it is.  `stage`: strand_batch_stage_bytes(njobs, n, seg, strands) of device memory laid
+// out as seg_encode_batch's, with tlens and slens behind lens and one region of the record's staging stride (kModelBound +
+// strands * strand_bound(L)) per segment of the launch.  Every blob is byte for byte strand_encode's.
+size_t strand_batch_stage_bytes(size_t njobs, size_t n, unsigned seg, unsigned strands);
+void strand_encode_batch(SegJob* jobs, size_t njobs, size_t n, unsigned seg, unsigned strands, uint8_t* host_table, uint8_t* stage,
+                         unsigned long long* result_host, hipStream_t st);
+// Decode (k_strand_decode_batch): every job has strands != 0; they may differ in n, seg, strands and brick.  first[] is the
+// prefix of wrsb::job_lanes(nseg_j, strands_j): a job's lanes rounded up to whole waves.  `table`, host_table: as
+// seg_decode_batch's.  Returns the lanes of the launch (a multiple of 64; the caller keeps them below 2^31).
+size_t strand_decode_batch(const SegJob* jobs, size_t njobs, uint8_t* host_table, uint8_t* table, hipStream_t st);
 
 // ---- the blocked symbol order of WRS2 (wr_blocked.hip; the order itself and its host geometry: wr_blocked.h).  `nat` is the
 // plane in natural order, `blk` the same n bytes in the blocked order, one array.  Forward: blk := nat permuted; inverse:

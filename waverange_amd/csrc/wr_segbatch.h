@@ -91,6 +91,20 @@ WRSB_HD unsigned long long lists_lanes(long long njobs, const size_t* nlist, con
     return run;
 }
 
+// ---- the lanes of a STRANDED ENCODE launch (k_strand_encode_batch): all jobs share K, first[0 .. njobs] is the exclusive
+// prefix of the jobs' SEGMENT counts as above, and lane g of the grid is strand g & (K - 1) of launch segment G = g >> log2(K),
+// which locate() resolves to (job, segment).  No padding between jobs: K divides kWaveLanes, so the K lanes of a segment stay
+// inside one wave and one job, while a wave may hold groups of several jobs.  The grid is rounded up to whole waves; a lane
+// with G >= first[njobs] is past the end (false, nothing written), and locate() is not asked about it.
+WRSB_HD bool strand_lane(const uint32_t* first, uint32_t njobs, unsigned strands, unsigned long long g, uint32_t* job, uint32_t* segment, uint32_t* strand)
+{
+    const unsigned long long G = g >> strands_shift(strands);
+    if (G >= first[njobs]) return false;
+    locate(first, njobs, (uint32_t)G, job, segment);
+    *strand = (uint32_t)(g & (strands - 1));
+    return true;
+}
+
 }  // namespace wrsb
 
 #endif

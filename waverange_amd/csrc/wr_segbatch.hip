@@ -16,6 +16,9 @@
 //                        planes of one stream, each with the union of the segments some regions need, go into one launch.
 //   k_strand_decode_list_batch   (at the end of the file) k_strand_decode<true> behind the locator: the WRS3 jobs of a region
 //                        decode over a batch of fields; a job's lanes are its list length times K, rounded up to a whole wave.
+//   k_strand_decode_batch        the same for whole planes: the WRS3 jobs of a mixed batch decode, every (field, plane) in one launch
+//   k_strand_encode_batch, k_strand_gather_batch   k_strand_encode and k_strand_gather behind the locator: plane l of a batch
+//                        of fields as WRS3, K lanes per segment of any of them (the scan is k_seg_scan_batch's)
 //
 // The coder steps are wr_segcoder.h's; the lane's tools and the lane programs themselves are wr_segcoder_dev.h's, the ones
 // wr_segcoder.hip's kernels call: every blob is byte for byte the single-plane kernels' blob.  A kernel here finds its job and
@@ -44,7 +47,8 @@ __global__ __launch_bounds__(kLanes) void k_seg_encode_batch(const SegJob* jobs,
     lens[g] = encode_segment_lane(LdsTable{tab + lane}, jobs[j].sym, view_of(jobs[j]), k, stage + g * stride_words, stride_words);
 }
 
-// Block j: results[2j], results[2j + 1] (and results_host's, if there) = the result pair of job j's scan
+// Block j: results[2j], results[2j + 1] (and results_host's, if there) = the result pair of job j's scan.  A stranded job
+// (job.strands != 0: strand_encode_batch's) gets the WRS3 header; the tables are zero-filled, so every other job carries 0.
 __global__ __launch_bounds__(kScanThreads) void k_seg_scan_batch(const SegJob* jobs, const uint32_t* first, const uint32_t* lens_all,
                                                                  unsigned long long* results, unsigned long long* results_host)
 {
@@ -52,7 +56,7 @@ __global__ __launch_bounds__(kScanThreads) void k_seg_scan_batch(const SegJob* j
     __shared__ unsigned int bad;
     const uint32_t j = blockIdx.x;
     const SegJob& job = jobs[j];
-    scan_lengths(part, &bad, threadIdx.x, lens_all + first[j], job.nseg, job.seg, job.brick, 0, job.offs, job.blob, job.cap, results + 2 * j,
+    scan_lengths(part, &bad, threadIdx.x, lens_all + first[j], job.nseg, job.seg, job.brick, job.strands, job.offs, job.blob, job.cap, results + 2 * j,
                  results_host ? results_host + 2 * j : nullptr);
 }
 
@@ -228,6 +232,79 @@ __global__ __launch_bounds__(kLanes) void k_strand_decode_list_batch(const SegJo
     }
 }
 
+// The same for whole planes: no lists, K and L from the job (job.strands != 0 in every job of the table), first[] the prefix
+// of wrsb::job_lanes(nseg_j, K_j).  Lane first[j] + r is strand r & (K - 1) of segment r >> log2(K); a segment id >= nseg is
+// padding.  Everything but the ids look-up is the list kernel's.
+__global__ __launch_bounds__(kLanes) void k_strand_decode_batch(const SegJob* jobs, const uint32_t* first, uint32_t njobs)
+{
+    __shared__ uint32_t tab[256 * kLanes];
+    const uint32_t lane = threadIdx.x;
+    const size_t g = (size_t)blockIdx.x * kLanes + lane;
+    bool live = g < first[njobs];
+    uint32_t jb = 0, r = 0;
+    if (live) wrsb::locate(first, njobs, (uint32_t)g, &jb, &r);
+    const SegJob& job = jobs[jb];  // (a lane past the end looks at job 0 and decodes nothing)
+    const uint32_t K = job.strands, j = r & (K - 1);
+    const size_t k = r >> wrsb::strands_shift(K);
+    live = live && k < job.nseg;
+    const uint32_t why = decode_strand_lane(LdsTable{tab + lane}, job.sym, view_of(job), K, wrseg::strand_len(job.seg, K), j, live, k);
+    if (live && j == 0) {
+        job.flags[k] = why;
+        if (why) atomicAdd(job.bad, 1u);
+    }
+}
+
+// k_strand_encode behind the locator.  All jobs share n, seg and K; first[] is the exclusive prefix of the jobs' segment
+// counts, as k_seg_encode_batch's.  Lane g of the grid is strand g & (K - 1) of launch segment G = g >> kshift
+// (wrsb::strand_lane); K divides kLanes, so the K lanes of a segment lie in one wave and one job, and a wave may hold groups of
+// two jobs -- the body touches only its own lane's plane and its group's columns.  A lane with G >= first[njobs] is not live:
+// it does not ask the locator, looks at job 0, and goes through the body to both barriers and the shuffles all the same.
+__global__ __launch_bounds__(kLanes) void k_strand_encode_batch(const SegJob* jobs, const uint32_t* first, uint32_t njobs, uint32_t K, uint32_t kshift,
+                                                                uint32_t L, uint32_t* stage, uint32_t stride_words, uint32_t* lens, uint32_t* tlens,
+                                                                uint32_t* slens)
+{
+    __shared__ uint32_t tab[256 * kLanes];
+    const uint32_t lane = threadIdx.x, j = lane & (K - 1);
+    const size_t G = ((size_t)blockIdx.x * kLanes + lane) >> kshift;
+    const bool live = G < first[njobs];
+    uint32_t jb = 0, k = 0;
+    if (live) wrsb::locate(first, njobs, (uint32_t)G, &jb, &k);
+    const SegJob& job = jobs[jb];
+    encode_strand_lane(tab, lane, job.sym, view_of(job), K, L, live, k, stage + G * stride_words, slens + G * K + j, tlens + G, lens + G);
+}
+
+// Segment g of the launch is segment k of job j: record k of blob_j := region g, as k_strand_gather writes it.  Nothing of a job
+// is written unless its whole blob fits under its cap and its every record is good.
+__global__ __launch_bounds__(kGatherThreads) void k_strand_gather_batch(const SegJob* jobs, const uint32_t* first, uint32_t njobs, const uint32_t* stage,
+                                                                        uint32_t stride_words, const uint32_t* lens, const uint32_t* tlens,
+                                                                        const uint32_t* slens, uint32_t K, uint32_t sb_words, const unsigned long long* results)
+{
+    const size_t total = first[njobs];
+    for (size_t g = blockIdx.x; g < total; g += gridDim.x) {
+        uint32_t j, k;
+        wrsb::locate(first, njobs, (uint32_t)g, &j, &k);
+        const SegJob& job = jobs[j];
+        if (results[2 * j] > job.cap || results[2 * j + 1]) continue;
+        const size_t front = wrseg::kHeaderBytesStrands + 4 * (size_t)job.nseg;
+        gather_record(job.blob + front + job.offs[k], stage + g * stride_words, tlens[g], slens + g * K, K, sb_words, lens[g], threadIdx.x);
+    }
+}
+
+// the staging of a stranded encode launch behind the table and the result pairs: offs, lens, tlens, slens, the regions
+struct StrandStage {
+    size_t nseg, at_offs, at_lens, at_regions, bytes;
+    uint32_t sb_words, stride_words;
+    StrandStage(size_t njobs, size_t n, unsigned seg, unsigned strands) : nseg(wrseg::seg_count(n, seg))
+    {
+        sb_words = wrseg::strand_bound(wrseg::strand_len(seg, strands)) / 4;
+        stride_words = wrseg::kModelBound / 4 + strands * sb_words;
+        at_offs = seg_batch_table_bytes(njobs) + up256(16 * njobs);
+        at_lens = at_offs + up256(8 * (nseg + 1) * njobs);
+        at_regions = at_lens + up256(4 * nseg * njobs * (2 + (size_t)strands));
+        bytes = at_regions + njobs * nseg * 4 * (size_t)stride_words;
+    }
+};
+
 }  // namespace
 
 size_t strand_lists_table_bytes(size_t njobs) { return seg_batch_table_bytes(njobs) + up256(njobs * sizeof(StrandList)); }
@@ -241,6 +318,50 @@ size_t strand_decode_lists(const SegJob* jobs, const StrandList* lists, size_t n
     (void)hipMemcpyAsync(table, host_table, strand_lists_table_bytes(njobs), hipMemcpyHostToDevice, st);
     hipLaunchKernelGGL(k_strand_decode_list_batch, dim3((unsigned)(total / kLanes)), dim3(kLanes), 0, st, table_jobs(table),
                        table_lists<StrandList>(table, njobs), table_first(table, njobs), (uint32_t)njobs);
+    return total;
+}
+
+size_t strand_batch_stage_bytes(size_t njobs, size_t n, unsigned seg, unsigned strands) { return StrandStage(njobs, n, seg, strands).bytes; }
+
+void strand_encode_batch(SegJob* jobs, size_t njobs, size_t n, unsigned seg, unsigned strands, uint8_t* host_table, uint8_t* stage,
+                         unsigned long long* result_host, hipStream_t st)
+{
+    const StrandStage sg(njobs, n, seg, strands);
+    const size_t nseg = sg.nseg;
+    unsigned long long* const results = seg_batch_results(stage, njobs);
+    unsigned long long* const offs = reinterpret_cast<unsigned long long*>(stage + sg.at_offs);
+    uint32_t* const lens = reinterpret_cast<uint32_t*>(stage + sg.at_lens);
+    uint32_t* const tlens = lens + nseg * njobs;
+    uint32_t* const slens = tlens + nseg * njobs;
+    uint32_t* const regions = reinterpret_cast<uint32_t*>(stage + sg.at_regions);
+    for (size_t j = 0; j < njobs; j++) {
+        jobs[j].n = n; jobs[j].seg = seg; jobs[j].nseg = (uint32_t)nseg; jobs[j].strands = strands;
+        jobs[j].offs = offs + j * (nseg + 1);
+    }
+    const size_t total = seg_batch_table_fill(host_table, jobs, njobs);
+    (void)hipMemcpyAsync(stage, host_table, seg_batch_table_bytes(njobs), hipMemcpyHostToDevice, st);
+    const SegJob* const d_jobs = table_jobs(stage);
+    const uint32_t* const d_first = table_first(stage, njobs);
+    if (total)
+        hipLaunchKernelGGL(k_strand_encode_batch, dim3((unsigned)((total * strands + kLanes - 1) / kLanes)), dim3(kLanes), 0, st, d_jobs, d_first,
+                           (uint32_t)njobs, (uint32_t)strands, wrsb::strands_shift(strands), wrseg::strand_len(seg, strands), regions, sg.stride_words, lens,
+                           tlens, slens);
+    hipLaunchKernelGGL(k_seg_scan_batch, dim3((unsigned)njobs), dim3(kScanThreads), 0, st, d_jobs, d_first, lens, results, result_host);
+    if (total) {
+        const unsigned grid = (unsigned)(total < 65536 ? total : 65536);
+        hipLaunchKernelGGL(k_strand_gather_batch, dim3(grid), dim3(kGatherThreads), 0, st, d_jobs, d_first, (uint32_t)njobs, regions, sg.stride_words, lens,
+                           tlens, slens, (uint32_t)strands, sg.sb_words, results);
+    }
+}
+
+size_t strand_decode_batch(const SegJob* jobs, size_t njobs, uint8_t* host_table, uint8_t* table, hipStream_t st)
+{
+    // the table of seg_decode_batch with first[] over the jobs' lanes (whole waves each)
+    const size_t total = table_fill(host_table, jobs, njobs, nullptr, 0, [&](size_t j) { return (size_t)wrsb::job_lanes(jobs[j].nseg, jobs[j].strands); });
+    if (!total) return 0;
+    (void)hipMemcpyAsync(table, host_table, seg_batch_table_bytes(njobs), hipMemcpyHostToDevice, st);
+    hipLaunchKernelGGL(k_strand_decode_batch, dim3((unsigned)(total / kLanes)), dim3(kLanes), 0, st, table_jobs(table), table_first(table, njobs),
+                       (uint32_t)njobs);
     return total;
 }
 

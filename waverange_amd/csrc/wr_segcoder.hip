@@ -12,8 +12,8 @@
 //   k_seg_decode   lane k: stream of segment k (at offs[k] in the blob) -> the plane's symbols [k*seg, k*seg + bs); with a
 //                  list of segment ids, lane j takes segment ids[j] and the others are left alone (a low-resolution decode)
 //
-// What a lane does once it knows its segment -- code it, scan the lengths, copy a staged piece, decode a segment, decode a
-// strand -- is written once, in wr_segcoder_dev.h, for these kernels and the batched ones of wr_segbatch.hip.  A kernel here
+// What a lane does once it knows its segment -- code it, scan the lengths, copy a staged piece, decode a segment, code, gather
+// or decode a strand -- is written once, in wr_segcoder_dev.h, for these kernels and the batched ones of wr_segbatch.hip.  A kernel here
 // finds its segment (the grid index or an id list), hands the body its arguments as they stand, and stores what it returns.
 #include "wr_kernels.h"
 #include "wr_segbatch.h"
@@ -90,58 +90,11 @@ __global__ __launch_bounds__(kLanes) void k_strand_encode(PlaneRef sym, size_t n
                                                           uint32_t* stage, uint32_t stride_words, uint32_t* lens, uint32_t* tlens, uint32_t* slens)
 {
     __shared__ uint32_t tab[256 * kLanes];
-    const uint32_t lane = threadIdx.x, j = lane & (K - 1), g0 = lane - j;
+    const uint32_t lane = threadIdx.x, j = lane & (K - 1);
     const size_t k = ((size_t)blockIdx.x * kLanes + lane) >> kshift;
-    // all 64 lanes reach both barriers and the shuffles below: a lane past the end, or of an empty strand, has m == 0
+    // all 64 lanes go through the body, to its barriers and shuffles: a lane past the end is not live
     const bool live = k < nseg;
-    const size_t base = live ? k * seg : 0;
-    const uint32_t bs = !live ? 0 : n - base < seg ? (uint32_t)(n - base) : seg;
-    const uint32_t s0 = j * L, m = s0 < bs ? (bs - s0 < L ? bs - s0 : L) : 0;
-    LdsTable t{tab + lane};
-    for (uint32_t s = 0; s < 256; s++) t.set(s, 0);
-    PlaneSource src{SegSpan(sym, m ? base + s0 : 0, m)};
-    if (m) wrseg::count_symbols(t, src, m);
-    __syncthreads();
-    // The K partial counts of a symbol row -> their sum, into all K columns.  Rows s = j, j + K, ... are lane j's and nobody
-    // else's between the two barriers, so no lane reads a row that another one is writing.  At step i the K lanes of a
-    // group are in K different columns (banks), and different groups in different columns anyway.
-    for (uint32_t s = j; s < 256; s += K) {
-        uint32_t* const row = tab + s * kLanes + g0;
-        uint32_t c = 0;
-        for (uint32_t i = 0; i < K; i++) c += row[(i + j) & (K - 1)];
-        for (uint32_t i = 0; i < K; i++) row[(i + j) & (K - 1)] = c;
-    }
-    __syncthreads();
-    wrseg::counts_to_model(t);
-    const uint32_t sb = wrseg::strand_bound(L);
-    uint32_t* const region = live ? stage + k * stride_words : stage;  // (only used by live lanes)
-    uint32_t tlen = 0, slen = 0, over = 0;
-    if (live && j == 0) {
-        wrseg::Enc<WordSink> e;
-        e.out = WordSink{region, wrseg::kModelBound, 0, 0, false};
-        wrseg::encode_model(e, t);
-        e.out.flush();
-        tlen = e.out.pos;
-        over |= e.out.overflow;
-    }
-    if (m) {
-        wrseg::Enc<WordSink> e;
-        e.out = WordSink{region + wrseg::kModelBound / 4 + j * (sb / 4), sb, 0, 0, false};
-        wrseg::encode_strand(e, t, src, m, bs);
-        e.out.flush();
-        slen = e.out.pos;
-        over |= e.out.overflow;  // (cannot happen: the regions are the bounds)
-    }
-    if (live) slens[k * K + j] = slen;
-    uint32_t sum = tlen + slen;
-    for (uint32_t off = 1; off < K; off <<= 1) {
-        sum += __shfl_xor(sum, (int)off);
-        over |= __shfl_xor(over, (int)off);
-    }
-    if (live && j == 0) {
-        tlens[k] = tlen;
-        lens[k] = over ? 0xffffffffu : (4 * (K + 1) + sum + 3) & ~3u;
-    }
+    encode_strand_lane(tab, lane, sym, SegView{n, seg, nseg}, K, L, live, k, stage + k * stride_words, slens + k * K + j, tlens + k, lens + k);
 }
 
 // k_seg_scan for the WRS3 header.  strands != 0 (strand_encode's callers see to it): with 0 the body would write a WRS1 / WRS2 header
@@ -163,22 +116,8 @@ __global__ __launch_bounds__(kGatherThreads) void k_strand_gather(const uint32_t
     if (result[0] > cap || result[1]) return;
     const size_t front = wrseg::kHeaderBytesStrands + 4 * (size_t)nseg;
     const uint32_t t = threadIdx.x;
-    for (size_t k = blockIdx.x; k < nseg; k += gridDim.x) {
-        const uint32_t* const region = stage + k * stride_words;
-        uint8_t* const rec = blob + front + offs[k];  // 4-byte aligned: the blob is, and every length before it is a multiple of 4
-        const uint32_t tlen = tlens[k];
-        if (t == 0) reinterpret_cast<uint32_t*>(rec)[0] = tlen;
-        else if (t <= K) reinterpret_cast<uint32_t*>(rec)[t] = slens[k * K + t - 1];
-        uint32_t at = 4 * (K + 1);
-        copy_piece(rec + at, region, tlen, t);
-        at += tlen;
-        for (uint32_t j = 0; j < K; j++) {
-            const uint32_t sl = slens[k * K + j];
-            if (sl) copy_piece(rec + at, region + wrseg::kModelBound / 4 + j * sb_words, sl, t);
-            at += sl;
-        }
-        if (t < lens[k] - at) rec[at + t] = 0;
-    }
+    for (size_t k = blockIdx.x; k < nseg; k += gridDim.x)
+        gather_record(blob + front + offs[k], stage + k * stride_words, tlens[k], slens + k * K, K, sb_words, lens[k], t);
 }
 
 // kList as k_seg_decode: the grid's lane groups take the segments ids[0 .. nlist), otherwise the segments 0 .. nseg.

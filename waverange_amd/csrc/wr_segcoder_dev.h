@@ -1,5 +1,5 @@
 // wr_segcoder_dev.h -- what a lane of the segment coder kernels works with (its column of the wave's LDS table, the symbols of
-// its segment in a plane, the sinks of coded words and decoded symbols) and, behind them, what it does: the five lane programs.
+// its segment in a plane, the sinks of coded words and decoded symbols) and, behind them, what it does: the seven lane programs.
 // Shared by wr_segcoder.hip (one plane per launch) and wr_segbatch.hip (the planes of a batch of fields per launch).
 #ifndef WR_SEGCODER_DEV_H
 #define WR_SEGCODER_DEV_H
@@ -255,6 +255,86 @@ __device__ inline uint32_t decode_strand_lane(LdsTable t, const PlaneRef& sym, c
     }
     for (uint32_t off = 1; off < K; off <<= 1) why |= __shfl_xor(why, (int)off);
     return why;
+}
+
+// The encoder's side of a record.  Lane `lane` of the wave is strand j = lane & (K - 1) of segment k: histogram of the strand
+// into the lane's column -> the K columns of the segment summed, the sum in all K of them -> the segment's model -> S_j into
+// its own piece of the record's staging region [region, region + kModelBound / 4 + K * strand_bound(L) / 4); strand 0 also T,
+// at the region's start.  A live lane stores the strand's length at *slen as soon as it has it; strand 0's lane then T's length
+// at *tlen and the record's at *len, 0xffffffff if a piece outgrew its bound (it cannot: the pieces are the bounds).  tab: the
+// wave's whole table.  EVERY lane of the wave comes here and reaches both barriers and the shuffles: a lane past the end has
+// live == false (k, region and the three places are then not looked at) and, like the lane of an empty strand, m == 0.  The K lanes of a segment
+// agree on live, k and region; different groups of a wave may belong to different planes.
+__device__ inline void encode_strand_lane(uint32_t* tab, uint32_t lane, const PlaneRef& sym, const SegView& v, uint32_t K, uint32_t L, bool live, size_t k,
+                                              uint32_t* region, uint32_t* slen_at, uint32_t* tlen_at, uint32_t* len_at)
+{
+    const uint32_t j = lane & (K - 1), g0 = lane - j;
+    const size_t base = live ? v.base(k) : 0;
+    const uint32_t bs = live ? v.len(k) : 0;
+    const uint32_t s0 = j * L, m = s0 < bs ? (bs - s0 < L ? bs - s0 : L) : 0;
+    LdsTable t{tab + lane};
+    for (uint32_t s = 0; s < 256; s++) t.set(s, 0);
+    PlaneSource src{SegSpan(sym, m ? base + s0 : 0, m)};
+    if (m) wrseg::count_symbols(t, src, m);
+    __syncthreads();
+    // The K partial counts of a symbol row -> their sum, into all K columns.  Rows s = j, j + K, ... are lane j's and nobody
+    // else's between the two barriers, so no lane reads a row that another one is writing.  At step i the K lanes of a
+    // group are in K different columns (banks), and different groups in different columns anyway.
+    for (uint32_t s = j; s < 256; s += K) {
+        uint32_t* const row = tab + s * kLanes + g0;
+        uint32_t c = 0;
+        for (uint32_t i = 0; i < K; i++) c += row[(i + j) & (K - 1)];
+        for (uint32_t i = 0; i < K; i++) row[(i + j) & (K - 1)] = c;
+    }
+    __syncthreads();
+    wrseg::counts_to_model(t);
+    const uint32_t sb = wrseg::strand_bound(L);
+    uint32_t tlen = 0, slen = 0, over = 0;
+    if (live && j == 0) {
+        wrseg::Enc<WordSink> e;
+        e.out = WordSink{region, wrseg::kModelBound, 0, 0, false};
+        wrseg::encode_model(e, t);
+        e.out.flush();
+        tlen = e.out.pos;
+        over |= e.out.overflow;
+    }
+    if (m) {
+        wrseg::Enc<WordSink> e;
+        e.out = WordSink{region + wrseg::kModelBound / 4 + j * (sb / 4), sb, 0, 0, false};
+        wrseg::encode_strand(e, t, src, m, bs);
+        e.out.flush();
+        slen = e.out.pos;
+        over |= e.out.overflow;  // (cannot happen: the regions are the bounds)
+    }
+    if (live) *slen_at = slen;
+    uint32_t sum = tlen + slen;
+    for (uint32_t off = 1; off < K; off <<= 1) {
+        sum += __shfl_xor(sum, (int)off);
+        over |= __shfl_xor(over, (int)off);
+    }
+    if (live && j == 0) {
+        *tlen_at = tlen;
+        *len_at = over ? 0xffffffffu : (4 * (K + 1) + sum + 3) & ~3u;
+    }
+}
+
+// rec[0, len) := a record from its staging region, by the kGatherThreads threads of a block (t = threadIdx.x): the length
+// words (tlen, then slens[0, K)), T, the strands behind one another, and zeros up to len.  rec is 4-byte aligned: the blob
+// is, and every length before it is a multiple of 4.
+__device__ inline void gather_record(uint8_t* rec, const uint32_t* region, uint32_t tlen, const uint32_t* slens, uint32_t K, uint32_t sb_words, uint32_t len,
+                                     uint32_t t)
+{
+    if (t == 0) reinterpret_cast<uint32_t*>(rec)[0] = tlen;
+    else if (t <= K) reinterpret_cast<uint32_t*>(rec)[t] = slens[t - 1];
+    uint32_t at = 4 * (K + 1);
+    copy_piece(rec + at, region, tlen, t);
+    at += tlen;
+    for (uint32_t j = 0; j < K; j++) {
+        const uint32_t sl = slens[j];
+        if (sl) copy_piece(rec + at, region + wrseg::kModelBound / 4 + j * sb_words, sl, t);
+        at += sl;
+    }
+    if (t < len - at) rec[at + t] = 0;
 }
 
 }  // namespace
