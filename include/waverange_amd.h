@@ -207,6 +207,8 @@ int wr_set_device_slots(int device, int nslots);
 #define WR_STAT_BATCH_CODER_LAUNCHES 18 /* coder kernel launches (k_*_encode_batch, k_*_decode_batch) of the batch calls, whole path
                                           and stage level: one per plane index of an encode and of wr_decode_*_seg_batch, at most two
                                           per wr_decode_*_seg_batch_mixed while neither kind of job exceeds WR_SEG_BATCH_MAX */
+#define WR_STAT_QUALITY_CODER_RUNS 19 /* planes the encodes to an RMS / PSNR target (wr_encode_*_seg_quality, any norm) have handed to
+                                        the segment coder: info->nlay per call */
 unsigned long wr_stat(int what);
 /* Hands the idle buffers of the device's plane pool back to the device (the pool keeps the plane memory of finished calls for
  * the next ones: after a burst of concurrent calls that can be most of the HBM).  Buffers in use are not touched. */
@@ -484,8 +486,79 @@ int wr_seg_error_host(wr_ctx *ctx, const double *h_fld, int nx, int ny, int nz, 
 int wr_seg_error_host_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny, int nz, const wr_enc_info *info,
                           const unsigned char *data_enc, size_t data_len, double *err);
 /* measurement hook: HIP-event milliseconds of the three stages of a trial -- the coefficient sum, the inverse, the compare --
- * summed over the trials of the context's last encode to an error bound (null pointers are skipped) */
+ * summed over the trials of the context's last encode to an error bound or to a quality target (null pointers are skipped) */
 int wr_ctx_bounded_trial_ms(wr_ctx *ctx, double *requant_ms, double *inverse_ms, double *compare_ms);
+/* ---- Encode to an RMS error or a PSNR target: the same search in the L2 norm, every plane coded once.
+ * Definitions.  For a field f of n samples and a grid point g, r_g is as above (bit for bit the decoder's reconstruction of the
+ * plain call's stream at t(g); for an fp32 field the fp32 reconstruction).  d_j = fl(f_j - r_j) in fp64, both operands widened
+ * first for fp32; q_j = fl(d_j * d_j), ONE rounding (the library is built with -ffp-contract=off: this is not an FMA);
+ * S*(g) = sum_j q_j, the real-number sum over the finite d_j; R*(g) = sqrt(S*(g) / n).  What the library computes is S(g), an
+ * fp64 summation of the same q_j, and R(g) = fl(sqrt(fl(S / n))).  Two guarantees:
+ *   reproducible   the same n, the same alignment class of the two pointers (both aligned for two-sample loads -- 16 bytes
+ *                  fp64, 8 bytes fp32 -- or not) and the same library give the same bits on every run: per-thread partial sums
+ *                  in index order, then a fixed tree over lanes, waves and blocks; no floating-point atomics, nothing depends
+ *                  on the order in which blocks finish.  (Inside the calls below both arrays are always aligned.)
+ *   accurate       |S - S*| <= 2^-36 * S* for every n <= 2^33 (the kernel's derivation gives 2^-38: csrc/wr_kernels.hip).
+ * A q_j that overflows makes S = R = +inf, which holds no target.  range = hi - lo of the field, the values every encode's
+ * prologue forms; PSNR = 20 log10(range / R), +inf for R = 0.
+ * wr_psnr_rms(db, lo, hi) = (hi - lo) * pow(10, -db / 20): the RMS error that PSNR db means on a field of that range; NaN unless
+ * db is finite and hi - lo is a positive finite number.  A PSNR target is converted with it once, on the host, and the value
+ * is returned in res->max_rms: the contract is stated on R against THAT value, so nothing depends on libm's last bit.
+ * The call.  wr_encode_*_seg_quality take the arguments of the _bounded calls with max_abs_err replaced by (norm, target):
+ *   WR_NORM_MAX    target is max_abs_err: g, info and data_enc are the bounded call's; res->max_abs = E(g), res->range is
+ *                  filled, res->rms, sumsq, psnr and max_rms are NaN (not measured)
+ *   WR_NORM_RMS    target is max_rms, in the field's units
+ *   WR_NORM_PSNR   target is in dB over the field's range; max_rms = wr_psnr_rms(target, lo, hi)
+ * For WR_NORM_RMS and WR_NORM_PSNR, with g_min = wr_budget_index(tol_min), they return a g in [g_min, WR_BUDGET_GMAX] such that
+ *   it holds         res->rms == R(g) <= res->max_rms; res->sumsq == S(g), res->max_abs == E(g), res->psnr from R(g) and range;
+ *   it is tight      g == WR_BUDGET_GMAX, or the call formed R(g + 1) and it exceeds max_rms (R is not monotone: the local
+ *                    property is the contract, as for E);
+ *   it is the same   info and data_enc are bit for bit the plain call's of the chosen format at cutoffvec = { t(g) };
+ *   coded once       WR_STAT_QUALITY_CODER_RUNS grows by info->nlay (for every norm; WR_STAT_BOUNDED_CODER_RUNS does not move).
+ * The walk starts at wr_bounded_start(max_rms, absmax): R never exceeds E, so that point normally holds and the walk goes
+ * coarser.  A constant field gives nlay = 0, g = WR_BUDGET_GMAX, rms = sumsq = max_abs = 0, trials = 0, psnr = +inf and
+ * range = 2 * info->halfspanval.  WR_ERR_BOUND: R(g_min) > max_rms; wr_last_error() names R(g_min), data_enc is not written.
+ * WR_ERR_ARG: an unknown norm, a target that is not a positive finite number, a PSNR target on a field with range == 0, and
+ * everything the bounded calls refuse that way (a NaN or an infinity in the field among it); WR_ERR_UNSUPPORTED as there.
+ * wtflag = 0 is supported.  Device memory as the bounded calls.
+ * wr_seg_error_stats_host / _f32: the measuring half, as wr_seg_error_host, filling a record: max_abs, sumsq = S, rms = R (the
+ * same kernel on arrays of the same alignment class: the bits the encode reported), lo and hi of h_fld (NaNs skipped, as the
+ * prologue's), psnr, and the count of differences that are not finite.  WR_ERR_ARG when nonfinite > 0, the record still filled.
+ * wr_dev_err_stats / _f32: the compare alone on two device arrays of n >= 1 samples, of any alignment; lo, hi and psnr are not
+ * its business and come back as NaN.  It returns WR_OK whatever nonfinite is. */
+enum { WR_NORM_MAX = 1, WR_NORM_RMS = 2, WR_NORM_PSNR = 3 };
+typedef struct wr_quality_result {
+    int g;          /* the grid point chosen */
+    double tolrel;  /* t(g) */
+    double max_abs; /* E(g) */
+    double rms;     /* R(g) */
+    double sumsq;   /* S(g) */
+    double range;   /* hi - lo of the field */
+    double psnr;    /* 20 log10(range / R(g)), +inf for R(g) = 0 */
+    double max_rms; /* the RMS target R(g) was held against: `target`, or what a PSNR target was converted to */
+    int trials;     /* tolerances whose reconstruction was formed */
+} wr_quality_result;
+typedef struct wr_error_stats {
+    double max_abs, sumsq, rms, lo, hi, psnr;
+    unsigned long long nonfinite;
+} wr_error_stats;
+double wr_psnr_rms(double db, double lo, double hi);
+int wr_encode_host_seg_quality(wr_ctx *ctx, const double *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                               int norm, double target, double tol_min, unsigned seg, unsigned brick, unsigned strands,
+                               wr_enc_info *info, unsigned char *data_enc, size_t cap, wr_timings *tm, wr_quality_result *res);
+int wr_encode_host_seg_quality_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                   int norm, double target, double tol_min, unsigned seg, unsigned brick, unsigned strands,
+                                   wr_enc_info *info, unsigned char *data_enc, size_t cap, wr_timings *tm,
+                                   wr_quality_result *res);
+int wr_encode_device_seg_quality(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                 int norm, double target, double tol_min, unsigned seg, unsigned brick, unsigned strands,
+                                 wr_enc_info *info, unsigned char *data_enc, size_t cap, wr_timings *tm, wr_quality_result *res);
+int wr_seg_error_stats_host(wr_ctx *ctx, const double *h_fld, int nx, int ny, int nz, const wr_enc_info *info,
+                            const unsigned char *data_enc, size_t data_len, wr_error_stats *stats);
+int wr_seg_error_stats_host_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny, int nz, const wr_enc_info *info,
+                                const unsigned char *data_enc, size_t data_len, wr_error_stats *stats);
+int wr_dev_err_stats(wr_ctx *ctx, const double *d_a, const double *d_b, size_t n, wr_error_stats *stats);
+int wr_dev_err_stats_f32(wr_ctx *ctx, const float *d_a, const float *d_b, size_t n, wr_error_stats *stats);
 /* ---- Low-resolution decode of segmented streams: a coarse version of the field without decoding the field.
  * The transform is a Mallat decomposition (waveletcdf97_3d.c:73-78): after level r the low-pass coefficients of an nx*ny*nz
  * field sit in the corner box [0,bx) x [0,by) x [0,bz) of the coefficient array.  With h(n) = (n + 1) / 2 in integer

@@ -70,6 +70,24 @@ class BoundedResult(C.Structure):
     _fields_ = [("g", C.c_int), ("tolrel", C.c_double), ("err", C.c_double), ("trials", C.c_int)]
 
 
+class QualityResult(C.Structure):
+    """wr_quality_result"""
+    _fields_ = [("g", C.c_int), ("tolrel", C.c_double), ("max_abs", C.c_double), ("rms", C.c_double), ("sumsq", C.c_double),
+                ("range", C.c_double), ("psnr", C.c_double), ("max_rms", C.c_double), ("trials", C.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ErrorStats(C.Structure):
+    """wr_error_stats"""
+    _fields_ = [("max_abs", C.c_double), ("sumsq", C.c_double), ("rms", C.c_double), ("lo", C.c_double), ("hi", C.c_double),
+                ("psnr", C.c_double), ("nonfinite", C.c_ulonglong)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class FusedLevel(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("tiles_x", "tiles_y", "zps", "zsegs", "zlast")]
 
@@ -224,6 +242,18 @@ def lib():
     L.wr_seg_error_host.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(EncInfo), _vp, C.c_size_t, _dp]
     L.wr_seg_error_host_f32.argtypes = L.wr_seg_error_host.argtypes
     L.wr_ctx_bounded_trial_ms.argtypes = [_vp, _dp, _dp, _dp]
+    # an encode to an RMS / PSNR target, its measuring half and the compare alone
+    L.wr_psnr_rms.argtypes = [C.c_double, C.c_double, C.c_double]
+    L.wr_psnr_rms.restype = C.c_double
+    L.wr_encode_host_seg_quality.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                             C.c_uint, C.c_uint, C.c_uint, C.POINTER(EncInfo), _vp, C.c_size_t, C.POINTER(Timings),
+                                             C.POINTER(QualityResult)]
+    L.wr_encode_host_seg_quality_f32.argtypes = L.wr_encode_host_seg_quality.argtypes
+    L.wr_encode_device_seg_quality.argtypes = L.wr_encode_host_seg_quality.argtypes
+    L.wr_seg_error_stats_host.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(EncInfo), _vp, C.c_size_t, C.POINTER(ErrorStats)]
+    L.wr_seg_error_stats_host_f32.argtypes = L.wr_seg_error_stats_host.argtypes
+    L.wr_dev_err_stats.argtypes = [_vp, _vp, _vp, C.c_size_t, C.POINTER(ErrorStats)]
+    L.wr_dev_err_stats_f32.argtypes = L.wr_dev_err_stats.argtypes
     L.wr_encode_device_seg.argtypes = L.wr_encode_host_seg.argtypes
     L.wr_decode_host_seg.argtypes = L.wr_decode_host.argtypes
     L.wr_decode_host_seg_f32.argtypes = L.wr_decode_host.argtypes
@@ -377,6 +407,7 @@ STAT_ROI_SEGMENTS, STAT_ROI_BYTES_UP = 13, 14
 STAT_ROI_CODER_LAUNCHES = 15
 STAT_BUDGET_CODER_RUNS = 16
 STAT_BOUNDED_CODER_RUNS = 17
+STAT_QUALITY_CODER_RUNS = 19
 
 
 def stat(what):
@@ -492,6 +523,7 @@ BUDGET_GMAX = 3840
 BUDGET_PROBE_MAX = 8
 ERR_BUDGET = -6
 ERR_BOUND = -7
+NORM_MAX, NORM_RMS, NORM_PSNR = 1, 2, 3
 
 
 def budget_tol(g):
@@ -508,6 +540,12 @@ def bounded_start(max_abs_err, absmax):
     """The largest g with budget_tol(g) * absmax <= max_abs_err, clamped to the grid; -1 when even budget_tol(0) is too coarse
     or an argument is not a positive finite number (wr_bounded_start)."""
     return int(lib().wr_bounded_start(float(max_abs_err), float(absmax)))
+
+
+def psnr_rms(db, lo, hi):
+    """The RMS error that a PSNR of `db` over the range hi - lo means, (hi - lo) * 10 ** (-db / 20); NaN unless db is finite and
+    the range a positive finite number (wr_psnr_rms)."""
+    return float(lib().wr_psnr_rms(float(db), float(lo), float(hi)))
 
 
 def seg_size_bound_host_ref(plane, seg=0):
@@ -1419,6 +1457,77 @@ class Context:
     def encode_seg_bounded(self, buf, shape, max_abs_err, tol_min=2.0 ** -60, seg=0, brick=0, strands=0, wtflag=1, out=None, m=(1, 1, 1)):
         """encode_host_seg_bounded with the field resident on the device (`buf` is consumed, as by encode)."""
         return self._encode_seg_bounded(lib().wr_encode_device_seg_bounded, buf.ptr, shape, max_abs_err, tol_min, wtflag, seg, brick, strands, out, m)
+
+    # ---- encode to an RMS error or a PSNR target: the same search in the L2 norm
+    def _encode_seg_quality(self, fn, ptr, shape, norm, target, tol_min, wtflag, seg, brick, strands, out, m):
+        nz, ny, nx = shape
+        cap = self._seg_cap(shape, seg, brick if brick else None, strands if strands else None)
+        data = out if out is not None else np.empty(cap, dtype=np.uint8)
+        info, tm, res = EncInfo(), Timings(), QualityResult()
+        _check(fn(self.h, ptr, nx, ny, nz, wtflag, m[0], m[1], m[2], int(norm), float(target), float(tol_min), seg, brick, strands, C.byref(info),
+                  data.ctypes.data, data.size, C.byref(tm), C.byref(res)))
+        d = info.as_dict()
+        d["data"] = data[:info.ntot_enc]
+        r = res.as_dict()
+        r["timings"] = tm.as_dict()
+        return d, d["data"], r
+
+    def encode_host_seg_quality(self, fld, norm, target, tol_min=2.0 ** -60, seg=0, brick=0, strands=0, wtflag=1, out=None, m=(1, 1, 1)):
+        """The segmented stream of `fld` at the coarsest tolerance of the grid, not below tol_min, that holds the target while the
+        next coarser point does not (wr_encode_host_seg_quality).  norm = NORM_RMS: target is the RMS error allowed, in the
+        field's units; NORM_PSNR: target is in dB over the field's range and result["max_rms"] is what it was converted to;
+        NORM_MAX: target is the pointwise bound of encode_host_seg_bounded.  Returns (info, data, result): result holds g, tolrel,
+        max_abs, rms, sumsq, range, psnr, max_rms, trials (QualityResult)."""
+        assert fld.dtype == np.float64 and fld.flags["C_CONTIGUOUS"]
+        return self._encode_seg_quality(lib().wr_encode_host_seg_quality, fld.ctypes.data, fld.shape, norm, target, tol_min, wtflag, seg, brick, strands, out, m)
+
+    def encode_host_seg_quality_f32(self, fld, norm, target, tol_min=2.0 ** -60, seg=0, brick=0, strands=0, wtflag=1, out=None, m=(1, 1, 1)):
+        if not (isinstance(fld, np.ndarray) and fld.dtype == np.float32 and fld.flags["C_CONTIGUOUS"]):
+            raise TypeError("encode_host_seg_quality_f32: a C-contiguous float32 array is required")
+        return self._encode_seg_quality(lib().wr_encode_host_seg_quality_f32, fld.ctypes.data, fld.shape, norm, target, tol_min, wtflag, seg, brick, strands, out, m)
+
+    def encode_seg_quality(self, buf, shape, norm, target, tol_min=2.0 ** -60, seg=0, brick=0, strands=0, wtflag=1, out=None, m=(1, 1, 1)):
+        """encode_host_seg_quality with the field resident on the device (`buf` is consumed, as by encode)."""
+        return self._encode_seg_quality(lib().wr_encode_device_seg_quality, buf.ptr, shape, norm, target, tol_min, wtflag, seg, brick, strands, out, m)
+
+    def _seg_error_stats(self, fn, fld, enc):
+        nz, ny, nx = fld.shape
+        info = EncInfo.from_dict(enc)
+        data = np.ascontiguousarray(enc["data"], dtype=np.uint8)
+        if data.size == 0:
+            data = np.zeros(1, dtype=np.uint8)
+        st = ErrorStats()
+        rc = fn(self.h, fld.ctypes.data, nx, ny, nz, C.byref(info), data.ctypes.data, data.size, C.byref(st))
+        return rc, st.as_dict()
+
+    def seg_error_stats_host(self, fld, enc, allow_nonfinite=False):
+        """max |d|, the sum of squares S, the RMS error R, the field's lo and hi, the PSNR and the count of non-finite differences
+        of `fld` against the reconstruction of the segmented stream `enc`, formed and compared on the device
+        (wr_seg_error_stats_host).  Differences that are not finite raise unless allow_nonfinite, which returns the record."""
+        assert fld.dtype == np.float64 and fld.flags["C_CONTIGUOUS"]
+        rc, st = self._seg_error_stats(lib().wr_seg_error_stats_host, fld, enc)
+        if not (allow_nonfinite and st["nonfinite"] > 0):
+            _check(rc)
+        return st
+
+    def seg_error_stats_host_f32(self, fld, enc, allow_nonfinite=False):
+        if not (isinstance(fld, np.ndarray) and fld.dtype == np.float32 and fld.flags["C_CONTIGUOUS"]):
+            raise TypeError("seg_error_stats_host_f32: a C-contiguous float32 array is required")
+        rc, st = self._seg_error_stats(lib().wr_seg_error_stats_host_f32, fld, enc)
+        if not (allow_nonfinite and st["nonfinite"] > 0):
+            _check(rc)
+        return st
+
+    def err_stats(self, a, b, n, dtype=np.float64, a_off=0, b_off=0):
+        """Stage level: the compare alone on n samples of two device buffers, starting a_off / b_off ELEMENTS into them (any
+        alignment): {"max_abs", "sumsq", "rms", "nonfinite", ...} (wr_dev_err_stats, wr_dev_err_stats_f32)."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise TypeError("err_stats: float64 or float32")
+        fn = lib().wr_dev_err_stats if dt == np.float64 else lib().wr_dev_err_stats_f32
+        st = ErrorStats()
+        _check(fn(self.h, a.ptr + a_off * dt.itemsize, b.ptr + b_off * dt.itemsize, int(n), C.byref(st)))
+        return st.as_dict()
 
     def bounded_trial_ms(self):
         """(requantize, inverse, compare) milliseconds summed over the trials of the last bounded encode on this context."""

@@ -64,6 +64,16 @@ int wr_encode_host_seg_bounded_f32(wr_ctx* ctx, const float* h_fld, int nx, int 
                                    wr_timings* tm, wr_bounded_result* res) __attribute__((weak));
 }
 
+// an encode to an RMS error or PSNR target (wrenc --rmse, --psnr)
+extern "C" {
+int wr_encode_host_seg_quality(wr_ctx* ctx, const double* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, int norm, double target,
+                               double tol_min, unsigned seg, unsigned brick, unsigned strands, wr_enc_info* info, unsigned char* data_enc, size_t cap,
+                               wr_timings* tm, wr_quality_result* res) __attribute__((weak));
+int wr_encode_host_seg_quality_f32(wr_ctx* ctx, const float* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, int norm, double target,
+                                   double tol_min, unsigned seg, unsigned brick, unsigned strands, wr_enc_info* info, unsigned char* data_enc, size_t cap,
+                                   wr_timings* tm, wr_quality_result* res) __attribute__((weak));
+}
+
 // the region decode over a batch of fields (wrdec --batch)
 extern "C" {
 int wr_decode_host_seg_roi_batch(wr_ctx* ctx, double* h_out, int nfields, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,

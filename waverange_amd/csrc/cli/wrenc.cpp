@@ -10,6 +10,9 @@
 //       wr_stream_format_parse); without it the library's setting decides (WR_STREAM_FORMAT, else the reference's stream)
 //   --maxerr=E  encode every compressed field to a pointwise error bound (wr_encode_host_seg_bounded): E is absolute, in the
 //               field's units; TOLERANCE is the finest tolerance allowed; needs --format=wrs1, wrs2 or wrs3, excludes --ratio
+//   --rmse=E    encode every compressed field to an RMS error target (wr_encode_host_seg_quality, WR_NORM_RMS): E is absolute, in
+//               the field's units.  --psnr=DB: to a PSNR target in dB over the field's range (WR_NORM_PSNR).  TOLERANCE, the
+//               formats and the exclusions are those of --maxerr; --rmse, --psnr, --maxerr and --ratio exclude one another
 //   --ratio=R   encode every compressed field to a byte budget (wr_encode_host_seg_budget): the field's bytes on disk divided
 //       by R.  TOLERANCE is then the finest tolerance the search may choose; the tool prints the one it chose.  Needs
 //       --format=wrs1.
@@ -17,6 +20,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <future>
 #include <thread>
@@ -189,6 +193,7 @@ void usage()
     cout << "interactive mode if not enough arguments are passed.\n";
     cout << "option: --format=ref|wrs1|wrs2|wrs3[:seg=N][:brick=B][:strands=K] (stream format of the coded fields; default: WR_STREAM_FORMAT, else ref)\n";
     cout << "option: --ratio=R (with --format=wrs1: every field coded into its bytes on disk / R, at the finest tolerance not below TOLERANCE that fits)\n";
+    cout << "option: --rmse=E | --psnr=DB (with --format=wrs1|wrs2|wrs3: every field coded at the coarsest tolerance not below TOLERANCE whose RMS error stays within E, in the field's units, or whose PSNR over the field's range reaches DB)\n";
     cout << "option: --maxerr=E (with --format=wrs1|wrs2|wrs3: every field coded at the coarsest tolerance not below TOLERANCE that keeps every sample within E, in the field's units)\n";
 }
 
@@ -248,6 +253,10 @@ int main(int argc, char** argv)
     double ratio = 0;
     string maxerr_text;
     double maxerr = 0;
+    string quality_text;
+    const char* quality_opt = nullptr;  // "rmse" or "psnr" once one of them is given
+    int quality_norm = 0;
+    double quality = 0;
     for (const string& o : options) {
         if (wrcli::option_value(o, "format", &format_text)) { have_format = true; continue; }
         if (wrcli::option_value(o, "ratio", &ratio_text)) {
@@ -269,6 +278,27 @@ int main(int argc, char** argv)
                 return 2;
             }
             continue;
+        }
+        {
+            const bool rmse = wrcli::option_value(o, "rmse", &quality_text);
+            if (rmse || wrcli::option_value(o, "psnr", &quality_text)) {
+                const char* name = rmse ? "rmse" : "psnr";
+                if (quality_opt && strcmp(quality_opt, name)) {
+                    usage();
+                    cout << "Error: --rmse and --psnr exclude one another" << endl;
+                    return 2;
+                }
+                char* end = nullptr;
+                quality = strtod(quality_text.c_str(), &end);
+                if (quality_text.empty() || *end || !(quality > 0) || !(quality < 1e308)) {
+                    usage();
+                    cout << "Error: --" << name << "=" << quality_text << ": a positive number is required" << endl;
+                    return 2;
+                }
+                quality_opt = name;
+                quality_norm = rmse ? WR_NORM_RMS : WR_NORM_PSNR;
+                continue;
+            }
         }
         usage();
         cout << "Error: unknown option " << o << endl;
@@ -297,7 +327,24 @@ int main(int argc, char** argv)
         }
         wr_get_stream_format(nullptr, &budget_seg, nullptr, nullptr);
     }
-    unsigned bounded_fmt[3] = {0, 0, 0};  // --maxerr: seg, brick, strands of the bounded calls
+    unsigned bounded_fmt[3] = {0, 0, 0};  // --maxerr, --rmse, --psnr: seg, brick, strands of the bounded / quality calls
+    if (quality_opt) {
+        if (maxerr > 0 || ratio > 0) {
+            usage();
+            cout << "Error: --" << quality_opt << " and --" << (maxerr > 0 ? "maxerr" : "ratio") << " exclude one another" << endl;
+            return 2;
+        }
+        if (stream_format != WR_FORMAT_WRS1 && stream_format != WR_FORMAT_WRS2 && stream_format != WR_FORMAT_WRS3) {
+            usage();
+            cout << "Error: --" << quality_opt << " needs --format=wrs1, wrs2 or wrs3" << endl;
+            return 2;
+        }
+        if (!wr_encode_host_seg_quality || !wr_encode_host_seg_quality_f32 || !wr_get_stream_format || !wr_ctx_create) {
+            usage();
+            cout << "Error: --" << quality_opt << ": " << wrcli::kNotSupported << endl;
+            return 2;
+        }
+    }
     if (maxerr > 0) {
         if (ratio > 0) {
             usage();
@@ -314,13 +361,15 @@ int main(int argc, char** argv)
             cout << "Error: --maxerr: " << wrcli::kNotSupported << endl;
             return 2;
         }
+    }
+    if (maxerr > 0 || quality_opt) {
         wr_get_stream_format(nullptr, &bounded_fmt[0], &bounded_fmt[1], &bounded_fmt[2]);
         if (stream_format == WR_FORMAT_WRS1) bounded_fmt[1] = bounded_fmt[2] = 0;
         if (stream_format == WR_FORMAT_WRS2) { bounded_fmt[2] = 0; if (!bounded_fmt[1]) bounded_fmt[1] = WR_BRICK_DEFAULT; }
         if (stream_format == WR_FORMAT_WRS3 && !bounded_fmt[2]) bounded_fmt[2] = WR_STRANDS_DEFAULT;
     }
     const unsigned bseg = bounded_fmt[0], bbrick = bounded_fmt[1], bstrands = bounded_fmt[2];
-    wrcli::ContextPool contexts;  // --ratio, --maxerr: one explicit context per field in flight
+    wrcli::ContextPool contexts;  // --ratio, --maxerr, --rmse, --psnr: one explicit context per field in flight
     wrcli::PhaseClock clock("wrenc");
 
     Job job;
@@ -452,7 +501,7 @@ int main(int argc, char** argv)
         }
         Item* ip = &im;
         const bool pipelined = depth > 0;
-        auto work = [ip, cutoff, pipelined, ratio, budget_seg, maxerr, bseg, bbrick, bstrands, &contexts, &scan, &clock]() {
+        auto work = [ip, cutoff, pipelined, ratio, budget_seg, maxerr, quality_opt, quality_norm, quality, bseg, bbrick, bstrands, &contexts, &scan, &clock]() {
             const wrio::FieldSpec& sp = ip->h.spec;
             if (pipelined) scan(*ip, ip->log);
             if (!sp.icomp) { (pipelined ? static_cast<std::ostream&>(ip->log) : cout) << "  Compression disabled" << endl; return; }
@@ -507,6 +556,34 @@ int main(int argc, char** argv)
                 char line[240];
                 snprintf(line, sizeof line, "  Error bound %.17g: relative tolerance %.17g (grid point %d), error %.17g, %d trials, coded %lu bytes\n", maxerr,
                          res.tolrel, res.g, res.err, res.trials, info.ntot_enc);
+                (pipelined ? static_cast<std::ostream&>(ip->log) : cout) << line;
+                ip->h.tolabs = info.tolabs; ip->h.midval = info.midval; ip->h.halfspanval = info.halfspanval;
+                wlev = info.wlev; nlay = info.nlay;
+                ip->h.ntot_enc = info.ntot_enc;
+                for (int l = 0; l < WR_NLAYMAX; l++) {
+                    ip->h.deps_vec[l] = info.deps_vec[l]; ip->h.minval_vec[l] = info.minval_vec[l]; ip->h.len_enc_vec[l] = info.len_enc_vec[l];
+                }
+            } else if (quality_opt) {  // to an RMS error or PSNR target, no tolerance finer than the command line's
+                wr_ctx* ctx = contexts.borrow();
+                wr_enc_info info;
+                wr_quality_result res;
+                int rc = ctx ? 0 : -1;
+                if (ctx)
+                    rc = ip->fld32 ? wr_encode_host_seg_quality_f32(ctx, ip->fld32.get(), sp.nx, sp.ny, sp.nz * sp.nh, 1, 1, 1, 1, quality_norm, quality, cut,
+                                                                    bseg, bbrick, bstrands, &info, ip->data_enc.data(), ip->cap, nullptr, &res)
+                                   : wr_encode_host_seg_quality(ctx, ip->fld.data(), sp.nx, sp.ny, sp.nz * sp.nh, 1, 1, 1, 1, quality_norm, quality, cut, bseg,
+                                                                bbrick, bstrands, &info, ip->data_enc.data(), ip->cap, nullptr, &res);
+                if (ctx) contexts.give(ctx);
+                if (rc != 0) {  // (as the codec's own failures: the tool ends here, whatever other fields are in flight)
+                    cout.flush();
+                    fprintf(stderr, "Error: field with a %s target of %.17g: %s\n", quality_norm == WR_NORM_RMS ? "RMS error" : "PSNR", quality, wr_last_error());
+                    std::_Exit(1);
+                }
+                char line[400];
+                snprintf(line, sizeof line,
+                         "  %s target %.17g: relative tolerance %.17g (grid point %d), rms %.17g (allowed %.17g), psnr %.17g dB, max error %.17g, %d trials, coded %lu bytes\n",
+                         quality_norm == WR_NORM_RMS ? "RMS error" : "PSNR", quality, res.tolrel, res.g, res.rms, res.max_rms, res.psnr, res.max_abs, res.trials,
+                         info.ntot_enc);
                 (pipelined ? static_cast<std::ostream&>(ip->log) : cout) << line;
                 ip->h.tolabs = info.tolabs; ip->h.midval = info.midval; ip->h.halfspanval = info.halfspanval;
                 wlev = info.wlev; nlay = info.nlay;

@@ -78,6 +78,15 @@ inline int bounded_start(double max_abs_err, double absmax)
     return lo;
 }
 
+// the RMS error a PSNR of `db` over the range hi - lo means: range * 10^(-db / 20); NaN unless db is finite and the range a
+// positive finite number (include/waverange_amd.h: wr_psnr_rms)
+inline double psnr_rms(double db, double lo, double hi)
+{
+    const double range = hi - lo;
+    if (!(fabs(db) <= DBL_MAX) || !(range > 0) || range > DBL_MAX) return NAN;
+    return range * pow(10.0, -db / 20.0);
+}
+
 // grid points a change of the error by the factor r (> 1) is worth at nominal: 64 to the octave, a quarter kept back
 inline int bounded_points(double r)
 {

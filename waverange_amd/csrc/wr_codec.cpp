@@ -7,6 +7,7 @@
 // exactly as wrappers.cpp:292-340 does.
 #include <algorithm>
 #include <cassert>
+#include <map>
 
 #include "wr_blocked.h"
 #include "wr_budget.h"
@@ -1695,6 +1696,18 @@ struct BudgetSearch {
     }
 };
 
+// PSNR = 20 log10(range / R), +inf for R = 0 (include/waverange_amd.h)
+inline double psnr_of(double range, double rms) { return rms == 0 ? INFINITY : 20.0 * log10(range / rms); }
+
+void fill_error_stats(wr_error_stats* o, double max_abs, double bad, double sumsq, size_t n, double lo, double hi)
+{
+    o->max_abs = max_abs; o->sumsq = sumsq;
+    o->rms = sqrt(sumsq / (double)n);
+    o->lo = lo; o->hi = hi;
+    o->psnr = psnr_of(hi - lo, o->rms);
+    o->nonfinite = (unsigned long long)bad;
+}
+
 // ---- the search of an encode to an error bound (include/waverange_amd.h) ------------------------------------------------------
 // E(g) is measured, not bounded: a trial at g forms the reconstruction the decoder would return and compares it with the field.
 // The planes of a trial are never written.  As above only the last plane depends on the tolerance: the residual range plane l
@@ -1705,15 +1718,24 @@ struct BudgetSearch {
 // The whole search runs at the pick of plane 0, on the context's stream, before anything is quantized: the loop then runs at
 // tolabs(g) exactly as the plain call does, which is what makes the stream the plain call's and codes every plane once.
 // The walk over the grid is wrbud::bounded_walk (wr_budget.h: plain host code, fuzzed on its own), from wrbud::bounded_start.
+// An encode to an RMS or PSNR target (wr_encode_*_seg_quality) is the same search with another functional: norm != WR_NORM_MAX
+// makes a trial's compare wrk::err_stats, and what the walk sees is R(g) = sqrt(S(g) / n) against max_err, the RMS target (a
+// PSNR target is converted once, in run(), from the prologue's range).  The walk does not know the difference.
 struct BoundedSearch {
     // what the caller asks for
     double max_err = 0;
     int g_min = 0;
+    int norm = WR_NORM_MAX;  // what max_err bounds: the largest |difference|, or R
+    double psnr_db = 0;      // WR_NORM_PSNR: the target, from which run() makes max_err
+    bool quality = false;    // one of the quality calls: their counter, their words in the messages
     // what comes out
     int g = -1;
     double err = 0;
     int trials = 0;
     double ms[3] = {0, 0, 0};
+    struct Stats { double max_abs = 0, bad = 0, sumsq = 0, rms = 0; };
+    std::map<int, Stats> seen;  // norm != WR_NORM_MAX: what the compare returned at every point formed
+    double range = 0;           // hi - lo of the field
 
     wr_ctx* c = nullptr;
     Slot* slot = nullptr;
@@ -1743,11 +1765,43 @@ struct BoundedSearch {
         return WR_OK;
     }
 
+    // the same with the sum of the squares of the finite differences, S, and R = sqrt(S / n) (wrk::err_stats)
+    template <class T>
+    static int compare_stats(wr_ctx* c, const T* a, const T* b, size_t n, Stats* st)
+    {
+        wrk::err_stats(a, b, n, c->d_partial, result_dev(c) + 2, c->stream);
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "compare launch failed");
+        HIPCHK(hipEventRecord(c->ev_d, c->stream));
+        HIPCHK(hipEventSynchronize(c->ev_d));
+        const double* r = result_host(c) + 2;
+        st->max_abs = r[0]; st->bad = r[1]; st->sumsq = r[2];
+        st->rms = sqrt(st->sumsq / (double)n);
+        return WR_OK;
+    }
+
+    // wr_dev_err_stats / _f32: the compare alone, as a stage call
+    template <class T>
+    static int stage_stats(wr_ctx* c, const T* d_a, const T* d_b, size_t n, wr_error_stats* stats)
+    {
+        if (int rc = ctx_bind(c)) return rc;
+        if (!stats || !d_a || !d_b) return fail(WR_ERR_ARG, "null pointer");
+        if (!n) return fail(WR_ERR_ARG, "empty array");
+        std::lock_guard<std::mutex> lk(c->mu);
+        StageLock cu(c->pool->cu_mu);
+        Stats st;
+        if (int rc = compare_stats(c, d_a, d_b, n, &st)) return rc;
+        fill_error_stats(stats, st.max_abs, st.bad, st.sumsq, n, NAN, NAN);
+        stats->psnr = NAN;
+        return WR_OK;
+    }
+
+    std::string who() const { return quality ? "an encode to a quality target" : "an encode to an error bound"; }
+
     int nonfinite_field(const std::string& what)
     {
         double mx = 0, bad = 0;
         if (int rc = orig_f32 ? compare(c, orig_f32, orig_f32, n, &mx, &bad) : compare(c, orig, orig, n, &mx, &bad)) return rc;
-        if (bad > 0) return fail(WR_ERR_ARG, "an encode to an error bound needs a finite field: " + std::to_string((unsigned long long)bad) +
+        if (bad > 0) return fail(WR_ERR_ARG, who() + " needs a finite field: " + std::to_string((unsigned long long)bad) +
                                                  " sample(s) are a NaN or an infinity");
         return fail(WR_ERR_ARG, what);
     }
@@ -1794,27 +1848,42 @@ struct BoundedSearch {
         HIPCHK(hipEventRecord(c->ev_c, c->stream));
         if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "a trial's kernel launch failed");
         double bad = 0;
-        if (int rc = orig_f32 ? compare(c, orig_f32, rec_f32, n, e, &bad) : compare(c, orig, rec, n, e, &bad)) return rc;
+        if (norm == WR_NORM_MAX) {
+            if (int rc = orig_f32 ? compare(c, orig_f32, rec_f32, n, e, &bad) : compare(c, orig, rec, n, e, &bad)) return rc;
+        } else {
+            Stats st;
+            if (int rc = orig_f32 ? compare_stats(c, orig_f32, rec_f32, n, &st) : compare_stats(c, orig, rec, n, &st)) return rc;
+            seen[gk] = st;
+            *e = st.rms; bad = st.bad;
+        }
         float t = 0;
         HIPCHK(hipEventElapsedTime(&t, c->ev_a, c->ev_b)); ms[0] += t;
         HIPCHK(hipEventElapsedTime(&t, c->ev_b, c->ev_c)); ms[1] += t;
         HIPCHK(hipEventElapsedTime(&t, c->ev_c, c->ev_d)); ms[2] += t;
         trials++;
-        if (bad > 0) return nonfinite_field("an encode to an error bound: the reconstruction at tolerance " + std::to_string(wrbud::grid_tol(gk)) + " is not finite");
+        if (bad > 0) return nonfinite_field(who() + ": the reconstruction at tolerance " + std::to_string(wrbud::grid_tol(gk)) + " is not finite");
         return WR_OK;
     }
 
     int run(double lo, double hi, const double* coef, const Prologue& pro)
     {
         d_coef = coef; p = pro;
-        if ((uintptr_t)d_coef & 15) return fail(WR_ERR_ARG, "an encode to an error bound needs a 16-byte aligned coefficient array");
+        if ((uintptr_t)d_coef & 15) return fail(WR_ERR_ARG, who() + " needs a 16-byte aligned coefficient array");
         const double absmax = fmax(fabs(p.lo), fabs(p.hi));
-        if (!(absmax <= DBL_MAX)) return nonfinite_field("an encode to an error bound needs a finite field");
+        if (!(absmax <= DBL_MAX)) return nonfinite_field(who() + " needs a finite field");
+        range = p.hi - p.lo;
+        if (norm == WR_NORM_PSNR) {  // the one conversion: everything below is stated on R against this value
+            max_err = wrbud::psnr_rms(psnr_db, p.lo, p.hi);
+            if (max_err != max_err) return fail(WR_ERR_ARG, "a PSNR target needs a field whose range hi - lo is a positive finite number");
+        }
         rlo[0] = lo; rhi[0] = hi; nrange = 1;
         const int rc = wrbud::bounded_walk(max_err, g_min, wrbud::bounded_start(max_err, absmax), [this](int gk, double* e) { return eval(gk, e); }, &g, &err);
         if (rc == wrbud::kBoundedMiss) {
             char b[200];
-            snprintf(b, sizeof b, "the error bound %.17g is below what the finest tolerance allowed reaches: E(g_min = %d) = %.17g", max_err, g, err);
+            if (norm == WR_NORM_MAX)
+                snprintf(b, sizeof b, "the error bound %.17g is below what the finest tolerance allowed reaches: E(g_min = %d) = %.17g", max_err, g, err);
+            else
+                snprintf(b, sizeof b, "the RMS target %.17g is below what the finest tolerance allowed reaches: R(g_min = %d) = %.17g", max_err, g, err);
             g = -1;
             return fail(WR_ERR_BOUND, b);
         }
@@ -1839,7 +1908,7 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
     if (bud && c->keep_residual)
         return fail(WR_ERR_UNSUPPORTED, "an encode to a byte budget does not keep the residual: wr_ctx_set_keep_residual(ctx, 0)");
     if (bnd && c->keep_residual)
-        return fail(WR_ERR_UNSUPPORTED, "an encode to an error bound does not keep the residual: wr_ctx_set_keep_residual(ctx, 0)");
+        return fail(WR_ERR_UNSUPPORTED, bnd->who() + " does not keep the residual: wr_ctx_set_keep_residual(ctx, 0)");
     ActiveCall active(c->pool);
     if (tm) wrdma::enable_timing();
     const double t0 = now();
@@ -1895,7 +1964,7 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
         auto after_quant = [&](unsigned l, bool) -> int {
             if (int arc = seg_encode_plane(c, t, c->ps[l].ref, n, (int)l, bufs.blob[l].p, bufs.ev)) return arc;
             if (bud) g_stat[WR_STAT_BUDGET_CODER_RUNS]++;
-            if (bnd) g_stat[WR_STAT_BOUNDED_CODER_RUNS]++;
+            if (bnd) g_stat[bnd->quality ? WR_STAT_QUALITY_CODER_RUNS : WR_STAT_BOUNDED_CODER_RUNS]++;
             return WR_OK;
         };
         clock_warmup(c, n);
@@ -2202,9 +2271,12 @@ int seg_coder_stage(wr_ctx* c, const CoderCall& k, wr_timings* tm)
 // is the stages above, in the same order: parse, gather the planes' buffers, "up", lease the slot, coder stage, finisher, tail.
 // err_out != nullptr (wr_seg_error_host): fld is the ORIGINAL field on the host and is only read; the reconstruction stays on
 // the device, where it is compared with an upload of the field: *err_out = max |field - reconstruction|
+// stats_out != nullptr (wr_seg_error_stats_host): likewise, the compare being wrk::err_stats and the field's min/max read too
 int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
-                    wr_timings* tm, double* err_out = nullptr)
+                    wr_timings* tm, double* err_out = nullptr, wr_error_stats* stats_out = nullptr)
 {
+    double err_unused = 0;
+    if (stats_out && !err_out) err_out = &err_unused;
     if (int rc = ctx_bind(c)) return rc;
     if (!info) return fail(WR_ERR_ARG, "null wr_enc_info");
     std::lock_guard<std::mutex> lk(c->mu);
@@ -2228,6 +2300,20 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
             const double d = fld.host ? fabs(fld.host[j] - info->midval) : fabs((double)fld.host_f32[j] - (double)(float)info->midval);
             if (d <= DBL_MAX) mx = d > mx ? d : mx;
             else bad++;
+        }
+        if (stats_out) {  // S by a compensated sum (Neumaier): its error does not grow with n
+            double sum = 0, comp = 0, lo = NAN, hi = NAN;
+            for (size_t j = 0; j < n; j++) {
+                const double v = fld.host ? fld.host[j] : (double)fld.host_f32[j];
+                lo = fmin(lo, v); hi = fmax(hi, v);
+                const double d = fld.host ? v - info->midval : v - (double)(float)info->midval;
+                if (!(fabs(d) <= DBL_MAX)) continue;
+                const double q = d * d, t = sum + q;
+                comp += sum >= q ? (sum - t) + q : (q - t) + sum;
+                sum = t;
+            }
+            if (sum <= DBL_MAX) sum += comp;
+            fill_error_stats(stats_out, mx, (double)bad, sum, n, lo, hi);
         }
         if (bad) return fail(WR_ERR_ARG, std::to_string(bad) + " difference(s) between the field and the reconstruction are not finite");
         *err_out = mx;
@@ -2272,8 +2358,20 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
         rc = kernel_stage_end(c, inverse_from_planes(c, slot.get(), d_fld, nx, ny, nz, (int)info->wlev, p, fld.host_f32 ? &d_f32 : nullptr));
         if (rc == WR_OK && err_out) {
             double bad = 0;
-            rc = fld.host_f32 ? BoundedSearch::compare(c, reinterpret_cast<const float*>(bufs.trial[2].p), (const float*)d_f32, n, err_out, &bad)
-                              : BoundedSearch::compare(c, reinterpret_cast<const double*>(bufs.trial[2].p), (const double*)d_fld, n, err_out, &bad);
+            if (stats_out) {
+                BoundedSearch::Stats st;
+                double lo = 0, hi = 0;
+                rc = fld.host_f32 ? BoundedSearch::compare_stats(c, reinterpret_cast<const float*>(bufs.trial[2].p), (const float*)d_f32, n, &st)
+                                  : BoundedSearch::compare_stats(c, reinterpret_cast<const double*>(bufs.trial[2].p), (const double*)d_fld, n, &st);
+                if (rc == WR_OK)
+                    rc = fld.host_f32 ? read_minmax(c, reinterpret_cast<const float*>(bufs.trial[2].p), n, false, &lo, &hi)
+                                      : read_minmax(c, reinterpret_cast<const double*>(bufs.trial[2].p), n, false, &lo, &hi);
+                if (rc == WR_OK) fill_error_stats(stats_out, st.max_abs, st.bad, st.sumsq, n, lo, hi);
+                *err_out = st.max_abs; bad = st.bad;
+            } else {
+                rc = fld.host_f32 ? BoundedSearch::compare(c, reinterpret_cast<const float*>(bufs.trial[2].p), (const float*)d_f32, n, err_out, &bad)
+                                  : BoundedSearch::compare(c, reinterpret_cast<const double*>(bufs.trial[2].p), (const double*)d_fld, n, err_out, &bad);
+            }
             if (rc == WR_OK && bad > 0)
                 rc = fail(WR_ERR_ARG, std::to_string((unsigned long long)bad) + " difference(s) between the field and the reconstruction are not finite");
         }
@@ -2789,6 +2887,103 @@ int wr_seg_error_host_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz,
     FieldRef f; f.host_f32 = const_cast<float*>(h_fld);
     return seg_error(c, f, nx, ny, nz, info, data_enc, data_len, err);
 }
+
+// ---- encode to an RMS or PSNR target: BoundedSearch in the L2 norm
+static int encode_seg_quality(wr_ctx* c, FieldRef f, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, int norm, double target, double tol_min,
+                              unsigned seg, unsigned brick, unsigned strands, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm,
+                              wr_quality_result* res)
+{
+    if (!res) return fail(WR_ERR_ARG, "null wr_quality_result");
+    if (norm != WR_NORM_MAX && norm != WR_NORM_RMS && norm != WR_NORM_PSNR) return fail(WR_ERR_ARG, "norm must be WR_NORM_MAX, WR_NORM_RMS or WR_NORM_PSNR");
+    if (!(target > 0) || target > DBL_MAX) return fail(WR_ERR_ARG, "the quality target must be a positive finite number");
+    if (!(tol_min > 0) || tol_min > DBL_MAX) return fail(WR_ERR_ARG, "tol_min must be a positive number");
+    if (mx < 1 || my < 1 || mz < 1) return fail(WR_ERR_ARG, "bad local cutoff description");
+    if ((long long)mx * my * mz > 1) return fail(WR_ERR_UNSUPPORTED, "an encode to a quality target takes no local cutoff (mx * my * mz > 1)");
+    BoundedSearch bnd;
+    bnd.quality = true;
+    bnd.norm = norm;
+    if (norm == WR_NORM_PSNR) bnd.psnr_db = target;  // (max_err: from the prologue's range, in run())
+    else bnd.max_err = target;
+    bnd.g_min = wrbud::grid_index(tol_min);
+    const double t_min = wrbud::grid_tol(bnd.g_min);
+    Cutoff cut; cut.vec = &t_min;
+    memset(res, 0, sizeof *res);
+    const int rc = encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick, strands, info, data_enc, cap, tm, nullptr, &bnd);
+    res->trials = bnd.trials;
+    if (c) for (int k = 0; k < 3; k++) c->bounded_ms[k] = bnd.ms[k];
+    if (rc) return rc;
+    BoundedSearch::Stats st;
+    if (info->nlay == 0) {  // a constant field: the search never ran
+        bnd.g = wrbud::kGMax;
+        bnd.range = 2 * info->halfspanval;
+        if (norm == WR_NORM_PSNR) {
+            if (!(bnd.range > 0)) return fail(WR_ERR_ARG, "a PSNR target needs a field whose range hi - lo is a positive finite number");
+            bnd.max_err = bnd.range * pow(10.0, -target / 20.0);
+        }
+    } else {
+        if (bnd.g < 0) return fail(WR_ERR_HIP, "internal: the search of an encode to a quality target chose no tolerance");
+        if (norm == WR_NORM_MAX) { st.max_abs = bnd.err; st.sumsq = st.rms = NAN; }
+        else st = bnd.seen[bnd.g];
+    }
+    res->g = bnd.g;
+    res->tolrel = wrbud::grid_tol(bnd.g);
+    res->max_abs = st.max_abs; res->rms = st.rms; res->sumsq = st.sumsq;
+    res->range = bnd.range;
+    res->psnr = norm == WR_NORM_MAX && info->nlay ? NAN : psnr_of(bnd.range, st.rms);
+    res->max_rms = norm == WR_NORM_MAX ? NAN : bnd.max_err;
+    return WR_OK;
+}
+
+int wr_encode_host_seg_quality(wr_ctx* c, const double* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, int norm, double target,
+                               double tol_min, unsigned seg, unsigned brick, unsigned strands, wr_enc_info* info, unsigned char* data_enc, size_t cap,
+                               wr_timings* tm, wr_quality_result* res)
+{
+    FieldRef f; f.host = const_cast<double*>(h_fld);  // (never written: the residual is not kept)
+    return encode_seg_quality(c, f, nx, ny, nz, wtflag, mx, my, mz, norm, target, tol_min, seg, brick, strands, info, data_enc, cap, tm, res);
+}
+
+int wr_encode_host_seg_quality_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, int norm, double target,
+                                   double tol_min, unsigned seg, unsigned brick, unsigned strands, wr_enc_info* info, unsigned char* data_enc, size_t cap,
+                                   wr_timings* tm, wr_quality_result* res)
+{
+    FieldRef f; f.host_f32 = const_cast<float*>(h_fld);
+    return encode_seg_quality(c, f, nx, ny, nz, wtflag, mx, my, mz, norm, target, tol_min, seg, brick, strands, info, data_enc, cap, tm, res);
+}
+
+int wr_encode_device_seg_quality(wr_ctx* c, double* d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, int norm, double target,
+                                 double tol_min, unsigned seg, unsigned brick, unsigned strands, wr_enc_info* info, unsigned char* data_enc, size_t cap,
+                                 wr_timings* tm, wr_quality_result* res)
+{
+    FieldRef f; f.dev = d_fld;
+    if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
+    return encode_seg_quality(c, f, nx, ny, nz, wtflag, mx, my, mz, norm, target, tol_min, seg, brick, strands, info, data_enc, cap, tm, res);
+}
+
+static int seg_error_stats(wr_ctx* c, FieldRef f, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
+                           wr_error_stats* stats)
+{
+    if (!stats) return fail(WR_ERR_ARG, "null result pointer");
+    if (f.none()) return fail(WR_ERR_ARG, "null field pointer");
+    memset(stats, 0, sizeof *stats);
+    return decode_seg_impl(c, f, nx, ny, nz, info, data_enc, data_len, nullptr, nullptr, stats);
+}
+
+int wr_seg_error_stats_host(wr_ctx* c, const double* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc,
+                            size_t data_len, wr_error_stats* stats)
+{
+    FieldRef f; f.host = const_cast<double*>(h_fld);  // (only read)
+    return seg_error_stats(c, f, nx, ny, nz, info, data_enc, data_len, stats);
+}
+
+int wr_seg_error_stats_host_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc,
+                                size_t data_len, wr_error_stats* stats)
+{
+    FieldRef f; f.host_f32 = const_cast<float*>(h_fld);
+    return seg_error_stats(c, f, nx, ny, nz, info, data_enc, data_len, stats);
+}
+
+int wr_dev_err_stats(wr_ctx* c, const double* d_a, const double* d_b, size_t n, wr_error_stats* stats) { return BoundedSearch::stage_stats(c, d_a, d_b, n, stats); }
+int wr_dev_err_stats_f32(wr_ctx* c, const float* d_a, const float* d_b, size_t n, wr_error_stats* stats) { return BoundedSearch::stage_stats(c, d_a, d_b, n, stats); }
 
 int wr_ctx_bounded_trial_ms(wr_ctx* c, double* requant_ms, double* inverse_ms, double* compare_ms)
 {

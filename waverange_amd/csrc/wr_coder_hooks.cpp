@@ -162,6 +162,7 @@ size_t wr_seg_bound(size_t n, unsigned seg)
 double wr_budget_tol(int g) { return wrbud::grid_tol(g); }
 int wr_budget_index(double tolrel) { return wrbud::grid_index(tolrel); }
 int wr_bounded_start(double max_abs_err, double absmax) { return wrbud::bounded_start(max_abs_err, absmax); }
+double wr_psnr_rms(double db, double lo, double hi) { return wrbud::psnr_rms(db, lo, hi); }
 
 size_t wr_seg_size_bound_host_ref(const unsigned char* sym, size_t n, unsigned seg)
 {

@@ -112,6 +112,12 @@ void requant_accum(const double* x, size_t n, const QuantPrev& prev, double aopt
 // subtraction each; 0 if there is none), result[1] = the count of those that are not.  partial: 2 * minmax_partials() doubles.
 void linf_count(const double* a, const double* b, size_t n, double* partial, double* result, hipStream_t st);
 void linf_count(const float* a, const float* b, size_t n, double* partial, double* result, hipStream_t st);
+// ---- the compare of an encode to an RMS or PSNR target (k_err_stats): result[0], result[1] as linf_count gives them, and
+// result[2] = S, the fp64 sum of fl(d * d) over the finite differences d = fl(a[j] - b[j]) in a summation order that n and the
+// alignment of the pointers fix: the same bits on every run, within 2^-38 S* of the real sum of those squares for n <= 2^33
+// (the derivation is next to the kernel).  +inf when a square overflows.  partial: 3 * minmax_partials() doubles.
+void err_stats(const double* a, const double* b, size_t n, double* partial, double* result, hipStream_t st);
+void err_stats(const float* a, const float* b, size_t n, double* partial, double* result, hipStream_t st);
 
 // ---- quantizer plane with the non-uniform (local) cutoff mask (wrappers.cpp:343-379, 397-398):
 // loops over PHYSICAL positions, maps each to its wavelet-space index (ind_p2w_3d,

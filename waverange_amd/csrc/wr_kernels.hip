@@ -1157,6 +1157,92 @@ static void linf_count_t(const T* a, const T* b, size_t n, double* partial, doub
 void linf_count(const double* a, const double* b, size_t n, double* partial, double* result, hipStream_t st) { linf_count_t(a, b, n, partial, result, st); }
 void linf_count(const float* a, const float* b, size_t n, double* partial, double* result, hipStream_t st) { linf_count_t(a, b, n, partial, result, st); }
 
+// The compare of an encode to an RMS or PSNR target: in one pass what k_linf_cnt gives -- the maximum of the finite |a - b| and
+// the count of differences that are not finite -- and S, the sum of q = fl(d * d) over the finite d = fl(a - b) (operands
+// widened to fp64; the product is rounded once, nothing here contracts to an FMA).  partial[3b .. 3b + 2] = block b's maximum,
+// count and sum.
+// The order of the sum is fixed by n and by which load form runs, never by the order in which blocks or waves finish: a thread
+// adds its terms in index order (the two-sample form keeps one sum per sample of the pair and adds the second to the first,
+// then the odd tail), the lanes of a wave combine by shuffles at distances 32 .. 1, thread 0 adds the waves' sums in wave
+// order, the final block's thread t adds the partials t, t + 256, .. in that order and reduces the same way.  No atomics.
+// Accuracy.  Every term is >= 0, so a sum that passes through k roundings lies within k u / (1 - k u) of the real sum of the
+// same q, u = 2^-53.  The grid is red_grid(n, 2) blocks of WR_RED_THREADS, at most WR_RED_BLOCKS x WR_RED_THREADS = 2^19
+// threads: a thread of the element-wise form adds at most ceil(n / 2^19) terms (2^14 at n = 2^33), a sum of the two-sample
+// form ceil(n / 2^20) and one addition joins the two; then 6 shuffle steps, 3 waves, and in the final block at most 8 partials,
+// 6 steps, 3 waves: k <= 2^14 + 26, |S - S*| < 2^-38 S* for every n <= 2^33.
+__device__ inline void err_stats_acc(double a, double b, double& mx, double& cnt, double& s)
+{
+    const double d = a - b, m = fabs(d);
+    if (m <= DBL_MAX) { mx = fmax(mx, m); s = s + d * d; }
+    else cnt += 1.0;
+}
+
+__device__ inline void block_max_sum_sum(double mx, double cnt, double s, double* __restrict__ out)
+{
+    for (int o = 32; o > 0; o >>= 1) {
+        mx = fmax(mx, __shfl_down(mx, o, 64));
+        cnt += __shfl_down(cnt, o, 64);
+        s = s + __shfl_down(s, o, 64);
+    }
+    __shared__ double smx[WR_RED_THREADS / 64], scn[WR_RED_THREADS / 64], ssq[WR_RED_THREADS / 64];
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { smx[w] = mx; scn[w] = cnt; ssq[w] = s; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < WR_RED_THREADS / 64; i++) { mx = fmax(mx, smx[i]); cnt += scn[i]; s = s + ssq[i]; }
+        out[0] = mx;
+        out[1] = cnt;
+        out[2] = s;
+    }
+}
+
+// PAIRS: as k_linf_cnt
+template <typename T, bool PAIRS>
+__global__ __launch_bounds__(WR_RED_THREADS) void k_err_stats(const T* __restrict__ a, const T* __restrict__ b, size_t n, double* __restrict__ partial)
+{
+    double mx = 0.0, cnt = 0.0, s = 0.0;
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (size_t)gridDim.x * blockDim.x;
+    if (PAIRS) {
+        double s1 = 0.0;
+        const size_t n2 = n >> 1;
+        const typename Pair<T>::type* a2 = reinterpret_cast<const typename Pair<T>::type*>(a);
+        const typename Pair<T>::type* b2 = reinterpret_cast<const typename Pair<T>::type*>(b);
+        for (size_t i = tid; i < n2; i += nthr) {
+            const typename Pair<T>::type va = a2[i], vb = b2[i];
+            err_stats_acc((double)va.x, (double)vb.x, mx, cnt, s);
+            err_stats_acc((double)va.y, (double)vb.y, mx, cnt, s1);
+        }
+        s = s + s1;
+        if ((n & 1) && tid == 0) err_stats_acc((double)a[n - 1], (double)b[n - 1], mx, cnt, s);
+    } else {
+        for (size_t i = tid; i < n; i += nthr) err_stats_acc((double)a[i], (double)b[i], mx, cnt, s);
+    }
+    block_max_sum_sum(mx, cnt, s, partial + 3 * blockIdx.x);
+}
+
+__global__ __launch_bounds__(WR_RED_THREADS) void k_err_stats_final(const double* __restrict__ partial, int np, double* __restrict__ result)
+{
+    double mx = 0.0, cnt = 0.0, s = 0.0;
+    for (int i = threadIdx.x; i < np; i += blockDim.x) {
+        mx = fmax(mx, partial[3 * i]);
+        cnt += partial[3 * i + 1];
+        s = s + partial[3 * i + 2];
+    }
+    block_max_sum_sum(mx, cnt, s, result);  // single block: lands in result[0 .. 2]
+}
+
+template <typename T>
+static void err_stats_t(const T* a, const T* b, size_t n, double* partial, double* result, hipStream_t st)
+{
+    const bool pairs = (((uintptr_t)a | (uintptr_t)b) & (2 * sizeof(T) - 1)) == 0;
+    const int g = red_grid(n, 2);
+    if (pairs) hipLaunchKernelGGL((k_err_stats<T, true>), dim3(g), dim3(WR_RED_THREADS), 0, st, a, b, n, partial);
+    else hipLaunchKernelGGL((k_err_stats<T, false>), dim3(g), dim3(WR_RED_THREADS), 0, st, a, b, n, partial);
+    hipLaunchKernelGGL(k_err_stats_final, dim3(1), dim3(WR_RED_THREADS), 0, st, partial, g, result);
+}
+void err_stats(const double* a, const double* b, size_t n, double* partial, double* result, hipStream_t st) { err_stats_t(a, b, n, partial, result, st); }
+void err_stats(const float* a, const float* b, size_t n, double* partial, double* result, hipStream_t st) { err_stats_t(a, b, n, partial, result, st); }
+
 // =====================================================================================
 // The trial of an encode to an error bound: what would the decoder's coefficient sum be, had the planes been cut with these
 // steps?  acc[j] is what k_dequant / k_dequant_lds give from the planes k_quant_blk would have written -- the full planes in
