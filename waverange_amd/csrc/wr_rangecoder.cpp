@@ -356,6 +356,15 @@ inline bool encode_block_header(Enc& e, const uint8_t* s, uint32_t bs, const uin
 // after a block: the coder's state says that the block model was not the symbols' (see encode_block_header)
 inline bool block_failed(const Enc& e) { return e.range == 0; }
 
+// A full block of one symbol is a no-op for the coder behind its header.  The symbol is the largest one present, so every
+// step takes the open-ended branch with lt = 0: low += 0, range -= 0 (Enc::freq, Dec::update; rangecod.c:217-229, 339-351).
+// The renormalisation in front of each step is idempotent, and whatever follows the block -- the next header, "no more
+// blocks", finish() -- renormalises first.  So the 60000 steps can be left out and the stream is byte for byte the same.
+inline bool constant_block(const SymEntry* tab, uint32_t top_sym, uint32_t bs) { return bs == kBlock && tab[top_sym].sy == kBlock; }
+// a histogram that came with the plane says so: the symbols are looked at before the block is passed over (the contract of
+// wr_rangecoder.h: a model that is not the symbols' ends the stream -- such a block goes through the symbol loop and fails there)
+inline bool all_symbols_are(const uint8_t* s, uint32_t sym) { return s[0] == sym && !memcmp(s, s + 1, kBlock - 1); }
+
 }  // namespace
 
 // The encoder's loop keeps five values per plane in registers; beyond three planes the spills cost more
@@ -417,22 +426,38 @@ public:
     }
     // one block of every stream; on_end(tag, stream length or (size_t)-1) for the streams that ended with it
     template <class OnEnd>
-    void step(OnEnd on_end) { step_streams(count_, es_, store_, st_, tabs_, tops_, on_end); }
+    void step(OnEnd on_end) { step_streams(count_, es_, store_, st_, tabs_, tops_, &passed_, on_end); }
+    // blocks that steps passed over since the last call (constant_block): stream-blocks advanced beside one per stream and step
+    unsigned long take_passed() { const unsigned long p = passed_; passed_ = 0; return p; }
+    // The header phase of a stream's step: the header of its next block -- and, past every block that is constant, the
+    // header of the one behind it, until a block is not constant, is partial, or the stream ends (done once per group kind
+    // here; the symbol loops never see such a block).  *bs, *ss: the block the symbol phase is to code; false: the stream
+    // has failed (*bs is 0).  *passed counts the blocks passed over.
+    static bool headers(Enc& e, Stream& s, SymEntry* tab, uint32_t* top, uint32_t* bs, const uint8_t** ss, unsigned long* passed)
+    {
+        for (;;) {
+            const size_t left = s.n - s.done;
+            *bs = left < kBlock ? (uint32_t)left : kBlock;
+            *ss = s.sym.at(s.done, s.n);  // (may move the window on; a refusal ends the stream)
+            if ((!*ss && *bs) || !encode_block_header(e, *ss, *bs, s.hist ? s.hist + s.blk * 256 : nullptr, tab, top)) { *bs = 0; return false; }
+            if (!constant_block(tab, *top, *bs) || (s.hist && !all_symbols_are(*ss, *top))) return true;
+            e.renorm();  // as the block's first step would: the state is now the one behind the block, to the byte
+            if (s.limit && e.pos > s.limit) { *bs = 0; return false; }
+            s.done += kBlock; s.blk++; ++*passed;
+        }
+    }
     // the same on the slots of another holder of at most kMaxEncStreams streams (a 16-lane session that is down to a few)
     template <class OnEnd>
     static void step_streams(int& count, Enc** es, unsigned char (*store)[sizeof(Enc)], Stream* st, SymEntry (*tabs)[256], uint32_t* tops,
-                             OnEnd on_end)
+                             unsigned long* passed, OnEnd on_end)
     {
         uint32_t bs[kMaxEncStreams];
         const uint8_t* ss[kMaxEncStreams];
         bool all_full = true, topsel = false;  // topsel: some plane's largest symbol holds > 2 % of this block
         for (int k = 0; k < count; k++) {
             Stream& s = st[k];
-            const size_t left = s.n - s.done;
-            bs[k] = left < kBlock ? (uint32_t)left : kBlock;
-            ss[k] = s.sym.at(s.done, s.n);
-            if ((!ss[k] && bs[k]) || !encode_block_header(*es[k], ss[k], bs[k], s.hist ? s.hist + s.blk * 256 : nullptr, tabs[k], &tops[k])) {
-                s.failed = true; bs[k] = 0; all_full = false;
+            if (!headers(*es[k], s, tabs[k], &tops[k], &bs[k], &ss[k], passed)) {
+                s.failed = true; all_full = false;
                 continue;
             }
             all_full = all_full && bs[k] == kBlock;
@@ -473,6 +498,7 @@ public:
 
 private:
     int count_ = 0;
+    unsigned long passed_ = 0;
     Enc* es_[kMaxEncStreams];
     alignas(Enc) unsigned char store_[kMaxEncStreams][sizeof(Enc)];
     Stream st_[kMaxEncStreams];
@@ -528,10 +554,11 @@ public:
     }
     void* tag_of_last() const { return st_[count_ - 1].tag; }
     void set_tag_of_last(void* t) { st_[count_ - 1].tag = t; }
+    unsigned long take_passed() { const unsigned long p = passed_; passed_ = 0; return p; }
     template <class OnEnd>
     void step(OnEnd on_end)
     {
-        if (count_ <= kMaxEncStreams) { EncGroup::step_streams(count_, es_, store_, st_, tabs_, tops_, on_end); return; }
+        if (count_ <= kMaxEncStreams) { EncGroup::step_streams(count_, es_, store_, st_, tabs_, tops_, &passed_, on_end); return; }
         WR_PROBE(1);
         uint32_t bs[kCap];
         VecEncBlock vb;
@@ -543,13 +570,10 @@ public:
         const uint8_t* ss[kCap];
         for (int k = 0; k < count_; k++) {
             EncGroup::Stream& s = st_[k];
-            const size_t left = s.n - s.done;
-            bs[k] = left < kBlock ? (uint32_t)left : kBlock;
-            ss[k] = s.sym.at(s.done, s.n);
             bool header_ok;
-            { WR_PROBE(0); header_ok = !(!ss[k] && bs[k]) && encode_block_header(*es_[k], ss[k], bs[k], s.hist ? s.hist + s.blk * 256 : nullptr, tabs_[k], &tops_[k]); }
+            { WR_PROBE(0); header_ok = EncGroup::headers(*es_[k], s, tabs_[k], &tops_[k], &bs[k], &ss[k], &passed_); }
             if (!header_ok) {
-                s.failed = true; bs[k] = 0;
+                s.failed = true;
                 continue;
             }
             if (bs[k] != kBlock) {  // the final, partial block of a stream: scalar
@@ -614,6 +638,7 @@ public:
 
 private:
     int count_ = 0;
+    unsigned long passed_ = 0;
     Enc* es_[kCap];
     alignas(Enc) unsigned char store_[kCap][sizeof(Enc)];
     EncGroup::Stream st_[kCap];
@@ -1231,6 +1256,7 @@ public:
         tails_[k] = std::move(m.tail);
     }
     void set_tag_of_last(void* t) { tag_[count_ - 1] = t; }
+    unsigned long take_passed() { const unsigned long p = passed_; passed_ = 0; return p; }  // as EncGroup's
     // one block of every stream; on_end(tag, symbols the stream held or (size_t)-1) for the streams that ended
     template <class OnEnd>
     void step(OnEnd on_end)
@@ -1253,10 +1279,7 @@ public:
                     if (c) top_sym = (uint32_t)b;
                 }
                 if (bs > kBlock) { failed_[k] = true; ended = true; }  // not a WaveRange stream (defs.h:36)
-                else {
-                    m.top = top_sym; m.bs = bs;
-                    finish_model(m);
-                }
+                else { m.top = top_sym; m.bs = bs; }
             }
             if (ended) { retire(k, on_end); continue; }
             const size_t at = produced_[k] < n_[k] ? produced_[k] : n_[k];
@@ -1269,7 +1292,18 @@ public:
                 memcpy(tails_[k].data(), d.in + (d.pos - 1), d.len - (d.pos - 1));
                 d.in = tails_[k].data(); d.len = tails_[k].size(); d.pos = 1;
             }
-            if (m.bs != kBlock || cur_[k].room(at) < kBlock || d.pos + kMargin > d.len) fast = false;
+            const bool fast_k = m.bs == kBlock && cur_[k].room(at) >= kBlock && d.pos + kMargin <= d.len;
+            // A constant block (constant_block: no coder step behind its header changes the state) that the unchecked loop
+            // would take -- a whole block of room in the window and in the plane, the stream's end not reached: the
+            // symbols are written and the same stream's next header is parsed.  Everything else goes the checked way,
+            // so a stream that announces more constant blocks than the plane holds never writes past n.
+            if (fast_k && constant_block(m.tab, m.top, m.bs) && produced_[k] + kBlock <= n_[k]) {
+                memset(dst_[k], (int)m.top, kBlock);
+                produced_[k] += kBlock; passed_++;
+                continue;
+            }
+            finish_model(m);
+            if (!fast_k) fast = false;
             k++;
         }
         if (!count_) return;
@@ -1306,6 +1340,7 @@ private:
     }
 
     int cap_, count_ = 0;
+    unsigned long passed_ = 0;
     std::vector<BlockModel> models_;
     BlockModel* ms_[kMaxDecStreams];
     Dec* ds_[kMaxDecStreams];
@@ -1370,6 +1405,7 @@ public:
         tails_[k] = std::move(m.tail);
     }
     void set_tag_of_last(void* t) { tag_[count_ - 1] = t; }
+    unsigned long take_passed() { const unsigned long p = passed_; passed_ = 0; return p; }
     template <class OnEnd>
     void step(OnEnd on_end)
     {
@@ -1407,10 +1443,7 @@ public:
                     if (c) top_sym = (uint32_t)b;
                 }
                 if (bs > kBlock) { failed_[k] = true; ended = true; }
-                else {
-                    m.top = top_sym; m.bs = bs;
-                    finish_model_stats(m);
-                }
+                else { m.top = top_sym; m.bs = bs; }
             }
             }
             if (ended) { retire(k, on_end); continue; }
@@ -1423,6 +1456,12 @@ public:
                 d.in = tails_[k].data(); d.len = tails_[k].size(); d.pos = 1;
             }
             const bool fast = m.bs == kBlock && cur_[k].room(at) >= kBlock && d.pos + kMargin <= d.len;
+            if (fast && constant_block(m.tab, m.top, m.bs) && produced_[k] + kBlock <= n_[k]) {  // passed over: see DecGroup::step
+                memset(dst_[k], (int)m.top, kBlock);
+                produced_[k] += kBlock; passed_++;
+                continue;
+            }
+            finish_model_stats(m);
             vec[k] = fast && m.cand_ok;
             all_fast = all_fast && fast;
             k++;
@@ -1516,6 +1555,7 @@ private:
 
     bool vec_[kCap];  // this step: the stream's block goes through the vector loop
     int count_ = 0;
+    unsigned long passed_ = 0;
     std::vector<BlockModel> models_;
     BlockModel* ms_[kCap];
     Dec* ds_[kCap];
@@ -1661,7 +1701,7 @@ private:
         std::unique_lock<std::mutex> lk(mu_);
         for (;;) {
             // at most vec_sessions_max() / venc_sessions_max() workers run a vector session of either kind at a time
-            // (5/16 and 3/8 of the workers): a session is worth its core
+            // (a quarter of the workers each): a session is worth its core
             // with many lanes filled, but every stream in it advances the slower the fuller it is, so their number is
             // what balances CPU time against the time a field waits for its planes (profiles/r02/NOTES.md); what is
             // queued beyond that joins a running session at its next block boundary
@@ -1824,7 +1864,7 @@ private:
                 add(g, j, t);
                 j = g.full() ? nullptr : pop(false, kind);
             }
-            { const int nstreams = g.count(); const double ts = now_s(); g.step(on_end); account(stat, now_s() - ts, nstreams); }
+            { const int nstreams = g.count(); const double ts = now_s(); g.step(on_end); account(stat, now_s() - ts, nstreams + (int)g.take_passed()); }
             offer(id, kind, g, pack);
             if (tops_up && !g.full()) j = pop(false, kind);
         }
@@ -1898,22 +1938,31 @@ private:
     // profiles/r03/h_rc_any_epyc9575f.txt, i_bench_*)
     // The encoder's vector loop takes every plane (WR_VEC_ENCODE=0: scalar loops of three instead): 16 planes at 1.0-1.3
     // Gsym/s per worker in the pipeline against 0.56 in the scalar loops.  Per stream it advances at 75-150 Msym/s against
-    // ~190, so the sessions are kept as many as leave a field's encode no longer than its decode (3/8 of the workers:
-    // 16 workers, 24 fields in flight: 6 sessions 11.3 GB/s, 4 sessions 9.4, scalar 9.4-9.7; 4 + 5, 4 + 6, 5 + 5 encoder +
-    // decoder sessions instead of 6 + 5: the same within the run-to-run spread, profiles/r03/be_sessions_*).
+    // ~190, so the sessions are kept as many as leave a field's encode no longer than its decode (until constant blocks
+    // were passed over 3/8 of the workers: 16 workers, 24 fields in flight: 6 sessions 11.3 GB/s, 4 sessions 9.4, scalar
+    // 9.4-9.7; 4 + 5, 4 + 6, 5 + 5 encoder + decoder sessions instead of 6 + 5: the same within the run-to-run spread,
+    // profiles/r03/be_sessions_*; now a quarter: venc_sessions_max).
     const bool vec_enc_ = !(getenv("WR_VEC_ENCODE") && !atoi(getenv("WR_VEC_ENCODE")));
     int venc_sessions_ = 0;
+    // Since the sessions pass over constant blocks (constant_block: the first plane of a field is mostly such blocks) a
+    // plane-0 stream leaves its lane many times sooner, but a 16-lane step costs the same whatever its lanes hold: the time
+    // comes back only where other streams move into those lanes.  So a quarter of the workers each (16 workers: 4 + 4
+    // sessions, 3/8 + 5/16 = 6 + 5 before): fuller sessions, and the workers left over go to the scalar decoder loops of
+    // the noise planes, which bound a field's decode.  16 workers, 40 fields in flight, one box, one call, GB/s: 6 + 5
+    // 18.56, 5 + 5 18.76, 6 + 4 17.93, 5 + 4 19.45, 4 + 4 19.49, scalar decode jobs before a new session 18.34
+    // (the model of tools/pool_sim.py at 8 workers: 2 + 2 and 3 + 2 ahead of 3 + 3).  As committed, parent commit / this /
+    // parent / this in one call: 17.36 / 19.31 / 17.92 / 19.44 GB/s (profiles/const_blocks/NOTES.md).
     int venc_sessions_max() const  // call with mu_ held
     {
         const int w = (int)workers_.size();
-        return w < 3 ? 1 : (w * 3 + 4) / 8;
+        return w < 4 ? 1 : (w + 2) / 4;
     }
     const bool vec_ok_ = vec_available();
     int vec_sessions_ = 0;
     int vec_sessions_max() const  // call with mu_ held
     {
         const int w = (int)workers_.size();
-        return w < 4 ? 1 : (w * 5 + 8) / 16;  // 16 workers: 5 sessions (with the vector encoder: 11.3 GB/s; 3 sessions: 10.1)
+        return w < 4 ? 1 : (w + 2) / 4;  // 16 workers: 4 sessions (see venc_sessions_max; 5 until constant blocks were passed over)
     }
     std::vector<std::thread> workers_;
     bool stop_ = false;

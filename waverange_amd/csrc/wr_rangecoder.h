@@ -107,6 +107,7 @@ void pool_test_steal_idle_min(int workers);  // native tests: a hand-over of str
 int pool_threads();
 constexpr int kLoopKinds = 4;
 // per loop kind {scalar enc, scalar dec, vector dec (dominant symbols), vector enc}: worker seconds in block steps, stream-blocks advanced
+// (a constant block that a step passes over behind its header counts as advanced)
 void pool_loop_stats(double seconds[kLoopKinds], double blocks[kLoopKinds]);
 unsigned long pool_streams_moved();  // streams that changed workers between two blocks (an idle worker took over half of the fullest session)
 // decoder jobs that are queued and no worker has taken yet: {planes for the scalar loops (noise), planes for the 16-lane sessions}
