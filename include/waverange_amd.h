@@ -559,6 +559,83 @@ int wr_seg_error_stats_host_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny,
                                 const unsigned char *data_enc, size_t data_len, wr_error_stats *stats);
 int wr_dev_err_stats(wr_ctx *ctx, const double *d_a, const double *d_b, size_t n, wr_error_stats *stats);
 int wr_dev_err_stats_f32(wr_ctx *ctx, const float *d_a, const float *d_b, size_t n, wr_error_stats *stats);
+/* ---- Masked fields: undefined samples travel as a bit mask, split from the field and put back on the GPU.
+ * Semantics.  A sample x of the field (fp64, or fp32 widened exactly) is UNDEFINED if it is not finite, !(fabs(x) <= DBL_MAX),
+ * or if x < below; `below` is the caller's threshold (-INFINITY switches it off, a NaN is WR_ERR_ARG).  All other samples are
+ * defined.  A masked encode
+ *   splits    finds the undefined samples, counts them (`undefined`, exact) and forms pad = S / count, the mean of the defined
+ *             samples: S is an fp64 sum in an order that n alone fixes (a thread in index order, lanes by shuffles at distances
+ *             32 .. 1, waves in order, partials in order; no floating-point atomics), so pad has the same bits on every run.  For
+ *             an fp32 field pad is that mean rounded to float, and the rounded value is what is stored and returned;
+ *   fills     every undefined sample with pad, in the device's work space: the caller's host buffer is only read (a
+ *             device-resident field is consumed, as by wr_encode_device_seg);
+ *   encodes   the padded field as the plain call of the chosen format does -- brick == 0 && strands == 0: WRS1
+ *             (wr_encode_host_seg), brick != 0: WRS2 (_blocked), strands != 0: WRS3 (_strands, brick 0 or an edge); nothing is
+ *             defaulted but seg -- so that info and the first info->ntot_enc bytes of data_enc are bit for bit what that call
+ *             returns for the caller's field with its undefined samples replaced by the returned pad;
+ *   appends   the mask blob at data_enc + info->ntot_enc, res->mask_len bytes.
+ * undefined == 0: mask_len == 0 and the whole result is the plain call's.  No defined sample: WR_ERR_ARG, nothing written.  A
+ * constant padded field (nlay == 0, ntot_enc == 0): the trivial record, and the mask blob at data_enc.  cap must hold the
+ * field's planes plus wr_mask_bound(n, seg) bytes when a sample is undefined: WR_ERR_OVERFLOW otherwise, before data_enc is
+ * written.  Every existing decoder, region decode, low-resolution decode and wr_transcode_host reads the field part as it is,
+ * and returns the padded field.
+ * The mask blob ("WRM1", little endian):
+ *   'W','R','M','1' | u32 0 | u64 n | u64 undefined | f64 pad | WRS1 plane blob of ceil(n / 8) symbols
+ * Bit j & 7 (least significant first) of symbol j >> 3 is 1 iff sample j, in the field's memory order, is undefined; the unused
+ * high bits of the last symbol are 0.  The WRS1 blob is exactly wr_seg_encode_host_ref of those symbols at the call's segment
+ * length, whatever the field's format.  pad is informative: no decoder needs it.
+ * A masked decode takes data_len = field planes + mask blob; data_len == info->ntot_enc (or 0) is an unmasked record and
+ * decodes as wr_decode_host_seg.  Undefined samples come back as `fill` (any double, a NaN included; (float)fill for fp32).
+ * WR_ERR_STREAM, before anything is written to the caller's field: a wrong magic, a nonzero reserved word, an n other than
+ * nx * ny * nz, a truncated or overlong blob, a WRS1 blob that does not decode, a set bit beyond n, a population count other
+ * than `undefined`.
+ * wr_mask_bound: the worst-case mask_len (0: seg refused).  wr_mask_blob_host_ref / wr_mask_parse_host_ref: the blob's
+ * definition on the calling thread, no device needed: from / to one flag byte (0 or 1) per sample; parse applies every refusal
+ * above (null outputs are skipped).  wr_mask_sniff: 1 if data starts like a mask blob.
+ * Stage level (device pointers of any alignment, n >= 1).  wr_dev_mask_split: d_bits[0, ceil(n / 8)) = the mask, *undefined and
+ * *pad as above (pad is a NaN when no sample is defined; the call still succeeds).  wr_dev_mask_fill: d_fld[j] = value where bit
+ * j is set, nothing else is touched.  wr_dev_mask_restore: the same with the mask checked: *undefined = its set bits,
+ * WR_ERR_STREAM if one lies at or beyond n.
+ * wr_mask_result: split_ms, fill_ms (a decode: the restore), mask_coder_ms are HIP-event milliseconds; the mask's coder kernels
+ * run on a stream of their own under the field's transform and quantizer (a decode: under the field's coder stage). */
+typedef struct wr_mask_result {
+    unsigned long long undefined;
+    double pad;
+    size_t mask_len;
+    float split_ms, fill_ms, mask_coder_ms;
+} wr_mask_result;
+size_t wr_mask_bound(size_t n, unsigned seg);
+size_t wr_mask_blob_host_ref(const unsigned char *undef_flags, size_t n, unsigned seg, double pad, unsigned char *blob);
+int wr_mask_parse_host_ref(const unsigned char *blob, size_t len, size_t n, unsigned char *undef_flags,
+                           unsigned long long *undefined, double *pad);
+int wr_mask_sniff(const unsigned char *data, size_t len);
+int wr_dev_mask_split(wr_ctx *ctx, const double *d_fld, size_t n, double below, unsigned char *d_bits,
+                      unsigned long long *undefined, double *pad);
+int wr_dev_mask_split_f32(wr_ctx *ctx, const float *d_fld, size_t n, double below, unsigned char *d_bits,
+                          unsigned long long *undefined, double *pad);
+int wr_dev_mask_fill(wr_ctx *ctx, double *d_fld, size_t n, const unsigned char *d_bits, double value);
+int wr_dev_mask_fill_f32(wr_ctx *ctx, float *d_fld, size_t n, const unsigned char *d_bits, double value);
+int wr_dev_mask_restore(wr_ctx *ctx, double *d_fld, size_t n, const unsigned char *d_bits, double fill,
+                        unsigned long long *undefined);
+int wr_dev_mask_restore_f32(wr_ctx *ctx, float *d_fld, size_t n, const unsigned char *d_bits, double fill,
+                            unsigned long long *undefined);
+int wr_encode_host_seg_masked(wr_ctx *ctx, const double *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                              const double *cutoffvec, unsigned seg, unsigned brick, unsigned strands, double below,
+                              wr_enc_info *info, unsigned char *data_enc, size_t cap, wr_timings *tm, wr_mask_result *res);
+int wr_encode_host_seg_masked_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                  const double *cutoffvec, unsigned seg, unsigned brick, unsigned strands, double below,
+                                  wr_enc_info *info, unsigned char *data_enc, size_t cap, wr_timings *tm, wr_mask_result *res);
+int wr_encode_device_seg_masked(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                const double *cutoffvec, unsigned seg, unsigned brick, unsigned strands, double below,
+                                wr_enc_info *info, unsigned char *data_enc, size_t cap, wr_timings *tm, wr_mask_result *res);
+int wr_decode_host_seg_masked(wr_ctx *ctx, double *h_fld, int nx, int ny, int nz, const wr_enc_info *info,
+                              const unsigned char *data_enc, size_t data_len, double fill, wr_timings *tm, wr_mask_result *res);
+int wr_decode_host_seg_masked_f32(wr_ctx *ctx, float *h_fld, int nx, int ny, int nz, const wr_enc_info *info,
+                                  const unsigned char *data_enc, size_t data_len, double fill, wr_timings *tm,
+                                  wr_mask_result *res);
+int wr_decode_device_seg_masked(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, const wr_enc_info *info,
+                                const unsigned char *data_enc, size_t data_len, double fill, wr_timings *tm,
+                                wr_mask_result *res);
 /* ---- Low-resolution decode of segmented streams: a coarse version of the field without decoding the field.
  * The transform is a Mallat decomposition (waveletcdf97_3d.c:73-78): after level r the low-pass coefficients of an nx*ny*nz
  * field sit in the corner box [0,bx) x [0,by) x [0,bz) of the coefficient array.  With h(n) = (n + 1) / 2 in integer

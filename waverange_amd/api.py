@@ -88,6 +88,15 @@ class ErrorStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class MaskResult(C.Structure):
+    """wr_mask_result"""
+    _fields_ = [("undefined", C.c_ulonglong), ("pad", C.c_double), ("mask_len", C.c_size_t), ("split_ms", C.c_float), ("fill_ms", C.c_float),
+                ("mask_coder_ms", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class FusedLevel(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("tiles_x", "tiles_y", "zps", "zsegs", "zlast")]
 
@@ -254,6 +263,27 @@ def lib():
     L.wr_seg_error_stats_host_f32.argtypes = L.wr_seg_error_stats_host.argtypes
     L.wr_dev_err_stats.argtypes = [_vp, _vp, _vp, C.c_size_t, C.POINTER(ErrorStats)]
     L.wr_dev_err_stats_f32.argtypes = L.wr_dev_err_stats.argtypes
+    # masked fields: the blob on the host, the stage calls and the drivers
+    L.wr_mask_bound.restype = C.c_size_t
+    L.wr_mask_bound.argtypes = [C.c_size_t, C.c_uint]
+    L.wr_mask_blob_host_ref.restype = C.c_size_t
+    L.wr_mask_blob_host_ref.argtypes = [_vp, C.c_size_t, C.c_uint, C.c_double, _vp]
+    L.wr_mask_parse_host_ref.argtypes = [_vp, C.c_size_t, C.c_size_t, _vp, C.POINTER(C.c_ulonglong), _dp]
+    L.wr_mask_sniff.argtypes = [_vp, C.c_size_t]
+    L.wr_dev_mask_split.argtypes = [_vp, _vp, C.c_size_t, C.c_double, _vp, C.POINTER(C.c_ulonglong), _dp]
+    L.wr_dev_mask_split_f32.argtypes = L.wr_dev_mask_split.argtypes
+    L.wr_dev_mask_fill.argtypes = [_vp, _vp, C.c_size_t, _vp, C.c_double]
+    L.wr_dev_mask_fill_f32.argtypes = L.wr_dev_mask_fill.argtypes
+    L.wr_dev_mask_restore.argtypes = [_vp, _vp, C.c_size_t, _vp, C.c_double, C.POINTER(C.c_ulonglong)]
+    L.wr_dev_mask_restore_f32.argtypes = L.wr_dev_mask_restore.argtypes
+    L.wr_encode_host_seg_masked.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_uint, C.c_uint, C.c_uint,
+                                            C.c_double, C.POINTER(EncInfo), _vp, C.c_size_t, C.POINTER(Timings), C.POINTER(MaskResult)]
+    L.wr_encode_host_seg_masked_f32.argtypes = L.wr_encode_host_seg_masked.argtypes
+    L.wr_encode_device_seg_masked.argtypes = L.wr_encode_host_seg_masked.argtypes
+    L.wr_decode_host_seg_masked.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(EncInfo), _vp, C.c_size_t, C.c_double,
+                                            C.POINTER(Timings), C.POINTER(MaskResult)]
+    L.wr_decode_host_seg_masked_f32.argtypes = L.wr_decode_host_seg_masked.argtypes
+    L.wr_decode_device_seg_masked.argtypes = L.wr_decode_host_seg_masked.argtypes
     L.wr_encode_device_seg.argtypes = L.wr_encode_host_seg.argtypes
     L.wr_decode_host_seg.argtypes = L.wr_decode_host.argtypes
     L.wr_decode_host_seg_f32.argtypes = L.wr_decode_host.argtypes
@@ -584,6 +614,46 @@ def seg_decode_host_ref(blob, n):
     out = np.zeros(max(n, 1), dtype=np.uint8)
     _check(lib().wr_seg_decode_host_ref(src.ctypes.data, b.size, out.ctypes.data, n))
     return out[:n]
+
+
+MASK_HEADER_BYTES = 32  # 'W','R','M','1' | u32 0 | u64 n | u64 undefined | f64 pad
+
+
+def mask_bound(n, seg=0):
+    """Worst-case bytes of the mask blob of a field of n samples (0 if `seg` is refused) (wr_mask_bound)."""
+    return int(lib().wr_mask_bound(n, seg))
+
+
+def mask_sniff(data):
+    """True if `data` starts like a mask blob ("WRM1")."""
+    b = np.ascontiguousarray(data, dtype=np.uint8).ravel()
+    return bool(b.size and lib().wr_mask_sniff(b.ctypes.data, b.size))
+
+
+def mask_blob_host_ref(flags, seg=0, pad=0.0):
+    """The mask blob of a field whose sample j is undefined iff flags[j] is nonzero, made on the calling thread: the definition
+    of the format (wr_mask_blob_host_ref)."""
+    f = np.ascontiguousarray(np.asarray(flags) != 0, dtype=np.uint8).ravel()
+    bound = mask_bound(f.size, seg)
+    if not bound:
+        raise WaveRangeError(_BAD_SEG)
+    out = np.empty(bound, dtype=np.uint8)
+    src = f if f.size else np.zeros(1, dtype=np.uint8)
+    n = lib().wr_mask_blob_host_ref(src.ctypes.data, f.size, seg, float(pad), out.ctypes.data)
+    if not n:
+        raise WaveRangeError(lib().wr_last_error().decode())
+    return out[:n].copy()
+
+
+def mask_parse_host_ref(blob, n):
+    """(flags, undefined, pad) of a mask blob for a field of n samples, parsed on the calling thread; raises WaveRangeError
+    (WR_ERR_STREAM) for every blob a decoder refuses (wr_mask_parse_host_ref)."""
+    b = np.ascontiguousarray(blob, dtype=np.uint8).ravel()
+    src = b if b.size else np.zeros(1, dtype=np.uint8)
+    flags = np.zeros(max(n, 1), dtype=np.uint8)
+    undefined, pad = C.c_ulonglong(0), C.c_double(0)
+    _check(lib().wr_mask_parse_host_ref(src.ctypes.data, b.size, n, flags.ctypes.data, C.byref(undefined), C.byref(pad)))
+    return flags[:n].astype(bool), int(undefined.value), pad.value
 
 
 BRICK_DEFAULT = 32  # WR_BRICK_DEFAULT
@@ -1401,6 +1471,91 @@ class Context:
         """encode_host_seg with the field resident on the device (`buf` is consumed, as by encode)."""
         fn = lib().wr_encode_device_seg_strands if strands is not None else lib().wr_encode_device_seg if brick is None else lib().wr_encode_device_seg_blocked
         return self._encode_seg(fn, buf.ptr, shape, tolrel, wtflag, seg, out, cutoff, m, brick, strands)
+
+    # ---- masked fields: undefined samples (not finite, or below `below`) travel as a bit mask behind the field's planes
+    def _encode_seg_masked(self, fn, ptr, shape, tolrel, below, wtflag, seg, brick, strands, out, cutoff, m):
+        nz, ny, nx = shape
+        cap = self._seg_cap(shape, seg, brick if brick else None, strands if strands else None) + mask_bound(nx * ny * nz, seg)
+        data = out if out is not None else np.empty(cap, dtype=np.uint8)
+        cut = np.ascontiguousarray([tolrel] if cutoff is None else cutoff, dtype=np.float64)
+        info, tm, res = EncInfo(), Timings(), MaskResult()
+        _check(fn(self.h, ptr, nx, ny, nz, wtflag, m[0], m[1], m[2], cut.ctypes.data_as(_dp), seg, brick, strands, float(below), C.byref(info),
+                  data.ctypes.data, data.size, C.byref(tm), C.byref(res)))
+        d = info.as_dict()
+        d["data"] = data[:info.ntot_enc + res.mask_len]
+        d["mask"] = res.as_dict()
+        return d, tm.as_dict()
+
+    def encode_host_seg_masked(self, fld, tolrel, below=-np.inf, wtflag=1, seg=0, brick=0, strands=0, out=None, cutoff=None, m=(1, 1, 1)):
+        """encode_host_seg of `fld` with its undefined samples -- not finite, or < below -- replaced by the mean of the defined
+        ones, and the mask blob behind the planes (wr_encode_host_seg_masked).  brick = 0, strands = 0: WRS1; brick > 0: WRS2;
+        strands > 0: WRS3.  The record's "data" holds ntot_enc bytes of planes, then mask["mask_len"] bytes of mask blob;
+        "mask" = {"undefined", "pad", "mask_len", ...}.  data[:ntot_enc] is what every other decoder reads."""
+        assert fld.dtype == np.float64 and fld.flags["C_CONTIGUOUS"]
+        return self._encode_seg_masked(lib().wr_encode_host_seg_masked, fld.ctypes.data, fld.shape, tolrel, below, wtflag, seg, brick, strands, out, cutoff, m)
+
+    def encode_host_seg_masked_f32(self, fld, tolrel, below=-np.inf, wtflag=1, seg=0, brick=0, strands=0, out=None, cutoff=None, m=(1, 1, 1)):
+        if not (isinstance(fld, np.ndarray) and fld.dtype == np.float32 and fld.flags["C_CONTIGUOUS"]):
+            raise TypeError("encode_host_seg_masked_f32: a C-contiguous float32 array is required")
+        return self._encode_seg_masked(lib().wr_encode_host_seg_masked_f32, fld.ctypes.data, fld.shape, tolrel, below, wtflag, seg, brick, strands, out, cutoff, m)
+
+    def encode_seg_masked(self, buf, shape, tolrel, below=-np.inf, wtflag=1, seg=0, brick=0, strands=0, out=None, cutoff=None, m=(1, 1, 1)):
+        """encode_host_seg_masked with the field resident on the device (`buf` is consumed, as by encode)."""
+        return self._encode_seg_masked(lib().wr_encode_device_seg_masked, buf.ptr, shape, tolrel, below, wtflag, seg, brick, strands, out, cutoff, m)
+
+    def _decode_seg_masked(self, fn, ptr, shape, enc, fill):
+        nz, ny, nx = shape
+        info = EncInfo.from_dict(enc)
+        tm, res = Timings(), MaskResult()
+        data = np.ascontiguousarray(enc["data"], dtype=np.uint8)
+        src = data if data.size else np.zeros(1, dtype=np.uint8)
+        _check(fn(self.h, ptr, nx, ny, nz, C.byref(info), src.ctypes.data, data.size, float(fill), C.byref(tm), C.byref(res)))
+        return res.as_dict(), tm.as_dict()
+
+    def decode_host_seg_masked(self, out, enc, fill=np.nan):
+        """decode_host_seg of a masked record (enc["data"]: planes, then the mask blob), the undefined samples set to `fill`; a
+        record without a mask blob decodes as decode_host_seg.  Returns (mask, timings)."""
+        assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"]
+        return self._decode_seg_masked(lib().wr_decode_host_seg_masked, out.ctypes.data, out.shape, enc, fill)
+
+    def decode_host_seg_masked_f32(self, out, enc, fill=np.nan):
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"]):
+            raise TypeError("decode_host_seg_masked_f32: a C-contiguous float32 array is required")
+        return self._decode_seg_masked(lib().wr_decode_host_seg_masked_f32, out.ctypes.data, out.shape, enc, fill)
+
+    def decode_seg_masked(self, buf, shape, enc, fill=np.nan):
+        """decode_host_seg_masked into a field resident on the device."""
+        return self._decode_seg_masked(lib().wr_decode_device_seg_masked, buf.ptr, shape, enc, fill)
+
+    @staticmethod
+    def _mask_dtype(who, dtype):
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise TypeError(who + ": float64 or float32")
+        return dt
+
+    def mask_split(self, fld, n, bits, below=-np.inf, dtype=np.float64, offset=0, bits_offset=0):
+        """Stage level: the mask of n samples of the device buffer `fld`, starting `offset` ELEMENTS into it, into the device
+        buffer `bits` (ceil(n / 8) bytes from byte bits_offset): (undefined, pad) (wr_dev_mask_split, wr_dev_mask_split_f32)."""
+        dt = self._mask_dtype("mask_split", dtype)
+        fn = lib().wr_dev_mask_split if dt == np.float64 else lib().wr_dev_mask_split_f32
+        undefined, pad = C.c_ulonglong(0), C.c_double(0)
+        _check(fn(self.h, fld.ptr + offset * dt.itemsize, int(n), float(below), bits.ptr + bits_offset, C.byref(undefined), C.byref(pad)))
+        return int(undefined.value), pad.value
+
+    def mask_fill(self, fld, n, bits, value, dtype=np.float64, offset=0, bits_offset=0):
+        """Stage level: `value` into the samples of `fld` whose mask bit is set (wr_dev_mask_fill, wr_dev_mask_fill_f32)."""
+        dt = self._mask_dtype("mask_fill", dtype)
+        fn = lib().wr_dev_mask_fill if dt == np.float64 else lib().wr_dev_mask_fill_f32
+        _check(fn(self.h, fld.ptr + offset * dt.itemsize, int(n), bits.ptr + bits_offset, float(value)))
+
+    def mask_restore(self, fld, n, bits, fill=np.nan, dtype=np.float64, offset=0, bits_offset=0):
+        """Stage level: mask_fill with the mask checked; returns the count of its set bits (wr_dev_mask_restore, _f32)."""
+        dt = self._mask_dtype("mask_restore", dtype)
+        fn = lib().wr_dev_mask_restore if dt == np.float64 else lib().wr_dev_mask_restore_f32
+        undefined = C.c_ulonglong(0)
+        _check(fn(self.h, fld.ptr + offset * dt.itemsize, int(n), bits.ptr + bits_offset, float(fill), C.byref(undefined)))
+        return int(undefined.value)
 
     # ---- encode to a byte budget: the library picks the tolerance on the grid budget_tol(g), every plane is coded once
     def _encode_seg_budget(self, fn, ptr, shape, max_bytes, tol_min, wtflag, seg, out, m):

@@ -6,6 +6,9 @@
 // TYPE 0: PREFIX.ctl + PREFIX_h.enc + PREFIX_f.enc -> OUT.grd (+ a copy of the control file as OUT.ctl)
 // TYPE 1: PREFIX.nmlst + PREFIX_h.enc/_f.enc      -> OUT.p_NNNN for every subdomain
 // TYPE 2: PREFIX.nmlst + PREFIX_hNNNN.enc/_fNNNN.enc -> OUT.p_NNNN for subdomain PROCID
+//
+// A TYPE 0 "mask" record whose payload is a WRM1 blob (wrenc_mssg --mask=bits) is decoded together with the field record behind
+// it by wr_decode_host_seg_masked, the undefined points coming back as the control file's `undef`; no option is needed.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +22,7 @@
 
 #include "../../../include/waverange_amd.h"
 #include "mssg_io.h"
+#include "segfmt.h"
 
 using namespace wrmssg;
 
@@ -67,14 +71,62 @@ void open_or_die(std::ifstream& f, const std::string& path, std::ios::openmode m
     if (!f) { std::cout << "Cannot read from " << path << std::endl; std::exit(1); }
 }
 
-// read ntot_enc payload bytes and decode them into fld (nothing to read for a constant field)
-void decode_dataset(std::ifstream& payload, const Coding& c, int nx, int ny, int nz, double* fld, std::vector<unsigned char>& buf)
+// the ntot_enc payload bytes of a data set into buf (nothing to read for a constant field)
+void read_dataset(std::ifstream& payload, const Coding& c, std::vector<unsigned char>& buf, size_t at = 0)
 {
-    if (buf.size() < c.ntot_enc) buf.resize(c.ntot_enc);
-    payload.read(reinterpret_cast<char*>(buf.data()), (std::streamsize)c.ntot_enc);
+    if (buf.size() < at + c.ntot_enc) buf.resize(at + c.ntot_enc);
+    payload.read(reinterpret_cast<char*>(buf.data() + at), (std::streamsize)c.ntot_enc);
+}
+
+// ... decoded into fld
+void decode_buffer(const Coding& c, int nx, int ny, int nz, double* fld, std::vector<unsigned char>& buf)
+{
     Coding m = c;  // decoding_wrap takes non-const pointers
     decoding_wrap(nx, ny, nz, fld, &m.tolabs, &m.midval, &m.halfspanval, &m.wlev, &m.nlay, &m.ntot_enc, m.deps_vec, m.minval_vec,
                   m.len_enc_vec, buf.data());
+}
+
+void decode_dataset(std::ifstream& payload, const Coding& c, int nx, int ny, int nz, double* fld, std::vector<unsigned char>& buf)
+{
+    read_dataset(payload, c, buf);
+    decode_buffer(c, nx, ny, nz, fld, buf);
+}
+
+// wr_mask_sniff, or for a codec library without it the magic alone (decode_masked then says that the library cannot read it)
+bool is_mask_blob(const std::vector<unsigned char>& buf, size_t len)
+{
+    return wr_mask_sniff ? wr_mask_sniff(buf.data(), len) != 0 : len >= 4 && memcmp(buf.data(), "WRM1", 4) == 0;
+}
+
+// A masked record: the WRM1 blob of `mask_len` bytes is in `blob`; the field record `c` follows in the payload.  The planes go in
+// front of the blob, as wr_decode_host_seg_masked reads them.
+void decode_masked(std::ifstream& payload, const Coding& c, size_t mask_len, int nx, int ny, int nz, double undef, double* fld,
+                   std::vector<unsigned char>& blob, std::vector<unsigned char>& buf)
+{
+    if (!(wr_decode_host_seg_masked && wr_mask_sniff && wr_ctx_create && wr_ctx_destroy && wr_last_error)) {
+        std::cout << "Error: a bit-mask record (WRM1): " << wrcli::kNotSupported << std::endl;
+        std::exit(2);
+    }
+    read_dataset(payload, c, buf);
+    if (buf.size() < c.ntot_enc + mask_len) buf.resize(c.ntot_enc + mask_len);
+    memcpy(buf.data() + c.ntot_enc, blob.data(), mask_len);
+    wr_enc_info info;
+    memset(&info, 0, sizeof info);
+    info.tolabs = c.tolabs; info.midval = c.midval; info.halfspanval = c.halfspanval;
+    info.wlev = c.wlev; info.nlay = c.nlay; info.ntot_enc = c.ntot_enc;
+    for (int l = 0; l < c.nlay && l < kNlayMax; l++) { info.deps_vec[l] = c.deps_vec[l]; info.minval_vec[l] = c.minval_vec[l]; info.len_enc_vec[l] = c.len_enc_vec[l]; }
+    int dev = 0;
+    if (const char* e = getenv("WR_DEVICE")) dev = atoi(e);
+    wr_ctx* ctx = nullptr;
+    int rc = wr_ctx_create(&ctx, dev, nullptr);
+    if (rc == 0) {
+        rc = wr_decode_host_seg_masked(ctx, fld, nx, ny, nz, &info, buf.data(), c.ntot_enc + mask_len, undef, nullptr, nullptr);
+        if (rc != 0) std::cout << "Error: " << wr_last_error() << std::endl;
+        wr_ctx_destroy(ctx);
+    } else {
+        std::cout << "Error: " << wr_last_error() << std::endl;
+    }
+    if (rc != 0) std::exit(1);
 }
 
 // ---- TYPE 0 (mssg_dec.cpp:152-331)
@@ -94,7 +146,7 @@ int regular_output(const Params& p, int nbytes)
     std::string line;
     for (int j = 0; j < 8; j++) std::getline(header, line);  // the preamble written by the encoder
     std::vector<double> fld(ntot), mask;
-    std::vector<unsigned char> buf;
+    std::vector<unsigned char> buf, blob;
     for (int it = 0; it < g.nt; it++) {
         Coding c;
         std::string name = read_header_record(header, it, &c);
@@ -102,11 +154,21 @@ int regular_output(const Params& p, int nbytes)
         bool masked = false;
         double mask_mid = 0;
         if (name == "mask") {  // a mask record precedes the field record of the same number (mssg_dec.cpp:233-273)
+            if (c.ntot_enc > 0) read_dataset(payload, c, blob);
+            if (c.ntot_enc > 0 && is_mask_blob(blob, c.ntot_enc)) {  // the undefined points as bits: one call restores the field
+                const size_t mask_len = c.ntot_enc;
+                name = read_header_record(header, it, &c);
+                std::cout << "  decoding mask bits and fld_1d_rec, it=" << it << std::endl;
+                decode_masked(payload, c, mask_len, g.nx, g.ny, g.nz, g.undef, fld.data(), blob, buf);
+                write_field(out_name, p.flip != 0, nbytes, it, g.nx, g.ny, g.nz, g.nx, g.ny, 0, 0, fld.data());
+                std::cout << "  wrote: fld_1d_rec[0]=" << fld[0] << " fld_1d_rec[last]=" << fld[ntot - 1] << std::endl;
+                continue;
+            }
             masked = true;
             mask.assign(ntot, c.midval);
             if (c.ntot_enc > 0) {
                 std::cout << "  decoding mask_1d_rec, it=" << it << std::endl;
-                decode_dataset(payload, c, g.nx, g.ny, g.nz, mask.data(), buf);
+                decode_buffer(c, g.nx, g.ny, g.nz, mask.data(), blob);
                 mask_mid = c.midval;
                 // the two mask values sit on either side of the middle value: back to {undef, 0}
                 for (size_t j = 0; j < ntot; j++) mask[j] = (mask[j] < c.midval) ? g.undef : 0;

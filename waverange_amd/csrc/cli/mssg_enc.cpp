@@ -9,6 +9,12 @@
 // TYPE 2: restart set, the one subdomain PROCID on its own                              -> PREFIX_hNNNN.enc/_fNNNN.enc
 // A file "inmeta" in the working directory replaces the arguments ("&name=value" lines or the seven
 // values one per line); with neither, the values are asked for on stdin.
+//
+// --mask=bits (an option of this tool, taken out of argv before the arguments are counted): a TYPE 0 field goes through
+// wr_encode_host_seg_masked in the segmented stream format in force (WR_STREAM_FORMAT), so that its undefined points -- values
+// below the mask threshold, NaNs, infinities -- travel as a packed bit mask: a record named "mask" whose payload is the WRM1
+// blob (nlay = 1, len_enc_vec[0] = ntot_enc = its length, the other scalars 0), then the field's record as always.  wrdec_mssg
+// recognises the blob by its magic.  Without the option nothing changes.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -23,6 +29,7 @@
 
 #include "../../../include/waverange_amd.h"
 #include "mssg_io.h"
+#include "segfmt.h"
 
 using namespace wrmssg;
 
@@ -171,8 +178,50 @@ void min_max(const double* f, size_t n, double* lo, double* hi)
     *lo = a; *hi = b;
 }
 
+// --mask=bits: the context and the segmented format the masked calls run in
+struct MaskBits {
+    wr_ctx* ctx = nullptr;
+    unsigned seg = 0, brick = 0, strands = 0;
+};
+
+// one TYPE 0 field through wr_encode_host_seg_masked: the "mask" record if a sample is undefined, then the field's record
+void code_masked(const MaskBits& mb, int nx, int ny, int nz, const double* fld, double tolrel, double below, std::vector<unsigned char>& buf,
+                 const std::string& header, const std::string& payload, int idset, const std::string& name)
+{
+    const size_t ntot = (size_t)nx * (size_t)ny * (size_t)nz;
+    unsigned char nlaymax;
+    unsigned long cap;
+    setup_wr(nx, ny, nz, &nlaymax, &cap);
+    const size_t need = (size_t)cap + wr_mask_bound(ntot, mb.seg);
+    if (buf.size() < need) buf.resize(need);
+    wr_enc_info info;
+    wr_mask_result res;
+    double cutoff = tolrel;
+    if (wr_encode_host_seg_masked(mb.ctx, fld, nx, ny, nz, 1, 1, 1, 1, &cutoff, mb.seg, mb.brick, mb.strands, below, &info, buf.data(), buf.size(),
+                                  nullptr, &res) != 0) {
+        std::cout << "Error: " << wr_last_error() << std::endl;
+        std::exit(1);
+    }
+    if (res.undefined) {
+        std::cout << " Masking detected, " << res.undefined << " undefined points as a bit mask of " << res.mask_len << " bytes, padding with fld_pad="
+                  << res.pad << std::endl;
+        Coding m;
+        m.nlay = 1;
+        m.ntot_enc = m.len_enc_vec[0] = (unsigned long)res.mask_len;
+        append_header_record(header, idset, "mask", m);
+        append_bytes(payload, buf.data() + info.ntot_enc, (unsigned long)res.mask_len);
+    }
+    Coding c;
+    c.tolabs = info.tolabs; c.midval = info.midval; c.halfspanval = info.halfspanval;
+    c.wlev = info.wlev; c.nlay = info.nlay; c.ntot_enc = info.ntot_enc;
+    for (int l = 0; l < info.nlay; l++) { c.deps_vec[l] = info.deps_vec[l]; c.minval_vec[l] = info.minval_vec[l]; c.len_enc_vec[l] = info.len_enc_vec[l]; }
+    append_header_record(header, idset, name, c);
+    if (c.ntot_enc > 0) append_bytes(payload, buf.data(), c.ntot_enc);
+    std::cout << "        tolabs=" << c.tolabs << std::endl;
+}
+
 // ---- TYPE 0 (mssg_enc.cpp:277-414)
-int regular_output(const Params& p, int nbytes)
+int regular_output(const Params& p, int nbytes, const MaskBits* mb)
 {
     const GradsControl g = read_grads_control(p.prefix + ".ctl");
     const size_t ntot = (size_t)g.nx * (size_t)g.ny * (size_t)g.nz;
@@ -194,6 +243,10 @@ int regular_output(const Params& p, int nbytes)
         // go into a two-valued mask field {min, 0}, coded without the transform at a tolerance that keeps
         // the two values apart, and are padded with the mean of the defined points (mssg_enc.cpp:323-381).
         const double thresh = g.undef + std::fabs(g.undef) * kMaskThresholdAcc;
+        if (mb) {
+            code_masked(*mb, g.nx, g.ny, g.nz, fld.data(), p.tol, thresh, buf, header, payload, it, g.dset);
+            continue;
+        }
         if (lo < thresh) {
             double pad = 0;
             int defined = 0;
@@ -269,9 +322,45 @@ int restart_set(const Params& p, int nbytes)
 
 }  // namespace
 
+// --mask=bits: refused, before anything is read or written, unless the library has the masked calls and a segmented format is in force
+int mask_bits_setup(MaskBits* mb)
+{
+    if (!(wr_encode_host_seg_masked && wr_mask_bound && wr_get_stream_format && wr_ctx_create && wr_ctx_destroy && wr_last_error)) {
+        fprintf(stderr, "wrenc_mssg: --mask=bits: %s\n", wrcli::kNotSupported);
+        return 2;
+    }
+    int format = WR_FORMAT_REF;
+    if (wr_get_stream_format(&format, &mb->seg, &mb->brick, &mb->strands) != 0) {
+        fprintf(stderr, "wrenc_mssg: --mask=bits: %s\n", wr_last_error());
+        return 2;
+    }
+    if (format == WR_FORMAT_REF) {
+        fprintf(stderr, "wrenc_mssg: --mask=bits needs a segmented stream format (WR_STREAM_FORMAT=wrs1, wrs2 or wrs3): the reference's stream "
+                        "format has no mask blob\n");
+        return 2;
+    }
+    int dev = 0;
+    if (const char* e = getenv("WR_DEVICE")) dev = atoi(e);
+    if (wr_ctx_create(&mb->ctx, dev, nullptr) != 0) {
+        fprintf(stderr, "wrenc_mssg: --mask=bits: %s\n", wr_last_error());
+        return 2;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     setenv("WR_WRITEBACK_RESIDUAL", "0", 0);  // the residual encoding_wrap leaves in the field array is not used here
+    std::vector<std::string> options;
+    argc = wrcli::take_options(argc, argv, options);
+    MaskBits mb;
+    bool mask_bits = false;
+    for (const std::string& o : options) {
+        std::string v;
+        if (wrcli::option_value(o, "mask", &v) && v == "bits") mask_bits = true;
+        else { fprintf(stderr, "wrenc_mssg: unknown option %s (--mask=bits is the only one)\n", o.c_str()); return 2; }
+    }
+    if (mask_bits) if (int rc = mask_bits_setup(&mb)) return rc;
     Params p;
     if (!get_params(argc, argv, &p)) return -1;
     const int nbytes = p.intype == 1 ? 4 : 8;
@@ -284,9 +373,10 @@ int main(int argc, char** argv)
     std::cout << "Base cutoff relative tolerance: " << p.tol << std::endl;
     std::cout << "This proc id: " << p.proc << std::endl;
     int rc = 0;
-    if (p.filetype == 0) rc = regular_output(p, nbytes);
+    if (p.filetype == 0) rc = regular_output(p, nbytes, mask_bits ? &mb : nullptr);
     else if (p.filetype == 1 || p.filetype == 2) rc = restart_set(p, nbytes);
     else std::cout << "Error: unknown file type" << std::endl;
     std::cout << "=== End of compression ===\n";
+    if (mb.ctx) wr_ctx_destroy(mb.ctx);
     return rc;
 }

@@ -74,6 +74,17 @@ int wr_encode_host_seg_quality_f32(wr_ctx* ctx, const float* h_fld, int nx, int 
                                    wr_timings* tm, wr_quality_result* res) __attribute__((weak));
 }
 
+// masked fields (wrenc_mssg --mask=bits, wrdec_mssg)
+extern "C" {
+size_t wr_mask_bound(size_t n, unsigned seg) __attribute__((weak));
+int wr_mask_sniff(const unsigned char* data, size_t len) __attribute__((weak));
+int wr_encode_host_seg_masked(wr_ctx* ctx, const double* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,
+                              unsigned seg, unsigned brick, unsigned strands, double below, wr_enc_info* info, unsigned char* data_enc, size_t cap,
+                              wr_timings* tm, wr_mask_result* res) __attribute__((weak));
+int wr_decode_host_seg_masked(wr_ctx* ctx, double* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
+                              double fill, wr_timings* tm, wr_mask_result* res) __attribute__((weak));
+}
+
 // the region decode over a batch of fields (wrdec --batch)
 extern "C" {
 int wr_decode_host_seg_roi_batch(wr_ctx* ctx, double* h_out, int nfields, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,

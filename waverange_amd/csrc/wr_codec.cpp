@@ -13,6 +13,7 @@
 #include "wr_budget.h"
 #include "wr_internal.h"
 #include "wr_lowres.h"
+#include "wr_mask.h"
 #include "wr_roi.h"
 #include "wr_segbatch.h"
 #include "wr_segcoder.h"
@@ -1346,6 +1347,8 @@ struct SegBufs {
     DevPlanes::Buf stage, blob[WR_NLAYMAX], work[WR_NLAYMAX];
     DevPlanes::Buf perm, bricks;  // a blocked stream: one plane in stream order (every plane in turn), the brick list of a partial decode
     DevPlanes::Buf trial[3];      // an encode to an error bound / wr_seg_error_host: two work arrays of a trial, the copy of the field
+    DevPlanes::Buf mask[3];       // a masked call: the mask bits (and the restore's counters), the mask coder's stage or work buffer, its blob
+    hipStream_t also = nullptr;   // a second stream that uses these buffers (a masked call's mask coder): waited for before they go back
     PlaneEvents ev;
     explicit SegBufs(wr_ctx* ctx) : c(ctx) {}
     int coded_plane(int l, size_t cap) { blob[l] = plane_scratch(c, cap); return blob[l].p ? ev.create(l) : WR_ERR_HIP; }  // an encoder's blob and event pair
@@ -1354,10 +1357,12 @@ struct SegBufs {
     ~SegBufs()
     {
         (void)hipStreamSynchronize(c->stream);
+        if (also) (void)hipStreamSynchronize(also);
         if (stage.p) c->pool->planes.give(stage);
         if (perm.p) c->pool->planes.give(perm);
         if (bricks.p) c->pool->planes.give(bricks);
         for (DevPlanes::Buf& b : trial) if (b.p) c->pool->planes.give(b);
+        for (DevPlanes::Buf& b : mask) if (b.p) c->pool->planes.give(b);
         for (int l = 0; l < WR_NLAYMAX; l++) {
             if (blob[l].p) c->pool->planes.give(blob[l]);
             if (work[l].p) c->pool->planes.give(work[l]);
@@ -1891,10 +1896,275 @@ struct BoundedSearch {
     }
 };
 
+// ---- masked fields (include/waverange_amd.h; the kernels and the blob: wr_mask.h) -------------------------------------------
+// A masked encode is the plain segmented encode with two stages in front of the prologue -- split (the mask bits, the count
+// and the mean of the defined samples: one read of the field where upload_field left it) and fill (the mean into the undefined
+// samples, in the slot) -- and the mask blob behind the field's planes.  The mask's coder kernels go on a stream of their own
+// as soon as the split has been read back, so that they run under the field's transform and quantizer; they share nothing with
+// the field's stages but the bits, which nothing writes after the split.  A masked decode runs the mask's decoder on the
+// second stream under the field's coder stage, checks the mask before the finisher writes anything, and puts `fill` into the
+// field behind the inverse transform, in the slot (a host field) or in the caller's array (a device field).
+std::string bad_segments_text(unsigned int k);
+int seg_upload_offsets(const uint8_t* front, size_t head, uint32_t nseg, uint8_t* work);
+
+struct MaskStreams {
+    hipStream_t st = nullptr;
+    hipEvent_t ev[6] = {nullptr};  // pairs: split (decode: unused), fill or restore, the mask's coder
+    MaskStreams() = default;
+    MaskStreams(const MaskStreams&) = delete;
+    MaskStreams& operator=(const MaskStreams&) = delete;
+    ~MaskStreams()
+    {
+        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+    int create()
+    {
+        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+        return WR_OK;
+    }
+    float ms(int pair) const
+    {
+        float t = 0;
+        if (hipEventElapsedTime(&t, ev[2 * pair], ev[2 * pair + 1]) != hipSuccess) { (void)hipGetLastError(); return 0; }
+        return t;
+    }
+};
+
+unsigned long long* mask_result_host(wr_ctx* c) { return reinterpret_cast<unsigned long long*>(c->h_result + 8 + 2 * WR_NLAYMAX + wrk::kProbeK + 5); }
+unsigned long long* mask_result_dev(wr_ctx* c) { return reinterpret_cast<unsigned long long*>(c->h_result_dev + 8 + 2 * WR_NLAYMAX + wrk::kProbeK + 5); }
+
+// the split's read-back: S and the count of the defined samples (c->h_result[0 .. 1]) as the count of undefined ones and the pad
+template <class T>
+void mask_split_result(wr_ctx* c, size_t n, unsigned long long* undefined, double* pad)
+{
+    unsigned long long count = 0;
+    memcpy(&count, c->h_result + 1, sizeof count);
+    *undefined = (unsigned long long)n - count;
+    double mean = count ? c->h_result[0] / (double)count : NAN;
+    if (sizeof(T) == sizeof(float)) mean = (double)(float)mean;  // (what an fp32 field is filled with)
+    *pad = mean;
+}
+
+struct MaskEncode {
+    // what the caller asks for
+    double below = -INFINITY;
+    // what comes out
+    unsigned long long undefined = 0;
+    double pad = 0;
+    size_t mask_len = 0;
+    float split_ms = 0, fill_ms = 0, coder_ms = 0;
+
+    wr_ctx* c = nullptr;
+    MaskStreams s;
+    size_t n = 0, nsym = 0, blob_cap = 0;
+    unsigned seg = 0;
+
+    // the buffers (from the plane pool, kept in bufs) and the second stream
+    int begin(wr_ctx* ctx, SegBufs* bufs, size_t count, unsigned seg_len)
+    {
+        c = ctx; n = count; seg = seg_len; nsym = wrmask::mask_bytes(n);
+        blob_cap = (wr_seg_bound(nsym, seg) + 15) & ~(size_t)15;
+        bufs->mask[0] = plane_scratch(c, (nsym + 255) & ~(size_t)255);
+        bufs->mask[1] = plane_scratch(c, wrk::seg_stage_bytes(nsym, seg));
+        bufs->mask[2] = plane_scratch(c, blob_cap);
+        for (const DevPlanes::Buf& b : bufs->mask) if (!b.p) return WR_ERR_HIP;
+        if (int rc = s.create()) return rc;
+        bufs->also = s.st;
+        return WR_OK;
+    }
+
+    // (cu_mu held, the context's stream) split and fill of the field at d_x; then the mask's coder kernels on the second stream
+    template <class T>
+    int split_fill(SegBufs* bufs, T* d_x)
+    {
+        uint8_t* const bits = bufs->mask[0].p;
+        HIPCHK(hipEventRecord(s.ev[0], c->stream));
+        wrk::mask_split(d_x, n, below, bits, c->d_partial, c->h_result_dev, c->stream);
+        HIPCHK(hipEventRecord(s.ev[1], c->stream));
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask split launch failed");
+        HIPCHK(hipEventSynchronize(s.ev[1]));
+        split_ms = s.ms(0);
+        mask_split_result<T>(c, n, &undefined, &pad);
+        if (undefined == (unsigned long long)n) return fail(WR_ERR_ARG, "no defined sample: every sample of the field is a NaN, an infinity or below the threshold");
+        if (!(fabs(pad) <= DBL_MAX)) return fail(WR_ERR_ARG, "the mean of the defined samples is not finite");
+        if (!undefined) return WR_OK;
+        HIPCHK(hipEventRecord(s.ev[2], c->stream));
+        wrk::mask_fill(d_x, n, bits, (T)pad, c->stream);
+        HIPCHK(hipEventRecord(s.ev[3], c->stream));
+        HIPCHK(hipEventRecord(s.ev[4], s.st));
+        wrk::seg_encode(wrk::plane_ref(bits), nsym, seg, bufs->mask[1].p, bufs->mask[2].p, blob_cap, mask_result_dev(c), s.st);
+        HIPCHK(hipEventRecord(s.ev[5], s.st));
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask coder launch failed");
+        return WR_OK;
+    }
+
+    // the blob to data_enc + at, once the field's planes are there
+    int finish(const SegBufs& bufs, unsigned char* data_enc, size_t at)
+    {
+        if (!undefined) return WR_OK;
+        if (hipStreamSynchronize(s.st) != hipSuccess) return fail(WR_ERR_HIP, "the mask's coder failed on the device");
+        const unsigned long long len = mask_result_host(c)[0], bad = mask_result_host(c)[1];
+        if (bad || len > blob_cap) return fail(WR_ERR_HIP, std::string("internal: mask plane: ") + kOutgrew);
+        wrmask::put_header(data_enc + at, n, undefined, pad);
+        if (int rc = xfer_field(c, &c->x_field, data_enc + at + wrmask::kHeaderBytes, bufs.mask[2].p, (size_t)len, kDown)) return rc;
+        mask_len = wrmask::kHeaderBytes + (size_t)len;
+        fill_ms = s.ms(1);
+        coder_ms = s.ms(2);
+        return WR_OK;
+    }
+
+    void result(wr_mask_result* res) const
+    {
+        if (!res) return;
+        res->undefined = undefined; res->pad = pad; res->mask_len = mask_len;
+        res->split_ms = split_ms; res->fill_ms = fill_ms; res->mask_coder_ms = coder_ms;
+    }
+};
+
+struct MaskDecode {
+    // what the caller gives: the blob behind the field's planes, and what the undefined samples become
+    const unsigned char* blob = nullptr;
+    size_t len = 0;
+    double fill = NAN;
+    // what comes out
+    unsigned long long undefined = 0;
+    double pad = 0;
+    float restore_ms = 0, coder_ms = 0;
+
+    wr_ctx* c = nullptr;
+    MaskStreams s;
+    size_t n = 0, nsym = 0;
+    uint32_t seg = 0, nseg = 0;
+    uint8_t* bits = nullptr;
+    unsigned long long* counters = nullptr;  // behind the bits
+    unsigned int h_bad = 0;
+    unsigned long long h_counters[2] = {0, 0};
+
+    const unsigned char* plane() const { return blob + wrmask::kHeaderBytes; }
+    size_t plane_len() const { return len - wrmask::kHeaderBytes; }
+
+    // the header and the index, on the host: nothing is launched for a blob that fails here
+    int parse(size_t count)
+    {
+        n = count; nsym = wrmask::mask_bytes(n);
+        if (!blob) return fail(WR_ERR_ARG, "null coded buffer");
+        if (const char* why = wrmask::check_header(blob, len, n, &undefined, &pad)) return fail(WR_ERR_STREAM, why);
+        if (const char* why = wrseg::check_index(plane(), plane_len(), plane_len(), nsym, &seg, &nseg)) return fail(WR_ERR_STREAM, std::string("mask blob: ") + why);
+        return WR_OK;
+    }
+
+    // the buffers, the second stream, the blob and its offsets on the device
+    int upload(wr_ctx* ctx, SegBufs* bufs)
+    {
+        c = ctx;
+        const size_t bits_bytes = (nsym + 255) & ~(size_t)255;
+        bufs->mask[0] = plane_scratch(c, bits_bytes + 256);
+        bufs->mask[1] = plane_scratch(c, wrk::seg_decode_work_bytes(nseg));
+        bufs->mask[2] = plane_scratch(c, (plane_len() + 15) & ~(size_t)15);
+        for (const DevPlanes::Buf& b : bufs->mask) if (!b.p) return WR_ERR_HIP;
+        bits = bufs->mask[0].p;
+        counters = reinterpret_cast<unsigned long long*>(bits + bits_bytes);
+        if (int rc = s.create()) return rc;
+        bufs->also = s.st;
+        if (int rc = xfer_field(c, &c->x_field, bufs->mask[2].p, plane(), plane_len(), kUp)) return rc;
+        return seg_upload_offsets(plane(), wrseg::kHeaderBytes, nseg, bufs->mask[1].p);
+    }
+
+    // (cu_mu held) the mask's decoder and the count of its bits, on the second stream
+    int launch(SegBufs* bufs)
+    {
+        HIPCHK(hipEventRecord(s.ev[4], s.st));
+        wrk::seg_decode(bufs->mask[2].p, plane_len(), wrk::plane_ref(bits), nsym, seg, bufs->mask[1].p, s.st);
+        HIPCHK(hipEventRecord(s.ev[5], s.st));
+        wrk::mask_restore((double*)nullptr, n, bits, 0.0, counters, s.st);
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask decoder launch failed");
+        HIPCHK(hipMemcpyAsync(&h_bad, wrk::seg_work_bad(bufs->mask[1].p), sizeof h_bad, hipMemcpyDeviceToHost, s.st));
+        HIPCHK(hipMemcpyAsync(h_counters, counters, sizeof h_counters, hipMemcpyDeviceToHost, s.st));
+        return WR_OK;
+    }
+
+    // ... waited for and judged: the caller's field has not been touched yet
+    int check()
+    {
+        if (hipStreamSynchronize(s.st) != hipSuccess) return fail(WR_ERR_HIP, "the mask's decoder failed on the device");
+        coder_ms = s.ms(2);
+        if (h_bad) return fail(WR_ERR_STREAM, "mask blob: " + bad_segments_text(h_bad));
+        if (h_counters[1]) return fail(WR_ERR_STREAM, "mask blob: a bit beyond the field's last sample is set");
+        if (h_counters[0] != undefined) return fail(WR_ERR_STREAM, "mask blob: the mask's set bits are not the count in its header");
+        return WR_OK;
+    }
+
+    // (the context's stream, behind the finisher) `fill` where a bit is set
+    template <class T>
+    int restore(T* d_x)
+    {
+        HIPCHK(hipEventRecord(s.ev[2], c->stream));
+        wrk::mask_restore(d_x, n, bits, (T)fill, counters, c->stream);
+        HIPCHK(hipEventRecord(s.ev[3], c->stream));
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask restore launch failed");
+        return WR_OK;
+    }
+
+    void result(wr_mask_result* res)
+    {
+        if (!res) return;
+        memset(res, 0, sizeof *res);
+        res->undefined = undefined; res->pad = pad; res->mask_len = len;
+        res->fill_ms = s.ev[2] ? s.ms(1) : 0; res->mask_coder_ms = coder_ms;
+    }
+};
+
+// wr_dev_mask_split / _f32: the split alone, as a stage call
+template <class T>
+int dev_mask_split(wr_ctx* c, const T* d_fld, size_t n, double below, unsigned char* d_bits, unsigned long long* undefined, double* pad)
+{
+    if (int rc = ctx_bind(c)) return rc;
+    if (!d_fld || !d_bits || !undefined || !pad) return fail(WR_ERR_ARG, "null pointer");
+    if (!n) return fail(WR_ERR_ARG, "empty array");
+    if (below != below) return fail(WR_ERR_ARG, "the threshold `below` is a NaN (-INFINITY switches it off)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    StageLock cu(c->pool->cu_mu);
+    wrk::mask_split(d_fld, n, below, d_bits, c->d_partial, c->h_result_dev, c->stream);
+    if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask split launch failed");
+    HIPCHK(hipStreamSynchronize(c->stream));
+    mask_split_result<T>(c, n, undefined, pad);
+    return WR_OK;
+}
+
+// wr_dev_mask_fill (undefined == nullptr) and wr_dev_mask_restore, and their _f32 forms
+template <class T>
+int dev_mask_apply(wr_ctx* c, T* d_fld, size_t n, const unsigned char* d_bits, double value, unsigned long long* undefined)
+{
+    if (int rc = ctx_bind(c)) return rc;
+    if (!d_fld || !d_bits) return fail(WR_ERR_ARG, "null pointer");
+    if (!n) return fail(WR_ERR_ARG, "empty array");
+    std::lock_guard<std::mutex> lk(c->mu);
+    StageLock cu(c->pool->cu_mu);
+    if (!undefined) {  // wr_dev_mask_fill
+        wrk::mask_fill(d_fld, n, d_bits, (T)value, c->stream);
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask fill launch failed");
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return WR_OK;
+    }
+    unsigned long long* const counters = reinterpret_cast<unsigned long long*>(c->d_partial);
+    unsigned long long got[2] = {0, 0};
+    wrk::mask_restore(d_fld, n, d_bits, (T)value, counters, c->stream);
+    if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask restore launch failed");
+    HIPCHK(hipMemcpyAsync(got, counters, sizeof got, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *undefined = got[0];
+    if (got[1]) return fail(WR_ERR_STREAM, "mask: a bit beyond the field's last sample is set");
+    return WR_OK;
+}
+
 // bud != nullptr: an encode to a byte budget (WRS1): the tolerance comes from the search, cut.vec[0] only names the finest one
 // bnd != nullptr: an encode to an error bound (any of the formats), likewise
+// msk != nullptr: a masked encode: split and fill in front of the prologue, the mask blob behind the planes
 int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, const Cutoff& cut, unsigned seg, unsigned brick, unsigned strands,
-                    wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm, BudgetSearch* bud = nullptr, BoundedSearch* bnd = nullptr)
+                    wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm, BudgetSearch* bud = nullptr, BoundedSearch* bnd = nullptr,
+                    MaskEncode* msk = nullptr)
 {
     if (int rc = seg_format_params(&seg, brick, strands)) return rc;
     if (int rc = ctx_bind(c)) return rc;
@@ -1932,6 +2202,7 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
     double* const d_fld = up.d_fld;
     SegTarget t;  // (a blob buffer per plane, as the planes come)
     if (int rc = seg_target(c, &bufs, n, seg, brick, strands, brick ? wrblk::order_of(nx, ny, nz, wtflag ? kWavLvl : 0, brick) : wrblk::Order{}, &t)) return rc;
+    if (msk) if (int rc = msk->begin(c, &bufs, n, seg)) return rc;
     if (bnd) {  // the trials' work arrays, and the field where the forward transform will not leave it as it is
         for (int k = 0; k < 2; k++) {
             bufs.trial[k] = plane_scratch(c, n * sizeof(double));
@@ -1968,6 +2239,10 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
             return WR_OK;
         };
         clock_warmup(c, n);
+        if (msk) {  // the field where it landed: an fp32 field before anything widens it
+            float* const x32 = up.d_f32 ? const_cast<float*>(up.d_f32) : up.widen_from;
+            if ((rc = fld.host_f32 ? msk->split_fill(&bufs, x32) : msk->split_fill(&bufs, d_fld)) != WR_OK) return rc;
+        }
         if (up.widen_from) wrk::widen_f32(up.widen_from, d_fld, n, c->stream);
         PickStep pick;
         if (bud) {
@@ -1995,8 +2270,11 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
     size_t total = 0;
     if ((rc = seg_coded_lengths(info->nlay, t.blob_cap, [&](int l) { return seg_result_host(c, l); }, info->len_enc_vec, &total)) != WR_OK) return rc;
     if (total > cap || (total && !data_enc)) return fail(WR_ERR_OVERFLOW, wrtc::kTooLarge);
+    if (msk && msk->undefined && (!data_enc || wr_mask_bound(n, seg) > cap - total))
+        return fail(WR_ERR_OVERFLOW, "the coded buffer does not hold the field's planes and the bound of the mask blob (wr_mask_bound)");
     if (bud && total > bud->bound) return fail(WR_ERR_HIP, "internal: the coded planes are longer than their size bound");
     if ((rc = seg_download_blobs(c, bufs, info->nlay, info->len_enc_vec, data_enc, &local)) != WR_OK) return rc;
+    if (msk) if ((rc = msk->finish(bufs, data_enc, total)) != WR_OK) return rc;
     info->ntot_enc = total;
     local.total = now() - t0;
     local.wait = t_phase - t0;
@@ -2272,8 +2550,10 @@ int seg_coder_stage(wr_ctx* c, const CoderCall& k, wr_timings* tm)
 // err_out != nullptr (wr_seg_error_host): fld is the ORIGINAL field on the host and is only read; the reconstruction stays on
 // the device, where it is compared with an upload of the field: *err_out = max |field - reconstruction|
 // stats_out != nullptr (wr_seg_error_stats_host): likewise, the compare being wrk::err_stats and the field's min/max read too
+// msk != nullptr (wr_decode_*_seg_masked): the mask blob of a masked record, judged before the result is written anywhere the
+// caller can see, and applied behind the inverse transform
 int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
-                    wr_timings* tm, double* err_out = nullptr, wr_error_stats* stats_out = nullptr)
+                    wr_timings* tm, double* err_out = nullptr, wr_error_stats* stats_out = nullptr, MaskDecode* msk = nullptr)
 {
     double err_unused = 0;
     if (stats_out && !err_out) err_out = &err_unused;
@@ -2293,6 +2573,31 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
     DevPool* const pool = c->pool;
     SegStream s;
     if (int rc = seg_stream_of(nx, ny, nz, info, data_enc, data_len, &s)) return rc;
+    if (msk) if (int rc = msk->parse(n)) return rc;
+    if (s.constant && msk) {  // midval everywhere, then the mask: a host field takes the bits on the host, as it takes midval there
+        if (int rc = msk->upload(c, &bufs)) return rc;
+        {
+            StageLock cu(pool->cu_mu);
+            if (int rc = msk->launch(&bufs)) return rc;
+            if (int rc = msk->check()) return rc;
+        }
+        if (int rc = fill_constant(c, fld, n, info->midval)) return rc;
+        if (fld.dev) {
+            StageLock cu(pool->cu_mu);
+            if (int rc = kernel_stage_end(c, msk->restore(fld.dev))) return rc;
+        } else {
+            std::vector<unsigned char> bits(msk->nsym);
+            HIPCHK(hipMemcpy(bits.data(), msk->bits, msk->nsym, hipMemcpyDeviceToHost));
+            for (size_t j = 0; j < n; j++) {
+                if (!((bits[j >> 3] >> (j & 7)) & 1)) continue;
+                if (fld.host) fld.host[j] = msk->fill;
+                else fld.host_f32[j] = (float)msk->fill;
+            }
+        }
+        local.total = now() - t0;
+        if (tm) *tm = local;
+        return WR_OK;
+    }
     if (s.constant && err_out) {  // the reconstruction is midval everywhere (fill_constant)
         double mx = 0;
         size_t bad = 0;
@@ -2336,6 +2641,7 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
         }
     }
     if (int rc = seg_upload_planes(c, s, info, data_enc, &bufs, &local.h2d_ms)) return rc;
+    if (msk) if (int rc = msk->upload(c, &bufs)) return rc;
     const double t_coded = now();
     SlotNeed need;
     transform_need(nx, ny, nz, info->wlev ? -kWavLvl : 0, &need);
@@ -2351,11 +2657,15 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
     {
         StageLock cu(pool->cu_mu);
         clock_warmup(c, n);
+        if (msk) if (int rc = msk->launch(&bufs)) return rc;  // (on its own stream, under the field's coder stage)
         CoderCall k{&s, info, s.nlay, n, &bufs, p.q};
         for (int l = 0; l < s.nlay; l++) k.perm[l] = bufs.perm.p;
         if (int rc = seg_coder_stage(c, k, &local)) return rc;
+        if (msk) if (int rc = msk->check()) return rc;
         launch_note(c, "dequant", s.nlay - 1, d_fld, n, nullptr, p.q[s.nlay - 1]);
-        rc = kernel_stage_end(c, inverse_from_planes(c, slot.get(), d_fld, nx, ny, nz, (int)info->wlev, p, fld.host_f32 ? &d_f32 : nullptr));
+        rc = inverse_from_planes(c, slot.get(), d_fld, nx, ny, nz, (int)info->wlev, p, fld.host_f32 ? &d_f32 : nullptr);
+        if (rc == WR_OK && msk) rc = fld.host_f32 ? msk->restore(d_f32) : msk->restore(d_fld);
+        rc = kernel_stage_end(c, rc);
         if (rc == WR_OK && err_out) {
             double bad = 0;
             if (stats_out) {
@@ -3057,6 +3367,98 @@ int wr_decode_device_seg(wr_ctx* c, double* d_fld, int nx, int ny, int nz, const
     FieldRef f; f.dev = d_fld;
     if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
     return decode_seg_impl(c, f, nx, ny, nz, info, data_enc, data_len, tm);
+}
+
+// ---- masked fields: the stage calls and the whole-path calls (MaskEncode / MaskDecode above)
+int wr_dev_mask_split(wr_ctx* c, const double* d_fld, size_t n, double below, unsigned char* d_bits, unsigned long long* undefined, double* pad)
+{
+    return dev_mask_split(c, d_fld, n, below, d_bits, undefined, pad);
+}
+int wr_dev_mask_split_f32(wr_ctx* c, const float* d_fld, size_t n, double below, unsigned char* d_bits, unsigned long long* undefined, double* pad)
+{
+    return dev_mask_split(c, d_fld, n, below, d_bits, undefined, pad);
+}
+int wr_dev_mask_fill(wr_ctx* c, double* d_fld, size_t n, const unsigned char* d_bits, double value) { return dev_mask_apply(c, d_fld, n, d_bits, value, nullptr); }
+int wr_dev_mask_fill_f32(wr_ctx* c, float* d_fld, size_t n, const unsigned char* d_bits, double value) { return dev_mask_apply(c, d_fld, n, d_bits, value, nullptr); }
+int wr_dev_mask_restore(wr_ctx* c, double* d_fld, size_t n, const unsigned char* d_bits, double fill, unsigned long long* undefined)
+{
+    if (!undefined) return fail(WR_ERR_ARG, "null pointer");
+    return dev_mask_apply(c, d_fld, n, d_bits, fill, undefined);
+}
+int wr_dev_mask_restore_f32(wr_ctx* c, float* d_fld, size_t n, const unsigned char* d_bits, double fill, unsigned long long* undefined)
+{
+    if (!undefined) return fail(WR_ERR_ARG, "null pointer");
+    return dev_mask_apply(c, d_fld, n, d_bits, fill, undefined);
+}
+
+static int encode_seg_masked(wr_ctx* c, FieldRef f, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec, unsigned seg,
+                             unsigned brick, unsigned strands, double below, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm,
+                             wr_mask_result* res)
+{
+    if (below != below) return fail(WR_ERR_ARG, "the threshold `below` is a NaN (-INFINITY switches it off)");
+    Cutoff cut; cut.mx = mx; cut.my = my; cut.mz = mz; cut.vec = cutoffvec;
+    MaskEncode m;
+    m.below = below;
+    const int rc = encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick, strands, info, data_enc, cap, tm, nullptr, nullptr, &m);
+    if (rc == WR_OK) m.result(res);
+    return rc;
+}
+
+static int decode_seg_masked(wr_ctx* c, FieldRef f, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
+                             double fill, wr_timings* tm, wr_mask_result* res)
+{
+    if (!info) return fail(WR_ERR_ARG, "null wr_enc_info");
+    if (res) memset(res, 0, sizeof *res);
+    if (data_len == 0 || data_len <= info->ntot_enc)  // an unmasked record (a shorter buffer: the plain call refuses it)
+        return decode_seg_impl(c, f, nx, ny, nz, info, data_enc, data_len, tm);
+    if (!data_enc) return fail(WR_ERR_ARG, "null coded buffer");
+    MaskDecode m;
+    m.blob = data_enc + info->ntot_enc; m.len = data_len - info->ntot_enc; m.fill = fill;
+    const int rc = decode_seg_impl(c, f, nx, ny, nz, info, data_enc, info->ntot_enc, tm, nullptr, nullptr, &m);
+    if (rc == WR_OK) m.result(res);
+    return rc;
+}
+
+int wr_encode_host_seg_masked(wr_ctx* c, const double* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,
+                              unsigned seg, unsigned brick, unsigned strands, double below, wr_enc_info* info, unsigned char* data_enc, size_t cap,
+                              wr_timings* tm, wr_mask_result* res)
+{
+    FieldRef f; f.host = const_cast<double*>(h_fld);  // (written only with wr_ctx_set_keep_residual(ctx, 1), as wr_encode_host)
+    return encode_seg_masked(c, f, nx, ny, nz, wtflag, mx, my, mz, cutoffvec, seg, brick, strands, below, info, data_enc, cap, tm, res);
+}
+int wr_encode_host_seg_masked_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,
+                                  unsigned seg, unsigned brick, unsigned strands, double below, wr_enc_info* info, unsigned char* data_enc, size_t cap,
+                                  wr_timings* tm, wr_mask_result* res)
+{
+    FieldRef f; f.host_f32 = const_cast<float*>(h_fld);
+    return encode_seg_masked(c, f, nx, ny, nz, wtflag, mx, my, mz, cutoffvec, seg, brick, strands, below, info, data_enc, cap, tm, res);
+}
+int wr_encode_device_seg_masked(wr_ctx* c, double* d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,
+                                unsigned seg, unsigned brick, unsigned strands, double below, wr_enc_info* info, unsigned char* data_enc, size_t cap,
+                                wr_timings* tm, wr_mask_result* res)
+{
+    FieldRef f; f.dev = d_fld;
+    if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
+    return encode_seg_masked(c, f, nx, ny, nz, wtflag, mx, my, mz, cutoffvec, seg, brick, strands, below, info, data_enc, cap, tm, res);
+}
+int wr_decode_host_seg_masked(wr_ctx* c, double* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
+                              double fill, wr_timings* tm, wr_mask_result* res)
+{
+    FieldRef f; f.host = h_fld;
+    return decode_seg_masked(c, f, nx, ny, nz, info, data_enc, data_len, fill, tm, res);
+}
+int wr_decode_host_seg_masked_f32(wr_ctx* c, float* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc,
+                                  size_t data_len, double fill, wr_timings* tm, wr_mask_result* res)
+{
+    FieldRef f; f.host_f32 = h_fld;
+    return decode_seg_masked(c, f, nx, ny, nz, info, data_enc, data_len, fill, tm, res);
+}
+int wr_decode_device_seg_masked(wr_ctx* c, double* d_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
+                                double fill, wr_timings* tm, wr_mask_result* res)
+{
+    FieldRef f; f.dev = d_fld;
+    if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
+    return decode_seg_masked(c, f, nx, ny, nz, info, data_enc, data_len, fill, tm, res);
 }
 
 int wr_encode_host_seg_blocked(wr_ctx* c, const double* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,

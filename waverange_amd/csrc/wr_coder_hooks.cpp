@@ -5,6 +5,7 @@
 #include "wr_budget.h"
 #include "wr_internal.h"
 #include "wr_lowres.h"
+#include "wr_mask.h"
 #include "wr_roi.h"
 #include "wr_segcoder.h"
 #include "wr_transcode.h"
@@ -203,6 +204,50 @@ int wr_seg_decode_host_ref(const unsigned char* blob, size_t len, unsigned char*
     uint32_t seg = 0, nseg = 0;
     if (const char* why = wrseg::check_index(blob, len, len, n, &seg, &nseg)) return fail(WR_ERR_STREAM, why);
     return seg_decode_ref(blob, len, sym, n, seg, nseg, 0);
+}
+
+// ---- the mask blob of a masked record ("WRM1", wr_mask.h) on the calling thread: the definition of the format
+size_t wr_mask_bound(size_t n, unsigned seg)
+{
+    const size_t b = wr_seg_bound(wrmask::mask_bytes(n), seg);
+    return b ? wrmask::kHeaderBytes + b : 0;
+}
+
+int wr_mask_sniff(const unsigned char* data, size_t len) { return wrmask::sniff(data, len) ? 1 : 0; }
+
+size_t wr_mask_blob_host_ref(const unsigned char* undef_flags, size_t n, unsigned seg, double pad, unsigned char* blob)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
+    if (!blob || !undef_flags || !n) { fail(WR_ERR_ARG, n ? "null pointer" : "empty field"); return 0; }
+    std::vector<unsigned char> bits(wrmask::mask_bytes(n), 0);
+    unsigned long long undefined = 0;
+    for (size_t j = 0; j < n; j++)
+        if (undef_flags[j]) { bits[j >> 3] |= (unsigned char)(1u << (j & 7)); undefined++; }
+    wrmask::put_header(blob, n, undefined, pad);
+    const size_t len = seg_encode_ref(bits.data(), bits.size(), seg, 0, blob + wrmask::kHeaderBytes);
+    return len ? wrmask::kHeaderBytes + len : 0;
+}
+
+int wr_mask_parse_host_ref(const unsigned char* blob, size_t len, size_t n, unsigned char* undef_flags, unsigned long long* undefined, double* pad)
+{
+    if (!blob || !n) return fail(WR_ERR_ARG, n ? "null pointer" : "empty field");
+    unsigned long long count = 0;
+    double p = 0;
+    if (const char* why = wrmask::check_header(blob, len, n, &count, &p)) return fail(WR_ERR_STREAM, why);
+    const size_t nsym = wrmask::mask_bytes(n), rest = len - wrmask::kHeaderBytes;
+    uint32_t seg = 0, nseg = 0;
+    if (const char* why = wrseg::check_index(blob + wrmask::kHeaderBytes, rest, rest, nsym, &seg, &nseg)) return fail(WR_ERR_STREAM, std::string("mask blob: ") + why);
+    std::vector<unsigned char> bits(nsym);
+    if (int rc = seg_decode_ref(blob + wrmask::kHeaderBytes, rest, bits.data(), nsym, seg, nseg, 0)) return rc;
+    if ((n & 7) && (bits[nsym - 1] >> (n & 7))) return fail(WR_ERR_STREAM, "mask blob: a bit beyond the field's last sample is set");
+    unsigned long long pop = 0;
+    for (size_t k = 0; k < nsym; k++) pop += (unsigned long long)__builtin_popcount(bits[k]);
+    if (pop != count) return fail(WR_ERR_STREAM, "mask blob: the mask's set bits are not the count in its header");
+    if (undef_flags) for (size_t j = 0; j < n; j++) undef_flags[j] = (bits[j >> 3] >> (j & 7)) & 1;
+    if (undefined) *undefined = count;
+    if (pad) *pad = p;
+    return WR_OK;
 }
 
 // ---- the blocked symbol order (wr_blocked.h) and the WRS2 container on the calling thread

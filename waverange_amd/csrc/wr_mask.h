@@ -1,0 +1,82 @@
+// Masked fields: the kernels that split a field into its defined samples and a packed bit mask, and put values back where
+// the mask says so (wr_mask.hip), and the mask blob "WRM1" (include/waverange_amd.h), whose host side is plain code here.
+//
+// A sample x is UNDEFINED if it is not finite, !(fabs(x) <= DBL_MAX), or if x < below (below = -inf: no threshold).  Sample j's
+// bit is bit j & 7 (least significant first) of mask byte j >> 3; a mask of n samples has ceil(n / 8) bytes, the unused high
+// bits of the last one 0.
+#ifndef WR_MASK_H
+#define WR_MASK_H
+
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <hip/hip_runtime.h>
+
+namespace wrmask {
+
+constexpr size_t kHeaderBytes = 32;  // 'W','R','M','1' | u32 0 | u64 n | u64 undefined | f64 pad
+constexpr unsigned char kMagic[4] = {'W', 'R', 'M', '1'};
+
+inline size_t mask_bytes(size_t n) { return (n + 7) >> 3; }
+
+inline void put_u64(unsigned char* p, unsigned long long v) { for (int k = 0; k < 8; k++) p[k] = (unsigned char)(v >> (8 * k)); }
+inline unsigned long long get_u64(const unsigned char* p)
+{
+    unsigned long long v = 0;
+    for (int k = 0; k < 8; k++) v |= (unsigned long long)p[k] << (8 * k);
+    return v;
+}
+
+inline void put_header(unsigned char* p, unsigned long long n, unsigned long long undefined, double pad)
+{
+    memcpy(p, kMagic, 4);
+    memset(p + 4, 0, 4);
+    put_u64(p + 8, n);
+    put_u64(p + 16, undefined);
+    unsigned long long bits;
+    memcpy(&bits, &pad, 8);
+    put_u64(p + 24, bits);
+}
+
+inline bool sniff(const unsigned char* p, size_t len) { return p && len >= kHeaderBytes && memcmp(p, kMagic, 4) == 0; }
+
+// What the header of a blob of `len` bytes says, for a field of n samples; nullptr, or why the blob is refused.  The WRS1 blob
+// behind the header is the caller's to check (wrseg::check_index).
+inline const char* check_header(const unsigned char* p, size_t len, size_t n, unsigned long long* undefined, double* pad)
+{
+    if (len < kHeaderBytes) return "mask blob: truncated header";
+    if (memcmp(p, kMagic, 4) != 0) return "mask blob: wrong magic";
+    if (p[4] | p[5] | p[6] | p[7]) return "mask blob: the reserved word is not 0";
+    if (get_u64(p + 8) != (unsigned long long)n) return "mask blob: its sample count is not the field's";
+    *undefined = get_u64(p + 16);
+    if (*undefined > (unsigned long long)n) return "mask blob: more undefined samples than samples";
+    const unsigned long long bits = get_u64(p + 24);
+    memcpy(pad, &bits, 8);
+    return nullptr;
+}
+
+}  // namespace wrmask
+
+namespace wrk {
+
+// ---- k_mask_split: one read of the field.  bits[0, ceil(n / 8)) = the mask; result[0] = S, the fp64 sum of the defined samples
+// (widened exactly for an fp32 field), result[1] = their count as an unsigned 64-bit integer (same 8 bytes).  The order of the
+// sum is fixed by n alone: a thread adds its samples in index order, lanes combine by shuffles at distances 32 .. 1, thread 0
+// adds the waves in wave order, the final block's thread t adds partials t, t + 256, .. and reduces the same way; no
+// floating-point atomics.  partial: 2 * mask_partials() 8-byte words.  `bits` may have any alignment (8-byte aligned: a wave
+// stores the 8 mask bytes of its 64 samples as one word).
+int mask_partials();
+void mask_split(const double* x, size_t n, double below, uint8_t* bits, double* partial, double* result, hipStream_t st);
+void mask_split(const float* x, size_t n, double below, uint8_t* bits, double* partial, double* result, hipStream_t st);
+// ---- k_mask_fill: x[j] = v where bit j is set; a wave whose 8 mask bytes are 0 stores nothing.
+void mask_fill(double* x, size_t n, const uint8_t* bits, double v, hipStream_t st);
+void mask_fill(float* x, size_t n, const uint8_t* bits, float v, hipStream_t st);
+// ---- k_mask_restore: the same walk with the mask checked: counters[0] += the set bits of the mask's ceil(n / 8) bytes,
+// counters[1] |= 1 if one of them lies at or beyond n (integer atomics, one per wave; zeroed here).  x == nullptr: only counted.
+void mask_restore(double* x, size_t n, const uint8_t* bits, double v, unsigned long long* counters, hipStream_t st);
+void mask_restore(float* x, size_t n, const uint8_t* bits, float v, unsigned long long* counters, hipStream_t st);
+
+}  // namespace wrk
+
+#endif

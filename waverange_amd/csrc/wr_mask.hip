@@ -1,0 +1,177 @@
+// Masked fields on the device (wr_mask.h): split a field into a packed bit mask and the sum and count of its defined samples,
+// fill the undefined ones, and put a value back where a decoded mask says so.  gfx950, wave64.
+//
+// All three kernels walk the field the same way: a wave takes 64 consecutive samples per turn (chunk `ch`: samples 64 ch ..
+// 64 ch + 63, mask bytes 8 ch .. 8 ch + 7), lane l sample 64 ch + l, so a wave's loads are one coalesced line and __ballot of
+// the undefined predicate IS the chunk's 8 mask bytes.  Chunks go round the grid's waves: wave w takes ch = w, w + W, ...
+#include "wr_mask.h"
+
+#include <float.h>
+
+namespace wrk {
+
+#define WR_MASK_BLOCKS 2048
+#define WR_MASK_THREADS 256
+#define WR_MASK_WAVES (WR_MASK_THREADS / 64)
+
+int mask_partials() { return WR_MASK_BLOCKS; }
+
+static int mask_grid(size_t n)
+{
+    const size_t nchunk = (n + 63) >> 6;
+    size_t g = (nchunk + WR_MASK_WAVES - 1) / WR_MASK_WAVES;
+    if (g < 1) g = 1;
+    if (g > WR_MASK_BLOCKS) g = WR_MASK_BLOCKS;
+    return (int)g;
+}
+
+// the block's sum and count into out[0], out[1]: shuffles 32 .. 1, then thread 0 adds the waves in order (block_max_sum_sum's scheme)
+__device__ inline void block_sum_count(double s, unsigned long long cnt, double* __restrict__ out)
+{
+    for (int o = 32; o > 0; o >>= 1) {
+        s = s + __shfl_down(s, o, 64);
+        cnt += __shfl_down(cnt, o, 64);
+    }
+    __shared__ double ssum[WR_MASK_WAVES];
+    __shared__ unsigned long long scnt[WR_MASK_WAVES];
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { ssum[w] = s; scnt[w] = cnt; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < WR_MASK_WAVES; i++) { s = s + ssum[i]; cnt += scnt[i]; }
+        out[0] = s;
+        reinterpret_cast<unsigned long long*>(out)[1] = cnt;
+    }
+}
+
+// the 8 mask bytes of chunk ch as one word: bytes at and beyond nbytes read as 0
+__device__ inline unsigned long long mask_word(const uint8_t* __restrict__ bits, size_t nbytes, size_t ch, bool wide)
+{
+    const size_t b0 = ch << 3;
+    if (wide && b0 + 8 <= nbytes) return *reinterpret_cast<const unsigned long long*>(bits + b0);
+    unsigned long long m = 0;
+    for (int k = 0; k < 8; k++)
+        if (b0 + k < nbytes) m |= (unsigned long long)bits[b0 + k] << (8 * k);
+    return m;
+}
+
+// WIDE: `bits` is 8-byte aligned
+template <typename T, bool WIDE>
+__global__ __launch_bounds__(WR_MASK_THREADS) void k_mask_split(const T* __restrict__ x, size_t n, double below, uint8_t* __restrict__ bits,
+                                                                  double* __restrict__ partial)
+{
+    double s = 0.0;
+    unsigned long long cnt = 0;
+    const int lane = threadIdx.x & 63;
+    const size_t wave = (size_t)blockIdx.x * WR_MASK_WAVES + (threadIdx.x >> 6), nwaves = (size_t)gridDim.x * WR_MASK_WAVES;
+    const size_t nchunk = (n + 63) >> 6, nbytes = (n + 7) >> 3;
+    // kTurns turns at a time: their loads are issued together (a load per lane and turn is too little in flight to fill the
+    // memory pipe), the samples then go into the sum in turn order, as they would one turn at a time
+    constexpr int kTurns = 4;
+    for (size_t ch0 = wave; ch0 < nchunk; ch0 += kTurns * nwaves) {
+        T v[kTurns];
+        bool have[kTurns];
+#pragma unroll
+        for (int u = 0; u < kTurns; u++) {
+            const size_t ch = ch0 + u * nwaves, i = (ch << 6) + lane;
+            have[u] = ch < nchunk && i < n;
+            v[u] = have[u] ? x[i] : (T)0;
+        }
+#pragma unroll
+        for (int u = 0; u < kTurns; u++) {
+            const size_t ch = ch0 + u * nwaves;
+            if (ch >= nchunk) break;  // (the whole wave)
+            const double w = (double)v[u];
+            const bool undef = have[u] && (!(fabs(w) <= DBL_MAX) || w < below);
+            if (have[u] && !undef) { s = s + w; cnt++; }
+            const unsigned long long m = __ballot(undef);
+            if (lane == 0) {
+                const size_t b0 = ch << 3;
+                if (WIDE && b0 + 8 <= nbytes) *reinterpret_cast<unsigned long long*>(bits + b0) = m;
+                else
+                    for (int k = 0; k < 8; k++)
+                        if (b0 + k < nbytes) bits[b0 + k] = (uint8_t)(m >> (8 * k));
+            }
+        }
+    }
+    block_sum_count(s, cnt, partial + 2 * blockIdx.x);
+}
+
+__global__ __launch_bounds__(WR_MASK_THREADS) void k_mask_split_final(const double* __restrict__ partial, int np, double* __restrict__ result)
+{
+    double s = 0.0;
+    unsigned long long cnt = 0;
+    for (int i = threadIdx.x; i < np; i += blockDim.x) {
+        s = s + partial[2 * i];
+        cnt += reinterpret_cast<const unsigned long long*>(partial)[2 * i + 1];
+    }
+    block_sum_count(s, cnt, result);  // single block: lands in result[0], result[1]
+}
+
+template <typename T>
+static void mask_split_t(const T* x, size_t n, double below, uint8_t* bits, double* partial, double* result, hipStream_t st)
+{
+    const int g = mask_grid(n);
+    if (((uintptr_t)bits & 7) == 0) hipLaunchKernelGGL((k_mask_split<T, true>), dim3(g), dim3(WR_MASK_THREADS), 0, st, x, n, below, bits, partial);
+    else hipLaunchKernelGGL((k_mask_split<T, false>), dim3(g), dim3(WR_MASK_THREADS), 0, st, x, n, below, bits, partial);
+    hipLaunchKernelGGL(k_mask_split_final, dim3(1), dim3(WR_MASK_THREADS), 0, st, partial, g, result);
+}
+void mask_split(const double* x, size_t n, double below, uint8_t* bits, double* partial, double* result, hipStream_t st) { mask_split_t(x, n, below, bits, partial, result, st); }
+void mask_split(const float* x, size_t n, double below, uint8_t* bits, double* partial, double* result, hipStream_t st) { mask_split_t(x, n, below, bits, partial, result, st); }
+
+template <typename T>
+__global__ __launch_bounds__(WR_MASK_THREADS) void k_mask_fill(T* __restrict__ x, size_t n, const uint8_t* __restrict__ bits, bool wide, T v)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t wave = (size_t)blockIdx.x * WR_MASK_WAVES + (threadIdx.x >> 6), nwaves = (size_t)gridDim.x * WR_MASK_WAVES;
+    const size_t nchunk = (n + 63) >> 6, nbytes = (n + 7) >> 3;
+    for (size_t ch = wave; ch < nchunk; ch += nwaves) {
+        const unsigned long long m = mask_word(bits, nbytes, ch, wide);
+        if (!m) continue;  // (the whole wave: m is the same in every lane)
+        const size_t i = (ch << 6) + lane;
+        if (i < n && ((m >> lane) & 1)) x[i] = v;
+    }
+}
+
+template <typename T>
+static void mask_fill_t(T* x, size_t n, const uint8_t* bits, T v, hipStream_t st)
+{
+    hipLaunchKernelGGL((k_mask_fill<T>), dim3(mask_grid(n)), dim3(WR_MASK_THREADS), 0, st, x, n, bits, ((uintptr_t)bits & 7) == 0, v);
+}
+void mask_fill(double* x, size_t n, const uint8_t* bits, double v, hipStream_t st) { mask_fill_t(x, n, bits, v, st); }
+void mask_fill(float* x, size_t n, const uint8_t* bits, float v, hipStream_t st) { mask_fill_t(x, n, bits, v, st); }
+
+template <typename T>
+__global__ __launch_bounds__(WR_MASK_THREADS) void k_mask_restore(T* __restrict__ x, size_t n, const uint8_t* __restrict__ bits, bool wide, T v,
+                                                                    unsigned long long* __restrict__ counters)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t wave = (size_t)blockIdx.x * WR_MASK_WAVES + (threadIdx.x >> 6), nwaves = (size_t)gridDim.x * WR_MASK_WAVES;
+    const size_t nchunk = (n + 63) >> 6, nbytes = (n + 7) >> 3;
+    unsigned long long pop = 0, beyond = 0;  // (of the wave: every lane holds the same values)
+    for (size_t ch = wave; ch < nchunk; ch += nwaves) {
+        const unsigned long long m = mask_word(bits, nbytes, ch, wide);
+        if (!m) continue;
+        const size_t left = n - (ch << 6);
+        const unsigned long long valid = left >= 64 ? ~0ull : (1ull << left) - 1;
+        pop += (unsigned long long)__popcll(m);
+        beyond |= m & ~valid;
+        const size_t i = (ch << 6) + lane;
+        if (x && i < n && ((m >> lane) & 1)) x[i] = v;
+    }
+    if (lane == 0) {
+        if (pop) atomicAdd(&counters[0], pop);
+        if (beyond) atomicOr(&counters[1], 1ull);
+    }
+}
+
+template <typename T>
+static void mask_restore_t(T* x, size_t n, const uint8_t* bits, T v, unsigned long long* counters, hipStream_t st)
+{
+    (void)hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), st);
+    hipLaunchKernelGGL((k_mask_restore<T>), dim3(mask_grid(n)), dim3(WR_MASK_THREADS), 0, st, x, n, bits, ((uintptr_t)bits & 7) == 0, v, counters);
+}
+void mask_restore(double* x, size_t n, const uint8_t* bits, double v, unsigned long long* counters, hipStream_t st) { mask_restore_t(x, n, bits, v, counters, st); }
+void mask_restore(float* x, size_t n, const uint8_t* bits, float v, unsigned long long* counters, hipStream_t st) { mask_restore_t(x, n, bits, v, counters, st); }
+
+}  // namespace wrk
