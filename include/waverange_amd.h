@@ -209,6 +209,8 @@ int wr_set_device_slots(int device, int nslots);
                                           per wr_decode_*_seg_batch_mixed while neither kind of job exceeds WR_SEG_BATCH_MAX */
 #define WR_STAT_QUALITY_CODER_RUNS 19 /* planes the encodes to an RMS / PSNR target (wr_encode_*_seg_quality, any norm) have handed to
                                         the segment coder: info->nlay per call */
+#define WR_STAT_MASK_ROI_SEGMENTS 20 /* mask-plane segments the masked region / low-resolution decodes (wr_decode_*_seg_roi_masked) have launched */
+#define WR_STAT_MASK_ROI_BYTES_UP 21 /* coded bytes of the mask plane those calls have copied to the device (the offsets tables are not counted) */
 unsigned long wr_stat(int what);
 /* Hands the idle buffers of the device's plane pool back to the device (the pool keeps the plane memory of finished calls for
  * the next ones: after a burst of concurrent calls that can be most of the HBM).  Buffers in use are not touched. */
@@ -578,7 +580,8 @@ int wr_dev_err_stats_f32(wr_ctx *ctx, const float *d_a, const float *d_b, size_t
  * constant padded field (nlay == 0, ntot_enc == 0): the trivial record, and the mask blob at data_enc.  cap must hold the
  * field's planes plus wr_mask_bound(n, seg) bytes when a sample is undefined: WR_ERR_OVERFLOW otherwise, before data_enc is
  * written.  Every existing decoder, region decode, low-resolution decode and wr_transcode_host reads the field part as it is,
- * and returns the padded field.
+ * and returns the padded field; wr_decode_*_seg_roi_masked (further down) are the region and low-resolution decodes that
+ * put `fill` back.
  * The mask blob ("WRM1", little endian):
  *   'W','R','M','1' | u32 0 | u64 n | u64 undefined | f64 pad | WRS1 plane blob of ceil(n / 8) symbols
  * Bit j & 7 (least significant first) of symbol j >> 3 is 1 iff sample j, in the field's memory order, is undefined; the unused
@@ -741,6 +744,51 @@ int wr_decode_host_seg_roi_f32(wr_ctx *ctx, float *h_out, int nx, int ny, int nz
 int wr_decode_device_seg_roi(wr_ctx *ctx, double *d_out, int nx, int ny, int nz, int level, int max_planes,
                              const wr_box *roi, const wr_enc_info *info, const unsigned char *data_enc, size_t data_len,
                              wr_timings *tm);
+/* ---- Masked region and low-resolution decode: the two partial decodes above with the mask of a masked record cropped on the
+ * GPU.  No new format: the record is what wr_encode_*_seg_masked wrote (field part WRS1, WRS2 or WRS3; the mask blob behind
+ * it, always a WRS1 plane in natural order).  b = h^r(n) per axis, r in 0 .. wlev; roi is a half-open box in the coordinates
+ * of the level-r box, roi == NULL means the whole box of the level (the low-resolution decode); p = max_planes.
+ * R(r, p, roi) is what wr_decode_host_seg_roi returns for the field part (wr_decode_host_seg_lowres for roi == NULL).
+ * The coarse mask.  Sample (i, j, k) of the level-r box is undefined iff sample (i << r, j << r, k << r) of the field is: mask
+ * bit J = (i << r) + nx * ((j << r) + ny * (k << r)), formed in size_t.  i << r <= n_axis - 1 always holds (i < ceil(n / 2^r));
+ * it is the position the level-r low-pass sample sits at, since lifting keeps the even samples.  No bit at or beyond n is ever
+ * read.  At r = 0 this is the mask itself.
+ * The masked result.  M(r, p, roi, fill)[x, y, z] = fill where coarse sample (x0 + x, y0 + y, z0 + z) is undefined, and
+ * R(r, p, roi)[x, y, z] otherwise; (float)fill for fp32 output; a NaN fill is allowed.  So
+ *   M(0, nlay, roi, fill) is bit for bit the crop of what wr_decode_host_seg_masked returns with the same fill;
+ *   M(r, ...) is where(und[::2^r, ::2^r, ::2^r][roi], fill, R(r, ...));
+ *   a record without a blob (data_len == info->ntot_enc, or 0) decodes as the plain call, and res is zeroed;
+ *   a constant padded field (nlay == 0, the blob at data_enc) gives midval with fill restored.
+ * Mask segments.  For a run (y, z) of the region the bits J(x0, y, z) .. J(x1 - 1, y, z) lie in symbols J >> 3, a symbol in
+ * segment (J >> 3) / seg, seg being read from the blob's own WRS1 header, not from the field part.  The ascending union over
+ * the region's runs (wr_mask_roi_segments) is all that is uploaded and decoded of the mask.
+ * Refusals.  Every argument the plain region / low-resolution call refuses: WR_ERR_ARG.  The blob's header and its whole
+ * segment index are validated on the host as by the full masked decode: a wrong magic, a nonzero reserved word, another n, a
+ * truncated or overlong blob: WR_ERR_STREAM, nothing launched.  A LISTED mask segment that does not decode: WR_ERR_STREAM
+ * before a byte of the caller's output is written.  Two checks of the full decode are NOT made by a partial decode: the
+ * population count against the header's `undefined`, and the unused high bits of the last symbol.  Damage inside a segment the
+ * region does not list does not fail the call: that segment is not decoded.
+ * res: undefined = the number of undefined samples INSIDE THE RETURNED BOX, counted by the restore kernel; pad and mask_len as
+ * in the full decode; fill_ms the box restore, mask_coder_ms the mask's list-decoder launch, split_ms 0.
+ * WR_STAT_MASK_ROI_SEGMENTS moves by the listed mask segments, WR_STAT_MASK_ROI_BYTES_UP by their stream bytes.
+ * wr_mask_roi_segments: host only, no device and no context; conventions of wr_seg_roi_segments (seg == 0: WR_SEG_DEFAULT).
+ * wr_dev_mask_restore_box: stage level, device pointers of any alignment: d_out is the contiguous region, x fastest; d_bits
+ * the full-length mask plane of ceil(n / 8) bytes, of which only the bytes that hold a bit of the region are read;
+ * *undefined = the set bits among the region's. */
+size_t wr_mask_roi_segments(int nx, int ny, int nz, int level, const wr_box *roi, unsigned seg, uint32_t *ids, size_t cap);
+int wr_dev_mask_restore_box(wr_ctx *ctx, double *d_out, int nx, int ny, int nz, int level, const wr_box *roi,
+                            const unsigned char *d_bits, double fill, unsigned long long *undefined);
+int wr_dev_mask_restore_box_f32(wr_ctx *ctx, float *d_out, int nx, int ny, int nz, int level, const wr_box *roi,
+                                const unsigned char *d_bits, double fill, unsigned long long *undefined);
+int wr_decode_host_seg_roi_masked(wr_ctx *ctx, double *h_out, int nx, int ny, int nz, int level, int max_planes,
+                                  const wr_box *roi, const wr_enc_info *info, const unsigned char *data_enc, size_t data_len,
+                                  double fill, wr_timings *tm, wr_mask_result *res);
+int wr_decode_host_seg_roi_masked_f32(wr_ctx *ctx, float *h_out, int nx, int ny, int nz, int level, int max_planes,
+                                      const wr_box *roi, const wr_enc_info *info, const unsigned char *data_enc,
+                                      size_t data_len, double fill, wr_timings *tm, wr_mask_result *res);
+int wr_decode_device_seg_roi_masked(wr_ctx *ctx, double *d_out, int nx, int ny, int nz, int level, int max_planes,
+                                    const wr_box *roi, const wr_enc_info *info, const unsigned char *data_enc,
+                                    size_t data_len, double fill, wr_timings *tm, wr_mask_result *res);
 /* host reference of the WRS1 format (its definition further up, on the calling thread): for tests and for readers without a GPU.
  * blob holds wr_seg_bound(n, seg) bytes; returns the blob's length (0: seg refused, wr_last_error says why). */
 size_t wr_seg_encode_host_ref(const unsigned char *sym, size_t n, unsigned seg, unsigned char *blob);

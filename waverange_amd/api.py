@@ -284,6 +284,15 @@ def lib():
                                             C.POINTER(Timings), C.POINTER(MaskResult)]
     L.wr_decode_host_seg_masked_f32.argtypes = L.wr_decode_host_seg_masked.argtypes
     L.wr_decode_device_seg_masked.argtypes = L.wr_decode_host_seg_masked.argtypes
+    # masked region and low-resolution decode (a NULL region: the whole box of the level)
+    L.wr_mask_roi_segments.restype = C.c_size_t
+    L.wr_mask_roi_segments.argtypes = [C.c_int] * 4 + [C.POINTER(Box), C.c_uint, _vp, C.c_size_t]
+    L.wr_dev_mask_restore_box.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Box), _vp, C.c_double, C.POINTER(C.c_ulonglong)]
+    L.wr_dev_mask_restore_box_f32.argtypes = L.wr_dev_mask_restore_box.argtypes
+    L.wr_decode_host_seg_roi_masked.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Box), C.POINTER(EncInfo), _vp, C.c_size_t,
+                                                C.c_double, C.POINTER(Timings), C.POINTER(MaskResult)]
+    L.wr_decode_host_seg_roi_masked_f32.argtypes = L.wr_decode_host_seg_roi_masked.argtypes
+    L.wr_decode_device_seg_roi_masked.argtypes = L.wr_decode_host_seg_roi_masked.argtypes
     L.wr_encode_device_seg.argtypes = L.wr_encode_host_seg.argtypes
     L.wr_decode_host_seg.argtypes = L.wr_decode_host.argtypes
     L.wr_decode_host_seg_f32.argtypes = L.wr_decode_host.argtypes
@@ -438,6 +447,7 @@ STAT_ROI_CODER_LAUNCHES = 15
 STAT_BUDGET_CODER_RUNS = 16
 STAT_BOUNDED_CODER_RUNS = 17
 STAT_QUALITY_CODER_RUNS = 19
+STAT_MASK_ROI_SEGMENTS, STAT_MASK_ROI_BYTES_UP = 20, 21
 
 
 def stat(what):
@@ -928,6 +938,20 @@ def seg_roi_segments(shape, level, roi, seg=0, wlev=4):
     ids = np.empty(count, dtype=np.uint32)
     got = lib().wr_seg_roi_segments(nx, ny, nz, level, wlev, C.byref(r), seg, ids.ctypes.data, ids.size)
     assert got == count
+    return ids
+
+
+def mask_roi_segments(shape, level, roi, seg=0):
+    """Ascending ids (uint32) of the segments of the MASK plane of a masked record, cut at `seg` symbols of 8 mask bits, that
+    hold a bit of the region `roi` of the box of `level` (roi = None: the whole box); host only (wr_mask_roi_segments).  An
+    empty array for a refused argument."""
+    nz, ny, nx = shape
+    r = C.byref(_box(roi)) if roi is not None else None
+    count = lib().wr_mask_roi_segments(nx, ny, nz, level, r, seg, None, 0)
+    ids = np.empty(count, dtype=np.uint32)
+    if count:
+        got = lib().wr_mask_roi_segments(nx, ny, nz, level, r, seg, ids.ctypes.data, ids.size)
+        assert got == count
     return ids
 
 
@@ -1526,6 +1550,47 @@ class Context:
     def decode_seg_masked(self, buf, shape, enc, fill=np.nan):
         """decode_host_seg_masked into a field resident on the device."""
         return self._decode_seg_masked(lib().wr_decode_device_seg_masked, buf.ptr, shape, enc, fill)
+
+    # ---- masked region / low-resolution decode: roi = ((z0, z1), (y0, y1), (x0, x1)) in the box of `level`, None: the whole box
+    def _decode_seg_roi_masked(self, fn, ptr, shape, level, roi, enc, fill, max_planes):
+        nz, ny, nx = shape
+        info = EncInfo.from_dict(enc)
+        tm, res = Timings(), MaskResult()
+        r = C.byref(_box(roi)) if roi is not None else None
+        data = np.ascontiguousarray(enc["data"], dtype=np.uint8)
+        src = data if data.size else np.zeros(1, dtype=np.uint8)
+        _check(fn(self.h, ptr, nx, ny, nz, level, max_planes, r, C.byref(info), src.ctypes.data, data.size, float(fill), C.byref(tm), C.byref(res)))
+        return res.as_dict(), tm.as_dict()
+
+    def decode_host_seg_roi_masked(self, out, shape, level, roi, enc, fill=np.nan, max_planes=0):
+        """decode_host_seg_roi (roi = None: decode_host_seg_lowres) of a masked record, `fill` where the coarse mask says
+        undefined; only the mask segments of the region are decoded.  mask["undefined"] counts inside the returned box.
+        Returns (mask, timings) (wr_decode_host_seg_roi_masked)."""
+        assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"]
+        assert tuple(out.shape) == (roi_shape(roi) if roi is not None else lowres_shape(shape, level))
+        return self._decode_seg_roi_masked(lib().wr_decode_host_seg_roi_masked, out.ctypes.data, shape, level, roi, enc, fill, max_planes)
+
+    def decode_host_seg_roi_masked_f32(self, out, shape, level, roi, enc, fill=np.nan, max_planes=0):
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"]):
+            raise TypeError("decode_host_seg_roi_masked_f32: a C-contiguous float32 array is required")
+        assert tuple(out.shape) == (roi_shape(roi) if roi is not None else lowres_shape(shape, level))
+        return self._decode_seg_roi_masked(lib().wr_decode_host_seg_roi_masked_f32, out.ctypes.data, shape, level, roi, enc, fill, max_planes)
+
+    def decode_seg_roi_masked(self, buf, shape, level, roi, enc, fill=np.nan, max_planes=0):
+        """decode_host_seg_roi_masked into device memory: `buf` holds the region's elements as float64."""
+        return self._decode_seg_roi_masked(lib().wr_decode_device_seg_roi_masked, buf.ptr, shape, level, roi, enc, fill, max_planes)
+
+    def mask_restore_box(self, buf, shape, level, roi, bits, fill=np.nan, dtype=np.float64, offset=0, bits_offset=0):
+        """Stage level: `fill` into the region `roi` of the box of `level` held contiguously in the device buffer `buf` (from
+        ELEMENT `offset`), where the mask plane `bits` (from byte bits_offset) of the field `shape` says undefined; returns the
+        count of those samples (wr_dev_mask_restore_box, _f32)."""
+        dt = self._mask_dtype("mask_restore_box", dtype)
+        fn = lib().wr_dev_mask_restore_box if dt == np.float64 else lib().wr_dev_mask_restore_box_f32
+        nz, ny, nx = shape
+        r = C.byref(_box(roi)) if roi is not None else None
+        undefined = C.c_ulonglong(0)
+        _check(fn(self.h, buf.ptr + offset * dt.itemsize, nx, ny, nz, level, r, bits.ptr + bits_offset, float(fill), C.byref(undefined)))
+        return int(undefined.value)
 
     @staticmethod
     def _mask_dtype(who, dtype):

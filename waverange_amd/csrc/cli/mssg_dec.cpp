@@ -9,6 +9,16 @@
 //
 // A TYPE 0 "mask" record whose payload is a WRM1 blob (wrenc_mssg --mask=bits) is decoded together with the field record behind
 // it by wr_decode_host_seg_masked, the undefined points coming back as the control file's `undef`; no option is needed.
+//
+// Options (taken out of the command line before its arguments are counted; TYPE 0 only, sets in a segmented stream format):
+//   --level=R               the low-pass box of level R (0..4, default 0: the field's own resolution)
+//   --roi=x0:x1,y0:y1,z0:z1 a half-open box in the coordinates of the box of level R, in the order NX NY NZ (default: all of it)
+//   --planes=P              the first P quantizer planes only (default 0: all)
+// With any of them OUT.grd holds that region of every time record; a bit-mask record and its field go through
+// wr_decode_host_seg_roi_masked (undefined points: the control file's `undef`), an unmasked record through the plain region /
+// low-resolution call.  The control file is not copied (its extents would be wrong): the region's extents are printed.  The
+// run is refused with status 2, nothing written, for TYPE 1 / 2, for a record in the reference's stream format, for a mask
+// record of the old kind (a coded field of doubles) and on a codec library without these calls.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -32,6 +42,19 @@ struct Params {
     std::string in_prefix, ext, out_prefix;
     int filetype = 0, outtype = 1, flip = 0, proc = 0;
 };
+
+struct Partial {  // --level, --roi, --planes
+    int level = 0, planes = 0;
+    bool have_roi = false;
+    wr_box roi{0, 0, 0, 0, 0, 0};
+};
+
+[[noreturn]] void refuse(const std::string& why)
+{
+    std::cout << "Error: " << why << std::endl;
+    std::cerr << "Error: " << why << std::endl;
+    std::exit(2);
+}
 
 void get_params(int argc, char** argv, Params* p)
 {
@@ -192,6 +215,105 @@ int regular_output(const Params& p, int nbytes)
     return 0;
 }
 
+wr_enc_info info_of(const Coding& c)
+{
+    wr_enc_info info;
+    memset(&info, 0, sizeof info);
+    info.tolabs = c.tolabs; info.midval = c.midval; info.halfspanval = c.halfspanval;
+    info.wlev = c.wlev; info.nlay = c.nlay; info.ntot_enc = c.ntot_enc;
+    for (int l = 0; l < c.nlay && l < kNlayMax; l++) { info.deps_vec[l] = c.deps_vec[l]; info.minval_vec[l] = c.minval_vec[l]; info.len_enc_vec[l] = c.len_enc_vec[l]; }
+    return info;
+}
+
+// ---- TYPE 0 with --level / --roi / --planes: a region of every time record
+int regular_output_region(const Params& p, int nbytes, const Partial& pd)
+{
+    if (!(wr_decode_host_seg_roi_masked && wr_decode_host_seg_roi && wr_decode_host_seg_lowres && wr_lowres_dims && wr_ctx_create && wr_ctx_destroy &&
+          wr_last_error))
+        refuse(std::string("--level / --roi / --planes: ") + wrcli::kNotSupported);
+    const std::string control = p.in_prefix + ".ctl";
+    const GradsControl g = read_grads_control(control);
+    std::cout << std::endl << "=== Parameters read from control file ===" << std::endl;
+    std::cout << " dset=" << g.dset << " nx=" << g.nx << " ny=" << g.ny << " nz=" << g.nz << " nt=" << g.nt << " undef=" << g.undef
+              << std::endl;
+    int bx = 0, by = 0, bz = 0;
+    if (wr_lowres_dims(g.nx, g.ny, g.nz, pd.level, &bx, &by, &bz) != 0) refuse(std::string("--level: ") + wr_last_error());
+    wr_box roi{0, 0, 0, bx, by, bz};
+    if (pd.have_roi) {
+        roi = pd.roi;
+        if (!(roi.x0 < roi.x1 && roi.x1 <= bx && roi.y0 < roi.y1 && roi.y1 <= by && roi.z0 < roi.z1 && roi.z1 <= bz))
+            refuse("--roi: the region is empty or reaches outside the box of the level");
+    }
+    const int cx = roi.x1 - roi.x0, cy = roi.y1 - roi.y0, cz = roi.z1 - roi.z0;
+    std::ifstream header, payload;
+    open_or_die(header, p.in_prefix + "_h" + p.ext, std::ios::in);
+    open_or_die(payload, p.in_prefix + "_f" + p.ext, std::ios::in | std::ios::binary);
+    std::string line;
+    // first the whole set's records are looked at, then the first byte is written
+    struct Record { Coding c; size_t mask_len; };
+    std::vector<Record> recs;
+    for (int j = 0; j < 8; j++) std::getline(header, line);  // the preamble written by the encoder
+    auto starts_with = [&](unsigned long len, unsigned char* head4) {
+        memset(head4, 0, 4);
+        payload.read(reinterpret_cast<char*>(head4), (std::streamsize)(len < 4 ? len : 4));
+        payload.seekg((std::streamoff)(len < 4 ? 0 : len - 4), std::ios::cur);
+    };
+    for (int it = 0; it < g.nt; it++) {
+        Record r;
+        r.mask_len = 0;
+        unsigned char head4[4];
+        std::string name = read_header_record(header, it, &r.c);
+        if (name == "mask") {
+            starts_with(r.c.ntot_enc, head4);
+            if (r.c.ntot_enc < 4 || memcmp(head4, "WRM1", 4) != 0)
+                refuse("time record " + std::to_string(it + 1) + ": a mask record of the old kind (a coded field): encode with --mask=bits for --level / --roi / --planes");
+            r.mask_len = r.c.ntot_enc;
+            (void)read_header_record(header, it, &r.c);
+        }
+        starts_with(r.c.ntot_enc, head4);
+        if (r.c.ntot_enc > 0 && !wrcli::is_segmented(head4, r.c.ntot_enc < 4 ? r.c.ntot_enc : 4))
+            refuse("time record " + std::to_string(it + 1) + ": --level / --roi / --planes need a segmented stream format (WR_STREAM_FORMAT=wrs1, wrs2 or wrs3 when encoding)");
+        if (pd.planes > (int)r.c.nlay) refuse("--planes exceeds the planes of time record " + std::to_string(it + 1));
+        if (pd.level > (int)r.c.wlev) refuse("--level exceeds the transform depth of time record " + std::to_string(it + 1));
+        recs.push_back(r);
+    }
+    payload.clear();
+    payload.seekg(0, std::ios::beg);
+    std::cout << " region: level=" << pd.level << " x=" << roi.x0 << ":" << roi.x1 << " y=" << roi.y0 << ":" << roi.y1 << " z=" << roi.z0 << ":" << roi.z1
+              << " nx=" << cx << " ny=" << cy << " nz=" << cz << " nt=" << g.nt << std::endl;
+    const std::string out_name = p.out_prefix + ".grd";
+    int dev = 0;
+    if (const char* e = getenv("WR_DEVICE")) dev = atoi(e);
+    wr_ctx* ctx = nullptr;
+    if (wr_ctx_create(&ctx, dev, nullptr) != 0) { std::cout << "Error: " << wr_last_error() << std::endl; std::exit(1); }
+    std::vector<double> out((size_t)cx * cy * cz);
+    std::vector<unsigned char> buf;
+    int rc = 0;
+    for (int it = 0; it < g.nt && rc == 0; it++) {
+        const Record& r = recs[(size_t)it];
+        const wr_enc_info info = info_of(r.c);
+        // the planes in front of the blob, as the masked call reads them; in the payload the blob comes first
+        buf.resize(r.c.ntot_enc + r.mask_len + 1);
+        payload.read(reinterpret_cast<char*>(buf.data() + r.c.ntot_enc), (std::streamsize)r.mask_len);
+        payload.read(reinterpret_cast<char*>(buf.data()), (std::streamsize)r.c.ntot_enc);
+        const wr_box* box = pd.have_roi ? &roi : nullptr;
+        if (r.mask_len) {
+            std::cout << "  decoding mask bits and fld_1d_rec, it=" << it << std::endl;
+            rc = wr_decode_host_seg_roi_masked(ctx, out.data(), g.nx, g.ny, g.nz, pd.level, pd.planes, box, &info, buf.data(), r.c.ntot_enc + r.mask_len,
+                                               g.undef, nullptr, nullptr);
+        } else {
+            std::cout << "  decoding fld_1d_rec, it=" << it << std::endl;
+            rc = box ? wr_decode_host_seg_roi(ctx, out.data(), g.nx, g.ny, g.nz, pd.level, pd.planes, box, &info, buf.data(), r.c.ntot_enc, nullptr)
+                     : wr_decode_host_seg_lowres(ctx, out.data(), g.nx, g.ny, g.nz, pd.level, pd.planes, &info, buf.data(), r.c.ntot_enc, nullptr);
+        }
+        if (rc != 0) { std::cout << "Error: " << wr_last_error() << std::endl; break; }
+        write_field(out_name, p.flip != 0, nbytes, it, cx, cy, cz, cx, cy, 0, 0, out.data());
+        std::cout << "  wrote: fld_1d_rec[0]=" << out[0] << " fld_1d_rec[last]=" << out[out.size() - 1] << std::endl;
+    }
+    wr_ctx_destroy(ctx);
+    return rc ? 1 : 0;
+}
+
 // ---- TYPE 1 and 2 (mssg_dec.cpp:334-548)
 int restart_set(const Params& p, int nbytes)
 {
@@ -261,9 +383,26 @@ int restart_set(const Params& p, int nbytes)
 
 int main(int argc, char** argv)
 {
+    std::vector<std::string> options;
+    argc = wrcli::take_options(argc, argv, options);
+    Partial pd;
+    bool partial = false;
+    for (const std::string& o : options) {
+        std::string v;
+        bool good = false;
+        if (wrcli::option_value(o, "level", &v)) good = wrcli::parse_uint(v, &pd.level) && pd.level <= 4;
+        else if (wrcli::option_value(o, "roi", &v)) good = pd.have_roi = wrcli::parse_roi(v, &pd.roi);
+        else if (wrcli::option_value(o, "planes", &v)) good = wrcli::parse_uint(v, &pd.planes);
+        if (!good) {
+            std::cout << "options (TYPE 0, segmented stream formats): --level=R (0..4) --roi=x0:x1,y0:y1,z0:z1 --planes=P\n";
+            refuse("bad option " + o);
+        }
+        partial = true;
+    }
     Params p;
     get_params(argc, argv, &p);
     const int nbytes = p.outtype == 1 ? 4 : 8;
+    if (partial && p.filetype != 0) refuse("--level / --roi / --planes apply to TYPE 0 (regular output) only");
     std::cout << std::endl << "=== Decoding parameters ===" << std::endl;
     std::cout << "Encoded file name prefix: " << p.in_prefix << std::endl;
     std::cout << "Encoded file extension name: " << p.ext << std::endl;
@@ -273,7 +412,7 @@ int main(int argc, char** argv)
     if (p.flip) std::cout << "Convert big endian to little endian or vice versa" << std::endl;
     std::cout << "This proc id: " << p.proc << std::endl;
     int rc = 0;
-    if (p.filetype == 0) rc = regular_output(p, nbytes);
+    if (p.filetype == 0) rc = partial ? regular_output_region(p, nbytes, pd) : regular_output(p, nbytes);
     else if (p.filetype == 1 || p.filetype == 2) rc = restart_set(p, nbytes);
     else std::cout << "Error: unknown file type" << std::endl;
     std::cout << "=== End of decompression ===\n";

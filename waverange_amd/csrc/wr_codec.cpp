@@ -2041,6 +2041,7 @@ struct MaskDecode {
     unsigned long long* counters = nullptr;  // behind the bits
     unsigned int h_bad = 0;
     unsigned long long h_counters[2] = {0, 0};
+    bool partial = false;  // (MaskRegion) only some segments are decoded: the checks over the whole mask are not made
 
     const unsigned char* plane() const { return blob + wrmask::kHeaderBytes; }
     size_t plane_len() const { return len - wrmask::kHeaderBytes; }
@@ -2091,6 +2092,7 @@ struct MaskDecode {
         if (hipStreamSynchronize(s.st) != hipSuccess) return fail(WR_ERR_HIP, "the mask's decoder failed on the device");
         coder_ms = s.ms(2);
         if (h_bad) return fail(WR_ERR_STREAM, "mask blob: " + bad_segments_text(h_bad));
+        if (partial) return WR_OK;
         if (h_counters[1]) return fail(WR_ERR_STREAM, "mask blob: a bit beyond the field's last sample is set");
         if (h_counters[0] != undefined) return fail(WR_ERR_STREAM, "mask blob: the mask's set bits are not the count in its header");
         return WR_OK;
@@ -2159,6 +2161,29 @@ int dev_mask_apply(wr_ctx* c, T* d_fld, size_t n, const unsigned char* d_bits, d
     return WR_OK;
 }
 
+// wr_dev_mask_restore_box / _f32: the box restore alone, as a stage call
+template <class T>
+int dev_mask_restore_box(wr_ctx* c, T* d_out, int nx, int ny, int nz, int level, const wr_box* roi, const unsigned char* d_bits, double fill,
+                                unsigned long long* undefined)
+{
+    if (int rc = ctx_bind(c)) return rc;
+    if (!d_out || !d_bits || !undefined) return fail(WR_ERR_ARG, "null pointer");
+    if (nx < 1 || ny < 1 || nz < 1 || !wrlow::level_ok(level)) return fail(WR_ERR_ARG, "non-positive dimension or level outside [0, 4]");
+    const wrlow::Box b = wrlow::box_of(nx, ny, nz, level);
+    if (roi && !wrroi::roi_ok(b, *roi)) return fail(WR_ERR_ARG, "the region is empty or reaches outside the box of the level");
+    const wrmask::Region g = roi ? wrmask::Region{nx, ny, nz, level, roi->x0, roi->y0, roi->z0, roi->x1, roi->y1, roi->z1}
+                                 : wrmask::Region{nx, ny, nz, level, 0, 0, 0, b.bx, b.by, b.bz};
+    std::lock_guard<std::mutex> lk(c->mu);
+    StageLock cu(c->pool->cu_mu);
+    unsigned long long* const counters = reinterpret_cast<unsigned long long*>(c->d_partial);
+    unsigned long long got = 0;
+    wrk::mask_restore_box(d_out, g, d_bits, (T)fill, counters, c->stream);
+    if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask restore launch failed");
+    HIPCHK(hipMemcpyAsync(&got, counters, sizeof got, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *undefined = got;
+    return WR_OK;
+}
 // bud != nullptr: an encode to a byte budget (WRS1): the tolerance comes from the search, cut.vec[0] only names the finest one
 // bnd != nullptr: an encode to an error bound (any of the formats), likewise
 // msk != nullptr: a masked encode: split and fill in front of the prologue, the mask blob behind the planes
@@ -2475,6 +2500,103 @@ int seg_upload_lists(wr_ctx* c, const SegStream& s, int used, const unsigned cha
     return seg_upload_lists(c, s, used, data_enc, blob, work, bufs->bricks.p, ids, bricks, ms, bytes_up);
 }
 
+// The mask of a masked region or low-resolution decode (include/waverange_amd.h): MaskDecode with the mask cropped.  Only the
+// segments that hold a bit of the region are uploaded and decoded (wrmask::roi_segments) -- the bits buffer is still the whole
+// plane, written where those segments lie -- and the restore runs on the region as the finisher left it.
+struct MaskRegion : MaskDecode {
+    wrmask::Region g{};
+    std::vector<uint32_t> ids;
+    size_t bytes_up = 0;
+    float up_ms = 0;
+
+    // (behind parse) the list of the region; roi == nullptr: the whole box of the level
+    void plan(int nx, int ny, int nz, int level, const wrlow::Box& box, const wr_box* roi)
+    {
+        partial = true;
+        g = roi ? wrmask::Region{nx, ny, nz, level, roi->x0, roi->y0, roi->z0, roi->x1, roi->y1, roi->z1}
+                : wrmask::Region{nx, ny, nz, level, 0, 0, 0, box.bx, box.by, box.bz};
+        ids.resize(wrmask::roi_segments(g, seg, nullptr, 0));
+        wrmask::roi_segments(g, seg, ids.data(), ids.size());
+    }
+
+    // the buffers, the second stream, the listed segments' bytes, the list and the offsets on the device
+    int upload(wr_ctx* ctx, SegBufs* bufs)
+    {
+        c = ctx;
+        const size_t bits_bytes = (nsym + 255) & ~(size_t)255;
+        bufs->mask[0] = plane_scratch(c, bits_bytes + 256);
+        bufs->mask[1] = plane_scratch(c, wrk::seg_decode_list_work_bytes(nseg, ids.size()));
+        bufs->mask[2] = plane_scratch(c, (plane_len() + 15) & ~(size_t)15);
+        for (const DevPlanes::Buf& b : bufs->mask) if (!b.p) return WR_ERR_HIP;
+        bits = bufs->mask[0].p;
+        counters = reinterpret_cast<unsigned long long*>(bits + bits_bytes);
+        if (int rc = s.create()) return rc;
+        bufs->also = s.st;
+        SegStream one;  // the mask's plane as a stream of one WRS1 plane
+        one.nlay = 1; one.off[1] = plane_len(); one.seg[0] = seg; one.nseg[0] = nseg;
+        uint8_t *blob_of[1] = {bufs->mask[2].p}, *work_of[1] = {bufs->mask[1].p};
+        if (int rc = seg_upload_lists(c, one, 1, plane(), blob_of, work_of, nullptr, &ids, std::vector<uint32_t>(), &up_ms, &bytes_up)) return rc;
+        g_stat[WR_STAT_MASK_ROI_BYTES_UP] += bytes_up;
+        return WR_OK;
+    }
+
+    // (cu_mu held) the mask's list decoder on the second stream
+    int launch(SegBufs* bufs)
+    {
+        HIPCHK(hipEventRecord(s.ev[4], s.st));
+        wrk::seg_decode_list(bufs->mask[2].p, plane_len(), wrk::plane_ref(bits), nsym, seg, bufs->mask[1].p, ids.size(), s.st, 0, 0);
+        HIPCHK(hipEventRecord(s.ev[5], s.st));
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask decoder launch failed");
+        HIPCHK(hipMemcpyAsync(&h_bad, wrk::seg_work_bad(bufs->mask[1].p), sizeof h_bad, hipMemcpyDeviceToHost, s.st));
+        g_stat[WR_STAT_MASK_ROI_SEGMENTS] += ids.size();
+        return WR_OK;
+    }
+
+    // (the context's stream, behind the finisher) `fill` into the region at d_out where a bit is set; the count comes back with
+    // the stream's next synchronisation
+    template <class T>
+    int restore_box(T* d_out)
+    {
+        HIPCHK(hipEventRecord(s.ev[2], c->stream));
+        wrk::mask_restore_box(d_out, g, bits, (T)fill, counters, c->stream);
+        HIPCHK(hipEventRecord(s.ev[3], c->stream));
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask restore launch failed");
+        HIPCHK(hipMemcpyAsync(h_counters, counters, sizeof h_counters[0], hipMemcpyDeviceToHost, c->stream));
+        restored = true;
+        return WR_OK;
+    }
+
+    // a host caller's region of a constant padded field: the bits come to the host, as midval was put there
+    int restore_host(const FieldRef& fld)
+    {
+        std::vector<unsigned char> h(nsym);
+        HIPCHK(hipMemcpy(h.data(), bits, nsym, hipMemcpyDeviceToHost));
+        const int cx = g.x1 - g.x0, cy = g.y1 - g.y0, cz = g.z1 - g.z0;
+        size_t at = 0;
+        h_counters[0] = 0;
+        for (int z = 0; z < cz; z++)
+            for (int y = 0; y < cy; y++)
+                for (int x = 0; x < cx; x++, at++) {
+                    const size_t J = g.bit(x, y, z);
+                    if (!((h[J >> 3] >> (J & 7)) & 1)) continue;
+                    if (fld.host) fld.host[at] = fill;
+                    else fld.host_f32[at] = (float)fill;
+                    h_counters[0]++;
+                }
+        return WR_OK;
+    }
+
+    bool restored = false;  // restore_box has recorded its events
+
+    void result(wr_mask_result* res)
+    {
+        if (!res) return;
+        memset(res, 0, sizeof *res);
+        res->undefined = h_counters[0]; res->pad = pad; res->mask_len = len;
+        res->fill_ms = restored ? s.ms(1) : 0; res->mask_coder_ms = coder_ms;
+    }
+};
+
 // One coder stage (cu_mu held): the first `planes` planes of the stream, from bufs->blob[l] into q[l].
 struct CoderCall {
     const SegStream* s;
@@ -2694,8 +2816,10 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
 // The box of level `level` from the first planes only, or with roi != nullptr a region of it: the segments the plan needs are
 // uploaded and decoded, a launch per used plane.  fld receives the plan's out_elems() elements; a region's crop comes
 // through the slot (roi_from_planes).
+// msk != nullptr (wr_decode_*_seg_roi_masked): the mask blob of a masked record, cropped to the region: judged before the
+// result is written anywhere the caller can see, and applied behind the finisher
 int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int level, int max_planes, const wr_box* roi, const wr_enc_info* info,
-                           const unsigned char* data_enc, size_t data_len, wr_timings* tm)
+                           const unsigned char* data_enc, size_t data_len, wr_timings* tm, MaskRegion* msk = nullptr)
 {
     if (int rc = ctx_bind(c)) return rc;
     if (!info) return fail(WR_ERR_ARG, "null wr_enc_info");
@@ -2716,6 +2840,26 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     // every plane's header and index, used or not, are validated (region_plan has refused what seg_stream_of would of nlay and wlev)
     SegStream s;
     if (int rc = seg_stream_of(nx, ny, nz, info, data_enc, data_len, &s)) return rc;
+    if (msk) {
+        if (int rc = msk->parse(n)) return rc;
+        msk->plan(nx, ny, nz, level, pl.box, roi);
+    }
+    if (s.constant && msk) {  // midval in the region, then the mask (decode_seg_impl)
+        if (int rc = msk->upload(c, &bufs)) return rc;
+        {
+            StageLock cu(pool->cu_mu);
+            if (int rc = msk->launch(&bufs)) return rc;
+            if (int rc = msk->check()) return rc;
+        }
+        if (int rc = fill_constant(c, fld, nbox, info->midval)) return rc;
+        if (fld.dev) {
+            StageLock cu(pool->cu_mu);
+            if (int rc = kernel_stage_end(c, msk->restore_box(fld.dev))) return rc;
+        } else if (int rc = msk->restore_host(fld)) return rc;
+        local.total = now() - t0;
+        if (tm) *tm = local;
+        return WR_OK;
+    }
     if (s.constant) return finish_constant(c, fld, nbox, info->midval, t0, &local, tm);
     const int used = pl.planes;
     // a blocked stream: the bricks the plan needs, the same in every plane
@@ -2742,6 +2886,7 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     size_t bytes_up = 0;
     if (int rc = seg_upload_lists(c, s, used, data_enc, &bufs, ids, bricks, &local.h2d_ms, &bytes_up)) return rc;
     g_stat[pl.stat_bytes_up] += bytes_up;
+    if (msk) if (int rc = msk->upload(c, &bufs)) return rc;
     const double t_coded = now();
     SlotNeed need;
     pl.need(fld.host || fld.host_f32, &need);
@@ -2757,6 +2902,7 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     {
         StageLock cu(pool->cu_mu);
         clock_warmup(c, pl.work_elems());
+        if (msk) if (int rc = msk->launch(&bufs)) return rc;  // (on its own stream, under the field's coder stage)
         CoderCall k{&s, info, used, n, &bufs, p.q};
         for (int l = 0; l < used; l++) k.perm[l] = bufs.perm.p;
         k.ids = ids;
@@ -2764,6 +2910,7 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
         k.stat_segments = pl.stat_segments;
         k.stat_launches = pl.roi;
         if (int rc = seg_coder_stage(c, k, &local)) return rc;
+        if (msk) if (int rc = msk->check()) return rc;
         if (pl.roi) {
             launch_note(c, "dequant_window", used - 1, slot->field, pl.work_elems(), nullptr, p.q[used - 1]);
             rc = roi_from_planes(c, slot.get(), fld.dev, nx, ny, pl, p, fld.host_f32 != nullptr, &d_roi);
@@ -2772,6 +2919,7 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
             launch_note(c, "dequant_box", used - 1, d_box, nbox, nullptr, p.q[used - 1]);
             rc = lowres_from_planes(c, slot.get(), d_box, nx, ny, pl, p, fld.host_f32 ? &d_f32 : nullptr);
         }
+        if (rc == WR_OK && msk) rc = fld.host_f32 ? msk->restore_box(d_f32) : msk->restore_box(d_box);
         rc = kernel_stage_end(c, rc);
     }
     if (rc) return rc;
@@ -3459,6 +3607,55 @@ int wr_decode_device_seg_masked(wr_ctx* c, double* d_fld, int nx, int ny, int nz
     FieldRef f; f.dev = d_fld;
     if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
     return decode_seg_masked(c, f, nx, ny, nz, info, data_enc, data_len, fill, tm, res);
+}
+
+// ---- masked region and low-resolution decode: roi == nullptr is the whole box of the level
+static int decode_seg_roi_masked(wr_ctx* c, FieldRef f, int nx, int ny, int nz, int level, int max_planes, const wr_box* roi, const wr_enc_info* info,
+                                 const unsigned char* data_enc, size_t data_len, double fill, wr_timings* tm, wr_mask_result* res)
+{
+    if (!info) return fail(WR_ERR_ARG, "null wr_enc_info");
+    if (res) memset(res, 0, sizeof *res);
+    if (data_len == 0 || data_len <= info->ntot_enc)  // an unmasked record (a shorter buffer: the plain call refuses it)
+        return decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, roi, info, data_enc, data_len, tm);
+    if (!data_enc) return fail(WR_ERR_ARG, "null coded buffer");
+    MaskRegion m;
+    m.blob = data_enc + info->ntot_enc; m.len = data_len - info->ntot_enc; m.fill = fill;
+    const int rc = decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, roi, info, data_enc, info->ntot_enc, tm, &m);
+    if (rc == WR_OK) m.result(res);
+    return rc;
+}
+
+int wr_decode_host_seg_roi_masked(wr_ctx* c, double* h_out, int nx, int ny, int nz, int level, int max_planes, const wr_box* roi, const wr_enc_info* info,
+                                  const unsigned char* data_enc, size_t data_len, double fill, wr_timings* tm, wr_mask_result* res)
+{
+    FieldRef f; f.host = h_out;
+    return decode_seg_roi_masked(c, f, nx, ny, nz, level, max_planes, roi, info, data_enc, data_len, fill, tm, res);
+}
+int wr_decode_host_seg_roi_masked_f32(wr_ctx* c, float* h_out, int nx, int ny, int nz, int level, int max_planes, const wr_box* roi,
+                                      const wr_enc_info* info, const unsigned char* data_enc, size_t data_len, double fill, wr_timings* tm,
+                                      wr_mask_result* res)
+{
+    FieldRef f; f.host_f32 = h_out;
+    return decode_seg_roi_masked(c, f, nx, ny, nz, level, max_planes, roi, info, data_enc, data_len, fill, tm, res);
+}
+int wr_decode_device_seg_roi_masked(wr_ctx* c, double* d_out, int nx, int ny, int nz, int level, int max_planes, const wr_box* roi,
+                                    const wr_enc_info* info, const unsigned char* data_enc, size_t data_len, double fill, wr_timings* tm,
+                                    wr_mask_result* res)
+{
+    FieldRef f; f.dev = d_out;
+    if (!d_out) return fail(WR_ERR_ARG, "null device output pointer");
+    return decode_seg_roi_masked(c, f, nx, ny, nz, level, max_planes, roi, info, data_enc, data_len, fill, tm, res);
+}
+
+int wr_dev_mask_restore_box(wr_ctx* c, double* d_out, int nx, int ny, int nz, int level, const wr_box* roi, const unsigned char* d_bits, double fill,
+                            unsigned long long* undefined)
+{
+    return dev_mask_restore_box(c, d_out, nx, ny, nz, level, roi, d_bits, fill, undefined);
+}
+int wr_dev_mask_restore_box_f32(wr_ctx* c, float* d_out, int nx, int ny, int nz, int level, const wr_box* roi, const unsigned char* d_bits, double fill,
+                                unsigned long long* undefined)
+{
+    return dev_mask_restore_box(c, d_out, nx, ny, nz, level, roi, d_bits, fill, undefined);
 }
 
 int wr_encode_host_seg_blocked(wr_ctx* c, const double* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, const double* cutoffvec,

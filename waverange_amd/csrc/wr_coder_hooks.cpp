@@ -421,6 +421,19 @@ size_t wr_seg_roi_segments(int nx, int ny, int nz, int level, int wlev, const wr
     return wrroi::segments_of(nx, ny, nz, wrroi::geometry_of(wrlow::box_of(nx, ny, nz, level), wlev - level, *roi), seg, ids, ids ? cap : 0);
 }
 
+// the crop of the mask of a masked record (wr_mask.h): host only
+size_t wr_mask_roi_segments(int nx, int ny, int nz, int level, const wr_box* roi, unsigned seg, uint32_t* ids, size_t cap)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
+    if (nx < 1 || ny < 1 || nz < 1 || !wrlow::level_ok(level)) { fail(WR_ERR_ARG, "non-positive dimension or level outside [0, 4]"); return 0; }
+    const wrlow::Box b = wrlow::box_of(nx, ny, nz, level);
+    const wr_box whole{0, 0, 0, b.bx, b.by, b.bz};
+    if (roi && !wrroi::roi_ok(b, *roi)) { fail(WR_ERR_ARG, "the region is empty or reaches outside the box of the level"); return 0; }
+    const wr_box& r = roi ? *roi : whole;
+    return wrmask::roi_segments(wrmask::Region{nx, ny, nz, level, r.x0, r.y0, r.z0, r.x1, r.y1, r.z1}, seg, ids, ids ? cap : 0);
+}
+
 size_t wr_seg_lowres_segments_blocked(int nx, int ny, int nz, int level, int wlev, unsigned brick, unsigned seg, uint32_t* ids, size_t cap)
 {
     if (!seg) seg = WR_SEG_DEFAULT;

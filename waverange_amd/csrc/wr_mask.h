@@ -11,7 +11,9 @@
 #include <stdint.h>
 #include <string.h>
 
+#ifndef WR_MASK_HOST_ONLY  // (defined by a host-only program that wants the blob and the crop below without the HIP runtime)
 #include <hip/hip_runtime.h>
+#endif
 
 namespace wrmask {
 
@@ -56,8 +58,45 @@ inline const char* check_header(const unsigned char* p, size_t len, size_t n, un
     return nullptr;
 }
 
+// ---- the crop of a mask (include/waverange_amd.h, "Masked region and low-resolution decode"), host only.  Sample (i, j, k) of
+// the level-r box sits at the field's sample (i << r, j << r, k << r): lifting keeps the even samples.  A region is a half-open
+// box in the coordinates of the level-r box, inside it.
+struct Region {
+    int nx, ny, nz;  // the FIELD's extents
+    int r;           // the level
+    int x0, y0, z0, x1, y1, z1;
+    size_t elems() const { return (size_t)(x1 - x0) * (y1 - y0) * (z1 - z0); }
+    // the mask bit of the region's sample (x, y, z), region coordinates
+    size_t bit(int x, int y, int z) const
+    {
+        return ((size_t)(x0 + x) << r) + (size_t)nx * (((size_t)(y0 + y) << r) + (size_t)ny * ((size_t)(z0 + z) << r));
+    }
+};
+
+// The ascending ids of the mask-plane segments (of `seg` symbols, a symbol = 8 bits) that hold a bit of the region; at most
+// `cap` are written to ids (nullptr: none), the number of all of them is returned.  The bits of a run (y, z) are 2^r <= 16
+// apart and a segment holds at least 128, so a run touches every segment between its first and its last; the runs ascend in the
+// plane, so do the segments.
+inline size_t roi_segments(const Region& g, uint32_t seg, uint32_t* ids, size_t cap)
+{
+    size_t count = 0, next = 0;  // next: the first segment not yet listed
+    for (int z = 0; z < g.z1 - g.z0; z++)
+        for (int y = 0; y < g.y1 - g.y0; y++) {
+            size_t k = (g.bit(0, y, z) >> 3) / seg;
+            const size_t last = (g.bit(g.x1 - g.x0 - 1, y, z) >> 3) / seg;
+            if (k < next) k = next;
+            for (; k <= last; k++) {
+                if (ids && count < cap) ids[count] = (uint32_t)k;
+                count++;
+            }
+            next = last + 1;
+        }
+    return count;
+}
+
 }  // namespace wrmask
 
+#ifndef WR_MASK_HOST_ONLY
 namespace wrk {
 
 // ---- k_mask_split: one read of the field.  bits[0, ceil(n / 8)) = the mask; result[0] = S, the fp64 sum of the defined samples
@@ -76,7 +115,14 @@ void mask_fill(float* x, size_t n, const uint8_t* bits, float v, hipStream_t st)
 // counters[1] |= 1 if one of them lies at or beyond n (integer atomics, one per wave; zeroed here).  x == nullptr: only counted.
 void mask_restore(double* x, size_t n, const uint8_t* bits, double v, unsigned long long* counters, hipStream_t st);
 void mask_restore(float* x, size_t n, const uint8_t* bits, float v, unsigned long long* counters, hipStream_t st);
+// ---- k_mask_restore_box: the restore on a region of a level's box.  out = the region's elements, contiguous, x fastest;
+// out[x, y, z] = v where bit g.bit(x, y, z) of `bits` is set, nothing else is touched; counters[0] += the set bits among the
+// region's (one integer atomic per wave; zeroed here).  `bits` is the full-length plane, any alignment; only bytes that hold a
+// bit of the region are read.
+void mask_restore_box(double* out, const wrmask::Region& g, const uint8_t* bits, double v, unsigned long long* counters, hipStream_t st);
+void mask_restore_box(float* out, const wrmask::Region& g, const uint8_t* bits, float v, unsigned long long* counters, hipStream_t st);
 
 }  // namespace wrk
+#endif
 
 #endif

@@ -174,4 +174,84 @@ static void mask_restore_t(T* x, size_t n, const uint8_t* bits, T v, unsigned lo
 void mask_restore(double* x, size_t n, const uint8_t* bits, double v, unsigned long long* counters, hipStream_t st) { mask_restore_t(x, n, bits, v, counters, st); }
 void mask_restore(float* x, size_t n, const uint8_t* bits, float v, unsigned long long* counters, hipStream_t st) { mask_restore_t(x, n, bits, v, counters, st); }
 
+// ---- the restore on a region of a level's box (wrmask::Region).  A wave takes 64 consecutive x of one region row per turn;
+// the turns of a row, then the rows, go round the grid's waves: wave w takes turn t = w, w + W, ...  (turn, y, z) are kept as
+// counters that advance by W's digits with carries, so the walk has no division after its first step.
+struct MaskBox {
+    unsigned long long nx, ny;  // the field's
+    uint32_t r;
+    uint32_t x0, y0, z0;
+    uint32_t cx, cy, cz;  // the region's extents
+};
+
+// The word of a turn at level 0: bits J0 .. J0 + cnt - 1 (cnt in 1 .. 64) as bits 0 .. cnt - 1, from the 1 .. 9 bytes that hold
+// them and no others (bits above cnt - 1: whatever those bytes hold).  Every lane of the wave passes the same J0 and cnt.
+__device__ inline unsigned long long mask_word_at(const uint8_t* __restrict__ bits, size_t J0, uint32_t cnt)
+{
+    const size_t b0 = J0 >> 3;
+    const uint32_t sh = (uint32_t)(J0 & 7), nb = (uint32_t)(((J0 + cnt - 1) >> 3) - b0) + 1;
+    unsigned long long lo = 0;
+    if (nb >= 8 && (reinterpret_cast<uintptr_t>(bits + b0) & 7) == 0) lo = *reinterpret_cast<const unsigned long long*>(bits + b0);
+    else
+        for (uint32_t k = 0; k < 8; k++)
+            if (k < nb) lo |= (unsigned long long)bits[b0 + k] << (8 * k);
+    unsigned long long m = lo >> sh;
+    if (nb == 9) m |= (unsigned long long)bits[b0 + 8] << (64 - sh);  // (nine bytes: sh != 0)
+    return m;
+}
+
+template <typename T>
+__global__ __launch_bounds__(WR_MASK_THREADS) void k_mask_restore_box(T* __restrict__ out, MaskBox g, const uint8_t* __restrict__ bits, T v,
+                                                                        unsigned long long* __restrict__ counters)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * WR_MASK_WAVES + (threadIdx.x >> 6)));
+    const uint32_t nwaves = gridDim.x * WR_MASK_WAVES;
+    const uint32_t tpr = (g.cx + 63) >> 6;  // turns per row
+    // the step W = nwaves as digits (dt, dy, dz) in the bases (tpr, cy, .), and where the wave starts
+    const uint32_t dt = nwaves % tpr, drow = nwaves / tpr, dy = drow % g.cy, dz = drow / g.cy;
+    uint32_t turn = wave % tpr, y = (wave / tpr) % g.cy, z = (wave / tpr) / g.cy;
+    unsigned long long pop = 0;  // (of the wave: every lane holds the same value)
+    while (z < g.cz) {
+        const uint32_t xs = turn << 6, left = g.cx - xs, cnt = left < 64 ? left : 64;
+        const unsigned long long valid = cnt == 64 ? ~0ull : (1ull << cnt) - 1;
+        const size_t row = (size_t)g.nx * (((size_t)(g.y0 + y) << g.r) + (size_t)g.ny * ((size_t)(g.z0 + z) << g.r));
+        unsigned long long m;
+        if (g.r == 0) {
+            m = mask_word_at(bits, row + g.x0 + xs, cnt) & valid;
+        } else {
+            const size_t J = row + ((size_t)(g.x0 + xs + lane) << g.r);
+            m = __ballot(lane < cnt && ((bits[J >> 3] >> (J & 7)) & 1));
+        }
+        if (m) {  // (the whole wave: m is the same in every lane)
+            pop += (unsigned long long)__popcll(m);
+            if ((m >> lane) & 1) out[((size_t)z * g.cy + y) * g.cx + xs + lane] = v;
+        }
+        turn += dt;
+        const uint32_t carry = turn >= tpr;
+        if (carry) turn -= tpr;
+        y += dy + carry;
+        if (y >= g.cy) { y -= g.cy; z++; }
+        z += dz;
+    }
+    if (lane == 0 && pop) atomicAdd(&counters[0], pop);
+}
+
+template <typename T>
+static void mask_restore_box_t(T* out, const wrmask::Region& g, const uint8_t* bits, T v, unsigned long long* counters, hipStream_t st)
+{
+    MaskBox b;
+    b.nx = (unsigned long long)g.nx; b.ny = (unsigned long long)g.ny;
+    b.r = (uint32_t)g.r;
+    b.x0 = (uint32_t)g.x0; b.y0 = (uint32_t)g.y0; b.z0 = (uint32_t)g.z0;
+    b.cx = (uint32_t)(g.x1 - g.x0); b.cy = (uint32_t)(g.y1 - g.y0); b.cz = (uint32_t)(g.z1 - g.z0);
+    const size_t turns = (size_t)((b.cx + 63) >> 6) * b.cy * b.cz;
+    size_t grid = (turns + WR_MASK_WAVES - 1) / WR_MASK_WAVES;
+    if (grid > WR_MASK_BLOCKS) grid = WR_MASK_BLOCKS;
+    (void)hipMemsetAsync(counters, 0, sizeof(unsigned long long), st);
+    hipLaunchKernelGGL((k_mask_restore_box<T>), dim3((unsigned)grid), dim3(WR_MASK_THREADS), 0, st, out, b, bits, v, counters);
+}
+void mask_restore_box(double* out, const wrmask::Region& g, const uint8_t* bits, double v, unsigned long long* counters, hipStream_t st) { mask_restore_box_t(out, g, bits, v, counters, st); }
+void mask_restore_box(float* out, const wrmask::Region& g, const uint8_t* bits, float v, unsigned long long* counters, hipStream_t st) { mask_restore_box_t(out, g, bits, v, counters, st); }
+
 }  // namespace wrk
