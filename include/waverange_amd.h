@@ -639,6 +639,84 @@ int wr_decode_host_seg_masked_f32(wr_ctx *ctx, float *h_fld, int nx, int ny, int
 int wr_decode_device_seg_masked(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, const wr_enc_info *info,
                                 const unsigned char *data_enc, size_t data_len, double fill, wr_timings *tm,
                                 wr_mask_result *res);
+/* ---- Masked fields in the tolerance searches: the error is taken over the defined samples only.
+ * Definitions.  Let D be the set of defined samples of the field f under `below` (above), nd = |D| = n - undefined, pad the
+ * split's mean, f_pad the padded field, and r_g the reconstruction of the plain call's stream of f_pad at t(g), formed exactly
+ * as a trial of the bounded and quality calls forms it (the fp32 reconstruction for an fp32 field).  Then
+ *   E_D(g) = max over j in D of |f_j - r_g[j]|           (one fp64 subtraction per sample: exact, whatever the order)
+ *   S_D(g) = the fp64 sum over j in D of fl(d_j * d_j), d_j = fl(f_j - r_g[j])      (finite d_j only)
+ *   R_D(g) = fl(sqrt(fl(S_D / nd)))                      (the division is by nd, not by n)
+ * lo, hi and range = hi - lo are those of the defined samples.  They equal the values the prologue forms for f_pad, because the
+ * mean of the defined samples -- and, for an fp32 field, that mean rounded to float, rounding being monotone -- lies in
+ * [lo, hi]; the calls rely on this: the start point of the walk and the conversion of a PSNR target use the prologue's lo and
+ * hi of f_pad.  The two guarantees of the quality calls hold as stated there: reproducible (the same n, the same mask, the same
+ * alignment class and the same library give the same bits: per-thread sums in index order, a fixed tree over lanes, waves and
+ * blocks, no floating-point atomics) and accurate (|S_D - S_D*| <= 2^-36 * S_D* for every n <= 2^33, S_D* the real sum of the
+ * same rounded squares; the kernel's derivation gives 2^-38: csrc/wr_mask.hip).  A difference at a DEFINED sample that is not
+ * finite is counted in `nonfinite`; nothing at an undefined position is ever looked at, whatever the two arrays hold there.
+ * wr_encode_*_seg_quality_masked take the arguments of the _quality calls plus `below`, and fill a wr_quality_result and a
+ * wr_mask_result (mres may be null).  The contract is that of the quality calls with E_D, S_D, R_D in the place of E, S, R:
+ *   it holds / it is tight / coded once   as there; WR_NORM_MAX is the masked pointwise bound, E_D(g) <= target (rms, sumsq, psnr
+ *                    and max_rms NaN, as there); WR_STAT_QUALITY_CODER_RUNS grows by info->nlay;
+ *   it is the same   info and the first info->ntot_enc bytes of data_enc are bit for bit the plain call's stream of f_pad at
+ *                    t(g) in the chosen format; the mask blob behind them, mres->mask_len bytes, and mres are what
+ *                    wr_encode_*_seg_masked gives at that tolerance.
+ * undefined == 0: the plain compare runs, and the whole result is bit for bit the plain quality call's.  A sample that is not
+ * finite is undefined by definition, so the quality calls' refusal of such a field does not apply.
+ * wr_encode_*_seg_budget_masked take the arguments of the _budget calls plus `below`.  The budget holds the whole record:
+ *   it fits          B(g) + mask_len <= max_bytes, mask_len the blob's exact length (the search waits for the mask's coder
+ *                    before its first probe); res->bound = B(g);
+ *   it is the same   g, res->bound, res->probe_passes, info and the first info->ntot_enc bytes are bit for bit what
+ *                    wr_encode_host_seg_budget returns for f_pad with max_bytes - mask_len; the blob is the masked call's.
+ * WR_ERR_BUDGET: max_bytes <= mask_len on a field that is not constant, or B(WR_BUDGET_GMAX) + mask_len > max_bytes;
+ * wr_last_error() names mask_len + B(WR_BUDGET_GMAX), the smallest budget that would do, and data_enc is not written.  WRS1 only.
+ * Common to both: cap must hold the planes plus wr_mask_bound(n, seg); no defined sample and a NaN `below`: WR_ERR_ARG; a
+ * constant f_pad: nlay = 0, g = WR_BUDGET_GMAX (budget: g_min), errors 0, trials = 0, the blob at data_enc; a local cutoff and
+ * wr_ctx_set_keep_residual(ctx, 1): WR_ERR_UNSUPPORTED.
+ * wr_seg_error_stats_host_masked / _f32: the measuring half.  data_len = the planes plus the mask blob of a masked record (the
+ * blob validated as wr_decode_host_seg_masked validates it: WR_ERR_STREAM; data_len == info->ntot_enc: an unmasked record,
+ * every sample defined).  The record is filled over the RECORD's defined samples -- max_abs = E_D, sumsq = S_D, rms = R_D, the
+ * bits the encode reported; lo and hi of the defined samples of h_fld -- and *defined = nd.  h_fld may hold anything at the
+ * undefined positions.  WR_ERR_ARG when nonfinite > 0, with the record still filled.
+ * wr_dev_err_stats_masked / _f32: the masked compare alone on two device arrays of n >= 1 samples and a packed mask d_bits (bit
+ * j & 7 of byte j >> 3), all of any alignment; no mask byte at or beyond ceil(n / 8) and no sample at or beyond n is read, and what a
+ * sample whose bit is set holds never matters.
+ * *defined = the clear bits below n, rms = sqrt(sumsq / *defined) (a NaN when there is none); lo, hi and psnr come back as
+ * NaN.  It returns WR_OK whatever nonfinite is. */
+int wr_encode_host_seg_quality_masked(wr_ctx *ctx, const double *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my,
+                                      int mz, int norm, double target, double tol_min, unsigned seg, unsigned brick,
+                                      unsigned strands, double below, wr_enc_info *info, unsigned char *data_enc, size_t cap,
+                                      wr_timings *tm, wr_quality_result *res, wr_mask_result *mres);
+int wr_encode_host_seg_quality_masked_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my,
+                                          int mz, int norm, double target, double tol_min, unsigned seg, unsigned brick,
+                                          unsigned strands, double below, wr_enc_info *info, unsigned char *data_enc,
+                                          size_t cap, wr_timings *tm, wr_quality_result *res, wr_mask_result *mres);
+int wr_encode_device_seg_quality_masked(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                        int norm, double target, double tol_min, unsigned seg, unsigned brick,
+                                        unsigned strands, double below, wr_enc_info *info, unsigned char *data_enc, size_t cap,
+                                        wr_timings *tm, wr_quality_result *res, wr_mask_result *mres);
+int wr_encode_host_seg_budget_masked(wr_ctx *ctx, const double *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my,
+                                     int mz, size_t max_bytes, double tol_min, unsigned seg, double below, wr_enc_info *info,
+                                     unsigned char *data_enc, size_t cap, wr_timings *tm, wr_budget_result *res,
+                                     wr_mask_result *mres);
+int wr_encode_host_seg_budget_masked_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny, int nz, int wtflag, int mx, int my,
+                                         int mz, size_t max_bytes, double tol_min, unsigned seg, double below,
+                                         wr_enc_info *info, unsigned char *data_enc, size_t cap, wr_timings *tm,
+                                         wr_budget_result *res, wr_mask_result *mres);
+int wr_encode_device_seg_budget_masked(wr_ctx *ctx, double *d_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                       size_t max_bytes, double tol_min, unsigned seg, double below, wr_enc_info *info,
+                                       unsigned char *data_enc, size_t cap, wr_timings *tm, wr_budget_result *res,
+                                       wr_mask_result *mres);
+int wr_seg_error_stats_host_masked(wr_ctx *ctx, const double *h_fld, int nx, int ny, int nz, const wr_enc_info *info,
+                                   const unsigned char *data_enc, size_t data_len, wr_error_stats *stats,
+                                   unsigned long long *defined);
+int wr_seg_error_stats_host_masked_f32(wr_ctx *ctx, const float *h_fld, int nx, int ny, int nz, const wr_enc_info *info,
+                                       const unsigned char *data_enc, size_t data_len, wr_error_stats *stats,
+                                       unsigned long long *defined);
+int wr_dev_err_stats_masked(wr_ctx *ctx, const double *d_a, const double *d_b, size_t n, const unsigned char *d_bits,
+                            wr_error_stats *stats, unsigned long long *defined);
+int wr_dev_err_stats_masked_f32(wr_ctx *ctx, const float *d_a, const float *d_b, size_t n, const unsigned char *d_bits,
+                                wr_error_stats *stats, unsigned long long *defined);
 /* ---- Low-resolution decode of segmented streams: a coarse version of the field without decoding the field.
  * The transform is a Mallat decomposition (waveletcdf97_3d.c:73-78): after level r the low-pass coefficients of an nx*ny*nz
  * field sit in the corner box [0,bx) x [0,by) x [0,bz) of the coefficient array.  With h(n) = (n + 1) / 2 in integer

@@ -284,6 +284,22 @@ def lib():
                                             C.POINTER(Timings), C.POINTER(MaskResult)]
     L.wr_decode_host_seg_masked_f32.argtypes = L.wr_decode_host_seg_masked.argtypes
     L.wr_decode_device_seg_masked.argtypes = L.wr_decode_host_seg_masked.argtypes
+    # masked fields in the tolerance searches: the quality and budget calls, the measuring half and the masked compare alone
+    L.wr_encode_host_seg_quality_masked.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                    C.c_double, C.c_uint, C.c_uint, C.c_uint, C.c_double, C.POINTER(EncInfo), _vp, C.c_size_t,
+                                                    C.POINTER(Timings), C.POINTER(QualityResult), C.POINTER(MaskResult)]
+    L.wr_encode_host_seg_quality_masked_f32.argtypes = L.wr_encode_host_seg_quality_masked.argtypes
+    L.wr_encode_device_seg_quality_masked.argtypes = L.wr_encode_host_seg_quality_masked.argtypes
+    L.wr_encode_host_seg_budget_masked.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_double,
+                                                   C.c_uint, C.c_double, C.POINTER(EncInfo), _vp, C.c_size_t, C.POINTER(Timings),
+                                                   C.POINTER(BudgetResult), C.POINTER(MaskResult)]
+    L.wr_encode_host_seg_budget_masked_f32.argtypes = L.wr_encode_host_seg_budget_masked.argtypes
+    L.wr_encode_device_seg_budget_masked.argtypes = L.wr_encode_host_seg_budget_masked.argtypes
+    L.wr_seg_error_stats_host_masked.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(EncInfo), _vp, C.c_size_t, C.POINTER(ErrorStats),
+                                                 C.POINTER(C.c_ulonglong)]
+    L.wr_seg_error_stats_host_masked_f32.argtypes = L.wr_seg_error_stats_host_masked.argtypes
+    L.wr_dev_err_stats_masked.argtypes = [_vp, _vp, _vp, C.c_size_t, _vp, C.POINTER(ErrorStats), C.POINTER(C.c_ulonglong)]
+    L.wr_dev_err_stats_masked_f32.argtypes = L.wr_dev_err_stats_masked.argtypes
     # masked region and low-resolution decode (a NULL region: the whole box of the level)
     L.wr_mask_roi_segments.restype = C.c_size_t
     L.wr_mask_roi_segments.argtypes = [C.c_int] * 4 + [C.POINTER(Box), C.c_uint, _vp, C.c_size_t]
@@ -1748,6 +1764,113 @@ class Context:
         st = ErrorStats()
         _check(fn(self.h, a.ptr + a_off * dt.itemsize, b.ptr + b_off * dt.itemsize, int(n), C.byref(st)))
         return st.as_dict()
+
+    # ---- masked fields in the tolerance searches: the error is taken over the defined samples only
+    def _encode_seg_quality_masked(self, fn, ptr, shape, norm, target, below, tol_min, wtflag, seg, brick, strands, out, m):
+        nz, ny, nx = shape
+        cap = self._seg_cap(shape, seg, brick if brick else None, strands if strands else None) + mask_bound(nx * ny * nz, seg)
+        data = out if out is not None else np.empty(cap, dtype=np.uint8)
+        info, tm, res, mres = EncInfo(), Timings(), QualityResult(), MaskResult()
+        _check(fn(self.h, ptr, nx, ny, nz, wtflag, m[0], m[1], m[2], int(norm), float(target), float(tol_min), seg, brick, strands, float(below),
+                  C.byref(info), data.ctypes.data, data.size, C.byref(tm), C.byref(res), C.byref(mres)))
+        d = info.as_dict()
+        d["data"] = data[:info.ntot_enc + mres.mask_len]
+        d["mask"] = mres.as_dict()
+        r = res.as_dict()
+        r["timings"] = tm.as_dict()
+        return d, d["data"], r
+
+    def encode_host_seg_quality_masked(self, fld, norm, target, below=-np.inf, tol_min=2.0 ** -60, seg=0, brick=0, strands=0, wtflag=1, out=None,
+                                       m=(1, 1, 1)):
+        """encode_host_seg_quality of a masked field: the samples that are not finite or < below are undefined, and max_abs, rms,
+        sumsq and psnr are taken over the defined samples only, rms dividing by their count (wr_encode_host_seg_quality_masked).
+        norm = NORM_MAX is the masked pointwise bound.  Returns (info, data, result): the record of encode_host_seg_masked at
+        tolrel = result["tolrel"] -- info["data"] holds ntot_enc bytes of planes, then info["mask"]["mask_len"] bytes of mask blob --
+        and the QualityResult of encode_host_seg_quality."""
+        assert fld.dtype == np.float64 and fld.flags["C_CONTIGUOUS"]
+        return self._encode_seg_quality_masked(lib().wr_encode_host_seg_quality_masked, fld.ctypes.data, fld.shape, norm, target, below, tol_min, wtflag,
+                                               seg, brick, strands, out, m)
+
+    def encode_host_seg_quality_masked_f32(self, fld, norm, target, below=-np.inf, tol_min=2.0 ** -60, seg=0, brick=0, strands=0, wtflag=1, out=None,
+                                           m=(1, 1, 1)):
+        if not (isinstance(fld, np.ndarray) and fld.dtype == np.float32 and fld.flags["C_CONTIGUOUS"]):
+            raise TypeError("encode_host_seg_quality_masked_f32: a C-contiguous float32 array is required")
+        return self._encode_seg_quality_masked(lib().wr_encode_host_seg_quality_masked_f32, fld.ctypes.data, fld.shape, norm, target, below, tol_min,
+                                               wtflag, seg, brick, strands, out, m)
+
+    def encode_seg_quality_masked(self, buf, shape, norm, target, below=-np.inf, tol_min=2.0 ** -60, seg=0, brick=0, strands=0, wtflag=1, out=None,
+                                  m=(1, 1, 1)):
+        """encode_host_seg_quality_masked with the field resident on the device (`buf` is consumed, as by encode)."""
+        return self._encode_seg_quality_masked(lib().wr_encode_device_seg_quality_masked, buf.ptr, shape, norm, target, below, tol_min, wtflag, seg,
+                                               brick, strands, out, m)
+
+    def _encode_seg_budget_masked(self, fn, ptr, shape, max_bytes, below, tol_min, wtflag, seg, out, m):
+        nz, ny, nx = shape
+        data = out if out is not None else np.empty(self._seg_cap(shape, seg) + mask_bound(nx * ny * nz, seg), dtype=np.uint8)
+        info, tm, res, mres = EncInfo(), Timings(), BudgetResult(), MaskResult()
+        _check(fn(self.h, ptr, nx, ny, nz, wtflag, m[0], m[1], m[2], int(max_bytes), float(tol_min), seg, float(below), C.byref(info),
+                  data.ctypes.data, data.size, C.byref(tm), C.byref(res), C.byref(mres)))
+        d = info.as_dict()
+        d["data"] = data[:info.ntot_enc + mres.mask_len]
+        d["mask"] = mres.as_dict()
+        return d, d["data"], {"g": res.g, "tolrel": res.tolrel, "bound": res.bound, "probe_passes": res.probe_passes, "timings": tm.as_dict()}
+
+    def encode_host_seg_budget_masked(self, fld, max_bytes, below=-np.inf, tol_min=2.0 ** -60, wtflag=1, seg=0, out=None, m=(1, 1, 1)):
+        """encode_host_seg_budget of a masked field: the planes and the mask blob together fit max_bytes,
+        result["bound"] + info["mask"]["mask_len"] <= max_bytes (wr_encode_host_seg_budget_masked).  Returns (info, data, result):
+        the record of encode_host_seg_masked at tolrel = result["tolrel"], and the result of encode_host_seg_budget."""
+        assert fld.dtype == np.float64 and fld.flags["C_CONTIGUOUS"]
+        return self._encode_seg_budget_masked(lib().wr_encode_host_seg_budget_masked, fld.ctypes.data, fld.shape, max_bytes, below, tol_min, wtflag, seg, out, m)
+
+    def encode_host_seg_budget_masked_f32(self, fld, max_bytes, below=-np.inf, tol_min=2.0 ** -60, wtflag=1, seg=0, out=None, m=(1, 1, 1)):
+        if not (isinstance(fld, np.ndarray) and fld.dtype == np.float32 and fld.flags["C_CONTIGUOUS"]):
+            raise TypeError("encode_host_seg_budget_masked_f32: a C-contiguous float32 array is required")
+        return self._encode_seg_budget_masked(lib().wr_encode_host_seg_budget_masked_f32, fld.ctypes.data, fld.shape, max_bytes, below, tol_min, wtflag, seg,
+                                              out, m)
+
+    def encode_seg_budget_masked(self, buf, shape, max_bytes, below=-np.inf, tol_min=2.0 ** -60, wtflag=1, seg=0, out=None, m=(1, 1, 1)):
+        """encode_host_seg_budget_masked with the field resident on the device (`buf` is consumed, as by encode)."""
+        return self._encode_seg_budget_masked(lib().wr_encode_device_seg_budget_masked, buf.ptr, shape, max_bytes, below, tol_min, wtflag, seg, out, m)
+
+    def _seg_error_stats_masked(self, fn, fld, enc, allow_nonfinite):
+        nz, ny, nx = fld.shape
+        info = EncInfo.from_dict(enc)
+        data = np.ascontiguousarray(enc["data"], dtype=np.uint8)
+        if data.size == 0:
+            data = np.zeros(1, dtype=np.uint8)
+        st, defined = ErrorStats(), C.c_ulonglong(0)
+        rc = fn(self.h, fld.ctypes.data, nx, ny, nz, C.byref(info), data.ctypes.data, np.ascontiguousarray(enc["data"]).size, C.byref(st), C.byref(defined))
+        d = st.as_dict()
+        d["defined"] = int(defined.value)
+        if not (allow_nonfinite and d["nonfinite"] > 0):
+            _check(rc)
+        return d
+
+    def seg_error_stats_host_masked(self, fld, enc, allow_nonfinite=False):
+        """seg_error_stats_host of a masked record (enc["data"]: planes, then the mask blob) over the record's defined samples:
+        the ErrorStats record with "defined", their count; lo and hi are those of the defined samples.  Whatever `fld` holds at an
+        undefined position is never looked at (wr_seg_error_stats_host_masked)."""
+        assert fld.dtype == np.float64 and fld.flags["C_CONTIGUOUS"]
+        return self._seg_error_stats_masked(lib().wr_seg_error_stats_host_masked, fld, enc, allow_nonfinite)
+
+    def seg_error_stats_host_masked_f32(self, fld, enc, allow_nonfinite=False):
+        if not (isinstance(fld, np.ndarray) and fld.dtype == np.float32 and fld.flags["C_CONTIGUOUS"]):
+            raise TypeError("seg_error_stats_host_masked_f32: a C-contiguous float32 array is required")
+        return self._seg_error_stats_masked(lib().wr_seg_error_stats_host_masked_f32, fld, enc, allow_nonfinite)
+
+    def err_stats_masked(self, a, b, n, bits, dtype=np.float64, a_off=0, b_off=0, bits_offset=0):
+        """Stage level: err_stats over the samples whose bit of the packed mask in the device buffer `bits` (from byte
+        bits_offset) is clear; nothing is read where a bit is set.  The record of err_stats with "defined", the count of samples
+        compared, and rms = sqrt(sumsq / defined) (wr_dev_err_stats_masked, wr_dev_err_stats_masked_f32)."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise TypeError("err_stats_masked: float64 or float32")
+        fn = lib().wr_dev_err_stats_masked if dt == np.float64 else lib().wr_dev_err_stats_masked_f32
+        st, defined = ErrorStats(), C.c_ulonglong(0)
+        _check(fn(self.h, a.ptr + a_off * dt.itemsize, b.ptr + b_off * dt.itemsize, int(n), bits.ptr + bits_offset, C.byref(st), C.byref(defined)))
+        d = st.as_dict()
+        d["defined"] = int(defined.value)
+        return d
 
     def bounded_trial_ms(self):
         """(requantize, inverse, compare) milliseconds summed over the trials of the last bounded encode on this context."""

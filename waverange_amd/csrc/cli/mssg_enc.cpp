@@ -15,10 +15,17 @@
 // below the mask threshold, NaNs, infinities -- travel as a packed bit mask: a record named "mask" whose payload is the WRM1
 // blob (nlay = 1, len_enc_vec[0] = ntot_enc = its length, the other scalars 0), then the field's record as always.  wrdec_mssg
 // recognises the blob by its magic.  Without the option nothing changes.
+//
+// --maxerr=E | --rmse=E | --psnr=DB (with --mask=bits): every TYPE 0 field goes through wr_encode_host_seg_quality_masked instead:
+// coded at the coarsest tolerance not below TOLERANCE that keeps every DEFINED point within E (--maxerr), or whose RMS error
+// over the defined points stays within E (--rmse), both in the field's units, or whose PSNR over the range of the defined
+// points reaches DB (--psnr).  TOLERANCE is then the finest tolerance allowed; the tool prints the one chosen and the error
+// reached.  The three exclude one another.  The container is the same: wrdec_mssg needs nothing.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <iomanip>
 #include <iostream>
@@ -182,6 +189,8 @@ void min_max(const double* f, size_t n, double* lo, double* hi)
 struct MaskBits {
     wr_ctx* ctx = nullptr;
     unsigned seg = 0, brick = 0, strands = 0;
+    int norm = 0;  // --maxerr: WR_NORM_MAX, --rmse: WR_NORM_RMS, --psnr: WR_NORM_PSNR; 0: the tolerance is TOLERANCE
+    double target = 0;
 };
 
 // one TYPE 0 field through wr_encode_host_seg_masked: the "mask" record if a sample is undefined, then the field's record
@@ -197,8 +206,26 @@ void code_masked(const MaskBits& mb, int nx, int ny, int nz, const double* fld, 
     wr_enc_info info;
     wr_mask_result res;
     double cutoff = tolrel;
-    if (wr_encode_host_seg_masked(mb.ctx, fld, nx, ny, nz, 1, 1, 1, 1, &cutoff, mb.seg, mb.brick, mb.strands, below, &info, buf.data(), buf.size(),
-                                  nullptr, &res) != 0) {
+    if (mb.norm) {  // to a target over the defined points, no tolerance finer than TOLERANCE
+        wr_quality_result q;
+        if (wr_encode_host_seg_quality_masked(mb.ctx, fld, nx, ny, nz, 1, 1, 1, 1, mb.norm, mb.target, tolrel, mb.seg, mb.brick, mb.strands, below, &info,
+                                              buf.data(), buf.size(), nullptr, &q, &res) != 0) {
+            std::cout << "Error: field with " << (mb.norm == WR_NORM_MAX ? "an error bound" : mb.norm == WR_NORM_RMS ? "an RMS error target" : "a PSNR target")
+                      << " of " << std::setprecision(17) << mb.target << ": " << wr_last_error() << std::endl;
+            std::exit(1);
+        }
+        char line[400];
+        if (mb.norm == WR_NORM_MAX)
+            snprintf(line, sizeof line, "  Error bound %.17g: relative tolerance %.17g (grid point %d), error %.17g, %d trials, coded %lu bytes", mb.target, q.tolrel,
+                     q.g, q.max_abs, q.trials, (unsigned long)info.ntot_enc);
+        else
+            snprintf(line, sizeof line,
+                     "  %s target %.17g: relative tolerance %.17g (grid point %d), rms %.17g (allowed %.17g), psnr %.17g dB, max error %.17g, %d trials, coded %lu bytes",
+                     mb.norm == WR_NORM_RMS ? "RMS error" : "PSNR", mb.target, q.tolrel, q.g, q.rms, q.max_rms, q.psnr, q.max_abs, q.trials,
+                     (unsigned long)info.ntot_enc);
+        std::cout << line << " (over the defined points)" << std::endl;
+    } else if (wr_encode_host_seg_masked(mb.ctx, fld, nx, ny, nz, 1, 1, 1, 1, &cutoff, mb.seg, mb.brick, mb.strands, below, &info, buf.data(), buf.size(),
+                                         nullptr, &res) != 0) {
         std::cout << "Error: " << wr_last_error() << std::endl;
         std::exit(1);
     }
@@ -329,6 +356,10 @@ int mask_bits_setup(MaskBits* mb)
         fprintf(stderr, "wrenc_mssg: --mask=bits: %s\n", wrcli::kNotSupported);
         return 2;
     }
+    if (mb->norm && !wr_encode_host_seg_quality_masked) {
+        fprintf(stderr, "wrenc_mssg: --%s: %s\n", mb->norm == WR_NORM_MAX ? "maxerr" : mb->norm == WR_NORM_RMS ? "rmse" : "psnr", wrcli::kNotSupported);
+        return 2;
+    }
     int format = WR_FORMAT_REF;
     if (wr_get_stream_format(&format, &mb->seg, &mb->brick, &mb->strands) != 0) {
         fprintf(stderr, "wrenc_mssg: --mask=bits: %s\n", wr_last_error());
@@ -355,10 +386,25 @@ int main(int argc, char** argv)
     argc = wrcli::take_options(argc, argv, options);
     MaskBits mb;
     bool mask_bits = false;
+    const char* target_opt = nullptr;  // "maxerr", "rmse" or "psnr" once one of them is given
     for (const std::string& o : options) {
         std::string v;
-        if (wrcli::option_value(o, "mask", &v) && v == "bits") mask_bits = true;
-        else { fprintf(stderr, "wrenc_mssg: unknown option %s (--mask=bits is the only one)\n", o.c_str()); return 2; }
+        if (wrcli::option_value(o, "mask", &v) && v == "bits") { mask_bits = true; continue; }
+        const char* name = wrcli::option_value(o, "maxerr", &v) ? "maxerr" : wrcli::option_value(o, "rmse", &v) ? "rmse" : wrcli::option_value(o, "psnr", &v) ? "psnr" : nullptr;
+        if (!name) { fprintf(stderr, "wrenc_mssg: unknown option %s (--mask=bits, --maxerr=E, --rmse=E, --psnr=DB)\n", o.c_str()); return 2; }
+        if (target_opt && strcmp(target_opt, name)) { fprintf(stderr, "wrenc_mssg: --%s and --%s exclude one another\n", target_opt, name); return 2; }
+        char* end = nullptr;
+        mb.target = strtod(v.c_str(), &end);
+        if (v.empty() || *end || !(mb.target > 0) || !(mb.target < 1e308)) {
+            fprintf(stderr, "wrenc_mssg: --%s=%s: a positive number is required\n", name, v.c_str());
+            return 2;
+        }
+        target_opt = name;
+        mb.norm = name[0] == 'm' ? WR_NORM_MAX : name[0] == 'r' ? WR_NORM_RMS : WR_NORM_PSNR;
+    }
+    if (target_opt && !mask_bits) {
+        fprintf(stderr, "wrenc_mssg: --%s needs --mask=bits: the error is taken over the defined points of a bit-masked field\n", target_opt);
+        return 2;
     }
     if (mask_bits) if (int rc = mask_bits_setup(&mb)) return rc;
     Params p;

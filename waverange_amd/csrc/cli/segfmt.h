@@ -83,6 +83,10 @@ int wr_encode_host_seg_masked(wr_ctx* ctx, const double* h_fld, int nx, int ny, 
                               wr_timings* tm, wr_mask_result* res) __attribute__((weak));
 int wr_decode_host_seg_masked(wr_ctx* ctx, double* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
                               double fill, wr_timings* tm, wr_mask_result* res) __attribute__((weak));
+// a masked field to a pointwise, RMS or PSNR target (wrenc_mssg --mask=bits --maxerr, --rmse, --psnr)
+int wr_encode_host_seg_quality_masked(wr_ctx* ctx, const double* h_fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, int norm, double target,
+                                      double tol_min, unsigned seg, unsigned brick, unsigned strands, double below, wr_enc_info* info, unsigned char* data_enc,
+                                      size_t cap, wr_timings* tm, wr_quality_result* res, wr_mask_result* mres) __attribute__((weak));
 // the masked region / low-resolution decode (wrdec_mssg --level, --roi, --planes)
 int wr_decode_host_seg_roi_masked(wr_ctx* ctx, double* h_out, int nx, int ny, int nz, int level, int max_planes, const wr_box* roi,
                                   const wr_enc_info* info, const unsigned char* data_enc, size_t data_len, double fill, wr_timings* tm,

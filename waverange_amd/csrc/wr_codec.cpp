@@ -1499,6 +1499,9 @@ struct BudgetSearch {
     // what the caller asks for
     size_t max_bytes = 0;
     int g_min = 0;
+    // a masked call: the mask blob's exact length, already taken off max_bytes (reserve() below); it only enters the message
+    size_t mask_len = 0, budget = 0;  // (budget: max_bytes as the caller gave it)
+    bool masked = false;
     // what comes out
     int g = -1;
     size_t bound = 0;
@@ -1550,6 +1553,14 @@ struct BudgetSearch {
         if (int rc = tables(c)) return rc;
         HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         return WR_OK;
+    }
+
+    // a masked call: B(g) + len <= max_bytes is B(g) <= max_bytes - len; a budget the blob alone uses up leaves 0 for the planes,
+    // which no tolerance fits (a blob's header and index are never empty), so the first pick names the smallest budget
+    void reserve(size_t len)
+    {
+        masked = len != 0; mask_len = len; budget = max_bytes;
+        max_bytes = max_bytes > len ? max_bytes - len : 0;
     }
 
     // one launch: the candidates' segment sums into out[0, cd.n) (the blob's header and index added)
@@ -1658,9 +1669,14 @@ struct BudgetSearch {
             return WR_OK;
         }
         const size_t b_top = at(cur, cur.top);
-        if (!fits_above && b_top > max_bytes)
+        if (!fits_above && b_top > max_bytes) {
+            if (masked)
+                return fail(WR_ERR_BUDGET, "the budget leaves " + std::to_string(max_bytes) + " bytes beside the mask blob of " + std::to_string(mask_len) +
+                                               " bytes, below what the coarsest tolerance takes: " + std::to_string(mask_len + b_top) +
+                                               " bytes is the smallest budget that would do");
             return fail(WR_ERR_BUDGET, "the budget of " + std::to_string(max_bytes) + " bytes is below what the coarsest tolerance takes: " +
                                            std::to_string(b_top) + " bytes is the smallest budget that would do");
+        }
         if (b_top > max_bytes) return fail(WR_ERR_HIP, "internal: the budget search lost the point that fits");
         fits_above = true;
         const size_t b_a = at(cur, cur.a);
@@ -1749,6 +1765,11 @@ struct BoundedSearch {
     unsigned seg = 0;
     const double* orig = nullptr;    // the field as the caller gave it, on the device, or
     const float* orig_f32 = nullptr;
+    // a masked call with an undefined sample: the split's bits and nd = n - undefined, the size of D.  The compares are then the
+    // masked kernel's (E_D, S_D, R_D = sqrt(S_D / nd)): whatever the field's copy and the reconstruction hold where a bit is set
+    // -- the caller's NaNs or the pad -- is never read.  nullptr: the plain compares, the plain call's bits.
+    const uint8_t* mask_bits = nullptr;
+    unsigned long long nd = 0;
     double *w1 = nullptr, *w2 = nullptr;
     const double* d_coef = nullptr;
     Prologue p{};
@@ -1757,6 +1778,10 @@ struct BoundedSearch {
 
     static double* result_host(wr_ctx* c) { return c->h_result + 8 + 2 * WR_NLAYMAX + wrk::kProbeK; }
     static double* result_dev(wr_ctx* c) { return c->h_result_dev + 8 + 2 * WR_NLAYMAX + wrk::kProbeK; }
+    // the masked compare's count of compared samples: behind the mask coder's record (mask_result_host: + 5, + 6), which a masked
+    // call's second stream may write while a trial runs
+    static unsigned long long* defined_host(wr_ctx* c) { return reinterpret_cast<unsigned long long*>(c->h_result + 8 + 2 * WR_NLAYMAX + wrk::kProbeK + 7); }
+    static unsigned long long* defined_dev(wr_ctx* c) { return reinterpret_cast<unsigned long long*>(c->h_result_dev + 8 + 2 * WR_NLAYMAX + wrk::kProbeK + 7); }
 
     // max |a - b| and the count of differences that are not finite, read back
     template <class T>
@@ -1784,6 +1809,38 @@ struct BoundedSearch {
         return WR_OK;
     }
 
+    // the same over the samples whose bit is clear (wrk::err_stats_masked): R = sqrt(S / defined), defined read back with the rest
+    template <class T>
+    static int compare_stats_masked(wr_ctx* c, const T* a, const T* b, size_t n, const uint8_t* bits, Stats* st, unsigned long long* defined)
+    {
+        wrk::err_stats_masked(a, b, n, bits, c->d_partial, result_dev(c) + 2, defined_dev(c), c->stream);
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "compare launch failed");
+        HIPCHK(hipEventRecord(c->ev_d, c->stream));
+        HIPCHK(hipEventSynchronize(c->ev_d));
+        const double* r = result_host(c) + 2;
+        st->max_abs = r[0]; st->bad = r[1]; st->sumsq = r[2];
+        *defined = *defined_host(c);
+        st->rms = sqrt(st->sumsq / (double)*defined);
+        return WR_OK;
+    }
+
+    // wr_dev_err_stats_masked / _f32: the masked compare alone, as a stage call
+    template <class T>
+    static int stage_stats_masked(wr_ctx* c, const T* d_a, const T* d_b, size_t n, const unsigned char* d_bits, wr_error_stats* stats,
+                                  unsigned long long* defined)
+    {
+        if (int rc = ctx_bind(c)) return rc;
+        if (!stats || !d_a || !d_b || !d_bits || !defined) return fail(WR_ERR_ARG, "null pointer");
+        if (!n) return fail(WR_ERR_ARG, "empty array");
+        std::lock_guard<std::mutex> lk(c->mu);
+        StageLock cu(c->pool->cu_mu);
+        Stats st;
+        if (int rc = compare_stats_masked(c, d_a, d_b, n, d_bits, &st, defined)) return rc;
+        fill_error_stats(stats, st.max_abs, st.bad, st.sumsq, (size_t)*defined, NAN, NAN);
+        stats->psnr = NAN;
+        return WR_OK;
+    }
+
     // wr_dev_err_stats / _f32: the compare alone, as a stage call
     template <class T>
     static int stage_stats(wr_ctx* c, const T* d_a, const T* d_b, size_t n, wr_error_stats* stats)
@@ -1804,6 +1861,7 @@ struct BoundedSearch {
 
     int nonfinite_field(const std::string& what)
     {
+        if (mask_bits) return fail(WR_ERR_ARG, what);  // (a sample that is not finite is undefined: the field is not to blame)
         double mx = 0, bad = 0;
         if (int rc = orig_f32 ? compare(c, orig_f32, orig_f32, n, &mx, &bad) : compare(c, orig, orig, n, &mx, &bad)) return rc;
         if (bad > 0) return fail(WR_ERR_ARG, who() + " needs a finite field: " + std::to_string((unsigned long long)bad) +
@@ -1853,7 +1911,15 @@ struct BoundedSearch {
         HIPCHK(hipEventRecord(c->ev_c, c->stream));
         if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "a trial's kernel launch failed");
         double bad = 0;
-        if (norm == WR_NORM_MAX) {
+        if (mask_bits) {  // every norm: one kernel knows the mask
+            Stats st;
+            unsigned long long defined = 0;
+            if (int rc = orig_f32 ? compare_stats_masked(c, orig_f32, rec_f32, n, mask_bits, &st, &defined)
+                                  : compare_stats_masked(c, orig, rec, n, mask_bits, &st, &defined)) return rc;
+            if (defined != nd) return fail(WR_ERR_HIP, "internal: the masked compare and the split disagree on the count of defined samples");
+            if (norm != WR_NORM_MAX) seen[gk] = st;
+            *e = norm == WR_NORM_MAX ? st.max_abs : st.rms; bad = st.bad;
+        } else if (norm == WR_NORM_MAX) {
             if (int rc = orig_f32 ? compare(c, orig_f32, rec_f32, n, e, &bad) : compare(c, orig, rec, n, e, &bad)) return rc;
         } else {
             Stats st;
@@ -2000,19 +2066,32 @@ struct MaskEncode {
         return WR_OK;
     }
 
-    // the blob to data_enc + at, once the field's planes are there
-    int finish(const SegBufs& bufs, unsigned char* data_enc, size_t at)
+    // the blob's exact length, mask_len: waits for the mask's coder (an encode to a byte budget needs it before its first probe)
+    int length()
     {
-        if (!undefined) return WR_OK;
+        if (!undefined || mask_len) return WR_OK;
         if (hipStreamSynchronize(s.st) != hipSuccess) return fail(WR_ERR_HIP, "the mask's coder failed on the device");
         const unsigned long long len = mask_result_host(c)[0], bad = mask_result_host(c)[1];
         if (bad || len > blob_cap) return fail(WR_ERR_HIP, std::string("internal: mask plane: ") + kOutgrew);
-        wrmask::put_header(data_enc + at, n, undefined, pad);
-        if (int rc = xfer_field(c, &c->x_field, data_enc + at + wrmask::kHeaderBytes, bufs.mask[2].p, (size_t)len, kDown)) return rc;
         mask_len = wrmask::kHeaderBytes + (size_t)len;
+        return WR_OK;
+    }
+
+    // the blob to data_enc + at, once the field's planes are there
+    int download(const SegBufs& bufs, unsigned char* data_enc, size_t at)
+    {
+        if (!undefined) return WR_OK;
+        wrmask::put_header(data_enc + at, n, undefined, pad);
+        if (int rc = xfer_field(c, &c->x_field, data_enc + at + wrmask::kHeaderBytes, bufs.mask[2].p, mask_len - wrmask::kHeaderBytes, kDown)) return rc;
         fill_ms = s.ms(1);
         coder_ms = s.ms(2);
         return WR_OK;
+    }
+
+    int finish(const SegBufs& bufs, unsigned char* data_enc, size_t at)
+    {
+        if (int rc = length()) return rc;
+        return download(bufs, data_enc, at);
     }
 
     void result(wr_mask_result* res) const
@@ -2187,6 +2266,7 @@ int dev_mask_restore_box(wr_ctx* c, T* d_out, int nx, int ny, int nz, int level,
 // bud != nullptr: an encode to a byte budget (WRS1): the tolerance comes from the search, cut.vec[0] only names the finest one
 // bnd != nullptr: an encode to an error bound (any of the formats), likewise
 // msk != nullptr: a masked encode: split and fill in front of the prologue, the mask blob behind the planes
+// msk with bnd: the trials compare over the defined samples only; msk with bud: the blob's exact length comes off the budget
 int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag, const Cutoff& cut, unsigned seg, unsigned brick, unsigned strands,
                     wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm, BudgetSearch* bud = nullptr, BoundedSearch* bnd = nullptr,
                     MaskEncode* msk = nullptr)
@@ -2267,11 +2347,19 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
         if (msk) {  // the field where it landed: an fp32 field before anything widens it
             float* const x32 = up.d_f32 ? const_cast<float*>(up.d_f32) : up.widen_from;
             if ((rc = fld.host_f32 ? msk->split_fill(&bufs, x32) : msk->split_fill(&bufs, d_fld)) != WR_OK) return rc;
+            // the trials compare over the defined samples only (the field's copy, where one was taken, went ahead of the fill
+            // in stream order: it holds the caller's values; the slot holds the padded field: the masked compare reads neither
+            // where a bit is set)
+            if (bnd && msk->undefined) { bnd->mask_bits = bufs.mask[0].p; bnd->nd = (unsigned long long)n - msk->undefined; }
         }
         if (up.widen_from) wrk::widen_f32(up.widen_from, d_fld, n, c->stream);
         PickStep pick;
         if (bud) {
             if ((rc = bud->begin(c, n, seg)) != WR_OK) return rc;
+            if (msk) {  // the planes get what the blob leaves: its exact length, so the mask's coder is waited for here
+                if ((rc = msk->length()) != WR_OK) return rc;
+                bud->reserve(msk->mask_len);
+            }
             pick = [bud](unsigned l, double lo, double hi, const wrk::QuantPrev& prev, const double* d_coef, const Prologue& p, double* tolabs) {
                 return bud->pick(l, lo, hi, prev, d_coef, p, tolabs);
             };
@@ -2298,6 +2386,8 @@ int encode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int wtflag,
     if (msk && msk->undefined && (!data_enc || wr_mask_bound(n, seg) > cap - total))
         return fail(WR_ERR_OVERFLOW, "the coded buffer does not hold the field's planes and the bound of the mask blob (wr_mask_bound)");
     if (bud && total > bud->bound) return fail(WR_ERR_HIP, "internal: the coded planes are longer than their size bound");
+    if (bud && bud->masked && total + bud->mask_len > bud->budget)  // (a constant padded field: no pick ever saw the budget)
+        return fail(WR_ERR_BUDGET, "the budget is below the mask blob: " + std::to_string(msk->mask_len) + " bytes is the smallest budget that would do");
     if ((rc = seg_download_blobs(c, bufs, info->nlay, info->len_enc_vec, data_enc, &local)) != WR_OK) return rc;
     if (msk) if ((rc = msk->finish(bufs, data_enc, total)) != WR_OK) return rc;
     info->ntot_enc = total;
@@ -2674,8 +2764,11 @@ int seg_coder_stage(wr_ctx* c, const CoderCall& k, wr_timings* tm)
 // stats_out != nullptr (wr_seg_error_stats_host): likewise, the compare being wrk::err_stats and the field's min/max read too
 // msk != nullptr (wr_decode_*_seg_masked): the mask blob of a masked record, judged before the result is written anywhere the
 // caller can see, and applied behind the inverse transform
+// stats_out and msk (wr_seg_error_stats_host_masked): the compare runs over the record's defined samples (the masked kernel, on
+// the decoded mask's bits: nothing is restored), *defined_out their count; lo and hi are those of the defined samples
 int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
-                    wr_timings* tm, double* err_out = nullptr, wr_error_stats* stats_out = nullptr, MaskDecode* msk = nullptr)
+                    wr_timings* tm, double* err_out = nullptr, wr_error_stats* stats_out = nullptr, MaskDecode* msk = nullptr,
+                    unsigned long long* defined_out = nullptr)
 {
     double err_unused = 0;
     if (stats_out && !err_out) err_out = &err_unused;
@@ -2696,6 +2789,7 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
     SegStream s;
     if (int rc = seg_stream_of(nx, ny, nz, info, data_enc, data_len, &s)) return rc;
     if (msk) if (int rc = msk->parse(n)) return rc;
+    std::vector<unsigned char> cbits;  // a constant masked record that is measured: the mask on the host
     if (s.constant && msk) {  // midval everywhere, then the mask: a host field takes the bits on the host, as it takes midval there
         if (int rc = msk->upload(c, &bufs)) return rc;
         {
@@ -2703,6 +2797,12 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
             if (int rc = msk->launch(&bufs)) return rc;
             if (int rc = msk->check()) return rc;
         }
+        if (err_out) {
+            cbits.resize(msk->nsym);
+            HIPCHK(hipMemcpy(cbits.data(), msk->bits, msk->nsym, hipMemcpyDeviceToHost));
+        }
+    }
+    if (s.constant && msk && !err_out) {
         if (int rc = fill_constant(c, fld, n, info->midval)) return rc;
         if (fld.dev) {
             StageLock cu(pool->cu_mu);
@@ -2722,8 +2822,12 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
     }
     if (s.constant && err_out) {  // the reconstruction is midval everywhere (fill_constant)
         double mx = 0;
-        size_t bad = 0;
+        size_t bad = 0, count = n;
+        auto undef = [&](size_t j) { return !cbits.empty() && ((cbits[j >> 3] >> (j & 7)) & 1); };
+        if (msk) count = n - (size_t)msk->undefined;
+        if (defined_out) *defined_out = count;
         for (size_t j = 0; j < n; j++) {
+            if (undef(j)) continue;
             const double d = fld.host ? fabs(fld.host[j] - info->midval) : fabs((double)fld.host_f32[j] - (double)(float)info->midval);
             if (d <= DBL_MAX) mx = d > mx ? d : mx;
             else bad++;
@@ -2731,6 +2835,7 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
         if (stats_out) {  // S by a compensated sum (Neumaier): its error does not grow with n
             double sum = 0, comp = 0, lo = NAN, hi = NAN;
             for (size_t j = 0; j < n; j++) {
+                if (undef(j)) continue;
                 const double v = fld.host ? fld.host[j] : (double)fld.host_f32[j];
                 lo = fmin(lo, v); hi = fmax(hi, v);
                 const double d = fld.host ? v - info->midval : v - (double)(float)info->midval;
@@ -2740,7 +2845,7 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
                 sum = t;
             }
             if (sum <= DBL_MAX) sum += comp;
-            fill_error_stats(stats_out, mx, (double)bad, sum, n, lo, hi);
+            fill_error_stats(stats_out, mx, (double)bad, sum, count, lo, hi);
         }
         if (bad) return fail(WR_ERR_ARG, std::to_string(bad) + " difference(s) between the field and the reconstruction are not finite");
         *err_out = mx;
@@ -2786,19 +2891,32 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
         if (msk) if (int rc = msk->check()) return rc;
         launch_note(c, "dequant", s.nlay - 1, d_fld, n, nullptr, p.q[s.nlay - 1]);
         rc = inverse_from_planes(c, slot.get(), d_fld, nx, ny, nz, (int)info->wlev, p, fld.host_f32 ? &d_f32 : nullptr);
-        if (rc == WR_OK && msk) rc = fld.host_f32 ? msk->restore(d_f32) : msk->restore(d_fld);
+        if (rc == WR_OK && msk && !err_out) rc = fld.host_f32 ? msk->restore(d_f32) : msk->restore(d_fld);
         rc = kernel_stage_end(c, rc);
         if (rc == WR_OK && err_out) {
             double bad = 0;
             if (stats_out) {
                 BoundedSearch::Stats st;
                 double lo = 0, hi = 0;
-                rc = fld.host_f32 ? BoundedSearch::compare_stats(c, reinterpret_cast<const float*>(bufs.trial[2].p), (const float*)d_f32, n, &st)
-                                  : BoundedSearch::compare_stats(c, reinterpret_cast<const double*>(bufs.trial[2].p), (const double*)d_fld, n, &st);
-                if (rc == WR_OK)
-                    rc = fld.host_f32 ? read_minmax(c, reinterpret_cast<const float*>(bufs.trial[2].p), n, false, &lo, &hi)
-                                      : read_minmax(c, reinterpret_cast<const double*>(bufs.trial[2].p), n, false, &lo, &hi);
-                if (rc == WR_OK) fill_error_stats(stats_out, st.max_abs, st.bad, st.sumsq, n, lo, hi);
+                unsigned long long defined = n;
+                float* const f32 = reinterpret_cast<float*>(bufs.trial[2].p);
+                double* const f64 = reinterpret_cast<double*>(bufs.trial[2].p);
+                if (msk) {
+                    rc = fld.host_f32 ? BoundedSearch::compare_stats_masked(c, (const float*)f32, (const float*)d_f32, n, msk->bits, &st, &defined)
+                                      : BoundedSearch::compare_stats_masked(c, (const double*)f64, (const double*)d_fld, n, msk->bits, &st, &defined);
+                    // lo and hi of the defined samples: the blob's pad, their mean, stands in for the others in the field's copy
+                    if (rc == WR_OK && msk->undefined) {
+                        if (fld.host_f32) wrk::mask_fill(f32, n, msk->bits, (float)msk->pad, c->stream);
+                        else wrk::mask_fill(f64, n, msk->bits, msk->pad, c->stream);
+                        if (hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "mask fill launch failed");
+                    }
+                } else {
+                    rc = fld.host_f32 ? BoundedSearch::compare_stats(c, (const float*)f32, (const float*)d_f32, n, &st)
+                                      : BoundedSearch::compare_stats(c, (const double*)f64, (const double*)d_fld, n, &st);
+                }
+                if (rc == WR_OK) rc = fld.host_f32 ? read_minmax(c, (const float*)f32, n, false, &lo, &hi) : read_minmax(c, (const double*)f64, n, false, &lo, &hi);
+                if (rc == WR_OK) fill_error_stats(stats_out, st.max_abs, st.bad, st.sumsq, (size_t)defined, lo, hi);
+                if (defined_out) *defined_out = defined;
                 *err_out = st.max_abs; bad = st.bad;
             } else {
                 rc = fld.host_f32 ? BoundedSearch::compare(c, reinterpret_cast<const float*>(bufs.trial[2].p), (const float*)d_f32, n, err_out, &bad)
@@ -3226,7 +3344,8 @@ int wr_encode_device_seg(wr_ctx* c, double* d_fld, int nx, int ny, int nz, int w
 
 // ---- encode to a byte budget (the search: BudgetSearch above)
 static int encode_seg_budget(wr_ctx* c, FieldRef f, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, size_t max_bytes, double tol_min,
-                             unsigned seg, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm, wr_budget_result* res)
+                             unsigned seg, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm, wr_budget_result* res,
+                             MaskEncode* msk = nullptr)
 {
     if (!res) return fail(WR_ERR_ARG, "null wr_budget_result");
     if (!(tol_min > 0) || tol_min > DBL_MAX) return fail(WR_ERR_ARG, "tol_min must be a positive number");
@@ -3238,7 +3357,7 @@ static int encode_seg_budget(wr_ctx* c, FieldRef f, int nx, int ny, int nz, int 
     const double t_min = wrbud::grid_tol(bud.g_min);  // (the loop's tolerance until the search sets it; a constant field never gets there)
     Cutoff cut; cut.vec = &t_min;
     memset(res, 0, sizeof *res);
-    const int rc = encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, 0, 0, info, data_enc, cap, tm, &bud);
+    const int rc = encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, 0, 0, info, data_enc, cap, tm, &bud, nullptr, msk);
     res->probe_passes = bud.passes;
     if (rc) return rc;
     if (info->nlay == 0) { bud.g = bud.g_min; bud.bound = 0; }
@@ -3349,7 +3468,7 @@ int wr_seg_error_host_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz,
 // ---- encode to an RMS or PSNR target: BoundedSearch in the L2 norm
 static int encode_seg_quality(wr_ctx* c, FieldRef f, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, int norm, double target, double tol_min,
                               unsigned seg, unsigned brick, unsigned strands, wr_enc_info* info, unsigned char* data_enc, size_t cap, wr_timings* tm,
-                              wr_quality_result* res)
+                              wr_quality_result* res, MaskEncode* msk = nullptr)
 {
     if (!res) return fail(WR_ERR_ARG, "null wr_quality_result");
     if (norm != WR_NORM_MAX && norm != WR_NORM_RMS && norm != WR_NORM_PSNR) return fail(WR_ERR_ARG, "norm must be WR_NORM_MAX, WR_NORM_RMS or WR_NORM_PSNR");
@@ -3366,7 +3485,7 @@ static int encode_seg_quality(wr_ctx* c, FieldRef f, int nx, int ny, int nz, int
     const double t_min = wrbud::grid_tol(bnd.g_min);
     Cutoff cut; cut.vec = &t_min;
     memset(res, 0, sizeof *res);
-    const int rc = encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick, strands, info, data_enc, cap, tm, nullptr, &bnd);
+    const int rc = encode_seg_impl(c, f, nx, ny, nz, wtflag, cut, seg, brick, strands, info, data_enc, cap, tm, nullptr, &bnd, msk);
     res->trials = bnd.trials;
     if (c) for (int k = 0; k < 3; k++) c->bounded_ms[k] = bnd.ms[k];
     if (rc) return rc;
@@ -3607,6 +3726,79 @@ int wr_decode_device_seg_masked(wr_ctx* c, double* d_fld, int nx, int ny, int nz
     FieldRef f; f.dev = d_fld;
     if (!d_fld) return fail(WR_ERR_ARG, "null device field pointer");
     return decode_seg_masked(c, f, nx, ny, nz, info, data_enc, data_len, fill, tm, res);
+}
+
+// ---- masked fields in the tolerance searches: the quality and budget calls with a MaskEncode beside the search
+#define WR_MASKED_SEARCH_CALLS(NAME, SUFFIX, FIELD_T, FIELD_MEMBER, CHECK)                                                                                \
+    int wr_encode_##NAME##_quality_masked##SUFFIX(wr_ctx* c, FIELD_T fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, int norm, double target, \
+                                          double tol_min, unsigned seg, unsigned brick, unsigned strands, double below, wr_enc_info* info,            \
+                                          unsigned char* data_enc, size_t cap, wr_timings* tm, wr_quality_result* res, wr_mask_result* mres)         \
+    {                                                                                                                                             \
+        FieldRef f; f.FIELD_MEMBER = const_cast<decltype(f.FIELD_MEMBER)>(fld);                                                                   \
+        CHECK                                                                                                                                     \
+        if (below != below) return fail(WR_ERR_ARG, "the threshold `below` is a NaN (-INFINITY switches it off)");                                \
+        MaskEncode m;                                                                                                                             \
+        m.below = below;                                                                                                                          \
+        const int rc = encode_seg_quality(c, f, nx, ny, nz, wtflag, mx, my, mz, norm, target, tol_min, seg, brick, strands, info, data_enc, cap, tm, res, &m); \
+        if (rc == WR_OK) m.result(mres);                                                                                                          \
+        return rc;                                                                                                                                \
+    }                                                                                                                                             \
+    int wr_encode_##NAME##_budget_masked##SUFFIX(wr_ctx* c, FIELD_T fld, int nx, int ny, int nz, int wtflag, int mx, int my, int mz, size_t max_bytes,       \
+                                         double tol_min, unsigned seg, double below, wr_enc_info* info, unsigned char* data_enc, size_t cap,        \
+                                         wr_timings* tm, wr_budget_result* res, wr_mask_result* mres)                                               \
+    {                                                                                                                                             \
+        FieldRef f; f.FIELD_MEMBER = const_cast<decltype(f.FIELD_MEMBER)>(fld);                                                                   \
+        CHECK                                                                                                                                     \
+        if (below != below) return fail(WR_ERR_ARG, "the threshold `below` is a NaN (-INFINITY switches it off)");                                \
+        MaskEncode m;                                                                                                                             \
+        m.below = below;                                                                                                                          \
+        const int rc = encode_seg_budget(c, f, nx, ny, nz, wtflag, mx, my, mz, max_bytes, tol_min, seg, info, data_enc, cap, tm, res, &m);          \
+        if (rc == WR_OK) m.result(mres);                                                                                                          \
+        return rc;                                                                                                                                \
+    }
+WR_MASKED_SEARCH_CALLS(host_seg, , const double*, host, )
+WR_MASKED_SEARCH_CALLS(host_seg, _f32, const float*, host_f32, )
+WR_MASKED_SEARCH_CALLS(device_seg, , double*, dev, if (!fld) return fail(WR_ERR_ARG, "null device field pointer");)
+#undef WR_MASKED_SEARCH_CALLS
+
+// the measuring half on a masked record: data_len = the field's planes + the mask blob (an unmasked record: every sample is defined)
+static int seg_error_stats_masked(wr_ctx* c, FieldRef f, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc, size_t data_len,
+                                  wr_error_stats* stats, unsigned long long* defined)
+{
+    if (!stats || !defined) return fail(WR_ERR_ARG, "null result pointer");
+    if (f.none()) return fail(WR_ERR_ARG, "null field pointer");
+    if (!info) return fail(WR_ERR_ARG, "null wr_enc_info");
+    memset(stats, 0, sizeof *stats);
+    *defined = 0;
+    if (data_len == 0 || data_len <= info->ntot_enc)
+        return decode_seg_impl(c, f, nx, ny, nz, info, data_enc, data_len, nullptr, nullptr, stats, nullptr, defined);
+    if (!data_enc) return fail(WR_ERR_ARG, "null coded buffer");
+    MaskDecode m;
+    m.blob = data_enc + info->ntot_enc; m.len = data_len - info->ntot_enc;
+    return decode_seg_impl(c, f, nx, ny, nz, info, data_enc, info->ntot_enc, nullptr, nullptr, stats, &m, defined);
+}
+
+int wr_seg_error_stats_host_masked(wr_ctx* c, const double* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc,
+                                   size_t data_len, wr_error_stats* stats, unsigned long long* defined)
+{
+    FieldRef f; f.host = const_cast<double*>(h_fld);  // (only read)
+    return seg_error_stats_masked(c, f, nx, ny, nz, info, data_enc, data_len, stats, defined);
+}
+int wr_seg_error_stats_host_masked_f32(wr_ctx* c, const float* h_fld, int nx, int ny, int nz, const wr_enc_info* info, const unsigned char* data_enc,
+                                       size_t data_len, wr_error_stats* stats, unsigned long long* defined)
+{
+    FieldRef f; f.host_f32 = const_cast<float*>(h_fld);
+    return seg_error_stats_masked(c, f, nx, ny, nz, info, data_enc, data_len, stats, defined);
+}
+int wr_dev_err_stats_masked(wr_ctx* c, const double* d_a, const double* d_b, size_t n, const unsigned char* d_bits, wr_error_stats* stats,
+                            unsigned long long* defined)
+{
+    return BoundedSearch::stage_stats_masked(c, d_a, d_b, n, d_bits, stats, defined);
+}
+int wr_dev_err_stats_masked_f32(wr_ctx* c, const float* d_a, const float* d_b, size_t n, const unsigned char* d_bits, wr_error_stats* stats,
+                                unsigned long long* defined)
+{
+    return BoundedSearch::stage_stats_masked(c, d_a, d_b, n, d_bits, stats, defined);
 }
 
 // ---- masked region and low-resolution decode: roi == nullptr is the whole box of the level

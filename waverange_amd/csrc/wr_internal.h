@@ -164,7 +164,7 @@ struct wr_ctx {
     unsigned long long* d_bound_tot = nullptr;    // the size probe's totals, wrk::kProbeK words
     double bounded_ms[3] = {0, 0, 0};             // the last encode to an error bound: its trials' requantize, inverse and compare stages, summed (HIP events)
     // pinned host
-    double* h_result = nullptr;  // [0..1] min/max, [2] probe value, [3] index, [4..7] fused min/max, [8 + 2l, 9 + 2l] plane l's segmented-coder result (u64: blob length, failed segments), [8 + 2 WR_NLAYMAX ..] the size probe's kProbeK totals (u64), then {max |diff|, non-finite differences} of a bounded encode's compare, then {max |diff|, non-finite differences, sum of squares} of wrk::err_stats, then the result of a masked encode's mask coder (u64: blob length, failed segments)
+    double* h_result = nullptr;  // [0..1] min/max, [2] probe value, [3] index, [4..7] fused min/max, [8 + 2l, 9 + 2l] plane l's segmented-coder result (u64: blob length, failed segments), [8 + 2 WR_NLAYMAX ..] the size probe's kProbeK totals (u64), then {max |diff|, non-finite differences} of a bounded encode's compare, then {max |diff|, non-finite differences, sum of squares} of wrk::err_stats, then the result of a masked encode's mask coder (u64: blob length, failed segments), then the samples a masked compare compared (u64)
     double* h_result_dev = nullptr;  // the same block as the device sees it: reductions write their result straight to the host
     uint16_t* h_hist = nullptr; size_t h_hist_elems = 0;  // pinned: per-block byte histograms, all planes
     // host coded-stream staging, one per plane

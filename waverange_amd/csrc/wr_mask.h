@@ -121,6 +121,15 @@ void mask_restore(float* x, size_t n, const uint8_t* bits, float v, unsigned lon
 // bit of the region are read.
 void mask_restore_box(double* out, const wrmask::Region& g, const uint8_t* bits, double v, unsigned long long* counters, hipStream_t st);
 void mask_restore_box(float* out, const wrmask::Region& g, const uint8_t* bits, float v, unsigned long long* counters, hipStream_t st);
+// ---- k_err_stats_masked: the compare of wrk::err_stats over the samples whose bit is clear.  result[0 .. 2] = the maximum of the
+// finite |a - b|, the count of differences that are not finite, the fp64 sum of the squared finite differences; *defined = the
+// clear bits below n (an exact integer; a word of its own, so that result's neighbours stay untouched).  Nothing at a position
+// whose bit is set enters a result, whatever it holds, and no sample at or beyond n and no mask byte at or beyond ceil(n / 8) is read.  a, b and bits may have any alignment (both arrays aligned for two-sample loads: 128 samples and 16
+// mask bytes per wave and turn; a turn whose bits are all set loads neither array).  partial: 4 * mask_partials() 8-byte words.
+void err_stats_masked(const double* a, const double* b, size_t n, const uint8_t* bits, double* partial, double* result, unsigned long long* defined,
+                      hipStream_t st);
+void err_stats_masked(const float* a, const float* b, size_t n, const uint8_t* bits, double* partial, double* result, unsigned long long* defined,
+                      hipStream_t st);
 
 }  // namespace wrk
 #endif

@@ -254,4 +254,160 @@ static void mask_restore_box_t(T* out, const wrmask::Region& g, const uint8_t* b
 void mask_restore_box(double* out, const wrmask::Region& g, const uint8_t* bits, double v, unsigned long long* counters, hipStream_t st) { mask_restore_box_t(out, g, bits, v, counters, st); }
 void mask_restore_box(float* out, const wrmask::Region& g, const uint8_t* bits, float v, unsigned long long* counters, hipStream_t st) { mask_restore_box_t(out, g, bits, v, counters, st); }
 
+// ---- the masked compare of an encode to an error bound or a quality target on a masked field (include/waverange_amd.h,
+// "Masked fields in the tolerance searches"): what k_err_stats gives (wr_kernels.hip) over the samples whose mask bit is clear
+// -- the maximum of the finite |a - b|, the count of differences that are not finite, S_D = the fp64 sum of q = fl(d * d) over
+// the finite d = fl(a - b), operands widened to fp64 first -- and the number of samples compared, the clear bits below n, as
+// an integer.  Nothing at a position whose bit is set is looked at: such a sample is loaded only as the other half of a pair
+// that has a defined sample, and a select puts 0 in its place.
+// The walk.  PAIRS (both arrays aligned for two-sample loads, 16 bytes fp64, 8 bytes fp32): a wave takes 128 consecutive
+// samples per turn, lane l the pair 128 t + 2 l, 128 t + 2 l + 1 in one load per array, and the turn's 16 mask bytes as two
+// words every lane holds (the wave index is made uniform, so the words are read once per wave, not once per sample); turns go
+// round the grid's waves, wave w takes t = w, w + W, ...  A turn whose 128 bits are all set costs those 16 bytes only.  The
+// element-wise form (any alignment): a turn is 64 samples and one word, lane l sample 64 t + l.  The mask words are read as
+// 8-byte words where `bits` is 8-byte aligned and all 8 bytes lie below ceil(n / 8), byte by byte otherwise (mask_word); no byte
+// at or beyond ceil(n / 8) and no sample at or beyond n is read: the bits at and beyond n count as set (cmp_word).
+// The order of the sum is fixed by n, by which of the two forms runs and by the mask, never by the order in which blocks or
+// waves finish: a thread adds its terms in index order (the two-sample form keeps one sum per sample of the pair and adds the
+// second to the first, then the odd last sample, which the grid's first thread takes), the lanes of a wave combine by shuffles
+// at distances 32 .. 1, thread 0 adds the waves' sums in wave order, the final block's thread t adds the partials t, t + 256,
+// .. in that order and reduces the same way.  No atomics.
+// Accuracy.  Every term is >= 0, so a sum that passes through k roundings lies within k u / (1 - k u) of the real sum of the
+// same q, u = 2^-53.  The grid is at most WR_MASK_BLOCKS x WR_MASK_THREADS = 2^19 threads and covers ceil(n / 512) blocks'
+// worth of samples before it wraps: a thread of the element-wise form adds at most ceil(n / 2^19) terms (2^14 at n = 2^33), a
+// sum of the two-sample form ceil(n / 2^20) and one addition joins the two, one more takes the odd sample; then 6 shuffle
+// steps, 3 waves, and in the final block at most 8 partials, 6 steps, 3 waves: k <= 2^14 + 27, |S_D - S_D*| < 2^-38 S_D* for
+// every n <= 2^33.  A mask only removes terms.
+// partial[4b .. 4b + 3] = block b's maximum, count, sum and (as an unsigned 64-bit integer) compared samples.
+template <typename T> struct CmpPair;
+template <> struct CmpPair<double> { using type = double2; };
+template <> struct CmpPair<float> { using type = float2; };
+
+__device__ inline void cmp_acc(double a, double b, double& mx, double& cnt, double& s)  // (err_stats_acc, wr_kernels.hip)
+{
+    const double d = a - b, m = fabs(d);
+    if (m <= DBL_MAX) { mx = fmax(mx, m); s = s + d * d; }
+    else cnt += 1.0;
+}
+
+// mask_word of chunk ch with the bits of the samples at and beyond n set
+__device__ inline unsigned long long cmp_word(const uint8_t* __restrict__ bits, size_t nbytes, size_t n, size_t ch, bool wide)
+{
+    const size_t base = ch << 6;
+    if (base >= n) return ~0ull;
+    unsigned long long m = mask_word(bits, nbytes, ch, wide);
+    if (n - base < 64) m |= ~0ull << (n - base);
+    return m;
+}
+
+// def: the caller's share of the compared samples (summed over the block's threads)
+__device__ inline void block_cmp_reduce(double mx, double cnt, double s, unsigned long long def, double* __restrict__ out,
+                                        unsigned long long* __restrict__ out_def)
+{
+    for (int o = 32; o > 0; o >>= 1) {
+        mx = fmax(mx, __shfl_down(mx, o, 64));
+        cnt += __shfl_down(cnt, o, 64);
+        s = s + __shfl_down(s, o, 64);
+        def += __shfl_down(def, o, 64);
+    }
+    __shared__ double smx[WR_MASK_WAVES], scn[WR_MASK_WAVES], ssq[WR_MASK_WAVES];
+    __shared__ unsigned long long sdf[WR_MASK_WAVES];
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { smx[w] = mx; scn[w] = cnt; ssq[w] = s; sdf[w] = def; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < WR_MASK_WAVES; i++) { mx = fmax(mx, smx[i]); cnt += scn[i]; s = s + ssq[i]; def += sdf[i]; }
+        out[0] = mx;
+        out[1] = cnt;
+        out[2] = s;
+        *out_def = def;
+    }
+}
+
+// wide: `bits` is 8-byte aligned
+template <typename T, bool PAIRS>
+__global__ __launch_bounds__(WR_MASK_THREADS) void k_err_stats_masked(const T* __restrict__ a, const T* __restrict__ b, size_t n,
+                                                                        const uint8_t* __restrict__ bits, bool wide, double* __restrict__ partial)
+{
+    double mx = 0.0, cnt = 0.0, s = 0.0;
+    unsigned long long def = 0;  // (of the wave: every lane holds the same value)
+    const uint32_t lane = threadIdx.x & 63;
+    const size_t wave = (size_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * WR_MASK_WAVES + (threadIdx.x >> 6)));
+    const size_t nwaves = (size_t)gridDim.x * WR_MASK_WAVES, nbytes = (n + 7) >> 3;
+    if (PAIRS) {
+        double s1 = 0.0;
+        const size_t n2 = n >> 1, nturn = (n + 127) >> 7;
+        const typename CmpPair<T>::type* a2 = reinterpret_cast<const typename CmpPair<T>::type*>(a);
+        const typename CmpPair<T>::type* b2 = reinterpret_cast<const typename CmpPair<T>::type*>(b);
+        for (size_t t = wave; t < nturn; t += nwaves) {
+            const unsigned long long m0 = cmp_word(bits, nbytes, n, 2 * t, wide), m1 = cmp_word(bits, nbytes, n, 2 * t + 1, wide);
+            def += (unsigned long long)(__popcll(~m0) + __popcll(~m1));
+            if ((m0 & m1) == ~0ull) continue;  // (the whole wave: the words are the same in every lane)
+            const size_t i = (t << 6) + lane;  // the lane's pair
+            const uint32_t und = (uint32_t)((lane < 32 ? m0 >> (2 * lane) : m1 >> (2 * (lane - 32))) & 3);
+            if (i < n2 && und != 3) {
+                // one load per array for the pair.  The undefined sample of a half-defined pair goes in as 0 - 0: the maximum and
+                // the count do not move and s + 0 is s, bit for bit, so the sum is the one of the defined samples in index
+                // order.  (Selects, not branches: with a branch per sample the compiler sinks the loads into the branches
+                // and splits each 16-byte load into two of 8.)
+                const typename CmpPair<T>::type va = a2[i], vb = b2[i];
+                const bool ux = und & 1, uy = und & 2;
+                cmp_acc(ux ? 0.0 : (double)va.x, ux ? 0.0 : (double)vb.x, mx, cnt, s);
+                cmp_acc(uy ? 0.0 : (double)va.y, uy ? 0.0 : (double)vb.y, mx, cnt, s1);
+            }
+        }
+        s = s + s1;
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0 && !((bits[(n - 1) >> 3] >> ((n - 1) & 7)) & 1))
+            cmp_acc((double)a[n - 1], (double)b[n - 1], mx, cnt, s);
+    } else {
+        const size_t nchunk = (n + 63) >> 6;
+        for (size_t ch = wave; ch < nchunk; ch += nwaves) {
+            const unsigned long long m = cmp_word(bits, nbytes, n, ch, wide);
+            def += (unsigned long long)__popcll(~m);
+            if (m == ~0ull) continue;  // (the whole wave)
+            const size_t i = (ch << 6) + lane;
+            if (!((m >> lane) & 1)) cmp_acc((double)a[i], (double)b[i], mx, cnt, s);  // (a clear bit: i < n)
+        }
+    }
+    block_cmp_reduce(mx, cnt, s, lane == 0 ? def : 0ull, partial + 4 * blockIdx.x,
+                     reinterpret_cast<unsigned long long*>(partial) + 4 * blockIdx.x + 3);
+}
+
+__global__ __launch_bounds__(WR_MASK_THREADS) void k_err_stats_masked_final(const double* __restrict__ partial, int np, double* __restrict__ result,
+                                                                              unsigned long long* __restrict__ defined)
+{
+    double mx = 0.0, cnt = 0.0, s = 0.0;
+    unsigned long long def = 0;
+    for (int i = threadIdx.x; i < np; i += blockDim.x) {
+        mx = fmax(mx, partial[4 * i]);
+        cnt += partial[4 * i + 1];
+        s = s + partial[4 * i + 2];
+        def += reinterpret_cast<const unsigned long long*>(partial)[4 * i + 3];
+    }
+    block_cmp_reduce(mx, cnt, s, def, result, defined);  // single block: lands in result[0 .. 2] and *defined
+}
+
+template <typename T>
+static void err_stats_masked_t(const T* a, const T* b, size_t n, const uint8_t* bits, double* partial, double* result, unsigned long long* defined,
+                               hipStream_t st)
+{
+    const bool pairs = (((uintptr_t)a | (uintptr_t)b) & (2 * sizeof(T) - 1)) == 0, wide = ((uintptr_t)bits & 7) == 0;
+    size_t g = (n + 2 * WR_MASK_THREADS - 1) / (2 * WR_MASK_THREADS);  // (the grid of k_err_stats)
+    if (g < 1) g = 1;
+    if (g > WR_MASK_BLOCKS) g = WR_MASK_BLOCKS;
+    if (pairs) hipLaunchKernelGGL((k_err_stats_masked<T, true>), dim3((unsigned)g), dim3(WR_MASK_THREADS), 0, st, a, b, n, bits, wide, partial);
+    else hipLaunchKernelGGL((k_err_stats_masked<T, false>), dim3((unsigned)g), dim3(WR_MASK_THREADS), 0, st, a, b, n, bits, wide, partial);
+    hipLaunchKernelGGL(k_err_stats_masked_final, dim3(1), dim3(WR_MASK_THREADS), 0, st, partial, (int)g, result, defined);
+}
+void err_stats_masked(const double* a, const double* b, size_t n, const uint8_t* bits, double* partial, double* result, unsigned long long* defined,
+                      hipStream_t st)
+{
+    err_stats_masked_t(a, b, n, bits, partial, result, defined, st);
+}
+void err_stats_masked(const float* a, const float* b, size_t n, const uint8_t* bits, double* partial, double* result, unsigned long long* defined,
+                      hipStream_t st)
+{
+    err_stats_masked_t(a, b, n, bits, partial, result, defined, st);
+}
+
 }  // namespace wrk

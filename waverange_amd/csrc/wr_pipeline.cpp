@@ -886,9 +886,9 @@ static int ctx_init(wr_ctx* c, int device, void* hip_stream)
     }
     if (hip_stream) c->stream = (hipStream_t)hip_stream;
     else { HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
-    HIPCHK(hipMalloc(&c->d_partial, 3 * wrk::minmax_partials() * sizeof(double)));  // (three per block: wrk::err_stats; two everywhere else)
+    HIPCHK(hipMalloc(&c->d_partial, 4 * wrk::minmax_partials() * sizeof(double)));  // (four per block: wrk::err_stats_masked; three: wrk::err_stats; two everywhere else)
     HIPCHK(hipMalloc(&c->d_idx, sizeof(unsigned long long)));
-    HIPCHK(hipHostMalloc(&c->h_result, (8 + 2 * WR_NLAYMAX + wrk::kProbeK + 5 + 2) * sizeof(double), hipHostMallocDefault));  // ([8 + 2l ..]: plane l's segmented-coder result; then the size probe's totals; then a bounded encode's compare; then a quality encode's; then a masked encode's mask coder's result)
+    HIPCHK(hipHostMalloc(&c->h_result, (8 + 2 * WR_NLAYMAX + wrk::kProbeK + 5 + 2 + 1) * sizeof(double), hipHostMallocDefault));  // ([8 + 2l ..]: plane l's segmented-coder result; then the size probe's totals; then a bounded encode's compare; then a quality encode's; then a masked encode's mask coder's result; then the masked compare's count of compared samples)
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_result_dev), c->h_result, 0));
     for (int i = 0; i < WR_NLAYMAX; i++) {
         HIPCHK(hipEventCreateWithFlags(&c->ev_plane[i], hipEventDisableTiming));
