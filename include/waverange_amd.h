@@ -1254,6 +1254,69 @@ int wr_decode_device_seg_roi_batch(wr_ctx *ctx, double *d_out, int nfields, int 
                                    int max_planes, const wr_box *rois, int nroi, const wr_enc_info *infos,
                                    const unsigned char *const *data_encs, const size_t *data_lens, wr_timings *tm);
 
+/* ---- Masked region decode across a batch of fields: the call above on records that wr_encode_*_seg_masked wrote, the
+ * undefined samples of every region coming back as `fill`.  No new format and no new error code.  Arguments and output layout
+ * are those of wr_decode_host_seg_roi_batch; data_lens[f] is the length of field f's planes PLUS its mask blob, as for
+ * wr_decode_host_seg_roi_masked, and data_lens[f] == infos[f].ntot_enc (or 0) marks an unmasked record.  Masked and unmasked
+ * records, WRS1 / WRS2 / WRS3 field parts and constant fields may be mixed; nfields = 1 is the masked many-region call.
+ *   Region i of field f is bit for bit what wr_decode_host_seg_roi_masked (_f32, the device form) returns for rois[i] of that
+ *   record alone with the same level, max_planes and fill ((float)fill for fp32 output; a NaN fill is allowed); for an
+ *   unmasked record it is the plain batch call's, and res[f] is zeroed.  A constant padded field with a blob (nlay == 0, the
+ *   blob at data_encs[f]) gives midval with fill restored, for a host caller too.
+ * Coder launches.  A masked field adds ONE job to the call's WRS1 / WRS2 launch, whatever the format of its field part: its
+ * blob, a plane of ceil(n / 8) symbols cut at the seg of the blob's own header, with the ascending union over the regions of
+ * wr_mask_roi_segments listed (wr_mask_roi_segments_multi).  The call still makes at most two launches (a batch of WRS3 fields
+ * with masks makes two: strands and masks) and nothing runs on a second stream.  Then the window stage as above, and ONE
+ * launch of k_mask_restore_boxes (csrc/wr_mask.hip) over every (masked field, region) box of the output buffer.
+ * res (nfields records, may be NULL): undefined = the set bits among field f's regions, summed over the regions (a sample in
+ * two overlapping regions counts twice: the sum of the single calls' values); pad and mask_len as in the full masked decode;
+ * fill_ms the call's one restore launch (HIP events; the same value in every masked record); mask_coder_ms and split_ms 0: the
+ * mask jobs ride in the fields' launch and their time is in tm->rangecoder.
+ * Validation, all of it before anything is copied or launched: every field's region plans ("field <f>: region <i>: "), every
+ * field's stream, every plane's header and index, then every blob's header and whole segment index as the single masked call
+ * validates them ("field <f>: mask blob: ...", WR_ERR_STREAM).  WR_ERR_ARG: more than WR_SEG_BATCH_MAX jobs, mask jobs
+ * counted; a coder launch of 2^31 lanes or more; a restore launch of 2^31 turns or more.  After the launch a listed segment of
+ * a field part ("field <f>: plane <l>: ") or of a mask ("field <f>: mask blob: ") that did not decode is WR_ERR_STREAM before
+ * any dequantiser runs, the caller's output untouched.  As in the single call, the population count against the header and the
+ * unused high bits of the last symbol are not checked, and damage in an unlisted mask segment does not fail the call.
+ * WR_STAT_MASK_ROI_SEGMENTS moves by the listed mask segments summed over the fields, WR_STAT_MASK_ROI_BYTES_UP by their
+ * stream bytes; WR_STAT_ROI_SEGMENTS / _BYTES_UP count the field parts only; WR_STAT_ROI_CODER_LAUNCHES moves by 0, 1 or 2.
+ * wr_seg_roi_batch_device_bytes_masked: wr_seg_roi_batch_device_bytes plus, per masked field, a job on ceil(n / 8) symbols (the
+ * plane at its pitch, the blob at wr_mask_bound(n, mask_seg), the job's offsets, flags and list) and once the restore's table
+ * (sized for WR_ROI_MULTI_MAX regions); 0 for a refused argument, also nmasked outside 0..nfields and nfields * planes +
+ * nmasked above WR_SEG_BATCH_MAX; with nmasked == 0 it is the plain function.  An upper bound of what the driver takes from the
+ * plane pool, which allocates by the same arithmetic.
+ * wr_mask_roi_segments_multi (host only): the ascending union of wr_mask_roi_segments over the regions, with its conventions.
+ * wr_mask_boxes_turns (host only): the turns of the restore launch for one field's regions -- a turn is 64 consecutive x of one
+ * region row, region i has ceil(cx / 64) * cy * cz --, first[0 .. nroi] (may be NULL) their exclusive prefix; 0 for an argument
+ * that wr_roi_multi_elems refuses and for 2^31 turns or more.
+ * wr_dev_mask_restore_boxes (stage level; device pointers of any alignment): wr_dev_mask_restore_box on d_out + f * T + offs[i]
+ * for every f with d_bits[f] != NULL (a HOST array of nfields device pointers) and every i, in one launch; a field without a
+ * plane is left untouched and its count is 0.  undefined: nfields counts, may be NULL. */
+size_t wr_seg_roi_batch_device_bytes_masked(int nfields, int nmasked, size_t n, int planes, unsigned seg, unsigned brick,
+                                            unsigned strands, unsigned mask_seg, size_t out_elems);
+size_t wr_mask_roi_segments_multi(int nx, int ny, int nz, int level, const wr_box *rois, int nroi, unsigned seg,
+                                  uint32_t *ids, size_t cap);
+size_t wr_mask_boxes_turns(int nx, int ny, int nz, int level, const wr_box *rois, int nroi, uint32_t *first);
+int wr_dev_mask_restore_boxes(wr_ctx *ctx, double *d_out, int nfields, int nx, int ny, int nz, int level,
+                              const wr_box *rois, int nroi, const unsigned char *const *d_bits, double fill,
+                              unsigned long long *undefined);
+int wr_dev_mask_restore_boxes_f32(wr_ctx *ctx, float *d_out, int nfields, int nx, int ny, int nz, int level,
+                                  const wr_box *rois, int nroi, const unsigned char *const *d_bits, double fill,
+                                  unsigned long long *undefined);
+int wr_decode_host_seg_roi_batch_masked(wr_ctx *ctx, double *h_out, int nfields, int nx, int ny, int nz, int level,
+                                        int max_planes, const wr_box *rois, int nroi, const wr_enc_info *infos,
+                                        const unsigned char *const *data_encs, const size_t *data_lens, double fill,
+                                        wr_timings *tm, wr_mask_result *res);
+int wr_decode_host_seg_roi_batch_masked_f32(wr_ctx *ctx, float *h_out, int nfields, int nx, int ny, int nz, int level,
+                                            int max_planes, const wr_box *rois, int nroi, const wr_enc_info *infos,
+                                            const unsigned char *const *data_encs, const size_t *data_lens, double fill,
+                                            wr_timings *tm, wr_mask_result *res);
+int wr_decode_device_seg_roi_batch_masked(wr_ctx *ctx, double *d_out, int nfields, int nx, int ny, int nz, int level,
+                                          int max_planes, const wr_box *rois, int nroi, const wr_enc_info *infos,
+                                          const unsigned char *const *data_encs, const size_t *data_lens, double fill,
+                                          wr_timings *tm, wr_mask_result *res);
+
 /* ---- The stream format of the drop-in symbols: which of the four formats the implicit-context ENCODERS write.
  * encoding_wrap, encoding_wrap_f and wr_encoding_wrap_f32 write the reference's stream unless this process-wide setting says
  * otherwise; then they run wr_encode_host_seg / _seg_blocked / _seg_strands (the _f32 forms) with the setting's parameters.

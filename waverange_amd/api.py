@@ -403,6 +403,18 @@ def lib():
                                                C.POINTER(Timings)]
     L.wr_decode_host_seg_roi_batch_f32.argtypes = L.wr_decode_host_seg_roi_batch.argtypes
     L.wr_decode_device_seg_roi_batch.argtypes = L.wr_decode_host_seg_roi_batch.argtypes
+    # masked region decode across a batch of fields
+    L.wr_decode_host_seg_roi_batch_masked.argtypes = L.wr_decode_host_seg_roi_batch.argtypes[:13] + [C.c_double, C.POINTER(Timings), _vp]
+    L.wr_decode_host_seg_roi_batch_masked_f32.argtypes = L.wr_decode_host_seg_roi_batch_masked.argtypes
+    L.wr_decode_device_seg_roi_batch_masked.argtypes = L.wr_decode_host_seg_roi_batch_masked.argtypes
+    L.wr_seg_roi_batch_device_bytes_masked.restype = C.c_size_t
+    L.wr_seg_roi_batch_device_bytes_masked.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_size_t]
+    L.wr_mask_roi_segments_multi.restype = C.c_size_t
+    L.wr_mask_roi_segments_multi.argtypes = [C.c_int] * 4 + [_vp, C.c_int, C.c_uint, _vp, C.c_size_t]
+    L.wr_mask_boxes_turns.restype = C.c_size_t
+    L.wr_mask_boxes_turns.argtypes = [C.c_int] * 4 + [_vp, C.c_int, _vp]
+    L.wr_dev_mask_restore_boxes.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_double, _vp]
+    L.wr_dev_mask_restore_boxes_f32.argtypes = L.wr_dev_mask_restore_boxes.argtypes
     L.wr_fused_plan.argtypes = [C.c_int] * 4 + [C.POINTER(FusedPlan)]
     L.wr_bench_transform.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]
     # drop-in symbols (reference src/core/wrappers.h:53,70,75)
@@ -1048,6 +1060,62 @@ def roi_batch_groups(nfields, n, planes, budget, seg=0, brick=0, strands=0, out_
             if not size or size > budget:  # (0: the jobs exceed SEG_BATCH_MAX, or an argument no group size mends)
                 break
             b, most = b + 1, m
+        if b == a:
+            alone.append(a)
+            b = a + 1
+        groups.append(range(a, b))
+        a = b
+    return groups, alone
+
+
+def mask_roi_segments_multi(shape, level, rois, seg=0):
+    """Ascending ids (uint32) of the segments of the MASK plane, cut at `seg` symbols, that hold a bit of any of the regions:
+    the union of mask_roi_segments over `rois` (wr_mask_roi_segments_multi); host only.  A refused argument raises."""
+    nz, ny, nx = shape
+    arr = _boxes(rois)
+    count = lib().wr_mask_roi_segments_multi(nx, ny, nz, level, arr, len(rois), seg, None, 0)
+    if not count:
+        raise WaveRangeError(lib().wr_last_error().decode())
+    ids = np.empty(count, dtype=np.uint32)
+    got = lib().wr_mask_roi_segments_multi(nx, ny, nz, level, arr, len(rois), seg, ids.ctypes.data, ids.size)
+    assert got == count
+    return ids
+
+
+def mask_boxes_turns(shape, level, rois):
+    """(turns, first) of the restore launch of the masked batch call for ONE field's regions (wr_mask_boxes_turns): a turn is
+    64 consecutive x of one region row; first (uint32, len(rois) + 1) is the exclusive prefix of the regions' turns.  A
+    refused argument raises."""
+    nz, ny, nx = shape
+    first = np.zeros(len(rois) + 1, dtype=np.uint32)
+    turns = int(lib().wr_mask_boxes_turns(nx, ny, nz, level, _boxes(rois), len(rois), first.ctypes.data))
+    if not turns:
+        raise WaveRangeError(lib().wr_last_error().decode())
+    return turns, first
+
+
+def seg_roi_batch_device_bytes_masked(nfields, nmasked, n, planes, seg=0, brick=0, strands=0, mask_seg=0, out_elems=0):
+    """seg_roi_batch_device_bytes for a call of which `nmasked` fields carry a mask blob cut at mask_seg
+    (wr_seg_roi_batch_device_bytes_masked); 0 for a refused argument."""
+    return int(lib().wr_seg_roi_batch_device_bytes_masked(nfields, nmasked, n, planes, seg, brick, strands, mask_seg, out_elems))
+
+
+def roi_batch_groups_masked(nfields, n, planes, budget, masked=True, seg=0, brick=0, strands=0, mask_seg=0, out_elems=0):
+    """roi_batch_groups for Context.decode_host_seg_rois_batch_masked: the groups are cut by
+    seg_roi_batch_device_bytes_masked.  masked: whether a field carries a mask blob, one flag or one per field."""
+    pl = [int(planes)] * nfields if np.isscalar(planes) else [int(p) for p in planes]
+    mk = [bool(masked)] * nfields if np.isscalar(masked) else [bool(m) for m in masked]
+    assert len(pl) == nfields and len(mk) == nfields
+    groups, alone = [], []
+    a = 0
+    while a < nfields:
+        b, most, nm = a, 0, 0
+        while b < nfields:
+            m, k = max(most, pl[b]), nm + mk[b]
+            size = seg_roi_batch_device_bytes_masked(b + 1 - a, k, n, m, seg, brick, strands, mask_seg, out_elems)
+            if not size or size > budget:
+                break
+            b, most, nm = b + 1, m, k
         if b == a:
             alone.append(a)
             b = a + 1
@@ -2162,6 +2230,65 @@ class Context:
         """decode_host_seg_rois_batch into device memory: `buf` holds len(encs) * roi_multi_offsets(...)[-1] float64 elements,
         region i of field f at element f * T + offset [i].  Returns the timings."""
         return self._decode_seg_rois_batch(lib().wr_decode_device_seg_roi_batch, buf.ptr, shape, level, rois, encs, max_planes)
+
+    # ---- masked region decode across a batch of fields: enc["data"] is a record's planes and, behind them, its mask blob
+    def _decode_seg_rois_batch_masked(self, fn, ptr, shape, level, rois, encs, fill, max_planes):
+        nz, ny, nx = shape
+        nf = len(encs)
+        infos = (EncInfo * max(nf, 1))(*[EncInfo.from_dict(e) for e in encs])
+        datas = [np.ascontiguousarray(e["data"], dtype=np.uint8) for e in encs]
+        keep = [d if d.size else np.zeros(1, dtype=np.uint8) for d in datas]
+        ptrs = (C.c_void_p * max(nf, 1))(*[d.ctypes.data for d in keep])
+        lens = (C.c_size_t * max(nf, 1))(*[d.size for d in datas])
+        tm = Timings()
+        res = (MaskResult * max(nf, 1))()
+        _check(fn(self.h, ptr, nf, nx, ny, nz, level, max_planes, _boxes(rois), len(rois), infos, ptrs, lens, float(fill), C.byref(tm), res))
+        return [res[f].as_dict() for f in range(nf)], tm.as_dict()
+
+    def decode_host_seg_rois_batch_masked(self, shape, level, rois, encs, fill=np.nan, max_planes=0, dtype=np.float64, timings=None, out=None, masks=None):
+        """decode_host_seg_rois_batch on records that may carry a mask blob: region i of field f is bit for bit what
+        decode_host_seg_roi_masked gives for rois[i] of that record alone, `fill` where the coarse mask says undefined; the
+        masks ride in the call's coder launches and one launch restores every region of every field
+        (wr_decode_host_seg_roi_batch_masked, _f32).  masks: a list that receives one wr_mask_result dict per field."""
+        dt = self._mask_dtype("decode_host_seg_rois_batch_masked", dtype)
+        try:
+            offs = roi_multi_offsets(shape, level, rois)
+        except WaveRangeError as e:
+            raise WaveRangeError("libwaverange_amd error -1: %s" % e) from None
+        T = int(offs[-1])
+        if out is None:
+            out = np.empty(max(len(encs), 1) * T, dtype=dt)
+        assert out.dtype == dt and out.size >= len(encs) * T and out.flags.c_contiguous
+        fn = lib().wr_decode_host_seg_roi_batch_masked if dt == np.dtype(np.float64) else lib().wr_decode_host_seg_roi_batch_masked_f32
+        res, tm = self._decode_seg_rois_batch_masked(fn, out.ctypes.data, shape, level, rois, encs, fill, max_planes)
+        if timings is not None:
+            timings.update(tm)
+        if masks is not None:
+            masks[:] = res
+        flat = out.reshape(-1)
+        return [[flat[f * T + offs[i]:f * T + offs[i + 1]].reshape(roi_shape(r)) for i, r in enumerate(rois)] for f in range(len(encs))]
+
+    def decode_host_seg_rois_batch_masked_f32(self, shape, level, rois, encs, fill=np.nan, max_planes=0, timings=None, out=None, masks=None):
+        return self.decode_host_seg_rois_batch_masked(shape, level, rois, encs, fill, max_planes, np.float32, timings, out, masks)
+
+    def decode_seg_rois_batch_masked(self, buf, shape, level, rois, encs, fill=np.nan, max_planes=0):
+        """decode_host_seg_rois_batch_masked into device memory (float64, the layout of decode_seg_rois_batch).  Returns
+        (masks, timings)."""
+        return self._decode_seg_rois_batch_masked(lib().wr_decode_device_seg_roi_batch_masked, buf.ptr, shape, level, rois, encs, fill, max_planes)
+
+    def mask_restore_boxes(self, buf, nfields, shape, level, rois, bits, fill=np.nan, dtype=np.float64, offset=0, bits_offset=0, byte_offset=0):
+        """Stage level: `fill` into every region of every field that has a mask plane, in one launch.  `buf` holds nfields
+        parts of T = roi_multi_offsets(...)[-1] elements from ELEMENT `offset` behind BYTE byte_offset (the pointers may have
+        any alignment); bits[f] is field f's mask plane (a device buffer, read from byte bits_offset) or None.  Returns the
+        per-field counts (wr_dev_mask_restore_boxes, _f32)."""
+        dt = self._mask_dtype("mask_restore_boxes", dtype)
+        fn = lib().wr_dev_mask_restore_boxes if dt == np.float64 else lib().wr_dev_mask_restore_boxes_f32
+        nz, ny, nx = shape
+        assert len(bits) == nfields
+        ptrs = (C.c_void_p * max(nfields, 1))(*[None if b is None else b.ptr + bits_offset for b in bits])
+        counts = (C.c_ulonglong * max(nfields, 1))()
+        _check(fn(self.h, buf.ptr + byte_offset + offset * dt.itemsize, nfields, nx, ny, nz, level, _boxes(rois), len(rois), ptrs, float(fill), counts))
+        return [int(counts[f]) for f in range(nfields)]
 
     def seg_encode_plane(self, plane, seg=0, strands=None):
         """Stage level: one plane of symbols (a numpy uint8 array) through the coder kernels; returns the blob (WRS1, or with

@@ -14,7 +14,12 @@
 //   --level=R               the low-pass box of level R (0..4, default 0: the field's own resolution)
 //   --roi=x0:x1,y0:y1,z0:z1 a half-open box in the coordinates of the box of level R, in the order NX NY NZ (default: all of it)
 //   --planes=P              the first P quantizer planes only (default 0: all)
-// With any of them OUT.grd holds that region of every time record; a bit-mask record and its field go through
+//   --batch=N               with one of the three above: up to N consecutive time records go through ONE call of
+//                           wr_decode_host_seg_roi_batch_masked (at most two coder launches and one restore launch for all of
+//                           them, masked or not); groups are cut further so that wr_seg_roi_batch_device_bytes_masked fits the
+//                           device's free memory.  Default 1: a call per record.  OUT.grd is byte for byte the same; the records
+//                           of a call that failed go the --batch=1 way, with its messages.
+// With any of the first three OUT.grd holds that region of every time record; a bit-mask record and its field go through
 // wr_decode_host_seg_roi_masked (undefined points: the control file's `undef`), an unmasked record through the plain region /
 // low-resolution call.  The control file is not copied (its extents would be wrong): the region's extents are printed.  The
 // run is refused with status 2, nothing written, for TYPE 1 / 2, for a record in the reference's stream format, for a mask
@@ -43,8 +48,8 @@ struct Params {
     int filetype = 0, outtype = 1, flip = 0, proc = 0;
 };
 
-struct Partial {  // --level, --roi, --planes
-    int level = 0, planes = 0;
+struct Partial {  // --level, --roi, --planes, --batch
+    int level = 0, planes = 0, batch = 1;
     bool have_roi = false;
     wr_box roi{0, 0, 0, 0, 0, 0};
 };
@@ -250,8 +255,9 @@ int regular_output_region(const Params& p, int nbytes, const Partial& pd)
     open_or_die(payload, p.in_prefix + "_f" + p.ext, std::ios::in | std::ios::binary);
     std::string line;
     // first the whole set's records are looked at, then the first byte is written
-    struct Record { Coding c; size_t mask_len; };
+    struct Record { Coding c; size_t mask_len; std::streamoff at; };  // at: where its bytes start in the payload (the blob, then the planes)
     std::vector<Record> recs;
+    std::streamoff at = 0;
     for (int j = 0; j < 8; j++) std::getline(header, line);  // the preamble written by the encoder
     auto starts_with = [&](unsigned long len, unsigned char* head4) {
         memset(head4, 0, 4);
@@ -275,6 +281,8 @@ int regular_output_region(const Params& p, int nbytes, const Partial& pd)
             refuse("time record " + std::to_string(it + 1) + ": --level / --roi / --planes need a segmented stream format (WR_STREAM_FORMAT=wrs1, wrs2 or wrs3 when encoding)");
         if (pd.planes > (int)r.c.nlay) refuse("--planes exceeds the planes of time record " + std::to_string(it + 1));
         if (pd.level > (int)r.c.wlev) refuse("--level exceeds the transform depth of time record " + std::to_string(it + 1));
+        r.at = at;
+        at += (std::streamoff)(r.mask_len + r.c.ntot_enc);
         recs.push_back(r);
     }
     payload.clear();
@@ -286,29 +294,111 @@ int regular_output_region(const Params& p, int nbytes, const Partial& pd)
     if (const char* e = getenv("WR_DEVICE")) dev = atoi(e);
     wr_ctx* ctx = nullptr;
     if (wr_ctx_create(&ctx, dev, nullptr) != 0) { std::cout << "Error: " << wr_last_error() << std::endl; std::exit(1); }
-    std::vector<double> out((size_t)cx * cy * cz);
+    const size_t count = (size_t)cx * cy * cz;
+    std::vector<double> out(count);
     std::vector<unsigned char> buf;
-    int rc = 0;
-    for (int it = 0; it < g.nt && rc == 0; it++) {
+    // the planes in front of the blob, as the masked calls read them; in the payload the blob comes first
+    auto load = [&](const Record& r, std::vector<unsigned char>& to) {
+        to.resize(r.c.ntot_enc + r.mask_len + 1);
+        payload.clear();
+        payload.seekg(r.at, std::ios::beg);
+        payload.read(reinterpret_cast<char*>(to.data() + r.c.ntot_enc), (std::streamsize)r.mask_len);
+        payload.read(reinterpret_cast<char*>(to.data()), (std::streamsize)r.c.ntot_enc);
+    };
+    auto wrote = [&](int it, const double* v) {
+        write_field(out_name, p.flip != 0, nbytes, it, cx, cy, cz, cx, cy, 0, 0, v);
+        std::cout << "  wrote: fld_1d_rec[0]=" << v[0] << " fld_1d_rec[last]=" << v[count - 1] << std::endl;
+    };
+    // a record through a call of its own (--batch=1, and the records of a batch call that failed)
+    auto decode_one = [&](int it, const std::vector<unsigned char>& data) {
         const Record& r = recs[(size_t)it];
         const wr_enc_info info = info_of(r.c);
-        // the planes in front of the blob, as the masked call reads them; in the payload the blob comes first
-        buf.resize(r.c.ntot_enc + r.mask_len + 1);
-        payload.read(reinterpret_cast<char*>(buf.data() + r.c.ntot_enc), (std::streamsize)r.mask_len);
-        payload.read(reinterpret_cast<char*>(buf.data()), (std::streamsize)r.c.ntot_enc);
         const wr_box* box = pd.have_roi ? &roi : nullptr;
+        int rc;
         if (r.mask_len) {
             std::cout << "  decoding mask bits and fld_1d_rec, it=" << it << std::endl;
-            rc = wr_decode_host_seg_roi_masked(ctx, out.data(), g.nx, g.ny, g.nz, pd.level, pd.planes, box, &info, buf.data(), r.c.ntot_enc + r.mask_len,
+            rc = wr_decode_host_seg_roi_masked(ctx, out.data(), g.nx, g.ny, g.nz, pd.level, pd.planes, box, &info, data.data(), r.c.ntot_enc + r.mask_len,
                                                g.undef, nullptr, nullptr);
         } else {
             std::cout << "  decoding fld_1d_rec, it=" << it << std::endl;
-            rc = box ? wr_decode_host_seg_roi(ctx, out.data(), g.nx, g.ny, g.nz, pd.level, pd.planes, box, &info, buf.data(), r.c.ntot_enc, nullptr)
-                     : wr_decode_host_seg_lowres(ctx, out.data(), g.nx, g.ny, g.nz, pd.level, pd.planes, &info, buf.data(), r.c.ntot_enc, nullptr);
+            rc = box ? wr_decode_host_seg_roi(ctx, out.data(), g.nx, g.ny, g.nz, pd.level, pd.planes, box, &info, data.data(), r.c.ntot_enc, nullptr)
+                     : wr_decode_host_seg_lowres(ctx, out.data(), g.nx, g.ny, g.nz, pd.level, pd.planes, &info, data.data(), r.c.ntot_enc, nullptr);
         }
-        if (rc != 0) { std::cout << "Error: " << wr_last_error() << std::endl; break; }
-        write_field(out_name, p.flip != 0, nbytes, it, cx, cy, cz, cx, cy, 0, 0, out.data());
-        std::cout << "  wrote: fld_1d_rec[0]=" << out[0] << " fld_1d_rec[last]=" << out[out.size() - 1] << std::endl;
+        if (rc != 0) { std::cout << "Error: " << wr_last_error() << std::endl; return rc; }
+        wrote(it, out.data());
+        return 0;
+    };
+    int rc = 0;
+    if (pd.batch <= 1) {
+        for (int it = 0; it < g.nt && rc == 0; it++) {
+            load(recs[(size_t)it], buf);
+            rc = decode_one(it, buf);
+        }
+        wr_ctx_destroy(ctx);
+        return rc ? 1 : 0;
+    }
+    // ---- --batch=N: up to N consecutive records per call, cut further by the device's free memory and the job limit
+    const size_t n = (size_t)g.nx * g.ny * g.nz;
+    // what a record's call takes, by the headers of its used planes (magic, seg, nseg, then brick in a WRS2 / WRS3 header and
+    // strands in a WRS3 one) and of its blob's plane; the library validates them, here they only size a call
+    auto size_of = [&](const Record& r, const std::vector<unsigned char>& data, int* jobs) {
+        const int used = r.c.ntot_enc ? (pd.planes ? pd.planes : (int)r.c.nlay) : 0;  // (a constant field has no job)
+        unsigned seg = 0, brick = 0, strands = 0, mask_seg = 0;
+        size_t off = 0;
+        for (int l = 0; l < used && l < kNlayMax; off += r.c.len_enc_vec[l], l++) {
+            if (off + 20 > r.c.ntot_enc) break;
+            uint32_t w[5];
+            memcpy(w, data.data() + off, sizeof w);
+            if (!seg || w[1] < seg) seg = w[1];
+            if (memcmp(data.data() + off, "WRS1", 4) != 0) brick = w[3];
+            if (memcmp(data.data() + off, "WRS3", 4) == 0) strands = w[4];
+        }
+        if (r.mask_len >= 32 + 12) memcpy(&mask_seg, data.data() + r.c.ntot_enc + 32 + 4, 4);
+        *jobs = used + (r.mask_len ? 1 : 0);
+        return wr_seg_roi_batch_device_bytes_masked(1, r.mask_len ? 1 : 0, n, used, seg, brick, strands, mask_seg, count);
+    };
+    std::vector<std::vector<unsigned char>> datas;
+    std::vector<double> outs;
+    int a = 0;
+    while (a < g.nt && rc == 0) {
+        const int most = a + pd.batch < g.nt ? a + pd.batch : g.nt;
+        const size_t budget = wr_ctx_device_free_bytes(ctx) / 4 * 3;
+        datas.resize((size_t)(most - a));
+        size_t need = 0, jobs = 0;
+        int b = a;
+        while (b < most) {
+            // every record is sized as a call of its own and the sum holds the tables and the output once per record: an upper
+            // bound of the group's call
+            load(recs[(size_t)b], datas[(size_t)(b - a)]);
+            int j = 0;
+            const size_t one = size_of(recs[(size_t)b], datas[(size_t)(b - a)], &j);
+            if (!one || need + one > budget || jobs + (size_t)j > WR_SEG_BATCH_MAX) break;  // (0: headers the library will refuse)
+            need += one; jobs += (size_t)j; b++;
+        }
+        bool done = false;
+        if (b - a >= 2) {
+            const size_t nf = (size_t)(b - a);
+            std::vector<wr_enc_info> infos(nf);
+            std::vector<const unsigned char*> ptrs(nf);
+            std::vector<size_t> lens(nf);
+            for (size_t f = 0; f < nf; f++) {
+                const Record& r = recs[(size_t)a + f];
+                infos[f] = info_of(r.c); ptrs[f] = datas[f].data(); lens[f] = r.c.ntot_enc + r.mask_len;
+            }
+            outs.resize(nf * count);
+            done = wr_decode_host_seg_roi_batch_masked(ctx, outs.data(), (int)nf, g.nx, g.ny, g.nz, pd.level, pd.planes, &roi, 1, infos.data(), ptrs.data(),
+                                                       lens.data(), g.undef, nullptr, nullptr) == 0;
+            for (size_t f = 0; f < nf && done; f++) {
+                const int it = a + (int)f;
+                std::cout << (recs[(size_t)it].mask_len ? "  decoding mask bits and fld_1d_rec, it=" : "  decoding fld_1d_rec, it=") << it << std::endl;
+                wrote(it, outs.data() + f * count);
+            }
+        }
+        if (!done) {
+            if (b == a) b = a + 1;  // (its bytes are in datas[0])
+            for (int it = a; it < b && rc == 0; it++) rc = decode_one(it, datas[(size_t)(it - a)]);
+        }
+        a = b;
     }
     wr_ctx_destroy(ctx);
     return rc ? 1 : 0;
@@ -386,19 +476,23 @@ int main(int argc, char** argv)
     std::vector<std::string> options;
     argc = wrcli::take_options(argc, argv, options);
     Partial pd;
-    bool partial = false;
+    bool partial = false, batch = false;
     for (const std::string& o : options) {
         std::string v;
         bool good = false;
         if (wrcli::option_value(o, "level", &v)) good = wrcli::parse_uint(v, &pd.level) && pd.level <= 4;
         else if (wrcli::option_value(o, "roi", &v)) good = pd.have_roi = wrcli::parse_roi(v, &pd.roi);
         else if (wrcli::option_value(o, "planes", &v)) good = wrcli::parse_uint(v, &pd.planes);
+        else if (wrcli::option_value(o, "batch", &v)) { good = wrcli::parse_uint(v, &pd.batch) && pd.batch >= 1; batch = true; }
         if (!good) {
-            std::cout << "options (TYPE 0, segmented stream formats): --level=R (0..4) --roi=x0:x1,y0:y1,z0:z1 --planes=P\n";
+            std::cout << "options (TYPE 0, segmented stream formats): --level=R (0..4) --roi=x0:x1,y0:y1,z0:z1 --planes=P --batch=N\n";
             refuse("bad option " + o);
         }
-        partial = true;
+        if (!wrcli::option_value(o, "batch", &v)) partial = true;
     }
+    if (batch && !partial) refuse("--batch groups the time records of a partial decode: give --level, --roi or --planes with it");
+    if (pd.batch > 1 && !(wr_decode_host_seg_roi_batch_masked && wr_seg_roi_batch_device_bytes_masked && wr_ctx_device_free_bytes))
+        refuse(std::string("--batch is ") + wrcli::kNotSupported);
     Params p;
     get_params(argc, argv, &p);
     const int nbytes = p.outtype == 1 ? 4 : 8;

@@ -101,6 +101,12 @@ int wr_decode_host_seg_roi_batch_f32(wr_ctx* ctx, float* h_out, int nfields, int
                                      const wr_enc_info* infos, const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm) __attribute__((weak));
 size_t wr_seg_roi_batch_device_bytes(int nfields, size_t n, int planes, unsigned seg, unsigned brick, unsigned strands, size_t out_elems) __attribute__((weak));
 size_t wr_ctx_device_free_bytes(wr_ctx* ctx) __attribute__((weak));
+// ... of masked records (wrdec_mssg --batch)
+int wr_decode_host_seg_roi_batch_masked(wr_ctx* ctx, double* h_out, int nfields, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                                        const wr_enc_info* infos, const unsigned char* const* data_encs, const size_t* data_lens, double fill, wr_timings* tm,
+                                        wr_mask_result* res) __attribute__((weak));
+size_t wr_seg_roi_batch_device_bytes_masked(int nfields, int nmasked, size_t n, int planes, unsigned seg, unsigned brick, unsigned strands, unsigned mask_seg,
+                                            size_t out_elems) __attribute__((weak));
 }
 
 namespace wrcli {

@@ -5128,10 +5128,40 @@ struct RoiBatchField : BatchField {  // ... of a region decode: its plans, its l
     uint8_t* perms[WR_NLAYMAX] = {nullptr};  // a WRS2 field: one stream-order plane per job (all jobs go in one launch)
     uint8_t* d_bricks = nullptr;
     int job0 = 0;  // its first job's place in the failure counts
+    // a masked record of the masked call: its blob as the host has validated it (MaskDecode::parse), the union of the mask
+    // segments the regions need, the job's buffers and its place in the failure counts
+    bool masked = false;
+    const unsigned char* mblob = nullptr;  // the WRM1 header, the WRS1 plane behind it
+    size_t mlen = 0, msym = 0;
+    unsigned long long mundefined = 0;
+    double mpad = 0;
+    uint32_t mseg = 0, mnseg = 0;
+    std::vector<uint32_t> mids;
+    uint8_t *mbits = nullptr, *md_blob = nullptr, *mwork = nullptr;
+    int mjob = 0;
+    const unsigned char* mplane() const { return mblob + wrmask::kHeaderBytes; }
+    size_t mplane_len() const { return mlen - wrmask::kHeaderBytes; }
 };
 
+// what the masked call adds (wr_decode_*_seg_roi_batch_masked)
+struct MaskBatch {
+    double fill;
+    wr_mask_result* res;  // nfields records, or nullptr
+};
+
+// what a masked field adds to the call's memory: the mask plane at its pitch (the blob and the work buffer go by
+// roi_batch_work_bytes and the blob's length), and once the restore's table
+size_t roi_batch_mask_plane_bytes(size_t n) { return batch_plane_bytes(wrmask::mask_bytes(n)); }
+size_t roi_batch_restore_bytes(size_t nroi, size_t nfields) { return wrk::mask_boxes_table_bytes(nroi, nfields); }
+
+// mb != nullptr (wr_decode_*_seg_roi_batch_masked): a record whose buffer is longer than its planes carries a mask blob.  The
+// blob is one more job of the WRS1 / WRS2 launch (a plane of ceil(n / 8) symbols, the union of wrmask::roi_segments over the
+// regions listed), judged with the field parts before any dequantiser runs; `fill` goes into every region of every such field
+// in one launch behind the window stage (k_mask_restore_boxes).  A constant field with a blob is made on the device, for a
+// host caller too, so that the restore finds it.
 int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
-                              const wr_enc_info* infos, const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm)
+                              const wr_enc_info* infos, const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm,
+                              const MaskBatch* mb = nullptr)
 {
     if (nfields < 1) return fail(WR_ERR_ARG, "nfields must be at least 1");
     if (!infos || !data_encs || !data_lens) return fail(WR_ERR_ARG, "null array");
@@ -5153,16 +5183,49 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
     for (int f = 0; f < nfields; f++)
         if (int rc = roi_multi_plans(nx, ny, nz, level, max_planes, rois, nroi, &infos[f], &bf[f].pls, &out_at)) return fail_at("field", f, rc);
     const size_t T = out_at[(size_t)nroi];  // (the regions' extents do not depend on the record)
-    size_t njobs = 0;
+    size_t njobs = 0, nmask = 0;
     for (int f = 0; f < nfields; f++) {
         RoiBatchField& b = bf[f];
-        if (int rc = seg_stream_of(nx, ny, nz, &infos[f], data_encs[f], data_lens[f], &b.s, "field " + std::to_string(f) + ": ")) return rc;
+        b.masked = mb && data_lens[f] != 0 && data_lens[f] > infos[f].ntot_enc;  // (as the single masked call tells the two apart)
+        if (int rc = seg_stream_of(nx, ny, nz, &infos[f], data_encs[f], b.masked ? infos[f].ntot_enc : data_lens[f], &b.s, "field " + std::to_string(f) + ": ")) return rc;
         if (b.s.constant) continue;
         b.used = b.pls[0].planes;
         njobs += (size_t)b.used;
     }
-    if (njobs > WR_SEG_BATCH_MAX)
-        return fail(WR_ERR_ARG, "too many jobs: the call has " + std::to_string(njobs) + " (field, plane) pairs, WR_SEG_BATCH_MAX is " + std::to_string(WR_SEG_BATCH_MAX));
+    // ---- 3. (the masked call) every blob's header and whole segment index, as the single masked region call validates them
+    std::vector<wrmask::Region> mregions;
+    if (mb) {
+        std::vector<const unsigned char*> blobs((size_t)nfields, nullptr);
+        std::vector<size_t> blens((size_t)nfields, 0);
+        std::vector<wrmask::BlobInfo> binfo((size_t)nfields);
+        for (int f = 0; f < nfields; f++) {
+            RoiBatchField& b = bf[f];
+            if (!b.masked) continue;
+            if (!data_encs[f]) return fail(WR_ERR_ARG, "field " + std::to_string(f) + ": null coded buffer");
+            blobs[f] = b.mblob = data_encs[f] + infos[f].ntot_enc;
+            blens[f] = b.mlen = data_lens[f] - infos[f].ntot_enc;
+            b.msym = wrmask::mask_bytes(n);
+            nmask++;
+        }
+        std::string why;
+        const int bad = wrmask::check_blobs(blobs.data(), blens.data(), nfields, n, binfo.data(), &why);
+        if (bad < nfields) return fail(WR_ERR_STREAM, "field " + std::to_string(bad) + ": " + why);
+        for (int f = 0; f < nfields; f++) {
+            RoiBatchField& b = bf[f];
+            b.mundefined = binfo[f].undefined; b.mpad = binfo[f].pad; b.mseg = binfo[f].seg; b.mnseg = binfo[f].nseg;
+        }
+    }
+    if (njobs + nmask > WR_SEG_BATCH_MAX)
+        return fail(WR_ERR_ARG, "too many jobs: the call has " + std::to_string(njobs) + " (field, plane) pairs" + (mb ? " and " + std::to_string(nmask) + " masks" : std::string()) +
+                                    ", WR_SEG_BATCH_MAX is " + std::to_string(WR_SEG_BATCH_MAX));
+    if (nmask) {
+        mregions.resize((size_t)nroi);
+        for (int i = 0; i < nroi; i++) mregions[i] = wrmask::Region{nx, ny, nz, level, rois[i].x0, rois[i].y0, rois[i].z0, rois[i].x1, rois[i].y1, rois[i].z1};
+        if (!wrmask::boxes_turns(mregions.data(), mregions.size(), nullptr) ||
+            (unsigned long long)nmask * wrmask::boxes_turns(mregions.data(), mregions.size(), nullptr) >= wrmask::kTurnLimit)
+            return fail(WR_ERR_ARG, "too many turns: the restore launch of the call has 2^31 or more");
+    }
+    const size_t nall = njobs + nmask;  // the jobs of the coder launches: the (field, plane) pairs and the masks
     // ---- per field the union of the bricks and, per used plane, of the segments the regions need (as the many-region call)
     size_t nplain = 0, nstranded = 0;
     unsigned long long lanes_plain = 0, lanes_stranded = 0;
@@ -5196,11 +5259,21 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
         need.scratch_elems = std::max(need.scratch_elems, nd.scratch_elems);
         need.lowbuf_elems = std::max(need.lowbuf_elems, nd.lowbuf_elems);
     }
+    // a mask is a WRS1 plane in the natural order whatever its field part is: one more job of the plain launch
+    for (int f = 0; f < nfields; f++) {
+        RoiBatchField& b = bf[f];
+        if (!b.masked) continue;
+        b.mids.resize(wrmask::roi_segments_multi(mregions.data(), mregions.size(), b.mseg, nullptr, 0));
+        wrmask::roi_segments_multi(mregions.data(), mregions.size(), b.mseg, b.mids.data(), b.mids.size());
+        lanes_plain += b.mids.size();
+        nplain++;
+    }
     if (lanes_plain >= wrsb::kLaneLimit || lanes_stranded >= wrsb::kLaneLimit) return fail(WR_ERR_ARG, "too many segments: a launch of the call has 2^31 lanes or more");
     c->pend_valid = false;
     PlaneHold planes(c);
     BatchBufs bufs(c);
-    uint8_t *d_once = nullptr, *d_host_out = nullptr;
+    uint8_t *d_once = nullptr, *d_host_out = nullptr, *d_restore = nullptr;
+    const size_t tables = roi_batch_tables_bytes(nplain, nstranded);
     {
         std::lock_guard<std::mutex> gather(pool->planes.gather_mu);  // one decode at a time gathers its planes (decode_impl)
         for (int f = 0; f < nfields; f++) {
@@ -5213,23 +5286,40 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
                 if (b.s.brick && !(b.perms[l] = bufs.take(batch_perm_bytes(n, b.s.brick)))) return fail_at("field", f, WR_ERR_HIP);
             }
             if (b.used && b.s.brick && !(b.d_bricks = bufs.take(roi_batch_bricks_bytes(b.bricks.size())))) return fail_at("field", f, WR_ERR_HIP);
+            if (b.masked) {
+                b.mbits = bufs.take(roi_batch_mask_plane_bytes(n));
+                b.md_blob = bufs.take(b.mplane_len());
+                b.mwork = bufs.take(roi_batch_work_bytes(b.mnseg, b.mids.size()));
+                if (!b.mbits || !b.md_blob || !b.mwork) return fail_at("field", f, WR_ERR_HIP);
+            }
         }
-        if (njobs) {
+        if (nall) {
             if (!(d_once = bufs.take(roi_batch_once_bytes(nplain, nstranded)))) return WR_ERR_HIP;
-            if (int rc = bufs.pin(roi_batch_tables_bytes(nplain, nstranded))) return rc;
+            if (nmask && !(d_restore = bufs.take(roi_batch_restore_bytes((size_t)nroi, (size_t)nfields)))) return WR_ERR_HIP;
+            if (int rc = bufs.pin(tables + (nmask ? roi_batch_restore_bytes((size_t)nroi, (size_t)nfields) : 0))) return rc;
             if (int rc = bufs.ev.create(0)) return rc;
+            if (nmask) if (int rc = bufs.ev.create(1)) return rc;
         }
-        if (njobs && !fld.dev && !(d_host_out = bufs.take((size_t)nfields * T * elem))) return WR_ERR_HIP;
+        if (nall && !fld.dev && !(d_host_out = bufs.take((size_t)nfields * T * elem))) return WR_ERR_HIP;
     }
     // ---- stage "up": only the listed segments' bytes
-    size_t bytes_up = 0, segments = 0;
+    size_t bytes_up = 0, segments = 0, mask_bytes_up = 0, mask_segments = 0;
     for (int f = 0; f < nfields; f++) {
         RoiBatchField& b = bf[f];
-        if (!b.used) continue;
-        if (int rc = seg_upload_lists(c, b.s, b.used, data_encs[f], b.blob, b.work, b.d_bricks, b.ids, b.bricks, &local.h2d_ms, &bytes_up)) return fail_at("field", f, rc);
-        for (int l = 0; l < b.used; l++) segments += b.ids[l].size();
+        if (b.used) {
+            if (int rc = seg_upload_lists(c, b.s, b.used, data_encs[f], b.blob, b.work, b.d_bricks, b.ids, b.bricks, &local.h2d_ms, &bytes_up)) return fail_at("field", f, rc);
+            for (int l = 0; l < b.used; l++) segments += b.ids[l].size();
+        }
+        if (b.masked) {
+            SegStream one;  // the mask's plane as a stream of one WRS1 plane (MaskRegion::upload)
+            one.nlay = 1; one.off[1] = b.mplane_len(); one.seg[0] = b.mseg; one.nseg[0] = b.mnseg;
+            uint8_t *blob_of[1] = {b.md_blob}, *work_of[1] = {b.mwork};
+            if (int rc = seg_upload_lists(c, one, 1, b.mplane(), blob_of, work_of, nullptr, &b.mids, std::vector<uint32_t>(), &local.h2d_ms, &mask_bytes_up)) return fail_at("field", f, rc);
+            mask_segments += b.mids.size();
+        }
     }
     g_stat[WR_STAT_ROI_BYTES_UP] += bytes_up;
+    if (nmask) g_stat[WR_STAT_MASK_ROI_BYTES_UP] += mask_bytes_up;
     const double t_coded = now();
     SlotLease slot;
     if (njobs)
@@ -5237,12 +5327,13 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
     const double t_phase = now();
     uint8_t* const d_out = fld.dev ? reinterpret_cast<uint8_t*>(fld.dev) : d_host_out;
     int rc = WR_OK;
-    if (njobs) {
+    std::vector<unsigned long long> restored((size_t)nfields, 0);  // (the masked call) per field the set bits among its regions
+    if (nall) {
         StageLock cu(pool->cu_mu);
-        clock_warmup(c, need.field_elems);
-        // the jobs' failure counts lie behind the tables, in the order of the fields and their planes
-        unsigned int* const d_bad = reinterpret_cast<unsigned int*>(d_once + roi_batch_tables_bytes(nplain, nstranded));
-        HIPCHK(hipMemsetAsync(d_bad, 0, 4 * njobs, c->stream));
+        if (njobs) clock_warmup(c, need.field_elems);
+        // the jobs' failure counts lie behind the tables, in the order of the fields, a field's planes and then its mask
+        unsigned int* const d_bad = reinterpret_cast<unsigned int*>(d_once + tables);
+        HIPCHK(hipMemsetAsync(d_bad, 0, 4 * nall, c->stream));
         ListJobs jobs;
         int at = 0;
         for (int f = 0; f < nfields; f++) {
@@ -5253,6 +5344,11 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
                 job.bad = d_bad + at;  // (the batch counts in one array, read back once)
                 jobs.add(job, wrk::seg_decode_list_ids(b.work[l], b.s.nseg[l]), b.ids[l].size(), b.s.strands);
             }
+            if (b.masked) {
+                wrk::SegJob job = seg_job(wrk::plane_ref(b.mbits), b.md_blob, b.mplane_len(), b.mwork, b.msym, b.mseg, b.mnseg, 0);
+                job.bad = d_bad + (b.mjob = at++);
+                jobs.add(job, wrk::seg_decode_list_ids(b.mwork, b.mnseg), b.mids.size(), 0);
+            }
         }
         launch_note(c, "seg_decode_lists_batch", 0, d_once, n, bufs.pinned, wrk::plane_ref(d_once));
         HIPCHK(hipEventRecord(bufs.ev[0], c->stream));
@@ -5261,14 +5357,18 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
         if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "batched segment decoder launch failed" + launch_describe(c));
         g_stat[WR_STAT_ROI_SEGMENTS] += segments;  // (behind the check: a launch that failed does not count as made)
         g_stat[WR_STAT_ROI_CODER_LAUNCHES] += (unsigned long)launches;
-        // no dequantiser runs unless every listed segment of every field decoded: the counts come back once
-        std::vector<unsigned int> bad(njobs);
-        HIPCHK(hipMemcpyAsync(bad.data(), d_bad, 4 * njobs, hipMemcpyDeviceToHost, c->stream));
+        if (nmask) g_stat[WR_STAT_MASK_ROI_SEGMENTS] += mask_segments;
+        // no dequantiser runs unless every listed segment of every field and of every mask decoded: the counts come back once
+        std::vector<unsigned int> bad(nall);
+        HIPCHK(hipMemcpyAsync(bad.data(), d_bad, 4 * nall, hipMemcpyDeviceToHost, c->stream));
         if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the batched segment decoder failed on the device" + launch_describe(c));
-        for (int f = 0; f < nfields; f++)
+        for (int f = 0; f < nfields; f++) {
             for (int l = 0; l < bf[f].used; l++)
                 if (const unsigned int k = bad[(size_t)bf[f].job0 + l])
                     return fail(WR_ERR_STREAM, "field " + std::to_string(f) + ": plane " + std::to_string(l) + ": " + bad_segments_text(k));
+            if (bf[f].masked)
+                if (const unsigned int k = bad[(size_t)bf[f].mjob]) return fail(WR_ERR_STREAM, "field " + std::to_string(f) + ": mask blob: " + bad_segments_text(k));
+        }
         fold_coder_seconds(bufs, 1, &local);
         // ---- every field in turn: its bricks back to their places, then its regions through the window stage
         for (int f = 0; f < nfields && rc == WR_OK; f++) {
@@ -5283,30 +5383,176 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
             rc = roi_multi_from_planes(c, slot.get(), d_out + (size_t)f * T * elem, nx, ny, b.pls, out_at, p, f32, tm ? &local : nullptr);
             if (rc) rc = fail_at("field", f, rc);
         }
+        // ---- (the masked call) the constant fields that have a mask, then `fill` into every region of every masked field: one launch
+        if (nmask && rc == WR_OK) {
+            std::vector<const uint8_t*> planes_of((size_t)nfields, nullptr);
+            for (int f = 0; f < nfields; f++) {
+                const RoiBatchField& b = bf[f];
+                if (!b.masked) continue;
+                planes_of[f] = b.mbits;
+                if (!b.s.constant) continue;
+                if (f32) wrk::fill_f32(reinterpret_cast<float*>(d_out) + (size_t)f * T, T, (float)infos[f].midval, c->stream);
+                else wrk::fill(reinterpret_cast<double*>(d_out) + (size_t)f * T, T, infos[f].midval, c->stream);
+            }
+            uint8_t* const host_table = bufs.pinned + tables;
+            HIPCHK(hipEventRecord(bufs.ev[2], c->stream));
+            const int nfld = f32 ? wrk::mask_restore_boxes(reinterpret_cast<float*>(d_out), mregions.data(), out_at.data(), (size_t)nroi, planes_of.data(), (size_t)nfields, T,
+                                                           (float)mb->fill, host_table, d_restore, c->stream)
+                                 : wrk::mask_restore_boxes(reinterpret_cast<double*>(d_out), mregions.data(), out_at.data(), (size_t)nroi, planes_of.data(), (size_t)nfields, T,
+                                                           mb->fill, host_table, d_restore, c->stream);
+            HIPCHK(hipEventRecord(bufs.ev[3], c->stream));
+            if (nfld != (int)nmask) rc = fail(WR_ERR_ARG, "too many turns: the restore launch of the call has 2^31 or more");
+            else if (hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "mask restore launch failed");
+            else {
+                std::vector<unsigned long long> counts(nmask);
+                HIPCHK(hipMemcpyAsync(counts.data(), wrk::mask_boxes_counters(d_restore, (size_t)nroi, (size_t)nfields), nmask * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipStreamSynchronize(c->stream));
+                size_t m = 0;
+                for (int f = 0; f < nfields; f++) if (bf[f].masked) restored[f] = counts[m++];
+            }
+        }
         rc = kernel_stage_end(c, rc);
     }
     if (rc) return rc;
-    // constant fields: midval in every region (device callers here, host callers behind the one copy down)
+    // constant fields: midval in every region (device callers here, host callers behind the one copy down); those that have
+    // a mask were made in the kernel stage
     for (int f = 0; f < nfields; f++)
-        if (bf[f].s.constant && fld.dev)
+        if (bf[f].s.constant && fld.dev && !bf[f].masked)
             if (int rc2 = fill_constant(c, FieldRef{fld.dev + (size_t)f * T}, T, infos[f].midval)) return rc2;
-    if (njobs)  // (an all-constant call has nothing to bring down)
+    if (nall)  // (an all-constant call has nothing to bring down)
         if (int rc2 = finish_call(c, fld, d_host_out, d_host_out, (size_t)nfields * T, false, t0, t_coded, t_phase, &local, nullptr)) return rc2;
     for (int f = 0; f < nfields; f++) {
-        if (!bf[f].s.constant || fld.dev) continue;
+        if (!bf[f].s.constant || fld.dev || bf[f].masked) continue;
         FieldRef part;
         if (f32) part.host_f32 = fld.host_f32 + (size_t)f * T;
         else part.host = fld.host + (size_t)f * T;
         if (int rc2 = fill_constant(c, part, T, infos[f].midval)) return rc2;
+    }
+    if (mb && mb->res) {
+        const float fill_ms = nmask ? (float)(bufs.ev.seconds(1) * 1e3) : 0;
+        for (int f = 0; f < nfields; f++) {
+            wr_mask_result& r = mb->res[f];
+            memset(&r, 0, sizeof r);
+            if (!bf[f].masked) continue;
+            r.undefined = restored[f]; r.pad = bf[f].mpad; r.mask_len = bf[f].mlen; r.fill_ms = fill_ms;
+        }
     }
     local.total = now() - t0;
     if (tm) *tm = local;
     return WR_OK;
 }
 
+int decode_seg_roi_batch_masked(wr_ctx* c, FieldRef f, int nfields, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                                const wr_enc_info* infos, const unsigned char* const* data_encs, const size_t* data_lens, double fill, wr_timings* tm,
+                                wr_mask_result* res)
+{
+    if (res && nfields > 0) memset(res, 0, (size_t)nfields * sizeof *res);
+    const MaskBatch mb{fill, res};
+    return decode_seg_roi_batch_impl(c, f, nfields, nx, ny, nz, level, max_planes, rois, nroi, infos, data_encs, data_lens, tm, &mb);
+}
+
+// wr_dev_mask_restore_boxes / _f32: the restore over the boxes alone, as a stage call
+template <class T>
+int dev_mask_restore_boxes(wr_ctx* c, T* d_out, int nfields, int nx, int ny, int nz, int level, const wr_box* rois, int nroi, const unsigned char* const* d_bits,
+                           double fill, unsigned long long* undefined)
+{
+    if (int rc = ctx_bind(c)) return rc;
+    if (!d_out || !d_bits) return fail(WR_ERR_ARG, "null pointer");
+    if (nfields < 1) return fail(WR_ERR_ARG, "nfields must be at least 1");
+    std::vector<size_t> offs((size_t)(nroi > 0 ? nroi : 0) + 1);
+    const size_t T_elems = wr_roi_multi_elems(nx, ny, nz, level, rois, nroi, offs.data());
+    if (!T_elems) return WR_ERR_ARG;  // (the message is wr_roi_multi_elems')
+    std::vector<wrmask::Region> gs((size_t)nroi);
+    for (int i = 0; i < nroi; i++) gs[i] = wrmask::Region{nx, ny, nz, level, rois[i].x0, rois[i].y0, rois[i].z0, rois[i].x1, rois[i].y1, rois[i].z1};
+    size_t nmask = 0;
+    for (int f = 0; f < nfields; f++) nmask += d_bits[f] != nullptr;
+    if (undefined) for (int f = 0; f < nfields; f++) undefined[f] = 0;
+    const size_t turns = wrmask::boxes_turns(gs.data(), gs.size(), nullptr);
+    if (!turns || (unsigned long long)nmask * turns >= wrmask::kTurnLimit) return fail(WR_ERR_ARG, "too many turns: the restore launch has 2^31 or more");
+    if (!nmask) return WR_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    BatchBufs bufs(c);
+    const size_t table = wrk::mask_boxes_table_bytes((size_t)nroi, (size_t)nfields);
+    uint8_t* const d_table = bufs.take(table);
+    if (!d_table) return WR_ERR_HIP;
+    if (int rc = bufs.pin(table)) return rc;
+    StageLock cu(c->pool->cu_mu);
+    if (wrk::mask_restore_boxes(d_out, gs.data(), offs.data(), (size_t)nroi, d_bits, (size_t)nfields, T_elems, (T)fill, bufs.pinned, d_table, c->stream) != (int)nmask)
+        return fail(WR_ERR_ARG, "too many turns: the restore launch has 2^31 or more");
+    if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask restore launch failed");
+    std::vector<unsigned long long> counts(nmask);
+    HIPCHK(hipMemcpyAsync(counts.data(), wrk::mask_boxes_counters(d_table, (size_t)nroi, (size_t)nfields), nmask * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (undefined) {
+        size_t m = 0;
+        for (int f = 0; f < nfields; f++) if (d_bits[f]) undefined[f] = counts[m++];
+    }
+    return WR_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int wr_decode_host_seg_roi_batch_masked(wr_ctx* c, double* h_out, int nfields, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                                        const wr_enc_info* infos, const unsigned char* const* data_encs, const size_t* data_lens, double fill, wr_timings* tm,
+                                        wr_mask_result* res)
+{
+    FieldRef f; f.host = h_out;
+    return decode_seg_roi_batch_masked(c, f, nfields, nx, ny, nz, level, max_planes, rois, nroi, infos, data_encs, data_lens, fill, tm, res);
+}
+
+int wr_decode_host_seg_roi_batch_masked_f32(wr_ctx* c, float* h_out, int nfields, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                                            const wr_enc_info* infos, const unsigned char* const* data_encs, const size_t* data_lens, double fill, wr_timings* tm,
+                                            wr_mask_result* res)
+{
+    FieldRef f; f.host_f32 = h_out;
+    return decode_seg_roi_batch_masked(c, f, nfields, nx, ny, nz, level, max_planes, rois, nroi, infos, data_encs, data_lens, fill, tm, res);
+}
+
+int wr_decode_device_seg_roi_batch_masked(wr_ctx* c, double* d_out, int nfields, int nx, int ny, int nz, int level, int max_planes, const wr_box* rois, int nroi,
+                                          const wr_enc_info* infos, const unsigned char* const* data_encs, const size_t* data_lens, double fill, wr_timings* tm,
+                                          wr_mask_result* res)
+{
+    FieldRef f; f.dev = d_out;
+    if (!d_out) return fail(WR_ERR_ARG, "null device output pointer");
+    return decode_seg_roi_batch_masked(c, f, nfields, nx, ny, nz, level, max_planes, rois, nroi, infos, data_encs, data_lens, fill, tm, res);
+}
+
+int wr_dev_mask_restore_boxes(wr_ctx* c, double* d_out, int nfields, int nx, int ny, int nz, int level, const wr_box* rois, int nroi,
+                              const unsigned char* const* d_bits, double fill, unsigned long long* undefined)
+{
+    return dev_mask_restore_boxes(c, d_out, nfields, nx, ny, nz, level, rois, nroi, d_bits, fill, undefined);
+}
+int wr_dev_mask_restore_boxes_f32(wr_ctx* c, float* d_out, int nfields, int nx, int ny, int nz, int level, const wr_box* rois, int nroi,
+                                  const unsigned char* const* d_bits, double fill, unsigned long long* undefined)
+{
+    return dev_mask_restore_boxes(c, d_out, nfields, nx, ny, nz, level, rois, nroi, d_bits, fill, undefined);
+}
+
+size_t wr_seg_roi_batch_device_bytes_masked(int nfields, int nmasked, size_t n, int planes, unsigned seg, unsigned brick, unsigned strands, unsigned mask_seg,
+                                            size_t out_elems)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!mask_seg) mask_seg = WR_SEG_DEFAULT;
+    if (nfields < 1 || nmasked < 0 || nmasked > nfields || !n || planes < 0 || planes > WR_NLAYMAX || !wrseg::seg_ok(seg) || !wrseg::seg_ok(mask_seg) ||
+        (brick && !wrblk::brick_ok(brick)))
+        return 0;
+    if (strands && !wrseg::strands_ok(strands, seg)) return 0;
+    const size_t N = (size_t)nfields, M = (size_t)nmasked, jobs = N * (size_t)planes;
+    if (jobs + M > WR_SEG_BATCH_MAX) return 0;
+    if (!M) return wr_seg_roi_batch_device_bytes(nfields, n, planes, seg, brick, strands, out_elems);
+    // the plain function's sum, with the masks' jobs in the table of the WRS1 / WRS2 launch
+    const size_t nseg = wrseg::seg_count(n, seg);
+    const size_t blob = ((strands ? wr_seg_bound_strands(n, seg, strands) : brick ? wr_seg_bound_blocked(n, seg) : wr_seg_bound(n, seg)) + 15) & ~(size_t)15;
+    const size_t per_job = batch_plane_bytes(n) + up256(blob) + up256(roi_batch_work_bytes(nseg, nseg)) + batch_perm_bytes(n, brick);
+    const size_t per_field = brick && planes ? up256(roi_batch_bricks_bytes(n)) : 0;
+    // per masked field: the mask plane at its pitch, the blob at its bound, the offsets, flags and list of all its segments
+    const size_t msym = wrmask::mask_bytes(n), mnseg = wrseg::seg_count(msym, mask_seg);
+    const size_t per_mask = roi_batch_mask_plane_bytes(n) + up256(wr_mask_bound(n, mask_seg)) + up256(roi_batch_work_bytes(mnseg, mnseg));
+    const size_t once = up256(roi_batch_once_bytes((strands ? 0 : jobs) + M, strands ? jobs : 0)) + up256(roi_batch_restore_bytes(WR_ROI_MULTI_MAX, N));
+    return jobs * per_job + N * per_field + M * per_mask + once + up256(N * out_elems * sizeof(double));
+}
 
 size_t wr_seg_lists_lanes(int njobs, const size_t* nlist, const unsigned* strands, uint32_t* first)
 {

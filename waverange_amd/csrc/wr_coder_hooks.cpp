@@ -490,4 +490,30 @@ size_t wr_seg_roi_segments_multi(int nx, int ny, int nz, int level, int wlev, co
     return wrroi::segments_of_multi(nx, ny, nz, g.data(), g.size(), seg, ids, ids ? cap : 0);
 }
 
+// the regions of a masked region decode across a batch of fields as the mask sees them (wr_mask.h): host only
+static std::vector<wrmask::Region> mask_regions(int nx, int ny, int nz, int level, const wr_box* rois, int nroi)
+{
+    std::vector<wrmask::Region> g((size_t)nroi);
+    for (int i = 0; i < nroi; i++) g[i] = wrmask::Region{nx, ny, nz, level, rois[i].x0, rois[i].y0, rois[i].z0, rois[i].x1, rois[i].y1, rois[i].z1};
+    return g;
+}
+
+size_t wr_mask_roi_segments_multi(int nx, int ny, int nz, int level, const wr_box* rois, int nroi, unsigned seg, uint32_t* ids, size_t cap)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (!wrseg::seg_ok(seg)) { fail(WR_ERR_ARG, "segment length must be a multiple of 16 in [16, 59999]"); return 0; }
+    if (!roi_multi_args_ok(nx, ny, nz, level, wrlow::kMaxLevel, rois, nroi)) return 0;
+    const std::vector<wrmask::Region> g = mask_regions(nx, ny, nz, level, rois, nroi);
+    return wrmask::roi_segments_multi(g.data(), g.size(), seg, ids, ids ? cap : 0);
+}
+
+size_t wr_mask_boxes_turns(int nx, int ny, int nz, int level, const wr_box* rois, int nroi, uint32_t* first)
+{
+    if (!roi_multi_args_ok(nx, ny, nz, level, wrlow::kMaxLevel, rois, nroi)) return 0;
+    const std::vector<wrmask::Region> g = mask_regions(nx, ny, nz, level, rois, nroi);
+    const size_t turns = wrmask::boxes_turns(g.data(), g.size(), first);
+    if (!turns) fail(WR_ERR_ARG, "too many turns: the regions have 2^31 or more");
+    return turns;
+}
+
 }  // extern "C"

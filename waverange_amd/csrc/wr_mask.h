@@ -11,6 +11,12 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "wr_segcoder.h"
+
 #ifndef WR_MASK_HOST_ONLY  // (defined by a host-only program that wants the blob and the crop below without the HIP runtime)
 #include <hip/hip_runtime.h>
 #endif
@@ -94,6 +100,66 @@ inline size_t roi_segments(const Region& g, uint32_t seg, uint32_t* ids, size_t 
     return count;
 }
 
+// The blobs of a batch of masked records, validated in field order as the single masked call validates its one: the header
+// (check_header), then the whole segment index of the WRS1 plane behind it (wrseg::check_index; the plane's seg is read from
+// its own header).  blobs[f] == nullptr: field f has no blob and is passed over.  Returns nfields if every blob passes and
+// info[f] is then filled for every field that has one; otherwise the first field whose blob fails, *why saying what ("mask
+// blob: ..."), and nothing behind that field has been looked at.
+struct BlobInfo {
+    unsigned long long undefined = 0;
+    double pad = 0;
+    uint32_t seg = 0, nseg = 0;
+};
+inline int check_blobs(const unsigned char* const* blobs, const size_t* lens, int nfields, size_t n, BlobInfo* info, std::string* why)
+{
+    for (int f = 0; f < nfields; f++) {
+        if (!blobs[f]) continue;
+        if (const char* w = check_header(blobs[f], lens[f], n, &info[f].undefined, &info[f].pad)) { *why = w; return f; }
+        const size_t rest = lens[f] - kHeaderBytes;
+        if (const char* w = wrseg::check_index(blobs[f] + kHeaderBytes, rest, rest, mask_bytes(n), &info[f].seg, &info[f].nseg)) {
+            *why = std::string("mask blob: ") + w;
+            return f;
+        }
+    }
+    return nfields;
+}
+
+// ... of several regions of one field (the masked region decode across a batch of fields): the ascending union of the regions'
+// lists, with roi_segments' conventions
+inline size_t roi_segments_multi(const Region* gs, size_t nroi, uint32_t seg, uint32_t* ids, size_t cap)
+{
+    std::vector<uint32_t> all;
+    for (size_t i = 0; i < nroi; i++) {
+        const size_t at = all.size(), count = roi_segments(gs[i], seg, nullptr, 0);
+        all.resize(at + count);
+        roi_segments(gs[i], seg, all.data() + at, count);
+    }
+    std::sort(all.begin(), all.end());
+    all.erase(std::unique(all.begin(), all.end()), all.end());
+    if (ids)
+        for (size_t k = 0; k < all.size() && k < cap; k++) ids[k] = all[k];
+    return all.size();
+}
+
+// The turns of k_mask_restore_boxes over one field's regions: a turn is 64 consecutive x of one region row, region i has
+// ceil(cx / 64) * cy * cz of them, first[0 .. nroi] (nullptr: not wanted) is their exclusive prefix.  Returns their number, or 0
+// for 2^31 turns or more (first[] is then not to be used).
+constexpr unsigned long long kTurnLimit = 1ull << 31;
+inline size_t boxes_turns(const Region* gs, size_t nroi, uint32_t* first)
+{
+    unsigned long long run = 0;
+    for (size_t i = 0; i < nroi; i++) {
+        if (first) first[i] = (uint32_t)run;
+        const Region& g = gs[i];
+        const unsigned long long rows = (unsigned long long)(((long long)g.x1 - g.x0 + 63) >> 6) * (unsigned long long)(g.y1 - g.y0);  // (below 2^56)
+        if (rows >= kTurnLimit) return 0;
+        run += rows * (unsigned long long)(g.z1 - g.z0);  // (below 2^62 + 2^31)
+        if (run >= kTurnLimit) return 0;
+    }
+    if (first) first[nroi] = (uint32_t)run;
+    return (size_t)run;
+}
+
 }  // namespace wrmask
 
 #ifndef WR_MASK_HOST_ONLY
@@ -121,6 +187,22 @@ void mask_restore(float* x, size_t n, const uint8_t* bits, float v, unsigned lon
 // bit of the region are read.
 void mask_restore_box(double* out, const wrmask::Region& g, const uint8_t* bits, double v, unsigned long long* counters, hipStream_t st);
 void mask_restore_box(float* out, const wrmask::Region& g, const uint8_t* bits, float v, unsigned long long* counters, hipStream_t st);
+// ---- k_mask_restore_boxes: mask_restore_box on every (field that has a mask, region) of a region decode across a batch of
+// fields, in one launch.  out = nfields parts of field_elems elements each; region i (gs[i], all of one field shape and level)
+// of field f lies at out + f * field_elems + offs[i].  bits[f] (a host array of device pointers): field f's full-length plane,
+// any alignment, or nullptr: a field without a mask, whose part is not touched.  The m-th field that has a plane counts the set
+// bits among its regions' (a sample in two regions twice) in mask_boxes_counters(table, nroi, nfields)[m] (integer atomics, one
+// per wave and item; zeroed here).  table: mask_boxes_table_bytes(nroi, nfields) of device memory, 256-byte aligned;
+// host_table: as much host memory, which stays alive until the stream has passed the copy.  Returns the fields that have a
+// plane (0: nothing was launched), or -1: refused, the launch would have 2^31 turns or more (wrmask::boxes_turns).
+size_t mask_boxes_table_bytes(size_t nroi, size_t nfields);
+unsigned long long* mask_boxes_counters(uint8_t* table, size_t nroi, size_t nfields);
+int mask_restore_boxes(double* out, const wrmask::Region* gs, const size_t* offs, size_t nroi, const uint8_t* const* bits, size_t nfields, size_t field_elems, double v,
+                       uint8_t* host_table, uint8_t* table, hipStream_t st);
+int mask_restore_boxes(float* out, const wrmask::Region* gs, const size_t* offs, size_t nroi, const uint8_t* const* bits, size_t nfields, size_t field_elems, float v,
+                       uint8_t* host_table, uint8_t* table, hipStream_t st);
+// x[0, n) = v in fp32 (wrk::fill is the fp64 one)
+void fill_f32(float* x, size_t n, float v, hipStream_t st);
 // ---- k_err_stats_masked: the compare of wrk::err_stats over the samples whose bit is clear.  result[0 .. 2] = the maximum of the
 // finite |a - b|, the count of differences that are not finite, the fp64 sum of the squared finite differences; *defined = the
 // clear bits below n (an exact integer; a word of its own, so that result's neighbours stay untouched).  Nothing at a position

@@ -254,6 +254,170 @@ static void mask_restore_box_t(T* out, const wrmask::Region& g, const uint8_t* b
 void mask_restore_box(double* out, const wrmask::Region& g, const uint8_t* bits, double v, unsigned long long* counters, hipStream_t st) { mask_restore_box_t(out, g, bits, v, counters, st); }
 void mask_restore_box(float* out, const wrmask::Region& g, const uint8_t* bits, float v, unsigned long long* counters, hipStream_t st) { mask_restore_box_t(out, g, bits, v, counters, st); }
 
+// ---- the restore on the boxes of a region decode across a batch of fields: every (field that has a mask, region) in ONE
+// launch.  An item is such a pair, in the order of the fields, then the regions.  The regions are the same for every field, so
+// the item table is kept in two parts: a record per region (its box, its turns per row, its element offset offs[i]) with
+// first[0 .. nroi], the exclusive prefix of the regions' turns (wrmask::boxes_turns), and a record per field with a mask (its
+// plane, its element offset f * T, its counter).  Item (m, i) -- m counts the fields that have a mask -- owns the turns
+// m * tpf + first[i] .. m * tpf + first[i + 1] - 1 of the launch, tpf = first[nroi]; a turn is 64 consecutive x of one region
+// row, exactly k_mask_restore_box's.  The launch's turns go round the grid's waves: wave w takes t = w, w + W, ...
+// The walk.  (m, u) = (t / tpf, t % tpf) are kept as counters that advance by W's digits with a carry, so the field costs no
+// division after the first step.  The region of u is found by bisection in first[] and kept with its range [lo, hi): a wave
+// searches again only when u has left the range (a step into the same region of the next field keeps it).  Inside the region
+// the turn's (turn, y, z) come from u - lo by two divisions, one where the rows have a single turn (cx <= 64: every probe):
+// the digits of W in a region's bases, which is how k_mask_restore_box avoids dividing, would have to be formed anew, by the
+// same divisions, each time the region changes.  Everything but the lane's own bit is uniform in the wave (the wave index is
+// made so) and lives in scalar registers.
+// The count: a wave adds up the set bits of its turns of one item and puts them into the field's counter with one integer
+// atomic when it leaves the item.  Nothing depends on where a block ends: a wave only knows its own index in the grid.
+struct MaskBoxRegion {
+    uint32_t x0, y0, z0;
+    uint32_t cx, cy, cz;  // the region's extents
+    uint32_t tpr, pad;    // turns per row
+    unsigned long long off;  // where the region starts in a field's part of the output, elements
+};
+struct MaskBoxField {
+    const uint8_t* bits;
+    unsigned long long off;  // where the field's part starts in the output, elements
+};
+struct MaskBoxes {
+    unsigned long long nx, ny;  // the fields'
+    uint32_t r, nroi, tpf, nfld;
+    const MaskBoxRegion* reg;
+    const uint32_t* first;
+    const MaskBoxField* fld;
+    unsigned long long* counters;  // one per field with a mask
+};
+
+template <typename T>
+__global__ __launch_bounds__(WR_MASK_THREADS) void k_mask_restore_boxes(T* __restrict__ out, MaskBoxes g, T v)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * WR_MASK_WAVES + (threadIdx.x >> 6)));
+    const uint32_t nwaves = gridDim.x * WR_MASK_WAVES;
+    const uint32_t du = nwaves % g.tpf, dm = nwaves / g.tpf;
+    uint32_t u = wave % g.tpf, m = wave / g.tpf;
+    uint32_t lo = 0, hi = 0, item_m = 0;  // the item at hand: field item_m, the region whose turns are [lo, hi); hi == 0: none yet
+    MaskBoxRegion b = {};
+    const uint8_t* bits = nullptr;
+    T* o = nullptr;
+    unsigned long long pop = 0;  // (of the wave and the item: every lane holds the same value)
+    while (m < g.nfld) {
+        if (u < lo || u >= hi || m != item_m) {
+            if (lane == 0 && pop) atomicAdd(&g.counters[item_m], pop);
+            pop = 0;
+            if (u < lo || u >= hi) {
+                uint32_t i = 0, end = g.nroi;  // first[i] <= u < first[end]
+                while (end - i > 1) {
+                    const uint32_t mid = (i + end) >> 1;
+                    if (g.first[mid] <= u) i = mid;
+                    else end = mid;
+                }
+                b = g.reg[i];
+                lo = g.first[i];
+                hi = g.first[i + 1];
+            }
+            item_m = m;
+            bits = g.fld[m].bits;
+            o = out + g.fld[m].off + b.off;
+        }
+        const uint32_t q = u - lo;
+        uint32_t turn = 0, rowi = q;
+        if (b.tpr != 1) { rowi = q / b.tpr; turn = q - rowi * b.tpr; }
+        const uint32_t z = rowi / b.cy, y = rowi - z * b.cy;
+        const uint32_t xs = turn << 6, left = b.cx - xs, cnt = left < 64 ? left : 64;
+        const unsigned long long valid = cnt == 64 ? ~0ull : (1ull << cnt) - 1;
+        const size_t row = (size_t)g.nx * (((size_t)(b.y0 + y) << g.r) + (size_t)g.ny * ((size_t)(b.z0 + z) << g.r));
+        unsigned long long w;
+        if (g.r == 0) {
+            w = mask_word_at(bits, row + b.x0 + xs, cnt) & valid;
+        } else {
+            const size_t J = row + ((size_t)(b.x0 + xs + lane) << g.r);
+            w = __ballot(lane < cnt && ((bits[J >> 3] >> (J & 7)) & 1));
+        }
+        if (w) {  // (the whole wave: w is the same in every lane)
+            pop += (unsigned long long)__popcll(w);
+            if ((w >> lane) & 1) o[((size_t)z * b.cy + y) * b.cx + xs + lane] = v;
+        }
+        u += du;
+        const uint32_t carry = u >= g.tpf;
+        if (carry) u -= g.tpf;
+        m += dm + carry;
+    }
+    if (lane == 0 && pop) atomicAdd(&g.counters[item_m], pop);
+}
+
+namespace {
+size_t up8(size_t v) { return (v + 7) & ~(size_t)7; }
+size_t boxes_first_at(size_t nroi) { return nroi * sizeof(MaskBoxRegion); }
+size_t boxes_fields_at(size_t nroi) { return boxes_first_at(nroi) + up8((nroi + 1) * sizeof(uint32_t)); }
+size_t boxes_counters_at(size_t nroi, size_t nfields) { return boxes_fields_at(nroi) + nfields * sizeof(MaskBoxField); }
+}  // namespace
+
+size_t mask_boxes_table_bytes(size_t nroi, size_t nfields) { return (boxes_counters_at(nroi, nfields) + nfields * sizeof(unsigned long long) + 255) & ~(size_t)255; }
+unsigned long long* mask_boxes_counters(uint8_t* table, size_t nroi, size_t nfields) { return reinterpret_cast<unsigned long long*>(table + boxes_counters_at(nroi, nfields)); }
+
+template <typename T>
+static int mask_restore_boxes_t(T* out, const wrmask::Region* gs, const size_t* offs, size_t nroi, const uint8_t* const* bits, size_t nfields, size_t field_elems,
+                                T v, uint8_t* host_table, uint8_t* table, hipStream_t st)
+{
+    MaskBoxRegion* const reg = reinterpret_cast<MaskBoxRegion*>(host_table);
+    uint32_t* const first = reinterpret_cast<uint32_t*>(host_table + boxes_first_at(nroi));
+    MaskBoxField* const fld = reinterpret_cast<MaskBoxField*>(host_table + boxes_fields_at(nroi));
+    const size_t tpf = wrmask::boxes_turns(gs, nroi, first);
+    if (!tpf) return -1;
+    for (size_t i = 0; i < nroi; i++) {
+        MaskBoxRegion& b = reg[i];
+        memset(&b, 0, sizeof b);
+        b.x0 = (uint32_t)gs[i].x0; b.y0 = (uint32_t)gs[i].y0; b.z0 = (uint32_t)gs[i].z0;
+        b.cx = (uint32_t)(gs[i].x1 - gs[i].x0); b.cy = (uint32_t)(gs[i].y1 - gs[i].y0); b.cz = (uint32_t)(gs[i].z1 - gs[i].z0);
+        b.tpr = (b.cx + 63) >> 6;
+        b.off = offs[i];
+    }
+    size_t nfld = 0;
+    for (size_t f = 0; f < nfields; f++)
+        if (bits[f]) { fld[nfld].bits = bits[f]; fld[nfld].off = (unsigned long long)f * field_elems; nfld++; }
+    if (!nfld) return 0;
+    const unsigned long long turns = (unsigned long long)nfld * tpf;
+    if (turns >= wrmask::kTurnLimit) return -1;
+    MaskBoxes g;
+    g.nx = (unsigned long long)gs[0].nx; g.ny = (unsigned long long)gs[0].ny;
+    g.r = (uint32_t)gs[0].r; g.nroi = (uint32_t)nroi; g.tpf = (uint32_t)tpf; g.nfld = (uint32_t)nfld;
+    g.reg = reinterpret_cast<const MaskBoxRegion*>(table);
+    g.first = reinterpret_cast<const uint32_t*>(table + boxes_first_at(nroi));
+    g.fld = reinterpret_cast<const MaskBoxField*>(table + boxes_fields_at(nroi));
+    g.counters = mask_boxes_counters(table, nroi, nfields);
+    size_t grid = (size_t)((turns + WR_MASK_WAVES - 1) / WR_MASK_WAVES);
+    if (grid > WR_MASK_BLOCKS) grid = WR_MASK_BLOCKS;
+    (void)hipMemcpyAsync(table, host_table, boxes_counters_at(nroi, nfields), hipMemcpyHostToDevice, st);
+    (void)hipMemsetAsync(g.counters, 0, nfld * sizeof(unsigned long long), st);
+    hipLaunchKernelGGL((k_mask_restore_boxes<T>), dim3((unsigned)grid), dim3(WR_MASK_THREADS), 0, st, out, g, v);
+    return (int)nfld;
+}
+int mask_restore_boxes(double* out, const wrmask::Region* gs, const size_t* offs, size_t nroi, const uint8_t* const* bits, size_t nfields, size_t field_elems, double v,
+                       uint8_t* host_table, uint8_t* table, hipStream_t st)
+{
+    return mask_restore_boxes_t(out, gs, offs, nroi, bits, nfields, field_elems, v, host_table, table, st);
+}
+int mask_restore_boxes(float* out, const wrmask::Region* gs, const size_t* offs, size_t nroi, const uint8_t* const* bits, size_t nfields, size_t field_elems, float v,
+                       uint8_t* host_table, uint8_t* table, hipStream_t st)
+{
+    return mask_restore_boxes_t(out, gs, offs, nroi, bits, nfields, field_elems, v, host_table, table, st);
+}
+
+// x[0, n) = v: the constant fp32 field of a host caller of the masked batch call, made where the restore will find it
+__global__ __launch_bounds__(WR_MASK_THREADS) void k_fill_f32(float* __restrict__ x, size_t n, float v)
+{
+    for (size_t i = (size_t)blockIdx.x * WR_MASK_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * WR_MASK_THREADS) x[i] = v;
+}
+void fill_f32(float* x, size_t n, float v, hipStream_t st)
+{
+    size_t g = (n + WR_MASK_THREADS - 1) / WR_MASK_THREADS;
+    if (g < 1) g = 1;
+    if (g > WR_MASK_BLOCKS) g = WR_MASK_BLOCKS;
+    hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)g), dim3(WR_MASK_THREADS), 0, st, x, n, v);
+}
+
 // ---- the masked compare of an encode to an error bound or a quality target on a masked field (include/waverange_amd.h,
 // "Masked fields in the tolerance searches"): what k_err_stats gives (wr_kernels.hip) over the samples whose mask bit is clear
 // -- the maximum of the finite |a - b|, the count of differences that are not finite, S_D = the fp64 sum of q = fl(d * d) over
