@@ -9,7 +9,11 @@ The field is tests/test_gpu_seg_drivers.py's: 64^3, tolerance 1e-6, seg 1008.  T
     batch          one wr_decode_host_seg_batch call of the two streams
     encode         one WRS2 (brick 16) and one WRS3 (8 strands) encode, nothing else
     encode_batch   one wr_encode_host_seg_batch call of two fields as WRS2, nothing else
-    transcode      the reference's stream of the field (one wr_encode_host), then reference -> WRS3 and WRS2 -> reference"""
+    transcode      the reference's stream of the field (one wr_encode_host), then reference -> WRS3 and WRS2 -> reference
+The masked modes code the field with a disc of undefined samples as one masked WRS1 record first (mask cut at seg 1008 too):
+    masked_whole   one wr_decode_host_seg_masked call
+    masked_region  one wr_decode_host_seg_roi_masked call of a centred 32^3 box at level 0
+    masked_batch   one wr_decode_host_seg_roi_batch_masked call of two such records and that box"""
 import os
 import sys
 
@@ -51,6 +55,21 @@ def main():
             wrs2, info2 = api.transcode_host_ref(shape, ref, ref["data"], "wrs2:seg=1008:brick=16")  # (on the host: no kernel)
             back, _ = ctx.transcode(info2, wrs2, "ref", shape=shape)
             print("transcode ok", wrs3.size, back.tobytes() == ref["data"].tobytes())
+            return
+        if what.startswith("masked_"):
+            z, y, x = np.meshgrid(np.arange(64), np.arange(64), np.arange(64), indexing="ij")
+            f[(x - 30) ** 2 + (y - 34) ** 2 < 300] = -9.99e33
+            rec = own(ctx.encode_host_seg_masked(f, TOL, -1e30, seg=SEG)[0])
+            box = ((16, 48), (16, 48), (16, 48))
+            if what == "masked_whole":
+                res, _ = ctx.decode_host_seg_masked(np.empty(shape), rec)
+            elif what == "masked_region":
+                res, _ = ctx.decode_host_seg_roi_masked(np.empty(api.roi_shape(box)), shape, 0, box, rec)
+            else:
+                masks = []
+                ctx.decode_host_seg_rois_batch_masked(shape, 0, [box], [rec, rec], masks=masks)
+                res = masks[1]
+            print(what, "ok", res["undefined"], res["mask_len"])
             return
         encs = [own(ctx.encode_host_seg(f, TOL, 1, SEG, **kw)[0]) for kw in (dict(), dict(brick=16))]
         if what == "multi":

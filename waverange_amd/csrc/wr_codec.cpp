@@ -1729,6 +1729,43 @@ void fill_error_stats(wr_error_stats* o, double max_abs, double bad, double sums
     o->nonfinite = (unsigned long long)bad;
 }
 
+// The measuring calls on a constant record: the reconstruction is midval everywhere (fill_constant), so the compare runs on the
+// host over the field as the caller holds it.  bits != nullptr: the record's mask, and only the samples whose bit is clear are
+// compared, `count` of them.  *err_out = max |field - midval|; stats_out (or nullptr) takes S by a compensated sum (Neumaier),
+// whose error does not grow with n, and lo and hi of the compared samples.
+int constant_error_stats(const FieldRef& fld, size_t n, double midval, const unsigned char* bits, size_t count, double* err_out, wr_error_stats* stats_out,
+                         unsigned long long* defined_out)
+{
+    double mx = 0;
+    size_t bad = 0;
+    auto undef = [&](size_t j) { return bits && ((bits[j >> 3] >> (j & 7)) & 1); };
+    if (defined_out) *defined_out = count;
+    for (size_t j = 0; j < n; j++) {
+        if (undef(j)) continue;
+        const double d = fld.host ? fabs(fld.host[j] - midval) : fabs((double)fld.host_f32[j] - (double)(float)midval);
+        if (d <= DBL_MAX) mx = d > mx ? d : mx;
+        else bad++;
+    }
+    if (stats_out) {
+        double sum = 0, comp = 0, lo = NAN, hi = NAN;
+        for (size_t j = 0; j < n; j++) {
+            if (undef(j)) continue;
+            const double v = fld.host ? fld.host[j] : (double)fld.host_f32[j];
+            lo = fmin(lo, v); hi = fmax(hi, v);
+            const double d = fld.host ? v - midval : v - (double)(float)midval;
+            if (!(fabs(d) <= DBL_MAX)) continue;
+            const double q = d * d, t = sum + q;
+            comp += sum >= q ? (sum - t) + q : (q - t) + sum;
+            sum = t;
+        }
+        if (sum <= DBL_MAX) sum += comp;
+        fill_error_stats(stats_out, mx, (double)bad, sum, count, lo, hi);
+    }
+    if (bad) return fail(WR_ERR_ARG, std::to_string(bad) + " difference(s) between the field and the reconstruction are not finite");
+    *err_out = mx;
+    return WR_OK;
+}
+
 // ---- the search of an encode to an error bound (include/waverange_amd.h) ------------------------------------------------------
 // E(g) is measured, not bounded: a trial at g forms the reconstruction the decoder would return and compares it with the field.
 // The planes of a trial are never written.  As above only the last plane depends on the tolerance: the residual range plane l
@@ -2102,100 +2139,14 @@ struct MaskEncode {
     }
 };
 
-struct MaskDecode {
-    // what the caller gives: the blob behind the field's planes, and what the undefined samples become
-    const unsigned char* blob = nullptr;
-    size_t len = 0;
-    double fill = NAN;
-    // what comes out
-    unsigned long long undefined = 0;
-    double pad = 0;
-    float restore_ms = 0, coder_ms = 0;
-
-    wr_ctx* c = nullptr;
-    MaskStreams s;
-    size_t n = 0, nsym = 0;
-    uint32_t seg = 0, nseg = 0;
-    uint8_t* bits = nullptr;
-    unsigned long long* counters = nullptr;  // behind the bits
-    unsigned int h_bad = 0;
-    unsigned long long h_counters[2] = {0, 0};
-    bool partial = false;  // (MaskRegion) only some segments are decoded: the checks over the whole mask are not made
-
-    const unsigned char* plane() const { return blob + wrmask::kHeaderBytes; }
-    size_t plane_len() const { return len - wrmask::kHeaderBytes; }
-
-    // the header and the index, on the host: nothing is launched for a blob that fails here
-    int parse(size_t count)
-    {
-        n = count; nsym = wrmask::mask_bytes(n);
-        if (!blob) return fail(WR_ERR_ARG, "null coded buffer");
-        if (const char* why = wrmask::check_header(blob, len, n, &undefined, &pad)) return fail(WR_ERR_STREAM, why);
-        if (const char* why = wrseg::check_index(plane(), plane_len(), plane_len(), nsym, &seg, &nseg)) return fail(WR_ERR_STREAM, std::string("mask blob: ") + why);
-        return WR_OK;
-    }
-
-    // the buffers, the second stream, the blob and its offsets on the device
-    int upload(wr_ctx* ctx, SegBufs* bufs)
-    {
-        c = ctx;
-        const size_t bits_bytes = (nsym + 255) & ~(size_t)255;
-        bufs->mask[0] = plane_scratch(c, bits_bytes + 256);
-        bufs->mask[1] = plane_scratch(c, wrk::seg_decode_work_bytes(nseg));
-        bufs->mask[2] = plane_scratch(c, (plane_len() + 15) & ~(size_t)15);
-        for (const DevPlanes::Buf& b : bufs->mask) if (!b.p) return WR_ERR_HIP;
-        bits = bufs->mask[0].p;
-        counters = reinterpret_cast<unsigned long long*>(bits + bits_bytes);
-        if (int rc = s.create()) return rc;
-        bufs->also = s.st;
-        if (int rc = xfer_field(c, &c->x_field, bufs->mask[2].p, plane(), plane_len(), kUp)) return rc;
-        return seg_upload_offsets(plane(), wrseg::kHeaderBytes, nseg, bufs->mask[1].p);
-    }
-
-    // (cu_mu held) the mask's decoder and the count of its bits, on the second stream
-    int launch(SegBufs* bufs)
-    {
-        HIPCHK(hipEventRecord(s.ev[4], s.st));
-        wrk::seg_decode(bufs->mask[2].p, plane_len(), wrk::plane_ref(bits), nsym, seg, bufs->mask[1].p, s.st);
-        HIPCHK(hipEventRecord(s.ev[5], s.st));
-        wrk::mask_restore((double*)nullptr, n, bits, 0.0, counters, s.st);
-        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask decoder launch failed");
-        HIPCHK(hipMemcpyAsync(&h_bad, wrk::seg_work_bad(bufs->mask[1].p), sizeof h_bad, hipMemcpyDeviceToHost, s.st));
-        HIPCHK(hipMemcpyAsync(h_counters, counters, sizeof h_counters, hipMemcpyDeviceToHost, s.st));
-        return WR_OK;
-    }
-
-    // ... waited for and judged: the caller's field has not been touched yet
-    int check()
-    {
-        if (hipStreamSynchronize(s.st) != hipSuccess) return fail(WR_ERR_HIP, "the mask's decoder failed on the device");
-        coder_ms = s.ms(2);
-        if (h_bad) return fail(WR_ERR_STREAM, "mask blob: " + bad_segments_text(h_bad));
-        if (partial) return WR_OK;
-        if (h_counters[1]) return fail(WR_ERR_STREAM, "mask blob: a bit beyond the field's last sample is set");
-        if (h_counters[0] != undefined) return fail(WR_ERR_STREAM, "mask blob: the mask's set bits are not the count in its header");
-        return WR_OK;
-    }
-
-    // (the context's stream, behind the finisher) `fill` where a bit is set
-    template <class T>
-    int restore(T* d_x)
-    {
-        HIPCHK(hipEventRecord(s.ev[2], c->stream));
-        wrk::mask_restore(d_x, n, bits, (T)fill, counters, c->stream);
-        HIPCHK(hipEventRecord(s.ev[3], c->stream));
-        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask restore launch failed");
-        return WR_OK;
-    }
-
-    void result(wr_mask_result* res)
-    {
-        if (!res) return;
-        memset(res, 0, sizeof *res);
-        res->undefined = undefined; res->pad = pad; res->mask_len = len;
-        res->fill_ms = s.ev[2] ? s.ms(1) : 0; res->mask_coder_ms = coder_ms;
-    }
-};
+// a region as the mask's crop takes it (wr_mask.h); roi == nullptr: the whole box of the level
+wrmask::Region mask_region(int nx, int ny, int nz, int level, const wr_box* roi)
+{
+    const wrlow::Box b = wrlow::box_of(nx, ny, nz, level);
+    const wr_box whole{0, 0, 0, b.bx, b.by, b.bz};
+    if (!roi) roi = &whole;
+    return wrmask::Region{nx, ny, nz, level, roi->x0, roi->y0, roi->z0, roi->x1, roi->y1, roi->z1};
+}
 
 // wr_dev_mask_split / _f32: the split alone, as a stage call
 template <class T>
@@ -2248,10 +2199,8 @@ int dev_mask_restore_box(wr_ctx* c, T* d_out, int nx, int ny, int nz, int level,
     if (int rc = ctx_bind(c)) return rc;
     if (!d_out || !d_bits || !undefined) return fail(WR_ERR_ARG, "null pointer");
     if (nx < 1 || ny < 1 || nz < 1 || !wrlow::level_ok(level)) return fail(WR_ERR_ARG, "non-positive dimension or level outside [0, 4]");
-    const wrlow::Box b = wrlow::box_of(nx, ny, nz, level);
-    if (roi && !wrroi::roi_ok(b, *roi)) return fail(WR_ERR_ARG, "the region is empty or reaches outside the box of the level");
-    const wrmask::Region g = roi ? wrmask::Region{nx, ny, nz, level, roi->x0, roi->y0, roi->z0, roi->x1, roi->y1, roi->z1}
-                                 : wrmask::Region{nx, ny, nz, level, 0, 0, 0, b.bx, b.by, b.bz};
+    if (roi && !wrroi::roi_ok(wrlow::box_of(nx, ny, nz, level), *roi)) return fail(WR_ERR_ARG, "the region is empty or reaches outside the box of the level");
+    const wrmask::Region g = mask_region(nx, ny, nz, level, roi);
     std::lock_guard<std::mutex> lk(c->mu);
     StageLock cu(c->pool->cu_mu);
     unsigned long long* const counters = reinterpret_cast<unsigned long long*>(c->d_partial);
@@ -2590,102 +2539,230 @@ int seg_upload_lists(wr_ctx* c, const SegStream& s, int used, const unsigned cha
     return seg_upload_lists(c, s, used, data_enc, blob, work, bufs->bricks.p, ids, bricks, ms, bytes_up);
 }
 
-// The mask of a masked region or low-resolution decode (include/waverange_amd.h): MaskDecode with the mask cropped.  Only the
-// segments that hold a bit of the region are uploaded and decoded (wrmask::roi_segments) -- the bits buffer is still the whole
-// plane, written where those segments lie -- and the restore runs on the region as the finisher left it.
-struct MaskRegion : MaskDecode {
-    wrmask::Region g{};
-    std::vector<uint32_t> ids;
-    size_t bytes_up = 0;
-    float up_ms = 0;
+// ---- the mask stage of the decode drivers: what every masked decode does with the WRM1 blob behind a record's planes -- validate
+// it on the host, get the needed segments onto the device, decode them beside the field's planes, judge them -- written once.
+// MaskJob is one blob being decoded.  The drivers differ in where its buffers come from and in who launches its decode: the
+// single calls (MaskDecode below) on a stream of the mask's own, the batch call as one more job of its list launch.
+struct MaskJob {
+    const unsigned char* blob = nullptr;  // the WRM1 header, the WRS1 plane behind it
+    size_t len = 0;
+    wrmask::BlobInfo info;   // what the header and the index say
+    size_t n = 0, nsym = 0;  // the field's samples, the plane's symbols
+    std::vector<uint32_t> ids;  // the segments to decode, ascending; empty: the whole plane
+    // the device buffers: the plane (always full length: a listed decode writes where its segments lie), the decoder's offsets,
+    // flags and list, the blob's bytes
+    uint8_t *bits = nullptr, *work = nullptr, *d_blob = nullptr;
 
-    // (behind parse) the list of the region; roi == nullptr: the whole box of the level
-    void plan(int nx, int ny, int nz, int level, const wrlow::Box& box, const wr_box* roi)
+    const unsigned char* plane() const { return blob + wrmask::kHeaderBytes; }
+    size_t plane_len() const { return len - wrmask::kHeaderBytes; }
+
+    // the header and the whole index, on the host; false: refused, *why saying what ("mask blob: ...", a WR_ERR_STREAM)
+    bool parse(size_t count, std::string* why)
     {
-        partial = true;
-        g = roi ? wrmask::Region{nx, ny, nz, level, roi->x0, roi->y0, roi->z0, roi->x1, roi->y1, roi->z1}
-                : wrmask::Region{nx, ny, nz, level, 0, 0, 0, box.bx, box.by, box.bz};
-        ids.resize(wrmask::roi_segments(g, seg, nullptr, 0));
-        wrmask::roi_segments(g, seg, ids.data(), ids.size());
+        n = count; nsym = wrmask::mask_bytes(n);
+        return wrmask::check_blob(blob, len, n, &info, why);
+    }
+    // (behind parse) only the segments that hold a bit of one of the regions are decoded
+    void list(const wrmask::Region* gs, size_t nroi)
+    {
+        ids.resize(nroi == 1 ? wrmask::roi_segments(gs[0], info.seg, nullptr, 0) : wrmask::roi_segments_multi(gs, nroi, info.seg, nullptr, 0));
+        if (nroi == 1) wrmask::roi_segments(gs[0], info.seg, ids.data(), ids.size());
+        else wrmask::roi_segments_multi(gs, nroi, info.seg, ids.data(), ids.size());
+    }
+    // what the job takes from the plane pool; the driver says from where, and rounds as its pool does
+    size_t bits_bytes() const { return (nsym + 255) & ~(size_t)255; }
+    size_t work_bytes() const { return ids.empty() ? wrk::seg_decode_work_bytes(info.nseg) : wrk::seg_decode_list_work_bytes(info.nseg, ids.size()); }
+    size_t blob_bytes() const { return plane_len(); }
+    // stage "up" (the buffers set): the whole blob and its offsets, or the listed segments' bytes, the list and the offsets.
+    // ms, *bytes_up: as seg_upload_lists counts them (a whole plane counts nothing)
+    int upload(wr_ctx* c, float* ms, size_t* bytes_up) const
+    {
+        if (ids.empty()) {
+            if (int rc = xfer_field(c, &c->x_field, d_blob, plane(), plane_len(), kUp)) return rc;
+            return seg_upload_offsets(plane(), wrseg::kHeaderBytes, info.nseg, work);
+        }
+        SegStream one;  // the mask's plane as a stream of one WRS1 plane
+        one.nlay = 1; one.off[1] = plane_len(); one.seg[0] = info.seg; one.nseg[0] = info.nseg;
+        uint8_t *blob_of[1] = {d_blob}, *work_of[1] = {work};
+        return seg_upload_lists(c, one, 1, plane(), blob_of, work_of, nullptr, &ids, std::vector<uint32_t>(), ms, bytes_up);
+    }
+    // the job and the list of its decode, for a launch someone else makes (a WRS1 plane in the natural order)
+    wrk::SegJob seg_job() const { return ::seg_job(wrk::plane_ref(bits), d_blob, plane_len(), work, nsym, info.seg, info.nseg, 0); }
+    wrk::SegList seg_list() const
+    {
+        wrk::SegList ls;
+        memset(&ls, 0, sizeof ls);
+        ls.ids = wrk::seg_decode_list_ids(work, info.nseg); ls.nlist = (uint32_t)ids.size();
+        return ls;
+    }
+};
+
+// `fill` into the elements of region g that the host holds at fld, where a bit of the plane h_bits is set (the whole field: the
+// whole box of level 0).  Returns the count of those elements.
+size_t mask_restore_host(const FieldRef& fld, const wrmask::Region& g, const unsigned char* h_bits, double fill)
+{
+    const int cx = g.x1 - g.x0, cy = g.y1 - g.y0, cz = g.z1 - g.z0;
+    size_t at = 0, count = 0;
+    for (int z = 0; z < cz; z++)
+        for (int y = 0; y < cy; y++)
+            for (int x = 0; x < cx; x++, at++) {
+                const size_t J = g.bit(x, y, z);
+                if (!((h_bits[J >> 3] >> (J & 7)) & 1)) continue;
+                if (fld.host) fld.host[at] = fill;
+                else fld.host_f32[at] = (float)fill;
+                count++;
+            }
+    return count;
+}
+
+// The mask of the single masked calls: its job on a stream of its own, under the field's coder stage.  Two distinctions and no
+// others: the job HAS A LIST (a region or low-resolution decode, plan(): only those segments are uploaded and decoded, and the
+// checks over the whole mask cannot be made) or not, and the result IS A REGION of a level's box (the restore runs on the region
+// as the finisher left it and counts there) or the whole field.
+struct MaskDecode {
+    // what the caller gives: the blob behind the field's planes (job.blob, job.len), and what the undefined samples become
+    MaskJob job;
+    double fill = NAN;
+    // what comes out
+    float coder_ms = 0, up_ms = 0;
+    size_t bytes_up = 0;
+
+    wr_ctx* c = nullptr;
+    MaskStreams s;
+    wrmask::Region g{};   // where the restore runs: the whole box of level 0, or the region of plan()
+    bool region = false;  // plan() was called
+    unsigned long long* counters = nullptr;  // behind the bits
+    unsigned int h_bad = 0;
+    unsigned long long h_counters[2] = {0, 0};
+    bool restored = false;  // restore() has recorded its events
+
+    // the header and the index, on the host: nothing is launched for a blob that fails here
+    int parse(int nx, int ny, int nz)
+    {
+        if (!job.blob) return fail(WR_ERR_ARG, "null coded buffer");
+        std::string why;
+        if (!job.parse((size_t)nx * ny * nz, &why)) return fail(WR_ERR_STREAM, why);
+        g = mask_region(nx, ny, nz, 0, nullptr);
+        return WR_OK;
     }
 
-    // the buffers, the second stream, the listed segments' bytes, the list and the offsets on the device
+    // (behind parse) the list of the region; roi == nullptr: the whole box of the level
+    void plan(int level, const wr_box* roi)
+    {
+        region = true;
+        g = mask_region(g.nx, g.ny, g.nz, level, roi);
+        job.list(&g, 1);
+    }
+
+    // the buffers, the second stream, and the job's stage "up"
     int upload(wr_ctx* ctx, SegBufs* bufs)
     {
         c = ctx;
-        const size_t bits_bytes = (nsym + 255) & ~(size_t)255;
-        bufs->mask[0] = plane_scratch(c, bits_bytes + 256);
-        bufs->mask[1] = plane_scratch(c, wrk::seg_decode_list_work_bytes(nseg, ids.size()));
-        bufs->mask[2] = plane_scratch(c, (plane_len() + 15) & ~(size_t)15);
+        bufs->mask[0] = plane_scratch(c, job.bits_bytes() + 256);
+        bufs->mask[1] = plane_scratch(c, job.work_bytes());
+        bufs->mask[2] = plane_scratch(c, (job.blob_bytes() + 15) & ~(size_t)15);
         for (const DevPlanes::Buf& b : bufs->mask) if (!b.p) return WR_ERR_HIP;
-        bits = bufs->mask[0].p;
-        counters = reinterpret_cast<unsigned long long*>(bits + bits_bytes);
+        job.bits = bufs->mask[0].p; job.work = bufs->mask[1].p; job.d_blob = bufs->mask[2].p;
+        counters = reinterpret_cast<unsigned long long*>(job.bits + job.bits_bytes());
         if (int rc = s.create()) return rc;
         bufs->also = s.st;
-        SegStream one;  // the mask's plane as a stream of one WRS1 plane
-        one.nlay = 1; one.off[1] = plane_len(); one.seg[0] = seg; one.nseg[0] = nseg;
-        uint8_t *blob_of[1] = {bufs->mask[2].p}, *work_of[1] = {bufs->mask[1].p};
-        if (int rc = seg_upload_lists(c, one, 1, plane(), blob_of, work_of, nullptr, &ids, std::vector<uint32_t>(), &up_ms, &bytes_up)) return rc;
+        if (int rc = job.upload(c, &up_ms, &bytes_up)) return rc;
         g_stat[WR_STAT_MASK_ROI_BYTES_UP] += bytes_up;
         return WR_OK;
     }
 
-    // (cu_mu held) the mask's list decoder on the second stream
-    int launch(SegBufs* bufs)
+    // (cu_mu held) on the second stream: the list decoder, or the whole plane's decoder and the count of its bits
+    int launch()
     {
         HIPCHK(hipEventRecord(s.ev[4], s.st));
-        wrk::seg_decode_list(bufs->mask[2].p, plane_len(), wrk::plane_ref(bits), nsym, seg, bufs->mask[1].p, ids.size(), s.st, 0, 0);
+        if (!job.ids.empty()) wrk::seg_decode_list(job.d_blob, job.plane_len(), wrk::plane_ref(job.bits), job.nsym, job.info.seg, job.work, job.ids.size(), s.st, 0, 0);
+        else wrk::seg_decode(job.d_blob, job.plane_len(), wrk::plane_ref(job.bits), job.nsym, job.info.seg, job.work, s.st);
         HIPCHK(hipEventRecord(s.ev[5], s.st));
+        if (job.ids.empty()) wrk::mask_restore((double*)nullptr, job.n, job.bits, 0.0, counters, s.st);
         if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask decoder launch failed");
-        HIPCHK(hipMemcpyAsync(&h_bad, wrk::seg_work_bad(bufs->mask[1].p), sizeof h_bad, hipMemcpyDeviceToHost, s.st));
-        g_stat[WR_STAT_MASK_ROI_SEGMENTS] += ids.size();
+        HIPCHK(hipMemcpyAsync(&h_bad, wrk::seg_work_bad(job.work), sizeof h_bad, hipMemcpyDeviceToHost, s.st));
+        if (job.ids.empty()) HIPCHK(hipMemcpyAsync(h_counters, counters, sizeof h_counters, hipMemcpyDeviceToHost, s.st));
+        g_stat[WR_STAT_MASK_ROI_SEGMENTS] += job.ids.size();
         return WR_OK;
     }
 
-    // (the context's stream, behind the finisher) `fill` into the region at d_out where a bit is set; the count comes back with
-    // the stream's next synchronisation
+    // ... waited for and judged: the caller's field has not been touched yet.  The two checks over the whole mask need the
+    // whole plane: a listed decode does not make them.
+    int check()
+    {
+        if (hipStreamSynchronize(s.st) != hipSuccess) return fail(WR_ERR_HIP, "the mask's decoder failed on the device");
+        coder_ms = s.ms(2);
+        if (h_bad) return fail(WR_ERR_STREAM, "mask blob: " + bad_segments_text(h_bad));
+        if (!job.ids.empty()) return WR_OK;
+        if (h_counters[1]) return fail(WR_ERR_STREAM, "mask blob: a bit beyond the field's last sample is set");
+        if (h_counters[0] != job.info.undefined) return fail(WR_ERR_STREAM, "mask blob: the mask's set bits are not the count in its header");
+        return WR_OK;
+    }
+
+    // the mask alone, decoded and judged: a constant record, which has no coder stage to run beside
+    int decode_alone(wr_ctx* ctx, SegBufs* bufs)
+    {
+        if (int rc = upload(ctx, bufs)) return rc;
+        StageLock cu(ctx->pool->cu_mu);
+        if (int rc = launch()) return rc;
+        return check();
+    }
+
+    // (the context's stream, behind the finisher) `fill` where a bit is set: over the whole field at d_x, or into the region at
+    // d_x, whose count comes back with the stream's next synchronisation
     template <class T>
-    int restore_box(T* d_out)
+    int restore(T* d_x)
     {
         HIPCHK(hipEventRecord(s.ev[2], c->stream));
-        wrk::mask_restore_box(d_out, g, bits, (T)fill, counters, c->stream);
+        if (region) wrk::mask_restore_box(d_x, g, job.bits, (T)fill, counters, c->stream);
+        else wrk::mask_restore(d_x, job.n, job.bits, (T)fill, counters, c->stream);
         HIPCHK(hipEventRecord(s.ev[3], c->stream));
         if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask restore launch failed");
-        HIPCHK(hipMemcpyAsync(h_counters, counters, sizeof h_counters[0], hipMemcpyDeviceToHost, c->stream));
+        if (region) HIPCHK(hipMemcpyAsync(h_counters, counters, sizeof h_counters[0], hipMemcpyDeviceToHost, c->stream));
         restored = true;
         return WR_OK;
     }
 
-    // a host caller's region of a constant padded field: the bits come to the host, as midval was put there
-    int restore_host(const FieldRef& fld)
+    // the plane as the device holds it, to the host
+    int host_bits(std::vector<unsigned char>* h) const
     {
-        std::vector<unsigned char> h(nsym);
-        HIPCHK(hipMemcpy(h.data(), bits, nsym, hipMemcpyDeviceToHost));
-        const int cx = g.x1 - g.x0, cy = g.y1 - g.y0, cz = g.z1 - g.z0;
-        size_t at = 0;
-        h_counters[0] = 0;
-        for (int z = 0; z < cz; z++)
-            for (int y = 0; y < cy; y++)
-                for (int x = 0; x < cx; x++, at++) {
-                    const size_t J = g.bit(x, y, z);
-                    if (!((h[J >> 3] >> (J & 7)) & 1)) continue;
-                    if (fld.host) fld.host[at] = fill;
-                    else fld.host_f32[at] = (float)fill;
-                    h_counters[0]++;
-                }
+        h->resize(job.nsym);
+        HIPCHK(hipMemcpy(h->data(), job.bits, job.nsym, hipMemcpyDeviceToHost));
         return WR_OK;
     }
 
-    bool restored = false;  // restore_box has recorded its events
+    // a host caller's constant padded field: the bits come to the host, as midval was put there
+    int restore_host(const FieldRef& fld)
+    {
+        std::vector<unsigned char> h;
+        if (int rc = host_bits(&h)) return rc;
+        h_counters[0] = mask_restore_host(fld, g, h.data(), fill);
+        return WR_OK;
+    }
 
+    // undefined: the header's count (judged against the plane), or the count inside the region
     void result(wr_mask_result* res)
     {
         if (!res) return;
         memset(res, 0, sizeof *res);
-        res->undefined = h_counters[0]; res->pad = pad; res->mask_len = len;
+        res->undefined = region ? h_counters[0] : job.info.undefined; res->pad = job.info.pad; res->mask_len = job.len;
         res->fill_ms = restored ? s.ms(1) : 0; res->mask_coder_ms = coder_ms;
     }
 };
+
+// A constant padded field with a mask (the mask judged: decode_alone): midval in the `count` elements, then the mask.  A host
+// field takes the bits on the host, as it takes midval there.
+int finish_constant_masked(wr_ctx* c, const FieldRef& fld, size_t count, double midval, MaskDecode* msk, double t0, wr_timings* local, wr_timings* tm)
+{
+    if (int rc = fill_constant(c, fld, count, midval)) return rc;
+    if (fld.dev) {
+        StageLock cu(c->pool->cu_mu);
+        if (int rc = kernel_stage_end(c, msk->restore(fld.dev))) return rc;
+    } else if (int rc = msk->restore_host(fld)) return rc;
+    local->total = now() - t0;
+    if (tm) *tm = *local;
+    return WR_OK;
+}
 
 // One coder stage (cu_mu held): the first `planes` planes of the stream, from bufs->blob[l] into q[l].
 struct CoderCall {
@@ -2788,69 +2865,14 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
     DevPool* const pool = c->pool;
     SegStream s;
     if (int rc = seg_stream_of(nx, ny, nz, info, data_enc, data_len, &s)) return rc;
-    if (msk) if (int rc = msk->parse(n)) return rc;
-    std::vector<unsigned char> cbits;  // a constant masked record that is measured: the mask on the host
-    if (s.constant && msk) {  // midval everywhere, then the mask: a host field takes the bits on the host, as it takes midval there
-        if (int rc = msk->upload(c, &bufs)) return rc;
-        {
-            StageLock cu(pool->cu_mu);
-            if (int rc = msk->launch(&bufs)) return rc;
-            if (int rc = msk->check()) return rc;
-        }
-        if (err_out) {
-            cbits.resize(msk->nsym);
-            HIPCHK(hipMemcpy(cbits.data(), msk->bits, msk->nsym, hipMemcpyDeviceToHost));
-        }
+    if (msk) if (int rc = msk->parse(nx, ny, nz)) return rc;
+    if (s.constant && msk) if (int rc = msk->decode_alone(c, &bufs)) return rc;
+    if (s.constant && err_out) {
+        std::vector<unsigned char> cbits;  // a masked record that is measured: the mask on the host
+        if (msk) if (int rc = msk->host_bits(&cbits)) return rc;
+        return constant_error_stats(fld, n, info->midval, msk ? cbits.data() : nullptr, msk ? n - (size_t)msk->job.info.undefined : n, err_out, stats_out, defined_out);
     }
-    if (s.constant && msk && !err_out) {
-        if (int rc = fill_constant(c, fld, n, info->midval)) return rc;
-        if (fld.dev) {
-            StageLock cu(pool->cu_mu);
-            if (int rc = kernel_stage_end(c, msk->restore(fld.dev))) return rc;
-        } else {
-            std::vector<unsigned char> bits(msk->nsym);
-            HIPCHK(hipMemcpy(bits.data(), msk->bits, msk->nsym, hipMemcpyDeviceToHost));
-            for (size_t j = 0; j < n; j++) {
-                if (!((bits[j >> 3] >> (j & 7)) & 1)) continue;
-                if (fld.host) fld.host[j] = msk->fill;
-                else fld.host_f32[j] = (float)msk->fill;
-            }
-        }
-        local.total = now() - t0;
-        if (tm) *tm = local;
-        return WR_OK;
-    }
-    if (s.constant && err_out) {  // the reconstruction is midval everywhere (fill_constant)
-        double mx = 0;
-        size_t bad = 0, count = n;
-        auto undef = [&](size_t j) { return !cbits.empty() && ((cbits[j >> 3] >> (j & 7)) & 1); };
-        if (msk) count = n - (size_t)msk->undefined;
-        if (defined_out) *defined_out = count;
-        for (size_t j = 0; j < n; j++) {
-            if (undef(j)) continue;
-            const double d = fld.host ? fabs(fld.host[j] - info->midval) : fabs((double)fld.host_f32[j] - (double)(float)info->midval);
-            if (d <= DBL_MAX) mx = d > mx ? d : mx;
-            else bad++;
-        }
-        if (stats_out) {  // S by a compensated sum (Neumaier): its error does not grow with n
-            double sum = 0, comp = 0, lo = NAN, hi = NAN;
-            for (size_t j = 0; j < n; j++) {
-                if (undef(j)) continue;
-                const double v = fld.host ? fld.host[j] : (double)fld.host_f32[j];
-                lo = fmin(lo, v); hi = fmax(hi, v);
-                const double d = fld.host ? v - info->midval : v - (double)(float)info->midval;
-                if (!(fabs(d) <= DBL_MAX)) continue;
-                const double q = d * d, t = sum + q;
-                comp += sum >= q ? (sum - t) + q : (q - t) + sum;
-                sum = t;
-            }
-            if (sum <= DBL_MAX) sum += comp;
-            fill_error_stats(stats_out, mx, (double)bad, sum, count, lo, hi);
-        }
-        if (bad) return fail(WR_ERR_ARG, std::to_string(bad) + " difference(s) between the field and the reconstruction are not finite");
-        *err_out = mx;
-        return WR_OK;
-    }
+    if (s.constant && msk) return finish_constant_masked(c, fld, n, info->midval, msk, t0, &local, tm);
     if (s.constant) return finish_constant(c, fld, n, info->midval, t0, &local, tm);
     {
         std::lock_guard<std::mutex> gather(pool->planes.gather_mu);  // one decode at a time gathers its planes (decode_impl)
@@ -2884,7 +2906,7 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
     {
         StageLock cu(pool->cu_mu);
         clock_warmup(c, n);
-        if (msk) if (int rc = msk->launch(&bufs)) return rc;  // (on its own stream, under the field's coder stage)
+        if (msk) if (int rc = msk->launch()) return rc;  // (on its own stream, under the field's coder stage)
         CoderCall k{&s, info, s.nlay, n, &bufs, p.q};
         for (int l = 0; l < s.nlay; l++) k.perm[l] = bufs.perm.p;
         if (int rc = seg_coder_stage(c, k, &local)) return rc;
@@ -2902,12 +2924,12 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
                 float* const f32 = reinterpret_cast<float*>(bufs.trial[2].p);
                 double* const f64 = reinterpret_cast<double*>(bufs.trial[2].p);
                 if (msk) {
-                    rc = fld.host_f32 ? BoundedSearch::compare_stats_masked(c, (const float*)f32, (const float*)d_f32, n, msk->bits, &st, &defined)
-                                      : BoundedSearch::compare_stats_masked(c, (const double*)f64, (const double*)d_fld, n, msk->bits, &st, &defined);
+                    rc = fld.host_f32 ? BoundedSearch::compare_stats_masked(c, (const float*)f32, (const float*)d_f32, n, msk->job.bits, &st, &defined)
+                                      : BoundedSearch::compare_stats_masked(c, (const double*)f64, (const double*)d_fld, n, msk->job.bits, &st, &defined);
                     // lo and hi of the defined samples: the blob's pad, their mean, stands in for the others in the field's copy
-                    if (rc == WR_OK && msk->undefined) {
-                        if (fld.host_f32) wrk::mask_fill(f32, n, msk->bits, (float)msk->pad, c->stream);
-                        else wrk::mask_fill(f64, n, msk->bits, msk->pad, c->stream);
+                    if (rc == WR_OK && msk->job.info.undefined) {
+                        if (fld.host_f32) wrk::mask_fill(f32, n, msk->job.bits, (float)msk->job.info.pad, c->stream);
+                        else wrk::mask_fill(f64, n, msk->job.bits, msk->job.info.pad, c->stream);
                         if (hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "mask fill launch failed");
                     }
                 } else {
@@ -2937,7 +2959,7 @@ int decode_seg_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, const wr_en
 // msk != nullptr (wr_decode_*_seg_roi_masked): the mask blob of a masked record, cropped to the region: judged before the
 // result is written anywhere the caller can see, and applied behind the finisher
 int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int level, int max_planes, const wr_box* roi, const wr_enc_info* info,
-                           const unsigned char* data_enc, size_t data_len, wr_timings* tm, MaskRegion* msk = nullptr)
+                           const unsigned char* data_enc, size_t data_len, wr_timings* tm, MaskDecode* msk = nullptr)
 {
     if (int rc = ctx_bind(c)) return rc;
     if (!info) return fail(WR_ERR_ARG, "null wr_enc_info");
@@ -2959,24 +2981,12 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     SegStream s;
     if (int rc = seg_stream_of(nx, ny, nz, info, data_enc, data_len, &s)) return rc;
     if (msk) {
-        if (int rc = msk->parse(n)) return rc;
-        msk->plan(nx, ny, nz, level, pl.box, roi);
+        if (int rc = msk->parse(nx, ny, nz)) return rc;
+        msk->plan(level, roi);
     }
-    if (s.constant && msk) {  // midval in the region, then the mask (decode_seg_impl)
-        if (int rc = msk->upload(c, &bufs)) return rc;
-        {
-            StageLock cu(pool->cu_mu);
-            if (int rc = msk->launch(&bufs)) return rc;
-            if (int rc = msk->check()) return rc;
-        }
-        if (int rc = fill_constant(c, fld, nbox, info->midval)) return rc;
-        if (fld.dev) {
-            StageLock cu(pool->cu_mu);
-            if (int rc = kernel_stage_end(c, msk->restore_box(fld.dev))) return rc;
-        } else if (int rc = msk->restore_host(fld)) return rc;
-        local.total = now() - t0;
-        if (tm) *tm = local;
-        return WR_OK;
+    if (s.constant && msk) {
+        if (int rc = msk->decode_alone(c, &bufs)) return rc;
+        return finish_constant_masked(c, fld, nbox, info->midval, msk, t0, &local, tm);
     }
     if (s.constant) return finish_constant(c, fld, nbox, info->midval, t0, &local, tm);
     const int used = pl.planes;
@@ -3020,7 +3030,7 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
     {
         StageLock cu(pool->cu_mu);
         clock_warmup(c, pl.work_elems());
-        if (msk) if (int rc = msk->launch(&bufs)) return rc;  // (on its own stream, under the field's coder stage)
+        if (msk) if (int rc = msk->launch()) return rc;  // (on its own stream, under the field's coder stage)
         CoderCall k{&s, info, used, n, &bufs, p.q};
         for (int l = 0; l < used; l++) k.perm[l] = bufs.perm.p;
         k.ids = ids;
@@ -3037,7 +3047,7 @@ int decode_seg_lowres_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, int 
             launch_note(c, "dequant_box", used - 1, d_box, nbox, nullptr, p.q[used - 1]);
             rc = lowres_from_planes(c, slot.get(), d_box, nx, ny, pl, p, fld.host_f32 ? &d_f32 : nullptr);
         }
-        if (rc == WR_OK && msk) rc = fld.host_f32 ? msk->restore_box(d_f32) : msk->restore_box(d_box);
+        if (rc == WR_OK && msk) rc = fld.host_f32 ? msk->restore(d_f32) : msk->restore(d_box);
         rc = kernel_stage_end(c, rc);
     }
     if (rc) return rc;
@@ -3680,7 +3690,7 @@ static int decode_seg_masked(wr_ctx* c, FieldRef f, int nx, int ny, int nz, cons
         return decode_seg_impl(c, f, nx, ny, nz, info, data_enc, data_len, tm);
     if (!data_enc) return fail(WR_ERR_ARG, "null coded buffer");
     MaskDecode m;
-    m.blob = data_enc + info->ntot_enc; m.len = data_len - info->ntot_enc; m.fill = fill;
+    m.job.blob = data_enc + info->ntot_enc; m.job.len = data_len - info->ntot_enc; m.fill = fill;
     const int rc = decode_seg_impl(c, f, nx, ny, nz, info, data_enc, info->ntot_enc, tm, nullptr, nullptr, &m);
     if (rc == WR_OK) m.result(res);
     return rc;
@@ -3774,7 +3784,7 @@ static int seg_error_stats_masked(wr_ctx* c, FieldRef f, int nx, int ny, int nz,
         return decode_seg_impl(c, f, nx, ny, nz, info, data_enc, data_len, nullptr, nullptr, stats, nullptr, defined);
     if (!data_enc) return fail(WR_ERR_ARG, "null coded buffer");
     MaskDecode m;
-    m.blob = data_enc + info->ntot_enc; m.len = data_len - info->ntot_enc;
+    m.job.blob = data_enc + info->ntot_enc; m.job.len = data_len - info->ntot_enc;
     return decode_seg_impl(c, f, nx, ny, nz, info, data_enc, info->ntot_enc, nullptr, nullptr, stats, &m, defined);
 }
 
@@ -3810,8 +3820,8 @@ static int decode_seg_roi_masked(wr_ctx* c, FieldRef f, int nx, int ny, int nz, 
     if (data_len == 0 || data_len <= info->ntot_enc)  // an unmasked record (a shorter buffer: the plain call refuses it)
         return decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, roi, info, data_enc, data_len, tm);
     if (!data_enc) return fail(WR_ERR_ARG, "null coded buffer");
-    MaskRegion m;
-    m.blob = data_enc + info->ntot_enc; m.len = data_len - info->ntot_enc; m.fill = fill;
+    MaskDecode m;
+    m.job.blob = data_enc + info->ntot_enc; m.job.len = data_len - info->ntot_enc; m.fill = fill;
     const int rc = decode_seg_lowres_impl(c, f, nx, ny, nz, level, max_planes, roi, info, data_enc, info->ntot_enc, tm, &m);
     if (rc == WR_OK) m.result(res);
     return rc;
@@ -4801,10 +4811,9 @@ int roi_multi_plans(int nx, int ny, int nz, int level, int max_planes, const wr_
     return WR_OK;
 }
 
-// the slot of the window stage: sized for the largest window
-SlotNeed roi_multi_need(const std::vector<LowresPlan>& pls)
+// the slot of the window stage: sized for the largest window of the plans, and no smaller than `need` (a batch: the fields in turn)
+SlotNeed roi_multi_need(const std::vector<LowresPlan>& pls, SlotNeed need = SlotNeed())
 {
-    SlotNeed need;
     for (const LowresPlan& pl : pls) {
         SlotNeed nd;
         pl.need(false, &nd);
@@ -4813,6 +4822,29 @@ SlotNeed roi_multi_need(const std::vector<LowresPlan>& pls)
         need.lowbuf_elems = std::max(need.lowbuf_elems, nd.lowbuf_elems);
     }
     return need;
+}
+
+// What the regions of one field need of its stream: on a blocked stream the union of their bricks, the same in every plane, and
+// per used plane the union of the segments (ids[0 .. used)).  false: a blocked stream with too many bricks.
+bool roi_multi_lists(const SegStream& s, int nx, int ny, int nz, const std::vector<LowresPlan>& pls, int used, std::vector<uint32_t>* ids,
+                     std::vector<uint32_t>* bricks)
+{
+    std::vector<wrroi::Geometry> geos(pls.size());
+    for (size_t i = 0; i < pls.size(); i++) geos[i] = pls[i].win;
+    if (s.brick) {
+        if (s.od.nbricks > 0x7fffffffu) return false;
+        wrblk::region_bricks_multi(s.od, geos.data(), geos.size(), bricks);
+    }
+    seg_plane_lists(s, used, ids, [&](uint32_t seg, std::vector<uint32_t>* out) {
+        if (s.brick) {
+            out->resize(wrblk::region_segments_multi(s.od, geos.data(), geos.size(), seg, nullptr, 0));
+            wrblk::region_segments_multi(s.od, geos.data(), geos.size(), seg, out->data(), out->size());
+        } else {
+            out->resize(wrroi::segments_of_multi(nx, ny, nz, geos.data(), geos.size(), seg, nullptr, 0));
+            wrroi::segments_of_multi(nx, ny, nz, geos.data(), geos.size(), seg, out->data(), out->size());
+        }
+    });
+    return true;
 }
 
 // Kernel stage (slot leased, cu_mu held): the regions one after another on the stream, region i's crop at d_out + offs[i]
@@ -4861,25 +4893,8 @@ int decode_seg_roi_multi_impl(wr_ctx* c, FieldRef fld, int nx, int ny, int nz, i
     if (int rc = seg_stream_of(nx, ny, nz, info, data_enc, data_len, &s)) return rc;
     if (s.constant) return finish_constant(c, fld, total, info->midval, t0, &local, tm);  // midval in every region
     const int used = pls[0].planes;
-    std::vector<wrroi::Geometry> geos(pls.size());
-    for (size_t i = 0; i < pls.size(); i++) geos[i] = pls[i].win;
-    // a blocked stream: the union of the bricks the regions need, the same in every plane
-    std::vector<uint32_t> bricks;
-    if (s.brick) {
-        if (s.od.nbricks > 0x7fffffffu) return fail(WR_ERR_ARG, "too many bricks");
-        wrblk::region_bricks_multi(s.od, geos.data(), geos.size(), &bricks);
-    }
-    // per plane the union of the segments the regions need
-    std::vector<uint32_t> ids[WR_NLAYMAX];
-    seg_plane_lists(s, used, ids, [&](uint32_t seg, std::vector<uint32_t>* out) {
-        if (s.brick) {
-            out->resize(wrblk::region_segments_multi(s.od, geos.data(), geos.size(), seg, nullptr, 0));
-            wrblk::region_segments_multi(s.od, geos.data(), geos.size(), seg, out->data(), out->size());
-        } else {
-            out->resize(wrroi::segments_of_multi(nx, ny, nz, geos.data(), geos.size(), seg, nullptr, 0));
-            wrroi::segments_of_multi(nx, ny, nz, geos.data(), geos.size(), seg, out->data(), out->size());
-        }
-    });
+    std::vector<uint32_t> bricks, ids[WR_NLAYMAX];
+    if (!roi_multi_lists(s, nx, ny, nz, pls, used, ids, &bricks)) return fail(WR_ERR_ARG, "too many bricks");
     unsigned long long lanes = 0;
     for (int l = 0; l < used; l++) lanes += ids[l].size();
     if (lanes >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the call has 2^31 segments or more");
@@ -5097,10 +5112,10 @@ struct ListJobs {
             wrk::SegList ls;
             memset(&ls, 0, sizeof ls);
             ls.ids = d_ids; ls.nlist = (uint32_t)nlist;
-            plain.push_back(job);
-            plain_lists.push_back(ls);
+            add(job, ls);
         }
     }
+    void add(const wrk::SegJob& job, const wrk::SegList& ls) { plain.push_back(job); plain_lists.push_back(ls); }
     // the lanes of the two launches, each below 2^31 (false: refused)
     bool lanes_ok() const
     {
@@ -5128,19 +5143,10 @@ struct RoiBatchField : BatchField {  // ... of a region decode: its plans, its l
     uint8_t* perms[WR_NLAYMAX] = {nullptr};  // a WRS2 field: one stream-order plane per job (all jobs go in one launch)
     uint8_t* d_bricks = nullptr;
     int job0 = 0;  // its first job's place in the failure counts
-    // a masked record of the masked call: its blob as the host has validated it (MaskDecode::parse), the union of the mask
-    // segments the regions need, the job's buffers and its place in the failure counts
-    bool masked = false;
-    const unsigned char* mblob = nullptr;  // the WRM1 header, the WRS1 plane behind it
-    size_t mlen = 0, msym = 0;
-    unsigned long long mundefined = 0;
-    double mpad = 0;
-    uint32_t mseg = 0, mnseg = 0;
-    std::vector<uint32_t> mids;
-    uint8_t *mbits = nullptr, *md_blob = nullptr, *mwork = nullptr;
-    int mjob = 0;
-    const unsigned char* mplane() const { return mblob + wrmask::kHeaderBytes; }
-    size_t mplane_len() const { return mlen - wrmask::kHeaderBytes; }
+    // a masked record of the masked call (mask.len != 0): its blob as the host has validated it, the union of the mask
+    // segments the regions need and the job's buffers (MaskJob); the job's place in the failure counts comes behind the planes'
+    MaskJob mask;
+    bool has_mask() const { return mask.len != 0; }
 };
 
 // what the masked call adds (wr_decode_*_seg_roi_batch_masked)
@@ -5186,41 +5192,32 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
     size_t njobs = 0, nmask = 0;
     for (int f = 0; f < nfields; f++) {
         RoiBatchField& b = bf[f];
-        b.masked = mb && data_lens[f] != 0 && data_lens[f] > infos[f].ntot_enc;  // (as the single masked call tells the two apart)
-        if (int rc = seg_stream_of(nx, ny, nz, &infos[f], data_encs[f], b.masked ? infos[f].ntot_enc : data_lens[f], &b.s, "field " + std::to_string(f) + ": ")) return rc;
+        const bool masked = mb && data_lens[f] != 0 && data_lens[f] > infos[f].ntot_enc;  // (as the single masked call tells the two apart)
+        if (int rc = seg_stream_of(nx, ny, nz, &infos[f], data_encs[f], masked ? infos[f].ntot_enc : data_lens[f], &b.s, "field " + std::to_string(f) + ": ")) return rc;
+        if (masked) {
+            b.mask.len = data_lens[f] - infos[f].ntot_enc;
+            nmask++;
+        }
         if (b.s.constant) continue;
         b.used = b.pls[0].planes;
         njobs += (size_t)b.used;
     }
     // ---- 3. (the masked call) every blob's header and whole segment index, as the single masked region call validates them
-    std::vector<wrmask::Region> mregions;
-    if (mb) {
-        std::vector<const unsigned char*> blobs((size_t)nfields, nullptr);
-        std::vector<size_t> blens((size_t)nfields, 0);
-        std::vector<wrmask::BlobInfo> binfo((size_t)nfields);
-        for (int f = 0; f < nfields; f++) {
-            RoiBatchField& b = bf[f];
-            if (!b.masked) continue;
-            if (!data_encs[f]) return fail(WR_ERR_ARG, "field " + std::to_string(f) + ": null coded buffer");
-            blobs[f] = b.mblob = data_encs[f] + infos[f].ntot_enc;
-            blens[f] = b.mlen = data_lens[f] - infos[f].ntot_enc;
-            b.msym = wrmask::mask_bytes(n);
-            nmask++;
-        }
+    for (int f = 0; f < nfields; f++) {
+        if (!bf[f].has_mask()) continue;
+        if (!data_encs[f]) return fail(WR_ERR_ARG, "field " + std::to_string(f) + ": null coded buffer");
+        bf[f].mask.blob = data_encs[f] + infos[f].ntot_enc;
+    }
+    for (int f = 0; f < nfields; f++) {
         std::string why;
-        const int bad = wrmask::check_blobs(blobs.data(), blens.data(), nfields, n, binfo.data(), &why);
-        if (bad < nfields) return fail(WR_ERR_STREAM, "field " + std::to_string(bad) + ": " + why);
-        for (int f = 0; f < nfields; f++) {
-            RoiBatchField& b = bf[f];
-            b.mundefined = binfo[f].undefined; b.mpad = binfo[f].pad; b.mseg = binfo[f].seg; b.mnseg = binfo[f].nseg;
-        }
+        if (bf[f].has_mask() && !bf[f].mask.parse(n, &why)) return fail(WR_ERR_STREAM, "field " + std::to_string(f) + ": " + why);
     }
     if (njobs + nmask > WR_SEG_BATCH_MAX)
         return fail(WR_ERR_ARG, "too many jobs: the call has " + std::to_string(njobs) + " (field, plane) pairs" + (mb ? " and " + std::to_string(nmask) + " masks" : std::string()) +
                                     ", WR_SEG_BATCH_MAX is " + std::to_string(WR_SEG_BATCH_MAX));
+    std::vector<wrmask::Region> mregions;
     if (nmask) {
-        mregions.resize((size_t)nroi);
-        for (int i = 0; i < nroi; i++) mregions[i] = wrmask::Region{nx, ny, nz, level, rois[i].x0, rois[i].y0, rois[i].z0, rois[i].x1, rois[i].y1, rois[i].z1};
+        for (int i = 0; i < nroi; i++) mregions.push_back(mask_region(nx, ny, nz, level, &rois[i]));
         if (!wrmask::boxes_turns(mregions.data(), mregions.size(), nullptr) ||
             (unsigned long long)nmask * wrmask::boxes_turns(mregions.data(), mregions.size(), nullptr) >= wrmask::kTurnLimit)
             return fail(WR_ERR_ARG, "too many turns: the restore launch of the call has 2^31 or more");
@@ -5234,38 +5231,20 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
         RoiBatchField& b = bf[f];
         if (b.s.constant) continue;
         const SegStream& s = b.s;
-        std::vector<wrroi::Geometry> geos(b.pls.size());
-        for (size_t i = 0; i < b.pls.size(); i++) geos[i] = b.pls[i].win;
-        if (s.brick) {
-            if (s.od.nbricks > 0x7fffffffu) return fail(WR_ERR_ARG, "field " + std::to_string(f) + ": too many bricks");
-            wrblk::region_bricks_multi(s.od, geos.data(), geos.size(), &b.bricks);
-        }
-        seg_plane_lists(s, b.used, b.ids, [&](uint32_t seg, std::vector<uint32_t>* out) {
-            if (s.brick) {
-                out->resize(wrblk::region_segments_multi(s.od, geos.data(), geos.size(), seg, nullptr, 0));
-                wrblk::region_segments_multi(s.od, geos.data(), geos.size(), seg, out->data(), out->size());
-            } else {
-                out->resize(wrroi::segments_of_multi(nx, ny, nz, geos.data(), geos.size(), seg, nullptr, 0));
-                wrroi::segments_of_multi(nx, ny, nz, geos.data(), geos.size(), seg, out->data(), out->size());
-            }
-        });
+        if (!roi_multi_lists(s, nx, ny, nz, b.pls, b.used, b.ids, &b.bricks)) return fail(WR_ERR_ARG, "field " + std::to_string(f) + ": too many bricks");
         for (int l = 0; l < b.used; l++) {
             if (s.strands) lanes_stranded += wrsb::job_lanes(b.ids[l].size(), s.strands);
             else lanes_plain += b.ids[l].size();
         }
         (s.strands ? nstranded : nplain) += (size_t)b.used;
-        const SlotNeed nd = roi_multi_need(b.pls);
-        need.field_elems = std::max(need.field_elems, nd.field_elems);
-        need.scratch_elems = std::max(need.scratch_elems, nd.scratch_elems);
-        need.lowbuf_elems = std::max(need.lowbuf_elems, nd.lowbuf_elems);
+        need = roi_multi_need(b.pls, need);
     }
     // a mask is a WRS1 plane in the natural order whatever its field part is: one more job of the plain launch
     for (int f = 0; f < nfields; f++) {
         RoiBatchField& b = bf[f];
-        if (!b.masked) continue;
-        b.mids.resize(wrmask::roi_segments_multi(mregions.data(), mregions.size(), b.mseg, nullptr, 0));
-        wrmask::roi_segments_multi(mregions.data(), mregions.size(), b.mseg, b.mids.data(), b.mids.size());
-        lanes_plain += b.mids.size();
+        if (!b.has_mask()) continue;
+        b.mask.list(mregions.data(), mregions.size());
+        lanes_plain += b.mask.ids.size();
         nplain++;
     }
     if (lanes_plain >= wrsb::kLaneLimit || lanes_stranded >= wrsb::kLaneLimit) return fail(WR_ERR_ARG, "too many segments: a launch of the call has 2^31 lanes or more");
@@ -5286,11 +5265,11 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
                 if (b.s.brick && !(b.perms[l] = bufs.take(batch_perm_bytes(n, b.s.brick)))) return fail_at("field", f, WR_ERR_HIP);
             }
             if (b.used && b.s.brick && !(b.d_bricks = bufs.take(roi_batch_bricks_bytes(b.bricks.size())))) return fail_at("field", f, WR_ERR_HIP);
-            if (b.masked) {
-                b.mbits = bufs.take(roi_batch_mask_plane_bytes(n));
-                b.md_blob = bufs.take(b.mplane_len());
-                b.mwork = bufs.take(roi_batch_work_bytes(b.mnseg, b.mids.size()));
-                if (!b.mbits || !b.md_blob || !b.mwork) return fail_at("field", f, WR_ERR_HIP);
+            if (b.has_mask()) {  // (the plane at the batch's pitch; the restore's counters are in its table)
+                b.mask.bits = bufs.take(roi_batch_mask_plane_bytes(n));
+                b.mask.d_blob = bufs.take(b.mask.blob_bytes());
+                b.mask.work = bufs.take(b.mask.work_bytes());
+                if (!b.mask.bits || !b.mask.d_blob || !b.mask.work) return fail_at("field", f, WR_ERR_HIP);
             }
         }
         if (nall) {
@@ -5310,12 +5289,9 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
             if (int rc = seg_upload_lists(c, b.s, b.used, data_encs[f], b.blob, b.work, b.d_bricks, b.ids, b.bricks, &local.h2d_ms, &bytes_up)) return fail_at("field", f, rc);
             for (int l = 0; l < b.used; l++) segments += b.ids[l].size();
         }
-        if (b.masked) {
-            SegStream one;  // the mask's plane as a stream of one WRS1 plane (MaskRegion::upload)
-            one.nlay = 1; one.off[1] = b.mplane_len(); one.seg[0] = b.mseg; one.nseg[0] = b.mnseg;
-            uint8_t *blob_of[1] = {b.md_blob}, *work_of[1] = {b.mwork};
-            if (int rc = seg_upload_lists(c, one, 1, b.mplane(), blob_of, work_of, nullptr, &b.mids, std::vector<uint32_t>(), &local.h2d_ms, &mask_bytes_up)) return fail_at("field", f, rc);
-            mask_segments += b.mids.size();
+        if (b.has_mask()) {
+            if (int rc = b.mask.upload(c, &local.h2d_ms, &mask_bytes_up)) return fail_at("field", f, rc);
+            mask_segments += b.mask.ids.size();
         }
     }
     g_stat[WR_STAT_ROI_BYTES_UP] += bytes_up;
@@ -5344,10 +5320,10 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
                 job.bad = d_bad + at;  // (the batch counts in one array, read back once)
                 jobs.add(job, wrk::seg_decode_list_ids(b.work[l], b.s.nseg[l]), b.ids[l].size(), b.s.strands);
             }
-            if (b.masked) {
-                wrk::SegJob job = seg_job(wrk::plane_ref(b.mbits), b.md_blob, b.mplane_len(), b.mwork, b.msym, b.mseg, b.mnseg, 0);
-                job.bad = d_bad + (b.mjob = at++);
-                jobs.add(job, wrk::seg_decode_list_ids(b.mwork, b.mnseg), b.mids.size(), 0);
+            if (b.has_mask()) {
+                wrk::SegJob job = b.mask.seg_job();
+                job.bad = d_bad + at++;
+                jobs.add(job, b.mask.seg_list());
             }
         }
         launch_note(c, "seg_decode_lists_batch", 0, d_once, n, bufs.pinned, wrk::plane_ref(d_once));
@@ -5366,8 +5342,8 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
             for (int l = 0; l < bf[f].used; l++)
                 if (const unsigned int k = bad[(size_t)bf[f].job0 + l])
                     return fail(WR_ERR_STREAM, "field " + std::to_string(f) + ": plane " + std::to_string(l) + ": " + bad_segments_text(k));
-            if (bf[f].masked)
-                if (const unsigned int k = bad[(size_t)bf[f].mjob]) return fail(WR_ERR_STREAM, "field " + std::to_string(f) + ": mask blob: " + bad_segments_text(k));
+            if (bf[f].has_mask())
+                if (const unsigned int k = bad[(size_t)bf[f].job0 + bf[f].used]) return fail(WR_ERR_STREAM, "field " + std::to_string(f) + ": mask blob: " + bad_segments_text(k));
         }
         fold_coder_seconds(bufs, 1, &local);
         // ---- every field in turn: its bricks back to their places, then its regions through the window stage
@@ -5388,8 +5364,8 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
             std::vector<const uint8_t*> planes_of((size_t)nfields, nullptr);
             for (int f = 0; f < nfields; f++) {
                 const RoiBatchField& b = bf[f];
-                if (!b.masked) continue;
-                planes_of[f] = b.mbits;
+                if (!b.has_mask()) continue;
+                planes_of[f] = b.mask.bits;
                 if (!b.s.constant) continue;
                 if (f32) wrk::fill_f32(reinterpret_cast<float*>(d_out) + (size_t)f * T, T, (float)infos[f].midval, c->stream);
                 else wrk::fill(reinterpret_cast<double*>(d_out) + (size_t)f * T, T, infos[f].midval, c->stream);
@@ -5408,7 +5384,7 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
                 HIPCHK(hipMemcpyAsync(counts.data(), wrk::mask_boxes_counters(d_restore, (size_t)nroi, (size_t)nfields), nmask * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
                 HIPCHK(hipStreamSynchronize(c->stream));
                 size_t m = 0;
-                for (int f = 0; f < nfields; f++) if (bf[f].masked) restored[f] = counts[m++];
+                for (int f = 0; f < nfields; f++) if (bf[f].has_mask()) restored[f] = counts[m++];
             }
         }
         rc = kernel_stage_end(c, rc);
@@ -5417,12 +5393,12 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
     // constant fields: midval in every region (device callers here, host callers behind the one copy down); those that have
     // a mask were made in the kernel stage
     for (int f = 0; f < nfields; f++)
-        if (bf[f].s.constant && fld.dev && !bf[f].masked)
+        if (bf[f].s.constant && fld.dev && !bf[f].has_mask())
             if (int rc2 = fill_constant(c, FieldRef{fld.dev + (size_t)f * T}, T, infos[f].midval)) return rc2;
     if (nall)  // (an all-constant call has nothing to bring down)
         if (int rc2 = finish_call(c, fld, d_host_out, d_host_out, (size_t)nfields * T, false, t0, t_coded, t_phase, &local, nullptr)) return rc2;
     for (int f = 0; f < nfields; f++) {
-        if (!bf[f].s.constant || fld.dev || bf[f].masked) continue;
+        if (!bf[f].s.constant || fld.dev || bf[f].has_mask()) continue;
         FieldRef part;
         if (f32) part.host_f32 = fld.host_f32 + (size_t)f * T;
         else part.host = fld.host + (size_t)f * T;
@@ -5433,8 +5409,8 @@ int decode_seg_roi_batch_impl(wr_ctx* c, FieldRef fld, int nfields, int nx, int 
         for (int f = 0; f < nfields; f++) {
             wr_mask_result& r = mb->res[f];
             memset(&r, 0, sizeof r);
-            if (!bf[f].masked) continue;
-            r.undefined = restored[f]; r.pad = bf[f].mpad; r.mask_len = bf[f].mlen; r.fill_ms = fill_ms;
+            if (!bf[f].has_mask()) continue;
+            r.undefined = restored[f]; r.pad = bf[f].mask.info.pad; r.mask_len = bf[f].mask.len; r.fill_ms = fill_ms;
         }
     }
     local.total = now() - t0;
@@ -5462,8 +5438,8 @@ int dev_mask_restore_boxes(wr_ctx* c, T* d_out, int nfields, int nx, int ny, int
     std::vector<size_t> offs((size_t)(nroi > 0 ? nroi : 0) + 1);
     const size_t T_elems = wr_roi_multi_elems(nx, ny, nz, level, rois, nroi, offs.data());
     if (!T_elems) return WR_ERR_ARG;  // (the message is wr_roi_multi_elems')
-    std::vector<wrmask::Region> gs((size_t)nroi);
-    for (int i = 0; i < nroi; i++) gs[i] = wrmask::Region{nx, ny, nz, level, rois[i].x0, rois[i].y0, rois[i].z0, rois[i].x1, rois[i].y1, rois[i].z1};
+    std::vector<wrmask::Region> gs;
+    for (int i = 0; i < nroi; i++) gs.push_back(mask_region(nx, ny, nz, level, &rois[i]));
     size_t nmask = 0;
     for (int f = 0; f < nfields; f++) nmask += d_bits[f] != nullptr;
     if (undefined) for (int f = 0; f < nfields; f++) undefined[f] = 0;

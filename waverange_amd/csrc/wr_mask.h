@@ -100,27 +100,33 @@ inline size_t roi_segments(const Region& g, uint32_t seg, uint32_t* ids, size_t 
     return count;
 }
 
-// The blobs of a batch of masked records, validated in field order as the single masked call validates its one: the header
-// (check_header), then the whole segment index of the WRS1 plane behind it (wrseg::check_index; the plane's seg is read from
-// its own header).  blobs[f] == nullptr: field f has no blob and is passed over.  Returns nfields if every blob passes and
-// info[f] is then filled for every field that has one; otherwise the first field whose blob fails, *why saying what ("mask
-// blob: ..."), and nothing behind that field has been looked at.
+// What the header and the index of a blob say: the one validation of a mask blob, for a field of n samples.  The header
+// (check_header), then the whole segment index of the WRS1 plane behind it (wrseg::check_index; the plane's seg is read from its
+// own header).  false: refused, *why saying what ("mask blob: ...").
 struct BlobInfo {
     unsigned long long undefined = 0;
     double pad = 0;
     uint32_t seg = 0, nseg = 0;
 };
+inline bool check_blob(const unsigned char* blob, size_t len, size_t n, BlobInfo* info, std::string* why)
+{
+    if (const char* w = check_header(blob, len, n, &info->undefined, &info->pad)) { *why = w; return false; }
+    const size_t rest = len - kHeaderBytes;
+    if (const char* w = wrseg::check_index(blob + kHeaderBytes, rest, rest, mask_bytes(n), &info->seg, &info->nseg)) {
+        *why = std::string("mask blob: ") + w;
+        return false;
+    }
+    return true;
+}
+
+// The blobs of a batch of masked records, validated in field order as the single masked call validates its one (check_blob).
+// blobs[f] == nullptr: field f has no blob and is passed over.  Returns nfields if every blob passes and info[f] is then filled
+// for every field that has one; otherwise the first field whose blob fails, *why saying what, and nothing behind that field has
+// been looked at.
 inline int check_blobs(const unsigned char* const* blobs, const size_t* lens, int nfields, size_t n, BlobInfo* info, std::string* why)
 {
-    for (int f = 0; f < nfields; f++) {
-        if (!blobs[f]) continue;
-        if (const char* w = check_header(blobs[f], lens[f], n, &info[f].undefined, &info[f].pad)) { *why = w; return f; }
-        const size_t rest = lens[f] - kHeaderBytes;
-        if (const char* w = wrseg::check_index(blobs[f] + kHeaderBytes, rest, rest, mask_bytes(n), &info[f].seg, &info[f].nseg)) {
-            *why = std::string("mask blob: ") + w;
-            return f;
-        }
-    }
+    for (int f = 0; f < nfields; f++)
+        if (blobs[f] && !check_blob(blobs[f], lens[f], n, &info[f], why)) return f;
     return nfields;
 }
 

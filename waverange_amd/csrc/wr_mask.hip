@@ -200,6 +200,31 @@ __device__ inline unsigned long long mask_word_at(const uint8_t* __restrict__ bi
     return m;
 }
 
+// One turn of a box restore, written once for k_mask_restore_box and k_mask_restore_boxes: the 64 consecutive x from xs of row
+// (y, z) of a region at (x0, y0, z0) with the extents (cx, cy, .), in the level-r box of a field of nx * ny * . samples.  o: the
+// region's elements; `v` goes where a bit is set, and the set bits among the turn's are added to pop.  Everything but `lane` is
+// the same in every lane of the wave.
+template <typename T>
+__device__ __forceinline__ void mask_box_turn(T* o, const uint8_t* bits, unsigned long long nx, unsigned long long ny, uint32_t r,
+                                              uint32_t x0, uint32_t y0, uint32_t z0, uint32_t cx, uint32_t cy, uint32_t xs, uint32_t y, uint32_t z, uint32_t lane, T v,
+                                              unsigned long long& pop)
+{
+    const uint32_t left = cx - xs, cnt = left < 64 ? left : 64;
+    const unsigned long long valid = cnt == 64 ? ~0ull : (1ull << cnt) - 1;
+    const size_t row = (size_t)nx * (((size_t)(y0 + y) << r) + (size_t)ny * ((size_t)(z0 + z) << r));
+    unsigned long long m;
+    if (r == 0) {
+        m = mask_word_at(bits, row + x0 + xs, cnt) & valid;
+    } else {
+        const size_t J = row + ((size_t)(x0 + xs + lane) << r);
+        m = __ballot(lane < cnt && ((bits[J >> 3] >> (J & 7)) & 1));
+    }
+    if (m) {  // (the whole wave: m is the same in every lane)
+        pop += (unsigned long long)__popcll(m);
+        if ((m >> lane) & 1) o[((size_t)z * cy + y) * cx + xs + lane] = v;
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(WR_MASK_THREADS) void k_mask_restore_box(T* __restrict__ out, MaskBox g, const uint8_t* __restrict__ bits, T v,
                                                                         unsigned long long* __restrict__ counters)
@@ -213,20 +238,7 @@ __global__ __launch_bounds__(WR_MASK_THREADS) void k_mask_restore_box(T* __restr
     uint32_t turn = wave % tpr, y = (wave / tpr) % g.cy, z = (wave / tpr) / g.cy;
     unsigned long long pop = 0;  // (of the wave: every lane holds the same value)
     while (z < g.cz) {
-        const uint32_t xs = turn << 6, left = g.cx - xs, cnt = left < 64 ? left : 64;
-        const unsigned long long valid = cnt == 64 ? ~0ull : (1ull << cnt) - 1;
-        const size_t row = (size_t)g.nx * (((size_t)(g.y0 + y) << g.r) + (size_t)g.ny * ((size_t)(g.z0 + z) << g.r));
-        unsigned long long m;
-        if (g.r == 0) {
-            m = mask_word_at(bits, row + g.x0 + xs, cnt) & valid;
-        } else {
-            const size_t J = row + ((size_t)(g.x0 + xs + lane) << g.r);
-            m = __ballot(lane < cnt && ((bits[J >> 3] >> (J & 7)) & 1));
-        }
-        if (m) {  // (the whole wave: m is the same in every lane)
-            pop += (unsigned long long)__popcll(m);
-            if ((m >> lane) & 1) out[((size_t)z * g.cy + y) * g.cx + xs + lane] = v;
-        }
+        mask_box_turn(out, bits, g.nx, g.ny, g.r, g.x0, g.y0, g.z0, g.cx, g.cy, turn << 6, y, z, lane, v, pop);
         turn += dt;
         const uint32_t carry = turn >= tpr;
         if (carry) turn -= tpr;
@@ -325,20 +337,7 @@ __global__ __launch_bounds__(WR_MASK_THREADS) void k_mask_restore_boxes(T* __res
         uint32_t turn = 0, rowi = q;
         if (b.tpr != 1) { rowi = q / b.tpr; turn = q - rowi * b.tpr; }
         const uint32_t z = rowi / b.cy, y = rowi - z * b.cy;
-        const uint32_t xs = turn << 6, left = b.cx - xs, cnt = left < 64 ? left : 64;
-        const unsigned long long valid = cnt == 64 ? ~0ull : (1ull << cnt) - 1;
-        const size_t row = (size_t)g.nx * (((size_t)(b.y0 + y) << g.r) + (size_t)g.ny * ((size_t)(b.z0 + z) << g.r));
-        unsigned long long w;
-        if (g.r == 0) {
-            w = mask_word_at(bits, row + b.x0 + xs, cnt) & valid;
-        } else {
-            const size_t J = row + ((size_t)(b.x0 + xs + lane) << g.r);
-            w = __ballot(lane < cnt && ((bits[J >> 3] >> (J & 7)) & 1));
-        }
-        if (w) {  // (the whole wave: w is the same in every lane)
-            pop += (unsigned long long)__popcll(w);
-            if ((w >> lane) & 1) o[((size_t)z * b.cy + y) * b.cx + xs + lane] = v;
-        }
+        mask_box_turn(o, bits, g.nx, g.ny, g.r, b.x0, b.y0, b.z0, b.cx, b.cy, turn << 6, y, z, lane, v, pop);
         u += du;
         const uint32_t carry = u >= g.tpf;
         if (carry) u -= g.tpf;
