@@ -1137,6 +1137,82 @@ int wr_decode_device_seg_batch_mixed(wr_ctx *ctx, int nfields, double *const *d_
                                      const wr_enc_info *infos, const unsigned char *const *data_encs,
                                      const size_t *data_lens, wr_timings *tm);
 
+/* ---- Masked batch encode and decode: N masked fields per call, their N masks in one coder launch.  No new format.
+ * A loop of wr_encode_*_seg_masked pays, per field, a coder launch per plane and one more for the mask, each as long as one
+ * segment's chain; here the planes go as in the batch calls above and all masks as one launch more.
+ * Encode.  wr_encode_*_seg_batch_masked take the arguments of wr_encode_*_seg_batch_strands, `below` (one threshold per call;
+ *   a NaN is WR_ERR_ARG) behind `strands`, and results[0, nfields) (may be NULL) at the end.  The format is chosen as the single
+ *   masked call chooses it and nothing is defaulted but seg: brick == 0 && strands == 0: WRS1; brick != 0: WRS2; strands != 0:
+ *   WRS3.  For every field f, infos[f], every byte of data_encs[f] -- the field part, then the WRM1 blob at infos[f].ntot_enc --
+ *   and results[f].undefined, .pad, .mask_len are exactly what wr_encode_*_seg_masked returns for that field alone with the
+ *   same seg, brick, strands and below, whatever the other fields are and whatever their order.  A field without an undefined
+ *   sample gives the plain batch record (mask_len == 0); a padded field that is constant gives the trivial record with the
+ *   blob at data_enc.  Device fields are split by one launch and filled by one launch before the first transform (the fields
+ *   are consumed); a host field is split and filled in the slot as it passes through.  Before a field's transform is queued:
+ *   no defined sample is WR_ERR_ARG "field f: no defined sample: ...", a mean that is not finite WR_ERR_ARG likewise.  The masks
+ *   of all fields that have an undefined sample are coded by ONE launch of the batched WRS1 coder, ceil(n / 8) symbols each at
+ *   the call's seg, on a stream of their own under the fields' plane launches: WR_STAT_BATCH_CODER_LAUNCHES grows by the plane
+ *   launches plus 1 (plus 0 when no field has an undefined sample).  caps[f] must hold the field part plus the blob's exact
+ *   length: WR_ERR_OVERFLOW naming the field otherwise, before data_encs[f] is written (earlier fields are complete).
+ *   results[f].mask_coder_ms is the one mask launch's time in every masked field; split_ms and fill_ms are the field's own for
+ *   host fields and the batched launches' for device fields.
+ * Decode.  wr_decode_*_seg_batch_masked take the arguments of wr_decode_*_seg_batch_mixed (data_lens is required), `fill` and
+ *   results[0, nfields) (may be NULL).  data_lens[f] is the field part plus the blob; data_lens[f] == infos[f].ntot_enc, or 0, is
+ *   an unmasked record.  WRS1, WRS2 and WRS3 field parts, masked, unmasked and constant records (a constant with or without a
+ *   blob) may share a call; every reconstruction is bit for bit wr_decode_*_seg_masked's for that record alone, a NaN `fill`
+ *   included.  Every blob is validated on the host before anything is copied or launched; each mask is one more WRS1 job of
+ *   the call's plain launch, so the call still makes at most two coder launches; one launch behind the coder stage counts every
+ *   mask.  WR_ERR_STREAM naming "field f: ", before any dequantizer runs and before any caller's field is written: a malformed
+ *   blob, a segment that does not decode, a set bit at or beyond n, a population count other than the header's.  results[f]:
+ *   undefined, pad and mask_len as the single call gives them, mask_coder_ms the call's coder launches; the fills are not timed.
+ * Stage level (device pointers of any alignment, n >= 1, 1..WR_SEG_BATCH_MAX fields or masks).  Field f's results are those of
+ *   wr_dev_mask_split / wr_dev_mask_fill for that field alone, bit for bit (pad is a NaN for a field with no defined sample; the
+ *   call still succeeds); a NULL d_flds[f] of a fill is skipped.  wr_dev_mask_check_batch reads no field: undefined[m] = the set
+ *   bits of mask m's ceil(n / 8) bytes, beyond[m] = 1 if one lies at or beyond n.  WR_ERR_ARG: null arrays or entries, n == 0,
+ *   a count out of range, a NaN `below`.
+ * Device memory: wr_seg_batch_device_bytes_masked is wr_seg_batch_device_bytes_strands (an encode with strands == 0:
+ *   wr_seg_batch_device_bytes, the WRS1 / WRS2 planes that call makes) plus
+ *   per masked field     the bit plane; the blob, at its bound (encode) or at wr_mask_bound with the decoder's work buffer (decode)
+ *   once, encode         the mask launch's staging, and the split partials of nfields fields
+ *   once, decode         the masks' share of the job tables and failure counts, and the check's counters
+ *   An encode cannot know nmasked in advance and holds a bit plane for every field: callers pass nfields.  0 for a refused
+ *   argument (those of the base, nmasked outside 0..nfields); it never decreases when nfields, nmasked, n or nlay grows (seg,
+ *   brick, strands and decode choose a layout; they are no measure of the work). */
+size_t wr_seg_batch_device_bytes_masked(int nfields, int nmasked, size_t n, int nlay, unsigned seg, unsigned brick,
+                                        unsigned strands, int decode);
+int wr_dev_mask_split_batch(wr_ctx *ctx, int nfields, const double *const *d_flds, size_t n, double below,
+                            unsigned char *const *d_bits, unsigned long long *undefined, double *pad);
+int wr_dev_mask_split_batch_f32(wr_ctx *ctx, int nfields, const float *const *d_flds, size_t n, double below,
+                                unsigned char *const *d_bits, unsigned long long *undefined, double *pad);
+int wr_dev_mask_fill_batch(wr_ctx *ctx, int nfields, double *const *d_flds, size_t n, const unsigned char *const *d_bits,
+                           const double *values);
+int wr_dev_mask_fill_batch_f32(wr_ctx *ctx, int nfields, float *const *d_flds, size_t n,
+                               const unsigned char *const *d_bits, const double *values);
+int wr_dev_mask_check_batch(wr_ctx *ctx, int nmasks, const unsigned char *const *d_bits, size_t n,
+                            unsigned long long *undefined, unsigned char *beyond);
+int wr_encode_host_seg_batch_masked(wr_ctx *ctx, int nfields, const double *const *h_flds, int nx, int ny, int nz, int wtflag,
+                                    int mx, int my, int mz, const double *const *cutoffvecs, unsigned seg, unsigned brick,
+                                    unsigned strands, double below, wr_enc_info *infos, unsigned char *const *data_encs,
+                                    const size_t *caps, wr_timings *tm, wr_mask_result *results);
+int wr_encode_host_seg_batch_masked_f32(wr_ctx *ctx, int nfields, const float *const *h_flds, int nx, int ny, int nz,
+                                        int wtflag, int mx, int my, int mz, const double *const *cutoffvecs, unsigned seg,
+                                        unsigned brick, unsigned strands, double below, wr_enc_info *infos,
+                                        unsigned char *const *data_encs, const size_t *caps, wr_timings *tm,
+                                        wr_mask_result *results);
+int wr_encode_device_seg_batch_masked(wr_ctx *ctx, int nfields, double *const *d_flds, int nx, int ny, int nz, int wtflag,
+                                      int mx, int my, int mz, const double *const *cutoffvecs, unsigned seg, unsigned brick,
+                                      unsigned strands, double below, wr_enc_info *infos, unsigned char *const *data_encs,
+                                      const size_t *caps, wr_timings *tm, wr_mask_result *results);
+int wr_decode_host_seg_batch_masked(wr_ctx *ctx, int nfields, double *const *h_flds, int nx, int ny, int nz,
+                                    const wr_enc_info *infos, const unsigned char *const *data_encs, const size_t *data_lens,
+                                    double fill, wr_timings *tm, wr_mask_result *results);
+int wr_decode_host_seg_batch_masked_f32(wr_ctx *ctx, int nfields, float *const *h_flds, int nx, int ny, int nz,
+                                        const wr_enc_info *infos, const unsigned char *const *data_encs,
+                                        const size_t *data_lens, double fill, wr_timings *tm, wr_mask_result *results);
+int wr_decode_device_seg_batch_masked(wr_ctx *ctx, int nfields, double *const *d_flds, int nx, int ny, int nz,
+                                      const wr_enc_info *infos, const unsigned char *const *data_encs, const size_t *data_lens,
+                                      double fill, wr_timings *tm, wr_mask_result *results);
+
 /* ---- Region decode, many regions per call: Q regions of one stream, and all used planes in ONE coder launch.  No new format.
  * A single-region call launches the coder once per used plane, back to back, and each launch lasts one segment's chain however
  * few lanes it has; Q probes of one snapshot pay that Q times.  Here the segments that any of the regions needs -- per plane the

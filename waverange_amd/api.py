@@ -351,6 +351,21 @@ def lib():
     L.wr_decode_host_seg_batch_mixed.argtypes = L.wr_decode_host_seg_batch.argtypes
     L.wr_decode_host_seg_batch_mixed_f32.argtypes = L.wr_decode_host_seg_batch.argtypes
     L.wr_decode_device_seg_batch_mixed.argtypes = L.wr_decode_host_seg_batch.argtypes
+    a = L.wr_encode_host_seg_batch_strands.argtypes
+    L.wr_encode_host_seg_batch_masked.argtypes = a[:14] + [C.c_double] + a[14:] + [_vp]
+    L.wr_encode_host_seg_batch_masked_f32.argtypes = L.wr_encode_host_seg_batch_masked.argtypes
+    L.wr_encode_device_seg_batch_masked.argtypes = L.wr_encode_host_seg_batch_masked.argtypes
+    a = L.wr_decode_host_seg_batch.argtypes
+    L.wr_decode_host_seg_batch_masked.argtypes = a[:9] + [C.c_double] + a[9:] + [_vp]
+    L.wr_decode_host_seg_batch_masked_f32.argtypes = L.wr_decode_host_seg_batch_masked.argtypes
+    L.wr_decode_device_seg_batch_masked.argtypes = L.wr_decode_host_seg_batch_masked.argtypes
+    L.wr_seg_batch_device_bytes_masked.restype = C.c_size_t
+    L.wr_seg_batch_device_bytes_masked.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_int]
+    L.wr_dev_mask_split_batch.argtypes = [_vp, C.c_int, _vp, C.c_size_t, C.c_double, _vp, _vp, _vp]
+    L.wr_dev_mask_split_batch_f32.argtypes = L.wr_dev_mask_split_batch.argtypes
+    L.wr_dev_mask_fill_batch.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, _vp]
+    L.wr_dev_mask_fill_batch_f32.argtypes = L.wr_dev_mask_fill_batch.argtypes
+    L.wr_dev_mask_check_batch.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, _vp]
     L.wr_seg_bound_blocked.restype = C.c_size_t
     L.wr_seg_bound_blocked.argtypes = [C.c_size_t, C.c_uint]
     L.wr_seg_lowres_segments_blocked.restype = C.c_size_t
@@ -822,6 +837,13 @@ def seg_batch_device_bytes_strands(nfields, n, nlay, seg=0, brick=0, strands=0, 
     """seg_batch_device_bytes for the WRS3 batch calls (wr_seg_batch_device_bytes_strands; strands = 0: STRANDS_DEFAULT;
     decode: the mixed decode of such fields); 0 for a refused argument."""
     return int(lib().wr_seg_batch_device_bytes_strands(nfields, n, nlay, seg, brick, strands, 1 if decode else 0))
+
+
+def seg_batch_device_bytes_masked(nfields, nmasked, n, nlay, seg=0, brick=0, strands=0, decode=False):
+    """Device bytes of the masked batch calls: seg_batch_device_bytes_strands (an encode with strands = 0:
+    seg_batch_device_bytes) plus, per masked field, the bit plane and the blob, and once the masks' launch
+    (wr_seg_batch_device_bytes_masked); an encode passes nmasked = nfields; 0 for a refused argument."""
+    return int(lib().wr_seg_batch_device_bytes_masked(nfields, nmasked, n, nlay, seg, brick, strands, 1 if decode else 0))
 
 
 def seg_batch_strand_lane(first, strands, g):
@@ -2443,6 +2465,125 @@ class Context:
     def decode_seg_batch_mixed(self, bufs, shape, encs):
         assert len(bufs) == len(encs)
         return self._decode_seg_batch(lib().wr_decode_device_seg_batch_mixed, [b.ptr for b in bufs], shape, encs)
+
+    # ---- masked batch encode and decode: N masked fields per call, their masks in one coder launch
+    def _encode_seg_batch_masked(self, fn, ptrs, shape, tolrels, below, wtflag, seg, brick, strands, cutoffs, m, caps, outs):
+        nz, ny, nx = shape
+        nf = len(ptrs)
+        if cutoffs is None:
+            tol = [tolrels] * nf if np.isscalar(tolrels) else list(tolrels)
+            cutoffs = [[t] for t in tol]
+        cuts = [np.ascontiguousarray(cv, dtype=np.float64) for cv in cutoffs]
+        cap = self._seg_cap(shape, seg, brick if brick else None, strands if strands else None) + mask_bound(nx * ny * nz, seg) if nf else 0
+        datas = list(outs) if outs is not None else [np.empty(cap if caps is None else caps[i], dtype=np.uint8) for i in range(nf)]
+        infos, tm = (EncInfo * max(nf, 1))(), Timings()
+        res = (MaskResult * max(nf, 1))()
+        fp = (C.c_void_p * max(nf, 1))(*ptrs)
+        cp = (C.c_void_p * max(nf, 1))(*[cv.ctypes.data for cv in cuts])
+        dp = (C.c_void_p * max(nf, 1))(*[d.ctypes.data for d in datas])
+        sz = (C.c_size_t * max(nf, 1))(*[d.size for d in datas])
+        _check(fn(self.h, nf, fp, nx, ny, nz, wtflag, m[0], m[1], m[2], cp, seg, brick, strands, float(below), infos, dp, sz, C.byref(tm), res))
+        encs = []
+        for i in range(nf):
+            d = infos[i].as_dict()
+            d["data"] = datas[i][:infos[i].ntot_enc + res[i].mask_len]
+            d["mask"] = res[i].as_dict()
+            encs.append(d)
+        return encs, tm.as_dict()
+
+    def encode_host_seg_batch_masked(self, fields, tolrels, below=-np.inf, wtflag=1, seg=0, brick=0, strands=0, cutoffs=None, m=(1, 1, 1), caps=None, outs=None):
+        """encode_host_seg_masked for a list of same-shaped float64 fields: plane l of all of them in one coder launch and all
+        their masks in one launch more (wr_encode_host_seg_batch_masked).  brick = 0, strands = 0: WRS1; brick > 0: WRS2;
+        strands > 0: WRS3.  Returns ([record per field], timings): every record is encode_host_seg_masked's for that field."""
+        assert all(f.dtype == np.float64 and f.flags["C_CONTIGUOUS"] and f.shape == fields[0].shape for f in fields)
+        shape = fields[0].shape if len(fields) else (1, 1, 1)
+        return self._encode_seg_batch_masked(lib().wr_encode_host_seg_batch_masked, [f.ctypes.data for f in fields], shape, tolrels, below, wtflag, seg, brick,
+                                             strands, cutoffs, m, caps, outs)
+
+    def encode_host_seg_batch_masked_f32(self, fields, tolrels, below=-np.inf, wtflag=1, seg=0, brick=0, strands=0, cutoffs=None, m=(1, 1, 1), caps=None, outs=None):
+        if not all(isinstance(f, np.ndarray) and f.dtype == np.float32 and f.flags["C_CONTIGUOUS"] and f.shape == fields[0].shape for f in fields):
+            raise TypeError("encode_host_seg_batch_masked_f32: C-contiguous float32 arrays of one shape are required")
+        shape = fields[0].shape if len(fields) else (1, 1, 1)
+        return self._encode_seg_batch_masked(lib().wr_encode_host_seg_batch_masked_f32, [f.ctypes.data for f in fields], shape, tolrels, below, wtflag, seg, brick,
+                                             strands, cutoffs, m, caps, outs)
+
+    def encode_seg_batch_masked(self, bufs, shape, tolrels, below=-np.inf, wtflag=1, seg=0, brick=0, strands=0, cutoffs=None, m=(1, 1, 1), caps=None, outs=None):
+        """encode_host_seg_batch_masked with the fields resident on the device (the buffers are consumed): one launch splits
+        all of them and one fills them."""
+        return self._encode_seg_batch_masked(lib().wr_encode_device_seg_batch_masked, [b.ptr for b in bufs], shape, tolrels, below, wtflag, seg, brick, strands,
+                                             cutoffs, m, caps, outs)
+
+    def _decode_seg_batch_masked(self, fn, ptrs, shape, encs, fill):
+        nz, ny, nx = shape
+        nf = len(ptrs)
+        infos, tm = (EncInfo * max(nf, 1))(), Timings()
+        res = (MaskResult * max(nf, 1))()
+        datas = [np.ascontiguousarray(e["data"], dtype=np.uint8) for e in encs]
+        keep = [d if d.size else np.zeros(1, dtype=np.uint8) for d in datas]
+        for i, enc in enumerate(encs):
+            infos[i] = EncInfo.from_dict(enc)
+        fp = (C.c_void_p * max(nf, 1))(*ptrs)
+        dp = (C.c_void_p * max(nf, 1))(*[d.ctypes.data for d in keep])
+        sz = (C.c_size_t * max(nf, 1))(*[d.size for d in datas])
+        _check(fn(self.h, nf, fp, nx, ny, nz, infos, dp, sz, float(fill), C.byref(tm), res))
+        return [res[i].as_dict() for i in range(nf)], tm.as_dict()
+
+    def decode_host_seg_batch_masked(self, outs, encs, fill=np.nan):
+        """decode_host_seg_masked for a list of records -- WRS1, WRS2 and WRS3, masked, unmasked and constant mixed freely --
+        into the same-shaped float64 arrays `outs`: the masks ride in the call's plain coder launch
+        (wr_decode_host_seg_batch_masked).  Returns ([mask per field], timings)."""
+        assert len(outs) == len(encs) and all(o.dtype == np.float64 and o.flags["C_CONTIGUOUS"] and o.shape == outs[0].shape for o in outs)
+        shape = outs[0].shape if len(outs) else (1, 1, 1)
+        return self._decode_seg_batch_masked(lib().wr_decode_host_seg_batch_masked, [o.ctypes.data for o in outs], shape, encs, fill)
+
+    def decode_host_seg_batch_masked_f32(self, outs, encs, fill=np.nan):
+        if not (len(outs) == len(encs) and all(isinstance(o, np.ndarray) and o.dtype == np.float32 and o.flags["C_CONTIGUOUS"] and o.shape == outs[0].shape for o in outs)):
+            raise TypeError("decode_host_seg_batch_masked_f32: C-contiguous float32 arrays of one shape are required")
+        shape = outs[0].shape if len(outs) else (1, 1, 1)
+        return self._decode_seg_batch_masked(lib().wr_decode_host_seg_batch_masked_f32, [o.ctypes.data for o in outs], shape, encs, fill)
+
+    def decode_seg_batch_masked(self, bufs, shape, encs, fill=np.nan):
+        """decode_host_seg_batch_masked into fields resident on the device."""
+        assert len(bufs) == len(encs)
+        return self._decode_seg_batch_masked(lib().wr_decode_device_seg_batch_masked, [b.ptr for b in bufs], shape, encs, fill)
+
+    def mask_split_batch(self, flds, n, bits, below=-np.inf, dtype=np.float64, offsets=None, bits_offsets=None):
+        """Stage level: mask_split of every device buffer of `flds` (n samples from ELEMENT offsets[f]) into the device buffer
+        bits[f] (from byte bits_offsets[f]) in one launch: [(undefined, pad) per field], each bit for bit mask_split's
+        (wr_dev_mask_split_batch, _f32)."""
+        dt = self._mask_dtype("mask_split_batch", dtype)
+        fn = lib().wr_dev_mask_split_batch if dt == np.float64 else lib().wr_dev_mask_split_batch_f32
+        nf = len(flds)
+        off = offsets if offsets is not None else [0] * nf
+        boff = bits_offsets if bits_offsets is not None else [0] * nf
+        fp = (C.c_void_p * max(nf, 1))(*[f.ptr + o * dt.itemsize for f, o in zip(flds, off)])
+        bp = (C.c_void_p * max(nf, 1))(*[b.ptr + o for b, o in zip(bits, boff)])
+        undefined, pad = (C.c_ulonglong * max(nf, 1))(), (C.c_double * max(nf, 1))()
+        _check(fn(self.h, nf, fp, int(n), float(below), bp, undefined, pad))
+        return [(int(undefined[f]), pad[f]) for f in range(nf)]
+
+    def mask_fill_batch(self, flds, n, bits, values, dtype=np.float64, offsets=None, bits_offsets=None):
+        """Stage level: mask_fill of every field with its own value in one launch; a None field is skipped
+        (wr_dev_mask_fill_batch, _f32)."""
+        dt = self._mask_dtype("mask_fill_batch", dtype)
+        fn = lib().wr_dev_mask_fill_batch if dt == np.float64 else lib().wr_dev_mask_fill_batch_f32
+        nf = len(flds)
+        off = offsets if offsets is not None else [0] * nf
+        boff = bits_offsets if bits_offsets is not None else [0] * nf
+        fp = (C.c_void_p * max(nf, 1))(*[None if f is None else f.ptr + o * dt.itemsize for f, o in zip(flds, off)])
+        bp = (C.c_void_p * max(nf, 1))(*[None if b is None else b.ptr + o for b, o in zip(bits, boff)])
+        vals = (C.c_double * max(nf, 1))(*[float(v) for v in values])
+        _check(fn(self.h, nf, fp, int(n), bp, vals))
+
+    def mask_check_batch(self, bits, n, bits_offsets=None):
+        """Stage level: per mask plane of n bits (count of its set bits, whether one lies at or beyond n), one launch, no field
+        read (wr_dev_mask_check_batch)."""
+        nm = len(bits)
+        boff = bits_offsets if bits_offsets is not None else [0] * nm
+        bp = (C.c_void_p * max(nm, 1))(*[b.ptr + o for b, o in zip(bits, boff)])
+        undefined, beyond = (C.c_ulonglong * max(nm, 1))(), (C.c_ubyte * max(nm, 1))()
+        _check(lib().wr_dev_mask_check_batch(self.h, nm, bp, int(n), undefined, beyond))
+        return [(int(undefined[k]), bool(beyond[k])) for k in range(nm)]
 
     def seg_encode_planes_batch_strands(self, planes, seg=0, strands=0):
         """Stage level: planes of one size through ONE batched strand-coder launch sequence; returns the WRS3 blob (natural

@@ -21,6 +21,11 @@
 // over the defined points stays within E (--rmse), both in the field's units, or whose PSNR over the range of the defined
 // points reaches DB (--psnr).  TOLERANCE is then the finest tolerance allowed; the tool prints the one chosen and the error
 // reached.  The three exclude one another.  The container is the same: wrdec_mssg needs nothing.
+//
+// --batch=N (with --mask=bits, without a target: the searches are not batched): up to N consecutive TYPE 0 time records are read
+// and coded by ONE call of wr_encode_host_seg_batch_masked -- a coder launch per plane index for all of them and one for all
+// their masks; a group is cut further so that wr_seg_batch_device_bytes_masked fits into 3/4 of the device's free memory.  The
+// records are written in order: both output files are byte for byte those of a run without the option.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -191,7 +196,30 @@ struct MaskBits {
     unsigned seg = 0, brick = 0, strands = 0;
     int norm = 0;  // --maxerr: WR_NORM_MAX, --rmse: WR_NORM_RMS, --psnr: WR_NORM_PSNR; 0: the tolerance is TOLERANCE
     double target = 0;
+    int batch = 1;  // --batch=N: time records per call
 };
+
+// a masked field's records: "mask" with the blob behind the field's planes in `data` if a sample is undefined, then the field's
+void write_masked(const wr_enc_info& info, const wr_mask_result& res, const unsigned char* data, const std::string& header, const std::string& payload,
+                  int idset, const std::string& name)
+{
+    if (res.undefined) {
+        std::cout << " Masking detected, " << res.undefined << " undefined points as a bit mask of " << res.mask_len << " bytes, padding with fld_pad="
+                  << res.pad << std::endl;
+        Coding m;
+        m.nlay = 1;
+        m.ntot_enc = m.len_enc_vec[0] = (unsigned long)res.mask_len;
+        append_header_record(header, idset, "mask", m);
+        append_bytes(payload, data + info.ntot_enc, (unsigned long)res.mask_len);
+    }
+    Coding c;
+    c.tolabs = info.tolabs; c.midval = info.midval; c.halfspanval = info.halfspanval;
+    c.wlev = info.wlev; c.nlay = info.nlay; c.ntot_enc = info.ntot_enc;
+    for (int l = 0; l < info.nlay; l++) { c.deps_vec[l] = info.deps_vec[l]; c.minval_vec[l] = info.minval_vec[l]; c.len_enc_vec[l] = info.len_enc_vec[l]; }
+    append_header_record(header, idset, name, c);
+    if (c.ntot_enc > 0) append_bytes(payload, data, c.ntot_enc);
+    std::cout << "        tolabs=" << c.tolabs << std::endl;
+}
 
 // one TYPE 0 field through wr_encode_host_seg_masked: the "mask" record if a sample is undefined, then the field's record
 void code_masked(const MaskBits& mb, int nx, int ny, int nz, const double* fld, double tolrel, double below, std::vector<unsigned char>& buf,
@@ -229,22 +257,40 @@ void code_masked(const MaskBits& mb, int nx, int ny, int nz, const double* fld, 
         std::cout << "Error: " << wr_last_error() << std::endl;
         std::exit(1);
     }
-    if (res.undefined) {
-        std::cout << " Masking detected, " << res.undefined << " undefined points as a bit mask of " << res.mask_len << " bytes, padding with fld_pad="
-                  << res.pad << std::endl;
-        Coding m;
-        m.nlay = 1;
-        m.ntot_enc = m.len_enc_vec[0] = (unsigned long)res.mask_len;
-        append_header_record(header, idset, "mask", m);
-        append_bytes(payload, buf.data() + info.ntot_enc, (unsigned long)res.mask_len);
+    write_masked(info, res, buf.data(), header, payload, idset, name);
+}
+
+// --batch=N: the time records [first, first + count) of a TYPE 0 set, already read into flds, through ONE call of
+// wr_encode_host_seg_batch_masked; their records are written in order
+void code_masked_batch(const MaskBits& mb, int nx, int ny, int nz, const std::vector<std::vector<double>>& flds, int count, double tolrel, double below,
+                       std::vector<std::vector<unsigned char>>& bufs, const std::string& header, const std::string& payload, int first, const std::string& name)
+{
+    const size_t ntot = (size_t)nx * (size_t)ny * (size_t)nz;
+    unsigned char nlaymax;
+    unsigned long cap;
+    setup_wr(nx, ny, nz, &nlaymax, &cap);
+    const size_t need = (size_t)cap + wr_mask_bound(ntot, mb.seg);
+    double cutoff = tolrel;
+    std::vector<const double*> ptrs((size_t)count), cuts((size_t)count, &cutoff);
+    std::vector<unsigned char*> datas((size_t)count);
+    std::vector<size_t> caps((size_t)count, need);
+    std::vector<wr_enc_info> infos((size_t)count);
+    std::vector<wr_mask_result> res((size_t)count);
+    if (bufs.size() < (size_t)count) bufs.resize((size_t)count);
+    for (int f = 0; f < count; f++) {
+        if (bufs[(size_t)f].size() < need) bufs[(size_t)f].resize(need);
+        ptrs[(size_t)f] = flds[(size_t)f].data();
+        datas[(size_t)f] = bufs[(size_t)f].data();
     }
-    Coding c;
-    c.tolabs = info.tolabs; c.midval = info.midval; c.halfspanval = info.halfspanval;
-    c.wlev = info.wlev; c.nlay = info.nlay; c.ntot_enc = info.ntot_enc;
-    for (int l = 0; l < info.nlay; l++) { c.deps_vec[l] = info.deps_vec[l]; c.minval_vec[l] = info.minval_vec[l]; c.len_enc_vec[l] = info.len_enc_vec[l]; }
-    append_header_record(header, idset, name, c);
-    if (c.ntot_enc > 0) append_bytes(payload, buf.data(), c.ntot_enc);
-    std::cout << "        tolabs=" << c.tolabs << std::endl;
+    if (wr_encode_host_seg_batch_masked(mb.ctx, count, ptrs.data(), nx, ny, nz, 1, 1, 1, 1, cuts.data(), mb.seg, mb.brick, mb.strands, below, infos.data(),
+                                        datas.data(), caps.data(), nullptr, res.data()) != 0) {
+        std::cout << "Error: time records " << first << ".." << first + count - 1 << ": " << wr_last_error() << std::endl;
+        std::exit(1);
+    }
+    for (int f = 0; f < count; f++) {
+        std::cout << "Field number it=" << first + f << " (coded in a batch of " << count << ")" << std::endl;
+        write_masked(infos[(size_t)f], res[(size_t)f], datas[(size_t)f], header, payload, first + f, name);
+    }
 }
 
 // ---- TYPE 0 (mssg_enc.cpp:277-414)
@@ -259,6 +305,40 @@ int regular_output(const Params& p, int nbytes, const MaskBits* mb)
     truncate_file(payload);
     std::vector<double> fld(ntot), mask;
     std::vector<unsigned char> buf;
+    if (mb && mb->batch > 1) {  // ---- --batch=N: groups of up to N records, cut further by the device's free memory
+        const double thresh = g.undef + std::fabs(g.undef) * kMaskThresholdAcc;
+        unsigned char nlaymax;
+        unsigned long cap;
+        setup_wr(g.nx, g.ny, g.nz, &nlaymax, &cap);
+        std::vector<std::vector<double>> flds;
+        std::vector<std::vector<unsigned char>> bufs;
+        for (int a = 0; a < g.nt;) {
+            int count = std::min(mb->batch, g.nt - a);
+            if (count > WR_SEG_BATCH_MAX) count = WR_SEG_BATCH_MAX;
+            // an encode cannot know which records have undefined points, nor their plane counts: all of them, the most planes
+            const size_t budget = wr_ctx_device_free_bytes(mb->ctx) / 4 * 3;
+            while (count > 1) {
+                const size_t need = wr_seg_batch_device_bytes_masked(count, count, ntot, nlaymax, mb->seg, mb->brick, mb->strands, 0);
+                if (need && need <= budget) break;
+                count--;
+            }
+            if ((int)flds.size() < count) flds.resize((size_t)count);
+            for (int f = 0; f < count; f++) {
+                const int it = a + f;
+                std::cout << "Field number it=" << it << std::endl;
+                flds[(size_t)f].resize(ntot);
+                read_field(g.dset, p.flip != 0, nbytes, it, g.nx, g.ny, g.nz, g.nx, g.ny, 0, 0, flds[(size_t)f].data());
+                std::cout << "  read: fld_1d[0]=" << flds[(size_t)f][0] << " fld_1d[last]=" << flds[(size_t)f][ntot - 1] << std::endl;
+                double lo, hi;
+                min_max(flds[(size_t)f].data(), ntot, &lo, &hi);
+                std::cout << "        min=" << lo << " max=" << hi << std::endl;
+            }
+            if (count == 1) code_masked(*mb, g.nx, g.ny, g.nz, flds[0].data(), p.tol, thresh, buf, header, payload, a, g.dset);
+            else code_masked_batch(*mb, g.nx, g.ny, g.nz, flds, count, p.tol, thresh, bufs, header, payload, a, g.dset);
+            a += count;
+        }
+        return 0;
+    }
     for (int it = 0; it < g.nt; it++) {
         std::cout << "Field number it=" << it << std::endl;
         read_field(g.dset, p.flip != 0, nbytes, it, g.nx, g.ny, g.nz, g.nx, g.ny, 0, 0, fld.data());
@@ -385,13 +465,18 @@ int main(int argc, char** argv)
     std::vector<std::string> options;
     argc = wrcli::take_options(argc, argv, options);
     MaskBits mb;
-    bool mask_bits = false;
+    bool mask_bits = false, batch = false;
     const char* target_opt = nullptr;  // "maxerr", "rmse" or "psnr" once one of them is given
     for (const std::string& o : options) {
         std::string v;
         if (wrcli::option_value(o, "mask", &v) && v == "bits") { mask_bits = true; continue; }
+        if (wrcli::option_value(o, "batch", &v)) {
+            if (!wrcli::parse_uint(v, &mb.batch) || mb.batch < 1) { fprintf(stderr, "wrenc_mssg: --batch=%s: a count of at least 1 is required\n", v.c_str()); return 2; }
+            batch = true;
+            continue;
+        }
         const char* name = wrcli::option_value(o, "maxerr", &v) ? "maxerr" : wrcli::option_value(o, "rmse", &v) ? "rmse" : wrcli::option_value(o, "psnr", &v) ? "psnr" : nullptr;
-        if (!name) { fprintf(stderr, "wrenc_mssg: unknown option %s (--mask=bits, --maxerr=E, --rmse=E, --psnr=DB)\n", o.c_str()); return 2; }
+        if (!name) { fprintf(stderr, "wrenc_mssg: unknown option %s (--mask=bits, --maxerr=E, --rmse=E, --psnr=DB, --batch=N)\n", o.c_str()); return 2; }
         if (target_opt && strcmp(target_opt, name)) { fprintf(stderr, "wrenc_mssg: --%s and --%s exclude one another\n", target_opt, name); return 2; }
         char* end = nullptr;
         mb.target = strtod(v.c_str(), &end);
@@ -404,6 +489,18 @@ int main(int argc, char** argv)
     }
     if (target_opt && !mask_bits) {
         fprintf(stderr, "wrenc_mssg: --%s needs --mask=bits: the error is taken over the defined points of a bit-masked field\n", target_opt);
+        return 2;
+    }
+    if (batch && !mask_bits) {
+        fprintf(stderr, "wrenc_mssg: --batch needs --mask=bits: it groups the time records of a bit-masked set into one call\n");
+        return 2;
+    }
+    if (batch && target_opt) {
+        fprintf(stderr, "wrenc_mssg: --batch and --%s exclude one another: the tolerance searches are not batched\n", target_opt);
+        return 2;
+    }
+    if (batch && !(wr_encode_host_seg_batch_masked && wr_seg_batch_device_bytes_masked && wr_ctx_device_free_bytes)) {
+        fprintf(stderr, "wrenc_mssg: --batch is %s\n", wrcli::kNotSupported);
         return 2;
     }
     if (mask_bits) if (int rc = mask_bits_setup(&mb)) return rc;

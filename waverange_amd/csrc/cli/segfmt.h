@@ -107,6 +107,12 @@ int wr_decode_host_seg_roi_batch_masked(wr_ctx* ctx, double* h_out, int nfields,
                                         wr_mask_result* res) __attribute__((weak));
 size_t wr_seg_roi_batch_device_bytes_masked(int nfields, int nmasked, size_t n, int planes, unsigned seg, unsigned brick, unsigned strands, unsigned mask_seg,
                                             size_t out_elems) __attribute__((weak));
+// the masked encode over a batch of fields (wrenc_mssg --mask=bits --batch)
+int wr_encode_host_seg_batch_masked(wr_ctx* ctx, int nfields, const double* const* h_flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                    const double* const* cutoffvecs, unsigned seg, unsigned brick, unsigned strands, double below, wr_enc_info* infos,
+                                    unsigned char* const* data_encs, const size_t* caps, wr_timings* tm, wr_mask_result* results) __attribute__((weak));
+size_t wr_seg_batch_device_bytes_masked(int nfields, int nmasked, size_t n, int nlay, unsigned seg, unsigned brick, unsigned strands, int decode)
+    __attribute__((weak));
 }
 
 namespace wrcli {

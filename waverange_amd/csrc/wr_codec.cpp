@@ -2039,16 +2039,19 @@ unsigned long long* mask_result_host(wr_ctx* c) { return reinterpret_cast<unsign
 unsigned long long* mask_result_dev(wr_ctx* c) { return reinterpret_cast<unsigned long long*>(c->h_result_dev + 8 + 2 * WR_NLAYMAX + wrk::kProbeK + 5); }
 
 // the split's read-back: S and the count of the defined samples (c->h_result[0 .. 1]) as the count of undefined ones and the pad
+// (res[0 .. 1]: where the split's final kernel left S and the count; the batched split reads a pair per field the same way)
 template <class T>
-void mask_split_result(wr_ctx* c, size_t n, unsigned long long* undefined, double* pad)
+void mask_split_result(const double* res, size_t n, unsigned long long* undefined, double* pad)
 {
     unsigned long long count = 0;
-    memcpy(&count, c->h_result + 1, sizeof count);
+    memcpy(&count, res + 1, sizeof count);
     *undefined = (unsigned long long)n - count;
-    double mean = count ? c->h_result[0] / (double)count : NAN;
+    double mean = count ? res[0] / (double)count : NAN;
     if (sizeof(T) == sizeof(float)) mean = (double)(float)mean;  // (what an fp32 field is filled with)
     *pad = mean;
 }
+template <class T>
+void mask_split_result(wr_ctx* c, size_t n, unsigned long long* undefined, double* pad) { mask_split_result<T>(c->h_result, n, undefined, pad); }
 
 struct MaskEncode {
     // what the caller asks for
@@ -4106,12 +4109,14 @@ struct BatchBufs {
     uint8_t* pinned = nullptr;      // the job tables (they stay alive until the stream has drained) and the results
     uint8_t* pinned_dev = nullptr;  // the same block as the device sees it
     PlaneEvents ev;                 // one pair per plane index
+    hipStream_t also = nullptr;     // a second stream that uses the buffers (a masked batch: the masks' coder)
     explicit BatchBufs(wr_ctx* ctx) : c(ctx) {}
     BatchBufs(const BatchBufs&) = delete;
     BatchBufs& operator=(const BatchBufs&) = delete;
     ~BatchBufs()
     {
         (void)hipStreamSynchronize(c->stream);
+        if (also) (void)hipStreamSynchronize(also);
         for (const DevPlanes::Buf& b : taken) c->pool->planes.give(b);
         if (pinned) (void)hipHostFree(pinned);
     }
@@ -4139,9 +4144,244 @@ int fail_at(const char* what, int i, int rc)
 
 constexpr unsigned long long kBatchLaneLimit = 1ull << 31;
 
+// ---- masks across a batch of fields (wr_mask.h, "the batch forms").  The tables of the batched mask kernels and what they
+// return live in a pinned block of the call's own; it goes back once the context's stream has drained.
+struct MaskPinned {
+    wr_ctx* c;
+    uint8_t *host = nullptr, *dev = nullptr;
+    explicit MaskPinned(wr_ctx* ctx) : c(ctx) {}
+    MaskPinned(const MaskPinned&) = delete;
+    MaskPinned& operator=(const MaskPinned&) = delete;
+    ~MaskPinned()
+    {
+        if (!host) return;
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipHostFree(host);
+    }
+    int alloc(size_t bytes)
+    {
+        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&host), bytes ? bytes : 256, hipHostMallocDefault));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&dev), host, 0));
+        memset(host, 0, bytes);
+        return WR_OK;
+    }
+};
+
+// What the batched mask stages take: device memory per masked field and once per call, and the pinned tables.  The drivers
+// allocate by these and wr_seg_batch_device_bytes_masked sums them.
+size_t mask_batch_bits_bytes(size_t n) { return up256(wrmask::mask_bytes(n)); }
+size_t mask_batch_blob_cap(size_t n, unsigned seg) { return (wr_seg_bound(wrmask::mask_bytes(n), seg) + 15) & ~(size_t)15; }  // (MaskEncode's)
+size_t mask_batch_partial_bytes(size_t nfields, size_t n) { return up256(nfields * wrk::mask_split_batch_partials(n) * sizeof(double)); }
+size_t mask_batch_counters_bytes(size_t nmasks) { return up256(2 * nmasks * sizeof(unsigned long long)); }
+// the pinned block of a split: the items, then a (sum, count) pair per field
+size_t mask_batch_split_results_at(size_t nfields) { return up256(nfields * sizeof(wrk::MaskSplitItem)); }
+size_t mask_batch_split_pinned(size_t nfields) { return mask_batch_split_results_at(nfields) + up256(2 * nfields * sizeof(double)); }
+
+// (cu_mu held, the context's stream) the split of nfields device fields in one launch pair, waited for: undefined[f] and
+// pad[f] as mask_split_result forms them from field f's pair.  pin: mask_batch_split_pinned(nfields) bytes; partial:
+// mask_batch_partial_bytes(nfields, n)
+template <class T>
+int mask_split_batch_run(wr_ctx* c, const MaskPinned& pin, double* partial, int nfields, const T* const* x, uint8_t* const* bits, size_t n, double below,
+                         unsigned long long* undefined, double* pad)
+{
+    wrk::MaskSplitItem* const items = reinterpret_cast<wrk::MaskSplitItem*>(pin.host);
+    for (int f = 0; f < nfields; f++) { items[f].x = x[f]; items[f].bits = bits[f]; }
+    const size_t at = mask_batch_split_results_at(nfields);
+    wrk::mask_split_batch(items, reinterpret_cast<const wrk::MaskSplitItem*>(pin.dev), nfields, sizeof(T) == sizeof(float), n, below, partial,
+                          reinterpret_cast<double*>(pin.dev + at), c->stream);
+    if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "batched mask split launch failed");
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const double* const res = reinterpret_cast<const double*>(pin.host + at);
+    for (int f = 0; f < nfields; f++) mask_split_result<T>(res + 2 * f, n, &undefined[f], &pad[f]);
+    return WR_OK;
+}
+
+// (cu_mu held, the context's stream) pad[f] into the undefined samples of every field that has one (x[f] == nullptr: skipped),
+// one launch, not waited for.  pin: nfields items.  Returns the fields filled through *filled.
+template <class T>
+int mask_fill_batch_run(wr_ctx* c, const MaskPinned& pin, int nfields, T* const* x, const uint8_t* const* bits, size_t n, const double* values, int* filled)
+{
+    wrk::MaskFillItem* const items = reinterpret_cast<wrk::MaskFillItem*>(pin.host);
+    int count = 0;
+    for (int f = 0; f < nfields; f++) {
+        if (!x[f]) continue;
+        items[count].x = x[f]; items[count].bits = bits[f]; items[count].value = wrk::mask_fill_value(values[f], sizeof(T) == sizeof(float));
+        count++;
+    }
+    *filled = count;
+    if (!count) return WR_OK;
+    wrk::mask_fill_batch(reinterpret_cast<const wrk::MaskFillItem*>(pin.dev), count, sizeof(T) == sizeof(float), n, c->stream);
+    if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "batched mask fill launch failed");
+    return WR_OK;
+}
+
+const char* const kNoDefined = "no defined sample: every sample of the field is a NaN, an infinity or below the threshold";
+const char* const kMeanNotFinite = "the mean of the defined samples is not finite";
+
+// The masks of a batched encode (wr_encode_*_seg_batch_masked): per field the bit plane and what the split said; the blobs of
+// the fields that have an undefined sample come from ONE seg_encode_batch launch on a stream of the masks' own, which runs
+// under the fields' plane launches.
+struct MaskBatchEncode {
+    double below = -INFINITY;
+    std::vector<unsigned long long> undefined;
+    std::vector<double> pad;
+    std::vector<size_t> mask_len;
+    std::vector<float> split_ms, fill_ms;
+    float coder_ms = 0;
+
+    wr_ctx* c = nullptr;
+    MaskStreams s;
+    size_t n = 0, nsym = 0, blob_cap = 0;
+    unsigned seg = 0;
+    int nfields = 0;
+    std::vector<uint8_t*> bits, blob;
+    std::vector<int> job_of;  // field -> its job in the mask launch, -1: no undefined sample
+    uint8_t *pinned = nullptr, *pinned_dev = nullptr;  // the mask launch's job table and results (BatchPinned)
+    int njobs = 0;
+
+    MaskBatchEncode() = default;
+    MaskBatchEncode(const MaskBatchEncode&) = delete;
+    MaskBatchEncode& operator=(const MaskBatchEncode&) = delete;
+    ~MaskBatchEncode()
+    {
+        if (!pinned) return;
+        if (s.st) (void)hipStreamSynchronize(s.st);
+        (void)hipHostFree(pinned);
+    }
+
+    int begin(wr_ctx* ctx, BatchBufs* bufs, int count, size_t samples, unsigned seg_len)
+    {
+        c = ctx; nfields = count; n = samples; seg = seg_len; nsym = wrmask::mask_bytes(n);
+        blob_cap = mask_batch_blob_cap(n, seg);
+        undefined.assign(count, 0); pad.assign(count, 0.0); mask_len.assign(count, 0);
+        split_ms.assign(count, 0.f); fill_ms.assign(count, 0.f);
+        bits.assign(count, nullptr); blob.assign(count, nullptr); job_of.assign(count, -1);
+        for (int f = 0; f < count; f++)
+            if (!(bits[f] = bufs->take(mask_batch_bits_bytes(n)))) return WR_ERR_HIP;
+        return s.create();
+    }
+
+    // what the single call refuses, with the field in front
+    int check(int f) const
+    {
+        const std::string who = "field " + std::to_string(f) + ": ";
+        if (undefined[f] == (unsigned long long)n) return fail(WR_ERR_ARG, who + kNoDefined);
+        if (!(fabs(pad[f]) <= DBL_MAX)) return fail(WR_ERR_ARG, who + kMeanNotFinite);
+        return WR_OK;
+    }
+
+    // (cu_mu held) a host field where upload_field left it, before anything widens it: the single-field launchers
+    template <class T>
+    int split_fill(int f, T* d_x)
+    {
+        HIPCHK(hipEventRecord(s.ev[0], c->stream));
+        wrk::mask_split(d_x, n, below, bits[f], c->d_partial, c->h_result_dev, c->stream);
+        HIPCHK(hipEventRecord(s.ev[1], c->stream));
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask split launch failed");
+        HIPCHK(hipEventSynchronize(s.ev[1]));
+        split_ms[f] = s.ms(0);
+        mask_split_result<T>(c, n, &undefined[f], &pad[f]);
+        if (int rc = check(f)) return rc;
+        if (!undefined[f]) return WR_OK;
+        HIPCHK(hipEventRecord(s.ev[2], c->stream));
+        wrk::mask_fill(d_x, n, bits[f], (T)pad[f], c->stream);
+        HIPCHK(hipEventRecord(s.ev[3], c->stream));
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask fill launch failed");
+        HIPCHK(hipEventSynchronize(s.ev[3]));
+        fill_ms[f] = s.ms(1);
+        return WR_OK;
+    }
+
+    // (cu_mu held) device fields: all of them by one split launch pair and one fill launch, before the first transform
+    int split_fill_all(BatchBufs* bufs, const std::vector<FieldRef>& flds)
+    {
+        MaskPinned pin(c);
+        if (int rc = pin.alloc(std::max(mask_batch_split_pinned(nfields), (size_t)nfields * sizeof(wrk::MaskFillItem)))) return rc;
+        double* const partial = reinterpret_cast<double*>(bufs->take(mask_batch_partial_bytes(nfields, n)));
+        if (!partial) return WR_ERR_HIP;
+        std::vector<double*> x(nfields);
+        for (int f = 0; f < nfields; f++) x[f] = flds[f].dev;
+        HIPCHK(hipEventRecord(s.ev[0], c->stream));
+        if (int rc = mask_split_batch_run<double>(c, pin, partial, nfields, x.data(), bits.data(), n, below, undefined.data(), pad.data())) return rc;
+        HIPCHK(hipEventRecord(s.ev[1], c->stream));
+        for (int f = 0; f < nfields; f++) {
+            if (int rc = check(f)) return rc;
+            if (!undefined[f]) x[f] = nullptr;
+        }
+        int filled = 0;
+        HIPCHK(hipEventRecord(s.ev[2], c->stream));
+        if (int rc = mask_fill_batch_run<double>(c, pin, nfields, x.data(), bits.data(), n, pad.data(), &filled)) return rc;
+        HIPCHK(hipEventRecord(s.ev[3], c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (int f = 0; f < nfields; f++) { split_ms[f] = s.ms(0); if (undefined[f]) fill_ms[f] = s.ms(1); }
+        return WR_OK;
+    }
+
+    // (cu_mu held) every split has been read back: the masks of the fields that have an undefined sample in one launch on the
+    // second stream.  Returns the launches made through *launches.
+    int launch(BatchBufs* bufs, int* launches)
+    {
+        *launches = 0;
+        std::vector<wrk::SegJob> jobs;
+        for (int f = 0; f < nfields; f++) {
+            if (!undefined[f]) continue;
+            if (!(blob[f] = bufs->take(blob_cap))) return fail_at("field", f, WR_ERR_HIP);
+            job_of[f] = (int)jobs.size();
+            jobs.push_back(seg_encode_job(wrk::plane_ref(bits[f]), blob[f], blob_cap, 0));
+        }
+        njobs = (int)jobs.size();
+        if (!njobs) return WR_OK;
+        if ((unsigned long long)wrseg::seg_count(nsym, seg) * (unsigned)njobs >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the masks have 2^31 segments or more");
+        uint8_t* const stage = bufs->take(wrk::seg_batch_stage_bytes(njobs, nsym, seg));
+        if (!stage) return WR_ERR_HIP;
+        const BatchPinned pin(njobs);
+        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&pinned), pin.bytes(1), hipHostMallocDefault));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&pinned_dev), pinned, 0));
+        memset(pinned, 0, pin.bytes(1));
+        HIPCHK(hipEventRecord(s.ev[4], s.st));
+        wrk::seg_encode_batch(jobs.data(), jobs.size(), nsym, seg, pin.jobs(pinned, 0), stage, pin.results(pinned_dev, 0), s.st);
+        HIPCHK(hipEventRecord(s.ev[5], s.st));
+        if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "mask coder launch failed");
+        *launches = 1;
+        return WR_OK;
+    }
+
+    // the blobs' exact lengths: waits for the mask launch
+    int lengths()
+    {
+        if (!njobs) return WR_OK;
+        if (hipStreamSynchronize(s.st) != hipSuccess) return fail(WR_ERR_HIP, "the masks' coder failed on the device");
+        const unsigned long long* const res = BatchPinned(njobs).results(pinned, 0);
+        for (int f = 0; f < nfields; f++) {
+            if (job_of[f] < 0) continue;
+            const unsigned long long len = res[2 * job_of[f]], bad = res[2 * job_of[f] + 1];
+            if (bad || len > blob_cap) return fail(WR_ERR_HIP, "field " + std::to_string(f) + ": internal: mask plane: " + kOutgrew);
+            mask_len[f] = wrmask::kHeaderBytes + (size_t)len;
+        }
+        coder_ms = s.ms(2);
+        return WR_OK;
+    }
+
+    // field f's blob to data_enc + at
+    int download(int f, unsigned char* data_enc, size_t at)
+    {
+        if (!undefined[f]) return WR_OK;
+        wrmask::put_header(data_enc + at, n, undefined[f], pad[f]);
+        return xfer_field(c, &c->x_field, data_enc + at + wrmask::kHeaderBytes, blob[f], mask_len[f] - wrmask::kHeaderBytes, kDown);
+    }
+
+    void result(int f, wr_mask_result* res) const
+    {
+        res->undefined = undefined[f]; res->pad = pad[f]; res->mask_len = mask_len[f];
+        res->split_ms = split_ms[f]; res->fill_ms = fill_ms[f]; res->mask_coder_ms = undefined[f] ? coder_ms : 0;
+    }
+};
+
+// msk != nullptr: a masked batch (wr_encode_*_seg_batch_masked): every field is split and filled in front of its transform,
+// the masks of the fields that have an undefined sample are coded by one more launch, each blob lands behind its field's planes
 int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
                           const double* const* cutoffvecs, unsigned seg, unsigned brick, unsigned strands, wr_enc_info* infos,
-                          unsigned char* const* data_encs, const size_t* caps, wr_timings* tm)
+                          unsigned char* const* data_encs, const size_t* caps, wr_timings* tm, MaskBatchEncode* msk = nullptr)
 {
     // strands == 0: WRS1 / WRS2 (the entry points without that argument); otherwise WRS3, K lanes per segment
     if (int rc = seg_format_params(&seg, brick, strands)) return rc;
@@ -4184,9 +4424,14 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
     std::vector<uint8_t*> blob((size_t)nfields * WR_NLAYMAX, nullptr), perm(nfields, nullptr);
     std::vector<int> job_of((size_t)nfields * WR_NLAYMAX, -1);  // (field, plane) -> its job in the launch sequence of that plane index
     int maxlay = 0;
+    if (msk) {
+        if (int rc = msk->begin(c, &bufs, nfields, n, seg)) return rc;
+        bufs.also = msk->s.st;
+    }
     {
         StageLock cu(pool->cu_mu);
         clock_warmup(c, n);
+        if (msk && !any_host) if (int rc = msk->split_fill_all(&bufs, flds)) return rc;
         // ---- every field in turn through the slot: upload, transform, quantizer; its planes stay in the batch's buffers
         for (int f = 0; f < nfields; f++) {
             const FieldRef& fld = flds[f];
@@ -4195,6 +4440,10 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
             if (int rc = upload_field(c, slot.get(), fld, nx, ny, nz, wtflag, &up)) return fail_at("field", f, rc);
             local.h2d_ms += up.ms;
             double* const d_fld = up.d_fld;
+            if (msk && any_host) {  // the field where it landed: an fp32 field before anything widens it
+                float* const x32 = up.d_f32 ? const_cast<float*>(up.d_f32) : up.widen_from;
+                if (int rc = fld.host_f32 ? msk->split_fill(f, x32) : msk->split_fill(f, d_fld)) return rc;
+            }
             if (up.widen_from) wrk::widen_f32(up.widen_from, d_fld, n, c->stream);  // (the stage is held: at once)
             auto plane_buf = [&](unsigned l) -> const wrk::PlaneRef* {
                 uint8_t* const p = bufs.take(batch_plane_bytes(n));
@@ -4211,6 +4460,11 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
             if (rc) return fail_at("field", f, rc);
             local.quant_ms += ft.quant_ms; local.transform_ms += ft.transform_ms; local.minmax_ms += ft.minmax_ms;
             if ((int)infos[f].nlay > maxlay) maxlay = infos[f].nlay;
+        }
+        if (msk) {  // ---- the masks' one launch, on their stream: it runs under the plane launches below
+            int launches = 0;
+            if (int rc = msk->launch(&bufs, &launches)) return rc;
+            g_stat[WR_STAT_BATCH_CODER_LAUNCHES] += (unsigned long)launches;
         }
         // ---- one launch sequence per plane index over the fields that have such a plane
         if (maxlay) {
@@ -4244,6 +4498,7 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
             }
             if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the batched segment coder failed on the device" + launch_describe(c));
         }
+        if (msk) if (int rc = msk->lengths()) return rc;
         pool->last_stage_end.store(now());
     }
     // ---- stage "down": every blob, one copy each, to its place in its field's data_enc
@@ -4254,12 +4509,15 @@ int encode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
         auto res_of = [&](int l) { return pin.results(bufs.pinned, l) + 2 * job_of[(size_t)f * WR_NLAYMAX + l]; };
         if (int rc = seg_coded_lengths(info->nlay, blob_cap, res_of, info->len_enc_vec, &total, who)) return rc;
         if (total > caps[f] || (total && !data_encs[f])) return fail(WR_ERR_OVERFLOW, who + wrtc::kTooLarge);
+        if (msk && msk->undefined[f] && (!data_encs[f] || msk->mask_len[f] > caps[f] - total))
+            return fail(WR_ERR_OVERFLOW, who + "the coded buffer does not hold the field's planes and the mask blob of " + std::to_string(msk->mask_len[f]) + " bytes");
         size_t at = 0;
         for (int l = 0; l < (int)info->nlay; l++) {
             if (int rc = xfer_field(c, &c->x_field, data_encs[f] + at, blob[(size_t)f * WR_NLAYMAX + l], info->len_enc_vec[l], kDown)) return fail_at("field", f, rc);
             local.d2h_ms += (float)c->x_field.ms;
             at += info->len_enc_vec[l];
         }
+        if (msk) if (int rc = msk->download(f, data_encs[f], total)) return fail_at("field", f, rc);
         info->ntot_enc = total;
     }
     fold_coder_seconds(bufs, maxlay, &local);  // one entry per plane index
@@ -4306,13 +4564,33 @@ int batch_chunk_launch(const std::vector<wrk::SegJob>& jobs, bool stranded, uint
     return launches;
 }
 
+// The masks of a batched decode (wr_decode_*_seg_batch_masked): a MaskJob per record that has a blob.  Each is one more WRS1 job
+// of the mixed driver's plain launch; one k_mask_check_batch launch behind the coder stage judges them all, before any
+// dequantizer runs; the existing fill then puts `fill` into each field behind its inverse transform.
+struct MaskBatchDecode {
+    double fill = NAN;
+    std::vector<MaskJob> job;  // per field; blob == nullptr: an unmasked record
+    std::vector<int> index;    // field -> its place among the masks, -1: none
+    int nmask = 0;
+    float coder_ms = 0;
+
+    void result(int f, wr_mask_result* res) const
+    {
+        memset(res, 0, sizeof *res);
+        if (index[f] < 0) return;
+        res->undefined = job[f].info.undefined; res->pad = job[f].info.pad; res->mask_len = job[f].len;
+        res->mask_coder_ms = coder_ms;
+    }
+};
+
 // mixed == false: wr_decode_*_seg_batch -- WRS1 and WRS2 fields, a WRS3 field is refused, one coder launch per plane index.
 // mixed == true: wr_decode_*_seg_batch_mixed -- WRS3 fields beside them, every (field, plane) of the call a job of its own, the
 // plain jobs through k_seg_decode_batch and the stranded ones through k_strand_decode_batch: two launches while neither kind has
 // more than WR_SEG_BATCH_MAX jobs.  Everything around the coder stage is the same code.
 int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& flds, int nx, int ny, int nz, const wr_enc_info* infos,
-                          const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm, bool mixed = false)
+                          const unsigned char* const* data_encs, const size_t* data_lens, wr_timings* tm, bool mixed = false, MaskBatchDecode* msk = nullptr)
 {
+    // msk != nullptr (mixed only): data_lens are the field parts' lengths, the blobs are the jobs'
     if (!infos || !data_encs) return fail(WR_ERR_ARG, "null array");
     if (int rc = ctx_bind(c)) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -4349,15 +4627,51 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
     }
     for (int l = 0; l < maxlay && !mixed; l++)
         if (lanes[l] >= kBatchLaneLimit) return fail(WR_ERR_ARG, "too many segments: the planes of index " + std::to_string(l) + " have 2^31 segments or more");
+    // ---- every mask blob, likewise.  A mask is one more plain job; its failure count lies behind the planes'
+    const size_t mask_job0 = njobs;
+    if (msk) {
+        std::vector<const unsigned char*> blobs(nfields);
+        std::vector<size_t> lens(nfields);
+        std::vector<wrmask::BlobInfo> bi(nfields);
+        for (int f = 0; f < nfields; f++) { blobs[f] = msk->job[f].blob; lens[f] = msk->job[f].len; }
+        std::string why;
+        const int failed = wrmask::check_blobs(blobs.data(), lens.data(), nfields, n, bi.data(), &why);
+        if (failed < nfields) return fail(WR_ERR_STREAM, "field " + std::to_string(failed) + ": " + why);
+        msk->index.assign(nfields, -1);
+        for (int f = 0; f < nfields; f++) {
+            if (!blobs[f]) continue;
+            MaskJob& j = msk->job[f];
+            j.info = bi[f]; j.n = n; j.nsym = wrmask::mask_bytes(n);
+            msk->index[f] = msk->nmask++;
+        }
+        njobs += (size_t)msk->nmask;
+        nplain += (size_t)msk->nmask;
+    }
+    const int nmask = msk ? msk->nmask : 0;
+    const bool coded = maxlay || nmask;
     c->pend_valid = false;
     PlaneHold planes(c);
     BatchBufs bufs(c);
+    MaskPinned mask_pin(c);  // the table of the masks' planes for their check
+    unsigned long long* d_counters = nullptr;
     uint8_t* d_once = nullptr;
     const size_t table = wrk::seg_batch_table_bytes(nfields);
     // the jobs' failure counts lie behind the tables, in the order of the fields and their planes
     const size_t tables_bytes = mixed ? batch_mixed_tables_bytes(nplain, nstranded) : (size_t)maxlay * table;
-    if (maxlay) {
+    if (coded) {
         std::lock_guard<std::mutex> gather(pool->planes.gather_mu);  // one decode at a time gathers its planes (decode_impl)
+        for (int f = 0; f < nfields && nmask; f++) {
+            if (msk->index[f] < 0) continue;
+            MaskJob& j = msk->job[f];
+            j.bits = bufs.take(j.bits_bytes());
+            j.work = bufs.take(j.work_bytes());
+            j.d_blob = bufs.take((j.blob_bytes() + 15) & ~(size_t)15);
+            if (!j.bits || !j.work || !j.d_blob) return fail_at("field", f, WR_ERR_HIP);
+        }
+        if (nmask) {
+            if (!(d_counters = reinterpret_cast<unsigned long long*>(bufs.take(mask_batch_counters_bytes(nmask))))) return WR_ERR_HIP;
+            if (int rc = mask_pin.alloc((size_t)nmask * sizeof(uint8_t*))) return rc;
+        }
         for (int f = 0; f < nfields; f++) {
             BatchField& b = bf[f];
             for (int l = 0; l < b.s.nlay; l++) {
@@ -4380,6 +4694,11 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
             local.h2d_ms += (float)c->x_field.ms;
             if (int rc = seg_upload_offsets(data_encs[f] + s.off[l], s.head(), s.nseg[l], bf[f].work[l])) return fail_at("field", f, rc);
         }
+    for (int f = 0; f < nfields && nmask; f++) {
+        if (msk->index[f] < 0) continue;
+        size_t bytes_up = 0;
+        if (int rc = msk->job[f].upload(c, &local.h2d_ms, &bytes_up)) return fail_at("field", f, rc);
+    }
     const double t_coded = now();
     SlotNeed need;
     transform_need(nx, ny, nz, wlev_any ? -kWavLvl : 0, &need);
@@ -4390,8 +4709,8 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
     {
         StageLock cu(pool->cu_mu);
         clock_warmup(c, n);
-        if (maxlay) {
-            // job (f, l) counts into d_bad[job0 of f + l]
+        if (coded) {
+            // job (f, l) counts into d_bad[job0 of f + l], the mask of field f into d_bad[mask_job0 + its place among the masks]
             unsigned int* const d_bad = reinterpret_cast<unsigned int*>(d_once + tables_bytes);
             const size_t per_l = BatchPinned(nfields).per_l;
             HIPCHK(hipMemsetAsync(d_bad, 0, 4 * njobs, c->stream));
@@ -4408,6 +4727,14 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
                         (b.s.strands ? stranded : jobs).push_back(job);
                     }
                 }
+                std::vector<const uint8_t*> mask_planes;
+                for (int f = 0; f < nfields && nmask; f++) {
+                    if (msk->index[f] < 0) continue;
+                    wrk::SegJob job = msk->job[f].seg_job();
+                    job.bad = d_bad + mask_job0 + (size_t)msk->index[f];
+                    jobs.push_back(job);
+                    mask_planes.push_back(msk->job[f].bits);
+                }
                 if (!batch_chunk_lanes_ok(jobs) || !batch_chunk_lanes_ok(stranded)) return fail(WR_ERR_ARG, "too many segments: a launch of the call has 2^31 lanes or more");
                 if (int rc = bufs.ev.create(0)) return rc;
                 launch_note(c, "seg_decode_batch_mixed", 0, d_once, n, bufs.pinned, wrk::plane_ref(d_once));
@@ -4418,6 +4745,11 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
                 HIPCHK(hipEventRecord(bufs.ev[1], c->stream));
                 if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "batched segment decoder launch failed" + launch_describe(c));
                 g_stat[WR_STAT_BATCH_CODER_LAUNCHES] += (unsigned long)launches;
+                if (nmask) {  // every mask judged by one launch: the counts come back with the failure counts
+                    memcpy(mask_pin.host, mask_planes.data(), mask_planes.size() * sizeof(uint8_t*));
+                    wrk::mask_check_batch(reinterpret_cast<const uint8_t* const*>(mask_pin.dev), nmask, n, d_counters, c->stream);
+                    if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "batched mask check launch failed");
+                }
             }
             for (int l = 0; l < maxlay && !mixed; l++) {
                 if (int rc = bufs.ev.create(l)) return rc;
@@ -4442,20 +4774,40 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
             // the dequantizers only run if every segment of every field decoded: the counts come back once
             std::vector<unsigned int> bad(njobs);
             HIPCHK(hipMemcpyAsync(bad.data(), d_bad, 4 * bad.size(), hipMemcpyDeviceToHost, c->stream));
+            std::vector<unsigned long long> counters(2 * (size_t)nmask);
+            if (nmask) HIPCHK(hipMemcpyAsync(counters.data(), d_counters, 8 * counters.size(), hipMemcpyDeviceToHost, c->stream));
             if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(WR_ERR_HIP, "the batched segment decoder failed on the device" + launch_describe(c));
-            for (int f = 0; f < nfields; f++)
+            for (int f = 0; f < nfields; f++) {
                 for (int l = 0; l < bf[f].s.nlay; l++)
                     if (const unsigned int k = bad[(size_t)bf[f].job0 + l])
                         return fail(WR_ERR_STREAM, "field " + std::to_string(f) + ": plane " + std::to_string(l) + ": " + bad_segments_text(k));
+                if (!nmask || msk->index[f] < 0) continue;
+                // the mask, in the single call's words (MaskDecode::check): nothing of the caller's has been written yet
+                const std::string who = "field " + std::to_string(f) + ": mask blob: ";
+                const size_t m = (size_t)msk->index[f];
+                if (const unsigned int k = bad[mask_job0 + m]) return fail(WR_ERR_STREAM, who + bad_segments_text(k));
+                if (counters[2 * m + 1]) return fail(WR_ERR_STREAM, who + "a bit beyond the field's last sample is set");
+                if (counters[2 * m] != msk->job[f].info.undefined) return fail(WR_ERR_STREAM, who + "the mask's set bits are not the count in its header");
+            }
             fold_coder_seconds(bufs, mixed ? 1 : maxlay, &local);  // one entry per plane index; mixed: one for the call's launches
+            if (nmask) msk->coder_ms = (float)(1e3 * local.plane_coder_s[0]);
         }
         // ---- every field in turn through the slot: dequantizer, inverse transform, download
         for (int f = 0; f < nfields; f++) {
             const FieldRef& fld = flds[f];
             const wr_enc_info* const info = &infos[f];
             const BatchField& b = bf[f];
+            const uint8_t* const mask_bits = (nmask && msk->index[f] >= 0) ? msk->job[f].bits : nullptr;
             if (!b.s.nlay) {
                 if (int rc = fill_constant(c, fld, n, info->midval)) return rc;
+                if (mask_bits && fld.dev) {
+                    wrk::mask_fill(fld.dev, n, mask_bits, msk->fill, c->stream);
+                    if (int rc = kernel_stage_end(c, WR_OK)) return fail_at("field", f, rc);
+                } else if (mask_bits) {  // a host field takes the bits on the host, as it took midval there
+                    std::vector<unsigned char> h(msk->job[f].nsym);
+                    HIPCHK(hipMemcpy(h.data(), mask_bits, h.size(), hipMemcpyDeviceToHost));
+                    mask_restore_host(fld, mask_region(nx, ny, nz, 0, nullptr), h.data(), msk->fill);
+                }
                 continue;
             }
             for (int l = 0; l < b.s.nlay && mixed; l++)  // a blocked field of a mixed decode: its planes back to the natural order
@@ -4467,6 +4819,10 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
             float* d_f32 = nullptr;
             launch_note(c, "dequant", b.s.nlay - 1, d_fld, n, nullptr, p.q[b.s.nlay - 1]);
             int rc = inverse_from_planes(c, slot.get(), d_fld, nx, ny, nz, (int)info->wlev, p, fld.host_f32 ? &d_f32 : nullptr);
+            if (rc == WR_OK && mask_bits) {  // `fill` where the finisher left the field: the slot (a host field) or the caller's buffer
+                if (fld.host_f32) wrk::mask_fill(d_f32, n, mask_bits, (float)msk->fill, c->stream);
+                else wrk::mask_fill(d_fld, n, mask_bits, msk->fill, c->stream);
+            }
             if (rc == WR_OK && hipGetLastError() != hipSuccess) rc = fail(WR_ERR_HIP, "kernel launch failed");
             if (hipStreamSynchronize(c->stream) != hipSuccess && rc == WR_OK) rc = fail(WR_ERR_HIP, "the decoder's kernel stage failed on the device" + launch_describe(c));
             if (rc) return fail_at("field", f, rc);
@@ -4488,6 +4844,50 @@ int decode_seg_batch_impl(wr_ctx* c, int nfields, const std::vector<FieldRef>& f
     local.wait = t_phase - t_coded;
     local.transfer = t_coded - t0;
     if (tm) *tm = local;
+    return WR_OK;
+}
+
+// the stage calls of the batched mask kernels (wr_dev_mask_split_batch, wr_dev_mask_fill_batch and their _f32 forms)
+int mask_batch_args(wr_ctx* c, int count, const char* what, const void* const* a, const void* const* b, size_t n, bool null_a_ok = false)
+{
+    if (count < 1 || count > WR_SEG_BATCH_MAX) return fail(WR_ERR_ARG, std::string(what) + " must be in 1.." + std::to_string(WR_SEG_BATCH_MAX));
+    if (int rc = ctx_bind(c)) return rc;
+    if (!a || !b) return fail(WR_ERR_ARG, "null array");
+    if (!n) return fail(WR_ERR_ARG, "empty array");
+    for (int f = 0; f < count; f++)
+        if ((!a[f] && !null_a_ok) || (a[f] && !b[f])) return fail(WR_ERR_ARG, "field " + std::to_string(f) + ": null pointer");
+    return WR_OK;
+}
+
+template <class T>
+int dev_mask_split_batch(wr_ctx* c, int nfields, const T* const* d_flds, size_t n, double below, unsigned char* const* d_bits,
+                                unsigned long long* undefined, double* pad)
+{
+    if (int rc = mask_batch_args(c, nfields, "nfields", reinterpret_cast<const void* const*>(d_flds), reinterpret_cast<const void* const*>(d_bits), n)) return rc;
+    if (!undefined || !pad) return fail(WR_ERR_ARG, "null array");
+    if (below != below) return fail(WR_ERR_ARG, "the threshold `below` is a NaN (-INFINITY switches it off)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    BatchBufs bufs(c);
+    MaskPinned pin(c);
+    if (int rc = pin.alloc(mask_batch_split_pinned(nfields))) return rc;
+    double* const partial = reinterpret_cast<double*>(bufs.take(mask_batch_partial_bytes(nfields, n)));
+    if (!partial) return WR_ERR_HIP;
+    StageLock cu(c->pool->cu_mu);
+    return mask_split_batch_run<T>(c, pin, partial, nfields, d_flds, d_bits, n, below, undefined, pad);
+}
+
+template <class T>
+int dev_mask_fill_batch(wr_ctx* c, int nfields, T* const* d_flds, size_t n, const unsigned char* const* d_bits, const double* values)
+{
+    if (int rc = mask_batch_args(c, nfields, "nfields", reinterpret_cast<const void* const*>(d_flds), reinterpret_cast<const void* const*>(d_bits), n, true)) return rc;
+    if (!values) return fail(WR_ERR_ARG, "null array");
+    std::lock_guard<std::mutex> lk(c->mu);
+    MaskPinned pin(c);
+    if (int rc = pin.alloc((size_t)nfields * sizeof(wrk::MaskFillItem))) return rc;
+    StageLock cu(c->pool->cu_mu);
+    int filled = 0;
+    if (int rc = mask_fill_batch_run<T>(c, pin, nfields, d_flds, d_bits, n, values, &filled)) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
     return WR_OK;
 }
 
@@ -4730,6 +5130,160 @@ int wr_decode_device_seg_batch_mixed(wr_ctx* c, int nfields, double* const* d_fl
     std::vector<FieldRef> flds;
     if (int rc = batch_fields(nfields, d_flds, 2, &flds)) return rc;
     return decode_seg_batch_impl(c, nfields, flds, nx, ny, nz, infos, data_encs, data_lens, tm, true);
+}
+
+// ---- masks across a batch: the stage calls, the sizing, and the whole-path calls (MaskBatchEncode / MaskBatchDecode above)
+int wr_dev_mask_split_batch(wr_ctx* c, int nfields, const double* const* d_flds, size_t n, double below, unsigned char* const* d_bits,
+                            unsigned long long* undefined, double* pad)
+{
+    return dev_mask_split_batch(c, nfields, d_flds, n, below, d_bits, undefined, pad);
+}
+int wr_dev_mask_split_batch_f32(wr_ctx* c, int nfields, const float* const* d_flds, size_t n, double below, unsigned char* const* d_bits,
+                                unsigned long long* undefined, double* pad)
+{
+    return dev_mask_split_batch(c, nfields, d_flds, n, below, d_bits, undefined, pad);
+}
+int wr_dev_mask_fill_batch(wr_ctx* c, int nfields, double* const* d_flds, size_t n, const unsigned char* const* d_bits, const double* values)
+{
+    return dev_mask_fill_batch(c, nfields, d_flds, n, d_bits, values);
+}
+int wr_dev_mask_fill_batch_f32(wr_ctx* c, int nfields, float* const* d_flds, size_t n, const unsigned char* const* d_bits, const double* values)
+{
+    return dev_mask_fill_batch(c, nfields, d_flds, n, d_bits, values);
+}
+
+int wr_dev_mask_check_batch(wr_ctx* c, int nmasks, const unsigned char* const* d_bits, size_t n, unsigned long long* undefined, unsigned char* beyond)
+{
+    if (int rc = mask_batch_args(c, nmasks, "nmasks", reinterpret_cast<const void* const*>(d_bits), reinterpret_cast<const void* const*>(d_bits), n)) return rc;
+    if (!undefined || !beyond) return fail(WR_ERR_ARG, "null array");
+    std::lock_guard<std::mutex> lk(c->mu);
+    BatchBufs bufs(c);
+    MaskPinned pin(c);
+    if (int rc = pin.alloc((size_t)nmasks * sizeof(uint8_t*))) return rc;
+    unsigned long long* const d_counters = reinterpret_cast<unsigned long long*>(bufs.take(mask_batch_counters_bytes(nmasks)));
+    if (!d_counters) return WR_ERR_HIP;
+    memcpy(pin.host, d_bits, (size_t)nmasks * sizeof(uint8_t*));
+    std::vector<unsigned long long> got(2 * (size_t)nmasks);
+    StageLock cu(c->pool->cu_mu);
+    wrk::mask_check_batch(reinterpret_cast<const uint8_t* const*>(pin.dev), nmasks, n, d_counters, c->stream);
+    if (hipGetLastError() != hipSuccess) return fail(WR_ERR_HIP, "batched mask check launch failed");
+    HIPCHK(hipMemcpyAsync(got.data(), d_counters, 8 * got.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int m = 0; m < nmasks; m++) { undefined[m] = got[2 * (size_t)m]; beyond[m] = got[2 * (size_t)m + 1] ? 1 : 0; }
+    return WR_OK;
+}
+
+size_t wr_seg_batch_device_bytes_masked(int nfields, int nmasked, size_t n, int nlay, unsigned seg, unsigned brick, unsigned strands, int decode)
+{
+    if (!seg) seg = WR_SEG_DEFAULT;
+    if (nfields < 1 || nfields > WR_SEG_BATCH_MAX || !n || nlay < 0 || nlay > WR_NLAYMAX || !wrseg::seg_ok(seg) || (brick && !wrblk::brick_ok(brick))) return 0;
+    if (strands && !wrseg::strands_ok(strands, seg)) return 0;
+    if (nmasked < 0 || nmasked > nfields) return 0;
+    // strands == 0 means WRS1 / WRS2 planes here (nothing is defaulted but seg).  An encode of such planes is the plain batch
+    // call's; their decode is the mixed driver's all the same, with the blobs at the WRS1 / WRS2 bound.  (nlay == 0, fields that
+    // are constant once padded: the base is 0 and the masks' share remains.)
+    size_t base = 0;
+    if (strands) base = wr_seg_batch_device_bytes_strands(nfields, n, nlay, seg, brick, strands, decode);
+    else if (!decode) base = wr_seg_batch_device_bytes(nfields, n, nlay, seg, brick, 0);
+    else {
+        const size_t jobs = (size_t)nfields * (size_t)nlay;
+        base = jobs * (batch_plane_bytes(n) + up256(seg_blob_cap(n, seg, brick, 0)) + up256(batch_work_bytes(wrseg::seg_count(n, seg))) + batch_perm_bytes(n, brick)) +
+               up256(batch_mixed_once_bytes(0, jobs));
+    }
+    const size_t M = (size_t)nmasked, nsym = wrmask::mask_bytes(n);
+    if (!decode) {
+        const size_t stage = M ? up256(wrk::seg_batch_stage_bytes(M, nsym, seg)) : 0;
+        return base + M * (mask_batch_bits_bytes(n) + up256(mask_batch_blob_cap(n, seg))) + stage + mask_batch_partial_bytes((size_t)nfields, n);
+    }
+    // the masks are plain jobs of the mixed launch: their tables and failure counts beside the planes', which the base sizes as
+    // stranded jobs
+    const size_t jobs = (size_t)nfields * (size_t)nlay;
+    const size_t once = up256(batch_mixed_once_bytes(M, jobs)) - up256(batch_mixed_once_bytes(0, jobs));
+    return base + M * (mask_batch_bits_bytes(n) + up256(wr_mask_bound(n, seg)) + up256(batch_work_bytes(wrseg::seg_count(nsym, seg)))) + once +
+           mask_batch_counters_bytes(M);
+}
+
+static int encode_seg_batch_masked(wr_ctx* c, int nfields, const std::vector<FieldRef>& flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                   const double* const* cutoffvecs, unsigned seg, unsigned brick, unsigned strands, double below, wr_enc_info* infos,
+                                   unsigned char* const* data_encs, const size_t* caps, wr_timings* tm, wr_mask_result* results)
+{
+    if (below != below) return fail(WR_ERR_ARG, "the threshold `below` is a NaN (-INFINITY switches it off)");
+    MaskBatchEncode m;
+    m.below = below;
+    const int rc = encode_seg_batch_impl(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, strands, infos, data_encs, caps, tm, &m);
+    if (rc == WR_OK && results)
+        for (int f = 0; f < nfields; f++) m.result(f, &results[f]);
+    return rc;
+}
+
+int wr_encode_host_seg_batch_masked(wr_ctx* c, int nfields, const double* const* h_flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                    const double* const* cutoffvecs, unsigned seg, unsigned brick, unsigned strands, double below, wr_enc_info* infos,
+                                    unsigned char* const* data_encs, const size_t* caps, wr_timings* tm, wr_mask_result* results)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, h_flds, 0, &flds)) return rc;
+    return encode_seg_batch_masked(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, strands, below, infos, data_encs, caps, tm, results);
+}
+int wr_encode_host_seg_batch_masked_f32(wr_ctx* c, int nfields, const float* const* h_flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                        const double* const* cutoffvecs, unsigned seg, unsigned brick, unsigned strands, double below, wr_enc_info* infos,
+                                        unsigned char* const* data_encs, const size_t* caps, wr_timings* tm, wr_mask_result* results)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, h_flds, 1, &flds)) return rc;
+    return encode_seg_batch_masked(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, strands, below, infos, data_encs, caps, tm, results);
+}
+int wr_encode_device_seg_batch_masked(wr_ctx* c, int nfields, double* const* d_flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,
+                                      const double* const* cutoffvecs, unsigned seg, unsigned brick, unsigned strands, double below, wr_enc_info* infos,
+                                      unsigned char* const* data_encs, const size_t* caps, wr_timings* tm, wr_mask_result* results)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, d_flds, 2, &flds)) return rc;
+    return encode_seg_batch_masked(c, nfields, flds, nx, ny, nz, wtflag, mx, my, mz, cutoffvecs, seg, brick, strands, below, infos, data_encs, caps, tm, results);
+}
+
+static int decode_seg_batch_masked(wr_ctx* c, int nfields, const std::vector<FieldRef>& flds, int nx, int ny, int nz, const wr_enc_info* infos,
+                                   const unsigned char* const* data_encs, const size_t* data_lens, double fill, wr_timings* tm, wr_mask_result* results)
+{
+    if (!infos || !data_encs || !data_lens) return fail(WR_ERR_ARG, "null array");
+    // data_lens[f] == infos[f].ntot_enc or 0: an unmasked record (a shorter buffer: the plain driver refuses it)
+    MaskBatchDecode m;
+    m.fill = fill;
+    m.job.resize(nfields);
+    std::vector<size_t> field_lens(nfields);
+    for (int f = 0; f < nfields; f++) {
+        field_lens[f] = data_lens[f];
+        if (data_lens[f] == 0 || data_lens[f] <= infos[f].ntot_enc) continue;
+        if (!data_encs[f]) return fail(WR_ERR_ARG, "field " + std::to_string(f) + ": null coded buffer");
+        m.job[f].blob = data_encs[f] + infos[f].ntot_enc;
+        m.job[f].len = data_lens[f] - infos[f].ntot_enc;
+        field_lens[f] = infos[f].ntot_enc;
+    }
+    const int rc = decode_seg_batch_impl(c, nfields, flds, nx, ny, nz, infos, data_encs, field_lens.data(), tm, true, &m);
+    if (rc == WR_OK && results)
+        for (int f = 0; f < nfields; f++) m.result(f, &results[f]);
+    return rc;
+}
+
+int wr_decode_host_seg_batch_masked(wr_ctx* c, int nfields, double* const* h_flds, int nx, int ny, int nz, const wr_enc_info* infos,
+                                    const unsigned char* const* data_encs, const size_t* data_lens, double fill, wr_timings* tm, wr_mask_result* results)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, h_flds, 0, &flds)) return rc;
+    return decode_seg_batch_masked(c, nfields, flds, nx, ny, nz, infos, data_encs, data_lens, fill, tm, results);
+}
+int wr_decode_host_seg_batch_masked_f32(wr_ctx* c, int nfields, float* const* h_flds, int nx, int ny, int nz, const wr_enc_info* infos,
+                                        const unsigned char* const* data_encs, const size_t* data_lens, double fill, wr_timings* tm, wr_mask_result* results)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, h_flds, 1, &flds)) return rc;
+    return decode_seg_batch_masked(c, nfields, flds, nx, ny, nz, infos, data_encs, data_lens, fill, tm, results);
+}
+int wr_decode_device_seg_batch_masked(wr_ctx* c, int nfields, double* const* d_flds, int nx, int ny, int nz, const wr_enc_info* infos,
+                                      const unsigned char* const* data_encs, const size_t* data_lens, double fill, wr_timings* tm, wr_mask_result* results)
+{
+    std::vector<FieldRef> flds;
+    if (int rc = batch_fields(nfields, d_flds, 2, &flds)) return rc;
+    return decode_seg_batch_masked(c, nfields, flds, nx, ny, nz, infos, data_encs, data_lens, fill, tm, results);
 }
 
 int wr_encode_host_seg_batch(wr_ctx* c, int nfields, const double* const* h_flds, int nx, int ny, int nz, int wtflag, int mx, int my, int mz,

@@ -207,6 +207,32 @@ int mask_restore_boxes(double* out, const wrmask::Region* gs, const size_t* offs
                        uint8_t* host_table, uint8_t* table, hipStream_t st);
 int mask_restore_boxes(float* out, const wrmask::Region* gs, const size_t* offs, size_t nroi, const uint8_t* const* bits, size_t nfields, size_t field_elems, float v,
                        uint8_t* host_table, uint8_t* table, hipStream_t st);
+// ---- the batch forms: split, fill and check across fields of n samples each, one launch per stage on a grid of
+// (mask_grid(n), fields) blocks.  The tables live in pinned host memory that the kernels read directly (d_items: the same
+// block as the device sees it) and stay alive until the stream has passed the launch.
+// k_mask_split_batch + k_mask_split_final_batch: field f's mask into items[f].bits, result[2f] = S and result[2f + 1] = the
+// count of its defined samples, bit for bit what mask_split gives for that field alone (block (x, f) is block x of
+// k_mask_split).  partial: nfields * mask_split_batch_partials(n) 8-byte words of device memory.  The kernel stores a word per
+// chunk only if every field's bits pointer is 8-byte aligned (host_items is read for that).
+struct MaskSplitItem {
+    const void* x;  // n samples, fp64 or fp32 as the launch says
+    uint8_t* bits;
+};
+size_t mask_split_batch_partials(size_t n);
+void mask_split_batch(const MaskSplitItem* host_items, const MaskSplitItem* d_items, int nfields, bool f32, size_t n, double below, double* partial, double* result,
+                      hipStream_t st);
+// k_mask_fill_batch: mask_fill on every item; value = mask_fill_value(v, f32), the bits of the (T)v that mask_fill would store
+struct MaskFillItem {
+    void* x;
+    const uint8_t* bits;
+    unsigned long long value;
+};
+unsigned long long mask_fill_value(double v, bool f32);
+void mask_fill_batch(const MaskFillItem* d_items, int nitems, bool f32, size_t n, hipStream_t st);
+// k_mask_check_batch: the count-only mask_restore on nmasks masks of n bits: counters[2m] += the set bits of mask m's
+// ceil(n / 8) bytes, counters[2m + 1] |= 1 if one lies at or beyond n (integer atomics, one per wave and mask; zeroed here).
+// d_masks: the table of plane pointers, device-visible; counters: 2 * nmasks words of device memory.
+void mask_check_batch(const uint8_t* const* d_masks, int nmasks, size_t n, unsigned long long* counters, hipStream_t st);
 // x[0, n) = v in fp32 (wrk::fill is the fp64 one)
 void fill_f32(float* x, size_t n, float v, hipStream_t st);
 // ---- k_err_stats_masked: the compare of wrk::err_stats over the samples whose bit is clear.  result[0 .. 2] = the maximum of the

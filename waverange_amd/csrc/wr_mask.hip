@@ -573,4 +573,155 @@ void err_stats_masked(const float* a, const float* b, size_t n, const uint8_t* b
     err_stats_masked_t(a, b, n, bits, partial, result, defined, st);
 }
 
+// ---- split, fill and check across a batch of fields of n samples each, one launch per stage.  The grid is two-dimensional:
+// gridDim.x = mask_grid(n), gridDim.y = the fields; block (x, y) finds field y's pointers in a table in device-visible memory
+// (pinned host memory: 1024 entries do not fit in kernel arguments) and then does for that field exactly what block x of the
+// single kernel does for it alone -- the same chunks per wave, the same kTurns, the same order of additions, block_sum_count's
+// shuffles and wave order -- so that S and the count of every field have the bits the single kernel gives.  The single
+// kernels above are not touched: these are bodies of their own.
+// k_mask_split_batch: partial[y * 2 * gridDim.x + 2x .. + 1] = the sum and count of block (x, y); k_mask_split_final_batch's
+// block y reduces field y's gridDim.x partials in k_mask_split_final's order into result[2y], result[2y + 1].
+// WIDE: every field's `bits` is 8-byte aligned
+template <typename T, bool WIDE>
+__global__ __launch_bounds__(WR_MASK_THREADS) void k_mask_split_batch(const MaskSplitItem* __restrict__ items, size_t n, double below,
+                                                                        double* __restrict__ partial)
+{
+    const MaskSplitItem it = items[blockIdx.y];
+    const T* __restrict__ x = static_cast<const T*>(it.x);
+    uint8_t* __restrict__ bits = it.bits;
+    double s = 0.0;
+    unsigned long long cnt = 0;
+    const int lane = threadIdx.x & 63;
+    const size_t wave = (size_t)blockIdx.x * WR_MASK_WAVES + (threadIdx.x >> 6), nwaves = (size_t)gridDim.x * WR_MASK_WAVES;
+    const size_t nchunk = (n + 63) >> 6, nbytes = (n + 7) >> 3;
+    constexpr int kTurns = 4;  // (k_mask_split's)
+    for (size_t ch0 = wave; ch0 < nchunk; ch0 += kTurns * nwaves) {
+        T v[kTurns];
+        bool have[kTurns];
+#pragma unroll
+        for (int u = 0; u < kTurns; u++) {
+            const size_t ch = ch0 + u * nwaves, i = (ch << 6) + lane;
+            have[u] = ch < nchunk && i < n;
+            v[u] = have[u] ? x[i] : (T)0;
+        }
+#pragma unroll
+        for (int u = 0; u < kTurns; u++) {
+            const size_t ch = ch0 + u * nwaves;
+            if (ch >= nchunk) break;  // (the whole wave)
+            const double w = (double)v[u];
+            const bool undef = have[u] && (!(fabs(w) <= DBL_MAX) || w < below);
+            if (have[u] && !undef) { s = s + w; cnt++; }
+            const unsigned long long m = __ballot(undef);
+            if (lane == 0) {
+                const size_t b0 = ch << 3;
+                if (WIDE && b0 + 8 <= nbytes) *reinterpret_cast<unsigned long long*>(bits + b0) = m;
+                else
+                    for (int k = 0; k < 8; k++)
+                        if (b0 + k < nbytes) bits[b0 + k] = (uint8_t)(m >> (8 * k));
+            }
+        }
+    }
+    block_sum_count(s, cnt, partial + 2 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x));
+}
+
+__global__ __launch_bounds__(WR_MASK_THREADS) void k_mask_split_final_batch(const double* __restrict__ partial, int np, double* __restrict__ result)
+{
+    const double* __restrict__ p = partial + 2 * (size_t)blockIdx.x * np;
+    double s = 0.0;
+    unsigned long long cnt = 0;
+    for (int i = threadIdx.x; i < np; i += blockDim.x) {
+        s = s + p[2 * i];
+        cnt += reinterpret_cast<const unsigned long long*>(p)[2 * i + 1];
+    }
+    block_sum_count(s, cnt, result + 2 * blockIdx.x);
+}
+
+size_t mask_split_batch_partials(size_t n) { return 2 * (size_t)mask_grid(n); }
+
+void mask_split_batch(const MaskSplitItem* host_items, const MaskSplitItem* d_items, int nfields, bool f32, size_t n, double below, double* partial, double* result,
+                      hipStream_t st)
+{
+    const int g = mask_grid(n);
+    bool wide = true;
+    for (int f = 0; f < nfields; f++) wide = wide && ((uintptr_t)host_items[f].bits & 7) == 0;
+    const dim3 grid((unsigned)g, (unsigned)nfields), block(WR_MASK_THREADS);
+    if (f32) {
+        if (wide) hipLaunchKernelGGL((k_mask_split_batch<float, true>), grid, block, 0, st, d_items, n, below, partial);
+        else hipLaunchKernelGGL((k_mask_split_batch<float, false>), grid, block, 0, st, d_items, n, below, partial);
+    } else {
+        if (wide) hipLaunchKernelGGL((k_mask_split_batch<double, true>), grid, block, 0, st, d_items, n, below, partial);
+        else hipLaunchKernelGGL((k_mask_split_batch<double, false>), grid, block, 0, st, d_items, n, below, partial);
+    }
+    hipLaunchKernelGGL(k_mask_split_final_batch, dim3((unsigned)nfields), block, 0, st, partial, g, result);
+}
+
+// k_mask_fill_batch: k_mask_fill on field blockIdx.y of the table; the value travels as the bits of a T
+template <typename T> __device__ inline T mask_value_of(unsigned long long v);
+template <> __device__ inline double mask_value_of<double>(unsigned long long v) { return __longlong_as_double((long long)v); }
+template <> __device__ inline float mask_value_of<float>(unsigned long long v) { return __uint_as_float((unsigned)v); }
+
+template <typename T>
+__global__ __launch_bounds__(WR_MASK_THREADS) void k_mask_fill_batch(const MaskFillItem* __restrict__ items, size_t n)
+{
+    const MaskFillItem it = items[blockIdx.y];
+    T* __restrict__ x = static_cast<T*>(it.x);
+    const uint8_t* __restrict__ bits = it.bits;
+    const bool wide = (reinterpret_cast<uintptr_t>(bits) & 7) == 0;
+    const T v = mask_value_of<T>(it.value);
+    const int lane = threadIdx.x & 63;
+    const size_t wave = (size_t)blockIdx.x * WR_MASK_WAVES + (threadIdx.x >> 6), nwaves = (size_t)gridDim.x * WR_MASK_WAVES;
+    const size_t nchunk = (n + 63) >> 6, nbytes = (n + 7) >> 3;
+    for (size_t ch = wave; ch < nchunk; ch += nwaves) {
+        const unsigned long long m = mask_word(bits, nbytes, ch, wide);
+        if (!m) continue;  // (the whole wave: m is the same in every lane)
+        const size_t i = (ch << 6) + lane;
+        if (i < n && ((m >> lane) & 1)) x[i] = v;
+    }
+}
+
+unsigned long long mask_fill_value(double v, bool f32)
+{
+    unsigned long long out = 0;
+    if (f32) { const float w = (float)v; memcpy(&out, &w, sizeof w); }
+    else memcpy(&out, &v, sizeof v);
+    return out;
+}
+
+void mask_fill_batch(const MaskFillItem* d_items, int nitems, bool f32, size_t n, hipStream_t st)
+{
+    const dim3 grid((unsigned)mask_grid(n), (unsigned)nitems), block(WR_MASK_THREADS);
+    if (f32) hipLaunchKernelGGL((k_mask_fill_batch<float>), grid, block, 0, st, d_items, n);
+    else hipLaunchKernelGGL((k_mask_fill_batch<double>), grid, block, 0, st, d_items, n);
+}
+
+// k_mask_check_batch: the count-only k_mask_restore on mask blockIdx.y: counters[2y] += its set bits, counters[2y + 1] |= 1 if
+// one lies at or beyond n; one integer atomic per wave and mask.  No field is read.
+__global__ __launch_bounds__(WR_MASK_THREADS) void k_mask_check_batch(const uint8_t* const* __restrict__ masks, size_t n, unsigned long long* __restrict__ counters)
+{
+    const uint8_t* __restrict__ bits = masks[blockIdx.y];
+    const bool wide = (reinterpret_cast<uintptr_t>(bits) & 7) == 0;
+    const int lane = threadIdx.x & 63;
+    const size_t wave = (size_t)blockIdx.x * WR_MASK_WAVES + (threadIdx.x >> 6), nwaves = (size_t)gridDim.x * WR_MASK_WAVES;
+    const size_t nchunk = (n + 63) >> 6, nbytes = (n + 7) >> 3;
+    unsigned long long pop = 0, beyond = 0;  // (of the wave: every lane holds the same values)
+    for (size_t ch = wave; ch < nchunk; ch += nwaves) {
+        const unsigned long long m = mask_word(bits, nbytes, ch, wide);
+        if (!m) continue;
+        const size_t left = n - (ch << 6);
+        const unsigned long long valid = left >= 64 ? ~0ull : (1ull << left) - 1;
+        pop += (unsigned long long)__popcll(m);
+        beyond |= m & ~valid;
+    }
+    if (lane == 0) {
+        if (pop) atomicAdd(&counters[2 * blockIdx.y], pop);
+        if (beyond) atomicOr(&counters[2 * blockIdx.y + 1], 1ull);
+    }
+}
+
+void mask_check_batch(const uint8_t* const* d_masks, int nmasks, size_t n, unsigned long long* counters, hipStream_t st)
+{
+    (void)hipMemsetAsync(counters, 0, 2 * (size_t)nmasks * sizeof(unsigned long long), st);
+    hipLaunchKernelGGL(k_mask_check_batch, dim3((unsigned)mask_grid(n), (unsigned)nmasks), dim3(WR_MASK_THREADS), 0, st, d_masks, n, counters);
+}
+
 }  // namespace wrk
